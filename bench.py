@@ -170,6 +170,28 @@ def _bytes_source(bytes_per_launch: float) -> str:
     return "HBM (working set larger than the 256 MB Infinity Cache)"
 
 
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir: str, result) -> None:
+    """--dump-outputs: what a caller of the timed path received from its last step, the merged top-k, as DIR/<name>.npy:
+    scores [B][k] float32 as returned, rows [B][k] and counts [B] as float64 (exact for ids below 2^53; unused tail entries are
+    (-inf, -1)). Above 64 MB in all, the same seeded sample of queries in every run, named by query_index.npy."""
+    s, r, c = (t.detach().cpu().numpy() for t in result)
+    arrays = {"scores": s.astype(np.float32), "rows": r.astype(np.float64), "counts": c.astype(np.float64)}
+    nq = s.shape[0]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        m = (DUMP_MAX_BYTES - 4096) // (total // nq + 8)      # (4 KB: room for the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(nq, size=m, replace=False))
+        arrays = {n: a[idx] for n, a in arrays.items()}
+        arrays["query_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(out_dir, n + ".npy"), a)
+    log(f"[bench] last timed step's outputs -> {out_dir}: " + ", ".join(f"{n} {list(a.shape)} {a.dtype}" for n, a in arrays.items()))
+
+
 def run_other_config(name: str, device, steps: int, warmup: int) -> dict:
     """One more BASELINE config in the same process, AFTER the timed region of the line's own workload (never inside it): its own
     index, `steps` timed searches with the corpus and the queries resident, the dominant kernel timed by librdx's HIP events on the
@@ -292,6 +314,9 @@ def main():
                          "have cosine ~0.5) and 2000 documents of contiguous near-duplicate chunks, queries near documents (rag_dpo_amd/synth.py)")
     ap.add_argument("--no-others", action="store_true", help="c4, N=1: skip the short legs of configs c1 / c2 / c3 behind the timed region (other_configs)")
     ap.add_argument("--no-check", action="store_true", help="N>1 / --force-dist: skip the cross-rank exactness leg and the step breakdown")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (scores, rows, counts) as DIR/<name>.npy, "
+                         "at most 64 MB in all: two builds run with the same arguments can be compared output for output")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -442,7 +467,7 @@ def main():
             if i + 1 < args.steps:
                 q_next = encode_now()
             h2 = time.perf_counter()
-            searcher.search_end()
+            last = searcher.search_end()
             h3 = time.perf_counter()
             for j, d in enumerate((h1 - h0, h2 - h1, h3 - h2)):
                 host_ms[j] += d * 1e3
@@ -456,7 +481,7 @@ def main():
     else:
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            last = step()
             st = shard.index.last_stats_struct()   # host struct copy, no device work (three field reads: a dict of all 20 fields
             scan_ms += st.ms_scan_main             #  cost 5 us per step, 8 % of a c1 step)
             exact_ms += st.ms_exact
@@ -468,6 +493,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # (before any leg below: a later search of the same shape reuses the searcher's output buffers)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
 
     # ---- N > 1 (and the one-rank RCCL group of --force-dist): the line proves itself ---------------------------------
     # (1) cross-rank exactness, no oracle over 10 M rows needed: for 32 queries every rank ALSO answers from its shard with the
