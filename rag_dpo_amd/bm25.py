@@ -1,0 +1,336 @@
+"""BM25 sparse retrieval — the sparse half of the reference's hybrid retrieval (src/rag/bm25_index.py), scored on the GPU.
+
+Two indexes with the reference's duck types, so that its unmodified `RAGRetriever` (and this repo's DenseRetriever) accept them:
+- SummaryBM25Index: BM25 over the document summaries, the pre-filter that keeps the top documents of a question;
+- ChunkBM25Index: BM25 over every chunk of the collection, the sparse ranking fused with the dense ones.
+
+Scores are rank_bm25 0.2.2's BM25Okapi (k1 = 1.5, b = 0.75, epsilon = 0.25), bit for bit:
+    doc_len[r] = tokens of row r (duplicates included), avgdl = sum(doc_len) / N, nd[t] = rows containing t
+    idf[t] = log(N - nd + 0.5) - log(nd + 0.5), summed in the vocabulary's first-occurrence order; every idf < 0 becomes
+             epsilon * (idf_sum / |V|)
+    score[r] = 0.0, then for each query token q, in query order, duplicates kept:
+             score[r] += idf(q) * ((tf * 2.5) / (tf + k1 * ((1 - b) + (b * doc_len[r]) / avgdl)))      (float64)
+A row without q adds +-0.0, so out-of-vocabulary tokens are dropped here; duplicates are kept ((s + w) + w is not s + 2w).
+The per-row denominator and the idf are computed on the host with exactly that operation order; the device adds the
+postings (include/rdx.h rdx_bm25_*, csrc/bm25_kernel.hpp). Search result: rows with score > 0 (and, for chunks, whose
+`document_path` is in `doc_filter` when it is not None: an empty set returns nothing), score descending, ties by
+ascending row, cut to top_k (bm25_index.py:146-168, :265-292).
+
+The index is immutable, as in the reference: to refresh, build again. Tokenisation is Python, as in the reference;
+the postings are built with numpy.
+"""
+from __future__ import annotations
+
+import ctypes
+import functools
+import json
+import logging
+import math
+import operator
+import re
+from dataclasses import dataclass
+from itertools import chain
+from pathlib import Path
+from typing import Callable, Dict, List, Optional, Sequence, Set
+
+import numpy as np
+
+logger = logging.getLogger(__name__)
+
+K1, B, EPSILON = 1.5, 0.75, 0.25
+MAX_K = 4096          # include/rdx.h rdx_bm25_search: results per query
+MAX_TERMS = 4096      # query terms per query (after dropping out-of-vocabulary ones)
+MAX_TF = 65535        # the device stores tf as uint16
+
+# French stop words of the reference's tokenizer (bm25_index.py FRENCH_STOPWORDS): a behavioural contract, pinned entry by
+# entry by tests/golden/bm25_golden.json
+STOPWORDS = frozenset("""
+    à après ainsi alors assez au aussi autre autres aux avant avec avoir ayant bien c car ce ces cet cette chaque chez comme
+    d dans de déjà depuis des donc dont du elle elles en encore entre est et été être fait faire il ils j jamais je l la le
+    les leur leurs lors m ma mais mes même mon n ne ni notre nous on ou où par pas pendant peu peut plus pour quel quelle
+    quelles quels que qui quoi rien s sa sans se ses si son sont sous sur t ta tes ton tous tout toute toutes très trop tu
+    un une vers votre vous y
+""".split())
+
+_WORD = "[0-9a-zàâäçéèêëîïôùûüÿæœ]+"
+_TOKEN = re.compile(f"{_WORD}(?:-{_WORD})*")
+
+
+def tokenize_french(text: str) -> List[str]:
+    """lowercase; words of letters (accented included) and digits, hyphen-joined; no stop words, no 1-character tokens"""
+    return [t for t in _TOKEN.findall(text.lower()) if len(t) > 1 and t not in STOPWORDS]
+
+
+@dataclass
+class BM25Result:
+    """reference bm25_index.py BM25Result: doc_key = document path (summaries) or chunk id (chunks)"""
+    doc_key: str
+    score: float
+    metadata: Dict
+
+
+@dataclass
+class Bm25Arrays:
+    """what the engine is built from (include/rdx.h rdx_bm25_create)"""
+    n_rows: int
+    idf: np.ndarray        # f64 [V]
+    denom: np.ndarray      # f64 [N]  k1 * ((1 - b) + (b * doc_len) / avgdl)
+    post_off: np.ndarray   # int64 [V+1]
+    post_row: np.ndarray   # int32 [nnz], ascending inside a term
+    post_tf: np.ndarray    # uint16 [nnz]
+    row_group: Optional[np.ndarray] = None   # int32 [N] interned document_path, or None
+    n_groups: int = 0
+
+
+class Bm25Model:
+    """the host half of an index: vocabulary, rank_bm25's statistics and the device arrays"""
+
+    def __init__(self, corpus_tokens: Sequence[Sequence[str]]):
+        n = len(corpus_tokens)
+        doc_len = np.fromiter(map(len, corpus_tokens), dtype=np.int64, count=n)
+        flat = list(chain.from_iterable(corpus_tokens))
+        vocab = dict.fromkeys(flat)                                   # first-occurrence order = rank_bm25's nd order
+        self.term_id: Dict[str, int] = dict(zip(vocab, range(len(vocab))))
+        self.n_rows, self.n_terms = n, len(self.term_id)
+        ids = np.fromiter(map(self.term_id.__getitem__, flat), dtype=np.int64, count=len(flat))
+        rows = np.repeat(np.arange(n, dtype=np.int64), doc_len)
+        key, tf = np.unique(ids * max(n, 1) + rows, return_counts=True)   # sorted by (term, row)
+        term = key // max(n, 1)
+        if tf.size and int(tf.max()) > MAX_TF:
+            raise ValueError(f"a token occurs {int(tf.max())} times in one text: the index stores tf in 16 bits (<= {MAX_TF})")
+        self.post_row = (key % max(n, 1)).astype(np.int32)
+        self.post_tf = tf.astype(np.uint16)
+        self.post_off = np.zeros(self.n_terms + 1, dtype=np.int64)
+        np.cumsum(np.bincount(term, minlength=self.n_terms), out=self.post_off[1:])
+        self.doc_len = doc_len
+        self.avgdl = int(doc_len.sum()) / n if n else 0.0
+        self.idf, self.average_idf = idf_of(n, np.diff(self.post_off))
+        # rank_bm25: self.k1 * (1 - self.b + self.b * doc_len / self.avgdl), doc_len an int64 array
+        self.denom = K1 * (1 - B + B * doc_len / self.avgdl) if n else np.zeros(0)
+
+    def arrays(self, row_group=None, n_groups=0) -> Bm25Arrays:
+        return Bm25Arrays(self.n_rows, self.idf, np.ascontiguousarray(self.denom, dtype=np.float64), self.post_off, self.post_row,
+                          self.post_tf, row_group, n_groups)
+
+    def query_ids(self, tokens: Sequence[str]) -> List[int]:
+        """query order, duplicates kept, out-of-vocabulary tokens dropped (they add +-0.0 to every row)"""
+        get = self.term_id.get
+        return [i for i in map(get, tokens) if i is not None]
+
+
+def idf_of(n_rows: int, nd: np.ndarray):
+    """rank_bm25 BM25Okapi._calc_idf: math.log per term, a plain left-to-right float sum (not sum(): Python >= 3.12 compensates)"""
+    idf = [math.log(n_rows - f + 0.5) - math.log(f + 0.5) for f in nd.tolist()]
+    if not idf:
+        return np.zeros(0), 0.0
+    average_idf = functools.reduce(operator.add, idf, 0) / len(idf)
+    out = np.array(idf, dtype=np.float64)
+    out[out < 0] = EPSILON * average_idf
+    return out, average_idf
+
+
+class HipBm25:
+    """one BM25 index in one MI355X's HBM, driven through include/rdx.h. No arithmetic happens in this class."""
+
+    def __init__(self, arrays: Bm25Arrays, device: int = 0):
+        from . import _lib as L
+        self._L = L
+        self._lib = L.load(require_gpu=True)
+        self.device = int(device)
+        a = arrays
+        self.n_groups = int(a.n_groups)
+        self._keep = [np.ascontiguousarray(a.post_off, np.int64), np.ascontiguousarray(a.post_row, np.int32),
+                      np.ascontiguousarray(a.post_tf, np.uint16), np.ascontiguousarray(a.idf, np.float64),
+                      np.ascontiguousarray(a.denom, np.float64)]
+        grp = np.ascontiguousarray(a.row_group, np.int32) if a.row_group is not None else None
+        p = [ctypes.c_void_p(x.ctypes.data) for x in self._keep]
+        self._h = ctypes.c_void_p()
+        L.check(self._lib.rdx_bm25_create(self.device, int(a.n_rows), int(len(a.idf)), *p,
+                                          ctypes.c_void_p(grp.ctypes.data) if grp is not None else None, int(a.n_groups),
+                                          ctypes.byref(self._h)))
+        self._keep = None   # copied to the device
+
+    def search(self, term_offsets: np.ndarray, term_ids: np.ndarray, k: int, allow_bits: Optional[np.ndarray] = None):
+        """-> scores f64 [nq, k], rows int64 [nq, k], counts int32 [nq]; on torch's current stream of the index's device"""
+        import torch
+        L = self._L
+        off = np.ascontiguousarray(term_offsets, np.int64)
+        ids = np.ascontiguousarray(term_ids, np.int32)
+        nq = off.shape[0] - 1
+        sc = np.empty((nq, k), np.float64)
+        ro = np.empty((nq, k), np.int64)
+        cn = np.empty(nq, np.int32)
+        ab = np.ascontiguousarray(allow_bits, np.uint32) if allow_bits is not None else None
+        if ab is not None and ab.size < (self.n_groups + 31) // 32:
+            raise ValueError("allow_bits must hold (n_groups + 31) // 32 words")
+        stream = torch._C._cuda_getCurrentRawStream(self.device)
+        L.check(self._lib.rdx_bm25_search(self._h, ctypes.c_void_p(off.ctypes.data), ctypes.c_void_p(ids.ctypes.data), nq, int(k),
+                                          ctypes.c_void_p(ab.ctypes.data) if ab is not None else None,
+                                          ctypes.c_void_p(sc.ctypes.data), ctypes.c_void_p(ro.ctypes.data),
+                                          ctypes.c_void_p(cn.ctypes.data), L.RDX_HOST, ctypes.c_void_p(stream)))
+        return sc, ro, cn
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.rdx_bm25_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _default_engine_factory(arrays: Bm25Arrays, device: int):
+    return HipBm25(arrays, device)
+
+
+class _Bm25Base:
+    def __init__(self, engine_factory: Optional[Callable[[Bm25Arrays, int], object]] = None, device: int = 0):
+        self._factory = engine_factory or _default_engine_factory
+        self.device = device
+        self.model: Optional[Bm25Model] = None
+        self.engine = None
+        self.corpus_tokens: List[List[str]] = []
+        self._is_built = False
+
+    @property
+    def is_built(self) -> bool:
+        return self._is_built
+
+    def _install(self, row_group=None, n_groups=0):
+        if self.engine is not None and hasattr(self.engine, "close"):
+            self.engine.close()
+        self.model = Bm25Model(self.corpus_tokens)
+        self.engine = self._factory(self.model.arrays(row_group, n_groups), self.device) if self.model.n_rows else None
+        self._is_built = True
+
+    def _search_rows(self, queries: Sequence[str], top_k: int, allow_bits=None):
+        """-> per query a list of (row, score), the reference's order and cut"""
+        if not self._is_built:
+            raise RuntimeError("the BM25 index is not built")
+        out: List[list] = [[] for _ in queries]
+        if top_k <= 0 or self.engine is None:
+            return out
+        k = min(int(top_k), self.model.n_rows)
+        terms = [self.model.query_ids(tokenize_french(q)) for q in queries]
+        live = [i for i, t in enumerate(terms) if t]           # a query without known tokens scores 0 everywhere: nothing
+        if not live:
+            return out
+        for i in live:
+            if len(terms[i]) > MAX_TERMS:
+                raise ValueError(f"a BM25 query has {len(terms[i])} known tokens; at most {MAX_TERMS} are supported")
+        off = np.zeros(len(live) + 1, np.int64)
+        np.cumsum([len(terms[i]) for i in live], out=off[1:])
+        ids = np.fromiter(chain.from_iterable(terms[i] for i in live), dtype=np.int32, count=int(off[-1]))
+        sc, ro, cn = self.engine.search(off, ids, k, allow_bits)
+        for j, i in enumerate(live):
+            c = int(cn[j])
+            out[i] = list(zip(ro[j, :c].tolist(), sc[j, :c].tolist()))
+        return out
+
+
+class SummaryBM25Index(_Bm25Base):
+    """reference bm25_index.py SummaryBM25Index: BM25 over the document summaries (pre-filter of the documents)"""
+
+    def __init__(self, summaries_path: Optional[Path] = None, engine_factory=None, device: int = 0):
+        super().__init__(engine_factory, device)
+        self.summaries_path = Path(summaries_path) if summaries_path else Path("data/keep/cnil/document_summaries.json")
+        self.doc_keys: List[str] = []
+        self.doc_metadata: List[Dict] = []
+
+    def build(self, summaries_path: Optional[str] = None) -> None:
+        if summaries_path:
+            self.summaries_path = Path(summaries_path)
+        if not self.summaries_path.exists():
+            raise FileNotFoundError(f"summaries file not found: {self.summaries_path}")
+        with open(self.summaries_path, "r", encoding="utf-8") as f:
+            summaries = json.load(f)
+        self.doc_keys, self.doc_metadata, self.corpus_tokens = [], [], []
+        skipped = 0
+        for doc_path, entry in summaries.items():
+            summary = entry.get("summary", "")
+            if not summary or summary.startswith("ERREUR"):
+                skipped += 1
+                continue
+            title, url = entry.get("document_title", ""), entry.get("source_url", "")
+            tokens = tokenize_french(f"{title} {summary} {url}")
+            if not tokens:
+                skipped += 1
+                continue
+            self.doc_keys.append(doc_path)
+            self.doc_metadata.append({"document_path": doc_path, "source_url": url, "document_title": title, "summary": summary})
+            self.corpus_tokens.append(tokens)
+        self._install()
+        logger.info("BM25 summaries index: %d documents (%d skipped)", len(self.doc_keys), skipped)
+
+    def search(self, query: str, top_k: int = 20) -> List[BM25Result]:
+        (hits,) = self._search_rows([query], top_k)
+        return [BM25Result(doc_key=self.doc_keys[r], score=s, metadata=self.doc_metadata[r]) for r, s in hits]
+
+    def get_relevant_doc_paths(self, query: str, top_k: int = 20) -> Set[str]:
+        return {r.doc_key for r in self.search(query, top_k=top_k)}
+
+
+class ChunkBM25Index(_Bm25Base):
+    """reference bm25_index.py ChunkBM25Index: BM25 over the chunks of a collection (the sparse ranking of hybrid retrieval)"""
+
+    def __init__(self, engine_factory=None, device: int = 0):
+        super().__init__(engine_factory, device)
+        self.chunk_ids: List[str] = []
+        self.chunk_texts: List[str] = []
+        self.chunk_metadatas: List[Dict] = []
+        self._group_of: Dict[str, int] = {}
+
+    def build_from_collection(self, collection, batch_size: int = 5000) -> None:
+        total = collection.count()
+        self.chunk_ids, self.chunk_texts, self.chunk_metadatas, self.corpus_tokens = [], [], [], []
+        offset = 0
+        while offset < total:
+            batch = collection.get(limit=batch_size, offset=offset, include=["documents", "metadatas"])
+            for chunk_id, text, metadata in zip(batch["ids"], batch["documents"], batch["metadatas"]):
+                if not text or not text.strip():
+                    continue
+                tokens = tokenize_french(text)
+                if not tokens:
+                    continue
+                self.chunk_ids.append(chunk_id)
+                self.chunk_texts.append(text)
+                self.chunk_metadatas.append(metadata)
+                self.corpus_tokens.append(tokens)
+            offset += batch_size
+        paths = [(m or {}).get("document_path", "") for m in self.chunk_metadatas]
+        self._group_of = dict(zip(dict.fromkeys(paths), range(len(paths))))
+        groups = np.fromiter(map(self._group_of.__getitem__, paths), dtype=np.int32, count=len(paths))
+        self._install(groups, len(self._group_of))
+        logger.info("BM25 chunk index: %d chunks", len(self.chunk_ids))
+
+    def _allow_bits(self, doc_filter: Set[str]):
+        """-> bitset over document groups, or None when no indexed document is in the filter (nothing can pass)"""
+        bits = np.zeros((len(self._group_of) + 31) // 32, np.uint32)
+        hit = False
+        for p in doc_filter:
+            g = self._group_of.get(p)
+            if g is not None:
+                bits[g >> 5] |= np.uint32(1 << (g & 31))
+                hit = True
+        return bits if hit else None
+
+    def search_batch(self, queries: Sequence[str], top_k: int = 30, doc_filter: Optional[Set[str]] = None) -> List[List[BM25Result]]:
+        """search() of every query, in one device call"""
+        if not self._is_built:
+            raise RuntimeError("the BM25 index is not built")
+        bits = None
+        if doc_filter is not None:
+            bits = self._allow_bits(doc_filter)
+            if bits is None:
+                return [[] for _ in queries]
+        out = []
+        for hits in self._search_rows(queries, top_k, bits):
+            out.append([BM25Result(doc_key=self.chunk_ids[r], score=s,
+                                   metadata={**(self.chunk_metadatas[r] or {}), "text": self.chunk_texts[r]}) for r, s in hits])
+        return out
+
+    def search(self, query: str, top_k: int = 30, doc_filter: Optional[Set[str]] = None) -> List[BM25Result]:
+        return self.search_batch([query], top_k, doc_filter)[0]

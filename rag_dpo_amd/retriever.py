@@ -6,8 +6,12 @@ document de-duplication stay identical to the reference's.
 
 Pinned by tests/golden/retriever_golden.json, captured by driving the IMPORTED reference retriever
 (tests/golden/make_retriever_golden.py) with the same collection and embedder.
-BM25 / summary pre-filter / LLM query expansion are out of scope: the expansion is an injected
-callable, sparse rankings can be passed in as extra rankings.
+Hybrid retrieval: given the BM25 indexes of rag_dpo_amd/bm25.py (summary pre-filter and chunk index), both methods
+follow the reference per method (retriever.py:187-285, :355-452): the summary pre-filter of the main query, the dense
+list filtered by it and topped up to 5 (retrieve) / 10 (retrieve_candidates), the BM25 rankings interleaved with the
+dense ones in the reference's order (RRF sums in ranking order), BM25-only chunks at distance 1.0. retrieve searches BM25
+for the main query only; retrieve_candidates for every sub-query, all in ONE batched device call.
+Pinned by tests/golden/bm25_golden.json. LLM query expansion stays out of scope: it is an injected callable.
 """
 from __future__ import annotations
 
@@ -86,7 +90,8 @@ def parse_query_results(results: Dict, b: int = 0) -> List[RetrievedChunk]:
 class DenseRetriever:
     def __init__(self, collection, embedding_provider, query_expander: Optional[Callable[[str], List[str]]] = None,
                  query_preprocessor: Optional[Callable[[str], str]] = None, n_documents: int = 5,
-                 n_chunks_per_doc: int = 3, fetch_multiplier: int = 10):
+                 n_chunks_per_doc: int = 3, fetch_multiplier: int = 10, summary_bm25_index=None, chunk_bm25_index=None,
+                 summary_prefilter_k: int = 20, enable_hybrid: bool = True, enable_summary_prefilter: bool = True):
         self.collection = collection
         self.embedding_provider = embedding_provider
         self.query_expander = query_expander            # reference: QueryExpander.expand (LLM, out of scope)
@@ -94,6 +99,11 @@ class DenseRetriever:
         self.n_documents = n_documents
         self.n_chunks_per_doc = n_chunks_per_doc
         self.fetch_multiplier = fetch_multiplier
+        self.summary_bm25 = summary_bm25_index          # reference: SummaryBM25Index (pre-filter), rag_dpo_amd.bm25
+        self.chunk_bm25 = chunk_bm25_index              # reference: ChunkBM25Index (sparse ranking), rag_dpo_amd.bm25
+        self.summary_prefilter_k = summary_prefilter_k
+        self.enable_hybrid = enable_hybrid
+        self.enable_summary_prefilter = enable_summary_prefilter
 
     # one batched device round trip for all the queries of a question
     def _dense(self, all_queries: List[str], n_fetch: int, where_filter):
@@ -120,15 +130,36 @@ class DenseRetriever:
         return out
 
     def _queries(self, query: str) -> List[str]:
-        expanded = self.query_preprocessor(query) if self.query_preprocessor else query
-        return list(self.query_expander(expanded)) if self.query_expander is not None else [expanded]
+        return self._expand(query)[1]
 
-    def _fuse(self, per_query: List[List[RetrievedChunk]], extra_rankings=(), extra_weights=()):
+    def _expand(self, query: str):
+        """-> (the preprocessed main query, all sub-queries)"""
+        expanded = self.query_preprocessor(query) if self.query_preprocessor else query
+        return expanded, (list(self.query_expander(expanded)) if self.query_expander is not None else [expanded])
+
+    def _doc_filter(self, expanded: str):
+        """the summary pre-filter of the main query (reference :187-196, :355-363), or None"""
+        if self.enable_summary_prefilter and self.summary_bm25 is not None and self.summary_bm25._is_built:
+            return self.summary_bm25.get_relevant_doc_paths(expanded, top_k=self.summary_prefilter_k)
+        return None
+
+    def _hybrid(self) -> bool:
+        return self.enable_hybrid and self.chunk_bm25 is not None and self.chunk_bm25.is_built
+
+    def _fuse(self, per_query: List[List[RetrievedChunk]], extra_rankings=(), extra_weights=(), bm25=None, doc_filter=None,
+              min_semantic: int = 5, bm25_keep_max: bool = False):
+        """bm25: per sub-query None or (its BM25 results, the ranking's weight); its ranking follows that sub-query's dense one"""
         all_rankings, weights = [], []
         chunk_map: Dict[str, RetrievedChunk] = {}
         for q_idx, chunks in enumerate(per_query):
-            if chunks is None:                                     # skipped sub-query: no ranking, no weight
+            if chunks is None:                                     # skipped sub-query: no ranking, no weight, no BM25
                 continue
+            if doc_filter:                                         # reference :226-232, :391-397 (an empty filter filters nothing)
+                filtered = [c for c in chunks if c.document_path in doc_filter]
+                if len(filtered) < min_semantic:
+                    kept = {id(c) for c in filtered}
+                    filtered.extend([c for c in chunks if id(c) not in kept][:min_semantic - len(filtered)])
+                chunks = filtered
             for c in chunks:
                 c.semantic_score = c.similarity_score
             all_rankings.append([c.chunk_id for c in chunks])
@@ -142,6 +173,20 @@ class DenseRetriever:
                         old.distance = c.distance
                     if c.semantic_score > old.semantic_score:
                         old.semantic_score = c.semantic_score
+            if bm25 is not None and bm25[q_idx] is not None:       # reference :258-285, :417-452
+                results, weight = bm25[q_idx]
+                all_rankings.append([r.doc_key for r in results])
+                weights.append(weight)
+                for r in results:
+                    c = chunk_map.get(r.doc_key)
+                    if c is None:
+                        meta = dict(r.metadata)
+                        text = meta.pop("text", "")
+                        c = chunk_map[r.doc_key] = RetrievedChunk(
+                            chunk_id=r.doc_key, text=text, document_path=meta.get("document_path", ""),
+                            chunk_nature=meta.get("chunk_nature", "UNKNOWN"), chunk_index=meta.get("chunk_index", 0),
+                            confidence=meta.get("confidence", "unknown"), distance=1.0, metadata=meta)
+                    c.bm25_score = max(c.bm25_score, r.score) if bm25_keep_max else r.score
         all_rankings += [list(r) for r in extra_rankings]
         weights += list(extra_weights)
         if len(all_rankings) > 1:                                  # reference :293-300, :455-462
@@ -156,18 +201,34 @@ class DenseRetriever:
         return out
 
     def retrieve_candidates(self, query: str, n_candidates: int = 100, where_filter=None) -> List[RetrievedChunk]:
-        """reference src/rag/retriever.py:312-470 without BM25 / summary pre-filter"""
+        """reference src/rag/retriever.py:312-470: BM25 for every sub-query, weights 1.5 x / 0.75 x, bm25_score keeps the max"""
         n_fetch = max(n_candidates, 50)
-        per_query = self._dense(self._queries(query), n_fetch, where_filter)
-        return self._fuse(per_query)[:n_candidates]
+        expanded, queries = self._expand(query)
+        doc_filter = self._doc_filter(expanded)
+        per_query = self._dense(queries, n_fetch, where_filter)
+        bm25 = None
+        if self._hybrid():
+            live = [i for i, c in enumerate(per_query) if c is not None]
+            found = self.chunk_bm25.search_batch([queries[i] for i in live], top_k=n_fetch, doc_filter=doc_filter) if live else []
+            bm25 = [None] * len(queries)
+            for i, res in zip(live, found):
+                bm25[i] = (res, 2.0 * 1.5 if i == 0 else 1.0 * 0.75)
+        return self._fuse(per_query, bm25=bm25, doc_filter=doc_filter, min_semantic=10, bm25_keep_max=True)[:n_candidates]
 
     def retrieve(self, query: str, where_filter=None, n_documents: Optional[int] = None,
                  n_chunks_per_doc: Optional[int] = None) -> List[RetrievedDocument]:
-        """reference src/rag/retriever.py:156-310 without BM25 / summary pre-filter"""
+        """reference src/rag/retriever.py:156-310: BM25 for the main query only, weight 2.0"""
         n_docs = n_documents or self.n_documents
         n_chunks = n_chunks_per_doc or self.n_chunks_per_doc
-        per_query = self._dense(self._queries(query), n_docs * self.fetch_multiplier, where_filter)
-        return deduplicate_by_document(self._fuse(per_query), n_docs, n_chunks)
+        n_fetch = n_docs * self.fetch_multiplier
+        expanded, queries = self._expand(query)
+        doc_filter = self._doc_filter(expanded)
+        per_query = self._dense(queries, n_fetch, where_filter)
+        bm25 = None
+        if self._hybrid() and per_query and per_query[0] is not None:
+            bm25 = [None] * len(queries)
+            bm25[0] = (self.chunk_bm25.search(queries[0], top_k=n_fetch, doc_filter=doc_filter), 2.0)
+        return deduplicate_by_document(self._fuse(per_query, bm25=bm25, doc_filter=doc_filter, min_semantic=5), n_docs, n_chunks)
 
 
 def deduplicate_by_document(chunks: List[RetrievedChunk], n_documents: int, n_chunks_per_doc: int) -> List[RetrievedDocument]:
