@@ -331,6 +331,28 @@ class _PackedEncoder:
         q0 = (np.arange(int(nb.sum()), dtype=np.int64) - np.repeat(np.cumsum(nb) - nb, nb)) * 64
         return torch.from_numpy(np.stack([first[tix], lens[tix], q0, np.zeros_like(q0)], axis=1).astype(np.int32))
 
+    @staticmethod
+    def _window_promise(max_len: int) -> int:
+        """the longest text rounded up to 16 / 32 / 64: a canonical shape's promise to the attention kernel (its LDS window)"""
+        return 16 if max_len <= 16 else (32 if max_len <= 32 else 64)
+
+    @staticmethod
+    def _canonical_texts(first: np.ndarray, lens: np.ndarray, Tp: int):
+        """tok_first / tok_len (int32 [Tp]) of a canonical shape: the real texts' tokens, then one-token dummy texts up to Tp"""
+        T = int(lens.sum())
+        tf, tl = np.empty(Tp, dtype=np.int32), np.empty(Tp, dtype=np.int32)
+        tf[:T], tf[T:] = np.repeat(first, lens), np.arange(T, Tp)
+        tl[:T], tl[T:] = np.repeat(lens, lens), 1
+        return tf, tl
+
+    @classmethod
+    def _canonical_query_blocks(cls, first: np.ndarray, lens: np.ndarray, Tp: int, units: int) -> torch.Tensor:
+        """the MFMA kernel's work units of a canonical shape: the real texts' and the dummies', then repeats of the last unit up to
+        `units` (the same rows written twice with the same values)"""
+        T = int(lens.sum())
+        qb = cls._query_blocks(np.concatenate([first, np.arange(T, Tp, dtype=np.int64)]), np.concatenate([lens, np.ones(Tp - T, dtype=np.int64)]))
+        return torch.cat([qb, qb[-1:].expand(units - qb.shape[0], 4)]).contiguous()
+
     @torch.no_grad()
     def cls(self, ids: torch.Tensor, lens: np.ndarray, to_dev) -> torch.Tensor:
         """ids: [B][S] int64 on the host, right-padded; lens[b] = tokens of text b (>= 1). -> fp32 [B][hidden] CLS rows on the device.
@@ -359,7 +381,7 @@ class _PackedEncoder:
                 #  are 8, 16, 24 and 32 tokens — a typical 20-token question pays for 24 rows, not 32)
                 g = 8 if (self.small_stage and T <= self.STAGE_TOKENS) else self.SMALL_TOKEN_GRANULE
                 Tp = -(-T // g) * g                               # one-token dummy texts behind the real ones
-                lb = 16 if max_len <= 16 else (32 if max_len <= 32 else 64)
+                lb = self._window_promise(max_len)
                 # the five index arrays of the canonical shape in ONE buffer: one pinned copy per question instead of five
                 # (each small copy is ~15 us of stream time: 0.07 of a 0.95 ms embed_query)
                 o1, o2, o3, o4, nb_ = 8 * Tp, 16 * Tp, 16 * Tp + 8 * self.SMALL_TEXTS, 20 * Tp + 8 * self.SMALL_TEXTS, 24 * Tp + 8 * self.SMALL_TEXTS
@@ -371,10 +393,7 @@ class _PackedEncoder:
                 v64[Tp + T:2 * Tp] = self.pad + 1
                 v64[2 * Tp:2 * Tp + B] = first
                 v64[2 * Tp + B:] = 0
-                v32[:T] = np.repeat(first, lens)
-                v32[T:Tp] = np.arange(T, Tp)
-                v32[Tp:Tp + T] = np.repeat(lens, lens)
-                v32[Tp + T:] = 1
+                v32[:Tp], v32[Tp:] = self._canonical_texts(first, lens, Tp)
 
                 def unpack(d):
                     return (d[:o1].view(torch.int64), d[o1:o2].view(torch.int64), d[o2:o3].view(torch.int64), d[o3:o4].view(torch.int32),
@@ -392,18 +411,14 @@ class _PackedEncoder:
                 g = self.LARGE_TOKEN_GRANULE
                 Tp = -(-T // g) * g
                 extra = Tp - T
-                lb = 16 if max_len <= 16 else (32 if max_len <= 32 else 64)
+                lb = self._window_promise(max_len)
+                tf, tl = self._canonical_texts(first, lens, Tp)
                 padded = {"pk_tok": torch.from_numpy(np.concatenate([host["pk_tok"].numpy(), np.full(extra, self.pad, dtype=np.int64)])),
                           "pk_pos": torch.from_numpy(np.concatenate([host["pk_pos"].numpy(), np.full(extra, self.pad + 1, dtype=np.int64)])),
-                          "pk_first": host["pk_first"],
-                          "pk_tfirst": torch.from_numpy(np.concatenate([host["pk_tfirst"].numpy(), np.arange(T, Tp, dtype=np.int32)])),
-                          "pk_tlen": torch.from_numpy(np.concatenate([host["pk_tlen"].numpy(), np.ones(extra, dtype=np.int32)]))}
+                          "pk_first": host["pk_first"], "pk_tfirst": torch.from_numpy(tf), "pk_tlen": torch.from_numpy(tl)}
                 if "pk_qb" in host:
-                    # (B + extra work units; `extra` moves with T inside one canonical shape, so the list is filled up to B + g units
-                    #  with repeats of the last one: the same rows written twice with the same values)
-                    qb = self._query_blocks(np.concatenate([first, np.arange(T, Tp, dtype=np.int64)]),
-                                            np.concatenate([lens, np.ones(extra, dtype=np.int64)]))
-                    padded["pk_qb"] = torch.cat([qb, qb[-1:].expand(B + g - qb.shape[0], 4)]).contiguous()
+                    # (B + extra work units; `extra` moves with T inside one canonical shape, so the list is filled up to B + g units)
+                    padded["pk_qb"] = self._canonical_query_blocks(first, lens, Tp, B + g)
                 big = [k_ for k_ in self._graph if k_[0] == "large"]
                 key = ("large", B, Tp, lb)
                 if key not in self._graph and len(big) >= self.MAX_LARGE_GRAPHS:
