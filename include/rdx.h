@@ -124,9 +124,10 @@ int rdx_index_set_row_ids(rdx_index* h, int64_t first_row, const int64_t* ids, i
  * main scan with the split-K kernel too (balanced in 32-row units instead of whole 256-row tiles);
  * "half_boot" 0/1 (default 1): searches of 129..256 queries take their threshold sample as two 128-query tiles per sampled corpus
  * tile (every CU busy, less data per k-step) instead of one 256-query tile on half the CUs;
- * "spread_boot" 0/1 (default 1): searches of more than 64 queries take their threshold sample as every div-th 32-row block of the corpus
- * instead of every div-th 256-row tile (the same number of rows, eight times finer: runs of similar rows stored together — a
- * document's chunks — are met by the sample instead of falling between two sampled tiles; speed only);
+ * "spread_boot" 0/1 (default 1): every threshold sample not taken by the split-K bootstrap (see "split_boot"), whatever the batch
+ * size, is every div-th 32-row block of the corpus instead of every div-th 256-row tile (the same number of rows, eight times finer:
+ * runs of similar rows stored together — a document's chunks — are met by the sample instead of falling between two sampled
+ * tiles; such a sample is not thinned to whole rounds of the streams as a tile sample is; speed only);
  * "fuse_finish" 0/1 (default 1): the end-of-search work (counters and small results to pinned host memory) runs in the last
  * block of the search's last kernel instead of a launch of its own (both: speed only);
  * "retry" 0/1 (default 1): queries whose candidate

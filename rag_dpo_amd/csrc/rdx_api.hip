@@ -98,27 +98,53 @@ struct HostOut {
     bool stale;
 };
 
+// What a search of (rows, nq, k, options) launches: every choice, made by plan_search before anything is enqueued
+struct SearchPlan {
+    int64_t nq = 0;
+    int k = 0, depth = 0, nq_pad = 0;  // depth 0 = the caller's batch; 1 = the second-chance batch of overflowed queries
+    int prof = 0;                      // option "profile" (depth 0 only)
+    bool exact_only = false;           // the exact full scan alone; the fields down to `stamps` are the MFMA path's
+    int bn = 0, nqt = 0, grid = 0, G = 0, n_streams = 0, n_sets = 0;   // G workgroups per XCD and query tile, 8 G streams
+    bool res = false;                  // the 64-query tile stays resident in LDS
+    int64_t n_tiles = 0, n_blocks32 = 0;
+    bool use_boot = false;             // bootstrap: k_boot over boot_units 32-row blocks, or k_scan<EPI_SETMAX> (the rest)
+    int64_t boot_units = 0;
+    int boot_sets = 0, bn_b = 0, nqt_b = 0, n_sets_b = 0, div = 1, n_sets_used = 0;
+    int64_t boot_tiles = 0, boot_wave_off = 0;   // the tile bootstrap's ScanParams n_tiles, wave_off, row_off, span
+    int boot_row_off = 0, boot_span = 0;
+    bool use_small = false;            // k_scan_small as the main scan
+    int64_t sample_rows = 0;
+    double expected_per_query = 0.0;   // candidates per query a random corpus would emit with this sample
+    uint32_t capw = 0, list_cap = 0;
+    int k_sel = 0;                     // rank of the sampled score the threshold is taken from (< k: speculative)
+    float slack = 0.f;
+    bool balance = false;              // XCD-weighted split of the main scan's tiles
+    int bulk_it = 0, xlo[9] = {};
+    bool stamps = false;               // the main scan's workgroups stamp their times
+    bool ride = false, big_copy = false;   // host results: with k_finish into pinned staging, or D2H copies
+    size_t b_s = 0, b_r = 0, b_c = 0;  // result bytes: scores, rows, counts
+};
+
+// the caller's buffers of one search chunk (device addresses)
+struct SearchIO {
+    const float* queries;
+    const uint32_t* allow;
+    float* score;
+    int64_t* row;
+    int32_t* count;
+    int32_t* flags;   // rdx_search_async(out_flags): the "incomplete" word of the packed partial, or NULL
+};
+
 // A search whose kernels (up to k_finish) are enqueued and whose host half — waiting for the mailbox, copying small
 // results out, re-weighting the XCD shares, the fallback passes for overflowed queries, the statistics — has not run yet.
 // rdx_search runs that half at once; rdx_search_async leaves it to rdx_search_wait, so that the caller can enqueue what
 // consumes the results (the RCCL all-gather and the merge) while the scan is still running.
 struct PendingSearch {
     bool active = false;
-    const float* d_queries = nullptr;
-    int64_t nq = 0;
-    int k = 0;
-    const uint32_t* d_allow = nullptr;
-    float* d_score = nullptr;
-    int64_t* d_row = nullptr;
-    int32_t* d_count = nullptr;
-    int32_t* d_flags = nullptr;    // rdx_search_async(out_flags): the "incomplete" word of the packed partial, or NULL
+    SearchPlan plan;
+    SearchIO io = {};
     hipStream_t st = nullptr;
     unsigned long long seq = 0;
-    bool exact_only = false, balance = false, ride = false, big_host_copy = false;
-    int grid = 0, G = 0, nqt = 0, depth = 0;
-    int64_t sample_rows = 0;
-    double expected_per_query = 0.0;   // candidates per query a random corpus would have emitted (0: exact path)
-    size_t b_s = 0, b_r = 0, b_c = 0;
     rdx_search_stats stats = {};   // rdx_search_async only: the statistics of the deferred search
 };
 
@@ -147,10 +173,9 @@ struct rdx_index {
     int fuse_finish = 1;     // option: the end-of-search work runs in the last block of the search's last kernel (0: its own launch k_finish)
     int spec_tau = 1;        // option: speculative scan threshold (rank < k of the sample, verified by k_refine)
     int dense_sample = 0;    // searches left with a threshold sample twice as dense (set when a search emitted 3x a random corpus' candidates)
-    int spread_boot = 1;     // option: the threshold sample is every div-th 32-row block instead of every div-th 256-row tile (B > 64)
+    int spread_boot = 1;     // option: a tile bootstrap (any not taken by k_boot) samples every div-th 32-row block instead of every div-th 256-row tile
     int spec_backoff = 0;    // searches left during which the provable threshold is used (set when a speculation failed)
     double xw[8] = {1, 1, 1, 1, 1, 1, 1, 1};   // relative speed of the XCDs as the last main scans showed it (sum 8)
-    unsigned long long wg_times[1024] = {};    // start/end stamps of the last main scan's workgroups (host copy)
     int sample_div = 64;
     int64_t cand_cap = 0;   // 0 = automatic
     int64_t row_base = 0;   // added to every returned row id (global ids of a shard)
@@ -168,7 +193,6 @@ struct rdx_index {
     unsigned long long seq = 0;       // number of the last search enqueued on this index
     char* pin_out = nullptr;          // pinned staging for the small results of host callers (score | row | count)
     char* pin_out_dev = nullptr;
-    size_t pin_out_bytes = 0;
     bool ctr_ready = false;           // the counter block was zeroed once; afterwards every k_finish re-zeroes it
     PendingSearch pending;            // rdx_search_async: the search whose host half is still to run
     hipEvent_t ev[8] = {};
@@ -978,12 +1002,9 @@ static int launch_scan_bn(rdx_index* h, int bn, bool res, const ScanParams& p, i
                 return launch_scan<256, EPI, false, false, true>(h, p, grid, st);
             }
         }
-        if (p.nqt == 1) return launch_scan<256, EPI, false, true>(h, p, grid, st);   // one query tile: corpus read once -> nt loads
-        return launch_scan<256, EPI, false>(h, p, grid, st);
-    } else {
-        if (p.nqt == 1) return launch_scan<256, EPI, false, true>(h, p, grid, st);
-        return launch_scan<256, EPI, false>(h, p, grid, st);
     }
+    if (p.nqt == 1) return launch_scan<256, EPI, false, true>(h, p, grid, st);   // one query tile: corpus read once -> nt loads
+    return launch_scan<256, EPI, false>(h, p, grid, st);
 }
 
 static const int K_FAST_MAX = 256;   // larger k goes through the exact full scan
@@ -1027,44 +1048,32 @@ static int run_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, con
 // had to rewrite some results afterwards they are copied again (HostOut::stale).
 static const size_t PIN_MAX = 256 * 1024;   // results up to this size ride with k_finish (one block writing over PCIe)
 
-static int ensure_mailbox(rdx_index* h) {
-    if (h->mbox) return RDX_OK;
+// zeroed pinned host memory the device reaches over PCIe: its host address and the device's address of the same bytes
+static int map_pinned(size_t bytes, void** host, void** dev) {
     void* p = nullptr;
-    HIP_TRY(hipHostMalloc(&p, sizeof(Mailbox), hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(p, 0, sizeof(Mailbox));
+    HIP_TRY(hipHostMalloc(&p, bytes, hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(p, 0, bytes);
     void* d = nullptr;
     hipError_t e = hipHostGetDevicePointer(&d, p, 0);
     if (e != hipSuccess) {
         (void)hipHostFree(p);
         return fail(RDX_ERR_HIP, std::string("hipHostGetDevicePointer: ") + hipGetErrorString(e));
     }
-    h->mbox = reinterpret_cast<Mailbox*>(p);
-    h->mbox_dev = reinterpret_cast<Mailbox*>(d);
+    *host = p;
+    *dev = d;
     return RDX_OK;
 }
 
-static int ensure_pin_out(rdx_index* h, size_t bytes) {
-    if (bytes <= h->pin_out_bytes) return RDX_OK;
-    if (h->pin_out) (void)hipHostFree(h->pin_out);
-    h->pin_out = nullptr;
-    h->pin_out_bytes = 0;
-    void* p = nullptr;
-    HIP_TRY(hipHostMalloc(&p, PIN_MAX, hipHostMallocMapped | hipHostMallocCoherent));
-    void* d = nullptr;
-    hipError_t e = hipHostGetDevicePointer(&d, p, 0);
-    if (e != hipSuccess) {
-        (void)hipHostFree(p);
-        return fail(RDX_ERR_HIP, std::string("hipHostGetDevicePointer: ") + hipGetErrorString(e));
+static int copy_results_to_host(const HostOut& ho, const float* d_score, const int64_t* d_row, const int32_t* d_count, int64_t nq,
+                                int k, hipStream_t st) {
+    if (k > 0) {
+        HIP_TRY(hipMemcpyAsync(ho.score, d_score, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(ho.row, d_row, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
     }
-    h->pin_out = reinterpret_cast<char*>(p);
-    h->pin_out_dev = reinterpret_cast<char*>(d);
-    h->pin_out_bytes = PIN_MAX;
+    HIP_TRY(hipMemcpyAsync(ho.count, d_count, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
     return RDX_OK;
 }
 
-// The search numbered `seq` has completed: its k_finish published the mailbox. Spin on the pinned word for a while
-// (short searches: the store arrives a couple of us after the kernel, no interrupt, no D2H copy), then fall back to
-// hipStreamSynchronize (long searches; it also surfaces a faulted kernel).
 // Waits until ready() says a word in pinned host memory has arrived — never for the stream: an asynchronous caller may have enqueued
 // other work behind the search or merge that publishes the word (BASELINE config 5: the next batch's query encode, 15 ms of kernels),
 // and a stream synchronise would wait for that too. Hot spin for 0.4 ms (a small search ends inside it), then poll with a yield
@@ -1121,63 +1130,57 @@ static int wait_word(F ready, hipStream_t st) {
     }
 }
 
-static int wait_search(rdx_index* h, hipStream_t st, unsigned long long seq) {
-    const int rc = wait_word([&] { return __atomic_load_n(&h->mbox->seq, __ATOMIC_ACQUIRE) == seq; }, st);
-    if (rc == 1) return fail(RDX_ERR_HIP, "internal: the search completed without publishing its mailbox");
-    return rc;
-}
-
-// depth 0 = the caller's batch; depth 1 = the second-chance batch of queries whose candidate segments overflowed
-static int complete_chunk_impl(rdx_index* h, const PendingSearch& ps, rdx_search_stats* acc_stats, HostOut* ho, bool* redone);
-// The counter block is zeroed once and afterwards by the k_finish of every search. A search that leaves early (allocation
-// failure, launch error, an internal check) may have skipped its k_finish: the next search zeroes the block itself again.
-static int complete_chunk(rdx_index* h, const PendingSearch& ps, rdx_search_stats* acc_stats, HostOut* ho, bool* redone) {
-    const int rc = complete_chunk_impl(h, ps, acc_stats, ho, redone);
-    if (rc != RDX_OK) h->ctr_ready = false;
-    return rc;
-}
-
-// `defer`: return as soon as everything up to k_finish is enqueued; the host half is left in h->pending (rdx_search_async)
-static int search_chunk_impl(rdx_index* h, const float* d_queries, int64_t nq, int k, const uint32_t* d_allow, float* d_score,
-                             int64_t* d_row, int32_t* d_count, hipStream_t st, rdx_search_stats* acc_stats, int depth,
-                             HostOut* ho, bool defer, int32_t* d_flags);
-static int search_chunk(rdx_index* h, const float* d_queries, int64_t nq, int k, const uint32_t* d_allow, float* d_score,
-                        int64_t* d_row, int32_t* d_count, hipStream_t st, rdx_search_stats* acc_stats, int depth = 0,
-                        HostOut* ho = nullptr, bool defer = false, int32_t* d_flags = nullptr) {
-    const int rc = search_chunk_impl(h, d_queries, nq, k, d_allow, d_score, d_row, d_count, st, acc_stats, depth, ho, defer, d_flags);
-    if (rc != RDX_OK) h->ctr_ready = false;
-    return rc;
-}
-
-static int search_chunk_impl(rdx_index* h, const float* d_queries, int64_t nq, int k, const uint32_t* d_allow, float* d_score,
-                             int64_t* d_row, int32_t* d_count, hipStream_t st, rdx_search_stats* acc_stats, int depth,
-                             HostOut* ho, bool defer, int32_t* d_flags) {
-    const int nq_pad = (int)((nq + 255) / 256 * 256);
-    const bool prof_all = h->profile == 1 && depth == 0, prof_main = (h->profile == 1 || h->profile == 2) && depth == 0;
-    const bool prof_stamps = h->profile == 3 && depth == 0;   // the kernels stamp their own times: nothing extra on the stream
-    auto mark = [&](int i) {
-        if (prof_all || (prof_main && (i == 3 || i == 4))) (void)hipEventRecord(h->ev[i], st);
-    };
-    double ps_expected_per_query = 0.0;   // candidates per query a random corpus would emit with this search's sample (MFMA path)
-    // K1 on the queries: qhat (fp32, exact re-score) + tiled fp16 copy (scan)
-    RDX_TRY(h->qhat.ensure((size_t)nq_pad * h->dim * 4));
-    RDX_TRY(h->qshadow.ensure((size_t)nq_pad * h->dim_pad * 2));
-    static_assert(sizeof(RefineCounters) <= 64, "counter block layout: one 64-byte line");
-    RDX_TRY(h->ctr.ensure(sizeof(RefineCounters)));
-    RDX_TRY(h->exact_list.ensure((size_t)nq_pad * 4));
-    RDX_TRY(ensure_mailbox(h));
-    if (!h->ctr_ready) {   // zeroed once; afterwards the k_finish of every search leaves it zeroed for the next one
-        HIP_TRY(hipMemsetAsync(h->ctr.p, 0, sizeof(RefineCounters), st));
-        h->ctr_ready = true;
+// Speculative threshold. The provable threshold is the k-th largest sampled score: k/S of the sample's
+// quantile scale where the corpus' k-th score sits at k/N — with a 1.6 % sample and k = 10 that is 60x the hits one
+// needs. The corpus' k-th score is ESTIMATED by the sample's j-th largest with j ~ k*S/N; taking the smallest j for
+// which fewer than k rows of the corpus lie above it (with a factor 2 for the 2E band the verification needs) with
+// probability <= 1e-7 per query (the count above the sample's j-th largest is N/S * Gamma(j)) cuts the hits 2-6x
+// (c4: 890 -> ~430 per query, c3: 4500 -> ~700). k_refine verifies every query (c_k - 2E >= T); a failed one takes the
+// fallback passes, which use rank k, and switches speculation off for the next searches (structured corpora, where
+// "every div-th tile" is not a random sample; h.spec_backoff counts them down in enqueue_scan, after this read).
+static int speculative_rank(const rdx_index& h, int k, int depth, int64_t sample_rows) {
+    if (!h.spec_tau || depth != 0 || h.spec_backoff != 0 || k <= 1) return k;
+    const double lam = 2.0 * (double)k * (double)sample_rows / (double)std::max<int64_t>(h.rows, 1);
+    double term = std::exp(-lam), cdf = term;   // P(Poisson(lam) <= j - 1)
+    int j = 1;
+    while (1.0 - cdf > 1e-7 && j < k) {
+        term *= lam / j;
+        cdf += term;
+        ++j;
     }
-    int* d_bad = reinterpret_cast<int*>(h->ctr.as<char>() + offsetof(RefineCounters, bad));
-    const unsigned long long seq = ++h->seq;
-    mark(0);
-    hipLaunchKernelGGL(k_normalize<true>, dim3((int)((nq_pad + 3) / 4)), dim3(256), 0, st, d_queries, (const uint16_t*)nullptr, nq, h->dim,
-                       (const int64_t*)nullptr, (int64_t)0, MasterView{h->qhat.as<float>(), nullptr, nullptr}, h->qshadow.as<_Float16>(), h->ksteps, h->scale(),
-                       d_bad, (int64_t)nq_pad, depth > 0 ? 1 : 0);   // depth 1: the rows ARE normalised queries (gathered from qhat): kept bit for bit
-    HIP_TRY(hipGetLastError());
-    mark(1);
+    return std::min(k, j);
+}
+
+// bulk: what the slowest XCD should get, dealt interleaved to everybody (whole iterations of all streams);
+// tail: the rest, one contiguous range per XCD holding what that XCD should get beyond the bulk
+static void plan_xcd_split(const rdx_index& h, SearchPlan* p) {
+    const double wmin = *std::min_element(h.xw, h.xw + 8);
+    p->bulk_it = (int)std::max<int64_t>(0, (int64_t)std::floor((double)p->n_tiles * wmin / 8.0 / p->G) - 1);
+    const int64_t t0 = (int64_t)p->bulk_it * p->n_streams, tail = p->n_tiles - t0;
+    double want[8], sum = 0;
+    for (int x = 0; x < 8; ++x) sum += (want[x] = std::max(0.0, (double)p->n_tiles * h.xw[x] / 8.0 - (double)p->bulk_it * p->G));
+    double acc = 0;
+    for (int x = 0; x <= 8; ++x) {
+        p->xlo[x] = (int)(t0 + std::llround((double)tail * (sum > 0 ? acc / sum : x / 8.0)));
+        if (x < 8) acc += want[x];
+    }
+    p->xlo[8] = (int)p->n_tiles;
+}
+
+// Every decision of a search of nq (<= one launch) queries at `depth`, from the index's state and options alone: no HIP call,
+// nothing written. The internal checks fail here, before anything is enqueued.
+static int plan_search(const rdx_index& h, int64_t nq, int k, int depth, bool host_out, SearchPlan* out) {
+    SearchPlan& p = *out = SearchPlan{};
+    p.nq = nq;
+    p.k = k;
+    p.depth = depth;
+    p.nq_pad = (int)((nq + 255) / 256 * 256);
+    p.prof = depth == 0 ? h.profile : 0;
+    p.b_s = (size_t)nq * k * 4;
+    p.b_r = (size_t)nq * k * 8;
+    p.b_c = (size_t)nq * 4;
+    p.ride = host_out && p.b_s + p.b_r + p.b_c <= PIN_MAX;
+    p.big_copy = host_out && !p.ride;
 
     // small problems and huge k are served by the exact full scan alone (one fp32 read of the corpus)
     // Round 2 re-measured the crossover (B = 4: exact path 0.060 / 0.099 / 0.129 ms at 24 k / 40 k / 60 k rows, MFMA path 0.081 / 0.085 /
@@ -1185,494 +1188,502 @@ static int search_chunk_impl(rdx_index* h, const float* d_queries, int64_t nq, i
     // MFMA path ~60 us more than that share whatever the size — and beyond 32 Ki rows the select no longer holds a score row in
     // registers. (The rule it replaces, nq * rows <= 4 M below 64 Ki rows, sent 64 queries x 60 k rows through 16 exact passes.)
     const int64_t exact_passes = (nq + 3) / 4;
-    const bool small = h->rows <= 32768 && (double)exact_passes * ((double)h->rows * 1.28e-3 + 10.0) <= 60.0;   // (any size: 600 queries on 1000 rows are 150 passes)
-    const bool exact_only = h->force_exact || k > K_FAST_MAX || k == 0 || h->rows < 1 || (small && !h->force_fast);
-    int64_t sample_rows = 0;
-    int grid = 0, G = 0, nqt = 0;
-    bool balance = false;
-    // K6 (end of search): results of small host calls -> pinned staging, counters (+ workgroup stamps) -> mailbox, counter block
-    // re-zeroed, sequence number published. Runs in the last block of the search's last kernel (option fuse_finish, default) or
-    // as its own launch behind it.
-    const size_t b_s = (size_t)nq * k * 4, b_r = (size_t)nq * k * 8, b_c = (size_t)nq * 4;
-    const bool ride = ho && b_s + b_r + b_c <= PIN_MAX;
-    if (ride) RDX_TRY(ensure_pin_out(h, b_s + b_r + b_c));
-    auto finish_args = [&](bool stamps) {
-        FinishArgs f = {};
-        f.ctr = h->ctr.as<RefineCounters>();
-        f.mb = h->mbox_dev;
-        f.seq = seq;
-        f.wgt = stamps ? h->wgt.as<unsigned long long>() : nullptr;
-        f.n_wgt = stamps ? 2 * grid : 0;
-        f.s0 = reinterpret_cast<const uint32_t*>(d_row);
-        f.d0 = reinterpret_cast<uint32_t*>(h->pin_out_dev);
-        f.w0 = (int64_t)(ride ? b_r / 4 : 0);
-        f.s1 = reinterpret_cast<const uint32_t*>(d_score);
-        f.d1 = reinterpret_cast<uint32_t*>(h->pin_out_dev + b_r);
-        f.w1 = (int64_t)(ride ? b_s / 4 : 0);
-        f.s2 = reinterpret_cast<const uint32_t*>(d_count);
-        f.d2 = reinterpret_cast<uint32_t*>(h->pin_out_dev + b_r + b_s);
-        f.w2 = (int64_t)(ride ? b_c / 4 : 0);
-        f.out_flags = depth == 0 ? d_flags : nullptr;
-        f.may_redo = (!exact_only && depth == 0) ? 1 : 0;
-        return f;
-    };
-    const FinishArgs no_fin = {};
-    FinishArgs fin_later = {};   // fuse_finish = 0: what the stand-alone k_finish gets
-    if (exact_only) {
-        for (int i = 2; i <= 3; ++i) mark(i);   // events 3..4 bracket the dominant kernels of this path too (K5a + K5b)
-        if ((size_t)nq_pad * 4 > h->iota.bytes) {   // identity query list, uploaded once (grow-only), not per search
-            RDX_TRY(h->iota.ensure((size_t)nq_pad * 4));
-            const size_t cnt = h->iota.bytes / 4;
-            std::vector<int32_t> io(cnt);
-            for (size_t i = 0; i < cnt; ++i) io[i] = (int32_t)i;
-            HIP_TRY(hipMemcpyAsync(h->iota.p, io.data(), cnt * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-        fin_later = finish_args(false);
-        RDX_TRY(run_exact(h, h->iota.as<int32_t>(), (int)nq, k, d_allow, d_score, d_row, d_count, st, prof_stamps,
-                          h->fuse_finish ? &fin_later : nullptr));
-        for (int i = 4; i <= 5; ++i) mark(i);
-    } else {
-        // queries per workgroup: 64 (tile resident in LDS), 128, 256. 257..384 queries run as three 128-query tiles rather than
-        // one full and one half-empty 256-query tile (measured at 1M x 1024, B = 384: 0.78 vs 0.84 ms; tools/bn_sweep.py)
-        int bn = nq <= 64 ? 64 : (nq <= 128 ? 128 : ((nq > 256 && nq <= 384) ? 128 : 256));
-        if (h->force_bn && (nq + h->force_bn - 1) / h->force_bn <= 32) bn = h->force_bn;   // developer option: queries per workgroup
-        nqt = (int)((nq + bn - 1) / bn);
-        grid = std::max(8, h->n_cu / 8 * 8);
-        const int wpx = grid / 8;
-        if (nqt > wpx) return fail(RDX_ERR_STATE, "internal: query chunk larger than one scan launch");
-        G = wpx / nqt;
-        const int n_streams = 8 * G;
-        if (n_streams > REFINE_STREAMS) return fail(RDX_ERR_STATE, "internal: more streams than the refine kernel gathers");
-        const int n_sets = n_streams * SETS_PER_STREAM;
-        const int64_t n_tiles = (h->rows + 255) / 256;
-        if (n_tiles * h->ksteps >= ((int64_t)1 << 31)) return fail(RDX_ERR_STATE, "shard too large for one scan launch");
-        // the 64-query tile stays resident in LDS when all its k-step images fit (no DMA, no barrier in the main loop)
-        const bool res = bn == 64 && (size_t)h->ksteps * 8192 + 512 <= 160 * 1024 - 1024;
-        // bootstrap sample: every div-th tile. More rows sampled = tighter tau = fewer hits; keep the expected hits
-        // per query (~1.3 k rows/sample_rows) around 4000/... of the refine list and the sample >= max(64k, 8192) rows
-        // Bootstrap geometry. 129..256 queries run their main scan as ONE 256-query tile per workgroup, but their bootstrap samples
-        // ~130 tiles: as one tile per workgroup that is half the CUs working through 16 dependent k-steps of 64 KB each (36 us at
-        // c3). As TWO 128-query tiles per sampled tile every CU works, a k-step moves 48 KB and takes 1.4 instead of 2.25 us
-        // (DESIGN.md §10's table): option "half_boot" (default 1).
-        int bn_b = bn, nqt_b = nqt, ns_b = n_streams;
-        if (h->half_boot && bn == 256 && nqt == 1) {
-            bn_b = 128;
-            nqt_b = 2;
-            ns_b = 8 * (wpx / 2);
-        }
-        const int n_sets_b = ns_b * SETS_PER_STREAM;
-        const int64_t want_rows = std::max<int64_t>(64 * (int64_t)k, 8192);
-        int div = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(h->sample_div, h->rows / want_rows), 3000 / std::max(k, 1)));
-        if (depth > 0) div = std::max(1, div / 8);   // second chance: 8x denser sample -> a threshold that sees the cluster
-        // A corpus whose last searches emitted far more candidates than a random corpus would (clustered rows: a query's neighbours are
-        // one document's chunks, and a thin sample holds too few of them to place the threshold among them) gets twice the sample for a
-        // while: +0.25 ms of bootstrap on a 10 M-row scan, against thousands of surplus candidates per query to gather and re-score
-        // (measured, embedding-like corpus at c4: 19.6 -> 16.2 ms per batch; N(0,1) corpus: +1 %, which is why it is not the default).
-        else if (h->dense_sample > 0 && div > 1) div = std::max(1, div / 2);
-        int64_t n_sched = (n_tiles + div - 1) / div;
-        // whole rounds only: the bootstrap takes as long as its busiest stream, so 77 tiles on 64 streams cost two tiles' time for
-        // 1.2 tiles' worth of threshold (a 1.25 M-row shard at B = 1024: 53 -> 27 us of a 2.26 ms search); thin the sample to the
-        // last full round instead, as long as it keeps the rows asked for above
-        if (n_sched > ns_b && n_sched % ns_b != 0) {
-            const int64_t full = n_sched / ns_b * ns_b;
-            const int div2 = (int)((n_tiles + full - 1) / full);
-            if ((n_tiles + div2 - 1) / div2 * 256 >= want_rows) {
-                div = div2;
-                n_sched = (n_tiles + div - 1) / div;
-            }
-        }
-        // The sample as every div-th 32-ROW BLOCK (option "spread_boot", default 1) instead of every div-th 256-row tile: the same number
-        // of rows, eight times finer. Wave w of virtual tile j takes block (8 j + w) * div; the last virtual tile ends inside the corpus.
-        const int64_t n_blocks32 = (h->rows + 31) / 32;
-        const int64_t n_virtual = ((n_blocks32 - 1) / div + 1) / 8;
-        const bool spread = h->spread_boot && n_virtual >= 1;
-        if (spread) n_sched = n_virtual;
-        sample_rows = n_sched * 256;
-        int n_sets_used = (int)std::min<int64_t>(ns_b, n_sched) * SETS_PER_STREAM;
-        // Small launches (<= 64 queries and a sample of at most four 32-row blocks per CU): the split-K bootstrap k_boot — one
-        // 32-row block per workgroup, the k-steps dealt to the waves — instead of a few whole tiles of 16 dependent k-steps on
-        // a few CUs (scan_kernel.hpp K2b). Whole rounds of the CUs when more than one.
-        int64_t boot_units = std::min<int64_t>(n_blocks32, n_sched * 8);
-        if (boot_units > h->n_cu) boot_units = boot_units / h->n_cu * h->n_cu;
-        const bool use_boot = h->split_boot && bn == BOOT_BN && nqt == 1 && boot_units <= 4 * (int64_t)h->n_cu;
-        // ... and the split-K main scan k_scan_small when the whole corpus is at most 32 such blocks per CU (scan_kernel.hpp K2c)
-        const bool use_small = h->small_scan && bn == BOOT_BN && nqt == 1 && h->ksteps <= 16 && n_streams == grid &&
-                               n_blocks32 <= 32 * (int64_t)h->n_cu && n_blocks32 >= grid;
-        int boot_sets = 0;
-        if (use_boot) {
-            sample_rows = boot_units * 32;
-            boot_sets = (int)boot_units * 4;
-            n_sets_used = boot_sets;
-        }
-        // slots per (query, stream) segment: 8x the expected hits, power of two, [32, 4096]
-        const double exp_hits = (1.5 * k * (double)h->rows / (double)std::max<int64_t>(sample_rows, 1) + k) / n_streams;
-        ps_expected_per_query = exp_hits * n_streams;
-        // (slots cost address space, not bandwidth: only occupied slots are ever touched)
-        // (nq_pad * n_streams is 65,536 whatever the batch: 1024 slots = 512 MiB, 4096 = 2 GiB of the 288)
-        uint32_t capw = depth > 0 ? 4096 : 1024;
-        while (capw < 4096 && capw < 8.0 * exp_hits) capw *= 2;
-        if (h->cand_cap && depth == 0) capw = (uint32_t)std::min<int64_t>(h->cand_cap, 8191);
-        // the scan addresses candidate slots with 32-bit indices (scan_kernel.hpp emit_block)
-        if ((uint64_t)nq_pad * (uint64_t)n_streams * capw >= (1ull << 29)) return fail(RDX_ERR_STATE, "internal: candidate segments exceed the 32-bit slot index");
-        RDX_TRY(h->tau.ensure((size_t)nq_pad * 4));
-        RDX_TRY(h->cntw.ensure((size_t)nq_pad * n_streams * 4));
-        RDX_TRY(h->cand.ensure((size_t)nq_pad * n_streams * capw * 8));
-        RDX_TRY(h->setmax.ensure((size_t)nq_pad * std::max(std::max(n_sets, n_sets_b), boot_sets) * 4));
+    const bool small = h.rows <= 32768 && (double)exact_passes * ((double)h.rows * 1.28e-3 + 10.0) <= 60.0;   // (any size: 600 queries on 1000 rows are 150 passes)
+    p.exact_only = h.force_exact || k > K_FAST_MAX || k == 0 || h.rows < 1 || (small && !h.force_fast);
+    if (p.exact_only) return RDX_OK;
 
-        ScanParams p = {};
-        p.shadow = h->shadow;
-        p.qshadow = h->qshadow.as<_Float16>();
-        p.ksteps = h->ksteps;
-        p.rows = h->rows;
-        p.n_tiles = n_tiles;
-        p.nqt = nqt;
-        p.nq_pad = nq_pad;
-        p.allow = d_allow;
-        p.setmax = h->setmax.as<float>();
-        p.n_sets = n_sets;
-        p.tau = h->tau.as<float>();
-        p.cntw = h->cntw.as<uint32_t>();
-        p.cand = h->cand.as<uint2>();
-        p.capw = capw;
-        p.inv_scale2 = std::ldexp(1.0f, -2 * h->scale_log2);
-        p.shadow_bytes = (int64_t)shadow_bytes(h, h->cap);
-        p.oob = reinterpret_cast<int*>(h->ctr.as<char>() + offsetof(RefineCounters, oob));
-
-        if (use_boot) {
-            BootParams bp = {};
-            bp.shadow = h->shadow;
-            bp.qshadow = h->qshadow.as<_Float16>();
-            bp.ksteps = h->ksteps;
-            bp.rows = h->rows;
-            bp.n_blocks32 = n_blocks32;
-            bp.units = (int)boot_units;
-            bp.allow = d_allow;
-            bp.setmax = h->setmax.as<float>();
-            bp.n_sets = boot_sets;
-            hipLaunchKernelGGL(k_boot, dim3((unsigned)boot_units), dim3(512), 0, st, bp);
-            HIP_TRY(hipGetLastError());
-        } else {
-            ScanParams pb = p;
-            pb.tile_stride = div;
-            pb.span = TILE_ROWS;
-            if (spread) {   // wave w of sampled entry j: block (8 j + w) * div (scan_kernel.hpp ScanParams::wave_off)
-                pb.wave_off = (int64_t)(div - 1) * h->ksteps * 4096;
-                pb.row_off = (div - 1) * 32;
-                pb.span = (7 * div + 1) * 32;
-                pb.n_tiles = (n_virtual - 1) * (int64_t)div + 1;   // ceil(n_tiles / div) = n_virtual entries: the last block lies inside the corpus
-            }
-            pb.nqt = nqt_b;
-            pb.n_sets = n_sets_b;
-            RDX_TRY(launch_scan_bn<EPI_SETMAX>(h, bn_b, bn_b == bn ? res : false, pb, grid, st));
-        }
-        mark(2);
-        // Speculative threshold. The provable threshold is the k-th largest sampled score: k/S of the sample's
-        // quantile scale where the corpus' k-th score sits at k/N — with a 1.6 % sample and k = 10 that is 60x the hits one
-        // needs. The corpus' k-th score is ESTIMATED by the sample's j-th largest with j ~ k*S/N; taking the smallest j for
-        // which fewer than k rows of the corpus lie above it (with a factor 2 for the 2E band the verification needs) with
-        // probability <= 1e-7 per query (the count above the sample's j-th largest is N/S * Gamma(j)) cuts the hits 2-6x
-        // (c4: 890 -> ~430 per query, c3: 4500 -> ~700). k_refine verifies every query (c_k - 2E >= T); a failed one takes the
-        // fallback passes, which use rank k, and switches speculation off for the next searches (structured corpora, where
-        // "every div-th tile" is not a random sample).
-        int k_sel = k;
-        if (h->spec_tau && depth == 0 && h->spec_backoff == 0 && k > 1) {
-            const double lam = 2.0 * (double)k * (double)sample_rows / (double)std::max<int64_t>(h->rows, 1);
-            double term = std::exp(-lam), cdf = term;   // P(Poisson(lam) <= j - 1)
-            int j = 1;
-            while (1.0 - cdf > 1e-7 && j < k) {
-                term *= lam / j;
-                cdf += term;
-                ++j;
-            }
-            k_sel = std::min(k, j);
-        }
-        if (depth == 0 && h->spec_backoff > 0) --h->spec_backoff;
-        acc_stats->tau_rank = (float)k_sel;
-        // proven threshold: 2E below the k-th sampled score — plus, when the sample was summed in another order than the main scan
-        // sums (k_boot), twice the fp32 accumulation bound, so that the verification (c_k - 2E >= T, with c_k from the main
-        // scan's sums) cannot fail on a rounding difference between the two orders
-        const float slack = h->two_e() + ((use_boot != use_small) ? 2.0f * (float)h->dim_pad * 1.1920929e-7f : 0.0f);
-        hipLaunchKernelGGL(k_tau, dim3(nq_pad), dim3(256), 0, st, h->setmax.as<float>(), use_boot ? boot_sets : n_sets_b, n_sets_used, k_sel,
-                           k_sel == k ? slack * std::ldexp(1.0f, 2 * h->scale_log2) : 0.0f, (int)nq, h->tau.as<float>());
-        HIP_TRY(hipGetLastError());
-        mark(3);
-        p.tile_stride = 1;
-        // The eight XCDs do not finish equal shares at the same time (measured on c4: the last XCD 1.1-1.7 ms after the
-        // first of 16.5, always the same ones). Each XCD therefore gets a contiguous range of the tile schedule sized by
-        // its speed in the previous main scans (from the workgroups' own time stamps, damped) — no coordination
-        // inside the kernel, just a different static split. Large launches only.
-        balance = h->xcd_balance && depth == 0 && n_tiles >= 1024 && grid <= 512;
-        if (balance) {
-            RDX_TRY(h->wgt.ensure((size_t)grid * 16));
-            p.use_xlo = 1;
-            p.wgt = h->wgt.as<unsigned long long>();
-            // bulk: what the slowest XCD should get, dealt interleaved to everybody (whole iterations of all streams);
-            // tail: the rest, one contiguous range per XCD holding what that XCD should get beyond the bulk
-            const double wmin = *std::min_element(h->xw, h->xw + 8);
-            p.bulk_it = (int)std::max<int64_t>(0, (int64_t)std::floor((double)n_tiles * wmin / 8.0 / G) - 1);
-            const int64_t t0 = (int64_t)p.bulk_it * n_streams, tail = n_tiles - t0;
-            double want[8], sum = 0;
-            for (int x = 0; x < 8; ++x) sum += (want[x] = std::max(0.0, (double)n_tiles * h->xw[x] / 8.0 - (double)p.bulk_it * G));
-            double acc = 0;
-            for (int x = 0; x <= 8; ++x) {
-                p.xlo[x] = (int)(t0 + std::llround((double)tail * (sum > 0 ? acc / sum : x / 8.0)));
-                if (x < 8) acc += want[x];
-            }
-            p.xlo[8] = (int)n_tiles;
-        }
-        if (prof_stamps && !balance && grid <= 512) {   // (Mailbox::wg_times holds 1024 stamps)
-            RDX_TRY(h->wgt.ensure((size_t)grid * 16));
-            p.wgt = h->wgt.as<unsigned long long>();
-        }
-        if (use_small) {
-            SmallScanParams sp = {};
-            sp.shadow = h->shadow;
-            sp.qshadow = h->qshadow.as<_Float16>();
-            sp.ksteps = h->ksteps;
-            sp.rows = h->rows;
-            sp.n_blocks32 = n_blocks32;
-            sp.allow = d_allow;
-            sp.tau = h->tau.as<float>();
-            sp.cntw = h->cntw.as<uint32_t>();
-            sp.cand = h->cand.as<uint2>();
-            sp.capw = capw;
-            sp.inv_scale2 = p.inv_scale2;
-            sp.wgt = p.wgt;
-            hipLaunchKernelGGL(k_scan_small, dim3((unsigned)grid), dim3(512), 0, st, sp);
-            HIP_TRY(hipGetLastError());
-        } else {
-            RDX_TRY(launch_scan_bn<EPI_EMIT>(h, bn, res, p, grid, st));
-        }
-        p.use_xlo = 0;
-        p.wgt = nullptr;
-        mark(4);
-        {
-            // LDS list of the gathered hits: 16x the expected count (heavy-tailed score distributions of structured corpora; a list overflow costs a second pass), at most REFINE_LIST
-            uint32_t list_cap = 1024;
-            while (list_cap < (uint32_t)REFINE_LIST && list_cap < 16.0 * exp_hits * n_streams) list_cap *= 2;
-            list_cap = std::min<uint32_t>(list_cap, REFINE_LIST);
-            const size_t lds = (size_t)list_cap * 8;
-            fin_later = finish_args((balance || prof_stamps) && grid <= 512);
-            RDX_TRY(ensure_dynamic_lds(h, (const void*)k_refine, lds));
-            hipLaunchKernelGGL(k_refine, dim3((int)nq), dim3(1024), lds, st, h->cand.as<uint2>(), h->cntw.as<uint32_t>(), n_streams, capw,
-                               list_cap, k, h->two_e(), h->qhat.as<float>(), h->mv(), h->dim, h->row_base, h->row_map, d_score, d_row, d_count,
-                               h->exact_list.as<int32_t>(), h->ctr.as<RefineCounters>(), h->tau.as<float>(), p.inv_scale2,
-                               h->fuse_finish ? fin_later : no_fin);
-            HIP_TRY(hipGetLastError());
-        }
-        mark(5);
+    // queries per workgroup: 64 (tile resident in LDS), 128, 256. 257..384 queries run as three 128-query tiles rather than
+    // one full and one half-empty 256-query tile (measured at 1M x 1024, B = 384: 0.78 vs 0.84 ms; tools/bn_sweep.py)
+    p.bn = nq <= 64 ? 64 : (nq <= 128 ? 128 : ((nq > 256 && nq <= 384) ? 128 : 256));
+    if (h.force_bn && (nq + h.force_bn - 1) / h.force_bn <= 32) p.bn = h.force_bn;   // developer option: queries per workgroup
+    p.nqt = (int)((nq + p.bn - 1) / p.bn);
+    p.grid = std::max(8, h.n_cu / 8 * 8);
+    const int wpx = p.grid / 8;
+    if (p.nqt > wpx) return fail(RDX_ERR_STATE, "internal: query chunk larger than one scan launch");
+    p.G = wpx / p.nqt;
+    p.n_streams = 8 * p.G;
+    if (p.n_streams > REFINE_STREAMS) return fail(RDX_ERR_STATE, "internal: more streams than the refine kernel gathers");
+    p.n_sets = p.n_streams * SETS_PER_STREAM;
+    p.n_tiles = (h.rows + 255) / 256;
+    if (p.n_tiles * h.ksteps >= ((int64_t)1 << 31)) return fail(RDX_ERR_STATE, "shard too large for one scan launch");
+    // the 64-query tile stays resident in LDS when all its k-step images fit (no DMA, no barrier in the main loop)
+    p.res = p.bn == 64 && (size_t)h.ksteps * 8192 + 512 <= 160 * 1024 - 1024;
+    // bootstrap sample: every div-th tile. More rows sampled = tighter tau = fewer hits; keep the expected hits
+    // per query (~1.3 k rows/sample_rows) around 4000/... of the refine list and the sample >= max(64k, 8192) rows
+    // Bootstrap geometry. 129..256 queries run their main scan as ONE 256-query tile per workgroup, but their bootstrap samples
+    // ~130 tiles: as one tile per workgroup that is half the CUs working through 16 dependent k-steps of 64 KB each (36 us at
+    // c3). As TWO 128-query tiles per sampled tile every CU works, a k-step moves 48 KB and takes 1.4 instead of 2.25 us
+    // (DESIGN.md §10's table): option "half_boot" (default 1).
+    p.bn_b = p.bn;
+    p.nqt_b = p.nqt;
+    int ns_b = p.n_streams;
+    if (h.half_boot && p.bn == 256 && p.nqt == 1) {
+        p.bn_b = 128;
+        p.nqt_b = 2;
+        ns_b = 8 * (wpx / 2);
     }
-    if (!h->fuse_finish) {
-        hipLaunchKernelGGL(k_finish, dim3(1), dim3(1024), 0, st, fin_later);
-        HIP_TRY(hipGetLastError());
-    }
-    if (ho && !ride) {   // large host results: plain copies behind the last kernel (complete_chunk synchronises the stream for them)
-        if (k > 0) {
-            HIP_TRY(hipMemcpyAsync(ho->score, d_score, b_s, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(ho->row, d_row, b_r, hipMemcpyDeviceToHost, st));
+    p.n_sets_b = ns_b * SETS_PER_STREAM;
+    const int64_t want_rows = std::max<int64_t>(64 * (int64_t)k, 8192);
+    int div = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(h.sample_div, h.rows / want_rows), 3000 / std::max(k, 1)));
+    if (depth > 0) div = std::max(1, div / 8);   // second chance: 8x denser sample -> a threshold that sees the cluster
+    // A corpus whose last searches emitted far more candidates than a random corpus would (clustered rows: a query's neighbours are
+    // one document's chunks, and a thin sample holds too few of them to place the threshold among them) gets twice the sample for a
+    // while: +0.25 ms of bootstrap on a 10 M-row scan, against thousands of surplus candidates per query to gather and re-score
+    // (measured, embedding-like corpus at c4: 19.6 -> 16.2 ms per batch; N(0,1) corpus: +1 %, which is why it is not the default).
+    else if (h.dense_sample > 0 && div > 1) div = std::max(1, div / 2);
+    int64_t n_sched = (p.n_tiles + div - 1) / div;
+    // whole rounds only: the bootstrap takes as long as its busiest stream, so 77 tiles on 64 streams cost two tiles' time for
+    // 1.2 tiles' worth of threshold (a 1.25 M-row shard at B = 1024: 53 -> 27 us of a 2.26 ms search); thin the sample to the
+    // last full round instead, as long as it keeps the rows asked for above
+    if (n_sched > ns_b && n_sched % ns_b != 0) {
+        const int64_t full = n_sched / ns_b * ns_b;
+        const int div2 = (int)((p.n_tiles + full - 1) / full);
+        if ((p.n_tiles + div2 - 1) / div2 * 256 >= want_rows) {
+            div = div2;
+            n_sched = (p.n_tiles + div - 1) / div;
         }
-        HIP_TRY(hipMemcpyAsync(ho->count, d_count, b_c, hipMemcpyDeviceToHost, st));
     }
-    PendingSearch ps;
-    ps.active = true;
-    ps.d_queries = d_queries;
-    ps.nq = nq;
-    ps.k = k;
-    ps.d_allow = d_allow;
-    ps.d_score = d_score;
-    ps.d_row = d_row;
-    ps.d_count = d_count;
-    ps.d_flags = depth == 0 ? d_flags : nullptr;
-    ps.st = st;
-    ps.seq = seq;
-    ps.exact_only = exact_only;
-    ps.balance = balance;
-    ps.ride = ride;
-    ps.big_host_copy = ho && !ride;
-    ps.grid = grid;
-    ps.G = G;
-    ps.nqt = nqt;
-    ps.depth = depth;
-    ps.sample_rows = sample_rows;
-    ps.expected_per_query = ps_expected_per_query;
-    ps.b_s = b_s;
-    ps.b_r = b_r;
-    ps.b_c = b_c;
-    if (defer) {
-        ps.stats = *acc_stats;
-        h->pending = ps;
-        return RDX_OK;
+    p.div = div;
+    // The sample as every div-th 32-ROW BLOCK (option "spread_boot", default 1) instead of every div-th 256-row tile: the same number
+    // of rows, eight times finer. Wave w of virtual tile j takes block (8 j + w) * div; the last virtual tile ends inside the corpus.
+    // It replaces the whole-rounds schedule above (n_sched becomes the number of virtual tiles) and applies to every bootstrap that
+    // k_boot does not take, whatever the batch size.
+    p.n_blocks32 = (h.rows + 31) / 32;
+    const int64_t n_virtual = ((p.n_blocks32 - 1) / div + 1) / 8;
+    p.boot_tiles = p.n_tiles;
+    p.boot_span = TILE_ROWS;
+    if (h.spread_boot && n_virtual >= 1) {   // wave w of sampled entry j: block (8 j + w) * div (scan_kernel.hpp ScanParams::wave_off)
+        n_sched = n_virtual;
+        p.boot_wave_off = (int64_t)(div - 1) * h.ksteps * 4096;
+        p.boot_row_off = (div - 1) * 32;
+        p.boot_span = (7 * div + 1) * 32;
+        p.boot_tiles = (n_virtual - 1) * (int64_t)div + 1;   // ceil(n_tiles / div) = n_virtual entries: the last block lies inside the corpus
     }
-    return complete_chunk(h, ps, acc_stats, ho, nullptr);
+    p.sample_rows = n_sched * 256;
+    p.n_sets_used = (int)std::min<int64_t>(ns_b, n_sched) * SETS_PER_STREAM;
+    // Small launches (<= 64 queries and a sample of at most four 32-row blocks per CU): the split-K bootstrap k_boot — one
+    // 32-row block per workgroup, the k-steps dealt to the waves — instead of a few whole tiles of 16 dependent k-steps on
+    // a few CUs (scan_kernel.hpp K2b). Whole rounds of the CUs when more than one.
+    p.boot_units = std::min<int64_t>(p.n_blocks32, n_sched * 8);
+    if (p.boot_units > h.n_cu) p.boot_units = p.boot_units / h.n_cu * h.n_cu;
+    p.use_boot = h.split_boot && p.bn == BOOT_BN && p.nqt == 1 && p.boot_units <= 4 * (int64_t)h.n_cu;
+    // ... and the split-K main scan k_scan_small when the whole corpus is at most 32 such blocks per CU (scan_kernel.hpp K2c)
+    p.use_small = h.small_scan && p.bn == BOOT_BN && p.nqt == 1 && h.ksteps <= 16 && p.n_streams == p.grid &&
+                  p.n_blocks32 <= 32 * (int64_t)h.n_cu && p.n_blocks32 >= p.grid;
+    if (p.use_boot) {
+        p.sample_rows = p.boot_units * 32;
+        p.boot_sets = (int)p.boot_units * 4;
+        p.n_sets_used = p.boot_sets;
+    }
+    // slots per (query, stream) segment: 8x the expected hits, power of two, [32, 4096]
+    const double exp_hits = (1.5 * k * (double)h.rows / (double)std::max<int64_t>(p.sample_rows, 1) + k) / p.n_streams;
+    p.expected_per_query = exp_hits * p.n_streams;
+    // (slots cost address space, not bandwidth: only occupied slots are ever touched)
+    // (nq_pad * n_streams is 65,536 whatever the batch: 1024 slots = 512 MiB, 4096 = 2 GiB of the 288)
+    uint32_t capw = depth > 0 ? 4096 : 1024;
+    while (capw < 4096 && capw < 8.0 * exp_hits) capw *= 2;
+    if (h.cand_cap && depth == 0) capw = (uint32_t)std::min<int64_t>(h.cand_cap, 8191);
+    // the scan addresses candidate slots with 32-bit indices (scan_kernel.hpp emit_block)
+    if ((uint64_t)p.nq_pad * (uint64_t)p.n_streams * capw >= (1ull << 29)) return fail(RDX_ERR_STATE, "internal: candidate segments exceed the 32-bit slot index");
+    p.capw = capw;
+    p.k_sel = speculative_rank(h, k, depth, p.sample_rows);
+    // proven threshold: 2E below the k-th sampled score — plus, when the sample was summed in another order than the main scan
+    // sums (k_boot), twice the fp32 accumulation bound, so that the verification (c_k - 2E >= T, with c_k from the main
+    // scan's sums) cannot fail on a rounding difference between the two orders
+    p.slack = h.two_e() + ((p.use_boot != p.use_small) ? 2.0f * (float)h.dim_pad * 1.1920929e-7f : 0.0f);
+    // The eight XCDs do not finish equal shares at the same time (measured on c4: the last XCD 1.1-1.7 ms after the
+    // first of 16.5, always the same ones). Each XCD therefore gets a contiguous range of the tile schedule sized by
+    // its speed in the previous main scans (from the workgroups' own time stamps, damped) — no coordination
+    // inside the kernel, just a different static split. Large launches only.
+    p.balance = h.xcd_balance && depth == 0 && p.n_tiles >= 1024 && p.grid <= 512;
+    if (p.balance) plan_xcd_split(h, &p);
+    p.stamps = (p.balance || p.prof == 3) && p.grid <= 512;   // (Mailbox::wg_times holds 1024 stamps)
+    // LDS list of the gathered hits: 16x the expected count (heavy-tailed score distributions of structured corpora; a list overflow costs a second pass), at most REFINE_LIST
+    uint32_t list_cap = 1024;
+    while (list_cap < (uint32_t)REFINE_LIST && list_cap < 16.0 * exp_hits * p.n_streams) list_cap *= 2;
+    p.list_cap = std::min<uint32_t>(list_cap, REFINE_LIST);
+    return RDX_OK;
 }
 
-// the host half of a search (see PendingSearch). *redone (if given) = a fallback pass rewrote results after k_finish.
-static int complete_chunk_impl(rdx_index* h, const PendingSearch& ps, rdx_search_stats* acc_stats, HostOut* ho, bool* redone) {
-    const int64_t nq = ps.nq;
-    const int k = ps.k, depth = ps.depth, grid = ps.grid, G = ps.G, nqt = ps.nqt;
-    const uint32_t* d_allow = ps.d_allow;
-    float* d_score = ps.d_score;
-    int64_t* d_row = ps.d_row;
-    int32_t* d_count = ps.d_count;
-    hipStream_t st = ps.st;
-    const bool exact_only = ps.exact_only, balance = ps.balance, ride = ps.ride;
-    const int64_t sample_rows = ps.sample_rows;
-    const size_t b_s = ps.b_s, b_r = ps.b_r, b_c = ps.b_c;
-    const bool prof_all = h->profile == 1 && depth == 0, prof_main = (h->profile == 1 || h->profile == 2) && depth == 0;
-    const bool prof_stamps = h->profile == 3 && depth == 0;   // the kernels stamp their own times: nothing extra on the stream
-    auto mark = [&](int i) {
-        if (prof_all || (prof_main && (i == 3 || i == 4))) (void)hipEventRecord(h->ev[i], st);
-    };
-    if (redone) *redone = false;
-    if (ps.big_host_copy) HIP_TRY(hipStreamSynchronize(st));   // pageable D2H copies: complete only after a stream synchronise
-    RDX_TRY(wait_search(h, st, ps.seq));   // the ONE host wait of a search
-    const Mailbox& mb = *h->mbox;
-    const unsigned long long c_emitted = mb.emitted, c_rescored = mb.rescored;
-    const int c_bad = mb.bad;
-    if (mb.spec_fail > 0 && depth == 0) h->spec_backoff = 64;   // a speculative threshold was too high: provable thresholds for a while
-    // three times the candidates a random corpus would emit: the corpus is clustered — a denser threshold sample for the next searches
-    // (search_chunk_impl; re-examined every 256 searches: the denser sample's own emission is what then keeps it on)
-    if (depth == 0 && !exact_only && ps.expected_per_query > 0.0) {
-        const double per_q = (double)c_emitted / (double)std::max<int64_t>(nq, 1);
-        if (per_q > (h->dense_sample > 0 ? 1.5 : 3.0) * ps.expected_per_query) h->dense_sample = 256;
-        else if (h->dense_sample > 0) --h->dense_sample;
+// profile 1: an event behind every kernel; profile 2: events 3 and 4 only, around the dominant kernel(s)
+static void mark(rdx_index* h, const SearchPlan& p, hipStream_t st, int i) {
+    if (p.prof == 1 || (p.prof == 2 && (i == 3 || i == 4))) (void)hipEventRecord(h->ev[i], st);
+}
+
+// K6 (end of search): results of small host calls -> pinned staging, counters (+ workgroup stamps) -> mailbox, counter block
+// re-zeroed, sequence number published. Runs in the last block of the search's last kernel (option fuse_finish, default) or
+// as its own launch behind it.
+static FinishArgs finish_args(const rdx_index* h, const SearchPlan& p, const SearchIO& io, unsigned long long seq) {
+    FinishArgs f = {};
+    f.ctr = h->ctr.as<RefineCounters>();
+    f.mb = h->mbox_dev;
+    f.seq = seq;
+    f.wgt = p.stamps ? h->wgt.as<unsigned long long>() : nullptr;
+    f.n_wgt = p.stamps ? 2 * p.grid : 0;
+    f.s0 = reinterpret_cast<const uint32_t*>(io.row);
+    f.d0 = reinterpret_cast<uint32_t*>(h->pin_out_dev);
+    f.w0 = (int64_t)(p.ride ? p.b_r / 4 : 0);
+    f.s1 = reinterpret_cast<const uint32_t*>(io.score);
+    f.d1 = reinterpret_cast<uint32_t*>(h->pin_out_dev + p.b_r);
+    f.w1 = (int64_t)(p.ride ? p.b_s / 4 : 0);
+    f.s2 = reinterpret_cast<const uint32_t*>(io.count);
+    f.d2 = reinterpret_cast<uint32_t*>(h->pin_out_dev + p.b_r + p.b_s);
+    f.w2 = (int64_t)(p.ride ? p.b_c / 4 : 0);
+    f.out_flags = io.flags;
+    f.may_redo = (!p.exact_only && p.depth == 0) ? 1 : 0;
+    return f;
+}
+
+// the MFMA path of a plan: bootstrap (k_boot or k_scan<EPI_SETMAX>), k_tau, main scan (k_scan_small or k_scan<EPI_EMIT>), k_refine
+static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, hipStream_t st, const FinishArgs& fin) {
+    ScanParams sp = {};
+    sp.shadow = h->shadow;
+    sp.qshadow = h->qshadow.as<_Float16>();
+    sp.ksteps = h->ksteps;
+    sp.rows = h->rows;
+    sp.n_tiles = p.n_tiles;
+    sp.nqt = p.nqt;
+    sp.nq_pad = p.nq_pad;
+    sp.allow = io.allow;
+    sp.setmax = h->setmax.as<float>();
+    sp.n_sets = p.n_sets;
+    sp.tau = h->tau.as<float>();
+    sp.cntw = h->cntw.as<uint32_t>();
+    sp.cand = h->cand.as<uint2>();
+    sp.capw = p.capw;
+    sp.inv_scale2 = std::ldexp(1.0f, -2 * h->scale_log2);
+    sp.shadow_bytes = (int64_t)shadow_bytes(h, h->cap);
+    sp.oob = reinterpret_cast<int*>(h->ctr.as<char>() + offsetof(RefineCounters, oob));
+
+    if (p.use_boot) {
+        BootParams bp = {};
+        bp.shadow = h->shadow;
+        bp.qshadow = h->qshadow.as<_Float16>();
+        bp.ksteps = h->ksteps;
+        bp.rows = h->rows;
+        bp.n_blocks32 = p.n_blocks32;
+        bp.units = (int)p.boot_units;
+        bp.allow = io.allow;
+        bp.setmax = h->setmax.as<float>();
+        bp.n_sets = p.boot_sets;
+        hipLaunchKernelGGL(k_boot, dim3((unsigned)p.boot_units), dim3(512), 0, st, bp);
+        HIP_TRY(hipGetLastError());
+    } else {
+        ScanParams pb = sp;
+        pb.tile_stride = p.div;
+        pb.wave_off = p.boot_wave_off;
+        pb.row_off = p.boot_row_off;
+        pb.span = p.boot_span;
+        pb.n_tiles = p.boot_tiles;
+        pb.nqt = p.nqt_b;
+        pb.n_sets = p.n_sets_b;
+        RDX_TRY(launch_scan_bn<EPI_SETMAX>(h, p.bn_b, p.bn_b == p.bn ? p.res : false, pb, p.grid, st));
     }
-    // profile = 3: the kernels' own stamps, read NOW — a second-chance pass below runs a nested search whose k_finish overwrites the mailbox
-    float stamp_ms_exact = 0.f, stamp_ms_main = 0.f;
-    if (prof_stamps) {
-        if (exact_only) {
-            if (mb.t_last > mb.t_first) stamp_ms_exact = (float)((double)(mb.t_last - mb.t_first) * 1e-5);
-        } else if (grid <= 512) {
-            unsigned long long t0 = ~0ull, t1 = 0;
-            for (int b = 0; b < grid; ++b) {
-                if ((b >> 3) >= G * nqt) continue;   // idle workgroups return before they stamp
-                t0 = std::min(t0, mb.wg_times[2 * b]);
-                t1 = std::max(t1, mb.wg_times[2 * b + 1]);
-            }
-            if (t1 > t0) stamp_ms_main = (float)((double)(t1 - t0) * 1e-5);
-        }
+    mark(h, p, st, 2);
+    if (p.depth == 0 && h->spec_backoff > 0) --h->spec_backoff;
+    hipLaunchKernelGGL(k_tau, dim3(p.nq_pad), dim3(256), 0, st, h->setmax.as<float>(), p.use_boot ? p.boot_sets : p.n_sets_b, p.n_sets_used,
+                       p.k_sel, p.k_sel == p.k ? p.slack * std::ldexp(1.0f, 2 * h->scale_log2) : 0.0f, (int)p.nq, h->tau.as<float>());
+    HIP_TRY(hipGetLastError());
+    mark(h, p, st, 3);
+    sp.tile_stride = 1;
+    sp.use_xlo = p.balance ? 1 : 0;
+    sp.bulk_it = p.bulk_it;
+    std::copy(p.xlo, p.xlo + 9, sp.xlo);
+    sp.wgt = p.stamps ? h->wgt.as<unsigned long long>() : nullptr;
+    if (p.use_small) {
+        SmallScanParams ss = {};
+        ss.shadow = h->shadow;
+        ss.qshadow = h->qshadow.as<_Float16>();
+        ss.ksteps = h->ksteps;
+        ss.rows = h->rows;
+        ss.n_blocks32 = p.n_blocks32;
+        ss.allow = io.allow;
+        ss.tau = h->tau.as<float>();
+        ss.cntw = h->cntw.as<uint32_t>();
+        ss.cand = h->cand.as<uint2>();
+        ss.capw = p.capw;
+        ss.inv_scale2 = sp.inv_scale2;
+        ss.wgt = sp.wgt;
+        hipLaunchKernelGGL(k_scan_small, dim3((unsigned)p.grid), dim3(512), 0, st, ss);
+        HIP_TRY(hipGetLastError());
+    } else {
+        RDX_TRY(launch_scan_bn<EPI_EMIT>(h, p.bn, p.res, sp, p.grid, st));
     }
-    if (mb.oob) return fail(RDX_ERR_STATE, "internal: the scan computed a corpus address outside the scan copy (RDX_CHECK_BOUNDS build)");
-    int n_exact = exact_only ? (int)nq : mb.n_exact;
-    if (ride) {
-        if (k > 0) {
-            std::memcpy(ho->row, h->pin_out, b_r);
-            std::memcpy(ho->score, h->pin_out + b_r, b_s);
-        }
-        std::memcpy(ho->count, h->pin_out + b_r + b_s, b_c);
+    mark(h, p, st, 4);
+    const size_t lds = (size_t)p.list_cap * 8;
+    RDX_TRY(ensure_dynamic_lds(h, (const void*)k_refine, lds));
+    hipLaunchKernelGGL(k_refine, dim3((int)p.nq), dim3(1024), lds, st, h->cand.as<uint2>(), h->cntw.as<uint32_t>(), p.n_streams, p.capw,
+                       p.list_cap, p.k, h->two_e(), h->qhat.as<float>(), h->mv(), h->dim, h->row_base, h->row_map, io.score, io.row, io.count,
+                       h->exact_list.as<int32_t>(), h->ctr.as<RefineCounters>(), h->tau.as<float>(), sp.inv_scale2, fin);
+    HIP_TRY(hipGetLastError());
+    mark(h, p, st, 5);
+    return RDX_OK;
+}
+
+// Grow the scratch the plan needs and enqueue it, up to k_finish and the D2H copies of large host results; *seq: the search's number
+static int enqueue_search(rdx_index* h, const SearchPlan& p, const SearchIO& io, const HostOut* ho, hipStream_t st,
+                          unsigned long long* seq) {
+    // K1 on the queries: qhat (fp32, exact re-score) + tiled fp16 copy (scan)
+    RDX_TRY(h->qhat.ensure((size_t)p.nq_pad * h->dim * 4));
+    RDX_TRY(h->qshadow.ensure((size_t)p.nq_pad * h->dim_pad * 2));
+    static_assert(sizeof(RefineCounters) <= 64, "counter block layout: one 64-byte line");
+    RDX_TRY(h->ctr.ensure(sizeof(RefineCounters)));
+    RDX_TRY(h->exact_list.ensure((size_t)p.nq_pad * 4));
+    if (!h->mbox) RDX_TRY(map_pinned(sizeof(Mailbox), (void**)&h->mbox, (void**)&h->mbox_dev));
+    if (p.ride && !h->pin_out) RDX_TRY(map_pinned(PIN_MAX, (void**)&h->pin_out, (void**)&h->pin_out_dev));
+    if (!p.exact_only) {
+        RDX_TRY(h->tau.ensure((size_t)p.nq_pad * 4));
+        RDX_TRY(h->cntw.ensure((size_t)p.nq_pad * p.n_streams * 4));
+        RDX_TRY(h->cand.ensure((size_t)p.nq_pad * p.n_streams * p.capw * 8));
+        RDX_TRY(h->setmax.ensure((size_t)p.nq_pad * std::max(std::max(p.n_sets, p.n_sets_b), p.boot_sets) * 4));
+        if (p.stamps) RDX_TRY(h->wgt.ensure((size_t)p.grid * 16));
     }
-    if (!exact_only && n_exact > 0 && !c_bad && redone) *redone = true;
-    if (!exact_only) {
-        if (n_exact > 0 && ho) ho->stale = true;   // a fallback pass rewrites some of the rows copied above
-        if (balance) {   // the stamps arrived with the counters: re-weight the XCD shares for the next search
-            const unsigned long long* wt = mb.wg_times;
-            unsigned long long t0 = ~0ull, tx[8] = {};
-            for (int b = 0; b < grid; ++b) {
-                if ((b >> 3) >= G * nqt) continue;   // idle workgroups (wpx % nqt != 0) return before they stamp
-                t0 = std::min(t0, wt[2 * b]);
-                tx[b & 7] = std::max(tx[b & 7], wt[2 * b + 1]);
-            }
-            double dur[8], mean = 0;
-            for (int x = 0; x < 8; ++x) mean += (dur[x] = (double)(tx[x] - t0)) / 8.0;
-            if (std::getenv("RDX_DEBUG_XCD")) {   // developer (tools/xcd_spread.py): when each XCD's last (first) workgroup ended, ms after the first start
-                std::fprintf(stderr, "xcd end ms:");
-                for (int x = 0; x < 8; ++x) {
-                    unsigned long long lo = ~0ull;
-                    for (int b = x; b < grid; b += 8)
-                        if ((b >> 3) < G * nqt) lo = std::min(lo, wt[2 * b + 1]);
-                    std::fprintf(stderr, " %.3f(%.3f)", dur[x] * 1e-5, (double)(lo - t0) * 1e-5);
-                }
-                std::fprintf(stderr, "\n");
-            }
-            acc_stats->xcd_finish_spread_ms = (float)((*std::max_element(dur, dur + 8) - *std::min_element(dur, dur + 8)) * 1e-5);   // 100 MHz ticks
-            acc_stats->xcd_share_min = (float)*std::min_element(h->xw, h->xw + 8);
-            acc_stats->xcd_share_max = (float)*std::max_element(h->xw, h->xw + 8);
-            if (mean > 0) {
-                double sum = 0;
-                for (int x = 0; x < 8; ++x) {
-                    h->xw[x] *= std::sqrt(mean / std::max(dur[x], 1.0));   // damped: half the correction per search
-                    h->xw[x] = std::min(1.5, std::max(0.6, h->xw[x]));
-                    sum += h->xw[x];
-                }
-                for (int x = 0; x < 8; ++x) h->xw[x] *= 8.0 / sum;
-            }
-        }
-        if (n_exact > 0 && !c_bad && depth == 0 && h->retry) {
-            // Overflow means "far more rows above the sampled threshold than expected": similar rows stored together
-            // (chunks of one document) that the sparse sample missed. Before paying the exact full scan (one fp32 pass over
-            // the corpus per 4 queries), give exactly these queries one more MFMA pass as a small, HBM-bound batch with a
-            // denser sample and larger segments; what overflows again goes to the exact scan inside that call.
-            const int m = n_exact, kk = std::max(k, 1);
-            RDX_TRY(h->r_list.ensure((size_t)m * 4));
-            RDX_TRY(h->r_q.ensure((size_t)m * h->dim * 4));
-            RDX_TRY(h->r_s.ensure((size_t)m * kk * 4));
-            RDX_TRY(h->r_r.ensure((size_t)m * kk * 8));
-            RDX_TRY(h->r_c.ensure((size_t)m * 4));
-            HIP_TRY(hipMemcpyAsync(h->r_list.p, h->exact_list.p, (size_t)m * 4, hipMemcpyDeviceToDevice, st));
-            // from the index's own normalised copy (qhat), not from the caller's buffer: an asynchronous caller may have reused
-            // that since (include/rdx.h "Lifetimes"); the nested search stores these rows verbatim, so its scores have the same bits
-            hipLaunchKernelGGL(k_gather_queries, dim3((m + 3) / 4), dim3(256), 0, st, h->qhat.as<float>(), h->r_list.as<int32_t>(), m, h->dim,
-                               h->r_q.as<float>());
-            HIP_TRY(hipGetLastError());
-            rdx_search_stats sub = {};
-            RDX_TRY(search_chunk(h, h->r_q.as<float>(), m, k, d_allow, h->r_s.as<float>(), h->r_r.as<int64_t>(), h->r_c.as<int32_t>(), st,
-                                 &sub, 1));
-            hipLaunchKernelGGL(k_scatter_topk, dim3(m), dim3(64), 0, st, h->r_s.as<float>(), h->r_r.as<int64_t>(), h->r_c.as<int32_t>(),
-                               h->r_list.as<int32_t>(), m, k, d_score, d_row, d_count);
-            HIP_TRY(hipGetLastError());
-            if (ps.d_flags) HIP_TRY(hipMemsetAsync(ps.d_flags, 0, 16, st));   // the partial is complete now
-            HIP_TRY(hipStreamSynchronize(st));   // rdx_search returns with the stream drained
-            acc_stats->retried_queries += m;
-            acc_stats->emitted += sub.emitted;
-            acc_stats->rescored += sub.rescored;
-            n_exact = (int)sub.exact_queries;
-        } else if (n_exact > 0 && !c_bad) {
-            RDX_TRY(run_exact(h, h->exact_list.as<int32_t>(), n_exact, k, d_allow, d_score, d_row, d_count, st));
-            if (ps.d_flags) HIP_TRY(hipMemsetAsync(ps.d_flags, 0, 16, st));
+    if (!h->ctr_ready) {   // zeroed once; afterwards the k_finish of every search leaves it zeroed for the next one
+        HIP_TRY(hipMemsetAsync(h->ctr.p, 0, sizeof(RefineCounters), st));
+        h->ctr_ready = true;
+    }
+    int* d_bad = reinterpret_cast<int*>(h->ctr.as<char>() + offsetof(RefineCounters, bad));
+    *seq = ++h->seq;
+    mark(h, p, st, 0);
+    hipLaunchKernelGGL(k_normalize<true>, dim3((int)((p.nq_pad + 3) / 4)), dim3(256), 0, st, io.queries, (const uint16_t*)nullptr, p.nq, h->dim,
+                       (const int64_t*)nullptr, (int64_t)0, MasterView{h->qhat.as<float>(), nullptr, nullptr}, h->qshadow.as<_Float16>(), h->ksteps, h->scale(),
+                       d_bad, (int64_t)p.nq_pad, p.depth > 0 ? 1 : 0);   // depth 1: the rows ARE normalised queries (gathered from qhat): kept bit for bit
+    HIP_TRY(hipGetLastError());
+    mark(h, p, st, 1);
+
+    const FinishArgs fin = finish_args(h, p, io, *seq);
+    if (p.exact_only) {
+        for (int i = 2; i <= 3; ++i) mark(h, p, st, i);   // events 3..4 bracket the dominant kernels of this path too (K5a + K5b)
+        if ((size_t)p.nq_pad * 4 > h->iota.bytes) {   // identity query list, uploaded once (grow-only), not per search
+            RDX_TRY(h->iota.ensure((size_t)p.nq_pad * 4));
+            const size_t cnt = h->iota.bytes / 4;
+            std::vector<int32_t> io_list(cnt);
+            for (size_t i = 0; i < cnt; ++i) io_list[i] = (int32_t)i;
+            HIP_TRY(hipMemcpyAsync(h->iota.p, io_list.data(), cnt * 4, hipMemcpyHostToDevice, st));
             HIP_TRY(hipStreamSynchronize(st));
         }
-        acc_stats->scan_main_launch_rows = h->rows;
-        acc_stats->scan_main_launch_queries = nq;
+        RDX_TRY(run_exact(h, h->iota.as<int32_t>(), (int)p.nq, p.k, io.allow, io.score, io.row, io.count, st, p.prof == 3,
+                          h->fuse_finish ? &fin : nullptr));
+        for (int i = 4; i <= 5; ++i) mark(h, p, st, i);
+    } else {
+        RDX_TRY(enqueue_scan(h, p, io, st, h->fuse_finish ? fin : FinishArgs{}));
     }
-    mark(6);
-    if (c_bad) return fail(RDX_ERR_INVALID, "query embeddings contain NaN or Inf");
-    if (prof_all) HIP_TRY(hipEventSynchronize(h->ev[6]));
+    if (!h->fuse_finish) {
+        hipLaunchKernelGGL(k_finish, dim3(1), dim3(1024), 0, st, fin);
+        HIP_TRY(hipGetLastError());
+    }
+    // large host results: plain copies behind the last kernel (read_mailbox synchronises the stream for them)
+    if (p.big_copy) RDX_TRY(copy_results_to_host(*ho, io.score, io.row, io.count, p.nq, p.k, st));
+    return RDX_OK;
+}
 
-    acc_stats->sample_rows += exact_only ? 0 : sample_rows;
-    acc_stats->emitted += (int64_t)c_emitted;
-    acc_stats->rescored += (int64_t)c_rescored;
-    acc_stats->exact_queries += n_exact;
-    acc_stats->path = exact_only ? 1 : 0;
-    if (prof_all) {
-        float ms[6] = {};
-        for (int i = 0; i < 6; ++i) (void)hipEventElapsedTime(&ms[i], h->ev[i], h->ev[i + 1]);
-        acc_stats->profiled = 1;
-        acc_stats->ms_normalize += ms[0];
-        acc_stats->ms_scan_sample += ms[1];
-        acc_stats->ms_tau += ms[2];
-        acc_stats->ms_scan_main += ms[3];
-        acc_stats->ms_refine += ms[4];
-        acc_stats->ms_exact += ms[5];
+// what the host half keeps of the mailbox: a second-chance pass runs a nested search whose k_finish overwrites it
+struct SearchCounts {
+    unsigned long long emitted = 0, rescored = 0;
+    int bad = 0, n_exact = 0;   // n_exact: queries left to the fallback passes (exact path: all of them)
+    float stamp_ms = 0.f;       // profile = 3: first workgroup start -> last workgroup end of the dominant kernel(s)
+};
+
+// f(b) for every workgroup of the main scan that stamped its times (idle ones, wpx % nqt != 0, return before they stamp)
+template <class F>
+static void for_stamped(const SearchPlan& p, F f) {
+    for (int b = 0; b < p.grid; ++b)
+        if ((b >> 3) < p.G * p.nqt) f(b);
+}
+
+static int read_mailbox(rdx_index* h, const PendingSearch& ps, SearchCounts* c) {
+    const SearchPlan& p = ps.plan;
+    if (p.big_copy) HIP_TRY(hipStreamSynchronize(ps.st));   // pageable D2H copies: complete only after a stream synchronise
+    const int rc = wait_word([&] { return __atomic_load_n(&h->mbox->seq, __ATOMIC_ACQUIRE) == ps.seq; }, ps.st);   // the ONE host wait of a search
+    if (rc == 1) return fail(RDX_ERR_HIP, "internal: the search completed without publishing its mailbox");
+    RDX_TRY(rc);
+    const Mailbox& mb = *h->mbox;
+    *c = {mb.emitted, mb.rescored, mb.bad, p.exact_only ? (int)p.nq : mb.n_exact};
+    if (p.prof == 3) {
+        if (p.exact_only) {
+            if (mb.t_last > mb.t_first) c->stamp_ms = (float)((double)(mb.t_last - mb.t_first) * 1e-5);
+        } else if (p.grid <= 512) {
+            unsigned long long t0 = ~0ull, t1 = 0;
+            for_stamped(p, [&](int b) {
+                t0 = std::min(t0, mb.wg_times[2 * b]);
+                t1 = std::max(t1, mb.wg_times[2 * b + 1]);
+            });
+            if (t1 > t0) c->stamp_ms = (float)((double)(t1 - t0) * 1e-5);
+        }
+    }
+    return RDX_OK;
+}
+
+// the sampling state the next searches start from
+static void adapt_sampling(rdx_index* h, const SearchPlan& p, const SearchCounts& c) {
+    if (p.depth != 0) return;
+    if (h->mbox->spec_fail > 0) h->spec_backoff = 64;   // a speculative threshold was too high: provable thresholds for a while
+    // three times the candidates a random corpus would emit: the corpus is clustered — a denser threshold sample for the next searches
+    // (plan_search; re-examined every 256 searches: the denser sample's own emission is what then keeps it on)
+    if (!p.exact_only && p.expected_per_query > 0.0) {
+        const double per_q = (double)c.emitted / (double)std::max<int64_t>(p.nq, 1);
+        if (per_q > (h->dense_sample > 0 ? 1.5 : 3.0) * p.expected_per_query) h->dense_sample = 256;
+        else if (h->dense_sample > 0) --h->dense_sample;
+    }
+}
+
+// the stamps arrived with the counters: re-weight the XCD shares for the next search
+static void reweight_xcds(rdx_index* h, const SearchPlan& p, rdx_search_stats* acc) {
+    const unsigned long long* wt = h->mbox->wg_times;
+    unsigned long long t0 = ~0ull, tx[8] = {}, lo[8];
+    std::fill(lo, lo + 8, ~0ull);
+    for_stamped(p, [&](int b) {
+        t0 = std::min(t0, wt[2 * b]);
+        tx[b & 7] = std::max(tx[b & 7], wt[2 * b + 1]);
+        lo[b & 7] = std::min(lo[b & 7], wt[2 * b + 1]);
+    });
+    double dur[8], mean = 0;
+    for (int x = 0; x < 8; ++x) mean += (dur[x] = (double)(tx[x] - t0)) / 8.0;
+    if (std::getenv("RDX_DEBUG_XCD")) {   // developer (tools/xcd_spread.py): when each XCD's last (first) workgroup ended, ms after the first start
+        std::fprintf(stderr, "xcd end ms:");
+        for (int x = 0; x < 8; ++x) std::fprintf(stderr, " %.3f(%.3f)", dur[x] * 1e-5, (double)(lo[x] - t0) * 1e-5);
+        std::fprintf(stderr, "\n");
+    }
+    acc->xcd_finish_spread_ms = (float)((*std::max_element(dur, dur + 8) - *std::min_element(dur, dur + 8)) * 1e-5);   // 100 MHz ticks
+    acc->xcd_share_min = (float)*std::min_element(h->xw, h->xw + 8);
+    acc->xcd_share_max = (float)*std::max_element(h->xw, h->xw + 8);
+    if (mean > 0) {
+        double sum = 0;
+        for (int x = 0; x < 8; ++x) {
+            h->xw[x] *= std::sqrt(mean / std::max(dur[x], 1.0));   // damped: half the correction per search
+            h->xw[x] = std::min(1.5, std::max(0.6, h->xw[x]));
+            sum += h->xw[x];
+        }
+        for (int x = 0; x < 8; ++x) h->xw[x] *= 8.0 / sum;
+    }
+}
+
+static int search_chunk(rdx_index* h, const SearchIO& io, int64_t nq, int k, hipStream_t st, rdx_search_stats* acc, int depth,
+                        HostOut* ho, bool defer);
+
+// The *n_exact queries whose candidate segments overflowed (listed in exact_list) get their results rewritten: by a second-chance
+// search (caller's batch, option retry) or the exact full scan. *n_exact = the queries the exact scan served in the end.
+static int redo_overflowed(rdx_index* h, const PendingSearch& ps, int* n_exact, rdx_search_stats* acc) {
+    const SearchPlan& p = ps.plan;
+    const hipStream_t st = ps.st;
+    if (p.depth == 0 && h->retry) {
+        // Overflow means "far more rows above the sampled threshold than expected": similar rows stored together
+        // (chunks of one document) that the sparse sample missed. Before paying the exact full scan (one fp32 pass over
+        // the corpus per 4 queries), give exactly these queries one more MFMA pass as a small, HBM-bound batch with a
+        // denser sample and larger segments; what overflows again goes to the exact scan inside that call.
+        const int m = *n_exact, kk = std::max(p.k, 1);
+        RDX_TRY(h->r_list.ensure((size_t)m * 4));
+        RDX_TRY(h->r_q.ensure((size_t)m * h->dim * 4));
+        RDX_TRY(h->r_s.ensure((size_t)m * kk * 4));
+        RDX_TRY(h->r_r.ensure((size_t)m * kk * 8));
+        RDX_TRY(h->r_c.ensure((size_t)m * 4));
+        HIP_TRY(hipMemcpyAsync(h->r_list.p, h->exact_list.p, (size_t)m * 4, hipMemcpyDeviceToDevice, st));
+        // from the index's own normalised copy (qhat), not from the caller's buffer: an asynchronous caller may have reused
+        // that since (include/rdx.h "Lifetimes"); the nested search stores these rows verbatim, so its scores have the same bits
+        hipLaunchKernelGGL(k_gather_queries, dim3((m + 3) / 4), dim3(256), 0, st, h->qhat.as<float>(), h->r_list.as<int32_t>(), m, h->dim,
+                           h->r_q.as<float>());
+        HIP_TRY(hipGetLastError());
+        rdx_search_stats sub = {};
+        const SearchIO sub_io = {h->r_q.as<float>(), ps.io.allow, h->r_s.as<float>(), h->r_r.as<int64_t>(), h->r_c.as<int32_t>(), nullptr};
+        RDX_TRY(search_chunk(h, sub_io, m, p.k, st, &sub, 1, nullptr, false));
+        hipLaunchKernelGGL(k_scatter_topk, dim3(m), dim3(64), 0, st, h->r_s.as<float>(), h->r_r.as<int64_t>(), h->r_c.as<int32_t>(),
+                           h->r_list.as<int32_t>(), m, p.k, ps.io.score, ps.io.row, ps.io.count);
+        HIP_TRY(hipGetLastError());
+        acc->retried_queries += m;
+        acc->emitted += sub.emitted;
+        acc->rescored += sub.rescored;
+        *n_exact = (int)sub.exact_queries;
+    } else {
+        RDX_TRY(run_exact(h, h->exact_list.as<int32_t>(), *n_exact, p.k, ps.io.allow, ps.io.score, ps.io.row, ps.io.count, st));
+    }
+    if (ps.io.flags) HIP_TRY(hipMemsetAsync(ps.io.flags, 0, 16, st));   // the partial is complete now
+    HIP_TRY(hipStreamSynchronize(st));   // rdx_search returns with the stream drained
+    return RDX_OK;
+}
+
+// the search's counters and, with option "profile", its times into the caller's statistics
+static int accumulate_stats(rdx_index* h, const SearchPlan& p, const SearchCounts& c, int n_exact, rdx_search_stats* acc) {
+    if (p.prof == 1) HIP_TRY(hipEventSynchronize(h->ev[6]));
+    acc->sample_rows += p.sample_rows;
+    acc->emitted += (int64_t)c.emitted;
+    acc->rescored += (int64_t)c.rescored;
+    acc->exact_queries += n_exact;
+    acc->path = p.exact_only ? 1 : 0;
+    if (p.prof == 1) {
+        float* const dst[6] = {&acc->ms_normalize, &acc->ms_scan_sample, &acc->ms_tau, &acc->ms_scan_main, &acc->ms_refine, &acc->ms_exact};
+        for (int i = 0; i < 6; ++i) {
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, h->ev[i], h->ev[i + 1]);
+            *dst[i] += ms;
+        }
+        acc->profiled = 1;
         float tot = 0;
         (void)hipEventElapsedTime(&tot, h->ev[0], h->ev[6]);
-        acc_stats->ms_total += tot;
-    } else if (prof_main) {
+        acc->ms_total += tot;
+    } else if (p.prof == 2) {
         float ms = 0;
         // non-exact path: both completed (the mailbox came after them in the stream). Exact path: ev[4] sits right behind the
         // kernel whose last block published the mailbox: wait for it (microseconds)
-        if (exact_only) (void)hipEventSynchronize(h->ev[4]);
+        if (p.exact_only) (void)hipEventSynchronize(h->ev[4]);
         (void)hipEventElapsedTime(&ms, h->ev[3], h->ev[4]);
-        acc_stats->profiled = 2;
-        if (exact_only) acc_stats->ms_exact += ms;   // exact path: K5a + K5b
-        else acc_stats->ms_scan_main += ms;
-    } else if (prof_stamps) {
-        // first workgroup start -> last workgroup end of the dominant kernel(s), from the kernels' own 100 MHz stamps
-        acc_stats->profiled = 3;
-        acc_stats->ms_exact += stamp_ms_exact;
-        acc_stats->ms_scan_main += stamp_ms_main;
+        acc->profiled = 2;
+        if (p.exact_only) acc->ms_exact += ms;   // exact path: K5a + K5b
+        else acc->ms_scan_main += ms;
+    } else if (p.prof == 3) {
+        acc->profiled = 3;
+        if (p.exact_only) acc->ms_exact += c.stamp_ms;
+        else acc->ms_scan_main += c.stamp_ms;
     }
     return RDX_OK;
+}
+
+// the host half of a search (see PendingSearch). *redone (if given) = a fallback pass rewrote results after k_finish.
+static int complete_search(rdx_index* h, const PendingSearch& ps, rdx_search_stats* acc, HostOut* ho, bool* redone) {
+    const SearchPlan& p = ps.plan;
+    if (redone) *redone = false;
+    SearchCounts c;
+    RDX_TRY(read_mailbox(h, ps, &c));
+    adapt_sampling(h, p, c);
+    if (h->mbox->oob) return fail(RDX_ERR_STATE, "internal: the scan computed a corpus address outside the scan copy (RDX_CHECK_BOUNDS build)");
+    if (p.ride) {
+        if (p.k > 0) {
+            std::memcpy(ho->row, h->pin_out, p.b_r);
+            std::memcpy(ho->score, h->pin_out + p.b_r, p.b_s);
+        }
+        std::memcpy(ho->count, h->pin_out + p.b_r + p.b_s, p.b_c);
+    }
+    int n_exact = c.n_exact;
+    if (!p.exact_only) {
+        const bool redo = n_exact > 0 && !c.bad;
+        if (redo && redone) *redone = true;
+        if (n_exact > 0 && ho) ho->stale = true;   // a fallback pass rewrites some of the rows copied above
+        if (p.balance) reweight_xcds(h, p, acc);
+        if (redo) RDX_TRY(redo_overflowed(h, ps, &n_exact, acc));
+        acc->scan_main_launch_rows = h->rows;
+        acc->scan_main_launch_queries = p.nq;
+    }
+    mark(h, p, ps.st, 6);
+    if (c.bad) return fail(RDX_ERR_INVALID, "query embeddings contain NaN or Inf");
+    return accumulate_stats(h, p, c, n_exact, acc);
+}
+
+// One launch of a search (nq <= 4096) at `depth`: plan, enqueue, and complete it unless `defer` (rdx_search_async: left in h->pending).
+// The counter block is zeroed once and afterwards by the k_finish of every search. A search that leaves early (an internal
+// check, allocation failure, launch error) may have skipped its k_finish: the next search zeroes the block itself again.
+static int search_chunk(rdx_index* h, const SearchIO& io, int64_t nq, int k, hipStream_t st, rdx_search_stats* acc, int depth,
+                        HostOut* ho, bool defer) {
+    SearchPlan plan;
+    unsigned long long seq = 0;
+    int rc = plan_search(*h, nq, k, depth, ho != nullptr, &plan);
+    if (rc == RDX_OK) rc = enqueue_search(h, plan, io, ho, st, &seq);
+    if (rc == RDX_OK) {
+        if (!plan.exact_only) acc->tau_rank = (float)plan.k_sel;
+        const PendingSearch ps = {true, plan, io, st, seq, defer ? *acc : rdx_search_stats{}};
+        if (defer) h->pending = ps;
+        else rc = complete_search(h, ps, acc, ho, nullptr);
+    }
+    if (rc != RDX_OK) h->ctr_ready = false;
+    return rc;
 }
 
 // run the host half of a search left pending by rdx_search_async (call with h->mu held)
@@ -1682,33 +1693,48 @@ static int finish_pending(rdx_index* h, bool* redone) {
     PendingSearch ps = h->pending;
     h->pending.active = false;
     RDX_TRY(set_device(h));
-    rdx_search_stats s = ps.stats;
-    const int rc = complete_chunk(h, ps, &s, nullptr, redone);
-    h->stats = s;
+    h->stats = ps.stats;
+    const int rc = complete_search(h, ps, &h->stats, nullptr, redone);
+    if (rc != RDX_OK) h->ctr_ready = false;   // (see search_chunk)
     return rc;
+}
+
+// what rdx_search and rdx_search_async do first (h->mu held): the pending search completes (scratch buffers are shared), the
+// device is selected, the profiling events exist, and the statistics start from the call's shape
+static int begin_search(rdx_index* h, int64_t nq, int k, rdx_search_stats* s) {
+    RDX_TRY(finish_pending(h, nullptr));
+    RDX_TRY(set_device(h));
+    if (h->profile && !h->ev_ok) {
+        for (auto& e : h->ev) HIP_TRY(hipEventCreate(&e));
+        h->ev_ok = true;
+    }
+    *s = {};
+    s->nq = nq;
+    s->k = k;
+    s->rows = h->rows;
+    return RDX_OK;
+}
+
+static int check_mask(const rdx_index* h, const rdx_mask* mask, const char* who) {
+    if (mask && (mask->device != h->device || mask->rows != h->rows))
+        return fail(RDX_ERR_STATE, std::string(who) + ": the mask was made for " + std::to_string(mask->rows) + " rows on device " +
+                                       std::to_string(mask->device) + ", the index now holds " + std::to_string(h->rows) +
+                                       " (a mask does not outlive a write to the index)");
+    return RDX_OK;
 }
 
 // allow_resident: allow_bits is already device memory whatever `space` says (a resident rdx_mask)
 static int search_impl(rdx_index* h, const float* queries, int64_t nq, int k, const uint32_t* allow_bits, bool allow_resident,
                        float* out_score, int64_t* out_row, int32_t* out_count, int space, void* stream) {
-    if (!h) return fail(RDX_ERR_INVALID, "rdx_search: null index");
     if (nq < 0 || k < 0) return fail(RDX_ERR_INVALID, "rdx_search: nq and k must be >= 0");
     if (k > SELECT_MAX_K) return fail(RDX_ERR_INVALID, "rdx_search: k larger than " + std::to_string(SELECT_MAX_K) + " is not supported");
     if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
     if (nq == 0) return RDX_OK;
     if (!queries || !out_count || (k > 0 && (!out_score || !out_row))) return fail(RDX_ERR_INVALID, "rdx_search: null pointer");
-    RDX_TRY(finish_pending(h, nullptr));   // scratch buffers are shared: an asynchronous search completes first
-    RDX_TRY(set_device(h));
+    rdx_search_stats s;
+    RDX_TRY(begin_search(h, nq, k, &s));
     // device pointers: the caller's stream as given (NULL = the default stream the caller produced its inputs on)
     hipStream_t st = (space == RDX_DEVICE || stream) ? (hipStream_t)stream : h->own_stream;
-    if (h->profile && !h->ev_ok) {
-        for (auto& e : h->ev) HIP_TRY(hipEventCreate(&e));
-        h->ev_ok = true;
-    }
-    rdx_search_stats s = {};
-    s.nq = nq;
-    s.k = k;
-    s.rows = h->rows;
 
     const uint32_t* d_allow = allow_bits;
     const size_t mask_words = (size_t)((h->rows + 31) / 32);
@@ -1724,29 +1750,23 @@ static int search_impl(rdx_index* h, const float* queries, int64_t nq, int k, co
     const int kk = std::max(k, 1);
     for (int64_t q0 = 0; q0 < nq; q0 += CHUNK) {
         const int64_t m = std::min(CHUNK, nq - q0);
-        const float* d_q = queries + (size_t)q0 * h->dim;
-        float* d_s = out_score ? out_score + (size_t)q0 * k : nullptr;
-        int64_t* d_r = out_row ? out_row + (size_t)q0 * k : nullptr;
-        int32_t* d_c = out_count + q0;
+        SearchIO io = {queries + (size_t)q0 * h->dim, d_allow, out_score ? out_score + (size_t)q0 * k : nullptr,
+                       out_row ? out_row + (size_t)q0 * k : nullptr, out_count + q0, nullptr};
+        HostOut ho = {io.score, io.row, io.count, false};
         if (space == RDX_HOST) {
             RDX_TRY(h->qraw.ensure((size_t)m * h->dim * 4));
             RDX_TRY(h->o_score.ensure((size_t)m * kk * 4));
             RDX_TRY(h->o_row.ensure((size_t)m * kk * 8));
             RDX_TRY(h->o_count.ensure((size_t)m * 4));
-            HIP_TRY(hipMemcpyAsync(h->qraw.p, d_q, (size_t)m * h->dim * 4, hipMemcpyHostToDevice, st));
-            d_q = h->qraw.as<float>();
-            d_s = h->o_score.as<float>();
-            d_r = h->o_row.as<int64_t>();
-            d_c = h->o_count.as<int32_t>();
+            HIP_TRY(hipMemcpyAsync(h->qraw.p, io.queries, (size_t)m * h->dim * 4, hipMemcpyHostToDevice, st));
+            io.queries = h->qraw.as<float>();
+            io.score = h->o_score.as<float>();
+            io.row = h->o_row.as<int64_t>();
+            io.count = h->o_count.as<int32_t>();
         }
-        HostOut ho = {out_score ? out_score + (size_t)q0 * k : nullptr, out_row ? out_row + (size_t)q0 * k : nullptr, out_count + q0, false};
-        RDX_TRY(search_chunk(h, d_q, m, k, d_allow, d_s, d_r, d_c, st, &s, 0, space == RDX_HOST ? &ho : nullptr));
+        RDX_TRY(search_chunk(h, io, m, k, st, &s, 0, space == RDX_HOST ? &ho : nullptr, false));
         if (space == RDX_HOST && ho.stale) {
-            if (k > 0) {
-                HIP_TRY(hipMemcpyAsync(ho.score, d_s, (size_t)m * k * 4, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipMemcpyAsync(ho.row, d_r, (size_t)m * k * 8, hipMemcpyDeviceToHost, st));
-            }
-            HIP_TRY(hipMemcpyAsync(ho.count, d_c, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+            RDX_TRY(copy_results_to_host(ho, io.score, io.row, io.count, m, k, st));
             HIP_TRY(hipStreamSynchronize(st));
         }
     }
@@ -1767,20 +1787,11 @@ extern "C" int rdx_search_async(rdx_index* h, const float* queries, int64_t nq, 
     if (nq < 1 || nq > 4096 || k < 0 || k > SELECT_MAX_K) return fail(RDX_ERR_INVALID, "rdx_search_async: 1 <= nq <= 4096, 0 <= k <= " + std::to_string(SELECT_MAX_K));
     if (!queries || !out_count || (k > 0 && (!out_score || !out_row))) return fail(RDX_ERR_INVALID, "rdx_search_async: null pointer");
     std::lock_guard<std::mutex> lk(h->mu);
-    if (mask && (mask->device != h->device || mask->rows != h->rows))
-        return fail(RDX_ERR_STATE, "rdx_search_async: the mask was made for another state of the index");
-    RDX_TRY(finish_pending(h, nullptr));
-    RDX_TRY(set_device(h));
-    if (h->profile && !h->ev_ok) {
-        for (auto& e : h->ev) HIP_TRY(hipEventCreate(&e));
-        h->ev_ok = true;
-    }
-    rdx_search_stats s = {};
-    s.nq = nq;
-    s.k = k;
-    s.rows = h->rows;
-    return search_chunk(h, queries, nq, k, mask ? mask->words.as<uint32_t>() : nullptr, out_score, out_row, out_count, (hipStream_t)stream, &s, 0,
-                        nullptr, true, out_flags);
+    RDX_TRY(check_mask(h, mask, "rdx_search_async"));
+    rdx_search_stats s;
+    RDX_TRY(begin_search(h, nq, k, &s));
+    const SearchIO io = {queries, mask ? mask->words.as<uint32_t>() : nullptr, out_score, out_row, out_count, out_flags};
+    return search_chunk(h, io, nq, k, (hipStream_t)stream, &s, 0, nullptr, true);
 }
 
 extern "C" int rdx_search_wait(rdx_index* h, int* redone) {
@@ -1834,10 +1845,7 @@ extern "C" int rdx_search_masked(rdx_index* h, const float* queries, int64_t nq,
                                  int64_t* out_row, int32_t* out_count, int space, void* stream) {
     if (!h) return fail(RDX_ERR_INVALID, "rdx_search_masked: null index");
     std::lock_guard<std::mutex> lk(h->mu);
-    if (mask && (mask->device != h->device || mask->rows != h->rows))
-        return fail(RDX_ERR_STATE, "rdx_search_masked: the mask was made for " + std::to_string(mask->rows) + " rows on device " +
-                                       std::to_string(mask->device) + ", the index now holds " + std::to_string(h->rows) +
-                                       " (a mask does not outlive a write to the index)");
+    RDX_TRY(check_mask(h, mask, "rdx_search_masked"));
     return search_impl(h, queries, nq, k, mask ? mask->words.as<uint32_t>() : nullptr, true, out_score, out_row, out_count, space, stream);
 }
 
@@ -1927,11 +1935,7 @@ extern "C" int rdx_merge_topk(int device, const float* part_score, const int64_t
         if (space == RDX_DEVICE && n_parts > 2) HIP_TRY(hipStreamSynchronize(st));   // the intermediates are freed on return
     }
     if (space == RDX_HOST) {
-        if (k > 0) {
-            HIP_TRY(hipMemcpyAsync(out_score, d_os, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(out_row, d_or, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
-        }
-        HIP_TRY(hipMemcpyAsync(out_count, d_oc, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+        RDX_TRY(copy_results_to_host(HostOut{out_score, out_row, out_count, false}, d_os, d_or, d_oc, nq, k, st));
         HIP_TRY(hipStreamSynchronize(st));
         for (DevBuf* b : {&ps, &pr, &pc, &os, &orow, &oc}) b->release();
     }
@@ -1941,15 +1945,8 @@ extern "C" int rdx_merge_topk(int device, const float* part_score, const int64_t
 extern "C" int rdx_signal_create(int device, rdx_signal** out) {
     if (!out) return fail(RDX_ERR_INVALID, "rdx_signal_create: null out pointer");
     HIP_TRY(hipSetDevice(device));
-    void* p = nullptr;
-    HIP_TRY(hipHostMalloc(&p, 64, hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(p, 0, 64);
-    void* d = nullptr;
-    hipError_t e = hipHostGetDevicePointer(&d, p, 0);
-    if (e != hipSuccess) {
-        (void)hipHostFree(p);
-        return fail(RDX_ERR_HIP, std::string("hipHostGetDevicePointer: ") + hipGetErrorString(e));
-    }
+    void *p = nullptr, *d = nullptr;
+    RDX_TRY(map_pinned(64, &p, &d));
     rdx_signal* s = new rdx_signal();
     s->device = device;
     s->host = reinterpret_cast<unsigned long long*>(p);

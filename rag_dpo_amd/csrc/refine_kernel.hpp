@@ -68,7 +68,7 @@ __device__ __forceinline__ void finish_body(const FinishArgs& f) {   // all thre
     __syncthreads();
     if (threadIdx.x == 0) {
         // rdx_search_async(out_flags): "this partial is incomplete, the host half will redo some queries" — the word travels with
-        // the packed partial through the all-gather (include/rdx.h); the same condition complete_chunk reports as *redone
+        // the packed partial through the all-gather (include/rdx.h); the same condition complete_search reports as *redone
         if (f.out_flags) {
             f.out_flags[0] = (f.may_redo && ctr->n_exact > 0 && !ctr->bad) ? 1 : 0;
             f.out_flags[1] = 0;
