@@ -211,6 +211,31 @@ int rdx_enc_attention_small_f16(int device, const void* qkv, const int32_t* tok_
 int rdx_enc_layernorm_rows_f16(int device, const void* s, const void* gamma, const void* beta, float eps, int rows,
                                int hidden, float* out, void* stream);
 
+/* Cross-encoder reranker --------------------------------------------------------------------- */
+/* The stage the reference runs on every question between retrieval and generation: CrossEncoderReranker.rerank
+ * (src/rag/reranker.py:112-216, called from src/rag/pipeline.py:221-262) — sentence-transformers' CrossEncoder.predict on the
+ * (question, chunk) pairs, the topic boost, a stable sort and the min_score / keep-3 filter. rag_dpo_amd/reranker.py runs the
+ * transformer backbone and calls these two on the pairs' <s> rows. Device pointers, enqueued on `stream`, nothing synchronised,
+ * no allocation (both can be captured in a graph); no float atomics: the same inputs give bit-identical outputs on every call.
+ *
+ * rdx_rerank_head_f16: the XLMRobertaForSequenceClassification head with num_labels = 1, then a sigmoid:
+ *     scores[p] = 1 / (1 + exp(-(w_out . tanh(w_dense cls[p] + b_dense) + b_out)))
+ *   cls fp32 [n][hidden] (16-byte aligned), w_dense fp16 [hidden][hidden] (row = output feature, 16-byte aligned), b_dense and
+ *   w_out fp16 [hidden], b_out fp16 [1], scores fp32 [n]. 1 <= n <= 1024, hidden a multiple of 64 in [64, 4096].
+ *   workspace: RDX_RERANK_WORKSPACE_BYTES(n, hidden) bytes of device memory (8-byte aligned), scratch owned by the caller: the
+ *   per-workgroup partial logits, summed in a fixed order by a second launch. Arithmetic: each z = w_dense cls + b_dense in fp32
+ *   (fma in a fixed order), tanh, the w_out products, the logit sum and the sigmoid in fp64, the score rounded once to fp32.
+ * rdx_rerank_select: final[p] = (double)scores[p], plus boosts[p] when boosts != NULL and boosts[p] > 0 (one fp64 add);
+ *   order int32 [n] = the candidates by final descending, ties in input order (Python's stable sort(reverse=True); NaN last);
+ *   final_score fp64 [n] in input order; *count = min(top_k, #{final >= min_score}), or keep_min when that is smaller and
+ *   n >= keep_min (the reference keeps 3 even when top_k < 3). The reranked result is order[0 .. *count). 1 <= n <= 1024,
+ *   top_k >= 0, keep_min >= 0. scores need not come from rdx_rerank_head_f16. */
+#define RDX_RERANK_WORKSPACE_BYTES(n, hidden) ((size_t)((hidden) / 8) * (size_t)(n) * 8u)
+int rdx_rerank_head_f16(int device, const float* cls, int n, int hidden, const void* w_dense, const void* b_dense,
+                        const void* w_out, const void* b_out, double* workspace, float* scores, void* stream);
+int rdx_rerank_select(int device, const float* scores, const double* boosts, int n, int top_k, double min_score,
+                      int keep_min, int32_t* order, double* final_score, int32_t* count, void* stream);
+
 /* `collection.query(query_embeddings=, n_results=k, where=)` (reference
  * src/rag/retriever.py:215-220,380-385; create_chromadb_index.py:405-408,435-439).
  *   queries     [nq][dim] raw fp32 (normalised on the device like corpus rows)

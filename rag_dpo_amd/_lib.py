@@ -17,6 +17,7 @@ RDX_OK, RDX_ERR_INVALID, RDX_ERR_HIP, RDX_ERR_NOMEM, RDX_ERR_STATE = 0, 1, 2, 3,
 RDX_HOST, RDX_DEVICE = 0, 1
 ABI_VERSION = 3          # include/rdx.h RDX_ABI_VERSION
 PACKED_FLAGS = 4         # include/rdx.h RDX_PACKED_FLAGS: int32 words behind the counts of a packed partial
+RERANK_FEATURES = 8      # include/rdx.h RDX_RERANK_WORKSPACE_BYTES: output features per head workgroup
 
 
 class RdxUnavailable(RuntimeError):
@@ -78,6 +79,8 @@ SYMBOLS = {
     "rdx_enc_stage_f16": (_i, [_i, _vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "rdx_enc_attention_small_f16": (_i, [_i, _vp, _vp, _i, _i, _i, ctypes.c_float, _vp, _vp]),
     "rdx_enc_layernorm_rows_f16": (_i, [_i, _vp, _vp, _vp, ctypes.c_float, _i, _i, _vp, _vp]),
+    "rdx_rerank_head_f16": (_i, [_i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rdx_rerank_select": (_i, [_i, _vp, _vp, _i, _i, ctypes.c_double, _i, _vp, _vp, _vp, _vp]),
     "rdx_search": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "rdx_mask_create": (_i, [_vp, _vp, _i, ctypes.POINTER(_vp)]),
     "rdx_mask_destroy": (_i, [_vp]),

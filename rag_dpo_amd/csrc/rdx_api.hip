@@ -26,6 +26,7 @@
 #include "enc_small.hpp"
 #include "k_rows.hpp"
 #include "refine_kernel.hpp"
+#include "rerank_kernel.hpp"
 #include "scan_kernel.hpp"
 
 using namespace rdx;
@@ -922,6 +923,51 @@ extern "C" int rdx_enc_gelu_f16(int device, void* x, int64_t n, void* stream) {
     return RDX_OK;
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// cross-encoder reranker: classification head and selection (rerank_kernel.hpp)
+// ------------------------------------------------------------------------------------------------
+extern "C" int rdx_rerank_head_f16(int device, const float* cls, int n, int hidden, const void* w_dense, const void* b_dense,
+                                   const void* w_out, const void* b_out, double* workspace, float* scores, void* stream) {
+    if (n < 1 || n > RERANK_MAX_N) return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: n must be in [1, 1024]");
+    if (hidden < 64 || hidden > RERANK_MAX_HIDDEN || hidden % 64)
+        return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: hidden must be a multiple of 64 in [64, 4096]");
+    if (!cls || !w_dense || !b_dense || !w_out || !b_out || !workspace || !scores) return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: null pointer");
+    if (((uintptr_t)cls | (uintptr_t)w_dense) & 15) return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: cls and w_dense must be 16-byte aligned");
+    if (((uintptr_t)b_dense | (uintptr_t)w_out | (uintptr_t)b_out) & 1 || ((uintptr_t)workspace & 7) || ((uintptr_t)scores & 3))
+        return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: misaligned pointer");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = hidden / RERANK_FEATURES;
+    const dim3 grid((unsigned)blocks, (unsigned)((n + RERANK_ROWS_PER_BLOCK - 1) / RERANK_ROWS_PER_BLOCK));
+    const size_t lds = (size_t)RERANK_FEATURES * hidden * sizeof(_Float16);   // <= 64 KiB at hidden 4096
+    RDX_TRY(enc_dynamic_lds(device, (const void*)k_rerank_head, lds));
+    hipLaunchKernelGGL(k_rerank_head, grid, dim3(RERANK_HEAD_THREADS), lds, st, cls, n, hidden, (const _Float16*)w_dense,
+                       (const _Float16*)b_dense, (const _Float16*)w_out, workspace);
+    HIP_TRY(hipGetLastError());
+    const int rows_per_block = RERANK_THREADS / 64;                           // K_R2: one wave per row
+    hipLaunchKernelGGL(k_rerank_combine, dim3((unsigned)((n + rows_per_block - 1) / rows_per_block)), dim3(RERANK_THREADS), 0, st,
+                       (const double*)workspace, n, blocks, (const _Float16*)b_out, scores);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+extern "C" int rdx_rerank_select(int device, const float* scores, const double* boosts, int n, int top_k, double min_score,
+                                 int keep_min, int32_t* order, double* final_score, int32_t* count, void* stream) {
+    if (n < 1 || n > RERANK_MAX_N) return fail(RDX_ERR_INVALID, "rdx_rerank_select: n must be in [1, 1024]");
+    if (top_k < 0) return fail(RDX_ERR_INVALID, "rdx_rerank_select: top_k must be >= 0");
+    if (keep_min < 0) return fail(RDX_ERR_INVALID, "rdx_rerank_select: keep_min must be >= 0");
+    if (!scores || !order || !final_score || !count) return fail(RDX_ERR_INVALID, "rdx_rerank_select: null pointer");
+    if (((uintptr_t)scores & 3) || ((uintptr_t)boosts & 7) || ((uintptr_t)order & 3) || ((uintptr_t)final_score & 7) || ((uintptr_t)count & 3))
+        return fail(RDX_ERR_INVALID, "rdx_rerank_select: misaligned pointer");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_rerank_select: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    hipLaunchKernelGGL(k_rerank_select, dim3(1), dim3(RERANK_MAX_N), 0, (hipStream_t)stream, scores, boosts, n, top_k, min_score,
+                       keep_min, order, final_score, count);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
 
 extern "C" int rdx_l2_normalize(int device, const float* in, int64_t n, int dim, float* out, int space, void* stream) {
     if (n < 0 || (n > 0 && (!in || !out))) return fail(RDX_ERR_INVALID, "rdx_l2_normalize: bad argument");

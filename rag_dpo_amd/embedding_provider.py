@@ -58,15 +58,7 @@ class _HashTokenizer:
         toks = [t.split()[:cap] for t in texts]
         lens = np.fromiter(map(len, toks), dtype=np.int64, count=n)
         words = [w for tk in toks for w in tk]
-        ids = list(map(self._ids.get, words))              # vocabulary lookup at C speed; misses (None) are hashed once
-        if None in ids:
-            for j, v in enumerate(ids):
-                if v is None:
-                    w = words[j]
-                    v = 4 + zlib.crc32(w.encode("utf-8")) % (self.vocab_size - 4)
-                    if len(self._ids) < 1_000_000:
-                        self._ids[w] = v
-                    ids[j] = v
+        ids = self._piece_ids(words)
         width = int(lens.max()) + 2 if n else 2
         inp = np.full((n, width), 1, dtype=np.int64)       # <pad> = 1
         if n:
@@ -76,6 +68,45 @@ class _HashTokenizer:
             inp[row, np.arange(len(words)) - np.repeat(first, lens) + 1] = np.asarray(ids, dtype=np.int64)
             inp[np.arange(n), lens + 1] = 2                # </s>
         att = (np.arange(width)[None, :] < (lens + 2)[:, None]).astype(np.int64)
+        return {"input_ids": torch.from_numpy(inp), "attention_mask": torch.from_numpy(att)}
+
+    def _piece_ids(self, words: List[str]) -> List[int]:
+        ids = list(map(self._ids.get, words))              # vocabulary lookup at C speed; misses (None) are hashed once
+        if None in ids:
+            for j, v in enumerate(ids):
+                if v is None:
+                    w = words[j]
+                    v = 4 + zlib.crc32(w.encode("utf-8")) % (self.vocab_size - 4)
+                    if len(self._ids) < 1_000_000:
+                        self._ids[w] = v
+                    ids[j] = v
+        return ids
+
+    def pairs(self, queries: List[str], texts: List[str], max_length: int):
+        """(query, text) pairs as ONE sequence each, XLM-R's pair layout `<s> q </s></s> d </s>`, cut to max_length tokens
+        longest-first (a token comes off the longer side, off the text on a tie: what the tokenizers library does)."""
+        rows = []
+        budget = max_length - 4
+        for q, d in zip(queries, texts):
+            a, b = q.split(), d.split()
+            la, lb = len(a), len(b)
+            if la + lb > budget:                         # closed form of "drop one from the longer side until it fits"
+                short = min(la, lb)
+                if short * 2 >= budget:
+                    la, lb = (budget + 1) // 2, budget // 2
+                elif la > lb:
+                    la = budget - lb
+                else:
+                    lb = budget - la
+            rows.append((a[:la], b[:lb]))
+        n = len(rows)
+        lens = np.fromiter((len(a) + len(b) + 4 for a, b in rows), dtype=np.int64, count=n)
+        width = int(lens.max()) if n else 4
+        inp = np.full((n, width), 1, dtype=np.int64)       # <pad> = 1
+        for i, (a, b) in enumerate(rows):
+            ids = self._piece_ids(a + b)
+            inp[i, :lens[i]] = [0] + ids[:len(a)] + [2, 2] + ids[len(a):] + [2]
+        att = (np.arange(width)[None, :] < lens[:, None]).astype(np.int64)
         return {"input_ids": torch.from_numpy(inp), "attention_mask": torch.from_numpy(att)}
 
 
