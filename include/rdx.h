@@ -353,6 +353,48 @@ int rdx_bm25_search(rdx_bm25* h, const int64_t* term_offsets, const int32_t* ter
                     const uint32_t* allow_groups, double* out_score, int64_t* out_row, int32_t* out_count, int space,
                     void* stream);
 
+/* Document store and where_document --------------------------------------------------------- */
+/* Chroma's where_document filter (chromadb 1.x `get` / `query` / `delete`): {"$contains": s}, {"$not_contains": s}, and
+ * {"$and": [...]} / {"$or": [...]} over them, nested to any depth; rag_dpo_amd/where_document.py validates the tree and compiles
+ * it into the leaves and the postfix program below. Match rule: case-sensitive, byte-exact substring of the UTF-8 text (exactly
+ * Python's `needle in document`, UTF-8 being self-synchronising). A row without text (len 0) contains nothing; $not_contains is
+ * the complement of $contains, so such a row matches it; rows the caller has deleted are removed through base_bits.
+ *
+ * An rdx_docs holds the rows' text on one device, in the collection's row order. Layout: each row's bytes start on a 16-byte
+ * boundary and are zero-padded to the next one; the row table is (start int64, len int32); the arena ends with at least 64 zero
+ * bytes. The store is independent of an rdx_index (the host keeps the two in step: same rows, same compaction keep lists).
+ *
+ * Calls that change the store (append / replace / compact) and rdx_docs_set_query take host pointers only and are complete on
+ * return; they first wait for the store's last filter / contains call to finish on its stream. The query is set by one host call
+ * and run by rdx_docs_contains / rdx_docs_filter, whose `space` covers their own bitmap pointers: this split keeps the rule that
+ * one `space` says where every pointer of a call lives (the patterns are validated and uploaded once, on the host, whatever
+ * space the bitmaps live in). Arguments are validated before the store handle is used. */
+typedef struct rdx_docs rdx_docs; /* opaque: one document store resident in one GPU's HBM */
+#define RDX_DOCS_MAX_LEAVES 1024  /* patterns per query; the scan tests 32 per pass (LDS-staged, <= 256 bytes) */
+#define RDX_DOCS_OP_NOT (-1)      /* program ops: >= 0 = push leaf i's bitmap; NOT / AND / OR on the top of the stack */
+#define RDX_DOCS_OP_AND (-2)
+#define RDX_DOCS_OP_OR (-3)
+int rdx_docs_create(int device, rdx_docs** out);
+int rdx_docs_destroy(rdx_docs* h);
+/* appends n rows: row i's text is bytes[offsets[i] .. offsets[i+1]) (offsets[0] = 0, non-decreasing; a row < 2^31 - 64 bytes) */
+int rdx_docs_append(rdx_docs* h, const uint8_t* bytes, const int64_t* offsets, int64_t n);
+/* row_ids[i] gets the text bytes[offsets[i] .. offsets[i+1]): written at the arena tail, the old bytes become dead; the arena is
+ * rewritten densely (the rows keep their ids) once dead bytes exceed both the live bytes and 16 MiB */
+int rdx_docs_replace(rdx_docs* h, const int64_t* row_ids, const uint8_t* bytes, const int64_t* offsets, int64_t n);
+/* keeps the rows keep[0 .. n_keep) (strictly ascending: the keep list of rdx_index_compact), renumbered 0 .. n_keep-1 */
+int rdx_docs_compact(rdx_docs* h, const int64_t* keep, int64_t n_keep);
+/* rows; live_bytes = padded bytes of the rows' current text; arena_bytes = padded bytes in use, dead text included */
+int rdx_docs_stats(const rdx_docs* h, int64_t* rows, int64_t* live_bytes, int64_t* arena_bytes);
+/* the query: P leaf patterns, leaf p = pat_bytes[pat_off[p] .. pat_off[p+1]) (pat_off[0] = 0, strictly increasing: no empty
+ * pattern), 1 <= P <= RDX_DOCS_MAX_LEAVES, any length (patterns over 256 bytes take a slower kernel); program: n_ops postfix ops
+ * (n_ops <= 4096, at most 16 stack entries, leaving exactly one; n_ops = 0: leaves only, for rdx_docs_contains) */
+int rdx_docs_set_query(rdx_docs* h, const uint8_t* pat_bytes, const int64_t* pat_off, int P, const int32_t* program, int n_ops);
+/* out_bits [P][ceil(rows/32)] words: bit (r&31) of word p*words + (r>>5) = row r contains leaf p; tail bits zero */
+int rdx_docs_contains(rdx_docs* h, uint32_t* out_bits, int space, void* stream);
+/* out_bits [ceil(rows/32)] = program(leaf bitmaps) AND base_bits (NULL = all rows), tail bits past `rows` zero: the allow_bits
+ * of rdx_search / rdx_mask_create. RDX_DEVICE: enqueued on `stream`, nothing crosses PCIe. */
+int rdx_docs_filter(rdx_docs* h, const uint32_t* base_bits, uint32_t* out_bits, int space, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,8 @@ RDX_HOST, RDX_DEVICE = 0, 1
 ABI_VERSION = 3          # include/rdx.h RDX_ABI_VERSION
 PACKED_FLAGS = 4         # include/rdx.h RDX_PACKED_FLAGS: int32 words behind the counts of a packed partial
 RERANK_FEATURES = 8      # include/rdx.h RDX_RERANK_WORKSPACE_BYTES: output features per head workgroup
+DOCS_OP_NOT, DOCS_OP_AND, DOCS_OP_OR = -1, -2, -3   # include/rdx.h RDX_DOCS_OP_*
+DOCS_MAX_LEAVES = 1024   # include/rdx.h RDX_DOCS_MAX_LEAVES
 
 
 class RdxUnavailable(RuntimeError):
@@ -96,6 +98,15 @@ SYMBOLS = {
     "rdx_bm25_create": (_i, [_i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.POINTER(_vp)]),
     "rdx_bm25_destroy": (_i, [_vp]),
     "rdx_bm25_search": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "rdx_docs_create": (_i, [_i, ctypes.POINTER(_vp)]),
+    "rdx_docs_destroy": (_i, [_vp]),
+    "rdx_docs_append": (_i, [_vp, _vp, _vp, _i64]),
+    "rdx_docs_replace": (_i, [_vp, _vp, _vp, _vp, _i64]),
+    "rdx_docs_compact": (_i, [_vp, _vp, _i64]),
+    "rdx_docs_stats": (_i, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "rdx_docs_set_query": (_i, [_vp, _vp, _vp, _i, _vp, _i]),
+    "rdx_docs_contains": (_i, [_vp, _vp, _i, _vp]),
+    "rdx_docs_filter": (_i, [_vp, _vp, _vp, _i, _vp]),
 }
 
 

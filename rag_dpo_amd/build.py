@@ -27,7 +27,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librdx.so")
 RESOURCES = os.path.join(HERE, "librdx.resources.json")
 SOURCES = ["rdx_api.hip"]
-HEADERS = ["rdx_common.hpp", "k_rows.hpp", "scan_kernel.hpp", "refine_kernel.hpp", "enc_kernels.hpp", "enc_small.hpp", "bm25_kernel.hpp", "rerank_kernel.hpp", "../../include/rdx.h"]
+HEADERS = ["rdx_common.hpp", "k_rows.hpp", "scan_kernel.hpp", "refine_kernel.hpp", "enc_kernels.hpp", "enc_small.hpp", "bm25_kernel.hpp", "rerank_kernel.hpp", "doc_kernel.hpp", "../../include/rdx.h"]
 CHECKERS = ["isa_check.py"]   # part of the recorded hash: a library is only "fresh" if it passed THIS version of the ISA check
 
 
@@ -132,6 +132,10 @@ def build_lib(force: bool = False, verbose: bool = False, extra_flags=(), out: s
         if bad:
             raise RuntimeError("scan kernels spill registers — refused (inline-asm loads may be in flight to a spilled register):\n" +
                                "\n".join(f"  {k}: {v}" for k, v in bad.items()))
+        docs = {k: v for k, v in res.items() if "k_docs" in k}
+        if len(docs) < 4 or any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in docs.values()):
+            raise RuntimeError("the where_document kernels (doc_kernel.hpp) spill or were not found — refused:\n" +
+                               "\n".join(f"  {k}: {v}" for k, v in docs.items()))
         # kernels that are given an occupancy target (amdgpu_waves_per_eu: the latency-bound attention kernel E12) pay for a miss
         # silently, in scratch traffic: refused as well (a variant build with extra flags may spill: it is nobody's product)
         slow = {k: v for k, v in res.items() if "k_enc_attention_mfma" in k and (v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0))}

@@ -7,6 +7,13 @@ Mirrors exactly the part of chromadb's API that RAG-DPO calls:
     collection.count() / delete(ids=) / update(ids=, metadatas=)        ingest_enterprise.py:272, tag_all_chunks.py:215
     client.get_collection / create_collection / delete_collection       app.py:58-59, create_chromadb_index.py:93-130
 Everything that crosses this boundary is plain Python lists/dicts/strs/floats, as with chromadb.
+
+`get`, `query`, `query_device` and `delete` also take chromadb's `where_document` ({"$contains": s}, {"$not_contains": s},
+{"$and": [...]}, {"$or": [...]}; `$regex` is refused): a case-sensitive substring test of the UTF-8 text, intersected with
+`where` (rag_dpo_amd/where_document.py states the rules). Trees of more than 1024 distinct patterns, 4096 compiled operations or
+about 15 levels of nesting (16 stack entries) raise ValueError on every engine. On a librdx engine the test runs on the GPU over a copy of the
+documents in HBM (engine.DocStore), built on the first where_document call and kept in step by every write after it; a
+collection that never filters by document allocates nothing for it. The copy is not persisted: it is rebuilt after a load.
 ids/documents/metadata stay on the host; embeddings go to the device index (`engine`). The engine is
 always librdx (rag_dpo_amd.engine.HipIndex): there is no CPU search path in this package.
 
@@ -24,6 +31,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence
 import numpy as np
 
 from . import where as W
+from . import where_document as WD
 
 DEFAULT_INCLUDE_QUERY = ["metadatas", "documents", "distances"]
 DEFAULT_INCLUDE_GET = ["metadatas", "documents"]
@@ -130,6 +138,7 @@ class Collection:
         self.mask_cache_hits = 0
         self._dir: Optional[str] = None        # set by PersistentClient: where the snapshot + journal live
         self._replaying = False
+        self._doc_store = None                 # engine.DocStore: the documents in HBM, made by the first where_document call
 
     # ---- small helpers ----------------------------------------------------------------------
     @property
@@ -246,9 +255,74 @@ class Collection:
                 res.close()
         self._mask_cache.clear()
 
-    def _search_args(self, where: Optional[dict]) -> dict:
+    # ---- where_document ---------------------------------------------------------------------------
+    def _docs_store(self):
+        """the device document store (engines that have one: HipIndex, MultiDeviceIndex on its first device), built from
+        self._docs on first use; None = evaluate on the host"""
+        if self._doc_store is None and self._engine is not None and getattr(self._engine, "has_device_docs", False):
+            from .engine import DocStore
+            st = DocStore(self._engine.device)
+            step = 65536
+            for a in range(0, self._rows, step):
+                st.append(self._docs[a: a + step])
+            self._doc_store = st
+        return self._doc_store
+
+    def _docs_write(self, fn):
+        """keep the device store in step with a write. The store is a cache of self._docs: if keeping it in step fails (device
+        error, out of memory), it is dropped and rebuilt by the next where_document call, and the write itself goes on (its
+        rows are already changed in memory and still have to reach the journal)."""
+        if self._doc_store is None:
+            return
+        try:
+            fn(self._doc_store)
+        except Exception:
+            try:
+                self._doc_store.close()
+            except Exception:
+                pass
+            self._doc_store = None
+
+    def _wd_mask(self, where: Optional[dict], where_document: dict) -> np.ndarray:
+        """bool[rows]: `where` AND `where_document` AND not deleted"""
+        n = self._rows
+        base = self._mask(where)
+        if n == 0:
+            return np.zeros(0, dtype=bool)
+        store = self._docs_store()
+        if store is None:
+            m = WD.evaluate_host(where_document, self._docs)
+            return m if base is None else (m & base)
+        leaves, prog = WD.compile_tree(where_document)
+        store.set_query(leaves, prog)
+        words = store.filter(W.pack_bits(base) if base is not None else None)
+        return np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(bool)
+
+    def _wd_resident(self, where: Optional[dict], where_document: dict):
+        """-> (host words or None, resident mask or None) of `where` AND `where_document` AND not deleted. On one device the
+        bitmap goes from the document filter straight into the resident mask: it never crosses PCIe."""
+        store = self._docs_store()
+        eng = self._engine
+        if store is not None and not hasattr(eng, "devices") and self._rows > 0:
+            import torch
+            dev = torch.device("cuda", store.device)
+            words = (self._rows + 31) // 32
+            base = self._mask(where)
+            base_t = torch.from_numpy(W.pack_bits(base).view(np.int32)).to(dev) if base is not None else None
+            out = torch.empty(words, dtype=torch.int32, device=dev)
+            leaves, prog = WD.compile_tree(where_document)
+            store.set_query(leaves, prog)
+            with torch.cuda.device(dev):
+                store.filter_device(out, base_t)
+            return None, eng.make_mask(out)
+        bits = W.pack_bits(self._wd_mask(where, where_document))
+        return bits, (eng.make_mask(bits) if hasattr(eng, "make_mask") else None)
+
+    def _search_args(self, where: Optional[dict], where_document: Optional[dict] = None) -> dict:
         """-> keyword arguments for engine.search: nothing (no filter, no tombstones), mask= (resident bitmap of a filter
         seen before or just uploaded) or allow_bits= (engines without resident masks)"""
+        if not WD.is_empty(where_document):
+            return self._search_args_wd(where, where_document)
         if where in (None, {}) and not self._n_dead:
             return {}
         try:
@@ -274,6 +348,27 @@ class Collection:
             self.mask_cache_hits += 1
         return {"mask": ent[1]} if ent[1] is not None else {"allow_bits": ent[0]}
 
+    def _search_args_wd(self, where: Optional[dict], where_document: dict) -> dict:
+        """_search_args with a where_document: cached under a key of its own ("wd:" + both filters; where-only keys are
+        unchanged), dropped on every write like the others"""
+        WD.validate(where_document)
+        try:
+            key = "wd:" + json.dumps([where, where_document], sort_keys=True, ensure_ascii=False, allow_nan=False)
+        except (TypeError, ValueError):
+            key = None
+        ent = self._mask_cache.get(key) if key is not None else None
+        if ent is None:
+            ent = self._wd_resident(where, where_document)
+            if key is not None:
+                if len(self._mask_cache) >= self._MASK_CACHE_MAX:
+                    _, r0 = self._mask_cache.pop(next(iter(self._mask_cache)))
+                    if r0 is not None and hasattr(r0, "close"):
+                        r0.close()
+                self._mask_cache[key] = ent
+        else:
+            self.mask_cache_hits += 1
+        return {"mask": ent[1]} if ent[1] is not None else {"allow_bits": ent[0]}
+
     @staticmethod
     def _check_include(include: Sequence[str], allowed: set):
         for inc in include:
@@ -288,6 +383,7 @@ class Collection:
         n = self._rows
         keep = np.flatnonzero(self._alive[:n])
         self._engine.compact(keep)
+        self._docs_write(lambda st: st.compact(keep))
         self._ids = [self._ids[i] for i in keep]
         self._docs = [self._docs[i] for i in keep]
         self._cols = {k: c.take(keep) for k, c in self._cols.items()}
@@ -351,6 +447,7 @@ class Collection:
                 self._row_of[ids[i]] = row
                 self._alive[row] = True
                 self._set_meta(row, metadatas[i] if metadatas is not None else None, replace=False)
+            self._docs_write(lambda st: st.append(self._docs[row0:]))
             self._log({"op": "add", "ids": [ids[i] for i in fresh],
                        "documents": None if documents is None else [documents[i] for i in fresh],
                        "metadatas": None if metadatas is None else [metadatas[i] for i in fresh]}, sel)
@@ -382,6 +479,12 @@ class Collection:
                     self._set_meta(row, metadatas[i], replace=False)
                 if documents is not None:
                     self._docs[row] = documents[i]
+            if documents is not None and hit:
+                for key in [k for k in self._mask_cache if k.startswith("wd:")]:   # where-only bitmaps do not read documents
+                    _, r0 = self._mask_cache.pop(key)
+                    if r0 is not None and hasattr(r0, "close"):
+                        r0.close()
+                self._docs_write(lambda st: st.replace([r for _, r in hit], [documents[i] for i, _ in hit]))
             if hit:
                 idx = [i for i, _ in hit]
                 self._log({"op": "update", "ids": [ids[i] for i in idx],
@@ -405,9 +508,13 @@ class Collection:
             if new:
                 self.add([ids[i] for i in new], None if emb is None else emb[new], pick(metadatas, new), pick(documents, new))
 
-    def delete(self, ids=None, where=None, **_ignored):
+    def delete(self, ids=None, where=None, where_document=None, **_ignored):
         """reference ingest_enterprise.py:272,304 (ids in batches of 5000). Rows are tombstoned (excluded from
-        every search through the row bitmap) and compacted out of HBM once a fifth of the rows is dead."""
+        every search through the row bitmap) and compacted out of HBM once a fifth of the rows is dead.
+        where_document narrows ids= / where=, or selects the rows alone."""
+        wd = None if WD.is_empty(where_document) else where_document
+        if wd is not None:
+            WD.validate(wd)
         with self._lock:
             rows: List[int] = []
             if ids is not None:
@@ -417,11 +524,16 @@ class Collection:
                 if where is not None and rows:
                     m = W.evaluate(where, self._cols, self._rows)
                     rows = [r for r in rows if m is None or m[r]]
+                if wd is not None and rows:
+                    m = self._wd_mask(None, wd)
+                    rows = [r for r in rows if m[r]]
+            elif wd is not None:
+                rows = np.flatnonzero(self._wd_mask(where, wd)).tolist()
             elif where is not None:
                 m = self._mask(where)
                 rows = np.flatnonzero(m).tolist() if m is not None else list(range(self._rows))
             else:
-                raise ValueError("delete needs ids= or where=")
+                raise ValueError("delete needs ids=, where= or where_document=")
             gone = [self._ids[r] for r in rows if self._alive[r]]
             if gone:
                 self._drop_masks()
@@ -442,8 +554,9 @@ class Collection:
         ingest_enterprise.py:142-145. Order = insertion order, like chromadb."""
         include = DEFAULT_INCLUDE_GET if include is None else list(include)
         self._check_include(include, {"embeddings", "documents", "metadatas", "uris", "data"})
-        if where_document is not None:
-            raise ValueError("where_document is not implemented (the reference never passes it)")
+        wd = None if WD.is_empty(where_document) else where_document
+        if wd is not None:
+            WD.validate(wd)
         with self._lock:
             if ids is not None:
                 if isinstance(ids, str):
@@ -452,6 +565,11 @@ class Collection:
                 if where is not None and rows:
                     m = W.evaluate(where, self._cols, self._rows)
                     rows = [r for r in rows if m is None or m[r]]
+                if wd is not None and rows:
+                    m = self._wd_mask(None, wd)
+                    rows = [r for r in rows if m[r]]
+            elif wd is not None:
+                rows = np.flatnonzero(self._wd_mask(where, wd)).tolist()
             else:
                 m = self._mask(where)
                 rows = list(range(self._rows)) if m is None else np.flatnonzero(m).tolist()
@@ -483,8 +601,8 @@ class Collection:
         if query_embeddings is None:
             raise ValueError("this collection has no embedding function: pass query_embeddings= "
                              "(the reference always does, retriever.py:215-220)")
-        if where_document is not None:
-            raise ValueError("where_document is not implemented (the reference never passes it)")
+        if not WD.is_empty(where_document):
+            WD.validate(where_document)
         if not isinstance(n_results, (int, np.integer)) or isinstance(n_results, bool) or n_results <= 0:
             raise ValueError(f"Number of requested results {n_results}, cannot be negative, or zero.")
         q = _as_matrix(query_embeddings, "query_embeddings")
@@ -501,7 +619,7 @@ class Collection:
                         "uris": None, "data": None, "included": include}
             if q.shape[1] != self._dim:
                 raise ValueError(f"Embedding dimension {q.shape[1]} does not match collection dimensionality {self._dim}")
-            scores, rows, counts = self._engine.search(q, int(n_results), **self._search_args(where))
+            scores, rows, counts = self._engine.search(q, int(n_results), **self._search_args(where, where_document))
             dist = (np.float32(1.0) - scores).astype(np.float32)   # Chroma cosine distance, fp32 like chromadb
             out_ids, out_docs, out_meta, out_dist, out_emb = [], [], [], [], []
             for b in range(nq):
@@ -527,13 +645,15 @@ class Collection:
                 "included": include,
             }
 
-    def query_device(self, query_embeddings, n_results: int = 10, where=None):
+    def query_device(self, query_embeddings, n_results: int = 10, where=None, where_document=None):
         """Batch callers that already hold their query embeddings on the GPU (the provider's `embed_device`, reference
         src/utils/embedding_provider.py:139-145 feeding src/rag/retriever.py:215-220) and want the neighbours there too:
         `query_embeddings` a [nq][dim] fp32 torch CUDA tensor -> (distances f32[nq, n_results], rows i64[nq, n_results],
         counts i32[nq]) torch tensors on the collection's (first) device; `ids_of(rows)` maps rows to the Chroma ids. Same
         filter semantics and the same floats as query() — nothing crosses PCIe but the call itself."""
         import torch
+        if not WD.is_empty(where_document):
+            WD.validate(where_document)
         with self._lock:
             if self._engine is None or self._rows == 0:
                 raise ValueError("query_device: the collection is empty")
@@ -541,7 +661,7 @@ class Collection:
                 raise NotImplementedError("this collection's engine has no device-pointer search")
             q = query_embeddings.contiguous()
             nq, k = int(q.shape[0]), int(n_results)
-            args = self._search_args(where)
+            args = self._search_args(where, where_document)
             if "allow_bits" in args:
                 raise NotImplementedError("query_device needs an engine with resident masks")
             dev = q.device
@@ -812,6 +932,9 @@ class PersistentClient:
             raise NotFoundError(f"Collection {name} does not exist.")
         c = self._cols.pop(name)
         c._drop_masks()
+        if c._doc_store is not None:
+            c._doc_store.close()
+            c._doc_store = None
         if c._engine is not None and hasattr(c._engine, "close"):
             c._engine.close()
         if self.path:

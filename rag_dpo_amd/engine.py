@@ -36,6 +36,8 @@ class ResidentMask:
 
 
 class HipIndex:
+    has_device_docs = True   # Collection keeps a DocStore on this device for where_document
+
     def __init__(self, dim: int, device: int = 0):
         self._lib = L.load(require_gpu=True)
         self._h = ctypes.c_void_p()
@@ -130,11 +132,23 @@ class HipIndex:
         L.check(self._lib.rdx_index_compact(self._h, _np_ptr(keep), keep.shape[0]))
 
     # ---- search -----------------------------------------------------------------------------
-    def make_mask(self, allow_bits: np.ndarray) -> ResidentMask:
-        allow_bits = np.ascontiguousarray(allow_bits, dtype=np.uint32)
-        if allow_bits.shape[0] != (len(self) + 31) // 32:
-            raise ValueError("allow_bits must hold ceil(count/32) words")
+    def make_mask(self, allow_bits) -> ResidentMask:
+        """allow_bits: ceil(count/32) uint32 words, a numpy array or a torch tensor (int32 / uint32) on this index's device
+        (e.g. DocStore.filter's output: the bitmap then never leaves the device)"""
+        words = (len(self) + 31) // 32
         h = ctypes.c_void_p()
+        import sys
+        torch = sys.modules.get("torch")
+        if torch is not None and isinstance(allow_bits, torch.Tensor) and allow_bits.is_cuda:
+            if allow_bits.device.index != self.device:
+                raise ValueError("allow_bits lives on another device than the index")
+            if allow_bits.element_size() != 4 or allow_bits.numel() != words or not allow_bits.is_contiguous():
+                raise ValueError("allow_bits must hold ceil(count/32) contiguous 32-bit words")
+            L.check(self._lib.rdx_mask_create(self._h, ctypes.c_void_p(allow_bits.data_ptr()), L.RDX_DEVICE, ctypes.byref(h)))
+            return ResidentMask(self._lib, h)
+        allow_bits = np.ascontiguousarray(allow_bits, dtype=np.uint32)
+        if allow_bits.shape[0] != words:
+            raise ValueError("allow_bits must hold ceil(count/32) words")
         L.check(self._lib.rdx_mask_create(self._h, _np_ptr(allow_bits), L.RDX_HOST, ctypes.byref(h)))
         return ResidentMask(self._lib, h)
 
@@ -230,6 +244,97 @@ class HipIndex:
         s = L.SearchStats()
         L.check(self._lib.rdx_search_last_stats(self._h, ctypes.byref(s)))
         return s.as_dict()
+
+
+class DocStore:
+    """The rows' document text resident in one device's HBM (include/rdx.h rdx_docs_*): where_document's substring scan.
+    Rows follow the collection's row order; the caller keeps it in step (append / replace / compact)."""
+
+    def __init__(self, device: int = 0):
+        self._lib = L.load(require_gpu=True)
+        self._h = ctypes.c_void_p()
+        L.check(self._lib.rdx_docs_create(int(device), ctypes.byref(self._h)))
+        self.device = int(device)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.rdx_docs_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def append(self, docs):
+        from .where_document import pack_docs
+        b, off = pack_docs(docs)
+        L.check(self._lib.rdx_docs_append(self._h, _np_ptr(b), _np_ptr(off), len(docs)))
+
+    def replace(self, rows, docs):
+        from .where_document import pack_docs
+        ids = np.ascontiguousarray(rows, dtype=np.int64)
+        b, off = pack_docs(docs)
+        if ids.shape[0] != len(docs):
+            raise ValueError("replace: one document per row")
+        L.check(self._lib.rdx_docs_replace(self._h, _np_ptr(ids), _np_ptr(b), _np_ptr(off), ids.shape[0]))
+
+    def compact(self, keep_rows):
+        keep = np.ascontiguousarray(keep_rows, dtype=np.int64)
+        L.check(self._lib.rdx_docs_compact(self._h, _np_ptr(keep), keep.shape[0]))
+
+    def stats(self) -> dict:
+        r, lv, ar = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        L.check(self._lib.rdx_docs_stats(self._h, ctypes.byref(r), ctypes.byref(lv), ctypes.byref(ar)))
+        return {"rows": r.value, "live_bytes": lv.value, "arena_bytes": ar.value}
+
+    def __len__(self) -> int:
+        return self.stats()["rows"]
+
+    def set_query(self, leaves, program=()):
+        """leaves: non-empty byte strings; program: postfix ops (include/rdx.h RDX_DOCS_OP_*), may be empty for contains()"""
+        from .where_document import pack_patterns
+        b, off = pack_patterns(leaves)
+        prog = np.ascontiguousarray(program, dtype=np.int32)
+        self._n_leaves = 0
+        L.check(self._lib.rdx_docs_set_query(self._h, _np_ptr(b), _np_ptr(off), len(leaves),
+                                             _np_ptr(prog) if prog.shape[0] else None, prog.shape[0]))
+        self._n_leaves = len(leaves)
+
+    _n_leaves = 0
+
+    def contains(self) -> np.ndarray:
+        """-> uint32 [P][ceil(rows/32)]: the leaf bitmaps of the query set last (host); P = its number of leaves"""
+        if not self._n_leaves:
+            raise RuntimeError("DocStore.contains: no query set")
+        out = np.zeros((self._n_leaves, (len(self) + 31) // 32), dtype=np.uint32)
+        L.check(self._lib.rdx_docs_contains(self._h, _np_ptr(out), L.RDX_HOST, None))
+        return out
+
+    def filter(self, base_bits: Optional[np.ndarray] = None) -> np.ndarray:
+        """-> uint32 [ceil(rows/32)]: program(leaves) AND base_bits (host in, host out)"""
+        words = (len(self) + 31) // 32
+        out = np.zeros(words, dtype=np.uint32)
+        base = None
+        if base_bits is not None:
+            base = np.ascontiguousarray(base_bits, dtype=np.uint32)
+            if base.shape[0] != words:
+                raise ValueError("base_bits must hold ceil(rows/32) words")
+        L.check(self._lib.rdx_docs_filter(self._h, _np_ptr(base) if base is not None else None, _np_ptr(out), L.RDX_HOST, None))
+        return out
+
+    def filter_device(self, out_bits, base_bits=None):
+        """torch int32 tensors on the store's device, enqueued on the current torch stream: nothing crosses PCIe"""
+        import torch
+        words = (len(self) + 31) // 32
+        for t in (out_bits, base_bits):
+            if t is not None and (not t.is_cuda or t.device.index != self.device or t.dtype != torch.int32
+                                  or t.numel() != words or not t.is_contiguous()):
+                raise ValueError(f"expected a contiguous int32 tensor of {words} words on cuda:{self.device}")
+        stream = HipIndex._raw_stream(out_bits.device)
+        L.check(self._lib.rdx_docs_filter(self._h, ctypes.c_void_p(base_bits.data_ptr()) if base_bits is not None else None,
+                                          ctypes.c_void_p(out_bits.data_ptr()), L.RDX_DEVICE, ctypes.c_void_p(stream)))
 
 
 def l2_normalize(x: np.ndarray, device: int = 0) -> np.ndarray:

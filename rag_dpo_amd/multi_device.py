@@ -93,6 +93,11 @@ class MultiDeviceIndex:
     def __len__(self) -> int:
         return self._n
 
+    @property
+    def has_device_docs(self) -> bool:
+        """where_document runs in a DocStore on the first device (the bitmap comes to the host for make_mask)"""
+        return all(getattr(s, "has_device_docs", False) for s in self._shards)
+
     def _each(self, fn, items=None):
         """fn(shard index) on every shard, concurrently; exceptions propagate (first one wins)"""
         idx = list(range(len(self._shards))) if items is None else items
