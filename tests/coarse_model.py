@@ -1,0 +1,449 @@
+"""TEST-ONLY: a model of the fp16 coarse pass of the dense scan and the constructions that pin it.
+
+The coarse score of (query, row) is the fp32-accumulated MFMA sum of fp16(2^s q̂_i) * fp16(2^s ĉ_i), scaled back by 4^-s
+(rag_dpo_amd/csrc/k_rows.hpp shadow_store4, scan_kernel.hpp). The model restates it from the same fp32 normalised rows the
+library computes (oracle.normalize_rows, bit-equal to K1: test_gpu_parity.py::test_normalize_bit_exact):
+
+    SCAN COPY   fp16(2^s * y) rounded to nearest even (numpy's conversion keeps fp16 subnormals), padding columns zero.
+    COARSE      the float64 sum of the exact fp16 products, times 4^-s, and a rigorous bound on the kernel's fp32 accumulation:
+                (n - 1) 2^-23 sum|x̃ỹ| with n the number of NON-ZERO products (zeros add exactly; valid for truncating adders).
+                When every product is a multiple of 2^L and sum|x̃ỹ| < 2^(L+24), every partial sum in any order is an fp32
+                number: the kernel's value is then the model's to the bit (bound 0).
+    CONSTANTS   E, 2E and the bootstrap slack as the library computes them in float32 (rdx_api.hip two_e(), plan_search
+                p.slack), and the refine band edge t2 = c_k - 2E (refine_kernel.hpp).
+
+Mutants (for the power tests of test_coarse_model.py, never built into the library): round-toward-zero conversion
+(`rtz`), fp16 subnormals flushed (`flush`).
+"""
+import math
+
+import numpy as np
+
+F16, F32, F64 = np.float16, np.float32, np.float64
+MAX_DIM = 4096                        # rdx_common.hpp
+REFINE_PMAX = 1024                    # refine_kernel.hpp: band rows re-scored in the ranking arrays; more -> in-place re-score
+F16_MIN_NORMAL = 2.0 ** -14
+EPS32 = F32(1.1920929e-7)             # the literal plan_search uses for 2^-23
+
+
+# ---- library constants (float32, as the library computes them) -----------------------------------------------------------------
+
+def dim_pad(dim):
+    return (dim + 63) // 64 * 64
+
+
+def scale_log2(dim):
+    """std::lround(std::log2(std::sqrt(dim))) (halves away from zero)"""
+    return int(math.floor(math.log2(math.sqrt(dim)) + 0.5))
+
+
+def e_bound(dim):
+    """E = 1.0e-3 + 2.5e-7 dim_pad in float32"""
+    return F32(F32(1.0e-3) + F32(F32(2.5e-7) * F32(dim_pad(dim))))
+
+
+def two_e(dim):
+    return F32(F32(2.0) * e_bound(dim))
+
+
+def slack(dim, use_boot, use_small):
+    """plan_search: 2E below the k-th sampled score, + twice the accumulation bound when bootstrap and main scan sum in
+    different orders (k_boot vs k_scan, or the tile bootstrap vs k_scan_small)"""
+    extra = F32(F32(2.0) * F32(dim_pad(dim)) * EPS32) if use_boot != use_small else F32(0.0)
+    return F32(two_e(dim) + extra)
+
+
+def band_edge(c_k, dim, band=None):
+    """k_refine's t2 = c_k - 2E in float32 (band: the value subtracted, 2E unless a mutant is modelled)"""
+    return F32(F32(c_k) - (two_e(dim) if band is None else F32(band)))
+
+
+def threshold(m_k, dim, use_boot, use_small):
+    """k_tau's proven threshold m_k - slack, in score units (the library subtracts in accumulator units, 4^s times larger:
+    power-of-two scaling, the same float32 result)"""
+    return F32(F32(m_k) - slack(dim, use_boot, use_small))
+
+
+# ---- §5's inequality chain -------------------------------------------------------------------------------------------------------
+
+def e_terms(dim):
+    """(fp16 term, subnormal term, accumulation term) of §5 at unit-norm rows, float64"""
+    dp = dim_pad(dim)
+    s = scale_log2(dim)
+    fp16 = 2.0 ** -10 + 2.0 ** -22
+    # an element below fp16's normal range after scaling (|2^s y| < 2^-14) is off by at most 2^-25 (half the subnormal spacing)
+    # instead of 2^-11 relative; over the row that is sum_i 2^-25 |2^s q_i| 4^-s + the same for the query <= 2 * 2^-25 * 2^-s * sqrt(dp)
+    sub = 2.0 * 2.0 ** -25 * 2.0 ** -s * math.sqrt(dp) * (1.0 + 2.0 ** -11)
+    acc = dp * 2.0 ** -23 * (1.0 + fp16)
+    return fp16, sub, acc
+
+
+# ---- the scan copy and the coarse score ------------------------------------------------------------------------------------------
+
+def _rtz16(x32):
+    """fp16 of float32 values rounded toward zero"""
+    h = x32.astype(F16)
+    over = np.abs(h.astype(F64)) > np.abs(x32.astype(F64))
+    h[over] = np.nextafter(h[over], F16(0.0))
+    return h
+
+
+def scan_copy(yhat, dim, rtz=False, flush=False):
+    """the fp16 scan copy [n][dim_pad] of normalised float32 rows [n][dim]"""
+    y = np.atleast_2d(np.asarray(yhat, dtype=F32))
+    sc = F32(2.0 ** scale_log2(dim))
+    x = (y * sc).astype(F32)                      # exact: a power of two
+    h = _rtz16(x) if rtz else x.astype(F16)
+    if flush:
+        h[np.abs(h.astype(F64)) < F16_MIN_NORMAL] = F16(0.0)
+    out = np.zeros((y.shape[0], dim_pad(dim)), dtype=F16)
+    out[:, :dim] = h
+    return out
+
+
+def _lsb_exp(p):
+    """exponent of the lowest set bit of each non-zero float64 value"""
+    m, e = np.frexp(np.abs(p))
+    mi = (m * 2.0 ** 53).astype(np.int64)
+    tz = np.zeros(mi.shape, dtype=np.int64)
+    v = mi.copy()
+    for b in (32, 16, 8, 4, 2, 1):
+        low = (v & ((1 << b) - 1)) == 0
+        tz += np.where(low, b, 0)
+        v = np.where(low, v >> b, v)
+    return e.astype(np.int64) - 53 + tz
+
+
+class Coarse:
+    """coarse scores of rows against one query: value (float64, the exact sum of the fp16 products times 4^-s), bound (the
+    kernel's fp32 accumulation may be off by at most this), exact (bound 0: every partial sum is an fp32 number)"""
+
+    def __init__(self, q16, c16, dim):
+        q = np.asarray(q16, dtype=F16).astype(F64).reshape(-1)
+        c = np.atleast_2d(np.asarray(c16, dtype=F16)).astype(F64)
+        p = c * q[None, :]                         # exact: 11 x 11 significant bits
+        inv = 4.0 ** -scale_log2(dim)
+        nz = p != 0.0
+        n = nz.sum(axis=1)
+        a = np.abs(p).sum(axis=1)
+        self.value = p.sum(axis=1) * inv
+        lsb = np.where(nz, _lsb_exp(np.where(nz, p, 1.0)), 10 ** 6).min(axis=1)
+        self.exact = (n <= 1) | (a < np.ldexp(1.0, np.minimum(lsb, 2000) + 24))
+        self.bound = np.where(self.exact, 0.0, np.maximum(n - 1, 0) * 2.0 ** -23 * a * inv)
+        self.abs_sum = a * inv
+        self.value32 = np.where(self.exact, self.value.astype(F32), F32(np.nan))
+
+    @property
+    def lo(self):
+        return self.value - self.bound
+
+    @property
+    def hi(self):
+        return self.value + self.bound
+
+
+def coarse(qhat, chat, dim, rtz=False, flush=False):
+    return Coarse(scan_copy(qhat, dim, rtz, flush)[0], scan_copy(chat, dim, rtz, flush), dim)
+
+
+def exact(qhat, chat):
+    """the exact score of the normalised float32 rows, float64 (the library's re-score is this rounded to float32)"""
+    return np.atleast_2d(np.asarray(chat, dtype=F32)).astype(F64) @ np.asarray(qhat, dtype=F32).astype(F64).reshape(-1)
+
+
+def normalize(x):
+    from oracle import oracle as O
+    return O.normalize_rows(np.atleast_2d(np.asarray(x, dtype=F32)))
+
+
+def to_bf16(x):
+    """float32 -> the nearest bf16 value (RNE), widened back to float32"""
+    u = np.asarray(x, dtype=F32).view(np.uint32).astype(np.uint64)
+    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+    return u.astype(np.uint32).view(F32)
+
+
+def bf16_bits(x):
+    """float32 values that ARE bf16 values -> their uint16 bit patterns (rdx_index_add_bf16's input)"""
+    u = np.asarray(x, dtype=F32).view(np.uint32)
+    assert np.all((u & 0xFFFF) == 0), "not bf16 values"
+    return (u >> 16).astype(np.uint16)
+
+
+# ---- predictions -----------------------------------------------------------------------------------------------------------------
+
+def count_at_least(cs, edge, lo_edge=None):
+    """rows whose kernel coarse score is certainly >= edge (an edge known to lie in [lo_edge, edge]); raises if any row's
+    membership depends on roundings the model does not pin"""
+    lo_edge = edge if lo_edge is None else lo_edge
+    lo, hi = cs.lo, cs.hi
+    v32 = cs.value32
+    n = 0
+    for i in range(lo.shape[0]):
+        if cs.exact[i] and lo_edge == edge:
+            n += int(v32[i] >= F32(edge))
+        elif lo[i] >= float(edge):
+            n += 1
+        elif hi[i] < float(lo_edge):
+            pass
+        else:
+            raise AssertionError(f"row {i}: coarse [{lo[i]!r}, {hi[i]!r}] straddles the edge [{lo_edge!r}, {edge!r}]")
+    return n
+
+
+def ladder_prediction(q_raw, rows_raw, k, dim, use_boot=None, use_small=None, allow=None, rtz=False, flush=False, band=None,
+                      normalized=False):
+    """What one query's search over `rows_raw` (with k-th largest coarse score exactly known) must report: the k-th coarse score
+    c_k, t2, `rescored` (rows with coarse >= t2) and, when use_boot / use_small are given (k = 1, proven threshold, the best row
+    sampled), `emitted` (rows with coarse >= T). Rows outside `allow` take no part. normalized: the inputs are rows K1 has
+    already normalised (oracle.normalize_rows)."""
+    qh = np.asarray(q_raw, F32) if normalized else normalize(q_raw)[0]
+    ch = np.asarray(rows_raw, F32) if normalized else normalize(rows_raw)
+    if allow is not None:
+        ch = ch[np.asarray(allow, dtype=bool)]
+    cs = coarse(qh, ch, dim, rtz, flush)
+    order = np.argsort(-cs.value, kind="stable")
+    kth = order[k - 1]
+    # the k-th largest is pinned when it is exact and no other row can reach over it from below / fall under it from above
+    lo_k, hi_k = cs.lo[kth], cs.hi[kth]
+    others = np.delete(np.arange(len(cs.value)), order[:k])
+    assert len(others) == 0 or cs.hi[others].max() <= lo_k, "the k-th largest coarse score is not pinned"
+    assert k == 1 or cs.lo[order[:k - 1]].min() >= hi_k, "the k-th largest coarse score is not pinned"
+    t2_lo = band_edge(lo_k, dim, band) if not cs.exact[kth] else None
+    c_k = cs.value32[kth] if cs.exact[kth] else None
+    if c_k is not None:
+        t2 = band_edge(c_k, dim, band)
+        rescored = count_at_least(cs, t2)
+    else:
+        t2 = band_edge(F32(hi_k), dim, band)
+        rescored = count_at_least(cs, t2, t2_lo)
+    out = {"c_k": c_k, "c_k_lo": lo_k, "c_k_hi": hi_k, "t2": t2, "rescored": rescored, "coarse": cs}
+    if use_boot is not None and k == 1:
+        if c_k is not None:
+            out["emitted"] = count_at_least(cs, threshold(c_k, dim, use_boot, use_small))
+        else:
+            t_hi = threshold(F32(hi_k), dim, use_boot, use_small)
+            t_lo = threshold(F32(lo_k), dim, use_boot, use_small)
+            try:
+                out["emitted"] = count_at_least(cs, t_hi, t_lo)
+            except AssertionError:
+                out["emitted"] = None
+    return out
+
+
+def band_top(q_raw, rows_raw, k, dim, band=None, rtz=False):
+    """the rows k_refine ranks (coarse >= c_k - band) ordered by exact score, as model indices"""
+    qh = normalize(q_raw)[0]
+    ch = normalize(rows_raw)
+    cs = coarse(qh, ch, dim, rtz)
+    c_k = np.sort(cs.value)[::-1][k - 1]
+    t2 = band_edge(F32(c_k), dim, band)
+    inband = np.nonzero(cs.value >= float(t2))[0]
+    ex = exact(qh, ch)
+    return inband[np.argsort(-ex[inband], kind="stable")][:k]
+
+
+# ---- constructions ---------------------------------------------------------------------------------------------------------------
+# Every construction returns raw float32 vectors on the columns it is given (`cols`, in order of decreasing query weight: the
+# first six carry the sign pattern that keeps several instances in one corpus apart) and zeros elsewhere.
+
+def _place(vals, cols, dim):
+    x = np.zeros(dim, dtype=F32)
+    x[np.asarray(cols[:len(vals)])] = vals
+    return x
+
+
+def _base4_digits(n):
+    d = []
+    while n:
+        d.append(n % 4)
+        n //= 4
+    return d
+
+
+def aligned_pattern(dim, sign=+1):
+    """Scaled magnitudes 2^e of the aligned worst case: the row equal to the query, every scaled component just past an fp16
+    rounding midpoint in the direction `sign`. Raw components are powers of two; the library's own normalisation puts the scaled
+    mantissa at 2^s / sqrt(sum of squares):
+      +1: 1023 * 4^(s-5) = three per binade 2^(s-5) .. 2^(s-1) (15 non-zeros): mantissa sqrt(1024/1023) = 1 + 2^-11 (1 + 1/2046):
+          every element rounds UP by (almost) half an ulp;
+      -1: 65473 * 4^(s-8) (16 non-zeros): mantissa sqrt(65536/65473) = 1 + 0.985 * 2^-11: every element rounds DOWN."""
+    s = scale_log2(dim)
+    if sign > 0:
+        n, base = 1023, s - 5
+    else:
+        n, base = 65473, s - 8
+    vals = []
+    for i, dgt in enumerate(_base4_digits(n)):
+        vals += [2.0 ** (base + i)] * dgt
+    return np.array(sorted(vals, reverse=True), dtype=F64)
+
+
+def aligned(dim, cols, sign=+1):
+    """(query, row) of the aligned worst case (the row IS the query)"""
+    v = aligned_pattern(dim, sign).astype(F32)
+    q = _place(v, cols, dim)
+    return q, q.copy()
+
+
+def split_pair(dim, cols, delta=1.5e-6):
+    """(query, row A, row B). A lies on support u2, B on u1 (disjoint). The query's scaled components sit just ABOVE fp16
+    midpoints on u1 (round up) and just BELOW midpoints on u2 (round down); B's just above (up), A's just below (down). Within
+    each support the weight is split into columns where query and row have the same binade and columns where the row's binade is
+    one higher (q_u1 cannot be parallel to B with |q_u1| = 1/sqrt2 and both on fp16 midpoints): exact(A) ~ exact(B) ~ 2/3,
+    coarse(B) - coarse(A) ~ 2 (2/3) 2^-10 = 1.28e-3 (more than E at d <= 1024). An extra column shared by query and A (a power of
+    two) makes exact(A) > exact(B) by about 1e-5. Needs 15 + 15 + 1 + 3 columns (u1, u2, the shared one, three balancing).
+    Values are set to their normalised size directly (each vector's sum of squares is 1 to float64 precision through a
+    balancing column of its own), so the library's normalisation moves them by float32 roundings only."""
+    s = scale_log2(dim)
+    S = 2.0 ** s
+    mid = 1.0 + 2.0 ** -11
+    up, down = mid * (1 + delta), mid * (1 - delta)
+    # (query binade, row binade) per column, both supports: one column per binade with equal binades, two with the row one higher
+    layout = []
+    for j in range(1, 6):
+        layout.append((s - j, s - j))
+        layout += [(s - j - 1, s - j)] * 2
+    q = np.zeros(dim, dtype=F64)
+    a = np.zeros(dim, dtype=F64)
+    b = np.zeros(dim, dtype=F64)
+    u1, u2 = cols[:15], cols[15:30]
+    for i, ((fq, fr), c) in enumerate(zip(layout, u1)):
+        if i < 14:                                # (the 15th column stays empty: room for the balancing columns)
+            q[c] = 2.0 ** fq * up / S
+            b[c] = 2.0 ** fr * up / S
+    for i, ((fq, fr), c) in enumerate(zip(layout, u2)):
+        if i < 14:
+            q[c] = 2.0 ** fq * down / S
+            a[c] = 2.0 ** fr * down / S
+    xa, xq, xb, xc = cols[30], cols[31], cols[32], cols[33]
+    g0 = (q * a).sum() - (q * b).sum()            # < 0: u1 rounds up, u2 down
+    x = 2.0 ** math.ceil(math.log2(math.sqrt(-g0)) + 1e-9)
+    a[xa] = x                                     # the extra shared column: x^2 in (|g0|, 4 |g0|]
+    q[xa] = x
+    for vec, col in ((q, xq), (a, xb), (b, xc)):
+        r = 1.0 - (vec * vec).sum()
+        assert r > 0, "construction left no room for the balancing column"
+        vec[col] = math.sqrt(r)
+    return q.astype(F32), a.astype(F32), b.astype(F32)
+
+
+DYADIC_Q = np.array([1, 1, 1, .5, .5, .5, .25, .25, .25, .125, .125, .125, .125], dtype=F32)   # sum of squares 4: q̂ = q / 2
+
+
+def dyadic_query(dim, cols):
+    """a query whose scaled components are powers of two (2^(s-1) .. 2^(s-4)): every product with it is an fp16 value times a
+    power of two, so a row's coarse score is an fp32 number the kernel reproduces to the bit (Coarse.exact)"""
+    return _place(DYADIC_Q, cols, dim)
+
+
+def _fast_coarse(q_raw, cand_raw, dim):
+    """the model on candidates whose columns are few: float64 normalisation (not the library's lane order: candidates are
+    re-checked with the real one)"""
+    y = (cand_raw / np.sqrt((cand_raw.astype(F64) ** 2).sum(axis=1, keepdims=True))).astype(F32)
+    qh = (q_raw / np.sqrt((q_raw.astype(F64) ** 2).sum())).astype(F32)
+    s = scale_log2(dim)
+    c16 = (y * F32(2.0 ** s)).astype(F16).astype(F64)
+    q16 = (qh * F32(2.0 ** s)).astype(F16).astype(F64)
+    return (c16 @ q16) * 4.0 ** -s
+
+
+def ladder_probes(q_raw, edge, dim, cols, rng, n_in=4, n_out=4, bf16=False, rtz_sensitive=2, edge_lo=None):
+    """Rows near q_raw whose coarse scores lie just above (n_in) and just below (n_out) `edge` (an fp32 value; the true edge
+    lies in [edge_lo, edge]): the nearest ones the search finds, all pinned by the model. `rtz_sensitive` of the rows above the
+    edge are chosen among those a round-toward-zero conversion would move below it. cols: the query's support, then one
+    tilt column. Returns (rows [n_in + n_out][dim], above: bool[n])."""
+    edge_lo = edge if edge_lo is None else edge_lo
+    supp = np.nonzero(q_raw)[0]
+    tilt = cols[len(supp)]
+    nq = float(np.sqrt((q_raw.astype(F64) ** 2).sum()))
+    g0 = nq * math.sqrt(1.0 / float(edge) ** 2 - 1.0)
+    sub_cols = list(supp) + [tilt]
+    qs = q_raw[sub_cols]
+    above, below = {}, {}
+    qh = normalize(q_raw)[0]
+    for rnd in range(40):
+        n = 4096
+        cand = np.zeros((n, dim), dtype=F32)
+        eta = rng.uniform(-2.0 ** -8, 2.0 ** -8, size=(n, len(supp)))
+        cand[:, supp] = q_raw[supp] * (1.0 + eta)
+        cand[:, tilt] = g0 * rng.uniform(0.6, 1.4, size=n)     # coarse scores over +-2.5e-3 around the edge: the
+        if bf16:
+            cand = to_bf16(cand)
+        fc = _fast_coarse(qs, cand[:, sub_cols], dim)       # rounding offset (up to E) needs no calibration
+        near = np.nonzero(np.abs(fc - float(edge)) < 3e-5)[0]
+        if len(near) == 0:
+            continue
+        rows = cand[near]
+        cs = coarse(qh, normalize(rows), dim)
+        cr = coarse(qh, normalize(rows), dim, rtz=True)
+        for i in range(len(near)):
+            key = rows[i].tobytes()
+            if cs.lo[i] >= float(edge) and (cs.bound[i] > 0 or cs.value32[i] >= edge):
+                above[key] = (cs.lo[i] - float(edge), bool(cr.hi[i] < float(edge_lo)), rows[i])
+            elif cs.hi[i] < float(edge_lo) and (cs.bound[i] > 0 or cs.value32[i] < edge_lo):
+                below[key] = (float(edge_lo) - cs.hi[i], rows[i])
+        if len(above) >= 4 * n_in and len(below) >= 4 * n_out and sum(v[1] for v in above.values()) >= rtz_sensitive:
+            break
+    ab = sorted(above.values(), key=lambda v: v[0])
+    sens = [v for v in ab if v[1]][:rtz_sensitive]
+    rest = [v for v in ab if not any(v is w for w in sens)][:n_in - len(sens)]
+    pick_a = [v[2] for v in sens + rest]
+    pick_b = [v[1] for v in sorted(below.values(), key=lambda v: v[0])[:n_out]]
+    assert len(pick_a) == n_in and len(pick_b) == n_out, (len(above), len(below))
+    rows = np.stack(pick_a + pick_b).astype(F32)
+    return rows, np.array([True] * n_in + [False] * n_out)
+
+
+def subnormal_ladder(dim, cols, side="row", n_sub=12):
+    """A low-score ladder whose band membership rests on fp16 SUBNORMAL products. The query is dyadic; the anchor's coarse score
+    c_k = 2E + 1.5e-3 comes from one column (a), so t2 = c_k - 2E ~ 1.5e-3. Probe rows have a normal part on column a at consecutive
+    fp16 values around t2 and, on n_sub further columns b, products whose fp16 operand is subnormal:
+      side = "row":   the query is 1/4 on each b column (scaled 2^(s-2)), the rows 2^-15 / 2^s there (scaled 2^-15: subnormal);
+      side = "query": the query is 2^-15 / 2^s on each b column (scaled 2^-15: subnormal), the rows 1/4 there (scaled 2^(s-2)).
+    Each subnormal product adds 2^-15 * (the other operand) 4^-s; all sums are exact in fp32. Needs 2 + n_sub + 3 columns.
+    Returns (query, anchor, probes [n][dim], subnormal_part: float64 per probe)."""
+    s = scale_log2(dim)
+    S = 2.0 ** s
+    a, z = cols[0], cols[1]
+    bcols = cols[2:2 + n_sub]
+    fill = cols[2 + n_sub:2 + n_sub + 3]
+    q = np.zeros(dim, dtype=F64)
+    if side == "row":
+        # q̂: 1/2 on a, 1/4 on the 12 b columns: 1/4 + 12/16 = 1
+        assert n_sub == 12
+        q[a] = 0.5
+        q[bcols] = 0.25
+        yb = 2.0 ** -15 / S
+        sub_each = (0.25 * S) * 2.0 ** -15 / S ** 2
+    else:
+        q[a] = 0.5
+        q[fill] = 0.5
+        q[bcols] = 2.0 ** -15 / S
+        yb = 0.25
+        sub_each = 2.0 ** -15 * (0.25 * S) / S ** 2
+    qa = 0.5 * S                                   # scaled query component on a
+    # anchor: scaled value va on a with coarse qa * va / S^2 ~ 2E + 1.5e-3 (t2 ~ 1.5e-3)
+    va = float(F16((float(two_e(dim)) + 1.5e-3) * S * S / qa))
+    anchor = np.zeros(dim, dtype=F64)
+    anchor[a] = va / S
+    anchor[z] = math.sqrt(1.0 - anchor[a] ** 2)
+    c_k = F32(qa * va / S ** 2)
+    t2 = band_edge(c_k, dim)
+    # fp16 values on a around t2 / (qa / S^2)
+    center = float(t2) * S * S / qa
+    v0 = float(F16(center))
+    vals = [v0]
+    for _ in range(6):
+        vals.append(float(np.nextafter(F16(vals[-1]), F16(np.inf))))
+        vals.insert(0, float(np.nextafter(F16(vals[0]), F16(0.0))))
+    probes, subs = [], []
+    for nb in (0, n_sub // 2, n_sub):
+        for v in vals:
+            r = np.zeros(dim, dtype=F64)
+            r[a] = v / S
+            r[bcols[:nb]] = yb
+            r[z] = math.sqrt(1.0 - (r * r).sum())
+            probes.append(r)
+            subs.append(nb * sub_each)
+    return q.astype(F32), anchor.astype(F32), np.stack(probes).astype(F32), np.array(subs)
