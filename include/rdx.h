@@ -131,7 +131,10 @@ int rdx_index_set_row_ids(rdx_index* h, int64_t first_row, const int64_t* ids, i
  * "fuse_finish" 0/1 (default 1): the end-of-search work (counters and small results to pinned host memory) runs in the last
  * block of the search's last kernel instead of a launch of its own (both: speed only);
  * "retry" 0/1 (default 1): queries whose candidate
- * segments overflow get a second MFMA pass as a small batch (denser threshold sample) before the exact full scan. */
+ * segments overflow get a second MFMA pass as a small batch (denser threshold sample) before the exact full scan;
+ * "coarse_i8" 0/1/2 (default 2): the main scan of more than 128 queries at dim_pad <= 1024 (a multiple of 128) on int8 MFMA over a
+ * block-scaled int8 copy of the corpus (built by the first search that needs it, +1 B per element; not persisted), with an error
+ * bound of its own per query: 0 never, 1 whenever the shape allows, 2 for more than 256 queries on at least 2^20 rows (speed only). */
 int rdx_index_set_option(rdx_index* h, const char* name, int64_t value);
 
 /* The main scan's tile shares of the 8 XCDs (1.0 = an eighth; option "xcd_balance"): learned from the workgroups' own time stamps
@@ -324,6 +327,9 @@ typedef struct rdx_search_stats {
     float tau_rank;           /* rank of the sampled score the scan threshold was taken from: k = provable, < k = speculative (verified per query) */
 } rdx_search_stats;
 int rdx_search_last_stats(rdx_index* h, rdx_search_stats* out);
+/* Which coarse pass the last rdx_search's main scan ran: 16 (fp16 MFMA), 8 (int8 MFMA, option "coarse_i8") or 0 (the exact
+ * full scan alone). Both coarse passes give the same ids and score bits. */
+int rdx_search_last_coarse_bits(rdx_index* h, int32_t* bits);
 
 /* BM25 sparse retrieval ----------------------------------------------------------------------- */
 /* The sparse half of the reference's hybrid retrieval: rank_bm25 0.2.2 BM25Okapi scores (k1 = 1.5, b = 0.75, epsilon = 0.25)

@@ -95,6 +95,7 @@ SYMBOLS = {
     "rdx_signal_wait": (_i, [_vp, _vp, ctypes.POINTER(ctypes.c_int32)]),
     "rdx_merge_topk_packed": (_i, [_i, _vp, _i64, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
     "rdx_search_last_stats": (_i, [_vp, ctypes.POINTER(SearchStats)]),
+    "rdx_search_last_coarse_bits": (_i, [_vp, ctypes.POINTER(ctypes.c_int32)]),
     "rdx_bm25_create": (_i, [_i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.POINTER(_vp)]),
     "rdx_bm25_destroy": (_i, [_vp]),
     "rdx_bm25_search": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp]),

@@ -538,4 +538,146 @@ __device__ __forceinline__ void select_dense_query(const float* __restrict__ sco
     }
 }
 
+// ---- int8 coarse pass (DESIGN.md §5 "int8 coarse pass"): block-scaled copies and their error terms ----------------------------
+__device__ __forceinline__ float wave_max_f(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+    return v;
+}
+// a float >= x (x >= 0): the error terms are rounded up, never down
+__device__ __forceinline__ float f32_up(double x) {
+    float f = (float)x;
+    if ((double)f < x) f = nextafterf(f, INFINITY);
+    return f;
+}
+__device__ __forceinline__ int8_t q8(float y, float inv) {
+    const float t = rintf(y * inv);
+    return (int8_t)fminf(fmaxf(t, -127.f), 127.f);
+}
+
+// Corpus copy, one wave per 32-row block b (the rows one wave of k_scan owns in a tile): s_b = max |y| over the block / 127,
+// c8 = rint(y / s_b) in fragment order (corpus_off8), eps_b = max over the block's rows of ||y - s_b c8||_2 (fp64, rounded up).
+// y is the normalised row exactly as k_refine re-scores it (MasterRow: the fp32 master, or the compact master's bf16 / divisor).
+// Rows past `rows` and columns past dim are zeros. eps_max (the bits of a float >= 0) takes the largest eps_b (atomicMax).
+__global__ __launch_bounds__(256) void k_quant8_corpus(MasterView master, int dim, int64_t rows, int64_t blk0, int64_t nblk,
+                                                       int8_t* __restrict__ c8, int ksteps8, float* __restrict__ sblk,
+                                                       unsigned int* __restrict__ eps_max) {
+    const int lane = threadIdx.x & 63;
+    const int64_t b = blk0 + (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (b >= blk0 + nblk) return;
+    const int n4 = dim >> 2, np4 = ksteps8 * 32;   // float4 groups of a row: real, padded
+    const int64_t r0 = b * 32;
+    const int nr = (int)(rows - r0 < 32 ? rows - r0 : 32);
+    float mx = 0.f;
+    for (int r = 0; r < nr; ++r) {
+        const MasterRow row = master_row(master, r0 + r, dim);
+        for (int g = lane; g < n4; g += 64) {
+            const float4 y = row[g];
+            mx = fmaxf(mx, fmaxf(fmaxf(fabsf(y.x), fabsf(y.y)), fmaxf(fabsf(y.z), fabsf(y.w))));
+        }
+    }
+    mx = wave_max_f(mx);
+    const float s = mx / 127.f;
+    const float inv = mx > 0.f ? 1.f / s : 0.f;   // (the rounding of inv is harmless: eps_b is measured on the c8 actually stored)
+    double worst = 0.0;
+    for (int r = 0; r < 32; ++r) {
+        const MasterRow row = master_row(master, r0 + (r < nr ? r : 0), dim);
+        double e2 = 0.0;
+        for (int g = lane; g < np4; g += 64) {
+            char4 v = make_char4(0, 0, 0, 0);
+            if (r < nr && g < n4) {
+                const float4 y = row[g];
+                v = make_char4(q8(y.x, inv), q8(y.y, inv), q8(y.z, inv), q8(y.w, inv));
+                const double d0 = (double)y.x - (double)s * v.x, d1 = (double)y.y - (double)s * v.y;
+                const double d2 = (double)y.z - (double)s * v.z, d3 = (double)y.w - (double)s * v.w;
+                e2 += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
+            }
+            *reinterpret_cast<char4*>(c8 + corpus_off8(r0 + r, 4 * g, ksteps8)) = v;
+        }
+        worst = fmax(worst, wave_sum(e2));
+    }
+    if (lane == 0) {
+        sblk[b] = s;
+        const float eps = f32_up(sqrt(worst) * (1.0 + 1e-12));
+        atomicMax(eps_max, __float_as_uint(eps));
+    }
+}
+
+// Query copy, one wave per query: t_q = max |q| / 127, q8 = rint(q / t_q) in the query-image order (query_off8), and, in fp64
+// rounded up, e_q >= ||q - t_q q8||_2 and n_q >= ||t_q q8||_2. Padding queries [n, n_pad) and padding columns are zeros.
+__global__ __launch_bounds__(256) void k_quant8_query(const float* __restrict__ qhat, int64_t n, int64_t n_pad, int dim,
+                                                      int8_t* __restrict__ qs8, int ksteps8, float* __restrict__ tq,
+                                                      float* __restrict__ eq, float* __restrict__ nqn) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (i >= n_pad) return;
+    const int n4 = dim >> 2, np4 = ksteps8 * 32;
+    const float4* q4 = reinterpret_cast<const float4*>(qhat + i * (int64_t)dim);
+    const bool real = i < n;
+    float mx = 0.f;
+    if (real)
+        for (int g = lane; g < n4; g += 64) {
+            const float4 y = q4[g];
+            mx = fmaxf(mx, fmaxf(fmaxf(fabsf(y.x), fabsf(y.y)), fmaxf(fabsf(y.z), fabsf(y.w))));
+        }
+    mx = wave_max_f(mx);
+    const float t = mx > 0.f ? mx / 127.f : 1.f;
+    const float inv = mx > 0.f ? 1.f / t : 0.f;
+    double e2 = 0.0, n2 = 0.0;
+    for (int g = lane; g < np4; g += 64) {
+        char4 v = make_char4(0, 0, 0, 0);
+        if (real && g < n4) {
+            const float4 y = q4[g];
+            v = make_char4(q8(y.x, inv), q8(y.y, inv), q8(y.z, inv), q8(y.w, inv));
+            const double a0 = (double)t * v.x, a1 = (double)t * v.y, a2 = (double)t * v.z, a3 = (double)t * v.w;
+            const double d0 = (double)y.x - a0, d1 = (double)y.y - a1, d2 = (double)y.z - a2, d3 = (double)y.w - a3;
+            e2 += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
+            n2 += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
+        }
+        *reinterpret_cast<char4*>(qs8 + query_off8(i, 4 * g, ksteps8)) = v;
+    }
+    e2 = wave_sum(e2);
+    n2 = wave_sum(n2);
+    if (lane == 0) {
+        tq[i] = t;
+        eq[i] = f32_up(sqrt(e2) * (1.0 + 1e-12));
+        nqn[i] = f32_up(sqrt(n2) * (1.0 + 1e-12));
+    }
+}
+
+// Per query, from the fp16 bootstrap's threshold T (k_tau, fp16 accumulator units): the int8 pass' error bound
+//   E_q = e_q (1 + 1e-6) + n_q eps_max + 1e-6                 (||y|| <= 1 + 1e-6, 1e-6 for the fp32 roundings)
+// and its three thresholds: thr (int8 accumulator units D s_b, what k_scan<I8> compares: coarse + E_q >= T), tau_s (score
+// units, what k_refine verifies c_k - 2E_q against: every row whose coarse score reaches tau_s was emitted) and 2E_q.
+__global__ __launch_bounds__(256) void k_tau8(const float* __restrict__ tau16, float inv_scale2, const float* __restrict__ tq,
+                                              const float* __restrict__ eq, const float* __restrict__ nqn,
+                                              const unsigned int* __restrict__ eps_max, int nq, int nq_pad,
+                                              float* __restrict__ thr, float* __restrict__ tau_s, float* __restrict__ two_e) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq_pad) return;
+    if (i >= nq) {   // padding query: never emits
+        thr[i] = INFINITY;
+        tau_s[i] = INFINITY;
+        two_e[i] = 0.f;
+        return;
+    }
+    const double E = (double)eq[i] * (1.0 + 1e-6) + (double)nqn[i] * (double)__uint_as_float(*eps_max) + 1e-6;
+    const float Ef = f32_up(E);
+    two_e[i] = f32_up(2.0 * (double)Ef);
+    const float T = tau16[i] * inv_scale2;   // (a power of two: exact; -inf stays -inf)
+    if (!(T > -INFINITY)) {
+        thr[i] = -INFINITY;
+        tau_s[i] = -INFINITY;
+        return;
+    }
+    const double t = (double)tq[i];
+    float th = (float)(((double)T - (double)Ef) / t);
+    if ((double)th * t > (double)T - (double)Ef) th = nextafterf(th, -INFINITY);   // rounded down: a lower threshold only emits more
+    thr[i] = th;
+    const double ts = (double)th * t + 1e-6;
+    float tsf = (float)ts;
+    if ((double)tsf < ts) tsf = nextafterf(tsf, INFINITY);
+    tau_s[i] = tsf;
+}
+
 }  // namespace rdx

@@ -115,6 +115,7 @@ struct SearchPlan {
     int64_t boot_tiles = 0, boot_wave_off = 0;   // the tile bootstrap's ScanParams n_tiles, wave_off, row_off, span
     int boot_row_off = 0, boot_span = 0;
     bool use_small = false;            // k_scan_small as the main scan
+    bool i8 = false;                   // the main scan runs on the int8 copies (k_scan<..., I8>; DESIGN.md §5 "int8 coarse pass")
     int64_t sample_rows = 0;
     double expected_per_query = 0.0;   // candidates per query a random corpus would emit with this sample
     uint32_t capw = 0, list_cap = 0;
@@ -177,6 +178,10 @@ struct rdx_index {
     int dense_sample = 0;    // searches left with a threshold sample twice as dense (set when a search emitted 3x a random corpus' candidates)
     int spread_boot = 1;     // option: a tile bootstrap (any not taken by k_boot) samples every div-th 32-row block instead of every div-th 256-row tile
     int spec_backoff = 0;    // searches left during which the provable threshold is used (set when a speculation failed)
+    int coarse_i8 = 2;       // option: main scan on int8 MFMA — 0 never, 1 whenever the shape allows, 2 (default) large batches on large shards
+    int coarse_bits = 0;     // the last search's coarse pass: 16, 8, or 0 (exact path only); rdx_search_last_coarse_bits
+    int i8_backoff = 0;      // searches left during which automatic choice (coarse_i8 = 2) keeps the fp16 pass (set when an int8 search
+                             // sent more than 1 in 64 of its queries to the fallback passes: rows too crowded for its band, see adapt_sampling)
     double xw[8] = {1, 1, 1, 1, 1, 1, 1, 1};   // relative speed of the XCDs as the last main scans showed it (sum 8)
     int sample_div = 64;
     int64_t cand_cap = 0;   // 0 = automatic
@@ -189,6 +194,10 @@ struct rdx_index {
     std::unordered_map<const void*, size_t> func_lds;   // dynamic-LDS limit already raised for a kernel ON THIS DEVICE
     DevBuf staging, qraw, qhat, qshadow, tau, cntw, cand, setmax, exact_list, iota, dense, ctr, bad, o_score, o_row,
         o_count, mask, ids;
+    // int8 coarse pass: corpus copy [cap][dim_pad] in corpus_off8 order + s_b per 32-row block + the largest eps_b (built by the first
+    // search that takes the path, rows [0, i8_valid) current; not persisted) and the per-search query copy, scales, bounds, thresholds
+    DevBuf c8, sblk, eps8, qshadow8, tq8, eq8, nq8, thr8, taus8, twoe8;
+    int64_t i8_valid = 0;
     // end-of-search mailbox in pinned host memory (k_finish writes it over PCIe; the host spins on its sequence number)
     Mailbox* mbox = nullptr;          // host address
     Mailbox* mbox_dev = nullptr;      // the same memory as the device sees it
@@ -363,7 +372,8 @@ extern "C" int rdx_index_destroy(rdx_index* h) {
     if (h->row_map) (void)hipFree(h->row_map);
     for (DevBuf* b : {&h->staging, &h->qraw, &h->qhat, &h->qshadow, &h->tau, &h->cntw, &h->cand, &h->setmax, &h->exact_list,
                       &h->iota, &h->dense, &h->ctr, &h->bad, &h->o_score, &h->o_row, &h->o_count, &h->mask, &h->ids,
-                      &h->r_list, &h->r_q, &h->r_s, &h->r_r, &h->r_c})
+                      &h->r_list, &h->r_q, &h->r_s, &h->r_r, &h->r_c, &h->c8, &h->sblk, &h->eps8, &h->qshadow8, &h->tq8,
+                      &h->eq8, &h->nq8, &h->thr8, &h->taus8, &h->twoe8})
         b->release();
     if (h->mbox) (void)hipHostFree(h->mbox);
     if (h->pin_out) (void)hipHostFree(h->pin_out);
@@ -407,6 +417,11 @@ extern "C" int rdx_index_set_option(rdx_index* h, const char* name, int64_t valu
     else if (n == "small_scan") h->small_scan = value != 0;
     else if (n == "half_boot") h->half_boot = value != 0;
     else if (n == "spread_boot") h->spread_boot = value != 0;
+    else if (n == "coarse_i8") {
+        if (value < 0 || value > 2) return fail(RDX_ERR_INVALID, "coarse_i8 must be 0 (never), 1 (whenever the shape allows) or 2 (automatic)");
+        h->coarse_i8 = (int)value;
+        h->i8_backoff = 0;
+    }
     else if (n == "spec_tau") {
         h->spec_tau = value != 0;
         h->spec_backoff = 0;
@@ -464,6 +479,8 @@ static const int64_t STAGE_ROWS = 32768;
 static int ingest(rdx_index* h, const void* rows, bool is_bf16, int64_t n, int space, int64_t row0, const int64_t* d_dst_ids,
                   bool verbatim = false) {
     hipStream_t st = h->own_stream;
+    // the int8 copy: an update may touch any block, an append the last partial one and the new ones
+    h->i8_valid = d_dst_ids ? 0 : std::min<int64_t>(h->i8_valid, row0 / 32 * 32);
     if (space == RDX_DEVICE) HIP_TRY(hipDeviceSynchronize());   // the caller's producers of `rows` (any stream) are done
     const size_t esz = is_bf16 ? 2 : 4;
     RDX_TRY(h->bad.ensure(sizeof(int)));
@@ -625,6 +642,7 @@ extern "C" int rdx_index_compact(rdx_index* h, const int64_t* keep, int64_t n_ke
     h->shadow = ns;
     h->cap = ncap;
     h->rows = n_keep;
+    h->i8_valid = 0;
     return RDX_OK;
 }
 
@@ -1016,11 +1034,11 @@ static int ensure_dynamic_lds(rdx_index* h, const void* func, size_t bytes) {
     return RDX_OK;
 }
 
-template <int BN, int EPI, bool RES, bool NTT = false, bool FUSED = false>
+template <int BN, int EPI, bool RES, bool NTT = false, bool FUSED = false, bool I8 = false>
 static int launch_scan(rdx_index* h, const ScanParams& p, int grid, hipStream_t st) {
     // LDS: query-image ring (or the whole resident query tile) + BN hit counters + BN thresholds
-    const size_t lds = (size_t)(RES ? p.ksteps : RING_SLOTS) * BN * BK * 2 + BN * 8;
-    void (*kern)(const ScanParams) = p.allow ? k_scan<BN, EPI, true, RES, NTT, FUSED> : k_scan<BN, EPI, false, RES, NTT, FUSED>;
+    const size_t lds = (size_t)(RES ? p.ksteps : RING_SLOTS) * BN * BK * 2 + BN * (I8 ? 12 : 8);   // (I8: + BN query scales)
+    void (*kern)(const ScanParams) = p.allow ? k_scan<BN, EPI, true, RES, NTT, FUSED, I8> : k_scan<BN, EPI, false, RES, NTT, FUSED, I8>;
     RDX_TRY(ensure_dynamic_lds(h, (const void*)kern, lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, p);
     HIP_TRY(hipGetLastError());
@@ -1052,6 +1070,14 @@ static int launch_scan_bn(rdx_index* h, int bn, bool res, const ScanParams& p, i
     }
     if (p.nqt == 1) return launch_scan<256, EPI, false, true>(h, p, grid, st);   // one query tile: corpus read once -> nt loads
     return launch_scan<256, EPI, false>(h, p, grid, st);
+}
+
+// the int8 main pass (plan_search p.i8: 256-query tiles, several of them, so never the one-tile nt variants)
+static int launch_scan_i8(rdx_index* h, const ScanParams& p, int grid, hipStream_t st) {
+#ifndef RDX_CHECK_BOUNDS
+    if ((p.ksteps & 1) == 0 && h->fuse_epilogue) return launch_scan<256, EPI_EMIT, false, false, true, true>(h, p, grid, st);
+#endif
+    return launch_scan<256, EPI_EMIT, false, false, false, true>(h, p, grid, st);
 }
 
 static const int K_FAST_MAX = 256;   // larger k goes through the exact full scan
@@ -1239,9 +1265,16 @@ static int plan_search(const rdx_index& h, int64_t nq, int k, int depth, bool ho
     p.exact_only = h.force_exact || k > K_FAST_MAX || k == 0 || h.rows < 1 || (small && !h.force_fast);
     if (p.exact_only) return RDX_OK;
 
+    // The main scan on int8 MFMA (twice the dot products per clock of fp16, half the bytes; DESIGN.md §5 "int8 coarse pass"): the
+    // caller's batch only (not the second pass), in 256-query tiles, at most 8 k-steps of 128 dimensions (|D| < 2^24: exact in fp32).
+    // Automatic (option 2): more than one query tile on a shard of at least 2^20 rows, where the MFMA rate decides the scan's time;
+    // the bootstrap, the second pass and the exact scan stay fp16 / fp32.
+    const bool i8_shape = depth == 0 && nq > 128 && h.dim_pad % 128 == 0 && h.dim_pad <= 1024 && h.force_bn == 0;
+    p.i8 = i8_shape && (h.coarse_i8 == 1 || (h.coarse_i8 == 2 && h.i8_backoff == 0 && nq > 256 && h.rows >= ((int64_t)1 << 20)));
+
     // queries per workgroup: 64 (tile resident in LDS), 128, 256. 257..384 queries run as three 128-query tiles rather than
     // one full and one half-empty 256-query tile (measured at 1M x 1024, B = 384: 0.78 vs 0.84 ms; tools/bn_sweep.py)
-    p.bn = nq <= 64 ? 64 : (nq <= 128 ? 128 : ((nq > 256 && nq <= 384) ? 128 : 256));
+    p.bn = nq <= 64 ? 64 : (nq <= 128 ? 128 : ((nq > 256 && nq <= 384 && !p.i8) ? 128 : 256));
     if (h.force_bn && (nq + h.force_bn - 1) / h.force_bn <= 32) p.bn = h.force_bn;   // developer option: queries per workgroup
     p.nqt = (int)((nq + p.bn - 1) / p.bn);
     p.grid = std::max(8, h.n_cu / 8 * 8);
@@ -1278,6 +1311,13 @@ static int plan_search(const rdx_index& h, int64_t nq, int k, int depth, bool ho
     // while: +0.25 ms of bootstrap on a 10 M-row scan, against thousands of surplus candidates per query to gather and re-score
     // (measured, embedding-like corpus at c4: 19.6 -> 16.2 ms per batch; N(0,1) corpus: +1 %, which is why it is not the default).
     else if (h.dense_sample > 0 && div > 1) div = std::max(1, div / 2);
+    // The int8 pass emits every row whose coarse score is within E_q (~0.6 sigma of a random corpus' scores at d = 1024) of the
+    // threshold: a threshold closer to the corpus' k-th score pays for its sample many times over. Measured on c4 (the refine list
+    // holds 7 168 hits): every 64th block 7 900 hits per query, 573 of 1 024 queries re-run; every 32nd 5 400 / 134; every 16th 2 600 /
+    // 0; every 8th, 2 640 hits, 11.8 ms per batch (iid) and 5 000 hits, 12.4 ms (embedding-like). The factor is measured at d = 1024 only; E_q relative to the score spread depends on d (both
+    // quantisation errors grow like the element spacing, the spread like 1/sqrt(d)), so at other widths it is a choice, not a derivation:
+    // what protects those shapes is the fallback, and automatic choice backs off from int8 when it overflows (adapt_sampling).
+    if (p.i8 && depth == 0) div = std::max(1, div / 8);
     int64_t n_sched = (p.n_tiles + div - 1) / div;
     // whole rounds only: the bootstrap takes as long as its busiest stream, so 77 tiles on 64 streams cost two tiles' time for
     // 1.2 tiles' worth of threshold (a 1.25 M-row shard at B = 1024: 53 -> 27 us of a 2.26 ms search); thin the sample to the
@@ -1323,7 +1363,11 @@ static int plan_search(const rdx_index& h, int64_t nq, int k, int depth, bool ho
         p.n_sets_used = p.boot_sets;
     }
     // slots per (query, stream) segment: 8x the expected hits, power of two, [32, 4096]
-    const double exp_hits = (1.5 * k * (double)h.rows / (double)std::max<int64_t>(p.sample_rows, 1) + k) / p.n_streams;
+    double exp_hits = (1.5 * k * (double)h.rows / (double)std::max<int64_t>(p.sample_rows, 1) + k) / p.n_streams;
+    // int8: the scan emits coarse + E_q >= T, E_q ~ 0.6 sigma of a random corpus' scores at d = 1024 — about 16x what the fp16 pass
+    // would emit from the same sample (measured at 10 M x 1024 with the 8x denser sample above: 2 640 hits per query against 146;
+    // DESIGN.md §5; a measured factor at d = 1024, not derived for other widths)
+    if (p.i8) exp_hits *= 16.0;
     p.expected_per_query = exp_hits * p.n_streams;
     // (slots cost address space, not bandwidth: only occupied slots are ever touched)
     // (nq_pad * n_streams is 65,536 whatever the batch: 1024 slots = 512 MiB, 4096 = 2 GiB of the 288)
@@ -1431,6 +1475,12 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
     hipLaunchKernelGGL(k_tau, dim3(p.nq_pad), dim3(256), 0, st, h->setmax.as<float>(), p.use_boot ? p.boot_sets : p.n_sets_b, p.n_sets_used,
                        p.k_sel, p.k_sel == p.k ? p.slack * std::ldexp(1.0f, 2 * h->scale_log2) : 0.0f, (int)p.nq, h->tau.as<float>());
     HIP_TRY(hipGetLastError());
+    if (p.i8) {
+        hipLaunchKernelGGL(k_tau8, dim3((p.nq_pad + 255) / 256), dim3(256), 0, st, h->tau.as<float>(), std::ldexp(1.0f, -2 * h->scale_log2),
+                           h->tq8.as<float>(), h->eq8.as<float>(), h->nq8.as<float>(), h->eps8.as<unsigned int>(), (int)p.nq, p.nq_pad,
+                           h->thr8.as<float>(), h->taus8.as<float>(), h->twoe8.as<float>());
+        HIP_TRY(hipGetLastError());
+    }
     mark(h, p, st, 3);
     sp.tile_stride = 1;
     sp.use_xlo = p.balance ? 1 : 0;
@@ -1453,6 +1503,16 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
         ss.wgt = sp.wgt;
         hipLaunchKernelGGL(k_scan_small, dim3((unsigned)p.grid), dim3(512), 0, st, ss);
         HIP_TRY(hipGetLastError());
+    } else if (p.i8) {
+        ScanParams s8 = sp;
+        s8.shadow = reinterpret_cast<const _Float16*>(h->c8.p);
+        s8.qshadow = reinterpret_cast<const _Float16*>(h->qshadow8.p);
+        s8.ksteps = h->dim_pad / 128;
+        s8.tau = h->thr8.as<float>();
+        s8.sblk = h->sblk.as<float>();
+        s8.qscale = h->tq8.as<float>();
+        s8.shadow_bytes = (int64_t)h->cap * h->dim_pad;
+        RDX_TRY(launch_scan_i8(h, s8, p.grid, st));
     } else {
         RDX_TRY(launch_scan_bn<EPI_EMIT>(h, p.bn, p.res, sp, p.grid, st));
     }
@@ -1460,10 +1520,38 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
     const size_t lds = (size_t)p.list_cap * 8;
     RDX_TRY(ensure_dynamic_lds(h, (const void*)k_refine, lds));
     hipLaunchKernelGGL(k_refine, dim3((int)p.nq), dim3(1024), lds, st, h->cand.as<uint2>(), h->cntw.as<uint32_t>(), p.n_streams, p.capw,
-                       p.list_cap, p.k, h->two_e(), h->qhat.as<float>(), h->mv(), h->dim, h->row_base, h->row_map, io.score, io.row, io.count,
-                       h->exact_list.as<int32_t>(), h->ctr.as<RefineCounters>(), h->tau.as<float>(), sp.inv_scale2, fin);
+                       p.list_cap, p.k, h->two_e(), p.i8 ? h->twoe8.as<float>() : nullptr, h->qhat.as<float>(), h->mv(), h->dim, h->row_base,
+                       h->row_map, io.score, io.row, io.count, h->exact_list.as<int32_t>(), h->ctr.as<RefineCounters>(),
+                       p.i8 ? h->taus8.as<float>() : h->tau.as<float>(), p.i8 ? 1.0f : sp.inv_scale2, fin);
     HIP_TRY(hipGetLastError());
     mark(h, p, st, 5);
+    return RDX_OK;
+}
+
+// int8 pass: bring the corpus copy up to date (blocks from the watermark on; the whole copy after an update, a compaction or a
+// reallocation) and quantise the queries (from qhat, which k_refine re-scores with)
+static int prepare_i8(rdx_index* h, const SearchPlan& p, hipStream_t st) {
+    const int ks8 = h->dim_pad / 128;
+    const void* old_c8 = h->c8.p;
+    const void* old_sb = h->sblk.p;
+    const void* old_eps = h->eps8.p;
+    RDX_TRY(h->c8.ensure((size_t)h->cap * h->dim_pad));
+    RDX_TRY(h->sblk.ensure((size_t)(h->cap / 32) * 4));
+    RDX_TRY(h->eps8.ensure(4));
+    if (h->c8.p != old_c8 || h->sblk.p != old_sb || h->eps8.p != old_eps) h->i8_valid = 0;   // (a reallocation loses the contents)
+    if (h->i8_valid < h->rows) {
+        if (h->i8_valid == 0) HIP_TRY(hipMemsetAsync(h->eps8.p, 0, 4, st));
+        const int64_t b0 = h->i8_valid / 32, nb = (h->rows + 31) / 32 - b0;
+        hipLaunchKernelGGL(k_quant8_corpus, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, h->mv(), h->dim, h->rows, b0, nb,
+                           h->c8.as<int8_t>(), ks8, h->sblk.as<float>(), h->eps8.as<unsigned int>());
+        HIP_TRY(hipGetLastError());
+        h->i8_valid = h->rows;
+    }
+    RDX_TRY(h->qshadow8.ensure((size_t)p.nq_pad * h->dim_pad));
+    for (DevBuf* b : {&h->tq8, &h->eq8, &h->nq8, &h->thr8, &h->taus8, &h->twoe8}) RDX_TRY(b->ensure((size_t)p.nq_pad * 4));
+    hipLaunchKernelGGL(k_quant8_query, dim3((p.nq_pad + 3) / 4), dim3(256), 0, st, h->qhat.as<float>(), p.nq, (int64_t)p.nq_pad, h->dim,
+                       h->qshadow8.as<int8_t>(), ks8, h->tq8.as<float>(), h->eq8.as<float>(), h->nq8.as<float>());
+    HIP_TRY(hipGetLastError());
     return RDX_OK;
 }
 
@@ -1496,6 +1584,7 @@ static int enqueue_search(rdx_index* h, const SearchPlan& p, const SearchIO& io,
                        (const int64_t*)nullptr, (int64_t)0, MasterView{h->qhat.as<float>(), nullptr, nullptr}, h->qshadow.as<_Float16>(), h->ksteps, h->scale(),
                        d_bad, (int64_t)p.nq_pad, p.depth > 0 ? 1 : 0);   // depth 1: the rows ARE normalised queries (gathered from qhat): kept bit for bit
     HIP_TRY(hipGetLastError());
+    if (p.i8) RDX_TRY(prepare_i8(h, p, st));
     mark(h, p, st, 1);
 
     const FinishArgs fin = finish_args(h, p, io, *seq);
@@ -1564,6 +1653,16 @@ static int read_mailbox(rdx_index* h, const PendingSearch& ps, SearchCounts* c) 
 // the sampling state the next searches start from
 static void adapt_sampling(rdx_index* h, const SearchPlan& p, const SearchCounts& c) {
     if (p.depth != 0) return;
+    // Automatic int8 pass: its band is E_q wide (~0.6 sigma of a random corpus' scores at d = 1024). On rows that crowd around a
+    // query's neighbours (a document's chunks) the hits can overflow the refine list and every such query pays the
+    // fp16 second pass on top; when more than 1 in 64 queries of an int8 search did, the next 256 searches take the fp16 pass, after
+    // which int8 is tried again. (Measured on the embedding-like c4 corpus: 5 000 hits per query, none re-run, int8 12.4 ms against
+    // fp16 16.0 ms per batch — the safeguard is for corpora more crowded than that.)
+    if (p.i8 && h->coarse_i8 == 2 && !p.exact_only) {
+        if ((int64_t)c.n_exact * 64 > p.nq) h->i8_backoff = 256;
+    } else if (h->i8_backoff > 0 && p.nq > 256) {
+        --h->i8_backoff;
+    }
     if (h->mbox->spec_fail > 0) h->spec_backoff = 64;   // a speculative threshold was too high: provable thresholds for a while
     // three times the candidates a random corpus would emit: the corpus is clustered — a denser threshold sample for the next searches
     // (plan_search; re-examined every 256 searches: the denser sample's own emission is what then keeps it on)
@@ -1722,6 +1821,7 @@ static int search_chunk(rdx_index* h, const SearchIO& io, int64_t nq, int k, hip
     SearchPlan plan;
     unsigned long long seq = 0;
     int rc = plan_search(*h, nq, k, depth, ho != nullptr, &plan);
+    if (rc == RDX_OK && depth == 0) h->coarse_bits = plan.exact_only ? 0 : (plan.i8 ? 8 : 16);
     if (rc == RDX_OK) rc = enqueue_search(h, plan, io, ho, st, &seq);
     if (rc == RDX_OK) {
         if (!plan.exact_only) acc->tau_rank = (float)plan.k_sel;
@@ -1906,6 +2006,13 @@ extern "C" int rdx_debug_select_stamps(unsigned long long* out16) {
     return hipMemcpyFromSymbol(out16, HIP_SYMBOL(rdx::g_select_stamps), 16 * sizeof(unsigned long long)) == hipSuccess ? 0 : 2;
 }
 #endif
+
+extern "C" int rdx_search_last_coarse_bits(rdx_index* h, int32_t* bits) {
+    if (!h || !bits) return fail(RDX_ERR_INVALID, "rdx_search_last_coarse_bits: null pointer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    *bits = h->coarse_bits;
+    return RDX_OK;
+}
 
 extern "C" int rdx_search_last_stats(rdx_index* h, rdx_search_stats* out) {
     if (!h || !out) return fail(RDX_ERR_INVALID, "rdx_search_last_stats: null pointer");

@@ -24,6 +24,7 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TILE_ROWS = 256;                    // corpus rows per scan tile / shadow block
 constexpr int BK = 64;                            // k elements per k-step image
@@ -47,6 +48,25 @@ __host__ __device__ inline int64_t query_off(int64_t r, int k, int ksteps) {
     const int chunk = (k & 63) >> 3;
     const int slot = chunk ^ ((rr >> 1) & 7);
     return ((blk * ksteps + ks) * 256 + rr) * 64 + slot * 8 + (k & 7);
+}
+
+// The int8 scan copies (large query batches, DESIGN.md §5 "int8 coarse pass"): the same fragment geometry with BYTES, so that one
+// 1 KiB chunk is one A operand of v_mfma_i32_16x16x64_i8 (16 rows x 64 k) and one k-step covers 128 dimensions.
+// corpus: byte offset of (row r, column k); lane l of chunk (rb, c = k/64, m) holds row rb*32 + m*16 + (l & 15), k = c*64 + 16*(l >> 4) + 0..15
+__host__ __device__ inline int64_t corpus_off8(int64_t r, int k, int ksteps8) {
+    const int64_t rb = r >> 5;
+    const int m = (int)((r >> 4) & 1), c = k >> 6;
+    const int lane16 = (int)(r & 15) + (((k & 63) >> 4) << 4);
+    return (((rb * (ksteps8 * 2) + c) * 2 + m) * 64 + lane16) * 16 + (k & 15);
+}
+// queries: [block of 256][k-step of 128][256 rows][128 B], 16-B chunk c (dimensions 16c..16c+15 of the step) in slot c ^ ((r >> 1) & 7)
+__host__ __device__ inline int64_t query_off8(int64_t r, int k, int ksteps8) {
+    const int64_t blk = r >> 8;
+    const int rr = (int)(r & 255);
+    const int ks = k >> 7;
+    const int chunk = (k & 127) >> 4;
+    const int slot = chunk ^ ((rr >> 1) & 7);
+    return ((blk * ksteps8 + ks) * 256 + rr) * 128 + slot * 16 + (k & 15);
 }
 
 // "lane order" reduction shared with oracle/rdx_oracle.c: butterfly p[l] += p[l ^ m], m = 32..1

@@ -137,7 +137,7 @@ __device__ unsigned long long g_refine_stamps[16];
 
 __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, const uint32_t* __restrict__ cntw,
                                                 int n_streams, uint32_t capw, uint32_t list_cap, int k, float two_e,
-                                                const float* __restrict__ qhat, MasterView master, int dim,
+                                                const float* __restrict__ two_e_q, const float* __restrict__ qhat, MasterView master, int dim,
                                                 int64_t row_base, const int64_t* __restrict__ row_map,
                                                 float* __restrict__ out_score, int64_t* __restrict__ out_row,
                                                 int32_t* __restrict__ out_count, int32_t* __restrict__ exact_list,
@@ -203,7 +203,8 @@ __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, con
     const int64_t kk = (uint32_t)k < m ? k : m;
     int64_t n_gt;
     const uint32_t kth = block_kth_largest([&](int64_t i) { return f2key(__uint_as_float(list[i].x)); }, m, kk, hist, bc, &n_gt);
-    const float t2 = key2f(kth) - two_e;
+    // (int8 coarse pass: the bound is the query's own, two_e_q[q] = 2 E_q, and tau is already in score units — DESIGN.md §5)
+    const float t2 = key2f(kth) - (two_e_q ? two_e_q[q] : two_e);
     RDX_RSTAMP(3);
     // Verification of the scan's threshold T (score units). The hits are exactly the allowed rows with coarse >= T. The k best of
     // them have exact >= c_k - E, so the exact k-th best of the corpus is >= c_k - E and every true top-k row has coarse >=
@@ -212,7 +213,19 @@ __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, con
     // lies) passes unless the estimate was too high — then the query goes to the fallback passes, which use
     // the provable threshold. T = -inf (fewer than k sets sampled): every allowed row was emitted, nothing to verify.
     const float tq = tau[q] * inv_scale2;
-    if (tq > -INFINITY && ((int64_t)m < (int64_t)k || t2 < tq)) {
+    // int8 coarse pass: verified AFTER the exact re-score, against the exact k-th score X of the hits (a row that was not emitted
+    // scores below tau + E_q exactly: the answer is complete iff X - E_q >= tau). Its E_q is ~14x the fp16 E, and the
+    // test before the re-score (c_k - 2E >= tau) would reject most speculative thresholds.
+    const bool late = two_e_q != nullptr;
+    auto verify_exact = [&](uint32_t kth_key) __attribute__((always_inline)) {
+        if (!late || !(tq > -INFINITY) || key2f(kth_key) - 0.5f * two_e_q[q] >= tq) return true;
+        if (threadIdx.x == 0) {
+            atomicAdd(&ctr->spec_fail, 1);
+            exact_list[atomicAdd(&ctr->n_exact, 1)] = q;
+        }
+        return false;
+    };
+    if (tq > -INFINITY && ((int64_t)m < (int64_t)k || (!late && t2 < tq))) {
         if (threadIdx.x == 0) {
             atomicAdd(&ctr->spec_fail, 1);
             exact_list[atomicAdd(&ctr->n_exact, 1)] = q;
@@ -323,6 +336,7 @@ __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, con
         const int64_t kk2 = k < p ? k : p;
         int64_t n_gt2;
         const uint32_t kth2 = block_kth_largest([&](int64_t i) { return f2key(__uint_as_float(list[i].x)); }, p, kk2, hist, bc, &n_gt2);
+        if (!verify_exact(kth2)) return;
         if (threadIdx.x == 0) n_p = 0;
         __syncthreads();
         // everything above the k-th key, and EVERY entry equal to it (identical rows tie: the ranking below orders them by row id)
@@ -350,6 +364,11 @@ __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, con
     RDX_RSTAMP(4);
     rescore(p, [&](int i) { return s_r[i]; }, [&](int i, float sx) { s_s[i] = sx; });
     __syncthreads();
+    if (late) {
+        int64_t n_gt3;
+        const uint32_t kth3 = block_kth_largest([&](int64_t i) { return f2key(s_s[i]); }, p, (int64_t)(k < p ? k : p), hist, bc, &n_gt3);
+        if (!verify_exact(kth3)) return;
+    }
     RDX_RSTAMP(5);
     // local -> returned row id: + row_base, or through the shard's (strictly increasing) row id map
     for (int i = threadIdx.x; i < p; i += blockDim.x) s_r[i] = row_map ? row_map[s_r[i]] : s_r[i] + row_base;
@@ -360,13 +379,13 @@ __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, con
 
 __global__ __launch_bounds__(1024) void k_refine(const uint2* __restrict__ cand, const uint32_t* __restrict__ cntw,
                                                 int n_streams, uint32_t capw, uint32_t list_cap, int k, float two_e,
-                                                const float* __restrict__ qhat, MasterView master, int dim,
+                                                const float* __restrict__ two_e_q, const float* __restrict__ qhat, MasterView master, int dim,
                                                 int64_t row_base, const int64_t* __restrict__ row_map,
                                                 float* __restrict__ out_score, int64_t* __restrict__ out_row,
                                                 int32_t* __restrict__ out_count, int32_t* __restrict__ exact_list,
                                                 RefineCounters* __restrict__ ctr, const float* __restrict__ tau, float inv_scale2,
                                                 const FinishArgs fin) {
-    refine_query(cand, cntw, n_streams, capw, list_cap, k, two_e, qhat, master, dim, row_base, row_map, out_score, out_row, out_count,
+    refine_query(cand, cntw, n_streams, capw, list_cap, k, two_e, two_e_q, qhat, master, dim, row_base, row_map, out_score, out_row, out_count,
                  exact_list, ctr, tau, inv_scale2);
     finish_if_last(fin);
 }

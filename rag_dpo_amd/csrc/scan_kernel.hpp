@@ -78,6 +78,10 @@ struct ScanParams {
     int use_xlo, bulk_it;      // main pass: after bulk_it interleaved iterations per stream, XCD x owns the schedule range
     int xlo[9];                //   [xlo[x], xlo[x+1]) (the XCDs of one chip do not run equally fast; the host sizes the ranges from the
     unsigned long long* wgt;   //   [grid][2] start / end wall_clock64 of every workgroup (NULL: not wanted)   finish times)
+    // I8 (int8 main pass, DESIGN.md §5 "int8 coarse pass"): shadow / qshadow are the int8 copies (corpus_off8 / query_off8), ksteps
+    // counts 128-dimension steps, tau is in units of t_q (the query's scale) and a 32-row block b scores (float)D * sblk[b] there
+    const float* sblk;         // [32-row blocks] s_b
+    const float* qscale;       // [nq_pad] t_q: score = (float)D * s_b * t_q
     int64_t shadow_bytes;      // RDX_CHECK_BOUNDS builds: size of the scan copy ...
     int* oob;                  // ... and the flag a corpus read outside it raises (tests/test_gpu_bounds.py)
 };
@@ -101,8 +105,13 @@ __device__ __forceinline__ void wait_vmcnt_keep(half8 (&a)[4]) {
 
 // FUSEDT (EMIT, BN = 256, even number of k-steps per tile — the host checks): a tile's emit check rides with the first
 // k-step of the next tile instead of interrupting the MFMA stream (see `step`).
-template <int BN, int EPI, bool HAS_MASK, bool RES, bool NTT = false, bool FUSEDT = false>
+// I8: the int8 main pass (EMIT, BN = 256 only): the same bytes move the same way; v_mfma_i32_16x16x64_i8 takes the cycles of the
+// fp16 instruction for twice the k, so a k-step covers 128 dimensions; the accumulators are exact int32 dot products D of the
+// quantised rows, the check compares (float)max D * s_b (one s_b per wave and tile: the block's scale) with thr in t_q units.
+template <int BN, int EPI, bool HAS_MASK, bool RES, bool NTT = false, bool FUSEDT = false, bool I8 = false>
 __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
+    static_assert(!I8 || (EPI == EPI_EMIT && BN == 256 && !RES), "int8 pass: main scan of 256-query tiles only");
+    using accv = std::conditional_t<I8, i32x4, f32x4>;
     constexpr bool FUSED = FUSEDT && EPI == EPI_EMIT;
     constexpr bool NT_A = NTT;            // host: NTT launches have ONE query tile (every corpus byte is read by one workgroup)
     constexpr int B_BYTES = BN * BK * 2;  // one k-step image of this workgroup's queries
@@ -186,13 +195,17 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
     // col = lane & 15 (query), row = (lane >> 4) * 4 + reg
     constexpr int NB16 = BN / 16;
     const int l15 = lane & 15, lq = lane >> 4;
-    f32x4 acc[2][NB16];
+    accv acc[2][NB16];
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int n = 0; n < NB16; ++n)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc[m][n][r] = 0.f;
+            for (int r = 0; r < 4; ++r) acc[m][n][r] = 0;
+    auto mma = [](const half8& a, const half8& b, const accv& c) __attribute__((always_inline)) {
+        if constexpr (I8) return __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b), c, 0, 0, 0);
+        else return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+    };
     float runmax[EPI == EPI_SETMAX ? NB16 : 1][1];
     float* tau_s = reinterpret_cast<float*>(lcnt + BN);   // [BN] thresholds of this query tile (LDS: registers are scarce)
     if constexpr (EPI == EPI_SETMAX) {
@@ -203,6 +216,8 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
     } else {
         // stored [l15][n] so that one ds_read_b128 fetches the thresholds of four consecutive query blocks of a lane
         for (int i = threadIdx.x; i < BN; i += 512) tau_s[(i & 15) * (BN / 16) + (i >> 4)] = p.tau[qt * BN + i];
+        if constexpr (I8)   // the rare emit path's t_q from LDS: a global load there would make the compiler drain vmcnt(0) (the asm prefetches)
+            for (int i = threadIdx.x; i < BN; i += 512) tau_s[BN + i] = p.qscale[qt * BN + i];
     }
 
     // LDS address of this lane's query fragment for k sub-step kk (16-query block n adds n*2048), swizzled:
@@ -236,17 +251,35 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
         asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
         return r;
     };
-    auto block_max = [&](int n) __attribute__((always_inline)) {
-        const float t1 = max3(acc[0][n][0], acc[0][n][1], acc[0][n][2]);
-        const float t2 = max3(acc[1][n][0], acc[1][n][1], acc[1][n][2]);
-        return max3(max3(t1, t2, acc[0][n][3]), acc[1][n][3], acc[1][n][3]);
+    auto max3i = [](int a, int b, int c) __attribute__((always_inline)) {
+        int r;
+        asm("v_max3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+        return r;
+    };
+    // I8: in t_q units, (float)max D * s_b — float conversion and the product with s_b > 0 are monotone, so this is the block's
+    // largest (float)D * s_b, the value the thresholds were set for
+    auto block_max = [&](int n, float sb) __attribute__((always_inline)) {
+        if constexpr (I8) {
+            const int t1 = max3i(acc[0][n][0], acc[0][n][1], acc[0][n][2]);
+            const int t2 = max3i(acc[1][n][0], acc[1][n][1], acc[1][n][2]);
+            return (float)max3i(max3i(t1, t2, acc[0][n][3]), acc[1][n][3], acc[1][n][3]) * sb;
+        } else {
+            const float t1 = max3(acc[0][n][0], acc[0][n][1], acc[0][n][2]);
+            const float t2 = max3(acc[1][n][0], acc[1][n][1], acc[1][n][2]);
+            return max3(max3(t1, t2, acc[0][n][3]), acc[1][n][3], acc[1][n][3]);
+        }
+    };
+    // I8: s_b of this wave's 32-row block of schedule entry it_done (wave-uniform: a scalar load)
+    auto block_scale = [&](int it_done) __attribute__((always_inline)) -> float {
+        if constexpr (I8) return p.sblk[(int64_t)sched_of(it_done) * 8 + wave];
+        else return 1.f;
     };
     // EMIT, rare path (a handful of blocks per tile): append the hits of block n to the (query, stream) segments. Slot from an
     // LDS counter (inline asm: next to LDS-DMA the compiler would put s_waitcnt vmcnt(0) in front of an LDS atomic and drain
     // the prefetch pipeline on every hit), 8-byte fire-and-forget store.
     uint2* const cand_s = p.cand;
     const uint32_t capw_s = p.capw;
-    auto emit_block = [&](int n, float tq, int it_done) __attribute__((always_inline)) {
+    auto emit_block = [&](int n, float tq, int it_done, float sb) __attribute__((always_inline)) {
         int64_t row_b;
         uint32_t okbits;
         bool filt;
@@ -261,16 +294,17 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
         // store address is an SGPR base + a 32-bit lane offset, no 64-bit vector arithmetic
         const uint32_t seg0 = ((uint32_t)(qt * BN + ql) * (uint32_t)n_streams + (uint32_t)stream) * capw_s;
         const uint32_t row0 = (uint32_t)row_b + (uint32_t)lr;
+        const float to_score = I8 ? tau_s[BN + ql] : p.inv_scale2;
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float v = acc[m][n][r];
+                const float v = I8 ? (float)acc[m][n][r] * sb : (float)acc[m][n][r];
                 if (v >= tq && (!filt || ((okbits >> (m * 16 + r + lr)) & 1u))) {
                     uint32_t pos;
                     const uint32_t lds_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(&lcnt[ql]);
                     asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(pos) : "v"(lds_addr), "v"(1u) : "memory");
-                    if (pos < capw_s) cand_s[seg0 + pos] = make_uint2(__float_as_uint(v * p.inv_scale2), row0 + (uint32_t)(m * 16 + r));
+                    if (pos < capw_s) cand_s[seg0 + pos] = make_uint2(__float_as_uint(v * to_score), row0 + (uint32_t)(m * 16 + r));
                 }
             }
     };
@@ -372,11 +406,18 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
             const char* stn = smem + (RES ? ksn : ((slot_c + 1) & 3)) * B_BYTES;   // image of step s+1
             const bool more = s + AD < total;   // step s+AD exists; otherwise re-read this stream's first step (never used)
             const char* an = RUNNING_A ? (more ? a_next : a_first) : a_src(more ? it2 : 0, more ? ks2 : 0);
+            if constexpr (I8 && !FUSED) {   // (the int8 variant with the stand-alone check otherwise keeps this uniform address in VGPRs)
+                const uint64_t u = (uint64_t)(uintptr_t)an;
+                an = reinterpret_cast<const char*>(((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(u >> 32)) << 32) |
+                                                   (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)u));
+            }
             float tq_cur = 0.f;   // FUSE: this lane's threshold for the next block to check, fetched one block ahead
             int tb = l15 * NB16;
+            float sb_prev = 1.f;  // FUSE, I8: s_b of the finished tile
             if constexpr (FUSE) {
                 asm volatile("" : "+v"(tb));
                 tq_cur = tau_one(tb, 0);
+                sb_prev = block_scale(it_prev);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -418,28 +459,28 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
                     if constexpr (FUSE) {
                         if (kk == 0) {
                             // the finished tile's emit check for block n, in front of the MFMAs that overwrite its registers
-                            const float mx = block_max(n);
+                            const float mx = block_max(n, sb_prev);
                             const float tq = tq_cur;
                             if (n + 1 < NB16) tq_cur = tau_one(tb, n + 1);   // next block's threshold, one block ahead
                             if (__any(mx >= tq)) {
-                                emit_block(n, tq, it_prev);
+                                emit_block(n, tq, it_prev, sb_prev);
                             }
                             // (zeroed here: the MFMAs taking C = 0 directly instead made the register allocator spill)
 #pragma unroll
                             for (int m = 0; m < 2; ++m)
 #pragma unroll
-                                for (int r = 0; r < 4; ++r) acc[m][n][r] = 0.f;
+                                for (int r = 0; r < 4; ++r) acc[m][n][r] = 0;
                             __builtin_amdgcn_sched_barrier(0);
                         }
                     }
-                    acc[0][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2 * kk], bf[g % NBUF][j], acc[0][n], 0, 0, 0);
+                    acc[0][n] = mma(af[2 * kk], bf[g % NBUF][j], acc[0][n]);
                     if (j == 0) {
                         __builtin_amdgcn_sched_barrier(0);
                         if (g + PD < NG) load_group(st, g + PD, bf[(g + PD) % NBUF]);
                         else load_group(stn, g + PD - NG, bf[(g + PD) % NBUF]);   // first groups of step s+1 (after the mid barrier)
                         __builtin_amdgcn_sched_barrier(0);
                     }
-                    acc[1][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2 * kk + 1], bf[g % NBUF][j], acc[1][n], 0, 0, 0);
+                    acc[1][n] = mma(af[2 * kk + 1], bf[g % NBUF][j], acc[1][n]);
                 }
                 if ((g % GPK) == GPK - 1) {
                     __builtin_amdgcn_sched_barrier(0);
@@ -463,8 +504,11 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
             int64_t row_b = 0;
             uint32_t okbits = 0xffffffffu;
             bool filt = false;
-            if constexpr (EPI == EPI_EMIT) tq4n = tau_quad(0);
-            else tile_rows(it_done, row_b, okbits, filt);
+            float sb = 1.f;
+            if constexpr (EPI == EPI_EMIT) {
+                tq4n = tau_quad(0);
+                sb = block_scale(it_done);
+            } else tile_rows(it_done, row_b, okbits, filt);
 #pragma unroll
             for (int n = 0; n < NB16; ++n) {
                 if constexpr (EPI == EPI_SETMAX) {
@@ -472,7 +516,7 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
                     for (int m = 0; m < 2; ++m)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            float v = acc[m][n][r];
+                            float v = (float)acc[m][n][r];
                             if (filt && !((okbits >> (m * 16 + lq * 4 + r)) & 1u)) v = -INFINITY;
                             runmax[n][0] = fmaxf(runmax[n][0], v);
                         }
@@ -481,14 +525,14 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
                         tq4 = tq4n;
                         if (n + 4 < NB16) tq4n = tau_quad(n + 4);
                     }
-                    const float mx = block_max(n);
+                    const float mx = block_max(n, sb);
                     const float tq = tq4[n & 3];
-                    if (__any(mx >= tq)) emit_block(n, tq, it_done);
+                    if (__any(mx >= tq)) emit_block(n, tq, it_done, sb);
                 }
 #pragma unroll
                 for (int m = 0; m < 2; ++m)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[m][n][r] = 0.f;
+                    for (int r = 0; r < 4; ++r) acc[m][n][r] = 0;
             }
         };
 

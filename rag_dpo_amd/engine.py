@@ -243,7 +243,11 @@ class HipIndex:
     def last_stats(self) -> dict:
         s = L.SearchStats()
         L.check(self._lib.rdx_search_last_stats(self._h, ctypes.byref(s)))
-        return s.as_dict()
+        d = s.as_dict()
+        bits = ctypes.c_int32(0)
+        L.check(self._lib.rdx_search_last_coarse_bits(self._h, ctypes.byref(bits)))
+        d["coarse_bits"] = int(bits.value)   # 16 / 8: which MFMA pass ran the main scan; 0: the exact scan alone
+        return d
 
 
 class DocStore:
