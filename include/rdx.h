@@ -134,7 +134,9 @@ int rdx_index_set_row_ids(rdx_index* h, int64_t first_row, const int64_t* ids, i
  * segments overflow get a second MFMA pass as a small batch (denser threshold sample) before the exact full scan;
  * "coarse_i8" 0/1/2 (default 2): the main scan of more than 128 queries at dim_pad <= 1024 (a multiple of 128) on int8 MFMA over a
  * block-scaled int8 copy of the corpus (built by the first search that needs it, +1 B per element; not persisted), with an error
- * bound of its own per query: 0 never, 1 whenever the shape allows, 2 for more than 256 queries on at least 2^20 rows (speed only). */
+ * bound of its own per query: 0 never, 1 whenever the shape allows, 2 for more than 256 queries on at least 2^20 rows (speed only);
+ * "refine_pilot" 0..64 (default 4): an int8 search re-scores its hits in two rounds, the refine_pilot * k best coarse hits first
+ * and then the hits within E_q of their exact k-th score; 0 = one band of 2 E_q below the k-th coarse score (speed only). */
 int rdx_index_set_option(rdx_index* h, const char* name, int64_t value);
 
 /* The main scan's tile shares of the 8 XCDs (1.0 = an eighth; option "xcd_balance"): learned from the workgroups' own time stamps

@@ -179,6 +179,8 @@ struct rdx_index {
     int spread_boot = 1;     // option: a tile bootstrap (any not taken by k_boot) samples every div-th 32-row block instead of every div-th 256-row tile
     int spec_backoff = 0;    // searches left during which the provable threshold is used (set when a speculation failed)
     int coarse_i8 = 2;       // option: main scan on int8 MFMA — 0 never, 1 whenever the shape allows, 2 (default) large batches on large shards
+    int refine_pilot = 4;    // option: int8 searches find their re-score band in two rounds — the pilot*k best coarse hits first, then what lies
+                             // within E_q of their exact k-th score (refine_kernel.hpp); 0 = one band of 2E_q below c_k
     int coarse_bits = 0;     // the last search's coarse pass: 16, 8, or 0 (exact path only); rdx_search_last_coarse_bits
     int i8_backoff = 0;      // searches left during which automatic choice (coarse_i8 = 2) keeps the fp16 pass (set when an int8 search
                              // sent more than 1 in 64 of its queries to the fallback passes: rows too crowded for its band, see adapt_sampling)
@@ -421,6 +423,10 @@ extern "C" int rdx_index_set_option(rdx_index* h, const char* name, int64_t valu
         if (value < 0 || value > 2) return fail(RDX_ERR_INVALID, "coarse_i8 must be 0 (never), 1 (whenever the shape allows) or 2 (automatic)");
         h->coarse_i8 = (int)value;
         h->i8_backoff = 0;
+    }
+    else if (n == "refine_pilot") {
+        if (value < 0 || value > 64) return fail(RDX_ERR_INVALID, "refine_pilot must be 0 (one band) or 1..64 (pilot of that many times k hits)");
+        h->refine_pilot = (int)value;
     }
     else if (n == "spec_tau") {
         h->spec_tau = value != 0;
@@ -1522,7 +1528,7 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
     hipLaunchKernelGGL(k_refine, dim3((int)p.nq), dim3(1024), lds, st, h->cand.as<uint2>(), h->cntw.as<uint32_t>(), p.n_streams, p.capw,
                        p.list_cap, p.k, h->two_e(), p.i8 ? h->twoe8.as<float>() : nullptr, h->qhat.as<float>(), h->mv(), h->dim, h->row_base,
                        h->row_map, io.score, io.row, io.count, h->exact_list.as<int32_t>(), h->ctr.as<RefineCounters>(),
-                       p.i8 ? h->taus8.as<float>() : h->tau.as<float>(), p.i8 ? 1.0f : sp.inv_scale2, fin);
+                       p.i8 ? h->taus8.as<float>() : h->tau.as<float>(), p.i8 ? 1.0f : sp.inv_scale2, h->refine_pilot, fin);
     HIP_TRY(hipGetLastError());
     mark(h, p, st, 5);
     return RDX_OK;

@@ -128,6 +128,10 @@ __device__ __forceinline__ void finish_if_last(const FinishArgs& f) {
 //   P = {coarse >= c_k - 2E} contains the exact top-k; P is re-scored exactly from the fp32 master copy (fp64 lane-order
 //   sum, oracle/rdx_oracle.c) and ranked (score desc, row asc).
 //   A segment, list or P overflow cannot be answered here: the query is flagged for the exact full scan.
+//   int8 coarse pass (two_e_q != NULL) with pilot > 0: the band is found in TWO rounds (DESIGN.md §5 "two-round re-score"). 2E_q pays
+//   for not knowing the exact k-th score X; so S1 = the hits that reach the k1-th largest coarse score (k1 = min(m, pilot k)) are
+//   re-scored first, X1 = the k-th largest exact score in S1 (X1 <= X: S1 is a subset), and only S2 = {coarse >= X1 - E_q} \ S1
+//   is re-scored after them: a hit outside S1 and S2 has exact <= coarse + E_q < X1 <= X, strictly below the k-th score.
 #ifdef RDX_REFINE_STAMPS   // developer build (tools/refine_stamps.py): where k_refine spends its time (block 0's phases, 100 MHz wall clock)
 __device__ unsigned long long g_refine_stamps[16];
 #define RDX_RSTAMP(i) do { __syncthreads(); if (blockIdx.x == 0 && threadIdx.x == 0) g_refine_stamps[i] = wall_clock64(); } while (0)
@@ -135,13 +139,21 @@ __device__ unsigned long long g_refine_stamps[16];
 #define RDX_RSTAMP(i) do { } while (0)
 #endif
 
+// a - b rounded toward -inf (both finite): a band edge may only move down
+__device__ __forceinline__ float sub_down(float a, float b) {
+    float d = a - b;
+    if ((double)d > (double)a - (double)b) d = nextafterf(d, -INFINITY);
+    return d;
+}
+
 __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, const uint32_t* __restrict__ cntw,
                                                 int n_streams, uint32_t capw, uint32_t list_cap, int k, float two_e,
                                                 const float* __restrict__ two_e_q, const float* __restrict__ qhat, MasterView master, int dim,
                                                 int64_t row_base, const int64_t* __restrict__ row_map,
                                                 float* __restrict__ out_score, int64_t* __restrict__ out_row,
                                                 int32_t* __restrict__ out_count, int32_t* __restrict__ exact_list,
-                                                RefineCounters* __restrict__ ctr, const float* __restrict__ tau, float inv_scale2) {
+                                                RefineCounters* __restrict__ ctr, const float* __restrict__ tau, float inv_scale2,
+                                                int pilot) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint2* list = reinterpret_cast<uint2*>(smem);                        // [REFINE_LIST]
     __shared__ __attribute__((aligned(16))) uint32_t hist[HIST_WORDS];
@@ -201,10 +213,19 @@ __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, con
     __syncthreads();
     RDX_RSTAMP(2);
     const int64_t kk = (uint32_t)k < m ? k : m;
-    int64_t n_gt;
-    const uint32_t kth = block_kth_largest([&](int64_t i) { return f2key(__uint_as_float(list[i].x)); }, m, kk, hist, bc, &n_gt);
+    // int8 coarse pass: verified AFTER the exact re-score, against the exact k-th score X of the hits (a row that was not emitted
+    // scores below tau + E_q exactly: the answer is complete iff X - E_q >= tau; DESIGN.md §5). Its E_q is ~14x the fp16 E, and the
+    // test before the re-score (c_k - 2E >= tau) would reject most speculative thresholds.
+    const bool late = two_e_q != nullptr;
+    bool two = late && pilot > 0;                           // two rounds: pilot S1, then the band below X1
+    auto coarse_kth = [&](int64_t rank) __attribute__((always_inline)) {
+        int64_t n_gt;
+        return key2f(block_kth_largest([&](int64_t i) { return f2key(__uint_as_float(list[i].x)); }, m, rank, hist, bc, &n_gt));
+    };
+    const int64_t k1 = (int64_t)pilot * k < (int64_t)m ? (int64_t)pilot * k : (int64_t)m;
+    // lower edge of the first collection: c_k - 2E (one band), or c_k1 itself (S1)
     // (int8 coarse pass: the bound is the query's own, two_e_q[q] = 2 E_q, and tau is already in score units — DESIGN.md §5)
-    const float t2 = key2f(kth) - (two_e_q ? two_e_q[q] : two_e);
+    float t2 = two ? coarse_kth(k1) : coarse_kth(kk) - (two_e_q ? two_e_q[q] : two_e);
     RDX_RSTAMP(3);
     // Verification of the scan's threshold T (score units). The hits are exactly the allowed rows with coarse >= T. The k best of
     // them have exact >= c_k - E, so the exact k-th best of the corpus is >= c_k - E and every true top-k row has coarse >=
@@ -213,10 +234,6 @@ __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, con
     // lies) passes unless the estimate was too high — then the query goes to the fallback passes, which use
     // the provable threshold. T = -inf (fewer than k sets sampled): every allowed row was emitted, nothing to verify.
     const float tq = tau[q] * inv_scale2;
-    // int8 coarse pass: verified AFTER the exact re-score, against the exact k-th score X of the hits (a row that was not emitted
-    // scores below tau + E_q exactly: the answer is complete iff X - E_q >= tau; DESIGN.md §5). Its E_q is ~14x the fp16 E, and the
-    // test before the re-score (c_k - 2E >= tau) would reject most speculative thresholds.
-    const bool late = two_e_q != nullptr;
     auto verify_exact = [&](uint32_t kth_key) __attribute__((always_inline)) {
         if (!late || !(tq > -INFINITY) || key2f(kth_key) - 0.5f * two_e_q[q] >= tq) return true;
         if (threadIdx.x == 0) {
@@ -232,18 +249,30 @@ __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, con
         }
         return;
     }
+    // rows of the hits with lo <= coarse < hi are appended to s_r (n_p counts them all, the arrays take the first REFINE_PMAX)
+    auto collect = [&](float lo, float hi) __attribute__((always_inline)) {
+        for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) {
+            const uint2 e = list[i];
+            const float c = __uint_as_float(e.x);
+            if (c >= lo && c < hi) {
+                const int pos = atomicAdd(&n_p, 1);
+                if (pos < REFINE_PMAX) s_r[pos] = (int64_t)e.y;
+            }
+        }
+        __syncthreads();
+        return n_p;
+    };
     if (threadIdx.x == 0) n_p = 0;
     __syncthreads();
-    for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) {
-        const uint2 e = list[i];
-        if (__uint_as_float(e.x) >= t2) {
-            const int pos = atomicAdd(&n_p, 1);
-            if (pos < REFINE_PMAX) s_r[pos] = (int64_t)e.y;
-        }
+    int p = collect(t2, INFINITY);
+    if (two && p > REFINE_PMAX) {
+        // more than the ranking arrays hold tie at the k1-th coarse score (identical rows): the single band, as without a pilot
+        two = false;
+        t2 = coarse_kth(kk) - two_e_q[q];
+        if (threadIdx.x == 0) n_p = 0;
+        __syncthreads();
+        p = collect(t2, INFINITY);
     }
-    __syncthreads();
-    const int p = n_p;
-    if (threadIdx.x == 0) atomicAdd(&ctr->rescored, (unsigned long long)p);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float4* q4 = reinterpret_cast<const float4*>(qhat + (int64_t)q * dim);
     const int n4 = dim >> 2, nw = (int)(blockDim.x >> 6);
@@ -295,6 +324,24 @@ __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, con
             }
         }
     };
+    int done = 0;                                           // entries of s_r / s_s that already hold their exact score (S1)
+    float c1 = INFINITY;                                    // the band's upper edge: S1 (coarse >= c1) is not collected twice
+    if (two) {
+        rescore(p, [&](int i) { return s_r[i]; }, [&](int i, float sx) { s_s[i] = sx; });
+        __syncthreads();
+        done = p;
+        c1 = t2;
+        // X1 = k-th largest exact score of S1; fewer than k rows in S1 (then S1 is every hit): no bound, the band is empty anyway.
+        // t3 = X1 - E_q rounded DOWN (E_q = two_e_q / 2 is exact): every hit with coarse >= X1 - E_q is inside whatever the rounding
+        t2 = -INFINITY;
+        if (p >= k) {
+            int64_t n_gt1;
+            const uint32_t kx = block_kth_largest([&](int64_t i) { return f2key(s_s[i]); }, p, (int64_t)k, hist, bc, &n_gt1);
+            t2 = sub_down(key2f(kx), 0.5f * two_e_q[q]);
+        }
+        p = collect(t2, c1);                                // S2 behind S1 (n_p goes on counting)
+    }
+    if (threadIdx.x == 0) atomicAdd(&ctr->rescored, (unsigned long long)p);
     if (p > REFINE_PMAX) {
         // More rows inside the 2E band than the ranking arrays hold: near-duplicate rows stored together (a document's chunks: their
         // scores lie closer together than the coarse pass can tell apart, so the band holds hundreds to thousands of them). Until
@@ -313,7 +360,8 @@ __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, con
             keep[j] = false;
             if (j < c && i < m) {
                 mine[j] = list[i];
-                keep[j] = __uint_as_float(mine[j].x) >= t2;
+                const float cs = __uint_as_float(mine[j].x);
+                keep[j] = cs >= t2 && cs < c1;
             }
             cnt += keep[j] ? 1 : 0;
         }
@@ -331,7 +379,10 @@ __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, con
         for (int j = 0; j < 7; ++j)
             if (keep[j]) list[pos++] = mine[j];
         __syncthreads();
-        rescore(p, [&](int i) { return (int64_t)list[i].y; }, [&](int i, float sx) { list[i].x = __float_as_uint(sx); });
+        // (two rounds: the p - done rows of S2 were compacted; S1, already exact in the ranking arrays, goes behind them — S1 and
+        //  S2 are disjoint subsets of the m hits, so p <= m slots)
+        for (int i = threadIdx.x; i < done; i += blockDim.x) list[p - done + i] = make_uint2(__float_as_uint(s_s[i]), (uint32_t)s_r[i]);
+        rescore(p - done, [&](int i) { return (int64_t)list[i].y; }, [&](int i, float sx) { list[i].x = __float_as_uint(sx); });
         __syncthreads();
         const int64_t kk2 = k < p ? k : p;
         int64_t n_gt2;
@@ -362,7 +413,7 @@ __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, con
         return;
     }
     RDX_RSTAMP(4);
-    rescore(p, [&](int i) { return s_r[i]; }, [&](int i, float sx) { s_s[i] = sx; });
+    rescore(p - done, [&](int i) { return s_r[done + i]; }, [&](int i, float sx) { s_s[done + i] = sx; });
     __syncthreads();
     if (late) {
         int64_t n_gt3;
@@ -384,9 +435,9 @@ __global__ __launch_bounds__(1024) void k_refine(const uint2* __restrict__ cand,
                                                 float* __restrict__ out_score, int64_t* __restrict__ out_row,
                                                 int32_t* __restrict__ out_count, int32_t* __restrict__ exact_list,
                                                 RefineCounters* __restrict__ ctr, const float* __restrict__ tau, float inv_scale2,
-                                                const FinishArgs fin) {
+                                                int pilot, const FinishArgs fin) {
     refine_query(cand, cntw, n_streams, capw, list_cap, k, two_e, two_e_q, qhat, master, dim, row_base, row_map, out_score, out_row, out_count,
-                 exact_list, ctr, tau, inv_scale2);
+                 exact_list, ctr, tau, inv_scale2, pilot);
     finish_if_last(fin);
 }
 
