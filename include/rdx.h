@@ -26,6 +26,8 @@
  *     reference src/processing/create_chromadb_index.py:100-106).
  *   - result order per query: score descending, ties by ascending row id (= ascending distance,
  *     the order `RAGRetriever._parse_chromadb_results` consumes, reference src/rag/retriever.py:472-494).
+ *     Scores are compared as floats: +0 and -0 are the same score for ordering (rows scoring either tie and are ordered by
+ *     row id), and the sign of a returned zero is the sign of that row's exact score.
  */
 #ifndef RDX_H
 #define RDX_H

@@ -377,6 +377,15 @@ __device__ __forceinline__ void rank_and_write(const float* __restrict__ s, cons
     if (threadIdx.x == 0) *out_count = c;
 }
 
+// Selection key of an EXACT score: f2key with -0.0 put onto +0.0. The documented order (include/rdx.h) compares scores as floats,
+// so the two zeros are one value and row ids decide among them; f2key alone keeps every -0.0 strictly below every +0.0. The
+// selects that choose a k-th exact score and its ties use this key; what they return is the row's own score, read back from where
+// it is stored (the key of a zero does not say which zero it was). The scan's thresholds keep f2key (rdx_common.hpp).
+constexpr uint32_t SEL_KEY_ZERO = 0x80000000u;   // f2key(+0.0f)
+__device__ __forceinline__ uint32_t f2key_sel(float f) {
+    return __float_as_uint(f) == 0x80000000u ? SEL_KEY_ZERO : f2key(f);
+}
+
 // K5b. top-k of a dense score row (one block per listed query): radix select of the k-th largest score, then
 // everything above it plus the LOWEST-row entries equal to it (ties -> ascending row id), then a rank sort.
 // -inf marks rows excluded by the `where` pre-filter; they are never returned.
@@ -428,7 +437,7 @@ __device__ __forceinline__ void select_dense_query(const float* __restrict__ sco
 #pragma unroll
         for (int j = 0; j < RN; ++j) {
             const int64_t i = (int64_t)j * 1024 + threadIdx.x;
-            kreg[j] = i < rows ? f2key(vreg[j]) : 0u;   // padding key 0 sorts below every real score (finite or -inf)
+            kreg[j] = i < rows ? f2key_sel(vreg[j]) : 0u;   // padding key 0 sorts below every real score (finite or -inf)
         }
     }
     RDX_STAMP(1);
@@ -439,7 +448,7 @@ __device__ __forceinline__ void select_dense_query(const float* __restrict__ sco
                                                if ((int64_t)j * 1024 + threadIdx.x < rows) f(kreg[j]);
                                        },
                                        kk, hist, bc, &n_gt)
-                                 : block_kth_largest([&](int64_t i) { return f2key(sc[i]); }, rows, kk, hist, bc, &n_gt);
+                                 : block_kth_largest([&](int64_t i) { return f2key_sel(sc[i]); }, rows, kk, hist, bc, &n_gt);
     RDX_STAMP(2);
     const int need_eq = (int)(kk - n_gt);   // >= 1
     constexpr int EQ_CAP = 1024;
@@ -456,7 +465,7 @@ __device__ __forceinline__ void select_dense_query(const float* __restrict__ sco
     auto collect = [&](int64_t i, uint32_t key) {
         if (key > kth) {
             const int pos = atomicAdd(&n_sel, 1);
-            s_s[pos] = key2f(key);
+            s_s[pos] = key == SEL_KEY_ZERO ? sc[i] : key2f(key);   // (a zero keeps its own sign)
             s_r[pos] = row_map ? row_map[i] : row_base + i;
         } else if (key == kth) {
             const int e = atomicAdd(&n_eq, 1);
@@ -470,7 +479,7 @@ __device__ __forceinline__ void select_dense_query(const float* __restrict__ sco
             if (i < rows) collect(i, kreg[j]);
         }
     } else {
-        for (int64_t i = threadIdx.x; i < rows; i += blockDim.x) collect(i, f2key(sc[i]));
+        for (int64_t i = threadIdx.x; i < rows; i += blockDim.x) collect(i, f2key_sel(sc[i]));
     }
     __syncthreads();
     RDX_STAMP(3);
@@ -492,7 +501,7 @@ __device__ __forceinline__ void select_dense_query(const float* __restrict__ sco
         for (int64_t base = 0; base < rows; base += blockDim.x) {
             if (n_eq_taken >= need_eq) break;   // uniform: read after the barrier below
             const int64_t i = base + threadIdx.x;
-            const bool eq = i < rows && f2key(sc[i]) == kth;
+            const bool eq = i < rows && f2key_sel(sc[i]) == kth;
             const unsigned long long m = __ballot(eq);
             if (lane == 0) wave_tot[wave] = __popcll(m);
             __syncthreads();

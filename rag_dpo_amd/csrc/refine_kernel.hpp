@@ -386,26 +386,42 @@ __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, con
         __syncthreads();
         const int64_t kk2 = k < p ? k : p;
         int64_t n_gt2;
-        const uint32_t kth2 = block_kth_largest([&](int64_t i) { return f2key(__uint_as_float(list[i].x)); }, p, kk2, hist, bc, &n_gt2);
+        // (selection keys, k_rows.hpp: +0.0 and -0.0 are one score — with f2key a k-th key of +0.0 left the -0.0 rows out of the ties)
+        const uint32_t kth2 = block_kth_largest([&](int64_t i) { return f2key_sel(__uint_as_float(list[i].x)); }, p, kk2, hist, bc, &n_gt2);
         if (!verify_exact(kth2)) return;
-        if (threadIdx.x == 0) n_p = 0;
-        __syncthreads();
-        // everything above the k-th key, and EVERY entry equal to it (identical rows tie: the ranking below orders them by row id)
-        for (int i = threadIdx.x; i < p; i += blockDim.x) {
-            const uint2 e = list[i];
-            if (f2key(__uint_as_float(e.x)) >= kth2) {
-                const int at = atomicAdd(&n_p, 1);
-                if (at < REFINE_PMAX) {
-                    s_s[at] = __uint_as_float(e.x);
-                    s_r[at] = (int64_t)e.y;
+        // everything above the k-th key and the entries equal to it whose row key reaches `rkey`: first EVERY tie (rkey = 0; the
+        // ranking below orders them by row id), which is all there is to do unless identical rows fill the ranking arrays
+        auto take = [&](uint32_t rkey) __attribute__((always_inline)) {
+            if (threadIdx.x == 0) n_p = 0;
+            __syncthreads();
+            for (int i = threadIdx.x; i < p; i += blockDim.x) {
+                const uint2 e = list[i];
+                const uint32_t key = f2key_sel(__uint_as_float(e.x));
+                if (key > kth2 || (key == kth2 && ~e.y >= rkey)) {
+                    const int at = atomicAdd(&n_p, 1);
+                    if (at < REFINE_PMAX) {
+                        s_s[at] = __uint_as_float(e.x);
+                        s_r[at] = (int64_t)e.y;
+                    }
                 }
             }
-        }
-        __syncthreads();
-        const int p2 = n_p;
-        if (p2 > REFINE_PMAX) {                              // > 1024 - k rows IDENTICAL to the k-th: only the exact scan orders those
-            if (threadIdx.x == 0) exact_list[atomicAdd(&ctr->n_exact, 1)] = q;
-            return;
+            __syncthreads();
+            return n_p;
+        };
+        int p2 = take(0u);
+        if (p2 > REFINE_PMAX) {
+            // > 1024 - k rows tie at the k-th score (identical rows; zeros of both signs): of the ties the kk2 - n_gt2 with the LOWEST
+            // rows belong to the answer. The hits' rows are distinct 32-bit local rows (returned ids grow with them: row_base, or the
+            // strictly increasing row id map), so that many lowest rows are the keys ~row down to their (kk2 - n_gt2)-th largest —
+            // one more radix select (non-ties count as key 0, below every ~row), then kk2 <= k entries are ranked.
+            int64_t n_gt_r;
+            const uint32_t rkey = block_kth_largest(
+                [&](int64_t i) {
+                    const uint2 e = list[i];
+                    return f2key_sel(__uint_as_float(e.x)) == kth2 ? ~e.y : 0u;
+                },
+                p, kk2 - n_gt2, hist, bc, &n_gt_r);
+            p2 = take(rkey);
         }
         for (int i = threadIdx.x; i < p2; i += blockDim.x) s_r[i] = row_map ? row_map[s_r[i]] : s_r[i] + row_base;
         __syncthreads();
