@@ -21,13 +21,16 @@ import re
 import shutil
 import subprocess
 import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librdx.so")
 RESOURCES = os.path.join(HERE, "librdx.resources.json")
-SOURCES = ["rdx_api.hip"]
-HEADERS = ["rdx_common.hpp", "k_rows.hpp", "scan_kernel.hpp", "refine_kernel.hpp", "enc_kernels.hpp", "enc_small.hpp", "bm25_kernel.hpp", "rerank_kernel.hpp", "doc_kernel.hpp", "../../include/rdx.h"]
+# one translation unit per subsystem, each compiled as a job of its own; whatever lies in csrc/ is a source and is hashed
+SOURCES = sorted(os.path.basename(f) for f in glob.glob(os.path.join(CSRC, "*.hip")))
+HEADERS = sorted(os.path.basename(f) for f in glob.glob(os.path.join(CSRC, "*.hpp"))) + ["../../include/rdx.h"]
+CORE = "rdx_index.hip"        # the dense index and its search: the only unit that may hold a k_scan kernel
 CHECKERS = ["isa_check.py"]   # part of the recorded hash: a library is only "fresh" if it passed THIS version of the ISA check
 
 
@@ -42,6 +45,7 @@ def source_hash() -> str:
     import hashlib
     h = hashlib.sha256()
     for f in SOURCES + HEADERS:
+        h.update(f.encode())
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(fh.read())
     for f in CHECKERS:
@@ -83,13 +87,23 @@ def parse_resources(remarks: str) -> dict:
     return out
 
 
-def check_isa(work: str) -> dict:
-    """run rag_dpo_amd/isa_check.py over the device listing -save-temps left in `work`; raises on any hazard"""
-    from . import isa_check
-    lst = glob.glob(os.path.join(work, "*gfx950*.s"))
+def _listing(unit_dir: str) -> str:
+    """the device listing -save-temps=obj left beside a unit's object file: the very text that was assembled into it"""
+    lst = glob.glob(os.path.join(unit_dir, "*gfx950*.s"))
     if len(lst) != 1:
-        raise RuntimeError(f"expected one gfx950 listing from -save-temps in {work}, found {lst}")
-    found = isa_check.check_listing(open(lst[0]).read())
+        raise RuntimeError(f"expected one gfx950 listing from -save-temps in {unit_dir}, found {lst}")
+    with open(lst[0]) as f:
+        return f.read()
+
+
+def check_isa(work: str) -> dict:
+    """run rag_dpo_amd/isa_check.py over the core unit's device listing (each unit was compiled in work/<unit>); raises on any
+    hazard, and on a k_scan kernel in any other unit, where nothing would check it"""
+    from . import isa_check
+    for s in SOURCES:
+        if s != CORE and re.search(r"^\S*k_scan\S*:", _listing(os.path.join(work, s)), re.M):
+            raise RuntimeError(f"{s} holds a k_scan kernel — refused: the ISA check reads {CORE} only")
+    found = isa_check.check_listing(_listing(os.path.join(work, CORE)))
     if len(found) < 16:
         raise RuntimeError(f"ISA check: only {len(found)} k_scan kernels in the listing — the parser no longer matches the compiler's output")
     bad = {k: hz for k, (hz, st) in found.items() if hz}
@@ -109,23 +123,35 @@ def build_lib(force: bool = False, verbose: bool = False, extra_flags=(), out: s
     """out: build a VARIANT (extra_flags) to this path; the product library and its resource record are left alone"""
     if out is None and not force and is_fresh() and not extra_flags:
         return LIB
-    # compiled in a scratch directory with -save-temps=obj: the device listing (…gfx950.s) lands beside the output and is the
-    # very text that gets assembled into the library
+    # compiled in a scratch directory, one sub-directory and one job per unit, with -save-temps=obj: a unit's device listing
+    # (…gfx950.s) lands beside its object file and is the very text that gets assembled into the library
     work = tempfile.mkdtemp(prefix="librdx_build_", dir=os.environ.get("TMPDIR") or None)
     try:
         tmp = os.path.join(work, "librdx.so")
-        cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-save-temps=obj",
-               "-Wall", "-Wno-unused-function", "-Rpass-analysis=kernel-resource-usage", *extra_flags]
-        cmd += [os.path.join(CSRC, s) for s in SOURCES]
-        cmd += ["-o", tmp]
+        flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-save-temps=obj", "-Wall", "-Wno-unused-function",
+                 "-Rpass-analysis=kernel-resource-usage", *extra_flags]
+
+        def compile_unit(s):
+            os.mkdir(os.path.join(work, s))
+            cmd = [_hipcc(), *flags, "-c", os.path.join(CSRC, s), "-o", os.path.join(work, s, "unit.o")]
+            if verbose:
+                print(" ".join(cmd))
+            return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=os.path.join(work, s))
+
+        with ThreadPoolExecutor(max_workers=min(16, len(SOURCES))) as pool:
+            jobs = list(pool.map(compile_unit, SOURCES))
+        remarks = "\n".join(j.stderr for j in jobs)
+        noise = ("-Rpass-analysis=kernel-resource-usage", "remark:")
+        diag = "\n".join(l for l in remarks.splitlines() if not any(n in l for n in noise))
+        if any(j.returncode != 0 for j in jobs):
+            raise RuntimeError(f"hipcc failed ({[j.returncode for j in jobs]}):\n{diag[-4000:]}")
+        cmd = [_hipcc(), "-shared", "-fPIC", *[os.path.join(work, s, "unit.o") for s in SOURCES], "-o", tmp]
         if verbose:
             print(" ".join(cmd))
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=work)
-        noise = ("-Rpass-analysis=kernel-resource-usage", "remark:")
-        diag = "\n".join(l for l in r.stderr.splitlines() if not any(n in l for n in noise))
         if r.returncode != 0:
-            raise RuntimeError(f"hipcc failed ({r.returncode}):\n{diag[-4000:]}")
-        res = parse_resources(r.stderr)
+            raise RuntimeError(f"linking librdx failed ({r.returncode}):\n{r.stderr[-4000:]}")
+        res = parse_resources(remarks)
         if sum(1 for k, v in res.items() if "k_scan" in k and "spill_vgprs" in v and "scratch_bytes" in v) < 16:
             raise RuntimeError("the compiler's resource remarks could not be read for the scan kernels — refused (the spill check would be blind)")
         bad = {k: v for k, v in res.items() if "k_scan" in k and (v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0))}

@@ -1,7 +1,7 @@
 // bm25_kernel.hpp — BM25 sparse scoring and top-k (gfx950). Serves the reference's ChunkBM25Index.search /
 // SummaryBM25Index.search (src/rag/bm25_index.py:126-292), whose scores come from rank_bm25 0.2.2's BM25Okapi.get_scores.
 //
-// HBM layout of one index (owned by rdx_bm25, rdx_api.hip; built by rag_dpo_amd/bm25.py):
+// HBM layout of one index (owned by rdx_bm25, rdx_bm25.hip; built by rag_dpo_amd/bm25.py):
 //   post_off  int64 [V+1]    CSR by term: term t's postings are [post_off[t], post_off[t+1])
 //   post_row  int32 [nnz]    row ids, strictly ascending inside a term
 //   post_tf   uint16 [nnz]   term frequency in that row (>= 1; the host refuses an index with a larger tf)

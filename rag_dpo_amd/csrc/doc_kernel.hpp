@@ -1,6 +1,6 @@
 // doc_kernel.hpp — the device document store behind `where_document` ($contains / $not_contains, include/rdx.h rdx_docs_*).
 //
-// Arena layout (one per device store, owned by rdx_docs in rdx_api.hip):
+// Arena layout (one per device store, owned by rdx_docs in rdx_docs.hip):
 //   every row's UTF-8 text starts on a 16-byte boundary and is zero-padded to the next one; the per-row table is
 //   (start int64, len int32); the arena ends with DOC_TAIL zero bytes. Rows without text have len 0 and no bytes.
 //

@@ -1,0 +1,199 @@
+// rdx_bm25.hip — BM25 sparse retrieval (rdx_bm25_*) of include/rdx.h.
+#include "rdx_host.hpp"
+
+#include <cmath>
+#include <mutex>
+#include <vector>
+
+#include "bm25_kernel.hpp"
+
+using namespace rdx;
+
+// ------------------------------------------------------------------------------------------------
+// BM25 sparse retrieval (bm25_kernel.hpp): an immutable index, rebuilt to refresh, as in the reference
+// ------------------------------------------------------------------------------------------------
+struct rdx_bm25 {
+    int device = 0;
+    int64_t n_rows = 0, n_terms = 0, nnz = 0, n_dir = 0;
+    int32_t n_groups = 0;
+    int n_tiles = 0;
+    DevBuf post_off, post_row, post_tf, idf, denom, dir_off, dir_tile, dir_pos, group;
+    DevBuf in, part, out;          // per search: packed inputs, tile partials, packed outputs
+    PinnedBuf h_in, h_out;
+    hipStream_t own_stream = nullptr;
+    std::mutex mu;                 // searches are synchronous: one at a time owns the buffers
+};
+
+static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+extern "C" int rdx_bm25_create(int device, int64_t n_rows, int64_t n_terms, const int64_t* post_off, const int32_t* post_row,
+                               const uint16_t* post_tf, const double* idf, const double* row_denom, const int32_t* row_group,
+                               int32_t n_groups, rdx_bm25** out) {
+    if (!out) return fail(RDX_ERR_INVALID, "rdx_bm25_create: null out pointer");
+    *out = nullptr;
+    if (n_rows < 1 || n_rows > INT32_MAX - BM25_TILE || n_terms < 0 || n_terms >= INT32_MAX)
+        return fail(RDX_ERR_INVALID, "rdx_bm25_create: n_rows must be in [1, 2^31 - 4097] and n_terms in [0, 2^31 - 1)");
+    if (!post_off || !row_denom || (n_terms > 0 && !idf)) return fail(RDX_ERR_INVALID, "rdx_bm25_create: null pointer");
+    if ((row_group == nullptr) != (n_groups == 0) || n_groups < 0)
+        return fail(RDX_ERR_INVALID, "rdx_bm25_create: row_group and n_groups > 0 go together");
+    const int64_t nnz = post_off[n_terms];
+    if (post_off[0] != 0 || nnz < 0) return fail(RDX_ERR_INVALID, "rdx_bm25_create: post_off must start at 0");
+    if (nnz > 0 && (!post_row || !post_tf)) return fail(RDX_ERR_INVALID, "rdx_bm25_create: null postings");
+    for (int64_t r = 0; r < n_rows; ++r) {
+        if (!(row_denom[r] > 0.0) || !std::isfinite(row_denom[r]))
+            return fail(RDX_ERR_INVALID, "rdx_bm25_create: row_denom[" + std::to_string(r) + "] is not a positive finite number");
+        if (row_group && (row_group[r] < 0 || row_group[r] >= n_groups))
+            return fail(RDX_ERR_INVALID, "rdx_bm25_create: row_group[" + std::to_string(r) + "] out of [0, n_groups)");
+    }
+    // validate the postings and build the per-term tile directory (one pass)
+    std::vector<int64_t> h_dir_off((size_t)n_terms + 1), h_dir_pos;
+    std::vector<int32_t> h_dir_tile;
+    for (int64_t t = 0; t < n_terms; ++t) {
+        if (!std::isfinite(idf[t])) return fail(RDX_ERR_INVALID, "rdx_bm25_create: idf[" + std::to_string(t) + "] is not finite");
+        const int64_t b = post_off[t], e = post_off[t + 1];
+        if (e < b || e > nnz) return fail(RDX_ERR_INVALID, "rdx_bm25_create: post_off must be non-decreasing up to post_off[n_terms]");
+        h_dir_off[(size_t)t] = (int64_t)h_dir_tile.size();
+        int32_t prev_row = -1, prev_tile = -1;
+        for (int64_t p = b; p < e; ++p) {
+            const int32_t r = post_row[p];
+            if (r <= prev_row || r >= n_rows)
+                return fail(RDX_ERR_INVALID, "rdx_bm25_create: term " + std::to_string(t) + ": rows must be strictly ascending and < n_rows");
+            if (post_tf[p] == 0) return fail(RDX_ERR_INVALID, "rdx_bm25_create: term " + std::to_string(t) + ": tf 0 in a posting");
+            prev_row = r;
+            const int32_t tile = r / BM25_TILE;
+            if (tile != prev_tile) {
+                h_dir_tile.push_back(tile);
+                h_dir_pos.push_back(p);
+                prev_tile = tile;
+            }
+        }
+    }
+    h_dir_off[(size_t)n_terms] = (int64_t)h_dir_tile.size();
+    h_dir_pos.push_back(nnz);
+
+    HIP_TRY(hipSetDevice(device));
+    rdx_bm25* h = new rdx_bm25();
+    h->device = device;
+    h->n_rows = n_rows;
+    h->n_terms = n_terms;
+    h->nnz = nnz;
+    h->n_dir = (int64_t)h_dir_tile.size();
+    h->n_groups = n_groups;
+    h->n_tiles = (int)((n_rows + BM25_TILE - 1) / BM25_TILE);
+    auto up = [&](DevBuf& d, const void* src, size_t bytes) -> int {
+        RDX_TRY(d.ensure(std::max(bytes, (size_t)16)));
+        if (bytes) HIP_TRY(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+        return RDX_OK;
+    };
+    int rc = RDX_OK;
+    if (rc == RDX_OK) rc = up(h->post_off, post_off, (size_t)(n_terms + 1) * 8);
+    if (rc == RDX_OK) rc = up(h->post_row, post_row, (size_t)nnz * 4);
+    if (rc == RDX_OK) rc = up(h->post_tf, post_tf, (size_t)nnz * 2);
+    if (rc == RDX_OK) rc = up(h->idf, idf, (size_t)n_terms * 8);
+    if (rc == RDX_OK) rc = up(h->denom, row_denom, (size_t)n_rows * 8);
+    if (rc == RDX_OK) rc = up(h->dir_off, h_dir_off.data(), h_dir_off.size() * 8);
+    if (rc == RDX_OK) rc = up(h->dir_tile, h_dir_tile.data(), h_dir_tile.size() * 4);
+    if (rc == RDX_OK) rc = up(h->dir_pos, h_dir_pos.data(), h_dir_pos.size() * 8);
+    if (rc == RDX_OK && row_group) rc = up(h->group, row_group, (size_t)n_rows * 4);
+    if (rc == RDX_OK) {
+        hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
+        if (e != hipSuccess) rc = fail(RDX_ERR_HIP, std::string("rdx_bm25_create: ") + hipGetErrorString(e));
+    }
+    if (rc != RDX_OK) {
+        rdx_bm25_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return RDX_OK;
+}
+
+extern "C" int rdx_bm25_destroy(rdx_bm25* h) {
+    if (!h) return RDX_OK;
+    (void)hipSetDevice(h->device);
+    if (h->own_stream) {
+        (void)hipStreamSynchronize(h->own_stream);
+        (void)hipStreamDestroy(h->own_stream);
+    }
+    delete h;
+    return RDX_OK;
+}
+
+extern "C" int rdx_bm25_search(rdx_bm25* h, const int64_t* term_offsets, const int32_t* term_ids, int64_t nq, int k,
+                               const uint32_t* allow_groups, double* out_score, int64_t* out_row, int32_t* out_count, int space,
+                               void* stream) {
+    if (!h) return fail(RDX_ERR_INVALID, "rdx_bm25_search: null index");
+    if (nq < 0 || k < 1 || k > BM25_MAX_K)
+        return fail(RDX_ERR_INVALID, "rdx_bm25_search: need nq >= 0 and 1 <= k <= " + std::to_string(BM25_MAX_K) + " (got k = " +
+                                         std::to_string(k) + ")");
+    if (space != RDX_HOST) return fail(RDX_ERR_INVALID, "rdx_bm25_search: space must be RDX_HOST (the terms are checked on the host)");
+    if (allow_groups && h->n_groups == 0) return fail(RDX_ERR_INVALID, "rdx_bm25_search: a group filter on an index without groups");
+    if (nq == 0) return RDX_OK;
+    if (!term_offsets || !out_score || !out_row || !out_count) return fail(RDX_ERR_INVALID, "rdx_bm25_search: null pointer");
+    std::lock_guard<std::mutex> lock(h->mu);
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->own_stream;
+
+    // the query terms are checked before anything is enqueued
+    const int64_t* off = term_offsets;
+    if (off[0] != 0) return fail(RDX_ERR_INVALID, "rdx_bm25_search: term_offsets[0] must be 0");
+    for (int64_t q = 0; q < nq; ++q) {
+        const int64_t T = off[q + 1] - off[q];
+        if (T < 0 || T > BM25_MAX_TERMS)
+            return fail(RDX_ERR_INVALID, "rdx_bm25_search: query " + std::to_string(q) + " has " + std::to_string(T) + " terms (0.." +
+                                             std::to_string(BM25_MAX_TERMS) + ")");
+    }
+    const int64_t n_ids = off[nq];
+    if (n_ids > 0 && !term_ids) return fail(RDX_ERR_INVALID, "rdx_bm25_search: null term_ids");
+    for (int64_t i = 0; i < n_ids; ++i)
+        if (term_ids[i] < 0 || term_ids[i] >= h->n_terms)
+            return fail(RDX_ERR_INVALID, "rdx_bm25_search: term id " + std::to_string(term_ids[i]) + " out of [0, " +
+                                             std::to_string(h->n_terms) + ")");
+
+    // one upload through pinned staging: offsets | ids | allow bits
+    const size_t allow_words = (size_t)(h->n_groups + 31) / 32;
+    const size_t b_off = align16((size_t)(nq + 1) * 8), b_ids = align16((size_t)std::max<int64_t>(n_ids, 1) * 4);
+    const size_t b_in = b_off + b_ids + (allow_groups ? align16(allow_words * 4) : 0);
+    RDX_TRY(h->h_in.ensure(b_in));
+    RDX_TRY(h->in.ensure(b_in));
+    char* hp = (char*)h->h_in.p;
+    std::memcpy(hp, term_offsets, (size_t)(nq + 1) * 8);
+    if (n_ids) std::memcpy(hp + b_off, term_ids, (size_t)n_ids * 4);
+    if (allow_groups) std::memcpy(hp + b_off + b_ids, allow_groups, allow_words * 4);
+    HIP_TRY(hipMemcpyAsync(h->in.p, hp, b_in, hipMemcpyHostToDevice, st));
+    const int64_t* d_off = (const int64_t*)h->in.p;
+    const int32_t* d_ids = (const int32_t*)((char*)h->in.p + b_off);
+    const uint32_t* d_allow = allow_groups ? (const uint32_t*)((char*)h->in.p + b_off + b_ids) : nullptr;
+    const size_t b_score = align16((size_t)nq * k * 8), b_row = align16((size_t)nq * k * 8), b_cnt = align16((size_t)nq * 4);
+    RDX_TRY(h->out.ensure(b_score + b_row + b_cnt));
+    double* o_score = (double*)h->out.p;
+    int64_t* o_row = (int64_t*)((char*)h->out.p + b_score);
+    int32_t* o_cnt = (int32_t*)((char*)h->out.p + b_score + b_row);
+    // queries go in chunks whose tile partials fit 256 MiB
+    const size_t per_query = (size_t)h->n_tiles * k * 12 + (size_t)h->n_tiles * 4;
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({nq, (int64_t)((size_t)256 << 20) / (int64_t)per_query, 65535}));
+    const size_t c_score = align16((size_t)chunk * h->n_tiles * k * 8), c_row = align16((size_t)chunk * h->n_tiles * k * 4);
+    RDX_TRY(h->part.ensure(c_score + c_row + align16((size_t)chunk * h->n_tiles * 4)));
+    double* p_score = h->part.as<double>();
+    int32_t* p_row = (int32_t*)((char*)h->part.p + c_score);
+    int32_t* p_cnt = (int32_t*)((char*)h->part.p + c_score + c_row);
+    for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+        const int nqc = (int)std::min<int64_t>(chunk, nq - q0);
+        hipLaunchKernelGGL(k_bm25_score, dim3(h->n_tiles, nqc), dim3(BM25_THREADS), 0, st, h->dir_off.as<int64_t>(),
+                           h->dir_tile.as<int32_t>(), h->dir_pos.as<int64_t>(), h->post_row.as<int32_t>(), h->post_tf.as<uint16_t>(),
+                           h->idf.as<double>(), h->denom.as<double>(), h->group.as<int32_t>(), d_allow, d_off + q0, d_ids, h->n_rows, k,
+                           h->n_tiles, p_score, p_row, p_cnt);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_bm25_merge, dim3(nqc), dim3(BM25_MERGE_THREADS), 0, st, p_score, p_row, p_cnt, h->n_tiles, k,
+                           o_score + (size_t)q0 * k, o_row + (size_t)q0 * k, o_cnt + q0);
+        HIP_TRY(hipGetLastError());
+    }
+    // one download, then out of the pinned staging
+    RDX_TRY(h->h_out.ensure(b_score + b_row + b_cnt));
+    HIP_TRY(hipMemcpyAsync(h->h_out.p, h->out.p, b_score + b_row + b_cnt, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const char* ho = (const char*)h->h_out.p;
+    std::memcpy(out_score, ho, (size_t)nq * k * 8);
+    std::memcpy(out_row, ho + b_score, (size_t)nq * k * 8);
+    std::memcpy(out_count, ho + b_score + b_row, (size_t)nq * 4);
+    return RDX_OK;
+}

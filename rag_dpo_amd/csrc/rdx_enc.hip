@@ -1,0 +1,313 @@
+// rdx_enc.hip — the encoder launchers (rdx_enc_*) and the reranker head and selection (rdx_rerank_*) of include/rdx.h.
+#include "rdx_host.hpp"
+
+#include <mutex>
+#include <unordered_map>
+
+#include "enc_kernels.hpp"
+#include "enc_small.hpp"
+#include "rerank_kernel.hpp"
+
+using namespace rdx;
+
+extern "C" int rdx_enc_attention_f16(int device, const void* qkv, const int32_t* tok_first, const int32_t* tok_len, int64_t n_tokens,
+                                     int heads, int head_dim, float scale, int max_text_tokens, void* ctx, void* stream) {
+    if (n_tokens < 0 || heads < 1 || heads > 65535) return fail(RDX_ERR_INVALID, "rdx_enc_attention_f16: bad shape");
+    if (head_dim != ENC_HEAD_DIM) return fail(RDX_ERR_INVALID, "rdx_enc_attention_f16: head_dim must be 64");
+    if (n_tokens == 0) return RDX_OK;
+    if (!qkv || !tok_first || !tok_len || !ctx) return fail(RDX_ERR_INVALID, "rdx_enc_attention_f16: null pointer");
+    if (((uintptr_t)qkv | (uintptr_t)ctx) & 15) return fail(RDX_ERR_INVALID, "rdx_enc_attention_f16: qkv and ctx must be 16-byte aligned");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_attention_f16: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    // keys a workgroup stages in LDS: its 64 tokens' texts span at most 64 + 2 (L - 1) tokens when no text is longer than L
+    int window = ENC_KEY_WINDOW;
+    if (max_text_tokens > 0) window = std::min<int64_t>(ENC_KEY_WINDOW, (64 + 2 * ((int64_t)max_text_tokens - 1) + 7) / 8 * 8);
+    hipLaunchKernelGGL(k_enc_attention, dim3((unsigned)((n_tokens + 63) / 64), (unsigned)heads), dim3(256), (size_t)window * 256, (hipStream_t)stream,
+                       (const _Float16*)qkv, tok_first, tok_len, n_tokens, heads, scale, window, (_Float16*)ctx);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+extern "C" int rdx_enc_attention_mfma_f16(int device, const void* qkv, const int32_t* query_blocks, int n_blocks, int heads, int head_dim,
+                                          float scale, void* ctx, void* stream) {
+    if (n_blocks < 0 || heads < 1 || heads > 65535) return fail(RDX_ERR_INVALID, "rdx_enc_attention_mfma_f16: bad shape");
+    if (head_dim != ENC_HEAD_DIM) return fail(RDX_ERR_INVALID, "rdx_enc_attention_mfma_f16: head_dim must be 64");
+    if (n_blocks == 0) return RDX_OK;
+    if (!qkv || !query_blocks || !ctx) return fail(RDX_ERR_INVALID, "rdx_enc_attention_mfma_f16: null pointer");
+    if (((uintptr_t)qkv | (uintptr_t)ctx | (uintptr_t)query_blocks) & 15) return fail(RDX_ERR_INVALID, "rdx_enc_attention_mfma_f16: pointers must be 16-byte aligned");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_attention_mfma_f16: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    hipLaunchKernelGGL(k_enc_attention_mfma, dim3((unsigned)n_blocks, (unsigned)heads), dim3(256), 0, (hipStream_t)stream, (const _Float16*)qkv, query_blocks, heads,
+                       scale * 1.4426950408889634f, (_Float16*)ctx);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+template <bool GELU>
+static void launch_linear_small(int ntb, dim3 grid, hipStream_t st, const _Float16* x, const _Float16* w, const _Float16* b, int T, int N, int K,
+                                _Float16* out) {
+    if (ntb <= 2 && K % 1024 == 0 && K <= 4096) {   // one question: 16 waves split K, a wave's whole slice in flight at once
+        const size_t lds = (size_t)16 * ntb * 1024;
+        if (ntb == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_enc_linear_small<1, GELU, 16>), grid, dim3(1024), lds, st, x, w, b, T, N, K, out);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_enc_linear_small<2, GELU, 16>), grid, dim3(1024), lds, st, x, w, b, T, N, K, out);
+        return;
+    }
+    const size_t lds = (size_t)ntb * 4096;   // 4 waves x ntb * 4 registers x 64 lanes x 4 B
+    switch (ntb) {
+        case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_enc_linear_small<1, GELU, 4>), grid, dim3(256), lds, st, x, w, b, T, N, K, out); break;
+        case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_enc_linear_small<2, GELU, 4>), grid, dim3(256), lds, st, x, w, b, T, N, K, out); break;
+        case 4: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_enc_linear_small<4, GELU, 4>), grid, dim3(256), lds, st, x, w, b, T, N, K, out); break;
+        case 8: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_enc_linear_small<8, GELU, 4>), grid, dim3(256), lds, st, x, w, b, T, N, K, out); break;
+        default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_enc_linear_small<16, GELU, 4>), grid, dim3(256), lds, st, x, w, b, T, N, K, out); break;
+    }
+}
+
+extern "C" int rdx_enc_linear_small_f16(int device, const void* x, const void* w, const void* bias, int n_tokens, int n_out, int n_in,
+                                        int act, void* out, void* stream) {
+    if (n_tokens < 0 || n_tokens > 256) return fail(RDX_ERR_INVALID, "rdx_enc_linear_small_f16: at most 256 tokens (use the BLAS library beyond)");
+    if (n_out < 16 || n_out % 16 || n_in < 512 || n_in % 512) return fail(RDX_ERR_INVALID, "rdx_enc_linear_small_f16: n_out must be a multiple of 16, n_in of 512");
+    if (act != 0 && act != 1) return fail(RDX_ERR_INVALID, "rdx_enc_linear_small_f16: act is 0 (none) or 1 (erf GELU)");
+    if (n_tokens == 0) return RDX_OK;
+    if (!x || !w || !bias || !out) return fail(RDX_ERR_INVALID, "rdx_enc_linear_small_f16: null pointer");
+    if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)out) & 15) return fail(RDX_ERR_INVALID, "rdx_enc_linear_small_f16: x, w and out must be 16-byte aligned");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_linear_small_f16: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    int ntb = 1;
+    while (ntb * 16 < n_tokens) ntb *= 2;
+    const dim3 grid((unsigned)(n_out / 16));
+    if (act) launch_linear_small<true>(ntb, grid, (hipStream_t)stream, (const _Float16*)x, (const _Float16*)w, (const _Float16*)bias, n_tokens, n_out, n_in, (_Float16*)out);
+    else launch_linear_small<false>(ntb, grid, (hipStream_t)stream, (const _Float16*)x, (const _Float16*)w, (const _Float16*)bias, n_tokens, n_out, n_in, (_Float16*)out);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+extern "C" int rdx_enc_add_layernorm_f16(int device, const void* a, const void* b, const void* gamma, const void* beta, float eps,
+                                         int64_t rows, int hidden, void* out, void* stream) {
+    if (rows < 0 || hidden < 512 || hidden > 2048 || hidden % 512) return fail(RDX_ERR_INVALID, "rdx_enc_add_layernorm_f16: hidden must be 512, 1024, 1536 or 2048");
+    if (rows == 0) return RDX_OK;
+    if (!a || !b || !gamma || !beta || !out) return fail(RDX_ERR_INVALID, "rdx_enc_add_layernorm_f16: null pointer");
+    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out) & 15)
+        return fail(RDX_ERR_INVALID, "rdx_enc_add_layernorm_f16: pointers must be 16-byte aligned");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_add_layernorm_f16: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    const _Float16 *pa = (const _Float16*)a, *pb = (const _Float16*)b, *pg = (const _Float16*)gamma, *pbt = (const _Float16*)beta;
+    switch (hidden / 512) {
+        case 1: hipLaunchKernelGGL(k_enc_add_ln<1>, grid, block, 0, st, pa, pb, pg, pbt, eps, rows, (_Float16*)out); break;
+        case 2: hipLaunchKernelGGL(k_enc_add_ln<2>, grid, block, 0, st, pa, pb, pg, pbt, eps, rows, (_Float16*)out); break;
+        case 3: hipLaunchKernelGGL(k_enc_add_ln<3>, grid, block, 0, st, pa, pb, pg, pbt, eps, rows, (_Float16*)out); break;
+        default: hipLaunchKernelGGL(k_enc_add_ln<4>, grid, block, 0, st, pa, pb, pg, pbt, eps, rows, (_Float16*)out); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+// ---- the single-question forward: E4..E7 (enc_small.hpp) ----------------------------------------------------------------------
+// kernels with more than 64 KiB of dynamic LDS need the limit raised once per kernel and device
+static std::mutex g_enc_attr_mu;
+static std::unordered_map<const void*, size_t>* const g_enc_attr = new std::unordered_map<const void*, size_t>[64];
+static int enc_dynamic_lds(int device, const void* func, size_t bytes) {
+    if (bytes <= 65536) return RDX_OK;
+    std::lock_guard<std::mutex> lk(g_enc_attr_mu);
+    size_t& have = g_enc_attr[device][func];
+    if (have < bytes) {
+        HIP_TRY(hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        have = bytes;
+    }
+    return RDX_OK;
+}
+
+template <int NTB, int KCS, int NPH, int FPB, bool LNPRO, int EPI>
+static int launch_enc_stage(int device, const EncStage& a, hipStream_t st) {
+    const size_t lds = (size_t)NTB * 16384 + (size_t)NTB * 16 * KCS * 512 * 2;
+    auto* fn = k_enc_stage<NTB, KCS, NPH, FPB, LNPRO, EPI>;
+    RDX_TRY(enc_dynamic_lds(device, (const void*)fn, lds));
+    hipLaunchKernelGGL(fn, dim3((unsigned)(a.N / FPB)), dim3(1024), lds, st, a);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+template <int NTB, int KCS, int NPH>
+static int dispatch_enc_stage(int device, const EncStage& a, bool lnpro, int epi, int fpb, hipStream_t st) {
+    if (lnpro) {
+        if constexpr (NPH == 1) {
+            if (epi == ENC_EPI_BIAS) return launch_enc_stage<NTB, KCS, 1, 16, true, ENC_EPI_BIAS>(device, a, st);
+            if (epi == ENC_EPI_GELU) return launch_enc_stage<NTB, KCS, 1, 16, true, ENC_EPI_GELU>(device, a, st);
+        }
+        return fail(RDX_ERR_INVALID, "rdx_enc_stage_f16: the LayerNorm prologue takes n_in 512 or 1024 and epilogue 0 or 1");
+    }
+#define RDX_ENC_PLAIN(F)                                                                                                   \
+    if (fpb == F) {                                                                                                        \
+        if (epi == ENC_EPI_BIAS) return launch_enc_stage<NTB, KCS, NPH, F, false, ENC_EPI_BIAS>(device, a, st);            \
+        if (epi == ENC_EPI_GELU) return launch_enc_stage<NTB, KCS, NPH, F, false, ENC_EPI_GELU>(device, a, st);            \
+        return launch_enc_stage<NTB, KCS, NPH, F, false, ENC_EPI_RESIDUAL>(device, a, st);                                  \
+    }
+    RDX_ENC_PLAIN(16)
+    RDX_ENC_PLAIN(8)
+    RDX_ENC_PLAIN(4)
+#undef RDX_ENC_PLAIN
+    return fail(RDX_ERR_INVALID, "rdx_enc_stage_f16: features_per_workgroup is 16, 8 or 4");
+}
+
+extern "C" int rdx_enc_stage_f16(int device, const void* x, const int64_t* x_rows, const void* ln_gamma, const void* ln_beta, float ln_eps,
+                                 void* y_out, const void* w, const void* bias, const void* res, int n_tokens, int n_out, int n_in,
+                                 int epilogue, int features_per_workgroup, void* out, void* stream) {
+    if (n_tokens < 0 || n_tokens > 32) return fail(RDX_ERR_INVALID, "rdx_enc_stage_f16: at most 32 tokens");
+    if (n_in != 512 && n_in != 1024 && n_in != 2048 && n_in != 4096) return fail(RDX_ERR_INVALID, "rdx_enc_stage_f16: n_in must be 512, 1024, 2048 or 4096");
+    if (epilogue < 0 || epilogue > 2) return fail(RDX_ERR_INVALID, "rdx_enc_stage_f16: epilogue is 0 (bias), 1 (bias + erf GELU) or 2 (bias + residual)");
+    int fpb = features_per_workgroup ? features_per_workgroup : 16;
+    if (n_out < fpb || n_out % fpb) return fail(RDX_ERR_INVALID, "rdx_enc_stage_f16: n_out must be a multiple of features_per_workgroup");
+    const bool lnpro = ln_gamma != nullptr;
+    if (lnpro && (!ln_beta || x_rows)) return fail(RDX_ERR_INVALID, "rdx_enc_stage_f16: the LayerNorm prologue needs gamma and beta and takes no row list");
+    if (lnpro && fpb != 16) return fail(RDX_ERR_INVALID, "rdx_enc_stage_f16: the LayerNorm prologue runs with 16 features per workgroup");
+    if (epilogue == 2 && !res) return fail(RDX_ERR_INVALID, "rdx_enc_stage_f16: epilogue 2 needs the residual");
+    if (n_tokens == 0) return RDX_OK;
+    if (!x || !w || !bias || !out) return fail(RDX_ERR_INVALID, "rdx_enc_stage_f16: null pointer");
+    if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)out | (uintptr_t)y_out | (uintptr_t)ln_gamma | (uintptr_t)ln_beta) & 15)
+        return fail(RDX_ERR_INVALID, "rdx_enc_stage_f16: pointers must be 16-byte aligned");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_stage_f16: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    EncStage a;
+    a.x = (const _Float16*)x;
+    a.x_rows = x_rows;
+    a.gamma = (const _Float16*)ln_gamma;
+    a.beta = (const _Float16*)ln_beta;
+    a.eps = ln_eps;
+    a.y_out = (_Float16*)y_out;
+    a.w = (const _Float16*)w;
+    a.bias = (const _Float16*)bias;
+    a.res = (const _Float16*)res;
+    a.out = (_Float16*)out;
+    a.T = n_tokens;
+    a.N = n_out;
+    hipStream_t st = (hipStream_t)stream;
+#define RDX_ENC_K(NTB)                                                                         \
+    switch (n_in) {                                                                            \
+        case 512: return dispatch_enc_stage<NTB, 1, 1>(device, a, lnpro, epilogue, fpb, st);   \
+        case 1024: return dispatch_enc_stage<NTB, 2, 1>(device, a, lnpro, epilogue, fpb, st);  \
+        case 2048: return dispatch_enc_stage<NTB, 2, 2>(device, a, lnpro, epilogue, fpb, st);  \
+        default: return dispatch_enc_stage<NTB, 2, 4>(device, a, lnpro, epilogue, fpb, st);    \
+    }
+    if (n_tokens <= 16) { RDX_ENC_K(1) }
+    RDX_ENC_K(2)
+#undef RDX_ENC_K
+}
+
+extern "C" int rdx_enc_attention_small_f16(int device, const void* qkv, const int32_t* tok_first, int n_tokens, int heads, int head_dim,
+                                           float scale, void* ctx, void* stream) {
+    if (n_tokens < 0 || n_tokens > 32) return fail(RDX_ERR_INVALID, "rdx_enc_attention_small_f16: at most 32 tokens");
+    if (heads < 1 || heads > 65535 || head_dim != ENC_HEAD_DIM) return fail(RDX_ERR_INVALID, "rdx_enc_attention_small_f16: head_dim must be 64");
+    if (n_tokens == 0) return RDX_OK;
+    if (!qkv || !tok_first || !ctx) return fail(RDX_ERR_INVALID, "rdx_enc_attention_small_f16: null pointer");
+    if (((uintptr_t)qkv | (uintptr_t)ctx) & 15) return fail(RDX_ERR_INVALID, "rdx_enc_attention_small_f16: qkv and ctx must be 16-byte aligned");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_attention_small_f16: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    const float sl2 = scale * 1.4426950408889634f;
+    if (n_tokens <= 16)
+        hipLaunchKernelGGL(k_enc_attn_small<1>, dim3((unsigned)heads), dim3(64), 0, (hipStream_t)stream, (const _Float16*)qkv, tok_first, n_tokens, heads, sl2, (_Float16*)ctx);
+    else
+        hipLaunchKernelGGL(k_enc_attn_small<2>, dim3((unsigned)heads), dim3(128), 0, (hipStream_t)stream, (const _Float16*)qkv, tok_first, n_tokens, heads, sl2, (_Float16*)ctx);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+extern "C" int rdx_enc_embed_f16(int device, const int64_t* tok, const int64_t* pos_id, const void* word, const void* pos, const void* type0,
+                                 int n_tokens, int hidden, void* out, void* stream) {
+    if (n_tokens < 0 || hidden < 512 || hidden > 2048 || hidden % 512) return fail(RDX_ERR_INVALID, "rdx_enc_embed_f16: hidden must be 512, 1024, 1536 or 2048");
+    if (n_tokens == 0) return RDX_OK;
+    if (!tok || !pos_id || !word || !pos || !type0 || !out) return fail(RDX_ERR_INVALID, "rdx_enc_embed_f16: null pointer");
+    if (((uintptr_t)word | (uintptr_t)pos | (uintptr_t)type0 | (uintptr_t)out) & 15) return fail(RDX_ERR_INVALID, "rdx_enc_embed_f16: pointers must be 16-byte aligned");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_embed_f16: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    const dim3 grid((unsigned)((n_tokens + 3) / 4)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    const _Float16 *pw = (const _Float16*)word, *pp = (const _Float16*)pos, *pt = (const _Float16*)type0;
+    switch (hidden / 512) {
+        case 1: hipLaunchKernelGGL(k_enc_embed<1>, grid, block, 0, st, tok, pos_id, pw, pp, pt, n_tokens, (_Float16*)out); break;
+        case 2: hipLaunchKernelGGL(k_enc_embed<2>, grid, block, 0, st, tok, pos_id, pw, pp, pt, n_tokens, (_Float16*)out); break;
+        case 3: hipLaunchKernelGGL(k_enc_embed<3>, grid, block, 0, st, tok, pos_id, pw, pp, pt, n_tokens, (_Float16*)out); break;
+        default: hipLaunchKernelGGL(k_enc_embed<4>, grid, block, 0, st, tok, pos_id, pw, pp, pt, n_tokens, (_Float16*)out); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+extern "C" int rdx_enc_layernorm_rows_f16(int device, const void* s, const void* gamma, const void* beta, float eps, int rows, int hidden,
+                                          float* out, void* stream) {
+    if (rows < 0 || hidden < 512 || hidden > 2048 || hidden % 512) return fail(RDX_ERR_INVALID, "rdx_enc_layernorm_rows_f16: hidden must be 512, 1024, 1536 or 2048");
+    if (rows == 0) return RDX_OK;
+    if (!s || !gamma || !beta || !out) return fail(RDX_ERR_INVALID, "rdx_enc_layernorm_rows_f16: null pointer");
+    if (((uintptr_t)s | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out) & 15) return fail(RDX_ERR_INVALID, "rdx_enc_layernorm_rows_f16: pointers must be 16-byte aligned");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_layernorm_rows_f16: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    const _Float16 *ps = (const _Float16*)s, *pg = (const _Float16*)gamma, *pb = (const _Float16*)beta;
+    switch (hidden / 512) {
+        case 1: hipLaunchKernelGGL(k_enc_ln_rows<1>, grid, block, 0, st, ps, pg, pb, eps, rows, out); break;
+        case 2: hipLaunchKernelGGL(k_enc_ln_rows<2>, grid, block, 0, st, ps, pg, pb, eps, rows, out); break;
+        case 3: hipLaunchKernelGGL(k_enc_ln_rows<3>, grid, block, 0, st, ps, pg, pb, eps, rows, out); break;
+        default: hipLaunchKernelGGL(k_enc_ln_rows<4>, grid, block, 0, st, ps, pg, pb, eps, rows, out); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+extern "C" int rdx_enc_gelu_f16(int device, void* x, int64_t n, void* stream) {
+    if (n < 0 || n % 8) return fail(RDX_ERR_INVALID, "rdx_enc_gelu_f16: n must be a non-negative multiple of 8");
+    if (n == 0) return RDX_OK;
+    if (!x || ((uintptr_t)x & 15)) return fail(RDX_ERR_INVALID, "rdx_enc_gelu_f16: x must be a 16-byte aligned device pointer");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_gelu_f16: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    const int64_t n8 = n / 8;
+    const unsigned grid = (unsigned)std::min<int64_t>((n8 + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_enc_gelu, dim3(grid), dim3(256), 0, (hipStream_t)stream, (_Float16*)x, n8);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// cross-encoder reranker: classification head and selection (rerank_kernel.hpp)
+// ------------------------------------------------------------------------------------------------
+extern "C" int rdx_rerank_head_f16(int device, const float* cls, int n, int hidden, const void* w_dense, const void* b_dense,
+                                   const void* w_out, const void* b_out, double* workspace, float* scores, void* stream) {
+    if (n < 1 || n > RERANK_MAX_N) return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: n must be in [1, 1024]");
+    if (hidden < 64 || hidden > RERANK_MAX_HIDDEN || hidden % 64)
+        return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: hidden must be a multiple of 64 in [64, 4096]");
+    if (!cls || !w_dense || !b_dense || !w_out || !b_out || !workspace || !scores) return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: null pointer");
+    if (((uintptr_t)cls | (uintptr_t)w_dense) & 15) return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: cls and w_dense must be 16-byte aligned");
+    if (((uintptr_t)b_dense | (uintptr_t)w_out | (uintptr_t)b_out) & 1 || ((uintptr_t)workspace & 7) || ((uintptr_t)scores & 3))
+        return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: misaligned pointer");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = hidden / RERANK_FEATURES;
+    const dim3 grid((unsigned)blocks, (unsigned)((n + RERANK_ROWS_PER_BLOCK - 1) / RERANK_ROWS_PER_BLOCK));
+    const size_t lds = (size_t)RERANK_FEATURES * hidden * sizeof(_Float16);   // <= 64 KiB at hidden 4096
+    RDX_TRY(enc_dynamic_lds(device, (const void*)k_rerank_head, lds));
+    hipLaunchKernelGGL(k_rerank_head, grid, dim3(RERANK_HEAD_THREADS), lds, st, cls, n, hidden, (const _Float16*)w_dense,
+                       (const _Float16*)b_dense, (const _Float16*)w_out, workspace);
+    HIP_TRY(hipGetLastError());
+    const int rows_per_block = RERANK_THREADS / 64;                           // K_R2: one wave per row
+    hipLaunchKernelGGL(k_rerank_combine, dim3((unsigned)((n + rows_per_block - 1) / rows_per_block)), dim3(RERANK_THREADS), 0, st,
+                       (const double*)workspace, n, blocks, (const _Float16*)b_out, scores);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+extern "C" int rdx_rerank_select(int device, const float* scores, const double* boosts, int n, int top_k, double min_score,
+                                 int keep_min, int32_t* order, double* final_score, int32_t* count, void* stream) {
+    if (n < 1 || n > RERANK_MAX_N) return fail(RDX_ERR_INVALID, "rdx_rerank_select: n must be in [1, 1024]");
+    if (top_k < 0) return fail(RDX_ERR_INVALID, "rdx_rerank_select: top_k must be >= 0");
+    if (keep_min < 0) return fail(RDX_ERR_INVALID, "rdx_rerank_select: keep_min must be >= 0");
+    if (!scores || !order || !final_score || !count) return fail(RDX_ERR_INVALID, "rdx_rerank_select: null pointer");
+    if (((uintptr_t)scores & 3) || ((uintptr_t)boosts & 7) || ((uintptr_t)order & 3) || ((uintptr_t)final_score & 7) || ((uintptr_t)count & 3))
+        return fail(RDX_ERR_INVALID, "rdx_rerank_select: misaligned pointer");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_rerank_select: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    hipLaunchKernelGGL(k_rerank_select, dim3(1), dim3(RERANK_MAX_N), 0, (hipStream_t)stream, scores, boosts, n, top_k, min_score,
+                       keep_min, order, final_score, count);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}

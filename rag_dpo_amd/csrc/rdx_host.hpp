@@ -1,0 +1,187 @@
+// rdx_host.hpp — what the host units of librdx (rdx_index.hip, rdx_enc.hip, rdx_bm25.hip, rdx_docs.hip) share: the error
+// string behind rdx_last_error(), the device / pinned buffers, and the wait on a word in pinned memory.
+#pragma once
+#include "../../include/rdx.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <thread>
+#include <sched.h>
+
+#include <immintrin.h>
+
+// one definition for the whole library (inline), invisible outside it (hidden)
+#define RDX_HOST_SHARED inline __attribute__((visibility("hidden")))
+
+// ------------------------------------------------------------------------------------------------
+// errors
+// ------------------------------------------------------------------------------------------------
+RDX_HOST_SHARED thread_local std::string g_err;
+
+RDX_HOST_SHARED int fail(int code, const std::string& msg) {
+    g_err = msg;
+    return code;
+}
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t _e = (expr);                                                                    \
+        if (_e != hipSuccess) {                                                                    \
+            const int _code = (_e == hipErrorOutOfMemory) ? RDX_ERR_NOMEM : RDX_ERR_HIP;           \
+            return fail(_code, std::string(#expr) + ": " + hipGetErrorString(_e));                \
+        }                                                                                          \
+    } while (0)
+
+#define RDX_TRY(expr)              \
+    do {                           \
+        int _r = (expr);           \
+        if (_r != RDX_OK) return _r; \
+    } while (0)
+
+// grow-only device buffer
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    int ensure(size_t need) {
+        if (need <= bytes) return RDX_OK;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+        size_t want = need + need / 4;
+        hipError_t e = hipMalloc(&p, want);
+        if (e != hipSuccess) {
+            want = need;
+            e = hipMalloc(&p, want);
+        }
+        if (e != hipSuccess) {
+            p = nullptr;
+            return fail(RDX_ERR_NOMEM, std::string("hipMalloc(") + std::to_string(need) + "): " + hipGetErrorString(e));
+        }
+        bytes = want;
+        return RDX_OK;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    template <class T>
+    T* as() const { return reinterpret_cast<T*>(p); }
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }   // error paths that return early do not leak scratch
+};
+
+struct PinnedBuf {   // grow-only pinned host staging
+    void* p = nullptr;
+    size_t bytes = 0;
+    int ensure(size_t need) {
+        if (need <= bytes) return RDX_OK;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        bytes = 0;
+        const size_t want = std::max(need + need / 4, (size_t)4096);
+        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            p = nullptr;
+            return fail(RDX_ERR_NOMEM, std::string("hipHostMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e));
+        }
+        bytes = want;
+        return RDX_OK;
+    }
+    ~PinnedBuf() {
+        if (p) (void)hipHostFree(p);
+    }
+};
+
+// grow a device buffer to `need` bytes, keeping its first `keep` (geometric: appends in small batches stay linear)
+RDX_HOST_SHARED int grow_keep(DevBuf& b, size_t keep, size_t need, const char* what) {
+    if (need <= b.bytes) return RDX_OK;
+    size_t want = std::max(need, b.bytes + b.bytes / 2);
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, want);
+    if (e != hipSuccess && want > need) e = hipMalloc(&p, want = need);
+    if (e != hipSuccess) return fail(RDX_ERR_NOMEM, std::string("rdx_docs: growing the ") + what + " to " + std::to_string(need) + " bytes: " + hipGetErrorString(e));
+    if (keep > 0) e = hipMemcpy(p, b.p, keep, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return fail(RDX_ERR_HIP, std::string("rdx_docs: ") + hipGetErrorString(e));
+    }
+    b.release();
+    b.p = p;
+    b.bytes = want;
+    return RDX_OK;
+}
+
+// zeroed pinned host memory the device reaches over PCIe: its host address and the device's address of the same bytes
+RDX_HOST_SHARED int map_pinned(size_t bytes, void** host, void** dev) {
+    void* p = nullptr;
+    HIP_TRY(hipHostMalloc(&p, bytes, hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(p, 0, bytes);
+    void* d = nullptr;
+    hipError_t e = hipHostGetDevicePointer(&d, p, 0);
+    if (e != hipSuccess) {
+        (void)hipHostFree(p);
+        return fail(RDX_ERR_HIP, std::string("hipHostGetDevicePointer: ") + hipGetErrorString(e));
+    }
+    *host = p;
+    *dev = d;
+    return RDX_OK;
+}
+
+// Waits until ready() says a word in pinned host memory has arrived — never for the stream: an asynchronous caller may have enqueued
+// other work behind the search or merge that publishes the word (BASELINE config 5: the next batch's query encode, 15 ms of kernels),
+// and a stream synchronise would wait for that too. Hot spin for 0.4 ms (a small search ends inside it), then poll with a yield
+// between looks (a 0.6 - 25 ms search is noticed within a microsecond; measured with 20 us sleeps instead: +30 us on a 0.56 ms search,
+// +170 us on a 2.2 ms one), after 200 ms with 50 us sleeps. The stream is only QUERIED, every 50 ms, to turn a failed or vanished
+// launch into an error instead of an endless wait. 0 = arrived, 1 = the stream ran dry without the word, < 0 = error code.
+// Wait policy (rdx_set_wait_policy; environment RDX_WAIT_SPIN_US / RDX_WAIT_SLEEP_US at load): the default burns a host core for the
+// length of a search — right for a benchmark or one rank per GPU, wrong for a server whose sessions share the cores (the reference
+// serves concurrent Streamlit sessions from one process, app.py:42-43). sleep_us > 0: after the hot spin the waiter SLEEPS that long
+// between looks (a 15 ms scan then costs the core ~1 % instead of 100 %; the result is noticed up to sleep_us later).
+RDX_HOST_SHARED std::atomic<int> g_wait_spin_us{[] {
+    const char* e = std::getenv("RDX_WAIT_SPIN_US");
+    return e ? std::atoi(e) : 400;
+}()};
+RDX_HOST_SHARED std::atomic<int> g_wait_sleep_us{[] {
+    const char* e = std::getenv("RDX_WAIT_SLEEP_US");
+    return e ? std::max(0, std::atoi(e)) : 0;
+}()};
+template <class F>
+RDX_HOST_SHARED int wait_word(F ready, hipStream_t st) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int spin_us = g_wait_spin_us.load(std::memory_order_relaxed), sleep_us = g_wait_sleep_us.load(std::memory_order_relaxed);
+    for (unsigned spins = 1;; ++spins) {
+        if (ready()) return 0;
+        if (spin_us == 0) break;
+        _mm_pause();
+        if ((spins & 255u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(spin_us)) break;
+    }
+    auto next_query = t0 + std::chrono::milliseconds(50);
+    const auto t_sleep = t0 + std::chrono::milliseconds(200);
+    for (unsigned n = 1;; ++n) {
+        if (ready()) return 0;
+        if (sleep_us > 0) {
+            std::this_thread::sleep_for(std::chrono::microseconds(sleep_us));
+            if (ready()) return 0;
+        } else if ((n & 15u) != 0) {
+            sched_yield();
+            continue;
+        }
+        const auto now = std::chrono::steady_clock::now();
+        if (sleep_us == 0 && now >= t_sleep) std::this_thread::sleep_for(std::chrono::microseconds(50));
+        if (now >= next_query) {
+            const hipError_t e = hipStreamQuery(st);
+            if (e == hipSuccess) return ready() ? 0 : 1;   // everything enqueued has run: the word must be there
+            if (e != hipErrorNotReady) return fail(RDX_ERR_HIP, std::string("hipStreamQuery: ") + hipGetErrorString(e));
+            next_query = now + std::chrono::milliseconds(50);
+        }
+    }
+}

@@ -1,0 +1,1717 @@
+// rdx_index.hip — the dense index of librdx: the rdx_index lifecycle, options and ingest, rdx_l2_normalize, the search, masks,
+// merge and signal of include/rdx.h. The only unit that holds a k_scan kernel (rag_dpo_amd/build.py checks that).
+#include "rdx_host.hpp"
+
+#include <cmath>
+#include <cstddef>
+#include <cstdio>
+#include <mutex>
+#include <unordered_map>
+#include <vector>
+
+#include "k_rows.hpp"
+#include "refine_kernel.hpp"
+#include "scan_kernel.hpp"
+
+using namespace rdx;
+
+// Host callers: where the results go (see search_chunk)
+struct HostOut {
+    float* score;
+    int64_t* row;
+    int32_t* count;
+    bool stale;
+};
+
+// What a search of (rows, nq, k, options) launches: every choice, made by plan_search before anything is enqueued
+struct SearchPlan {
+    int64_t nq = 0;
+    int k = 0, depth = 0, nq_pad = 0;  // depth 0 = the caller's batch; 1 = the second-chance batch of overflowed queries
+    int prof = 0;                      // option "profile" (depth 0 only)
+    bool exact_only = false;           // the exact full scan alone; the fields down to `stamps` are the MFMA path's
+    int bn = 0, nqt = 0, grid = 0, G = 0, n_streams = 0, n_sets = 0;   // G workgroups per XCD and query tile, 8 G streams
+    bool res = false;                  // the 64-query tile stays resident in LDS
+    int64_t n_tiles = 0, n_blocks32 = 0;
+    bool use_boot = false;             // bootstrap: k_boot over boot_units 32-row blocks, or k_scan<EPI_SETMAX> (the rest)
+    int64_t boot_units = 0;
+    int boot_sets = 0, bn_b = 0, nqt_b = 0, n_sets_b = 0, div = 1, n_sets_used = 0;
+    int64_t boot_tiles = 0, boot_wave_off = 0;   // the tile bootstrap's ScanParams n_tiles, wave_off, row_off, span
+    int boot_row_off = 0, boot_span = 0;
+    bool use_small = false;            // k_scan_small as the main scan
+    bool i8 = false;                   // the main scan runs on the int8 copies (k_scan<..., I8>; DESIGN.md §5 "int8 coarse pass")
+    int64_t sample_rows = 0;
+    double expected_per_query = 0.0;   // candidates per query a random corpus would emit with this sample
+    uint32_t capw = 0, list_cap = 0;
+    int k_sel = 0;                     // rank of the sampled score the threshold is taken from (< k: speculative)
+    float slack = 0.f;
+    bool balance = false;              // XCD-weighted split of the main scan's tiles
+    int bulk_it = 0, xlo[9] = {};
+    bool stamps = false;               // the main scan's workgroups stamp their times
+    bool ride = false, big_copy = false;   // host results: with k_finish into pinned staging, or D2H copies
+    size_t b_s = 0, b_r = 0, b_c = 0;  // result bytes: scores, rows, counts
+};
+
+// the caller's buffers of one search chunk (device addresses)
+struct SearchIO {
+    const float* queries;
+    const uint32_t* allow;
+    float* score;
+    int64_t* row;
+    int32_t* count;
+    int32_t* flags;   // rdx_search_async(out_flags): the "incomplete" word of the packed partial, or NULL
+};
+
+// A search whose kernels (up to k_finish) are enqueued and whose host half — waiting for the mailbox, copying small
+// results out, re-weighting the XCD shares, the fallback passes for overflowed queries, the statistics — has not run yet.
+// rdx_search runs that half at once; rdx_search_async leaves it to rdx_search_wait, so that the caller can enqueue what
+// consumes the results (the RCCL all-gather and the merge) while the scan is still running.
+struct PendingSearch {
+    bool active = false;
+    SearchPlan plan;
+    SearchIO io = {};
+    hipStream_t st = nullptr;
+    unsigned long long seq = 0;
+    rdx_search_stats stats = {};   // rdx_search_async only: the statistics of the deferred search
+};
+
+// ------------------------------------------------------------------------------------------------
+// the index: one corpus shard resident in one GPU's HBM
+// ------------------------------------------------------------------------------------------------
+struct rdx_index {
+    int device = 0;
+    int dim = 0, dim_pad = 0, ksteps = 0, scale_log2 = 0;
+    int n_cu = 256;
+    int64_t rows = 0, cap = 0;   // cap is a multiple of 256
+    float* master = nullptr;     // [cap][dim] normalised fp32 rows (default), or NULL with option compact_master:
+    uint16_t* raw16 = nullptr;   //   [cap][dim] raw bf16 rows as delivered ...
+    double* den = nullptr;       //   [cap] ... and their divisors max(|x|, 1e-12); k_rows.hpp MasterView
+    int compact = 0;             // option "compact_master" (settable while the index is empty): 4 instead of 6 B/element
+    MasterView mv() const { return MasterView{master, raw16, den}; }
+    _Float16* shadow = nullptr;  // [cap][dim_pad] fp16 scan copy in MFMA fragment order (rdx_common.hpp corpus_off)
+    hipStream_t own_stream = nullptr;
+    std::mutex mu;
+
+    // options
+    int force_exact = 0, force_fast = 0, profile = 0, retry = 1, xcd_balance = 1, fuse_epilogue = 1, force_bn = 0;
+    int half_boot = 1;       // option: 129..256 queries take their threshold sample as two 128-query tiles per sampled corpus tile
+    int small_scan = 1;      // option: k_scan_small (split-K over all rows) as the main scan of small launches
+    int split_boot = 1;      // option: k_boot (K loop split over the waves) for the threshold bootstrap of small launches
+    int fuse_finish = 1;     // option: the end-of-search work runs in the last block of the search's last kernel (0: its own launch k_finish)
+    int spec_tau = 1;        // option: speculative scan threshold (rank < k of the sample, verified by k_refine)
+    int dense_sample = 0;    // searches left with a threshold sample twice as dense (set when a search emitted 3x a random corpus' candidates)
+    int spread_boot = 1;     // option: a tile bootstrap (any not taken by k_boot) samples every div-th 32-row block instead of every div-th 256-row tile
+    int spec_backoff = 0;    // searches left during which the provable threshold is used (set when a speculation failed)
+    int coarse_i8 = 2;       // option: main scan on int8 MFMA — 0 never, 1 whenever the shape allows, 2 (default) large batches on large shards
+    int refine_pilot = 4;    // option: int8 searches find their re-score band in two rounds — the pilot*k best coarse hits first, then what lies
+                             // within E_q of their exact k-th score (refine_kernel.hpp); 0 = one band of 2E_q below c_k
+    int coarse_bits = 0;     // the last search's coarse pass: 16, 8, or 0 (exact path only); rdx_search_last_coarse_bits
+    int i8_backoff = 0;      // searches left during which automatic choice (coarse_i8 = 2) keeps the fp16 pass (set when an int8 search
+                             // sent more than 1 in 64 of its queries to the fallback passes: rows too crowded for its band, see adapt_sampling)
+    double xw[8] = {1, 1, 1, 1, 1, 1, 1, 1};   // relative speed of the XCDs as the last main scans showed it (sum 8)
+    int sample_div = 64;
+    int64_t cand_cap = 0;   // 0 = automatic
+    int64_t row_base = 0;   // added to every returned row id (global ids of a shard)
+    int64_t* row_map = nullptr;   // [cap] local row -> returned row id (strictly increasing), or NULL = local + row_base
+
+    // scratch (grow-only; never allocated inside a warmed-up search)
+    DevBuf r_list, r_q, r_s, r_r, r_c;   // second-chance batch of overflowed queries
+    DevBuf wgt;                          // [grid][2] workgroup time stamps of the main scan
+    std::unordered_map<const void*, size_t> func_lds;   // dynamic-LDS limit already raised for a kernel ON THIS DEVICE
+    DevBuf staging, qraw, qhat, qshadow, tau, cntw, cand, setmax, exact_list, iota, dense, ctr, bad, o_score, o_row,
+        o_count, mask, ids;
+    // int8 coarse pass: corpus copy [cap][dim_pad] in corpus_off8 order + s_b per 32-row block + the largest eps_b (built by the first
+    // search that takes the path, rows [0, i8_valid) current; not persisted) and the per-search query copy, scales, bounds, thresholds
+    DevBuf c8, sblk, eps8, qshadow8, tq8, eq8, nq8, thr8, taus8, twoe8;
+    int64_t i8_valid = 0;
+    // end-of-search mailbox in pinned host memory (k_finish writes it over PCIe; the host spins on its sequence number)
+    Mailbox* mbox = nullptr;          // host address
+    Mailbox* mbox_dev = nullptr;      // the same memory as the device sees it
+    unsigned long long seq = 0;       // number of the last search enqueued on this index
+    char* pin_out = nullptr;          // pinned staging for the small results of host callers (score | row | count)
+    char* pin_out_dev = nullptr;
+    bool ctr_ready = false;           // the counter block was zeroed once; afterwards every k_finish re-zeroes it
+    PendingSearch pending;            // rdx_search_async: the search whose host half is still to run
+    hipEvent_t ev[8] = {};
+    bool ev_ok = false;
+    rdx_search_stats stats = {};
+
+    float scale() const { return std::ldexp(1.0f, scale_log2); }
+    float two_e() const { return 2.0f * (1.0e-3f + 2.5e-7f * (float)dim_pad); }   // see DESIGN.md "error bound"
+};
+
+// a `where` bitmap kept resident in HBM between searches (the reference's filters are a handful of fixed shapes)
+struct rdx_mask {
+    int device = 0;
+    int64_t rows = 0;   // row count of the index when the mask was made: a mask never outlives a write to the index
+    DevBuf words;
+};
+
+// a pinned, device-visible word the merge kernel publishes ((sequence << 1) | value) and the host waits on
+struct rdx_signal {
+    int device = 0;
+    unsigned long long* host = nullptr;
+    unsigned long long* dev = nullptr;
+    unsigned long long seq = 0;   // number of the last merge that was given this signal
+};
+
+static size_t shadow_bytes(const rdx_index* h, int64_t cap) { return (size_t)cap * h->dim_pad * 2; }
+
+static int set_device(const rdx_index* h) {
+    HIP_TRY(hipSetDevice(h->device));
+    return RDX_OK;
+}
+
+static void free_master(float* m, uint16_t* r, double* d) {
+    if (m) (void)hipFree(m);
+    if (r) (void)hipFree(r);
+    if (d) (void)hipFree(d);
+}
+
+// master storage for `cap` rows in the index's mode
+static hipError_t alloc_master(const rdx_index* h, int64_t cap, float** m, uint16_t** r, double** d) {
+    *m = nullptr;
+    *r = nullptr;
+    *d = nullptr;
+    if (!h->compact) return hipMalloc((void**)m, (size_t)cap * h->dim * 4);
+    hipError_t e = hipMalloc((void**)r, (size_t)cap * h->dim * 2);
+    if (e == hipSuccess) e = hipMalloc((void**)d, (size_t)cap * 8);
+    if (e != hipSuccess) {
+        free_master(nullptr, *r, *d);
+        *r = nullptr;
+        *d = nullptr;
+    }
+    return e;
+}
+
+static int grow(rdx_index* h, int64_t need_rows) {
+    if (need_rows <= h->cap) return RDX_OK;
+    int64_t ncap = std::max<int64_t>(need_rows, h->cap + h->cap / 2);
+    ncap = (ncap + 255) / 256 * 256;
+    float* nm = nullptr;
+    uint16_t* nr16 = nullptr;
+    double* nd = nullptr;
+    _Float16* ns = nullptr;
+    hipError_t e = alloc_master(h, ncap, &nm, &nr16, &nd);
+    if (e == hipSuccess) e = hipMalloc((void**)&ns, shadow_bytes(h, ncap));
+    if (e != hipSuccess && ncap > (need_rows + 255) / 256 * 256) {   // retry without head-room
+        free_master(nm, nr16, nd);
+        ncap = (need_rows + 255) / 256 * 256;
+        e = alloc_master(h, ncap, &nm, &nr16, &nd);
+        if (e == hipSuccess) e = hipMalloc((void**)&ns, shadow_bytes(h, ncap));
+    }
+    if (e != hipSuccess) {
+        free_master(nm, nr16, nd);
+        return fail(RDX_ERR_NOMEM, std::string("growing index to ") + std::to_string(ncap) + " rows: " + hipGetErrorString(e));
+    }
+    hipStream_t st = h->own_stream;
+    int64_t* nr = nullptr;
+    if (h->row_map) {   // the id map grows with the rows: old entries kept, new ones start as local + row_base
+        e = hipMalloc((void**)&nr, (size_t)ncap * 8);
+        if (e != hipSuccess) {
+            free_master(nm, nr16, nd);
+            (void)hipFree(ns);
+            return fail(RDX_ERR_NOMEM, std::string("growing the row id map: ") + hipGetErrorString(e));
+        }
+        if (h->rows > 0) HIP_TRY(hipMemcpyAsync(nr, h->row_map, (size_t)h->rows * 8, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(k_iota64, dim3((unsigned)((ncap - h->rows + 255) / 256)), dim3(256), 0, st, nr, h->rows, ncap - h->rows, h->row_base);
+    }
+    HIP_TRY(hipMemsetAsync(ns, 0, shadow_bytes(h, ncap), st));
+    if (h->rows > 0) {
+        if (h->compact) {
+            HIP_TRY(hipMemcpyAsync(nr16, h->raw16, (size_t)h->rows * h->dim * 2, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(nd, h->den, (size_t)h->rows * 8, hipMemcpyDeviceToDevice, st));
+        } else {
+            HIP_TRY(hipMemcpyAsync(nm, h->master, (size_t)h->rows * h->dim * 4, hipMemcpyDeviceToDevice, st));
+        }
+        HIP_TRY(hipMemcpyAsync(ns, h->shadow, shadow_bytes(h, h->cap), hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    free_master(h->master, h->raw16, h->den);
+    if (h->shadow) (void)hipFree(h->shadow);
+    if (h->row_map) (void)hipFree(h->row_map);
+    h->master = nm;
+    h->raw16 = nr16;
+    h->den = nd;
+    h->shadow = ns;
+    h->row_map = nr;
+    h->cap = ncap;
+    return RDX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// search: plan, enqueue, complete — ahead of the lifecycle because every call that writes to the index runs finish_pending first
+// ------------------------------------------------------------------------------------------------
+// kernels using more than 64 KiB of dynamic LDS need the limit raised once per kernel and device (the attribute is
+// per device: the cache lives in the index, which is bound to one)
+static int ensure_dynamic_lds(rdx_index* h, const void* func, size_t bytes) {
+    size_t& have = h->func_lds[func];
+    if (have < bytes) {
+        HIP_TRY(hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        have = bytes;
+    }
+    return RDX_OK;
+}
+
+template <int BN, int EPI, bool RES, bool NTT = false, bool FUSED = false, bool I8 = false>
+static int launch_scan(rdx_index* h, const ScanParams& p, int grid, hipStream_t st) {
+    // LDS: query-image ring (or the whole resident query tile) + BN hit counters + BN thresholds
+    const size_t lds = (size_t)(RES ? p.ksteps : RING_SLOTS) * BN * BK * 2 + BN * (I8 ? 12 : 8);   // (I8: + BN query scales)
+    void (*kern)(const ScanParams) = p.allow ? k_scan<BN, EPI, true, RES, NTT, FUSED, I8> : k_scan<BN, EPI, false, RES, NTT, FUSED, I8>;
+    RDX_TRY(ensure_dynamic_lds(h, (const void*)kern, lds));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, p);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+template <int EPI>
+static int launch_scan_bn(rdx_index* h, int bn, bool res, const ScanParams& p, int grid, hipStream_t st) {
+    // NTT (4th template argument): one query tile -> every corpus byte is read by exactly one workgroup -> non-temporal loads
+    if (bn == 64) {
+        if (p.nqt == 1) return res ? launch_scan<64, EPI, true, true>(h, p, grid, st) : launch_scan<64, EPI, false, true>(h, p, grid, st);
+        return res ? launch_scan<64, EPI, true>(h, p, grid, st) : launch_scan<64, EPI, false>(h, p, grid, st);
+    }
+    if (bn == 128) return p.nqt == 1 ? launch_scan<128, EPI, false, true>(h, p, grid, st) : launch_scan<128, EPI, false>(h, p, grid, st);
+    if constexpr (EPI == EPI_EMIT) {
+#ifdef RDX_CHECK_BOUNDS
+        constexpr bool HAVE_FUSED = false;   // the address-checking test build carries one more live value: no fused variants
+#else
+        constexpr bool HAVE_FUSED = true;
+#endif
+        // option fuse_epilogue (default on: +1 % at B = 1024 since the static wave priority went in): with an even
+        // number of k-steps per tile the emit check of a tile rides with the first k-step of the next one
+        if constexpr (HAVE_FUSED) {
+            if ((p.ksteps & 1) == 0 && h->fuse_epilogue) {
+                if (p.nqt == 1) return launch_scan<256, EPI, false, true, true>(h, p, grid, st);
+                return launch_scan<256, EPI, false, false, true>(h, p, grid, st);
+            }
+        }
+    }
+    if (p.nqt == 1) return launch_scan<256, EPI, false, true>(h, p, grid, st);   // one query tile: corpus read once -> nt loads
+    return launch_scan<256, EPI, false>(h, p, grid, st);
+}
+
+// the int8 main pass (plan_search p.i8: 256-query tiles, several of them, so never the one-tile nt variants)
+static int launch_scan_i8(rdx_index* h, const ScanParams& p, int grid, hipStream_t st) {
+#ifndef RDX_CHECK_BOUNDS
+    if ((p.ksteps & 1) == 0 && h->fuse_epilogue) return launch_scan<256, EPI_EMIT, false, false, true, true>(h, p, grid, st);
+#endif
+    return launch_scan<256, EPI_EMIT, false, false, false, true>(h, p, grid, st);
+}
+
+static const int K_FAST_MAX = 256;   // larger k goes through the exact full scan
+
+// exact full scan for the queries listed in d_list[0..n_list)
+static int run_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, const uint32_t* d_allow, float* d_score,
+                     int64_t* d_row, int32_t* d_count, hipStream_t st, bool stamps = false, const FinishArgs* fin = nullptr) {
+    const FinishArgs no_fin = {};   // (ctr == NULL: the launch does not end a search)
+    // profile = 3: the scoring kernel's first block and the select kernel's last block leave their times in the counter block
+    unsigned long long* t_first = stamps ? reinterpret_cast<unsigned long long*>(h->ctr.as<char>() + offsetof(RefineCounters, t_first_inv)) : nullptr;
+    unsigned long long* t_last = stamps ? reinterpret_cast<unsigned long long*>(h->ctr.as<char>() + offsetof(RefineCounters, t_last)) : nullptr;
+    RDX_TRY(h->dense.ensure((size_t)QX * std::max<int64_t>(h->rows, 1) * 4));
+    const int grid_rows = (int)std::min<int64_t>((h->rows + 3) / 4, (int64_t)h->n_cu * 16);   // one row per wave up to 16 Ki rows
+    for (int j0 = 0; j0 < n_list; j0 += QX) {
+        const int nq = std::min(QX, n_list - j0);
+        if (h->rows > 0 && h->dim <= 1024) {
+            // queries in registers, two rows in flight per wave, 2 blocks per CU (all resident at once)
+            const int u = (h->dim / 4 + 63) / 64;
+            const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>((h->rows + 3) / 4, (int64_t)h->n_cu * 2))), b(256);
+#define RDX_K5A(U) hipLaunchKernelGGL(k_exact_scores_reg<U>, g, b, 0, st, h->mv(), h->rows, h->dim, h->qhat.as<float>(), d_list + j0, nq, d_allow, h->dense.as<float>(), t_first)
+            if (u == 1) RDX_K5A(1);
+            else if (u == 2) RDX_K5A(2);
+            else if (u == 3) RDX_K5A(3);
+            else RDX_K5A(4);
+#undef RDX_K5A
+            HIP_TRY(hipGetLastError());
+        } else if (h->rows > 0) {
+            hipLaunchKernelGGL(k_exact_scores, dim3(std::max(grid_rows, 1)), dim3(256), (size_t)nq * h->dim * 4, st, h->mv(),
+                               h->rows, h->dim, h->qhat.as<float>(), d_list + j0, nq, d_allow, h->dense.as<float>(), t_first);
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_select_dense, dim3(nq), dim3(1024), 0, st, h->dense.as<float>(), h->rows, d_list + j0, k, h->row_base,
+                           h->row_map, d_score, d_row, d_count, t_last, (fin && j0 + QX >= n_list) ? *fin : no_fin);
+        HIP_TRY(hipGetLastError());
+    }
+    return RDX_OK;
+}
+
+// Host callers (HostOut): small results travel with the end-of-search kernel into pinned staging and are copied to the
+// caller's buffers by the CPU once the mailbox says the search is complete; large ones use D2H copies. When a fallback pass
+// had to rewrite some results afterwards they are copied again (HostOut::stale).
+static const size_t PIN_MAX = 256 * 1024;   // results up to this size ride with k_finish (one block writing over PCIe)
+
+static int copy_results_to_host(const HostOut& ho, const float* d_score, const int64_t* d_row, const int32_t* d_count, int64_t nq,
+                                int k, hipStream_t st) {
+    if (k > 0) {
+        HIP_TRY(hipMemcpyAsync(ho.score, d_score, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(ho.row, d_row, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(ho.count, d_count, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    return RDX_OK;
+}
+
+// the wait policy of wait_word (rdx_host.hpp)
+extern "C" int rdx_set_wait_policy(int spin_us, int sleep_us) {
+    if (spin_us < 0 || sleep_us < 0 || sleep_us > 1000000) return fail(RDX_ERR_INVALID, "rdx_set_wait_policy: spin_us >= 0, 0 <= sleep_us <= 1000000");
+    g_wait_spin_us.store(spin_us);
+    g_wait_sleep_us.store(sleep_us);
+    return RDX_OK;
+}
+
+// Speculative threshold. The provable threshold is the k-th largest sampled score: k/S of the sample's
+// quantile scale where the corpus' k-th score sits at k/N — with a 1.6 % sample and k = 10 that is 60x the hits one
+// needs. The corpus' k-th score is ESTIMATED by the sample's j-th largest with j ~ k*S/N; taking the smallest j for
+// which fewer than k rows of the corpus lie above it (with a factor 2 for the 2E band the verification needs) with
+// probability <= 1e-7 per query (the count above the sample's j-th largest is N/S * Gamma(j)) cuts the hits 2-6x
+// (c4: 890 -> ~430 per query, c3: 4500 -> ~700). k_refine verifies every query (c_k - 2E >= T); a failed one takes the
+// fallback passes, which use rank k, and switches speculation off for the next searches (structured corpora, where
+// "every div-th tile" is not a random sample; h.spec_backoff counts them down in enqueue_scan, after this read).
+static int speculative_rank(const rdx_index& h, int k, int depth, int64_t sample_rows) {
+    if (!h.spec_tau || depth != 0 || h.spec_backoff != 0 || k <= 1) return k;
+    const double lam = 2.0 * (double)k * (double)sample_rows / (double)std::max<int64_t>(h.rows, 1);
+    double term = std::exp(-lam), cdf = term;   // P(Poisson(lam) <= j - 1)
+    int j = 1;
+    while (1.0 - cdf > 1e-7 && j < k) {
+        term *= lam / j;
+        cdf += term;
+        ++j;
+    }
+    return std::min(k, j);
+}
+
+// bulk: what the slowest XCD should get, dealt interleaved to everybody (whole iterations of all streams);
+// tail: the rest, one contiguous range per XCD holding what that XCD should get beyond the bulk
+static void plan_xcd_split(const rdx_index& h, SearchPlan* p) {
+    const double wmin = *std::min_element(h.xw, h.xw + 8);
+    p->bulk_it = (int)std::max<int64_t>(0, (int64_t)std::floor((double)p->n_tiles * wmin / 8.0 / p->G) - 1);
+    const int64_t t0 = (int64_t)p->bulk_it * p->n_streams, tail = p->n_tiles - t0;
+    double want[8], sum = 0;
+    for (int x = 0; x < 8; ++x) sum += (want[x] = std::max(0.0, (double)p->n_tiles * h.xw[x] / 8.0 - (double)p->bulk_it * p->G));
+    double acc = 0;
+    for (int x = 0; x <= 8; ++x) {
+        p->xlo[x] = (int)(t0 + std::llround((double)tail * (sum > 0 ? acc / sum : x / 8.0)));
+        if (x < 8) acc += want[x];
+    }
+    p->xlo[8] = (int)p->n_tiles;
+}
+
+// Every decision of a search of nq (<= one launch) queries at `depth`, from the index's state and options alone: no HIP call,
+// nothing written. The internal checks fail here, before anything is enqueued.
+static int plan_search(const rdx_index& h, int64_t nq, int k, int depth, bool host_out, SearchPlan* out) {
+    SearchPlan& p = *out = SearchPlan{};
+    p.nq = nq;
+    p.k = k;
+    p.depth = depth;
+    p.nq_pad = (int)((nq + 255) / 256 * 256);
+    p.prof = depth == 0 ? h.profile : 0;
+    p.b_s = (size_t)nq * k * 4;
+    p.b_r = (size_t)nq * k * 8;
+    p.b_c = (size_t)nq * 4;
+    p.ride = host_out && p.b_s + p.b_r + p.b_c <= PIN_MAX;
+    p.big_copy = host_out && !p.ride;
+
+    // small problems and huge k are served by the exact full scan alone (one fp32 read of the corpus)
+    // Round 2 re-measured the crossover (B = 4: exact path 0.060 / 0.099 / 0.129 ms at 24 k / 40 k / 60 k rows, MFMA path 0.081 / 0.085 /
+    // 0.087): the exact path costs ceil(nq / 4) passes of (1.28 us per 1000 rows + 10 us) on top of what both paths share, the
+    // MFMA path ~60 us more than that share whatever the size — and beyond 32 Ki rows the select no longer holds a score row in
+    // registers. (The rule it replaces, nq * rows <= 4 M below 64 Ki rows, sent 64 queries x 60 k rows through 16 exact passes.)
+    const int64_t exact_passes = (nq + 3) / 4;
+    const bool small = h.rows <= 32768 && (double)exact_passes * ((double)h.rows * 1.28e-3 + 10.0) <= 60.0;   // (any size: 600 queries on 1000 rows are 150 passes)
+    p.exact_only = h.force_exact || k > K_FAST_MAX || k == 0 || h.rows < 1 || (small && !h.force_fast);
+    if (p.exact_only) return RDX_OK;
+
+    // The main scan on int8 MFMA (twice the dot products per clock of fp16, half the bytes; DESIGN.md §5 "int8 coarse pass"): the
+    // caller's batch only (not the second pass), in 256-query tiles, at most 8 k-steps of 128 dimensions (|D| < 2^24: exact in fp32).
+    // Automatic (option 2): more than one query tile on a shard of at least 2^20 rows, where the MFMA rate decides the scan's time;
+    // the bootstrap, the second pass and the exact scan stay fp16 / fp32.
+    const bool i8_shape = depth == 0 && nq > 128 && h.dim_pad % 128 == 0 && h.dim_pad <= 1024 && h.force_bn == 0;
+    p.i8 = i8_shape && (h.coarse_i8 == 1 || (h.coarse_i8 == 2 && h.i8_backoff == 0 && nq > 256 && h.rows >= ((int64_t)1 << 20)));
+
+    // queries per workgroup: 64 (tile resident in LDS), 128, 256. 257..384 queries run as three 128-query tiles rather than
+    // one full and one half-empty 256-query tile (measured at 1M x 1024, B = 384: 0.78 vs 0.84 ms; tools/bn_sweep.py)
+    p.bn = nq <= 64 ? 64 : (nq <= 128 ? 128 : ((nq > 256 && nq <= 384 && !p.i8) ? 128 : 256));
+    if (h.force_bn && (nq + h.force_bn - 1) / h.force_bn <= 32) p.bn = h.force_bn;   // developer option: queries per workgroup
+    p.nqt = (int)((nq + p.bn - 1) / p.bn);
+    p.grid = std::max(8, h.n_cu / 8 * 8);
+    const int wpx = p.grid / 8;
+    if (p.nqt > wpx) return fail(RDX_ERR_STATE, "internal: query chunk larger than one scan launch");
+    p.G = wpx / p.nqt;
+    p.n_streams = 8 * p.G;
+    if (p.n_streams > REFINE_STREAMS) return fail(RDX_ERR_STATE, "internal: more streams than the refine kernel gathers");
+    p.n_sets = p.n_streams * SETS_PER_STREAM;
+    p.n_tiles = (h.rows + 255) / 256;
+    if (p.n_tiles * h.ksteps >= ((int64_t)1 << 31)) return fail(RDX_ERR_STATE, "shard too large for one scan launch");
+    // the 64-query tile stays resident in LDS when all its k-step images fit (no DMA, no barrier in the main loop)
+    p.res = p.bn == 64 && (size_t)h.ksteps * 8192 + 512 <= 160 * 1024 - 1024;
+    // bootstrap sample: every div-th tile. More rows sampled = tighter tau = fewer hits; keep the expected hits
+    // per query (~1.3 k rows/sample_rows) around 4000/... of the refine list and the sample >= max(64k, 8192) rows
+    // Bootstrap geometry. 129..256 queries run their main scan as ONE 256-query tile per workgroup, but their bootstrap samples
+    // ~130 tiles: as one tile per workgroup that is half the CUs working through 16 dependent k-steps of 64 KB each (36 us at
+    // c3). As TWO 128-query tiles per sampled tile every CU works, a k-step moves 48 KB and takes 1.4 instead of 2.25 us
+    // (DESIGN.md §10's table): option "half_boot" (default 1).
+    p.bn_b = p.bn;
+    p.nqt_b = p.nqt;
+    int ns_b = p.n_streams;
+    if (h.half_boot && p.bn == 256 && p.nqt == 1) {
+        p.bn_b = 128;
+        p.nqt_b = 2;
+        ns_b = 8 * (wpx / 2);
+    }
+    p.n_sets_b = ns_b * SETS_PER_STREAM;
+    const int64_t want_rows = std::max<int64_t>(64 * (int64_t)k, 8192);
+    int div = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(h.sample_div, h.rows / want_rows), 3000 / std::max(k, 1)));
+    if (depth > 0) div = std::max(1, div / 8);   // second chance: 8x denser sample -> a threshold that sees the cluster
+    // A corpus whose last searches emitted far more candidates than a random corpus would (clustered rows: a query's neighbours are
+    // one document's chunks, and a thin sample holds too few of them to place the threshold among them) gets twice the sample for a
+    // while: +0.25 ms of bootstrap on a 10 M-row scan, against thousands of surplus candidates per query to gather and re-score
+    // (measured, embedding-like corpus at c4: 19.6 -> 16.2 ms per batch; N(0,1) corpus: +1 %, which is why it is not the default).
+    else if (h.dense_sample > 0 && div > 1) div = std::max(1, div / 2);
+    // The int8 pass emits every row whose coarse score is within E_q (~0.6 sigma of a random corpus' scores at d = 1024) of the
+    // threshold: a threshold closer to the corpus' k-th score pays for its sample many times over. Measured on c4 (the refine list
+    // holds 7 168 hits): every 64th block 7 900 hits per query, 573 of 1 024 queries re-run; every 32nd 5 400 / 134; every 16th 2 600 /
+    // 0; every 8th, 2 640 hits, 11.8 ms per batch (iid) and 5 000 hits, 12.4 ms (embedding-like). The factor is measured at d = 1024 only; E_q relative to the score spread depends on d (both
+    // quantisation errors grow like the element spacing, the spread like 1/sqrt(d)), so at other widths it is a choice, not a derivation:
+    // what protects those shapes is the fallback, and automatic choice backs off from int8 when it overflows (adapt_sampling).
+    if (p.i8 && depth == 0) div = std::max(1, div / 8);
+    int64_t n_sched = (p.n_tiles + div - 1) / div;
+    // whole rounds only: the bootstrap takes as long as its busiest stream, so 77 tiles on 64 streams cost two tiles' time for
+    // 1.2 tiles' worth of threshold (a 1.25 M-row shard at B = 1024: 53 -> 27 us of a 2.26 ms search); thin the sample to the
+    // last full round instead, as long as it keeps the rows asked for above
+    if (n_sched > ns_b && n_sched % ns_b != 0) {
+        const int64_t full = n_sched / ns_b * ns_b;
+        const int div2 = (int)((p.n_tiles + full - 1) / full);
+        if ((p.n_tiles + div2 - 1) / div2 * 256 >= want_rows) {
+            div = div2;
+            n_sched = (p.n_tiles + div - 1) / div;
+        }
+    }
+    p.div = div;
+    // The sample as every div-th 32-ROW BLOCK (option "spread_boot", default 1) instead of every div-th 256-row tile: the same number
+    // of rows, eight times finer. Wave w of virtual tile j takes block (8 j + w) * div; the last virtual tile ends inside the corpus.
+    // It replaces the whole-rounds schedule above (n_sched becomes the number of virtual tiles) and applies to every bootstrap that
+    // k_boot does not take, whatever the batch size.
+    p.n_blocks32 = (h.rows + 31) / 32;
+    const int64_t n_virtual = ((p.n_blocks32 - 1) / div + 1) / 8;
+    p.boot_tiles = p.n_tiles;
+    p.boot_span = TILE_ROWS;
+    if (h.spread_boot && n_virtual >= 1) {   // wave w of sampled entry j: block (8 j + w) * div (scan_kernel.hpp ScanParams::wave_off)
+        n_sched = n_virtual;
+        p.boot_wave_off = (int64_t)(div - 1) * h.ksteps * 4096;
+        p.boot_row_off = (div - 1) * 32;
+        p.boot_span = (7 * div + 1) * 32;
+        p.boot_tiles = (n_virtual - 1) * (int64_t)div + 1;   // ceil(n_tiles / div) = n_virtual entries: the last block lies inside the corpus
+    }
+    p.sample_rows = n_sched * 256;
+    p.n_sets_used = (int)std::min<int64_t>(ns_b, n_sched) * SETS_PER_STREAM;
+    // Small launches (<= 64 queries and a sample of at most four 32-row blocks per CU): the split-K bootstrap k_boot — one
+    // 32-row block per workgroup, the k-steps dealt to the waves — instead of a few whole tiles of 16 dependent k-steps on
+    // a few CUs (scan_kernel.hpp K2b). Whole rounds of the CUs when more than one.
+    p.boot_units = std::min<int64_t>(p.n_blocks32, n_sched * 8);
+    if (p.boot_units > h.n_cu) p.boot_units = p.boot_units / h.n_cu * h.n_cu;
+    p.use_boot = h.split_boot && p.bn == BOOT_BN && p.nqt == 1 && p.boot_units <= 4 * (int64_t)h.n_cu;
+    // ... and the split-K main scan k_scan_small when the whole corpus is at most 32 such blocks per CU (scan_kernel.hpp K2c)
+    p.use_small = h.small_scan && p.bn == BOOT_BN && p.nqt == 1 && h.ksteps <= 16 && p.n_streams == p.grid &&
+                  p.n_blocks32 <= 32 * (int64_t)h.n_cu && p.n_blocks32 >= p.grid;
+    if (p.use_boot) {
+        p.sample_rows = p.boot_units * 32;
+        p.boot_sets = (int)p.boot_units * 4;
+        p.n_sets_used = p.boot_sets;
+    }
+    // slots per (query, stream) segment: 8x the expected hits, power of two, [32, 4096]
+    double exp_hits = (1.5 * k * (double)h.rows / (double)std::max<int64_t>(p.sample_rows, 1) + k) / p.n_streams;
+    // int8: the scan emits coarse + E_q >= T, E_q ~ 0.6 sigma of a random corpus' scores at d = 1024 — about 16x what the fp16 pass
+    // would emit from the same sample (measured at 10 M x 1024 with the 8x denser sample above: 2 640 hits per query against 146;
+    // DESIGN.md §5; a measured factor at d = 1024, not derived for other widths)
+    if (p.i8) exp_hits *= 16.0;
+    p.expected_per_query = exp_hits * p.n_streams;
+    // (slots cost address space, not bandwidth: only occupied slots are ever touched)
+    // (nq_pad * n_streams is 65,536 whatever the batch: 1024 slots = 512 MiB, 4096 = 2 GiB of the 288)
+    uint32_t capw = depth > 0 ? 4096 : 1024;
+    while (capw < 4096 && capw < 8.0 * exp_hits) capw *= 2;
+    if (h.cand_cap && depth == 0) capw = (uint32_t)std::min<int64_t>(h.cand_cap, 8191);
+    // the scan addresses candidate slots with 32-bit indices (scan_kernel.hpp emit_block)
+    if ((uint64_t)p.nq_pad * (uint64_t)p.n_streams * capw >= (1ull << 29)) return fail(RDX_ERR_STATE, "internal: candidate segments exceed the 32-bit slot index");
+    p.capw = capw;
+    p.k_sel = speculative_rank(h, k, depth, p.sample_rows);
+    // proven threshold: 2E below the k-th sampled score — plus, when the sample was summed in another order than the main scan
+    // sums (k_boot), twice the fp32 accumulation bound, so that the verification (c_k - 2E >= T, with c_k from the main
+    // scan's sums) cannot fail on a rounding difference between the two orders
+    p.slack = h.two_e() + ((p.use_boot != p.use_small) ? 2.0f * (float)h.dim_pad * 1.1920929e-7f : 0.0f);
+    // The eight XCDs do not finish equal shares at the same time (measured on c4: the last XCD 1.1-1.7 ms after the
+    // first of 16.5, always the same ones). Each XCD therefore gets a contiguous range of the tile schedule sized by
+    // its speed in the previous main scans (from the workgroups' own time stamps, damped) — no coordination
+    // inside the kernel, just a different static split. Large launches only.
+    p.balance = h.xcd_balance && depth == 0 && p.n_tiles >= 1024 && p.grid <= 512;
+    if (p.balance) plan_xcd_split(h, &p);
+    p.stamps = (p.balance || p.prof == 3) && p.grid <= 512;   // (Mailbox::wg_times holds 1024 stamps)
+    // LDS list of the gathered hits: 16x the expected count (heavy-tailed score distributions of structured corpora; a list overflow costs a second pass), at most REFINE_LIST
+    uint32_t list_cap = 1024;
+    while (list_cap < (uint32_t)REFINE_LIST && list_cap < 16.0 * exp_hits * p.n_streams) list_cap *= 2;
+    p.list_cap = std::min<uint32_t>(list_cap, REFINE_LIST);
+    return RDX_OK;
+}
+
+// profile 1: an event behind every kernel; profile 2: events 3 and 4 only, around the dominant kernel(s)
+static void mark(rdx_index* h, const SearchPlan& p, hipStream_t st, int i) {
+    if (p.prof == 1 || (p.prof == 2 && (i == 3 || i == 4))) (void)hipEventRecord(h->ev[i], st);
+}
+
+// K6 (end of search): results of small host calls -> pinned staging, counters (+ workgroup stamps) -> mailbox, counter block
+// re-zeroed, sequence number published. Runs in the last block of the search's last kernel (option fuse_finish, default) or
+// as its own launch behind it.
+static FinishArgs finish_args(const rdx_index* h, const SearchPlan& p, const SearchIO& io, unsigned long long seq) {
+    FinishArgs f = {};
+    f.ctr = h->ctr.as<RefineCounters>();
+    f.mb = h->mbox_dev;
+    f.seq = seq;
+    f.wgt = p.stamps ? h->wgt.as<unsigned long long>() : nullptr;
+    f.n_wgt = p.stamps ? 2 * p.grid : 0;
+    f.s0 = reinterpret_cast<const uint32_t*>(io.row);
+    f.d0 = reinterpret_cast<uint32_t*>(h->pin_out_dev);
+    f.w0 = (int64_t)(p.ride ? p.b_r / 4 : 0);
+    f.s1 = reinterpret_cast<const uint32_t*>(io.score);
+    f.d1 = reinterpret_cast<uint32_t*>(h->pin_out_dev + p.b_r);
+    f.w1 = (int64_t)(p.ride ? p.b_s / 4 : 0);
+    f.s2 = reinterpret_cast<const uint32_t*>(io.count);
+    f.d2 = reinterpret_cast<uint32_t*>(h->pin_out_dev + p.b_r + p.b_s);
+    f.w2 = (int64_t)(p.ride ? p.b_c / 4 : 0);
+    f.out_flags = io.flags;
+    f.may_redo = (!p.exact_only && p.depth == 0) ? 1 : 0;
+    return f;
+}
+
+// the MFMA path of a plan: bootstrap (k_boot or k_scan<EPI_SETMAX>), k_tau, main scan (k_scan_small or k_scan<EPI_EMIT>), k_refine
+static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, hipStream_t st, const FinishArgs& fin) {
+    ScanParams sp = {};
+    sp.shadow = h->shadow;
+    sp.qshadow = h->qshadow.as<_Float16>();
+    sp.ksteps = h->ksteps;
+    sp.rows = h->rows;
+    sp.n_tiles = p.n_tiles;
+    sp.nqt = p.nqt;
+    sp.nq_pad = p.nq_pad;
+    sp.allow = io.allow;
+    sp.setmax = h->setmax.as<float>();
+    sp.n_sets = p.n_sets;
+    sp.tau = h->tau.as<float>();
+    sp.cntw = h->cntw.as<uint32_t>();
+    sp.cand = h->cand.as<uint2>();
+    sp.capw = p.capw;
+    sp.inv_scale2 = std::ldexp(1.0f, -2 * h->scale_log2);
+    sp.shadow_bytes = (int64_t)shadow_bytes(h, h->cap);
+    sp.oob = reinterpret_cast<int*>(h->ctr.as<char>() + offsetof(RefineCounters, oob));
+
+    if (p.use_boot) {
+        BootParams bp = {};
+        bp.shadow = h->shadow;
+        bp.qshadow = h->qshadow.as<_Float16>();
+        bp.ksteps = h->ksteps;
+        bp.rows = h->rows;
+        bp.n_blocks32 = p.n_blocks32;
+        bp.units = (int)p.boot_units;
+        bp.allow = io.allow;
+        bp.setmax = h->setmax.as<float>();
+        bp.n_sets = p.boot_sets;
+        hipLaunchKernelGGL(k_boot, dim3((unsigned)p.boot_units), dim3(512), 0, st, bp);
+        HIP_TRY(hipGetLastError());
+    } else {
+        ScanParams pb = sp;
+        pb.tile_stride = p.div;
+        pb.wave_off = p.boot_wave_off;
+        pb.row_off = p.boot_row_off;
+        pb.span = p.boot_span;
+        pb.n_tiles = p.boot_tiles;
+        pb.nqt = p.nqt_b;
+        pb.n_sets = p.n_sets_b;
+        RDX_TRY(launch_scan_bn<EPI_SETMAX>(h, p.bn_b, p.bn_b == p.bn ? p.res : false, pb, p.grid, st));
+    }
+    mark(h, p, st, 2);
+    if (p.depth == 0 && h->spec_backoff > 0) --h->spec_backoff;
+    hipLaunchKernelGGL(k_tau, dim3(p.nq_pad), dim3(256), 0, st, h->setmax.as<float>(), p.use_boot ? p.boot_sets : p.n_sets_b, p.n_sets_used,
+                       p.k_sel, p.k_sel == p.k ? p.slack * std::ldexp(1.0f, 2 * h->scale_log2) : 0.0f, (int)p.nq, h->tau.as<float>());
+    HIP_TRY(hipGetLastError());
+    if (p.i8) {
+        hipLaunchKernelGGL(k_tau8, dim3((p.nq_pad + 255) / 256), dim3(256), 0, st, h->tau.as<float>(), std::ldexp(1.0f, -2 * h->scale_log2),
+                           h->tq8.as<float>(), h->eq8.as<float>(), h->nq8.as<float>(), h->eps8.as<unsigned int>(), (int)p.nq, p.nq_pad,
+                           h->thr8.as<float>(), h->taus8.as<float>(), h->twoe8.as<float>());
+        HIP_TRY(hipGetLastError());
+    }
+    mark(h, p, st, 3);
+    sp.tile_stride = 1;
+    sp.use_xlo = p.balance ? 1 : 0;
+    sp.bulk_it = p.bulk_it;
+    std::copy(p.xlo, p.xlo + 9, sp.xlo);
+    sp.wgt = p.stamps ? h->wgt.as<unsigned long long>() : nullptr;
+    if (p.use_small) {
+        SmallScanParams ss = {};
+        ss.shadow = h->shadow;
+        ss.qshadow = h->qshadow.as<_Float16>();
+        ss.ksteps = h->ksteps;
+        ss.rows = h->rows;
+        ss.n_blocks32 = p.n_blocks32;
+        ss.allow = io.allow;
+        ss.tau = h->tau.as<float>();
+        ss.cntw = h->cntw.as<uint32_t>();
+        ss.cand = h->cand.as<uint2>();
+        ss.capw = p.capw;
+        ss.inv_scale2 = sp.inv_scale2;
+        ss.wgt = sp.wgt;
+        hipLaunchKernelGGL(k_scan_small, dim3((unsigned)p.grid), dim3(512), 0, st, ss);
+        HIP_TRY(hipGetLastError());
+    } else if (p.i8) {
+        ScanParams s8 = sp;
+        s8.shadow = reinterpret_cast<const _Float16*>(h->c8.p);
+        s8.qshadow = reinterpret_cast<const _Float16*>(h->qshadow8.p);
+        s8.ksteps = h->dim_pad / 128;
+        s8.tau = h->thr8.as<float>();
+        s8.sblk = h->sblk.as<float>();
+        s8.qscale = h->tq8.as<float>();
+        s8.shadow_bytes = (int64_t)h->cap * h->dim_pad;
+        RDX_TRY(launch_scan_i8(h, s8, p.grid, st));
+    } else {
+        RDX_TRY(launch_scan_bn<EPI_EMIT>(h, p.bn, p.res, sp, p.grid, st));
+    }
+    mark(h, p, st, 4);
+    const size_t lds = (size_t)p.list_cap * 8;
+    RDX_TRY(ensure_dynamic_lds(h, (const void*)k_refine, lds));
+    hipLaunchKernelGGL(k_refine, dim3((int)p.nq), dim3(1024), lds, st, h->cand.as<uint2>(), h->cntw.as<uint32_t>(), p.n_streams, p.capw,
+                       p.list_cap, p.k, h->two_e(), p.i8 ? h->twoe8.as<float>() : nullptr, h->qhat.as<float>(), h->mv(), h->dim, h->row_base,
+                       h->row_map, io.score, io.row, io.count, h->exact_list.as<int32_t>(), h->ctr.as<RefineCounters>(),
+                       p.i8 ? h->taus8.as<float>() : h->tau.as<float>(), p.i8 ? 1.0f : sp.inv_scale2, h->refine_pilot, fin);
+    HIP_TRY(hipGetLastError());
+    mark(h, p, st, 5);
+    return RDX_OK;
+}
+
+// int8 pass: bring the corpus copy up to date (blocks from the watermark on; the whole copy after an update, a compaction or a
+// reallocation) and quantise the queries (from qhat, which k_refine re-scores with)
+static int prepare_i8(rdx_index* h, const SearchPlan& p, hipStream_t st) {
+    const int ks8 = h->dim_pad / 128;
+    const void* old_c8 = h->c8.p;
+    const void* old_sb = h->sblk.p;
+    const void* old_eps = h->eps8.p;
+    RDX_TRY(h->c8.ensure((size_t)h->cap * h->dim_pad));
+    RDX_TRY(h->sblk.ensure((size_t)(h->cap / 32) * 4));
+    RDX_TRY(h->eps8.ensure(4));
+    if (h->c8.p != old_c8 || h->sblk.p != old_sb || h->eps8.p != old_eps) h->i8_valid = 0;   // (a reallocation loses the contents)
+    if (h->i8_valid < h->rows) {
+        if (h->i8_valid == 0) HIP_TRY(hipMemsetAsync(h->eps8.p, 0, 4, st));
+        const int64_t b0 = h->i8_valid / 32, nb = (h->rows + 31) / 32 - b0;
+        hipLaunchKernelGGL(k_quant8_corpus, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, h->mv(), h->dim, h->rows, b0, nb,
+                           h->c8.as<int8_t>(), ks8, h->sblk.as<float>(), h->eps8.as<unsigned int>());
+        HIP_TRY(hipGetLastError());
+        h->i8_valid = h->rows;
+    }
+    RDX_TRY(h->qshadow8.ensure((size_t)p.nq_pad * h->dim_pad));
+    for (DevBuf* b : {&h->tq8, &h->eq8, &h->nq8, &h->thr8, &h->taus8, &h->twoe8}) RDX_TRY(b->ensure((size_t)p.nq_pad * 4));
+    hipLaunchKernelGGL(k_quant8_query, dim3((p.nq_pad + 3) / 4), dim3(256), 0, st, h->qhat.as<float>(), p.nq, (int64_t)p.nq_pad, h->dim,
+                       h->qshadow8.as<int8_t>(), ks8, h->tq8.as<float>(), h->eq8.as<float>(), h->nq8.as<float>());
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+// Grow the scratch the plan needs and enqueue it, up to k_finish and the D2H copies of large host results; *seq: the search's number
+static int enqueue_search(rdx_index* h, const SearchPlan& p, const SearchIO& io, const HostOut* ho, hipStream_t st,
+                          unsigned long long* seq) {
+    // K1 on the queries: qhat (fp32, exact re-score) + tiled fp16 copy (scan)
+    RDX_TRY(h->qhat.ensure((size_t)p.nq_pad * h->dim * 4));
+    RDX_TRY(h->qshadow.ensure((size_t)p.nq_pad * h->dim_pad * 2));
+    static_assert(sizeof(RefineCounters) <= 64, "counter block layout: one 64-byte line");
+    RDX_TRY(h->ctr.ensure(sizeof(RefineCounters)));
+    RDX_TRY(h->exact_list.ensure((size_t)p.nq_pad * 4));
+    if (!h->mbox) RDX_TRY(map_pinned(sizeof(Mailbox), (void**)&h->mbox, (void**)&h->mbox_dev));
+    if (p.ride && !h->pin_out) RDX_TRY(map_pinned(PIN_MAX, (void**)&h->pin_out, (void**)&h->pin_out_dev));
+    if (!p.exact_only) {
+        RDX_TRY(h->tau.ensure((size_t)p.nq_pad * 4));
+        RDX_TRY(h->cntw.ensure((size_t)p.nq_pad * p.n_streams * 4));
+        RDX_TRY(h->cand.ensure((size_t)p.nq_pad * p.n_streams * p.capw * 8));
+        RDX_TRY(h->setmax.ensure((size_t)p.nq_pad * std::max(std::max(p.n_sets, p.n_sets_b), p.boot_sets) * 4));
+        if (p.stamps) RDX_TRY(h->wgt.ensure((size_t)p.grid * 16));
+    }
+    if (!h->ctr_ready) {   // zeroed once; afterwards the k_finish of every search leaves it zeroed for the next one
+        HIP_TRY(hipMemsetAsync(h->ctr.p, 0, sizeof(RefineCounters), st));
+        h->ctr_ready = true;
+    }
+    int* d_bad = reinterpret_cast<int*>(h->ctr.as<char>() + offsetof(RefineCounters, bad));
+    *seq = ++h->seq;
+    mark(h, p, st, 0);
+    hipLaunchKernelGGL(k_normalize<true>, dim3((int)((p.nq_pad + 3) / 4)), dim3(256), 0, st, io.queries, (const uint16_t*)nullptr, p.nq, h->dim,
+                       (const int64_t*)nullptr, (int64_t)0, MasterView{h->qhat.as<float>(), nullptr, nullptr}, h->qshadow.as<_Float16>(), h->ksteps, h->scale(),
+                       d_bad, (int64_t)p.nq_pad, p.depth > 0 ? 1 : 0);   // depth 1: the rows ARE normalised queries (gathered from qhat): kept bit for bit
+    HIP_TRY(hipGetLastError());
+    if (p.i8) RDX_TRY(prepare_i8(h, p, st));
+    mark(h, p, st, 1);
+
+    const FinishArgs fin = finish_args(h, p, io, *seq);
+    if (p.exact_only) {
+        for (int i = 2; i <= 3; ++i) mark(h, p, st, i);   // events 3..4 bracket the dominant kernels of this path too (K5a + K5b)
+        if ((size_t)p.nq_pad * 4 > h->iota.bytes) {   // identity query list, uploaded once (grow-only), not per search
+            RDX_TRY(h->iota.ensure((size_t)p.nq_pad * 4));
+            const size_t cnt = h->iota.bytes / 4;
+            std::vector<int32_t> io_list(cnt);
+            for (size_t i = 0; i < cnt; ++i) io_list[i] = (int32_t)i;
+            HIP_TRY(hipMemcpyAsync(h->iota.p, io_list.data(), cnt * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        RDX_TRY(run_exact(h, h->iota.as<int32_t>(), (int)p.nq, p.k, io.allow, io.score, io.row, io.count, st, p.prof == 3,
+                          h->fuse_finish ? &fin : nullptr));
+        for (int i = 4; i <= 5; ++i) mark(h, p, st, i);
+    } else {
+        RDX_TRY(enqueue_scan(h, p, io, st, h->fuse_finish ? fin : FinishArgs{}));
+    }
+    if (!h->fuse_finish) {
+        hipLaunchKernelGGL(k_finish, dim3(1), dim3(1024), 0, st, fin);
+        HIP_TRY(hipGetLastError());
+    }
+    // large host results: plain copies behind the last kernel (read_mailbox synchronises the stream for them)
+    if (p.big_copy) RDX_TRY(copy_results_to_host(*ho, io.score, io.row, io.count, p.nq, p.k, st));
+    return RDX_OK;
+}
+
+// what the host half keeps of the mailbox: a second-chance pass runs a nested search whose k_finish overwrites it
+struct SearchCounts {
+    unsigned long long emitted = 0, rescored = 0;
+    int bad = 0, n_exact = 0;   // n_exact: queries left to the fallback passes (exact path: all of them)
+    float stamp_ms = 0.f;       // profile = 3: first workgroup start -> last workgroup end of the dominant kernel(s)
+};
+
+// f(b) for every workgroup of the main scan that stamped its times (idle ones, wpx % nqt != 0, return before they stamp)
+template <class F>
+static void for_stamped(const SearchPlan& p, F f) {
+    for (int b = 0; b < p.grid; ++b)
+        if ((b >> 3) < p.G * p.nqt) f(b);
+}
+
+static int read_mailbox(rdx_index* h, const PendingSearch& ps, SearchCounts* c) {
+    const SearchPlan& p = ps.plan;
+    if (p.big_copy) HIP_TRY(hipStreamSynchronize(ps.st));   // pageable D2H copies: complete only after a stream synchronise
+    const int rc = wait_word([&] { return __atomic_load_n(&h->mbox->seq, __ATOMIC_ACQUIRE) == ps.seq; }, ps.st);   // the ONE host wait of a search
+    if (rc == 1) return fail(RDX_ERR_HIP, "internal: the search completed without publishing its mailbox");
+    RDX_TRY(rc);
+    const Mailbox& mb = *h->mbox;
+    *c = {mb.emitted, mb.rescored, mb.bad, p.exact_only ? (int)p.nq : mb.n_exact};
+    if (p.prof == 3) {
+        if (p.exact_only) {
+            if (mb.t_last > mb.t_first) c->stamp_ms = (float)((double)(mb.t_last - mb.t_first) * 1e-5);
+        } else if (p.grid <= 512) {
+            unsigned long long t0 = ~0ull, t1 = 0;
+            for_stamped(p, [&](int b) {
+                t0 = std::min(t0, mb.wg_times[2 * b]);
+                t1 = std::max(t1, mb.wg_times[2 * b + 1]);
+            });
+            if (t1 > t0) c->stamp_ms = (float)((double)(t1 - t0) * 1e-5);
+        }
+    }
+    return RDX_OK;
+}
+
+// the sampling state the next searches start from
+static void adapt_sampling(rdx_index* h, const SearchPlan& p, const SearchCounts& c) {
+    if (p.depth != 0) return;
+    // Automatic int8 pass: its band is E_q wide (~0.6 sigma of a random corpus' scores at d = 1024). On rows that crowd around a
+    // query's neighbours (a document's chunks) the hits can overflow the refine list and every such query pays the
+    // fp16 second pass on top; when more than 1 in 64 queries of an int8 search did, the next 256 searches take the fp16 pass, after
+    // which int8 is tried again. (Measured on the embedding-like c4 corpus: 5 000 hits per query, none re-run, int8 12.4 ms against
+    // fp16 16.0 ms per batch — the safeguard is for corpora more crowded than that.)
+    if (p.i8 && h->coarse_i8 == 2 && !p.exact_only) {
+        if ((int64_t)c.n_exact * 64 > p.nq) h->i8_backoff = 256;
+    } else if (h->i8_backoff > 0 && p.nq > 256) {
+        --h->i8_backoff;
+    }
+    if (h->mbox->spec_fail > 0) h->spec_backoff = 64;   // a speculative threshold was too high: provable thresholds for a while
+    // three times the candidates a random corpus would emit: the corpus is clustered — a denser threshold sample for the next searches
+    // (plan_search; re-examined every 256 searches: the denser sample's own emission is what then keeps it on)
+    if (!p.exact_only && p.expected_per_query > 0.0) {
+        const double per_q = (double)c.emitted / (double)std::max<int64_t>(p.nq, 1);
+        if (per_q > (h->dense_sample > 0 ? 1.5 : 3.0) * p.expected_per_query) h->dense_sample = 256;
+        else if (h->dense_sample > 0) --h->dense_sample;
+    }
+}
+
+// the stamps arrived with the counters: re-weight the XCD shares for the next search
+static void reweight_xcds(rdx_index* h, const SearchPlan& p, rdx_search_stats* acc) {
+    const unsigned long long* wt = h->mbox->wg_times;
+    unsigned long long t0 = ~0ull, tx[8] = {}, lo[8];
+    std::fill(lo, lo + 8, ~0ull);
+    for_stamped(p, [&](int b) {
+        t0 = std::min(t0, wt[2 * b]);
+        tx[b & 7] = std::max(tx[b & 7], wt[2 * b + 1]);
+        lo[b & 7] = std::min(lo[b & 7], wt[2 * b + 1]);
+    });
+    double dur[8], mean = 0;
+    for (int x = 0; x < 8; ++x) mean += (dur[x] = (double)(tx[x] - t0)) / 8.0;
+    if (std::getenv("RDX_DEBUG_XCD")) {   // developer (tools/xcd_spread.py): when each XCD's last (first) workgroup ended, ms after the first start
+        std::fprintf(stderr, "xcd end ms:");
+        for (int x = 0; x < 8; ++x) std::fprintf(stderr, " %.3f(%.3f)", dur[x] * 1e-5, (double)(lo[x] - t0) * 1e-5);
+        std::fprintf(stderr, "\n");
+    }
+    acc->xcd_finish_spread_ms = (float)((*std::max_element(dur, dur + 8) - *std::min_element(dur, dur + 8)) * 1e-5);   // 100 MHz ticks
+    acc->xcd_share_min = (float)*std::min_element(h->xw, h->xw + 8);
+    acc->xcd_share_max = (float)*std::max_element(h->xw, h->xw + 8);
+    if (mean > 0) {
+        double sum = 0;
+        for (int x = 0; x < 8; ++x) {
+            h->xw[x] *= std::sqrt(mean / std::max(dur[x], 1.0));   // damped: half the correction per search
+            h->xw[x] = std::min(1.5, std::max(0.6, h->xw[x]));
+            sum += h->xw[x];
+        }
+        for (int x = 0; x < 8; ++x) h->xw[x] *= 8.0 / sum;
+    }
+}
+
+static int search_chunk(rdx_index* h, const SearchIO& io, int64_t nq, int k, hipStream_t st, rdx_search_stats* acc, int depth,
+                        HostOut* ho, bool defer);
+
+// The *n_exact queries whose candidate segments overflowed (listed in exact_list) get their results rewritten: by a second-chance
+// search (caller's batch, option retry) or the exact full scan. *n_exact = the queries the exact scan served in the end.
+static int redo_overflowed(rdx_index* h, const PendingSearch& ps, int* n_exact, rdx_search_stats* acc) {
+    const SearchPlan& p = ps.plan;
+    const hipStream_t st = ps.st;
+    if (p.depth == 0 && h->retry) {
+        // Overflow means "far more rows above the sampled threshold than expected": similar rows stored together
+        // (chunks of one document) that the sparse sample missed. Before paying the exact full scan (one fp32 pass over
+        // the corpus per 4 queries), give exactly these queries one more MFMA pass as a small, HBM-bound batch with a
+        // denser sample and larger segments; what overflows again goes to the exact scan inside that call.
+        const int m = *n_exact, kk = std::max(p.k, 1);
+        RDX_TRY(h->r_list.ensure((size_t)m * 4));
+        RDX_TRY(h->r_q.ensure((size_t)m * h->dim * 4));
+        RDX_TRY(h->r_s.ensure((size_t)m * kk * 4));
+        RDX_TRY(h->r_r.ensure((size_t)m * kk * 8));
+        RDX_TRY(h->r_c.ensure((size_t)m * 4));
+        HIP_TRY(hipMemcpyAsync(h->r_list.p, h->exact_list.p, (size_t)m * 4, hipMemcpyDeviceToDevice, st));
+        // from the index's own normalised copy (qhat), not from the caller's buffer: an asynchronous caller may have reused
+        // that since (include/rdx.h "Lifetimes"); the nested search stores these rows verbatim, so its scores have the same bits
+        hipLaunchKernelGGL(k_gather_queries, dim3((m + 3) / 4), dim3(256), 0, st, h->qhat.as<float>(), h->r_list.as<int32_t>(), m, h->dim,
+                           h->r_q.as<float>());
+        HIP_TRY(hipGetLastError());
+        rdx_search_stats sub = {};
+        const SearchIO sub_io = {h->r_q.as<float>(), ps.io.allow, h->r_s.as<float>(), h->r_r.as<int64_t>(), h->r_c.as<int32_t>(), nullptr};
+        RDX_TRY(search_chunk(h, sub_io, m, p.k, st, &sub, 1, nullptr, false));
+        hipLaunchKernelGGL(k_scatter_topk, dim3(m), dim3(64), 0, st, h->r_s.as<float>(), h->r_r.as<int64_t>(), h->r_c.as<int32_t>(),
+                           h->r_list.as<int32_t>(), m, p.k, ps.io.score, ps.io.row, ps.io.count);
+        HIP_TRY(hipGetLastError());
+        acc->retried_queries += m;
+        acc->emitted += sub.emitted;
+        acc->rescored += sub.rescored;
+        *n_exact = (int)sub.exact_queries;
+    } else {
+        RDX_TRY(run_exact(h, h->exact_list.as<int32_t>(), *n_exact, p.k, ps.io.allow, ps.io.score, ps.io.row, ps.io.count, st));
+    }
+    if (ps.io.flags) HIP_TRY(hipMemsetAsync(ps.io.flags, 0, 16, st));   // the partial is complete now
+    HIP_TRY(hipStreamSynchronize(st));   // rdx_search returns with the stream drained
+    return RDX_OK;
+}
+
+// the search's counters and, with option "profile", its times into the caller's statistics
+static int accumulate_stats(rdx_index* h, const SearchPlan& p, const SearchCounts& c, int n_exact, rdx_search_stats* acc) {
+    if (p.prof == 1) HIP_TRY(hipEventSynchronize(h->ev[6]));
+    acc->sample_rows += p.sample_rows;
+    acc->emitted += (int64_t)c.emitted;
+    acc->rescored += (int64_t)c.rescored;
+    acc->exact_queries += n_exact;
+    acc->path = p.exact_only ? 1 : 0;
+    if (p.prof == 1) {
+        float* const dst[6] = {&acc->ms_normalize, &acc->ms_scan_sample, &acc->ms_tau, &acc->ms_scan_main, &acc->ms_refine, &acc->ms_exact};
+        for (int i = 0; i < 6; ++i) {
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, h->ev[i], h->ev[i + 1]);
+            *dst[i] += ms;
+        }
+        acc->profiled = 1;
+        float tot = 0;
+        (void)hipEventElapsedTime(&tot, h->ev[0], h->ev[6]);
+        acc->ms_total += tot;
+    } else if (p.prof == 2) {
+        float ms = 0;
+        // non-exact path: both completed (the mailbox came after them in the stream). Exact path: ev[4] sits right behind the
+        // kernel whose last block published the mailbox: wait for it (microseconds)
+        if (p.exact_only) (void)hipEventSynchronize(h->ev[4]);
+        (void)hipEventElapsedTime(&ms, h->ev[3], h->ev[4]);
+        acc->profiled = 2;
+        if (p.exact_only) acc->ms_exact += ms;   // exact path: K5a + K5b
+        else acc->ms_scan_main += ms;
+    } else if (p.prof == 3) {
+        acc->profiled = 3;
+        if (p.exact_only) acc->ms_exact += c.stamp_ms;
+        else acc->ms_scan_main += c.stamp_ms;
+    }
+    return RDX_OK;
+}
+
+// the host half of a search (see PendingSearch). *redone (if given) = a fallback pass rewrote results after k_finish.
+static int complete_search(rdx_index* h, const PendingSearch& ps, rdx_search_stats* acc, HostOut* ho, bool* redone) {
+    const SearchPlan& p = ps.plan;
+    if (redone) *redone = false;
+    SearchCounts c;
+    RDX_TRY(read_mailbox(h, ps, &c));
+    adapt_sampling(h, p, c);
+    if (h->mbox->oob) return fail(RDX_ERR_STATE, "internal: the scan computed a corpus address outside the scan copy (RDX_CHECK_BOUNDS build)");
+    if (p.ride) {
+        if (p.k > 0) {
+            std::memcpy(ho->row, h->pin_out, p.b_r);
+            std::memcpy(ho->score, h->pin_out + p.b_r, p.b_s);
+        }
+        std::memcpy(ho->count, h->pin_out + p.b_r + p.b_s, p.b_c);
+    }
+    int n_exact = c.n_exact;
+    if (!p.exact_only) {
+        const bool redo = n_exact > 0 && !c.bad;
+        if (redo && redone) *redone = true;
+        if (n_exact > 0 && ho) ho->stale = true;   // a fallback pass rewrites some of the rows copied above
+        if (p.balance) reweight_xcds(h, p, acc);
+        if (redo) RDX_TRY(redo_overflowed(h, ps, &n_exact, acc));
+        acc->scan_main_launch_rows = h->rows;
+        acc->scan_main_launch_queries = p.nq;
+    }
+    mark(h, p, ps.st, 6);
+    if (c.bad) return fail(RDX_ERR_INVALID, "query embeddings contain NaN or Inf");
+    return accumulate_stats(h, p, c, n_exact, acc);
+}
+
+// One launch of a search (nq <= 4096) at `depth`: plan, enqueue, and complete it unless `defer` (rdx_search_async: left in h->pending).
+// The counter block is zeroed once and afterwards by the k_finish of every search. A search that leaves early (an internal
+// check, allocation failure, launch error) may have skipped its k_finish: the next search zeroes the block itself again.
+static int search_chunk(rdx_index* h, const SearchIO& io, int64_t nq, int k, hipStream_t st, rdx_search_stats* acc, int depth,
+                        HostOut* ho, bool defer) {
+    SearchPlan plan;
+    unsigned long long seq = 0;
+    int rc = plan_search(*h, nq, k, depth, ho != nullptr, &plan);
+    if (rc == RDX_OK && depth == 0) h->coarse_bits = plan.exact_only ? 0 : (plan.i8 ? 8 : 16);
+    if (rc == RDX_OK) rc = enqueue_search(h, plan, io, ho, st, &seq);
+    if (rc == RDX_OK) {
+        if (!plan.exact_only) acc->tau_rank = (float)plan.k_sel;
+        const PendingSearch ps = {true, plan, io, st, seq, defer ? *acc : rdx_search_stats{}};
+        if (defer) h->pending = ps;
+        else rc = complete_search(h, ps, acc, ho, nullptr);
+    }
+    if (rc != RDX_OK) h->ctr_ready = false;
+    return rc;
+}
+
+// run the host half of a search left pending by rdx_search_async (call with h->mu held)
+static int finish_pending(rdx_index* h, bool* redone) {
+    if (redone) *redone = false;
+    if (!h->pending.active) return RDX_OK;
+    PendingSearch ps = h->pending;
+    h->pending.active = false;
+    RDX_TRY(set_device(h));
+    h->stats = ps.stats;
+    const int rc = complete_search(h, ps, &h->stats, nullptr, redone);
+    if (rc != RDX_OK) h->ctr_ready = false;   // (see search_chunk)
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// library / lifecycle
+// ------------------------------------------------------------------------------------------------
+extern "C" int rdx_version(void) { return RDX_ABI_VERSION; }
+extern "C" const char* rdx_last_error(void) { return g_err.c_str(); }
+
+extern "C" int rdx_device_count(int* n) {
+    if (!n) return fail(RDX_ERR_INVALID, "rdx_device_count: null pointer");
+    HIP_TRY(hipGetDeviceCount(n));
+    return RDX_OK;
+}
+
+static int check_dim(int dim) {
+    if (dim <= 0 || dim % 4 != 0 || dim > MAX_DIM)
+        return fail(RDX_ERR_INVALID, "dim must be a positive multiple of 4, at most " + std::to_string(MAX_DIM) + " (got " +
+                                         std::to_string(dim) + ")");
+    return RDX_OK;
+}
+
+extern "C" int rdx_index_create(int device, int dim, rdx_index** out) {
+    if (!out) return fail(RDX_ERR_INVALID, "rdx_index_create: null out pointer");
+    RDX_TRY(check_dim(dim));
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev)
+        return fail(RDX_ERR_INVALID, "device " + std::to_string(device) + " out of range (" + std::to_string(ndev) + " visible)");
+    HIP_TRY(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
+        return fail(RDX_ERR_STATE, std::string("librdx is built for gfx950 (MI355X) only; device reports ") + prop.gcnArchName);
+    rdx_index* h = new rdx_index();
+    h->device = device;
+    h->dim = dim;
+    h->dim_pad = (dim + 63) / 64 * 64;
+    h->ksteps = h->dim_pad / 64;
+    h->scale_log2 = (int)std::lround(std::log2(std::sqrt((double)dim)));
+    h->n_cu = prop.multiProcessorCount;
+    hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+        delete h;
+        return fail(RDX_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+    }
+    *out = h;
+    return RDX_OK;
+}
+
+extern "C" int rdx_index_destroy(rdx_index* h) {
+    if (!h) return RDX_OK;
+    (void)hipSetDevice(h->device);
+    if (h->pending.active) (void)hipStreamSynchronize(h->pending.st);   // an abandoned asynchronous search: let its kernels finish
+    (void)hipStreamSynchronize(h->own_stream);
+    free_master(h->master, h->raw16, h->den);
+    if (h->shadow) (void)hipFree(h->shadow);
+    if (h->row_map) (void)hipFree(h->row_map);
+    for (DevBuf* b : {&h->staging, &h->qraw, &h->qhat, &h->qshadow, &h->tau, &h->cntw, &h->cand, &h->setmax, &h->exact_list,
+                      &h->iota, &h->dense, &h->ctr, &h->bad, &h->o_score, &h->o_row, &h->o_count, &h->mask, &h->ids,
+                      &h->r_list, &h->r_q, &h->r_s, &h->r_r, &h->r_c, &h->c8, &h->sblk, &h->eps8, &h->qshadow8, &h->tq8,
+                      &h->eq8, &h->nq8, &h->thr8, &h->taus8, &h->twoe8})
+        b->release();
+    if (h->mbox) (void)hipHostFree(h->mbox);
+    if (h->pin_out) (void)hipHostFree(h->pin_out);
+    if (h->ev_ok)
+        for (auto& e : h->ev) (void)hipEventDestroy(e);
+    (void)hipStreamDestroy(h->own_stream);
+    delete h;
+    return RDX_OK;
+}
+
+extern "C" int rdx_index_dim(const rdx_index* h, int* dim) {
+    if (!h || !dim) return fail(RDX_ERR_INVALID, "rdx_index_dim: null pointer");
+    *dim = h->dim;
+    return RDX_OK;
+}
+
+extern "C" int rdx_index_count(const rdx_index* h, int64_t* rows) {
+    if (!h || !rows) return fail(RDX_ERR_INVALID, "rdx_index_count: null pointer");
+    *rows = h->rows;
+    return RDX_OK;
+}
+
+extern "C" int rdx_index_reserve(rdx_index* h, int64_t rows) {
+    if (!h || rows < 0) return fail(RDX_ERR_INVALID, "rdx_index_reserve: bad argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    RDX_TRY(set_device(h));
+    return grow(h, rows);
+}
+
+extern "C" int rdx_index_set_option(rdx_index* h, const char* name, int64_t value) {
+    if (!h || !name) return fail(RDX_ERR_INVALID, "rdx_index_set_option: null pointer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    RDX_TRY(finish_pending(h, nullptr));   // the host half of an asynchronous search reads the options it was enqueued under
+    const std::string n(name);
+    if (n == "force_exact") h->force_exact = value != 0;
+    else if (n == "force_fast") h->force_fast = value != 0;
+    else if (n == "retry") h->retry = value != 0;
+    else if (n == "fuse_epilogue") h->fuse_epilogue = value != 0;
+    else if (n == "fuse_finish") h->fuse_finish = value != 0;
+    else if (n == "split_boot") h->split_boot = value != 0;
+    else if (n == "small_scan") h->small_scan = value != 0;
+    else if (n == "half_boot") h->half_boot = value != 0;
+    else if (n == "spread_boot") h->spread_boot = value != 0;
+    else if (n == "coarse_i8") {
+        if (value < 0 || value > 2) return fail(RDX_ERR_INVALID, "coarse_i8 must be 0 (never), 1 (whenever the shape allows) or 2 (automatic)");
+        h->coarse_i8 = (int)value;
+        h->i8_backoff = 0;
+    }
+    else if (n == "refine_pilot") {
+        if (value < 0 || value > 64) return fail(RDX_ERR_INVALID, "refine_pilot must be 0 (one band) or 1..64 (pilot of that many times k hits)");
+        h->refine_pilot = (int)value;
+    }
+    else if (n == "spec_tau") {
+        h->spec_tau = value != 0;
+        h->spec_backoff = 0;
+    }
+    else if (n == "force_bn") {
+        if (value != 0 && value != 64 && value != 128 && value != 256) return fail(RDX_ERR_INVALID, "force_bn must be 0 (automatic), 64, 128 or 256");
+        h->force_bn = (int)value;
+    }
+    else if (n == "compact_master") {
+        if (h->rows > 0 || h->cap > 0) return fail(RDX_ERR_STATE, "compact_master can only be chosen while the index is empty");
+        h->compact = value != 0;
+    }
+    else if (n == "xcd_balance") {
+        h->xcd_balance = value != 0;
+        for (double& w : h->xw) w = 1.0;
+    }
+    else if (n == "profile") h->profile = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 3);
+    else if (n == "sample_div") {
+        if (value < 1) return fail(RDX_ERR_INVALID, "sample_div must be >= 1");
+        h->sample_div = (int)std::min<int64_t>(value, 1 << 20);
+    } else if (n == "row_base") {
+        if (value < 0) return fail(RDX_ERR_INVALID, "row_base must be >= 0");
+        h->row_base = value;
+    } else if (n == "cand_cap") {
+        if (value < 0) return fail(RDX_ERR_INVALID, "cand_cap must be 0 (auto) or a positive slot count per (query, stream) segment");
+        h->cand_cap = value;
+    } else
+        return fail(RDX_ERR_INVALID, "unknown option '" + n + "'");
+    return RDX_OK;
+}
+
+extern "C" int rdx_index_xcd_shares(rdx_index* h, double* out8, const double* in8) {
+    if (!h) return fail(RDX_ERR_INVALID, "rdx_index_xcd_shares: null index");
+    std::lock_guard<std::mutex> lk(h->mu);
+    RDX_TRY(finish_pending(h, nullptr));
+    if (in8) {
+        double w[8], sum = 0;
+        for (int x = 0; x < 8; ++x) {
+            if (!(in8[x] > 0.0) || !(in8[x] < 100.0)) return fail(RDX_ERR_INVALID, "rdx_index_xcd_shares: shares must be positive finite numbers");
+            sum += (w[x] = std::min(1.5, std::max(0.6, in8[x])));
+        }
+        for (int x = 0; x < 8; ++x) h->xw[x] = w[x] * 8.0 / sum;
+    }
+    if (out8)
+        for (int x = 0; x < 8; ++x) out8[x] = h->xw[x];
+    return RDX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// ingest
+// ------------------------------------------------------------------------------------------------
+static const int64_t STAGE_ROWS = 32768;
+
+// normalise n rows (host or device, fp32 or bf16) into master/shadow at dst rows (row0.. or dst_ids)
+static int ingest(rdx_index* h, const void* rows, bool is_bf16, int64_t n, int space, int64_t row0, const int64_t* d_dst_ids,
+                  bool verbatim = false) {
+    hipStream_t st = h->own_stream;
+    // the int8 copy: an update may touch any block, an append the last partial one and the new ones
+    h->i8_valid = d_dst_ids ? 0 : std::min<int64_t>(h->i8_valid, row0 / 32 * 32);
+    if (space == RDX_DEVICE) HIP_TRY(hipDeviceSynchronize());   // the caller's producers of `rows` (any stream) are done
+    const size_t esz = is_bf16 ? 2 : 4;
+    RDX_TRY(h->bad.ensure(sizeof(int)));
+    HIP_TRY(hipMemsetAsync(h->bad.p, 0, sizeof(int), st));
+    for (int64_t off = 0; off < n; off += STAGE_ROWS) {
+        const int64_t m = std::min(STAGE_ROWS, n - off);
+        const char* src = reinterpret_cast<const char*>(rows) + (size_t)off * h->dim * esz;
+        if (space == RDX_HOST) {
+            RDX_TRY(h->staging.ensure((size_t)STAGE_ROWS * h->dim * 4));
+            HIP_TRY(hipMemcpyAsync(h->staging.p, src, (size_t)m * h->dim * esz, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipStreamSynchronize(st));   // pageable source: keep the copy ordered with the caller's buffer
+            src = h->staging.as<char>();
+        }
+        const int grid = (int)((m + 3) / 4);
+        hipLaunchKernelGGL(k_normalize<false>, dim3(grid), dim3(256), 0, st, is_bf16 ? nullptr : (const float*)src,
+                           is_bf16 ? (const uint16_t*)src : nullptr, m, h->dim, d_dst_ids ? d_dst_ids + off : nullptr,
+                           row0 + off, h->mv(), h->shadow, h->ksteps, h->scale(), h->bad.as<int>(), (int64_t)0, verbatim ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+        if (space == RDX_HOST) HIP_TRY(hipStreamSynchronize(st));   // staging is reused by the next chunk
+    }
+    int bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, h->bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad) return fail(RDX_ERR_INVALID, "embeddings contain NaN or Inf");
+    return RDX_OK;
+}
+
+static int add_impl(rdx_index* h, const void* rows, bool is_bf16, int64_t n, int space, bool verbatim = false) {
+    if (!h || (n > 0 && !rows) || n < 0) return fail(RDX_ERR_INVALID, "rdx_index_add: bad argument");
+    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    if (n == 0) return RDX_OK;
+    std::lock_guard<std::mutex> lk(h->mu);
+    RDX_TRY(finish_pending(h, nullptr));
+    if (h->compact && (!is_bf16 || verbatim))
+        return fail(RDX_ERR_STATE, "this index keeps a compact master (raw bf16 rows + divisors): rows must arrive through rdx_index_add_bf16");
+    RDX_TRY(set_device(h));
+    RDX_TRY(grow(h, h->rows + n));
+    RDX_TRY(ingest(h, rows, is_bf16, n, space, h->rows, nullptr, verbatim));
+    h->rows += n;
+    return RDX_OK;
+}
+
+extern "C" int rdx_index_add(rdx_index* h, const float* rows, int64_t n, int space) { return add_impl(h, rows, false, n, space); }
+extern "C" int rdx_index_add_bf16(rdx_index* h, const uint16_t* rows, int64_t n, int space) {
+    return add_impl(h, rows, true, n, space);
+}
+extern "C" int rdx_index_add_stored(rdx_index* h, const float* rows, int64_t n, int space) {
+    return add_impl(h, rows, false, n, space, true);
+}
+
+// copy a host or device int64 id list to the device scratch `ids`, validating on the host when possible
+static int stage_ids(rdx_index* h, const int64_t* ids, int64_t n, int space, const int64_t** d_ids) {
+    hipStream_t st = h->own_stream;
+    std::vector<int64_t> tmp;
+    const int64_t* host_ids = ids;
+    if (space == RDX_DEVICE) {
+        HIP_TRY(hipDeviceSynchronize());   // the caller's producers of `ids` (any stream) are done
+        tmp.resize((size_t)n);
+        HIP_TRY(hipMemcpy(tmp.data(), ids, (size_t)n * 8, hipMemcpyDeviceToHost));
+        host_ids = tmp.data();
+    }
+    for (int64_t i = 0; i < n; ++i)
+        if (host_ids[i] < 0 || host_ids[i] >= h->rows)
+            return fail(RDX_ERR_INVALID, "row id " + std::to_string(host_ids[i]) + " out of range [0, " + std::to_string(h->rows) + ")");
+    if (space == RDX_DEVICE) {
+        *d_ids = ids;
+        return RDX_OK;
+    }
+    RDX_TRY(h->ids.ensure((size_t)n * 8));
+    HIP_TRY(hipMemcpyAsync(h->ids.p, ids, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *d_ids = h->ids.as<int64_t>();
+    return RDX_OK;
+}
+
+extern "C" int rdx_index_update(rdx_index* h, const int64_t* row_ids, const float* rows, int64_t n, int space) {
+    if (!h || n < 0 || (n > 0 && (!row_ids || !rows))) return fail(RDX_ERR_INVALID, "rdx_index_update: bad argument");
+    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    if (n == 0) return RDX_OK;
+    std::lock_guard<std::mutex> lk(h->mu);
+    RDX_TRY(finish_pending(h, nullptr));
+    if (h->compact) return fail(RDX_ERR_STATE, "rdx_index_update takes fp32 rows: not available on an index with a compact (bf16) master");
+    RDX_TRY(set_device(h));
+    const int64_t* d_ids = nullptr;
+    RDX_TRY(stage_ids(h, row_ids, n, space, &d_ids));
+    return ingest(h, rows, false, n, space, 0, d_ids);
+}
+
+extern "C" int rdx_index_get(rdx_index* h, const int64_t* row_ids, int64_t n, float* out, int space) {
+    if (!h || n < 0 || (n > 0 && (!row_ids || !out))) return fail(RDX_ERR_INVALID, "rdx_index_get: bad argument");
+    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    if (n == 0) return RDX_OK;
+    std::lock_guard<std::mutex> lk(h->mu);
+    RDX_TRY(finish_pending(h, nullptr));
+    RDX_TRY(set_device(h));
+    hipStream_t st = h->own_stream;
+    const int64_t* d_ids = nullptr;
+    RDX_TRY(stage_ids(h, row_ids, n, space, &d_ids));
+    for (int64_t off = 0; off < n; off += STAGE_ROWS) {
+        const int64_t m = std::min(STAGE_ROWS, n - off);
+        float* dst = out + (size_t)off * h->dim;
+        if (space == RDX_HOST) {
+            RDX_TRY(h->staging.ensure((size_t)STAGE_ROWS * h->dim * 4));
+            dst = h->staging.as<float>();
+        }
+        hipLaunchKernelGGL(k_gather_rows, dim3((int)((m + 3) / 4)), dim3(256), 0, st, h->mv(), d_ids + off, m, h->dim, dst);
+        HIP_TRY(hipGetLastError());
+        if (space == RDX_HOST) {
+            HIP_TRY(hipMemcpyAsync(out + (size_t)off * h->dim, dst, (size_t)m * h->dim * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return RDX_OK;
+}
+
+extern "C" int rdx_index_compact(rdx_index* h, const int64_t* keep, int64_t n_keep) {
+    if (!h || n_keep < 0 || (n_keep > 0 && !keep)) return fail(RDX_ERR_INVALID, "rdx_index_compact: bad argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    RDX_TRY(finish_pending(h, nullptr));
+    RDX_TRY(set_device(h));
+    for (int64_t i = 0; i < n_keep; ++i) {
+        if (keep[i] < 0 || keep[i] >= h->rows) return fail(RDX_ERR_INVALID, "compact: row id out of range");
+        if (i > 0 && keep[i] <= keep[i - 1]) return fail(RDX_ERR_INVALID, "compact: keep list must be strictly ascending");
+    }
+    hipStream_t st = h->own_stream;
+    const int64_t ncap = std::max<int64_t>(256, (n_keep + 255) / 256 * 256);
+    float* nm = nullptr;
+    uint16_t* nr16 = nullptr;
+    double* nd = nullptr;
+    _Float16* ns = nullptr;
+    hipError_t e = alloc_master(h, ncap, &nm, &nr16, &nd);
+    if (e == hipSuccess) e = hipMalloc((void**)&ns, shadow_bytes(h, ncap));
+    if (e != hipSuccess) {
+        free_master(nm, nr16, nd);
+        return fail(RDX_ERR_NOMEM, std::string("compact: ") + hipGetErrorString(e));
+    }
+    HIP_TRY(hipMemsetAsync(ns, 0, shadow_bytes(h, ncap), st));
+    if (n_keep > 0) {
+        RDX_TRY(h->ids.ensure((size_t)n_keep * 8));
+        HIP_TRY(hipMemcpyAsync(h->ids.p, keep, (size_t)n_keep * 8, hipMemcpyHostToDevice, st));
+        const MasterView nv{nm, nr16, nd};
+        if (h->compact)
+            hipLaunchKernelGGL(k_gather_raw, dim3((int)((n_keep + 3) / 4)), dim3(256), 0, st, h->mv(), h->ids.as<int64_t>(), n_keep, h->dim, nv);
+        else
+            hipLaunchKernelGGL(k_gather_rows, dim3((int)((n_keep + 3) / 4)), dim3(256), 0, st, h->mv(), h->ids.as<int64_t>(), n_keep, h->dim, nm);
+        hipLaunchKernelGGL(k_reshadow, dim3((int)((n_keep + 3) / 4)), dim3(256), 0, st, nv, (int64_t)0, n_keep, h->dim, ns,
+                           h->ksteps, h->scale());
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    free_master(h->master, h->raw16, h->den);
+    if (h->shadow) (void)hipFree(h->shadow);
+    if (h->row_map) (void)hipFree(h->row_map);   // rows were renumbered: the caller sets a new id map (or none)
+    h->row_map = nullptr;
+    h->master = nm;
+    h->raw16 = nr16;
+    h->den = nd;
+    h->shadow = ns;
+    h->cap = ncap;
+    h->rows = n_keep;
+    h->i8_valid = 0;
+    return RDX_OK;
+}
+
+extern "C" int rdx_index_set_row_ids(rdx_index* h, int64_t first_row, const int64_t* ids, int64_t n, int space) {
+    if (!h || first_row < 0 || n < 0 || (n > 0 && !ids)) return fail(RDX_ERR_INVALID, "rdx_index_set_row_ids: bad argument");
+    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (first_row + n > h->rows) return fail(RDX_ERR_INVALID, "rdx_index_set_row_ids: rows [first_row, first_row + n) must exist");
+    if (n == 0) return RDX_OK;
+    RDX_TRY(finish_pending(h, nullptr));   // k_refine / k_select_dense of an asynchronous search may still be reading the map
+    RDX_TRY(set_device(h));
+    hipStream_t st = h->own_stream;
+    std::vector<int64_t> tmp;
+    const int64_t* host_ids = ids;
+    if (space == RDX_DEVICE) {
+        HIP_TRY(hipDeviceSynchronize());   // the caller's producer of `ids` (any stream) is done
+        tmp.resize((size_t)n);             // the merge's tie order rests on the map being increasing: checked for device ids too
+        HIP_TRY(hipMemcpy(tmp.data(), ids, (size_t)n * 8, hipMemcpyDeviceToHost));
+        host_ids = tmp.data();
+    }
+    for (int64_t i = 0; i < n; ++i)
+        if (host_ids[i] < 0 || (i > 0 && host_ids[i] <= host_ids[i - 1]))
+            return fail(RDX_ERR_INVALID, "rdx_index_set_row_ids: ids must be non-negative and strictly increasing");
+    if (!h->row_map) {
+        HIP_TRY(hipMalloc((void**)&h->row_map, (size_t)std::max<int64_t>(h->cap, 256) * 8));
+        hipLaunchKernelGGL(k_iota64, dim3((unsigned)((h->cap + 255) / 256)), dim3(256), 0, st, h->row_map, (int64_t)0, h->cap, h->row_base);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(h->row_map + first_row, ids, (size_t)n * 8, space == RDX_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RDX_OK;
+}
+
+// scratch of rdx_l2_normalize, kept per device (the call sits on the embed() path of every query: no hipMalloc/hipFree per call)
+struct NormScratch {
+    std::mutex mu;
+    DevBuf in, out, bad;
+};
+// (never destroyed: a static destructor would call hipFree at process exit, possibly after the HIP runtime is gone)
+static NormScratch* const g_norm = new NormScratch[64];
+
+extern "C" int rdx_l2_normalize(int device, const float* in, int64_t n, int dim, float* out, int space, void* stream) {
+    if (n < 0 || (n > 0 && (!in || !out))) return fail(RDX_ERR_INVALID, "rdx_l2_normalize: bad argument");
+    RDX_TRY(check_dim(dim));
+    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_l2_normalize: device out of range");
+    if (n == 0) return RDX_OK;
+    HIP_TRY(hipSetDevice(device));
+    NormScratch& sc = g_norm[device];
+    std::lock_guard<std::mutex> lk(sc.mu);
+    hipStream_t st = (hipStream_t)stream;
+    const float* d_in = in;
+    float* d_out = out;
+    RDX_TRY(sc.bad.ensure(sizeof(int)));
+    if (space == RDX_HOST) {
+        RDX_TRY(sc.in.ensure((size_t)n * dim * 4));
+        RDX_TRY(sc.out.ensure((size_t)n * dim * 4));
+        HIP_TRY(hipMemcpyAsync(sc.in.p, in, (size_t)n * dim * 4, hipMemcpyHostToDevice, st));
+        d_in = sc.in.as<float>();
+        d_out = sc.out.as<float>();
+    }
+    HIP_TRY(hipMemsetAsync(sc.bad.p, 0, sizeof(int), st));
+    hipLaunchKernelGGL(k_normalize<false>, dim3((int)((n + 3) / 4)), dim3(256), 0, st, d_in, (const uint16_t*)nullptr, n, dim,
+                       (const int64_t*)nullptr, (int64_t)0, MasterView{d_out, nullptr, nullptr}, (_Float16*)nullptr, 0, 1.0f, sc.bad.as<int>());
+    HIP_TRY(hipGetLastError());
+    int b = 0;
+    if (space == RDX_HOST) HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n * dim * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&b, sc.bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // the NaN/Inf verdict is part of the return value
+    if (b) return fail(RDX_ERR_INVALID, "embeddings contain NaN or Inf");
+    return RDX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// search: the entry points, masks, merge and signal
+// ------------------------------------------------------------------------------------------------
+// what rdx_search and rdx_search_async do first (h->mu held): the pending search completes (scratch buffers are shared), the
+// device is selected, the profiling events exist, and the statistics start from the call's shape
+static int begin_search(rdx_index* h, int64_t nq, int k, rdx_search_stats* s) {
+    RDX_TRY(finish_pending(h, nullptr));
+    RDX_TRY(set_device(h));
+    if (h->profile && !h->ev_ok) {
+        for (auto& e : h->ev) HIP_TRY(hipEventCreate(&e));
+        h->ev_ok = true;
+    }
+    *s = {};
+    s->nq = nq;
+    s->k = k;
+    s->rows = h->rows;
+    return RDX_OK;
+}
+
+static int check_mask(const rdx_index* h, const rdx_mask* mask, const char* who) {
+    if (mask && (mask->device != h->device || mask->rows != h->rows))
+        return fail(RDX_ERR_STATE, std::string(who) + ": the mask was made for " + std::to_string(mask->rows) + " rows on device " +
+                                       std::to_string(mask->device) + ", the index now holds " + std::to_string(h->rows) +
+                                       " (a mask does not outlive a write to the index)");
+    return RDX_OK;
+}
+
+// allow_resident: allow_bits is already device memory whatever `space` says (a resident rdx_mask)
+static int search_impl(rdx_index* h, const float* queries, int64_t nq, int k, const uint32_t* allow_bits, bool allow_resident,
+                       float* out_score, int64_t* out_row, int32_t* out_count, int space, void* stream) {
+    if (nq < 0 || k < 0) return fail(RDX_ERR_INVALID, "rdx_search: nq and k must be >= 0");
+    if (k > SELECT_MAX_K) return fail(RDX_ERR_INVALID, "rdx_search: k larger than " + std::to_string(SELECT_MAX_K) + " is not supported");
+    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    if (nq == 0) return RDX_OK;
+    if (!queries || !out_count || (k > 0 && (!out_score || !out_row))) return fail(RDX_ERR_INVALID, "rdx_search: null pointer");
+    rdx_search_stats s;
+    RDX_TRY(begin_search(h, nq, k, &s));
+    // device pointers: the caller's stream as given (NULL = the default stream the caller produced its inputs on)
+    hipStream_t st = (space == RDX_DEVICE || stream) ? (hipStream_t)stream : h->own_stream;
+
+    const uint32_t* d_allow = allow_bits;
+    const size_t mask_words = (size_t)((h->rows + 31) / 32);
+    if (allow_bits && space == RDX_HOST && !allow_resident && mask_words > 0) {
+        // pad to whole 256-row tiles so the scan may read the word of any block it touches
+        const size_t pad_words = (size_t)((h->rows + 255) / 256 * 8);
+        RDX_TRY(h->mask.ensure(pad_words * 4));
+        HIP_TRY(hipMemsetAsync(h->mask.p, 0, pad_words * 4, st));
+        HIP_TRY(hipMemcpyAsync(h->mask.p, allow_bits, mask_words * 4, hipMemcpyHostToDevice, st));
+        d_allow = h->mask.as<uint32_t>();
+    }
+    const int64_t CHUNK = 4096;   // queries per pipeline pass (<= 256 * WGs per XCD)
+    const int kk = std::max(k, 1);
+    for (int64_t q0 = 0; q0 < nq; q0 += CHUNK) {
+        const int64_t m = std::min(CHUNK, nq - q0);
+        SearchIO io = {queries + (size_t)q0 * h->dim, d_allow, out_score ? out_score + (size_t)q0 * k : nullptr,
+                       out_row ? out_row + (size_t)q0 * k : nullptr, out_count + q0, nullptr};
+        HostOut ho = {io.score, io.row, io.count, false};
+        if (space == RDX_HOST) {
+            RDX_TRY(h->qraw.ensure((size_t)m * h->dim * 4));
+            RDX_TRY(h->o_score.ensure((size_t)m * kk * 4));
+            RDX_TRY(h->o_row.ensure((size_t)m * kk * 8));
+            RDX_TRY(h->o_count.ensure((size_t)m * 4));
+            HIP_TRY(hipMemcpyAsync(h->qraw.p, io.queries, (size_t)m * h->dim * 4, hipMemcpyHostToDevice, st));
+            io.queries = h->qraw.as<float>();
+            io.score = h->o_score.as<float>();
+            io.row = h->o_row.as<int64_t>();
+            io.count = h->o_count.as<int32_t>();
+        }
+        RDX_TRY(search_chunk(h, io, m, k, st, &s, 0, space == RDX_HOST ? &ho : nullptr, false));
+        if (space == RDX_HOST && ho.stale) {
+            RDX_TRY(copy_results_to_host(ho, io.score, io.row, io.count, m, k, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+    }
+    h->stats = s;
+    return RDX_OK;
+}
+
+extern "C" int rdx_search(rdx_index* h, const float* queries, int64_t nq, int k, const uint32_t* allow_bits, float* out_score,
+                          int64_t* out_row, int32_t* out_count, int space, void* stream) {
+    if (!h) return fail(RDX_ERR_INVALID, "rdx_search: null index");
+    std::lock_guard<std::mutex> lk(h->mu);
+    return search_impl(h, queries, nq, k, allow_bits, false, out_score, out_row, out_count, space, stream);
+}
+
+extern "C" int rdx_search_async(rdx_index* h, const float* queries, int64_t nq, int k, const rdx_mask* mask, float* out_score,
+                                int64_t* out_row, int32_t* out_count, int32_t* out_flags, void* stream) {
+    if (!h) return fail(RDX_ERR_INVALID, "rdx_search_async: null index");
+    if (nq < 1 || nq > 4096 || k < 0 || k > SELECT_MAX_K) return fail(RDX_ERR_INVALID, "rdx_search_async: 1 <= nq <= 4096, 0 <= k <= " + std::to_string(SELECT_MAX_K));
+    if (!queries || !out_count || (k > 0 && (!out_score || !out_row))) return fail(RDX_ERR_INVALID, "rdx_search_async: null pointer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    RDX_TRY(check_mask(h, mask, "rdx_search_async"));
+    rdx_search_stats s;
+    RDX_TRY(begin_search(h, nq, k, &s));
+    const SearchIO io = {queries, mask ? mask->words.as<uint32_t>() : nullptr, out_score, out_row, out_count, out_flags};
+    return search_chunk(h, io, nq, k, (hipStream_t)stream, &s, 0, nullptr, true);
+}
+
+extern "C" int rdx_search_wait(rdx_index* h, int* redone) {
+    if (!h) return fail(RDX_ERR_INVALID, "rdx_search_wait: null index");
+    std::lock_guard<std::mutex> lk(h->mu);
+    bool r = false;
+    const int rc = finish_pending(h, &r);
+    if (redone) *redone = r ? 1 : 0;
+    return rc;
+}
+
+extern "C" int rdx_mask_create(rdx_index* h, const uint32_t* allow_bits, int space, rdx_mask** out) {
+    if (!h || !allow_bits || !out) return fail(RDX_ERR_INVALID, "rdx_mask_create: null pointer");
+    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    std::lock_guard<std::mutex> lk(h->mu);
+    RDX_TRY(finish_pending(h, nullptr));
+    RDX_TRY(set_device(h));
+    rdx_mask* m = new rdx_mask();
+    m->device = h->device;
+    m->rows = h->rows;
+    const size_t words = (size_t)((h->rows + 31) / 32), pad_words = (size_t)((h->rows + 255) / 256 * 8);
+    int rc = m->words.ensure(std::max<size_t>(pad_words, 8) * 4);
+    if (rc != RDX_OK) {
+        delete m;
+        return rc;
+    }
+    hipStream_t st = h->own_stream;
+    hipError_t e = hipMemsetAsync(m->words.p, 0, std::max<size_t>(pad_words, 8) * 4, st);
+    if (e == hipSuccess && words > 0) {
+        if (space == RDX_DEVICE) e = hipDeviceSynchronize();   // the caller's producer of the bits (any stream) is done
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(m->words.p, allow_bits, words * 4, space == RDX_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        delete m;
+        return fail(RDX_ERR_HIP, std::string("rdx_mask_create: ") + hipGetErrorString(e));
+    }
+    *out = m;
+    return RDX_OK;
+}
+
+extern "C" int rdx_mask_destroy(rdx_mask* m) {
+    if (!m) return RDX_OK;
+    (void)hipSetDevice(m->device);
+    delete m;
+    return RDX_OK;
+}
+
+extern "C" int rdx_search_masked(rdx_index* h, const float* queries, int64_t nq, int k, const rdx_mask* mask, float* out_score,
+                                 int64_t* out_row, int32_t* out_count, int space, void* stream) {
+    if (!h) return fail(RDX_ERR_INVALID, "rdx_search_masked: null index");
+    std::lock_guard<std::mutex> lk(h->mu);
+    RDX_TRY(check_mask(h, mask, "rdx_search_masked"));
+    return search_impl(h, queries, nq, k, mask ? mask->words.as<uint32_t>() : nullptr, true, out_score, out_row, out_count, space, stream);
+}
+
+#ifdef RDX_REFINE_STAMPS
+extern "C" int rdx_debug_refine_stamps(unsigned long long* out16) {
+    return hipMemcpyFromSymbol(out16, HIP_SYMBOL(rdx::g_refine_stamps), 16 * sizeof(unsigned long long)) == hipSuccess ? 0 : 2;
+}
+#endif
+#ifdef RDX_SELECT_STAMPS
+extern "C" int rdx_debug_select_stamps(unsigned long long* out16) {
+    return hipMemcpyFromSymbol(out16, HIP_SYMBOL(rdx::g_select_stamps), 16 * sizeof(unsigned long long)) == hipSuccess ? 0 : 2;
+}
+#endif
+
+extern "C" int rdx_search_last_coarse_bits(rdx_index* h, int32_t* bits) {
+    if (!h || !bits) return fail(RDX_ERR_INVALID, "rdx_search_last_coarse_bits: null pointer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    *bits = h->coarse_bits;
+    return RDX_OK;
+}
+
+extern "C" int rdx_search_last_stats(rdx_index* h, rdx_search_stats* out) {
+    if (!h || !out) return fail(RDX_ERR_INVALID, "rdx_search_last_stats: null pointer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    *out = h->stats;
+    return RDX_OK;
+}
+
+extern "C" int rdx_merge_topk(int device, const float* part_score, const int64_t* part_row, const int32_t* part_count, int n_parts,
+                              int64_t nq, int k, float* out_score, int64_t* out_row, int32_t* out_count, int space, void* stream) {
+    if (n_parts < 1 || n_parts > 64 || nq < 0 || k < 0 || k > SELECT_MAX_K) return fail(RDX_ERR_INVALID, "rdx_merge_topk: bad shape");
+    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    if (nq == 0) return RDX_OK;
+    if (!part_count || !out_count || (k > 0 && (!part_score || !part_row || !out_score || !out_row)))
+        return fail(RDX_ERR_INVALID, "rdx_merge_topk: null pointer");
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t np = (size_t)n_parts * nq;
+    const int kk = std::max(k, 1);
+    DevBuf ps, pr, pc, os, orow, oc;
+    const float* d_ps = part_score;
+    const int64_t* d_pr = part_row;
+    const int32_t* d_pc = part_count;
+    float* d_os = out_score;
+    int64_t* d_or = out_row;
+    int32_t* d_oc = out_count;
+    if (space == RDX_HOST) {
+        RDX_TRY(ps.ensure(np * kk * 4));
+        RDX_TRY(pr.ensure(np * kk * 8));
+        RDX_TRY(pc.ensure(np * 4));
+        RDX_TRY(os.ensure((size_t)nq * kk * 4));
+        RDX_TRY(orow.ensure((size_t)nq * kk * 8));
+        RDX_TRY(oc.ensure((size_t)nq * 4));
+        if (k > 0) {
+            HIP_TRY(hipMemcpyAsync(ps.p, part_score, np * k * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(pr.p, part_row, np * k * 8, hipMemcpyHostToDevice, st));
+        }
+        HIP_TRY(hipMemcpyAsync(pc.p, part_count, np * 4, hipMemcpyHostToDevice, st));
+        d_ps = ps.as<float>();
+        d_pr = pr.as<int64_t>();
+        d_pc = pc.as<int32_t>();
+        d_os = os.as<float>();
+        d_or = orow.as<int64_t>();
+        d_oc = oc.as<int32_t>();
+    }
+    DevBuf t_s[2], t_r[2], t_c[2];   // the fold's intermediate lists (large k only)
+    if ((int64_t)n_parts * k <= MERGE_MAX) {
+        hipLaunchKernelGGL(k_merge, dim3((int)nq), dim3(256), 0, st, d_ps, d_pr, d_pc, (int64_t)nq * k, (int64_t)nq * k, (int64_t)nq, n_parts, nq, k,
+                           d_os, d_or, d_oc);
+        HIP_TRY(hipGetLastError());
+    } else {
+        // more candidates per query than k_merge ranks in LDS (several shards at k > 2048 / n_parts): fold the parts pairwise
+        const size_t nk = (size_t)nq * k;
+        for (int j = 0; j < 2 && n_parts > 2; ++j) {
+            RDX_TRY(t_s[j].ensure(nk * 4));
+            RDX_TRY(t_r[j].ensure(nk * 8));
+            RDX_TRY(t_c[j].ensure((size_t)nq * 4));
+        }
+        const float* a_s = d_ps;
+        const int64_t* a_r = d_pr;
+        const int32_t* a_c = d_pc;
+        for (int p = 1; p < n_parts; ++p) {
+            const bool last = p == n_parts - 1;
+            float* o_s = last ? d_os : t_s[p & 1].as<float>();
+            int64_t* o_r = last ? d_or : t_r[p & 1].as<int64_t>();
+            int32_t* o_c = last ? d_oc : t_c[p & 1].as<int32_t>();
+            hipLaunchKernelGGL(k_merge_pair, dim3((int)nq), dim3(256), 0, st, a_s, a_r, a_c, d_ps + (size_t)p * nk, d_pr + (size_t)p * nk,
+                               d_pc + (size_t)p * nq, k, o_s, o_r, o_c);
+            HIP_TRY(hipGetLastError());
+            a_s = o_s;
+            a_r = o_r;
+            a_c = o_c;
+        }
+        if (space == RDX_DEVICE && n_parts > 2) HIP_TRY(hipStreamSynchronize(st));   // the intermediates are freed on return
+    }
+    if (space == RDX_HOST) {
+        RDX_TRY(copy_results_to_host(HostOut{out_score, out_row, out_count, false}, d_os, d_or, d_oc, nq, k, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (DevBuf* b : {&ps, &pr, &pc, &os, &orow, &oc}) b->release();
+    }
+    return RDX_OK;
+}
+
+extern "C" int rdx_signal_create(int device, rdx_signal** out) {
+    if (!out) return fail(RDX_ERR_INVALID, "rdx_signal_create: null out pointer");
+    HIP_TRY(hipSetDevice(device));
+    void *p = nullptr, *d = nullptr;
+    RDX_TRY(map_pinned(64, &p, &d));
+    rdx_signal* s = new rdx_signal();
+    s->device = device;
+    s->host = reinterpret_cast<unsigned long long*>(p);
+    s->dev = reinterpret_cast<unsigned long long*>(d);
+    *out = s;
+    return RDX_OK;
+}
+
+extern "C" int rdx_signal_destroy(rdx_signal* s) {
+    if (!s) return RDX_OK;
+    (void)hipSetDevice(s->device);
+    if (s->host) (void)hipHostFree(s->host);
+    delete s;
+    return RDX_OK;
+}
+
+extern "C" int rdx_signal_wait(rdx_signal* s, void* stream, int32_t* value) {
+    if (!s || !value) return fail(RDX_ERR_INVALID, "rdx_signal_wait: null pointer");
+    if (s->seq == 0) return fail(RDX_ERR_STATE, "rdx_signal_wait: no merge has been given this signal");
+    HIP_TRY(hipSetDevice(s->device));
+    unsigned long long w = 0;
+    const int rc = wait_word([&] { return ((w = __atomic_load_n(s->host, __ATOMIC_ACQUIRE)) >> 1) == s->seq; }, (hipStream_t)stream);
+    if (rc == 1) return fail(RDX_ERR_HIP, "internal: the merge completed without publishing its signal");
+    if (rc != 0) return rc;
+    *value = (int32_t)(w & 1ull);
+    return RDX_OK;
+}
+
+// the packed layout one rank contributes to the all-gather: rows i64[nq][k] | scores f32[nq][k] | counts i32[nq] | flags i32[4]
+extern "C" int rdx_merge_topk_packed(int device, const void* packed, int64_t part_stride, int n_parts, int64_t nq, int k,
+                                     float* out_score, int64_t* out_row, int32_t* out_count, rdx_signal* sig, void* stream) {
+    if (n_parts < 1 || n_parts > 64 || nq < 0 || k < 1) return fail(RDX_ERR_INVALID, "rdx_merge_topk_packed: bad shape");
+    if ((int64_t)n_parts * k > MERGE_MAX) return fail(RDX_ERR_INVALID, "rdx_merge_topk_packed: n_parts * k exceeds " + std::to_string(MERGE_MAX));
+    const int64_t flags_off = nq * k * 12 + nq * 4;
+    if (part_stride % 16 != 0 || part_stride < flags_off + 4 * RDX_PACKED_FLAGS)
+        return fail(RDX_ERR_INVALID, "rdx_merge_topk_packed: part_stride must be a multiple of 16 covering one packed partial (rows | scores | counts | flags)");
+    if (sig && sig->device != device) return fail(RDX_ERR_INVALID, "rdx_merge_topk_packed: the signal belongs to another device");
+    if (nq == 0) {
+        if (sig) return fail(RDX_ERR_INVALID, "rdx_merge_topk_packed: a signal needs nq >= 1");
+        return RDX_OK;
+    }
+    if (!packed || !out_score || !out_row || !out_count) return fail(RDX_ERR_INVALID, "rdx_merge_topk_packed: null pointer");
+    HIP_TRY(hipSetDevice(device));
+    const char* b = reinterpret_cast<const char*>(packed);
+    const unsigned long long seq = sig ? ++sig->seq : 0;
+    hipLaunchKernelGGL(k_merge, dim3((int)nq), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float*>(b + nq * k * 8),
+                       reinterpret_cast<const int64_t*>(b), reinterpret_cast<const int32_t*>(b + nq * k * 12), part_stride / 4,
+                       part_stride / 8, part_stride / 4, n_parts, nq, k, out_score, out_row, out_count,
+                       reinterpret_cast<const int32_t*>(b + flags_off), part_stride / 4, sig ? sig->dev : (unsigned long long*)nullptr, seq);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}

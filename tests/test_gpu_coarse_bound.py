@@ -1,5 +1,5 @@
 """The fp16 coarse scan against its model (tests/coarse_model.py) at the error bound E, through every scan variant the launch plan
-(rdx_api.hip plan_search) can choose. Each query of a batch gets an instance of its own — a ladder of probe rows around its refine
+(rdx_index.hip plan_search) can choose. Each query of a batch gets an instance of its own — a ladder of probe rows around its refine
 band edge t2 = c_k - 2E (dyadic: the kernel's coarse scores are the model's to the bit; aligned: the anchor sits 0.78 E above or
 below its exact score), a split pair (coarse(B) - coarse(A) > E, exact(A) > exact(B)) or a subnormal ladder — on its own columns
 or sign pattern; the rest of the corpus lies on other columns (coarse score exactly 0).
@@ -42,7 +42,7 @@ def eng():
 
 def _n_cu():
     import torch
-    return torch.cuda.get_device_properties(0).multi_processor_count    # what rdx_index_create reads (rdx_api.hip h->n_cu)
+    return torch.cuda.get_device_properties(0).multi_processor_count    # what rdx_index_create reads (rdx_index.hip h->n_cu)
 
 
 def _plan(rows, dim, nq, k, opts, n_cu):

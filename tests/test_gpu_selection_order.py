@@ -120,7 +120,7 @@ def test_signed_zeros_behind_the_mfma_scan(eng, oracle, plateau, B):
 @pytest.mark.parametrize("pilot", [0, 4])
 def test_signed_zeros_behind_the_int8_scan(eng, oracle, pilot):
     """the 1 500-zero landscape at B = 300 on the int8 scan, one band (refine_pilot 0) and two rounds (4). d = 128, not 64: the
-    int8 scan's shape gate wants the padded dimension to be a multiple of 128 (rdx_api.hip, i8_shape)."""
+    int8 scan's shape gate wants the padded dimension to be a multiple of 128 (rdx_index.hip, i8_shape)."""
     corpus, q8, facts = SL.mfma_zeros(oracle, 40_000, 1500, nq=8, d=128)
     for f in facts.at(10):
         assert f["kth"] == 0.0 and f["n_gt"] == 4 and f["plateau"] == 1500 and f["key_order_differs"], f

@@ -1,11 +1,11 @@
 """Developer A/B of compile-time variants: python tools/ab_lib.py build NAME "-DFOO=1 ..." ; python tools/ab_lib.py run NAME|base [rows]"""
-import os, subprocess, sys
+import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 def path(name): return os.path.join(ROOT, "tools", f"librdx_{name}.so")
 if sys.argv[1] == "build":
-    subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", *sys.argv[3].split(),
-                           os.path.join(ROOT, "rag_dpo_amd", "csrc", "rdx_api.hip"), "-o", path(sys.argv[2])]); sys.exit(0)
+    from rag_dpo_amd.build import build_lib
+    build_lib(extra_flags=tuple(sys.argv[3].split()), out=path(sys.argv[2])); sys.exit(0)
 which = sys.argv[2]
 from rag_dpo_amd import _lib
 if which != "base":

@@ -1,13 +1,13 @@
 """Compare two gfx950 device listings kernel by kernel: did a source change alter the code of any kernel both builds share?
 
-Make each listing and its resource remarks with
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S rag_dpo_amd/csrc/rdx_api.hip -o X.s \\
-          -Rpass-analysis=kernel-resource-usage 2> X.remarks
-then run  python tools/compare_listings.py OLD.s OLD.remarks NEW.s NEW.remarks
+Make a listing and its resource remarks for every translation unit U of rag_dpo_amd/csrc/*.hip with
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S rag_dpo_amd/csrc/U.hip -o U.s \\
+          -Rpass-analysis=kernel-resource-usage 2> U.remarks
+concatenate the units' listings into X.s and their remarks into X.remarks (no kernel is in two units), then run  python tools/compare_listings.py OLD.s OLD.remarks NEW.s NEW.remarks
 
-Kernels are matched by symbol. A k_scan instantiation of the OLD listing with the seven template arguments
-<BN, EPI, MASK, RES, SIBT, NTT, FUSED> of the scan before the sibling lock-step was removed is matched through SIBT = false
-to the six-argument symbol; SIBT = true instantiations have no counterpart and are listed as removed.
+Kernels are matched by symbol. A k_scan instantiation of the OLD listing that the NEW one does not have, with the seven template
+arguments <BN, EPI, MASK, RES, SIBT, NTT, FUSED> of the scan before the sibling lock-step was removed, is matched through
+SIBT = false to the six-argument symbol; SIBT = true instantiations have no counterpart and are listed as removed.
 
 For every matched pair it compares
   * the compiler's resource remarks (SGPRs, VGPRs, AGPRs, scratch, occupancy, LDS, spills) and the .amdhsa_* descriptor
@@ -59,7 +59,7 @@ def parse_listing(text: str) -> dict:
             kern = m.group(1)
             continue
         m = re.match(r"^\s*(\.amdhsa_\S+)\s+(\S+)", line)
-        if m and kern in out:
+        if m and kern in out and m.group(1) != ".amdhsa_code_object_version":   # (a directive of the file, at the head of every unit's listing)
             out[kern]["desc"][m.group(1)] = m.group(2)
             continue
         if line.strip() == ".end_amdhsa_kernel":
@@ -96,7 +96,7 @@ def main(old_s, old_r, new_s, new_r) -> int:
     ok = True
     matched, removed = [], []
     for sym in old:
-        n = new_name(sym)
+        n = sym if sym in new else new_name(sym)
         if n is None or n not in new:
             removed.append(sym)
         else:
