@@ -7,8 +7,9 @@ import numpy as np
 import pytest
 
 import test_i8_refine_model as RM
+from i8_model import coarse_model as _model
 from rag_dpo_amd import synth
-from test_i8_bound_model import F32, quant_query
+from test_i8_bound_model import F32
 
 pytestmark = pytest.mark.gpu
 
@@ -167,35 +168,6 @@ def test_failed_verification_falls_back(eng, oracle):
     st = _check(oracle, ix, corpus, q, k, fallback_ok=True)
     assert st["tau_rank"] < k and st["retried_queries"] >= 3, st
     ix.close()
-
-
-def _model(oracle, corpus, q):
-    """the int8 coarse scores of every (row, query) as k_quant8_corpus / k_quant8_query / k_scan<I8> compute them — the rows and
-    queries normalised by the C oracle (the bits the library holds), block scales and (float)D s_b t_q in float32 — and E_q"""
-    y = oracle.normalize_rows(corpus)
-    qh = oracle.normalize_rows(q)
-    n, d = y.shape
-    assert n % 32 == 0
-    yb = y.reshape(n // 32, 32, d)
-    mx = np.abs(yb).max(axis=(1, 2)).astype(F32)
-    s = (mx / F32(127)).astype(F32)
-    inv = (F32(1) / s).astype(F32)
-    c8 = np.clip(np.rint((yb * inv[:, None, None]).astype(F32)), -127, 127)
-    err = yb.astype(np.float64) - s.astype(np.float64)[:, None, None] * c8
-    eps = np.sqrt((err * err).sum(axis=2).max(axis=1)) * (1 + 1e-12)
-    eps32 = eps.astype(F32)
-    eps32 = np.where(eps32.astype(np.float64) < eps, np.nextafter(eps32, F32(np.inf)), eps32)
-    eps_max = eps32.max()
-    c8 = c8.reshape(n, d)
-    s_row = np.repeat(s, 32)
-    coarse = np.empty((q.shape[0], n), F32)
-    Eq = np.empty(q.shape[0], F32)
-    for i, v in enumerate(qh):
-        t, q8, e, nn = quant_query(v)
-        D = c8 @ q8.astype(np.float64)                   # |D| < 2^24: exact in float64 and in float32
-        coarse[i] = ((D.astype(F32) * s_row).astype(F32) * t).astype(F32)
-        Eq[i] = RM.e_q(e, nn, eps_max)
-    return y, qh, coarse, Eq
 
 
 @pytest.mark.parametrize("pilot", [1, 4])
