@@ -154,8 +154,8 @@ int rdx_l2_normalize(int device, const float* in, int64_t n, int dim, float* out
                      void* stream);
 
 /* Two fused kernels for the memory-bound parts of the query encoder's forward — what `SentenceTransformer.encode` runs on the
- * GPU in front of that normalisation (reference src/utils/embedding_provider.py:118-147; the GEMMs stay the BLAS library's, driven
- * from rag_dpo_amd/embedding_provider.py). fp16 device pointers, 16-byte aligned; enqueued on `stream`, nothing is synchronised.
+ * GPU in front of that normalisation (reference src/utils/embedding_provider.py:118-147; the projections of a batch are the BLAS library's by default, or
+ * rdx_enc_gemm_f16 below: rag_dpo_amd/embedding_provider.py, gemm="blas" | "rdx"). fp16 device pointers, 16-byte aligned; enqueued on `stream`, nothing is synchronised.
  *
  * rdx_enc_attention_f16: self-attention over PACKED tokens (no padding). qkv [n_tokens][3*heads*head_dim]: per token its query,
  *   key and value rows (heads x head_dim each, head-major); token t belongs to the text whose tokens are
@@ -217,6 +217,23 @@ int rdx_enc_attention_small_f16(int device, const void* qkv, const int32_t* tok_
                                 int head_dim, float scale, void* ctx, void* stream);
 int rdx_enc_layernorm_rows_f16(int device, const void* s, const void* gamma, const void* beta, float eps, int rows,
                                int hidden, float* out, void* stream);
+
+/* The projections of a BATCH (any token count) with the epilogue the encoder applies next, and the LayerNorm that follows the residual
+ * epilogue. fp16 device pointers, 16-byte aligned; `out` overlaps no input; enqueued on `stream`, nothing is synchronised or
+ * allocated (graph-capturable). Arguments are validated before the device is touched.
+ *
+ * rdx_enc_gemm_f16: out[n_tokens][n_out] = epi(x[n_tokens][n_in] w[n_out][n_in]^T + bias[n_out]) on v_mfma_f32_16x16x32_f16, fp32
+ *   accumulation in k order, w in the checkpoint's own layout (no re-tiled copy). n_tokens >= 0 is arbitrary (0: nothing is
+ *   launched); n_out and n_in are multiples of 64. epilogue 0: + bias; 1: erf GELU(+ bias) in fp32 (rdx_enc_gelu_f16's erf);
+ *   2: res[n_tokens][n_out] + (fp16)(+ bias), rdx_enc_stage_f16's residual epilogue (`res` is read for epilogue 2 only). No row at
+ *   or past n_tokens of x, res or out is touched. No split-K, no atomics: the same inputs give the same bits on every call.
+ *   At most 2^24 - 1 tiles (128 x 128 from 256 tiles on, else 64 x 64) per call.
+ * rdx_enc_layernorm_f16: out[r] = LayerNorm(s[r]) * gamma + beta, fp16 in and out: rdx_enc_add_layernorm_f16 (same hidden sizes,
+ *   statistics and rounding) for a sum that already exists; rows <= 4 * (2^24 - 1). */
+int rdx_enc_gemm_f16(int device, const void* x, const void* w, const void* bias, const void* res, int64_t n_tokens,
+                     int n_out, int n_in, int epilogue, void* out, void* stream);
+int rdx_enc_layernorm_f16(int device, const void* s, const void* gamma, const void* beta, float eps, int64_t rows,
+                          int hidden, void* out, void* stream);
 
 /* Cross-encoder reranker --------------------------------------------------------------------- */
 /* The stage the reference runs on every question between retrieval and generation: CrossEncoderReranker.rerank

@@ -81,6 +81,8 @@ SYMBOLS = {
     "rdx_enc_stage_f16": (_i, [_i, _vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "rdx_enc_attention_small_f16": (_i, [_i, _vp, _vp, _i, _i, _i, ctypes.c_float, _vp, _vp]),
     "rdx_enc_layernorm_rows_f16": (_i, [_i, _vp, _vp, _vp, ctypes.c_float, _i, _i, _vp, _vp]),
+    "rdx_enc_gemm_f16": (_i, [_i, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp]),
+    "rdx_enc_layernorm_f16": (_i, [_i, _vp, _vp, _vp, ctypes.c_float, _i64, _i, _vp, _vp]),
     "rdx_rerank_head_f16": (_i, [_i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rdx_rerank_select": (_i, [_i, _vp, _vp, _i, _i, ctypes.c_double, _i, _vp, _vp, _vp, _vp]),
     "rdx_search": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp]),

@@ -168,6 +168,13 @@ def build_lib(force: bool = False, verbose: bool = False, extra_flags=(), out: s
         if slow and not extra_flags:
             raise RuntimeError("k_enc_attention_mfma no longer fits its occupancy target without spilling — refused:\n" +
                                "\n".join(f"  {k}: {v}" for k, v in slow.items()))
+        # the batch GEMM (E14, enc_gemm.hpp) is sized for two or three workgroups per CU; scratch traffic in its k-loop would cost that silently
+        gemm = {k: v for k, v in res.items() if "k_enc_gemm" in k}
+        if len(gemm) < 6 or any("spill_vgprs" not in v or "scratch_bytes" not in v for v in gemm.values()):
+            raise RuntimeError(f"the compiler's resource remarks could not be read for the k_enc_gemm kernels ({len(gemm)} found) — refused")
+        bad = {k: v for k, v in gemm.items() if v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0)}
+        if bad and not extra_flags:
+            raise RuntimeError("k_enc_gemm kernels spill or use scratch — refused:\n" + "\n".join(f"  {k}: {v}" for k, v in bad.items()))
         isa = check_isa(work)
         final_tmp = (out or LIB) + ".tmp"
         shutil.move(tmp, final_tmp)

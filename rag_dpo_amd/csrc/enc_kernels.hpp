@@ -153,8 +153,9 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-// NCH = hidden / 512 (each lane holds NCH chunks of 8 halves); grid ceil(rows / 4), 256 threads = 4 rows
-template <int NCH>
+// NCH = hidden / 512 (each lane holds NCH chunks of 8 halves); grid ceil(rows / 4), 256 threads = 4 rows.
+// ADD = false: LayerNorm(a) alone (rdx_enc_layernorm_f16: the sum already exists, E14's residual epilogue wrote it); b is not read.
+template <int NCH, bool ADD = true>
 __global__ __launch_bounds__(256) void k_enc_add_ln(const _Float16* __restrict__ a, const _Float16* __restrict__ b,
                                                     const _Float16* __restrict__ gamma, const _Float16* __restrict__ beta, float eps,
                                                     int64_t rows, _Float16* __restrict__ out) {
@@ -167,8 +168,8 @@ __global__ __launch_bounds__(256) void k_enc_add_ln(const _Float16* __restrict__
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
         const int64_t off = r * HID + c * 512 + lane * 8;
-        const h8 va = *reinterpret_cast<const h8*>(a + off), vb = *reinterpret_cast<const h8*>(b + off);
-        const h8 vs = va + vb;   // fp16 sum, rounded like the stand-alone add kernel's
+        h8 vs = *reinterpret_cast<const h8*>(a + off);
+        if constexpr (ADD) vs = vs + *reinterpret_cast<const h8*>(b + off);   // fp16 sum, rounded like the stand-alone add kernel's
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             x[c][e] = (float)vs[e];
@@ -451,28 +452,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
 // |gelu| >= 6e-5, within 1e-6 absolutely in the underflowing negative tail (tests/test_embedding_provider.py), NaN -> NaN.
 // HBM-bound target: 4 B per element. grid = min(n / 2048, 2048) workgroups of 256 lanes, 16 B per lane per step.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-__global__ __launch_bounds__(256) void k_enc_gelu(_Float16* __restrict__ x, int64_t n8) {
-    // two elements per vector instruction where the ISA has one (v_pk_fma_f32 / v_pk_mul_f32): the kernel is bound by the vector ALU
+// two elements per vector instruction where the ISA has one (v_pk_fma_f32 / v_pk_mul_f32); fp32 in, fp32 out (the caller rounds).
+// Shared by E13 and by the GELU epilogue of E14 (enc_gemm.hpp).
+__device__ __forceinline__ f32x2 gelu_poly2(f32x2 f) {
     const f32x2 c5 = {1.061405429f, 1.061405429f}, c4 = {-1.453152027f, -1.453152027f}, c3 = {1.421413741f, 1.421413741f},
                 c2 = {-0.284496736f, -0.284496736f}, c1 = {0.254829592f, 0.254829592f}, one = {1.f, 1.f}, pp = {0.3275911f, 0.3275911f};
+    const f32x2 h = 0.5f * f, z = 0.70710678118654752f * f;
+    const f32x2 az = {__builtin_fabsf(z[0]), __builtin_fabsf(z[1])};
+    const f32x2 d = __builtin_elementwise_fma(pp, az, one);
+    const f32x2 t = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+    f32x2 pl = __builtin_elementwise_fma(c5, t, c4);
+    pl = __builtin_elementwise_fma(pl, t, c3);
+    pl = __builtin_elementwise_fma(pl, t, c2);
+    pl = __builtin_elementwise_fma(pl, t, c1);
+    const f32x2 e2 = -1.4426950408889634f * z * z;
+    const f32x2 ex = {__builtin_amdgcn_exp2f(e2[0]), __builtin_amdgcn_exp2f(e2[1])};   // exp2 of -inf = 0
+    const f32x2 q = pl * t * ex;                                                        // erfc(|z|)
+    const f32x2 w = {z[0] >= 0.f ? 2.0f - q[0] : q[0], z[1] >= 0.f ? 2.0f - q[1] : q[1]};   // (NaN: the comparison is false -> NaN * NaN)
+    return h * w;
+}
+
+__global__ __launch_bounds__(256) void k_enc_gelu(_Float16* __restrict__ x, int64_t n8) {
+    // (the kernel is bound by the vector ALU)
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
         half8 v = *reinterpret_cast<const half8*>(x + i * 8);
 #pragma unroll
         for (int j = 0; j < 8; j += 2) {
-            const f32x2 f = {(float)v[j], (float)v[j + 1]};
-            const f32x2 h = 0.5f * f, z = 0.70710678118654752f * f;
-            const f32x2 az = {__builtin_fabsf(z[0]), __builtin_fabsf(z[1])};
-            const f32x2 d = __builtin_elementwise_fma(pp, az, one);
-            const f32x2 t = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
-            f32x2 pl = __builtin_elementwise_fma(c5, t, c4);
-            pl = __builtin_elementwise_fma(pl, t, c3);
-            pl = __builtin_elementwise_fma(pl, t, c2);
-            pl = __builtin_elementwise_fma(pl, t, c1);
-            const f32x2 e2 = -1.4426950408889634f * z * z;
-            const f32x2 ex = {__builtin_amdgcn_exp2f(e2[0]), __builtin_amdgcn_exp2f(e2[1])};   // exp2 of -inf = 0
-            const f32x2 q = pl * t * ex;                                                        // erfc(|z|)
-            const f32x2 w = {z[0] >= 0.f ? 2.0f - q[0] : q[0], z[1] >= 0.f ? 2.0f - q[1] : q[1]};   // (NaN: the comparison is false -> NaN * NaN)
-            const f32x2 r = h * w;
+            const f32x2 r = gelu_poly2(f32x2{(float)v[j], (float)v[j + 1]});
             v[j] = (_Float16)r[0];
             v[j + 1] = (_Float16)r[1];
         }

@@ -6,6 +6,7 @@
 
 #include "enc_kernels.hpp"
 #include "enc_small.hpp"
+#include "enc_gemm.hpp"
 #include "rerank_kernel.hpp"
 
 using namespace rdx;
@@ -99,6 +100,76 @@ extern "C" int rdx_enc_add_layernorm_f16(int device, const void* a, const void* 
         case 3: hipLaunchKernelGGL(k_enc_add_ln<3>, grid, block, 0, st, pa, pb, pg, pbt, eps, rows, (_Float16*)out); break;
         default: hipLaunchKernelGGL(k_enc_add_ln<4>, grid, block, 0, st, pa, pb, pg, pbt, eps, rows, (_Float16*)out); break;
     }
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+constexpr int64_t ENC_MAX_WORKGROUPS = (1 << 24) - 1;   // x 256 threads < 2^32, the most one launch holds
+
+extern "C" int rdx_enc_layernorm_f16(int device, const void* s, const void* gamma, const void* beta, float eps, int64_t rows, int hidden,
+                                     void* out, void* stream) {
+    if (hidden < 512 || hidden > 2048 || hidden % 512) return fail(RDX_ERR_INVALID, "rdx_enc_layernorm_f16: hidden must be 512, 1024, 1536 or 2048");
+    // one workgroup of 256 threads per 4 rows; a launch holds fewer than 2^32 threads
+    if (rows < 0 || (rows + 3) / 4 > ENC_MAX_WORKGROUPS) return fail(RDX_ERR_INVALID, "rdx_enc_layernorm_f16: rows must be in [0, 4 * (2^24 - 1)]");
+    if (rows == 0) return RDX_OK;
+    if (!s || !gamma || !beta || !out) return fail(RDX_ERR_INVALID, "rdx_enc_layernorm_f16: null pointer");
+    if (((uintptr_t)s | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out) & 15)
+        return fail(RDX_ERR_INVALID, "rdx_enc_layernorm_f16: pointers must be 16-byte aligned");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_layernorm_f16: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    const _Float16 *ps = (const _Float16*)s, *pg = (const _Float16*)gamma, *pbt = (const _Float16*)beta;
+    switch (hidden / 512) {   // the add + LayerNorm kernel without its second operand
+        case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_enc_add_ln<1, false>), grid, block, 0, st, ps, ps, pg, pbt, eps, rows, (_Float16*)out); break;
+        case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_enc_add_ln<2, false>), grid, block, 0, st, ps, ps, pg, pbt, eps, rows, (_Float16*)out); break;
+        case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_enc_add_ln<3, false>), grid, block, 0, st, ps, ps, pg, pbt, eps, rows, (_Float16*)out); break;
+        default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_enc_add_ln<4, false>), grid, block, 0, st, ps, ps, pg, pbt, eps, rows, (_Float16*)out); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+// ---- E14: the projections of a batch (enc_gemm.hpp) ---------------------------------------------------------------------------
+template <int BM, int BN>
+static void launch_enc_gemm(EncGemm& a, int epi, hipStream_t st) {
+    a.tiles_m = (int)((a.T + BM - 1) / BM);
+    a.tiles_n = (a.N + BN - 1) / BN;
+    const dim3 grid((unsigned)a.tiles_m * (unsigned)a.tiles_n), block(256);
+    const size_t lds = (size_t)2 * (BM + BN) * 128;   // <= 64 KiB
+    if (epi == ENC_EPI_BIAS) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_enc_gemm<BM, BN, ENC_EPI_BIAS>), grid, block, lds, st, a);
+    else if (epi == ENC_EPI_GELU) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_enc_gemm<BM, BN, ENC_EPI_GELU>), grid, block, lds, st, a);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_enc_gemm<BM, BN, ENC_EPI_RESIDUAL>), grid, block, lds, st, a);
+}
+
+extern "C" int rdx_enc_gemm_f16(int device, const void* x, const void* w, const void* bias, const void* res, int64_t n_tokens, int n_out,
+                                int n_in, int epilogue, void* out, void* stream) {
+    if (n_tokens < 0) return fail(RDX_ERR_INVALID, "rdx_enc_gemm_f16: n_tokens must be >= 0");
+    if (n_out < 64 || n_out % 64 || n_in < 64 || n_in % 64) return fail(RDX_ERR_INVALID, "rdx_enc_gemm_f16: n_out and n_in must be multiples of 64");
+    if (epilogue < 0 || epilogue > 2) return fail(RDX_ERR_INVALID, "rdx_enc_gemm_f16: epilogue is 0 (bias), 1 (bias + erf GELU) or 2 (bias + residual)");
+    if (epilogue == ENC_EPI_RESIDUAL && !res) return fail(RDX_ERR_INVALID, "rdx_enc_gemm_f16: epilogue 2 needs the residual");
+    {   // the tile count of the shape the launcher will choose: one workgroup of 256 threads each, fewer than 2^32 threads per launch
+        const int64_t bm = n_tokens <= ((int64_t)1 << 40) && enc_gemm_large(n_tokens, n_out, n_in) ? 128 : 64;
+        if (n_tokens > ((int64_t)1 << 40) || (n_tokens + bm - 1) / bm * ((n_out + bm - 1) / bm) > ENC_MAX_WORKGROUPS)
+            return fail(RDX_ERR_INVALID, "rdx_enc_gemm_f16: n_tokens x n_out needs more than 2^24 - 1 tiles");
+    }
+    if (n_tokens == 0) return RDX_OK;
+    if (!x || !w || !bias || !out) return fail(RDX_ERR_INVALID, "rdx_enc_gemm_f16: null pointer");
+    if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)bias | (uintptr_t)res | (uintptr_t)out) & 15)
+        return fail(RDX_ERR_INVALID, "rdx_enc_gemm_f16: pointers must be 16-byte aligned");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_gemm_f16: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    EncGemm a;
+    a.x = (const _Float16*)x;
+    a.w = (const _Float16*)w;
+    a.bias = (const _Float16*)bias;
+    a.res = (const _Float16*)res;
+    a.out = (_Float16*)out;
+    a.T = n_tokens;
+    a.N = n_out;
+    a.K = n_in;
+    if (enc_gemm_large(n_tokens, n_out, n_in)) launch_enc_gemm<128, 128>(a, epilogue, (hipStream_t)stream);
+    else launch_enc_gemm<64, 64>(a, epilogue, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return RDX_OK;
 }

@@ -8,7 +8,8 @@ Reference behaviour mirrored (file:line in /root/reference/src/utils/embedding_p
   embed_query, is_available, get_info, __repr__                                     :149-185
 
 What differs underneath: the transformer forward runs over the checkpoint's `transformers.XLMRobertaModel` weights on the packed
-real tokens of a batch (`_PackedEncoder`: GEMMs and GELU are PyTorch-ROCm plumbing; on a GPU in fp16 the attention and the
+real tokens of a batch (`_PackedEncoder`: GEMMs and GELU are PyTorch-ROCm plumbing — or, with gemm="rdx", librdx's MFMA GEMM with fused
+epilogues, `rdx_enc_gemm_f16`; on a GPU in fp16 the attention and the
 add + LayerNorm pairs are librdx kernels, `rdx_enc_attention_f16` / `rdx_enc_add_layernorm_f16`, for a single question the
 projections too, `rdx_enc_linear_small_f16`; batches of up to 8 texts replay their forward as a HIP graph), CLS pooling as BGE-M3's dense
 head, and the L2-normalise is librdx K1 on the device (`rdx_l2_normalize`, the same arithmetic the index uses for corpus rows). Weights and tokenizer are loaded ONLY from a local directory
@@ -148,6 +149,7 @@ class _PackedEncoder:
         self.fused = False
         self.small_linear = False
         self.small_stage = False
+        self.gemm_shapes = False
         p0 = self.layers[0][0]
         if fused and p0.is_cuda and p0.dtype == torch.float16 and self.hidden // self.heads == 64 and self.hidden % 512 == 0 and self.hidden <= 2048:
             from . import _lib
@@ -158,6 +160,7 @@ class _PackedEncoder:
             self.small_linear = self.hidden % 512 == 0 and inter0.weight.shape[0] % 512 == 0   # (rdx_enc_linear_small_f16: inputs a multiple of 512 wide)
             # the five-launches-per-layer forward of one question (rdx_enc_stage_f16 & co., csrc/enc_small.hpp)
             self.small_stage = self.hidden in (512, 1024) and inter0.weight.shape[0] in (512, 1024, 2048, 4096)
+            self.gemm_shapes = inter0.weight.shape[0] % 64 == 0   # (rdx_enc_gemm_f16: feature counts a multiple of 64; hidden is one of 512)
             self.stage_fpb_o = int(os.environ.get("RDX_ENC_FPB_O", self.STAGE_FPB_O))
             self.stage_fpb_f2 = int(os.environ.get("RDX_ENC_FPB_F2", self.STAGE_FPB_F2))
 
@@ -169,6 +172,35 @@ class _PackedEncoder:
     MFMA_MIN_TOKENS = int(os.environ.get("RDX_ENC_MFMA_MIN", str(1 << 40)))
     FUSED_MAX_TOKENS = 64       # up to here the VALU attention kernel (written for questions); beyond, the MFMA kernel (long_attention)
     long_attention = os.environ.get("RDX_ENC_LONG_ATTN", "mfma") != "torch"   # developer: "torch" = scatter -> SDPA -> gather for texts beyond 64 tokens
+
+    # gemm = "rdx": the projections of a batch of at least GEMM_MIN_TOKENS tokens are librdx's MFMA GEMM with the epilogue fused in
+    # (rdx_enc_gemm_f16, csrc/enc_gemm.hpp: QKV + bias, O + residual, FFN-up + GELU, FFN-down + residual) and the add + LayerNorm pairs
+    # shrink to rdx_enc_layernorm_f16: no torch GEMM, GELU or add on the stream. Default "blas"; developer knob RDX_ENC_GEMM.
+    # GEMM_MIN_TOKENS: the per-layer A/B of tools/enc_gemm_bench.py (profiles/enc_gemm/layer_ab.txt) found NO token count
+    # from 257 to 30 720 at which the fused layer is not slower than the BLAS path (new / parent 1.14 - 1.35), so the constant keeps a value
+    # that never triggers: gemm="rdx" runs the kernel only where the developer knob RDX_ENC_GEMM_MIN lowers it.
+    gemm = os.environ.get("RDX_ENC_GEMM", "blas")
+    GEMM_MIN_TOKENS = int(os.environ.get("RDX_ENC_GEMM_MIN", str(1 << 40)))
+
+    def _use_gemm(self, T: int) -> bool:
+        return self.fused and self.gemm_shapes and self.gemm == "rdx" and T >= self.GEMM_MIN_TOKENS and T > self.SMALL_TOKENS
+
+    def _gemm(self, x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, epi: int = 0, res: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """out = epi(x w^T + b): 0 plain, 1 erf GELU, 2 res + half(x w^T + b) — rdx_enc_gemm_f16"""
+        out = torch.empty((x.shape[0], w.shape[0]), dtype=x.dtype, device=x.device)
+        rc = self._lib.rdx_enc_gemm_f16(x.device.index or 0, x.data_ptr(), w.data_ptr(), b.data_ptr(), res.data_ptr() if res is not None else None,
+                                        x.shape[0], w.shape[0], w.shape[1], epi, out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream)
+        if rc:
+            raise RuntimeError("rdx_enc_gemm_f16: " + self._last_error())
+        return out
+
+    def _ln(self, s: torch.Tensor, ln) -> torch.Tensor:
+        out = torch.empty_like(s)
+        rc = self._lib.rdx_enc_layernorm_f16(s.device.index or 0, s.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps),
+                                             s.shape[0], s.shape[1], out.data_ptr(), torch.cuda.current_stream(s.device).cuda_stream)
+        if rc:
+            raise RuntimeError("rdx_enc_layernorm_f16: " + self._last_error())
+        return out
 
     def _add_ln(self, a: torch.Tensor, b: torch.Tensor, ln) -> torch.Tensor:
         out = torch.empty_like(a)
@@ -297,6 +329,16 @@ class _PackedEncoder:
         x = self.ln(self.word(tok) + self.pos(pos) + self.typ.weight[0])                                         # [T][H]
         last = len(self.layers) - 1
         small = self.small_linear and x.shape[0] <= self.SMALL_TOKENS   # one question, a question's sub-queries: weight-streaming projections, GELU in the epilogue
+        if not small and self._use_gemm(int(x.shape[0])):
+            # librdx's GEMM with fused epilogues: QKV, attention, O + residual, LayerNorm, FFN-up + GELU, FFN-down + residual, LayerNorm
+            x = x.contiguous()
+            for li, (wqkv, bqkv, dense_o, ln1, inter, out, ln2) in enumerate(self.layers):
+                ctx = self._attention(self._gemm(x, wqkv, bqkv), tok_first, tok_len, max_len, qb)
+                if li == last:
+                    ctx, x = ctx.index_select(0, first_d), x.index_select(0, first_d)
+                x = self._ln(self._gemm(ctx, dense_o.weight, dense_o.bias, 2, x), ln1)
+                x = self._ln(self._gemm(self._gemm(x, inter.weight, inter.bias, 1), out.weight, out.bias, 2, x), ln2)
+            return x.to(torch.float32)
         for li, (wqkv, bqkv, dense_o, ln1, inter, out, ln2) in enumerate(self.layers):
             qkv = self._linear(x, wqkv, bqkv) if small else F.linear(x, wqkv, bqkv)
             ctx = self._attention(qkv, tok_first, tok_len, max_len, qb)                                           # [T][H], no padding anywhere
@@ -477,14 +519,18 @@ class _PackedEncoder:
             qkv_pad = self._pad_buf[key] = torch.zeros((B * S, 3 * H), dtype=x.dtype, device=x.device)   # (stale padding slots are masked keys / dropped queries)
         last = len(self.layers) - 1
         for li, (wqkv, bqkv, dense_o, ln1, inter, out, ln2) in enumerate(self.layers):
-            qkv_pad.index_copy_(0, flat_d, F.linear(x, wqkv, bqkv))
+            qkv_pad.index_copy_(0, flat_d, self._gemm(x.contiguous(), wqkv, bqkv) if self._use_gemm(T) else F.linear(x, wqkv, bqkv))
             q, k, v = qkv_pad.view(B, S, 3, nh, H // nh).permute(2, 0, 3, 1, 4)                                   # [B][heads][S][head_dim] views
             ctx = F.scaled_dot_product_attention(q, k, v, attn_mask=kmask)
             ctx = ctx.transpose(1, 2).reshape(B * S, H).index_select(0, flat_d)                                   # back to [T][H]
             if li == last:                                   # everything behind the last attention is row-wise: only the CLS rows are needed
                 ctx, x = ctx.index_select(0, first_d), x.index_select(0, first_d)
-            x = ln1(dense_o(ctx) + x)
-            x = ln2(out(F.gelu(inter(x))) + x)
+            if self._use_gemm(T):
+                x = self._ln(self._gemm(ctx, dense_o.weight, dense_o.bias, 2, x.contiguous()), ln1)
+                x = self._ln(self._gemm(self._gemm(x, inter.weight, inter.bias, 1), out.weight, out.bias, 2, x), ln2)
+            else:
+                x = ln1(dense_o(ctx) + x)
+                x = ln2(out(F.gelu(inter(x))) + x)
         return x.to(torch.float32)
 
 
@@ -505,8 +551,28 @@ def _resolve_local_dir(model_name: str, cache_dir: Optional[str]) -> Optional[st
     return None
 
 
-class EmbeddingProvider:
+class _ProviderOptions(type):
+    """Keyword options of THIS build that the reference's constructor does not have. `EmbeddingProvider.__init__` keeps the reference's
+    parameter list exactly (src/utils/embedding_provider.py:44-51; tests/test_embedding_provider.py pins it), so such an option is taken
+    off the call here, validated, and set on the finished object.
+      gemm = "blas" | "rdx": who runs the projections of a batch in the fused forward (`_PackedEncoder.gemm`); default "blas".
+        NOTE: "rdx" takes librdx's GEMM only for batches of at least `_PackedEncoder.GEMM_MIN_TOKENS` tokens, and that constant's
+        measured default NEVER triggers (the kernel is slower than the BLAS library at every token count measured):
+        with the default, gemm="rdx" still runs the BLAS path everywhere. Lower it (`provider._packed.GEMM_MIN_TOKENS = 33` after
+        load(), or RDX_ENC_GEMM_MIN=33 in the environment) to actually run the kernel."""
+
+    def __call__(cls, *args, gemm: Optional[str] = None, **kwargs):
+        if gemm not in (None, "blas", "rdx"):
+            raise ValueError(f"EmbeddingProvider: gemm must be 'blas' or 'rdx', not {gemm!r}")
+        obj = super().__call__(*args, **kwargs)
+        obj.gemm = gemm
+        return obj
+
+
+class EmbeddingProvider(metaclass=_ProviderOptions):
     """Dense BGE-M3 embeddings, L2-normalised (unit rows), d = 1024. Calls are synchronous and thread-safe."""
+
+    gemm: Optional[str] = None             # None: "blas", unless the developer knob RDX_ENC_GEMM says otherwise where the fused forward runs
 
     def __init__(self, model_name: str = DEFAULT_MODEL, device: str = DEFAULT_DEVICE, dtype: torch.dtype = DEFAULT_DTYPE,
                  batch_size: int = DEFAULT_BATCH_SIZE, cache_dir: Optional[str] = None):
@@ -536,6 +602,8 @@ class EmbeddingProvider:
         if self._model is not None:
             return self
         t0 = time.time()
+        if self.gemm == "rdx" and not (str(self.device).startswith("cuda") and self.dtype == torch.float16 and self.packed_forward and self.fused_kernels is not False):
+            raise ValueError(f"EmbeddingProvider: gemm='rdx' needs the fused forward (fp16 on a GPU); this provider runs {self.device}, {self.dtype}")
         from transformers import XLMRobertaConfig, XLMRobertaModel
         if self.model_name.startswith("random-init:"):
             spec = self.model_name.split(":", 1)[1]
@@ -568,8 +636,14 @@ class EmbeddingProvider:
                 fused = self.fused_kernels if self.fused_kernels is not None else (str(self.device).startswith("cuda") and self.dtype == torch.float16)
                 self._packed = _PackedEncoder(self._model, fused=bool(fused))
                 self._packed.graphs = "auto" if self.encoder_graphs is None else bool(self.encoder_graphs)
+                if self.gemm is not None:
+                    self._packed.gemm = self.gemm
             except ValueError as e:                                           # another architecture: the module forward stays
                 logger.info(f"packed forward not available for this model ({e}); using the module forward")
+        if self.gemm == "rdx" and not (self._packed is not None and self._packed.fused and self._packed.gemm_shapes):
+            self._model = self._packed = self._tokenizer = None
+            raise ValueError("EmbeddingProvider: gemm='rdx' needs the fused forward (fp16 on a GPU, 64-wide heads, hidden a multiple of 512 "
+                             f"up to 2048); this provider runs {self.device}, {self.dtype}")
         logger.info(f"{self.model_name} loaded in {time.time() - t0:.1f}s (dims={self._dims})")
         return self
 
