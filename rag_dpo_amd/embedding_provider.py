@@ -8,7 +8,7 @@ Reference behaviour mirrored (file:line in /root/reference/src/utils/embedding_p
   embed_query, is_available, get_info, __repr__                                     :149-185
 
 What differs underneath: the transformer forward runs over the checkpoint's `transformers.XLMRobertaModel` weights on the packed
-real tokens of a batch (`_PackedEncoder`: GEMMs and GELU are PyTorch-ROCm plumbing — or, with gemm="rdx", librdx's MFMA GEMM with fused
+real tokens of a batch (`_PackedEncoder`, rag_dpo_amd/packed_encoder.py: GEMMs and GELU are PyTorch-ROCm plumbing — or, with gemm="rdx", librdx's MFMA GEMM with fused
 epilogues, `rdx_enc_gemm_f16`; on a GPU in fp16 the attention and the
 add + LayerNorm pairs are librdx kernels, `rdx_enc_attention_f16` / `rdx_enc_add_layernorm_f16`, for a single question the
 projections too, `rdx_enc_linear_small_f16`; batches of up to 8 texts replay their forward as a HIP graph), CLS pooling as BGE-M3's dense
@@ -21,13 +21,13 @@ random weights and a hashing tokenizer — shape/perf faithful for benchmarks, N
 from __future__ import annotations
 
 import logging
-import os
 import time
-import zlib
 from typing import List, Optional
 
 import numpy as np
 import torch
+
+from .packed_encoder import _XLMR_LARGE, _HashTokenizer, _PackedEncoder, _resolve_local_dir  # noqa: F401  (tests and tools import them from here too)
 
 logger = logging.getLogger(__name__)
 
@@ -38,517 +38,6 @@ DEFAULT_DTYPE = torch.float16 if torch.cuda.is_available() else torch.float32
 DEFAULT_BATCH_SIZE = 64
 MAX_SEQ_LENGTH = 8192
 TRUNCATE_CHARS = 20000
-
-# XLM-RoBERTa-large = BGE-M3's backbone (24 layers x 1024 hidden x 16 heads, FFN 4096, vocab 250 002)
-_XLMR_LARGE = dict(vocab_size=250002, hidden_size=1024, num_hidden_layers=24, num_attention_heads=16,
-                   intermediate_size=4096, max_position_embeddings=8194, type_vocab_size=1, pad_token_id=1,
-                   bos_token_id=0, eos_token_id=2, layer_norm_eps=1e-5)
-
-
-class _HashTokenizer:
-    """whitespace pieces -> crc32 ids; only for random-init benchmarking (no sentencepiece model offline). The id of a piece is
-    remembered (a real tokenizer's vocabulary lookup is a hash-table hit too) and the padded batch is assembled in numpy: 1024
-    short questions take ~1.5 ms instead of 10 — the encode leg of BASELINE config 5 measures the GPU, not this stand-in."""
-
-    def __init__(self, vocab_size: int, max_len: int = 512):
-        self.vocab_size, self.max_len = vocab_size, max_len
-        self._ids: dict = {}
-
-    def __call__(self, texts: List[str]):
-        cap, n = self.max_len - 2, len(texts)
-        toks = [t.split()[:cap] for t in texts]
-        lens = np.fromiter(map(len, toks), dtype=np.int64, count=n)
-        words = [w for tk in toks for w in tk]
-        ids = self._piece_ids(words)
-        width = int(lens.max()) + 2 if n else 2
-        inp = np.full((n, width), 1, dtype=np.int64)       # <pad> = 1
-        if n:
-            inp[:, 0] = 0                                  # <s>
-            first = np.cumsum(lens) - lens
-            row = np.repeat(np.arange(n), lens)
-            inp[row, np.arange(len(words)) - np.repeat(first, lens) + 1] = np.asarray(ids, dtype=np.int64)
-            inp[np.arange(n), lens + 1] = 2                # </s>
-        att = (np.arange(width)[None, :] < (lens + 2)[:, None]).astype(np.int64)
-        return {"input_ids": torch.from_numpy(inp), "attention_mask": torch.from_numpy(att)}
-
-    def _piece_ids(self, words: List[str]) -> List[int]:
-        ids = list(map(self._ids.get, words))              # vocabulary lookup at C speed; misses (None) are hashed once
-        if None in ids:
-            for j, v in enumerate(ids):
-                if v is None:
-                    w = words[j]
-                    v = 4 + zlib.crc32(w.encode("utf-8")) % (self.vocab_size - 4)
-                    if len(self._ids) < 1_000_000:
-                        self._ids[w] = v
-                    ids[j] = v
-        return ids
-
-    def pairs(self, queries: List[str], texts: List[str], max_length: int):
-        """(query, text) pairs as ONE sequence each, XLM-R's pair layout `<s> q </s></s> d </s>`, cut to max_length tokens
-        longest-first (a token comes off the longer side, off the text on a tie: what the tokenizers library does)."""
-        rows = []
-        budget = max_length - 4
-        for q, d in zip(queries, texts):
-            a, b = q.split(), d.split()
-            la, lb = len(a), len(b)
-            if la + lb > budget:                         # closed form of "drop one from the longer side until it fits"
-                short = min(la, lb)
-                if short * 2 >= budget:
-                    la, lb = (budget + 1) // 2, budget // 2
-                elif la > lb:
-                    la = budget - lb
-                else:
-                    lb = budget - la
-            rows.append((a[:la], b[:lb]))
-        n = len(rows)
-        lens = np.fromiter((len(a) + len(b) + 4 for a, b in rows), dtype=np.int64, count=n)
-        width = int(lens.max()) if n else 4
-        inp = np.full((n, width), 1, dtype=np.int64)       # <pad> = 1
-        for i, (a, b) in enumerate(rows):
-            ids = self._piece_ids(a + b)
-            inp[i, :lens[i]] = [0] + ids[:len(a)] + [2, 2] + ids[len(a):] + [2]
-        att = (np.arange(width)[None, :] < lens[:, None]).astype(np.int64)
-        return {"input_ids": torch.from_numpy(inp), "attention_mask": torch.from_numpy(att)}
-
-
-class _PackedEncoder:
-    """The XLM-R forward over the REAL tokens only (PyTorch-ROCm plumbing, the checkpoint's own modules and weights).
-
-    transformers pads a batch to its longest text and runs every token-wise operation — QKV / output / FFN projections, GELU,
-    residual adds, LayerNorms: all but the attention itself — over the padding too (BASELINE config 5's 1024 questions: 28 672
-    token slots for 20 649 tokens). Here the hidden states stay PACKED ([T_real][hidden]) through the whole stack; only around
-    the attention are Q, K, V scattered into the padded [batch][seq] layout (index_copy) and the context gathered back
-    (index_select). The three projections are ONE GEMM on concatenated weights. About half the launches of the module-by-module
-    forward (the encode of a batch is launch-bound on a busy host) and 28 % fewer GEMM rows for that batch. Same arithmetic per
-    token as `XLMRobertaModel.forward` (post-LayerNorm blocks, erf GELU, position ids = padding_idx + 1 + index in the text,
-    attention over the text's own tokens only): tests/test_embedding_provider.py compares the two. With `fused` (fp16 on a GPU)
-    the attention and the add + LayerNorm pairs are librdx kernels working on the packed layout directly: nothing is ever padded."""
-
-    def __init__(self, model, fused: bool = False):
-        e = model.embeddings
-        self.word, self.pos, self.typ, self.ln, self.pad = e.word_embeddings, e.position_embeddings, e.token_type_embeddings, e.LayerNorm, int(e.padding_idx)
-        cfg = model.config
-        if getattr(cfg, "hidden_act", "gelu") != "gelu" or getattr(cfg, "position_embedding_type", None) not in (None, "absolute"):
-            raise ValueError("packed forward: unsupported configuration")
-        self.heads = int(cfg.num_attention_heads)
-        self.hidden = int(cfg.hidden_size)
-        self.layers = []
-        for L in model.encoder.layer:
-            a = L.attention
-            wqkv = torch.cat([a.self.query.weight, a.self.key.weight, a.self.value.weight], 0).contiguous()
-            bqkv = torch.cat([a.self.query.bias, a.self.key.bias, a.self.value.bias], 0).contiguous()
-            self.layers.append((wqkv, bqkv, a.output.dense, a.output.LayerNorm, L.intermediate.dense, L.output.dense, L.output.LayerNorm))
-        self._pad_buf: dict = {}
-        self._graph: dict = {}
-        self._seen: dict = {}
-        # librdx's two encoder kernels (include/rdx.h: rdx_enc_attention_f16, rdx_enc_add_layernorm_f16) take the place of the
-        # scatter -> padded attention -> transposing copy -> gather chain and of the add + LayerNorm pairs: fp16 on a GPU, 64-wide
-        # heads, hidden a multiple of 512 up to 2048, texts up to FUSED_MAX_TOKENS tokens (the attention kernel is written for
-        # questions: its work per token grows with the text). Anything else runs the torch operations below.
-        self._lib = None
-        self.fused = False
-        self.small_linear = False
-        self.small_stage = False
-        self.gemm_shapes = False
-        p0 = self.layers[0][0]
-        if fused and p0.is_cuda and p0.dtype == torch.float16 and self.hidden // self.heads == 64 and self.hidden % 512 == 0 and self.hidden <= 2048:
-            from . import _lib
-            self._lib = _lib.load()          # raises RdxUnavailable: a GPU provider asked for its kernels and the library is missing
-            self._last_error = _lib.last_error
-            self.fused = True
-            inter0 = self.layers[0][4]
-            self.small_linear = self.hidden % 512 == 0 and inter0.weight.shape[0] % 512 == 0   # (rdx_enc_linear_small_f16: inputs a multiple of 512 wide)
-            # the five-launches-per-layer forward of one question (rdx_enc_stage_f16 & co., csrc/enc_small.hpp)
-            self.small_stage = self.hidden in (512, 1024) and inter0.weight.shape[0] in (512, 1024, 2048, 4096)
-            self.gemm_shapes = inter0.weight.shape[0] % 64 == 0   # (rdx_enc_gemm_f16: feature counts a multiple of 64; hidden is one of 512)
-            self.stage_fpb_o = int(os.environ.get("RDX_ENC_FPB_O", self.STAGE_FPB_O))
-            self.stage_fpb_f2 = int(os.environ.get("RDX_ENC_FPB_F2", self.STAGE_FPB_F2))
-
-    # Question batches (every text <= FUSED_MAX_TOKENS) of at least this many tokens would take the MFMA attention kernel too. Alone it
-    # wins (1024 questions: 39 us per layer against the VALU kernel's 57, profiles/r04/attention_mfma_bench.txt); inside config 5's
-    # pipeline it LOSES: the encode of batch i+1 runs beside the MFMA-bound search of batch i, and a kernel on the vector ALU fills what
-    # the scan leaves idle while a second MFMA kernel queues for the same pipes (encode 16.1 / 16.0 against 15.4 / 15.4 ms, step 31.96 /
-    # 31.76 against 31.15 / 31.24 ms, profiles/r04/c5_n1_bench.json, c5_mfma_attention_for_questions_n1_bench.json). Default: never; developer knob RDX_ENC_MFMA_MIN.
-    MFMA_MIN_TOKENS = int(os.environ.get("RDX_ENC_MFMA_MIN", str(1 << 40)))
-    FUSED_MAX_TOKENS = 64       # up to here the VALU attention kernel (written for questions); beyond, the MFMA kernel (long_attention)
-    long_attention = os.environ.get("RDX_ENC_LONG_ATTN", "mfma") != "torch"   # developer: "torch" = scatter -> SDPA -> gather for texts beyond 64 tokens
-
-    # gemm = "rdx": the projections of a batch of at least GEMM_MIN_TOKENS tokens are librdx's MFMA GEMM with the epilogue fused in
-    # (rdx_enc_gemm_f16, csrc/enc_gemm.hpp: QKV + bias, O + residual, FFN-up + GELU, FFN-down + residual) and the add + LayerNorm pairs
-    # shrink to rdx_enc_layernorm_f16: no torch GEMM, GELU or add on the stream. Default "blas"; developer knob RDX_ENC_GEMM.
-    # GEMM_MIN_TOKENS: the per-layer A/B of tools/enc_gemm_bench.py (profiles/enc_gemm/layer_ab.txt, DESIGN.md §14) found NO token count
-    # from 257 to 30 720 at which the fused layer is not slower than the BLAS path (new / parent 1.14 - 1.35), so the constant keeps a value
-    # that never triggers: gemm="rdx" runs the kernel only where the developer knob RDX_ENC_GEMM_MIN lowers it.
-    gemm = os.environ.get("RDX_ENC_GEMM", "blas")
-    GEMM_MIN_TOKENS = int(os.environ.get("RDX_ENC_GEMM_MIN", str(1 << 40)))
-
-    def _use_gemm(self, T: int) -> bool:
-        return self.fused and self.gemm_shapes and self.gemm == "rdx" and T >= self.GEMM_MIN_TOKENS and T > self.SMALL_TOKENS
-
-    def _gemm(self, x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, epi: int = 0, res: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """out = epi(x w^T + b): 0 plain, 1 erf GELU, 2 res + half(x w^T + b) — rdx_enc_gemm_f16"""
-        out = torch.empty((x.shape[0], w.shape[0]), dtype=x.dtype, device=x.device)
-        rc = self._lib.rdx_enc_gemm_f16(x.device.index or 0, x.data_ptr(), w.data_ptr(), b.data_ptr(), res.data_ptr() if res is not None else None,
-                                        x.shape[0], w.shape[0], w.shape[1], epi, out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream)
-        if rc:
-            raise RuntimeError("rdx_enc_gemm_f16: " + self._last_error())
-        return out
-
-    def _ln(self, s: torch.Tensor, ln) -> torch.Tensor:
-        out = torch.empty_like(s)
-        rc = self._lib.rdx_enc_layernorm_f16(s.device.index or 0, s.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps),
-                                             s.shape[0], s.shape[1], out.data_ptr(), torch.cuda.current_stream(s.device).cuda_stream)
-        if rc:
-            raise RuntimeError("rdx_enc_layernorm_f16: " + self._last_error())
-        return out
-
-    def _add_ln(self, a: torch.Tensor, b: torch.Tensor, ln) -> torch.Tensor:
-        out = torch.empty_like(a)
-        rc = self._lib.rdx_enc_add_layernorm_f16(a.device.index or 0, a.data_ptr(), b.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(),
-                                                 float(ln.eps), a.shape[0], a.shape[1], out.data_ptr(),
-                                                 torch.cuda.current_stream(a.device).cuda_stream)
-        if rc:
-            raise RuntimeError("rdx_enc_add_layernorm_f16: " + self._last_error())
-        return out
-
-    # The FFN's erf GELU is the framework's operation (bit-equal to the module forward). librdx's in-place kernel (E13, rdx_enc_gelu_f16: the
-    # same values to within one fp16 ulp) is 81 against 101 us behind a 148 us FFN1 GEMM at 20 K tokens, and NOTHING in the pipeline: c5
-    # encode 15.71 / 15.73 against 15.87 / 15.80 ms, ingest 3 429 against 3 435 chunks/s (profiles/r04/gelu_inplace_ab.txt) — opt-in only.
-    inplace_gelu = os.environ.get("RDX_ENC_GELU", "torch") == "inplace"
-
-    def _gelu(self, x: torch.Tensor) -> torch.Tensor:
-        """erf GELU of the FFN's first projection: the framework's, or (RDX_ENC_GELU=inplace) librdx's in-place kernel E13"""
-        if not self.inplace_gelu or x.numel() % 8 or not x.is_contiguous():
-            return torch.nn.functional.gelu(x)
-        if self._lib.rdx_enc_gelu_f16(x.device.index or 0, x.data_ptr(), x.numel(), torch.cuda.current_stream(x.device).cuda_stream):
-            raise RuntimeError("rdx_enc_gelu_f16: " + self._last_error())
-        return x
-
-    # up to here the projections are librdx's weight-streaming kernel (rdx_enc_linear_small_f16) instead of the BLAS library's GEMM. Measured
-    # (tools/enc_small_sweep.py, graph replay, XLM-R-large): one question (32 padded tokens) 1.71 -> 1.36 ms; at 64 tokens the two are
-    # equal (1.74), beyond the kernel loses (every 16-feature workgroup re-reads all activations: 128 tokens 2.12 against 1.78 ms)
-    SMALL_TOKENS = 32
-
-    def _linear(self, x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, gelu: bool = False) -> torch.Tensor:
-        out = torch.empty((x.shape[0], w.shape[0]), dtype=x.dtype, device=x.device)
-        rc = self._lib.rdx_enc_linear_small_f16(x.device.index or 0, x.data_ptr(), w.data_ptr(), b.data_ptr(), x.shape[0], w.shape[0], w.shape[1],
-                                                1 if gelu else 0, out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream)
-        if rc:
-            raise RuntimeError("rdx_enc_linear_small_f16: " + self._last_error())
-        return out
-
-    def _attention(self, qkv: torch.Tensor, tok_first: torch.Tensor, tok_len: torch.Tensor, max_len: int, qb=None) -> torch.Tensor:
-        T = qkv.shape[0]
-        ctx = torch.empty((T, self.hidden), dtype=qkv.dtype, device=qkv.device)
-        if qb is not None:                # texts beyond FUSED_MAX_TOKENS (the corpus side): the flash-style MFMA kernel over 64-query blocks
-            rc = self._lib.rdx_enc_attention_mfma_f16(qkv.device.index or 0, qkv.data_ptr(), qb.data_ptr(), int(qb.shape[0]), self.heads,
-                                                      self.hidden // self.heads, (self.hidden // self.heads) ** -0.5, ctx.data_ptr(),
-                                                      torch.cuda.current_stream(qkv.device).cuda_stream)
-            if rc:
-                raise RuntimeError("rdx_enc_attention_mfma_f16: " + self._last_error())
-            return ctx
-        rc = self._lib.rdx_enc_attention_f16(qkv.device.index or 0, qkv.data_ptr(), tok_first.data_ptr(), tok_len.data_ptr(), T, self.heads,
-                                             self.hidden // self.heads, (self.hidden // self.heads) ** -0.5, int(max_len), ctx.data_ptr(),
-                                             torch.cuda.current_stream(qkv.device).cuda_stream)
-        if rc:
-            raise RuntimeError("rdx_enc_attention_f16: " + self._last_error())
-        return ctx
-
-    # HIP-graph replay of the fused forward: captured per shape the second time the shape is seen, replayed with ONE launch; the five
-    # small index tensors go into static device buffers first. graphs = "auto" (default): batches of at most SMALL_TEXTS texts — the
-    # reference's online path: embed_query(), or the <= 4 sub-queries of one question embedded together (rag_dpo_amd/retriever.py) —
-    # whose ~200 tiny kernels are pure launch latency (measured, one question on XLM-R-large fp16: module forward 6.3 ms, this
-    # forward eager 3.4, replayed 1.55). Such a batch is padded to a CANONICAL shape so that the graphs are few and always hit: real
-    # tokens up to a multiple of SMALL_TOKEN_GRANULE with one-token dummy texts (they attend to themselves; nobody reads their rows),
-    # the CLS index list up to SMALL_TEXTS entries, the longest text up to 16 / 32 / 64 (it sizes the attention's LDS window): at
-    # most 24 shapes. True: additionally every larger batch by its exact (texts, tokens, longest text) shape (a batch of 1024 gains
-    # nothing on the GPU, 3 ms of host time; production batches rarely repeat a token count). False: never. At most MAX_GRAPHS shapes
-    # are kept (least recently used out).
-    graphs = "auto"
-    large_graphs = os.environ.get("RDX_ENC_LARGE_GRAPHS", "1") != "0"   # canonical-shape graphs for large question batches too (cls())
-    LARGE_TOKEN_GRANULE = 1024
-    MAX_LARGE_GRAPHS = 3
-    MAX_GRAPHS = 64
-    SMALL_TEXTS = 8
-    SMALL_TOKEN_GRANULE = 32
-
-    # One question (at most STAGE_TOKENS packed tokens, padded to 16 or 32): five launches per layer, csrc/enc_small.hpp. The output
-    # projection and FFN-down have 1024 features: with 16 per workgroup they would occupy 64 CUs, so their workgroups take 8 / 4 rows of
-    # the MFMA tile (developer knobs RDX_ENC_FPB_O / RDX_ENC_FPB_F2; measured values in DESIGN.md §10).
-    STAGE_TOKENS = 32
-    STAGE_FPB_O = 8
-    STAGE_FPB_F2 = 8
-
-    def _stage(self, x, w, b, T, ln=None, y_out=None, res=None, rows=None, epi=0, fpb=0):
-        N, K = int(w.shape[0]), int(w.shape[1])
-        out = torch.empty((T, N), dtype=torch.float16, device=w.device)
-        rc = self._lib.rdx_enc_stage_f16(w.device.index or 0, x.data_ptr(), rows.data_ptr() if rows is not None else None,
-                                         ln.weight.data_ptr() if ln is not None else None, ln.bias.data_ptr() if ln is not None else None,
-                                         float(ln.eps) if ln is not None else 0.0, y_out.data_ptr() if y_out is not None else None,
-                                         w.data_ptr(), b.data_ptr(), res.data_ptr() if res is not None else None, T, N, K, epi, fpb,
-                                         out.data_ptr(), torch.cuda.current_stream(w.device).cuda_stream)
-        if rc:
-            raise RuntimeError("rdx_enc_stage_f16: " + self._last_error())
-        return out
-
-    def _small_forward(self, tok, pos, first_d, tok_first) -> torch.Tensor:
-        """[T <= 32] ids / positions -> fp32 [len(first_d)][hidden] CLS rows; librdx kernels only (no torch operation on the stream)"""
-        lib, dev = self._lib, tok.device
-        di, st = dev.index or 0, torch.cuda.current_stream(dev).cuda_stream
-        T, H, n_cls = int(tok.shape[0]), self.hidden, int(first_d.shape[0])
-        s = torch.empty((T, H), dtype=torch.float16, device=dev)
-        if lib.rdx_enc_embed_f16(di, tok.data_ptr(), pos.data_ptr(), self.word.weight.data_ptr(), self.pos.weight.data_ptr(),
-                                 self.typ.weight.data_ptr(), T, H, s.data_ptr(), st):
-            raise RuntimeError("rdx_enc_embed_f16: " + self._last_error())
-        ln, last = self.ln, len(self.layers) - 1
-        for li, (wqkv, bqkv, dense_o, ln1, inter, out, ln2) in enumerate(self.layers):
-            y = torch.empty((T, H), dtype=torch.float16, device=dev)
-            qkv = self._stage(s, wqkv, bqkv, T, ln=ln, y_out=y, epi=0)
-            ctx = torch.empty((T, H), dtype=torch.float16, device=dev)
-            if lib.rdx_enc_attention_small_f16(di, qkv.data_ptr(), tok_first.data_ptr(), T, self.heads, H // self.heads,
-                                               (H // self.heads) ** -0.5, ctx.data_ptr(), st):
-                raise RuntimeError("rdx_enc_attention_small_f16: " + self._last_error())
-            rows = None
-            if li == last:                                   # everything behind the last attention is row-wise: only the CLS rows are needed
-                rows, T = first_d, n_cls
-            s1 = self._stage(ctx, dense_o.weight, dense_o.bias, T, res=y, rows=rows, epi=2, fpb=self.stage_fpb_o)
-            y1 = torch.empty((T, H), dtype=torch.float16, device=dev)
-            f = self._stage(s1, inter.weight, inter.bias, T, ln=ln1, y_out=y1, epi=1)
-            s = self._stage(f, out.weight, out.bias, T, res=y1, epi=2, fpb=self.stage_fpb_f2)
-            ln = ln2
-        o = torch.empty((n_cls, H), dtype=torch.float32, device=dev)
-        if lib.rdx_enc_layernorm_rows_f16(di, s.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps), n_cls, H, o.data_ptr(), st):
-            raise RuntimeError("rdx_enc_layernorm_rows_f16: " + self._last_error())
-        return o
-
-    def _fused_forward(self, tok, pos, first_d, tok_first, tok_len, max_len: int = 0, qb=None) -> torch.Tensor:
-        """the forward on packed tokens with librdx's kernels: [T] ids / positions -> fp32 [B][hidden] CLS rows"""
-        if self.small_stage and tok.shape[0] <= self.STAGE_TOKENS:
-            return self._small_forward(tok, pos, first_d, tok_first)
-        F = torch.nn.functional
-        x = self.ln(self.word(tok) + self.pos(pos) + self.typ.weight[0])                                         # [T][H]
-        last = len(self.layers) - 1
-        small = self.small_linear and x.shape[0] <= self.SMALL_TOKENS   # one question, a question's sub-queries: weight-streaming projections, GELU in the epilogue
-        if not small and self._use_gemm(int(x.shape[0])):
-            # librdx's GEMM with fused epilogues: QKV, attention, O + residual, LayerNorm, FFN-up + GELU, FFN-down + residual, LayerNorm
-            x = x.contiguous()
-            for li, (wqkv, bqkv, dense_o, ln1, inter, out, ln2) in enumerate(self.layers):
-                ctx = self._attention(self._gemm(x, wqkv, bqkv), tok_first, tok_len, max_len, qb)
-                if li == last:
-                    ctx, x = ctx.index_select(0, first_d), x.index_select(0, first_d)
-                x = self._ln(self._gemm(ctx, dense_o.weight, dense_o.bias, 2, x), ln1)
-                x = self._ln(self._gemm(self._gemm(x, inter.weight, inter.bias, 1), out.weight, out.bias, 2, x), ln2)
-            return x.to(torch.float32)
-        for li, (wqkv, bqkv, dense_o, ln1, inter, out, ln2) in enumerate(self.layers):
-            qkv = self._linear(x, wqkv, bqkv) if small else F.linear(x, wqkv, bqkv)
-            ctx = self._attention(qkv, tok_first, tok_len, max_len, qb)                                           # [T][H], no padding anywhere
-            if li == last:                                   # everything behind the last attention is row-wise: only the CLS rows are needed
-                ctx, x = ctx.index_select(0, first_d), x.index_select(0, first_d)
-            if small:
-                x = self._add_ln(self._linear(ctx, dense_o.weight, dense_o.bias), x, ln1)
-                x = self._add_ln(self._linear(self._linear(x, inter.weight, inter.bias, gelu=True), out.weight, out.bias), x, ln2)
-            else:
-                x = self._add_ln(dense_o(ctx), x, ln1)
-                x = self._add_ln(out(self._gelu(inter(x))), x, ln2)
-        return x.to(torch.float32)
-
-    def _replay(self, key, host: dict, to_dev, max_len: int, unpack=None):
-        """-> the CLS rows from a captured graph of this shape, or None (shape not captured: the caller runs eagerly).
-        unpack: the forward's index tensors as views of the one static buffer host["pk_blob"] is copied into"""
-        args = (lambda st: unpack(st["pk_blob"])) if unpack is not None else (lambda st: tuple(st[n] for n in self._ORDER))
-        ent = self._graph.pop(key, None)
-        if ent is None:
-            if len(self._seen) > 4096:
-                self._seen.clear()
-            self._seen[key] = self._seen.get(key, 0) + 1
-            if self._seen[key] < 2:
-                return None
-            while len(self._graph) >= self.MAX_GRAPHS:
-                torch.cuda.current_stream(self.layers[0][0].device).synchronize()   # (its last replay may still run: its pool is freed with it)
-                self._graph.pop(next(iter(self._graph)))          # least recently used (dicts keep insertion order; a hit re-inserts)
-            dev = self.layers[0][0].device
-            static = {n: torch.empty(tuple(t.shape), dtype=t.dtype, device=dev) for n, t in host.items()}
-            for n, t in host.items():
-                to_dev(n, t, static[n])
-            try:
-                side = torch.cuda.Stream(device=dev)             # one eager run on a side stream first (library workspaces), as torch asks
-                side.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(side):
-                    self._fused_forward(*args(static), max_len, static.get("pk_qb"))
-                torch.cuda.current_stream(dev).wait_stream(side)
-                g = torch.cuda.CUDAGraph()
-                # thread-local capture mode: only THIS thread's calls are restricted while the capture runs — a search another
-                # thread has in flight on the same device (one shared provider and collection serve concurrent sessions, reference
-                # app.py:42-43) may allocate and synchronise as it likes
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    out = self._fused_forward(*args(static), max_len, static.get("pk_qb"))
-            except Exception as e:                               # noqa: BLE001  (a capture that fails costs speed only: eager from now on)
-                logger.warning(f"encoder graph capture failed ({e!r}); the forward stays eager")
-                self.graphs = False
-                return None
-            ent = (g, static, out)
-        self._graph[key] = ent
-        g, static, out = ent
-        for n, t in host.items():
-            to_dev(n, t, static[n])
-        g.replay()
-        return out                                               # (overwritten by the next replay of this shape: consume it on the stream)
-
-    _ORDER = ("pk_tok", "pk_pos", "pk_first", "pk_tfirst", "pk_tlen")
-
-    @staticmethod
-    def _query_blocks(first: np.ndarray, lens: np.ndarray) -> torch.Tensor:
-        """The MFMA attention kernel's work units: one per 64 queries of a text, {first token, length, first query, 0}."""
-        nb = (lens + 63) // 64
-        tix = np.repeat(np.arange(len(lens), dtype=np.int64), nb)
-        q0 = (np.arange(int(nb.sum()), dtype=np.int64) - np.repeat(np.cumsum(nb) - nb, nb)) * 64
-        return torch.from_numpy(np.stack([first[tix], lens[tix], q0, np.zeros_like(q0)], axis=1).astype(np.int32))
-
-    @staticmethod
-    def _window_promise(max_len: int) -> int:
-        """the longest text rounded up to 16 / 32 / 64: a canonical shape's promise to the attention kernel (its LDS window)"""
-        return 16 if max_len <= 16 else (32 if max_len <= 32 else 64)
-
-    @staticmethod
-    def _canonical_texts(first: np.ndarray, lens: np.ndarray, Tp: int):
-        """tok_first / tok_len (int32 [Tp]) of a canonical shape: the real texts' tokens, then one-token dummy texts up to Tp"""
-        T = int(lens.sum())
-        tf, tl = np.empty(Tp, dtype=np.int32), np.empty(Tp, dtype=np.int32)
-        tf[:T], tf[T:] = np.repeat(first, lens), np.arange(T, Tp)
-        tl[:T], tl[T:] = np.repeat(lens, lens), 1
-        return tf, tl
-
-    @classmethod
-    def _canonical_query_blocks(cls, first: np.ndarray, lens: np.ndarray, Tp: int, units: int) -> torch.Tensor:
-        """the MFMA kernel's work units of a canonical shape: the real texts' and the dummies', then repeats of the last unit up to
-        `units` (the same rows written twice with the same values)"""
-        T = int(lens.sum())
-        qb = cls._query_blocks(np.concatenate([first, np.arange(T, Tp, dtype=np.int64)]), np.concatenate([lens, np.ones(Tp - T, dtype=np.int64)]))
-        return torch.cat([qb, qb[-1:].expand(units - qb.shape[0], 4)]).contiguous()
-
-    @torch.no_grad()
-    def cls(self, ids: torch.Tensor, lens: np.ndarray, to_dev) -> torch.Tensor:
-        """ids: [B][S] int64 on the host, right-padded; lens[b] = tokens of text b (>= 1). -> fp32 [B][hidden] CLS rows on the device.
-        to_dev(name, host tensor[, out]) -> device tensor (the provider's pinned, non-blocking copies)."""
-        F = torch.nn.functional
-        B, S = int(ids.shape[0]), int(ids.shape[1])
-        lens = np.asarray(lens, dtype=np.int64)
-        T = int(lens.sum())
-        first = np.cumsum(lens) - lens                                   # packed index of every text's first token (CLS)
-        row = np.repeat(np.arange(B, dtype=np.int64), lens)
-        col = np.arange(T, dtype=np.int64) - np.repeat(first, lens)
-        ids_np = ids.numpy()
-        host = {"pk_tok": torch.from_numpy(np.ascontiguousarray(ids_np[row, col])), "pk_pos": torch.from_numpy(col + (self.pad + 1)),
-                "pk_first": torch.from_numpy(first)}
-        H, nh = self.hidden, self.heads
-        if self.fused and (int(lens.max()) <= self.FUSED_MAX_TOKENS or self.long_attention):
-            host["pk_tfirst"] = torch.from_numpy(np.repeat(first, lens).astype(np.int32))
-            host["pk_tlen"] = torch.from_numpy(np.repeat(lens, lens).astype(np.int32))
-            max_len = int(lens.max())
-            if max_len > self.FUSED_MAX_TOKENS or (self.long_attention and T >= self.MFMA_MIN_TOKENS):
-                # the corpus side (chunk texts of hundreds of tokens; and large question batches when MFMA_MIN_TOKENS says so): the MFMA
-                # kernel, one work unit per 64 queries
-                host["pk_qb"] = self._query_blocks(first, lens)
-            if self.graphs and B <= self.SMALL_TEXTS and max_len <= self.FUSED_MAX_TOKENS:
-                # (<= 32 tokens run the stage kernels: their cost follows the activation rows a workgroup stages, so the canonical shapes
-                #  are 8, 16, 24 and 32 tokens — a typical 20-token question pays for 24 rows, not 32)
-                g = 8 if (self.small_stage and T <= self.STAGE_TOKENS) else self.SMALL_TOKEN_GRANULE
-                Tp = -(-T // g) * g                               # one-token dummy texts behind the real ones
-                lb = self._window_promise(max_len)
-                # the five index arrays of the canonical shape in ONE buffer: one pinned copy per question instead of five
-                # (each small copy is ~15 us of stream time: 0.07 of a 0.95 ms embed_query)
-                o1, o2, o3, o4, nb_ = 8 * Tp, 16 * Tp, 16 * Tp + 8 * self.SMALL_TEXTS, 20 * Tp + 8 * self.SMALL_TEXTS, 24 * Tp + 8 * self.SMALL_TEXTS
-                blob = np.empty(nb_, dtype=np.uint8)
-                v64, v32 = blob[:o3].view(np.int64), blob[o3:].view(np.int32)
-                v64[:T] = ids_np[row, col]
-                v64[T:Tp] = self.pad
-                v64[Tp:Tp + T] = col + (self.pad + 1)
-                v64[Tp + T:2 * Tp] = self.pad + 1
-                v64[2 * Tp:2 * Tp + B] = first
-                v64[2 * Tp + B:] = 0
-                v32[:Tp], v32[Tp:] = self._canonical_texts(first, lens, Tp)
-
-                def unpack(d):
-                    return (d[:o1].view(torch.int64), d[o1:o2].view(torch.int64), d[o2:o3].view(torch.int64), d[o3:o4].view(torch.int32),
-                            d[o4:].view(torch.int32))
-                hb = {"pk_blob": torch.from_numpy(blob)}
-                out = self._replay(("small", Tp, lb), hb, to_dev, lb, unpack)
-                if out is None:   # shape not captured yet: the SAME padded tensors eagerly, so that call 1 and the replays run identical shapes
-                    out = self._fused_forward(*unpack(to_dev("pk_blob", hb["pk_blob"])), lb)
-                return out[:B]
-            elif self.graphs and self.large_graphs and max_len <= self.FUSED_MAX_TOKENS and T >= self.LARGE_TOKEN_GRANULE:
-                # a large batch of questions (BASELINE config 5: 1024 texts, ~20 K tokens): its ~230 launches cost a busy host 15 - 35 ms
-                # per encode (measured, DESIGN.md §10) against 15 ms of GPU time. Canonical shape = real tokens padded to a multiple of
-                # LARGE_TOKEN_GRANULE with one-token dummy texts (<= 5 % more rows at 20 K tokens; nobody reads their outputs), the
-                # longest text rounded to 16 / 32 / 64: consecutive batches of a serving loop hit the same graph, ONE launch per encode.
-                g = self.LARGE_TOKEN_GRANULE
-                Tp = -(-T // g) * g
-                extra = Tp - T
-                lb = self._window_promise(max_len)
-                tf, tl = self._canonical_texts(first, lens, Tp)
-                padded = {"pk_tok": torch.from_numpy(np.concatenate([host["pk_tok"].numpy(), np.full(extra, self.pad, dtype=np.int64)])),
-                          "pk_pos": torch.from_numpy(np.concatenate([host["pk_pos"].numpy(), np.full(extra, self.pad + 1, dtype=np.int64)])),
-                          "pk_first": host["pk_first"], "pk_tfirst": torch.from_numpy(tf), "pk_tlen": torch.from_numpy(tl)}
-                if "pk_qb" in host:
-                    # (B + extra work units; `extra` moves with T inside one canonical shape, so the list is filled up to B + g units)
-                    padded["pk_qb"] = self._canonical_query_blocks(first, lens, Tp, B + g)
-                big = [k_ for k_ in self._graph if k_[0] == "large"]
-                key = ("large", B, Tp, lb)
-                if key not in self._graph and len(big) >= self.MAX_LARGE_GRAPHS:
-                    torch.cuda.current_stream(self.layers[0][0].device).synchronize()   # (its last replay may still run)
-                    self._graph.pop(big[0])                       # each holds the activations of ~Tp tokens: keep few
-                out = self._replay(key, padded, to_dev, lb)
-                if out is not None:
-                    return out
-                return self._fused_forward(*(to_dev(n, padded[n]) for n in self._ORDER), lb, to_dev("pk_qb", padded["pk_qb"]) if "pk_qb" in padded else None)
-            elif self.graphs is True:
-                nqb = int(host["pk_qb"].shape[0]) if "pk_qb" in host else 0
-                out = self._replay((B, T, max_len, nqb), host, to_dev, max_len)   # (the longest text sizes the attention's LDS window: part of the shape)
-                if out is not None:
-                    return out
-            return self._fused_forward(*(to_dev(n, host[n]) for n in self._ORDER), max_len, to_dev("pk_qb", host["pk_qb"]) if "pk_qb" in host else None)
-        tok, pos, first_d = (to_dev(n, host[n]) for n in ("pk_tok", "pk_pos", "pk_first"))
-        x = self.ln(self.word(tok) + self.pos(pos) + self.typ.weight[0])                                         # [T][H]
-        flat_d = to_dev("pk_flat", torch.from_numpy(row * S + col))                                              # slot of packed token t in the padded [B*S] layout
-        kmask = to_dev("pk_mask", torch.from_numpy(np.arange(S)[None, :] < lens[:, None])).view(B, 1, 1, S)       # keys of the text itself
-        key = (B, S, x.dtype, x.device)
-        qkv_pad = self._pad_buf.get(key)
-        if qkv_pad is None:
-            if len(self._pad_buf) > 8:
-                self._pad_buf.clear()
-            qkv_pad = self._pad_buf[key] = torch.zeros((B * S, 3 * H), dtype=x.dtype, device=x.device)   # (stale padding slots are masked keys / dropped queries)
-        last = len(self.layers) - 1
-        for li, (wqkv, bqkv, dense_o, ln1, inter, out, ln2) in enumerate(self.layers):
-            qkv_pad.index_copy_(0, flat_d, self._gemm(x.contiguous(), wqkv, bqkv) if self._use_gemm(T) else F.linear(x, wqkv, bqkv))
-            q, k, v = qkv_pad.view(B, S, 3, nh, H // nh).permute(2, 0, 3, 1, 4)                                   # [B][heads][S][head_dim] views
-            ctx = F.scaled_dot_product_attention(q, k, v, attn_mask=kmask)
-            ctx = ctx.transpose(1, 2).reshape(B * S, H).index_select(0, flat_d)                                   # back to [T][H]
-            if li == last:                                   # everything behind the last attention is row-wise: only the CLS rows are needed
-                ctx, x = ctx.index_select(0, first_d), x.index_select(0, first_d)
-            if self._use_gemm(T):
-                x = self._ln(self._gemm(ctx, dense_o.weight, dense_o.bias, 2, x.contiguous()), ln1)
-                x = self._ln(self._gemm(self._gemm(x, inter.weight, inter.bias, 1), out.weight, out.bias, 2, x), ln2)
-            else:
-                x = ln1(dense_o(ctx) + x)
-                x = ln2(out(F.gelu(inter(x))) + x)
-        return x.to(torch.float32)
-
-
-def _resolve_local_dir(model_name: str, cache_dir: Optional[str]) -> Optional[str]:
-    cands = [model_name]
-    if cache_dir:
-        cands += [os.path.join(cache_dir, model_name), os.path.join(cache_dir, model_name.replace("/", "_")),
-                  os.path.join(cache_dir, "models--" + model_name.replace("/", "--"))]
-    for c in cands:
-        if os.path.isdir(c):
-            if os.path.exists(os.path.join(c, "config.json")):
-                return c
-            snaps = os.path.join(c, "snapshots")   # HF hub cache layout
-            if os.path.isdir(snaps):
-                for s in sorted(os.listdir(snaps)):
-                    if os.path.exists(os.path.join(snaps, s, "config.json")):
-                        return os.path.join(snaps, s)
-    return None
 
 
 class _ProviderOptions(type):
@@ -634,8 +123,7 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
         if self.packed_forward:
             try:
                 fused = self.fused_kernels if self.fused_kernels is not None else (str(self.device).startswith("cuda") and self.dtype == torch.float16)
-                self._packed = _PackedEncoder(self._model, fused=bool(fused))
-                self._packed.graphs = "auto" if self.encoder_graphs is None else bool(self.encoder_graphs)
+                self._packed = _PackedEncoder(self._model, fused=bool(fused), graphs="auto" if self.encoder_graphs is None else bool(self.encoder_graphs))
                 if self.gemm is not None:
                     self._packed.gemm = self.gemm
             except ValueError as e:                                           # another architecture: the module forward stays
@@ -653,9 +141,7 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
         with self._lock:
             if self._model is not None or self._packed is not None:
                 if self._packed is not None:
-                    self._packed._graph.clear()       # graphs first: their pools go back to the allocator
-                    self._packed._pad_buf.clear()
-                    self._packed.layers = []
+                    self._packed.release()
                 self._packed = None
                 self._pinned.clear()
                 self._model = None

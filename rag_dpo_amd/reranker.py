@@ -32,7 +32,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from .embedding_provider import _XLMR_LARGE, _HashTokenizer, _PackedEncoder, _resolve_local_dir
+from .packed_encoder import _XLMR_LARGE, _HashTokenizer, _PackedEncoder, _resolve_local_dir
 
 logger = logging.getLogger(__name__)
 
@@ -91,8 +91,7 @@ class _CrossEncoderModel:
         if use_packed:
             try:
                 fused = self.on_gpu and dtype == torch.float16
-                self._packed = _PackedEncoder(model.roberta, fused=fused)
-                self._packed.graphs = False          # eager: graph capture of the rerank forward is not part of this path
+                self._packed = _PackedEncoder(model.roberta, fused=fused, graphs=False)   # eager: graph capture of the rerank forward is not part of this path
                 if self.on_gpu and not self._packed.fused:
                     self._packed = None              # another GPU shape or dtype: the module backbone, then the head kernel
             except ValueError as e:

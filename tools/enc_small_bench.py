@@ -1,5 +1,5 @@
 """Developer: latency of the single-question forward (embed_device([q]) + synchronise, HIP-graph replay) under the knobs of
-rag_dpo_amd/embedding_provider.py `_PackedEncoder` (RDX_ENC_FPB_O, RDX_ENC_FPB_F2). One JSON line.
+rag_dpo_amd/packed_encoder.py `_PackedEncoder` (RDX_ENC_FPB_O, RDX_ENC_FPB_F2). One JSON line.
   python tools/enc_small_bench.py [reps]         RDX_ENC_OLD=1: round 3's seven-launches-per-layer path for comparison"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
