@@ -20,6 +20,12 @@ PACKED_FLAGS = 4         # include/rdx.h RDX_PACKED_FLAGS: int32 words behind th
 RERANK_FEATURES = 8      # include/rdx.h RDX_RERANK_WORKSPACE_BYTES: output features per head workgroup
 DOCS_OP_NOT, DOCS_OP_AND, DOCS_OP_OR = -1, -2, -3   # include/rdx.h RDX_DOCS_OP_*
 DOCS_MAX_LEAVES = 1024   # include/rdx.h RDX_DOCS_MAX_LEAVES
+TOPIC_MAX_N, TOPIC_MAX_TOPICS, TOPIC_MAX_TAGS, TOPIC_MAX_DIM = 1024, 32, 64, 4096   # include/rdx.h rdx_topic_boost's limits
+
+
+def topic_pair(topic: int, tag: int, exact: bool) -> int:
+    """include/rdx.h RDX_TOPIC_PAIR"""
+    return (tag << 8) | (128 if exact else 0) | (topic & 31)
 
 
 class RdxUnavailable(RuntimeError):
@@ -85,6 +91,7 @@ SYMBOLS = {
     "rdx_enc_layernorm_f16": (_i, [_i, _vp, _vp, _vp, ctypes.c_float, _i64, _i, _vp, _vp]),
     "rdx_rerank_head_f16": (_i, [_i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rdx_rerank_select": (_i, [_i, _vp, _vp, _i, _i, ctypes.c_double, _i, _vp, _vp, _vp, _vp]),
+    "rdx_topic_boost": (_i, [_i, _vp, _i64, _i, _vp, _i, _vp, _i, _vp, _vp, _i64, _i, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp]),
     "rdx_search": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "rdx_mask_create": (_i, [_vp, _vp, _i, ctypes.POINTER(_vp)]),
     "rdx_mask_destroy": (_i, [_vp]),

@@ -1,4 +1,5 @@
-// rdx_enc.hip — the encoder launchers (rdx_enc_*) and the reranker head and selection (rdx_rerank_*) of include/rdx.h.
+// rdx_enc.hip — the encoder launchers (rdx_enc_*), the reranker head and selection (rdx_rerank_*) and the topic boost
+// (rdx_topic_boost) of include/rdx.h.
 #include "rdx_host.hpp"
 
 #include <mutex>
@@ -8,6 +9,7 @@
 #include "enc_small.hpp"
 #include "enc_gemm.hpp"
 #include "rerank_kernel.hpp"
+#include "topic_kernel.hpp"
 
 using namespace rdx;
 
@@ -379,6 +381,42 @@ extern "C" int rdx_rerank_select(int device, const float* scores, const double* 
     HIP_TRY(hipSetDevice(device));
     hipLaunchKernelGGL(k_rerank_select, dim3(1), dim3(RERANK_MAX_N), 0, (hipStream_t)stream, scores, boosts, n, top_k, min_score,
                        keep_min, order, final_score, count);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// topic boost of a question's candidates (topic_kernel.hpp): the boosts rdx_rerank_select reads
+// ------------------------------------------------------------------------------------------------
+extern "C" int rdx_topic_boost(int device, const float* table, int64_t table_rows, int dim, const int32_t* topic_slots, int n_topics,
+                               const int32_t* tag_slots, int n_tags, const int32_t* pair_offsets, const int32_t* pairs, int64_t n_pairs,
+                               int n, double threshold, double max_boost, double* sims, double* boosts, double* best_sim, void* stream) {
+    if (n < 1 || n > TOPIC_MAX_N) return fail(RDX_ERR_INVALID, "rdx_topic_boost: n must be in [1, 1024]");
+    if (dim < 1 || dim > TOPIC_MAX_DIM) return fail(RDX_ERR_INVALID, "rdx_topic_boost: dim must be in [1, 4096]");
+    if (n_topics < 0 || n_topics > TOPIC_MAX_TOPICS) return fail(RDX_ERR_INVALID, "rdx_topic_boost: n_topics must be in [0, 32]");
+    if (n_tags < 0 || n_tags > TOPIC_MAX_CALL_TAGS) return fail(RDX_ERR_INVALID, "rdx_topic_boost: n_tags must be in [0, 65536]");
+    if (n_pairs < 0 || n_pairs > (int64_t)n * TOPIC_MAX_TOPICS * TOPIC_MAX_TAGS)
+        return fail(RDX_ERR_INVALID, "rdx_topic_boost: n_pairs must be in [0, n * 32 * 64] (at most 64 tags per candidate)");
+    if (table_rows < 0 || table_rows > (int64_t)1 << 31) return fail(RDX_ERR_INVALID, "rdx_topic_boost: table_rows must be in [0, 2^31]");
+    const bool dots = n_topics > 0 && n_tags > 0;
+    if (!pair_offsets || !boosts || (n_pairs > 0 && !pairs)) return fail(RDX_ERR_INVALID, "rdx_topic_boost: null pointer");
+    if (dots && ((table_rows > 0 && !table) || !topic_slots || !tag_slots || !sims))   // (an empty table may be NULL: no slot has an embedding)
+        return fail(RDX_ERR_INVALID, "rdx_topic_boost: null pointer (table, slots or sims)");
+    if (((uintptr_t)table | (uintptr_t)topic_slots | (uintptr_t)tag_slots | (uintptr_t)pair_offsets | (uintptr_t)pairs) & 3)
+        return fail(RDX_ERR_INVALID, "rdx_topic_boost: misaligned pointer");
+    if (((uintptr_t)sims | (uintptr_t)boosts | (uintptr_t)best_sim) & 7) return fail(RDX_ERR_INVALID, "rdx_topic_boost: misaligned pointer");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_topic_boost: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    if (dots) {
+        const int64_t waves = (int64_t)n_topics * n_tags;                  // <= 2^21
+        hipLaunchKernelGGL(k_topic_sims, dim3((unsigned)((waves + TOPIC_THREADS / 64 - 1) / (TOPIC_THREADS / 64))), dim3(TOPIC_THREADS), 0, st,
+                           table, table_rows, dim, topic_slots, n_topics, tag_slots, n_tags, sims);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_topic_replay, dim3((unsigned)((n + TOPIC_THREADS - 1) / TOPIC_THREADS)), dim3(TOPIC_THREADS), 0, st,
+                       (const double*)sims, dots ? n_topics : 0, dots ? n_tags : 0, pair_offsets, pairs, n_pairs, n, threshold, max_boost,
+                       boosts, best_sim);
     HIP_TRY(hipGetLastError());
     return RDX_OK;
 }

@@ -16,7 +16,9 @@ and on a GPU:
   - the backbone runs as ONE packed forward over the pairs' real tokens (`_PackedEncoder`, the embedding provider's forward: fp16 with
     64-wide heads and a hidden size that is a multiple of 512 uses librdx's attention and add + LayerNorm kernels), or, for other
     shapes and dtypes, as transformers' module forward in padded batches of `batch_size`;
-  - the classification head, the sigmoid and the selection are librdx kernels (`rdx_rerank_head_f16`, `rdx_rerank_select`, include/rdx.h).
+  - the classification head, the sigmoid and the selection are librdx kernels (`rdx_rerank_head_f16`, `rdx_rerank_select`, include/rdx.h);
+  - a `topic_matcher` that has `topic_boosts_device` and lives on the same GPU (rag_dpo_amd/topics.py) is asked ONCE for all candidates
+    and its device tensor goes to the selection as it is; any other matcher is called per candidate, as in the reference.
 On the CPU the module forward scores and the selection is the Python below. Jina's reranker (the reference's default) needs remote
 code and is not supported: `trust_remote_code` is accepted and never acted on.
 One deliberate difference: where the reference keeps nothing (n < 3 candidates, none above min_score, or top_k = 0 with n < 3) its
@@ -310,10 +312,14 @@ class CrossEncoderReranker:
         n = min(len(chunks), len(scores))                        # (zip(chunks, scores), reranker.py:166)
         boosts = None
         if topic_matcher is not None and question_topics:
-            boosts = [topic_matcher.topic_boost(question_topics, c.metadata.get("rgpd_topics", "")) for c in chunks[:n]]
-            hit = sum(1 for b in boosts if b > 0)
-            if hit:
-                logger.info(f"topic boost applied to {hit}/{n} chunks")
+            if self._boosts_on_device(topic_matcher, n):
+                # all candidates in one call, left where rdx_rerank_select reads them (rag_dpo_amd/topics.py): no host list, no upload
+                boosts = topic_matcher.topic_boosts_device(question_topics, [c.metadata.get("rgpd_topics", "") for c in chunks[:n]])
+            else:
+                boosts = [topic_matcher.topic_boost(question_topics, c.metadata.get("rgpd_topics", "")) for c in chunks[:n]]
+                hit = sum(1 for b in boosts if b > 0)
+                if hit:
+                    logger.info(f"topic boost applied to {hit}/{n} chunks")
         if str(self.device).startswith("cuda"):
             order, final, count = self._select_device(scores, boosts, n, top_k, stats)
         else:
@@ -335,8 +341,19 @@ class CrossEncoderReranker:
         return [RankedChunk(chunk_id=chunks[i].chunk_id, text=chunks[i].text, document_path=chunks[i].document_path,
                             rerank_score=final[i], original_rank=i, metadata=chunks[i].metadata) for i in order[:count]]
 
+    def _boosts_on_device(self, topic_matcher, n: int) -> bool:
+        """a matcher with topic_boosts_device whose table lives on the GPU this reranker selects on"""
+        if not str(self.device).startswith("cuda") or not hasattr(topic_matcher, "topic_boosts_device") or not 1 <= n <= MAX_GPU_CANDIDATES:
+            return False
+        mine, theirs = torch.device(self.device), getattr(topic_matcher, "device", None)
+        if not isinstance(theirs, torch.device) or theirs.type != "cuda":
+            return False
+        index = lambda d: torch.cuda.current_device() if d.index is None else d.index   # noqa: E731
+        return index(mine) == index(theirs)
+
     def _select_device(self, scores, boosts, n: int, top_k: int, stats: dict):
-        """rdx_rerank_select on the GPU: scores from the head kernel (device tensor) or from a model's predict() (numpy)"""
+        """rdx_rerank_select on the GPU: scores from the head kernel (device tensor) or from a model's predict() (numpy); boosts None,
+        a host list, or the fp64 device tensor of TopicMatcher.topic_boosts_device"""
         from . import _lib as L
         if n > MAX_GPU_CANDIDATES:
             raise ValueError(f"the GPU reranker selects among at most {MAX_GPU_CANDIDATES} candidates per call, got {n}")
@@ -347,7 +364,11 @@ class CrossEncoderReranker:
         scores = scores[:n].contiguous()
         dev = scores.device
         b = None
-        if boosts is not None:
+        if isinstance(boosts, torch.Tensor):
+            if boosts.dtype != torch.float64 or boosts.device != dev or boosts.numel() < n:
+                raise ValueError(f"topic_boosts_device must return fp64 [{n}] on {dev}, got {boosts.dtype} [{boosts.numel()}] on {boosts.device}")
+            b = boosts[:n].contiguous()
+        elif boosts is not None:
             b = torch.from_numpy(np.asarray([float(x) for x in boosts], dtype=np.float64)).to(dev)
         order = torch.empty((n,), dtype=torch.int32, device=dev)
         final = torch.empty((n,), dtype=torch.float64, device=dev)
@@ -360,4 +381,8 @@ class CrossEncoderReranker:
         s1.record()
         c = int(count.item())                                    # (synchronises the stream: the events below are complete)
         stats["events"] = (s0, s1)
+        if isinstance(boosts, torch.Tensor):                     # (the stream is drained: the copy waits for nothing)
+            hit = int((b.cpu().numpy() > 0).sum())
+            if hit:
+                logger.info(f"topic boost applied to {hit}/{n} chunks")
         return order[:c].cpu().tolist(), final.cpu().tolist(), c
