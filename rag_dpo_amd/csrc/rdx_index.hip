@@ -599,18 +599,10 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
     sp.inv_scale2 = std::ldexp(1.0f, -2 * h->scale_log2);
     sp.shadow_bytes = (int64_t)shadow_bytes(h, h->cap);
     sp.oob = reinterpret_cast<int*>(h->ctr.as<char>() + offsetof(RefineCounters, oob));
+    const SplitKParams sk = {sp.shadow, sp.qshadow, sp.ksteps, sp.rows, p.n_blocks32, sp.allow};   // k_boot's and k_scan_small's share
 
     if (p.use_boot) {
-        BootParams bp = {};
-        bp.shadow = h->shadow;
-        bp.qshadow = h->qshadow.as<_Float16>();
-        bp.ksteps = h->ksteps;
-        bp.rows = h->rows;
-        bp.n_blocks32 = p.n_blocks32;
-        bp.units = (int)p.boot_units;
-        bp.allow = io.allow;
-        bp.setmax = h->setmax.as<float>();
-        bp.n_sets = p.boot_sets;
+        const BootParams bp = {sk, (int)p.boot_units, sp.setmax, p.boot_sets};
         hipLaunchKernelGGL(k_boot, dim3((unsigned)p.boot_units), dim3(512), 0, st, bp);
         HIP_TRY(hipGetLastError());
     } else {
@@ -642,19 +634,7 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
     std::copy(p.xlo, p.xlo + 9, sp.xlo);
     sp.wgt = p.stamps ? h->wgt.as<unsigned long long>() : nullptr;
     if (p.use_small) {
-        SmallScanParams ss = {};
-        ss.shadow = h->shadow;
-        ss.qshadow = h->qshadow.as<_Float16>();
-        ss.ksteps = h->ksteps;
-        ss.rows = h->rows;
-        ss.n_blocks32 = p.n_blocks32;
-        ss.allow = io.allow;
-        ss.tau = h->tau.as<float>();
-        ss.cntw = h->cntw.as<uint32_t>();
-        ss.cand = h->cand.as<uint2>();
-        ss.capw = p.capw;
-        ss.inv_scale2 = sp.inv_scale2;
-        ss.wgt = sp.wgt;
+        const SmallScanParams ss = {sk, sp.tau, sp.cntw, sp.cand, sp.capw, sp.inv_scale2, sp.wgt};
         hipLaunchKernelGGL(k_scan_small, dim3((unsigned)p.grid), dim3(512), 0, st, ss);
         HIP_TRY(hipGetLastError());
     } else if (p.i8) {

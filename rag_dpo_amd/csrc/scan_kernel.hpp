@@ -229,6 +229,7 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
 
     // ---- per-tile epilogue pieces -----------------------------------------------------------------------------------
     // which rows of this wave's 32-row block of schedule entry it_done may be used (ragged last tile, `where` bitmap)
+    // (block_row_mask below states the same rule; this copy is part of k_scan's tuned register budget and stays as it is)
     auto tile_rows = [&](int it_done, int64_t& row_b, uint32_t& okbits, bool& filt) __attribute__((always_inline)) {
         const int64_t tile = (int64_t)sched_of(it_done) * p.tile_stride;
         row_b = tile * TILE_ROWS + wave * (EPI == EPI_SETMAX ? 32 + p.row_off : 32);   // first row of this wave's 32-row block
@@ -636,48 +637,134 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
     }
 }
 
+// ---- The split-K core of K2b (k_boot) and K2c (k_scan_small): launches of at most 64 queries ------------------------------------
+// One workgroup scores ONE 32-row block of the scan copy against the 64 queries at a time, the K loop split over its eight waves;
+// the eight partial 32 x 64 tiles meet in four LDS slabs. Both kernels are built from the pieces below and from nothing else that
+// adds, so a (row, query) pair gets THE SAME fp32 number from either. The summation order, in full:
+//   1. wave w owns the k-steps ks = w, w + 8, w + 16, ... < ksteps and adds them in ascending order into acc (zero at the start):
+//      splitk_kstep per k-step, its two 32-wide sub-steps kk = 0, 1 in that order, one v_mfma_f32_16x16x32_f16 per 16 x 16 block
+//      and sub-step. A wave that owns no k-step keeps acc = +0.
+//   2. splitk_reduce: waves 4..7 park acc in slab[w - 4]; wave w = 0..3 then stores  acc(w) + slab[w]  (its own tile the left
+//      operand, wave w + 4's the right one) back into slab[w].
+//   3. splitk_sum: ((((0 + slab[0]) + slab[1]) + slab[2]) + slab[3]).
+// plan_search (rdx_index.hip) relies on this: with use_boot && use_small the threshold's slack holds NO term for a rounding
+// difference between the sample's sums and the main scan's. (k_boot takes its k-steps two per round, ks0 = w, w + 16, ... with
+// ks0 + 8 each; k_scan_small holds exactly w and w + 8, and is only planned for ksteps <= 16 — the orders coincide wherever both
+// kernels run. With another main scan, k_scan, the orders differ and the plan adds twice the fp32 accumulation bound.)
+struct SplitKParams {
+    const _Float16* shadow;    // fragment-ordered corpus scan copy
+    const _Float16* qshadow;   // tiled query scan copy (query block 0: <= 64 queries)
+    int ksteps;                // dim_pad / 64
+    int64_t rows;              // valid corpus rows
+    int64_t n_blocks32;        // ceil(rows / 32)
+    const uint32_t* allow;     // NULL or row bitmap
+};
+constexpr int BOOT_BN = 64;
+constexpr int BOOT_NB = BOOT_BN / 16;   // 16-query blocks
+constexpr int BOOT_LD = 32 + 4;   // floats per query in a partial-sum slab [query][row]: a lane's 4 rows are one ds_write_b128, and the 16 lanes of
+                                  // a pass land on 16 distinct bank quads (9 * query mod 16)
+using SplitKSlabs = float[4][BOOT_BN * BOOT_LD];
+
+// this lane's B fragment of 16-query block n for sub-step kk of k-step ks, straight from the query scan copy (rdx_common.hpp "query
+// scan copy": image ks of query block 0, image row r = the query, 16-B chunk c = 4 kk + lq in slot c ^ ((r >> 1) & 7))
+__device__ __forceinline__ half8 splitk_qfrag(const char* q_base, int ks, int kk, int n, int l15, int lq) {
+    const int r = n * 16 + l15;
+    return *reinterpret_cast<const half8*>(q_base + ((int64_t)ks * 256 + r) * 128 + (((kk * 4 + lq) ^ ((r >> 1) & 7)) << 4));
+}
+
+// one k-step: a = the wave's four 1 KiB corpus chunks of it, b[kk][n] = splitk_qfrag(.., kk, n, ..); acc[m][n] = rows
+// m*16 + lq*4 + 0..3 of the block for query n*16 + l15
+__device__ __forceinline__ void splitk_kstep(const half8 (&a)[4], const half8 (&b)[2][BOOT_NB], f32x4 (&acc)[2][BOOT_NB]) {
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int n = 0; n < BOOT_NB; ++n) {
+            acc[0][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[2 * kk], b[kk][n], acc[0][n], 0, 0, 0);
+            acc[1][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[2 * kk + 1], b[kk][n], acc[1][n], 0, 0, 0);
+        }
+}
+
+// The eight waves' partial tiles meet in LDS WITHOUT atomics: ds_add_f32 measured ~125 cycles per wave-instruction on this chip
+// (256 of them per workgroup: 20 of k_boot's first version's 27 us). Waves 4-7 park their tiles, waves 0-3 add their partner's to
+// their own and park the sums: afterwards (both barriers passed) slab[0..3][query][row] hold the four partial sums.
+__device__ __forceinline__ void splitk_reduce(SplitKSlabs& slab, int wave, int l15, int lq, const f32x4 (&acc)[2][BOOT_NB]) {
+    float* mine = slab[wave & 3] + l15 * BOOT_LD + lq * 4;
+    if (wave >= 4) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int n = 0; n < BOOT_NB; ++n) *reinterpret_cast<f32x4*>(mine + n * 16 * BOOT_LD + m * 16) = acc[m][n];
+    }
+    __syncthreads();
+    if (wave < 4) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int n = 0; n < BOOT_NB; ++n) {
+                f32x4* cell = reinterpret_cast<f32x4*>(mine + n * 16 * BOOT_LD + m * 16);
+                const f32x4 o = *cell;
+                *cell = f32x4{acc[m][n][0] + o[0], acc[m][n][1] + o[1], acc[m][n][2] + o[2], acc[m][n][3] + o[3]};
+            }
+    }
+    __syncthreads();
+}
+
+// the block's scores of query q for its rows 8j .. 8j+3 (lo) and 8j+4 .. 8j+7 (hi): the four slabs, added in the order 0, 1, 2, 3
+__device__ __forceinline__ void splitk_sum(const SplitKSlabs& slab, int q, int j, f32x4& lo, f32x4& hi) {
+    lo = f32x4{0.f, 0.f, 0.f, 0.f};
+    hi = lo;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(slab[w] + q * BOOT_LD + j * 8);
+        const f32x4 y = *reinterpret_cast<const f32x4*>(slab[w] + q * BOOT_LD + j * 8 + 4);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            lo[r] += x[r];
+            hi[r] += y[r];
+        }
+    }
+}
+
+// which rows of 32-row block rb count, bit i = row 32 rb + i: the ragged end of the corpus, then the `where` bitmap (one word per block)
+__device__ __forceinline__ uint32_t block_row_mask(int64_t rb, int64_t rows, const uint32_t* allow) {
+    uint32_t ok = 0xffffffffu;
+    const int64_t left = rows - rb * 32;
+    if (left < 32) ok = left <= 0 ? 0u : ((1u << left) - 1u);
+    if (allow && left > 0) ok &= allow[rb];
+    return ok;
+}
+
 // K2b. Threshold bootstrap for SMALL launches (<= 64 queries, at most a few 32-row blocks per CU): the K loop split over the waves.
 // The scan kernel above samples whole 256-row tiles: a launch that samples 33 tiles (100 k rows, the sample is 8 K rows) keeps
 // 33 of 256 CUs busy with 16 DEPENDENT k-steps each — 19 us of latency for 0.3 us of arithmetic (round 2's c2: the bootstrap
-// was a fifth of the step). Here one workgroup takes ONE 32-row block of the scan copy, wave w takes the k-steps w, w+8, ...
-// of it (all their fragment loads in flight at once: no dependent chain), the eight partial 32 x 64 tiles are summed in LDS
-// (ds_add_f32), and the block's four 8-row sets leave their per-query maxima: 256 workgroups x 32 rows sample the same 8 K
-// rows in one round of two k-steps. The query fragments come straight from the tiled query scan copy into registers (each
-// fragment is used once; no LDS image). The partial sums are added in another order than the main scan adds them: both are
-// within E of the exact score (E bounds fp32 accumulation in ANY order), which is all the threshold's proof uses.
+// was a fifth of the step). Here one workgroup takes ONE 32-row block of the scan copy and runs the split-K core above on it, two
+// k-steps per wave and round with all their fragment loads in flight at once (no dependent chain), and the block's four 8-row sets
+// leave their per-query maxima: 256 workgroups x 32 rows sample the same 8 K rows in one round of two k-steps. The query fragments
+// come straight from the tiled query scan copy into registers (each fragment is used once; no LDS image). The sums are added in
+// another order than k_scan adds them: both are within E of the exact score (E bounds fp32 accumulation in ANY order,
+// DESIGN.md §5), which is all the threshold's proof uses.
 //   unit u of U -> 32-row block rb = floor(u * n_blocks32 / U); set id = u * 4 + j, j = 8-row group; setmax[query][n_sets]
 struct BootParams {
-    const _Float16* shadow;
-    const _Float16* qshadow;
-    int ksteps;
-    int64_t rows;
-    int64_t n_blocks32;
+    SplitKParams sk;
     int units;
-    const uint32_t* allow;
     float* setmax;
     int n_sets;
 };
-constexpr int BOOT_BN = 64;
-constexpr int BOOT_LD = 32 + 4;   // floats per query in a partial-sum slab [query][row]: a lane's 4 rows are one ds_write_b128, and the 16 lanes of
-                                  // a pass land on 16 distinct bank quads (9 * query mod 16)
 __global__ __launch_bounds__(512) void k_boot(const BootParams p) {
-    // The eight waves' partial tiles meet in LDS WITHOUT atomics: ds_add_f32 measured ~125 cycles per wave-instruction on this chip
-    // (256 of them per workgroup: 20 of the first version's 27 us). Waves 4-7 park their tiles, waves 0-3 add their partner's to
-    // their own and park the sums, and the final pass adds the four slabs.
-    __shared__ __attribute__((aligned(16))) float slab[4][BOOT_BN * BOOT_LD];
+    __shared__ __attribute__((aligned(16))) SplitKSlabs slab;
     const int u = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int l15 = lane & 15, lq = lane >> 4;
-    const int64_t rb = (int64_t)u * p.n_blocks32 / p.units;
-    const int KS = p.ksteps;
-    constexpr int NB = BOOT_BN / 16;
+    const int64_t rb = (int64_t)u * p.sk.n_blocks32 / p.units;
+    const int KS = p.sk.ksteps;
+    constexpr int NB = BOOT_NB;
     f32x4 acc[2][NB];
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int n = 0; n < NB; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const char* a_base = reinterpret_cast<const char*>(p.shadow) + rb * ((int64_t)KS * 4096) + lane * 16;
-    const char* q_base = reinterpret_cast<const char*>(p.qshadow);   // query block 0 (<= 64 queries): image row r, 16-B chunk c -> slot c ^ ((r >> 1) & 7)
+    const char* a_base = reinterpret_cast<const char*>(p.sk.shadow) + rb * ((int64_t)KS * 4096) + lane * 16;
+    const char* q_base = reinterpret_cast<const char*>(p.sk.qshadow);
     // two k-steps per round: 8 corpus + 16 query fragments (96 VGPRs) requested together, then 32 MFMAs
     for (int ks0 = wave; ks0 < KS; ks0 += 16) {
         half8 a[2][4], b[2][2][NB];
@@ -690,10 +777,7 @@ __global__ __launch_bounds__(512) void k_boot(const BootParams p) {
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-                for (int n = 0; n < NB; ++n) {
-                    const int r = n * 16 + l15;
-                    b[t][kk][n] = *reinterpret_cast<const half8*>(q_base + ((int64_t)ks * 256 + r) * 128 + (((kk * 4 + lq) ^ ((r >> 1) & 7)) << 4));
-                }
+                for (int n = 0; n < NB; ++n) b[t][kk][n] = splitk_qfrag(q_base, ks, kk, n, l15, lq);
         }
         // all 24 requests are out before the first MFMA asks for one (left to itself the scheduler interleaves load, wait, MFMA
         // with two loads in flight: 24 dependent round trips, the very chain this kernel exists to avoid)
@@ -701,54 +785,15 @@ __global__ __launch_bounds__(512) void k_boot(const BootParams p) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             if (t == 1 && ks0 + 8 >= KS) break;
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                for (int n = 0; n < NB; ++n) {
-                    acc[0][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[t][2 * kk], b[t][kk][n], acc[0][n], 0, 0, 0);
-                    acc[1][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[t][2 * kk + 1], b[t][kk][n], acc[1][n], 0, 0, 0);
-                }
+            splitk_kstep(a[t], b[t], acc);
         }
     }
-    // acc[m][n] = rows m*16 + lq*4 + 0..3 of query n*16 + l15  ->  slab[query][row]
-    float* mine = slab[wave & 3] + l15 * BOOT_LD + lq * 4;
-    if (wave >= 4) {
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int n = 0; n < NB; ++n) *reinterpret_cast<f32x4*>(mine + n * 16 * BOOT_LD + m * 16) = acc[m][n];
-    }
-    __syncthreads();
-    if (wave < 4) {
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int n = 0; n < NB; ++n) {
-                f32x4* cell = reinterpret_cast<f32x4*>(mine + n * 16 * BOOT_LD + m * 16);
-                const f32x4 o = *cell;
-                *cell = f32x4{acc[m][n][0] + o[0], acc[m][n][1] + o[1], acc[m][n][2] + o[2], acc[m][n][3] + o[3]};
-            }
-    }
-    __syncthreads();
-    // which of the block's 32 rows count (ragged end of the corpus, `where` bitmap: one word per 32-row block)
-    const int64_t row0 = rb * 32;
-    uint32_t ok = 0xffffffffu;
-    const int64_t left = p.rows - row0;
-    if (left < 32) ok = left <= 0 ? 0u : ((1u << left) - 1u);
-    if (p.allow && left > 0) ok &= p.allow[rb];
+    splitk_reduce(slab, wave, l15, lq, acc);
+    const uint32_t ok = block_row_mask(rb, p.sk.rows, p.sk.allow);
     if (threadIdx.x < 4 * BOOT_BN) {
         const int q = threadIdx.x & (BOOT_BN - 1), j = threadIdx.x / BOOT_BN;   // set j = rows 8j .. 8j+7 of the block
-        f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = lo;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const f32x4 x = *reinterpret_cast<const f32x4*>(slab[w] + q * BOOT_LD + j * 8);
-            const f32x4 y = *reinterpret_cast<const f32x4*>(slab[w] + q * BOOT_LD + j * 8 + 4);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                lo[r] += x[r];
-                hi[r] += y[r];
-            }
-        }
+        f32x4 lo, hi;
+        splitk_sum(slab, q, j, lo, hi);
         float mx = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -759,22 +804,17 @@ __global__ __launch_bounds__(512) void k_boot(const BootParams p) {
     }
 }
 
-// K2c. Main scan of SMALL launches (<= 64 queries, <= 16 k-steps per row, at most a few hundred 32-row blocks per CU): k_boot's split-K
-// dataflow over ALL rows, with the emit epilogue. Why: the streaming kernel above deals whole 256-row tiles to 256 workgroups —
+// K2c. Main scan of SMALL launches (<= 64 queries, <= 16 k-steps per row, at most a few hundred 32-row blocks per CU): the split-K
+// core over ALL rows, with the emit epilogue. Why: the streaming kernel above deals whole 256-row tiles to 256 workgroups —
 // 100 k rows are 391 tiles, 1.53 per workgroup, i.e. TWO rounds of a 16-step pipeline for 1.5 rounds of work (and no finer unit
 // helps: 6 250 16-row blocks on 2 048 waves are 3.05 each, i.e. 4) — 41.9 us for a 25.6 us HBM stream at c2. Here a workgroup
 // takes a contiguous range of 32-row blocks (3 125 blocks / 256 = 12.2: the longest range is 13, 6 % over the mean), wave w owns
 // k-steps w and w + 8 of every block, its query fragments stay in registers for the whole launch (64 VGPRs, loaded once), the
-// next block's corpus fragments are requested before the current block is multiplied (64 KB in flight per CU), the eight partial
-// 32 x 64 tiles are summed through LDS slabs exactly as in k_boot (same order: the same coarse scores, bit for bit) and 256
-// threads compare the sums with the thresholds and append the hits (LDS counter per query, 8-byte store).
+// next block's corpus fragments are requested before the current block is multiplied (64 KB in flight per CU), the core sums the
+// eight partial tiles (the coarse scores k_boot sampled, bit for bit) and 256 threads compare the sums with the thresholds and
+// append the hits (LDS counter per query, 8-byte store).
 struct SmallScanParams {
-    const _Float16* shadow;
-    const _Float16* qshadow;
-    int ksteps;
-    int64_t rows;
-    int64_t n_blocks32;
-    const uint32_t* allow;
+    SplitKParams sk;
     const float* tau;          // [>= 64] accumulator units
     uint32_t* cntw;            // [nq_pad][n_streams]
     uint2* cand;               // [nq_pad][n_streams][capw]
@@ -783,7 +823,7 @@ struct SmallScanParams {
     unsigned long long* wgt;   // [grid][2] start / end stamps (NULL: not wanted)
 };
 __global__ __launch_bounds__(512) void k_scan_small(const SmallScanParams p) {
-    __shared__ __attribute__((aligned(16))) float slab[4][BOOT_BN * BOOT_LD];
+    __shared__ __attribute__((aligned(16))) SplitKSlabs slab;
     __shared__ uint32_t lcnt[BOOT_BN];
     __shared__ float tau_s[BOOT_BN];
     const int stream = blockIdx.x, n_streams = gridDim.x;
@@ -794,26 +834,23 @@ __global__ __launch_bounds__(512) void k_scan_small(const SmallScanParams p) {
         lcnt[threadIdx.x] = 0;
         tau_s[threadIdx.x] = p.tau[threadIdx.x];
     }
-    const int KS = p.ksteps;   // <= 16 (host)
-    constexpr int NB = BOOT_BN / 16;
+    const int KS = p.sk.ksteps;   // <= 16 (host)
+    constexpr int NB = BOOT_NB;
     const bool has0 = wave < KS, has1 = wave + 8 < KS;
     const int ks0 = has0 ? wave : 0, ks1 = has1 ? wave + 8 : ks0;
-    const int64_t b0 = (int64_t)stream * p.n_blocks32 / n_streams, b1 = (int64_t)(stream + 1) * p.n_blocks32 / n_streams;
+    const int64_t b0 = (int64_t)stream * p.sk.n_blocks32 / n_streams, b1 = (int64_t)(stream + 1) * p.sk.n_blocks32 / n_streams;
     // this wave's query fragments, for the whole launch
     half8 b[2][2][NB];
     {
-        const char* q_base = reinterpret_cast<const char*>(p.qshadow);
+        const char* q_base = reinterpret_cast<const char*>(p.sk.qshadow);
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-                for (int n = 0; n < NB; ++n) {
-                    const int r = n * 16 + l15;
-                    b[t][kk][n] = *reinterpret_cast<const half8*>(q_base + ((int64_t)(t ? ks1 : ks0) * 256 + r) * 128 + (((kk * 4 + lq) ^ ((r >> 1) & 7)) << 4));
-                }
+                for (int n = 0; n < NB; ++n) b[t][kk][n] = splitk_qfrag(q_base, t ? ks1 : ks0, kk, n, l15, lq);
     }
-    const char* a_lane = reinterpret_cast<const char*>(p.shadow) + lane * 16;
+    const char* a_lane = reinterpret_cast<const char*>(p.sk.shadow) + lane * 16;
     const int64_t rb_bytes = (int64_t)KS * 4096;
     auto load_a = [&](int64_t rb, half8 (&a)[2][4]) __attribute__((always_inline)) {
         const char* base = a_lane + rb * rb_bytes;
@@ -822,7 +859,6 @@ __global__ __launch_bounds__(512) void k_scan_small(const SmallScanParams p) {
 #pragma unroll
             for (int c = 0; c < 4; ++c) a[t][c] = *reinterpret_cast<const half8*>(base + (int64_t)(t ? ks1 : ks0) * 4096 + c * 1024);
     };
-    float* mine = slab[wave & 3] + l15 * BOOT_LD + lq * 4;
     // one block: multiply (fragments `a`), request the next block's fragments into `an` first
     auto block = [&](int64_t rb, half8 (&a)[2][4], half8 (&an)[2][4]) __attribute__((always_inline)) {
         load_a(rb + 1 < b1 ? rb + 1 : rb, an);   // (the last block re-reads itself: no branch around loads)
@@ -835,50 +871,15 @@ __global__ __launch_bounds__(512) void k_scan_small(const SmallScanParams p) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             if (t == 0 ? !has0 : !has1) continue;
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                for (int n = 0; n < NB; ++n) {
-                    acc[0][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[t][2 * kk], b[t][kk][n], acc[0][n], 0, 0, 0);
-                    acc[1][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[t][2 * kk + 1], b[t][kk][n], acc[1][n], 0, 0, 0);
-                }
+            splitk_kstep(a[t], b[t], acc);
         }
-        if (wave >= 4) {
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int n = 0; n < NB; ++n) *reinterpret_cast<f32x4*>(mine + n * 16 * BOOT_LD + m * 16) = acc[m][n];
-        }
-        __syncthreads();
-        if (wave < 4) {
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int n = 0; n < NB; ++n) {
-                    f32x4* cell = reinterpret_cast<f32x4*>(mine + n * 16 * BOOT_LD + m * 16);
-                    const f32x4 o = *cell;
-                    *cell = f32x4{acc[m][n][0] + o[0], acc[m][n][1] + o[1], acc[m][n][2] + o[2], acc[m][n][3] + o[3]};
-                }
-        }
-        __syncthreads();
+        splitk_reduce(slab, wave, l15, lq, acc);
         if (threadIdx.x < 4 * BOOT_BN) {
             const int q = threadIdx.x & (BOOT_BN - 1), j = threadIdx.x / BOOT_BN;   // rows 8j .. 8j+7 of the block, query q
             const int64_t row0 = rb * 32;
-            uint32_t ok = 0xffffffffu;
-            const int64_t left = p.rows - row0;
-            if (left < 32) ok = left <= 0 ? 0u : ((1u << left) - 1u);
-            if (p.allow && left > 0) ok &= p.allow[rb];
-            f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = lo;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const f32x4 x = *reinterpret_cast<const f32x4*>(slab[w] + q * BOOT_LD + j * 8);
-                const f32x4 y = *reinterpret_cast<const f32x4*>(slab[w] + q * BOOT_LD + j * 8 + 4);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    lo[r] += x[r];
-                    hi[r] += y[r];
-                }
-            }
+            const uint32_t ok = block_row_mask(rb, p.sk.rows, p.sk.allow);
+            f32x4 lo, hi;
+            splitk_sum(slab, q, j, lo, hi);
             const float tq = tau_s[q];
             const uint32_t seg0 = ((uint32_t)q * (uint32_t)n_streams + (uint32_t)stream) * p.capw;
 #pragma unroll

@@ -9,7 +9,7 @@ retried; `rescored` (rows k_refine found in its band) equals the model's count e
 probes' distance to t2 (2.5e-6 in the band, 6e-6 outside) changes it; `emitted` too where the threshold is known (k = 1: the sampled maximum is the query's own anchor).
 
 Which kernels a parametrisation takes (plan_search; `_plan` restates the part that decides it):
-  B <= 64, d <= 1024, split_boot / small_scan: k_boot / k_scan<SETMAX,64> + k_scan_small / k_scan<EMIT,64>
+  B <= 64, split_boot / small_scan: k_boot / k_scan<SETMAX,64> + k_scan_small (d <= 1024: at most 16 k-steps) / k_scan<EMIT,64>
   B = 65 .. 128: k_scan<*,128>; B = 129 .. 256: bootstrap k_scan<SETMAX,128> x 2 tiles (half_boot) or <SETMAX,256>, main <EMIT,256>
   B > 1024: several 256-query tiles; force_bn: 64 / 128 / 256 queries per workgroup; d = 4096: no k_scan_small (64 k-steps)
   fuse_epilogue 0/1: the emit check after the tile or fused into the next tile's first k-step (k_scan<EMIT> only)
@@ -278,10 +278,12 @@ KINDS = ["ladder", "aligned+", "split", "aligned-"]
 SMALL = [dict(split_boot=a, small_scan=b, fuse_epilogue=f) for a in (0, 1) for b in (0, 1) for f in (0, 1)]
 
 
-@pytest.mark.parametrize("dim", [64, 100, 1024])
+@pytest.mark.parametrize("dim", [64, 100, 576, 1024, 1536])
 @pytest.mark.parametrize("opts", SMALL, ids=lambda o: "-".join(f"{k}{v}" for k, v in o.items()))
 def test_small_launch_variants(eng, oracle, dim, opts):
-    """B = 64 (one LDS-resident 64-query tile): k_boot or the tile bootstrap, k_scan_small or k_scan<EMIT,64>"""
+    """B = 64 (one LDS-resident 64-query tile): k_boot or the tile bootstrap, k_scan_small or k_scan<EMIT,64>, at 1, 2, 9, 16 and
+    24 k-steps. 9: wave 0 of the split-K kernels owns two k-steps (0 and 8), waves 1..7 one each. 24: k_boot's second round holds
+    one k-step per wave, and k_scan_small (<= 16 k-steps) is not planned, so the threshold carries the extra slack."""
     rng = np.random.default_rng(dim)
     insts, fill = _instances(dim, 64 if dim >= 100 else 48, KINDS)
     corpus, owner = _corpus(insts, fill, dim, 9000, rng, opts_list=[opts])
