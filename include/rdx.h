@@ -449,6 +449,69 @@ int rdx_docs_contains(rdx_docs* h, uint32_t* out_bits, int space, void* stream);
  * of rdx_search / rdx_mask_create. RDX_DEVICE: enqueued on `stream`, nothing crosses PCIe. */
 int rdx_docs_filter(rdx_docs* h, const uint32_t* base_bits, uint32_t* out_bits, int space, void* stream);
 
+/* Metadata store and `where` -------------------------------------------------------------------- */
+/* Chroma's `where` filter (`collection.query(where=...)`, reference src/rag/pipeline.py:35-71, pages/1_Chat.py:245-247) evaluated on
+ * the device from metadata columns resident in HBM. rag_dpo_amd/where.py states the semantics and is the model;
+ * rag_dpo_amd/where_device.py validates a filter and compiles it into the leaves and the postfix program below.
+ *
+ * An rdx_meta holds some of a collection's metadata columns on one device, in the collection's row order; a column lives in a
+ * "slot" (0 <= col < RDX_META_MAX_COLUMNS) chosen by the caller. Layout per slot: kind uint8 [rows] (0 missing, 1 str, 2 int,
+ * 3 float, 4 bool: where.py K_*) and payload double [rows] — the value of an int / float / bool row, (double)code of a str row
+ * (code = the string's index in the column's host vocabulary, exact in a double), +0.0 for a missing row: 9 bytes per row. The
+ * store is independent of an rdx_index (the host keeps the two in step) and allocates nothing on the device until rows are set.
+ *
+ * A leaf is true for a row iff the row's kind equals the leaf's kind and `payload <op> operand` holds as an IEEE double
+ * comparison (the operand of a str leaf is its code, of any other leaf its num): a NaN operand matches nothing, -0.0 equals 0.0,
+ * an int 1 matches neither a bool True nor a float 1.0, a missing row matches no leaf (where.py Column._eq / Column._cmp).
+ * RDX_META_CONST0 / _CONST1 are false / true for every row and read no column (a key no row has).
+ *
+ * rdx_meta_set_rows / _drop_column / _truncate / _set_query take host pointers only and are complete on return; the ones that
+ * write or free device memory (set_rows with n > 0, drop_column of a slot in use, set_query) first wait for the store's last
+ * rdx_meta_filter to finish on its stream; truncate only lowers row counts and waits for nothing. Changing the store (the first three) unsets the query: call
+ * rdx_meta_set_query again before the next rdx_meta_filter. Arguments are validated before the store handle is used and before
+ * the device is touched. */
+typedef struct rdx_meta rdx_meta; /* opaque: metadata columns resident in one GPU's HBM */
+#define RDX_META_MAX_COLUMNS 4096
+#define RDX_META_MAX_LEAVES 1024
+#define RDX_META_EQ 0 /* leaf ops */
+#define RDX_META_GT 1
+#define RDX_META_GE 2
+#define RDX_META_LT 3
+#define RDX_META_LE 4
+#define RDX_META_CONST0 5
+#define RDX_META_CONST1 6
+#define RDX_META_OP_NOT (-1) /* program ops: >= 0 = push leaf i's verdict; NOT / AND / OR on the top of the stack (= RDX_DOCS_OP_*) */
+#define RDX_META_OP_AND (-2)
+#define RDX_META_OP_OR (-3)
+typedef struct rdx_meta_leaf {
+    int32_t col;  /* column slot (ignored by CONST0 / CONST1) */
+    int32_t op;   /* RDX_META_EQ .. RDX_META_CONST1 */
+    int32_t kind; /* 1 str (op EQ only), 2 int, 3 float, 4 bool */
+    int32_t code; /* operand of a str leaf; a code no row holds (e.g. -2: a string not in the vocabulary) matches nothing */
+    double num;   /* operand of an int / float / bool leaf */
+} rdx_meta_leaf;
+int rdx_meta_create(int device, rdx_meta** out);
+int rdx_meta_destroy(rdx_meta* h);
+/* writes rows [first_row, first_row + n) of slot `col` from host arrays kind uint8 [n] (each <= 4), num double [n] (read for
+ * int / float / bool rows), code int32 [n] (read for str rows). The column grows as needed; rows between its old end and
+ * first_row become "missing". */
+int rdx_meta_set_rows(rdx_meta* h, int col, int64_t first_row, const uint8_t* kind, const double* num, const int32_t* code,
+                      int64_t n);
+/* frees slot `col` (it then holds no rows) */
+int rdx_meta_drop_column(rdx_meta* h, int col);
+/* every column longer than `rows` is cut to `rows` rows (memory is kept) */
+int rdx_meta_truncate(rdx_meta* h, int64_t rows);
+/* columns = slots holding rows; bytes = device memory allocated for them (0 until the first rdx_meta_set_rows) */
+int rdx_meta_stats(const rdx_meta* h, int64_t* columns, int64_t* bytes);
+/* the query: 1 <= n_leaves <= RDX_META_MAX_LEAVES leaves and a postfix program of 1 <= n_ops <= 4096 ops using at most 16 stack
+ * entries and leaving exactly one. A leaf (other than a CONST) naming a slot that holds no rows: RDX_ERR_INVALID. */
+int rdx_meta_set_query(rdx_meta* h, const rdx_meta_leaf* leaves, int n_leaves, const int32_t* program, int n_ops);
+/* out_bits [ceil(rows/32)] = program AND base_bits (NULL = all rows; the caller's tombstones), bits past `rows` zero: the
+ * allow_bits of rdx_search / rdx_mask_create. `space` covers base_bits and out_bits. Every column the query names must hold
+ * exactly `rows` rows and a query must be set, else RDX_ERR_STATE (nothing is launched). RDX_DEVICE: one kernel enqueued on
+ * `stream`; nothing is synchronised or allocated and nothing crosses PCIe. RDX_HOST: complete on return. */
+int rdx_meta_filter(rdx_meta* h, int64_t rows, const uint32_t* base_bits, uint32_t* out_bits, int space, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

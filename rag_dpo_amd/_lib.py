@@ -20,6 +20,7 @@ PACKED_FLAGS = 4         # include/rdx.h RDX_PACKED_FLAGS: int32 words behind th
 RERANK_FEATURES = 8      # include/rdx.h RDX_RERANK_WORKSPACE_BYTES: output features per head workgroup
 DOCS_OP_NOT, DOCS_OP_AND, DOCS_OP_OR = -1, -2, -3   # include/rdx.h RDX_DOCS_OP_*
 DOCS_MAX_LEAVES = 1024   # include/rdx.h RDX_DOCS_MAX_LEAVES
+META_MAX_COLUMNS = 4096   # include/rdx.h RDX_META_MAX_COLUMNS (leaf ops, program ops and query limits: rag_dpo_amd/where_device.py)
 TOPIC_MAX_N, TOPIC_MAX_TOPICS, TOPIC_MAX_TAGS, TOPIC_MAX_DIM = 1024, 32, 64, 4096   # include/rdx.h rdx_topic_boost's limits
 
 
@@ -117,6 +118,14 @@ SYMBOLS = {
     "rdx_docs_set_query": (_i, [_vp, _vp, _vp, _i, _vp, _i]),
     "rdx_docs_contains": (_i, [_vp, _vp, _i, _vp]),
     "rdx_docs_filter": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "rdx_meta_create": (_i, [_i, ctypes.POINTER(_vp)]),
+    "rdx_meta_destroy": (_i, [_vp]),
+    "rdx_meta_set_rows": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _i64]),
+    "rdx_meta_drop_column": (_i, [_vp, _i]),
+    "rdx_meta_truncate": (_i, [_vp, _i64]),
+    "rdx_meta_stats": (_i, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "rdx_meta_set_query": (_i, [_vp, _vp, _i, _vp, _i]),
+    "rdx_meta_filter": (_i, [_vp, _i64, _vp, _vp, _i, _vp]),
 }
 
 

@@ -162,6 +162,11 @@ def build_lib(force: bool = False, verbose: bool = False, extra_flags=(), out: s
         if len(docs) < 4 or any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in docs.values()):
             raise RuntimeError("the where_document kernels (doc_kernel.hpp) spill or were not found — refused:\n" +
                                "\n".join(f"  {k}: {v}" for k, v in docs.items()))
+        meta = {k: v for k, v in res.items() if "k_meta" in k}
+        if len(meta) < 2 or any("spill_vgprs" not in v or "scratch_bytes" not in v for v in meta.values()) or \
+                any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in meta.values()):
+            raise RuntimeError("the `where` predicate kernels (meta_kernel.hpp) spill or were not found — refused:\n" +
+                               "\n".join(f"  {k}: {v}" for k, v in meta.items()))
         topic = {k: v for k, v in res.items() if "k_topic" in k}
         if len(topic) < 2 or any("spill_vgprs" not in v or "scratch_bytes" not in v for v in topic.values()) or \
                 any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in topic.values()):

@@ -14,6 +14,11 @@ Everything that crosses this boundary is plain Python lists/dicts/strs/floats, a
 about 15 levels of nesting (16 stack entries) raise ValueError on every engine. On a librdx engine the test runs on the GPU over a copy of the
 documents in HBM (engine.DocStore), built on the first where_document call and kept in step by every write after it; a
 collection that never filters by document allocates nothing for it. The copy is not persisted: it is rebuilt after a load.
+`query` / `query_device` evaluate a `where` they have not cached on the GPU as well, on a single-device librdx engine with at least
+_WHERE_DEVICE_MIN_ROWS rows: the filter is compiled (rag_dpo_amd/where_device.py) and one kernel computes the row bitmap from the
+metadata columns the filter names, kept in HBM (engine.MetaStore) from the first filter that names them and brought up to date
+with the host's columns before every evaluation. rag_dpo_amd/where.py is the model and remains the path of get / delete, of
+other engines, of smaller collections and of trees over the device's limits; results are the same on both. Not persisted.
 ids/documents/metadata stay on the host; embeddings go to the device index (`engine`). The engine is
 always librdx (rag_dpo_amd.engine.HipIndex): there is no CPU search path in this package.
 
@@ -139,6 +144,8 @@ class Collection:
         self._dir: Optional[str] = None        # set by PersistentClient: where the snapshot + journal live
         self._replaying = False
         self._doc_store = None                 # engine.DocStore: the documents in HBM, made by the first where_document call
+        self._meta_store = None                # engine.MetaStore: the metadata columns filters have named, made by the first `where`
+        self._meta_res: Dict[str, list] = {}   # key -> [slot in the store, rows [0, r) of the column that are on the device]
 
     # ---- small helpers ----------------------------------------------------------------------
     @property
@@ -156,6 +163,11 @@ class Collection:
         self._meta_cache.pop(row, None)
         if self._mask_cache:
             self._drop_masks()
+        if self._meta_res:                     # rows of resident columns changed in place: uploaded again from `row` on
+            for k in (self._meta_res if replace else (meta or ())):
+                ent = self._meta_res.get(k)
+                if ent is not None and row < ent[1]:
+                    ent[1] = row
         if replace:
             for col in self._cols.values():
                 col.kind[row] = W.K_MISSING
@@ -255,6 +267,75 @@ class Collection:
                 res.close()
         self._mask_cache.clear()
 
+    # ---- where on the device --------------------------------------------------------------------
+    # Below this many rows the host evaluator (0.1 ms at the reference's 16 919 rows) beats a set_query + launch + make_mask:
+    # the smallest size at which tools/where_bench.py measured the device path faster (DESIGN.md §16 names the run).
+    _WHERE_DEVICE_MIN_ROWS = 262_144
+
+    def _meta_close(self):
+        if self._meta_store is not None:
+            try:
+                self._meta_store.close()
+            except Exception:
+                pass
+        self._meta_store = None
+        self._meta_res = {}
+
+    def _where_device(self, where: Optional[dict]):
+        """`where` AND not deleted as a device bitmap (torch int32 [ceil(rows/32)]) computed by the predicate scan from the
+        metadata columns in HBM, or None = evaluate on the host: no filter, an engine without a device store or with several
+        devices, fewer rows than _WHERE_DEVICE_MIN_ROWS, a tree over the device's limits. The store (engine.MetaStore) is a
+        cache of self._cols, built lazily: a column is uploaded the first time a filter names it and follows the host here —
+        the tail added since, and everything from the lowest row a metadata update touched. If the device fails on the way
+        (out of memory for a column, a HIP error) the store is closed, the next filter rebuilds it, and THIS filter is
+        evaluated on the host as it was before there was a store: a failing cache never becomes the caller's error, and writes
+        never wait on it. A column stays resident from the first filter that names it until a compaction or the collection's
+        end: 9 bytes x rows per distinct key ever filtered on (the reference filters on a handful of keys)."""
+        eng, n = self._engine, self._rows
+        if where in (None, {}) or n == 0 or n < self._WHERE_DEVICE_MIN_ROWS or eng is None \
+                or not getattr(eng, "has_device_meta", False) or hasattr(eng, "devices"):
+            return None
+        from . import where_device as WV
+        prog = WV.compile_where(where, self._cols)     # raises what W.validate_where raises
+        if prog is None:
+            return None
+        from . import _lib as L
+        if len(set(self._meta_res) | set(prog.keys)) > L.META_MAX_COLUMNS:
+            return None
+        import torch
+        try:
+            if self._meta_store is None:
+                from .engine import MetaStore
+                self._meta_store, self._meta_res = MetaStore(eng.device), {}
+            st = self._meta_store
+            slots = []
+            for key in prog.keys:
+                ent = self._meta_res.get(key)
+                if ent is None:
+                    taken = {e[0] for e in self._meta_res.values()}
+                    ent = self._meta_res[key] = [next(s for s in range(len(taken) + 1) if s not in taken), 0]
+                if ent[1] < n:
+                    col, a = self._cols[key], ent[1]
+                    st.set_rows(ent[0], a, col.kind[a:n], col.num[a:n], col.code[a:n])
+                    ent[1] = n
+                slots.append(ent[0])
+            leaves = prog.leaves.copy()
+            named = leaves["col"] >= 0
+            leaves["col"][named] = np.asarray(slots, dtype=np.int32)[leaves["col"][named]]
+            st.set_query(leaves, prog.program)
+            dev = torch.device("cuda", st.device)
+            base = torch.from_numpy(W.pack_bits(self._alive[:n]).view(np.int32)).to(dev) if self._n_dead else None
+            out = torch.empty((n + 31) // 32, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                st.filter_device(n, out, base)
+            return out
+        except (RuntimeError, MemoryError):             # RdxError / torch's out-of-memory: the device's failure, not the filter's
+            self._meta_close()
+            return None
+        except Exception:
+            self._meta_close()
+            raise
+
     # ---- where_document ---------------------------------------------------------------------------
     def _docs_store(self):
         """the device document store (engines that have one: HipIndex, MultiDeviceIndex on its first device), built from
@@ -307,8 +388,10 @@ class Collection:
             import torch
             dev = torch.device("cuda", store.device)
             words = (self._rows + 31) // 32
-            base = self._mask(where)
-            base_t = torch.from_numpy(W.pack_bits(base).view(np.int32)).to(dev) if base is not None else None
+            base_t = self._where_device(where)       # the `where` half from the columns in HBM: nothing is packed or uploaded
+            if base_t is None:
+                base = self._mask(where)
+                base_t = torch.from_numpy(W.pack_bits(base).view(np.int32)).to(dev) if base is not None else None
             out = torch.empty(words, dtype=torch.int32, device=dev)
             leaves, prog = WD.compile_tree(where_document)
             store.set_query(leaves, prog)
@@ -331,12 +414,15 @@ class Collection:
             key = None                                  # not canonicalisable: W.evaluate will say what is wrong with it
         ent = self._mask_cache.get(key) if key is not None else None
         if ent is None:
-            m = self._mask(where)
-            if m is None:
-                return {}
-            bits = W.pack_bits(m)
-            res = self._engine.make_mask(bits) if hasattr(self._engine, "make_mask") else None
-            ent = (bits, res)
+            dev_bits = self._where_device(where)
+            if dev_bits is not None:                    # computed in HBM and handed to the resident mask there
+                ent = (None, self._engine.make_mask(dev_bits))
+            else:
+                m = self._mask(where)
+                if m is None:
+                    return {}
+                bits = W.pack_bits(m)
+                ent = (bits, self._engine.make_mask(bits) if hasattr(self._engine, "make_mask") else None)
             if key is not None:
                 if len(self._mask_cache) >= self._MASK_CACHE_MAX:
                     old = next(iter(self._mask_cache))          # oldest entry (insertion order)
@@ -384,6 +470,7 @@ class Collection:
         keep = np.flatnonzero(self._alive[:n])
         self._engine.compact(keep)
         self._docs_write(lambda st: st.compact(keep))
+        self._meta_close()                              # rows are renumbered: rebuilt by the next `where`
         self._ids = [self._ids[i] for i in keep]
         self._docs = [self._docs[i] for i in keep]
         self._cols = {k: c.take(keep) for k, c in self._cols.items()}
@@ -447,6 +534,7 @@ class Collection:
                 self._row_of[ids[i]] = row
                 self._alive[row] = True
                 self._set_meta(row, metadatas[i] if metadatas is not None else None, replace=False)
+            self._grow_cols(self._rows)   # a key first seen in this batch: its column is as long as the others (the rest is missing)
             self._docs_write(lambda st: st.append(self._docs[row0:]))
             self._log({"op": "add", "ids": [ids[i] for i in fresh],
                        "documents": None if documents is None else [documents[i] for i in fresh],
@@ -935,6 +1023,7 @@ class PersistentClient:
         if c._doc_store is not None:
             c._doc_store.close()
             c._doc_store = None
+        c._meta_close()
         if c._engine is not None and hasattr(c._engine, "close"):
             c._engine.close()
         if self.path:

@@ -1,4 +1,4 @@
-// rdx_host.hpp — what the host units of librdx (rdx_index.hip, rdx_enc.hip, rdx_bm25.hip, rdx_docs.hip) share: the error
+// rdx_host.hpp — what the host units of librdx (rdx_index.hip, rdx_enc.hip, rdx_bm25.hip, rdx_docs.hip, rdx_meta.hip) share: the error
 // string behind rdx_last_error(), the device / pinned buffers, and the wait on a word in pinned memory.
 #pragma once
 #include "../../include/rdx.h"
@@ -108,11 +108,11 @@ RDX_HOST_SHARED int grow_keep(DevBuf& b, size_t keep, size_t need, const char* w
     void* p = nullptr;
     hipError_t e = hipMalloc(&p, want);
     if (e != hipSuccess && want > need) e = hipMalloc(&p, want = need);
-    if (e != hipSuccess) return fail(RDX_ERR_NOMEM, std::string("rdx_docs: growing the ") + what + " to " + std::to_string(need) + " bytes: " + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(RDX_ERR_NOMEM, std::string("growing the ") + what + " to " + std::to_string(need) + " bytes: " + hipGetErrorString(e));
     if (keep > 0) e = hipMemcpy(p, b.p, keep, hipMemcpyDeviceToDevice);
     if (e != hipSuccess) {
         (void)hipFree(p);
-        return fail(RDX_ERR_HIP, std::string("rdx_docs: ") + hipGetErrorString(e));
+        return fail(RDX_ERR_HIP, std::string("growing the ") + what + ": " + hipGetErrorString(e));
     }
     b.release();
     b.p = p;

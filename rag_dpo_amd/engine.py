@@ -37,6 +37,7 @@ class ResidentMask:
 
 class HipIndex:
     has_device_docs = True   # Collection keeps a DocStore on this device for where_document
+    has_device_meta = True   # ... and a MetaStore for `where` (single-device collections)
 
     def __init__(self, dim: int, device: int = 0):
         self._lib = L.load(require_gpu=True)
@@ -338,6 +339,82 @@ class DocStore:
                 raise ValueError(f"expected a contiguous int32 tensor of {words} words on cuda:{self.device}")
         stream = HipIndex._raw_stream(out_bits.device)
         L.check(self._lib.rdx_docs_filter(self._h, ctypes.c_void_p(base_bits.data_ptr()) if base_bits is not None else None,
+                                          ctypes.c_void_p(out_bits.data_ptr()), L.RDX_DEVICE, ctypes.c_void_p(stream)))
+
+
+class MetaStore:
+    """Some of a collection's metadata columns resident in one device's HBM (include/rdx.h rdx_meta_*): the `where` predicate
+    scan. A column lives in a slot chosen by the caller; rows follow the collection's row order and the caller keeps them in
+    step (set_rows / drop_column / truncate). Nothing is allocated on the device before the first set_rows."""
+
+
+    def __init__(self, device: int = 0):
+        self._lib = L.load(require_gpu=True)
+        self._h = ctypes.c_void_p()
+        L.check(self._lib.rdx_meta_create(int(device), ctypes.byref(self._h)))
+        self.device = int(device)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.rdx_meta_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_rows(self, col: int, first_row: int, kind, num, code):
+        """rows [first_row, first_row + n) of slot `col` from where.Column's three arrays (kind int8 / uint8, num f64, code i32)"""
+        kind = np.ascontiguousarray(kind).view(np.uint8)
+        num = np.ascontiguousarray(num, dtype=np.float64)
+        code = np.ascontiguousarray(code, dtype=np.int32)
+        if not (kind.shape[0] == num.shape[0] == code.shape[0]):
+            raise ValueError("set_rows: kind, num and code must have one entry per row")
+        L.check(self._lib.rdx_meta_set_rows(self._h, int(col), int(first_row), _np_ptr(kind), _np_ptr(num), _np_ptr(code), kind.shape[0]))
+
+    def drop_column(self, col: int):
+        L.check(self._lib.rdx_meta_drop_column(self._h, int(col)))
+
+    def truncate(self, rows: int):
+        L.check(self._lib.rdx_meta_truncate(self._h, int(rows)))
+
+    def stats(self) -> dict:
+        c, b = ctypes.c_int64(), ctypes.c_int64()
+        L.check(self._lib.rdx_meta_stats(self._h, ctypes.byref(c), ctypes.byref(b)))
+        return {"columns": c.value, "bytes": b.value}
+
+    def set_query(self, leaves, program):
+        """leaves: a where_device.LEAF array (col = slot); program: postfix ops (include/rdx.h RDX_META_OP_*)"""
+        from .where_device import LEAF
+        lv = np.ascontiguousarray(leaves, dtype=LEAF)
+        prog = np.ascontiguousarray(program, dtype=np.int32)
+        L.check(self._lib.rdx_meta_set_query(self._h, _np_ptr(lv) if lv.shape[0] else None, lv.shape[0],
+                                             _np_ptr(prog) if prog.shape[0] else None, prog.shape[0]))
+
+    def filter(self, rows: int, base_bits: Optional[np.ndarray] = None) -> np.ndarray:
+        """-> uint32 [ceil(rows/32)]: program(leaves) AND base_bits (host in, host out)"""
+        words = (int(rows) + 31) // 32
+        out = np.zeros(words, dtype=np.uint32)
+        base = None
+        if base_bits is not None:
+            base = np.ascontiguousarray(base_bits, dtype=np.uint32)
+            if base.shape[0] != words:
+                raise ValueError("base_bits must hold ceil(rows/32) words")
+        L.check(self._lib.rdx_meta_filter(self._h, int(rows), _np_ptr(base) if base is not None else None, _np_ptr(out), L.RDX_HOST, None))
+        return out
+
+    def filter_device(self, rows: int, out_bits, base_bits=None):
+        """torch int32 tensors on the store's device, enqueued on the current torch stream: nothing crosses PCIe"""
+        import torch
+        words = (int(rows) + 31) // 32
+        for t in (out_bits, base_bits):
+            if t is not None and (not t.is_cuda or t.device.index != self.device or t.dtype != torch.int32
+                                  or t.numel() != words or not t.is_contiguous()):
+                raise ValueError(f"expected a contiguous int32 tensor of {words} words on cuda:{self.device}")
+        stream = HipIndex._raw_stream(out_bits.device)
+        L.check(self._lib.rdx_meta_filter(self._h, int(rows), ctypes.c_void_p(base_bits.data_ptr()) if base_bits is not None else None,
                                           ctypes.c_void_p(out_bits.data_ptr()), L.RDX_DEVICE, ctypes.c_void_p(stream)))
 
 

@@ -1,0 +1,136 @@
+"""Chroma `where` compiled for the device predicate scan (include/rdx.h rdx_meta_*, csrc/meta_kernel.hpp).
+
+rag_dpo_amd/where.py is the model and stays the host path; this module lowers a validated filter into what the kernel runs:
+a table of leaves (one typed comparison against one column each) and a postfix program over them.
+
+    {k: v}, {k: {"$eq": v}}          one EQ leaf
+    {k: {"$ne": v}}                  EQ, NOT
+    {k: {"$in": [a, b, ...]}}        EQ a, EQ b, OR, ...        ("$nin": the same, then NOT)
+    {k: {"$gt" | "$gte" | "$lt" | "$lte": v}}   one GT / GE / LT / LE leaf
+    {"$and" | "$or": [x, y, z, ...]}  x y AND z AND ...          (a left chain, as where._eval folds them)
+
+A leaf is true for a row iff the row's kind equals the operand's kind and the comparison holds between doubles; a string operand
+is its code in the column's vocabulary, or -2 when the column has never held that string (Column._eq's own code: no row has it).
+A key that no row has is CONST0 under the positive operators and CONST1 under $ne / $nin, as where._eval answers today.
+
+A tree that needs more than 1024 leaves, 4096 program ops or 16 stack entries is not an error: compile_where returns None and
+the caller evaluates it on the host, where any size works.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import where as W
+
+EQ, GT, GE, LT, LE, CONST0, CONST1 = range(7)    # include/rdx.h RDX_META_*
+OP_NOT, OP_AND, OP_OR = -1, -2, -3               # include/rdx.h RDX_META_OP_*
+MAX_LEAVES, MAX_OPS, MAX_STACK = 1024, 4096, 16
+LEAF = np.dtype([("col", "<i4"), ("op", "<i4"), ("kind", "<i4"), ("code", "<i4"), ("num", "<f8")])   # rdx_meta_leaf
+_CMP = {"$gt": GT, "$gte": GE, "$lt": LT, "$lte": LE}
+
+
+class Compiled(NamedTuple):
+    leaves: np.ndarray        # LEAF [n_leaves]; col = index into keys (-1 for CONST0 / CONST1)
+    program: np.ndarray       # int32 [n_ops], postfix
+    keys: Tuple[str, ...]     # the column keys the filter needs, in order of first use
+
+
+class _TooBig(Exception):
+    pass
+
+
+def compile_where(where: dict, columns: Dict[str, W.Column]) -> Optional[Compiled]:
+    """-> Compiled, or None when the tree exceeds the device's limits. Raises what W.validate_where raises."""
+    W.validate_where(where)
+    leaves: List[tuple] = []
+    prog: List[int] = []
+    keys: Dict[str, int] = {}
+
+    def leaf(key, op, v):
+        if len(leaves) >= MAX_LEAVES:
+            raise _TooBig
+        col = columns[key]
+        k = W.kind_of(v)
+        if k == W.K_STR:
+            leaves.append((keys.setdefault(key, len(keys)), op, k, col._lookup.get(v, -2), 0.0))
+        else:
+            leaves.append((keys.setdefault(key, len(keys)), op, k, -1, float(v)))
+        prog.append(len(leaves) - 1)
+
+    def const(value: bool):
+        if len(leaves) >= MAX_LEAVES:
+            raise _TooBig
+        leaves.append((-1, CONST1 if value else CONST0, 0, -1, 0.0))
+        prog.append(len(leaves) - 1)
+
+    def emit(w):
+        (key, val), = w.items()
+        if key in ("$and", "$or"):
+            emit(val[0])
+            for x in val[1:]:
+                emit(x)
+                prog.append(OP_AND if key == "$and" else OP_OR)
+            return
+        if isinstance(val, dict):
+            (op, operand), = val.items()
+        else:
+            op, operand = "$eq", val
+        if key not in columns:
+            const(op in ("$ne", "$nin"))
+            return
+        if op in ("$eq", "$ne"):
+            leaf(key, EQ, operand)
+        elif op in ("$in", "$nin"):
+            leaf(key, EQ, operand[0])
+            for x in operand[1:]:
+                leaf(key, EQ, x)
+                prog.append(OP_OR)
+        else:
+            leaf(key, _CMP[op], operand)
+        if op in ("$ne", "$nin"):
+            prog.append(OP_NOT)
+        if len(prog) > MAX_OPS:
+            raise _TooBig
+
+    try:
+        emit(where)
+    except (_TooBig, RecursionError):
+        return None
+    if len(prog) > MAX_OPS:
+        return None
+    depth = 0
+    for op in prog:
+        depth += 1 if op >= 0 else (0 if op == OP_NOT else -1)
+        if depth > MAX_STACK:
+            return None
+    return Compiled(np.array(leaves, dtype=LEAF), np.array(prog, dtype=np.int32), tuple(keys))
+
+
+def run_program_host(leaves: np.ndarray, program: Sequence[int], columns: Sequence[W.Column], n: int) -> np.ndarray:
+    """bool[n]: the compiled form interpreted with numpy the way k_meta_filter runs it (columns[i] = the column of leaves whose
+    col is i). The compiler's test without a GPU, and the statement of what the kernel computes."""
+    pay = {}
+    stack: List[np.ndarray] = []
+    for op in np.asarray(program).tolist():
+        if op >= 0:
+            lf = leaves[op]
+            lop, c = int(lf["op"]), int(lf["col"])
+            if lop in (CONST0, CONST1):
+                stack.append(np.full(n, lop == CONST1, dtype=bool))
+                continue
+            col = columns[c]
+            if c not in pay:    # the device payload: (double)code for str rows, the number otherwise
+                pay[c] = np.where(col.kind[:n] == W.K_STR, col.code[:n].astype(np.float64), col.num[:n])
+            x = pay[c]
+            v = np.float64(lf["code"]) if int(lf["kind"]) == W.K_STR else np.float64(lf["num"])
+            cmp = (x == v) if lop == EQ else (x > v) if lop == GT else (x >= v) if lop == GE else (x < v) if lop == LT else (x <= v)
+            stack.append((col.kind[:n] == int(lf["kind"])) & cmp)
+        elif op == OP_NOT:
+            stack.append(~stack.pop())
+        else:
+            b, a = stack.pop(), stack.pop()
+            stack.append((a & b) if op == OP_AND else (a | b))
+    assert len(stack) == 1
+    return stack[0]
