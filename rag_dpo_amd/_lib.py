@@ -18,9 +18,12 @@ RDX_HOST, RDX_DEVICE = 0, 1
 ABI_VERSION = 3          # include/rdx.h RDX_ABI_VERSION
 PACKED_FLAGS = 4         # include/rdx.h RDX_PACKED_FLAGS: int32 words behind the counts of a packed partial
 RERANK_FEATURES = 8      # include/rdx.h RDX_RERANK_WORKSPACE_BYTES: output features per head workgroup
-DOCS_OP_NOT, DOCS_OP_AND, DOCS_OP_OR = -1, -2, -3   # include/rdx.h RDX_DOCS_OP_*
+# the postfix filter programs of rdx_docs_set_query and rdx_meta_set_query (where_document.py and where_device.py compile them):
+OP_NOT, OP_AND, OP_OR = -1, -2, -3   # include/rdx.h RDX_DOCS_OP_* = RDX_META_OP_*
+MAX_OPS, MAX_STACK = 4096, 16        # include/rdx.h: at most 4096 ops and 16 stack entries
+DOCS_OP_NOT, DOCS_OP_AND, DOCS_OP_OR = OP_NOT, OP_AND, OP_OR
 DOCS_MAX_LEAVES = 1024   # include/rdx.h RDX_DOCS_MAX_LEAVES
-META_MAX_COLUMNS = 4096   # include/rdx.h RDX_META_MAX_COLUMNS (leaf ops, program ops and query limits: rag_dpo_amd/where_device.py)
+META_MAX_COLUMNS = 4096   # include/rdx.h RDX_META_MAX_COLUMNS (leaf ops and the leaf limit: rag_dpo_amd/where_device.py)
 TOPIC_MAX_N, TOPIC_MAX_TOPICS, TOPIC_MAX_TAGS, TOPIC_MAX_DIM = 1024, 32, 64, 4096   # include/rdx.h rdx_topic_boost's limits
 
 

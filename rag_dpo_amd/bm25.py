@@ -35,6 +35,9 @@ from typing import Callable, Dict, List, Optional, Sequence, Set
 
 import numpy as np
 
+from . import _lib as L
+from .engine import _Handle
+
 logger = logging.getLogger(__name__)
 
 K1, B, EPSILON = 1.5, 0.75, 0.25
@@ -129,13 +132,12 @@ def idf_of(n_rows: int, nd: np.ndarray):
     return out, average_idf
 
 
-class HipBm25:
+class HipBm25(_Handle):
     """one BM25 index in one MI355X's HBM, driven through include/rdx.h. No arithmetic happens in this class."""
+    _destroy = "rdx_bm25_destroy"
 
     def __init__(self, arrays: Bm25Arrays, device: int = 0):
-        from . import _lib as L
-        self._L = L
-        self._lib = L.load(require_gpu=True)
+        out = self._new_handle()
         self.device = int(device)
         a = arrays
         self.n_groups = int(a.n_groups)
@@ -144,16 +146,13 @@ class HipBm25:
                       np.ascontiguousarray(a.denom, np.float64)]
         grp = np.ascontiguousarray(a.row_group, np.int32) if a.row_group is not None else None
         p = [ctypes.c_void_p(x.ctypes.data) for x in self._keep]
-        self._h = ctypes.c_void_p()
         L.check(self._lib.rdx_bm25_create(self.device, int(a.n_rows), int(len(a.idf)), *p,
-                                          ctypes.c_void_p(grp.ctypes.data) if grp is not None else None, int(a.n_groups),
-                                          ctypes.byref(self._h)))
+                                          ctypes.c_void_p(grp.ctypes.data) if grp is not None else None, int(a.n_groups), out))
         self._keep = None   # copied to the device
 
     def search(self, term_offsets: np.ndarray, term_ids: np.ndarray, k: int, allow_bits: Optional[np.ndarray] = None):
         """-> scores f64 [nq, k], rows int64 [nq, k], counts int32 [nq]; on torch's current stream of the index's device"""
         import torch
-        L = self._L
         off = np.ascontiguousarray(term_offsets, np.int64)
         ids = np.ascontiguousarray(term_ids, np.int32)
         nq = off.shape[0] - 1
@@ -169,17 +168,6 @@ class HipBm25:
                                           ctypes.c_void_p(sc.ctypes.data), ctypes.c_void_p(ro.ctypes.data),
                                           ctypes.c_void_p(cn.ctypes.data), L.RDX_HOST, ctypes.c_void_p(stream)))
         return sc, ro, cn
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.rdx_bm25_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _default_engine_factory(arrays: Bm25Arrays, device: int):

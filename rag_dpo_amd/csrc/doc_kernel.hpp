@@ -29,10 +29,7 @@ constexpr int DOC_THREADS = 256;
 constexpr int DOC_WAVES = DOC_THREADS / 64;
 constexpr int DOC_EXT_CHUNKS = DOC_STAGE_MAX / 16;              // overlap chunks behind a segment (bytes up to 1023 + 255)
 constexpr int DOC_CHUNKS = DOC_SEG / 16 + DOC_EXT_CHUNKS;       // 80 x 16 B of LDS per wave
-constexpr int DOC_MAX_STACK = 16;
-constexpr int DOC_MAX_OPS = 4096;
 constexpr int DOC_EVAL_THREADS = 256;
-constexpr int32_t DOC_OP_NOT = -1, DOC_OP_AND = -2, DOC_OP_OR = -3;   // include/rdx.h RDX_DOCS_OP_*
 
 // one leaf as the scan sees it: bytes pat[off, off + len); prefix / pmask = its first min(len, 4) bytes (little-endian)
 struct DocLeaf {
@@ -152,12 +149,13 @@ __global__ __launch_bounds__(DOC_THREADS) void k_docs_contains_long(const uint8_
 }
 
 // out[w] = program(leaf bitmaps)[w] & base[w] (base may be null); bits past `rows` cleared. The program was checked on the
-// host: every op is a leaf index < P or one of DOC_OP_*, the stack never underflows, never exceeds DOC_MAX_STACK, ends at 1.
+// host (check_program, rdx_store.hpp): every op is a leaf index < P or OP_NOT / OP_AND / OP_OR, the stack never underflows, never
+// exceeds FILTER_MAX_STACK, ends at 1.
 __global__ __launch_bounds__(DOC_EVAL_THREADS) void k_docs_eval(const uint32_t* __restrict__ leaf_bits, int64_t words, int64_t rows,
                                                                 const int32_t* __restrict__ prog, int n_ops, const uint32_t* __restrict__ base,
                                                                 uint32_t* __restrict__ out) {
-    __shared__ int32_t s_prog[DOC_MAX_OPS];
-    __shared__ uint32_t s_stack[DOC_MAX_STACK - 1][DOC_EVAL_THREADS];   // below the top, which stays in a register
+    __shared__ int32_t s_prog[FILTER_MAX_OPS];
+    __shared__ uint32_t s_stack[FILTER_MAX_STACK - 1][DOC_EVAL_THREADS];   // below the top, which stays in a register
     for (int i = threadIdx.x; i < n_ops; i += DOC_EVAL_THREADS) s_prog[i] = prog[i];
     __syncthreads();
     const int t = threadIdx.x;
@@ -170,11 +168,11 @@ __global__ __launch_bounds__(DOC_EVAL_THREADS) void k_docs_eval(const uint32_t* 
         if (op >= 0) {
             if (i > 0) s_stack[sp++][t] = top;
             top = leaf_bits[(int64_t)op * words + wd];
-        } else if (op == DOC_OP_NOT) {
+        } else if (op == OP_NOT) {
             top = ~top;
         } else {
             const uint32_t b = s_stack[--sp][t];
-            top = op == DOC_OP_AND ? (b & top) : (b | top);
+            top = op == OP_AND ? (b & top) : (b | top);
         }
     }
     if (base) top &= base[wd];

@@ -18,7 +18,7 @@
 //     and the program then runs on those bits;
 //   otherwise the leaves are tested in program order: once per run of leaves on one column (a `$in` of any length is one
 //     run); a column named again later is loaded again (from the caches).
-// The boolean stack is one 32-bit register per row (bit 0 = top, at most META_MAX_STACK entries). Each 64 verdicts become one
+// The boolean stack is one 32-bit register per row (bit 0 = top, at most FILTER_MAX_STACK entries). Each 64 verdicts become one
 // ballot; lanes 0 .. 2 META_ROWS - 1 store the ballots' halves (ANDed with base_bits) with plain vector stores: every output
 // word has exactly one writer, so no atomics and no dependence on the schedule. Rows past `rows` vote 0: the tail bits are zero.
 #pragma once
@@ -29,10 +29,7 @@ namespace rdx {
 constexpr int META_THREADS = 256;
 constexpr int META_ROWS = 4;                 // rows per lane and pass: a wave takes 256 consecutive rows, four loads in flight per column
 constexpr int META_MAX_LEAVES = 1024;
-constexpr int META_MAX_OPS = 4096;
-constexpr int META_MAX_STACK = 16;
 constexpr int META_SORTED_LEAVES = 64;
-constexpr int32_t META_OP_NOT = -1, META_OP_AND = -2, META_OP_OR = -3;           // include/rdx.h RDX_META_OP_*
 constexpr int32_t META_EQ = 0, META_GT = 1, META_GE = 2, META_LT = 3, META_LE = 4, META_CONST0 = 5, META_CONST1 = 6;
 
 struct MetaLeaf {      // include/rdx.h rdx_meta_leaf, with num = (double)code for a str leaf and col = -1 for a CONST leaf
@@ -82,18 +79,18 @@ __device__ __forceinline__ void meta_test(int32_t op, int32_t kind, double num, 
 __device__ __forceinline__ void meta_fold(int32_t op, uint32_t (&st)[META_ROWS]) {
 #pragma unroll
     for (int u = 0; u < META_ROWS; ++u) {
-        if (op == META_OP_NOT) {
+        if (op == OP_NOT) {
             st[u] ^= 1u;
         } else {
             const uint32_t a = st[u] & 1u;
             st[u] >>= 1;
-            st[u] = op == META_OP_AND ? (st[u] & (a | ~1u)) : (st[u] | a);
+            st[u] = op == OP_AND ? (st[u] & (a | ~1u)) : (st[u] | a);
         }
     }
 }
 
-// The query was checked on the host (rdx_meta_set_query): every program op is a leaf index < n_leaves or one of META_OP_*,
-// the stack never underflows, never exceeds META_MAX_STACK and ends at one entry; every leaf's col is -1 or a column of
+// The query was checked on the host (rdx_meta_set_query; the program by check_program, rdx_store.hpp): every program op is a leaf
+// index < n_leaves or OP_NOT / OP_AND / OP_OR, the stack never underflows, never exceeds FILTER_MAX_STACK and ends at one entry; every leaf's col is -1 or a column of
 // exactly `rows` rows. words = ceil(rows / 32); base may be null.
 template <bool SORTED>
 __global__ __launch_bounds__(META_THREADS) void k_meta_filter(const MetaCol* __restrict__ cols, const MetaLeaf* __restrict__ leaves,

@@ -31,6 +31,13 @@ constexpr int BK = 64;                            // k elements per k-step image
 constexpr int KSTEP_BYTES = TILE_ROWS * BK * 2;   // 32 KiB
 constexpr int MAX_DIM = 4096;
 
+// The postfix filter programs of where_document (k_docs_eval, doc_kernel.hpp) and `where` (k_meta_filter, meta_kernel.hpp): one
+// format, two machines. An op >= 0 pushes leaf op; the rest work on the top of the stack (include/rdx.h RDX_DOCS_OP_* = RDX_META_OP_*).
+// check_program (rdx_store.hpp) holds every program to the two limits before a kernel sees it.
+constexpr int32_t OP_NOT = -1, OP_AND = -2, OP_OR = -3;
+constexpr int FILTER_MAX_STACK = 16;
+constexpr int FILTER_MAX_OPS = 4096;
+
 // offset (in halfs) of element (row r, column k) inside the fragment-ordered corpus scan copy
 __host__ __device__ inline int64_t corpus_off(int64_t r, int k, int ksteps) {
     // 16x16x32 A operand: chunk (rb, c = k/32, m = row half): lane l = row m*16 + (l & 15), k = c*32 + 8*(l >> 4) + 0..7

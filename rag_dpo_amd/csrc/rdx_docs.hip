@@ -1,7 +1,7 @@
-// rdx_docs.hip — the document store and where_document (rdx_docs_*) of include/rdx.h.
-#include "rdx_host.hpp"
+// rdx_docs.hip — the document store and where_document (rdx_docs_*) of include/rdx.h. What it has in common with the metadata
+// store (rdx_meta.hip) is in rdx_store.hpp: StoreBase (device, stream, last-use event, lock), check_program and BitmapStage.
+#include "rdx_store.hpp"
 
-#include <mutex>
 #include <vector>
 
 #include "doc_kernel.hpp"
@@ -11,8 +11,7 @@ using namespace rdx;
 // ------------------------------------------------------------------------------------------------
 // document store and where_document (doc_kernel.hpp): the rows' UTF-8 text in HBM, scanned for substrings
 // ------------------------------------------------------------------------------------------------
-struct rdx_docs {
-    int device = 0;
+struct rdx_docs : StoreBase {
     int64_t rows = 0;
     int64_t used = 0;                  // arena bytes holding text (current and replaced), in front of the DOC_TAIL zero bytes
     int64_t live = 0;                  // padded bytes of the rows' current text
@@ -27,9 +26,6 @@ struct rdx_docs {
     int n_leaves = 0, n_short = 0, n_long = 0, n_ops = 0;
     std::vector<int> pass_ext;         // per pass of k_docs_contains: overlap chunks its longest pattern needs
     DevBuf pat, leaves, prog, leaf_bits, tmp_in, tmp_out;
-    hipStream_t own_stream = nullptr;
-    hipEvent_t last_use = nullptr;     // recorded behind the last kernel that read the store: writes and re-allocations wait for it
-    std::mutex mu;
 };
 
 static int64_t doc_pad(int64_t n) { return (n + DOC_ALIGN - 1) & ~(int64_t)(DOC_ALIGN - 1); }
@@ -45,12 +41,6 @@ static int check_offsets(const char* who, const uint8_t* bytes, const int64_t* o
                                              " (entry " + std::to_string(i) + " has length " + std::to_string(l) + ")");
     }
     if (off[n] > 0 && !bytes) return fail(RDX_ERR_INVALID, std::string(who) + ": null bytes");
-    return RDX_OK;
-}
-
-static int docs_wait(rdx_docs* h) {
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipEventSynchronize(h->last_use));
     return RDX_OK;
 }
 
@@ -152,20 +142,14 @@ static int docs_sync(rdx_docs* h) {
 extern "C" int rdx_docs_create(int device, rdx_docs** out) {
     if (!out) return fail(RDX_ERR_INVALID, "rdx_docs_create: null out pointer");
     *out = nullptr;
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev)
-        return fail(RDX_ERR_INVALID, "rdx_docs_create: device " + std::to_string(device) + " out of range (" + std::to_string(ndev) + " visible)");
-    HIP_TRY(hipSetDevice(device));
+    RDX_TRY(check_device("rdx_docs_create: ", device));
     rdx_docs* h = new rdx_docs();
-    h->device = device;
-    int rc = h->arena.ensure(DOC_TAIL);
-    hipError_t e = hipSuccess;
-    if (rc == RDX_OK) e = hipMemset(h->arena.p, 0, DOC_TAIL);
-    if (rc == RDX_OK && e == hipSuccess) e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-    if (rc == RDX_OK && e == hipSuccess) e = hipEventCreateWithFlags(&h->last_use, hipEventDisableTiming);
-    if (rc == RDX_OK && e == hipSuccess) e = hipEventRecord(h->last_use, h->own_stream);
-    if (rc == RDX_OK && e != hipSuccess) rc = fail(RDX_ERR_HIP, std::string("rdx_docs_create: ") + hipGetErrorString(e));
+    int rc = h->open("rdx_docs_create", device);
+    if (rc == RDX_OK) rc = h->arena.ensure(DOC_TAIL);
+    if (rc == RDX_OK) {
+        const hipError_t e = hipMemset(h->arena.p, 0, DOC_TAIL);
+        if (e != hipSuccess) rc = fail(RDX_ERR_HIP, std::string("rdx_docs_create: ") + hipGetErrorString(e));
+    }
     if (rc != RDX_OK) {
         rdx_docs_destroy(h);
         return rc;
@@ -176,15 +160,7 @@ extern "C" int rdx_docs_create(int device, rdx_docs** out) {
 
 extern "C" int rdx_docs_destroy(rdx_docs* h) {
     if (!h) return RDX_OK;
-    (void)hipSetDevice(h->device);
-    if (h->last_use) {
-        (void)hipEventSynchronize(h->last_use);
-        (void)hipEventDestroy(h->last_use);
-    }
-    if (h->own_stream) {
-        (void)hipStreamSynchronize(h->own_stream);
-        (void)hipStreamDestroy(h->own_stream);
-    }
+    h->close();
     delete h;
     return RDX_OK;
 }
@@ -195,7 +171,7 @@ extern "C" int rdx_docs_append(rdx_docs* h, const uint8_t* bytes, const int64_t*
     if (!h) return fail(RDX_ERR_INVALID, "rdx_docs_append: null store");
     if (h->rows + n > INT32_MAX) return fail(RDX_ERR_INVALID, "rdx_docs_append: more than 2^31 - 1 rows");
     std::lock_guard<std::mutex> lk(h->mu);
-    RDX_TRY(docs_wait(h));
+    RDX_TRY(h->wait());
     std::vector<int64_t> at;
     RDX_TRY(docs_write_tail(h, bytes, offsets, n, at));
     for (int64_t i = 0; i < n; ++i) {
@@ -215,7 +191,7 @@ extern "C" int rdx_docs_replace(rdx_docs* h, const int64_t* row_ids, const uint8
     for (int64_t i = 0; i < n; ++i)
         if (row_ids[i] < 0 || row_ids[i] >= h->rows)
             return fail(RDX_ERR_INVALID, "rdx_docs_replace: row id " + std::to_string(row_ids[i]) + " out of range [0, " + std::to_string(h->rows) + ")");
-    RDX_TRY(docs_wait(h));
+    RDX_TRY(h->wait());
     std::vector<int64_t> at;
     RDX_TRY(docs_write_tail(h, bytes, offsets, n, at));
     for (int64_t i = 0; i < n; ++i) {
@@ -240,7 +216,7 @@ extern "C" int rdx_docs_compact(rdx_docs* h, const int64_t* keep, int64_t n_keep
         if (keep[i] < 0 || keep[i] >= h->rows) return fail(RDX_ERR_INVALID, "rdx_docs_compact: row id out of range");
         if (i > 0 && keep[i] <= keep[i - 1]) return fail(RDX_ERR_INVALID, "rdx_docs_compact: keep list must be strictly ascending");
     }
-    RDX_TRY(docs_wait(h));
+    RDX_TRY(h->wait());
     return docs_rewrite(h, std::vector<int64_t>(keep, keep + n_keep));
 }
 
@@ -257,21 +233,12 @@ extern "C" int rdx_docs_set_query(rdx_docs* h, const uint8_t* pat_bytes, const i
         return fail(RDX_ERR_INVALID, "rdx_docs_set_query: P must be in [1, " + std::to_string(RDX_DOCS_MAX_LEAVES) + "] (got " + std::to_string(P) + ")");
     if (!pat_bytes) return fail(RDX_ERR_INVALID, "rdx_docs_set_query: null pattern bytes");
     RDX_TRY(check_offsets("rdx_docs_set_query", pat_bytes, pat_off, P, true));
-    if (n_ops < 0 || n_ops > DOC_MAX_OPS || (n_ops > 0 && !program))
-        return fail(RDX_ERR_INVALID, "rdx_docs_set_query: need 0 <= n_ops <= " + std::to_string(DOC_MAX_OPS) + " and a program when n_ops > 0");
-    int depth = 0;
-    for (int i = 0; i < n_ops; ++i) {
-        const int32_t op = program[i];
-        if (op >= P || op < RDX_DOCS_OP_OR) return fail(RDX_ERR_INVALID, "rdx_docs_set_query: op " + std::to_string(i) + " is neither a leaf < P nor NOT / AND / OR");
-        const int need = op >= 0 ? 0 : (op == RDX_DOCS_OP_NOT ? 1 : 2);
-        if (depth < need) return fail(RDX_ERR_INVALID, "rdx_docs_set_query: op " + std::to_string(i) + " pops an empty stack");
-        depth += op >= 0 ? 1 : (op == RDX_DOCS_OP_NOT ? 0 : -1);
-        if (depth > DOC_MAX_STACK) return fail(RDX_ERR_INVALID, "rdx_docs_set_query: the program needs more than " + std::to_string(DOC_MAX_STACK) + " stack entries");
-    }
-    if (n_ops > 0 && depth != 1) return fail(RDX_ERR_INVALID, "rdx_docs_set_query: the program must leave exactly one value");
+    if (n_ops < 0 || n_ops > FILTER_MAX_OPS || (n_ops > 0 && !program))
+        return fail(RDX_ERR_INVALID, "rdx_docs_set_query: need 0 <= n_ops <= " + std::to_string(FILTER_MAX_OPS) + " and a program when n_ops > 0");
+    RDX_TRY(check_program("rdx_docs_set_query: ", "P", program, n_ops, P));
     if (!h) return fail(RDX_ERR_INVALID, "rdx_docs_set_query: null store");
     std::lock_guard<std::mutex> lk(h->mu);
-    RDX_TRY(docs_wait(h));
+    RDX_TRY(h->wait());
     std::vector<DocLeaf> shorts, longs;
     for (int p = 0; p < P; ++p) {
         DocLeaf lf;
@@ -333,43 +300,30 @@ static int docs_run_leaves(rdx_docs* h, hipStream_t st) {
 
 extern "C" int rdx_docs_contains(rdx_docs* h, uint32_t* out_bits, int space, void* stream) {
     if (!h || !out_bits) return fail(RDX_ERR_INVALID, "rdx_docs_contains: null pointer");
-    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    RDX_TRY(check_space(space));
     std::lock_guard<std::mutex> lk(h->mu);
-    RDX_TRY(docs_wait(h));
-    hipStream_t st = space == RDX_HOST ? h->own_stream : (hipStream_t)stream;
+    RDX_TRY(h->wait());
+    hipStream_t st = h->stream_for(space, stream);
     RDX_TRY(docs_run_leaves(h, st));
     const size_t bytes = (size_t)h->n_leaves * (size_t)((h->rows + 31) / 32) * 4;
     if (bytes) HIP_TRY(hipMemcpyAsync(out_bits, h->leaf_bits.p, bytes, space == RDX_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipEventRecord(h->last_use, st));
-    if (space == RDX_HOST) HIP_TRY(hipStreamSynchronize(st));
-    return RDX_OK;
+    return h->finish(space, st);
 }
 
 extern "C" int rdx_docs_filter(rdx_docs* h, const uint32_t* base_bits, uint32_t* out_bits, int space, void* stream) {
     if (!h || !out_bits) return fail(RDX_ERR_INVALID, "rdx_docs_filter: null pointer");
-    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    RDX_TRY(check_space(space));
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->n_ops == 0) return fail(RDX_ERR_STATE, "rdx_docs_filter: the query has no program (rdx_docs_set_query with n_ops > 0)");
-    RDX_TRY(docs_wait(h));
-    hipStream_t st = space == RDX_HOST ? h->own_stream : (hipStream_t)stream;
-    const int64_t words = (h->rows + 31) / 32;
-    const uint32_t* base = base_bits;
-    uint32_t* out = out_bits;
-    if (space == RDX_HOST) {
-        RDX_TRY(h->tmp_in.ensure((size_t)std::max<int64_t>(words, 1) * 4));
-        RDX_TRY(h->tmp_out.ensure((size_t)std::max<int64_t>(words, 1) * 4));
-        if (base_bits && words) HIP_TRY(hipMemcpyAsync(h->tmp_in.p, base_bits, (size_t)words * 4, hipMemcpyHostToDevice, st));
-        base = base_bits ? h->tmp_in.as<uint32_t>() : nullptr;
-        out = h->tmp_out.as<uint32_t>();
-    }
-    RDX_TRY(docs_run_leaves(h, st));
+    RDX_TRY(h->wait());
+    const int64_t words = (h->rows + 31) / 32;   // 0: nothing is copied or launched, the event is still recorded
+    BitmapStage g;
+    RDX_TRY(g.begin(*h, space, stream, words, base_bits, out_bits, h->tmp_in, h->tmp_out));
+    RDX_TRY(docs_run_leaves(h, g.st));
     if (words) {
-        hipLaunchKernelGGL(k_docs_eval, dim3((unsigned)((words + DOC_EVAL_THREADS - 1) / DOC_EVAL_THREADS)), dim3(DOC_EVAL_THREADS), 0, st,
-                           h->leaf_bits.as<uint32_t>(), words, h->rows, h->prog.as<int32_t>(), h->n_ops, base, out);
+        hipLaunchKernelGGL(k_docs_eval, dim3((unsigned)((words + DOC_EVAL_THREADS - 1) / DOC_EVAL_THREADS)), dim3(DOC_EVAL_THREADS), 0, g.st,
+                           h->leaf_bits.as<uint32_t>(), words, h->rows, h->prog.as<int32_t>(), h->n_ops, g.base, g.out);
         HIP_TRY(hipGetLastError());
-        if (space == RDX_HOST) HIP_TRY(hipMemcpyAsync(out_bits, out, (size_t)words * 4, hipMemcpyDeviceToHost, st));
     }
-    HIP_TRY(hipEventRecord(h->last_use, st));
-    if (space == RDX_HOST) HIP_TRY(hipStreamSynchronize(st));
-    return RDX_OK;
+    return g.end(*h, space, words, out_bits);
 }

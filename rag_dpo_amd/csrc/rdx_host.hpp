@@ -1,5 +1,6 @@
 // rdx_host.hpp — what the host units of librdx (rdx_index.hip, rdx_enc.hip, rdx_bm25.hip, rdx_docs.hip, rdx_meta.hip) share: the error
-// string behind rdx_last_error(), the device / pinned buffers, and the wait on a word in pinned memory.
+// string behind rdx_last_error(), the checks of `space` and `device`, the device / pinned buffers, and the wait on a word in pinned
+// memory. What only the row-filter stores share (rdx_docs.hip, rdx_meta.hip) is in rdx_store.hpp.
 #pragma once
 #include "../../include/rdx.h"
 
@@ -43,6 +44,21 @@ RDX_HOST_SHARED int fail(int code, const std::string& msg) {
         int _r = (expr);           \
         if (_r != RDX_OK) return _r; \
     } while (0)
+
+// the `space` argument of every entry point whose pointers may live on either side
+RDX_HOST_SHARED int check_space(int space) {
+    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    return RDX_OK;
+}
+
+// the `device` argument of a *_create; prefix = "" or "rdx_x_create: "
+RDX_HOST_SHARED int check_device(const char* prefix, int device) {
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev)
+        return fail(RDX_ERR_INVALID, std::string(prefix) + "device " + std::to_string(device) + " out of range (" + std::to_string(ndev) + " visible)");
+    return RDX_OK;
+}
 
 // grow-only device buffer
 struct DevBuf {

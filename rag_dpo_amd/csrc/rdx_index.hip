@@ -1002,10 +1002,7 @@ static int check_dim(int dim) {
 extern "C" int rdx_index_create(int device, int dim, rdx_index** out) {
     if (!out) return fail(RDX_ERR_INVALID, "rdx_index_create: null out pointer");
     RDX_TRY(check_dim(dim));
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev)
-        return fail(RDX_ERR_INVALID, "device " + std::to_string(device) + " out of range (" + std::to_string(ndev) + " visible)");
+    RDX_TRY(check_device("", device));
     HIP_TRY(hipSetDevice(device));
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -1179,7 +1176,7 @@ static int ingest(rdx_index* h, const void* rows, bool is_bf16, int64_t n, int s
 
 static int add_impl(rdx_index* h, const void* rows, bool is_bf16, int64_t n, int space, bool verbatim = false) {
     if (!h || (n > 0 && !rows) || n < 0) return fail(RDX_ERR_INVALID, "rdx_index_add: bad argument");
-    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    RDX_TRY(check_space(space));
     if (n == 0) return RDX_OK;
     std::lock_guard<std::mutex> lk(h->mu);
     RDX_TRY(finish_pending(h, nullptr));
@@ -1227,7 +1224,7 @@ static int stage_ids(rdx_index* h, const int64_t* ids, int64_t n, int space, con
 
 extern "C" int rdx_index_update(rdx_index* h, const int64_t* row_ids, const float* rows, int64_t n, int space) {
     if (!h || n < 0 || (n > 0 && (!row_ids || !rows))) return fail(RDX_ERR_INVALID, "rdx_index_update: bad argument");
-    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    RDX_TRY(check_space(space));
     if (n == 0) return RDX_OK;
     std::lock_guard<std::mutex> lk(h->mu);
     RDX_TRY(finish_pending(h, nullptr));
@@ -1240,7 +1237,7 @@ extern "C" int rdx_index_update(rdx_index* h, const int64_t* row_ids, const floa
 
 extern "C" int rdx_index_get(rdx_index* h, const int64_t* row_ids, int64_t n, float* out, int space) {
     if (!h || n < 0 || (n > 0 && (!row_ids || !out))) return fail(RDX_ERR_INVALID, "rdx_index_get: bad argument");
-    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    RDX_TRY(check_space(space));
     if (n == 0) return RDX_OK;
     std::lock_guard<std::mutex> lk(h->mu);
     RDX_TRY(finish_pending(h, nullptr));
@@ -1317,7 +1314,7 @@ extern "C" int rdx_index_compact(rdx_index* h, const int64_t* keep, int64_t n_ke
 
 extern "C" int rdx_index_set_row_ids(rdx_index* h, int64_t first_row, const int64_t* ids, int64_t n, int space) {
     if (!h || first_row < 0 || n < 0 || (n > 0 && !ids)) return fail(RDX_ERR_INVALID, "rdx_index_set_row_ids: bad argument");
-    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    RDX_TRY(check_space(space));
     std::lock_guard<std::mutex> lk(h->mu);
     if (first_row + n > h->rows) return fail(RDX_ERR_INVALID, "rdx_index_set_row_ids: rows [first_row, first_row + n) must exist");
     if (n == 0) return RDX_OK;
@@ -1356,7 +1353,7 @@ static NormScratch* const g_norm = new NormScratch[64];
 extern "C" int rdx_l2_normalize(int device, const float* in, int64_t n, int dim, float* out, int space, void* stream) {
     if (n < 0 || (n > 0 && (!in || !out))) return fail(RDX_ERR_INVALID, "rdx_l2_normalize: bad argument");
     RDX_TRY(check_dim(dim));
-    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    RDX_TRY(check_space(space));
     if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_l2_normalize: device out of range");
     if (n == 0) return RDX_OK;
     HIP_TRY(hipSetDevice(device));
@@ -1417,7 +1414,7 @@ static int search_impl(rdx_index* h, const float* queries, int64_t nq, int k, co
                        float* out_score, int64_t* out_row, int32_t* out_count, int space, void* stream) {
     if (nq < 0 || k < 0) return fail(RDX_ERR_INVALID, "rdx_search: nq and k must be >= 0");
     if (k > SELECT_MAX_K) return fail(RDX_ERR_INVALID, "rdx_search: k larger than " + std::to_string(SELECT_MAX_K) + " is not supported");
-    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    RDX_TRY(check_space(space));
     if (nq == 0) return RDX_OK;
     if (!queries || !out_count || (k > 0 && (!out_score || !out_row))) return fail(RDX_ERR_INVALID, "rdx_search: null pointer");
     rdx_search_stats s;
@@ -1494,7 +1491,7 @@ extern "C" int rdx_search_wait(rdx_index* h, int* redone) {
 
 extern "C" int rdx_mask_create(rdx_index* h, const uint32_t* allow_bits, int space, rdx_mask** out) {
     if (!h || !allow_bits || !out) return fail(RDX_ERR_INVALID, "rdx_mask_create: null pointer");
-    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    RDX_TRY(check_space(space));
     std::lock_guard<std::mutex> lk(h->mu);
     RDX_TRY(finish_pending(h, nullptr));
     RDX_TRY(set_device(h));
@@ -1566,7 +1563,7 @@ extern "C" int rdx_search_last_stats(rdx_index* h, rdx_search_stats* out) {
 extern "C" int rdx_merge_topk(int device, const float* part_score, const int64_t* part_row, const int32_t* part_count, int n_parts,
                               int64_t nq, int k, float* out_score, int64_t* out_row, int32_t* out_count, int space, void* stream) {
     if (n_parts < 1 || n_parts > 64 || nq < 0 || k < 0 || k > SELECT_MAX_K) return fail(RDX_ERR_INVALID, "rdx_merge_topk: bad shape");
-    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    RDX_TRY(check_space(space));
     if (nq == 0) return RDX_OK;
     if (!part_count || !out_count || (k > 0 && (!part_score || !part_row || !out_score || !out_row)))
         return fail(RDX_ERR_INVALID, "rdx_merge_topk: null pointer");

@@ -1,7 +1,7 @@
-// rdx_meta.hip — the metadata store and the `where` predicate scan (rdx_meta_*) of include/rdx.h.
-#include "rdx_host.hpp"
+// rdx_meta.hip — the metadata store and the `where` predicate scan (rdx_meta_*) of include/rdx.h. What it has in common with the
+// document store (rdx_docs.hip) is in rdx_store.hpp: StoreBase (device, stream, last-use event, lock), check_program and BitmapStage.
+#include "rdx_store.hpp"
 
-#include <mutex>
 #include <vector>
 
 #include "meta_kernel.hpp"
@@ -18,8 +18,7 @@ struct MetaColumn {
     DevBuf kind, pay;
 };
 
-struct rdx_meta {
-    int device = 0;
+struct rdx_meta : StoreBase {   // last_use is recorded behind every filter kernel
     int max_blocks = 1;
     std::vector<MetaColumn*> cols;     // by slot; null = never used
     // the query of rdx_meta_set_query; n_ops = 0: none set, or unset by a change of the store
@@ -27,18 +26,9 @@ struct rdx_meta {
     bool sorted = false;
     std::vector<int> used;             // the slots the query names = the rows of the device column table
     DevBuf leaves, prog, coltab, tmp_in, tmp_out;
-    hipStream_t own_stream = nullptr;
-    hipEvent_t last_use = nullptr;     // recorded behind the last filter kernel: writes and re-allocations wait for it
-    std::mutex mu;
 };
 
 static constexpr int64_t META_STAGE_ROWS = (int64_t)1 << 22;   // rows per staged upload (32 MiB of payload)
-
-static int meta_wait(rdx_meta* h) {
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipEventSynchronize(h->last_use));
-    return RDX_OK;
-}
 
 static int meta_check_col(const char* who, int col) {
     if (col < 0 || col >= RDX_META_MAX_COLUMNS)
@@ -49,21 +39,17 @@ static int meta_check_col(const char* who, int col) {
 extern "C" int rdx_meta_create(int device, rdx_meta** out) {
     if (!out) return fail(RDX_ERR_INVALID, "rdx_meta_create: null out pointer");
     *out = nullptr;
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev)
-        return fail(RDX_ERR_INVALID, "rdx_meta_create: device " + std::to_string(device) + " out of range (" + std::to_string(ndev) + " visible)");
-    HIP_TRY(hipSetDevice(device));
+    RDX_TRY(check_device("rdx_meta_create: ", device));
     rdx_meta* h = new rdx_meta();
-    h->device = device;
     int cus = 0;
-    hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->last_use, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(h->last_use, h->own_stream);
-    if (e != hipSuccess) {
+    int rc = h->open("rdx_meta_create", device);
+    if (rc == RDX_OK) {
+        const hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+        if (e != hipSuccess) rc = fail(RDX_ERR_HIP, std::string("rdx_meta_create: ") + hipGetErrorString(e));
+    }
+    if (rc != RDX_OK) {
         rdx_meta_destroy(h);
-        return fail(RDX_ERR_HIP, std::string("rdx_meta_create: ") + hipGetErrorString(e));
+        return rc;
     }
     h->max_blocks = std::max(cus, 1) * (2048 / META_THREADS);   // every wave slot of the device once; more rows go grid-stride
     *out = h;
@@ -72,15 +58,7 @@ extern "C" int rdx_meta_create(int device, rdx_meta** out) {
 
 extern "C" int rdx_meta_destroy(rdx_meta* h) {
     if (!h) return RDX_OK;
-    (void)hipSetDevice(h->device);
-    if (h->last_use) {
-        (void)hipEventSynchronize(h->last_use);
-        (void)hipEventDestroy(h->last_use);
-    }
-    if (h->own_stream) {
-        (void)hipStreamSynchronize(h->own_stream);
-        (void)hipStreamDestroy(h->own_stream);
-    }
+    h->close();
     for (MetaColumn* c : h->cols) delete c;
     delete h;
     return RDX_OK;
@@ -96,7 +74,7 @@ extern "C" int rdx_meta_set_rows(rdx_meta* h, int col, int64_t first_row, const 
     std::lock_guard<std::mutex> lk(h->mu);
     h->n_ops = 0;
     if (n == 0) return RDX_OK;
-    RDX_TRY(meta_wait(h));
+    RDX_TRY(h->wait());
     if ((size_t)col >= h->cols.size()) h->cols.resize((size_t)col + 1, nullptr);
     if (!h->cols[(size_t)col]) h->cols[(size_t)col] = new MetaColumn();
     MetaColumn* c = h->cols[(size_t)col];
@@ -128,7 +106,7 @@ extern "C" int rdx_meta_drop_column(rdx_meta* h, int col) {
     std::lock_guard<std::mutex> lk(h->mu);
     h->n_ops = 0;
     if ((size_t)col >= h->cols.size() || !h->cols[(size_t)col]) return RDX_OK;
-    RDX_TRY(meta_wait(h));
+    RDX_TRY(h->wait());
     delete h->cols[(size_t)col];
     h->cols[(size_t)col] = nullptr;
     return RDX_OK;
@@ -159,8 +137,8 @@ extern "C" int rdx_meta_set_query(rdx_meta* h, const rdx_meta_leaf* leaves, int 
     const std::string who = "rdx_meta_set_query: ";
     if (n_leaves < 1 || n_leaves > META_MAX_LEAVES || !leaves)
         return fail(RDX_ERR_INVALID, who + "need 1 <= n_leaves <= " + std::to_string(META_MAX_LEAVES) + " and a leaf table (got " + std::to_string(n_leaves) + ")");
-    if (n_ops < 1 || n_ops > META_MAX_OPS || !program)
-        return fail(RDX_ERR_INVALID, who + "need 1 <= n_ops <= " + std::to_string(META_MAX_OPS) + " and a program (got " + std::to_string(n_ops) + ")");
+    if (n_ops < 1 || n_ops > FILTER_MAX_OPS || !program)
+        return fail(RDX_ERR_INVALID, who + "need 1 <= n_ops <= " + std::to_string(FILTER_MAX_OPS) + " and a program (got " + std::to_string(n_ops) + ")");
     for (int i = 0; i < n_leaves; ++i) {
         const rdx_meta_leaf& lf = leaves[i];
         if (lf.op < RDX_META_EQ || lf.op > RDX_META_CONST1) return fail(RDX_ERR_INVALID, who + "leaf " + std::to_string(i) + " has an unknown op");
@@ -169,16 +147,7 @@ extern "C" int rdx_meta_set_query(rdx_meta* h, const rdx_meta_leaf* leaves, int 
         if (lf.kind < 1 || lf.kind > 4) return fail(RDX_ERR_INVALID, who + "leaf " + std::to_string(i) + " has a kind outside 1 .. 4");
         if (lf.kind == 1 && lf.op != RDX_META_EQ) return fail(RDX_ERR_INVALID, who + "leaf " + std::to_string(i) + " orders strings: a str leaf takes EQ only");
     }
-    int depth = 0;
-    for (int i = 0; i < n_ops; ++i) {
-        const int32_t op = program[i];
-        if (op >= n_leaves || op < META_OP_OR) return fail(RDX_ERR_INVALID, who + "op " + std::to_string(i) + " is neither a leaf < n_leaves nor NOT / AND / OR");
-        const int need = op >= 0 ? 0 : (op == META_OP_NOT ? 1 : 2);
-        if (depth < need) return fail(RDX_ERR_INVALID, who + "op " + std::to_string(i) + " pops an empty stack");
-        depth += op >= 0 ? 1 : (op == META_OP_NOT ? 0 : -1);
-        if (depth > META_MAX_STACK) return fail(RDX_ERR_INVALID, who + "the program needs more than " + std::to_string(META_MAX_STACK) + " stack entries");
-    }
-    if (depth != 1) return fail(RDX_ERR_INVALID, who + "the program must leave exactly one value");
+    RDX_TRY(check_program(who, "n_leaves", program, n_ops, n_leaves));
     if (!h) return fail(RDX_ERR_INVALID, who + "null store");
     std::lock_guard<std::mutex> lk(h->mu);
     for (int i = 0; i < n_leaves; ++i) {
@@ -218,7 +187,7 @@ extern "C" int rdx_meta_set_query(rdx_meta* h, const rdx_meta_leaf* leaves, int 
     }
     std::vector<MetaCol> tab(std::max<size_t>(used.size(), 1), MetaCol{nullptr, nullptr});
     for (size_t u = 0; u < used.size(); ++u) tab[u] = MetaCol{h->cols[(size_t)used[u]]->kind.as<uint8_t>(), h->cols[(size_t)used[u]]->pay.as<double>()};
-    RDX_TRY(meta_wait(h));
+    RDX_TRY(h->wait());
     h->n_ops = 0;   // a refused query leaves the one before it in place; one that fails from here on leaves none
     RDX_TRY(h->leaves.ensure(lv.size() * sizeof(MetaLeaf)));
     RDX_TRY(h->prog.ensure(prog.size() * 4));
@@ -235,7 +204,7 @@ extern "C" int rdx_meta_set_query(rdx_meta* h, const rdx_meta_leaf* leaves, int 
 
 extern "C" int rdx_meta_filter(rdx_meta* h, int64_t rows, const uint32_t* base_bits, uint32_t* out_bits, int space, void* stream) {
     if (!h || !out_bits) return fail(RDX_ERR_INVALID, "rdx_meta_filter: null pointer");
-    if (space != RDX_HOST && space != RDX_DEVICE) return fail(RDX_ERR_INVALID, "space must be RDX_HOST or RDX_DEVICE");
+    RDX_TRY(check_space(space));
     if (rows < 0 || rows > INT32_MAX) return fail(RDX_ERR_INVALID, "rdx_meta_filter: rows must be in [0, 2^31)");
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->n_ops == 0) return fail(RDX_ERR_STATE, "rdx_meta_filter: no query set since the store last changed (rdx_meta_set_query)");
@@ -245,28 +214,17 @@ extern "C" int rdx_meta_filter(rdx_meta* h, int64_t rows, const uint32_t* base_b
                                            " rows, the call says " + std::to_string(rows));
     if (rows == 0) return RDX_OK;
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = space == RDX_HOST ? h->own_stream : (hipStream_t)stream;
     const int64_t words = (rows + 31) / 32;
-    const uint32_t* base = base_bits;
-    uint32_t* out = out_bits;
-    if (space == RDX_HOST) {
-        RDX_TRY(h->tmp_in.ensure((size_t)words * 4));
-        RDX_TRY(h->tmp_out.ensure((size_t)words * 4));
-        if (base_bits) HIP_TRY(hipMemcpyAsync(h->tmp_in.p, base_bits, (size_t)words * 4, hipMemcpyHostToDevice, st));
-        base = base_bits ? h->tmp_in.as<uint32_t>() : nullptr;
-        out = h->tmp_out.as<uint32_t>();
-    }
+    BitmapStage g;
+    RDX_TRY(g.begin(*h, space, stream, words, base_bits, out_bits, h->tmp_in, h->tmp_out));
     const int64_t block_rows = META_THREADS * META_ROWS;
     const unsigned grid = (unsigned)std::min<int64_t>((rows + block_rows - 1) / block_rows, h->max_blocks);
     if (h->sorted)
-        hipLaunchKernelGGL(k_meta_filter<true>, dim3(grid), dim3(META_THREADS), 0, st, h->coltab.as<MetaCol>(), h->leaves.as<MetaLeaf>(), h->n_leaves,
-                           h->prog.as<int32_t>(), h->n_ops, rows, words, base, out);
+        hipLaunchKernelGGL(k_meta_filter<true>, dim3(grid), dim3(META_THREADS), 0, g.st, h->coltab.as<MetaCol>(), h->leaves.as<MetaLeaf>(), h->n_leaves,
+                           h->prog.as<int32_t>(), h->n_ops, rows, words, g.base, g.out);
     else
-        hipLaunchKernelGGL(k_meta_filter<false>, dim3(grid), dim3(META_THREADS), 0, st, h->coltab.as<MetaCol>(), h->leaves.as<MetaLeaf>(), h->n_leaves,
-                           h->prog.as<int32_t>(), h->n_ops, rows, words, base, out);
+        hipLaunchKernelGGL(k_meta_filter<false>, dim3(grid), dim3(META_THREADS), 0, g.st, h->coltab.as<MetaCol>(), h->leaves.as<MetaLeaf>(), h->n_leaves,
+                           h->prog.as<int32_t>(), h->n_ops, rows, words, g.base, g.out);
     HIP_TRY(hipGetLastError());
-    if (space == RDX_HOST) HIP_TRY(hipMemcpyAsync(out_bits, out, (size_t)words * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(h->last_use, st));
-    if (space == RDX_HOST) HIP_TRY(hipStreamSynchronize(st));
-    return RDX_OK;
+    return g.end(*h, space, words, out_bits);
 }

@@ -17,39 +17,22 @@ def _np_ptr(a: np.ndarray):
     return ctypes.c_void_p(a.ctypes.data)
 
 
-class ResidentMask:
-    """a `where` bitmap resident in HBM (rdx_mask): made once per distinct filter, passed with every search"""
+class _Handle:
+    """one opaque librdx handle and the rdx_*_destroy that frees it: close() may be called any number of times, and __del__
+    swallows errors (at interpreter exit the library may be gone before the object)"""
+    _destroy = ""   # the subclass names its destroy function
+    _lib = None
+    _h = None
 
-    def __init__(self, lib, handle):
-        self._lib, self._h = lib, handle
+    def _new_handle(self):
+        """loads the library; -> what an rdx_*_create takes as its `out`"""
+        self._lib = L.load(require_gpu=True)
+        self._h = ctypes.c_void_p()
+        return ctypes.byref(self._h)
 
     def close(self):
         if self._h is not None and self._h.value:
-            self._lib.rdx_mask_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class HipIndex:
-    has_device_docs = True   # Collection keeps a DocStore on this device for where_document
-    has_device_meta = True   # ... and a MetaStore for `where` (single-device collections)
-
-    def __init__(self, dim: int, device: int = 0):
-        self._lib = L.load(require_gpu=True)
-        self._h = ctypes.c_void_p()
-        L.check(self._lib.rdx_index_create(int(device), int(dim), ctypes.byref(self._h)))
-        self.dim = int(dim)
-        self.device = int(device)
-
-    # ---- lifecycle -------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.rdx_index_destroy(self._h)
+            getattr(self._lib, self._destroy)(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):
@@ -57,6 +40,50 @@ class HipIndex:
             self.close()
         except Exception:
             pass
+
+
+class ResidentMask(_Handle):
+    """a `where` bitmap resident in HBM (rdx_mask): made once per distinct filter, passed with every search"""
+    _destroy = "rdx_mask_destroy"
+
+    def __init__(self, lib, handle):
+        self._lib, self._h = lib, handle
+
+
+def _filter_host(fn, lead, words: int, base_bits) -> np.ndarray:
+    """DocStore.filter / MetaStore.filter: fn(*lead, base_bits, out_bits, space, stream) is rdx_docs_filter / rdx_meta_filter"""
+    out = np.zeros(words, dtype=np.uint32)
+    base = None
+    if base_bits is not None:
+        base = np.ascontiguousarray(base_bits, dtype=np.uint32)
+        if base.shape[0] != words:
+            raise ValueError("base_bits must hold ceil(rows/32) words")
+    L.check(fn(*lead, _np_ptr(base) if base is not None else None, _np_ptr(out), L.RDX_HOST, None))
+    return out
+
+
+def _filter_device(fn, lead, device: int, words: int, out_bits, base_bits):
+    """DocStore.filter_device / MetaStore.filter_device: the same call with device pointers, on the current torch stream"""
+    import torch
+    for t in (out_bits, base_bits):
+        if t is not None and (not t.is_cuda or t.device.index != device or t.dtype != torch.int32
+                              or t.numel() != words or not t.is_contiguous()):
+            raise ValueError(f"expected a contiguous int32 tensor of {words} words on cuda:{device}")
+    stream = HipIndex._raw_stream(out_bits.device)
+    L.check(fn(*lead, ctypes.c_void_p(base_bits.data_ptr()) if base_bits is not None else None,
+               ctypes.c_void_p(out_bits.data_ptr()), L.RDX_DEVICE, ctypes.c_void_p(stream)))
+
+
+class HipIndex(_Handle):
+    _destroy = "rdx_index_destroy"
+    has_device_docs = True   # Collection keeps a DocStore on this device for where_document
+    has_device_meta = True   # ... and a MetaStore for `where` (single-device collections)
+
+    def __init__(self, dim: int, device: int = 0):
+        out = self._new_handle()
+        L.check(self._lib.rdx_index_create(int(device), int(dim), out))
+        self.dim = int(dim)
+        self.device = int(device)
 
     def __len__(self) -> int:
         n = ctypes.c_int64(0)
@@ -251,26 +278,16 @@ class HipIndex:
         return d
 
 
-class DocStore:
+class DocStore(_Handle):
     """The rows' document text resident in one device's HBM (include/rdx.h rdx_docs_*): where_document's substring scan.
     Rows follow the collection's row order; the caller keeps it in step (append / replace / compact)."""
 
+    _destroy = "rdx_docs_destroy"
+
     def __init__(self, device: int = 0):
-        self._lib = L.load(require_gpu=True)
-        self._h = ctypes.c_void_p()
-        L.check(self._lib.rdx_docs_create(int(device), ctypes.byref(self._h)))
+        out = self._new_handle()
+        L.check(self._lib.rdx_docs_create(int(device), out))
         self.device = int(device)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.rdx_docs_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def append(self, docs):
         from .where_document import pack_docs
@@ -319,51 +336,23 @@ class DocStore:
 
     def filter(self, base_bits: Optional[np.ndarray] = None) -> np.ndarray:
         """-> uint32 [ceil(rows/32)]: program(leaves) AND base_bits (host in, host out)"""
-        words = (len(self) + 31) // 32
-        out = np.zeros(words, dtype=np.uint32)
-        base = None
-        if base_bits is not None:
-            base = np.ascontiguousarray(base_bits, dtype=np.uint32)
-            if base.shape[0] != words:
-                raise ValueError("base_bits must hold ceil(rows/32) words")
-        L.check(self._lib.rdx_docs_filter(self._h, _np_ptr(base) if base is not None else None, _np_ptr(out), L.RDX_HOST, None))
-        return out
+        return _filter_host(self._lib.rdx_docs_filter, (self._h,), (len(self) + 31) // 32, base_bits)
 
     def filter_device(self, out_bits, base_bits=None):
         """torch int32 tensors on the store's device, enqueued on the current torch stream: nothing crosses PCIe"""
-        import torch
-        words = (len(self) + 31) // 32
-        for t in (out_bits, base_bits):
-            if t is not None and (not t.is_cuda or t.device.index != self.device or t.dtype != torch.int32
-                                  or t.numel() != words or not t.is_contiguous()):
-                raise ValueError(f"expected a contiguous int32 tensor of {words} words on cuda:{self.device}")
-        stream = HipIndex._raw_stream(out_bits.device)
-        L.check(self._lib.rdx_docs_filter(self._h, ctypes.c_void_p(base_bits.data_ptr()) if base_bits is not None else None,
-                                          ctypes.c_void_p(out_bits.data_ptr()), L.RDX_DEVICE, ctypes.c_void_p(stream)))
+        _filter_device(self._lib.rdx_docs_filter, (self._h,), self.device, (len(self) + 31) // 32, out_bits, base_bits)
 
 
-class MetaStore:
+class MetaStore(_Handle):
     """Some of a collection's metadata columns resident in one device's HBM (include/rdx.h rdx_meta_*): the `where` predicate
     scan. A column lives in a slot chosen by the caller; rows follow the collection's row order and the caller keeps them in
     step (set_rows / drop_column / truncate). Nothing is allocated on the device before the first set_rows."""
-
+    _destroy = "rdx_meta_destroy"
 
     def __init__(self, device: int = 0):
-        self._lib = L.load(require_gpu=True)
-        self._h = ctypes.c_void_p()
-        L.check(self._lib.rdx_meta_create(int(device), ctypes.byref(self._h)))
+        out = self._new_handle()
+        L.check(self._lib.rdx_meta_create(int(device), out))
         self.device = int(device)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.rdx_meta_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_rows(self, col: int, first_row: int, kind, num, code):
         """rows [first_row, first_row + n) of slot `col` from where.Column's three arrays (kind int8 / uint8, num f64, code i32)"""
@@ -395,27 +384,11 @@ class MetaStore:
 
     def filter(self, rows: int, base_bits: Optional[np.ndarray] = None) -> np.ndarray:
         """-> uint32 [ceil(rows/32)]: program(leaves) AND base_bits (host in, host out)"""
-        words = (int(rows) + 31) // 32
-        out = np.zeros(words, dtype=np.uint32)
-        base = None
-        if base_bits is not None:
-            base = np.ascontiguousarray(base_bits, dtype=np.uint32)
-            if base.shape[0] != words:
-                raise ValueError("base_bits must hold ceil(rows/32) words")
-        L.check(self._lib.rdx_meta_filter(self._h, int(rows), _np_ptr(base) if base is not None else None, _np_ptr(out), L.RDX_HOST, None))
-        return out
+        return _filter_host(self._lib.rdx_meta_filter, (self._h, int(rows)), (int(rows) + 31) // 32, base_bits)
 
     def filter_device(self, rows: int, out_bits, base_bits=None):
         """torch int32 tensors on the store's device, enqueued on the current torch stream: nothing crosses PCIe"""
-        import torch
-        words = (int(rows) + 31) // 32
-        for t in (out_bits, base_bits):
-            if t is not None and (not t.is_cuda or t.device.index != self.device or t.dtype != torch.int32
-                                  or t.numel() != words or not t.is_contiguous()):
-                raise ValueError(f"expected a contiguous int32 tensor of {words} words on cuda:{self.device}")
-        stream = HipIndex._raw_stream(out_bits.device)
-        L.check(self._lib.rdx_meta_filter(self._h, int(rows), ctypes.c_void_p(base_bits.data_ptr()) if base_bits is not None else None,
-                                          ctypes.c_void_p(out_bits.data_ptr()), L.RDX_DEVICE, ctypes.c_void_p(stream)))
+        _filter_device(self._lib.rdx_meta_filter, (self._h, int(rows)), self.device, (int(rows) + 31) // 32, out_bits, base_bits)
 
 
 def l2_normalize(x: np.ndarray, device: int = 0) -> np.ndarray:

@@ -23,10 +23,10 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from . import where as W
+from ._lib import MAX_OPS, MAX_STACK, OP_AND, OP_NOT, OP_OR   # the program format, shared with where_document.py
 
 EQ, GT, GE, LT, LE, CONST0, CONST1 = range(7)    # include/rdx.h RDX_META_*
-OP_NOT, OP_AND, OP_OR = -1, -2, -3               # include/rdx.h RDX_META_OP_*
-MAX_LEAVES, MAX_OPS, MAX_STACK = 1024, 4096, 16
+MAX_LEAVES = 1024
 LEAF = np.dtype([("col", "<i4"), ("op", "<i4"), ("kind", "<i4"), ("code", "<i4"), ("num", "<f8")])   # rdx_meta_leaf
 _CMP = {"$gt": GT, "$gte": GE, "$lt": LT, "$lte": LE}
 

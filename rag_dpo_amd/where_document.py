@@ -21,9 +21,8 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-OP_NOT, OP_AND, OP_OR = -1, -2, -3   # include/rdx.h RDX_DOCS_OP_*
-MAX_STACK = 16                       # include/rdx.h: at most 16 stack entries
-MAX_OPS = 4096
+from ._lib import MAX_OPS, MAX_STACK, OP_AND, OP_NOT, OP_OR   # the program format, shared with where_device.py
+
 MAX_LEAVES = 1024
 
 _LEAF_OPS = ("$contains", "$not_contains")

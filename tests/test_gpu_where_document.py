@@ -201,6 +201,45 @@ def test_depth3_tree_with_base_bits():
     st.close()
 
 
+@pytest.mark.parametrize("rows", [0, 1, 32, 33, 1025])
+def test_filter_words_are_the_same_in_both_spaces(rows):
+    """host bitmaps are staged through the store's own buffers, device ones are taken as they are: both give the words of the
+    host model, with and without base_bits. No rows (nothing is launched, nothing written), one row, a full word, a second word,
+    more than 1024 rows; row 0 is longer than 1024 bytes, with a pattern across the start of its second segment."""
+    import ctypes
+    import torch
+    from rag_dpo_amd import _lib as L
+    from rag_dpo_amd import where_document as WD
+    from rag_dpo_amd.where import pack_bits
+    from rag_dpo_amd.engine import DocStore
+    from test_where_document import TREES, make_docs
+    docs = make_docs(rows, seed=6)
+    if rows:
+        docs[0] = "x" * 1019 + "article 28 … CNIL"
+    words = (rows + 31) // 32
+    base = np.random.default_rng(8).random(rows) < 0.7
+    back = torch.from_numpy(np.append(pack_bits(base), np.uint32(0)).view(np.int32)).cuda()   # one word more: the base of no rows has an address too
+    base_t = back[:words]
+    st = DocStore(0)
+    st.append(docs)
+    for tree in TREES:
+        st.set_query(*WD.compile_tree(tree))
+        want = WD.evaluate_host(tree, docs)
+        for b, b_t, expect in ((None, None, pack_bits(want)), (pack_bits(base), base_t, pack_bits(want & base))):
+            host = st.filter(b)
+            assert host.dtype == np.uint32 and host.shape == (words,) and (host == expect).all(), tree
+            room = torch.full((words + 1,), -1, dtype=torch.int32, device="cuda")
+            if rows:
+                st.filter_device(room[:words], b_t)
+            else:       # a tensor of no words has no address: the call itself, with the address of the word that must stay as it is
+                L.check(st._lib.rdx_docs_filter(st._h, ctypes.c_void_p(back.data_ptr()) if b is not None else None, ctypes.c_void_p(room.data_ptr()),
+                                                L.RDX_DEVICE, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            torch.cuda.synchronize()
+            got = room.cpu().numpy().view(np.uint32)
+            assert (got[:words] == host).all() and got[words] == 0xFFFFFFFF, tree
+    st.close()
+
+
 def test_collection_contract_on_hipindex(tmp_path):
     from test_where_document import run_wd_contract
     from rag_dpo_amd.collection import _default_engine_factory

@@ -275,6 +275,26 @@ def test_cabi_rejects_bad_arguments_without_gpu():
     assert L.rdx_docs_destroy(None) == 0
 
 
+def test_c_abi_argument_checks_under_asan_and_ubsan(tmp_path):
+    """rdx_docs_* validate before they use the handle or touch a device: a stand-alone C program, built with the sanitizers,
+    run on the CPU"""
+    import os
+    import subprocess
+    from rag_dpo_amd import build
+    here = os.path.dirname(os.path.abspath(__file__))
+    lib_dir = os.path.dirname(build.build_lib())
+    exe = str(tmp_path / "docs_errors")
+    subprocess.check_call(["gcc", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1", "-std=c11",
+                           "-Wall", "-I", os.path.join(os.path.dirname(here), "include"), os.path.join(here, "c_abi", "docs_errors.c"),
+                           "-L", lib_dir, "-l:librdx.so", f"-Wl,-rpath,{lib_dir}", "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    # (leak detection off: the HIP runtime librdx links keeps allocations of its own until process exit)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    assert "docs error paths ok: 35 checks" in r.stdout, r.stdout
+
+
 def test_size_limits_hold_on_every_engine():
     """the device program's limits (16 stack entries, 1024 patterns, 4096 operations) apply to the host evaluator as well"""
     from rag_dpo_amd import where_document as WD
