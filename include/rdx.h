@@ -87,6 +87,9 @@ int rdx_index_add_bf16(rdx_index* h, const uint16_t* rows, int64_t n, int space)
 int rdx_index_add_stored(rdx_index* h, const float* rows, int64_t n, int space);
 /* `collection.update(ids=, embeddings=)` / upsert: overwrite existing rows in place. */
 int rdx_index_update(rdx_index* h, const int64_t* row_ids, const float* rows, int64_t n, int space);
+/* rdx_index_update for rows that ARE stored values, as rdx_index_add_stored is to rdx_index_add: written verbatim (the lifted rows
+ * of an "ip" / "l2" collection, below). Additive: rdx_index_update is unchanged. */
+int rdx_index_update_stored(rdx_index* h, const int64_t* row_ids, const float* rows, int64_t n, int space);
 /* `collection.get(include=["embeddings"])`: the stored (normalised) fp32 rows. */
 int rdx_index_get(rdx_index* h, const int64_t* row_ids, int64_t n, float* out, int space);
 /* `collection.delete(ids=...)` (reference ingest_enterprise.py:272,304): keep exactly the rows
@@ -511,6 +514,53 @@ int rdx_meta_set_query(rdx_meta* h, const rdx_meta_leaf* leaves, int n_leaves, c
  * exactly `rows` rows and a query must be set, else RDX_ERR_STATE (nothing is launched). RDX_DEVICE: one kernel enqueued on
  * `stream`; nothing is synchronised or allocated and nothing crosses PCIe. RDX_HOST: complete on return. */
 int rdx_meta_filter(rdx_meta* h, int64_t rows, const uint32_t* base_bits, uint32_t* out_bits, int space, void* stream);
+
+/* Inner-product and squared-L2 spaces ------------------------------------------------------------ */
+/* Chroma's two other spaces (`create_collection(metadata={"hnsw:space": "ip" | "l2"})`) on the cosine engine; DESIGN.md §17 has the
+ * reduction and the proof, rag_dpo_amd/spaces.py drives these calls and is their model, bit for bit.
+ *
+ * The contract of such a collection. Stored embeddings are kept exactly as given (fp32; get / query return them bit for bit; nothing
+ * is normalised). distance = 1 - sum_j q_j x_j (ip) or sum_j (q_j - x_j)^2 (l2: the SQUARED Euclidean distance), computed in fp64
+ * from the raw fp32 query and the raw fp32 row in a fixed order — 64 partial sums, partial l takes j = l, l + 64, ... in that order
+ * from +0.0, combined by the xor butterfly s[l] += s[l ^ m], m = 32, 16, 8, 4, 2, 1 (rdx_topic_boost's order) — and rounded to fp32
+ * once. ip: the term is (double)q_j * (double)x_j and the distance (float)(1.0 - sum). l2: diff = (double)q_j - (double)x_j,
+ * sq = diff * diff, acc += sq, each rounded, never fused. Result order per query: fp32 distance ascending, ties by ascending row
+ * id; counts, padding (+inf, -1), filters and tombstones as in the cosine space. NaN / Inf are rejected; so is a row whose lifted
+ * form is not finite or whose power-of-two scaling is not exactly invertible in fp32. Results depend on the raw values only.
+ *
+ * The engine rows ("lifted"): y = 2^e x (ip, engine dim = dim) or y = 2^e (x, a, 0, 0, 0) with a = (float)(-|x|^2 / 2), |x|^2 in the
+ * order above (l2, engine dim = dim + 4; a query is (q, 1, 0, 0, 0)); e = scale_exp, one per collection, chosen so that every
+ * |y| <= 1. They are stored with rdx_index_add_stored / rdx_index_update_stored; x = 2^-e y exactly.
+ *
+ * All four calls: device pointers, enqueued on `stream`, nothing synchronised, no allocation, no float atomics (the same inputs
+ * give the same bits); arguments are validated before the device is touched. dim: the RAW dimension, a multiple of 4 with the
+ * engine dimension at most 4096. Rows, queries and engine rows are 16-byte aligned.
+ *
+ * rdx_space_measure: lifted_sq[i] (fp64) = |x_i|^2 (ip) or |x_i|^2 + a_i^2 (l2), the squared norm of the lifted row before
+ *   scaling; bad[i] = 1 when the row holds NaN / Inf or a_i is not finite, else 0. The host picks scale_exp from the largest.
+ * rdx_space_lift: out [n][engine dim] from rows [n][dim] and scale_exp (is_query = 1: queries, scale_exp 0, fifth column 1);
+ *   bad[i] = 1 when some element does not scale back to its own bits (ldexpf(ldexpf(x, e), -e) != x), else 0.
+ * rdx_space_rescore: per query b the candidates cand_rows / cand_scores [nq][kp] (what rdx_search returned for the lifted query with
+ *   k = kp; cand_counts [nq]) and their engine rows cand_vecs [nq][kp][engine dim] (rdx_index_get of cand_rows; slots past the
+ *   count are not used) -> the k best by (distance, row): out_dist / out_row [nq][k], out_count [nq] = min(k, count), and
+ *   out_proven [nq] = 1 when no row outside the candidates can belong to the answer: count < kp, or the lower bound on the
+ *   distance of every other row — from the lowest candidate score plus `guard` (spaces.GUARD_IP / GUARD_L2) — is strictly above the k-th distance.
+ *   work_dist: [nq][kp] floats of scratch owned by the caller. 1 <= k <= kp <= 4096, nq <= 65535.
+ * rdx_space_distances: out[b * out_stride + r] = distance(query b, engine row r of the page vecs [n][engine dim]), or +inf when bit
+ *   first_row + r of allow_bits (NULL = all rows) is clear: the brute-force pass. nq <= 64, n <= 2^24. */
+#define RDX_SPACE_IP 0
+#define RDX_SPACE_L2 1
+int rdx_space_measure(int device, int space_kind, const float* rows, int64_t n, int dim, double* lifted_sq, int32_t* bad,
+                      void* stream);
+int rdx_space_lift(int device, int space_kind, int is_query, const float* rows, int64_t n, int dim, int scale_exp, float* out,
+                   int32_t* bad, void* stream);
+int rdx_space_rescore(int device, int space_kind, const float* queries, int64_t nq, int dim, const float* cand_vecs,
+                      const int64_t* cand_rows, const float* cand_scores, const int32_t* cand_counts, int kp, int k,
+                      int scale_exp, double guard, float* work_dist, float* out_dist, int64_t* out_row, int32_t* out_count,
+                      int32_t* out_proven, void* stream);
+int rdx_space_distances(int device, int space_kind, const float* queries, int nq, int dim, const float* vecs, int64_t n,
+                        int scale_exp, const uint32_t* allow_bits, int64_t first_row, float* out, int64_t out_stride,
+                        void* stream);
 
 #ifdef __cplusplus
 }

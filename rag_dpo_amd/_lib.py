@@ -24,6 +24,8 @@ MAX_OPS, MAX_STACK = 4096, 16        # include/rdx.h: at most 4096 ops and 16 st
 DOCS_OP_NOT, DOCS_OP_AND, DOCS_OP_OR = OP_NOT, OP_AND, OP_OR
 DOCS_MAX_LEAVES = 1024   # include/rdx.h RDX_DOCS_MAX_LEAVES
 META_MAX_COLUMNS = 4096   # include/rdx.h RDX_META_MAX_COLUMNS (leaf ops and the leaf limit: rag_dpo_amd/where_device.py)
+SPACE_IP, SPACE_L2 = 0, 1   # include/rdx.h RDX_SPACE_*
+SPACE_MAX_CAND, SPACE_MAX_PAGE_QUERIES = 4096, 64   # include/rdx.h rdx_space_rescore's / rdx_space_distances' limits
 TOPIC_MAX_N, TOPIC_MAX_TOPICS, TOPIC_MAX_TAGS, TOPIC_MAX_DIM = 1024, 32, 64, 4096   # include/rdx.h rdx_topic_boost's limits
 
 
@@ -76,6 +78,7 @@ SYMBOLS = {
     "rdx_index_add_bf16": (_i, [_vp, _vp, _i64, _i]),
     "rdx_index_add_stored": (_i, [_vp, _vp, _i64, _i]),
     "rdx_index_update": (_i, [_vp, _vp, _vp, _i64, _i]),
+    "rdx_index_update_stored": (_i, [_vp, _vp, _vp, _i64, _i]),
     "rdx_index_get": (_i, [_vp, _vp, _i64, _vp, _i]),
     "rdx_index_compact": (_i, [_vp, _vp, _i64]),
     "rdx_index_set_row_ids": (_i, [_vp, _i64, _vp, _i64, _i]),
@@ -129,6 +132,10 @@ SYMBOLS = {
     "rdx_meta_stats": (_i, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "rdx_meta_set_query": (_i, [_vp, _vp, _i, _vp, _i]),
     "rdx_meta_filter": (_i, [_vp, _i64, _vp, _vp, _i, _vp]),
+    "rdx_space_measure": (_i, [_i, _i, _vp, _i64, _i, _vp, _vp, _vp]),
+    "rdx_space_lift": (_i, [_i, _i, _i, _vp, _i64, _i, _i, _vp, _vp, _vp]),
+    "rdx_space_rescore": (_i, [_i, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rdx_space_distances": (_i, [_i, _i, _vp, _i, _i, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp]),
 }
 
 

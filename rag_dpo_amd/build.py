@@ -172,6 +172,11 @@ def build_lib(force: bool = False, verbose: bool = False, extra_flags=(), out: s
                 any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in topic.values()):
             raise RuntimeError("the topic boost kernels (topic_kernel.hpp) spill or were not found — refused:\n" +
                                "\n".join(f"  {k}: {v}" for k, v in topic.items()))
+        space = {k: v for k, v in res.items() if "k_space" in k}
+        if len(space) < 5 or any("spill_vgprs" not in v or "scratch_bytes" not in v for v in space.values()) or \
+                any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in space.values()):
+            raise RuntimeError("the ip / l2 space kernels (space_kernel.hpp) spill or were not found — refused:\n" +
+                               "\n".join(f"  {k}: {v}" for k, v in space.items()))
         # kernels that are given an occupancy target (amdgpu_waves_per_eu: the latency-bound attention kernel E12) pay for a miss
         # silently, in scratch traffic: refused as well (a variant build with extra flags may spill: it is nobody's product)
         slow = {k: v for k, v in res.items() if "k_enc_attention_mfma" in k and (v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0))}

@@ -25,6 +25,9 @@ always librdx (rag_dpo_amd.engine.HipIndex): there is no CPU search path in this
 Distances keep Chroma's cosine convention: distance = 1 - cos, ascending (so that
 `similarity_score = 1/(1+distance)` reference retriever.py:39-42 and the 0.80 relevance threshold
 reference validators.py:64-81 keep their meaning). The search itself is exact (brute force), not HNSW.
+metadata={"hnsw:space": "ip"} / "l2" give Chroma's other two spaces (distance 1 - q.x, squared Euclidean distance) on the same
+engine, exactly: rag_dpo_amd/spaces.py. Such a collection keeps its embeddings as given, runs on one device, and takes fp32 rows.
+An absent "hnsw:space" means cosine here (chromadb's own default is l2).
 """
 from __future__ import annotations
 
@@ -114,11 +117,14 @@ class Collection:
         self.name = name
         self.metadata = dict(metadata or {})
         space = self.metadata.get("hnsw:space", "cosine")
-        if space != "cosine":
-            raise ValueError(f"only the cosine space is implemented (the reference uses 'hnsw:space': 'cosine'), got {space!r}")
+        if space not in ("cosine", "ip", "l2"):
+            raise ValueError(f"hnsw:space must be 'cosine' (the reference's, and the default here), 'ip' or 'l2', got {space!r}")
+        self._space_exp_hint: Optional[int] = None   # an "ip" / "l2" store's persisted scale (rag_dpo_amd/spaces.py)
         self._device = device
         if engine_factory is None:
             devs = list(devices) if devices is not None else _devices_from_env()
+            if devs is not None and len(devs) > 1 and space != "cosine":
+                raise ValueError(f"the {space!r} space runs on one device in this version: no devices= / RDX_DEVICES")
             if devs is not None and len(devs) > 1:
                 from .multi_device import multi_device_factory
                 engine_factory = multi_device_factory(devs)
@@ -154,7 +160,16 @@ class Collection:
 
     def _ensure_engine(self, dim: int):
         if self._engine is None:
-            self._engine = self._factory(dim, self._device)
+            space = self.metadata.get("hnsw:space", "cosine")
+            if space == "cosine":
+                self._engine = self._factory(dim, self._device)
+            else:       # the same engine over lifted rows, behind a wrapper that returns the space's exact distances
+                from . import spaces as S
+                if dim % 4 or S.lifted_dim(space, dim) > 4096:
+                    raise ValueError(f"the {space!r} space needs a dimension that is a multiple of 4, at most {4096 - S.lifted_dim(space, 0)}")
+                inner = self._factory(S.lifted_dim(space, dim), self._device)
+                self._engine = S.SpaceEngine(space, inner, scale_exp=self._space_exp_hint,
+                                             factory=lambda: self._factory(S.lifted_dim(space, dim), self._device))
             self._dim = dim
         elif dim != self._dim:
             raise ValueError(f"Embedding dimension {dim} does not match collection dimensionality {self._dim}")
@@ -708,7 +723,10 @@ class Collection:
             if q.shape[1] != self._dim:
                 raise ValueError(f"Embedding dimension {q.shape[1]} does not match collection dimensionality {self._dim}")
             scores, rows, counts = self._engine.search(q, int(n_results), **self._search_args(where, where_document))
-            dist = (np.float32(1.0) - scores).astype(np.float32)   # Chroma cosine distance, fp32 like chromadb
+            if getattr(self._engine, "returns_distances", False):
+                dist = scores                                       # "ip" / "l2": the wrapper's exact distances (spaces.py)
+            else:
+                dist = (np.float32(1.0) - scores).astype(np.float32)   # Chroma cosine distance, fp32 like chromadb
             out_ids, out_docs, out_meta, out_dist, out_emb = [], [], [], [], []
             for b in range(nq):
                 rr = rows[b, : counts[b]].tolist()
@@ -757,6 +775,8 @@ class Collection:
             r = torch.empty((nq, k), dtype=torch.int64, device=dev)
             c = torch.empty((nq,), dtype=torch.int32, device=dev)
             self._engine.search_device(q, k, s, r, c, mask=args.get("mask"))
+            if getattr(self._engine, "returns_distances", False):
+                return s, r, c
             return (1.0 - s), r, c            # Chroma cosine distance, fp32 (padding entries: distance +inf, row -1)
 
     def ids_of(self, rows) -> List[List[str]]:
@@ -811,6 +831,8 @@ class Collection:
                     hdr["xcd_shares"] = [round(x, 5) for x in self._engine.xcd_shares()]
                 except Exception:
                     pass
+            if getattr(self._engine, "scale_exp", None) is not None:
+                hdr["space_scale_exp"] = int(self._engine.scale_exp)   # speed only: the lift is redone from the raw rows at load
             json.dump(hdr, f)
             f.flush()
             os.fsync(f.fileno())
@@ -896,6 +918,10 @@ class Collection:
         with open(os.path.join(path, "collection.json"), encoding="utf-8") as f:
             meta = json.load(f)
         self.metadata = meta.get("metadata") or {}
+        if self.metadata.get("hnsw:space", "cosine") not in ("cosine", "ip", "l2"):
+            raise ValueError(f"{path}: unknown hnsw:space {self.metadata.get('hnsw:space')!r}")
+        if meta.get("space_scale_exp") is not None:
+            self._space_exp_hint = int(meta["space_scale_exp"])
         n = int(meta.get("rows", 0))
         self._snap_rows = n
         self._snap_format = int(meta.get("format", 2))

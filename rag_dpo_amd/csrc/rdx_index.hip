@@ -1222,17 +1222,24 @@ static int stage_ids(rdx_index* h, const int64_t* ids, int64_t n, int space, con
     return RDX_OK;
 }
 
-extern "C" int rdx_index_update(rdx_index* h, const int64_t* row_ids, const float* rows, int64_t n, int space) {
-    if (!h || n < 0 || (n > 0 && (!row_ids || !rows))) return fail(RDX_ERR_INVALID, "rdx_index_update: bad argument");
+static int update_impl(const char* fn, rdx_index* h, const int64_t* row_ids, const float* rows, int64_t n, int space, bool verbatim) {
+    if (!h || n < 0 || (n > 0 && (!row_ids || !rows))) return fail(RDX_ERR_INVALID, std::string(fn) + ": bad argument");
     RDX_TRY(check_space(space));
     if (n == 0) return RDX_OK;
     std::lock_guard<std::mutex> lk(h->mu);
     RDX_TRY(finish_pending(h, nullptr));
-    if (h->compact) return fail(RDX_ERR_STATE, "rdx_index_update takes fp32 rows: not available on an index with a compact (bf16) master");
+    if (h->compact) return fail(RDX_ERR_STATE, std::string(fn) + " takes fp32 rows: not available on an index with a compact (bf16) master");
     RDX_TRY(set_device(h));
     const int64_t* d_ids = nullptr;
     RDX_TRY(stage_ids(h, row_ids, n, space, &d_ids));
-    return ingest(h, rows, false, n, space, 0, d_ids);
+    return ingest(h, rows, false, n, space, 0, d_ids, verbatim);
+}
+
+extern "C" int rdx_index_update(rdx_index* h, const int64_t* row_ids, const float* rows, int64_t n, int space) {
+    return update_impl("rdx_index_update", h, row_ids, rows, n, space, false);
+}
+extern "C" int rdx_index_update_stored(rdx_index* h, const int64_t* row_ids, const float* rows, int64_t n, int space) {
+    return update_impl("rdx_index_update_stored", h, row_ids, rows, n, space, true);
 }
 
 extern "C" int rdx_index_get(rdx_index* h, const int64_t* row_ids, int64_t n, float* out, int space) {

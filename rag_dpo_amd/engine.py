@@ -144,6 +144,25 @@ class HipIndex(_Handle):
             raise ValueError("update: rows must be [len(row_ids)][dim]")
         L.check(self._lib.rdx_index_update(self._h, _np_ptr(ids), _np_ptr(a), ids.shape[0], L.RDX_HOST))
 
+    def update_stored(self, row_ids, rows):
+        """update() for rows that are stored values (spaces.py's lifted rows): written verbatim"""
+        ids = np.ascontiguousarray(row_ids, dtype=np.int64)
+        a = np.ascontiguousarray(rows, dtype=np.float32)
+        if a.ndim != 2 or a.shape != (ids.shape[0], self.dim):
+            raise ValueError("update_stored: rows must be [len(row_ids)][dim]")
+        L.check(self._lib.rdx_index_update_stored(self._h, _np_ptr(ids), _np_ptr(a), ids.shape[0], L.RDX_HOST))
+
+    def get_device(self, row_ids, out):
+        """get() with torch CUDA tensors: row_ids int64 [n], out fp32 [n][dim] on this index's device; complete on return (the call
+        waits for the device first: include/rdx.h, calls without a stream argument)"""
+        import torch
+        n = row_ids.numel()
+        if not (row_ids.is_cuda and out.is_cuda and row_ids.device.index == self.device and out.device.index == self.device
+                and row_ids.dtype == torch.int64 and out.dtype == torch.float32 and row_ids.is_contiguous() and out.is_contiguous()
+                and out.numel() == n * self.dim):
+            raise ValueError(f"get_device: expected int64 [n] and fp32 [n][{self.dim}] contiguous tensors on cuda:{self.device}")
+        L.check(self._lib.rdx_index_get(self._h, ctypes.c_void_p(row_ids.data_ptr()), n, ctypes.c_void_p(out.data_ptr()), L.RDX_DEVICE))
+
     def get(self, row_ids) -> np.ndarray:
         ids = np.ascontiguousarray(row_ids, dtype=np.int64)
         out = np.empty((ids.shape[0], self.dim), dtype=np.float32)
@@ -389,6 +408,70 @@ class MetaStore(_Handle):
     def filter_device(self, rows: int, out_bits, base_bits=None):
         """torch int32 tensors on the store's device, enqueued on the current torch stream: nothing crosses PCIe"""
         _filter_device(self._lib.rdx_meta_filter, (self._h, int(rows)), self.device, (int(rows) + 31) // 32, out_bits, base_bits)
+
+
+# ---- the "ip" / "l2" spaces (include/rdx.h rdx_space_*; rag_dpo_amd/spaces.py drives them) ------------------------------------
+def _space_ptrs(*tensors):
+    dev = tensors[0].device
+    for t in tensors:
+        if t is not None and (not t.is_cuda or t.device != dev or not t.is_contiguous()):
+            raise ValueError("the rdx_space_* calls take contiguous torch tensors on one CUDA device")
+    return dev, [ctypes.c_void_p(t.data_ptr()) if t is not None else None for t in tensors]
+
+
+def space_measure(kind: int, rows):
+    """rows fp32 [n][dim] on the device -> (lifted_sq fp64 [n], bad int32 [n]) there, enqueued on the current torch stream"""
+    import torch
+    lib = L.load(require_gpu=True)
+    n, dim = rows.shape
+    sq = torch.empty(n, dtype=torch.float64, device=rows.device)
+    bad = torch.empty(n, dtype=torch.int32, device=rows.device)
+    dev, (pr, ps, pb) = _space_ptrs(rows, sq, bad)
+    L.check(lib.rdx_space_measure(dev.index, int(kind), pr, n, dim, ps, pb, ctypes.c_void_p(HipIndex._raw_stream(dev))))
+    return sq, bad
+
+
+def space_lift(kind: int, rows, scale_exp: int, is_query: bool = False):
+    """rows fp32 [n][dim] on the device -> (engine rows fp32 [n][engine dim], bad int32 [n])"""
+    import torch
+    lib = L.load(require_gpu=True)
+    n, dim = rows.shape
+    out = torch.empty((n, dim + 4 if kind == L.SPACE_L2 else dim), dtype=torch.float32, device=rows.device)
+    bad = torch.empty(n, dtype=torch.int32, device=rows.device)
+    dev, (pr, po, pb) = _space_ptrs(rows, out, bad)
+    L.check(lib.rdx_space_lift(dev.index, int(kind), int(bool(is_query)), pr, n, dim, int(scale_exp), po, pb,
+                               ctypes.c_void_p(HipIndex._raw_stream(dev))))
+    return out, bad
+
+
+def space_rescore(kind: int, queries, cand_vecs, cand_rows, cand_scores, cand_counts, k: int, scale_exp: int, guard: float):
+    """-> (dist f32 [nq][k], rows i64 [nq][k], counts i32 [nq], proven i32 [nq]) of the candidates [nq][kp]"""
+    import torch
+    lib = L.load(require_gpu=True)
+    nq, dim = queries.shape
+    kp = cand_rows.shape[1]
+    dev = queries.device
+    work = torch.empty((nq, kp), dtype=torch.float32, device=dev)
+    od = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    orow = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    oc = torch.empty(nq, dtype=torch.int32, device=dev)
+    pv = torch.empty(nq, dtype=torch.int32, device=dev)
+    _, p = _space_ptrs(queries, cand_vecs, cand_rows, cand_scores, cand_counts, work, od, orow, oc, pv)
+    L.check(lib.rdx_space_rescore(dev.index, int(kind), p[0], nq, dim, p[1], p[2], p[3], p[4], int(kp), int(k), int(scale_exp),
+                                  float(guard), p[5], p[6], p[7], p[8], p[9], ctypes.c_void_p(HipIndex._raw_stream(dev))))
+    return od, orow, oc, pv
+
+
+def space_distances(kind: int, queries, vecs, scale_exp: int, allow_bits, first_row: int, out, col0: int):
+    """out[b][col0 + r] = distance(query b, engine row r of the page `vecs`), +inf where bit first_row + r of allow_bits is clear"""
+    lib = L.load(require_gpu=True)
+    nq, dim = queries.shape
+    n = vecs.shape[0]
+    if out.dim() != 2 or out.shape[0] != nq or col0 < 0 or col0 + n > out.shape[1]:
+        raise ValueError("space_distances: the page does not fit the output")
+    dev, p = _space_ptrs(queries, vecs, allow_bits, out)
+    L.check(lib.rdx_space_distances(dev.index, int(kind), p[0], nq, dim, p[1], n, int(scale_exp), p[2], int(first_row),
+                                    ctypes.c_void_p(out.data_ptr() + 4 * col0), out.shape[1], ctypes.c_void_p(HipIndex._raw_stream(dev))))
 
 
 def l2_normalize(x: np.ndarray, device: int = 0) -> np.ndarray:

@@ -111,6 +111,8 @@ class ShardedSearcher:
 
     def __init__(self, shard, group: Optional[dist.ProcessGroup] = None, device=None, host_staged: bool = False,
                  always_exchange: bool = False):
+        if getattr(shard, "returns_distances", False):   # rag_dpo_amd/spaces.py: the merge ranks cosine scores, descending
+            raise ValueError("sharded search serves the cosine space only in this version: an 'ip' / 'l2' engine runs on one device")
         self.shard = shard
         self.group = group
         self.host_staged = host_staged
