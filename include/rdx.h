@@ -141,7 +141,14 @@ int rdx_index_set_row_ids(rdx_index* h, int64_t first_row, const int64_t* ids, i
  * block-scaled int8 copy of the corpus (built by the first search that needs it, +1 B per element; not persisted), with an error
  * bound of its own per query: 0 never, 1 whenever the shape allows, 2 for more than 256 queries on at least 2^20 rows (speed only);
  * "refine_pilot" 0..64 (default 4): an int8 search re-scores its hits in two rounds, the refine_pilot * k best coarse hits first
- * and then the hits within E_q of their exact k-th score; 0 = one band of 2 E_q below the k-th coarse score (speed only). */
+ * and then the hits within E_q of their exact k-th score; 0 = one band of 2 E_q below the k-th coarse score (speed only);
+ * "refine_spill" 0/1/2 (default 2): a query with more scan hits than the refine kernel's list in LDS holds (7 168) is answered from a
+ * list in HBM (up to 40 960 hits per query, allocated by the first search that needs it: 320 MB per 1 024 queries) instead of by the
+ * fallback passes: 0 never, 1 on every MFMA-path search, 2 where "coarse_i8" = 2 chose the int8 pass (speed only);
+ * "i8_sample_mul" 0/1/2/4/8 (default 0): the threshold sample of an int8 search, in multiples of the fp16 pass's (every 64th 32-row
+ * block on a large shard): 0 = 2 where "coarse_i8" = 2 chose the int8 pass with "refine_spill" in force, 8 elsewhere (speed only);
+ * developer options "refine_list" (0 = automatic, or 32..7168: upper bound on the LDS list's entries) and "spill_cap" (0 = automatic,
+ * or 32..40960: upper bound on the HBM list's entries) drive the two lists' limits at small sizes (tests). */
 int rdx_index_set_option(rdx_index* h, const char* name, int64_t value);
 
 /* The main scan's tile shares of the 8 XCDs (1.0 = an eighth; option "xcd_balance"): learned from the workgroups' own time stamps

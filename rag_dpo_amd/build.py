@@ -177,6 +177,14 @@ def build_lib(force: bool = False, verbose: bool = False, extra_flags=(), out: s
                 any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in space.values()):
             raise RuntimeError("the ip / l2 space kernels (space_kernel.hpp) spill or were not found — refused:\n" +
                                "\n".join(f"  {k}: {v}" for k, v in space.items()))
+        # k_refine / k_refine_spill run 1024 threads at the 128-register limit (refine_kernel.hpp): a spill would be paid on every search
+        refine = {k: v for k, v in res.items() if "k_refine" in k}
+        if extra_flags:
+            pass   # (a variant build may spill: it is nobody's product)
+        elif len(refine) < 2 or any("spill_vgprs" not in v or "scratch_bytes" not in v for v in refine.values()) or \
+                any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in refine.values()):
+            raise RuntimeError("the refine kernels (refine_kernel.hpp) spill or were not found — refused:\n" +
+                               "\n".join(f"  {k}: {v}" for k, v in refine.items()))
         # kernels that are given an occupancy target (amdgpu_waves_per_eu: the latency-bound attention kernel E12) pay for a miss
         # silently, in scratch traffic: refused as well (a variant build with extra flags may spill: it is nobody's product)
         slow = {k: v for k, v in res.items() if "k_enc_attention_mfma" in k and (v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0))}

@@ -42,6 +42,8 @@ struct SearchPlan {
     int64_t sample_rows = 0;
     double expected_per_query = 0.0;   // candidates per query a random corpus would emit with this sample
     uint32_t capw = 0, list_cap = 0;
+    bool spill = false;                // queries with more than list_cap hits are answered from a list in HBM (k_refine_spill), not by the fallback
+    uint32_t spill_cap = 0;            // entries of that list per query
     int k_sel = 0;                     // rank of the sampled score the threshold is taken from (< k: speculative)
     float slack = 0.f;
     bool balance = false;              // XCD-weighted split of the main scan's tiles
@@ -104,6 +106,12 @@ struct rdx_index {
     int coarse_i8 = 2;       // option: main scan on int8 MFMA — 0 never, 1 whenever the shape allows, 2 (default) large batches on large shards
     int refine_pilot = 4;    // option: int8 searches find their re-score band in two rounds — the pilot*k best coarse hits first, then what lies
                              // within E_q of their exact k-th score (refine_kernel.hpp); 0 = one band of 2E_q below c_k
+    int i8_sample_mul = 0;   // option: how many times denser than the fp16 pass's an int8 search samples its threshold — 1, 2, 4, 8, or 0 (default):
+                             // I8_AUTO_SAMPLE_MUL where int8 was chosen automatically (those searches spill), 8 where it was forced
+    int refine_spill = 2;    // option: k_refine_spill for queries with more hits than the LDS list — 0 never, 1 always, 2 (default) where int8
+                             // was chosen automatically
+    int refine_list = 0;     // developer option: upper bound on the LDS list's entries (>= 32), 0 = automatic
+    int spill_cap = 0;       // developer option: upper bound on the spill list's entries per query (>= 32), 0 = SPILL_CAP
     int coarse_bits = 0;     // the last search's coarse pass: 16, 8, or 0 (exact path only); rdx_search_last_coarse_bits
     int i8_backoff = 0;      // searches left during which automatic choice (coarse_i8 = 2) keeps the fp16 pass (set when an int8 search
                              // sent more than 1 in 64 of its queries to the fallback passes: rows too crowded for its band, see adapt_sampling)
@@ -122,6 +130,7 @@ struct rdx_index {
     // int8 coarse pass: corpus copy [cap][dim_pad] in corpus_off8 order + s_b per 32-row block + the largest eps_b (built by the first
     // search that takes the path, rows [0, i8_valid) current; not persisted) and the per-search query copy, scales, bounds, thresholds
     DevBuf c8, sblk, eps8, qshadow8, tq8, eq8, nq8, thr8, taus8, twoe8;
+    DevBuf spill, spill_q;   // k_refine_spill: [nq_pad][spill_cap] hit lists, [nq_pad] queue of the queries that use them (first spilling plan)
     int64_t i8_valid = 0;
     // end-of-search mailbox in pinned host memory (k_finish writes it over PCIe; the host spins on its sequence number)
     Mailbox* mbox = nullptr;          // host address
@@ -365,6 +374,8 @@ extern "C" int rdx_set_wait_policy(int spin_us, int sleep_us) {
 // (c4: 890 -> ~430 per query, c3: 4500 -> ~700). k_refine verifies every query (c_k - 2E >= T); a failed one takes the
 // fallback passes, which use rank k, and switches speculation off for the next searches (structured corpora, where
 // "every div-th tile" is not a random sample; h.spec_backoff counts them down in enqueue_scan, after this read).
+constexpr int I8_AUTO_SAMPLE_MUL = 2;   // (plan_search: the int8 sample where int8 is chosen automatically)
+
 static int speculative_rank(const rdx_index& h, int k, int depth, int64_t sample_rows) {
     if (!h.spec_tau || depth != 0 || h.spec_backoff != 0 || k <= 1) return k;
     const double lam = 2.0 * (double)k * (double)sample_rows / (double)std::max<int64_t>(h.rows, 1);
@@ -424,7 +435,13 @@ static int plan_search(const rdx_index& h, int64_t nq, int k, int depth, bool ho
     // Automatic (option 2): more than one query tile on a shard of at least 2^20 rows, where the MFMA rate decides the scan's time;
     // the bootstrap, the second pass and the exact scan stay fp16 / fp32.
     const bool i8_shape = depth == 0 && nq > 128 && h.dim_pad % 128 == 0 && h.dim_pad <= 1024 && h.force_bn == 0;
-    p.i8 = i8_shape && (h.coarse_i8 == 1 || (h.coarse_i8 == 2 && h.i8_backoff == 0 && nq > 256 && h.rows >= ((int64_t)1 << 20)));
+    const bool i8_auto = i8_shape && h.coarse_i8 == 2 && h.i8_backoff == 0 && nq > 256 && h.rows >= ((int64_t)1 << 20);
+    p.i8 = i8_shape && (h.coarse_i8 == 1 || i8_auto);
+    // Queries with more hits than the LDS list are answered from a list in HBM (k_refine_spill) instead of the fallback passes: where
+    // int8 was chosen automatically (option refine_spill = 2), or on every MFMA-path search (1). Everywhere else the plan is what it
+    // was before the spill list existed, to the counter.
+    p.spill = h.refine_spill == 1 || (h.refine_spill == 2 && i8_auto);
+    p.spill_cap = p.spill ? (uint32_t)(h.spill_cap ? std::min(h.spill_cap, SPILL_CAP) : SPILL_CAP) : 0u;
 
     // queries per workgroup: 64 (tile resident in LDS), 128, 256. 257..384 queries run as three 128-query tiles rather than
     // one full and one half-empty 256-query tile (measured at 1M x 1024, B = 384: 0.78 vs 0.84 ms; tools/bn_sweep.py)
@@ -471,7 +488,10 @@ static int plan_search(const rdx_index& h, int64_t nq, int k, int depth, bool ho
     // 0; every 8th, 2 640 hits, 11.8 ms per batch (iid) and 5 000 hits, 12.4 ms (embedding-like). The factor is measured at d = 1024 only; E_q relative to the score spread depends on d (both
     // quantisation errors grow like the element spacing, the spread like 1/sqrt(d)), so at other widths it is a choice, not a derivation:
     // what protects those shapes is the fallback, and automatic choice backs off from int8 when it overflows (adapt_sampling).
-    if (p.i8 && depth == 0) div = std::max(1, div / 8);
+    // With the spill list a long list costs a longer gather, not a second pass, and the pilot re-scores a few hundred rows whatever the
+    // hit count: where int8 is chosen automatically (the searches that spill) the sample is I8_AUTO_SAMPLE_MUL times the fp16 pass's
+    // instead of 8 (measured, profiles/i8_sample/ab_c4.txt). Option i8_sample_mul sets the factor for every int8 search.
+    if (p.i8 && depth == 0) div = std::max(1, div / (h.i8_sample_mul ? h.i8_sample_mul : (i8_auto && p.spill ? I8_AUTO_SAMPLE_MUL : 8)));
     int64_t n_sched = (p.n_tiles + div - 1) / div;
     // whole rounds only: the bootstrap takes as long as its busiest stream, so 77 tiles on 64 streams cost two tiles' time for
     // 1.2 tiles' worth of threshold (a 1.25 M-row shard at B = 1024: 53 -> 27 us of a 2.26 ms search); thin the sample to the
@@ -520,7 +540,10 @@ static int plan_search(const rdx_index& h, int64_t nq, int k, int depth, bool ho
     double exp_hits = (1.5 * k * (double)h.rows / (double)std::max<int64_t>(p.sample_rows, 1) + k) / p.n_streams;
     // int8: the scan emits coarse + E_q >= T, E_q ~ 0.6 sigma of a random corpus' scores at d = 1024 — about 16x what the fp16 pass
     // would emit from the same sample (measured at 10 M x 1024 with the 8x denser sample above: 2 640 hits per query against 146;
-    // DESIGN.md §5; a measured factor at d = 1024, not derived for other widths)
+    // DESIGN.md §5; a measured factor at d = 1024, not derived for other widths). The ratio falls as the sample thins — the E_q
+    // band is a fixed width, the fp16 count grows with rows / sample_rows: 7 900 hits against 970 at every 64th block, a factor 8 —
+    // so at the thinner samples x16 over-estimates: segments up to twice as long as needed (address space only), and the
+    // dense_sample trigger below fires at up to 6x instead of 3x a random corpus' hits (profiles/i8_sample/ab_c4.txt).
     if (p.i8) exp_hits *= 16.0;
     p.expected_per_query = exp_hits * p.n_streams;
     // (slots cost address space, not bandwidth: only occupied slots are ever touched)
@@ -547,6 +570,7 @@ static int plan_search(const rdx_index& h, int64_t nq, int k, int depth, bool ho
     uint32_t list_cap = 1024;
     while (list_cap < (uint32_t)REFINE_LIST && list_cap < 16.0 * exp_hits * p.n_streams) list_cap *= 2;
     p.list_cap = std::min<uint32_t>(list_cap, REFINE_LIST);
+    if (h.refine_list) p.list_cap = std::min<uint32_t>(p.list_cap, (uint32_t)h.refine_list);
     return RDX_OK;
 }
 
@@ -656,8 +680,17 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
     hipLaunchKernelGGL(k_refine, dim3((int)p.nq), dim3(1024), lds, st, h->cand.as<uint2>(), h->cntw.as<uint32_t>(), p.n_streams, p.capw,
                        p.list_cap, p.k, h->two_e(), p.i8 ? h->twoe8.as<float>() : nullptr, h->qhat.as<float>(), h->mv(), h->dim, h->row_base,
                        h->row_map, io.score, io.row, io.count, h->exact_list.as<int32_t>(), h->ctr.as<RefineCounters>(),
-                       p.i8 ? h->taus8.as<float>() : h->tau.as<float>(), p.i8 ? 1.0f : sp.inv_scale2, h->refine_pilot, fin);
+                       p.i8 ? h->taus8.as<float>() : h->tau.as<float>(), p.i8 ? 1.0f : sp.inv_scale2, h->refine_pilot, p.spill_cap,
+                       h->spill_q.as<int32_t>(), p.spill ? FinishArgs{} : fin);
     HIP_TRY(hipGetLastError());
+    if (p.spill) {   // the search's last kernel when the plan spills: it ends the search whether or not a query was queued
+        hipLaunchKernelGGL(k_refine_spill, dim3((int)p.nq), dim3(1024), 0, st, h->spill.as<uint2>(), p.spill_cap, h->spill_q.as<int32_t>(),
+                           h->cand.as<uint2>(), h->cntw.as<uint32_t>(), p.n_streams, p.capw, p.k, h->two_e(),
+                           p.i8 ? h->twoe8.as<float>() : nullptr, h->qhat.as<float>(), h->mv(), h->dim, h->row_base, h->row_map, io.score, io.row,
+                           io.count, h->exact_list.as<int32_t>(), h->ctr.as<RefineCounters>(),
+                           p.i8 ? h->taus8.as<float>() : h->tau.as<float>(), p.i8 ? 1.0f : sp.inv_scale2, h->refine_pilot, fin);
+        HIP_TRY(hipGetLastError());
+    }
     mark(h, p, st, 5);
     return RDX_OK;
 }
@@ -706,6 +739,10 @@ static int enqueue_search(rdx_index* h, const SearchPlan& p, const SearchIO& io,
         RDX_TRY(h->cand.ensure((size_t)p.nq_pad * p.n_streams * p.capw * 8));
         RDX_TRY(h->setmax.ensure((size_t)p.nq_pad * std::max(std::max(p.n_sets, p.n_sets_b), p.boot_sets) * 4));
         if (p.stamps) RDX_TRY(h->wgt.ensure((size_t)p.grid * 16));
+        if (p.spill) {
+            RDX_TRY(h->spill.ensure((size_t)p.nq_pad * p.spill_cap * 8));
+            RDX_TRY(h->spill_q.ensure((size_t)p.nq_pad * 4));
+        }
     }
     if (!h->ctr_ready) {   // zeroed once; afterwards the k_finish of every search leaves it zeroed for the next one
         HIP_TRY(hipMemsetAsync(h->ctr.p, 0, sizeof(RefineCounters), st));
@@ -797,6 +834,8 @@ static void adapt_sampling(rdx_index* h, const SearchPlan& p, const SearchCounts
     } else if (h->i8_backoff > 0 && p.nq > 256) {
         --h->i8_backoff;
     }
+    if (std::getenv("RDX_DEBUG_HITS"))   // developer (tools/ab_i8_sample.py): the longest hit list of the search and how many queries spilled
+        std::fprintf(stderr, "hits max %d spilled %d\n", h->mbox->max_hits, h->mbox->n_spill);
     if (h->mbox->spec_fail > 0) h->spec_backoff = 64;   // a speculative threshold was too high: provable thresholds for a while
     // three times the candidates a random corpus would emit: the corpus is clustered — a denser threshold sample for the next searches
     // (plan_search; re-examined every 256 searches: the denser sample's own emission is what then keeps it on)
@@ -1032,7 +1071,7 @@ extern "C" int rdx_index_destroy(rdx_index* h) {
     free_master(h->master, h->raw16, h->den);
     if (h->shadow) (void)hipFree(h->shadow);
     if (h->row_map) (void)hipFree(h->row_map);
-    for (DevBuf* b : {&h->staging, &h->qraw, &h->qhat, &h->qshadow, &h->tau, &h->cntw, &h->cand, &h->setmax, &h->exact_list,
+    for (DevBuf* b : {&h->staging, &h->qraw, &h->qhat, &h->qshadow, &h->tau, &h->cntw, &h->cand, &h->setmax, &h->exact_list, &h->spill, &h->spill_q,
                       &h->iota, &h->dense, &h->ctr, &h->bad, &h->o_score, &h->o_row, &h->o_count, &h->mask, &h->ids,
                       &h->r_list, &h->r_q, &h->r_s, &h->r_r, &h->r_c, &h->c8, &h->sblk, &h->eps8, &h->qshadow8, &h->tq8,
                       &h->eq8, &h->nq8, &h->thr8, &h->taus8, &h->twoe8})
@@ -1087,6 +1126,22 @@ extern "C" int rdx_index_set_option(rdx_index* h, const char* name, int64_t valu
     else if (n == "refine_pilot") {
         if (value < 0 || value > 64) return fail(RDX_ERR_INVALID, "refine_pilot must be 0 (one band) or 1..64 (pilot of that many times k hits)");
         h->refine_pilot = (int)value;
+    }
+    else if (n == "i8_sample_mul") {
+        if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return fail(RDX_ERR_INVALID, "i8_sample_mul must be 0 (automatic), 1, 2, 4 or 8");
+        h->i8_sample_mul = (int)value;
+    }
+    else if (n == "refine_spill") {
+        if (value < 0 || value > 2) return fail(RDX_ERR_INVALID, "refine_spill must be 0 (never), 1 (always) or 2 (automatic)");
+        h->refine_spill = (int)value;
+    }
+    else if (n == "refine_list") {
+        if (value != 0 && (value < 32 || value > REFINE_LIST)) return fail(RDX_ERR_INVALID, "refine_list must be 0 (automatic) or 32.." + std::to_string(REFINE_LIST));
+        h->refine_list = (int)value;
+    }
+    else if (n == "spill_cap") {
+        if (value != 0 && (value < 32 || value > SPILL_CAP)) return fail(RDX_ERR_INVALID, "spill_cap must be 0 (automatic) or 32.." + std::to_string(SPILL_CAP));
+        h->spill_cap = (int)value;
     }
     else if (n == "spec_tau") {
         h->spec_tau = value != 0;

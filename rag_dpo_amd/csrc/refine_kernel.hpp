@@ -9,6 +9,9 @@ constexpr int REFINE_PMAX = 1024;    // most candidates re-scored exactly per qu
 constexpr int REFINE_LIST = 7168;    // most scan hits gathered per query (56 KiB of LDS: with the 22 KiB of static LDS TWO blocks fit a CU's 160 KiB —
                                      // at B = 1024 the kernel runs in two rounds instead of four); more -> second pass / exact full scan
 constexpr int REFINE_STREAMS = 512;  // most (query, stream) segments
+constexpr int SPILL_CAP = 40960;     // most hits of a query whose list lives in HBM instead (k_refine_spill; plan_search SearchPlan::spill): 2.4x the
+                                     // longest list seen at c4 with the thinnest sample (17 264 hits, every 64th block; 13 358 at the default's
+                                     // every 32nd; DESIGN.md §5 "Spill list"), 320 MB for 1 024 queries; more -> second pass
 
 struct RefineCounters {   // one per index, zeroed before every search
     unsigned long long emitted;
@@ -21,6 +24,8 @@ struct RefineCounters {   // one per index, zeroed before every search
     // scoring kernel started (kept as max(~clock): zero = unset) and when the last block of its select kernel ended (100 MHz ticks)
     unsigned long long t_first_inv, t_last;
     int done;             // blocks of the search's last kernel that have finished (the last one runs the end-of-search work)
+    int n_spill;          // queries k_refine queued for k_refine_spill (more hits than the LDS list holds)
+    int max_hits;         // most hits of one query (developer: RDX_DEBUG_HITS)
     int pad1;
 };
 
@@ -33,6 +38,7 @@ struct Mailbox {
     int oob, spec_fail;
     unsigned long long t_first, t_last;   // profile = 3, exact path (see RefineCounters)
     unsigned long long wg_times[1024]; // [grid][2] start/end stamps of the main scan's workgroups (XCD balancing)
+    int n_spill, max_hits;             // (RefineCounters)
 };
 
 // K6. End of every search: (1) small results of HOST callers go from the device result buffers to pinned host staging,
@@ -82,6 +88,10 @@ __device__ __forceinline__ void finish_body(const FinishArgs& f) {   // all thre
         mb->oob = ctr->oob;
         mb->spec_fail = ctr->spec_fail;
         ctr->spec_fail = 0;
+        mb->n_spill = ctr->n_spill;
+        mb->max_hits = ctr->max_hits;
+        ctr->n_spill = 0;
+        ctr->max_hits = 0;
         mb->t_first = ~ctr->t_first_inv;
         mb->t_last = ctr->t_last;
         ctr->t_first_inv = 0;
@@ -134,7 +144,7 @@ __device__ __forceinline__ void finish_if_last(const FinishArgs& f) {
 //   is re-scored after them: a hit outside S1 and S2 has exact <= coarse + E_q < X1 <= X, strictly below the k-th score.
 #ifdef RDX_REFINE_STAMPS   // developer build (tools/refine_stamps.py): where k_refine spends its time (block 0's phases, 100 MHz wall clock)
 __device__ unsigned long long g_refine_stamps[16];
-#define RDX_RSTAMP(i) do { __syncthreads(); if (blockIdx.x == 0 && threadIdx.x == 0) g_refine_stamps[i] = wall_clock64(); } while (0)
+#define RDX_RSTAMP(i) do { __syncthreads(); if (!SPILL && blockIdx.x == 0 && threadIdx.x == 0) g_refine_stamps[i] = wall_clock64(); } while (0)   // (k_refine only)
 #else
 #define RDX_RSTAMP(i) do { } while (0)
 #endif
@@ -146,7 +156,13 @@ __device__ __forceinline__ float sub_down(float a, float b) {
     return d;
 }
 
-__device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, const uint32_t* __restrict__ cntw,
+// The list of a query's hits lives in LDS (SPILL = false: k_refine, at most list_cap <= REFINE_LIST entries) or in the query's
+// row of the spill buffer in HBM (SPILL = true: k_refine_spill, at most spill_cap entries). k_refine queues a query with more hits
+// than its list holds in spill_q (spill_cap > 0, no segment overflowed) and k_refine_spill, launched behind it, answers it: the
+// same code, so which rows are re-scored does not depend on where the list lives. The hits were counted by k_refine.
+template <bool SPILL>
+__device__ __forceinline__ void refine_query(const int q, uint2* __restrict__ spill, uint32_t spill_cap, int32_t* __restrict__ spill_q,
+                                                const uint2* __restrict__ cand, const uint32_t* __restrict__ cntw,
                                                 int n_streams, uint32_t capw, uint32_t list_cap, int k, float two_e,
                                                 const float* __restrict__ two_e_q, const float* __restrict__ qhat, MasterView master, int dim,
                                                 int64_t row_base, const int64_t* __restrict__ row_map,
@@ -155,14 +171,13 @@ __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, con
                                                 RefineCounters* __restrict__ ctr, const float* __restrict__ tau, float inv_scale2,
                                                 int pilot) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint2* list = reinterpret_cast<uint2*>(smem);                        // [REFINE_LIST]
+    uint2* list = SPILL ? spill + (int64_t)q * spill_cap : reinterpret_cast<uint2*>(smem);   // [spill_cap] : [REFINE_LIST]
     __shared__ __attribute__((aligned(16))) uint32_t hist[HIST_WORDS];
     __shared__ uint32_t bc[4];
     __shared__ uint32_t seg_off[REFINE_STREAMS + 1];
     __shared__ float s_s[REFINE_PMAX];
     __shared__ int64_t s_r[REFINE_PMAX];
     __shared__ int n_p, overflow;
-    const int q = blockIdx.x;
     float* o_s = out_score + (int64_t)q * k;
     int64_t* o_r = out_row + (int64_t)q * k;
     if (threadIdx.x == 0) overflow = 0;
@@ -195,20 +210,34 @@ __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, con
     __syncthreads();
     const uint32_t m = seg_off[n_streams];
     RDX_RSTAMP(1);
-    if (threadIdx.x == 0) atomicAdd(&ctr->emitted, (unsigned long long)m);
-    if (overflow || m > list_cap) {
-        if (threadIdx.x == 0) exact_list[atomicAdd(&ctr->n_exact, 1)] = q;
-        return;
+    if (!SPILL) {
+        if (threadIdx.x == 0) {
+            atomicAdd(&ctr->emitted, (unsigned long long)m);
+            atomicMax(&ctr->max_hits, (int)m);
+        }
+        if (overflow || m > list_cap) {
+            if (threadIdx.x == 0) {
+                if (!overflow && m <= spill_cap) spill_q[atomicAdd(&ctr->n_spill, 1)] = q;
+                else exact_list[atomicAdd(&ctr->n_exact, 1)] = q;
+            }
+            return;
+        }
     }
     if (m == 0 || k == 0) {
         rank_and_write(s_s, s_r, 0, k, o_s, o_r, out_count + q);
         return;
     }
-    // gather: thread w walks segment w (independent loads across threads)
-    for (int w = threadIdx.x; w < n_streams; w += blockDim.x) {
-        const uint32_t a = seg_off[w], b = seg_off[w + 1];
-        const uint2* seg = cand + ((int64_t)q * n_streams + w) * capw;
-        for (uint32_t i = a; i < b; ++i) list[i] = seg[i - a];
+    // gather: one thread per ENTRY — its segment is the last w with seg_off[w] <= i (binary search of the prefix in LDS), so every
+    // thread has loads in flight and none depends on another (a thread per segment was 64 of 1024 threads at c4, each walking
+    // 40-125 dependent 8-byte loads). The entries keep their order: segment after segment.
+    for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) {
+        int lo = 0, hi = n_streams;                         // seg_off[lo] <= i < seg_off[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (seg_off[mid] <= i) lo = mid;
+            else hi = mid;
+        }
+        list[i] = cand[((int64_t)q * n_streams + lo) * capw + (i - seg_off[lo])];
     }
     __syncthreads();
     RDX_RSTAMP(2);
@@ -347,38 +376,44 @@ __device__ __forceinline__ void refine_query(const uint2* __restrict__ cand, con
         // scores lie closer together than the coarse pass can tell apart, so the band holds hundreds to thousands of them). Until
         // round 4 such a query paid the exact full scan of the WHOLE corpus (7 ms per 4 queries at 10 M rows: an embedding-like corpus
         // ran at 2 % of the N(0,1) corpus' speed). The band is small next to the corpus: its members are compacted to the front of the
-        // list (every thread reads its <= 7 entries, then — behind a barrier — writes the members back), re-scored exactly in place
+        // list (every thread reads 7 entries, then — behind a barrier — writes the members back), re-scored exactly in place
         // (exact score over coarse score), the k-th largest exact score is found by the radix select, and only what reaches it is ranked.
+        // The list is compacted in rounds of 7 entries per thread (the LDS list is one round; a spill list takes up to
+        // spill_cap / 7168): a round's members are written behind the earlier rounds' — at or below the round's own first entry, and
+        // every entry up to the round's end was read before the barrier, so nothing unread is overwritten.
         __shared__ int wtot[16];
-        const int c = (int)((m + blockDim.x - 1) / blockDim.x);      // <= REFINE_LIST / 1024 = 7
-        uint2 mine[7];
-        bool keep[7];
-        int cnt = 0;
+        int base_out = 0;
+        for (uint32_t r0 = 0; r0 < m; r0 += 7u * blockDim.x) {
+            uint2 mine[7];
+            bool keep[7];
+            int cnt = 0;
 #pragma unroll
-        for (int j = 0; j < 7; ++j) {
-            const uint32_t i = threadIdx.x * c + j;
-            keep[j] = false;
-            if (j < c && i < m) {
-                mine[j] = list[i];
-                const float cs = __uint_as_float(mine[j].x);
-                keep[j] = cs >= t2 && cs < c1;
+            for (int j = 0; j < 7; ++j) {
+                const uint32_t i = r0 + threadIdx.x * 7 + j;
+                keep[j] = false;
+                if (i < m) {
+                    mine[j] = list[i];
+                    const float cs = __uint_as_float(mine[j].x);
+                    keep[j] = cs >= t2 && cs < c1;
+                }
+                cnt += keep[j] ? 1 : 0;
             }
-            cnt += keep[j] ? 1 : 0;
-        }
-        int incl = cnt;
+            int incl = cnt;
 #pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += t;
-        }
-        if (lane == 63) wtot[wave] = incl;
-        __syncthreads();                                              // (also: every thread has read its chunk)
-        int pos = incl - cnt;
-        for (int w = 0; w < wave; ++w) pos += wtot[w];
+            for (int off = 1; off < 64; off <<= 1) {
+                const int t = __shfl_up(incl, off, 64);
+                if (lane >= off) incl += t;
+            }
+            if (lane == 63) wtot[wave] = incl;
+            __syncthreads();                                          // (also: every thread has read its entries of this round)
+            int pos = base_out + incl - cnt;
+            for (int w = 0; w < wave; ++w) pos += wtot[w];
+            for (int w = 0; w < nw; ++w) base_out += wtot[w];
 #pragma unroll
-        for (int j = 0; j < 7; ++j)
-            if (keep[j]) list[pos++] = mine[j];
-        __syncthreads();
+            for (int j = 0; j < 7; ++j)
+                if (keep[j]) list[pos++] = mine[j];
+            __syncthreads();
+        }
         // (two rounds: the p - done rows of S2 were compacted; S1, already exact in the ranking arrays, goes behind them — S1 and
         //  S2 are disjoint subsets of the m hits, so p <= m slots)
         for (int i = threadIdx.x; i < done; i += blockDim.x) list[p - done + i] = make_uint2(__float_as_uint(s_s[i]), (uint32_t)s_r[i]);
@@ -451,9 +486,28 @@ __global__ __launch_bounds__(1024) void k_refine(const uint2* __restrict__ cand,
                                                 float* __restrict__ out_score, int64_t* __restrict__ out_row,
                                                 int32_t* __restrict__ out_count, int32_t* __restrict__ exact_list,
                                                 RefineCounters* __restrict__ ctr, const float* __restrict__ tau, float inv_scale2,
-                                                int pilot, const FinishArgs fin) {
-    refine_query(cand, cntw, n_streams, capw, list_cap, k, two_e, two_e_q, qhat, master, dim, row_base, row_map, out_score, out_row, out_count,
-                 exact_list, ctr, tau, inv_scale2, pilot);
+                                                int pilot, uint32_t spill_cap, int32_t* __restrict__ spill_q, const FinishArgs fin) {
+    refine_query<false>((int)blockIdx.x, nullptr, spill_cap, spill_q, cand, cntw, n_streams, capw, list_cap, k, two_e, two_e_q, qhat, master, dim,
+                        row_base, row_map, out_score, out_row, out_count, exact_list, ctr, tau, inv_scale2, pilot);
+    finish_if_last(fin);
+}
+
+// K4b. The queries k_refine queued (more hits than its LDS list holds; SearchPlan::spill): one block per POSSIBLE query, the blocks
+// beyond the queue's length leave at once. The list is the query's row of `spill` ([nq_pad][spill_cap] in HBM, L2-resident while
+// a block works on it); no dynamic LDS. Launched behind k_refine only when the plan enables spilling, and then the search's last
+// kernel.
+__global__ __launch_bounds__(1024) void k_refine_spill(uint2* __restrict__ spill, uint32_t spill_cap, const int32_t* __restrict__ spill_q,
+                                                      const uint2* __restrict__ cand, const uint32_t* __restrict__ cntw,
+                                                      int n_streams, uint32_t capw, int k, float two_e,
+                                                      const float* __restrict__ two_e_q, const float* __restrict__ qhat, MasterView master, int dim,
+                                                      int64_t row_base, const int64_t* __restrict__ row_map,
+                                                      float* __restrict__ out_score, int64_t* __restrict__ out_row,
+                                                      int32_t* __restrict__ out_count, int32_t* __restrict__ exact_list,
+                                                      RefineCounters* __restrict__ ctr, const float* __restrict__ tau, float inv_scale2,
+                                                      int pilot, const FinishArgs fin) {
+    if ((int)blockIdx.x < ctr->n_spill)
+        refine_query<true>(spill_q[blockIdx.x], spill, spill_cap, nullptr, cand, cntw, n_streams, capw, spill_cap, k, two_e, two_e_q, qhat, master,
+                           dim, row_base, row_map, out_score, out_row, out_count, exact_list, ctr, tau, inv_scale2, pilot);
     finish_if_last(fin);
 }
 
