@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rdx_limits.hpp"
+
 namespace rdx {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -26,8 +28,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int TILE_ROWS = 256;                    // corpus rows per scan tile / shadow block
-constexpr int BK = 64;                            // k elements per k-step image
 constexpr int KSTEP_BYTES = TILE_ROWS * BK * 2;   // 32 KiB
 constexpr int MAX_DIM = 4096;
 

@@ -12,6 +12,7 @@
 #include "k_rows.hpp"
 #include "refine_kernel.hpp"
 #include "scan_kernel.hpp"
+#include "search_plan.hpp"
 
 using namespace rdx;
 
@@ -21,36 +22,6 @@ struct HostOut {
     int64_t* row;
     int32_t* count;
     bool stale;
-};
-
-// What a search of (rows, nq, k, options) launches: every choice, made by plan_search before anything is enqueued
-struct SearchPlan {
-    int64_t nq = 0;
-    int k = 0, depth = 0, nq_pad = 0;  // depth 0 = the caller's batch; 1 = the second-chance batch of overflowed queries
-    int prof = 0;                      // option "profile" (depth 0 only)
-    bool exact_only = false;           // the exact full scan alone; the fields down to `stamps` are the MFMA path's
-    int bn = 0, nqt = 0, grid = 0, G = 0, n_streams = 0, n_sets = 0;   // G workgroups per XCD and query tile, 8 G streams
-    bool res = false;                  // the 64-query tile stays resident in LDS
-    int64_t n_tiles = 0, n_blocks32 = 0;
-    bool use_boot = false;             // bootstrap: k_boot over boot_units 32-row blocks, or k_scan<EPI_SETMAX> (the rest)
-    int64_t boot_units = 0;
-    int boot_sets = 0, bn_b = 0, nqt_b = 0, n_sets_b = 0, div = 1, n_sets_used = 0;
-    int64_t boot_tiles = 0, boot_wave_off = 0;   // the tile bootstrap's ScanParams n_tiles, wave_off, row_off, span
-    int boot_row_off = 0, boot_span = 0;
-    bool use_small = false;            // k_scan_small as the main scan
-    bool i8 = false;                   // the main scan runs on the int8 copies (k_scan<..., I8>; DESIGN.md §5 "int8 coarse pass")
-    int64_t sample_rows = 0;
-    double expected_per_query = 0.0;   // candidates per query a random corpus would emit with this sample
-    uint32_t capw = 0, list_cap = 0;
-    bool spill = false;                // queries with more than list_cap hits are answered from a list in HBM (k_refine_spill), not by the fallback
-    uint32_t spill_cap = 0;            // entries of that list per query
-    int k_sel = 0;                     // rank of the sampled score the threshold is taken from (< k: speculative)
-    float slack = 0.f;
-    bool balance = false;              // XCD-weighted split of the main scan's tiles
-    int bulk_it = 0, xlo[9] = {};
-    bool stamps = false;               // the main scan's workgroups stamp their times
-    bool ride = false, big_copy = false;   // host results: with k_finish into pinned staging, or D2H copies
-    size_t b_s = 0, b_r = 0, b_c = 0;  // result bytes: scores, rows, counts
 };
 
 // the caller's buffers of one search chunk (device addresses)
@@ -93,31 +64,10 @@ struct rdx_index {
     hipStream_t own_stream = nullptr;
     std::mutex mu;
 
-    // options
-    int force_exact = 0, force_fast = 0, profile = 0, retry = 1, xcd_balance = 1, fuse_epilogue = 1, force_bn = 0;
-    int half_boot = 1;       // option: 129..256 queries take their threshold sample as two 128-query tiles per sampled corpus tile
-    int small_scan = 1;      // option: k_scan_small (split-K over all rows) as the main scan of small launches
-    int split_boot = 1;      // option: k_boot (K loop split over the waves) for the threshold bootstrap of small launches
-    int fuse_finish = 1;     // option: the end-of-search work runs in the last block of the search's last kernel (0: its own launch k_finish)
-    int spec_tau = 1;        // option: speculative scan threshold (rank < k of the sample, verified by k_refine)
-    int dense_sample = 0;    // searches left with a threshold sample twice as dense (set when a search emitted 3x a random corpus' candidates)
-    int spread_boot = 1;     // option: a tile bootstrap (any not taken by k_boot) samples every div-th 32-row block instead of every div-th 256-row tile
-    int spec_backoff = 0;    // searches left during which the provable threshold is used (set when a speculation failed)
-    int coarse_i8 = 2;       // option: main scan on int8 MFMA — 0 never, 1 whenever the shape allows, 2 (default) large batches on large shards
-    int refine_pilot = 4;    // option: int8 searches find their re-score band in two rounds — the pilot*k best coarse hits first, then what lies
-                             // within E_q of their exact k-th score (refine_kernel.hpp); 0 = one band of 2E_q below c_k
-    int i8_sample_mul = 0;   // option: how many times denser than the fp16 pass's an int8 search samples its threshold — 1, 2, 4, 8, or 0 (default):
-                             // I8_AUTO_SAMPLE_MUL where int8 was chosen automatically (those searches spill), 8 where it was forced
-    int refine_spill = 2;    // option: k_refine_spill for queries with more hits than the LDS list — 0 never, 1 always, 2 (default) where int8
-                             // was chosen automatically
-    int refine_list = 0;     // developer option: upper bound on the LDS list's entries (>= 32), 0 = automatic
-    int spill_cap = 0;       // developer option: upper bound on the spill list's entries per query (>= 32), 0 = SPILL_CAP
-    int coarse_bits = 0;     // the last search's coarse pass: 16, 8, or 0 (exact path only); rdx_search_last_coarse_bits
-    int i8_backoff = 0;      // searches left during which automatic choice (coarse_i8 = 2) keeps the fp16 pass (set when an int8 search
-                             // sent more than 1 in 64 of its queries to the fallback passes: rows too crowded for its band, see adapt_sampling)
-    double xw[8] = {1, 1, 1, 1, 1, 1, 1, 1};   // relative speed of the XCDs as the last main scans showed it (sum 8)
-    int sample_div = 64;
-    int64_t cand_cap = 0;   // 0 = automatic
+    // what a plan reads (search_plan.hpp), beside shape()
+    SearchOptions opt;      // the search options of rdx_index_set_option
+    SearchAdapt adapt;      // what finished searches feed back
+    int coarse_bits = 0;    // the last search's coarse pass: 16, 8, or 0 (exact path only); rdx_search_last_coarse_bits
     int64_t row_base = 0;   // added to every returned row id (global ids of a shard)
     int64_t* row_map = nullptr;   // [cap] local row -> returned row id (strictly increasing), or NULL = local + row_base
 
@@ -146,6 +96,7 @@ struct rdx_index {
 
     float scale() const { return std::ldexp(1.0f, scale_log2); }
     float two_e() const { return 2.0f * (1.0e-3f + 2.5e-7f * (float)dim_pad); }   // see DESIGN.md "error bound"
+    PlanShape shape() const { return PlanShape{rows, dim_pad, ksteps, n_cu, two_e()}; }
 };
 
 // a `where` bitmap kept resident in HBM between searches (the reference's filters are a handful of fixed shapes)
@@ -273,7 +224,7 @@ static int launch_scan(rdx_index* h, const ScanParams& p, int grid, hipStream_t 
 }
 
 template <int EPI>
-static int launch_scan_bn(rdx_index* h, int bn, bool res, const ScanParams& p, int grid, hipStream_t st) {
+static int launch_scan_bn(rdx_index* h, int bn, bool res, bool fused, const ScanParams& p, int grid, hipStream_t st) {
     // NTT (4th template argument): one query tile -> every corpus byte is read by exactly one workgroup -> non-temporal loads
     if (bn == 64) {
         if (p.nqt == 1) return res ? launch_scan<64, EPI, true, true>(h, p, grid, st) : launch_scan<64, EPI, false, true>(h, p, grid, st);
@@ -286,10 +237,9 @@ static int launch_scan_bn(rdx_index* h, int bn, bool res, const ScanParams& p, i
 #else
         constexpr bool HAVE_FUSED = true;
 #endif
-        // option fuse_epilogue (default on: +1 % at B = 1024 since the static wave priority went in): with an even
-        // number of k-steps per tile the emit check of a tile rides with the first k-step of the next one
+        // SearchPlan::fused: the emit check of a tile rides with the first k-step of the next one
         if constexpr (HAVE_FUSED) {
-            if ((p.ksteps & 1) == 0 && h->fuse_epilogue) {
+            if (fused) {
                 if (p.nqt == 1) return launch_scan<256, EPI, false, true, true>(h, p, grid, st);
                 return launch_scan<256, EPI, false, false, true>(h, p, grid, st);
             }
@@ -299,15 +249,14 @@ static int launch_scan_bn(rdx_index* h, int bn, bool res, const ScanParams& p, i
     return launch_scan<256, EPI, false>(h, p, grid, st);
 }
 
-// the int8 main pass (plan_search p.i8: 256-query tiles, several of them, so never the one-tile nt variants)
-static int launch_scan_i8(rdx_index* h, const ScanParams& p, int grid, hipStream_t st) {
+// the int8 main pass (plan_search p.i8: 256-query tiles, several of them, so never the one-tile nt variants). Its k-steps are 128
+// dimensions wide, half as many as the plan counted: the fused variant needs THEIR number even (dim_pad a multiple of 256).
+static int launch_scan_i8(rdx_index* h, bool fused, const ScanParams& p, int grid, hipStream_t st) {
 #ifndef RDX_CHECK_BOUNDS
-    if ((p.ksteps & 1) == 0 && h->fuse_epilogue) return launch_scan<256, EPI_EMIT, false, false, true, true>(h, p, grid, st);
+    if (fused && (p.ksteps & 1) == 0) return launch_scan<256, EPI_EMIT, false, false, true, true>(h, p, grid, st);
 #endif
     return launch_scan<256, EPI_EMIT, false, false, false, true>(h, p, grid, st);
 }
-
-static const int K_FAST_MAX = 256;   // larger k goes through the exact full scan
 
 // exact full scan for the queries listed in d_list[0..n_list)
 static int run_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, const uint32_t* d_allow, float* d_score,
@@ -345,9 +294,7 @@ static int run_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, con
 
 // Host callers (HostOut): small results travel with the end-of-search kernel into pinned staging and are copied to the
 // caller's buffers by the CPU once the mailbox says the search is complete; large ones use D2H copies. When a fallback pass
-// had to rewrite some results afterwards they are copied again (HostOut::stale).
-static const size_t PIN_MAX = 256 * 1024;   // results up to this size ride with k_finish (one block writing over PCIe)
-
+// had to rewrite some results afterwards they are copied again (HostOut::stale). (PIN_MAX: search_plan.hpp)
 static int copy_results_to_host(const HostOut& ho, const float* d_score, const int64_t* d_row, const int32_t* d_count, int64_t nq,
                                 int k, hipStream_t st) {
     if (k > 0) {
@@ -363,214 +310,6 @@ extern "C" int rdx_set_wait_policy(int spin_us, int sleep_us) {
     if (spin_us < 0 || sleep_us < 0 || sleep_us > 1000000) return fail(RDX_ERR_INVALID, "rdx_set_wait_policy: spin_us >= 0, 0 <= sleep_us <= 1000000");
     g_wait_spin_us.store(spin_us);
     g_wait_sleep_us.store(sleep_us);
-    return RDX_OK;
-}
-
-// Speculative threshold. The provable threshold is the k-th largest sampled score: k/S of the sample's
-// quantile scale where the corpus' k-th score sits at k/N — with a 1.6 % sample and k = 10 that is 60x the hits one
-// needs. The corpus' k-th score is ESTIMATED by the sample's j-th largest with j ~ k*S/N; taking the smallest j for
-// which fewer than k rows of the corpus lie above it (with a factor 2 for the 2E band the verification needs) with
-// probability <= 1e-7 per query (the count above the sample's j-th largest is N/S * Gamma(j)) cuts the hits 2-6x
-// (c4: 890 -> ~430 per query, c3: 4500 -> ~700). k_refine verifies every query (c_k - 2E >= T); a failed one takes the
-// fallback passes, which use rank k, and switches speculation off for the next searches (structured corpora, where
-// "every div-th tile" is not a random sample; h.spec_backoff counts them down in enqueue_scan, after this read).
-constexpr int I8_AUTO_SAMPLE_MUL = 2;   // (plan_search: the int8 sample where int8 is chosen automatically)
-
-static int speculative_rank(const rdx_index& h, int k, int depth, int64_t sample_rows) {
-    if (!h.spec_tau || depth != 0 || h.spec_backoff != 0 || k <= 1) return k;
-    const double lam = 2.0 * (double)k * (double)sample_rows / (double)std::max<int64_t>(h.rows, 1);
-    double term = std::exp(-lam), cdf = term;   // P(Poisson(lam) <= j - 1)
-    int j = 1;
-    while (1.0 - cdf > 1e-7 && j < k) {
-        term *= lam / j;
-        cdf += term;
-        ++j;
-    }
-    return std::min(k, j);
-}
-
-// bulk: what the slowest XCD should get, dealt interleaved to everybody (whole iterations of all streams);
-// tail: the rest, one contiguous range per XCD holding what that XCD should get beyond the bulk
-static void plan_xcd_split(const rdx_index& h, SearchPlan* p) {
-    const double wmin = *std::min_element(h.xw, h.xw + 8);
-    p->bulk_it = (int)std::max<int64_t>(0, (int64_t)std::floor((double)p->n_tiles * wmin / 8.0 / p->G) - 1);
-    const int64_t t0 = (int64_t)p->bulk_it * p->n_streams, tail = p->n_tiles - t0;
-    double want[8], sum = 0;
-    for (int x = 0; x < 8; ++x) sum += (want[x] = std::max(0.0, (double)p->n_tiles * h.xw[x] / 8.0 - (double)p->bulk_it * p->G));
-    double acc = 0;
-    for (int x = 0; x <= 8; ++x) {
-        p->xlo[x] = (int)(t0 + std::llround((double)tail * (sum > 0 ? acc / sum : x / 8.0)));
-        if (x < 8) acc += want[x];
-    }
-    p->xlo[8] = (int)p->n_tiles;
-}
-
-// Every decision of a search of nq (<= one launch) queries at `depth`, from the index's state and options alone: no HIP call,
-// nothing written. The internal checks fail here, before anything is enqueued.
-static int plan_search(const rdx_index& h, int64_t nq, int k, int depth, bool host_out, SearchPlan* out) {
-    SearchPlan& p = *out = SearchPlan{};
-    p.nq = nq;
-    p.k = k;
-    p.depth = depth;
-    p.nq_pad = (int)((nq + 255) / 256 * 256);
-    p.prof = depth == 0 ? h.profile : 0;
-    p.b_s = (size_t)nq * k * 4;
-    p.b_r = (size_t)nq * k * 8;
-    p.b_c = (size_t)nq * 4;
-    p.ride = host_out && p.b_s + p.b_r + p.b_c <= PIN_MAX;
-    p.big_copy = host_out && !p.ride;
-
-    // small problems and huge k are served by the exact full scan alone (one fp32 read of the corpus)
-    // Round 2 re-measured the crossover (B = 4: exact path 0.060 / 0.099 / 0.129 ms at 24 k / 40 k / 60 k rows, MFMA path 0.081 / 0.085 /
-    // 0.087): the exact path costs ceil(nq / 4) passes of (1.28 us per 1000 rows + 10 us) on top of what both paths share, the
-    // MFMA path ~60 us more than that share whatever the size — and beyond 32 Ki rows the select no longer holds a score row in
-    // registers. (The rule it replaces, nq * rows <= 4 M below 64 Ki rows, sent 64 queries x 60 k rows through 16 exact passes.)
-    const int64_t exact_passes = (nq + 3) / 4;
-    const bool small = h.rows <= 32768 && (double)exact_passes * ((double)h.rows * 1.28e-3 + 10.0) <= 60.0;   // (any size: 600 queries on 1000 rows are 150 passes)
-    p.exact_only = h.force_exact || k > K_FAST_MAX || k == 0 || h.rows < 1 || (small && !h.force_fast);
-    if (p.exact_only) return RDX_OK;
-
-    // The main scan on int8 MFMA (twice the dot products per clock of fp16, half the bytes; DESIGN.md §5 "int8 coarse pass"): the
-    // caller's batch only (not the second pass), in 256-query tiles, at most 8 k-steps of 128 dimensions (|D| < 2^24: exact in fp32).
-    // Automatic (option 2): more than one query tile on a shard of at least 2^20 rows, where the MFMA rate decides the scan's time;
-    // the bootstrap, the second pass and the exact scan stay fp16 / fp32.
-    const bool i8_shape = depth == 0 && nq > 128 && h.dim_pad % 128 == 0 && h.dim_pad <= 1024 && h.force_bn == 0;
-    const bool i8_auto = i8_shape && h.coarse_i8 == 2 && h.i8_backoff == 0 && nq > 256 && h.rows >= ((int64_t)1 << 20);
-    p.i8 = i8_shape && (h.coarse_i8 == 1 || i8_auto);
-    // Queries with more hits than the LDS list are answered from a list in HBM (k_refine_spill) instead of the fallback passes: where
-    // int8 was chosen automatically (option refine_spill = 2), or on every MFMA-path search (1). Everywhere else the plan is what it
-    // was before the spill list existed, to the counter.
-    p.spill = h.refine_spill == 1 || (h.refine_spill == 2 && i8_auto);
-    p.spill_cap = p.spill ? (uint32_t)(h.spill_cap ? std::min(h.spill_cap, SPILL_CAP) : SPILL_CAP) : 0u;
-
-    // queries per workgroup: 64 (tile resident in LDS), 128, 256. 257..384 queries run as three 128-query tiles rather than
-    // one full and one half-empty 256-query tile (measured at 1M x 1024, B = 384: 0.78 vs 0.84 ms; tools/bn_sweep.py)
-    p.bn = nq <= 64 ? 64 : (nq <= 128 ? 128 : ((nq > 256 && nq <= 384 && !p.i8) ? 128 : 256));
-    if (h.force_bn && (nq + h.force_bn - 1) / h.force_bn <= 32) p.bn = h.force_bn;   // developer option: queries per workgroup
-    p.nqt = (int)((nq + p.bn - 1) / p.bn);
-    p.grid = std::max(8, h.n_cu / 8 * 8);
-    const int wpx = p.grid / 8;
-    if (p.nqt > wpx) return fail(RDX_ERR_STATE, "internal: query chunk larger than one scan launch");
-    p.G = wpx / p.nqt;
-    p.n_streams = 8 * p.G;
-    if (p.n_streams > REFINE_STREAMS) return fail(RDX_ERR_STATE, "internal: more streams than the refine kernel gathers");
-    p.n_sets = p.n_streams * SETS_PER_STREAM;
-    p.n_tiles = (h.rows + 255) / 256;
-    if (p.n_tiles * h.ksteps >= ((int64_t)1 << 31)) return fail(RDX_ERR_STATE, "shard too large for one scan launch");
-    // the 64-query tile stays resident in LDS when all its k-step images fit (no DMA, no barrier in the main loop)
-    p.res = p.bn == 64 && (size_t)h.ksteps * 8192 + 512 <= 160 * 1024 - 1024;
-    // bootstrap sample: every div-th tile. More rows sampled = tighter tau = fewer hits; keep the expected hits
-    // per query (~1.3 k rows/sample_rows) around 4000/... of the refine list and the sample >= max(64k, 8192) rows
-    // Bootstrap geometry. 129..256 queries run their main scan as ONE 256-query tile per workgroup, but their bootstrap samples
-    // ~130 tiles: as one tile per workgroup that is half the CUs working through 16 dependent k-steps of 64 KB each (36 us at
-    // c3). As TWO 128-query tiles per sampled tile every CU works, a k-step moves 48 KB and takes 1.4 instead of 2.25 us
-    // (DESIGN.md §10's table): option "half_boot" (default 1).
-    p.bn_b = p.bn;
-    p.nqt_b = p.nqt;
-    int ns_b = p.n_streams;
-    if (h.half_boot && p.bn == 256 && p.nqt == 1) {
-        p.bn_b = 128;
-        p.nqt_b = 2;
-        ns_b = 8 * (wpx / 2);
-    }
-    p.n_sets_b = ns_b * SETS_PER_STREAM;
-    const int64_t want_rows = std::max<int64_t>(64 * (int64_t)k, 8192);
-    int div = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(h.sample_div, h.rows / want_rows), 3000 / std::max(k, 1)));
-    if (depth > 0) div = std::max(1, div / 8);   // second chance: 8x denser sample -> a threshold that sees the cluster
-    // A corpus whose last searches emitted far more candidates than a random corpus would (clustered rows: a query's neighbours are
-    // one document's chunks, and a thin sample holds too few of them to place the threshold among them) gets twice the sample for a
-    // while: +0.25 ms of bootstrap on a 10 M-row scan, against thousands of surplus candidates per query to gather and re-score
-    // (measured, embedding-like corpus at c4: 19.6 -> 16.2 ms per batch; N(0,1) corpus: +1 %, which is why it is not the default).
-    else if (h.dense_sample > 0 && div > 1) div = std::max(1, div / 2);
-    // The int8 pass emits every row whose coarse score is within E_q (~0.6 sigma of a random corpus' scores at d = 1024) of the
-    // threshold: a threshold closer to the corpus' k-th score pays for its sample many times over. Measured on c4 (the refine list
-    // holds 7 168 hits): every 64th block 7 900 hits per query, 573 of 1 024 queries re-run; every 32nd 5 400 / 134; every 16th 2 600 /
-    // 0; every 8th, 2 640 hits, 11.8 ms per batch (iid) and 5 000 hits, 12.4 ms (embedding-like). The factor is measured at d = 1024 only; E_q relative to the score spread depends on d (both
-    // quantisation errors grow like the element spacing, the spread like 1/sqrt(d)), so at other widths it is a choice, not a derivation:
-    // what protects those shapes is the fallback, and automatic choice backs off from int8 when it overflows (adapt_sampling).
-    // With the spill list a long list costs a longer gather, not a second pass, and the pilot re-scores a few hundred rows whatever the
-    // hit count: where int8 is chosen automatically (the searches that spill) the sample is I8_AUTO_SAMPLE_MUL times the fp16 pass's
-    // instead of 8 (measured, profiles/i8_sample/ab_c4.txt). Option i8_sample_mul sets the factor for every int8 search.
-    if (p.i8 && depth == 0) div = std::max(1, div / (h.i8_sample_mul ? h.i8_sample_mul : (i8_auto && p.spill ? I8_AUTO_SAMPLE_MUL : 8)));
-    int64_t n_sched = (p.n_tiles + div - 1) / div;
-    // whole rounds only: the bootstrap takes as long as its busiest stream, so 77 tiles on 64 streams cost two tiles' time for
-    // 1.2 tiles' worth of threshold (a 1.25 M-row shard at B = 1024: 53 -> 27 us of a 2.26 ms search); thin the sample to the
-    // last full round instead, as long as it keeps the rows asked for above
-    if (n_sched > ns_b && n_sched % ns_b != 0) {
-        const int64_t full = n_sched / ns_b * ns_b;
-        const int div2 = (int)((p.n_tiles + full - 1) / full);
-        if ((p.n_tiles + div2 - 1) / div2 * 256 >= want_rows) {
-            div = div2;
-            n_sched = (p.n_tiles + div - 1) / div;
-        }
-    }
-    p.div = div;
-    // The sample as every div-th 32-ROW BLOCK (option "spread_boot", default 1) instead of every div-th 256-row tile: the same number
-    // of rows, eight times finer. Wave w of virtual tile j takes block (8 j + w) * div; the last virtual tile ends inside the corpus.
-    // It replaces the whole-rounds schedule above (n_sched becomes the number of virtual tiles) and applies to every bootstrap that
-    // k_boot does not take, whatever the batch size.
-    p.n_blocks32 = (h.rows + 31) / 32;
-    const int64_t n_virtual = ((p.n_blocks32 - 1) / div + 1) / 8;
-    p.boot_tiles = p.n_tiles;
-    p.boot_span = TILE_ROWS;
-    if (h.spread_boot && n_virtual >= 1) {   // wave w of sampled entry j: block (8 j + w) * div (scan_kernel.hpp ScanParams::wave_off)
-        n_sched = n_virtual;
-        p.boot_wave_off = (int64_t)(div - 1) * h.ksteps * 4096;
-        p.boot_row_off = (div - 1) * 32;
-        p.boot_span = (7 * div + 1) * 32;
-        p.boot_tiles = (n_virtual - 1) * (int64_t)div + 1;   // ceil(n_tiles / div) = n_virtual entries: the last block lies inside the corpus
-    }
-    p.sample_rows = n_sched * 256;
-    p.n_sets_used = (int)std::min<int64_t>(ns_b, n_sched) * SETS_PER_STREAM;
-    // Small launches (<= 64 queries and a sample of at most four 32-row blocks per CU): the split-K bootstrap k_boot — one
-    // 32-row block per workgroup, the k-steps dealt to the waves — instead of a few whole tiles of 16 dependent k-steps on
-    // a few CUs (scan_kernel.hpp K2b). Whole rounds of the CUs when more than one.
-    p.boot_units = std::min<int64_t>(p.n_blocks32, n_sched * 8);
-    if (p.boot_units > h.n_cu) p.boot_units = p.boot_units / h.n_cu * h.n_cu;
-    p.use_boot = h.split_boot && p.bn == BOOT_BN && p.nqt == 1 && p.boot_units <= 4 * (int64_t)h.n_cu;
-    // ... and the split-K main scan k_scan_small when the whole corpus is at most 32 such blocks per CU (scan_kernel.hpp K2c)
-    p.use_small = h.small_scan && p.bn == BOOT_BN && p.nqt == 1 && h.ksteps <= 16 && p.n_streams == p.grid &&
-                  p.n_blocks32 <= 32 * (int64_t)h.n_cu && p.n_blocks32 >= p.grid;
-    if (p.use_boot) {
-        p.sample_rows = p.boot_units * 32;
-        p.boot_sets = (int)p.boot_units * 4;
-        p.n_sets_used = p.boot_sets;
-    }
-    // slots per (query, stream) segment: 8x the expected hits, power of two, [32, 4096]
-    double exp_hits = (1.5 * k * (double)h.rows / (double)std::max<int64_t>(p.sample_rows, 1) + k) / p.n_streams;
-    // int8: the scan emits coarse + E_q >= T, E_q ~ 0.6 sigma of a random corpus' scores at d = 1024 — about 16x what the fp16 pass
-    // would emit from the same sample (measured at 10 M x 1024 with the 8x denser sample above: 2 640 hits per query against 146;
-    // DESIGN.md §5; a measured factor at d = 1024, not derived for other widths). The ratio falls as the sample thins — the E_q
-    // band is a fixed width, the fp16 count grows with rows / sample_rows: 7 900 hits against 970 at every 64th block, a factor 8 —
-    // so at the thinner samples x16 over-estimates: segments up to twice as long as needed (address space only), and the
-    // dense_sample trigger below fires at up to 6x instead of 3x a random corpus' hits (profiles/i8_sample/ab_c4.txt).
-    if (p.i8) exp_hits *= 16.0;
-    p.expected_per_query = exp_hits * p.n_streams;
-    // (slots cost address space, not bandwidth: only occupied slots are ever touched)
-    // (nq_pad * n_streams is 65,536 whatever the batch: 1024 slots = 512 MiB, 4096 = 2 GiB of the 288)
-    uint32_t capw = depth > 0 ? 4096 : 1024;
-    while (capw < 4096 && capw < 8.0 * exp_hits) capw *= 2;
-    if (h.cand_cap && depth == 0) capw = (uint32_t)std::min<int64_t>(h.cand_cap, 8191);
-    // the scan addresses candidate slots with 32-bit indices (scan_kernel.hpp emit_block)
-    if ((uint64_t)p.nq_pad * (uint64_t)p.n_streams * capw >= (1ull << 29)) return fail(RDX_ERR_STATE, "internal: candidate segments exceed the 32-bit slot index");
-    p.capw = capw;
-    p.k_sel = speculative_rank(h, k, depth, p.sample_rows);
-    // proven threshold: 2E below the k-th sampled score — plus, when the sample was summed in another order than the main scan
-    // sums (k_boot), twice the fp32 accumulation bound, so that the verification (c_k - 2E >= T, with c_k from the main
-    // scan's sums) cannot fail on a rounding difference between the two orders
-    p.slack = h.two_e() + ((p.use_boot != p.use_small) ? 2.0f * (float)h.dim_pad * 1.1920929e-7f : 0.0f);
-    // The eight XCDs do not finish equal shares at the same time (measured on c4: the last XCD 1.1-1.7 ms after the
-    // first of 16.5, always the same ones). Each XCD therefore gets a contiguous range of the tile schedule sized by
-    // its speed in the previous main scans (from the workgroups' own time stamps, damped) — no coordination
-    // inside the kernel, just a different static split. Large launches only.
-    p.balance = h.xcd_balance && depth == 0 && p.n_tiles >= 1024 && p.grid <= 512;
-    if (p.balance) plan_xcd_split(h, &p);
-    p.stamps = (p.balance || p.prof == 3) && p.grid <= 512;   // (Mailbox::wg_times holds 1024 stamps)
-    // LDS list of the gathered hits: 16x the expected count (heavy-tailed score distributions of structured corpora; a list overflow costs a second pass), at most REFINE_LIST
-    uint32_t list_cap = 1024;
-    while (list_cap < (uint32_t)REFINE_LIST && list_cap < 16.0 * exp_hits * p.n_streams) list_cap *= 2;
-    p.list_cap = std::min<uint32_t>(list_cap, REFINE_LIST);
-    if (h.refine_list) p.list_cap = std::min<uint32_t>(p.list_cap, (uint32_t)h.refine_list);
     return RDX_OK;
 }
 
@@ -638,10 +377,10 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
         pb.n_tiles = p.boot_tiles;
         pb.nqt = p.nqt_b;
         pb.n_sets = p.n_sets_b;
-        RDX_TRY(launch_scan_bn<EPI_SETMAX>(h, p.bn_b, p.bn_b == p.bn ? p.res : false, pb, p.grid, st));
+        RDX_TRY(launch_scan_bn<EPI_SETMAX>(h, p.bn_b, p.bn_b == p.bn ? p.res : false, false, pb, p.grid, st));
     }
     mark(h, p, st, 2);
-    if (p.depth == 0 && h->spec_backoff > 0) --h->spec_backoff;
+    if (p.depth == 0 && h->adapt.spec_backoff > 0) --h->adapt.spec_backoff;
     hipLaunchKernelGGL(k_tau, dim3(p.nq_pad), dim3(256), 0, st, h->setmax.as<float>(), p.use_boot ? p.boot_sets : p.n_sets_b, p.n_sets_used,
                        p.k_sel, p.k_sel == p.k ? p.slack * std::ldexp(1.0f, 2 * h->scale_log2) : 0.0f, (int)p.nq, h->tau.as<float>());
     HIP_TRY(hipGetLastError());
@@ -670,9 +409,9 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
         s8.sblk = h->sblk.as<float>();
         s8.qscale = h->tq8.as<float>();
         s8.shadow_bytes = (int64_t)h->cap * h->dim_pad;
-        RDX_TRY(launch_scan_i8(h, s8, p.grid, st));
+        RDX_TRY(launch_scan_i8(h, p.fused, s8, p.grid, st));
     } else {
-        RDX_TRY(launch_scan_bn<EPI_EMIT>(h, p.bn, p.res, sp, p.grid, st));
+        RDX_TRY(launch_scan_bn<EPI_EMIT>(h, p.bn, p.res, p.fused, sp, p.grid, st));
     }
     mark(h, p, st, 4);
     const size_t lds = (size_t)p.list_cap * 8;
@@ -680,7 +419,7 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
     hipLaunchKernelGGL(k_refine, dim3((int)p.nq), dim3(1024), lds, st, h->cand.as<uint2>(), h->cntw.as<uint32_t>(), p.n_streams, p.capw,
                        p.list_cap, p.k, h->two_e(), p.i8 ? h->twoe8.as<float>() : nullptr, h->qhat.as<float>(), h->mv(), h->dim, h->row_base,
                        h->row_map, io.score, io.row, io.count, h->exact_list.as<int32_t>(), h->ctr.as<RefineCounters>(),
-                       p.i8 ? h->taus8.as<float>() : h->tau.as<float>(), p.i8 ? 1.0f : sp.inv_scale2, h->refine_pilot, p.spill_cap,
+                       p.i8 ? h->taus8.as<float>() : h->tau.as<float>(), p.i8 ? 1.0f : sp.inv_scale2, p.pilot, p.spill_cap,
                        h->spill_q.as<int32_t>(), p.spill ? FinishArgs{} : fin);
     HIP_TRY(hipGetLastError());
     if (p.spill) {   // the search's last kernel when the plan spills: it ends the search whether or not a query was queued
@@ -688,7 +427,7 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
                            h->cand.as<uint2>(), h->cntw.as<uint32_t>(), p.n_streams, p.capw, p.k, h->two_e(),
                            p.i8 ? h->twoe8.as<float>() : nullptr, h->qhat.as<float>(), h->mv(), h->dim, h->row_base, h->row_map, io.score, io.row,
                            io.count, h->exact_list.as<int32_t>(), h->ctr.as<RefineCounters>(),
-                           p.i8 ? h->taus8.as<float>() : h->tau.as<float>(), p.i8 ? 1.0f : sp.inv_scale2, h->refine_pilot, fin);
+                           p.i8 ? h->taus8.as<float>() : h->tau.as<float>(), p.i8 ? 1.0f : sp.inv_scale2, p.pilot, fin);
         HIP_TRY(hipGetLastError());
     }
     mark(h, p, st, 5);
@@ -770,12 +509,12 @@ static int enqueue_search(rdx_index* h, const SearchPlan& p, const SearchIO& io,
             HIP_TRY(hipStreamSynchronize(st));
         }
         RDX_TRY(run_exact(h, h->iota.as<int32_t>(), (int)p.nq, p.k, io.allow, io.score, io.row, io.count, st, p.prof == 3,
-                          h->fuse_finish ? &fin : nullptr));
+                          p.fuse_finish ? &fin : nullptr));
         for (int i = 4; i <= 5; ++i) mark(h, p, st, i);
     } else {
-        RDX_TRY(enqueue_scan(h, p, io, st, h->fuse_finish ? fin : FinishArgs{}));
+        RDX_TRY(enqueue_scan(h, p, io, st, p.fuse_finish ? fin : FinishArgs{}));
     }
-    if (!h->fuse_finish) {
+    if (!p.fuse_finish) {
         hipLaunchKernelGGL(k_finish, dim3(1), dim3(1024), 0, st, fin);
         HIP_TRY(hipGetLastError());
     }
@@ -824,31 +563,33 @@ static int read_mailbox(rdx_index* h, const PendingSearch& ps, SearchCounts* c) 
 // the sampling state the next searches start from
 static void adapt_sampling(rdx_index* h, const SearchPlan& p, const SearchCounts& c) {
     if (p.depth != 0) return;
+    SearchAdapt& a = h->adapt;
     // Automatic int8 pass: its band is E_q wide (~0.6 sigma of a random corpus' scores at d = 1024). On rows that crowd around a
     // query's neighbours (a document's chunks) the hits can overflow the refine list and every such query pays the
     // fp16 second pass on top; when more than 1 in 64 queries of an int8 search did, the next 256 searches take the fp16 pass, after
     // which int8 is tried again. (Measured on the embedding-like c4 corpus: 5 000 hits per query, none re-run, int8 12.4 ms against
     // fp16 16.0 ms per batch — the safeguard is for corpora more crowded than that.)
-    if (p.i8 && h->coarse_i8 == 2 && !p.exact_only) {
-        if ((int64_t)c.n_exact * 64 > p.nq) h->i8_backoff = 256;
-    } else if (h->i8_backoff > 0 && p.nq > 256) {
-        --h->i8_backoff;
+    if (p.i8_auto && !p.exact_only) {
+        if ((int64_t)c.n_exact * 64 > p.nq) a.i8_backoff = 256;
+    } else if (a.i8_backoff > 0 && p.nq > 256) {
+        --a.i8_backoff;
     }
     if (std::getenv("RDX_DEBUG_HITS"))   // developer (tools/ab_i8_sample.py): the longest hit list of the search and how many queries spilled
         std::fprintf(stderr, "hits max %d spilled %d\n", h->mbox->max_hits, h->mbox->n_spill);
-    if (h->mbox->spec_fail > 0) h->spec_backoff = 64;   // a speculative threshold was too high: provable thresholds for a while
+    if (h->mbox->spec_fail > 0) a.spec_backoff = 64;   // a speculative threshold was too high: provable thresholds for a while
     // three times the candidates a random corpus would emit: the corpus is clustered — a denser threshold sample for the next searches
     // (plan_search; re-examined every 256 searches: the denser sample's own emission is what then keeps it on)
     if (!p.exact_only && p.expected_per_query > 0.0) {
         const double per_q = (double)c.emitted / (double)std::max<int64_t>(p.nq, 1);
-        if (per_q > (h->dense_sample > 0 ? 1.5 : 3.0) * p.expected_per_query) h->dense_sample = 256;
-        else if (h->dense_sample > 0) --h->dense_sample;
+        if (per_q > (a.dense_sample > 0 ? 1.5 : 3.0) * p.expected_per_query) a.dense_sample = 256;
+        else if (a.dense_sample > 0) --a.dense_sample;
     }
 }
 
 // the stamps arrived with the counters: re-weight the XCD shares for the next search
 static void reweight_xcds(rdx_index* h, const SearchPlan& p, rdx_search_stats* acc) {
     const unsigned long long* wt = h->mbox->wg_times;
+    double* const xw = h->adapt.xw;
     unsigned long long t0 = ~0ull, tx[8] = {}, lo[8];
     std::fill(lo, lo + 8, ~0ull);
     for_stamped(p, [&](int b) {
@@ -864,16 +605,16 @@ static void reweight_xcds(rdx_index* h, const SearchPlan& p, rdx_search_stats* a
         std::fprintf(stderr, "\n");
     }
     acc->xcd_finish_spread_ms = (float)((*std::max_element(dur, dur + 8) - *std::min_element(dur, dur + 8)) * 1e-5);   // 100 MHz ticks
-    acc->xcd_share_min = (float)*std::min_element(h->xw, h->xw + 8);
-    acc->xcd_share_max = (float)*std::max_element(h->xw, h->xw + 8);
+    acc->xcd_share_min = (float)*std::min_element(xw, xw + 8);
+    acc->xcd_share_max = (float)*std::max_element(xw, xw + 8);
     if (mean > 0) {
         double sum = 0;
         for (int x = 0; x < 8; ++x) {
-            h->xw[x] *= std::sqrt(mean / std::max(dur[x], 1.0));   // damped: half the correction per search
-            h->xw[x] = std::min(1.5, std::max(0.6, h->xw[x]));
-            sum += h->xw[x];
+            xw[x] *= std::sqrt(mean / std::max(dur[x], 1.0));   // damped: half the correction per search
+            xw[x] = std::min(1.5, std::max(0.6, xw[x]));
+            sum += xw[x];
         }
-        for (int x = 0; x < 8; ++x) h->xw[x] *= 8.0 / sum;
+        for (int x = 0; x < 8; ++x) xw[x] *= 8.0 / sum;
     }
 }
 
@@ -885,7 +626,7 @@ static int search_chunk(rdx_index* h, const SearchIO& io, int64_t nq, int k, hip
 static int redo_overflowed(rdx_index* h, const PendingSearch& ps, int* n_exact, rdx_search_stats* acc) {
     const SearchPlan& p = ps.plan;
     const hipStream_t st = ps.st;
-    if (p.depth == 0 && h->retry) {
+    if (p.depth == 0 && p.retry) {
         // Overflow means "far more rows above the sampled threshold than expected": similar rows stored together
         // (chunks of one document) that the sparse sample missed. Before paying the exact full scan (one fp32 pass over
         // the corpus per 4 queries), give exactly these queries one more MFMA pass as a small, HBM-bound batch with a
@@ -993,7 +734,9 @@ static int search_chunk(rdx_index* h, const SearchIO& io, int64_t nq, int k, hip
                         HostOut* ho, bool defer) {
     SearchPlan plan;
     unsigned long long seq = 0;
-    int rc = plan_search(*h, nq, k, depth, ho != nullptr, &plan);
+    std::string err;
+    int rc = plan_search(h->shape(), h->opt, h->adapt, nq, k, depth, ho != nullptr, &plan, &err);
+    if (rc != RDX_OK) (void)fail(rc, err);
     if (rc == RDX_OK && depth == 0) h->coarse_bits = plan.exact_only ? 0 : (plan.i8 ? 8 : 16);
     if (rc == RDX_OK) rc = enqueue_search(h, plan, io, ho, st, &seq);
     if (rc == RDX_OK) {
@@ -1109,69 +852,19 @@ extern "C" int rdx_index_set_option(rdx_index* h, const char* name, int64_t valu
     std::lock_guard<std::mutex> lk(h->mu);
     RDX_TRY(finish_pending(h, nullptr));   // the host half of an asynchronous search reads the options it was enqueued under
     const std::string n(name);
-    if (n == "force_exact") h->force_exact = value != 0;
-    else if (n == "force_fast") h->force_fast = value != 0;
-    else if (n == "retry") h->retry = value != 0;
-    else if (n == "fuse_epilogue") h->fuse_epilogue = value != 0;
-    else if (n == "fuse_finish") h->fuse_finish = value != 0;
-    else if (n == "split_boot") h->split_boot = value != 0;
-    else if (n == "small_scan") h->small_scan = value != 0;
-    else if (n == "half_boot") h->half_boot = value != 0;
-    else if (n == "spread_boot") h->spread_boot = value != 0;
-    else if (n == "coarse_i8") {
-        if (value < 0 || value > 2) return fail(RDX_ERR_INVALID, "coarse_i8 must be 0 (never), 1 (whenever the shape allows) or 2 (automatic)");
-        h->coarse_i8 = (int)value;
-        h->i8_backoff = 0;
-    }
-    else if (n == "refine_pilot") {
-        if (value < 0 || value > 64) return fail(RDX_ERR_INVALID, "refine_pilot must be 0 (one band) or 1..64 (pilot of that many times k hits)");
-        h->refine_pilot = (int)value;
-    }
-    else if (n == "i8_sample_mul") {
-        if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return fail(RDX_ERR_INVALID, "i8_sample_mul must be 0 (automatic), 1, 2, 4 or 8");
-        h->i8_sample_mul = (int)value;
-    }
-    else if (n == "refine_spill") {
-        if (value < 0 || value > 2) return fail(RDX_ERR_INVALID, "refine_spill must be 0 (never), 1 (always) or 2 (automatic)");
-        h->refine_spill = (int)value;
-    }
-    else if (n == "refine_list") {
-        if (value != 0 && (value < 32 || value > REFINE_LIST)) return fail(RDX_ERR_INVALID, "refine_list must be 0 (automatic) or 32.." + std::to_string(REFINE_LIST));
-        h->refine_list = (int)value;
-    }
-    else if (n == "spill_cap") {
-        if (value != 0 && (value < 32 || value > SPILL_CAP)) return fail(RDX_ERR_INVALID, "spill_cap must be 0 (automatic) or 32.." + std::to_string(SPILL_CAP));
-        h->spill_cap = (int)value;
-    }
-    else if (n == "spec_tau") {
-        h->spec_tau = value != 0;
-        h->spec_backoff = 0;
-    }
-    else if (n == "force_bn") {
-        if (value != 0 && value != 64 && value != 128 && value != 256) return fail(RDX_ERR_INVALID, "force_bn must be 0 (automatic), 64, 128 or 256");
-        h->force_bn = (int)value;
-    }
-    else if (n == "compact_master") {
+    if (n == "compact_master") {
         if (h->rows > 0 || h->cap > 0) return fail(RDX_ERR_STATE, "compact_master can only be chosen while the index is empty");
         h->compact = value != 0;
+        return RDX_OK;
     }
-    else if (n == "xcd_balance") {
-        h->xcd_balance = value != 0;
-        for (double& w : h->xw) w = 1.0;
-    }
-    else if (n == "profile") h->profile = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 3);
-    else if (n == "sample_div") {
-        if (value < 1) return fail(RDX_ERR_INVALID, "sample_div must be >= 1");
-        h->sample_div = (int)std::min<int64_t>(value, 1 << 20);
-    } else if (n == "row_base") {
+    if (n == "row_base") {
         if (value < 0) return fail(RDX_ERR_INVALID, "row_base must be >= 0");
         h->row_base = value;
-    } else if (n == "cand_cap") {
-        if (value < 0) return fail(RDX_ERR_INVALID, "cand_cap must be 0 (auto) or a positive slot count per (query, stream) segment");
-        h->cand_cap = value;
-    } else
-        return fail(RDX_ERR_INVALID, "unknown option '" + n + "'");
-    return RDX_OK;
+        return RDX_OK;
+    }
+    std::string err;   // every other option is a search's (search_plan.hpp)
+    const int rc = set_search_option(h->opt, h->adapt, name, value, &err);
+    return rc == RDX_OK ? rc : fail(rc, err);
 }
 
 extern "C" int rdx_index_xcd_shares(rdx_index* h, double* out8, const double* in8) {
@@ -1184,10 +877,10 @@ extern "C" int rdx_index_xcd_shares(rdx_index* h, double* out8, const double* in
             if (!(in8[x] > 0.0) || !(in8[x] < 100.0)) return fail(RDX_ERR_INVALID, "rdx_index_xcd_shares: shares must be positive finite numbers");
             sum += (w[x] = std::min(1.5, std::max(0.6, in8[x])));
         }
-        for (int x = 0; x < 8; ++x) h->xw[x] = w[x] * 8.0 / sum;
+        for (int x = 0; x < 8; ++x) h->adapt.xw[x] = w[x] * 8.0 / sum;
     }
     if (out8)
-        for (int x = 0; x < 8; ++x) out8[x] = h->xw[x];
+        for (int x = 0; x < 8; ++x) out8[x] = h->adapt.xw[x];
     return RDX_OK;
 }
 
@@ -1452,7 +1145,7 @@ extern "C" int rdx_l2_normalize(int device, const float* in, int64_t n, int dim,
 static int begin_search(rdx_index* h, int64_t nq, int k, rdx_search_stats* s) {
     RDX_TRY(finish_pending(h, nullptr));
     RDX_TRY(set_device(h));
-    if (h->profile && !h->ev_ok) {
+    if (h->opt.profile && !h->ev_ok) {
         for (auto& e : h->ev) HIP_TRY(hipEventCreate(&e));
         h->ev_ok = true;
     }

@@ -45,7 +45,6 @@ namespace rdx {
 
 constexpr int EPI_SETMAX = 0;
 constexpr int EPI_EMIT = 1;
-constexpr int SETS_PER_STREAM = 32;   // bootstrap sets per (stream, query): 8 waves x 2 lane halves x 2 register classes
 constexpr int RING_SLOTS = 4;     // LDS ring of query images: step s, s+1 (certified), s+2, s+3 (in flight)
 
 struct ScanParams {
@@ -647,7 +646,7 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
 //   2. splitk_reduce: waves 4..7 park acc in slab[w - 4]; wave w = 0..3 then stores  acc(w) + slab[w]  (its own tile the left
 //      operand, wave w + 4's the right one) back into slab[w].
 //   3. splitk_sum: ((((0 + slab[0]) + slab[1]) + slab[2]) + slab[3]).
-// plan_search (rdx_index.hip) relies on this: with use_boot && use_small the threshold's slack holds NO term for a rounding
+// plan_search (search_plan.hpp) relies on this: with use_boot && use_small the threshold's slack holds NO term for a rounding
 // difference between the sample's sums and the main scan's. (k_boot takes its k-steps two per round, ks0 = w, w + 16, ... with
 // ks0 + 8 each; k_scan_small holds exactly w and w + 8, and is only planned for ksteps <= 16 — the orders coincide wherever both
 // kernels run. With another main scan, k_scan, the orders differ and the plan adds twice the fp32 accumulation bound.)
@@ -659,7 +658,6 @@ struct SplitKParams {
     int64_t n_blocks32;        // ceil(rows / 32)
     const uint32_t* allow;     // NULL or row bitmap
 };
-constexpr int BOOT_BN = 64;
 constexpr int BOOT_NB = BOOT_BN / 16;   // 16-query blocks
 constexpr int BOOT_LD = 32 + 4;   // floats per query in a partial-sum slab [query][row]: a lane's 4 rows are one ds_write_b128, and the 16 lanes of
                                   // a pass land on 16 distinct bank quads (9 * query mod 16)
@@ -910,7 +908,7 @@ __global__ __launch_bounds__(512) void k_scan_small(const SmallScanParams p) {
 // non-empty sets exist (then every allowed row is emitted). One block per query (padding queries: +inf).
 // Only the first n_sets_used sets (streams that scanned at least one tile) are looked at.
 // k = rank taken: the search's k (provable: k distinct sampled rows reach the value, two_e_scaled = 2E) or a smaller rank with
-// two_e_scaled = 0 (speculative threshold, verified by k_refine; rdx_index.hip speculative_rank).
+// two_e_scaled = 0 (speculative threshold, verified by k_refine; search_plan.hpp speculative_rank).
 __global__ __launch_bounds__(256) void k_tau(const float* __restrict__ setmax, int n_sets, int n_sets_used, int k,
                                              float two_e_scaled, int nq, float* __restrict__ tau) {
     __shared__ __attribute__((aligned(16))) uint32_t hist[HIST_WORDS];

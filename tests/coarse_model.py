@@ -9,8 +9,8 @@ library computes (oracle.normalize_rows, bit-equal to K1: test_gpu_parity.py::te
                 (n - 1) 2^-23 sum|x̃ỹ| with n the number of NON-ZERO products (zeros add exactly; valid for truncating adders).
                 When every product is a multiple of 2^L and sum|x̃ỹ| < 2^(L+24), every partial sum in any order is an fp32
                 number: the kernel's value is then the model's to the bit (bound 0).
-    CONSTANTS   E, 2E and the bootstrap slack as the library computes them in float32 (rdx_index.hip two_e(), plan_search
-                p.slack), and the refine band edge t2 = c_k - 2E (refine_kernel.hpp).
+    CONSTANTS   E, 2E and the bootstrap slack as the library computes them in float32 (rdx_index.hip two_e(), search_plan.hpp
+                plan_search p.slack), and the refine band edge t2 = c_k - 2E (refine_kernel.hpp).
 
 Mutants (for the power tests of test_coarse_model.py, never built into the library): round-toward-zero conversion
 (`rtz`), fp16 subnormals flushed (`flush`).

@@ -25,7 +25,7 @@ from rag_dpo_amd import synth
 from test_i8_bound_model import F32
 
 REFINE_PMAX = 1024           # refine_kernel.hpp: a band with more rows than this is re-scored in place (not what is measured here)
-REFINE_LIST = 7168           # refine_kernel.hpp: a query with more hits than this goes to the fallback passes
+REFINE_LIST = 7168           # rdx_limits.hpp: a query with more hits than this goes to the fallback passes
 K = 10
 
 
