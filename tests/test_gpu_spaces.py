@@ -2,7 +2,8 @@
 spaces.SpaceEngine over the CPU oracle engine, whose scores are bit-identical to librdx's, so distances, rows, counts AND the
 proof decisions (last_stats) must be equal — there is no tolerance anywhere in this file.
 Shapes: d = 64 and 1024 (l2: engine dims 68 and 1028 = 2 and 17 k-steps), 2 000 and 20 000 rows, 1 / 4 / 70 queries, k = 1 / 10 / 50,
-each with the engine's default path and with force_fast (the exact scan and the MFMA scan both feed the re-score)."""
+each with the engine's default path and with force_fast (the exact scan and the MFMA scan both feed the re-score).
+The kernels on their own — ragged dims, selection edges, the proof flag at its boundary, page addressing: tests/test_gpu_space_kernels.py."""
 import numpy as np
 import pytest
 
