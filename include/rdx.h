@@ -569,6 +569,57 @@ int rdx_space_distances(int device, int space_kind, const float* queries, int nq
                         int scale_exp, const uint32_t* allow_bits, int64_t first_row, float* out, int64_t out_stride,
                         void* stream);
 
+/* Rank fusion ----------------------------------------------------------------------------------- */
+/* The step that joins the dense and the BM25 rankings of a question: the reference's summary filter of the dense lists, the
+ * min-distance / max-score merge, reciprocal rank fusion, the stable sort and the cut (src/rag/retriever.py:226-300, :391-462), as
+ * DenseRetriever._fuse (rag_dpo_amd/retriever.py) computes them — that method is the model, bit for bit — for nq questions in ONE
+ * launch, one workgroup per question. rag_dpo_amd/fusion.py packs the lists and builds the winners' objects; DESIGN.md §18.
+ *
+ * Limits (RDX_ERR_INVALID beyond them, checked before anything is launched or written): 1 <= n_lists <= RDX_FUSE_MAX_LISTS lists per
+ * question, 1 <= list_stride <= RDX_FUSE_MAX_LIST_ENTRIES entries per list, n_lists * list_stride <= RDX_FUSE_MAX_ENTRIES entries per
+ * question, 1 <= top_n <= RDX_FUSE_MAX_ENTRIES, nq <= 2^24.
+ *
+ * Input. Question q's lists are [q][0 .. n_lists) in the order _fuse visits them (dense q0, BM25 q0, dense q1, BM25 q1, ...):
+ *   list_kind   int32 [nq][n_lists]  RDX_FUSE_DENSE or RDX_FUSE_BM25
+ *   list_weight fp64  [nq][n_lists]  the ranking's RRF weight
+ *   list_count  int32 [nq][n_lists]  entries of the list, 0 .. list_stride; -1 = the list is absent (a skipped sub-query: no ranking,
+ *                                    no weight). RDX_HOST: counts and kinds outside these values are RDX_ERR_INVALID; RDX_DEVICE (they
+ *                                    cannot be read before the launch): a count above list_stride is read as list_stride, below -1 as -1.
+ *   keys        int64 [nq][n_lists][list_stride]  what identifies a chunk across lists (the host layer: its collection row)
+ *   dense_dist  fp32  [nq][n_lists][list_stride]  read for the entries of dense lists: the distance
+ *   bm25_score  fp64  [nq][n_lists][list_stride]  read for the entries of BM25 lists: the score
+ *   filter_on   NULL (no question is filtered), or int32 [nq]: != 0 = question q's dense lists are filtered by
+ *   allow_groups uint32 [nq][group_words]: bit (g & 31) of word g >> 5 set = document group g is allowed, and
+ *   row_group   int32 [n_rows]: the group of key r. A dense key that is negative, >= n_rows, or whose group is negative or
+ *               >= 32 * group_words is never allowed.
+ * Filtering. A dense list of a filtered question becomes its allowed entries, in order; when fewer than min_semantic are allowed, its
+ *   first refused entries follow, in order, up to min_semantic entries in all. Every other list is taken as given.
+ * Per key, over the filtered lists in list order, then rank order ("first appearance" = the first such occurrence):
+ *   distance (fp32)  the first appearance's distance, or 1.0 when that is a BM25 one; then d wherever a later dense occurrence has d < distance
+ *   semantic (fp64)  1.0 / (1.0 + (double)distance) of the first appearance, or +0.0 when that is a BM25 one; then the value s of a
+ *                    later dense occurrence wherever s > semantic (the two are not functions of each other)
+ *   bm25 (fp64)      +0.0, then over the BM25 occurrences: s where s > bm25 (bm25_keep_max = 1) or the last s (bm25_keep_max = 0)
+ *   hybrid (fp64)    with more than one list present (count >= 0; an empty list counts): +0.0, then
+ *                    += list_weight / (double)(rrf_k + rank + 1) at EVERY occurrence (rank = 0-based position in the filtered list;
+ *                    IEEE division, one add each, in that order). With one list or none present: hybrid = semantic.
+ * Output per question: the keys by hybrid descending, ties (+0.0 == -0.0) by first appearance — Python's stable sort(reverse=True) over
+ *   dict insertion order; NaN after every number. out_count [nq] = min(top_n, distinct keys); [nq][top_n] each: out_key, out_distance,
+ *   out_semantic, out_bm25, out_hybrid, and out_list / out_rank = the INPUT position (list, rank before filtering) of the key's first
+ *   appearance: where the host takes the chunk's text and metadata from. Slots past the count hold key -1, list -1, rank -1 and zeros.
+ * `space` covers every pointer. RDX_DEVICE: one launch enqueued on `stream`, nothing synchronised or allocated, no atomics — the same
+ * inputs give the same bits on every call, whatever nq. RDX_HOST: staged through the device, complete on return (NULL = HIP's default stream). */
+#define RDX_FUSE_MAX_LISTS 16
+#define RDX_FUSE_MAX_LIST_ENTRIES 512
+#define RDX_FUSE_MAX_ENTRIES 1024
+#define RDX_FUSE_DENSE 0
+#define RDX_FUSE_BM25 1
+int rdx_fuse_rankings(int device, int64_t nq, int n_lists, int list_stride, const int32_t* list_kind, const double* list_weight,
+                      const int32_t* list_count, const int64_t* keys, const float* dense_dist, const double* bm25_score,
+                      const int32_t* row_group, int64_t n_rows, const int32_t* filter_on, const uint32_t* allow_groups,
+                      int group_words, int min_semantic, int bm25_keep_max, int rrf_k, int top_n, int64_t* out_key,
+                      float* out_distance, double* out_semantic, double* out_bm25, double* out_hybrid, int32_t* out_list,
+                      int32_t* out_rank, int32_t* out_count, int space, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,8 @@ DOCS_MAX_LEAVES = 1024   # include/rdx.h RDX_DOCS_MAX_LEAVES
 META_MAX_COLUMNS = 4096   # include/rdx.h RDX_META_MAX_COLUMNS (leaf ops and the leaf limit: rag_dpo_amd/where_device.py)
 SPACE_IP, SPACE_L2 = 0, 1   # include/rdx.h RDX_SPACE_*
 SPACE_MAX_CAND, SPACE_MAX_PAGE_QUERIES = 4096, 64   # include/rdx.h rdx_space_rescore's / rdx_space_distances' limits
+FUSE_MAX_LISTS, FUSE_MAX_LIST_ENTRIES, FUSE_MAX_ENTRIES = 16, 512, 1024   # include/rdx.h RDX_FUSE_MAX_*: rdx_fuse_rankings' limits
+FUSE_DENSE, FUSE_BM25 = 0, 1   # include/rdx.h RDX_FUSE_DENSE / RDX_FUSE_BM25
 TOPIC_MAX_N, TOPIC_MAX_TOPICS, TOPIC_MAX_TAGS, TOPIC_MAX_DIM = 1024, 32, 64, 4096   # include/rdx.h rdx_topic_boost's limits
 
 
@@ -136,6 +138,8 @@ SYMBOLS = {
     "rdx_space_lift": (_i, [_i, _i, _i, _vp, _i64, _i, _i, _vp, _vp, _vp]),
     "rdx_space_rescore": (_i, [_i, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rdx_space_distances": (_i, [_i, _i, _vp, _i, _i, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp]),
+    "rdx_fuse_rankings": (_i, [_i, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i,
+                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
 }
 
 

@@ -194,18 +194,19 @@ class _Bm25Base:
         self.engine = self._factory(self.model.arrays(row_group, n_groups), self.device) if self.model.n_rows else None
         self._is_built = True
 
-    def _search_rows(self, queries: Sequence[str], top_k: int, allow_bits=None):
-        """-> per query a list of (row, score), the reference's order and cut"""
+    def _search_arrays(self, queries: Sequence[str], top_k: int, allow_bits=None):
+        """-> (live, scores f64 [len(live), k], rows int64 [len(live), k], counts int32 [len(live)]): the engine's own arrays for the
+        queries (indices `live`) that have a known token, the reference's order and cut; every other query finds nothing"""
         if not self._is_built:
             raise RuntimeError("the BM25 index is not built")
-        out: List[list] = [[] for _ in queries]
+        none = ([], np.zeros((0, 0), np.float64), np.zeros((0, 0), np.int64), np.zeros(0, np.int32))
         if top_k <= 0 or self.engine is None:
-            return out
+            return none
         k = min(int(top_k), self.model.n_rows)
         terms = [self.model.query_ids(tokenize_french(q)) for q in queries]
         live = [i for i, t in enumerate(terms) if t]           # a query without known tokens scores 0 everywhere: nothing
         if not live:
-            return out
+            return none
         for i in live:
             if len(terms[i]) > MAX_TERMS:
                 raise ValueError(f"a BM25 query has {len(terms[i])} known tokens; at most {MAX_TERMS} are supported")
@@ -213,6 +214,12 @@ class _Bm25Base:
         np.cumsum([len(terms[i]) for i in live], out=off[1:])
         ids = np.fromiter(chain.from_iterable(terms[i] for i in live), dtype=np.int32, count=int(off[-1]))
         sc, ro, cn = self.engine.search(off, ids, k, allow_bits)
+        return live, sc, ro, cn
+
+    def _search_rows(self, queries: Sequence[str], top_k: int, allow_bits=None):
+        """-> per query a list of (row, score), the reference's order and cut"""
+        live, sc, ro, cn = self._search_arrays(queries, top_k, allow_bits)
+        out: List[list] = [[] for _ in queries]
         for j, i in enumerate(live):
             c = int(cn[j])
             out[i] = list(zip(ro[j, :c].tolist(), sc[j, :c].tolist()))
@@ -259,6 +266,10 @@ class SummaryBM25Index(_Bm25Base):
 
     def get_relevant_doc_paths(self, query: str, top_k: int = 20) -> Set[str]:
         return {r.doc_key for r in self.search(query, top_k=top_k)}
+
+    def get_relevant_doc_paths_batch(self, queries: Sequence[str], top_k: int = 20) -> List[Set[str]]:
+        """get_relevant_doc_paths of every query, in one device call"""
+        return [{self.doc_keys[r] for r, _ in hits} for hits in self._search_rows(queries, top_k)]
 
 
 class ChunkBM25Index(_Bm25Base):
@@ -314,11 +325,25 @@ class ChunkBM25Index(_Bm25Base):
             bits = self._allow_bits(doc_filter)
             if bits is None:
                 return [[] for _ in queries]
-        out = []
-        for hits in self._search_rows(queries, top_k, bits):
-            out.append([BM25Result(doc_key=self.chunk_ids[r], score=s,
-                                   metadata={**(self.chunk_metadatas[r] or {}), "text": self.chunk_texts[r]}) for r, s in hits])
-        return out
+        return [[self.result_of(r, s) for r, s in hits] for hits in self._search_rows(queries, top_k, bits)]
+
+    def result_of(self, row: int, score: float) -> BM25Result:
+        """the BM25Result of one hit: the index's own copy of the chunk's metadata, plus its text"""
+        return BM25Result(doc_key=self.chunk_ids[row], score=score,
+                          metadata={**(self.chunk_metadatas[row] or {}), "text": self.chunk_texts[row]})
+
+    def search_batch_arrays(self, queries: Sequence[str], top_k: int = 30, doc_filter: Optional[Set[str]] = None):
+        """search_batch without the result objects, for callers that materialise a few of the hits (rag_dpo_amd/fusion.py):
+        -> (live, scores f64 [len(live), k], rows int64 [len(live), k], counts int32 [len(live)]), rows = indexes into chunk_ids;
+        a query that is not in `live` found nothing"""
+        if not self._is_built:
+            raise RuntimeError("the BM25 index is not built")
+        bits = None
+        if doc_filter is not None:
+            bits = self._allow_bits(doc_filter)
+            if bits is None:
+                return [], np.zeros((0, 0), np.float64), np.zeros((0, 0), np.int64), np.zeros(0, np.int32)
+        return self._search_arrays(queries, top_k, bits)
 
     def search(self, query: str, top_k: int = 30, doc_filter: Optional[Set[str]] = None) -> List[BM25Result]:
         return self.search_batch([query], top_k, doc_filter)[0]

@@ -177,6 +177,11 @@ def build_lib(force: bool = False, verbose: bool = False, extra_flags=(), out: s
                 any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in space.values()):
             raise RuntimeError("the ip / l2 space kernels (space_kernel.hpp) spill or were not found — refused:\n" +
                                "\n".join(f"  {k}: {v}" for k, v in space.items()))
+        fuse = {k: v for k, v in res.items() if "k_fuse" in k}
+        if len(fuse) < 1 or any("spill_vgprs" not in v or "scratch_bytes" not in v for v in fuse.values()) or \
+                any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in fuse.values()):
+            raise RuntimeError("the rank fusion kernel (fuse_kernel.hpp) spills or was not found — refused:\n" +
+                               "\n".join(f"  {k}: {v}" for k, v in fuse.items()))
         # k_refine / k_refine_spill run 1024 threads at the 128-register limit (refine_kernel.hpp): a spill would be paid on every search
         refine = {k: v for k, v in res.items() if "k_refine" in k}
         if extra_flags:

@@ -152,6 +152,8 @@ class Collection:
         self._doc_store = None                 # engine.DocStore: the documents in HBM, made by the first where_document call
         self._meta_store = None                # engine.MetaStore: the metadata columns filters have named, made by the first `where`
         self._meta_res: Dict[str, list] = {}   # key -> [slot in the store, rows [0, r) of the column that are on the device]
+        self._writes = 0                       # bumped by every add / update / upsert / delete / compaction that changes a row: what tables
+                                               # derived from the rows (rag_dpo_amd/fusion.py's row -> document group) are keyed on
 
     # ---- small helpers ----------------------------------------------------------------------
     @property
@@ -494,6 +496,7 @@ class Collection:
         self._n_dead = 0
         self._meta_cache.clear()
         self._drop_masks()
+        self._writes += 1
 
     # ---- chromadb.Collection API ---------------------------------------------------------------
     def count(self) -> int:
@@ -535,6 +538,7 @@ class Collection:
                 for i in fresh:
                     W.check_meta(metadatas[i])
             self._drop_masks()
+            self._writes += 1
             sel = emb if len(fresh) == n else (emb[fresh].contiguous() if _is_device_tensor(emb) else np.ascontiguousarray(emb[fresh]))
             row0 = self._rows
             if _stored:             # snapshot reload: rows are the stored (already normalised) values, kept verbatim
@@ -573,6 +577,8 @@ class Collection:
                 W.check_meta(m)
         with self._lock:
             hit = [(i, self._row_of[s]) for i, s in enumerate(ids) if s in self._row_of]
+            if hit:
+                self._writes += 1
             if emb is not None and hit:
                 self._ensure_engine(emb.shape[1])
                 self._engine.update(np.array([r for _, r in hit], dtype=np.int64),
@@ -640,6 +646,7 @@ class Collection:
             gone = [self._ids[r] for r in rows if self._alive[r]]
             if gone:
                 self._drop_masks()
+                self._writes += 1
                 self._log({"op": "delete", "ids": gone}, None)
             for r in rows:
                 if self._alive[r]:
@@ -784,6 +791,41 @@ class Collection:
         with self._lock:
             rr = rows.tolist() if hasattr(rows, "tolist") else rows
             return [[self._ids[x] for x in row if x >= 0] for row in rr]
+
+    def rows_of(self, ids) -> List[int]:
+        """the inverse of ids_of for a flat list of Chroma ids: the row query_device would return for each, -1 for an id the
+        collection does not hold (never added, or deleted)"""
+        with self._lock:
+            get = self._row_of.get
+            return [get(s, -1) for s in ids]
+
+    def payload_of(self, rows):
+        """-> (ids, documents, metadatas) of row ids as returned by query_device: what query() puts beside these rows"""
+        with self._lock:
+            rr = [int(r) for r in rows]
+            return [self._ids[r] for r in rr], [self._docs[r] for r in rr], self._metas_of(rr)
+
+    def column_values(self, key: str, default=None) -> list:
+        """the value of metadata key `key` for every row, in row order (`default` where a row has none)"""
+        with self._lock:
+            col, n = self._cols.get(key), self._rows
+            if col is None:
+                return [default] * n
+            out = [default] * n
+            kinds = col.kind[:n]
+            strs = np.flatnonzero(kinds == W.K_STR)
+            vocab = col.vocab
+            for r, c in zip(strs.tolist(), col.code[strs].tolist()):
+                out[r] = vocab[c]
+            for r in np.flatnonzero((kinds != W.K_STR) & (kinds != W.K_MISSING)).tolist():
+                out[r] = col.get(r)
+            return out
+
+    @property
+    def write_count(self) -> int:
+        """how many writes (add / update / upsert / delete / compaction) have changed this collection's rows: a table derived from
+        the rows is valid for the count it was built at"""
+        return self._writes
 
     def modify(self, name: Optional[str] = None, metadata: Optional[dict] = None):
         with self._lock:

@@ -91,7 +91,11 @@ class DenseRetriever:
     def __init__(self, collection, embedding_provider, query_expander: Optional[Callable[[str], List[str]]] = None,
                  query_preprocessor: Optional[Callable[[str], str]] = None, n_documents: int = 5,
                  n_chunks_per_doc: int = 3, fetch_multiplier: int = 10, summary_bm25_index=None, chunk_bm25_index=None,
-                 summary_prefilter_k: int = 20, enable_hybrid: bool = True, enable_summary_prefilter: bool = True):
+                 summary_prefilter_k: int = 20, enable_hybrid: bool = True, enable_summary_prefilter: bool = True,
+                 fusion: str = "auto"):
+        if fusion not in ("auto", "device", "host"):
+            raise ValueError(f"fusion must be 'auto', 'device' or 'host', got {fusion!r}")
+        self.fusion = fusion                            # how retrieve_candidates_batch fuses: rag_dpo_amd/fusion.py, or the loop
         self.collection = collection
         self.embedding_provider = embedding_provider
         self.query_expander = query_expander            # reference: QueryExpander.expand (LLM, out of scope)
@@ -142,6 +146,12 @@ class DenseRetriever:
         if self.enable_summary_prefilter and self.summary_bm25 is not None and self.summary_bm25._is_built:
             return self.summary_bm25.get_relevant_doc_paths(expanded, top_k=self.summary_prefilter_k)
         return None
+
+    def _doc_filters(self, expanded: Sequence[str]):
+        """_doc_filter of every main query, the summary searches in one device call"""
+        if self.enable_summary_prefilter and self.summary_bm25 is not None and self.summary_bm25._is_built:
+            return self.summary_bm25.get_relevant_doc_paths_batch(list(expanded), top_k=self.summary_prefilter_k)
+        return [None] * len(expanded)
 
     def _hybrid(self) -> bool:
         return self.enable_hybrid and self.chunk_bm25 is not None and self.chunk_bm25.is_built
@@ -214,6 +224,49 @@ class DenseRetriever:
             for i, res in zip(live, found):
                 bm25[i] = (res, 2.0 * 1.5 if i == 0 else 1.0 * 0.75)
         return self._fuse(per_query, bm25=bm25, doc_filter=doc_filter, min_semantic=10, bm25_keep_max=True)[:n_candidates]
+
+    def retrieve_candidates_batch(self, queries: Sequence[str], n_candidates: int = 100, where_filter=None) -> List[List[RetrievedChunk]]:
+        """retrieve_candidates of every question — the same ids, order and floats — with the sub-queries of the whole batch encoded,
+        searched and BM25-scored together and their rankings fused on the GPU by one launch (rag_dpo_amd/fusion.py).
+        where_filter: one filter for every question, or a list / tuple with one filter (or None) per question.
+        fusion="host" loops retrieve_candidates; "device" needs librdx and a GPU collection and refuses a question beyond the kernel's
+        limits; "auto" takes the device where it can and the loop for the rest. If the batched device calls raise (a sub-query the
+        index rejects), every question goes through retrieve_candidates, which skips exactly the failing sub-queries."""
+        queries = list(queries)
+        wheres = list(where_filter) if isinstance(where_filter, (list, tuple)) else [where_filter] * len(queries)
+        if len(wheres) != len(queries):
+            raise ValueError(f"where_filter: {len(wheres)} filters for {len(queries)} questions")
+        loop = lambda idx: [self.retrieve_candidates(queries[i], n_candidates=n_candidates, where_filter=wheres[i]) for i in idx]
+        if self.fusion == "host" or not queries:
+            return loop(range(len(queries)))
+        from . import fusion as F
+        if self.fusion == "device":
+            from . import _lib
+            _lib.load(require_gpu=True)                             # raises RdxUnavailable: there is no quiet fall-back
+            if not F.device_ready(self):
+                raise RuntimeError("fusion='device' needs a collection on a GPU engine (query_device)")
+        elif not F.device_ready(self):
+            return loop(range(len(queries)))
+        per_sub = 2 if self._hybrid() else 1
+        n_fetch = max(n_candidates, 50)
+        expanded = [self._expand(q) for q in queries]                # (expanded once: the expander may be a model)
+        on_device = [i for i, (_, subs) in enumerate(expanded) if F.fits(per_sub * len(subs), n_fetch, n_candidates)]
+        if self.fusion == "device" and len(on_device) < len(queries):
+            raise ValueError("fusion='device': a question's rankings are beyond rdx_fuse_rankings' limits "
+                             f"({F.MAX_LISTS} lists, {F.MAX_ENTRIES} entries per question)")
+        out: List[Optional[List[RetrievedChunk]]] = [None] * len(queries)
+        if on_device:
+            try:
+                got = F.retrieve_candidates_device(self, [expanded[i] for i in on_device], n_candidates, [wheres[i] for i in on_device])
+            except Exception as e:
+                logger.error("the batched device retrieval failed (%s): retrieving the %d questions one by one", e, len(on_device))
+                got = loop(on_device)
+            for i, g in zip(on_device, got):
+                out[i] = g
+        rest = [i for i in range(len(queries)) if out[i] is None]
+        for i, g in zip(rest, loop(rest)):
+            out[i] = g
+        return out
 
     def retrieve_reranked(self, query: str, reranker, n_candidates: int = 40, top_k: int = 10, where_filter=None, topic_matcher=None,
                           question_topics: Optional[List[str]] = None) -> List[RetrievedDocument]:
