@@ -297,6 +297,46 @@ int rdx_topic_boost(int device, const float* table, int64_t table_rows, int dim,
                     const int32_t* tag_slots, int n_tags, const int32_t* pair_offsets, const int32_t* pairs, int64_t n_pairs,
                     int n, double threshold, double max_boost, double* sims, double* boosts, double* best_sim, void* stream);
 
+/* The reranker for a batch of questions ---------------------------------------------------------- */
+/* The three calls above for nq questions at once (rag_dpo_amd/reranker.py rerank_batch). The candidates of all
+ * questions lie side by side on one axis of n_total entries; question q is the segment [cand_off[q], cand_off[q + 1]). Enqueued on
+ * `stream`, nothing synchronised, nothing allocated, no float atomics: the same inputs give the same bits on every call. Invalid
+ * arguments return RDX_ERR_INVALID before anything is launched. Per question every output holds the bits and integers the
+ * single-question call gives on that question alone; no question's result depends on its neighbours or on nq.
+ *
+ * Shape arrays. cand_off (and rdx_topic_boost_batch's topic_off, tag_off, sim_off) say where each question's data lies. The library
+ * reads them on the host, to check the call and size the launches, and the kernels read the same words: they must lie in PINNED
+ * HOST memory (hipHostMalloc / hipHostRegister; torch's pin_memory()) and stay unchanged until `stream` has passed the call. A
+ * shape array in device or pageable memory is RDX_ERR_INVALID. Every other pointer is device memory.
+ *   cand_off int32 [nq + 1]: cand_off[0] = 0, never decreasing, empty segments allowed, at most 1024 candidates per segment,
+ *   n_total = cand_off[nq] <= RDX_RERANK_BATCH_MAX_ROWS; 1 <= nq <= RDX_RERANK_BATCH_MAX_QUESTIONS.
+ *
+ * rdx_rerank_head_rows_f16: rdx_rerank_head_f16 for 1 <= n <= RDX_RERANK_BATCH_MAX_ROWS rows (it knows no segments). scores[p] has
+ *   the bits rdx_rerank_head_f16 gives row p in any call that contains it: a row's arithmetic does not depend on n. workspace:
+ *   RDX_RERANK_WORKSPACE_BYTES(n, hidden) bytes.
+ * rdx_topic_boost_batch: rdx_topic_boost per question over one shared table, two launches in all. Question q's topics are
+ *   topic_slots[topic_off[q] .. topic_off[q + 1]) (at most 32), its distinct tags tag_slots[tag_off[q] .. tag_off[q + 1]) (at most
+ *   65536), its similarity block sims + sim_off[q], [T_q][U_q] (sim_off int64 [nq + 1], sim_off[q + 1] - sim_off[q] >= T_q * U_q);
+ *   candidate c of the axis owns pairs[pair_off[c] .. pair_off[c + 1]) (pair_off int64 [n_total + 1], device memory, clamped to
+ *   [0, n_pairs]), RDX_TOPIC_PAIR words whose indices are local to the candidate's question. boosts fp64 [n_total], every entry
+ *   written; best_sim NULL or fp64 [n_total]. A question without topics or without tags gets +0.0 boosts unless a pair is exact.
+ * rdx_rerank_select_batch: rdx_rerank_select per segment in one launch. order int32 [n_total]: segment q's permutation, indices
+ *   local to the segment, at order + cand_off[q]; final_score fp64 [n_total]; count int32 [nq] (0 for an empty segment); boosted
+ *   NULL or int32 [nq]: the candidates of the segment with boosts > 0. One workgroup per question, RDX_RERANK_SELECT_WIDTHS
+ *   threads wide: the smallest width that holds the call's longest segment. */
+#define RDX_RERANK_BATCH_MAX_ROWS (1 << 20)
+#define RDX_RERANK_BATCH_MAX_QUESTIONS 65535
+#define RDX_RERANK_SELECT_WIDTHS {64, 256, 1024}
+int rdx_rerank_head_rows_f16(int device, const float* cls, int64_t n, int hidden, const void* w_dense, const void* b_dense,
+                             const void* w_out, const void* b_out, double* workspace, float* scores, void* stream);
+int rdx_topic_boost_batch(int device, const float* table, int64_t table_rows, int dim, int nq, const int32_t* topic_off,
+                          const int32_t* topic_slots, const int32_t* tag_off, const int32_t* tag_slots, const int64_t* sim_off,
+                          const int32_t* cand_off, const int64_t* pair_off, const int32_t* pairs, int64_t n_pairs, double threshold,
+                          double max_boost, double* sims, double* boosts, double* best_sim, void* stream);
+int rdx_rerank_select_batch(int device, const float* scores, const double* boosts, int nq, const int32_t* cand_off, int top_k,
+                            double min_score, int keep_min, int32_t* order, double* final_score, int32_t* count, int32_t* boosted,
+                            void* stream);
+
 /* `collection.query(query_embeddings=, n_results=k, where=)` (reference
  * src/rag/retriever.py:215-220,380-385; create_chromadb_index.py:405-408,435-439).
  *   queries     [nq][dim] raw fp32 (normalised on the device like corpus rows)

@@ -29,6 +29,9 @@ SPACE_MAX_CAND, SPACE_MAX_PAGE_QUERIES = 4096, 64   # include/rdx.h rdx_space_re
 FUSE_MAX_LISTS, FUSE_MAX_LIST_ENTRIES, FUSE_MAX_ENTRIES = 16, 512, 1024   # include/rdx.h RDX_FUSE_MAX_*: rdx_fuse_rankings' limits
 FUSE_DENSE, FUSE_BM25 = 0, 1   # include/rdx.h RDX_FUSE_DENSE / RDX_FUSE_BM25
 TOPIC_MAX_N, TOPIC_MAX_TOPICS, TOPIC_MAX_TAGS, TOPIC_MAX_DIM = 1024, 32, 64, 4096   # include/rdx.h rdx_topic_boost's limits
+# include/rdx.h RDX_RERANK_BATCH_MAX_ROWS / _MAX_QUESTIONS / RDX_RERANK_SELECT_WIDTHS: the batched reranker calls' limits, and the workgroup
+# widths rdx_rerank_select_batch chooses among (the smallest that holds the call's longest segment)
+RERANK_BATCH_MAX_ROWS, RERANK_BATCH_MAX_QUESTIONS, RERANK_SELECT_WIDTHS = 1 << 20, 65535, (64, 256, 1024)
 
 
 def topic_pair(topic: int, tag: int, exact: bool) -> int:
@@ -101,6 +104,10 @@ SYMBOLS = {
     "rdx_rerank_head_f16": (_i, [_i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rdx_rerank_select": (_i, [_i, _vp, _vp, _i, _i, ctypes.c_double, _i, _vp, _vp, _vp, _vp]),
     "rdx_topic_boost": (_i, [_i, _vp, _i64, _i, _vp, _i, _vp, _i, _vp, _vp, _i64, _i, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp]),
+    "rdx_rerank_head_rows_f16": (_i, [_i, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rdx_topic_boost_batch": (_i, [_i, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double,
+                                   _vp, _vp, _vp, _vp]),
+    "rdx_rerank_select_batch": (_i, [_i, _vp, _vp, _i, _vp, _i, ctypes.c_double, _i, _vp, _vp, _vp, _vp, _vp]),
     "rdx_search": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "rdx_mask_create": (_i, [_vp, _vp, _i, ctypes.POINTER(_vp)]),
     "rdx_mask_destroy": (_i, [_vp]),

@@ -172,6 +172,11 @@ def build_lib(force: bool = False, verbose: bool = False, extra_flags=(), out: s
                 any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in topic.values()):
             raise RuntimeError("the topic boost kernels (topic_kernel.hpp) spill or were not found — refused:\n" +
                                "\n".join(f"  {k}: {v}" for k, v in topic.items()))
+        batch = {k: v for k, v in res.items() if "k_rerank_select_batch" in k or "k_topic_sims_batch" in k or "k_topic_replay_batch" in k}
+        if len(batch) < 5 or any("spill_vgprs" not in v or "scratch_bytes" not in v for v in batch.values()) or \
+                any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in batch.values()):
+            raise RuntimeError("the batched reranker kernels (rerank_batch_kernel.hpp) spill or were not found — refused:\n" +
+                               "\n".join(f"  {k}: {v}" for k, v in batch.items()))
         space = {k: v for k, v in res.items() if "k_space" in k}
         if len(space) < 5 or any("spill_vgprs" not in v or "scratch_bytes" not in v for v in space.values()) or \
                 any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in space.values()):

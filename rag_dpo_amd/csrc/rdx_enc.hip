@@ -1,5 +1,6 @@
 // rdx_enc.hip — the encoder launchers (rdx_enc_*), the reranker head and selection (rdx_rerank_*) and the topic boost
-// (rdx_topic_boost) of include/rdx.h.
+// (rdx_topic_boost) of include/rdx.h, and their forms for a batch of questions (rdx_rerank_head_rows_f16, rdx_topic_boost_batch,
+// rdx_rerank_select_batch).
 #include "rdx_host.hpp"
 
 #include <mutex>
@@ -10,6 +11,7 @@
 #include "enc_gemm.hpp"
 #include "rerank_kernel.hpp"
 #include "topic_kernel.hpp"
+#include "rerank_batch_kernel.hpp"
 
 using namespace rdx;
 
@@ -417,6 +419,164 @@ extern "C" int rdx_topic_boost(int device, const float* table, int64_t table_row
     hipLaunchKernelGGL(k_topic_replay, dim3((unsigned)((n + TOPIC_THREADS - 1) / TOPIC_THREADS)), dim3(TOPIC_THREADS), 0, st,
                        (const double*)sims, dots ? n_topics : 0, dots ? n_tags : 0, pair_offsets, pairs, n_pairs, n, threshold, max_boost,
                        boosts, best_sim);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the reranker for a batch of questions (rerank_batch_kernel.hpp)
+// ------------------------------------------------------------------------------------------------
+extern "C" int rdx_rerank_head_rows_f16(int device, const float* cls, int64_t n, int hidden, const void* w_dense, const void* b_dense,
+                                        const void* w_out, const void* b_out, double* workspace, float* scores, void* stream) {
+    if (n < 1 || n > RERANK_BATCH_MAX_ROWS) return fail(RDX_ERR_INVALID, "rdx_rerank_head_rows_f16: n must be in [1, 2^20]");
+    if (hidden < 64 || hidden > RERANK_MAX_HIDDEN || hidden % 64)
+        return fail(RDX_ERR_INVALID, "rdx_rerank_head_rows_f16: hidden must be a multiple of 64 in [64, 4096]");
+    if (!cls || !w_dense || !b_dense || !w_out || !b_out || !workspace || !scores)
+        return fail(RDX_ERR_INVALID, "rdx_rerank_head_rows_f16: null pointer");
+    if (((uintptr_t)cls | (uintptr_t)w_dense) & 15) return fail(RDX_ERR_INVALID, "rdx_rerank_head_rows_f16: cls and w_dense must be 16-byte aligned");
+    if (((uintptr_t)b_dense | (uintptr_t)w_out | (uintptr_t)b_out) & 1 || ((uintptr_t)workspace & 7) || ((uintptr_t)scores & 3))
+        return fail(RDX_ERR_INVALID, "rdx_rerank_head_rows_f16: misaligned pointer");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_rerank_head_rows_f16: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    // rdx_rerank_head_f16's two kernels on a taller grid: workgroup (b, y) takes rows [64 y, 64 y + 64) whatever n is, and row r's
+    // partials lie at part[b * n + r] (size_t: 2^29 words at the limits), so a row's arithmetic is that of any shorter call
+    const int rows = (int)n;
+    const int blocks = hidden / RERANK_FEATURES;
+    const dim3 grid((unsigned)blocks, (unsigned)((rows + RERANK_ROWS_PER_BLOCK - 1) / RERANK_ROWS_PER_BLOCK));   // y <= 2^14
+    const size_t lds = (size_t)RERANK_FEATURES * hidden * sizeof(_Float16);
+    RDX_TRY(enc_dynamic_lds(device, (const void*)k_rerank_head, lds));
+    hipLaunchKernelGGL(k_rerank_head, grid, dim3(RERANK_HEAD_THREADS), lds, st, cls, rows, hidden, (const _Float16*)w_dense,
+                       (const _Float16*)b_dense, (const _Float16*)w_out, workspace);
+    HIP_TRY(hipGetLastError());
+    const int rows_per_block = RERANK_THREADS / 64;
+    hipLaunchKernelGGL(k_rerank_combine, dim3((unsigned)((rows + rows_per_block - 1) / rows_per_block)), dim3(RERANK_THREADS), 0, st,
+                       (const double*)workspace, rows, blocks, (const _Float16*)b_out, scores);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+// A shape array of a batched call is read here, to check the call and size its grids, and by the kernels: it has to lie in pinned
+// host memory (hipHostMalloc / hipHostRegister), which both sides address. -> *dev = the address the kernels use. Anything
+// else (device memory, pageable host memory) is refused: nothing is copied and nothing waited for.
+static int shape_array(const char* fn, const char* name, const void* p, size_t align, const void** dev) {
+    if (!p) return fail(RDX_ERR_INVALID, std::string(fn) + ": null pointer (" + name + ")");
+    if ((uintptr_t)p & (align - 1)) return fail(RDX_ERR_INVALID, std::string(fn) + ": misaligned pointer (" + name + ")");
+    hipPointerAttribute_t attr;
+    hipError_t e = hipPointerGetAttributes(&attr, p);
+    if (e != hipSuccess || attr.type != hipMemoryTypeHost) {
+        (void)hipGetLastError();
+        return fail(RDX_ERR_INVALID, std::string(fn) + ": " + name + " must lie in pinned host memory (the library reads it to check the "
+                                     "call and size the launch, the kernels read the same words)");
+    }
+    void* d = nullptr;
+    e = hipHostGetDevicePointer(&d, const_cast<void*>(p), 0);
+    if (e != hipSuccess || !d) {
+        (void)hipGetLastError();
+        return fail(RDX_ERR_INVALID, std::string(fn) + ": " + name + " is pinned host memory that is not mapped to the device");
+    }
+    *dev = d;
+    return RDX_OK;
+}
+
+// cand_off [nq + 1]: starts at 0, never decreases, no segment above 1024, at most 2^20 candidates -> the longest segment
+static int check_segments(const char* fn, const int32_t* cand_off, int nq, int* longest) {
+    if (cand_off[0] != 0) return fail(RDX_ERR_INVALID, std::string(fn) + ": cand_off must start at 0");
+    int top = 0;
+    for (int q = 0; q < nq; ++q) {
+        const int64_t len = (int64_t)cand_off[q + 1] - cand_off[q];
+        if (len < 0) return fail(RDX_ERR_INVALID, std::string(fn) + ": cand_off must not decrease");
+        if (len > RERANK_MAX_N) return fail(RDX_ERR_INVALID, std::string(fn) + ": a question has at most 1024 candidates");
+        top = std::max(top, (int)len);
+    }
+    if (cand_off[nq] > RERANK_BATCH_MAX_ROWS) return fail(RDX_ERR_INVALID, std::string(fn) + ": at most 2^20 candidates per call");
+    *longest = top;
+    return RDX_OK;
+}
+
+extern "C" int rdx_topic_boost_batch(int device, const float* table, int64_t table_rows, int dim, int nq, const int32_t* topic_off,
+                                     const int32_t* topic_slots, const int32_t* tag_off, const int32_t* tag_slots, const int64_t* sim_off,
+                                     const int32_t* cand_off, const int64_t* pair_off, const int32_t* pairs, int64_t n_pairs,
+                                     double threshold, double max_boost, double* sims, double* boosts, double* best_sim, void* stream) {
+    static const char* fn = "rdx_topic_boost_batch";
+    if (nq < 1 || nq > RERANK_BATCH_MAX_QUESTIONS) return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: nq must be in [1, 65535]");
+    if (dim < 1 || dim > TOPIC_MAX_DIM) return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: dim must be in [1, 4096]");
+    if (table_rows < 0 || table_rows > (int64_t)1 << 31) return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: table_rows must be in [0, 2^31]");
+    if (n_pairs < 0) return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: n_pairs must be >= 0");
+    if (!pair_off || !boosts || (n_pairs > 0 && !pairs)) return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: null pointer");
+    if (((uintptr_t)table | (uintptr_t)topic_slots | (uintptr_t)tag_slots | (uintptr_t)pairs) & 3)
+        return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: misaligned pointer");
+    if (((uintptr_t)pair_off | (uintptr_t)sims | (uintptr_t)boosts | (uintptr_t)best_sim) & 7)
+        return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: misaligned pointer");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    const void *d_topic, *d_tag, *d_sim, *d_cand;
+    RDX_TRY(shape_array(fn, "topic_off", topic_off, 4, &d_topic));
+    RDX_TRY(shape_array(fn, "tag_off", tag_off, 4, &d_tag));
+    RDX_TRY(shape_array(fn, "sim_off", sim_off, 8, &d_sim));
+    RDX_TRY(shape_array(fn, "cand_off", cand_off, 4, &d_cand));
+    int longest = 0;
+    RDX_TRY(check_segments(fn, cand_off, nq, &longest));
+    if (topic_off[0] < 0 || tag_off[0] < 0 || sim_off[0] < 0)
+        return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: topic_off, tag_off and sim_off must start at 0 or above");
+    int64_t most = 0;                                                     // max_q T_q * U_q
+    for (int q = 0; q < nq; ++q) {
+        const int64_t T = (int64_t)topic_off[q + 1] - topic_off[q], U = (int64_t)tag_off[q + 1] - tag_off[q];
+        if (T < 0 || T > TOPIC_MAX_TOPICS) return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: a question has 0 to 32 topics (topic_off must not decrease)");
+        if (U < 0 || U > TOPIC_MAX_CALL_TAGS) return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: a question has 0 to 65536 distinct tags (tag_off must not decrease)");
+        if (sim_off[q + 1] - sim_off[q] < T * U)
+            return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: sim_off leaves question q less than its T_q * U_q similarities");
+        most = std::max(most, T * U);
+    }
+    if (most > 0 && ((table_rows > 0 && !table) || !topic_slots || !tag_slots || !sims))
+        return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: null pointer (table, slots or sims)");
+    if (longest == 0) return RDX_OK;                                      // no candidate anywhere: nothing to write
+    hipStream_t st = (hipStream_t)stream;
+    if (most > 0) {
+        const int64_t per = TOPIC_THREADS / 64;
+        hipLaunchKernelGGL(k_topic_sims_batch, dim3((unsigned)((most + per - 1) / per), (unsigned)nq), dim3(TOPIC_THREADS), 0, st, table,
+                           table_rows, dim, (const int32_t*)d_topic, topic_slots, (const int32_t*)d_tag, tag_slots, (const int64_t*)d_sim, sims);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_topic_replay_batch, dim3((unsigned)((longest + TOPIC_THREADS - 1) / TOPIC_THREADS), (unsigned)nq), dim3(TOPIC_THREADS), 0,
+                       st, (const double*)sims, (const int32_t*)d_topic, (const int32_t*)d_tag, (const int64_t*)d_sim, (const int32_t*)d_cand,
+                       pair_off, pairs, n_pairs, threshold, max_boost, boosts, best_sim);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+template <int W>
+static void launch_select_batch(int nq, hipStream_t st, const float* scores, const double* boosts, const int32_t* cand_off, int top_k,
+                                double min_score, int keep_min, int32_t* order, double* final_score, int32_t* count, int32_t* boosted) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rerank_select_batch<W>), dim3((unsigned)nq), dim3(W), 0, st, scores, boosts, cand_off, top_k, min_score,
+                       keep_min, order, final_score, count, boosted);
+}
+
+extern "C" int rdx_rerank_select_batch(int device, const float* scores, const double* boosts, int nq, const int32_t* cand_off, int top_k,
+                                       double min_score, int keep_min, int32_t* order, double* final_score, int32_t* count,
+                                       int32_t* boosted, void* stream) {
+    static const char* fn = "rdx_rerank_select_batch";
+    if (nq < 1 || nq > RERANK_BATCH_MAX_QUESTIONS) return fail(RDX_ERR_INVALID, "rdx_rerank_select_batch: nq must be in [1, 65535]");
+    if (top_k < 0) return fail(RDX_ERR_INVALID, "rdx_rerank_select_batch: top_k must be >= 0");
+    if (keep_min < 0) return fail(RDX_ERR_INVALID, "rdx_rerank_select_batch: keep_min must be >= 0");
+    if (!scores || !order || !final_score || !count) return fail(RDX_ERR_INVALID, "rdx_rerank_select_batch: null pointer");
+    if (((uintptr_t)scores & 3) || ((uintptr_t)boosts & 7) || ((uintptr_t)order & 3) || ((uintptr_t)final_score & 7) || ((uintptr_t)count & 3) ||
+        ((uintptr_t)boosted & 3))
+        return fail(RDX_ERR_INVALID, "rdx_rerank_select_batch: misaligned pointer");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_rerank_select_batch: device out of range");
+    HIP_TRY(hipSetDevice(device));
+    const void* d_cand;
+    RDX_TRY(shape_array(fn, "cand_off", cand_off, 4, &d_cand));
+    int longest = 0;
+    RDX_TRY(check_segments(fn, cand_off, nq, &longest));
+    hipStream_t st = (hipStream_t)stream;
+    const int32_t* co = (const int32_t*)d_cand;
+    if (longest <= RERANK_BATCH_WIDTHS[0])
+        launch_select_batch<RERANK_BATCH_WIDTHS[0]>(nq, st, scores, boosts, co, top_k, min_score, keep_min, order, final_score, count, boosted);
+    else if (longest <= RERANK_BATCH_WIDTHS[1])
+        launch_select_batch<RERANK_BATCH_WIDTHS[1]>(nq, st, scores, boosts, co, top_k, min_score, keep_min, order, final_score, count, boosted);
+    else
+        launch_select_batch<RERANK_BATCH_WIDTHS[2]>(nq, st, scores, boosts, co, top_k, min_score, keep_min, order, final_score, count, boosted);
     HIP_TRY(hipGetLastError());
     return RDX_OK;
 }

@@ -21,6 +21,13 @@ and on a GPU:
     and its device tensor goes to the selection as it is; any other matcher is called per candidate, as in the reference.
 On the CPU the module forward scores and the selection is the Python below. Jina's reranker (the reference's default) needs remote
 code and is not supported: `trust_remote_code` is accepted and never acted on.
+`rerank_batch` takes SEVERAL questions: the pairs of all of them go through the packed forward together, so forwards
+fill to MAX_FORWARD_TOKENS across questions, then one head call (`rdx_rerank_head_rows_f16`), one boost call
+(`rdx_topic_boost_batch`), one selection launch (`rdx_rerank_select_batch`) and ONE copy to the host. What is equal and what is not:
+the head, the boosts and the selection are bit for bit the single-question kernels, so with the same scores in, rerank_batch equals
+[rerank(...)] exactly. The <s> rows are not promised equal: a batch groups pairs into forwards differently and the BLAS GEMMs may
+round differently at another token count; with a real backbone the two agree wherever neighbouring scores differ by more than the
+backbone's tolerance (the statement made against the module forward).
 One deliberate difference: where the reference keeps nothing (n < 3 candidates, none above min_score, or top_k = 0 with n < 3) its
 closing log line indexes the empty result and raises IndexError; here rerank() returns [].
 """
@@ -41,6 +48,8 @@ logger = logging.getLogger(__name__)
 DEFAULT_MODEL = "jinaai/jina-reranker-v2-base-multilingual"
 KEEP_MIN = 3                     # reranker.py:204-205
 MAX_GPU_CANDIDATES = 1024        # rdx_rerank_head_f16 / rdx_rerank_select
+# pairs per device call of rerank_batch: a memory cap (the fp32 <s> rows of 65 536 pairs are 256 MB at H = 1024, the head's workspace 64 MB)
+MAX_BATCH_PAIRS = 65536
 
 # XLM-R-base: the Jina reranker's and most multilingual rerankers' width (its backbone takes the module forward: 768 is not a multiple of 512)
 _XLMR_BASE = dict(_XLMR_LARGE, hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072, max_position_embeddings=514)
@@ -175,6 +184,29 @@ class _CrossEncoderModel:
         cls = self._cls_rows(pairs, batch_size)
         e1.record()
         scores = self.head_device(cls)
+        e2.record()
+        self.stats["events"] = (e0, e1, e2)
+        return scores
+
+    @torch.no_grad()
+    def predict_device_batch(self, pairs, batch_size: int = 32) -> torch.Tensor:
+        """predict_device for the pairs of several questions (any number up to rdx_rerank_head_rows_f16's 2^20): _cls_rows sorts by
+        length and groups across questions, the head runs once. A row's score has the bits rdx_rerank_head_f16 gives that <s> row."""
+        from . import _lib as L
+        if not self.on_gpu:
+            raise RuntimeError("predict_device_batch needs the model on a GPU")
+        n, H = len(pairs), self.hidden
+        if not 1 <= n <= L.RERANK_BATCH_MAX_ROWS:
+            raise ValueError(f"the GPU reranker scores 1 to {L.RERANK_BATCH_MAX_ROWS} pairs per call, got {n}")
+        e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+        e0.record()
+        cls = self._cls_rows(pairs, batch_size).contiguous()
+        e1.record()
+        ws = torch.empty(((H // L.RERANK_FEATURES) * n,), dtype=torch.float64, device=cls.device)
+        scores = torch.empty((n,), dtype=torch.float32, device=cls.device)
+        L.check(self._lib.rdx_rerank_head_rows_f16(cls.device.index or 0, cls.data_ptr(), n, H, self.w_d.data_ptr(), self.b_d.data_ptr(),
+                                                   self.w_o.data_ptr(), self.b_o.data_ptr(), ws.data_ptr(), scores.data_ptr(),
+                                                   torch.cuda.current_stream(cls.device).cuda_stream))
         e2.record()
         self.stats["events"] = (e0, e1, e2)
         return scores
@@ -340,6 +372,155 @@ class CrossEncoderReranker:
         stats.pop("events", None)
         return [RankedChunk(chunk_id=chunks[i].chunk_id, text=chunks[i].text, document_path=chunks[i].document_path,
                             rerank_score=final[i], original_rank=i, metadata=chunks[i].metadata) for i in order[:count]]
+
+    def _pairs(self, query: str, chunks) -> list:
+        """the (question, text) pairs of rerank(): heading prefix, then the max_length * 4 character cut (reranker.py:131-144)"""
+        pairs = []
+        for chunk in chunks:
+            text = chunk.text
+            heading = chunk.metadata.get("heading", "")
+            if heading:
+                text = f"{heading}\n{text}"
+            pairs.append((query, text[:self.max_length * 4]))
+        return pairs
+
+    def rerank_batch(self, queries, chunks_lists, top_k: int = 8, topic_matcher=None, question_topics=None) -> List[List[RankedChunk]]:
+        """rerank() of every question: [rerank(queries[i], chunks_lists[i], top_k, topic_matcher, question_topics[i])].
+        question_topics: None, or one list (or None) per question. On a GPU the pairs of all questions are scored together and the
+        boosts and the selection of all questions run in one call each, with one copy to the host at the end (module docstring:
+        the head, the boosts and the selection are the single-question kernels bit for bit; the backbone's <s> rows are equal up to
+        its tolerance only, because pairs are grouped into forwards differently). Questions are cut into device calls of at most
+        MAX_BATCH_PAIRS pairs. A question with more than 1024 candidates takes rerank(); one without candidates gives []. On the
+        CPU this is the loop. If the batched scoring raises, every question of that call goes through rerank(), which has the
+        reference's own fallback."""
+        queries, chunks_lists = list(queries), [list(c) if c else [] for c in chunks_lists]
+        nq = len(queries)
+        if len(chunks_lists) != nq:
+            raise ValueError(f"rerank_batch: {len(chunks_lists)} candidate lists for {nq} questions")
+        topics = [None] * nq if question_topics is None else list(question_topics)
+        if len(topics) != nq:
+            raise ValueError(f"rerank_batch: question_topics has {len(topics)} entries for {nq} questions")
+        one = lambda i: self.rerank(queries[i], chunks_lists[i], top_k=top_k, topic_matcher=topic_matcher, question_topics=topics[i])   # noqa: E731
+        if not str(self.device).startswith("cuda"):
+            return [one(i) for i in range(nq)]
+        from . import _lib as L
+        out: List[Optional[List[RankedChunk]]] = [None] * nq
+        groups, group, held = [], [], 0
+        for i, chunks in enumerate(chunks_lists):
+            if not chunks:
+                out[i] = []
+            elif len(chunks) > MAX_GPU_CANDIDATES:
+                out[i] = one(i)
+            else:
+                if group and (held + len(chunks) > MAX_BATCH_PAIRS or len(group) >= L.RERANK_BATCH_MAX_QUESTIONS):
+                    groups.append(group)
+                    group, held = [], 0
+                group.append(i)
+                held += len(chunks)
+        if group:
+            groups.append(group)
+        if not groups:
+            return out
+        self._load_model()
+        total = {"questions": 0, "pairs": 0, "tokens": None, "ms_forward": None, "ms_head_select": None, "path": None, "kept": 0, "device_calls": 0}
+        t0 = time.perf_counter()
+        for group in groups:
+            ranked = self._rerank_group(group, queries, chunks_lists, topics, top_k, topic_matcher, total)
+            if ranked is None:                                       # the scoring raised: the reference's fallback, question by question
+                ranked = [one(i) for i in group]
+                total["path"] = "loop"
+            for i, r in zip(group, ranked):
+                out[i] = r
+        total["ms_total"] = (time.perf_counter() - t0) * 1e3
+        self.last_rerank_stats = total
+        return out
+
+    def _rerank_group(self, group, queries, chunks_lists, topics, top_k, topic_matcher, total):
+        """one device call of rerank_batch over the questions `group` (each 1 to 1024 candidates) -> their results, or None when the
+        scoring raised"""
+        from . import _lib as L
+        lib = L.load()
+        m = self._model
+        dev = torch.device(self.device)
+        pairs, cand_off = [], [0]
+        for i in group:
+            pairs.extend(self._pairs(queries[i], chunks_lists[i]))
+            cand_off.append(len(pairs))
+        n_total, nq = len(pairs), len(group)
+        try:
+            if hasattr(m, "predict_device_batch"):
+                scores, path = m.predict_device_batch(pairs, batch_size=self.batch_size), getattr(m, "path", "device")
+            else:
+                s = np.asarray(m.predict(pairs, batch_size=self.batch_size, show_progress_bar=False), dtype=np.float32).reshape(-1)
+                if len(s) != n_total:
+                    raise ValueError(f"predict returned {len(s)} scores for {n_total} pairs")
+                scores, path = torch.from_numpy(np.ascontiguousarray(s)).to(dev), getattr(m, "path", "predict")
+        except Exception as e:  # noqa: BLE001
+            logger.error(f"batched reranking failed ({e}): question by question")
+            return None
+        scores = scores.contiguous()
+        dev = scores.device
+        # boosts: the matcher's batched device call where it has one on this GPU, else the reference's call per candidate
+        boosts, counted = None, [False] * nq
+        wants = [topic_matcher is not None and bool(topics[i]) for i in group]
+        if any(wants):
+            tags = lambda i: [c.metadata.get("rgpd_topics", "") for c in chunks_lists[i]]   # noqa: E731
+            if hasattr(topic_matcher, "topic_boosts_device_batch") and self._boosts_on_device(topic_matcher, 1):
+                boosts = topic_matcher.topic_boosts_device_batch([topics[i] if w else [] for i, w in zip(group, wants)], [tags(i) for i in group])
+                if boosts.dtype != torch.float64 or boosts.device != dev or boosts.numel() != n_total:
+                    raise ValueError(f"topic_boosts_device_batch must return fp64 [{n_total}] on {dev}, got {boosts.dtype} [{boosts.numel()}] on {boosts.device}")
+                boosts = boosts.contiguous()
+                counted = wants
+            else:
+                host = np.zeros((n_total,), dtype=np.float64)
+                for q, (i, w) in enumerate(zip(group, wants)):
+                    if not w:
+                        continue
+                    b = [topic_matcher.topic_boost(topics[i], t) for t in tags(i)]
+                    host[cand_off[q]:cand_off[q + 1]] = b
+                    hit = sum(1 for x in b if x > 0)
+                    if hit:
+                        logger.info(f"topic boost applied to {hit}/{len(b)} chunks")
+                boosts = torch.from_numpy(host).to(dev)
+        # one output buffer, one copy back: final fp64 [n_total] | order int32 [n_total] | count int32 [nq] | boosted int32 [nq]
+        buf = torch.empty((8 * n_total + 4 * n_total + 8 * nq,), dtype=torch.uint8, device=dev)
+        base = buf.data_ptr()
+        shape = torch.tensor(cand_off, dtype=torch.int32).pin_memory()   # (read by the library here and by the kernel: pinned; alive until the copy below has drained the stream)
+        s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s0.record()
+        L.check(lib.rdx_rerank_select_batch(dev.index or 0, scores.data_ptr(), boosts.data_ptr() if boosts is not None else None, nq,
+                                            shape.data_ptr(), int(top_k), float(self.min_score), KEEP_MIN, base + 8 * n_total, base,
+                                            base + 12 * n_total, base + 12 * n_total + 4 * nq, torch.cuda.current_stream(dev).cuda_stream))
+        s1.record()
+        host = buf.cpu().numpy()                                         # THE copy: it drains the stream
+        final = host[:8 * n_total].view(np.float64)
+        order = host[8 * n_total:12 * n_total].view(np.int32)
+        count = host[12 * n_total:12 * n_total + 4 * nq].view(np.int32)
+        boosted = host[12 * n_total + 4 * nq:].view(np.int32)
+        ranked = []
+        for q, i in enumerate(group):
+            lo, chunks = cand_off[q], chunks_lists[i]
+            if counted[q] and boosted[q]:
+                logger.info(f"topic boost applied to {int(boosted[q])}/{len(chunks)} chunks")
+            ranked.append([RankedChunk(chunk_id=chunks[p].chunk_id, text=chunks[p].text, document_path=chunks[p].document_path,
+                                       rerank_score=float(final[lo + p]), original_rank=int(p), metadata=chunks[p].metadata)
+                           for p in order[lo:lo + int(count[q])].tolist()])
+        add = lambda k, v: total.__setitem__(k, v if total[k] is None else total[k] + v)   # noqa: E731
+        total["questions"] += nq
+        total["pairs"] += n_total
+        total["kept"] += int(count.sum())
+        total["device_calls"] += 1
+        total["path"] = path
+        ms_select = s0.elapsed_time(s1)
+        if isinstance(m, _CrossEncoderModel):
+            if m.stats.get("tokens") is not None:
+                add("tokens", m.stats["tokens"])
+            ev = m.stats.pop("events", None)
+            if ev is not None:
+                add("ms_forward", ev[0].elapsed_time(ev[1]))
+                ms_select += ev[1].elapsed_time(ev[2])
+        add("ms_head_select", ms_select)
+        return ranked
 
     def _boosts_on_device(self, topic_matcher, n: int) -> bool:
         """a matcher with topic_boosts_device whose table lives on the GPU this reranker selects on"""

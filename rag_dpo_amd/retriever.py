@@ -279,6 +279,32 @@ class DenseRetriever:
         ranked = reranker.rerank(query=query, chunks=candidates, top_k=top_k, topic_matcher=topic_matcher, question_topics=question_topics)
         return documents_from_ranked_chunks(ranked)
 
+    def retrieve_reranked_batch(self, queries: Sequence[str], reranker, n_candidates: int = 40, top_k: int = 10, where_filter=None,
+                                topic_matcher=None, question_topics=None) -> List[List[RetrievedDocument]]:
+        """retrieve_reranked of every question: retrieve_candidates_batch, then the reranker's rerank_batch (a reranker without one is
+        called question by question), then the documents rebuilt per question on the host (at most top_k winners each). A question
+        without candidates gives []. question_topics: None, or one list (or None) per question. With a reranker whose scores do not
+        depend on how pairs are grouped this equals [retrieve_reranked(...)] exactly; a real backbone's scores agree up to its
+        tolerance (rag_dpo_amd/reranker.py)."""
+        queries = list(queries)
+        topics = [None] * len(queries) if question_topics is None else list(question_topics)
+        if len(topics) != len(queries):
+            raise ValueError(f"question_topics has {len(topics)} entries for {len(queries)} questions")
+        candidates = self.retrieve_candidates_batch(queries, n_candidates=n_candidates, where_filter=where_filter)
+        live = [i for i, c in enumerate(candidates) if c]
+        out: List[List[RetrievedDocument]] = [[] for _ in queries]
+        if not live:
+            return out
+        if hasattr(reranker, "rerank_batch"):
+            ranked = reranker.rerank_batch([queries[i] for i in live], [candidates[i] for i in live], top_k=top_k, topic_matcher=topic_matcher,
+                                           question_topics=[topics[i] for i in live])
+        else:
+            ranked = [reranker.rerank(query=queries[i], chunks=candidates[i], top_k=top_k, topic_matcher=topic_matcher,
+                                      question_topics=topics[i]) for i in live]
+        for i, r in zip(live, ranked):
+            out[i] = documents_from_ranked_chunks(r)
+        return out
+
     def retrieve(self, query: str, where_filter=None, n_documents: Optional[int] = None,
                  n_chunks_per_doc: Optional[int] = None) -> List[RetrievedDocument]:
         """reference src/rag/retriever.py:156-310: BM25 for the main query only, weight 2.0"""

@@ -20,7 +20,10 @@ rounded once). A similarity is the fp64 sum of the exact products in the kernel'
 and in the host evaluator below alike: the two agree bit for bit, and differ from numpy's `dot` of the reference by the order of the
 additions only (|d sim| <= dim * 2^-53 * sum |a_i b_i|). `embed_device` of this project's provider returns rows that are NOT yet
 normalised; they are normalised here by `rdx_l2_normalize`, the very step `embed()` applies, so both ways store the same bits.
-A call beyond the kernel's limits (1024 candidates, 32 topics, 64 tags per candidate, dim 4096) is evaluated by the host evaluator."""
+A call beyond the kernel's limits (1024 candidates, 32 topics, 64 tags per candidate, dim 4096) is evaluated by the host evaluator.
+`topic_boosts_device_batch` does the same for the candidates of SEVERAL questions: one `_Plan` per question, one embed call for the
+batch's unseen strings, one upload and one `rdx_topic_boost_batch` call; per question the bits of
+`topic_boosts_device`."""
 from __future__ import annotations
 
 import logging
@@ -106,6 +109,31 @@ class _Plan:
         return list(dict.fromkeys(self.topics + self.tags)) if self.tags else []
 
 
+def pack_plans(plans: Sequence[_Plan], slot_of) -> dict:
+    """The plans of several questions in rdx_topic_boost_batch's layout (include/rdx.h), as host arrays. Question q's topics are
+    topic_slots[topic_off[q]:topic_off[q + 1]], its distinct tags tag_slots[tag_off[q]:tag_off[q + 1]], its candidates the segment
+    [cand_off[q], cand_off[q + 1]) of the candidate axis and its similarity block starts at sim_off[q] ([T_q][U_q] doubles, one
+    block behind the other). pair_off (int64) is ONE running offset array over the whole axis; the pair words keep the topic and tag
+    indices LOCAL to their question, exactly the words a single-question call gets. slot_of: text -> table row, or -1."""
+    from . import _lib as L
+    nq = len(plans)
+    topic_off, tag_off, cand_off = (np.zeros((nq + 1,), dtype=np.int32) for _ in range(3))
+    sim_off = np.zeros((nq + 1,), dtype=np.int64)
+    topic_slots, tag_slots, pair_off, pairs = [], [], [0], []
+    for q, plan in enumerate(plans):
+        T, U, n = len(plan.topics), len(plan.tags), len(plan.offsets) - 1
+        topic_slots.extend(slot_of(t) for t in plan.topics)
+        tag_slots.extend(slot_of(t) for t in plan.tags)
+        base = len(pairs)
+        pairs.extend(L.topic_pair(t, u, e) for t, u, e in plan.pairs)
+        pair_off.extend(base + o for o in plan.offsets[1:])
+        topic_off[q + 1], tag_off[q + 1], cand_off[q + 1] = topic_off[q] + T, tag_off[q] + U, cand_off[q] + n
+        sim_off[q + 1] = sim_off[q] + T * U
+    return {"topic_off": topic_off, "tag_off": tag_off, "cand_off": cand_off, "sim_off": sim_off,
+            "topic_slots": np.asarray(topic_slots, dtype=np.int32), "tag_slots": np.asarray(tag_slots, dtype=np.int32),
+            "pair_off": np.asarray(pair_off, dtype=np.int64), "pairs": np.asarray(pairs, dtype=np.int32)}
+
+
 class TopicMatcher:
     """Semantic matching of question topics and chunk tags; one instance serves every session, as the provider does."""
 
@@ -129,6 +157,8 @@ class TopicMatcher:
         self._lib = None
         self._staging: list = []     # pinned int32 buffers of the plans' uploads, each with the event of the copy that read it last
         self._staging_next = 0
+        self._shapes: list = []      # pinned int32 buffers of the batched calls' shape arrays, each with the event behind the kernels that read it
+        self._shapes_next = 0
         self.stats = {"embed_calls": 0, "embedded": 0, "device_calls": 0, "host_calls": 0}
         if self.on_gpu:
             from . import _lib
@@ -287,6 +317,34 @@ class TopicMatcher:
             return self._device(plan, threshold)
         return torch.from_numpy(np.asarray(self._host(plan, threshold)[0], dtype=np.float64)).to(self.device)
 
+    def topic_boosts_device_batch(self, question_topics_list: Sequence, chunk_tags_strs_list: Sequence[Sequence],
+                                  threshold: float = DEFAULT_THRESHOLD) -> torch.Tensor:
+        """topic_boosts_device for several questions at once: fp64 [n_total] on the matcher's device, question q's candidates at
+        [sum of the lengths before it, ...), enqueued on the current stream; nothing is synchronised. One plan per question, ONE
+        embed call for every string of the batch that has no embedding yet, one upload and one rdx_topic_boost_batch call: per
+        question the bits of topic_boosts_device on that question alone. A question beyond the kernel's limits (_fits_kernel) is
+        evaluated by the host evaluator, that question only, and its values are copied into place."""
+        if not self.on_gpu:
+            raise RuntimeError("topic_boosts_device_batch needs the matcher on a GPU")
+        topics_list, tags_list = list(question_topics_list), [list(t) for t in chunk_tags_strs_list]
+        if len(topics_list) != len(tags_list):
+            raise ValueError(f"topic_boosts_device_batch: {len(topics_list)} topic lists for {len(tags_list)} candidate lists")
+        plans = [_Plan(t, c) for t, c in zip(topics_list, tags_list)]
+        self._ensure([s for plan in plans for s in plan.strings()])
+        on_device = [q for q, plan in enumerate(plans) if self._fits_kernel(plan, threshold)]
+        dev = self._device_batch([plans[q] for q in on_device], threshold) if on_device else None
+        if dev is not None and len(on_device) == sum(1 for plan in plans if len(plan.offsets) > 1):
+            return dev                                           # every question that has candidates went to the kernel: its axis is the answer
+        pieces, at, where = [], 0, set(on_device)
+        for q, plan in enumerate(plans):
+            n = len(plan.offsets) - 1
+            if q in where:
+                pieces.append(dev[at:at + n])
+                at += n
+            elif n:
+                pieces.append(torch.from_numpy(np.asarray(self._host(plan, threshold)[0], dtype=np.float64)).to(self.device))
+        return torch.cat(pieces) if pieces else torch.empty((0,), dtype=torch.float64, device=self.device)
+
     def best_similarities(self, question_topics: List[str], chunk_tags_strs: Sequence[str]) -> List[float]:
         """the best similarity behind each boost (the host evaluator's; the kernel's `best_sim` holds the same bits)"""
         return self._host(self._plan(question_topics, chunk_tags_strs), DEFAULT_THRESHOLD, boosts=False)[1]
@@ -350,6 +408,59 @@ class TopicMatcher:
         slot[1] = torch.cuda.Event()
         slot[1].record(torch.cuda.current_stream(self.device))
         return dev
+
+    def _pin_shapes(self, words: np.ndarray):
+        """int32 host words -> a pinned buffer that stays as it is until the kernels reading it have run: the caller records
+        slot[1] behind its launch. -> (the pinned tensor, slot)"""
+        if len(self._shapes) < 4:
+            self._shapes.append([torch.empty((max(1024, 2 * len(words)),), dtype=torch.int32).pin_memory(), None])
+            slot = self._shapes[-1]
+        else:
+            slot = self._shapes[self._shapes_next]
+            self._shapes_next = (self._shapes_next + 1) % len(self._shapes)
+            if slot[1] is not None:
+                slot[1].synchronize()
+            if slot[0].numel() < len(words):
+                slot[0] = torch.empty((2 * len(words),), dtype=torch.int32).pin_memory()
+        buf = slot[0][:len(words)]
+        buf.numpy()[:] = words
+        return buf, slot
+
+    def _device_batch(self, plans: Sequence[_Plan], threshold: float, want_best: bool = False):
+        """rdx_topic_boost_batch on plans that fit the kernel -> fp64 [sum of their candidates] (and the best similarities)"""
+        from . import _lib as L
+        self.stats["device_calls"] += 1
+        nq = len(plans)
+        with self._lock, torch.cuda.device(self.device):
+            p = pack_plans(plans, lambda t: self._slots.get(t, -1))
+            n, T, U, P = int(p["cand_off"][-1]), len(p["topic_slots"]), len(p["tag_slots"]), len(p["pairs"])
+            # shape arrays, pinned (the library reads them on the host, the kernels the same words): three int32 arrays, then sim_off (int64, 8-byte aligned)
+            pad = (3 * (nq + 1)) % 2
+            shape = np.zeros((3 * (nq + 1) + pad + 2 * (nq + 1),), dtype=np.int32)
+            shape[:nq + 1], shape[nq + 1:2 * (nq + 1)], shape[2 * (nq + 1):3 * (nq + 1)] = p["topic_off"], p["tag_off"], p["cand_off"]
+            shape[3 * (nq + 1) + pad:] = p["sim_off"].view(np.int32)
+            pinned, slot = self._pin_shapes(shape)
+            # everything else in one upload: the slots, then pair_off (int64, 8-byte aligned), then the pair words
+            at_off = T + U + (T + U) % 2
+            words = np.zeros((at_off + 2 * (n + 1) + P,), dtype=np.int32)
+            words[:T], words[T:T + U] = p["topic_slots"], p["tag_slots"]
+            words[at_off:at_off + 2 * (n + 1)] = p["pair_off"].view(np.int32)
+            words[at_off + 2 * (n + 1):] = p["pairs"]
+            d = self._upload(words)
+            table, rows, dim = self._table, len(self._slots), self._dim or 1
+            sims = torch.empty((max(1, int(p["sim_off"][-1])),), dtype=torch.float64, device=self.device)
+            boosts = torch.empty((n,), dtype=torch.float64, device=self.device)
+            best = torch.empty((n,), dtype=torch.float64, device=self.device) if want_best else None
+            base, sbase = d.data_ptr(), pinned.data_ptr()
+            stream = torch.cuda.current_stream(self.device)
+            L.check(self._lib.rdx_topic_boost_batch(self.device.index, table.data_ptr() if table is not None else None, rows, dim, nq,
+                                                    sbase, base, sbase + 4 * (nq + 1), base + 4 * T, sbase + 4 * (3 * (nq + 1) + pad),
+                                                    sbase + 8 * (nq + 1), base + 4 * at_off, base + 4 * (at_off + 2 * (n + 1)), P,
+                                                    float(threshold), MAX_BOOST, sims.data_ptr(), boosts.data_ptr(),
+                                                    best.data_ptr() if best is not None else None, stream.cuda_stream))
+            slot[1] = torch.cuda.Event()
+            slot[1].record(stream)
+        return (boosts, best) if want_best else boosts
 
     def _device(self, plan: _Plan, threshold: float, want_best: bool = False):
         from . import _lib as L
