@@ -22,6 +22,7 @@ import shutil
 import subprocess
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
+from typing import NamedTuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -119,6 +120,58 @@ def check_isa(work: str) -> dict:
                        "C: 5 wait states between a VALU SGPR write and an asm VMEM read of it"]}
 
 
+class SpillCheck(NamedTuple):
+    """one condition under which build_lib refuses a library, read from the compiler's resource remarks"""
+    fragments: tuple      # a kernel belongs to the check when its symbol holds one of these
+    least: int            # kernels there must be (0: however many there are)
+    remarks: str          # kernels whose remarks lack the spill or scratch figure: "counted" out of `least`, "required" (one refuses), "ignored"
+    spill: bool           # refuse a kernel that spills or uses scratch
+    variant: bool         # checked in a variant build (extra_flags) too: a variant may spill where that only costs speed, it is nobody's product
+    message: str          # {n}: kernels found; behind a spill check the kernels follow (the offenders alone when least is 0)
+
+
+SPILL_CHECKS = (
+    SpillCheck(("k_scan",), 16, "counted", False, True,
+               "the compiler's resource remarks could not be read for the scan kernels — refused (the spill check would be blind)"),
+    SpillCheck(("k_scan",), 0, "ignored", True, True,
+               "scan kernels spill registers — refused (inline-asm loads may be in flight to a spilled register):"),
+    SpillCheck(("k_docs",), 4, "ignored", True, True, "the where_document kernels (doc_kernel.hpp) spill or were not found — refused:"),
+    SpillCheck(("k_meta",), 2, "required", True, True, "the `where` predicate kernels (meta_kernel.hpp) spill or were not found — refused:"),
+    SpillCheck(("k_topic",), 2, "required", True, True, "the topic boost kernels (topic_kernel.hpp) spill or were not found — refused:"),
+    SpillCheck(("k_rerank_select_batch", "k_topic_sims_batch", "k_topic_replay_batch"), 5, "required", True, True,
+               "the batched reranker kernels (rerank_batch_kernel.hpp) spill or were not found — refused:"),
+    SpillCheck(("k_space",), 5, "required", True, True, "the ip / l2 space kernels (space_kernel.hpp) spill or were not found — refused:"),
+    SpillCheck(("k_fuse",), 1, "required", True, True, "the rank fusion kernel (fuse_kernel.hpp) spills or was not found — refused:"),
+    # k_refine / k_refine_spill run 1024 threads at the 128-register limit (refine_kernel.hpp): a spill would be paid on every search
+    SpillCheck(("k_refine",), 2, "required", True, False, "the refine kernels (refine_kernel.hpp) spill or were not found — refused:"),
+    # kernels that are given an occupancy target (amdgpu_waves_per_eu: the latency-bound attention kernel E12) pay for a miss
+    # silently, in scratch traffic
+    SpillCheck(("k_enc_attention_mfma",), 0, "ignored", True, False,
+               "k_enc_attention_mfma no longer fits its occupancy target without spilling — refused:"),
+    # the batch GEMM (E14, enc_gemm.hpp) is sized for two or three workgroups per CU; scratch traffic in its k-loop would cost that silently
+    SpillCheck(("k_enc_gemm",), 6, "required", False, True,
+               "the compiler's resource remarks could not be read for the k_enc_gemm kernels ({n} found) — refused"),
+    SpillCheck(("k_enc_gemm",), 0, "ignored", True, False, "k_enc_gemm kernels spill or use scratch — refused:"),
+)
+
+
+def refusals(res: dict, variant: bool = False) -> list:
+    """the messages of the SPILL_CHECKS that the resource record `res` (parse_resources) fails, in the table's order; a variant
+    build is asked only the checks marked for it. build_lib raises on the first."""
+    out = []
+    for c in SPILL_CHECKS:
+        if variant and not c.variant:
+            continue
+        found = {k: v for k, v in res.items() if any(f in k for f in c.fragments)}
+        readable = [k for k, v in found.items() if "spill_vgprs" in v and "scratch_bytes" in v]
+        spilling = {k: v for k, v in found.items() if v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0)}
+        if (len(readable) if c.remarks == "counted" else len(found)) < c.least or (c.remarks == "required" and len(readable) < len(found)) \
+                or (c.spill and spilling):
+            listed = found if c.least else spilling
+            out.append(c.message.format(n=len(found)) + ("\n" + "\n".join(f"  {k}: {v}" for k, v in listed.items()) if c.spill else ""))
+    return out
+
+
 def build_lib(force: bool = False, verbose: bool = False, extra_flags=(), out: str = None) -> str:
     """out: build a VARIANT (extra_flags) to this path; the product library and its resource record are left alone"""
     if out is None and not force and is_fresh() and not extra_flags:
@@ -152,62 +205,9 @@ def build_lib(force: bool = False, verbose: bool = False, extra_flags=(), out: s
         if r.returncode != 0:
             raise RuntimeError(f"linking librdx failed ({r.returncode}):\n{r.stderr[-4000:]}")
         res = parse_resources(remarks)
-        if sum(1 for k, v in res.items() if "k_scan" in k and "spill_vgprs" in v and "scratch_bytes" in v) < 16:
-            raise RuntimeError("the compiler's resource remarks could not be read for the scan kernels — refused (the spill check would be blind)")
-        bad = {k: v for k, v in res.items() if "k_scan" in k and (v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0))}
-        if bad:
-            raise RuntimeError("scan kernels spill registers — refused (inline-asm loads may be in flight to a spilled register):\n" +
-                               "\n".join(f"  {k}: {v}" for k, v in bad.items()))
-        docs = {k: v for k, v in res.items() if "k_docs" in k}
-        if len(docs) < 4 or any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in docs.values()):
-            raise RuntimeError("the where_document kernels (doc_kernel.hpp) spill or were not found — refused:\n" +
-                               "\n".join(f"  {k}: {v}" for k, v in docs.items()))
-        meta = {k: v for k, v in res.items() if "k_meta" in k}
-        if len(meta) < 2 or any("spill_vgprs" not in v or "scratch_bytes" not in v for v in meta.values()) or \
-                any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in meta.values()):
-            raise RuntimeError("the `where` predicate kernels (meta_kernel.hpp) spill or were not found — refused:\n" +
-                               "\n".join(f"  {k}: {v}" for k, v in meta.items()))
-        topic = {k: v for k, v in res.items() if "k_topic" in k}
-        if len(topic) < 2 or any("spill_vgprs" not in v or "scratch_bytes" not in v for v in topic.values()) or \
-                any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in topic.values()):
-            raise RuntimeError("the topic boost kernels (topic_kernel.hpp) spill or were not found — refused:\n" +
-                               "\n".join(f"  {k}: {v}" for k, v in topic.items()))
-        batch = {k: v for k, v in res.items() if "k_rerank_select_batch" in k or "k_topic_sims_batch" in k or "k_topic_replay_batch" in k}
-        if len(batch) < 5 or any("spill_vgprs" not in v or "scratch_bytes" not in v for v in batch.values()) or \
-                any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in batch.values()):
-            raise RuntimeError("the batched reranker kernels (rerank_batch_kernel.hpp) spill or were not found — refused:\n" +
-                               "\n".join(f"  {k}: {v}" for k, v in batch.items()))
-        space = {k: v for k, v in res.items() if "k_space" in k}
-        if len(space) < 5 or any("spill_vgprs" not in v or "scratch_bytes" not in v for v in space.values()) or \
-                any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in space.values()):
-            raise RuntimeError("the ip / l2 space kernels (space_kernel.hpp) spill or were not found — refused:\n" +
-                               "\n".join(f"  {k}: {v}" for k, v in space.items()))
-        fuse = {k: v for k, v in res.items() if "k_fuse" in k}
-        if len(fuse) < 1 or any("spill_vgprs" not in v or "scratch_bytes" not in v for v in fuse.values()) or \
-                any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in fuse.values()):
-            raise RuntimeError("the rank fusion kernel (fuse_kernel.hpp) spills or was not found — refused:\n" +
-                               "\n".join(f"  {k}: {v}" for k, v in fuse.items()))
-        # k_refine / k_refine_spill run 1024 threads at the 128-register limit (refine_kernel.hpp): a spill would be paid on every search
-        refine = {k: v for k, v in res.items() if "k_refine" in k}
-        if extra_flags:
-            pass   # (a variant build may spill: it is nobody's product)
-        elif len(refine) < 2 or any("spill_vgprs" not in v or "scratch_bytes" not in v for v in refine.values()) or \
-                any(v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0) for v in refine.values()):
-            raise RuntimeError("the refine kernels (refine_kernel.hpp) spill or were not found — refused:\n" +
-                               "\n".join(f"  {k}: {v}" for k, v in refine.items()))
-        # kernels that are given an occupancy target (amdgpu_waves_per_eu: the latency-bound attention kernel E12) pay for a miss
-        # silently, in scratch traffic: refused as well (a variant build with extra flags may spill: it is nobody's product)
-        slow = {k: v for k, v in res.items() if "k_enc_attention_mfma" in k and (v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0))}
-        if slow and not extra_flags:
-            raise RuntimeError("k_enc_attention_mfma no longer fits its occupancy target without spilling — refused:\n" +
-                               "\n".join(f"  {k}: {v}" for k, v in slow.items()))
-        # the batch GEMM (E14, enc_gemm.hpp) is sized for two or three workgroups per CU; scratch traffic in its k-loop would cost that silently
-        gemm = {k: v for k, v in res.items() if "k_enc_gemm" in k}
-        if len(gemm) < 6 or any("spill_vgprs" not in v or "scratch_bytes" not in v for v in gemm.values()):
-            raise RuntimeError(f"the compiler's resource remarks could not be read for the k_enc_gemm kernels ({len(gemm)} found) — refused")
-        bad = {k: v for k, v in gemm.items() if v.get("spill_vgprs", 0) or v.get("scratch_bytes", 0)}
-        if bad and not extra_flags:
-            raise RuntimeError("k_enc_gemm kernels spill or use scratch — refused:\n" + "\n".join(f"  {k}: {v}" for k, v in bad.items()))
+        refused = refusals(res, variant=bool(extra_flags))
+        if refused:
+            raise RuntimeError(refused[0])
         isa = check_isa(work)
         final_tmp = (out or LIB) + ".tmp"
         shutil.move(tmp, final_tmp)

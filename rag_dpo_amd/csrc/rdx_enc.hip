@@ -345,41 +345,61 @@ extern "C" int rdx_enc_gelu_f16(int device, void* x, int64_t n, void* stream) {
 // ------------------------------------------------------------------------------------------------
 // cross-encoder reranker: classification head and selection (rerank_kernel.hpp)
 // ------------------------------------------------------------------------------------------------
-extern "C" int rdx_rerank_head_f16(int device, const float* cls, int n, int hidden, const void* w_dense, const void* b_dense,
-                                   const void* w_out, const void* b_out, double* workspace, float* scores, void* stream) {
-    if (n < 1 || n > RERANK_MAX_N) return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: n must be in [1, 1024]");
-    if (hidden < 64 || hidden > RERANK_MAX_HIDDEN || hidden % 64)
-        return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: hidden must be a multiple of 64 in [64, 4096]");
-    if (!cls || !w_dense || !b_dense || !w_out || !b_out || !workspace || !scores) return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: null pointer");
-    if (((uintptr_t)cls | (uintptr_t)w_dense) & 15) return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: cls and w_dense must be 16-byte aligned");
+// the head's two kernels over n rows, for both entry points (fn: the entry point's name, range: its bound on n, as its messages say it)
+static int launch_rerank_head(const char* fn, int64_t max_n, const char* range, int device, const float* cls, int64_t n, int hidden,
+                              const void* w_dense, const void* b_dense, const void* w_out, const void* b_out, double* workspace,
+                              float* scores, void* stream) {
+    const std::string f(fn);
+    if (n < 1 || n > max_n) return fail(RDX_ERR_INVALID, f + ": n must be in " + range);
+    if (hidden < 64 || hidden > RERANK_MAX_HIDDEN || hidden % 64) return fail(RDX_ERR_INVALID, f + ": hidden must be a multiple of 64 in [64, 4096]");
+    if (!cls || !w_dense || !b_dense || !w_out || !b_out || !workspace || !scores) return fail(RDX_ERR_INVALID, f + ": null pointer");
+    if (((uintptr_t)cls | (uintptr_t)w_dense) & 15) return fail(RDX_ERR_INVALID, f + ": cls and w_dense must be 16-byte aligned");
     if (((uintptr_t)b_dense | (uintptr_t)w_out | (uintptr_t)b_out) & 1 || ((uintptr_t)workspace & 7) || ((uintptr_t)scores & 3))
-        return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: misaligned pointer");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_rerank_head_f16: device out of range");
+        return fail(RDX_ERR_INVALID, f + ": misaligned pointer");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, f + ": device out of range");
     HIP_TRY(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
+    // workgroup (b, y) takes rows [64 y, 64 y + 64) whatever n is, and row r's partials lie at part[b * n + r] (size_t: 2^29 words at
+    // the limits), so a row's arithmetic is that of any shorter call
+    const int rows = (int)n;
     const int blocks = hidden / RERANK_FEATURES;
-    const dim3 grid((unsigned)blocks, (unsigned)((n + RERANK_ROWS_PER_BLOCK - 1) / RERANK_ROWS_PER_BLOCK));
+    const dim3 grid((unsigned)blocks, (unsigned)((rows + RERANK_ROWS_PER_BLOCK - 1) / RERANK_ROWS_PER_BLOCK));   // y <= 2^14
     const size_t lds = (size_t)RERANK_FEATURES * hidden * sizeof(_Float16);   // <= 64 KiB at hidden 4096
     RDX_TRY(enc_dynamic_lds(device, (const void*)k_rerank_head, lds));
-    hipLaunchKernelGGL(k_rerank_head, grid, dim3(RERANK_HEAD_THREADS), lds, st, cls, n, hidden, (const _Float16*)w_dense,
+    hipLaunchKernelGGL(k_rerank_head, grid, dim3(RERANK_HEAD_THREADS), lds, st, cls, rows, hidden, (const _Float16*)w_dense,
                        (const _Float16*)b_dense, (const _Float16*)w_out, workspace);
     HIP_TRY(hipGetLastError());
     const int rows_per_block = RERANK_THREADS / 64;                           // K_R2: one wave per row
-    hipLaunchKernelGGL(k_rerank_combine, dim3((unsigned)((n + rows_per_block - 1) / rows_per_block)), dim3(RERANK_THREADS), 0, st,
-                       (const double*)workspace, n, blocks, (const _Float16*)b_out, scores);
+    hipLaunchKernelGGL(k_rerank_combine, dim3((unsigned)((rows + rows_per_block - 1) / rows_per_block)), dim3(RERANK_THREADS), 0, st,
+                       (const double*)workspace, rows, blocks, (const _Float16*)b_out, scores);
     HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+extern "C" int rdx_rerank_head_f16(int device, const float* cls, int n, int hidden, const void* w_dense, const void* b_dense,
+                                   const void* w_out, const void* b_out, double* workspace, float* scores, void* stream) {
+    return launch_rerank_head("rdx_rerank_head_f16", RERANK_MAX_N, "[1, 1024]", device, cls, n, hidden, w_dense, b_dense, w_out, b_out,
+                              workspace, scores, stream);
+}
+
+// what rdx_rerank_select and rdx_rerank_select_batch check alike (boosted: the batch's, NULL for the single call)
+static int check_select_args(const char* fn, const float* scores, const double* boosts, int top_k, int keep_min, const int32_t* order,
+                             const double* final_score, const int32_t* count, const int32_t* boosted, int device) {
+    const std::string f(fn);
+    if (top_k < 0) return fail(RDX_ERR_INVALID, f + ": top_k must be >= 0");
+    if (keep_min < 0) return fail(RDX_ERR_INVALID, f + ": keep_min must be >= 0");
+    if (!scores || !order || !final_score || !count) return fail(RDX_ERR_INVALID, f + ": null pointer");
+    if (((uintptr_t)scores & 3) || ((uintptr_t)boosts & 7) || ((uintptr_t)order & 3) || ((uintptr_t)final_score & 7) || ((uintptr_t)count & 3) ||
+        ((uintptr_t)boosted & 3))
+        return fail(RDX_ERR_INVALID, f + ": misaligned pointer");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, f + ": device out of range");
     return RDX_OK;
 }
 
 extern "C" int rdx_rerank_select(int device, const float* scores, const double* boosts, int n, int top_k, double min_score,
                                  int keep_min, int32_t* order, double* final_score, int32_t* count, void* stream) {
     if (n < 1 || n > RERANK_MAX_N) return fail(RDX_ERR_INVALID, "rdx_rerank_select: n must be in [1, 1024]");
-    if (top_k < 0) return fail(RDX_ERR_INVALID, "rdx_rerank_select: top_k must be >= 0");
-    if (keep_min < 0) return fail(RDX_ERR_INVALID, "rdx_rerank_select: keep_min must be >= 0");
-    if (!scores || !order || !final_score || !count) return fail(RDX_ERR_INVALID, "rdx_rerank_select: null pointer");
-    if (((uintptr_t)scores & 3) || ((uintptr_t)boosts & 7) || ((uintptr_t)order & 3) || ((uintptr_t)final_score & 7) || ((uintptr_t)count & 3))
-        return fail(RDX_ERR_INVALID, "rdx_rerank_select: misaligned pointer");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_rerank_select: device out of range");
+    RDX_TRY(check_select_args("rdx_rerank_select", scores, boosts, top_k, keep_min, order, final_score, count, nullptr, device));
     HIP_TRY(hipSetDevice(device));
     hipLaunchKernelGGL(k_rerank_select, dim3(1), dim3(RERANK_MAX_N), 0, (hipStream_t)stream, scores, boosts, n, top_k, min_score,
                        keep_min, order, final_score, count);
@@ -390,6 +410,18 @@ extern "C" int rdx_rerank_select(int device, const float* scores, const double* 
 // ------------------------------------------------------------------------------------------------
 // topic boost of a question's candidates (topic_kernel.hpp): the boosts rdx_rerank_select reads
 // ------------------------------------------------------------------------------------------------
+// the alignment and device checks rdx_topic_boost and rdx_topic_boost_batch end their argument checks with (offsets: the single
+// call's int32 pair_offsets or the batch's int64 pair_off, aligned to offsets_bytes)
+static int check_topic_pointers(const char* fn, const float* table, const int32_t* topic_slots, const int32_t* tag_slots, const int32_t* pairs,
+                                const void* offsets, int offsets_bytes, const double* sims, const double* boosts, const double* best_sim,
+                                int device) {
+    if ((((uintptr_t)table | (uintptr_t)topic_slots | (uintptr_t)tag_slots | (uintptr_t)pairs) & 3) || ((uintptr_t)offsets & (offsets_bytes - 1)) ||
+        (((uintptr_t)sims | (uintptr_t)boosts | (uintptr_t)best_sim) & 7))
+        return fail(RDX_ERR_INVALID, std::string(fn) + ": misaligned pointer");
+    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, std::string(fn) + ": device out of range");
+    return RDX_OK;
+}
+
 extern "C" int rdx_topic_boost(int device, const float* table, int64_t table_rows, int dim, const int32_t* topic_slots, int n_topics,
                                const int32_t* tag_slots, int n_tags, const int32_t* pair_offsets, const int32_t* pairs, int64_t n_pairs,
                                int n, double threshold, double max_boost, double* sims, double* boosts, double* best_sim, void* stream) {
@@ -404,10 +436,7 @@ extern "C" int rdx_topic_boost(int device, const float* table, int64_t table_row
     if (!pair_offsets || !boosts || (n_pairs > 0 && !pairs)) return fail(RDX_ERR_INVALID, "rdx_topic_boost: null pointer");
     if (dots && ((table_rows > 0 && !table) || !topic_slots || !tag_slots || !sims))   // (an empty table may be NULL: no slot has an embedding)
         return fail(RDX_ERR_INVALID, "rdx_topic_boost: null pointer (table, slots or sims)");
-    if (((uintptr_t)table | (uintptr_t)topic_slots | (uintptr_t)tag_slots | (uintptr_t)pair_offsets | (uintptr_t)pairs) & 3)
-        return fail(RDX_ERR_INVALID, "rdx_topic_boost: misaligned pointer");
-    if (((uintptr_t)sims | (uintptr_t)boosts | (uintptr_t)best_sim) & 7) return fail(RDX_ERR_INVALID, "rdx_topic_boost: misaligned pointer");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_topic_boost: device out of range");
+    RDX_TRY(check_topic_pointers("rdx_topic_boost", table, topic_slots, tag_slots, pairs, pair_offsets, 4, sims, boosts, best_sim, device));
     HIP_TRY(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
     if (dots) {
@@ -428,32 +457,9 @@ extern "C" int rdx_topic_boost(int device, const float* table, int64_t table_row
 // ------------------------------------------------------------------------------------------------
 extern "C" int rdx_rerank_head_rows_f16(int device, const float* cls, int64_t n, int hidden, const void* w_dense, const void* b_dense,
                                         const void* w_out, const void* b_out, double* workspace, float* scores, void* stream) {
-    if (n < 1 || n > RERANK_BATCH_MAX_ROWS) return fail(RDX_ERR_INVALID, "rdx_rerank_head_rows_f16: n must be in [1, 2^20]");
-    if (hidden < 64 || hidden > RERANK_MAX_HIDDEN || hidden % 64)
-        return fail(RDX_ERR_INVALID, "rdx_rerank_head_rows_f16: hidden must be a multiple of 64 in [64, 4096]");
-    if (!cls || !w_dense || !b_dense || !w_out || !b_out || !workspace || !scores)
-        return fail(RDX_ERR_INVALID, "rdx_rerank_head_rows_f16: null pointer");
-    if (((uintptr_t)cls | (uintptr_t)w_dense) & 15) return fail(RDX_ERR_INVALID, "rdx_rerank_head_rows_f16: cls and w_dense must be 16-byte aligned");
-    if (((uintptr_t)b_dense | (uintptr_t)w_out | (uintptr_t)b_out) & 1 || ((uintptr_t)workspace & 7) || ((uintptr_t)scores & 3))
-        return fail(RDX_ERR_INVALID, "rdx_rerank_head_rows_f16: misaligned pointer");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_rerank_head_rows_f16: device out of range");
-    HIP_TRY(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
-    // rdx_rerank_head_f16's two kernels on a taller grid: workgroup (b, y) takes rows [64 y, 64 y + 64) whatever n is, and row r's
-    // partials lie at part[b * n + r] (size_t: 2^29 words at the limits), so a row's arithmetic is that of any shorter call
-    const int rows = (int)n;
-    const int blocks = hidden / RERANK_FEATURES;
-    const dim3 grid((unsigned)blocks, (unsigned)((rows + RERANK_ROWS_PER_BLOCK - 1) / RERANK_ROWS_PER_BLOCK));   // y <= 2^14
-    const size_t lds = (size_t)RERANK_FEATURES * hidden * sizeof(_Float16);
-    RDX_TRY(enc_dynamic_lds(device, (const void*)k_rerank_head, lds));
-    hipLaunchKernelGGL(k_rerank_head, grid, dim3(RERANK_HEAD_THREADS), lds, st, cls, rows, hidden, (const _Float16*)w_dense,
-                       (const _Float16*)b_dense, (const _Float16*)w_out, workspace);
-    HIP_TRY(hipGetLastError());
-    const int rows_per_block = RERANK_THREADS / 64;
-    hipLaunchKernelGGL(k_rerank_combine, dim3((unsigned)((rows + rows_per_block - 1) / rows_per_block)), dim3(RERANK_THREADS), 0, st,
-                       (const double*)workspace, rows, blocks, (const _Float16*)b_out, scores);
-    HIP_TRY(hipGetLastError());
-    return RDX_OK;
+    // rdx_rerank_head_f16's two kernels on a taller grid
+    return launch_rerank_head("rdx_rerank_head_rows_f16", RERANK_BATCH_MAX_ROWS, "[1, 2^20]", device, cls, n, hidden, w_dense, b_dense, w_out,
+                              b_out, workspace, scores, stream);
 }
 
 // A shape array of a batched call is read here, to check the call and size its grids, and by the kernels: it has to lie in pinned
@@ -504,11 +510,7 @@ extern "C" int rdx_topic_boost_batch(int device, const float* table, int64_t tab
     if (table_rows < 0 || table_rows > (int64_t)1 << 31) return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: table_rows must be in [0, 2^31]");
     if (n_pairs < 0) return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: n_pairs must be >= 0");
     if (!pair_off || !boosts || (n_pairs > 0 && !pairs)) return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: null pointer");
-    if (((uintptr_t)table | (uintptr_t)topic_slots | (uintptr_t)tag_slots | (uintptr_t)pairs) & 3)
-        return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: misaligned pointer");
-    if (((uintptr_t)pair_off | (uintptr_t)sims | (uintptr_t)boosts | (uintptr_t)best_sim) & 7)
-        return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: misaligned pointer");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_topic_boost_batch: device out of range");
+    RDX_TRY(check_topic_pointers(fn, table, topic_slots, tag_slots, pairs, pair_off, 8, sims, boosts, best_sim, device));
     HIP_TRY(hipSetDevice(device));
     const void *d_topic, *d_tag, *d_sim, *d_cand;
     RDX_TRY(shape_array(fn, "topic_off", topic_off, 4, &d_topic));
@@ -557,13 +559,7 @@ extern "C" int rdx_rerank_select_batch(int device, const float* scores, const do
                                        int32_t* boosted, void* stream) {
     static const char* fn = "rdx_rerank_select_batch";
     if (nq < 1 || nq > RERANK_BATCH_MAX_QUESTIONS) return fail(RDX_ERR_INVALID, "rdx_rerank_select_batch: nq must be in [1, 65535]");
-    if (top_k < 0) return fail(RDX_ERR_INVALID, "rdx_rerank_select_batch: top_k must be >= 0");
-    if (keep_min < 0) return fail(RDX_ERR_INVALID, "rdx_rerank_select_batch: keep_min must be >= 0");
-    if (!scores || !order || !final_score || !count) return fail(RDX_ERR_INVALID, "rdx_rerank_select_batch: null pointer");
-    if (((uintptr_t)scores & 3) || ((uintptr_t)boosts & 7) || ((uintptr_t)order & 3) || ((uintptr_t)final_score & 7) || ((uintptr_t)count & 3) ||
-        ((uintptr_t)boosted & 3))
-        return fail(RDX_ERR_INVALID, "rdx_rerank_select_batch: misaligned pointer");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_rerank_select_batch: device out of range");
+    RDX_TRY(check_select_args(fn, scores, boosts, top_k, keep_min, order, final_score, count, boosted, device));
     HIP_TRY(hipSetDevice(device));
     const void* d_cand;
     RDX_TRY(shape_array(fn, "cand_off", cand_off, 4, &d_cand));

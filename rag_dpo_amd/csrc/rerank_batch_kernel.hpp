@@ -4,9 +4,9 @@
 // empty and holds at most 1024 candidates. The head needs no kernel of its own: k_rerank_head and k_rerank_combine index rows
 // with size_t and take any n their grid can hold, and a row's arithmetic in them never depended on n (rdx_rerank_head_rows_f16).
 //
-// Every kernel here is the single-question kernel's arithmetic, statement for statement, behind another way of finding its
-// operands: the same fp64 summation order in the similarities, the same replay, the same rank rule. A question's outputs are
-// therefore the bits and integers of the single-question call on that question alone, whatever its neighbours are.
+// The arithmetic is shared, not repeated: topic_sim_wave, topic_replay_one and rerank_select_segment are the cores the
+// single-question kernels call; a kernel here only finds its question's operands. A question's outputs are therefore the bits
+// and integers of the single-question call on that question alone, whatever its neighbours are.
 //
 // The shape arrays (cand_off, topic_off, tag_off, sim_off) are read by the launcher on the host, which checks them and sizes the
 // grids, and by the kernels through the same words: they live in pinned host memory. A workgroup reads the handful of words of
@@ -44,26 +44,7 @@ __global__ void __launch_bounds__(TOPIC_THREADS) k_topic_sims_batch(const float*
     const int64_t pair = (int64_t)blockIdx.x * (TOPIC_THREADS / 64) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (pair >= (int64_t)T * U) return;                                  // (whole waves: pair is uniform in a wave)
-    const int64_t sa = topic_slots[t0 + pair / U], sb = tag_slots[u0 + pair % U];
-    double s = 0.0;
-    if (sa >= 0 && sa < rows && sb >= 0 && sb < rows) {                  // (uniform in the wave as well)
-        const float* a = table + sa * dim;
-        const float* b = table + sb * dim;
-        for (int i0 = lane; i0 < dim; i0 += 64 * TOPIC_KU) {             // k_topic_sims' loop: the same order of additions
-            float av[TOPIC_KU], bv[TOPIC_KU];
-#pragma unroll
-            for (int k = 0; k < TOPIC_KU; ++k) {
-                const int i = i0 + 64 * k;
-                av[k] = i < dim ? a[i] : 0.0f;
-                bv[k] = i < dim ? b[i] : 0.0f;
-            }
-#pragma unroll
-            for (int k = 0; k < TOPIC_KU; ++k)
-                if (i0 + 64 * k < dim) s += (double)av[k] * (double)bv[k];
-        }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-    }
+    const double s = topic_sim_wave(table, rows, dim, topic_slots[t0 + pair / U], tag_slots[u0 + pair % U], lane);
     if (lane == 0) sims[sim_off[q] + pair] = s;
 }
 
@@ -80,67 +61,22 @@ __global__ void __launch_bounds__(TOPIC_THREADS) k_topic_replay_batch(const doub
     if (local >= n) return;
     int T = topic_off[q + 1] - topic_off[q], U = tag_off[q + 1] - tag_off[q];
     if (T <= 0 || U <= 0) T = U = 0;
-    const double* qs = sims + sim_off[q];
     const int64_t c = (int64_t)c0 + local;
     const int64_t lo = max(pair_off[c], (int64_t)0), hi = min(pair_off[c + 1], n_pairs);
-    double best = 0.0;
-    int prev = -1;
-    for (int64_t p = lo; p < hi; ++p) {
-        const int32_t w = pairs[p];
-        const int t = topic_pair_topic(w), u = topic_pair_tag(w);
-        if (t != prev && prev >= 0 && best >= 1.0) break;
-        prev = t;
-        if (topic_pair_exact(w)) {
-            best = 1.0;
-            break;
-        }
-        const double sim = (t < T && u < U) ? qs[(int64_t)t * U + u] : 0.0;
-        if (sim > best) best = sim;
-    }
-    double boost = 0.0;
-    if (!(best < threshold)) boost = max_boost * (best - threshold) / (1.0 - threshold);
-    boosts[c] = boost;
-    if (best_sim) best_sim[c] = best;
+    topic_replay_one(sims + sim_off[q], T, U, pairs, lo, hi, threshold, max_boost, boosts + c, best_sim ? best_sim + c : nullptr);
 }
 
-// K_B3: k_rerank_select for the segment of question blockIdx.x, W >= its length. No thread leaves before the barriers.
+// K_B3: k_rerank_select for the segment of question blockIdx.x, W >= its length. No thread leaves before the core's barriers.
 template <int W>
 __global__ void __launch_bounds__(W) k_rerank_select_batch(const float* __restrict__ scores, const double* __restrict__ boosts,
                                                           const int32_t* __restrict__ cand_off, int top_k, double min_score, int keep_min,
                                                           int32_t* __restrict__ order, double* __restrict__ final_out,
                                                           int32_t* __restrict__ count, int32_t* __restrict__ boosted) {
-    __shared__ double fin[W];
     const int seg = blockIdx.x;
     const int c0 = cand_off[seg];
     const int n = min(cand_off[seg + 1] - c0, W);                        // (the launcher refused a longer segment)
-    const int p = threadIdx.x;
-    double f = 0.0;
-    bool lifted = false;
-    if (p < n) {
-        f = (double)scores[c0 + p];
-        if (boosts) {
-            const double b = boosts[c0 + p];
-            if (b > 0.0) {
-                f += b;
-                lifted = true;
-            }
-        }
-        fin[p] = f;
-        final_out[c0 + p] = f;
-    }
-    const int passing = __syncthreads_count(p < n && f >= min_score);   // (also the barrier behind the fin[] stores)
-    const int lifts = boosted ? __syncthreads_count(lifted) : 0;         // (boosted is uniform: every thread takes the same side)
-    if (p < n) {
-        int rank = 0;
-        for (int q = 0; q < n; ++q) rank += (q != p && rerank_before(fin[q], f, q < p)) ? 1 : 0;
-        order[c0 + rank] = p;
-    }
-    if (p == 0) {
-        int c = min(top_k, passing);
-        if (c < keep_min && n >= keep_min) c = keep_min;
-        count[seg] = n > 0 ? c : 0;
-        if (boosted) boosted[seg] = lifts;
-    }
+    rerank_select_segment<W>(scores + c0, boosts ? boosts + c0 : nullptr, n, top_k, min_score, keep_min, order + c0, final_out + c0,
+                             count + seg, boosted ? boosted + seg : nullptr);
 }
 
 }  // namespace rdx

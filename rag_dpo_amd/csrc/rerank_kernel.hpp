@@ -12,7 +12,7 @@
 // [H / 8][n]; K_R2 (one wave per row) adds the H / 8 partials of a row in a fixed order, then b_o, and applies the sigmoid in fp64,
 // rounded once to fp32. No atomics anywhere: the same inputs give the same bits on every call, on any stream.
 //
-// Selection (K_R3, one workgroup, n <= 1024). final[p] = (double)score[p] (+ boost[p] when boost[p] > 0: one fp64 add, as
+// Selection (rerank_select_segment: K_R3, one workgroup, n <= 1024). final[p] = (double)score[p] (+ boost[p] when boost[p] > 0: one fp64 add, as
 // `float(np.float32) + boost` in the reference); rank[p] = #{q : final[q] > final[p] or (final[q] == final[p] and q < p)} —
 // Python's stable sort(reverse=True); NaN finals rank after every number (Python's sort leaves them where the comparisons
 // happen to put them: undefined there). order[rank[p]] = p. count = min(top_k, #{final >= min_score}), raised to keep_min
@@ -131,24 +131,31 @@ __device__ __forceinline__ bool rerank_before(double a, double b, bool a_first) 
     return a > b || (a == b && a_first);
 }
 
-// K_R3: one workgroup of 1024 threads, thread p = candidate p
-__global__ void __launch_bounds__(RERANK_MAX_N) k_rerank_select(const float* __restrict__ scores, const double* __restrict__ boosts,
-                                                               int n, int top_k, double min_score, int keep_min,
-                                                               int32_t* __restrict__ order, double* __restrict__ final_out,
-                                                               int32_t* __restrict__ count) {
-    __shared__ double fin[RERANK_MAX_N];
+// The selection of one segment of n <= W candidates by a workgroup of W threads, thread p = candidate p (K_R3's arithmetic above).
+// The pointers are already advanced to the segment; order holds indices local to it. boosted (nullptr, or where to count the
+// candidates a boost lifted) is uniform in the workgroup. Every thread of the workgroup must call this: it holds barriers.
+template <int W>
+__device__ __forceinline__ void rerank_select_segment(const float* __restrict__ scores, const double* __restrict__ boosts, int n, int top_k,
+                                                      double min_score, int keep_min, int32_t* __restrict__ order,
+                                                      double* __restrict__ final_out, int32_t* count, int32_t* boosted) {
+    __shared__ double fin[W];
     const int p = threadIdx.x;
     double f = 0.0;
+    bool lifted = false;
     if (p < n) {
         f = (double)scores[p];
         if (boosts) {
             const double b = boosts[p];
-            if (b > 0.0) f += b;
+            if (b > 0.0) {
+                f += b;
+                lifted = true;
+            }
         }
         fin[p] = f;
         final_out[p] = f;
     }
     const int passing = __syncthreads_count(p < n && f >= min_score);   // (also the barrier behind the fin[] stores)
+    const int lifts = boosted ? __syncthreads_count(lifted) : 0;         // (boosted is uniform: every thread takes the same side)
     if (p < n) {
         int rank = 0;
         for (int q = 0; q < n; ++q) rank += (q != p && rerank_before(fin[q], f, q < p)) ? 1 : 0;
@@ -157,8 +164,17 @@ __global__ void __launch_bounds__(RERANK_MAX_N) k_rerank_select(const float* __r
     if (p == 0) {
         int c = min(top_k, passing);
         if (c < keep_min && n >= keep_min) c = keep_min;
-        *count = c;
+        *count = c;                                                      // (0 for an empty segment: top_k and keep_min are >= 0, the launchers see to it)
+        if (boosted) *boosted = lifts;
     }
+}
+
+// K_R3: one workgroup of 1024 threads over the call's n candidates
+__global__ void __launch_bounds__(RERANK_MAX_N) k_rerank_select(const float* __restrict__ scores, const double* __restrict__ boosts,
+                                                               int n, int top_k, double min_score, int keep_min,
+                                                               int32_t* __restrict__ order, double* __restrict__ final_out,
+                                                               int32_t* __restrict__ count) {
+    rerank_select_segment<RERANK_MAX_N>(scores, boosts, n, top_k, min_score, keep_min, order, final_out, count, nullptr);
 }
 
 }  // namespace rdx

@@ -66,6 +66,11 @@ class RankedChunk:
     metadata: dict
 
 
+def _ranked(chunk, score, original_rank: int) -> RankedChunk:
+    return RankedChunk(chunk_id=chunk.chunk_id, text=chunk.text, document_path=chunk.document_path, rerank_score=score,
+                       original_rank=original_rank, metadata=chunk.metadata)
+
+
 def select_host(scores, boosts, top_k: int, min_score: float, keep_min: int = KEEP_MIN):
     """The selection of reranker.py:162-206 restated (what rdx_rerank_select computes):
     -> (order: every candidate, final descending, ties in input order; final fp64 per candidate in input order; count)"""
@@ -161,55 +166,51 @@ class _CrossEncoderModel:
             out[lo:hi] = self.model.roberta(**feed).last_hidden_state[:, 0].to(torch.float32)
         return out
 
-    def head_device(self, cls: torch.Tensor) -> torch.Tensor:
-        """rdx_rerank_head_f16 on fp32 CLS rows -> fp32 sigmoid scores on the device"""
+    def _head(self, cls: torch.Tensor, head_fn: str) -> torch.Tensor:
+        """the entry point head_fn (rdx_rerank_head_f16 or rdx_rerank_head_rows_f16) on fp32 CLS rows -> fp32 sigmoid scores on the device"""
         from . import _lib as L
         n, H = int(cls.shape[0]), self.hidden
         cls = cls.contiguous()
         ws = torch.empty(((H // L.RERANK_FEATURES) * n,), dtype=torch.float64, device=cls.device)
         scores = torch.empty((n,), dtype=torch.float32, device=cls.device)
         st = torch.cuda.current_stream(cls.device).cuda_stream
-        L.check(self._lib.rdx_rerank_head_f16(cls.device.index or 0, cls.data_ptr(), n, H, self.w_d.data_ptr(), self.b_d.data_ptr(),
-                                              self.w_o.data_ptr(), self.b_o.data_ptr(), ws.data_ptr(), scores.data_ptr(), st))
+        L.check(getattr(self._lib, head_fn)(cls.device.index or 0, cls.data_ptr(), n, H, self.w_d.data_ptr(), self.b_d.data_ptr(), self.w_o.data_ptr(),
+                        self.b_o.data_ptr(), ws.data_ptr(), scores.data_ptr(), st))
         return scores
 
+    def head_device(self, cls: torch.Tensor) -> torch.Tensor:
+        """rdx_rerank_head_f16 on fp32 CLS rows -> fp32 sigmoid scores on the device"""
+        return self._head(cls, "rdx_rerank_head_f16")
+
     @torch.no_grad()
-    def predict_device(self, pairs, batch_size: int = 32, show_progress_bar: bool = False) -> torch.Tensor:
+    def _predict_on_device(self, pairs, batch_size: int, head_fn: str, what: str, refusal) -> torch.Tensor:
+        """the backbone's <s> rows, then head_fn on them, with the three events of the stats around the two steps. what: the caller's
+        name; refusal: None, or why it does not take this many pairs"""
         if not self.on_gpu:
-            raise RuntimeError("predict_device needs the model on a GPU")
-        if len(pairs) > MAX_GPU_CANDIDATES:
-            raise ValueError(f"the GPU reranker scores at most {MAX_GPU_CANDIDATES} candidates per call, got {len(pairs)}")
+            raise RuntimeError(f"{what} needs the model on a GPU")
+        if refusal:
+            raise ValueError(refusal)
         e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
         e0.record()
         cls = self._cls_rows(pairs, batch_size)
         e1.record()
-        scores = self.head_device(cls)
+        scores = self._head(cls, head_fn)
         e2.record()
         self.stats["events"] = (e0, e1, e2)
         return scores
 
-    @torch.no_grad()
+    def predict_device(self, pairs, batch_size: int = 32, show_progress_bar: bool = False) -> torch.Tensor:
+        n = len(pairs)
+        return self._predict_on_device(pairs, batch_size, "rdx_rerank_head_f16", "predict_device",
+                                       n > MAX_GPU_CANDIDATES and f"the GPU reranker scores at most {MAX_GPU_CANDIDATES} candidates per call, got {n}")
+
     def predict_device_batch(self, pairs, batch_size: int = 32) -> torch.Tensor:
         """predict_device for the pairs of several questions (any number up to rdx_rerank_head_rows_f16's 2^20): _cls_rows sorts by
         length and groups across questions, the head runs once. A row's score has the bits rdx_rerank_head_f16 gives that <s> row."""
         from . import _lib as L
-        if not self.on_gpu:
-            raise RuntimeError("predict_device_batch needs the model on a GPU")
-        n, H = len(pairs), self.hidden
-        if not 1 <= n <= L.RERANK_BATCH_MAX_ROWS:
-            raise ValueError(f"the GPU reranker scores 1 to {L.RERANK_BATCH_MAX_ROWS} pairs per call, got {n}")
-        e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-        e0.record()
-        cls = self._cls_rows(pairs, batch_size).contiguous()
-        e1.record()
-        ws = torch.empty(((H // L.RERANK_FEATURES) * n,), dtype=torch.float64, device=cls.device)
-        scores = torch.empty((n,), dtype=torch.float32, device=cls.device)
-        L.check(self._lib.rdx_rerank_head_rows_f16(cls.device.index or 0, cls.data_ptr(), n, H, self.w_d.data_ptr(), self.b_d.data_ptr(),
-                                                   self.w_o.data_ptr(), self.b_o.data_ptr(), ws.data_ptr(), scores.data_ptr(),
-                                                   torch.cuda.current_stream(cls.device).cuda_stream))
-        e2.record()
-        self.stats["events"] = (e0, e1, e2)
-        return scores
+        n = len(pairs)
+        return self._predict_on_device(pairs, batch_size, "rdx_rerank_head_rows_f16", "predict_device_batch",
+                                       not 1 <= n <= L.RERANK_BATCH_MAX_ROWS and f"the GPU reranker scores 1 to {L.RERANK_BATCH_MAX_ROWS} pairs per call, got {n}")
 
     @torch.no_grad()
     def predict(self, pairs, batch_size: int = 32, show_progress_bar: bool = False) -> np.ndarray:
@@ -323,13 +324,7 @@ class CrossEncoderReranker:
         if not chunks:
             return []
         self._load_model()
-        pairs = []
-        for chunk in chunks:
-            text = chunk.text
-            heading = chunk.metadata.get("heading", "")
-            if heading:
-                text = f"{heading}\n{text}"
-            pairs.append((query, text[:self.max_length * 4]))
+        pairs = self._pairs(query, chunks)
         stats = {"pairs": len(pairs), "tokens": None, "ms_forward": None, "ms_head_select": None}
         self.last_rerank_stats = stats
         t0 = time.perf_counter()
@@ -338,8 +333,7 @@ class CrossEncoderReranker:
         except Exception as e:                                   # reranker.py:153-160
             logger.error(f"reranking failed: {e}")
             stats["path"] = "fallback"
-            return [RankedChunk(chunk_id=c.chunk_id, text=c.text, document_path=c.document_path, rerank_score=c.similarity_score,
-                                original_rank=i, metadata=c.metadata) for i, c in enumerate(chunks[:top_k])]
+            return [_ranked(c, c.similarity_score, i) for i, c in enumerate(chunks[:top_k])]
         stats["path"] = path
         n = min(len(chunks), len(scores))                        # (zip(chunks, scores), reranker.py:166)
         boosts = None
@@ -370,8 +364,7 @@ class CrossEncoderReranker:
             elif ev is not None:
                 stats["ms_forward"] = ev[0].elapsed_time(ev[1])
         stats.pop("events", None)
-        return [RankedChunk(chunk_id=chunks[i].chunk_id, text=chunks[i].text, document_path=chunks[i].document_path,
-                            rerank_score=final[i], original_rank=i, metadata=chunks[i].metadata) for i in order[:count]]
+        return [_ranked(chunks[i], final[i], i) for i in order[:count]]
 
     def _pairs(self, query: str, chunks) -> list:
         """the (question, text) pairs of rerank(): heading prefix, then the max_length * 4 character cut (reranker.py:131-144)"""
@@ -502,9 +495,7 @@ class CrossEncoderReranker:
             lo, chunks = cand_off[q], chunks_lists[i]
             if counted[q] and boosted[q]:
                 logger.info(f"topic boost applied to {int(boosted[q])}/{len(chunks)} chunks")
-            ranked.append([RankedChunk(chunk_id=chunks[p].chunk_id, text=chunks[p].text, document_path=chunks[p].document_path,
-                                       rerank_score=float(final[lo + p]), original_rank=int(p), metadata=chunks[p].metadata)
-                           for p in order[lo:lo + int(count[q])].tolist()])
+            ranked.append([_ranked(chunks[p], float(final[lo + p]), p) for p in order[lo:lo + int(count[q])].tolist()])
         add = lambda k, v: total.__setitem__(k, v if total[k] is None else total[k] + v)   # noqa: E731
         total["questions"] += nq
         total["pairs"] += n_total

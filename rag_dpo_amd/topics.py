@@ -134,6 +134,34 @@ def pack_plans(plans: Sequence[_Plan], slot_of) -> dict:
             "pair_off": np.asarray(pair_off, dtype=np.int64), "pairs": np.asarray(pairs, dtype=np.int32)}
 
 
+class _PinnedRing:
+    """Four pinned int32 host buffers used in turn. A slot is [buffer, event]: the event stands behind the last device work that
+    reads the buffer and is waited on before the buffer is written again; a buffer too small for a call is replaced by one of
+    twice the call's words."""
+    SLOTS = 4
+
+    def __init__(self, min_words: int):
+        self.min_words = min_words
+        self.slots: list = []
+        self.next = 0
+
+    def put(self, words: np.ndarray):
+        """int32 host words -> (the pinned tensor holding them, its slot); the caller records slot[1] behind what reads the tensor"""
+        if len(self.slots) < self.SLOTS:
+            self.slots.append([torch.empty((max(self.min_words, 2 * len(words)),), dtype=torch.int32).pin_memory(), None])
+            slot = self.slots[-1]
+        else:
+            slot = self.slots[self.next]
+            self.next = (self.next + 1) % len(self.slots)
+            if slot[1] is not None:
+                slot[1].synchronize()
+            if slot[0].numel() < len(words):
+                slot[0] = torch.empty((2 * len(words),), dtype=torch.int32).pin_memory()
+        buf = slot[0][:len(words)]
+        buf.numpy()[:] = words
+        return buf, slot
+
+
 class TopicMatcher:
     """Semantic matching of question topics and chunk tags; one instance serves every session, as the provider does."""
 
@@ -155,10 +183,8 @@ class TopicMatcher:
         self._table = None           # fp32 [capacity][dim]: a device tensor on a GPU, a numpy array on the CPU
         self._dim: Optional[int] = None
         self._lib = None
-        self._staging: list = []     # pinned int32 buffers of the plans' uploads, each with the event of the copy that read it last
-        self._staging_next = 0
-        self._shapes: list = []      # pinned int32 buffers of the batched calls' shape arrays, each with the event behind the kernels that read it
-        self._shapes_next = 0
+        self._staging = _PinnedRing(4096)   # the plans' uploads: a slot's event stands behind the copy that read it
+        self._shapes = _PinnedRing(1024)    # the batched calls' shape arrays: a slot's event stands behind the kernels that read it
         self.stats = {"embed_calls": 0, "embedded": 0, "device_calls": 0, "host_calls": 0}
         if self.on_gpu:
             from . import _lib
@@ -391,40 +417,25 @@ class TopicMatcher:
         return out, bests
 
     def _upload(self, words: np.ndarray) -> torch.Tensor:
-        """int32 host words -> device through a ring of pinned buffers (a pageable copy would park the host behind the stream's work)"""
-        if len(self._staging) < 4:
-            self._staging.append([torch.empty((max(4096, 2 * len(words)),), dtype=torch.int32).pin_memory(), None])
-            slot = self._staging[-1]
-        else:
-            slot = self._staging[self._staging_next]
-            self._staging_next = (self._staging_next + 1) % len(self._staging)
-            if slot[1] is not None:
-                slot[1].synchronize()
-            if slot[0].numel() < len(words):
-                slot[0] = torch.empty((2 * len(words),), dtype=torch.int32).pin_memory()
-        buf = slot[0][:len(words)]
-        buf.numpy()[:] = words
+        """int32 host words -> device through the ring of pinned buffers (a pageable copy would park the host behind the stream's work)"""
+        buf, slot = self._staging.put(words)
         dev = buf.to(self.device, non_blocking=True)
-        slot[1] = torch.cuda.Event()
-        slot[1].record(torch.cuda.current_stream(self.device))
+        slot[1] = self._event()
         return dev
 
-    def _pin_shapes(self, words: np.ndarray):
-        """int32 host words -> a pinned buffer that stays as it is until the kernels reading it have run: the caller records
-        slot[1] behind its launch. -> (the pinned tensor, slot)"""
-        if len(self._shapes) < 4:
-            self._shapes.append([torch.empty((max(1024, 2 * len(words)),), dtype=torch.int32).pin_memory(), None])
-            slot = self._shapes[-1]
-        else:
-            slot = self._shapes[self._shapes_next]
-            self._shapes_next = (self._shapes_next + 1) % len(self._shapes)
-            if slot[1] is not None:
-                slot[1].synchronize()
-            if slot[0].numel() < len(words):
-                slot[0] = torch.empty((2 * len(words),), dtype=torch.int32).pin_memory()
-        buf = slot[0][:len(words)]
-        buf.numpy()[:] = words
-        return buf, slot
+    def _event(self):
+        """an event recorded on the current stream of the matcher's device"""
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        return ev
+
+    def _call_buffers(self, n_sims: int, n: int, want_best: bool):
+        """what both device calls are given besides the plan: (table pointer or None, rows, dim, sims, boosts, best or None)"""
+        table = self._table.data_ptr() if self._table is not None else None
+        sims = torch.empty((max(1, n_sims),), dtype=torch.float64, device=self.device)
+        boosts = torch.empty((n,), dtype=torch.float64, device=self.device)
+        best = torch.empty((n,), dtype=torch.float64, device=self.device) if want_best else None
+        return table, len(self._slots), self._dim or 1, sims, boosts, best
 
     def _device_batch(self, plans: Sequence[_Plan], threshold: float, want_best: bool = False):
         """rdx_topic_boost_batch on plans that fit the kernel -> fp64 [sum of their candidates] (and the best similarities)"""
@@ -439,7 +450,7 @@ class TopicMatcher:
             shape = np.zeros((3 * (nq + 1) + pad + 2 * (nq + 1),), dtype=np.int32)
             shape[:nq + 1], shape[nq + 1:2 * (nq + 1)], shape[2 * (nq + 1):3 * (nq + 1)] = p["topic_off"], p["tag_off"], p["cand_off"]
             shape[3 * (nq + 1) + pad:] = p["sim_off"].view(np.int32)
-            pinned, slot = self._pin_shapes(shape)
+            pinned, slot = self._shapes.put(shape)
             # everything else in one upload: the slots, then pair_off (int64, 8-byte aligned), then the pair words
             at_off = T + U + (T + U) % 2
             words = np.zeros((at_off + 2 * (n + 1) + P,), dtype=np.int32)
@@ -447,19 +458,15 @@ class TopicMatcher:
             words[at_off:at_off + 2 * (n + 1)] = p["pair_off"].view(np.int32)
             words[at_off + 2 * (n + 1):] = p["pairs"]
             d = self._upload(words)
-            table, rows, dim = self._table, len(self._slots), self._dim or 1
-            sims = torch.empty((max(1, int(p["sim_off"][-1])),), dtype=torch.float64, device=self.device)
-            boosts = torch.empty((n,), dtype=torch.float64, device=self.device)
-            best = torch.empty((n,), dtype=torch.float64, device=self.device) if want_best else None
+            table, rows, dim, sims, boosts, best = self._call_buffers(int(p["sim_off"][-1]), n, want_best)
             base, sbase = d.data_ptr(), pinned.data_ptr()
-            stream = torch.cuda.current_stream(self.device)
-            L.check(self._lib.rdx_topic_boost_batch(self.device.index, table.data_ptr() if table is not None else None, rows, dim, nq,
+            L.check(self._lib.rdx_topic_boost_batch(self.device.index, table, rows, dim, nq,
                                                     sbase, base, sbase + 4 * (nq + 1), base + 4 * T, sbase + 4 * (3 * (nq + 1) + pad),
                                                     sbase + 8 * (nq + 1), base + 4 * at_off, base + 4 * (at_off + 2 * (n + 1)), P,
                                                     float(threshold), MAX_BOOST, sims.data_ptr(), boosts.data_ptr(),
-                                                    best.data_ptr() if best is not None else None, stream.cuda_stream))
-            slot[1] = torch.cuda.Event()
-            slot[1].record(stream)
+                                                    best.data_ptr() if best is not None else None,
+                                                    torch.cuda.current_stream(self.device).cuda_stream))
+            slot[1] = self._event()
         return (boosts, best) if want_best else boosts
 
     def _device(self, plan: _Plan, threshold: float, want_best: bool = False):
@@ -474,12 +481,9 @@ class TopicMatcher:
             words[T + U:T + U + n + 1] = plan.offsets
             words[T + U + n + 1:] = [L.topic_pair(t, u, e) for t, u, e in plan.pairs]
             d = self._upload(words)
-            table, rows, dim = self._table, len(self._slots), self._dim or 1
-            sims = torch.empty((max(1, T * U),), dtype=torch.float64, device=self.device)
-            boosts = torch.empty((n,), dtype=torch.float64, device=self.device)
-            best = torch.empty((n,), dtype=torch.float64, device=self.device) if want_best else None
+            table, rows, dim, sims, boosts, best = self._call_buffers(T * U, n, want_best)
             base = d.data_ptr()
-            L.check(self._lib.rdx_topic_boost(self.device.index, table.data_ptr() if table is not None else None, rows, dim,
+            L.check(self._lib.rdx_topic_boost(self.device.index, table, rows, dim,
                                               base, T, base + 4 * T, U, base + 4 * (T + U), base + 4 * (T + U + n + 1), P, n,
                                               float(threshold), MAX_BOOST, sims.data_ptr(), boosts.data_ptr(),
                                               best.data_ptr() if best is not None else None,
