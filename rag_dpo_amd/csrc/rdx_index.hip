@@ -80,7 +80,7 @@ struct rdx_index {
     // int8 coarse pass: corpus copy [cap][dim_pad] in corpus_off8 order + s_b per 32-row block + the largest eps_b (built by the first
     // search that takes the path, rows [0, i8_valid) current; not persisted) and the per-search query copy, scales, bounds, thresholds
     DevBuf c8, sblk, eps8, qshadow8, tq8, eq8, nq8, thr8, taus8, twoe8;
-    DevBuf spill, spill_q;   // k_refine_spill: [nq_pad][spill_cap] hit lists, [nq_pad] queue of the queries that use them (first spilling plan)
+    DevBuf spill;            // k_refine<true>: [nq_pad][spill_cap] hit lists of the queries that outgrow the LDS list (first spilling plan)
     int64_t i8_valid = 0;
     // end-of-search mailbox in pinned host memory (k_finish writes it over PCIe; the host spins on its sequence number)
     Mailbox* mbox = nullptr;          // host address
@@ -414,22 +414,17 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
         RDX_TRY(launch_scan_bn<EPI_EMIT>(h, p.bn, p.res, p.fused, sp, p.grid, st));
     }
     mark(h, p, st, 4);
+    // ONE launch, the search's last kernel on this path: a query with more hits than the LDS list holds goes on in its own block,
+    // on its row of the spill buffer (plans that spill run the instantiation that holds both routes)
     const size_t lds = (size_t)p.list_cap * 8;
-    RDX_TRY(ensure_dynamic_lds(h, (const void*)k_refine, lds));
-    hipLaunchKernelGGL(k_refine, dim3((int)p.nq), dim3(1024), lds, st, h->cand.as<uint2>(), h->cntw.as<uint32_t>(), p.n_streams, p.capw,
+    const auto refine = p.spill ? k_refine<true> : k_refine<false>;
+    RDX_TRY(ensure_dynamic_lds(h, (const void*)refine, lds));
+    hipLaunchKernelGGL(refine, dim3((int)p.nq), dim3(1024), lds, st, h->cand.as<uint2>(), h->cntw.as<uint32_t>(), p.n_streams, p.capw,
                        p.list_cap, p.k, h->two_e(), p.i8 ? h->twoe8.as<float>() : nullptr, h->qhat.as<float>(), h->mv(), h->dim, h->row_base,
                        h->row_map, io.score, io.row, io.count, h->exact_list.as<int32_t>(), h->ctr.as<RefineCounters>(),
                        p.i8 ? h->taus8.as<float>() : h->tau.as<float>(), p.i8 ? 1.0f : sp.inv_scale2, p.pilot, p.spill_cap,
-                       h->spill_q.as<int32_t>(), p.spill ? FinishArgs{} : fin);
+                       p.spill ? h->spill.as<uint2>() : nullptr, fin);
     HIP_TRY(hipGetLastError());
-    if (p.spill) {   // the search's last kernel when the plan spills: it ends the search whether or not a query was queued
-        hipLaunchKernelGGL(k_refine_spill, dim3((int)p.nq), dim3(1024), 0, st, h->spill.as<uint2>(), p.spill_cap, h->spill_q.as<int32_t>(),
-                           h->cand.as<uint2>(), h->cntw.as<uint32_t>(), p.n_streams, p.capw, p.k, h->two_e(),
-                           p.i8 ? h->twoe8.as<float>() : nullptr, h->qhat.as<float>(), h->mv(), h->dim, h->row_base, h->row_map, io.score, io.row,
-                           io.count, h->exact_list.as<int32_t>(), h->ctr.as<RefineCounters>(),
-                           p.i8 ? h->taus8.as<float>() : h->tau.as<float>(), p.i8 ? 1.0f : sp.inv_scale2, p.pilot, fin);
-        HIP_TRY(hipGetLastError());
-    }
     mark(h, p, st, 5);
     return RDX_OK;
 }
@@ -480,7 +475,6 @@ static int enqueue_search(rdx_index* h, const SearchPlan& p, const SearchIO& io,
         if (p.stamps) RDX_TRY(h->wgt.ensure((size_t)p.grid * 16));
         if (p.spill) {
             RDX_TRY(h->spill.ensure((size_t)p.nq_pad * p.spill_cap * 8));
-            RDX_TRY(h->spill_q.ensure((size_t)p.nq_pad * 4));
         }
     }
     if (!h->ctr_ready) {   // zeroed once; afterwards the k_finish of every search leaves it zeroed for the next one
@@ -814,7 +808,7 @@ extern "C" int rdx_index_destroy(rdx_index* h) {
     free_master(h->master, h->raw16, h->den);
     if (h->shadow) (void)hipFree(h->shadow);
     if (h->row_map) (void)hipFree(h->row_map);
-    for (DevBuf* b : {&h->staging, &h->qraw, &h->qhat, &h->qshadow, &h->tau, &h->cntw, &h->cand, &h->setmax, &h->exact_list, &h->spill, &h->spill_q,
+    for (DevBuf* b : {&h->staging, &h->qraw, &h->qhat, &h->qshadow, &h->tau, &h->cntw, &h->cand, &h->setmax, &h->exact_list, &h->spill,
                       &h->iota, &h->dense, &h->ctr, &h->bad, &h->o_score, &h->o_row, &h->o_count, &h->mask, &h->ids,
                       &h->r_list, &h->r_q, &h->r_s, &h->r_r, &h->r_c, &h->c8, &h->sblk, &h->eps8, &h->qshadow8, &h->tq8,
                       &h->eq8, &h->nq8, &h->thr8, &h->taus8, &h->twoe8})

@@ -14,7 +14,7 @@ constexpr int REFINE_PMAX = 1024;    // most candidates re-scored exactly per qu
 constexpr int REFINE_LIST = 7168;    // most scan hits gathered per query (56 KiB of LDS: with the 22 KiB of static LDS TWO blocks fit a CU's 160 KiB —
                                      // at B = 1024 the kernel runs in two rounds instead of four); more -> second pass / exact full scan
 constexpr int REFINE_STREAMS = 512;  // most (query, stream) segments
-constexpr int SPILL_CAP = 40960;     // most hits of a query whose list lives in HBM instead (k_refine_spill; plan_search SearchPlan::spill): 2.4x the
+constexpr int SPILL_CAP = 40960;     // most hits of a query whose list lives in HBM instead (k_refine<true>; plan_search SearchPlan::spill): 2.4x the
                                      // longest list seen at c4 with the thinnest sample (17 264 hits, every 64th block; 13 358 at the default's
                                      // every 32nd; DESIGN.md §5 "Spill list"), 320 MB for 1 024 queries; more -> second pass
 

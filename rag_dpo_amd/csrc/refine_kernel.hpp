@@ -16,7 +16,7 @@ struct RefineCounters {   // one per index, zeroed before every search
     // scoring kernel started (kept as max(~clock): zero = unset) and when the last block of its select kernel ended (100 MHz ticks)
     unsigned long long t_first_inv, t_last;
     int done;             // blocks of the search's last kernel that have finished (the last one runs the end-of-search work)
-    int n_spill;          // queries k_refine queued for k_refine_spill (more hits than the LDS list holds)
+    int n_spill;          // queries k_refine answered from its spill list in HBM (more hits than the LDS list holds)
     int max_hits;         // most hits of one query (developer: RDX_DEBUG_HITS)
     int pad1;
 };
@@ -136,7 +136,7 @@ __device__ __forceinline__ void finish_if_last(const FinishArgs& f) {
 //   is re-scored after them: a hit outside S1 and S2 has exact <= coarse + E_q < X1 <= X, strictly below the k-th score.
 #ifdef RDX_REFINE_STAMPS   // developer build (tools/refine_stamps.py): where k_refine spends its time (block 0's phases, 100 MHz wall clock)
 __device__ unsigned long long g_refine_stamps[16];
-#define RDX_RSTAMP(i) do { __syncthreads(); if (!SPILL && blockIdx.x == 0 && threadIdx.x == 0) g_refine_stamps[i] = wall_clock64(); } while (0)   // (k_refine only)
+#define RDX_RSTAMP(i) do { __syncthreads(); if (blockIdx.x == 0 && threadIdx.x == 0) g_refine_stamps[i] = wall_clock64(); } while (0)
 #else
 #define RDX_RSTAMP(i) do { } while (0)
 #endif
@@ -148,77 +148,41 @@ __device__ __forceinline__ float sub_down(float a, float b) {
     return d;
 }
 
-// The list of a query's hits lives in LDS (SPILL = false: k_refine, at most list_cap <= REFINE_LIST entries) or in the query's
-// row of the spill buffer in HBM (SPILL = true: k_refine_spill, at most spill_cap entries). k_refine queues a query with more hits
-// than its list holds in spill_q (spill_cap > 0, no segment overflowed) and k_refine_spill, launched behind it, answers it: the
-// same code, so which rows are re-scored does not depend on where the list lives. The hits were counted by k_refine.
+// The static LDS of a k_refine block. ONE object per kernel, handed to refine_list by reference: the kernel of a spilling plan holds
+// both instantiations of refine_list, and arrays declared inside the template would be laid out once for each (22 KiB twice — with
+// the 56 KiB list, the second block of a CU would no longer fit).
+struct RefineLds {
+    __attribute__((aligned(16))) uint32_t hist[HIST_WORDS];
+    int64_t s_r[REFINE_PMAX];
+    float s_s[REFINE_PMAX];
+    uint32_t seg_off[REFINE_STREAMS + 1];
+    uint32_t bc[4];
+    int wtot[16];
+    int n_p, overflow;
+};
+
+// A query's m > 0 hits, counted and prefixed by refine_block (L.seg_off), are gathered into `list` and answered. The list lives in
+// LDS (SPILL = false: at most list_cap <= REFINE_LIST entries) or in the query's row of the spill buffer in HBM (SPILL = true: at
+// most spill_cap entries, L2-resident while the block works on it): the same statements, so which rows are re-scored does not
+// depend on where the list lives.
 template <bool SPILL>
-__device__ __forceinline__ void refine_query(const int q, uint2* __restrict__ spill, uint32_t spill_cap, int32_t* __restrict__ spill_q,
-                                                const uint2* __restrict__ cand, const uint32_t* __restrict__ cntw,
-                                                int n_streams, uint32_t capw, uint32_t list_cap, int k, float two_e,
-                                                const float* __restrict__ two_e_q, const float* __restrict__ qhat, MasterView master, int dim,
-                                                int64_t row_base, const int64_t* __restrict__ row_map,
-                                                float* __restrict__ out_score, int64_t* __restrict__ out_row,
-                                                int32_t* __restrict__ out_count, int32_t* __restrict__ exact_list,
-                                                RefineCounters* __restrict__ ctr, const float* __restrict__ tau, float inv_scale2,
-                                                int pilot) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint2* list = SPILL ? spill + (int64_t)q * spill_cap : reinterpret_cast<uint2*>(smem);   // [spill_cap] : [REFINE_LIST]
-    __shared__ __attribute__((aligned(16))) uint32_t hist[HIST_WORDS];
-    __shared__ uint32_t bc[4];
-    __shared__ uint32_t seg_off[REFINE_STREAMS + 1];
-    __shared__ float s_s[REFINE_PMAX];
-    __shared__ int64_t s_r[REFINE_PMAX];
-    __shared__ int n_p, overflow;
+__device__ __forceinline__ void refine_list(RefineLds& L, uint2* const list, const uint32_t m, const int q,
+                                            const uint2* __restrict__ cand, int n_streams, uint32_t capw, int k, float two_e,
+                                            const float* __restrict__ two_e_q, const float* __restrict__ qhat, MasterView master, int dim,
+                                            int64_t row_base, const int64_t* __restrict__ row_map,
+                                            float* __restrict__ out_score, int64_t* __restrict__ out_row,
+                                            int32_t* __restrict__ out_count, int32_t* __restrict__ exact_list,
+                                            RefineCounters* __restrict__ ctr, const float* __restrict__ tau, float inv_scale2,
+                                            int pilot) {
+    uint32_t* const hist = L.hist;
+    uint32_t* const bc = L.bc;
+    const uint32_t* const seg_off = L.seg_off;
+    float* const s_s = L.s_s;
+    int64_t* const s_r = L.s_r;
+    int* const wtot = L.wtot;
+    int& n_p = L.n_p;
     float* o_s = out_score + (int64_t)q * k;
     int64_t* o_r = out_row + (int64_t)q * k;
-    if (threadIdx.x == 0) overflow = 0;
-    __syncthreads();
-    RDX_RSTAMP(0);
-    // segment sizes -> exclusive prefix. Wave 0 scans them 64 at a time with shuffles (n_streams <= 512: at most 8 rounds; the
-    // serial loop this replaces was 3-5 us of the kernel at 256 streams)
-    for (int w = threadIdx.x; w < n_streams; w += blockDim.x) {
-        const uint32_t c = cntw[(int64_t)q * n_streams + w];
-        if (c > capw) overflow = 1;
-        seg_off[w + 1] = c > capw ? capw : c;
-    }
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        const int l = threadIdx.x;
-        uint32_t carry = 0;
-        for (int base = 0; base < n_streams; base += 64) {
-            const int w = base + l;
-            uint32_t v = w < n_streams ? seg_off[w + 1] : 0u;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t t = __shfl_up(v, off, 64);
-                if (l >= off) v += t;
-            }
-            if (w < n_streams) seg_off[w + 1] = carry + v;      // inclusive prefix -> offset of segment w + 1
-            carry += __shfl(v, 63, 64);
-        }
-        if (l == 0) seg_off[0] = 0;
-    }
-    __syncthreads();
-    const uint32_t m = seg_off[n_streams];
-    RDX_RSTAMP(1);
-    if (!SPILL) {
-        if (threadIdx.x == 0) {
-            atomicAdd(&ctr->emitted, (unsigned long long)m);
-            atomicMax(&ctr->max_hits, (int)m);
-        }
-        if (overflow || m > list_cap) {
-            if (threadIdx.x == 0) {
-                if (!overflow && m <= spill_cap) spill_q[atomicAdd(&ctr->n_spill, 1)] = q;
-                else exact_list[atomicAdd(&ctr->n_exact, 1)] = q;
-            }
-            return;
-        }
-    }
-    if (m == 0 || k == 0) {
-        rank_and_write(s_s, s_r, 0, k, o_s, o_r, out_count + q);
-        return;
-    }
     // gather: one thread per ENTRY — its segment is the last w with seg_off[w] <= i (binary search of the prefix in LDS), so every
     // thread has loads in flight and none depends on another (a thread per segment was 64 of 1024 threads at c4, each walking
     // 40-125 dependent 8-byte loads). The entries keep their order: segment after segment.
@@ -373,7 +337,6 @@ __device__ __forceinline__ void refine_query(const int q, uint2* __restrict__ sp
         // The list is compacted in rounds of 7 entries per thread (the LDS list is one round; a spill list takes up to
         // spill_cap / 7168): a round's members are written behind the earlier rounds' — at or below the round's own first entry, and
         // every entry up to the round's end was read before the barrier, so nothing unread is overwritten.
-        __shared__ int wtot[16];
         int base_out = 0;
         for (uint32_t r0 = 0; r0 < m; r0 += 7u * blockDim.x) {
             uint2 mine[7];
@@ -471,6 +434,87 @@ __device__ __forceinline__ void refine_query(const int q, uint2* __restrict__ sp
     RDX_RSTAMP(6);
 }
 
+// K4, one block per query: the hits are counted (segment sizes -> exclusive prefix), and the query takes one of three routes.
+//   m <= list_cap, no segment overflowed: the list in LDS (refine_list<false>);
+//   MAY_SPILL (the plan spills: SearchPlan::spill), m <= spill_cap, no segment overflowed: the block goes on IN THIS LAUNCH with its
+//     row of the spill buffer as the list (refine_list<true>). Until the one-launch form a second kernel, launched behind this one
+//     with a block per possible query, answered the queued queries: 0.22 ms at c4 for 134 of 1 024 blocks with work;
+//   otherwise: the exact full scan (exact_list).
+template <bool MAY_SPILL>
+__device__ __forceinline__ void refine_block(const int q, uint2* __restrict__ spill, uint32_t spill_cap,
+                                             const uint2* __restrict__ cand, const uint32_t* __restrict__ cntw,
+                                             int n_streams, uint32_t capw, uint32_t list_cap, int k, float two_e,
+                                             const float* __restrict__ two_e_q, const float* __restrict__ qhat, MasterView master, int dim,
+                                             int64_t row_base, const int64_t* __restrict__ row_map,
+                                             float* __restrict__ out_score, int64_t* __restrict__ out_row,
+                                             int32_t* __restrict__ out_count, int32_t* __restrict__ exact_list,
+                                             RefineCounters* __restrict__ ctr, const float* __restrict__ tau, float inv_scale2,
+                                             int pilot) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // [list_cap] hits (the LDS list)
+    __shared__ RefineLds L;
+    uint32_t* const seg_off = L.seg_off;
+    if (threadIdx.x == 0) L.overflow = 0;
+    __syncthreads();
+    RDX_RSTAMP(0);
+    // segment sizes -> exclusive prefix. Wave 0 scans them 64 at a time with shuffles (n_streams <= 512: at most 8 rounds; the
+    // serial loop this replaces was 3-5 us of the kernel at 256 streams)
+    for (int w = threadIdx.x; w < n_streams; w += blockDim.x) {
+        const uint32_t c = cntw[(int64_t)q * n_streams + w];
+        if (c > capw) L.overflow = 1;
+        seg_off[w + 1] = c > capw ? capw : c;
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        const int l = threadIdx.x;
+        uint32_t carry = 0;
+        for (int base = 0; base < n_streams; base += 64) {
+            const int w = base + l;
+            uint32_t v = w < n_streams ? seg_off[w + 1] : 0u;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t t = __shfl_up(v, off, 64);
+                if (l >= off) v += t;
+            }
+            if (w < n_streams) seg_off[w + 1] = carry + v;      // inclusive prefix -> offset of segment w + 1
+            carry += __shfl(v, 63, 64);
+        }
+        if (l == 0) seg_off[0] = 0;
+    }
+    __syncthreads();
+    const uint32_t m = seg_off[n_streams];
+    const bool overflow = L.overflow != 0;
+    RDX_RSTAMP(1);
+    if (threadIdx.x == 0) {
+        atomicAdd(&ctr->emitted, (unsigned long long)m);
+        atomicMax(&ctr->max_hits, (int)m);
+    }
+    bool to_spill = false;
+    if (overflow || m > list_cap) {
+        to_spill = MAY_SPILL && !overflow && m <= spill_cap;
+        if (threadIdx.x == 0) {
+            if (to_spill) atomicAdd(&ctr->n_spill, 1);
+            else exact_list[atomicAdd(&ctr->n_exact, 1)] = q;
+        }
+        if (!to_spill) return;
+    }
+    if (m == 0 || k == 0) {
+        rank_and_write(L.s_s, L.s_r, 0, k, out_score + (int64_t)q * k, out_row + (int64_t)q * k, out_count + q);
+        return;
+    }
+    if constexpr (MAY_SPILL) {
+        if (to_spill) {
+            refine_list<true>(L, spill + (int64_t)q * spill_cap, m, q, cand, n_streams, capw, k, two_e, two_e_q, qhat, master, dim, row_base,
+                              row_map, out_score, out_row, out_count, exact_list, ctr, tau, inv_scale2, pilot);
+            return;
+        }
+    }
+    refine_list<false>(L, reinterpret_cast<uint2*>(smem), m, q, cand, n_streams, capw, k, two_e, two_e_q, qhat, master, dim, row_base,
+                       row_map, out_score, out_row, out_count, exact_list, ctr, tau, inv_scale2, pilot);
+}
+
+// MAY_SPILL = false: the kernel of every plan that does not spill, the LDS route alone (what k_refine was before the spill list).
+// MAY_SPILL = true: both routes; `spill` is [nq_pad][spill_cap] in HBM. The search's last kernel on the MFMA path for every plan.
+template <bool MAY_SPILL>
 __global__ __launch_bounds__(1024) void k_refine(const uint2* __restrict__ cand, const uint32_t* __restrict__ cntw,
                                                 int n_streams, uint32_t capw, uint32_t list_cap, int k, float two_e,
                                                 const float* __restrict__ two_e_q, const float* __restrict__ qhat, MasterView master, int dim,
@@ -478,28 +522,9 @@ __global__ __launch_bounds__(1024) void k_refine(const uint2* __restrict__ cand,
                                                 float* __restrict__ out_score, int64_t* __restrict__ out_row,
                                                 int32_t* __restrict__ out_count, int32_t* __restrict__ exact_list,
                                                 RefineCounters* __restrict__ ctr, const float* __restrict__ tau, float inv_scale2,
-                                                int pilot, uint32_t spill_cap, int32_t* __restrict__ spill_q, const FinishArgs fin) {
-    refine_query<false>((int)blockIdx.x, nullptr, spill_cap, spill_q, cand, cntw, n_streams, capw, list_cap, k, two_e, two_e_q, qhat, master, dim,
-                        row_base, row_map, out_score, out_row, out_count, exact_list, ctr, tau, inv_scale2, pilot);
-    finish_if_last(fin);
-}
-
-// K4b. The queries k_refine queued (more hits than its LDS list holds; SearchPlan::spill): one block per POSSIBLE query, the blocks
-// beyond the queue's length leave at once. The list is the query's row of `spill` ([nq_pad][spill_cap] in HBM, L2-resident while
-// a block works on it); no dynamic LDS. Launched behind k_refine only when the plan enables spilling, and then the search's last
-// kernel.
-__global__ __launch_bounds__(1024) void k_refine_spill(uint2* __restrict__ spill, uint32_t spill_cap, const int32_t* __restrict__ spill_q,
-                                                      const uint2* __restrict__ cand, const uint32_t* __restrict__ cntw,
-                                                      int n_streams, uint32_t capw, int k, float two_e,
-                                                      const float* __restrict__ two_e_q, const float* __restrict__ qhat, MasterView master, int dim,
-                                                      int64_t row_base, const int64_t* __restrict__ row_map,
-                                                      float* __restrict__ out_score, int64_t* __restrict__ out_row,
-                                                      int32_t* __restrict__ out_count, int32_t* __restrict__ exact_list,
-                                                      RefineCounters* __restrict__ ctr, const float* __restrict__ tau, float inv_scale2,
-                                                      int pilot, const FinishArgs fin) {
-    if ((int)blockIdx.x < ctr->n_spill)
-        refine_query<true>(spill_q[blockIdx.x], spill, spill_cap, nullptr, cand, cntw, n_streams, capw, spill_cap, k, two_e, two_e_q, qhat, master,
-                           dim, row_base, row_map, out_score, out_row, out_count, exact_list, ctr, tau, inv_scale2, pilot);
+                                                int pilot, uint32_t spill_cap, uint2* __restrict__ spill, const FinishArgs fin) {
+    refine_block<MAY_SPILL>((int)blockIdx.x, spill, spill_cap, cand, cntw, n_streams, capw, list_cap, k, two_e, two_e_q, qhat, master, dim,
+                            row_base, row_map, out_score, out_row, out_count, exact_list, ctr, tau, inv_scale2, pilot);
     finish_if_last(fin);
 }
 

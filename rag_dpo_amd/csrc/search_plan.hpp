@@ -29,7 +29,7 @@ struct SearchOptions {
                              // within E_q of their exact k-th score (refine_kernel.hpp); 0 = one band of 2E_q below c_k
     int i8_sample_mul = 0;   // how many times denser than the fp16 pass's an int8 search samples its threshold — 1, 2, 4, 8, or 0 (default):
                              // I8_AUTO_SAMPLE_MUL where int8 was chosen automatically (those searches spill), 8 where it was forced
-    int refine_spill = 2;    // k_refine_spill for queries with more hits than the LDS list — 0 never, 1 always, 2 (default) where int8
+    int refine_spill = 2;    // spill list (k_refine<true>) for queries with more hits than the LDS list — 0 never, 1 always, 2 (default) where int8
                              // was chosen automatically
     int refine_list = 0;     // developer option: upper bound on the LDS list's entries (>= 32), 0 = automatic
     int spill_cap = 0;       // developer option: upper bound on the spill list's entries per query (>= 32), 0 = SPILL_CAP
@@ -77,9 +77,9 @@ struct SearchPlan {
     int64_t sample_rows = 0;
     double expected_per_query = 0.0;   // candidates per query a random corpus would emit with this sample
     uint32_t capw = 0, list_cap = 0;
-    bool spill = false;                // queries with more than list_cap hits are answered from a list in HBM (k_refine_spill), not by the fallback
+    bool spill = false;                // queries with more than list_cap hits are answered from a list in HBM (k_refine<true>), not by the fallback
     uint32_t spill_cap = 0;            // entries of that list per query
-    int pilot = 0;                     // option "refine_pilot" (k_refine, k_refine_spill)
+    int pilot = 0;                     // option "refine_pilot" (k_refine)
     int k_sel = 0;                     // rank of the sampled score the threshold is taken from (< k: speculative)
     float slack = 0.f;
     bool balance = false;              // XCD-weighted split of the main scan's tiles
@@ -178,7 +178,7 @@ inline int plan_search(const PlanShape& h, const SearchOptions& o, const SearchA
     const bool i8_shape = depth == 0 && nq > 128 && h.dim_pad % 128 == 0 && h.dim_pad <= 1024 && o.force_bn == 0;
     p.i8_auto = i8_shape && o.coarse_i8 == 2 && a.i8_backoff == 0 && nq > 256 && h.rows >= ((int64_t)1 << 20);
     p.i8 = i8_shape && (o.coarse_i8 == 1 || p.i8_auto);
-    // Queries with more hits than the LDS list are answered from a list in HBM (k_refine_spill) instead of the fallback passes: where
+    // Queries with more hits than the LDS list are answered from a list in HBM (k_refine<true>) instead of the fallback passes: where
     // int8 was chosen automatically (option refine_spill = 2), or on every MFMA-path search (1). Everywhere else the plan is what it
     // was before the spill list existed, to the counter.
     p.spill = o.refine_spill == 1 || (o.refine_spill == 2 && p.i8_auto);

@@ -1,0 +1,55 @@
+"""A/B of whole libraries on the contract bench, a sibling of ab_i8_sample.py (whose run() it uses: same command, same record):
+
+    python tools/ab_libs.py --arm parent=tools/librdx_parent.so --arm part1=tools/librdx_p1.so --arm new= --arm new_mul1=:i8_sample_mul=1 \\
+                            [--shape iid|embed] [--rounds 3] [--out DIR]
+
+An arm is NAME=LIBRARY[:OPTION=VALUE,...]; an empty LIBRARY is the product library. The FIRST arm is the base. The arms alternate for
+`rounds` rounds, each run a process of its own; round 0 also writes --dump-outputs of every arm, compared byte for byte with the
+base's. One line per run, then per arm the mean queries/s, its spread (max - min over mean) and its gain on the base."""
+import argparse
+import filecmp
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from ab_i8_sample import ROOT, run
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--arm", action="append", required=True)
+    ap.add_argument("--shape", default="iid", choices=["iid", "embed"])
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "build", "ab_libs"), help="where the dumped outputs go (build/ is git-ignored)")
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    a = ap.parse_args()
+    arms = []
+    for spec in a.arm:
+        name, _, rest = spec.partition("=")
+        lib, _, sets = rest.partition(":")
+        arms.append((name, lib or None, [s for s in sets.split(",") if s]))
+    os.makedirs(a.out, exist_ok=True)
+    got = {name: [] for name, _, _ in arms}
+    for rnd in range(a.rounds):
+        for name, lib, sets in arms:
+            dump = os.path.join(a.out, f"dump_{a.shape}_{name}") if rnd == 0 else None
+            res = run(lib, a.shape, sets, dump, a.steps, a.warmup)
+            got[name].append(res)
+            print(a.shape, rnd, name, json.dumps(res), flush=True)
+    base = arms[0][0]
+    mean = {n: sum(r["qps"] for r in rs) / len(rs) for n, rs in got.items()}
+    for name, rs in got.items():
+        q = [r["qps"] for r in rs]
+        print(f"{a.shape} {name}: queries/s mean {mean[name]:.1f} spread {(max(q) - min(q)) / mean[name] * 100:.2f} % of {len(q)} run(s), "
+              f"{(mean[name] / mean[base] - 1) * 100:+.2f} % on {base}", flush=True)
+    for name in got:
+        if name != base:
+            same = all(filecmp.cmp(os.path.join(a.out, f"dump_{a.shape}_{base}", f), os.path.join(a.out, f"dump_{a.shape}_{name}", f), shallow=False)
+                       for f in ("scores.npy", "rows.npy", "counts.npy"))
+            print(f"{a.shape} {name}: dumped outputs byte-identical to {base}: {same}", flush=True)
+
+
+if __name__ == "__main__":
+    main()
