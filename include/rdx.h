@@ -147,6 +147,9 @@ int rdx_index_set_row_ids(rdx_index* h, int64_t first_row, const int64_t* ids, i
  * fallback passes: 0 never, 1 on every MFMA-path search, 2 where "coarse_i8" = 2 chose the int8 pass (speed only);
  * "i8_sample_mul" 0/1/2/4/8 (default 0): the threshold sample of an int8 search, in multiples of the fp16 pass's (every 64th 32-row
  * block on a large shard): 0 = 2 where "coarse_i8" = 2 chose the int8 pass with "refine_spill" in force, 8 elsewhere (speed only);
+ * "i8_eps_classes" 0/1/2/4/8 (default 0): an int8 search's scan charges a 32-row block the quantisation error of its class of blocks
+ * (edges at the 50 / 75 / 87.5 ... % quantiles of the blocks' errors, the top class the corpus' largest) instead of the corpus' largest
+ * throughout: fewer hits to gather, the same answers; 0 = 8 where "coarse_i8" = 2 chose the int8 pass, 1 elsewhere (speed only);
  * developer options "refine_list" (0 = automatic, or 32..7168: upper bound on the LDS list's entries) and "spill_cap" (0 = automatic,
  * or 32..40960: upper bound on the HBM list's entries) drive the two lists' limits at small sizes (tests). */
 int rdx_index_set_option(rdx_index* h, const char* name, int64_t value);

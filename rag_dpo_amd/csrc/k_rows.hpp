@@ -567,10 +567,11 @@ __device__ __forceinline__ int8_t q8(float y, float inv) {
 // Corpus copy, one wave per 32-row block b (the rows one wave of k_scan owns in a tile): s_b = max |y| over the block / 127,
 // c8 = rint(y / s_b) in fragment order (corpus_off8), eps_b = max over the block's rows of ||y - s_b c8||_2 (fp64, rounded up).
 // y is the normalised row exactly as k_refine re-scores it (MasterRow: the fp32 master, or the compact master's bf16 / divisor).
-// Rows past `rows` and columns past dim are zeros. eps_max (the bits of a float >= 0) takes the largest eps_b (atomicMax).
+// Rows past `rows` and columns past dim are zeros. eps_max (the bits of a float >= 0) takes the largest eps_b (atomicMax); epsb[b]
+// keeps eps_b itself (what k_eps_edges and k_eps_classify sort the blocks into classes by).
 __global__ __launch_bounds__(256) void k_quant8_corpus(MasterView master, int dim, int64_t rows, int64_t blk0, int64_t nblk,
                                                        int8_t* __restrict__ c8, int ksteps8, float* __restrict__ sblk,
-                                                       unsigned int* __restrict__ eps_max) {
+                                                       unsigned int* __restrict__ eps_max, float* __restrict__ epsb) {
     const int lane = threadIdx.x & 63;
     const int64_t b = blk0 + (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (b >= blk0 + nblk) return;
@@ -609,7 +610,36 @@ __global__ __launch_bounds__(256) void k_quant8_corpus(MasterView master, int di
         sblk[b] = s;
         const float eps = f32_up(sqrt(worst) * (1.0 + 1e-12));
         atomicMax(eps_max, __float_as_uint(eps));
+        epsb[b] = eps;
     }
+}
+
+// Classes of block error (DESIGN.md §5 "classes of eps_b"). The int8 scan charges a block the edge of its class instead of the
+// corpus' largest eps_b: edge[c], c < EPS_CLASSES - 1, is the ceil((1 - 2^-(c+1)) nb)-th smallest eps_b of the nb blocks of a full
+// quantisation (an exact order statistic: the bits of floats >= 0 order as uint32), and the top class's edge is the live eps_max
+// (never stored: k_tau8 reads it where it always did). A search with C <= EPS_CLASSES classes uses edges 0..C-2 and eps_max, and
+// puts block b into class min(cls[b], C - 1): the edges nest, so one table of classes serves every C.
+// One workgroup per stored edge.
+__global__ __launch_bounds__(1024) void k_eps_edges(const float* __restrict__ epsb, int64_t nb, float* __restrict__ edge) {
+    __shared__ __attribute__((aligned(16))) uint32_t hist[HIST_WORDS];
+    __shared__ uint32_t bc[4];
+    const int c = blockIdx.x;
+    const int64_t tail = nb >> (c + 1);                       // floor(nb / 2^(c+1)): rank = nb - tail = ceil((1 - 2^-(c+1)) nb), 1-based
+    int64_t n_gt;
+    const uint32_t key = block_kth_largest([&](int64_t i) { return __float_as_uint(epsb[i]); }, nb, tail + 1, hist, bc, &n_gt);
+    if (threadIdx.x == 0) edge[c] = __uint_as_float(key);
+}
+
+// cls[b] = the smallest c < EPS_CLASSES - 1 with eps_b <= edge[c], or EPS_CLASSES - 1 (whose edge is eps_max >= every eps_b). Blocks
+// quantised after the edges were taken (appends) are classified against the same edges.
+__global__ __launch_bounds__(256) void k_eps_classify(const float* __restrict__ epsb, int64_t blk0, int64_t nblk,
+                                                      const float* __restrict__ edge, uint8_t* __restrict__ cls) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nblk) return;
+    const float e = epsb[blk0 + i];
+    int c = 0;
+    while (c < EPS_CLASSES - 1 && !(e <= edge[c])) ++c;
+    cls[blk0 + i] = (uint8_t)c;
 }
 
 // Query copy, one wave per query: t_q = max |q| / 127, q8 = rint(q / t_q) in the query-image order (query_off8), and, in fp64
@@ -658,13 +688,21 @@ __global__ __launch_bounds__(256) void k_quant8_query(const float* __restrict__ 
 //   E_q = e_q (1 + 1e-6) + n_q eps_max + 1e-6                 (||y|| <= 1 + 1e-6, 1e-6 for the fp32 roundings)
 // and its three thresholds: thr (int8 accumulator units D s_b, what k_scan<I8> compares: coarse + E_q >= T), tau_s (score
 // units, what k_refine verifies c_k - 2E_q against: every row whose coarse score reaches tau_s was emitted) and 2E_q.
+// With ncls > 1 classes of block error (k_eps_edges) thr is [ncls][nq_pad]: the top class ncls - 1 is the bound above with eps_max,
+// to the statement; class c below it charges edge[c] instead, E_{q,c} = e_q (1 + 1e-6) + n_q edge[c] + 1e-6 <= E_q, and compares
+// thr_c = fl_down((T - E_{q,c}) / t_q). A row of class c that was not emitted has coarse < tau_c = thr_c t_q + 1e-6 and so
+// exact < tau_c + E_{q,c}: tau_s = max_c (tau_c + E_{q,c}) - E_q (fp64, rounded up) keeps k_refine's check X - E_q >= tau_s
+// sufficient; 2E_q stays the band with eps_max.
 __global__ __launch_bounds__(256) void k_tau8(const float* __restrict__ tau16, float inv_scale2, const float* __restrict__ tq,
                                               const float* __restrict__ eq, const float* __restrict__ nqn,
                                               const unsigned int* __restrict__ eps_max, int nq, int nq_pad,
-                                              float* __restrict__ thr, float* __restrict__ tau_s, float* __restrict__ two_e) {
+                                              float* __restrict__ thr_all, float* __restrict__ tau_s, float* __restrict__ two_e,
+                                              const float* __restrict__ edge, int ncls) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nq_pad) return;
+    float* const thr = thr_all + (size_t)(ncls - 1) * nq_pad;   // the top class: today's table
     if (i >= nq) {   // padding query: never emits
+        for (int c = 0; c < ncls - 1; ++c) thr_all[(size_t)c * nq_pad + i] = INFINITY;
         thr[i] = INFINITY;
         tau_s[i] = INFINITY;
         two_e[i] = 0.f;
@@ -675,6 +713,7 @@ __global__ __launch_bounds__(256) void k_tau8(const float* __restrict__ tau16, f
     two_e[i] = f32_up(2.0 * (double)Ef);
     const float T = tau16[i] * inv_scale2;   // (a power of two: exact; -inf stays -inf)
     if (!(T > -INFINITY)) {
+        for (int c = 0; c < ncls - 1; ++c) thr_all[(size_t)c * nq_pad + i] = -INFINITY;
         thr[i] = -INFINITY;
         tau_s[i] = -INFINITY;
         return;
@@ -687,6 +726,26 @@ __global__ __launch_bounds__(256) void k_tau8(const float* __restrict__ tau16, f
     float tsf = (float)ts;
     if ((double)tsf < ts) tsf = nextafterf(tsf, INFINITY);
     tau_s[i] = tsf;
+    if (ncls == 1) return;
+    double worst = (double)tsf + (double)Ef;   // max over the classes of tau_c + E_{q,c}; the top class's is tau_s + E_q
+    bool lower = false;
+    for (int c = 0; c < ncls - 1; ++c) {
+        const float Ec = f32_up((double)eq[i] * (1.0 + 1e-6) + (double)nqn[i] * (double)edge[c] + 1e-6);
+        float thc = (float)(((double)T - (double)Ec) / t);
+        if ((double)thc * t > (double)T - (double)Ec) thc = nextafterf(thc, -INFINITY);
+        thr_all[(size_t)c * nq_pad + i] = thc;
+        const float tc = f32_up((double)thc * t + 1e-6);
+        if ((double)tc + (double)Ec > worst) {
+            worst = (double)tc + (double)Ec;
+            lower = true;
+        }
+    }
+    if (lower) {
+        const double x = worst - (double)Ef;
+        float f = (float)x;
+        if ((double)f < x) f = nextafterf(f, INFINITY);
+        tau_s[i] = f;
+    }
 }
 
 }  // namespace rdx

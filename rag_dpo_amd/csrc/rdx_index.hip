@@ -80,6 +80,8 @@ struct rdx_index {
     // int8 coarse pass: corpus copy [cap][dim_pad] in corpus_off8 order + s_b per 32-row block + the largest eps_b (built by the first
     // search that takes the path, rows [0, i8_valid) current; not persisted) and the per-search query copy, scales, bounds, thresholds
     DevBuf c8, sblk, eps8, qshadow8, tq8, eq8, nq8, thr8, taus8, twoe8;
+    // ... and the classes of block error: eps_b per block, the EPS_CLASSES - 1 stored edges (taken at a full quantisation), a class byte per block
+    DevBuf epsb, edge8, cls8;
     DevBuf spill;            // k_refine<true>: [nq_pad][spill_cap] hit lists of the queries that outgrow the LDS list (first spilling plan)
     int64_t i8_valid = 0;
     // end-of-search mailbox in pinned host memory (k_finish writes it over PCIe; the host spins on its sequence number)
@@ -215,7 +217,7 @@ static int ensure_dynamic_lds(rdx_index* h, const void* func, size_t bytes) {
 template <int BN, int EPI, bool RES, bool NTT = false, bool FUSED = false, bool I8 = false>
 static int launch_scan(rdx_index* h, const ScanParams& p, int grid, hipStream_t st) {
     // LDS: query-image ring (or the whole resident query tile) + BN hit counters + BN thresholds
-    const size_t lds = (size_t)(RES ? p.ksteps : RING_SLOTS) * BN * BK * 2 + BN * (I8 ? 12 : 8);   // (I8: + BN query scales)
+    const size_t lds = (size_t)(RES ? p.ksteps : RING_SLOTS) * BN * BK * 2 + BN * (I8 ? 8 + 4 * p.ncls : 8);   // (I8: BN query scales, a table per class)
     void (*kern)(const ScanParams) = p.allow ? k_scan<BN, EPI, true, RES, NTT, FUSED, I8> : k_scan<BN, EPI, false, RES, NTT, FUSED, I8>;
     RDX_TRY(ensure_dynamic_lds(h, (const void*)kern, lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, p);
@@ -387,7 +389,7 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
     if (p.i8) {
         hipLaunchKernelGGL(k_tau8, dim3((p.nq_pad + 255) / 256), dim3(256), 0, st, h->tau.as<float>(), std::ldexp(1.0f, -2 * h->scale_log2),
                            h->tq8.as<float>(), h->eq8.as<float>(), h->nq8.as<float>(), h->eps8.as<unsigned int>(), (int)p.nq, p.nq_pad,
-                           h->thr8.as<float>(), h->taus8.as<float>(), h->twoe8.as<float>());
+                           h->thr8.as<float>(), h->taus8.as<float>(), h->twoe8.as<float>(), h->edge8.as<float>(), p.eps_classes);
         HIP_TRY(hipGetLastError());
     }
     mark(h, p, st, 3);
@@ -408,6 +410,8 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
         s8.tau = h->thr8.as<float>();
         s8.sblk = h->sblk.as<float>();
         s8.qscale = h->tq8.as<float>();
+        s8.cls = h->cls8.as<uint32_t>();
+        s8.ncls = p.eps_classes;
         s8.shadow_bytes = (int64_t)h->cap * h->dim_pad;
         RDX_TRY(launch_scan_i8(h, p.fused, s8, p.grid, st));
     } else {
@@ -436,20 +440,39 @@ static int prepare_i8(rdx_index* h, const SearchPlan& p, hipStream_t st) {
     const void* old_c8 = h->c8.p;
     const void* old_sb = h->sblk.p;
     const void* old_eps = h->eps8.p;
+    const void* old_eb = h->epsb.p;
+    const void* old_ed = h->edge8.p;
+    const void* old_cl = h->cls8.p;
     RDX_TRY(h->c8.ensure((size_t)h->cap * h->dim_pad));
     RDX_TRY(h->sblk.ensure((size_t)(h->cap / 32) * 4));
     RDX_TRY(h->eps8.ensure(4));
-    if (h->c8.p != old_c8 || h->sblk.p != old_sb || h->eps8.p != old_eps) h->i8_valid = 0;   // (a reallocation loses the contents)
+    RDX_TRY(h->epsb.ensure((size_t)(h->cap / 32) * 4));
+    RDX_TRY(h->edge8.ensure((size_t)EPS_CLASSES * 4));
+    RDX_TRY(h->cls8.ensure((size_t)(h->cap / 32 + 3) / 4 * 4));   // (k_scan<I8> reads whole dwords)
+    if (h->c8.p != old_c8 || h->sblk.p != old_sb || h->eps8.p != old_eps || h->epsb.p != old_eb || h->edge8.p != old_ed || h->cls8.p != old_cl)
+        h->i8_valid = 0;   // (a reallocation loses the contents)
     if (h->i8_valid < h->rows) {
-        if (h->i8_valid == 0) HIP_TRY(hipMemsetAsync(h->eps8.p, 0, 4, st));
+        const bool full = h->i8_valid == 0;
+        if (full) HIP_TRY(hipMemsetAsync(h->eps8.p, 0, 4, st));
         const int64_t b0 = h->i8_valid / 32, nb = (h->rows + 31) / 32 - b0;
         hipLaunchKernelGGL(k_quant8_corpus, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, h->mv(), h->dim, h->rows, b0, nb,
-                           h->c8.as<int8_t>(), ks8, h->sblk.as<float>(), h->eps8.as<unsigned int>());
+                           h->c8.as<int8_t>(), ks8, h->sblk.as<float>(), h->eps8.as<unsigned int>(), h->epsb.as<float>());
+        HIP_TRY(hipGetLastError());
+        // classes of block error: the edges from the eps_b of a full quantisation (on the stream: no host round trip); what an append
+        // quantises is classified against the edges that stand (a block above the last stored edge lands in the top class, whose
+        // edge is the running eps_max)
+        if (full) {
+            hipLaunchKernelGGL(k_eps_edges, dim3(EPS_CLASSES - 1), dim3(1024), 0, st, h->epsb.as<float>(), nb, h->edge8.as<float>());
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_eps_classify, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, h->epsb.as<float>(), b0, nb,
+                           h->edge8.as<float>(), h->cls8.as<uint8_t>());
         HIP_TRY(hipGetLastError());
         h->i8_valid = h->rows;
     }
     RDX_TRY(h->qshadow8.ensure((size_t)p.nq_pad * h->dim_pad));
-    for (DevBuf* b : {&h->tq8, &h->eq8, &h->nq8, &h->thr8, &h->taus8, &h->twoe8}) RDX_TRY(b->ensure((size_t)p.nq_pad * 4));
+    for (DevBuf* b : {&h->tq8, &h->eq8, &h->nq8, &h->taus8, &h->twoe8}) RDX_TRY(b->ensure((size_t)p.nq_pad * 4));
+    RDX_TRY(h->thr8.ensure((size_t)p.eps_classes * p.nq_pad * 4));
     hipLaunchKernelGGL(k_quant8_query, dim3((p.nq_pad + 3) / 4), dim3(256), 0, st, h->qhat.as<float>(), p.nq, (int64_t)p.nq_pad, h->dim,
                        h->qshadow8.as<int8_t>(), ks8, h->tq8.as<float>(), h->eq8.as<float>(), h->nq8.as<float>());
     HIP_TRY(hipGetLastError());
@@ -811,7 +834,7 @@ extern "C" int rdx_index_destroy(rdx_index* h) {
     for (DevBuf* b : {&h->staging, &h->qraw, &h->qhat, &h->qshadow, &h->tau, &h->cntw, &h->cand, &h->setmax, &h->exact_list, &h->spill,
                       &h->iota, &h->dense, &h->ctr, &h->bad, &h->o_score, &h->o_row, &h->o_count, &h->mask, &h->ids,
                       &h->r_list, &h->r_q, &h->r_s, &h->r_r, &h->r_c, &h->c8, &h->sblk, &h->eps8, &h->qshadow8, &h->tq8,
-                      &h->eq8, &h->nq8, &h->thr8, &h->taus8, &h->twoe8})
+                      &h->eq8, &h->nq8, &h->thr8, &h->taus8, &h->twoe8, &h->epsb, &h->edge8, &h->cls8})
         b->release();
     if (h->mbox) (void)hipHostFree(h->mbox);
     if (h->pin_out) (void)hipHostFree(h->pin_out);

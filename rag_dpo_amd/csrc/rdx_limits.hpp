@@ -17,5 +17,7 @@ constexpr int REFINE_STREAMS = 512;  // most (query, stream) segments
 constexpr int SPILL_CAP = 40960;     // most hits of a query whose list lives in HBM instead (k_refine<true>; plan_search SearchPlan::spill): 2.4x the
                                      // longest list seen at c4 with the thinnest sample (17 264 hits, every 64th block; 13 358 at the default's
                                      // every 32nd; DESIGN.md §5 "Spill list"), 320 MB for 1 024 queries; more -> second pass
+constexpr int EPS_CLASSES = 8;       // most classes of block error the int8 scan tells apart (k_eps_edges, SearchPlan::eps_classes): edges at the
+                                     // 50 / 75 / 87.5 ... % quantiles of eps_b, the top class's edge eps_max
 
 }   // namespace rdx

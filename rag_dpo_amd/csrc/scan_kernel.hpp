@@ -81,6 +81,10 @@ struct ScanParams {
     // counts 128-dimension steps, tau is in units of t_q (the query's scale) and a 32-row block b scores (float)D * sblk[b] there
     const float* sblk;         // [32-row blocks] s_b
     const float* qscale;       // [nq_pad] t_q: score = (float)D * s_b * t_q
+    // ... in ncls classes of block error (k_rows.hpp k_eps_edges): tau is [ncls][nq_pad], block b compares with the table of class
+    // min(cls[b], ncls - 1). cls is read a dword at a time (a scalar load): the host pads it to a multiple of four bytes.
+    const uint32_t* cls;       // [32-row blocks] one byte each
+    int ncls;                  // 1 .. EPS_CLASSES
     int64_t shadow_bytes;      // RDX_CHECK_BOUNDS builds: size of the scan copy ...
     int* oob;                  // ... and the flag a corpus read outside it raises (tests/test_gpu_bounds.py)
 };
@@ -206,7 +210,10 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
         else return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
     };
     float runmax[EPI == EPI_SETMAX ? NB16 : 1][1];
-    float* tau_s = reinterpret_cast<float*>(lcnt + BN);   // [BN] thresholds of this query tile (LDS: registers are scarce)
+    // [BN] thresholds of this query tile (LDS: registers are scarce). I8: the BN query scales t_q first, then ncls tables of BN
+    // thresholds, one per class of block error
+    float* tau_s = reinterpret_cast<float*>(lcnt + BN);
+    constexpr int TAU0 = I8 ? BN : 0;   // where the (first) threshold table starts
     if constexpr (EPI == EPI_SETMAX) {
 #pragma unroll
         for (int n = 0; n < (int)(sizeof(runmax) / sizeof(runmax[0])); ++n)
@@ -214,9 +221,15 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
             for (int j = 0; j < (int)(sizeof(runmax[0]) / sizeof(float)); ++j) runmax[n][j] = -INFINITY;
     } else {
         // stored [l15][n] so that one ds_read_b128 fetches the thresholds of four consecutive query blocks of a lane
-        for (int i = threadIdx.x; i < BN; i += 512) tau_s[(i & 15) * (BN / 16) + (i >> 4)] = p.tau[qt * BN + i];
-        if constexpr (I8)   // the rare emit path's t_q from LDS: a global load there would make the compiler drain vmcnt(0) (the asm prefetches)
-            for (int i = threadIdx.x; i < BN; i += 512) tau_s[BN + i] = p.qscale[qt * BN + i];
+        if constexpr (I8) {
+            for (int c = 0; c < p.ncls; ++c)
+                for (int i = threadIdx.x; i < BN; i += 512)
+                    tau_s[TAU0 + c * BN + (i & 15) * (BN / 16) + (i >> 4)] = p.tau[(int64_t)c * p.nq_pad + qt * BN + i];
+            // the rare emit path's t_q from LDS: a global load there would make the compiler drain vmcnt(0) (the asm prefetches)
+            for (int i = threadIdx.x; i < BN; i += 512) tau_s[i] = p.qscale[qt * BN + i];
+        } else {
+            for (int i = threadIdx.x; i < BN; i += 512) tau_s[(i & 15) * (BN / 16) + (i >> 4)] = p.tau[qt * BN + i];
+        }
     }
 
     // LDS address of this lane's query fragment for k sub-step kk (16-query block n adds n*2048), swizzled:
@@ -269,10 +282,23 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
             return max3(max3(t1, t2, acc[0][n][3]), acc[1][n][3], acc[1][n][3]);
         }
     };
-    // I8: s_b of this wave's 32-row block of schedule entry it_done (wave-uniform: a scalar load)
+    // I8: s_b of this wave's 32-row block of schedule entry it_done (wave-uniform; the compiler issues it as a vector load of one
+    // dword and waits for it with vmcnt(0), once per tile. Read as a scalar load instead — through the constant address space — the
+    // main scan measured 1.5 % slower, profiles/i8_classes/ab_c4.txt)
     auto block_scale = [&](int it_done) __attribute__((always_inline)) -> float {
         if constexpr (I8) return p.sblk[(int64_t)sched_of(it_done) * 8 + wave];
         else return 1.f;
+    };
+    // I8: where in tau_s the threshold table of that block's class starts. Wave-uniform, and read through the constant address space
+    // (nothing writes cls while a scan runs): a scalar dword load and scalar arithmetic, no vector register
+    using cu32_p = const __attribute__((address_space(4))) uint32_t*;
+    auto class_base = [&](int it_done) __attribute__((always_inline)) -> int {
+        if constexpr (I8) {
+            const int64_t b = (int64_t)sched_of(it_done) * 8 + wave;
+            const uint32_t c = (((cu32_p)p.cls)[b >> 2] >> ((wave & 3) * 8)) & 0xffu;
+            const uint32_t top = (uint32_t)p.ncls - 1u;
+            return TAU0 + (int)(c < top ? c : top) * BN;
+        } else return 0;
     };
     // EMIT, rare path (a handful of blocks per tile): append the hits of block n to the (query, stream) segments. Slot from an
     // LDS counter (inline asm: next to LDS-DMA the compiler would put s_waitcnt vmcnt(0) in front of an LDS atomic and drain
@@ -294,7 +320,7 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
         // store address is an SGPR base + a 32-bit lane offset, no 64-bit vector arithmetic
         const uint32_t seg0 = ((uint32_t)(qt * BN + ql) * (uint32_t)n_streams + (uint32_t)stream) * capw_s;
         const uint32_t row0 = (uint32_t)row_b + (uint32_t)lr;
-        const float to_score = I8 ? tau_s[BN + ql] : p.inv_scale2;
+        const float to_score = I8 ? tau_s[ql] : p.inv_scale2;
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -309,8 +335,8 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
             }
     };
     // thresholds of this lane's query column for blocks n0..n0+3 (one ds_read_b128; stored [l15][block])
-    auto tau_quad = [&](int n0) __attribute__((always_inline)) {
-        int t = l15 * NB16 + n0;
+    auto tau_quad = [&](int n0, int cb) __attribute__((always_inline)) {
+        int t = l15 * NB16 + n0 + cb;
         asm volatile("" : "+v"(t));   // not a loop invariant worth a register
         return *reinterpret_cast<const f32x4*>(tau_s + t);
     };
@@ -415,9 +441,10 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
             int tb = l15 * NB16;
             float sb_prev = 1.f;  // FUSE, I8: s_b of the finished tile
             if constexpr (FUSE) {
+                sb_prev = block_scale(it_prev);
+                if constexpr (I8) tb += class_base(it_prev);   // the finished tile's block: its class's table
                 asm volatile("" : "+v"(tb));
                 tq_cur = tau_one(tb, 0);
-                sb_prev = block_scale(it_prev);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -505,9 +532,11 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
             uint32_t okbits = 0xffffffffu;
             bool filt = false;
             float sb = 1.f;
+            int cb = 0;
             if constexpr (EPI == EPI_EMIT) {
-                tq4n = tau_quad(0);
                 sb = block_scale(it_done);
+                cb = class_base(it_done);
+                tq4n = tau_quad(0, cb);
             } else tile_rows(it_done, row_b, okbits, filt);
 #pragma unroll
             for (int n = 0; n < NB16; ++n) {
@@ -523,7 +552,7 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
                 } else {
                     if ((n & 3) == 0) {
                         tq4 = tq4n;
-                        if (n + 4 < NB16) tq4n = tau_quad(n + 4);
+                        if (n + 4 < NB16) tq4n = tau_quad(n + 4, cb);
                     }
                     const float mx = block_max(n, sb);
                     const float tq = tq4[n & 3];

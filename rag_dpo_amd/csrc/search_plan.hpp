@@ -29,6 +29,8 @@ struct SearchOptions {
                              // within E_q of their exact k-th score (refine_kernel.hpp); 0 = one band of 2E_q below c_k
     int i8_sample_mul = 0;   // how many times denser than the fp16 pass's an int8 search samples its threshold — 1, 2, 4, 8, or 0 (default):
                              // I8_AUTO_SAMPLE_MUL where int8 was chosen automatically (those searches spill), 8 where it was forced
+    int i8_eps_classes = 0;  // classes of block error the int8 scan's emit threshold tells apart (k_eps_edges) — 1, 2, 4, 8, or 0 (default):
+                             // I8_AUTO_EPS_CLASSES where int8 was chosen automatically, 1 where it was forced
     int refine_spill = 2;    // spill list (k_refine<true>) for queries with more hits than the LDS list — 0 never, 1 always, 2 (default) where int8
                              // was chosen automatically
     int refine_list = 0;     // developer option: upper bound on the LDS list's entries (>= 32), 0 = automatic
@@ -74,6 +76,7 @@ struct SearchPlan {
     bool use_small = false;            // k_scan_small as the main scan
     bool i8 = false;                   // the main scan runs on the int8 copies (k_scan<..., I8>; DESIGN.md §5 "int8 coarse pass")
     bool i8_auto = false;              // ... chosen automatically (coarse_i8 = 2): the search adapt_sampling's int8 back-off judges
+    int eps_classes = 1;               // ... with its emit thresholds in this many classes of block error (1: every block is charged eps_max)
     int64_t sample_rows = 0;
     double expected_per_query = 0.0;   // candidates per query a random corpus would emit with this sample
     uint32_t capw = 0, list_cap = 0;
@@ -104,6 +107,7 @@ constexpr size_t PIN_MAX = 256 * 1024;   // results up to this size ride with k_
 // fallback passes, which use rank k, and switches speculation off for the next searches (structured corpora, where
 // "every div-th tile" is not a random sample; SearchAdapt::spec_backoff counts them down in enqueue_scan, after this read).
 constexpr int I8_AUTO_SAMPLE_MUL = 2;   // (plan_search: the int8 sample where int8 is chosen automatically)
+constexpr int I8_AUTO_EPS_CLASSES = EPS_CLASSES;   // (plan_search: classes of block error where int8 is chosen automatically)
 
 inline int speculative_rank(const SearchOptions& o, const SearchAdapt& a, int64_t rows, int k, int depth, int64_t sample_rows) {
     if (!o.spec_tau || depth != 0 || a.spec_backoff != 0 || k <= 1) return k;
@@ -182,6 +186,10 @@ inline int plan_search(const PlanShape& h, const SearchOptions& o, const SearchA
     // int8 was chosen automatically (option refine_spill = 2), or on every MFMA-path search (1). Everywhere else the plan is what it
     // was before the spill list existed, to the counter.
     p.spill = o.refine_spill == 1 || (o.refine_spill == 2 && p.i8_auto);
+    // The int8 scan's emit threshold in classes of block error (DESIGN.md §5 "classes of eps_b"): by the same rule, where int8 was
+    // chosen automatically at depth 0; a forced int8 search keeps the one threshold with eps_max unless option i8_eps_classes says
+    // otherwise. Only the scan's hits change: segments, lists and the sample stay sized for one class.
+    p.eps_classes = !p.i8 ? 1 : (o.i8_eps_classes ? o.i8_eps_classes : (p.i8_auto ? I8_AUTO_EPS_CLASSES : 1));
     p.spill_cap = p.spill ? (uint32_t)(o.spill_cap ? std::min(o.spill_cap, SPILL_CAP) : SPILL_CAP) : 0u;
 
     // queries per workgroup: 64 (tile resident in LDS), 128, 256. 257..384 queries run as three 128-query tiles rather than
@@ -355,6 +363,7 @@ inline const OptionRow SEARCH_OPTIONS[] = {
     {"refine_pilot", &SearchOptions::refine_pilot, nullptr, OPT_RANGE, 0, 64,
      "refine_pilot must be 0 (one band) or 1..64 (pilot of that many times k hits)"},
     {"i8_sample_mul", &SearchOptions::i8_sample_mul, nullptr, OPT_ZERO_OR_POW2, 1, 8, "i8_sample_mul must be 0 (automatic), 1, 2, 4 or 8"},
+    {"i8_eps_classes", &SearchOptions::i8_eps_classes, nullptr, OPT_ZERO_OR_POW2, 1, EPS_CLASSES, "i8_eps_classes must be 0 (automatic), 1, 2, 4 or 8"},
     {"refine_spill", &SearchOptions::refine_spill, nullptr, OPT_RANGE, 0, 2, "refine_spill must be 0 (never), 1 (always) or 2 (automatic)"},
     {"refine_list", &SearchOptions::refine_list, nullptr, OPT_ZERO_OR_RANGE, 32, REFINE_LIST, "refine_list must be 0 (automatic) or 32.."},
     {"spill_cap", &SearchOptions::spill_cap, nullptr, OPT_ZERO_OR_RANGE, 32, SPILL_CAP, "spill_cap must be 0 (automatic) or 32.."},
