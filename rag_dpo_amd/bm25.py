@@ -16,8 +16,9 @@ postings (include/rdx.h rdx_bm25_*, csrc/bm25_kernel.hpp). Search result: rows w
 `document_path` is in `doc_filter` when it is not None: an empty set returns nothing), score descending, ties by
 ascending row, cut to top_k (bm25_index.py:146-168, :265-292).
 
-The index is immutable, as in the reference: to refresh, build again. Tokenisation is Python, as in the reference;
-the postings are built with numpy.
+The index is immutable, as in the reference: to refresh, build again. By default tokenisation is Python, as in the reference,
+and the postings are built with numpy; build="device" does both on the GPU (rag_dpo_amd/bm25_build.py), for collections whose
+tokens do not fit Python strings.
 """
 from __future__ import annotations
 
@@ -92,9 +93,7 @@ class Bm25Model:
         n = len(corpus_tokens)
         doc_len = np.fromiter(map(len, corpus_tokens), dtype=np.int64, count=n)
         flat = list(chain.from_iterable(corpus_tokens))
-        vocab = dict.fromkeys(flat)                                   # first-occurrence order = rank_bm25's nd order
-        self.term_id: Dict[str, int] = dict(zip(vocab, range(len(vocab))))
-        self.n_rows, self.n_terms = n, len(self.term_id)
+        self._set_vocab(n, dict.fromkeys(flat))                       # first-occurrence order = rank_bm25's nd order
         ids = np.fromiter(map(self.term_id.__getitem__, flat), dtype=np.int64, count=len(flat))
         rows = np.repeat(np.arange(n, dtype=np.int64), doc_len)
         key, tf = np.unique(ids * max(n, 1) + rows, return_counts=True)   # sorted by (term, row)
@@ -105,6 +104,30 @@ class Bm25Model:
         self.post_tf = tf.astype(np.uint16)
         self.post_off = np.zeros(self.n_terms + 1, dtype=np.int64)
         np.cumsum(np.bincount(term, minlength=self.n_terms), out=self.post_off[1:])
+        self._set_statistics(doc_len)
+
+    @classmethod
+    def from_postings(cls, n_rows: int, doc_len: np.ndarray, vocab: Sequence[str], post_off: np.ndarray, post_row: np.ndarray,
+                      post_tf: np.ndarray) -> "Bm25Model":
+        """the model of postings built elsewhere (rag_dpo_amd/bm25_build.py builds them on the GPU): `vocab` = the terms in
+        first-occurrence order, doc_len int64 [n_rows], the postings as in Bm25Arrays. The statistics are __init__'s own."""
+        self = cls.__new__(cls)
+        self._set_vocab(int(n_rows), vocab)
+        self.post_off = np.ascontiguousarray(post_off, dtype=np.int64)
+        self.post_row = np.ascontiguousarray(post_row, dtype=np.int32)
+        self.post_tf = np.ascontiguousarray(post_tf, dtype=np.uint16)
+        if self.post_off.shape != (self.n_terms + 1,) or len(doc_len) != self.n_rows or len(self.post_row) != len(self.post_tf):
+            raise ValueError("from_postings: the arrays do not fit n_rows and the vocabulary")
+        self._set_statistics(np.ascontiguousarray(doc_len, dtype=np.int64))
+        return self
+
+    def _set_vocab(self, n: int, vocab) -> None:
+        self.term_id: Dict[str, int] = dict(zip(vocab, range(len(vocab))))
+        self.n_rows, self.n_terms = n, len(self.term_id)
+
+    def _set_statistics(self, doc_len: np.ndarray) -> None:
+        """rank_bm25's statistics from doc_len and post_off, for both ways of building the postings"""
+        n = self.n_rows
         self.doc_len = doc_len
         self.avgdl = int(doc_len.sum()) / n if n else 0.0
         self.idf, self.average_idf = idf_of(n, np.diff(self.post_off))
@@ -174,10 +197,31 @@ def _default_engine_factory(arrays: Bm25Arrays, device: int):
     return HipBm25(arrays, device)
 
 
+def _resolve_build(build: str) -> str:
+    """-> "host" or "device": where an index's postings are built ("auto" = the device when librdx loads with a GPU)"""
+    if build not in ("host", "device", "auto"):
+        raise ValueError(f'build must be "host", "device" or "auto" (got {build!r})')
+    if build == "host":
+        return build
+    try:
+        L.load(require_gpu=True)
+    except L.RdxUnavailable:
+        if build == "device":
+            raise
+        return "host"
+    return "device"
+
+
 class _Bm25Base:
-    def __init__(self, engine_factory: Optional[Callable[[Bm25Arrays, int], object]] = None, device: int = 0):
+    """build="host" tokenises in Python and builds the postings with numpy; build="device" does both on the GPU
+    (rag_dpo_amd/bm25_build.py: the same model and engine arrays, bit for bit) and raises RuntimeError without librdx or a GPU;
+    build="auto" takes the device when there is one. After a device build `corpus_tokens` stays []: the tokens never exist as
+    Python strings."""
+
+    def __init__(self, engine_factory: Optional[Callable[[Bm25Arrays, int], object]] = None, device: int = 0, build: str = "host"):
         self._factory = engine_factory or _default_engine_factory
         self.device = device
+        self.build_mode = _resolve_build(build)
         self.model: Optional[Bm25Model] = None
         self.engine = None
         self.corpus_tokens: List[List[str]] = []
@@ -187,10 +231,15 @@ class _Bm25Base:
     def is_built(self) -> bool:
         return self._is_built
 
-    def _install(self, row_group=None, n_groups=0):
+    def _device_build(self, texts: Sequence[Optional[str]]):
+        """-> (indexes of the texts that have a token, their Bm25Model), built on the GPU"""
+        from .bm25_build import DeviceBm25Builder
+        return DeviceBm25Builder(self.device).build(texts)
+
+    def _install(self, row_group=None, n_groups=0, model: Optional[Bm25Model] = None):
         if self.engine is not None and hasattr(self.engine, "close"):
             self.engine.close()
-        self.model = Bm25Model(self.corpus_tokens)
+        self.model = model if model is not None else Bm25Model(self.corpus_tokens)
         self.engine = self._factory(self.model.arrays(row_group, n_groups), self.device) if self.model.n_rows else None
         self._is_built = True
 
@@ -229,8 +278,8 @@ class _Bm25Base:
 class SummaryBM25Index(_Bm25Base):
     """reference bm25_index.py SummaryBM25Index: BM25 over the document summaries (pre-filter of the documents)"""
 
-    def __init__(self, summaries_path: Optional[Path] = None, engine_factory=None, device: int = 0):
-        super().__init__(engine_factory, device)
+    def __init__(self, summaries_path: Optional[Path] = None, engine_factory=None, device: int = 0, build: str = "host"):
+        super().__init__(engine_factory, device, build)
         self.summaries_path = Path(summaries_path) if summaries_path else Path("data/keep/cnil/document_summaries.json")
         self.doc_keys: List[str] = []
         self.doc_metadata: List[Dict] = []
@@ -243,22 +292,29 @@ class SummaryBM25Index(_Bm25Base):
         with open(self.summaries_path, "r", encoding="utf-8") as f:
             summaries = json.load(f)
         self.doc_keys, self.doc_metadata, self.corpus_tokens = [], [], []
-        skipped = 0
+        device = self.build_mode == "device"
+        texts = []
         for doc_path, entry in summaries.items():
             summary = entry.get("summary", "")
             if not summary or summary.startswith("ERREUR"):
-                skipped += 1
                 continue
             title, url = entry.get("document_title", ""), entry.get("source_url", "")
-            tokens = tokenize_french(f"{title} {summary} {url}")
-            if not tokens:
-                skipped += 1
-                continue
+            text = f"{title} {summary} {url}"
+            if device:      # every entry goes to the GPU; the ones without a token are dropped below, by its count
+                texts.append(text)
+            else:
+                tokens = tokenize_french(text)
+                if not tokens:
+                    continue
+                self.corpus_tokens.append(tokens)
             self.doc_keys.append(doc_path)
             self.doc_metadata.append({"document_path": doc_path, "source_url": url, "document_title": title, "summary": summary})
-            self.corpus_tokens.append(tokens)
-        self._install()
-        logger.info("BM25 summaries index: %d documents (%d skipped)", len(self.doc_keys), skipped)
+        model = None
+        if device:
+            kept, model = self._device_build(texts)
+            self.doc_keys, self.doc_metadata = ([col[i] for i in kept.tolist()] for col in (self.doc_keys, self.doc_metadata))
+        self._install(model=model)
+        logger.info("BM25 summaries index: %d documents (%d skipped)", len(self.doc_keys), len(summaries) - len(self.doc_keys))
 
     def search(self, query: str, top_k: int = 20) -> List[BM25Result]:
         (hits,) = self._search_rows([query], top_k)
@@ -275,8 +331,8 @@ class SummaryBM25Index(_Bm25Base):
 class ChunkBM25Index(_Bm25Base):
     """reference bm25_index.py ChunkBM25Index: BM25 over the chunks of a collection (the sparse ranking of hybrid retrieval)"""
 
-    def __init__(self, engine_factory=None, device: int = 0):
-        super().__init__(engine_factory, device)
+    def __init__(self, engine_factory=None, device: int = 0, build: str = "host"):
+        super().__init__(engine_factory, device, build)
         self.chunk_ids: List[str] = []
         self.chunk_texts: List[str] = []
         self.chunk_metadatas: List[Dict] = []
@@ -286,8 +342,15 @@ class ChunkBM25Index(_Bm25Base):
         total = collection.count()
         self.chunk_ids, self.chunk_texts, self.chunk_metadatas, self.corpus_tokens = [], [], [], []
         offset = 0
+        device = self.build_mode == "device"
         while offset < total:
             batch = collection.get(limit=batch_size, offset=offset, include=["documents", "metadatas"])
+            if device:      # every row goes to the GPU; the rows without a token are dropped below, by its count
+                self.chunk_ids += batch["ids"]
+                self.chunk_texts += batch["documents"]
+                self.chunk_metadatas += batch["metadatas"]
+                offset += batch_size
+                continue
             for chunk_id, text, metadata in zip(batch["ids"], batch["documents"], batch["metadatas"]):
                 if not text or not text.strip():
                     continue
@@ -299,10 +362,15 @@ class ChunkBM25Index(_Bm25Base):
                 self.chunk_metadatas.append(metadata)
                 self.corpus_tokens.append(tokens)
             offset += batch_size
+        model = None
+        if device:
+            kept, model = self._device_build(self.chunk_texts)
+            self.chunk_ids, self.chunk_texts, self.chunk_metadatas = ([col[i] for i in kept.tolist()] for col in
+                                                                      (self.chunk_ids, self.chunk_texts, self.chunk_metadatas))
         paths = [(m or {}).get("document_path", "") for m in self.chunk_metadatas]
         self._group_of = dict(zip(dict.fromkeys(paths), range(len(paths))))
         groups = np.fromiter(map(self._group_of.__getitem__, paths), dtype=np.int32, count=len(paths))
-        self._install(groups, len(self._group_of))
+        self._install(groups, len(self._group_of), model)
         logger.info("BM25 chunk index: %d chunks", len(self.chunk_ids))
 
     def _allow_bits(self, doc_filter: Set[str]):
