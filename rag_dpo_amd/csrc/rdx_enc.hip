@@ -3,9 +3,6 @@
 // rdx_rerank_select_batch).
 #include "rdx_host.hpp"
 
-#include <mutex>
-#include <unordered_map>
-
 #include "enc_kernels.hpp"
 #include "enc_small.hpp"
 #include "enc_gemm.hpp"
@@ -22,7 +19,7 @@ extern "C" int rdx_enc_attention_f16(int device, const void* qkv, const int32_t*
     if (n_tokens == 0) return RDX_OK;
     if (!qkv || !tok_first || !tok_len || !ctx) return fail(RDX_ERR_INVALID, "rdx_enc_attention_f16: null pointer");
     if (((uintptr_t)qkv | (uintptr_t)ctx) & 15) return fail(RDX_ERR_INVALID, "rdx_enc_attention_f16: qkv and ctx must be 16-byte aligned");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_attention_f16: device out of range");
+    RDX_TRY(check_device_index("rdx_enc_attention_f16", device));
     HIP_TRY(hipSetDevice(device));
     // keys a workgroup stages in LDS: its 64 tokens' texts span at most 64 + 2 (L - 1) tokens when no text is longer than L
     int window = ENC_KEY_WINDOW;
@@ -40,7 +37,7 @@ extern "C" int rdx_enc_attention_mfma_f16(int device, const void* qkv, const int
     if (n_blocks == 0) return RDX_OK;
     if (!qkv || !query_blocks || !ctx) return fail(RDX_ERR_INVALID, "rdx_enc_attention_mfma_f16: null pointer");
     if (((uintptr_t)qkv | (uintptr_t)ctx | (uintptr_t)query_blocks) & 15) return fail(RDX_ERR_INVALID, "rdx_enc_attention_mfma_f16: pointers must be 16-byte aligned");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_attention_mfma_f16: device out of range");
+    RDX_TRY(check_device_index("rdx_enc_attention_mfma_f16", device));
     HIP_TRY(hipSetDevice(device));
     hipLaunchKernelGGL(k_enc_attention_mfma, dim3((unsigned)n_blocks, (unsigned)heads), dim3(256), 0, (hipStream_t)stream, (const _Float16*)qkv, query_blocks, heads,
                        scale * 1.4426950408889634f, (_Float16*)ctx);
@@ -75,7 +72,7 @@ extern "C" int rdx_enc_linear_small_f16(int device, const void* x, const void* w
     if (n_tokens == 0) return RDX_OK;
     if (!x || !w || !bias || !out) return fail(RDX_ERR_INVALID, "rdx_enc_linear_small_f16: null pointer");
     if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)out) & 15) return fail(RDX_ERR_INVALID, "rdx_enc_linear_small_f16: x, w and out must be 16-byte aligned");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_linear_small_f16: device out of range");
+    RDX_TRY(check_device_index("rdx_enc_linear_small_f16", device));
     HIP_TRY(hipSetDevice(device));
     int ntb = 1;
     while (ntb * 16 < n_tokens) ntb *= 2;
@@ -93,7 +90,7 @@ extern "C" int rdx_enc_add_layernorm_f16(int device, const void* a, const void* 
     if (!a || !b || !gamma || !beta || !out) return fail(RDX_ERR_INVALID, "rdx_enc_add_layernorm_f16: null pointer");
     if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out) & 15)
         return fail(RDX_ERR_INVALID, "rdx_enc_add_layernorm_f16: pointers must be 16-byte aligned");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_add_layernorm_f16: device out of range");
+    RDX_TRY(check_device_index("rdx_enc_add_layernorm_f16", device));
     HIP_TRY(hipSetDevice(device));
     const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
@@ -119,7 +116,7 @@ extern "C" int rdx_enc_layernorm_f16(int device, const void* s, const void* gamm
     if (!s || !gamma || !beta || !out) return fail(RDX_ERR_INVALID, "rdx_enc_layernorm_f16: null pointer");
     if (((uintptr_t)s | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out) & 15)
         return fail(RDX_ERR_INVALID, "rdx_enc_layernorm_f16: pointers must be 16-byte aligned");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_layernorm_f16: device out of range");
+    RDX_TRY(check_device_index("rdx_enc_layernorm_f16", device));
     HIP_TRY(hipSetDevice(device));
     const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
@@ -161,7 +158,7 @@ extern "C" int rdx_enc_gemm_f16(int device, const void* x, const void* w, const 
     if (!x || !w || !bias || !out) return fail(RDX_ERR_INVALID, "rdx_enc_gemm_f16: null pointer");
     if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)bias | (uintptr_t)res | (uintptr_t)out) & 15)
         return fail(RDX_ERR_INVALID, "rdx_enc_gemm_f16: pointers must be 16-byte aligned");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_gemm_f16: device out of range");
+    RDX_TRY(check_device_index("rdx_enc_gemm_f16", device));
     HIP_TRY(hipSetDevice(device));
     EncGemm a;
     a.x = (const _Float16*)x;
@@ -179,25 +176,11 @@ extern "C" int rdx_enc_gemm_f16(int device, const void* x, const void* w, const 
 }
 
 // ---- the single-question forward: E4..E7 (enc_small.hpp) ----------------------------------------------------------------------
-// kernels with more than 64 KiB of dynamic LDS need the limit raised once per kernel and device
-static std::mutex g_enc_attr_mu;
-static std::unordered_map<const void*, size_t>* const g_enc_attr = new std::unordered_map<const void*, size_t>[64];
-static int enc_dynamic_lds(int device, const void* func, size_t bytes) {
-    if (bytes <= 65536) return RDX_OK;
-    std::lock_guard<std::mutex> lk(g_enc_attr_mu);
-    size_t& have = g_enc_attr[device][func];
-    if (have < bytes) {
-        HIP_TRY(hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-        have = bytes;
-    }
-    return RDX_OK;
-}
-
 template <int NTB, int KCS, int NPH, int FPB, bool LNPRO, int EPI>
 static int launch_enc_stage(int device, const EncStage& a, hipStream_t st) {
     const size_t lds = (size_t)NTB * 16384 + (size_t)NTB * 16 * KCS * 512 * 2;
     auto* fn = k_enc_stage<NTB, KCS, NPH, FPB, LNPRO, EPI>;
-    RDX_TRY(enc_dynamic_lds(device, (const void*)fn, lds));
+    RDX_TRY(dynamic_lds(device, (const void*)fn, lds));
     hipLaunchKernelGGL(fn, dim3((unsigned)(a.N / FPB)), dim3(1024), lds, st, a);
     HIP_TRY(hipGetLastError());
     return RDX_OK;
@@ -241,7 +224,7 @@ extern "C" int rdx_enc_stage_f16(int device, const void* x, const int64_t* x_row
     if (!x || !w || !bias || !out) return fail(RDX_ERR_INVALID, "rdx_enc_stage_f16: null pointer");
     if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)out | (uintptr_t)y_out | (uintptr_t)ln_gamma | (uintptr_t)ln_beta) & 15)
         return fail(RDX_ERR_INVALID, "rdx_enc_stage_f16: pointers must be 16-byte aligned");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_stage_f16: device out of range");
+    RDX_TRY(check_device_index("rdx_enc_stage_f16", device));
     HIP_TRY(hipSetDevice(device));
     EncStage a;
     a.x = (const _Float16*)x;
@@ -276,7 +259,7 @@ extern "C" int rdx_enc_attention_small_f16(int device, const void* qkv, const in
     if (n_tokens == 0) return RDX_OK;
     if (!qkv || !tok_first || !ctx) return fail(RDX_ERR_INVALID, "rdx_enc_attention_small_f16: null pointer");
     if (((uintptr_t)qkv | (uintptr_t)ctx) & 15) return fail(RDX_ERR_INVALID, "rdx_enc_attention_small_f16: qkv and ctx must be 16-byte aligned");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_attention_small_f16: device out of range");
+    RDX_TRY(check_device_index("rdx_enc_attention_small_f16", device));
     HIP_TRY(hipSetDevice(device));
     const float sl2 = scale * 1.4426950408889634f;
     if (n_tokens <= 16)
@@ -293,7 +276,7 @@ extern "C" int rdx_enc_embed_f16(int device, const int64_t* tok, const int64_t* 
     if (n_tokens == 0) return RDX_OK;
     if (!tok || !pos_id || !word || !pos || !type0 || !out) return fail(RDX_ERR_INVALID, "rdx_enc_embed_f16: null pointer");
     if (((uintptr_t)word | (uintptr_t)pos | (uintptr_t)type0 | (uintptr_t)out) & 15) return fail(RDX_ERR_INVALID, "rdx_enc_embed_f16: pointers must be 16-byte aligned");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_embed_f16: device out of range");
+    RDX_TRY(check_device_index("rdx_enc_embed_f16", device));
     HIP_TRY(hipSetDevice(device));
     const dim3 grid((unsigned)((n_tokens + 3) / 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
@@ -314,7 +297,7 @@ extern "C" int rdx_enc_layernorm_rows_f16(int device, const void* s, const void*
     if (rows == 0) return RDX_OK;
     if (!s || !gamma || !beta || !out) return fail(RDX_ERR_INVALID, "rdx_enc_layernorm_rows_f16: null pointer");
     if (((uintptr_t)s | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out) & 15) return fail(RDX_ERR_INVALID, "rdx_enc_layernorm_rows_f16: pointers must be 16-byte aligned");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_layernorm_rows_f16: device out of range");
+    RDX_TRY(check_device_index("rdx_enc_layernorm_rows_f16", device));
     HIP_TRY(hipSetDevice(device));
     const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
@@ -333,7 +316,7 @@ extern "C" int rdx_enc_gelu_f16(int device, void* x, int64_t n, void* stream) {
     if (n < 0 || n % 8) return fail(RDX_ERR_INVALID, "rdx_enc_gelu_f16: n must be a non-negative multiple of 8");
     if (n == 0) return RDX_OK;
     if (!x || ((uintptr_t)x & 15)) return fail(RDX_ERR_INVALID, "rdx_enc_gelu_f16: x must be a 16-byte aligned device pointer");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_enc_gelu_f16: device out of range");
+    RDX_TRY(check_device_index("rdx_enc_gelu_f16", device));
     HIP_TRY(hipSetDevice(device));
     const int64_t n8 = n / 8;
     const unsigned grid = (unsigned)std::min<int64_t>((n8 + 255) / 256, 2048);
@@ -356,7 +339,7 @@ static int launch_rerank_head(const char* fn, int64_t max_n, const char* range, 
     if (((uintptr_t)cls | (uintptr_t)w_dense) & 15) return fail(RDX_ERR_INVALID, f + ": cls and w_dense must be 16-byte aligned");
     if (((uintptr_t)b_dense | (uintptr_t)w_out | (uintptr_t)b_out) & 1 || ((uintptr_t)workspace & 7) || ((uintptr_t)scores & 3))
         return fail(RDX_ERR_INVALID, f + ": misaligned pointer");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, f + ": device out of range");
+    RDX_TRY(check_device_index(fn, device));
     HIP_TRY(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
     // workgroup (b, y) takes rows [64 y, 64 y + 64) whatever n is, and row r's partials lie at part[b * n + r] (size_t: 2^29 words at
@@ -365,7 +348,7 @@ static int launch_rerank_head(const char* fn, int64_t max_n, const char* range, 
     const int blocks = hidden / RERANK_FEATURES;
     const dim3 grid((unsigned)blocks, (unsigned)((rows + RERANK_ROWS_PER_BLOCK - 1) / RERANK_ROWS_PER_BLOCK));   // y <= 2^14
     const size_t lds = (size_t)RERANK_FEATURES * hidden * sizeof(_Float16);   // <= 64 KiB at hidden 4096
-    RDX_TRY(enc_dynamic_lds(device, (const void*)k_rerank_head, lds));
+    RDX_TRY(dynamic_lds(device, (const void*)k_rerank_head, lds));
     hipLaunchKernelGGL(k_rerank_head, grid, dim3(RERANK_HEAD_THREADS), lds, st, cls, rows, hidden, (const _Float16*)w_dense,
                        (const _Float16*)b_dense, (const _Float16*)w_out, workspace);
     HIP_TRY(hipGetLastError());
@@ -392,7 +375,7 @@ static int check_select_args(const char* fn, const float* scores, const double* 
     if (((uintptr_t)scores & 3) || ((uintptr_t)boosts & 7) || ((uintptr_t)order & 3) || ((uintptr_t)final_score & 7) || ((uintptr_t)count & 3) ||
         ((uintptr_t)boosted & 3))
         return fail(RDX_ERR_INVALID, f + ": misaligned pointer");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, f + ": device out of range");
+    RDX_TRY(check_device_index(fn, device));
     return RDX_OK;
 }
 
@@ -418,7 +401,7 @@ static int check_topic_pointers(const char* fn, const float* table, const int32_
     if ((((uintptr_t)table | (uintptr_t)topic_slots | (uintptr_t)tag_slots | (uintptr_t)pairs) & 3) || ((uintptr_t)offsets & (offsets_bytes - 1)) ||
         (((uintptr_t)sims | (uintptr_t)boosts | (uintptr_t)best_sim) & 7))
         return fail(RDX_ERR_INVALID, std::string(fn) + ": misaligned pointer");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, std::string(fn) + ": device out of range");
+    RDX_TRY(check_device_index(fn, device));
     return RDX_OK;
 }
 

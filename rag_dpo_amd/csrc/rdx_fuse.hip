@@ -100,7 +100,7 @@ extern "C" int rdx_fuse_rankings(int device, int64_t nq, int n_lists, int list_s
                                  double* out_hybrid, int32_t* out_list, int32_t* out_rank, int32_t* out_count, int space,
                                  void* stream) {
     RDX_TRY(check_space(space));
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_fuse_rankings: device out of range");
+    RDX_TRY(check_device_index("rdx_fuse_rankings", device));
     if (nq < 0 || nq > (int64_t)1 << 24) return fail(RDX_ERR_INVALID, "rdx_fuse_rankings: nq must be in [0, 2^24]");
     if (n_lists < 1 || n_lists > FUSE_MAX_LISTS) return fail(RDX_ERR_INVALID, "rdx_fuse_rankings: n_lists must be in [1, 16]");
     if (list_stride < 1 || list_stride > FUSE_MAX_LIST_ENTRIES)

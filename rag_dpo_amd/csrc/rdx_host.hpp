@@ -1,8 +1,9 @@
 // rdx_host.hpp — what the host units of librdx (rdx_index.hip, rdx_enc.hip, rdx_bm25.hip, rdx_docs.hip, rdx_meta.hip) share: the error
-// string behind rdx_last_error(), the checks of `space` and `device`, the device / pinned buffers, and the wait on a word in pinned
-// memory. What only the row-filter stores share (rdx_docs.hip, rdx_meta.hip) is in rdx_store.hpp.
+// string behind rdx_last_error(), the checks of `space` and `device`, the device / pinned buffers, the dynamic-LDS limit of a kernel,
+// and the wait on a word in pinned memory. What only the row-filter stores share (rdx_docs.hip, rdx_meta.hip) is in rdx_store.hpp.
 #pragma once
 #include "../../include/rdx.h"
+#include "rdx_limits.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -11,8 +12,10 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <sched.h>
 
 #include <immintrin.h>
@@ -60,10 +63,24 @@ RDX_HOST_SHARED int check_device(const char* prefix, int device) {
     return RDX_OK;
 }
 
-// grow-only device buffer
+// the `device` argument of an entry point that keeps state per device (tables of rdx::MAX_DEVICES entries); who = the entry point
+RDX_HOST_SHARED int check_device_index(const char* who, int device) {
+    if (device < 0 || device >= rdx::MAX_DEVICES) return fail(RDX_ERR_INVALID, std::string(who) + ": device out of range");
+    return RDX_OK;
+}
+
+// owning device buffer: grow-only scratch (ensure), or an allocation of exactly the size asked for (alloc) that a caller fills
+// and then moves into place
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    hipError_t alloc(size_t need) {   // what it held is freed first
+        release();
+        const hipError_t e = hipMalloc(&p, need);
+        if (e != hipSuccess) p = nullptr;
+        else bytes = need;
+        return e;
+    }
     int ensure(size_t need) {
         if (need <= bytes) return RDX_OK;
         if (p) (void)hipFree(p);
@@ -92,6 +109,12 @@ struct DevBuf {
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {   // (o takes what this held, and frees it when it goes)
+        std::swap(p, o.p);
+        std::swap(bytes, o.bytes);
+        return *this;
+    }
     ~DevBuf() { release(); }   // error paths that return early do not leak scratch
 };
 
@@ -137,18 +160,56 @@ RDX_HOST_SHARED int grow_keep(DevBuf& b, size_t keep, size_t need, const char* w
 }
 
 // zeroed pinned host memory the device reaches over PCIe: its host address and the device's address of the same bytes
-RDX_HOST_SHARED int map_pinned(size_t bytes, void** host, void** dev) {
-    void* p = nullptr;
-    HIP_TRY(hipHostMalloc(&p, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(p, 0, bytes);
-    void* d = nullptr;
-    hipError_t e = hipHostGetDevicePointer(&d, p, 0);
-    if (e != hipSuccess) {
-        (void)hipHostFree(p);
-        return fail(RDX_ERR_HIP, std::string("hipHostGetDevicePointer: ") + hipGetErrorString(e));
+template <class T>
+struct MappedPin {
+    T* host = nullptr;
+    T* dev = nullptr;
+    int map(size_t bytes) {
+        void* p = nullptr;
+        HIP_TRY(hipHostMalloc(&p, bytes, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(p, 0, bytes);
+        void* d = nullptr;
+        hipError_t e = hipHostGetDevicePointer(&d, p, 0);
+        if (e != hipSuccess) {
+            (void)hipHostFree(p);
+            return fail(RDX_ERR_HIP, std::string("hipHostGetDevicePointer: ") + hipGetErrorString(e));
+        }
+        host = static_cast<T*>(p);
+        dev = static_cast<T*>(d);
+        return RDX_OK;
     }
-    *host = p;
-    *dev = d;
+    MappedPin() = default;
+    MappedPin(const MappedPin&) = delete;
+    MappedPin& operator=(const MappedPin&) = delete;
+    ~MappedPin() {
+        if (host) (void)hipHostFree(host);
+    }
+};
+
+// Kernels that use more than 64 KiB of dynamic LDS need the limit raised, once per kernel and device and again when the need
+// grows. The limits already raised on a device are a table that is replaced, never changed: a launch reads the current one
+// without a lock (one lookup); whoever has to raise a limit takes the lock, sets the kernel's attribute and publishes a copy. (The
+// tables it replaces are left standing for their readers: a handful per kernel in the life of a process.)
+using LdsLimits = std::unordered_map<const void*, size_t>;
+RDX_HOST_SHARED std::atomic<const LdsLimits*> g_lds_limits[rdx::MAX_DEVICES];
+RDX_HOST_SHARED std::mutex g_lds_limits_mu;
+
+RDX_HOST_SHARED int dynamic_lds(int device, const void* func, size_t bytes) {
+    if (bytes <= 65536) return RDX_OK;
+    RDX_TRY(check_device_index("dynamic_lds", device));
+    const auto raised = [&](const LdsLimits* t) {
+        if (!t) return false;
+        const auto it = t->find(func);
+        return it != t->end() && it->second >= bytes;
+    };
+    if (raised(g_lds_limits[device].load(std::memory_order_acquire))) return RDX_OK;
+    std::lock_guard<std::mutex> lk(g_lds_limits_mu);
+    const LdsLimits* cur = g_lds_limits[device].load(std::memory_order_acquire);
+    if (raised(cur)) return RDX_OK;
+    HIP_TRY(hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    LdsLimits* next = cur ? new LdsLimits(*cur) : new LdsLimits();
+    (*next)[func] = bytes;
+    g_lds_limits[device].store(next, std::memory_order_release);
     return RDX_OK;
 }
 

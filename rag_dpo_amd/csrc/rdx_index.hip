@@ -5,10 +5,11 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
+#include <memory>
 #include <mutex>
-#include <unordered_map>
 #include <vector>
 
+#include "index_state.hpp"
 #include "k_rows.hpp"
 #include "refine_kernel.hpp"
 #include "scan_kernel.hpp"
@@ -50,17 +51,63 @@ struct PendingSearch {
 // ------------------------------------------------------------------------------------------------
 // the index: one corpus shard resident in one GPU's HBM
 // ------------------------------------------------------------------------------------------------
+// The rows, allocated for `cap` of them (a multiple of 256; the policy: index_state.hpp). grow() and rdx_index_compact() fill a
+// fresh store and move it into place once everything enqueued on it has run: leaving early frees the fresh one, and the index
+// stands as it was.
+struct RowStore {
+    int compact = 0;   // option "compact_master" (settable while the index is empty): 4 instead of 6 B/element
+    int64_t cap = 0;
+    DevBuf master;     // [cap][dim] normalised fp32 rows (default), or none with compact_master:
+    DevBuf raw16;      //   [cap][dim] raw bf16 rows as delivered ...
+    DevBuf den;        //   [cap] ... and their divisors max(|x|, 1e-12); k_rows.hpp MasterView
+    DevBuf shadow;     // [cap][dim_pad] fp16 scan copy in MFMA fragment order (rdx_common.hpp corpus_off)
+    DevBuf row_map;    // [cap] local row -> returned row id (strictly increasing), or none = local + row_base
+
+    MasterView mv() const { return MasterView{master.as<float>(), raw16.as<uint16_t>(), den.as<double>()}; }
+    const int64_t* ids() const { return row_map.as<int64_t>(); }
+    // master (in this store's mode) and shadow for ncap rows; all or nothing
+    hipError_t alloc_rows(int64_t ncap, int dim, int dim_pad) {
+        hipError_t e = compact ? raw16.alloc((size_t)ncap * dim * 2) : master.alloc((size_t)ncap * dim * 4);
+        if (e == hipSuccess && compact) e = den.alloc((size_t)ncap * 8);
+        if (e == hipSuccess) e = shadow.alloc((size_t)ncap * dim_pad * 2);
+        if (e != hipSuccess)
+            for (DevBuf* b : {&master, &raw16, &den, &shadow}) b->release();
+        cap = e == hipSuccess ? ncap : 0;
+        return e;
+    }
+    hipError_t alloc_ids() { return row_map.alloc((size_t)std::max<int64_t>(cap, 256) * 8); }
+};
+
+// The int8 coarse pass's copy of the corpus, built by the first search that takes the path and brought up to date by every later
+// one (prepare_i8); not persisted. Which rows of it are current is the watermark's to say (index_state.hpp).
+struct I8Copy {
+    DevBuf c8;      // [cap][dim_pad] in corpus_off8 order
+    DevBuf sblk;    // s_b per 32-row block
+    DevBuf eps8;    // the largest eps_b
+    // the classes of block error: eps_b per block, the EPS_CLASSES - 1 stored edges (taken at a full quantisation), a class byte per block
+    DevBuf epsb, edge8, cls8;
+    I8Watermark mark;
+
+    // room for cap rows; a buffer that had to be allocated anew lost its contents, and the watermark is told
+    int ensure(int64_t cap, int dim_pad) {
+        const size_t need[6] = {(size_t)cap * dim_pad, (size_t)(cap / 32) * 4, 4, (size_t)(cap / 32) * 4, (size_t)EPS_CLASSES * 4,
+                                (size_t)(cap / 32 + 3) / 4 * 4};   // (cls8: k_scan<I8> reads whole dwords)
+        DevBuf* const buf[6] = {&c8, &sblk, &eps8, &epsb, &edge8, &cls8};
+        for (int i = 0; i < 6; ++i) {
+            const void* was = buf[i]->p;
+            RDX_TRY(buf[i]->ensure(need[i]));
+            if (buf[i]->p != was) mark.reallocated();
+        }
+        return RDX_OK;
+    }
+};
+
 struct rdx_index {
     int device = 0;
     int dim = 0, dim_pad = 0, ksteps = 0, scale_log2 = 0;
     int n_cu = 256;
-    int64_t rows = 0, cap = 0;   // cap is a multiple of 256
-    float* master = nullptr;     // [cap][dim] normalised fp32 rows (default), or NULL with option compact_master:
-    uint16_t* raw16 = nullptr;   //   [cap][dim] raw bf16 rows as delivered ...
-    double* den = nullptr;       //   [cap] ... and their divisors max(|x|, 1e-12); k_rows.hpp MasterView
-    int compact = 0;             // option "compact_master" (settable while the index is empty): 4 instead of 6 B/element
-    MasterView mv() const { return MasterView{master, raw16, den}; }
-    _Float16* shadow = nullptr;  // [cap][dim_pad] fp16 scan copy in MFMA fragment order (rdx_common.hpp corpus_off)
+    int64_t rows = 0;
+    RowStore store;
     hipStream_t own_stream = nullptr;
     std::mutex mu;
 
@@ -69,33 +116,27 @@ struct rdx_index {
     SearchAdapt adapt;      // what finished searches feed back
     int coarse_bits = 0;    // the last search's coarse pass: 16, 8, or 0 (exact path only); rdx_search_last_coarse_bits
     int64_t row_base = 0;   // added to every returned row id (global ids of a shard)
-    int64_t* row_map = nullptr;   // [cap] local row -> returned row id (strictly increasing), or NULL = local + row_base
 
     // scratch (grow-only; never allocated inside a warmed-up search)
     DevBuf r_list, r_q, r_s, r_r, r_c;   // second-chance batch of overflowed queries
     DevBuf wgt;                          // [grid][2] workgroup time stamps of the main scan
-    std::unordered_map<const void*, size_t> func_lds;   // dynamic-LDS limit already raised for a kernel ON THIS DEVICE
     DevBuf staging, qraw, qhat, qshadow, tau, cntw, cand, setmax, exact_list, iota, dense, ctr, bad, o_score, o_row,
         o_count, mask, ids;
-    // int8 coarse pass: corpus copy [cap][dim_pad] in corpus_off8 order + s_b per 32-row block + the largest eps_b (built by the first
-    // search that takes the path, rows [0, i8_valid) current; not persisted) and the per-search query copy, scales, bounds, thresholds
-    DevBuf c8, sblk, eps8, qshadow8, tq8, eq8, nq8, thr8, taus8, twoe8;
-    // ... and the classes of block error: eps_b per block, the EPS_CLASSES - 1 stored edges (taken at a full quantisation), a class byte per block
-    DevBuf epsb, edge8, cls8;
+    I8Copy i8;
+    // the int8 pass's per-search query copy, scales, bounds, thresholds (nothing of it outlives a search)
+    DevBuf qshadow8, tq8, eq8, nq8, thr8, taus8, twoe8;
     DevBuf spill;            // k_refine<true>: [nq_pad][spill_cap] hit lists of the queries that outgrow the LDS list (first spilling plan)
-    int64_t i8_valid = 0;
     // end-of-search mailbox in pinned host memory (k_finish writes it over PCIe; the host spins on its sequence number)
-    Mailbox* mbox = nullptr;          // host address
-    Mailbox* mbox_dev = nullptr;      // the same memory as the device sees it
+    MappedPin<Mailbox> mbox;
     unsigned long long seq = 0;       // number of the last search enqueued on this index
-    char* pin_out = nullptr;          // pinned staging for the small results of host callers (score | row | count)
-    char* pin_out_dev = nullptr;
+    MappedPin<char> pin_out;          // pinned staging for the small results of host callers (score | row | count)
     bool ctr_ready = false;           // the counter block was zeroed once; afterwards every k_finish re-zeroes it
     PendingSearch pending;            // rdx_search_async: the search whose host half is still to run
     hipEvent_t ev[8] = {};
     bool ev_ok = false;
     rdx_search_stats stats = {};
 
+    MasterView mv() const { return store.mv(); }
     float scale() const { return std::ldexp(1.0f, scale_log2); }
     float two_e() const { return 2.0f * (1.0e-3f + 2.5e-7f * (float)dim_pad); }   // see DESIGN.md "error bound"
     PlanShape shape() const { return PlanShape{rows, dim_pad, ksteps, n_cu, two_e()}; }
@@ -111,115 +152,56 @@ struct rdx_mask {
 // a pinned, device-visible word the merge kernel publishes ((sequence << 1) | value) and the host waits on
 struct rdx_signal {
     int device = 0;
-    unsigned long long* host = nullptr;
-    unsigned long long* dev = nullptr;
+    MappedPin<unsigned long long> word;
     unsigned long long seq = 0;   // number of the last merge that was given this signal
 };
-
-static size_t shadow_bytes(const rdx_index* h, int64_t cap) { return (size_t)cap * h->dim_pad * 2; }
 
 static int set_device(const rdx_index* h) {
     HIP_TRY(hipSetDevice(h->device));
     return RDX_OK;
 }
 
-static void free_master(float* m, uint16_t* r, double* d) {
-    if (m) (void)hipFree(m);
-    if (r) (void)hipFree(r);
-    if (d) (void)hipFree(d);
-}
-
-// master storage for `cap` rows in the index's mode
-static hipError_t alloc_master(const rdx_index* h, int64_t cap, float** m, uint16_t** r, double** d) {
-    *m = nullptr;
-    *r = nullptr;
-    *d = nullptr;
-    if (!h->compact) return hipMalloc((void**)m, (size_t)cap * h->dim * 4);
-    hipError_t e = hipMalloc((void**)r, (size_t)cap * h->dim * 2);
-    if (e == hipSuccess) e = hipMalloc((void**)d, (size_t)cap * 8);
-    if (e != hipSuccess) {
-        free_master(nullptr, *r, *d);
-        *r = nullptr;
-        *d = nullptr;
-    }
-    return e;
-}
-
 static int grow(rdx_index* h, int64_t need_rows) {
-    if (need_rows <= h->cap) return RDX_OK;
-    int64_t ncap = std::max<int64_t>(need_rows, h->cap + h->cap / 2);
-    ncap = (ncap + 255) / 256 * 256;
-    float* nm = nullptr;
-    uint16_t* nr16 = nullptr;
-    double* nd = nullptr;
-    _Float16* ns = nullptr;
-    hipError_t e = alloc_master(h, ncap, &nm, &nr16, &nd);
-    if (e == hipSuccess) e = hipMalloc((void**)&ns, shadow_bytes(h, ncap));
-    if (e != hipSuccess && ncap > (need_rows + 255) / 256 * 256) {   // retry without head-room
-        free_master(nm, nr16, nd);
-        ncap = (need_rows + 255) / 256 * 256;
-        e = alloc_master(h, ncap, &nm, &nr16, &nd);
-        if (e == hipSuccess) e = hipMalloc((void**)&ns, shadow_bytes(h, ncap));
-    }
-    if (e != hipSuccess) {
-        free_master(nm, nr16, nd);
-        return fail(RDX_ERR_NOMEM, std::string("growing index to ") + std::to_string(ncap) + " rows: " + hipGetErrorString(e));
-    }
+    const RowStore& old = h->store;
+    const GrowCaps caps = grow_caps(old.cap, need_rows);
+    if (caps.roomy == old.cap) return RDX_OK;
+    RowStore ns;
+    ns.compact = old.compact;
+    int64_t ncap = caps.roomy;
+    hipError_t e = ns.alloc_rows(ncap, h->dim, h->dim_pad);
+    if (e != hipSuccess && caps.tight < caps.roomy) e = ns.alloc_rows(ncap = caps.tight, h->dim, h->dim_pad);   // retry without head-room
+    if (e != hipSuccess) return fail(RDX_ERR_NOMEM, std::string("growing index to ") + std::to_string(ncap) + " rows: " + hipGetErrorString(e));
     hipStream_t st = h->own_stream;
-    int64_t* nr = nullptr;
-    if (h->row_map) {   // the id map grows with the rows: old entries kept, new ones start as local + row_base
-        e = hipMalloc((void**)&nr, (size_t)ncap * 8);
-        if (e != hipSuccess) {
-            free_master(nm, nr16, nd);
-            (void)hipFree(ns);
-            return fail(RDX_ERR_NOMEM, std::string("growing the row id map: ") + hipGetErrorString(e));
-        }
-        if (h->rows > 0) HIP_TRY(hipMemcpyAsync(nr, h->row_map, (size_t)h->rows * 8, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(k_iota64, dim3((unsigned)((ncap - h->rows + 255) / 256)), dim3(256), 0, st, nr, h->rows, ncap - h->rows, h->row_base);
+    if (old.row_map.p) {   // the id map grows with the rows: old entries kept, new ones start as local + row_base
+        e = ns.alloc_ids();
+        if (e != hipSuccess) return fail(RDX_ERR_NOMEM, std::string("growing the row id map: ") + hipGetErrorString(e));
+        if (h->rows > 0) HIP_TRY(hipMemcpyAsync(ns.row_map.p, old.row_map.p, (size_t)h->rows * 8, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(k_iota64, dim3((unsigned)((ncap - h->rows + 255) / 256)), dim3(256), 0, st, ns.row_map.as<int64_t>(), h->rows, ncap - h->rows, h->row_base);
     }
-    HIP_TRY(hipMemsetAsync(ns, 0, shadow_bytes(h, ncap), st));
+    HIP_TRY(hipMemsetAsync(ns.shadow.p, 0, ns.shadow.bytes, st));
     if (h->rows > 0) {
-        if (h->compact) {
-            HIP_TRY(hipMemcpyAsync(nr16, h->raw16, (size_t)h->rows * h->dim * 2, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemcpyAsync(nd, h->den, (size_t)h->rows * 8, hipMemcpyDeviceToDevice, st));
+        if (old.compact) {
+            HIP_TRY(hipMemcpyAsync(ns.raw16.p, old.raw16.p, (size_t)h->rows * h->dim * 2, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ns.den.p, old.den.p, (size_t)h->rows * 8, hipMemcpyDeviceToDevice, st));
         } else {
-            HIP_TRY(hipMemcpyAsync(nm, h->master, (size_t)h->rows * h->dim * 4, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ns.master.p, old.master.p, (size_t)h->rows * h->dim * 4, hipMemcpyDeviceToDevice, st));
         }
-        HIP_TRY(hipMemcpyAsync(ns, h->shadow, shadow_bytes(h, h->cap), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ns.shadow.p, old.shadow.p, old.shadow.bytes, hipMemcpyDeviceToDevice, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
-    free_master(h->master, h->raw16, h->den);
-    if (h->shadow) (void)hipFree(h->shadow);
-    if (h->row_map) (void)hipFree(h->row_map);
-    h->master = nm;
-    h->raw16 = nr16;
-    h->den = nd;
-    h->shadow = ns;
-    h->row_map = nr;
-    h->cap = ncap;
+    h->store = std::move(ns);   // (ns leaves with the old arrays)
     return RDX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
 // search: plan, enqueue, complete — ahead of the lifecycle because every call that writes to the index runs finish_pending first
 // ------------------------------------------------------------------------------------------------
-// kernels using more than 64 KiB of dynamic LDS need the limit raised once per kernel and device (the attribute is
-// per device: the cache lives in the index, which is bound to one)
-static int ensure_dynamic_lds(rdx_index* h, const void* func, size_t bytes) {
-    size_t& have = h->func_lds[func];
-    if (have < bytes) {
-        HIP_TRY(hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-        have = bytes;
-    }
-    return RDX_OK;
-}
-
 template <int BN, int EPI, bool RES, bool NTT = false, bool FUSED = false, bool I8 = false>
 static int launch_scan(rdx_index* h, const ScanParams& p, int grid, hipStream_t st) {
     // LDS: query-image ring (or the whole resident query tile) + BN hit counters + BN thresholds
     const size_t lds = (size_t)(RES ? p.ksteps : RING_SLOTS) * BN * BK * 2 + BN * (I8 ? 8 + 4 * p.ncls : 8);   // (I8: BN query scales, a table per class)
     void (*kern)(const ScanParams) = p.allow ? k_scan<BN, EPI, true, RES, NTT, FUSED, I8> : k_scan<BN, EPI, false, RES, NTT, FUSED, I8>;
-    RDX_TRY(ensure_dynamic_lds(h, (const void*)kern, lds));
+    RDX_TRY(dynamic_lds(h->device, (const void*)kern, lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, p);
     HIP_TRY(hipGetLastError());
     return RDX_OK;
@@ -288,7 +270,7 @@ static int run_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, con
             HIP_TRY(hipGetLastError());
         }
         hipLaunchKernelGGL(k_select_dense, dim3(nq), dim3(1024), 0, st, h->dense.as<float>(), h->rows, d_list + j0, k, h->row_base,
-                           h->row_map, d_score, d_row, d_count, t_last, (fin && j0 + QX >= n_list) ? *fin : no_fin);
+                           h->store.ids(), d_score, d_row, d_count, t_last, (fin && j0 + QX >= n_list) ? *fin : no_fin);
         HIP_TRY(hipGetLastError());
     }
     return RDX_OK;
@@ -326,18 +308,18 @@ static void mark(rdx_index* h, const SearchPlan& p, hipStream_t st, int i) {
 static FinishArgs finish_args(const rdx_index* h, const SearchPlan& p, const SearchIO& io, unsigned long long seq) {
     FinishArgs f = {};
     f.ctr = h->ctr.as<RefineCounters>();
-    f.mb = h->mbox_dev;
+    f.mb = h->mbox.dev;
     f.seq = seq;
     f.wgt = p.stamps ? h->wgt.as<unsigned long long>() : nullptr;
     f.n_wgt = p.stamps ? 2 * p.grid : 0;
     f.s0 = reinterpret_cast<const uint32_t*>(io.row);
-    f.d0 = reinterpret_cast<uint32_t*>(h->pin_out_dev);
+    f.d0 = reinterpret_cast<uint32_t*>(h->pin_out.dev);
     f.w0 = (int64_t)(p.ride ? p.b_r / 4 : 0);
     f.s1 = reinterpret_cast<const uint32_t*>(io.score);
-    f.d1 = reinterpret_cast<uint32_t*>(h->pin_out_dev + p.b_r);
+    f.d1 = reinterpret_cast<uint32_t*>(h->pin_out.dev + p.b_r);
     f.w1 = (int64_t)(p.ride ? p.b_s / 4 : 0);
     f.s2 = reinterpret_cast<const uint32_t*>(io.count);
-    f.d2 = reinterpret_cast<uint32_t*>(h->pin_out_dev + p.b_r + p.b_s);
+    f.d2 = reinterpret_cast<uint32_t*>(h->pin_out.dev + p.b_r + p.b_s);
     f.w2 = (int64_t)(p.ride ? p.b_c / 4 : 0);
     f.out_flags = io.flags;
     f.may_redo = (!p.exact_only && p.depth == 0) ? 1 : 0;
@@ -347,7 +329,7 @@ static FinishArgs finish_args(const rdx_index* h, const SearchPlan& p, const Sea
 // the MFMA path of a plan: bootstrap (k_boot or k_scan<EPI_SETMAX>), k_tau, main scan (k_scan_small or k_scan<EPI_EMIT>), k_refine
 static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, hipStream_t st, const FinishArgs& fin) {
     ScanParams sp = {};
-    sp.shadow = h->shadow;
+    sp.shadow = h->store.shadow.as<_Float16>();
     sp.qshadow = h->qshadow.as<_Float16>();
     sp.ksteps = h->ksteps;
     sp.rows = h->rows;
@@ -362,7 +344,7 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
     sp.cand = h->cand.as<uint2>();
     sp.capw = p.capw;
     sp.inv_scale2 = std::ldexp(1.0f, -2 * h->scale_log2);
-    sp.shadow_bytes = (int64_t)shadow_bytes(h, h->cap);
+    sp.shadow_bytes = (int64_t)h->store.shadow.bytes;
     sp.oob = reinterpret_cast<int*>(h->ctr.as<char>() + offsetof(RefineCounters, oob));
     const SplitKParams sk = {sp.shadow, sp.qshadow, sp.ksteps, sp.rows, p.n_blocks32, sp.allow};   // k_boot's and k_scan_small's share
 
@@ -388,8 +370,8 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
     HIP_TRY(hipGetLastError());
     if (p.i8) {
         hipLaunchKernelGGL(k_tau8, dim3((p.nq_pad + 255) / 256), dim3(256), 0, st, h->tau.as<float>(), std::ldexp(1.0f, -2 * h->scale_log2),
-                           h->tq8.as<float>(), h->eq8.as<float>(), h->nq8.as<float>(), h->eps8.as<unsigned int>(), (int)p.nq, p.nq_pad,
-                           h->thr8.as<float>(), h->taus8.as<float>(), h->twoe8.as<float>(), h->edge8.as<float>(), p.eps_classes);
+                           h->tq8.as<float>(), h->eq8.as<float>(), h->nq8.as<float>(), h->i8.eps8.as<unsigned int>(), (int)p.nq, p.nq_pad,
+                           h->thr8.as<float>(), h->taus8.as<float>(), h->twoe8.as<float>(), h->i8.edge8.as<float>(), p.eps_classes);
         HIP_TRY(hipGetLastError());
     }
     mark(h, p, st, 3);
@@ -404,15 +386,15 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
         HIP_TRY(hipGetLastError());
     } else if (p.i8) {
         ScanParams s8 = sp;
-        s8.shadow = reinterpret_cast<const _Float16*>(h->c8.p);
+        s8.shadow = reinterpret_cast<const _Float16*>(h->i8.c8.p);
         s8.qshadow = reinterpret_cast<const _Float16*>(h->qshadow8.p);
         s8.ksteps = h->dim_pad / 128;
         s8.tau = h->thr8.as<float>();
-        s8.sblk = h->sblk.as<float>();
+        s8.sblk = h->i8.sblk.as<float>();
         s8.qscale = h->tq8.as<float>();
-        s8.cls = h->cls8.as<uint32_t>();
+        s8.cls = h->i8.cls8.as<uint32_t>();
         s8.ncls = p.eps_classes;
-        s8.shadow_bytes = (int64_t)h->cap * h->dim_pad;
+        s8.shadow_bytes = (int64_t)h->store.cap * h->dim_pad;
         RDX_TRY(launch_scan_i8(h, p.fused, s8, p.grid, st));
     } else {
         RDX_TRY(launch_scan_bn<EPI_EMIT>(h, p.bn, p.res, p.fused, sp, p.grid, st));
@@ -422,10 +404,10 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
     // on its row of the spill buffer (plans that spill run the instantiation that holds both routes)
     const size_t lds = (size_t)p.list_cap * 8;
     const auto refine = p.spill ? k_refine<true> : k_refine<false>;
-    RDX_TRY(ensure_dynamic_lds(h, (const void*)refine, lds));
+    RDX_TRY(dynamic_lds(h->device, (const void*)refine, lds));
     hipLaunchKernelGGL(refine, dim3((int)p.nq), dim3(1024), lds, st, h->cand.as<uint2>(), h->cntw.as<uint32_t>(), p.n_streams, p.capw,
                        p.list_cap, p.k, h->two_e(), p.i8 ? h->twoe8.as<float>() : nullptr, h->qhat.as<float>(), h->mv(), h->dim, h->row_base,
-                       h->row_map, io.score, io.row, io.count, h->exact_list.as<int32_t>(), h->ctr.as<RefineCounters>(),
+                       h->store.ids(), io.score, io.row, io.count, h->exact_list.as<int32_t>(), h->ctr.as<RefineCounters>(),
                        p.i8 ? h->taus8.as<float>() : h->tau.as<float>(), p.i8 ? 1.0f : sp.inv_scale2, p.pilot, p.spill_cap,
                        p.spill ? h->spill.as<uint2>() : nullptr, fin);
     HIP_TRY(hipGetLastError());
@@ -437,38 +419,25 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
 // reallocation) and quantise the queries (from qhat, which k_refine re-scores with)
 static int prepare_i8(rdx_index* h, const SearchPlan& p, hipStream_t st) {
     const int ks8 = h->dim_pad / 128;
-    const void* old_c8 = h->c8.p;
-    const void* old_sb = h->sblk.p;
-    const void* old_eps = h->eps8.p;
-    const void* old_eb = h->epsb.p;
-    const void* old_ed = h->edge8.p;
-    const void* old_cl = h->cls8.p;
-    RDX_TRY(h->c8.ensure((size_t)h->cap * h->dim_pad));
-    RDX_TRY(h->sblk.ensure((size_t)(h->cap / 32) * 4));
-    RDX_TRY(h->eps8.ensure(4));
-    RDX_TRY(h->epsb.ensure((size_t)(h->cap / 32) * 4));
-    RDX_TRY(h->edge8.ensure((size_t)EPS_CLASSES * 4));
-    RDX_TRY(h->cls8.ensure((size_t)(h->cap / 32 + 3) / 4 * 4));   // (k_scan<I8> reads whole dwords)
-    if (h->c8.p != old_c8 || h->sblk.p != old_sb || h->eps8.p != old_eps || h->epsb.p != old_eb || h->edge8.p != old_ed || h->cls8.p != old_cl)
-        h->i8_valid = 0;   // (a reallocation loses the contents)
-    if (h->i8_valid < h->rows) {
-        const bool full = h->i8_valid == 0;
-        if (full) HIP_TRY(hipMemsetAsync(h->eps8.p, 0, 4, st));
-        const int64_t b0 = h->i8_valid / 32, nb = (h->rows + 31) / 32 - b0;
-        hipLaunchKernelGGL(k_quant8_corpus, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, h->mv(), h->dim, h->rows, b0, nb,
-                           h->c8.as<int8_t>(), ks8, h->sblk.as<float>(), h->eps8.as<unsigned int>(), h->epsb.as<float>());
+    I8Copy& c = h->i8;
+    RDX_TRY(c.ensure(h->store.cap, h->dim_pad));
+    const I8Work w = c.mark.work(h->rows);
+    if (w.nb > 0) {
+        if (w.full) HIP_TRY(hipMemsetAsync(c.eps8.p, 0, 4, st));
+        hipLaunchKernelGGL(k_quant8_corpus, dim3((unsigned)((w.nb + 3) / 4)), dim3(256), 0, st, h->mv(), h->dim, h->rows, w.b0, w.nb,
+                           c.c8.as<int8_t>(), ks8, c.sblk.as<float>(), c.eps8.as<unsigned int>(), c.epsb.as<float>());
         HIP_TRY(hipGetLastError());
         // classes of block error: the edges from the eps_b of a full quantisation (on the stream: no host round trip); what an append
         // quantises is classified against the edges that stand (a block above the last stored edge lands in the top class, whose
         // edge is the running eps_max)
-        if (full) {
-            hipLaunchKernelGGL(k_eps_edges, dim3(EPS_CLASSES - 1), dim3(1024), 0, st, h->epsb.as<float>(), nb, h->edge8.as<float>());
+        if (w.full) {
+            hipLaunchKernelGGL(k_eps_edges, dim3(EPS_CLASSES - 1), dim3(1024), 0, st, c.epsb.as<float>(), w.nb, c.edge8.as<float>());
             HIP_TRY(hipGetLastError());
         }
-        hipLaunchKernelGGL(k_eps_classify, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, h->epsb.as<float>(), b0, nb,
-                           h->edge8.as<float>(), h->cls8.as<uint8_t>());
+        hipLaunchKernelGGL(k_eps_classify, dim3((unsigned)((w.nb + 255) / 256)), dim3(256), 0, st, c.epsb.as<float>(), w.b0, w.nb,
+                           c.edge8.as<float>(), c.cls8.as<uint8_t>());
         HIP_TRY(hipGetLastError());
-        h->i8_valid = h->rows;
+        c.mark.quantised(h->rows);
     }
     RDX_TRY(h->qshadow8.ensure((size_t)p.nq_pad * h->dim_pad));
     for (DevBuf* b : {&h->tq8, &h->eq8, &h->nq8, &h->taus8, &h->twoe8}) RDX_TRY(b->ensure((size_t)p.nq_pad * 4));
@@ -488,8 +457,8 @@ static int enqueue_search(rdx_index* h, const SearchPlan& p, const SearchIO& io,
     static_assert(sizeof(RefineCounters) <= 64, "counter block layout: one 64-byte line");
     RDX_TRY(h->ctr.ensure(sizeof(RefineCounters)));
     RDX_TRY(h->exact_list.ensure((size_t)p.nq_pad * 4));
-    if (!h->mbox) RDX_TRY(map_pinned(sizeof(Mailbox), (void**)&h->mbox, (void**)&h->mbox_dev));
-    if (p.ride && !h->pin_out) RDX_TRY(map_pinned(PIN_MAX, (void**)&h->pin_out, (void**)&h->pin_out_dev));
+    if (!h->mbox.host) RDX_TRY(h->mbox.map(sizeof(Mailbox)));
+    if (p.ride && !h->pin_out.host) RDX_TRY(h->pin_out.map(PIN_MAX));
     if (!p.exact_only) {
         RDX_TRY(h->tau.ensure((size_t)p.nq_pad * 4));
         RDX_TRY(h->cntw.ensure((size_t)p.nq_pad * p.n_streams * 4));
@@ -557,10 +526,10 @@ static void for_stamped(const SearchPlan& p, F f) {
 static int read_mailbox(rdx_index* h, const PendingSearch& ps, SearchCounts* c) {
     const SearchPlan& p = ps.plan;
     if (p.big_copy) HIP_TRY(hipStreamSynchronize(ps.st));   // pageable D2H copies: complete only after a stream synchronise
-    const int rc = wait_word([&] { return __atomic_load_n(&h->mbox->seq, __ATOMIC_ACQUIRE) == ps.seq; }, ps.st);   // the ONE host wait of a search
+    const int rc = wait_word([&] { return __atomic_load_n(&h->mbox.host->seq, __ATOMIC_ACQUIRE) == ps.seq; }, ps.st);   // the ONE host wait of a search
     if (rc == 1) return fail(RDX_ERR_HIP, "internal: the search completed without publishing its mailbox");
     RDX_TRY(rc);
-    const Mailbox& mb = *h->mbox;
+    const Mailbox& mb = *h->mbox.host;
     *c = {mb.emitted, mb.rescored, mb.bad, p.exact_only ? (int)p.nq : mb.n_exact};
     if (p.prof == 3) {
         if (p.exact_only) {
@@ -592,8 +561,8 @@ static void adapt_sampling(rdx_index* h, const SearchPlan& p, const SearchCounts
         --a.i8_backoff;
     }
     if (std::getenv("RDX_DEBUG_HITS"))   // developer (tools/ab_i8_sample.py): the longest hit list of the search and how many queries spilled
-        std::fprintf(stderr, "hits max %d spilled %d\n", h->mbox->max_hits, h->mbox->n_spill);
-    if (h->mbox->spec_fail > 0) a.spec_backoff = 64;   // a speculative threshold was too high: provable thresholds for a while
+        std::fprintf(stderr, "hits max %d spilled %d\n", h->mbox.host->max_hits, h->mbox.host->n_spill);
+    if (h->mbox.host->spec_fail > 0) a.spec_backoff = 64;   // a speculative threshold was too high: provable thresholds for a while
     // three times the candidates a random corpus would emit: the corpus is clustered — a denser threshold sample for the next searches
     // (plan_search; re-examined every 256 searches: the denser sample's own emission is what then keeps it on)
     if (!p.exact_only && p.expected_per_query > 0.0) {
@@ -605,7 +574,7 @@ static void adapt_sampling(rdx_index* h, const SearchPlan& p, const SearchCounts
 
 // the stamps arrived with the counters: re-weight the XCD shares for the next search
 static void reweight_xcds(rdx_index* h, const SearchPlan& p, rdx_search_stats* acc) {
-    const unsigned long long* wt = h->mbox->wg_times;
+    const unsigned long long* wt = h->mbox.host->wg_times;
     double* const xw = h->adapt.xw;
     unsigned long long t0 = ~0ull, tx[8] = {}, lo[8];
     std::fill(lo, lo + 8, ~0ull);
@@ -721,13 +690,13 @@ static int complete_search(rdx_index* h, const PendingSearch& ps, rdx_search_sta
     SearchCounts c;
     RDX_TRY(read_mailbox(h, ps, &c));
     adapt_sampling(h, p, c);
-    if (h->mbox->oob) return fail(RDX_ERR_STATE, "internal: the scan computed a corpus address outside the scan copy (RDX_CHECK_BOUNDS build)");
+    if (h->mbox.host->oob) return fail(RDX_ERR_STATE, "internal: the scan computed a corpus address outside the scan copy (RDX_CHECK_BOUNDS build)");
     if (p.ride) {
         if (p.k > 0) {
-            std::memcpy(ho->row, h->pin_out, p.b_r);
-            std::memcpy(ho->score, h->pin_out + p.b_r, p.b_s);
+            std::memcpy(ho->row, h->pin_out.host, p.b_r);
+            std::memcpy(ho->score, h->pin_out.host + p.b_r, p.b_s);
         }
-        std::memcpy(ho->count, h->pin_out + p.b_r + p.b_s, p.b_c);
+        std::memcpy(ho->count, h->pin_out.host + p.b_r + p.b_s, p.b_c);
     }
     int n_exact = c.n_exact;
     if (!p.exact_only) {
@@ -807,41 +776,29 @@ extern "C" int rdx_index_create(int device, int dim, rdx_index** out) {
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
         return fail(RDX_ERR_STATE, std::string("librdx is built for gfx950 (MI355X) only; device reports ") + prop.gcnArchName);
-    rdx_index* h = new rdx_index();
+    auto h = std::make_unique<rdx_index>();
     h->device = device;
     h->dim = dim;
     h->dim_pad = (dim + 63) / 64 * 64;
     h->ksteps = h->dim_pad / 64;
     h->scale_log2 = (int)std::lround(std::log2(std::sqrt((double)dim)));
     h->n_cu = prop.multiProcessorCount;
-    hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete h;
-        return fail(RDX_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
-    }
-    *out = h;
+    const hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
+    if (e != hipSuccess) return fail(RDX_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+    *out = h.release();
     return RDX_OK;
 }
 
+// Both streams that may still hold work on the index's memory are drained; then the members free what they own.
 extern "C" int rdx_index_destroy(rdx_index* h) {
     if (!h) return RDX_OK;
+    const std::unique_ptr<rdx_index> owner(h);
     (void)hipSetDevice(h->device);
     if (h->pending.active) (void)hipStreamSynchronize(h->pending.st);   // an abandoned asynchronous search: let its kernels finish
     (void)hipStreamSynchronize(h->own_stream);
-    free_master(h->master, h->raw16, h->den);
-    if (h->shadow) (void)hipFree(h->shadow);
-    if (h->row_map) (void)hipFree(h->row_map);
-    for (DevBuf* b : {&h->staging, &h->qraw, &h->qhat, &h->qshadow, &h->tau, &h->cntw, &h->cand, &h->setmax, &h->exact_list, &h->spill,
-                      &h->iota, &h->dense, &h->ctr, &h->bad, &h->o_score, &h->o_row, &h->o_count, &h->mask, &h->ids,
-                      &h->r_list, &h->r_q, &h->r_s, &h->r_r, &h->r_c, &h->c8, &h->sblk, &h->eps8, &h->qshadow8, &h->tq8,
-                      &h->eq8, &h->nq8, &h->thr8, &h->taus8, &h->twoe8, &h->epsb, &h->edge8, &h->cls8})
-        b->release();
-    if (h->mbox) (void)hipHostFree(h->mbox);
-    if (h->pin_out) (void)hipHostFree(h->pin_out);
     if (h->ev_ok)
         for (auto& e : h->ev) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(h->own_stream);
-    delete h;
     return RDX_OK;
 }
 
@@ -870,8 +827,8 @@ extern "C" int rdx_index_set_option(rdx_index* h, const char* name, int64_t valu
     RDX_TRY(finish_pending(h, nullptr));   // the host half of an asynchronous search reads the options it was enqueued under
     const std::string n(name);
     if (n == "compact_master") {
-        if (h->rows > 0 || h->cap > 0) return fail(RDX_ERR_STATE, "compact_master can only be chosen while the index is empty");
-        h->compact = value != 0;
+        if (h->rows > 0 || h->store.cap > 0) return fail(RDX_ERR_STATE, "compact_master can only be chosen while the index is empty");
+        h->store.compact = value != 0;
         return RDX_OK;
     }
     if (n == "row_base") {
@@ -911,7 +868,8 @@ static int ingest(rdx_index* h, const void* rows, bool is_bf16, int64_t n, int s
                   bool verbatim = false) {
     hipStream_t st = h->own_stream;
     // the int8 copy: an update may touch any block, an append the last partial one and the new ones
-    h->i8_valid = d_dst_ids ? 0 : std::min<int64_t>(h->i8_valid, row0 / 32 * 32);
+    if (d_dst_ids) h->i8.mark.rewritten();
+    else h->i8.mark.appended(row0);
     if (space == RDX_DEVICE) HIP_TRY(hipDeviceSynchronize());   // the caller's producers of `rows` (any stream) are done
     const size_t esz = is_bf16 ? 2 : 4;
     RDX_TRY(h->bad.ensure(sizeof(int)));
@@ -928,7 +886,7 @@ static int ingest(rdx_index* h, const void* rows, bool is_bf16, int64_t n, int s
         const int grid = (int)((m + 3) / 4);
         hipLaunchKernelGGL(k_normalize<false>, dim3(grid), dim3(256), 0, st, is_bf16 ? nullptr : (const float*)src,
                            is_bf16 ? (const uint16_t*)src : nullptr, m, h->dim, d_dst_ids ? d_dst_ids + off : nullptr,
-                           row0 + off, h->mv(), h->shadow, h->ksteps, h->scale(), h->bad.as<int>(), (int64_t)0, verbatim ? 1 : 0);
+                           row0 + off, h->mv(), h->store.shadow.as<_Float16>(), h->ksteps, h->scale(), h->bad.as<int>(), (int64_t)0, verbatim ? 1 : 0);
         HIP_TRY(hipGetLastError());
         if (space == RDX_HOST) HIP_TRY(hipStreamSynchronize(st));   // staging is reused by the next chunk
     }
@@ -945,7 +903,7 @@ static int add_impl(rdx_index* h, const void* rows, bool is_bf16, int64_t n, int
     if (n == 0) return RDX_OK;
     std::lock_guard<std::mutex> lk(h->mu);
     RDX_TRY(finish_pending(h, nullptr));
-    if (h->compact && (!is_bf16 || verbatim))
+    if (h->store.compact && (!is_bf16 || verbatim))
         return fail(RDX_ERR_STATE, "this index keeps a compact master (raw bf16 rows + divisors): rows must arrive through rdx_index_add_bf16");
     RDX_TRY(set_device(h));
     RDX_TRY(grow(h, h->rows + n));
@@ -962,8 +920,35 @@ extern "C" int rdx_index_add_stored(rdx_index* h, const float* rows, int64_t n, 
     return add_impl(h, rows, false, n, space, true);
 }
 
-// copy a host or device int64 id list to the device scratch `ids`, validating on the host when possible
-static int stage_ids(rdx_index* h, const int64_t* ids, int64_t n, int space, const int64_t** d_ids) {
+// What a list of row ids must satisfy: every id in [0, limit) and, with `increasing`, above the one before it.
+struct IdRule {
+    int64_t limit;
+    bool increasing;
+};
+enum class IdFault { none, range, order };
+
+// the first fault of a host id list, *at = its position
+static IdFault check_ids(const int64_t* ids, int64_t n, IdRule rule, int64_t* at) {
+    for (int64_t i = 0; i < n; ++i) {
+        *at = i;
+        if (ids[i] < 0 || ids[i] >= rule.limit) return IdFault::range;
+        if (rule.increasing && i > 0 && ids[i] <= ids[i - 1]) return IdFault::order;
+    }
+    return IdFault::none;
+}
+
+// the ids of rdx_index_update and rdx_index_get: rows the index holds
+static int check_row_ids(const rdx_index* h, const int64_t* ids, int64_t n) {
+    int64_t at = 0;
+    if (check_ids(ids, n, IdRule{h->rows, false}, &at) != IdFault::none)
+        return fail(RDX_ERR_INVALID, "row id " + std::to_string(ids[at]) + " out of range [0, " + std::to_string(h->rows) + ")");
+    return RDX_OK;
+}
+
+// A host or device int64 id list: checked on the host by check(host copy) — a device list is brought over for that — and made
+// available on the device: a device list as it is, a host list through the scratch `ids`.
+template <class Check>
+static int stage_ids(rdx_index* h, const int64_t* ids, int64_t n, int space, Check check, const int64_t** d_ids) {
     hipStream_t st = h->own_stream;
     std::vector<int64_t> tmp;
     const int64_t* host_ids = ids;
@@ -973,9 +958,7 @@ static int stage_ids(rdx_index* h, const int64_t* ids, int64_t n, int space, con
         HIP_TRY(hipMemcpy(tmp.data(), ids, (size_t)n * 8, hipMemcpyDeviceToHost));
         host_ids = tmp.data();
     }
-    for (int64_t i = 0; i < n; ++i)
-        if (host_ids[i] < 0 || host_ids[i] >= h->rows)
-            return fail(RDX_ERR_INVALID, "row id " + std::to_string(host_ids[i]) + " out of range [0, " + std::to_string(h->rows) + ")");
+    RDX_TRY(check(host_ids));
     if (space == RDX_DEVICE) {
         *d_ids = ids;
         return RDX_OK;
@@ -993,10 +976,10 @@ static int update_impl(const char* fn, rdx_index* h, const int64_t* row_ids, con
     if (n == 0) return RDX_OK;
     std::lock_guard<std::mutex> lk(h->mu);
     RDX_TRY(finish_pending(h, nullptr));
-    if (h->compact) return fail(RDX_ERR_STATE, std::string(fn) + " takes fp32 rows: not available on an index with a compact (bf16) master");
+    if (h->store.compact) return fail(RDX_ERR_STATE, std::string(fn) + " takes fp32 rows: not available on an index with a compact (bf16) master");
     RDX_TRY(set_device(h));
     const int64_t* d_ids = nullptr;
-    RDX_TRY(stage_ids(h, row_ids, n, space, &d_ids));
+    RDX_TRY(stage_ids(h, row_ids, n, space, [&](const int64_t* v) { return check_row_ids(h, v, n); }, &d_ids));
     return ingest(h, rows, false, n, space, 0, d_ids, verbatim);
 }
 
@@ -1016,7 +999,7 @@ extern "C" int rdx_index_get(rdx_index* h, const int64_t* row_ids, int64_t n, fl
     RDX_TRY(set_device(h));
     hipStream_t st = h->own_stream;
     const int64_t* d_ids = nullptr;
-    RDX_TRY(stage_ids(h, row_ids, n, space, &d_ids));
+    RDX_TRY(stage_ids(h, row_ids, n, space, [&](const int64_t* v) { return check_row_ids(h, v, n); }, &d_ids));
     for (int64_t off = 0; off < n; off += STAGE_ROWS) {
         const int64_t m = std::min(STAGE_ROWS, n - off);
         float* dst = out + (size_t)off * h->dim;
@@ -1040,47 +1023,32 @@ extern "C" int rdx_index_compact(rdx_index* h, const int64_t* keep, int64_t n_ke
     std::lock_guard<std::mutex> lk(h->mu);
     RDX_TRY(finish_pending(h, nullptr));
     RDX_TRY(set_device(h));
-    for (int64_t i = 0; i < n_keep; ++i) {
-        if (keep[i] < 0 || keep[i] >= h->rows) return fail(RDX_ERR_INVALID, "compact: row id out of range");
-        if (i > 0 && keep[i] <= keep[i - 1]) return fail(RDX_ERR_INVALID, "compact: keep list must be strictly ascending");
-    }
+    int64_t at = 0;
+    const IdFault bad = check_ids(keep, n_keep, IdRule{h->rows, true}, &at);
+    if (bad == IdFault::range) return fail(RDX_ERR_INVALID, "compact: row id out of range");
+    if (bad == IdFault::order) return fail(RDX_ERR_INVALID, "compact: keep list must be strictly ascending");
     hipStream_t st = h->own_stream;
-    const int64_t ncap = std::max<int64_t>(256, (n_keep + 255) / 256 * 256);
-    float* nm = nullptr;
-    uint16_t* nr16 = nullptr;
-    double* nd = nullptr;
-    _Float16* ns = nullptr;
-    hipError_t e = alloc_master(h, ncap, &nm, &nr16, &nd);
-    if (e == hipSuccess) e = hipMalloc((void**)&ns, shadow_bytes(h, ncap));
-    if (e != hipSuccess) {
-        free_master(nm, nr16, nd);
-        return fail(RDX_ERR_NOMEM, std::string("compact: ") + hipGetErrorString(e));
-    }
-    HIP_TRY(hipMemsetAsync(ns, 0, shadow_bytes(h, ncap), st));
+    RowStore ns;   // (without an id map: the rows are renumbered, the caller sets a new map or none)
+    ns.compact = h->store.compact;
+    const hipError_t e = ns.alloc_rows(compact_cap(n_keep), h->dim, h->dim_pad);
+    if (e != hipSuccess) return fail(RDX_ERR_NOMEM, std::string("compact: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemsetAsync(ns.shadow.p, 0, ns.shadow.bytes, st));
     if (n_keep > 0) {
         RDX_TRY(h->ids.ensure((size_t)n_keep * 8));
         HIP_TRY(hipMemcpyAsync(h->ids.p, keep, (size_t)n_keep * 8, hipMemcpyHostToDevice, st));
-        const MasterView nv{nm, nr16, nd};
-        if (h->compact)
+        const MasterView nv = ns.mv();
+        if (ns.compact)
             hipLaunchKernelGGL(k_gather_raw, dim3((int)((n_keep + 3) / 4)), dim3(256), 0, st, h->mv(), h->ids.as<int64_t>(), n_keep, h->dim, nv);
         else
-            hipLaunchKernelGGL(k_gather_rows, dim3((int)((n_keep + 3) / 4)), dim3(256), 0, st, h->mv(), h->ids.as<int64_t>(), n_keep, h->dim, nm);
-        hipLaunchKernelGGL(k_reshadow, dim3((int)((n_keep + 3) / 4)), dim3(256), 0, st, nv, (int64_t)0, n_keep, h->dim, ns,
+            hipLaunchKernelGGL(k_gather_rows, dim3((int)((n_keep + 3) / 4)), dim3(256), 0, st, h->mv(), h->ids.as<int64_t>(), n_keep, h->dim, nv.f32);
+        hipLaunchKernelGGL(k_reshadow, dim3((int)((n_keep + 3) / 4)), dim3(256), 0, st, nv, (int64_t)0, n_keep, h->dim, ns.shadow.as<_Float16>(),
                            h->ksteps, h->scale());
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(st));
-    free_master(h->master, h->raw16, h->den);
-    if (h->shadow) (void)hipFree(h->shadow);
-    if (h->row_map) (void)hipFree(h->row_map);   // rows were renumbered: the caller sets a new id map (or none)
-    h->row_map = nullptr;
-    h->master = nm;
-    h->raw16 = nr16;
-    h->den = nd;
-    h->shadow = ns;
-    h->cap = ncap;
+    h->store = std::move(ns);   // (ns leaves with the old arrays and the old id map)
     h->rows = n_keep;
-    h->i8_valid = 0;
+    h->i8.mark.renumbered();
     return RDX_OK;
 }
 
@@ -1093,23 +1061,22 @@ extern "C" int rdx_index_set_row_ids(rdx_index* h, int64_t first_row, const int6
     RDX_TRY(finish_pending(h, nullptr));   // k_refine / k_select_dense of an asynchronous search may still be reading the map
     RDX_TRY(set_device(h));
     hipStream_t st = h->own_stream;
-    std::vector<int64_t> tmp;
-    const int64_t* host_ids = ids;
-    if (space == RDX_DEVICE) {
-        HIP_TRY(hipDeviceSynchronize());   // the caller's producer of `ids` (any stream) is done
-        tmp.resize((size_t)n);             // the merge's tie order rests on the map being increasing: checked for device ids too
-        HIP_TRY(hipMemcpy(tmp.data(), ids, (size_t)n * 8, hipMemcpyDeviceToHost));
-        host_ids = tmp.data();
-    }
-    for (int64_t i = 0; i < n; ++i)
-        if (host_ids[i] < 0 || (i > 0 && host_ids[i] <= host_ids[i - 1]))
+    // the merge's tie order rests on the map being increasing: checked for device ids too
+    const auto increasing = [&](const int64_t* v) {
+        int64_t at = 0;
+        if (check_ids(v, n, IdRule{INT64_MAX, true}, &at) != IdFault::none)
             return fail(RDX_ERR_INVALID, "rdx_index_set_row_ids: ids must be non-negative and strictly increasing");
-    if (!h->row_map) {
-        HIP_TRY(hipMalloc((void**)&h->row_map, (size_t)std::max<int64_t>(h->cap, 256) * 8));
-        hipLaunchKernelGGL(k_iota64, dim3((unsigned)((h->cap + 255) / 256)), dim3(256), 0, st, h->row_map, (int64_t)0, h->cap, h->row_base);
+        return (int)RDX_OK;
+    };
+    const int64_t* d_ids = nullptr;
+    RDX_TRY(stage_ids(h, ids, n, space, increasing, &d_ids));
+    RowStore& rs = h->store;
+    if (!rs.row_map.p) {
+        HIP_TRY(rs.alloc_ids());
+        hipLaunchKernelGGL(k_iota64, dim3((unsigned)((rs.cap + 255) / 256)), dim3(256), 0, st, rs.row_map.as<int64_t>(), (int64_t)0, rs.cap, h->row_base);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipMemcpyAsync(h->row_map + first_row, ids, (size_t)n * 8, space == RDX_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(rs.row_map.as<int64_t>() + first_row, d_ids, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
     return RDX_OK;
 }
@@ -1120,13 +1087,13 @@ struct NormScratch {
     DevBuf in, out, bad;
 };
 // (never destroyed: a static destructor would call hipFree at process exit, possibly after the HIP runtime is gone)
-static NormScratch* const g_norm = new NormScratch[64];
+static NormScratch* const g_norm = new NormScratch[MAX_DEVICES];
 
 extern "C" int rdx_l2_normalize(int device, const float* in, int64_t n, int dim, float* out, int space, void* stream) {
     if (n < 0 || (n > 0 && (!in || !out))) return fail(RDX_ERR_INVALID, "rdx_l2_normalize: bad argument");
     RDX_TRY(check_dim(dim));
     RDX_TRY(check_space(space));
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, "rdx_l2_normalize: device out of range");
+    RDX_TRY(check_device_index("rdx_l2_normalize", device));
     if (n == 0) return RDX_OK;
     HIP_TRY(hipSetDevice(device));
     NormScratch& sc = g_norm[device];
@@ -1267,15 +1234,11 @@ extern "C" int rdx_mask_create(rdx_index* h, const uint32_t* allow_bits, int spa
     std::lock_guard<std::mutex> lk(h->mu);
     RDX_TRY(finish_pending(h, nullptr));
     RDX_TRY(set_device(h));
-    rdx_mask* m = new rdx_mask();
+    auto m = std::make_unique<rdx_mask>();
     m->device = h->device;
     m->rows = h->rows;
     const size_t words = (size_t)((h->rows + 31) / 32), pad_words = (size_t)((h->rows + 255) / 256 * 8);
-    int rc = m->words.ensure(std::max<size_t>(pad_words, 8) * 4);
-    if (rc != RDX_OK) {
-        delete m;
-        return rc;
-    }
+    RDX_TRY(m->words.ensure(std::max<size_t>(pad_words, 8) * 4));
     hipStream_t st = h->own_stream;
     hipError_t e = hipMemsetAsync(m->words.p, 0, std::max<size_t>(pad_words, 8) * 4, st);
     if (e == hipSuccess && words > 0) {
@@ -1284,18 +1247,15 @@ extern "C" int rdx_mask_create(rdx_index* h, const uint32_t* allow_bits, int spa
             e = hipMemcpyAsync(m->words.p, allow_bits, words * 4, space == RDX_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        delete m;
-        return fail(RDX_ERR_HIP, std::string("rdx_mask_create: ") + hipGetErrorString(e));
-    }
-    *out = m;
+    if (e != hipSuccess) return fail(RDX_ERR_HIP, std::string("rdx_mask_create: ") + hipGetErrorString(e));
+    *out = m.release();
     return RDX_OK;
 }
 
 extern "C" int rdx_mask_destroy(rdx_mask* m) {
     if (!m) return RDX_OK;
     (void)hipSetDevice(m->device);
-    delete m;
+    const std::unique_ptr<rdx_mask> owner(m);
     return RDX_OK;
 }
 
@@ -1410,21 +1370,17 @@ extern "C" int rdx_merge_topk(int device, const float* part_score, const int64_t
 extern "C" int rdx_signal_create(int device, rdx_signal** out) {
     if (!out) return fail(RDX_ERR_INVALID, "rdx_signal_create: null out pointer");
     HIP_TRY(hipSetDevice(device));
-    void *p = nullptr, *d = nullptr;
-    RDX_TRY(map_pinned(64, &p, &d));
-    rdx_signal* s = new rdx_signal();
+    auto s = std::make_unique<rdx_signal>();
     s->device = device;
-    s->host = reinterpret_cast<unsigned long long*>(p);
-    s->dev = reinterpret_cast<unsigned long long*>(d);
-    *out = s;
+    RDX_TRY(s->word.map(64));
+    *out = s.release();
     return RDX_OK;
 }
 
 extern "C" int rdx_signal_destroy(rdx_signal* s) {
     if (!s) return RDX_OK;
     (void)hipSetDevice(s->device);
-    if (s->host) (void)hipHostFree(s->host);
-    delete s;
+    const std::unique_ptr<rdx_signal> owner(s);
     return RDX_OK;
 }
 
@@ -1433,7 +1389,7 @@ extern "C" int rdx_signal_wait(rdx_signal* s, void* stream, int32_t* value) {
     if (s->seq == 0) return fail(RDX_ERR_STATE, "rdx_signal_wait: no merge has been given this signal");
     HIP_TRY(hipSetDevice(s->device));
     unsigned long long w = 0;
-    const int rc = wait_word([&] { return ((w = __atomic_load_n(s->host, __ATOMIC_ACQUIRE)) >> 1) == s->seq; }, (hipStream_t)stream);
+    const int rc = wait_word([&] { return ((w = __atomic_load_n(s->word.host, __ATOMIC_ACQUIRE)) >> 1) == s->seq; }, (hipStream_t)stream);
     if (rc == 1) return fail(RDX_ERR_HIP, "internal: the merge completed without publishing its signal");
     if (rc != 0) return rc;
     *value = (int32_t)(w & 1ull);
@@ -1460,7 +1416,7 @@ extern "C" int rdx_merge_topk_packed(int device, const void* packed, int64_t par
     hipLaunchKernelGGL(k_merge, dim3((int)nq), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float*>(b + nq * k * 8),
                        reinterpret_cast<const int64_t*>(b), reinterpret_cast<const int32_t*>(b + nq * k * 12), part_stride / 4,
                        part_stride / 8, part_stride / 4, n_parts, nq, k, out_score, out_row, out_count,
-                       reinterpret_cast<const int32_t*>(b + flags_off), part_stride / 4, sig ? sig->dev : (unsigned long long*)nullptr, seq);
+                       reinterpret_cast<const int32_t*>(b + flags_off), part_stride / 4, sig ? sig->word.dev : (unsigned long long*)nullptr, seq);
     HIP_TRY(hipGetLastError());
     return RDX_OK;
 }

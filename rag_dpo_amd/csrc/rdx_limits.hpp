@@ -1,5 +1,5 @@
 // rdx_limits.hpp — the compile-time limits that both the kernels (rdx_common.hpp, scan_kernel.hpp, refine_kernel.hpp) and the search
-// plan (search_plan.hpp) use, and nothing else. No HIP include: a plain C++ compiler builds it.
+// plan (search_plan.hpp) use, and the one limit every host unit shares. No HIP include: a plain C++ compiler builds it.
 #pragma once
 
 namespace rdx {
@@ -19,5 +19,7 @@ constexpr int SPILL_CAP = 40960;     // most hits of a query whose list lives in
                                      // every 32nd; DESIGN.md §5 "Spill list"), 320 MB for 1 024 queries; more -> second pass
 constexpr int EPS_CLASSES = 8;       // most classes of block error the int8 scan tells apart (k_eps_edges, SearchPlan::eps_classes): edges at the
                                      // 50 / 75 / 87.5 ... % quantiles of eps_b, the top class's edge eps_max
+
+constexpr int MAX_DEVICES = 64;      // device indices the per-device host state is sized for (rdx_host.hpp check_device_index)
 
 }   // namespace rdx

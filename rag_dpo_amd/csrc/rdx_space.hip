@@ -10,8 +10,7 @@ static int space_common(const char* fn, int device, int kind, int dim) {
     if (kind != SPACE_IP && kind != SPACE_L2) return fail(RDX_ERR_INVALID, std::string(fn) + ": space_kind must be RDX_SPACE_IP or RDX_SPACE_L2");
     if (dim < 4 || dim % 4 != 0 || space_lifted_dim(kind, dim) > SPACE_MAX_DIM)
         return fail(RDX_ERR_INVALID, std::string(fn) + ": dim must be a positive multiple of 4 whose lifted form is at most 4096");
-    if (device < 0 || device >= 64) return fail(RDX_ERR_INVALID, std::string(fn) + ": device out of range");
-    return RDX_OK;
+    return check_device_index(fn, device);
 }
 
 static unsigned space_grid(int64_t waves) { return (unsigned)((waves + SPACE_WAVES - 1) / SPACE_WAVES); }

@@ -20,9 +20,11 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run(lib, shape, sets, dump, steps, warmup):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--no-cpu", "--no-others",
-           "--profile-all"]
+def run(lib, shape, sets, dump, steps, warmup, workload=None):
+    """workload: another workload of bench.py than c4, with the timer bench.py uses by itself (events around every kernel would
+    sit on the host path that is most of a small workload's step)"""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--no-cpu", "--no-others"]
+    cmd += ["--workload", workload] if workload else ["--profile-all"]
     if shape != "iid":
         cmd += ["--corpus-shape", shape]
     for s in sets:
