@@ -459,6 +459,18 @@ int rdx_bm25_destroy(rdx_bm25* h);
 int rdx_bm25_search(rdx_bm25* h, const int64_t* term_offsets, const int32_t* term_ids, int64_t nq, int k,
                     const uint32_t* allow_groups, double* out_score, int64_t* out_row, int32_t* out_count, int space,
                     void* stream);
+/* rdx_bm25_search with a filter per query: filter_sets is a table [n_filters][(n_groups + 31) / 32] of bitsets as allow_groups is
+ * one, and query_filter[q] in [-1, n_filters) is the row of the table that filters query q, -1 = no filter. Equal entries share a
+ * set; a set of zeros is valid (its queries return count 0); n_filters = 0 with every entry -1 is rdx_bm25_search(.., NULL, ..).
+ * Query q's result is, bit for bit, what rdx_bm25_search returns for that query alone with that set. The table and query_filter
+ * travel in the upload of the offsets and ids: still one upload, one download. RDX_ERR_INVALID before anything is enqueued (the
+ * outputs are not written), the message naming the query and the value: an entry outside [-1, n_filters); n_filters > 0 on an index
+ * created without groups; filter_sets NULL with n_filters > 0; query_filter NULL with nq > 0. Everything else as rdx_bm25_search.
+ * Serves the doc_filter of ChunkBM25Index.search (bm25_index.py:265-292) for a batch of questions, each with its own summary
+ * pre-filter (retriever.py:417-452). */
+int rdx_bm25_search_filtered(rdx_bm25* h, const int64_t* term_offsets, const int32_t* term_ids, int64_t nq, int k,
+                             const uint32_t* filter_sets, int32_t n_filters, const int32_t* query_filter, double* out_score,
+                             int64_t* out_row, int32_t* out_count, int space, void* stream);
 
 /* Building a BM25 index from text ----------------------------------------------------------- */
 /* The tokenizer of the reference's indexes (tokenize_french, bm25_index.py:38-49) and the vocabulary and postings that

@@ -124,6 +124,7 @@ SYMBOLS = {
     "rdx_bm25_create": (_i, [_i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.POINTER(_vp)]),
     "rdx_bm25_destroy": (_i, [_vp]),
     "rdx_bm25_search": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "rdx_bm25_search_filtered": (_i, [_vp, _vp, _vp, _i64, _i, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _i, _vp]),
     "rdx_bm25_build_create": (_i, [_i, _i64, ctypes.c_uint64, ctypes.POINTER(_vp)]),
     "rdx_bm25_build_destroy": (_i, [_vp]),
     "rdx_bm25_build_tokenize": (_i, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),

@@ -14,7 +14,8 @@ A row without q adds +-0.0, so out-of-vocabulary tokens are dropped here; duplic
 The per-row denominator and the idf are computed on the host with exactly that operation order; the device adds the
 postings (include/rdx.h rdx_bm25_*, csrc/bm25_kernel.hpp). Search result: rows with score > 0 (and, for chunks, whose
 `document_path` is in `doc_filter` when it is not None: an empty set returns nothing), score descending, ties by
-ascending row, cut to top_k (bm25_index.py:146-168, :265-292).
+ascending row, cut to top_k (bm25_index.py:146-168, :265-292). A batch of chunk queries may give every query a doc_filter of its
+own (`doc_filters`): still one device call (rdx_bm25_search_filtered), each query answered as if searched alone with its set.
 
 The index is immutable, as in the reference: to refresh, build again. By default tokenisation is Python, as in the reference,
 and the postings are built with numpy; build="device" does both on the GPU (rag_dpo_amd/bm25_build.py), for collections whose
@@ -30,7 +31,7 @@ import math
 import operator
 import re
 from dataclasses import dataclass
-from itertools import chain
+from itertools import accumulate, chain
 from pathlib import Path
 from typing import Callable, Dict, List, Optional, Sequence, Set
 
@@ -45,6 +46,7 @@ K1, B, EPSILON = 1.5, 0.75, 0.25
 MAX_K = 4096          # include/rdx.h rdx_bm25_search: results per query
 MAX_TERMS = 4096      # query terms per query (after dropping out-of-vocabulary ones)
 MAX_TF = 65535        # the device stores tf as uint16
+NOTHING = -2          # a query's entry in place of a filter row: its doc_filter names no indexed document
 
 # French stop words of the reference's tokenizer (bm25_index.py FRENCH_STOPWORDS): a behavioural contract, pinned entry by
 # entry by tests/golden/bm25_golden.json
@@ -192,6 +194,32 @@ class HipBm25(_Handle):
                                           ctypes.c_void_p(cn.ctypes.data), L.RDX_HOST, ctypes.c_void_p(stream)))
         return sc, ro, cn
 
+    def search_filtered(self, term_offsets: np.ndarray, term_ids: np.ndarray, k: int, filter_sets: Optional[np.ndarray],
+                        query_filter: np.ndarray):
+        """search with a filter per query (rdx_bm25_search_filtered): filter_sets uint32 [n_filters, (n_groups + 31) // 32] (None =
+        no sets), query_filter int32 [nq] = the query's row of filter_sets, or -1 for no filter -> what search returns"""
+        import torch
+        off = np.ascontiguousarray(term_offsets, np.int64)
+        ids = np.ascontiguousarray(term_ids, np.int32)
+        nq = off.shape[0] - 1
+        qf = np.ascontiguousarray(query_filter, np.int32).reshape(-1)
+        if qf.shape[0] != nq:
+            raise ValueError(f"query_filter has {qf.shape[0]} entries for {nq} queries")
+        words = (self.n_groups + 31) // 32
+        fs = np.ascontiguousarray(filter_sets, np.uint32) if filter_sets is not None else np.zeros((0, words), np.uint32)
+        if fs.ndim != 2 or (fs.shape[0] and fs.shape[1] != words):
+            raise ValueError(f"filter_sets must be [n_filters, (n_groups + 31) // 32 = {words}] words (got {fs.shape})")
+        sc = np.empty((nq, k), np.float64)
+        ro = np.empty((nq, k), np.int64)
+        cn = np.empty(nq, np.int32)
+        stream = torch._C._cuda_getCurrentRawStream(self.device)
+        L.check(self._lib.rdx_bm25_search_filtered(self._h, ctypes.c_void_p(off.ctypes.data), ctypes.c_void_p(ids.ctypes.data), nq, int(k),
+                                                   ctypes.c_void_p(fs.ctypes.data) if fs.shape[0] else None, int(fs.shape[0]),
+                                                   ctypes.c_void_p(qf.ctypes.data), ctypes.c_void_p(sc.ctypes.data),
+                                                   ctypes.c_void_p(ro.ctypes.data), ctypes.c_void_p(cn.ctypes.data), L.RDX_HOST,
+                                                   ctypes.c_void_p(stream)))
+        return sc, ro, cn
+
 
 def _default_engine_factory(arrays: Bm25Arrays, device: int):
     return HipBm25(arrays, device)
@@ -243,9 +271,11 @@ class _Bm25Base:
         self.engine = self._factory(self.model.arrays(row_group, n_groups), self.device) if self.model.n_rows else None
         self._is_built = True
 
-    def _search_arrays(self, queries: Sequence[str], top_k: int, allow_bits=None):
+    def _search_arrays(self, queries: Sequence[str], top_k: int, allow_bits=None, filters=None):
         """-> (live, scores f64 [len(live), k], rows int64 [len(live), k], counts int32 [len(live)]): the engine's own arrays for the
-        queries (indices `live`) that have a known token, the reference's order and cut; every other query finds nothing"""
+        queries (indices `live`) that have a known token, the reference's order and cut; every other query finds nothing.
+        allow_bits: one bitset for every query. filters = (filter_sets, which) instead: a bitset per row of filter_sets and, per
+        query, its row, -1 (no filter) or NOTHING (its filter names no indexed document: the query finds nothing)"""
         if not self._is_built:
             raise RuntimeError("the BM25 index is not built")
         none = ([], np.zeros((0, 0), np.float64), np.zeros((0, 0), np.int64), np.zeros(0, np.int32))
@@ -253,7 +283,9 @@ class _Bm25Base:
             return none
         k = min(int(top_k), self.model.n_rows)
         terms = [self.model.query_ids(tokenize_french(q)) for q in queries]
-        live = [i for i, t in enumerate(terms) if t]           # a query without known tokens scores 0 everywhere: nothing
+        sets, which = filters if filters is not None else (None, None)
+        # a query without known tokens scores 0 everywhere: nothing
+        live = [i for i, t in enumerate(terms) if t and (which is None or which[i] != NOTHING)]
         if not live:
             return none
         for i in live:
@@ -262,12 +294,31 @@ class _Bm25Base:
         off = np.zeros(len(live) + 1, np.int64)
         np.cumsum([len(terms[i]) for i in live], out=off[1:])
         ids = np.fromiter(chain.from_iterable(terms[i] for i in live), dtype=np.int32, count=int(off[-1]))
-        sc, ro, cn = self.engine.search(off, ids, k, allow_bits)
+        if sets is None or not len(sets):
+            sc, ro, cn = self.engine.search(off, ids, k, allow_bits)
+        else:
+            sc, ro, cn = self._engine_search_filtered(off, ids, k, sets, np.asarray(which, np.int32)[live])
         return live, sc, ro, cn
 
-    def _search_rows(self, queries: Sequence[str], top_k: int, allow_bits=None):
+    def _engine_search_filtered(self, off: np.ndarray, ids: np.ndarray, k: int, sets: np.ndarray, query_filter: np.ndarray):
+        """the engine's search_filtered; an engine without one (a custom engine_factory's) is asked once per distinct set through
+        search, with the same results"""
+        if hasattr(self.engine, "search_filtered"):
+            return self.engine.search_filtered(off, ids, k, sets, query_filter)
+        nq = len(query_filter)
+        sc, ro, cn = np.zeros((nq, k), np.float64), np.full((nq, k), -1, np.int64), np.zeros(nq, np.int32)
+        lens = np.diff(off)
+        for f in np.unique(query_filter).tolist():
+            js = np.flatnonzero(query_filter == f)
+            sub_off = np.zeros(len(js) + 1, np.int64)
+            np.cumsum(lens[js], out=sub_off[1:])
+            sub_ids = np.concatenate([ids[off[j]:off[j + 1]] for j in js.tolist()])
+            sc[js], ro[js], cn[js] = self.engine.search(sub_off, sub_ids, k, None if f < 0 else sets[f])
+        return sc, ro, cn
+
+    def _search_rows(self, queries: Sequence[str], top_k: int, allow_bits=None, filters=None):
         """-> per query a list of (row, score), the reference's order and cut"""
-        live, sc, ro, cn = self._search_arrays(queries, top_k, allow_bits)
+        live, sc, ro, cn = self._search_arrays(queries, top_k, allow_bits, filters)
         out: List[list] = [[] for _ in queries]
         for j, i in enumerate(live):
             c = int(cn[j])
@@ -384,10 +435,41 @@ class ChunkBM25Index(_Bm25Base):
                 hit = True
         return bits if hit else None
 
-    def search_batch(self, queries: Sequence[str], top_k: int = 30, doc_filter: Optional[Set[str]] = None) -> List[List[BM25Result]]:
-        """search() of every query, in one device call"""
+    def _filter_table(self, queries: Sequence[str], doc_filter, doc_filters):
+        """doc_filters (one Optional[Set[str]] per query) -> _search_arrays' `filters`: equal sets share one row of the table, a
+        set that names no indexed document has none (its queries find nothing). None without doc_filters."""
+        if doc_filters is None:
+            return None
+        if doc_filter is not None:
+            raise ValueError("give doc_filter (one set for every query) or doc_filters (one per query), not both")
+        if len(doc_filters) != len(queries):
+            raise ValueError(f"doc_filters has {len(doc_filters)} entries for {len(queries)} queries")
+        row_of: Dict[frozenset, int] = {}
+        seen: Dict[int, int] = {}         # by identity first: the sub-queries of one question share one set object
+        which = []
+        for f in doc_filters:
+            w = -1 if f is None else seen.get(id(f))
+            if w is None:
+                w = seen[id(f)] = row_of.setdefault(frozenset(f), len(row_of))
+            which.append(w)
+        # per distinct set the groups of its indexed documents; the sets that have one are the table's rows, in that order
+        known = [[g for g in map(self._group_of.get, f) if g is not None] for f in row_of]
+        row = list(accumulate(map(bool, known), initial=0))
+        sets = np.zeros((row[-1], (len(self._group_of) + 31) // 32), np.uint32)
+        if row[-1]:         # the bits of every set OR-ed in at once
+            groups = np.fromiter(chain.from_iterable(known), dtype=np.int64)
+            owner = np.repeat(np.arange(row[-1]), [len(gs) for gs in known if gs])
+            np.bitwise_or.at(sets, (owner, groups >> 5), np.left_shift(np.uint32(1), (groups & 31).astype(np.uint32)))
+        return sets, np.array([w if w < 0 else (row[w] if known[w] else NOTHING) for w in which], np.int32)
+
+    def search_batch(self, queries: Sequence[str], top_k: int = 30, doc_filter: Optional[Set[str]] = None,
+                     doc_filters: Optional[Sequence[Optional[Set[str]]]] = None) -> List[List[BM25Result]]:
+        """search() of every query, in one device call; doc_filters gives every query a doc_filter of its own (None = unfiltered)"""
         if not self._is_built:
             raise RuntimeError("the BM25 index is not built")
+        filters = self._filter_table(queries, doc_filter, doc_filters)
+        if filters is not None:
+            return [[self.result_of(r, s) for r, s in hits] for hits in self._search_rows(queries, top_k, filters=filters)]
         bits = None
         if doc_filter is not None:
             bits = self._allow_bits(doc_filter)
@@ -400,12 +482,16 @@ class ChunkBM25Index(_Bm25Base):
         return BM25Result(doc_key=self.chunk_ids[row], score=score,
                           metadata={**(self.chunk_metadatas[row] or {}), "text": self.chunk_texts[row]})
 
-    def search_batch_arrays(self, queries: Sequence[str], top_k: int = 30, doc_filter: Optional[Set[str]] = None):
+    def search_batch_arrays(self, queries: Sequence[str], top_k: int = 30, doc_filter: Optional[Set[str]] = None,
+                            doc_filters: Optional[Sequence[Optional[Set[str]]]] = None):
         """search_batch without the result objects, for callers that materialise a few of the hits (rag_dpo_amd/fusion.py):
         -> (live, scores f64 [len(live), k], rows int64 [len(live), k], counts int32 [len(live)]), rows = indexes into chunk_ids;
         a query that is not in `live` found nothing"""
         if not self._is_built:
             raise RuntimeError("the BM25 index is not built")
+        filters = self._filter_table(queries, doc_filter, doc_filters)
+        if filters is not None:
+            return self._search_arrays(queries, top_k, filters=filters)
         bits = None
         if doc_filter is not None:
             bits = self._allow_bits(doc_filter)

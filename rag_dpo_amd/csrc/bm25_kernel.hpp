@@ -11,7 +11,11 @@
 //   dir_tile  int32 [ndir]   a tile (BM25_TILE rows) holding postings of the term, ascending
 //   dir_pos   int64 [ndir+1] the entry's first posting; dir_pos[e+1] ends it (the next entry, of this term or the next one,
 //                            starts where it ends; dir_pos[ndir] = nnz)
-//   group     int32 [N]      interned document_path of the row (the doc_filter is a bitset over groups)
+//   group     int32 [N]      interned document_path of the row (a doc_filter is a bitset over groups)
+//
+// Filters of one search: a table of n_filters bitsets over the groups, allow_words = (n_groups + 31) / 32 words each, and per query
+// the row of the table it is filtered by, or -1 for no filter (query_filter). A search with one bitset for all its queries is a
+// table of one row.
 //
 // Exactness: rank_bm25 adds, for each query token in query order (duplicates kept), the float64 vector
 //   idf * ((tf * 2.5) / (tf + denom))
@@ -94,12 +98,13 @@ __device__ __forceinline__ int bm25_pow2_at_least(int n) {
 }
 
 // Grid (doc tile, query of this chunk). Writes the tile's top-min(k, passing) rows, UNORDERED, to
-// part_{score,row}[q][tile][0..count) and the count to part_count[q][tile]; rows are global.
+// part_{score,row}[q][tile][0..count) and the count to part_count[q][tile]; rows are global. q_off and query_filter are the
+// chunk's own: entry 0 belongs to the chunk's first query.
 __global__ __launch_bounds__(BM25_THREADS) void k_bm25_score(
     const int64_t* __restrict__ dir_off, const int32_t* __restrict__ dir_tile, const int64_t* __restrict__ dir_pos,
     const int32_t* __restrict__ post_row, const uint16_t* __restrict__ post_tf, const double* __restrict__ idf,
-    const double* __restrict__ denom, const int32_t* __restrict__ row_group, const uint32_t* __restrict__ allow,
-    const int64_t* __restrict__ q_off, const int32_t* __restrict__ q_terms, int64_t n_rows, int k, int n_tiles,
+    const double* __restrict__ denom, const int32_t* __restrict__ row_group, const uint32_t* __restrict__ filter_sets,
+    int allow_words, const int32_t* __restrict__ query_filter, const int64_t* __restrict__ q_off, const int32_t* __restrict__ q_terms, int64_t n_rows, int k, int n_tiles,
     double* __restrict__ part_score, int32_t* __restrict__ part_row, int32_t* __restrict__ part_count) {
 #pragma clang fp contract(off)
     __shared__ double acc[BM25_TILE];          // per-row scores; after phase C's compaction: the candidates' scores
@@ -114,6 +119,8 @@ __global__ __launch_bounds__(BM25_THREADS) void k_bm25_score(
     const int64_t base = (int64_t)tile * BM25_TILE;
     const int rows = (int)min((int64_t)BM25_TILE, n_rows - base);
     const size_t part = (size_t)q * n_tiles + tile;
+    const int32_t filter = query_filter[q];   // uniform over the block
+    const uint32_t* set = filter < 0 ? nullptr : filter_sets + (size_t)filter * allow_words;
     for (int i = tid; i < BM25_TILE; i += BM25_THREADS) acc[i] = 0.0;
     if (tid == 0) s_any = 0;
 
@@ -174,9 +181,9 @@ __global__ __launch_bounds__(BM25_THREADS) void k_bm25_score(
         const int l = tid + j * BM25_THREADS;
         v[j] = l < rows ? acc[l] : 0.0;
         bool pass = v[j] > 0.0;
-        if (pass && allow != nullptr) {
+        if (pass && set != nullptr) {
             const int32_t g = row_group[base + l];
-            pass = (allow[g >> 5] >> (g & 31)) & 1u;
+            pass = (set[g >> 5] >> (g & 31)) & 1u;
         }
         ok |= (uint32_t)pass << j;
         cnt += pass;

@@ -118,51 +118,67 @@ extern "C" int rdx_bm25_destroy(rdx_bm25* h) {
     return RDX_OK;
 }
 
-extern "C" int rdx_bm25_search(rdx_bm25* h, const int64_t* term_offsets, const int32_t* term_ids, int64_t nq, int k,
-                               const uint32_t* allow_groups, double* out_score, int64_t* out_row, int32_t* out_count, int space,
-                               void* stream) {
-    if (!h) return fail(RDX_ERR_INVALID, "rdx_bm25_search: null index");
+// The one search behind rdx_bm25_search and rdx_bm25_search_filtered (`who` names the caller in messages). The filters are a table
+// of n_filters bitsets and, per query, its row of the table or -1; query_filter == nullptr gives every query `uniform_filter`.
+static int bm25_search(const char* who, rdx_bm25* h, const int64_t* term_offsets, const int32_t* term_ids, int64_t nq, int k,
+                       const uint32_t* filter_sets, int32_t n_filters, const int32_t* query_filter, int32_t uniform_filter,
+                       double* out_score, int64_t* out_row, int32_t* out_count, int space, void* stream) {
+    const std::string me = who;
+    if (!h) return fail(RDX_ERR_INVALID, me + ": null index");
     if (nq < 0 || k < 1 || k > BM25_MAX_K)
-        return fail(RDX_ERR_INVALID, "rdx_bm25_search: need nq >= 0 and 1 <= k <= " + std::to_string(BM25_MAX_K) + " (got k = " +
+        return fail(RDX_ERR_INVALID, me + ": need nq >= 0 and 1 <= k <= " + std::to_string(BM25_MAX_K) + " (got k = " +
                                          std::to_string(k) + ")");
-    if (space != RDX_HOST) return fail(RDX_ERR_INVALID, "rdx_bm25_search: space must be RDX_HOST (the terms are checked on the host)");
-    if (allow_groups && h->n_groups == 0) return fail(RDX_ERR_INVALID, "rdx_bm25_search: a group filter on an index without groups");
+    if (space != RDX_HOST) return fail(RDX_ERR_INVALID, me + ": space must be RDX_HOST (the terms are checked on the host)");
+    if (n_filters < 0) return fail(RDX_ERR_INVALID, me + ": n_filters = " + std::to_string(n_filters) + " is negative");
+    if (n_filters > 0 && h->n_groups == 0) return fail(RDX_ERR_INVALID, me + ": a group filter on an index without groups");
+    if (n_filters > 0 && !filter_sets)
+        return fail(RDX_ERR_INVALID, me + ": null filter_sets with n_filters = " + std::to_string(n_filters));
     if (nq == 0) return RDX_OK;
-    if (!term_offsets || !out_score || !out_row || !out_count) return fail(RDX_ERR_INVALID, "rdx_bm25_search: null pointer");
+    if (!term_offsets || !out_score || !out_row || !out_count) return fail(RDX_ERR_INVALID, me + ": null pointer");
+    if (query_filter)
+        for (int64_t q = 0; q < nq; ++q)
+            if (query_filter[q] < -1 || query_filter[q] >= n_filters)
+                return fail(RDX_ERR_INVALID, me + ": query_filter[" + std::to_string(q) + "] = " + std::to_string(query_filter[q]) +
+                                                 " out of [-1, " + std::to_string(n_filters) + ")");
     std::lock_guard<std::mutex> lock(h->mu);
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->own_stream;
 
     // the query terms are checked before anything is enqueued
     const int64_t* off = term_offsets;
-    if (off[0] != 0) return fail(RDX_ERR_INVALID, "rdx_bm25_search: term_offsets[0] must be 0");
+    if (off[0] != 0) return fail(RDX_ERR_INVALID, me + ": term_offsets[0] must be 0");
     for (int64_t q = 0; q < nq; ++q) {
         const int64_t T = off[q + 1] - off[q];
         if (T < 0 || T > BM25_MAX_TERMS)
-            return fail(RDX_ERR_INVALID, "rdx_bm25_search: query " + std::to_string(q) + " has " + std::to_string(T) + " terms (0.." +
+            return fail(RDX_ERR_INVALID, me + ": query " + std::to_string(q) + " has " + std::to_string(T) + " terms (0.." +
                                              std::to_string(BM25_MAX_TERMS) + ")");
     }
     const int64_t n_ids = off[nq];
-    if (n_ids > 0 && !term_ids) return fail(RDX_ERR_INVALID, "rdx_bm25_search: null term_ids");
+    if (n_ids > 0 && !term_ids) return fail(RDX_ERR_INVALID, me + ": null term_ids");
     for (int64_t i = 0; i < n_ids; ++i)
         if (term_ids[i] < 0 || term_ids[i] >= h->n_terms)
-            return fail(RDX_ERR_INVALID, "rdx_bm25_search: term id " + std::to_string(term_ids[i]) + " out of [0, " +
+            return fail(RDX_ERR_INVALID, me + ": term id " + std::to_string(term_ids[i]) + " out of [0, " +
                                              std::to_string(h->n_terms) + ")");
 
-    // one upload through pinned staging: offsets | ids | allow bits
+    // one upload through pinned staging: offsets | ids | query_filter | filter sets
     const size_t allow_words = (size_t)(h->n_groups + 31) / 32;
     const size_t b_off = align16((size_t)(nq + 1) * 8), b_ids = align16((size_t)std::max<int64_t>(n_ids, 1) * 4);
-    const size_t b_in = b_off + b_ids + (allow_groups ? align16(allow_words * 4) : 0);
+    const size_t b_qf = align16((size_t)nq * 4), n_set_bytes = (size_t)n_filters * allow_words * 4;
+    const size_t b_in = b_off + b_ids + b_qf + align16(n_set_bytes);
     RDX_TRY(h->h_in.ensure(b_in));
     RDX_TRY(h->in.ensure(b_in));
     char* hp = (char*)h->h_in.p;
     std::memcpy(hp, term_offsets, (size_t)(nq + 1) * 8);
     if (n_ids) std::memcpy(hp + b_off, term_ids, (size_t)n_ids * 4);
-    if (allow_groups) std::memcpy(hp + b_off + b_ids, allow_groups, allow_words * 4);
+    int32_t* h_qf = (int32_t*)(hp + b_off + b_ids);
+    if (query_filter) std::memcpy(h_qf, query_filter, (size_t)nq * 4);
+    else std::fill(h_qf, h_qf + nq, uniform_filter);
+    if (n_set_bytes) std::memcpy(hp + b_off + b_ids + b_qf, filter_sets, n_set_bytes);
     HIP_TRY(hipMemcpyAsync(h->in.p, hp, b_in, hipMemcpyHostToDevice, st));
     const int64_t* d_off = (const int64_t*)h->in.p;
     const int32_t* d_ids = (const int32_t*)((char*)h->in.p + b_off);
-    const uint32_t* d_allow = allow_groups ? (const uint32_t*)((char*)h->in.p + b_off + b_ids) : nullptr;
+    const int32_t* d_qf = (const int32_t*)((char*)h->in.p + b_off + b_ids);
+    const uint32_t* d_sets = (const uint32_t*)((char*)h->in.p + b_off + b_ids + b_qf);   // never read when n_filters = 0
     const size_t b_score = align16((size_t)nq * k * 8), b_row = align16((size_t)nq * k * 8), b_cnt = align16((size_t)nq * 4);
     RDX_TRY(h->out.ensure(b_score + b_row + b_cnt));
     double* o_score = (double*)h->out.p;
@@ -180,8 +196,8 @@ extern "C" int rdx_bm25_search(rdx_bm25* h, const int64_t* term_offsets, const i
         const int nqc = (int)std::min<int64_t>(chunk, nq - q0);
         hipLaunchKernelGGL(k_bm25_score, dim3(h->n_tiles, nqc), dim3(BM25_THREADS), 0, st, h->dir_off.as<int64_t>(),
                            h->dir_tile.as<int32_t>(), h->dir_pos.as<int64_t>(), h->post_row.as<int32_t>(), h->post_tf.as<uint16_t>(),
-                           h->idf.as<double>(), h->denom.as<double>(), h->group.as<int32_t>(), d_allow, d_off + q0, d_ids, h->n_rows, k,
-                           h->n_tiles, p_score, p_row, p_cnt);
+                           h->idf.as<double>(), h->denom.as<double>(), h->group.as<int32_t>(), d_sets, (int)allow_words,
+                           d_qf + q0, d_off + q0, d_ids, h->n_rows, k, h->n_tiles, p_score, p_row, p_cnt);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_bm25_merge, dim3(nqc), dim3(BM25_MERGE_THREADS), 0, st, p_score, p_row, p_cnt, h->n_tiles, k,
                            o_score + (size_t)q0 * k, o_row + (size_t)q0 * k, o_cnt + q0);
@@ -196,4 +212,20 @@ extern "C" int rdx_bm25_search(rdx_bm25* h, const int64_t* term_offsets, const i
     std::memcpy(out_row, ho + b_score, (size_t)nq * k * 8);
     std::memcpy(out_count, ho + b_score + b_row, (size_t)nq * 4);
     return RDX_OK;
+}
+
+extern "C" int rdx_bm25_search(rdx_bm25* h, const int64_t* term_offsets, const int32_t* term_ids, int64_t nq, int k,
+                               const uint32_t* allow_groups, double* out_score, int64_t* out_row, int32_t* out_count, int space,
+                               void* stream) {
+    // one bitset for every query = a table of one row
+    return bm25_search("rdx_bm25_search", h, term_offsets, term_ids, nq, k, allow_groups, allow_groups ? 1 : 0, nullptr,
+                       allow_groups ? 0 : -1, out_score, out_row, out_count, space, stream);
+}
+
+extern "C" int rdx_bm25_search_filtered(rdx_bm25* h, const int64_t* term_offsets, const int32_t* term_ids, int64_t nq, int k,
+                                        const uint32_t* filter_sets, int32_t n_filters, const int32_t* query_filter,
+                                        double* out_score, int64_t* out_row, int32_t* out_count, int space, void* stream) {
+    if (nq > 0 && !query_filter) return fail(RDX_ERR_INVALID, "rdx_bm25_search_filtered: null query_filter with nq = " + std::to_string(nq));
+    return bm25_search("rdx_bm25_search_filtered", h, term_offsets, term_ids, nq, k, filter_sets, n_filters, query_filter, -1,
+                       out_score, out_row, out_count, space, stream);
 }

@@ -17,6 +17,7 @@ from __future__ import annotations
 import ctypes
 import json
 from dataclasses import dataclass
+from itertools import chain
 from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
@@ -65,15 +66,23 @@ class PackedLists:
 
     def set_filter(self, q: int, allowed_groups: Sequence[int], n_groups: int):
         """question q's dense lists are filtered: only keys whose group is in allowed_groups pass"""
+        self.set_filters({q: allowed_groups}, n_groups)
+
+    def set_filters(self, allowed: Dict[int, Sequence[int]], n_groups: int):
+        """set_filter for every question q of `allowed` (q -> its allowed groups), the bits of all of them OR-ed in at once"""
+        if not allowed:
+            return
         words = max(1, (int(n_groups) + 31) // 32)
         if words > self.group_words:
             grown = np.zeros((self.nq, words), np.uint32)
             grown[:, : self.group_words] = self.allow
             self.allow, self.group_words = grown, words
-        self.filter_on[q] = 1
-        self.allow[q] = 0
-        for g in allowed_groups:
-            self.allow[q, g >> 5] |= np.uint32(1 << (g & 31))
+        qs = np.fromiter(allowed, dtype=np.int64, count=len(allowed))
+        sizes = np.fromiter(map(len, allowed.values()), dtype=np.int64, count=len(allowed))
+        groups = np.fromiter(chain.from_iterable(allowed.values()), dtype=np.int64, count=int(sizes.sum()))
+        self.filter_on[qs] = 1
+        self.allow[qs] = 0
+        np.bitwise_or.at(self.allow, (np.repeat(qs, sizes), groups >> 5), np.left_shift(np.uint32(1), (groups & 31).astype(np.uint32)))
 
     def lists_of(self, q: int):
         """-> per list None (absent) or (kind, weight, keys, values): what set_list was given"""
@@ -281,32 +290,25 @@ def retrieve_candidates_device(r, expanded: List[tuple], n_candidates: int, wher
                 dd, rr, cc = col.query_device(vectors.index_select(0, idx), n_results=n_fetch, where=wheres[sub_q[ts[0]]])
                 d_dist[idx], d_rows[idx], d_cnt[idx] = dd, rr, cc
 
-        # BM25 of every sub-query: one device call per distinct summary filter; the hits stay arrays
+        # BM25 of every sub-query, each under its question's summary filter: one device call; the hits stay arrays
         bm_rows = None
         if hybrid:
             bm_rows = np.full((nq * n_lists, n_fetch), -1, np.int64)
             keymap = tables.bm25_keys(col, r.chunk_bm25)
             keys2, score2, count1 = packed.keys.reshape(nq * n_lists, n_fetch), packed.score.reshape(nq * n_lists, n_fetch), packed.count.reshape(-1)
-            by_filter: Dict[Any, List[int]] = {}
-            for t, q in enumerate(sub_q):
-                f = doc_filters[q]
-                by_filter.setdefault(None if f is None else frozenset(f), []).append(t)
-            for f, ts in by_filter.items():
-                slots = dense_slot[ts] + 1
-                packed.kind.reshape(-1)[slots] = BM25
-                packed.weight.reshape(-1)[slots] = [2.0 * 1.5 if sub_i[t] == 0 else 1.0 * 0.75 for t in ts]     # reference :421, :430
-                count1[slots] = 0                                                    # searched: present, maybe empty
-                live, sc, ro, cn = r.chunk_bm25.search_batch_arrays([texts[t] for t in ts], top_k=n_fetch,
-                                                                     doc_filter=None if f is None else set(f))
-                if len(live):
-                    ls, k = slots[live], ro.shape[1]
-                    bm_rows[ls, :k] = ro
-                    keys2[ls, :k] = np.where(ro >= 0, keymap[np.maximum(ro, 0)], -1)
-                    score2[ls, :k] = sc
-                    count1[ls] = cn
-        for q, f in enumerate(doc_filters):
-            if f:                                                                    # (an empty filter filters nothing: reference :226, :391)
-                packed.set_filter(q, tables.groups_allowed(f), tables.n_groups)
+            slots = dense_slot + 1
+            packed.kind.reshape(-1)[slots] = BM25
+            packed.weight.reshape(-1)[slots] = [2.0 * 1.5 if i == 0 else 1.0 * 0.75 for i in sub_i]                 # reference :421, :430
+            count1[slots] = 0                                                        # searched: present, maybe empty
+            live, sc, ro, cn = r.chunk_bm25.search_batch_arrays(texts, top_k=n_fetch, doc_filters=[doc_filters[q] for q in sub_q])
+            if len(live):
+                ls, k = slots[live], ro.shape[1]
+                bm_rows[ls, :k] = ro
+                keys2[ls, :k] = np.where(ro >= 0, keymap[np.maximum(ro, 0)], -1)
+                score2[ls, :k] = sc
+                count1[ls] = cn
+        # (an empty filter filters nothing: reference :226, :391)
+        packed.set_filters({q: tables.groups_allowed(f) for q, f in enumerate(doc_filters) if f}, tables.n_groups)
 
         # one upload: every host array in one buffer (8-byte fields first)
         parts = [("keys", packed.keys), ("score", packed.score), ("weight", packed.weight), ("slot", dense_slot), ("kind", packed.kind),
