@@ -1,5 +1,6 @@
 // k_rows.hpp — row-wise kernels: K1 L2-normalise (+ tiled fp16 scan copy), gather, exact scoring, dense select.
-// One 64-lane wavefront owns one row: 16 B/lane coalesced loads, fp64 lane-order sums (oracle/rdx_oracle.c).
+// One 64-lane wavefront owns one row: 16 B/lane coalesced loads, fp64 lane-order sums (oracle/rdx_oracle.c: see exact_dot4).
+// The exact path's kernels take ExactParams / SelectParams; RowIds and TopkOut are the value types they share with k_refine.
 #pragma once
 #include "rdx_common.hpp"
 
@@ -38,6 +39,15 @@ __device__ __forceinline__ MasterRow master_row(const MasterView& mv, int64_t r,
     m.den = mv.f32 ? 1.0 : mv.den[r];
     return m;
 }
+
+// The id a search returns for a local row: through the shard's (strictly increasing) row-id map, or local + base without one.
+// The one place that says so: k_refine's ranking and k_select_dense's three collections go through of().
+struct RowIds {
+    int64_t base;
+    const int64_t* map;
+    __device__ __forceinline__ int64_t of(int64_t local) const { return map ? map[local] : local + base; }
+};
+struct TopkOut { float* score; int64_t* row; int32_t* count; };   // a search's answers: [nq][k], [nq][k] returned ids, [nq]
 
 // write the 4 consecutive elements k..k+3 of a normalised row into a scan copy (corpus: fragment order, queries: LDS images)
 template <bool QUERY>
@@ -185,34 +195,64 @@ __global__ __launch_bounds__(256) void k_gather_raw(MasterView master, const int
     if (lane == 0) out.den[i] = master.den[r];
 }
 
+// The exact score's arithmetic, stated once. oracle/rdx_oracle.c sums a row's products per LANE — lane l takes the float4 groups
+// l, l + 64, ... in increasing order, and within a group x, y, z, w — into one fp64 accumulator, then adds the 64 lanes by the
+// butterfly of wave_sum. A product of two floats is exact in fp64 (fused or not), so the score's bits depend only on the ORDER of
+// the additions. Every site that scores a row keeps that order and therefore those bits: exact_score, k_exact_scores and
+// k_refine's re-score through exact_dot4; k_exact_scores_reg with the query widened to doubles beforehand (the same operands).
+// A group past the row's end (lane_groups) multiplies by a zero query: it adds zeros, which leave a sum that started at +0.0 as it is.
+__device__ __forceinline__ void exact_dot4(double& acc, const float4& q, const float4& c) {
+    acc += (double)q.x * (double)c.x;
+    acc += (double)q.y * (double)c.y;
+    acc += (double)q.z * (double)c.z;
+    acc += (double)q.w * (double)c.w;
+}
+
+// A lane's U float4 groups of a row of n4 <= 64 U groups kept in registers: gi = lane + 64 u, clamped (a group past the row's end
+// re-reads the last one: no branch around loads), gv = whether the group exists (its query values are zeros where it does not).
+template <int U>
+struct lane_groups {
+    int gi[U];
+    bool gv[U];
+    __device__ __forceinline__ lane_groups(int lane, int n4) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            gv[u] = lane + 64 * u < n4;
+            gi[u] = gv[u] ? lane + 64 * u : n4 - 1;
+        }
+    }
+    __device__ __forceinline__ void load(const MasterRow& row4, float4 (&c)[U]) const {
+#pragma unroll
+        for (int u = 0; u < U; ++u) c[u] = row4[gi[u]];
+    }
+};
+
 // exact score of one normalised query (float4 view, global or LDS) against one master row, all 64 lanes get it
 template <class Q4>
 __device__ __forceinline__ float exact_score(const MasterRow& row4, Q4 q4, int n4, int lane) {
     double acc = 0.0;
-    for (int g = lane; g < n4; g += 64) {
-        const float4 c = row4[g];
-        const float4 q = q4[g];
-        acc += (double)q.x * (double)c.x;
-        acc += (double)q.y * (double)c.y;
-        acc += (double)q.z * (double)c.z;
-        acc += (double)q.w * (double)c.w;
-    }
+    for (int g = lane; g < n4; g += 64) exact_dot4(acc, q4[g], row4[g]);
     return (float)wave_sum(acc);
 }
 
 // K5a. Exact scores of up to QX queries against EVERY row (small problems, huge k, overflow fallback):
 // out[j][r] = score(q_list[j], r), or -inf when the row fails the `where` pre-filter.
 constexpr int QX = 4;
-__global__ __launch_bounds__(256) void k_exact_scores(MasterView master, int64_t rows, int dim,
-                                                      const float* __restrict__ qhat, const int32_t* __restrict__ q_list,
-                                                      int nq, const uint32_t* __restrict__ allow,
-                                                      float* __restrict__ out, unsigned long long* __restrict__ t_first_inv) {
+struct ExactParams {   // of k_exact_scores and k_exact_scores_reg<U>; run_exact changes q_list and nq per group of QX queries
+    MasterView master; int64_t rows; int dim;
+    const float* qhat; const int32_t* q_list; int nq;   // the normalised queries [..][dim], and which nq <= QX of them
+    const uint32_t* allow; float* out;                  // the `where` bitmap or NULL; [nq][rows]
+    unsigned long long* t_first_inv;                    // profile = 3: max(~clock) over the blocks' starts (RefineCounters), or NULL
+};
+
+__global__ __launch_bounds__(256) void k_exact_scores(const ExactParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (t_first_inv && threadIdx.x == 0) atomicMax(t_first_inv, ~wall_clock64());   // profile = 3: earliest block start
+    if (p.t_first_inv && threadIdx.x == 0) atomicMax(p.t_first_inv, ~wall_clock64());   // profile = 3: earliest block start
     float4* q4 = reinterpret_cast<float4*>(smem);   // [nq][dim/4]
-    const int n4 = dim >> 2;
+    const int n4 = p.dim >> 2, nq = p.nq;
+    const int64_t rows = p.rows;
     for (int j = 0; j < nq; ++j) {
-        const float4* src = reinterpret_cast<const float4*>(qhat + (int64_t)q_list[j] * dim);
+        const float4* src = reinterpret_cast<const float4*>(p.qhat + (int64_t)p.q_list[j] * p.dim);
         for (int g = threadIdx.x; g < n4; g += blockDim.x) q4[j * n4 + g] = src[g];
     }
     __syncthreads();
@@ -221,10 +261,10 @@ __global__ __launch_bounds__(256) void k_exact_scores(MasterView master, int64_t
     const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
     // A wave owns rows wave0, wave0 + nwaves, ...; the loads of a row's next four float4 groups are all issued before the
     // first of them is used (four independent 1 KiB requests in flight per wave instead of one: the kernel is latency-bound
-    // at the reference's 16,919 rows). Per lane the groups are still added in increasing g: the oracle's lane order.
+    // at the reference's 16,919 rows). Per lane the groups are still added in increasing g: the oracle's lane order (exact_dot4).
     for (int64_t r = wave0; r < rows; r += nwaves) {
-        const bool ok = !allow || ((allow[r >> 5] >> (r & 31)) & 1u);
-        const MasterRow row4 = master_row(master, r, dim);
+        const bool ok = !p.allow || ((p.allow[r >> 5] >> (r & 31)) & 1u);
+        const MasterRow row4 = master_row(p.master, r, p.dim);
         double acc[QX];
 #pragma unroll
         for (int j = 0; j < QX; ++j) acc[j] = 0.0;
@@ -237,15 +277,8 @@ __global__ __launch_bounds__(256) void k_exact_scores(MasterView master, int64_t
                 for (int u = 0; u < 4; ++u) {
                     if (g0 + 64 * u < n4) {
 #pragma unroll
-                        for (int j = 0; j < QX; ++j) {
-                            if (j < nq) {
-                                const float4 q = q4[j * n4 + g0 + 64 * u];
-                                acc[j] += (double)q.x * (double)c[u].x;
-                                acc[j] += (double)q.y * (double)c[u].y;
-                                acc[j] += (double)q.z * (double)c[u].z;
-                                acc[j] += (double)q.w * (double)c[u].w;
-                            }
-                        }
+                        for (int j = 0; j < QX; ++j)
+                            if (j < nq) exact_dot4(acc[j], q4[j * n4 + g0 + 64 * u], c[u]);
                     }
                 }
             }
@@ -254,7 +287,7 @@ __global__ __launch_bounds__(256) void k_exact_scores(MasterView master, int64_t
         for (int j = 0; j < QX; ++j) {
             if (j < nq) {
                 const float s = (float)wave_sum(acc[j]);
-                if (lane == 0) out[(int64_t)j * rows + r] = ok ? s : -INFINITY;
+                if (lane == 0) p.out[(int64_t)j * rows + r] = ok ? s : -INFINITY;
             }
         }
     }
@@ -266,41 +299,28 @@ __global__ __launch_bounds__(256) void k_exact_scores(MasterView master, int64_t
 // (2 blocks per CU) that a wave keeps them over ~8 rows. (2) The next row's loads are issued before the current row is
 // summed (two rows in flight per wave). (3) The four per-query butterflies run as ONE transposed butterfly: after the m = 32
 // stage a lane keeps two of the four partial sums, after m = 16 one, so 14 cross-lane dword moves and 7 additions replace 48
-// and 24 — every addition pairs the same two values as wave_sum's butterfly (lane order, oracle/rdx_oracle.c), so the bits
+// and 24 — every addition pairs the same two values as wave_sum's butterfly (the order stated at exact_dot4), so the bits
 // are the same. The sum of query j ends on lanes with (lane >> 4) == j.
 template <int U>
-__global__ __launch_bounds__(256, 2) void k_exact_scores_reg(MasterView master, int64_t rows, int dim,
-                                                             const float* __restrict__ qhat, const int32_t* __restrict__ q_list,
-                                                             int nq, const uint32_t* __restrict__ allow, float* __restrict__ out,
-                                                             unsigned long long* __restrict__ t_first_inv) {
-    if (t_first_inv && threadIdx.x == 0) atomicMax(t_first_inv, ~wall_clock64());   // profile = 3: earliest block start
-    const int n4 = dim >> 2;
+__global__ __launch_bounds__(256, 2) void k_exact_scores_reg(const ExactParams p) {
+    if (p.t_first_inv && threadIdx.x == 0) atomicMax(p.t_first_inv, ~wall_clock64());   // profile = 3: earliest block start
+    const int dim = p.dim, n4 = dim >> 2, nq = p.nq;
+    const int64_t rows = p.rows;
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
     if (wave0 >= rows) return;
-    int gi[U];        // this lane's float4 groups (clamped: a group past the row's end re-reads the last one and counts as zeros)
-    bool gv[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        gv[u] = lane + 64 * u < n4;
-        gi[u] = gv[u] ? lane + 64 * u : n4 - 1;
-    }
-    auto load_row = [&](int64_t r, float4 (&c)[U]) __attribute__((always_inline)) {
-        const MasterRow row4 = master_row(master, r, dim);
-#pragma unroll
-        for (int u = 0; u < U; ++u) c[u] = row4[gi[u]];
-    };
+    const lane_groups<U> grp(lane, n4);
     float4 cur[U], nxt[U];
-    load_row(wave0, cur);
+    grp.load(master_row(p.master, wave0, dim), cur);
     double qd[QX][U][4];
 #pragma unroll
     for (int j = 0; j < QX; ++j) {
-        const float4* src = reinterpret_cast<const float4*>(qhat + (int64_t)q_list[j < nq ? j : 0] * dim);
+        const float4* src = reinterpret_cast<const float4*>(p.qhat + (int64_t)p.q_list[j < nq ? j : 0] * dim);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const float4 q = src[gi[u]];
-            const bool on = j < nq && gv[u];
+            const float4 q = src[grp.gi[u]];
+            const bool on = j < nq && grp.gv[u];
             qd[j][u][0] = on ? (double)q.x : 0.0;
             qd[j][u][1] = on ? (double)q.y : 0.0;
             qd[j][u][2] = on ? (double)q.z : 0.0;
@@ -310,8 +330,8 @@ __global__ __launch_bounds__(256, 2) void k_exact_scores_reg(MasterView master, 
     const bool hi32 = (lane & 32) != 0, hi16 = (lane & 16) != 0;
     for (int64_t r = wave0; r < rows; r += nwaves) {
         const int64_t rn = r + nwaves < rows ? r + nwaves : r;   // (the last iteration re-reads its own row: no branch around loads)
-        load_row(rn, nxt);
-        const bool ok = !allow || ((allow[r >> 5] >> (r & 31)) & 1u);
+        grp.load(master_row(p.master, rn, dim), nxt);
+        const bool ok = !p.allow || ((p.allow[r >> 5] >> (r & 31)) & 1u);
         double acc[QX];
 #pragma unroll
         for (int j = 0; j < QX; ++j) acc[j] = 0.0;
@@ -337,7 +357,7 @@ __global__ __launch_bounds__(256, 2) void k_exact_scores_reg(MasterView master, 
 #pragma unroll
         for (int m = 8; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
         const int j = lane >> 4;
-        if ((lane & 15) == 0 && j < nq) out[(int64_t)j * rows + r] = ok ? (float)v : -INFINITY;
+        if ((lane & 15) == 0 && j < nq) p.out[(int64_t)j * rows + r] = ok ? (float)v : -INFINITY;
 #pragma unroll
         for (int u = 0; u < U; ++u) cur[u] = nxt[u];
     }
@@ -396,23 +416,29 @@ __device__ unsigned long long g_select_stamps[16];
 #else
 #define RDX_STAMP(i) do { } while (0)
 #endif
-__device__ __forceinline__ void select_dense_query(const float* __restrict__ scores, int64_t rows,
-                                                   const int32_t* __restrict__ q_list, int k, int64_t row_base,
-                                                   const int64_t* __restrict__ row_map,
-                                                   float* __restrict__ out_score, int64_t* __restrict__ out_row,
-                                                   int32_t* __restrict__ out_count, unsigned long long* __restrict__ t_last) {
+struct SelectParams {   // of select_dense_query / k_select_dense; run_exact changes q_list per group of QX queries
+    const float* scores; int64_t rows; const int32_t* q_list; int k;   // what K5a left [gridDim.x][rows]; the query of each block
+    RowIds ids; TopkOut out;
+    unsigned long long* t_last;                                        // profile = 3: latest block end (RefineCounters), or NULL
+};
+
+__device__ __forceinline__ void select_dense_query(const SelectParams& p) {
     __shared__ __attribute__((aligned(16))) uint32_t hist[HIST_WORDS];
     __shared__ uint32_t bc[4];
     __shared__ float s_s[SELECT_MAX_K];
     __shared__ int64_t s_r[SELECT_MAX_K];
     __shared__ int n_sel, n_eq_taken, wave_tot[16];
     const int j = blockIdx.x;
-    const int q = q_list[j];
-    const float* sc = scores + (int64_t)j * rows;
-    float* o_s = out_score + (int64_t)q * k;
-    int64_t* o_r = out_row + (int64_t)q * k;
+    const int q = p.q_list[j];
+    const int64_t rows = p.rows;
+    const int k = p.k;
+    const RowIds ids = p.ids;
+    const float* __restrict__ sc = p.scores + (int64_t)j * rows;
+    float* o_s = p.out.score + (int64_t)q * k;
+    int64_t* o_r = p.out.row + (int64_t)q * k;
+    int32_t* o_c = p.out.count + q;
     if (rows == 0 || k == 0) {
-        rank_and_write(s_s, s_r, 0, k, o_s, o_r, out_count + q);
+        rank_and_write(s_s, s_r, 0, k, o_s, o_r, o_c);
         return;
     }
     RDX_STAMP(0);
@@ -466,7 +492,7 @@ __device__ __forceinline__ void select_dense_query(const float* __restrict__ sco
         if (key > kth) {
             const int pos = atomicAdd(&n_sel, 1);
             s_s[pos] = key == SEL_KEY_ZERO ? sc[i] : key2f(key);   // (a zero keeps its own sign)
-            s_r[pos] = row_map ? row_map[i] : row_base + i;
+            s_r[pos] = ids.of(i);
         } else if (key == kth) {
             const int e = atomicAdd(&n_eq, 1);
             if (e < EQ_CAP) eq_idx[e] = i;
@@ -493,7 +519,7 @@ __device__ __forceinline__ void select_dense_query(const float* __restrict__ sco
             for (int f = 0; f < ne; ++f) rank += eq_idx[f] < i;
             if (rank < need_eq) {
                 s_s[(int)n_gt + rank] = sc[i];
-                s_r[(int)n_gt + rank] = row_map ? row_map[i] : row_base + i;
+                s_r[(int)n_gt + rank] = ids.of(i);
             }
         }
     } else {
@@ -510,7 +536,7 @@ __device__ __forceinline__ void select_dense_query(const float* __restrict__ sco
             const int my = before + __popcll(m & ((1ull << lane) - 1ull));
             if (eq && my < need_eq) {
                 s_s[(int)n_gt + my] = sc[i];
-                s_r[(int)n_gt + my] = row_map ? row_map[i] : row_base + i;
+                s_r[(int)n_gt + my] = ids.of(i);
             }
             __syncthreads();
             if (threadIdx.x == 0) {
@@ -524,20 +550,20 @@ __device__ __forceinline__ void select_dense_query(const float* __restrict__ sco
     __syncthreads();
     RDX_STAMP(4);
     // drop -inf (filtered) entries: they sort last, so count the finite prefix after ranking
-    int p = (int)kk;
+    const int n_top = (int)kk;
     __shared__ int n_fin;
     if (threadIdx.x == 0) n_fin = 0;
     __syncthreads();
     int loc = 0;
-    for (int i = threadIdx.x; i < p; i += blockDim.x) loc += (s_s[i] > -INFINITY);
+    for (int i = threadIdx.x; i < n_top; i += blockDim.x) loc += (s_s[i] > -INFINITY);
     if (loc) atomicAdd(&n_fin, loc);
     __syncthreads();
     const int valid = n_fin;
     RDX_STAMP(5);
-    rank_and_write(s_s, s_r, p, valid < k ? valid : k, o_s, o_r, out_count + q);
-    if (t_last) {   // profile = 3: latest block end
+    rank_and_write(s_s, s_r, n_top, valid < k ? valid : k, o_s, o_r, o_c);
+    if (p.t_last) {   // profile = 3: latest block end
         __syncthreads();
-        if (threadIdx.x == 0) atomicMax(t_last, wall_clock64());
+        if (threadIdx.x == 0) atomicMax(p.t_last, wall_clock64());
     }
     RDX_STAMP(6);
     // rank_and_write filled [valid, k) only up to its own k argument; pad the rest

@@ -1,5 +1,7 @@
 // rdx_index.hip — the dense index of librdx: the rdx_index lifecycle, options and ingest, rdx_l2_normalize, the search, masks,
 // merge and signal of include/rdx.h. The only unit that holds a k_scan kernel (rag_dpo_amd/build.py checks that).
+// The scans and the tail of a search are launched from parameter structs filled by name: enqueue_scan fills ScanParams and its split-K kin,
+// refine_params fills k_refine's RefineParams, run_exact fills the exact path's ExactParams and SelectParams.
 #include "rdx_host.hpp"
 
 #include <cmath>
@@ -242,35 +244,52 @@ static int launch_scan_i8(rdx_index* h, bool fused, const ScanParams& p, int gri
     return launch_scan<256, EPI_EMIT, false, false, false, true>(h, p, grid, st);
 }
 
+// K5a for dim <= 1024 with U = float4 groups per lane: queries in registers, two rows in flight per wave, 2 blocks per CU (all
+// resident at once)
+template <int U>
+static void launch_exact_reg(const rdx_index* h, const ExactParams& ep, hipStream_t st) {
+    const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>((h->rows + 3) / 4, (int64_t)h->n_cu * 2)));
+    hipLaunchKernelGGL(k_exact_scores_reg<U>, g, dim3(256), 0, st, ep);
+}
+
 // exact full scan for the queries listed in d_list[0..n_list)
 static int run_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, const uint32_t* d_allow, float* d_score,
                      int64_t* d_row, int32_t* d_count, hipStream_t st, bool stamps = false, const FinishArgs* fin = nullptr) {
     const FinishArgs no_fin = {};   // (ctr == NULL: the launch does not end a search)
-    // profile = 3: the scoring kernel's first block and the select kernel's last block leave their times in the counter block
-    unsigned long long* t_first = stamps ? reinterpret_cast<unsigned long long*>(h->ctr.as<char>() + offsetof(RefineCounters, t_first_inv)) : nullptr;
-    unsigned long long* t_last = stamps ? reinterpret_cast<unsigned long long*>(h->ctr.as<char>() + offsetof(RefineCounters, t_last)) : nullptr;
     RDX_TRY(h->dense.ensure((size_t)QX * std::max<int64_t>(h->rows, 1) * 4));
+    // profile = 3: the scoring kernel's first block and the select kernel's last block leave their times in the counter block
+    char* const ctr = stamps ? h->ctr.as<char>() : nullptr;
+    ExactParams ep = {};   // (q_list and nq: per group of QX queries, below)
+    ep.master = h->mv();
+    ep.rows = h->rows;
+    ep.dim = h->dim;
+    ep.qhat = h->qhat.as<float>();
+    ep.allow = d_allow;
+    ep.out = h->dense.as<float>();
+    ep.t_first_inv = ctr ? reinterpret_cast<unsigned long long*>(ctr + offsetof(RefineCounters, t_first_inv)) : nullptr;
+    SelectParams sel = {};
+    sel.scores = h->dense.as<float>();
+    sel.rows = h->rows;
+    sel.k = k;
+    sel.ids = RowIds{h->row_base, h->store.ids()};
+    sel.out = TopkOut{d_score, d_row, d_count};
+    sel.t_last = ctr ? reinterpret_cast<unsigned long long*>(ctr + offsetof(RefineCounters, t_last)) : nullptr;
     const int grid_rows = (int)std::min<int64_t>((h->rows + 3) / 4, (int64_t)h->n_cu * 16);   // one row per wave up to 16 Ki rows
     for (int j0 = 0; j0 < n_list; j0 += QX) {
-        const int nq = std::min(QX, n_list - j0);
+        ep.q_list = sel.q_list = d_list + j0;
+        ep.nq = std::min(QX, n_list - j0);
         if (h->rows > 0 && h->dim <= 1024) {
-            // queries in registers, two rows in flight per wave, 2 blocks per CU (all resident at once)
             const int u = (h->dim / 4 + 63) / 64;
-            const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>((h->rows + 3) / 4, (int64_t)h->n_cu * 2))), b(256);
-#define RDX_K5A(U) hipLaunchKernelGGL(k_exact_scores_reg<U>, g, b, 0, st, h->mv(), h->rows, h->dim, h->qhat.as<float>(), d_list + j0, nq, d_allow, h->dense.as<float>(), t_first)
-            if (u == 1) RDX_K5A(1);
-            else if (u == 2) RDX_K5A(2);
-            else if (u == 3) RDX_K5A(3);
-            else RDX_K5A(4);
-#undef RDX_K5A
+            if (u == 1) launch_exact_reg<1>(h, ep, st);
+            else if (u == 2) launch_exact_reg<2>(h, ep, st);
+            else if (u == 3) launch_exact_reg<3>(h, ep, st);
+            else launch_exact_reg<4>(h, ep, st);
             HIP_TRY(hipGetLastError());
         } else if (h->rows > 0) {
-            hipLaunchKernelGGL(k_exact_scores, dim3(std::max(grid_rows, 1)), dim3(256), (size_t)nq * h->dim * 4, st, h->mv(),
-                               h->rows, h->dim, h->qhat.as<float>(), d_list + j0, nq, d_allow, h->dense.as<float>(), t_first);
+            hipLaunchKernelGGL(k_exact_scores, dim3(std::max(grid_rows, 1)), dim3(256), (size_t)ep.nq * h->dim * 4, st, ep);
             HIP_TRY(hipGetLastError());
         }
-        hipLaunchKernelGGL(k_select_dense, dim3(nq), dim3(1024), 0, st, h->dense.as<float>(), h->rows, d_list + j0, k, h->row_base,
-                           h->store.ids(), d_score, d_row, d_count, t_last, (fin && j0 + QX >= n_list) ? *fin : no_fin);
+        hipLaunchKernelGGL(k_select_dense, dim3(ep.nq), dim3(1024), 0, st, sel, (fin && j0 + QX >= n_list) ? *fin : no_fin);
         HIP_TRY(hipGetLastError());
     }
     return RDX_OK;
@@ -324,6 +343,33 @@ static FinishArgs finish_args(const rdx_index* h, const SearchPlan& p, const Sea
     f.out_flags = io.flags;
     f.may_redo = (!p.exact_only && p.depth == 0) ? 1 : 0;
     return f;
+}
+
+// what k_refine is told about a plan's search (refine_kernel.hpp RefineParams). An int8 search (p.i8) is refined against the
+// bounds and thresholds k_tau8 left: 2 E_q per query, and tau_s, which is in score units already.
+static RefineParams refine_params(const rdx_index* h, const SearchPlan& p, const SearchIO& io) {
+    RefineParams r = {};
+    r.cand = h->cand.as<uint2>();
+    r.cntw = h->cntw.as<uint32_t>();
+    r.n_streams = p.n_streams;
+    r.capw = p.capw;
+    r.list_cap = p.list_cap;
+    r.k = p.k;
+    r.two_e = h->two_e();
+    r.pilot = p.pilot;
+    r.two_e_q = p.i8 ? h->twoe8.as<float>() : nullptr;
+    r.tau = p.i8 ? h->taus8.as<float>() : h->tau.as<float>();
+    r.inv_scale2 = p.i8 ? 1.0f : std::ldexp(1.0f, -2 * h->scale_log2);
+    r.qhat = h->qhat.as<float>();
+    r.master = h->mv();
+    r.dim = h->dim;
+    r.ids = RowIds{h->row_base, h->store.ids()};
+    r.out = TopkOut{io.score, io.row, io.count};
+    r.exact_list = h->exact_list.as<int32_t>();
+    r.ctr = h->ctr.as<RefineCounters>();
+    r.spill_cap = p.spill_cap;
+    r.spill = p.spill ? h->spill.as<uint2>() : nullptr;
+    return r;
 }
 
 // the MFMA path of a plan: bootstrap (k_boot or k_scan<EPI_SETMAX>), k_tau, main scan (k_scan_small or k_scan<EPI_EMIT>), k_refine
@@ -405,11 +451,7 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
     const size_t lds = (size_t)p.list_cap * 8;
     const auto refine = p.spill ? k_refine<true> : k_refine<false>;
     RDX_TRY(dynamic_lds(h->device, (const void*)refine, lds));
-    hipLaunchKernelGGL(refine, dim3((int)p.nq), dim3(1024), lds, st, h->cand.as<uint2>(), h->cntw.as<uint32_t>(), p.n_streams, p.capw,
-                       p.list_cap, p.k, h->two_e(), p.i8 ? h->twoe8.as<float>() : nullptr, h->qhat.as<float>(), h->mv(), h->dim, h->row_base,
-                       h->store.ids(), io.score, io.row, io.count, h->exact_list.as<int32_t>(), h->ctr.as<RefineCounters>(),
-                       p.i8 ? h->taus8.as<float>() : h->tau.as<float>(), p.i8 ? 1.0f : sp.inv_scale2, p.pilot, p.spill_cap,
-                       p.spill ? h->spill.as<uint2>() : nullptr, fin);
+    hipLaunchKernelGGL(refine, dim3((int)p.nq), dim3(1024), lds, st, refine_params(h, p, io), fin);
     HIP_TRY(hipGetLastError());
     mark(h, p, st, 5);
     return RDX_OK;

@@ -1,5 +1,5 @@
 // refine_kernel.hpp — K4: exact re-score + final ordering of the scan's candidates, and C1's merge of per-shard
-// partial results after the RCCL all-gather.
+// partial results after the RCCL all-gather. k_refine (RefineParams) and k_select_dense (SelectParams, k_rows.hpp) each end a search.
 #pragma once
 #include "k_rows.hpp"
 
@@ -161,56 +161,226 @@ struct RefineLds {
     int n_p, overflow;
 };
 
-// A query's m > 0 hits, counted and prefixed by refine_block (L.seg_off), are gathered into `list` and answered. The list lives in
-// LDS (SPILL = false: at most list_cap <= REFINE_LIST entries) or in the query's row of the spill buffer in HBM (SPILL = true: at
-// most spill_cap entries, L2-resident while the block works on it): the same statements, so which rows are re-scored does not
-// depend on where the list lives.
-template <bool SPILL>
-__device__ __forceinline__ void refine_list(RefineLds& L, uint2* const list, const uint32_t m, const int q,
-                                            const uint2* __restrict__ cand, int n_streams, uint32_t capw, int k, float two_e,
-                                            const float* __restrict__ two_e_q, const float* __restrict__ qhat, MasterView master, int dim,
-                                            int64_t row_base, const int64_t* __restrict__ row_map,
-                                            float* __restrict__ out_score, int64_t* __restrict__ out_row,
-                                            int32_t* __restrict__ out_count, int32_t* __restrict__ exact_list,
-                                            RefineCounters* __restrict__ ctr, const float* __restrict__ tau, float inv_scale2,
-                                            int pilot) {
-    uint32_t* const hist = L.hist;
-    uint32_t* const bc = L.bc;
-    const uint32_t* const seg_off = L.seg_off;
-    float* const s_s = L.s_s;
-    int64_t* const s_r = L.s_r;
-    int* const wtot = L.wtot;
-    int& n_p = L.n_p;
-    float* o_s = out_score + (int64_t)q * k;
-    int64_t* o_r = out_row + (int64_t)q * k;
-    // gather: one thread per ENTRY — its segment is the last w with seg_off[w] <= i (binary search of the prefix in LDS), so every
-    // thread has loads in flight and none depends on another (a thread per segment was 64 of 1024 threads at c4, each walking
-    // 40-125 dependent 8-byte loads). The entries keep their order: segment after segment.
-    for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) {
-        int lo = 0, hi = n_streams;                         // seg_off[lo] <= i < seg_off[hi]
+// Everything k_refine is told (FinishArgs apart), grouped by what reads it; refine_params (rdx_index.hip) fills it by name.
+struct RefineParams {
+    const uint2* cand; const uint32_t* cntw; int n_streams; uint32_t capw, list_cap;   // the scan's hit segments; entries of the LDS list
+    // thresholds and bands: 2E of the fp16 pass, or [nq] 2 E_q of the int8 pass (else NULL); tau[q] * inv_scale2 = the scan's threshold
+    // in score units (int8: tau_s and 1); option "refine_pilot"
+    int k; float two_e; const float* two_e_q; const float* tau; float inv_scale2; int pilot;
+    const float* qhat; MasterView master; int dim;   // the exact re-score: the normalised queries [nq][dim] against the master rows
+    RowIds ids; TopkOut out;
+    int32_t* exact_list; RefineCounters* ctr;        // queries handed to the fallback passes (RefineCounters::n_exact of them)
+    uint32_t spill_cap; uint2* spill;                // MAY_SPILL: [nq_pad][spill_cap] in HBM
+};
+
+// One block's query: its m > 0 hits (counted and prefixed in L.seg_off by refine_block) live in `list`, in LDS or in its spill row.
+struct RefineQuery { RefineLds& L; uint2* list; uint32_t m; int q; };
+
+// The stages of refine_list, in the order it calls them (DESIGN.md §5 has the table and the measurements behind each).
+// gather: one thread per ENTRY — its segment is the last w with seg_off[w] <= i (binary search of the prefix in LDS), so every
+// thread has loads in flight and none depends on another. The entries keep their order: segment after segment.
+__device__ __forceinline__ void gather_hits(const RefineParams& p, const RefineQuery& c) {
+    const uint32_t* const seg_off = c.L.seg_off;
+    for (uint32_t i = threadIdx.x; i < c.m; i += blockDim.x) {
+        int lo = 0, hi = p.n_streams;                       // seg_off[lo] <= i < seg_off[hi]
         while (hi - lo > 1) {
             const int mid = (lo + hi) >> 1;
             if (seg_off[mid] <= i) lo = mid;
             else hi = mid;
         }
-        list[i] = cand[((int64_t)q * n_streams + lo) * capw + (i - seg_off[lo])];
+        c.list[i] = p.cand[((int64_t)c.q * p.n_streams + lo) * p.capw + (i - seg_off[lo])];
     }
     __syncthreads();
+}
+
+// threshold: the rank-th largest coarse score of the hits; a query whose threshold cannot be verified goes to the fallback passes
+__device__ __forceinline__ float coarse_kth(const RefineQuery& c, int64_t rank) {
+    const uint2* const list = c.list;
+    int64_t n_gt;
+    return key2f(block_kth_largest([&](int64_t i) { return f2key(__uint_as_float(list[i].x)); }, c.m, rank, c.L.hist, c.L.bc, &n_gt));
+}
+__device__ __forceinline__ void to_fallback(const RefineParams& p, int q) {
+    if (threadIdx.x == 0) {
+        atomicAdd(&p.ctr->spec_fail, 1);
+        p.exact_list[atomicAdd(&p.ctr->n_exact, 1)] = q;
+    }
+}
+// The int8 pass is verified AFTER the exact re-score, against the exact k-th score X of the hits: complete iff X - E_q >= tau
+// (with E_q ~14x the fp16 E, c_k - 2E >= tau would reject most speculative thresholds). False: left for the fallback.
+__device__ __forceinline__ bool verify_exact(const RefineParams& p, int q, float tq, uint32_t kth_key) {
+    if (!p.two_e_q || !(tq > -INFINITY) || key2f(kth_key) - 0.5f * p.two_e_q[q] >= tq) return true;
+    to_fallback(p, q);
+    return false;
+}
+
+// collect: rows of the hits with lo <= coarse < hi are appended to s_r (n_p counts them all, the arrays take the first REFINE_PMAX)
+__device__ __forceinline__ void reset_count(RefineLds& L) {
+    if (threadIdx.x == 0) L.n_p = 0;
+    __syncthreads();
+}
+__device__ __forceinline__ int collect_band(const RefineQuery& c, float lo, float hi) {
+    for (uint32_t i = threadIdx.x; i < c.m; i += blockDim.x) {
+        const uint2 e = c.list[i];
+        const float cs = __uint_as_float(e.x);
+        if (cs >= lo && cs < hi) {
+            const int pos = atomicAdd(&c.L.n_p, 1);
+            if (pos < REFINE_PMAX) c.L.s_r[pos] = (int64_t)e.y;
+        }
+    }
+    __syncthreads();
+    return c.L.n_p;
+}
+
+// re-score: one wave per candidate row, row_at(i) = its row, put(i, s) takes its exact score (the oracle's bits: exact_dot4)
+template <class RowAt, class Put>
+__device__ __forceinline__ void rescore_rows(const RefineParams& p, int q, int cnt, RowAt row_at, Put put) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (int)(blockDim.x >> 6);
+    const int dim = p.dim, n4 = dim >> 2;
+    const float4* q4 = reinterpret_cast<const float4*>(p.qhat + (int64_t)q * dim);
+    if (n4 <= 256) {
+        // dim <= 1024: the query sits in registers (converted once per block, not once per candidate), a row's four 1 KiB pieces
+        // are requested together and the NEXT candidate's pieces before this one is summed.
+        const lane_groups<4> grp(lane, n4);
+        float4 qf[4];                                       // (kept as floats, widened at use: 16 registers instead of 32)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float4 qq = q4[grp.gi[u]];
+            qf[u] = grp.gv[u] ? qq : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        float4 cur[4], nxt[4];
+        if (wave < cnt) grp.load(master_row(p.master, row_at(wave), dim), cur);
+        for (int i = wave; i < cnt; i += nw) {
+            grp.load(master_row(p.master, row_at(i + nw < cnt ? i + nw : i), dim), nxt);   // (the last one re-reads its own row: no branch around loads)
+            double acc = 0.0;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) exact_dot4(acc, qf[u], cur[u]);
+            const float sx = (float)wave_sum(acc);
+            if (lane == 0) put(i, sx);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) cur[u] = nxt[u];
+        }
+        // (a third row in flight per wave — the loop is 9 dependent ~2 us round trips at c3 — needs 16 more registers than the
+        //  1024-thread block has: 17 spilled. Measured instead: profiles/r04/refine_stamps.txt)
+    } else {
+        for (int i = wave; i < cnt; i += nw) {
+            const float sx = exact_score(master_row(p.master, row_at(i), dim), q4, n4, lane);
+            if (lane == 0) put(i, sx);
+        }
+    }
+}
+
+// rank: local -> returned row id (RowIds, k_rows.hpp), then the best k of the n entries of the ranking arrays (score desc, row asc)
+__device__ __forceinline__ void rank_rows(const RefineParams& p, const RefineQuery& c, int n) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) c.L.s_r[i] = p.ids.of(c.L.s_r[i]);
+    __syncthreads();
+    rank_and_write(c.L.s_s, c.L.s_r, n, p.k, p.out.score + (int64_t)c.q * p.k, p.out.row + (int64_t)c.q * p.k, p.out.count + c.q);
+}
+
+// crowded band, the ranking arrays refilled: of the list's first n (exact score, row) what lies above the k-th key or ties with ~row >= rkey
+__device__ __forceinline__ int take_reaching(const RefineQuery& c, int n, uint32_t kth, uint32_t rkey) {
+    reset_count(c.L);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const uint2 e = c.list[i];
+        const uint32_t key = f2key_sel(__uint_as_float(e.x));
+        if (key > kth || (key == kth && ~e.y >= rkey)) {
+            const int at = atomicAdd(&c.L.n_p, 1);
+            if (at < REFINE_PMAX) {
+                c.L.s_s[at] = __uint_as_float(e.x);
+                c.L.s_r[at] = (int64_t)e.y;
+            }
+        }
+    }
+    __syncthreads();
+    return c.L.n_p;
+}
+
+// crowded band: n > REFINE_PMAX rows inside the band [lo, hi), more than the ranking arrays hold (near-duplicate rows stored together:
+// a document's chunks). Its members are compacted to the front of the list, re-scored exactly in place (exact score over coarse
+// score), the k-th largest exact score is found by the radix select, and only what reaches it is ranked. `done` entries of the
+// ranking arrays (the pilot's S1, coarse >= hi) already hold their exact scores.
+__device__ __forceinline__ void crowded_band(const RefineParams& p, const RefineQuery& c, float lo, float hi, int n, int done, float tq) {
+    RefineLds& L = c.L;
+    uint2* const list = c.list;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (int)(blockDim.x >> 6);
+    // The list is compacted in rounds of 7 entries per thread (the LDS list is one round; a spill list takes up to
+    // spill_cap / 7168): a round's members are written behind the earlier rounds' — at or below the round's own first entry, and
+    // every entry up to the round's end was read before the barrier, so nothing unread is overwritten.
+    int base_out = 0;
+    for (uint32_t r0 = 0; r0 < c.m; r0 += 7u * blockDim.x) {
+        uint2 mine[7];
+        bool keep[7];
+        int cnt = 0;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            const uint32_t i = r0 + threadIdx.x * 7 + j;
+            keep[j] = false;
+            if (i < c.m) {
+                mine[j] = list[i];
+                const float cs = __uint_as_float(mine[j].x);
+                keep[j] = cs >= lo && cs < hi;
+            }
+            cnt += keep[j] ? 1 : 0;
+        }
+        int incl = cnt;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int t = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += t;
+        }
+        if (lane == 63) L.wtot[wave] = incl;
+        __syncthreads();                                          // (also: every thread has read its entries of this round)
+        int pos = base_out + incl - cnt;
+        for (int w = 0; w < wave; ++w) pos += L.wtot[w];
+        for (int w = 0; w < nw; ++w) base_out += L.wtot[w];
+#pragma unroll
+        for (int j = 0; j < 7; ++j)
+            if (keep[j]) list[pos++] = mine[j];
+        __syncthreads();
+    }
+    // (two rounds: the n - done rows of S2 were compacted; S1, already exact in the ranking arrays, goes behind them — S1 and
+    //  S2 are disjoint subsets of the m hits, so n <= m slots)
+    for (int i = threadIdx.x; i < done; i += blockDim.x) list[n - done + i] = make_uint2(__float_as_uint(L.s_s[i]), (uint32_t)L.s_r[i]);
+    rescore_rows(p, c.q, n - done, [&](int i) { return (int64_t)list[i].y; }, [&](int i, float sx) { list[i].x = __float_as_uint(sx); });
+    __syncthreads();
+    const int64_t kk2 = p.k < n ? p.k : n;
+    int64_t n_gt2;
+    // (selection keys, k_rows.hpp: +0.0 and -0.0 are one score — with f2key a k-th key of +0.0 left the -0.0 rows out of the ties)
+    const uint32_t kth2 = block_kth_largest([&](int64_t i) { return f2key_sel(__uint_as_float(list[i].x)); }, n, kk2, L.hist, L.bc, &n_gt2);
+    if (!verify_exact(p, c.q, tq, kth2)) return;
+    // first EVERY tie (rkey = 0; the ranking orders them by row id): all there is to do unless identical rows fill the ranking arrays
+    int n2 = take_reaching(c, n, kth2, 0u);
+    if (n2 > REFINE_PMAX) {
+        // > 1024 - k rows tie at the k-th score (identical rows; zeros of both signs): of the ties the kk2 - n_gt2 with the LOWEST
+        // rows belong to the answer. The hits' rows are distinct 32-bit local rows (returned ids grow with them: RowIds), so that
+        // many lowest rows are the keys ~row down to their (kk2 - n_gt2)-th largest — one more radix select (non-ties count as
+        // key 0, below every ~row), then kk2 <= k entries are ranked.
+        int64_t n_gt_r;
+        const uint32_t rkey = block_kth_largest(
+            [&](int64_t i) {
+                const uint2 e = list[i];
+                return f2key_sel(__uint_as_float(e.x)) == kth2 ? ~e.y : 0u;
+            },
+            n, kk2 - n_gt2, L.hist, L.bc, &n_gt_r);
+        n2 = take_reaching(c, n, kth2, rkey);
+    }
+    rank_rows(p, c, n2);
+}
+
+// A query's hits are gathered into `list` and answered: the stages above, and the control flow of the two rounds. The list lives in
+// LDS (SPILL = false) or in HBM (SPILL = true): the same statements, so which rows are re-scored does not depend on where it lives.
+template <bool SPILL>
+__device__ __forceinline__ void refine_list(const RefineParams& p, RefineLds& L, uint2* const list, const uint32_t m, const int q) {
+    const RefineQuery c = {L, list, m, q};
+    const int k = p.k;
+    gather_hits(p, c);
     RDX_RSTAMP(2);
     const int64_t kk = (uint32_t)k < m ? k : m;
-    // int8 coarse pass: verified AFTER the exact re-score, against the exact k-th score X of the hits (a row that was not emitted
-    // scores below tau + E_q exactly: the answer is complete iff X - E_q >= tau). Its E_q is ~14x the fp16 E, and the
-    // test before the re-score (c_k - 2E >= tau) would reject most speculative thresholds.
-    const bool late = two_e_q != nullptr;
-    bool two = late && pilot > 0;                           // two rounds: pilot S1, then the band below X1
-    auto coarse_kth = [&](int64_t rank) __attribute__((always_inline)) {
-        int64_t n_gt;
-        return key2f(block_kth_largest([&](int64_t i) { return f2key(__uint_as_float(list[i].x)); }, m, rank, hist, bc, &n_gt));
-    };
-    const int64_t k1 = (int64_t)pilot * k < (int64_t)m ? (int64_t)pilot * k : (int64_t)m;
+    const bool late = p.two_e_q != nullptr;                 // int8 coarse pass: verified after the re-score (verify_exact)
+    bool two = late && p.pilot > 0;                         // two rounds: pilot S1, then the band below X1
+    const int64_t k1 = (int64_t)p.pilot * k < (int64_t)m ? (int64_t)p.pilot * k : (int64_t)m;
     // lower edge of the first collection: c_k - 2E (one band), or c_k1 itself (S1)
     // (int8 coarse pass: the bound is the query's own, two_e_q[q] = 2 E_q, and tau is already in score units — DESIGN.md §5)
-    float t2 = two ? coarse_kth(k1) : coarse_kth(kk) - (two_e_q ? two_e_q[q] : two_e);
+    float t2 = two ? coarse_kth(c, k1) : coarse_kth(c, kk) - (late ? p.two_e_q[q] : p.two_e);
     RDX_RSTAMP(3);
     // Verification of the scan's threshold T (score units). The hits are exactly the allowed rows with coarse >= T. The k best of
     // them have exact >= c_k - E, so the exact k-th best of the corpus is >= c_k - E and every true top-k row has coarse >=
@@ -218,250 +388,75 @@ __device__ __forceinline__ void refine_list(RefineLds& L, uint2* const list, con
     // (k_tau with rank k) passes by construction; a SPECULATIVE one (rank < k: an estimate of where the corpus' k-th score
     // lies) passes unless the estimate was too high — then the query goes to the fallback passes, which use
     // the provable threshold. T = -inf (fewer than k sets sampled): every allowed row was emitted, nothing to verify.
-    const float tq = tau[q] * inv_scale2;
-    auto verify_exact = [&](uint32_t kth_key) __attribute__((always_inline)) {
-        if (!late || !(tq > -INFINITY) || key2f(kth_key) - 0.5f * two_e_q[q] >= tq) return true;
-        if (threadIdx.x == 0) {
-            atomicAdd(&ctr->spec_fail, 1);
-            exact_list[atomicAdd(&ctr->n_exact, 1)] = q;
-        }
-        return false;
-    };
+    const float tq = p.tau[q] * p.inv_scale2;
     if (tq > -INFINITY && ((int64_t)m < (int64_t)k || (!late && t2 < tq))) {
-        if (threadIdx.x == 0) {
-            atomicAdd(&ctr->spec_fail, 1);
-            exact_list[atomicAdd(&ctr->n_exact, 1)] = q;
-        }
+        to_fallback(p, q);
         return;
     }
-    // rows of the hits with lo <= coarse < hi are appended to s_r (n_p counts them all, the arrays take the first REFINE_PMAX)
-    auto collect = [&](float lo, float hi) __attribute__((always_inline)) {
-        for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) {
-            const uint2 e = list[i];
-            const float c = __uint_as_float(e.x);
-            if (c >= lo && c < hi) {
-                const int pos = atomicAdd(&n_p, 1);
-                if (pos < REFINE_PMAX) s_r[pos] = (int64_t)e.y;
-            }
-        }
-        __syncthreads();
-        return n_p;
-    };
-    if (threadIdx.x == 0) n_p = 0;
-    __syncthreads();
-    int p = collect(t2, INFINITY);
-    if (two && p > REFINE_PMAX) {
+    reset_count(L);
+    int n = collect_band(c, t2, INFINITY);
+    if (two && n > REFINE_PMAX) {
         // more than the ranking arrays hold tie at the k1-th coarse score (identical rows): the single band, as without a pilot
         two = false;
-        t2 = coarse_kth(kk) - two_e_q[q];
-        if (threadIdx.x == 0) n_p = 0;
-        __syncthreads();
-        p = collect(t2, INFINITY);
+        t2 = coarse_kth(c, kk) - p.two_e_q[q];
+        reset_count(L);
+        n = collect_band(c, t2, INFINITY);
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float4* q4 = reinterpret_cast<const float4*>(qhat + (int64_t)q * dim);
-    const int n4 = dim >> 2, nw = (int)(blockDim.x >> 6);
-    // exact re-score of `cnt` candidates, one wave per candidate row: row_at(i) = its row, put(i, s) takes its exact score
-    auto rescore = [&](int cnt, auto row_at, auto put) __attribute__((always_inline)) {
-        if (n4 <= 256) {
-            // dim <= 1024: the query sits in registers as doubles (converted once per block, not once per candidate), a row's four
-            // 1 KiB pieces are requested together and the NEXT candidate's pieces before this one is summed. Same products, same
-            // order per lane, same butterfly as exact_score(): the same bits. (c3: k = 100, ~140 candidates per query = 9 dependent
-            // round trips to random HBM rows per wave before.)
-            int gi[4];
-            bool gv[4];
-            float4 qf[4];                                   // (kept as floats, widened at use: 16 registers instead of 32)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                gv[u] = lane + 64 * u < n4;
-                gi[u] = gv[u] ? lane + 64 * u : n4 - 1;
-                const float4 qq = q4[gi[u]];
-                qf[u] = gv[u] ? qq : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            auto load_row = [&](int i, float4 (&c)[4]) __attribute__((always_inline)) {
-                const MasterRow row4 = master_row(master, row_at(i), dim);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) c[u] = row4[gi[u]];
-            };
-            float4 cur[4], nxt[4];
-            if (wave < cnt) load_row(wave, cur);
-            for (int i = wave; i < cnt; i += nw) {
-                load_row(i + nw < cnt ? i + nw : i, nxt);   // (the last one re-reads its own row: no branch around loads)
-                double acc = 0.0;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    acc += (double)qf[u].x * (double)cur[u].x;
-                    acc += (double)qf[u].y * (double)cur[u].y;
-                    acc += (double)qf[u].z * (double)cur[u].z;
-                    acc += (double)qf[u].w * (double)cur[u].w;
-                }
-                const float sx = (float)wave_sum(acc);
-                if (lane == 0) put(i, sx);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) cur[u] = nxt[u];
-            }
-            // (a third row in flight per wave — the loop is 9 dependent ~2 us round trips at c3 — needs 16 more registers than the
-            //  1024-thread block has: 17 spilled. Measured instead: profiles/r04/refine_stamps.txt)
-        } else {
-            for (int i = wave; i < cnt; i += nw) {
-                const float sx = exact_score(master_row(master, row_at(i), dim), q4, n4, lane);
-                if (lane == 0) put(i, sx);
-            }
-        }
-    };
     int done = 0;                                           // entries of s_r / s_s that already hold their exact score (S1)
     float c1 = INFINITY;                                    // the band's upper edge: S1 (coarse >= c1) is not collected twice
     if (two) {
-        rescore(p, [&](int i) { return s_r[i]; }, [&](int i, float sx) { s_s[i] = sx; });
+        rescore_rows(p, q, n, [&](int i) { return L.s_r[i]; }, [&](int i, float sx) { L.s_s[i] = sx; });
         __syncthreads();
-        done = p;
+        done = n;
         c1 = t2;
         // X1 = k-th largest exact score of S1; fewer than k rows in S1 (then S1 is every hit): no bound, the band is empty anyway.
         // t3 = X1 - E_q rounded DOWN (E_q = two_e_q / 2 is exact): every hit with coarse >= X1 - E_q is inside whatever the rounding
         t2 = -INFINITY;
-        if (p >= k) {
+        if (n >= k) {
             int64_t n_gt1;
-            const uint32_t kx = block_kth_largest([&](int64_t i) { return f2key(s_s[i]); }, p, (int64_t)k, hist, bc, &n_gt1);
-            t2 = sub_down(key2f(kx), 0.5f * two_e_q[q]);
+            const uint32_t kx = block_kth_largest([&](int64_t i) { return f2key(L.s_s[i]); }, n, (int64_t)k, L.hist, L.bc, &n_gt1);
+            t2 = sub_down(key2f(kx), 0.5f * p.two_e_q[q]);
         }
-        p = collect(t2, c1);                                // S2 behind S1 (n_p goes on counting)
+        n = collect_band(c, t2, c1);                        // S2 behind S1 (n_p goes on counting)
     }
-    if (threadIdx.x == 0) atomicAdd(&ctr->rescored, (unsigned long long)p);
-    if (p > REFINE_PMAX) {
-        // More rows inside the 2E band than the ranking arrays hold: near-duplicate rows stored together (a document's chunks: their
-        // scores lie closer together than the coarse pass can tell apart, so the band holds hundreds to thousands of them). Until
-        // round 4 such a query paid the exact full scan of the WHOLE corpus (7 ms per 4 queries at 10 M rows: an embedding-like corpus
-        // ran at 2 % of the N(0,1) corpus' speed). The band is small next to the corpus: its members are compacted to the front of the
-        // list (every thread reads 7 entries, then — behind a barrier — writes the members back), re-scored exactly in place
-        // (exact score over coarse score), the k-th largest exact score is found by the radix select, and only what reaches it is ranked.
-        // The list is compacted in rounds of 7 entries per thread (the LDS list is one round; a spill list takes up to
-        // spill_cap / 7168): a round's members are written behind the earlier rounds' — at or below the round's own first entry, and
-        // every entry up to the round's end was read before the barrier, so nothing unread is overwritten.
-        int base_out = 0;
-        for (uint32_t r0 = 0; r0 < m; r0 += 7u * blockDim.x) {
-            uint2 mine[7];
-            bool keep[7];
-            int cnt = 0;
-#pragma unroll
-            for (int j = 0; j < 7; ++j) {
-                const uint32_t i = r0 + threadIdx.x * 7 + j;
-                keep[j] = false;
-                if (i < m) {
-                    mine[j] = list[i];
-                    const float cs = __uint_as_float(mine[j].x);
-                    keep[j] = cs >= t2 && cs < c1;
-                }
-                cnt += keep[j] ? 1 : 0;
-            }
-            int incl = cnt;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const int t = __shfl_up(incl, off, 64);
-                if (lane >= off) incl += t;
-            }
-            if (lane == 63) wtot[wave] = incl;
-            __syncthreads();                                          // (also: every thread has read its entries of this round)
-            int pos = base_out + incl - cnt;
-            for (int w = 0; w < wave; ++w) pos += wtot[w];
-            for (int w = 0; w < nw; ++w) base_out += wtot[w];
-#pragma unroll
-            for (int j = 0; j < 7; ++j)
-                if (keep[j]) list[pos++] = mine[j];
-            __syncthreads();
-        }
-        // (two rounds: the p - done rows of S2 were compacted; S1, already exact in the ranking arrays, goes behind them — S1 and
-        //  S2 are disjoint subsets of the m hits, so p <= m slots)
-        for (int i = threadIdx.x; i < done; i += blockDim.x) list[p - done + i] = make_uint2(__float_as_uint(s_s[i]), (uint32_t)s_r[i]);
-        rescore(p - done, [&](int i) { return (int64_t)list[i].y; }, [&](int i, float sx) { list[i].x = __float_as_uint(sx); });
-        __syncthreads();
-        const int64_t kk2 = k < p ? k : p;
-        int64_t n_gt2;
-        // (selection keys, k_rows.hpp: +0.0 and -0.0 are one score — with f2key a k-th key of +0.0 left the -0.0 rows out of the ties)
-        const uint32_t kth2 = block_kth_largest([&](int64_t i) { return f2key_sel(__uint_as_float(list[i].x)); }, p, kk2, hist, bc, &n_gt2);
-        if (!verify_exact(kth2)) return;
-        // everything above the k-th key and the entries equal to it whose row key reaches `rkey`: first EVERY tie (rkey = 0; the
-        // ranking below orders them by row id), which is all there is to do unless identical rows fill the ranking arrays
-        auto take = [&](uint32_t rkey) __attribute__((always_inline)) {
-            if (threadIdx.x == 0) n_p = 0;
-            __syncthreads();
-            for (int i = threadIdx.x; i < p; i += blockDim.x) {
-                const uint2 e = list[i];
-                const uint32_t key = f2key_sel(__uint_as_float(e.x));
-                if (key > kth2 || (key == kth2 && ~e.y >= rkey)) {
-                    const int at = atomicAdd(&n_p, 1);
-                    if (at < REFINE_PMAX) {
-                        s_s[at] = __uint_as_float(e.x);
-                        s_r[at] = (int64_t)e.y;
-                    }
-                }
-            }
-            __syncthreads();
-            return n_p;
-        };
-        int p2 = take(0u);
-        if (p2 > REFINE_PMAX) {
-            // > 1024 - k rows tie at the k-th score (identical rows; zeros of both signs): of the ties the kk2 - n_gt2 with the LOWEST
-            // rows belong to the answer. The hits' rows are distinct 32-bit local rows (returned ids grow with them: row_base, or the
-            // strictly increasing row id map), so that many lowest rows are the keys ~row down to their (kk2 - n_gt2)-th largest —
-            // one more radix select (non-ties count as key 0, below every ~row), then kk2 <= k entries are ranked.
-            int64_t n_gt_r;
-            const uint32_t rkey = block_kth_largest(
-                [&](int64_t i) {
-                    const uint2 e = list[i];
-                    return f2key_sel(__uint_as_float(e.x)) == kth2 ? ~e.y : 0u;
-                },
-                p, kk2 - n_gt2, hist, bc, &n_gt_r);
-            p2 = take(rkey);
-        }
-        for (int i = threadIdx.x; i < p2; i += blockDim.x) s_r[i] = row_map ? row_map[s_r[i]] : s_r[i] + row_base;
-        __syncthreads();
-        rank_and_write(s_s, s_r, p2, k, o_s, o_r, out_count + q);
+    if (threadIdx.x == 0) atomicAdd(&p.ctr->rescored, (unsigned long long)n);
+    if (n > REFINE_PMAX) {
+        crowded_band(p, c, t2, c1, n, done, tq);
         return;
     }
     RDX_RSTAMP(4);
-    rescore(p - done, [&](int i) { return s_r[done + i]; }, [&](int i, float sx) { s_s[done + i] = sx; });
+    rescore_rows(p, q, n - done, [&](int i) { return L.s_r[done + i]; }, [&](int i, float sx) { L.s_s[done + i] = sx; });
     __syncthreads();
     if (late) {
         int64_t n_gt3;
-        const uint32_t kth3 = block_kth_largest([&](int64_t i) { return f2key(s_s[i]); }, p, (int64_t)(k < p ? k : p), hist, bc, &n_gt3);
-        if (!verify_exact(kth3)) return;
+        const uint32_t kth3 = block_kth_largest([&](int64_t i) { return f2key(L.s_s[i]); }, n, (int64_t)(k < n ? k : n), L.hist, L.bc, &n_gt3);
+        if (!verify_exact(p, q, tq, kth3)) return;
     }
     RDX_RSTAMP(5);
-    // local -> returned row id: + row_base, or through the shard's (strictly increasing) row id map
-    for (int i = threadIdx.x; i < p; i += blockDim.x) s_r[i] = row_map ? row_map[s_r[i]] : s_r[i] + row_base;
-    __syncthreads();
-    rank_and_write(s_s, s_r, p, k, o_s, o_r, out_count + q);
+    rank_rows(p, c, n);
     RDX_RSTAMP(6);
 }
 
 // K4, one block per query: the hits are counted (segment sizes -> exclusive prefix), and the query takes one of three routes.
 //   m <= list_cap, no segment overflowed: the list in LDS (refine_list<false>);
 //   MAY_SPILL (the plan spills: SearchPlan::spill), m <= spill_cap, no segment overflowed: the block goes on IN THIS LAUNCH with its
-//     row of the spill buffer as the list (refine_list<true>). Until the one-launch form a second kernel, launched behind this one
-//     with a block per possible query, answered the queued queries: 0.22 ms at c4 for 134 of 1 024 blocks with work;
+//     row of the spill buffer as the list (refine_list<true>);
 //   otherwise: the exact full scan (exact_list).
 template <bool MAY_SPILL>
-__device__ __forceinline__ void refine_block(const int q, uint2* __restrict__ spill, uint32_t spill_cap,
-                                             const uint2* __restrict__ cand, const uint32_t* __restrict__ cntw,
-                                             int n_streams, uint32_t capw, uint32_t list_cap, int k, float two_e,
-                                             const float* __restrict__ two_e_q, const float* __restrict__ qhat, MasterView master, int dim,
-                                             int64_t row_base, const int64_t* __restrict__ row_map,
-                                             float* __restrict__ out_score, int64_t* __restrict__ out_row,
-                                             int32_t* __restrict__ out_count, int32_t* __restrict__ exact_list,
-                                             RefineCounters* __restrict__ ctr, const float* __restrict__ tau, float inv_scale2,
-                                             int pilot) {
+__device__ __forceinline__ void refine_block(const RefineParams& p, const int q) {
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [list_cap] hits (the LDS list)
     __shared__ RefineLds L;
     uint32_t* const seg_off = L.seg_off;
+    const int n_streams = p.n_streams;
     if (threadIdx.x == 0) L.overflow = 0;
     __syncthreads();
     RDX_RSTAMP(0);
     // segment sizes -> exclusive prefix. Wave 0 scans them 64 at a time with shuffles (n_streams <= 512: at most 8 rounds; the
     // serial loop this replaces was 3-5 us of the kernel at 256 streams)
     for (int w = threadIdx.x; w < n_streams; w += blockDim.x) {
-        const uint32_t c = cntw[(int64_t)q * n_streams + w];
-        if (c > capw) L.overflow = 1;
-        seg_off[w + 1] = c > capw ? capw : c;
+        const uint32_t cw = p.cntw[(int64_t)q * n_streams + w];
+        if (cw > p.capw) L.overflow = 1;
+        seg_off[w + 1] = cw > p.capw ? p.capw : cw;
     }
     __syncthreads();
     if (threadIdx.x < 64) {
@@ -485,57 +480,60 @@ __device__ __forceinline__ void refine_block(const int q, uint2* __restrict__ sp
     const bool overflow = L.overflow != 0;
     RDX_RSTAMP(1);
     if (threadIdx.x == 0) {
-        atomicAdd(&ctr->emitted, (unsigned long long)m);
-        atomicMax(&ctr->max_hits, (int)m);
+        atomicAdd(&p.ctr->emitted, (unsigned long long)m);
+        atomicMax(&p.ctr->max_hits, (int)m);
     }
     bool to_spill = false;
-    if (overflow || m > list_cap) {
-        to_spill = MAY_SPILL && !overflow && m <= spill_cap;
+    if (overflow || m > p.list_cap) {
+        to_spill = MAY_SPILL && !overflow && m <= p.spill_cap;
         if (threadIdx.x == 0) {
-            if (to_spill) atomicAdd(&ctr->n_spill, 1);
-            else exact_list[atomicAdd(&ctr->n_exact, 1)] = q;
+            if (to_spill) atomicAdd(&p.ctr->n_spill, 1);
+            else p.exact_list[atomicAdd(&p.ctr->n_exact, 1)] = q;
         }
         if (!to_spill) return;
     }
-    if (m == 0 || k == 0) {
-        rank_and_write(L.s_s, L.s_r, 0, k, out_score + (int64_t)q * k, out_row + (int64_t)q * k, out_count + q);
+    if (m == 0 || p.k == 0) {
+        rank_and_write(L.s_s, L.s_r, 0, p.k, p.out.score + (int64_t)q * p.k, p.out.row + (int64_t)q * p.k, p.out.count + q);
         return;
     }
     if constexpr (MAY_SPILL) {
         if (to_spill) {
-            refine_list<true>(L, spill + (int64_t)q * spill_cap, m, q, cand, n_streams, capw, k, two_e, two_e_q, qhat, master, dim, row_base,
-                              row_map, out_score, out_row, out_count, exact_list, ctr, tau, inv_scale2, pilot);
+            refine_list<true>(p, L, p.spill + (int64_t)q * p.spill_cap, m, q);
             return;
         }
     }
-    refine_list<false>(L, reinterpret_cast<uint2*>(smem), m, q, cand, n_streams, capw, k, two_e, two_e_q, qhat, master, dim, row_base,
-                       row_map, out_score, out_row, out_count, exact_list, ctr, tau, inv_scale2, pilot);
+    refine_list<false>(p, L, reinterpret_cast<uint2*>(smem), m, q);
+}
+
+// A pointer into global memory, or NULL, as a value the compiler keeps (in SGPRs, or parked in a VGPR lane) instead of one it may
+// load again from the kernel arguments wherever it is used. NULL stays NULL: both address spaces write it as 0, the casts change no bit.
+template <class T>
+__device__ __forceinline__ T* held_in_sgprs(T* ptr) {
+    auto g = (__attribute__((address_space(1))) T*)ptr;
+    asm volatile("" : "+s"(g));
+    return (T*)g;
+}
+__device__ __forceinline__ int held_in_sgprs(int v) {
+    asm volatile("" : "+s"(v));
+    return v;
 }
 
 // MAY_SPILL = false: the kernel of every plan that does not spill, the LDS route alone (what k_refine was before the spill list).
-// MAY_SPILL = true: both routes; `spill` is [nq_pad][spill_cap] in HBM. The search's last kernel on the MFMA path for every plan.
+// MAY_SPILL = true: both routes. The search's last kernel on the MFMA path for every plan.
 template <bool MAY_SPILL>
-__global__ __launch_bounds__(1024) void k_refine(const uint2* __restrict__ cand, const uint32_t* __restrict__ cntw,
-                                                int n_streams, uint32_t capw, uint32_t list_cap, int k, float two_e,
-                                                const float* __restrict__ two_e_q, const float* __restrict__ qhat, MasterView master, int dim,
-                                                int64_t row_base, const int64_t* __restrict__ row_map,
-                                                float* __restrict__ out_score, int64_t* __restrict__ out_row,
-                                                int32_t* __restrict__ out_count, int32_t* __restrict__ exact_list,
-                                                RefineCounters* __restrict__ ctr, const float* __restrict__ tau, float inv_scale2,
-                                                int pilot, uint32_t spill_cap, uint2* __restrict__ spill, const FinishArgs fin) {
-    refine_block<MAY_SPILL>((int)blockIdx.x, spill, spill_cap, cand, cntw, n_streams, capw, list_cap, k, two_e, two_e_q, qhat, master, dim,
-                            row_base, row_map, out_score, out_row, out_count, exact_list, ctr, tau, inv_scale2, pilot);
+__global__ __launch_bounds__(1024) void k_refine(const RefineParams args, const FinishArgs fin) {
+    // The master view and dim are read from the kernel arguments ONCE, here: read through the struct at their uses, they were loaded
+    // again (a scalar load and its wait) for every candidate row of the re-score loop: +1.7 % on k_refine at c4, profiles/refine_params.
+    RefineParams p = args;
+    p.master = MasterView{held_in_sgprs(args.master.f32), held_in_sgprs(args.master.raw16), held_in_sgprs(args.master.den)};
+    p.dim = held_in_sgprs(args.dim);
+    refine_block<MAY_SPILL>(p, (int)blockIdx.x);
     finish_if_last(fin);
 }
 
 // K5b as a kernel (the per-query work is select_dense_query, k_rows.hpp): the last launch of an exact-path search ends it
-__global__ __launch_bounds__(1024) void k_select_dense(const float* __restrict__ scores, int64_t rows,
-                                                       const int32_t* __restrict__ q_list, int k, int64_t row_base,
-                                                       const int64_t* __restrict__ row_map,
-                                                       float* __restrict__ out_score, int64_t* __restrict__ out_row,
-                                                       int32_t* __restrict__ out_count, unsigned long long* __restrict__ t_last,
-                                                       const FinishArgs fin) {
-    select_dense_query(scores, rows, q_list, k, row_base, row_map, out_score, out_row, out_count, t_last);
+__global__ __launch_bounds__(1024) void k_select_dense(const SelectParams p, const FinishArgs fin) {
+    select_dense_query(p);
     finish_if_last(fin);
 }
 

@@ -7,7 +7,9 @@ concatenate the units' listings into X.s and their remarks into X.remarks (no ke
 
 Kernels are matched by symbol. A k_scan instantiation of the OLD listing that the NEW one does not have, with the seven template
 arguments <BN, EPI, MASK, RES, SIBT, NTT, FUSED> of the scan before the sibling lock-step was removed, is matched through
-SIBT = false to the six-argument symbol; SIBT = true instantiations have no counterpart and are listed as removed.
+SIBT = false to the six-argument symbol; SIBT = true instantiations have no counterpart and are listed as removed. k_refine,
+k_select_dense, k_exact_scores and k_exact_scores_reg with their loose arguments are matched to the symbols that take
+RefineParams / SelectParams / ExactParams.
 
 For every matched pair it compares
   * the compiler's resource remarks (SGPRs, VGPRs, AGPRs, scratch, occupancy, LDS, spills) and the .amdhsa_* descriptor
@@ -24,8 +26,20 @@ _REMARK_KEYS = ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occ
                 "VGPRs Spill", "LDS Size [bytes/block]")
 
 
+# kernels whose loose arguments became one parameter struct (k_refine and k_select_dense keep FinishArgs as their second argument)
+_STRUCT_ARGS = (
+    (re.compile(r"^(_ZN3rdx8k_refineILb[01]EEEv)PK15HIP_vector_typeIjLj2EE\S*(NS_10FinishArgsE)$"), r"\1NS_12RefineParamsE\2"),
+    (re.compile(r"^(_ZN3rdx14k_select_denseE)PKfl\S*(NS_10FinishArgsE)$"), r"\1NS_12SelectParamsE\2"),
+    (re.compile(r"^(_ZN3rdx14k_exact_scoresE)NS_10MasterViewEli\S*$"), r"\1NS_11ExactParamsE"),
+    (re.compile(r"^(_ZN3rdx18k_exact_scores_regILi\dEEEv)NS_10MasterViewEli\S*$"), r"\1NS_11ExactParamsE"),
+)
+
+
 def new_name(sym: str):
     """the symbol a kernel of the OLD listing has in the NEW one, or None if it was removed"""
+    for pat, repl in _STRUCT_ARGS:
+        if pat.match(sym):
+            return pat.sub(repl, sym)
     m = _SCAN7.match(sym)
     if not m:
         return sym
