@@ -711,6 +711,47 @@ int rdx_fuse_rankings(int device, int64_t nq, int n_lists, int list_stride, cons
                       float* out_distance, double* out_semantic, double* out_bm25, double* out_hybrid, int32_t* out_list,
                       int32_t* out_rank, int32_t* out_count, int space, void* stream);
 
+/* Grouped search -------------------------------------------------------------------------------- */
+/* Exact top-k grouped by a metadata key: the first n_want distinct groups met while walking a query's ranking (score descending, row
+ * ascending), each with its first group_size rows. It replaces the reference's heuristic — fetch n_docs*10 chunks (src/rag/retriever.py:202)
+ * and deduplicate them by document on the host (src/rag/retriever.py:539-578) — by the exact answer. rag_dpo_amd/groups.py drives the two
+ * calls; DESIGN.md §21.
+ *
+ * rdx_group_select (serves retriever.py:539-578 over the n_docs*10 list of :202). Cuts ranked lists, as a search returned them, into groups:
+ * one workgroup per query, independent of any index. Device pointers only, one launch enqueued on `stream`, nothing allocated or synchronised.
+ *   scores fp32 / rows int64 [nq][k], counts int32 [nq]: the lists; entries at or beyond the count, and entries whose row is negative, are padding
+ *   row_group int32 [n_rows]: a row's group code in [0, n_groups), or -1 = the row has no group and is ignored
+ *   group_off int64 [n_groups + 1]: non-decreasing; group c has group_off[c + 1] - group_off[c] rows in the whole collection
+ *   out_score fp32 / out_row int64 [nq][n_want][group_size]: the members in ranking order (padding -inf / -1)
+ *   out_count / out_code / out_complete int32 [nq][n_want]: members written; the group's code (-1 past the groups found); 1 = the members
+ *     are the group's first group_size rows of the WHOLE ranking (the list is not full, or it holds min(group_size, |group|) rows of the group)
+ *   out_found / out_short int32 [nq]: groups written; 1 = the list is full (count == k) and holds fewer than n_want groups, so a longer
+ *     list may hold more
+ *   out_bad int32 [1], zeroed by the caller: set to 1 when a listed row is >= n_rows or its code is >= n_groups. Such an entry is treated
+ *     as padding and nothing is read through it; the caller treats the call as failed.
+ * Limits (RDX_ERR_INVALID, before anything is enqueued): nq <= 65535, 1 <= k <= RDX_GROUP_MAX_K, 1 <= n_want <= RDX_GROUP_MAX_GROUPS,
+ * 1 <= group_size <= RDX_GROUP_MAX_SIZE, n_groups < 2^31.
+ *
+ * rdx_index_group_fill (serves the same reference call, for the groups whose rows the n_docs*10 list of :202 cut off). Job j: the best
+ * group_size rows of group_rows[job_begin[j], job_end[j]) that `mask` allows (NULL: all), for query job_query[j], by (exact score descending,
+ * row ascending) with the scores of rdx_search bit for bit (the same normalisation of `queries`, the same summation order).
+ *   queries fp32 [nq][dim], group_rows int64 [n_group_rows], the outputs: device memory. job_query int32 / job_begin / job_end int64
+ *   [n_jobs]: HOST memory, checked before anything is enqueued (0 <= job_query < nq, 0 <= begin <= end <= n_group_rows, a span of at most
+ *   RDX_GROUP_FILL_SPAN rows: longer groups are split by the caller and the parts' lists merged). An entry of group_rows that is not a row
+ *   of the index is skipped, never read. out_score fp32 / out_row int64 [n_jobs][group_size] (padding -inf / -1), out_count int32 [n_jobs].
+ * Enqueued on `stream`; the call returns when the results are complete. RDX_ERR_STATE on an index with mapped row ids (a shard). */
+#define RDX_GROUP_MAX_K 4096
+#define RDX_GROUP_MAX_GROUPS 64
+#define RDX_GROUP_MAX_SIZE 16
+#define RDX_GROUP_FILL_SPAN 4096
+int rdx_group_select(int device, const float* scores, const int64_t* rows, const int32_t* counts, int64_t nq, int k,
+                     const int32_t* row_group, int64_t n_rows, const int64_t* group_off, int64_t n_groups, int n_want, int group_size,
+                     float* out_score, int64_t* out_row, int32_t* out_count, int32_t* out_code, int32_t* out_complete,
+                     int32_t* out_found, int32_t* out_short, int32_t* out_bad, void* stream);
+int rdx_index_group_fill(rdx_index* h, const float* queries, int64_t nq, const rdx_mask* mask, const int32_t* job_query,
+                         const int64_t* job_begin, const int64_t* job_end, int64_t n_jobs, const int64_t* group_rows,
+                         int64_t n_group_rows, int m, float* out_score, int64_t* out_row, int32_t* out_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

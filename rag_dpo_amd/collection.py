@@ -19,6 +19,9 @@ _WHERE_DEVICE_MIN_ROWS rows: the filter is compiled (rag_dpo_amd/where_device.py
 metadata columns the filter names, kept in HBM (engine.MetaStore) from the first filter that names them and brought up to date
 with the host's columns before every evaluation. rag_dpo_amd/where.py is the model and remains the path of get / delete, of
 other engines, of smaller collections and of trees over the device's limits; results are the same on both. Not persisted.
+`query_groups` / `query_groups_device` (not part of chromadb's API) return the exact top groups of a metadata key, each with its best
+rows, instead of rows: what the reference approximates by over-fetching chunks and deduplicating them by document
+(src/rag/retriever.py:202, 539-578); rag_dpo_amd/groups.py states the definition. Cosine collections on one device.
 ids/documents/metadata stay on the host; embeddings go to the device index (`engine`). The engine is
 always librdx (rag_dpo_amd.engine.HipIndex): there is no CPU search path in this package.
 
@@ -38,6 +41,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
+from . import groups as GR
 from . import where as W
 from . import where_document as WD
 
@@ -154,6 +158,8 @@ class Collection:
         self._meta_res: Dict[str, list] = {}   # key -> [slot in the store, rows [0, r) of the column that are on the device]
         self._writes = 0                       # bumped by every add / update / upsert / delete / compaction that changes a row: what tables
                                                # derived from the rows (rag_dpo_amd/fusion.py's row -> document group) are keyed on
+        self._group_tables: Dict[str, Any] = {}    # groups.GroupTables per metadata key query_groups has grouped by (valid for one _writes)
+        self._group_stats = {k: 0 for k in GR.STAT_KEYS}   # group_stats
 
     # ---- small helpers ----------------------------------------------------------------------
     @property
@@ -785,6 +791,107 @@ class Collection:
             if getattr(self._engine, "returns_distances", False):
                 return s, r, c
             return (1.0 - s), r, c            # Chroma cosine distance, fp32 (padding entries: distance +inf, row -1)
+
+    # ---- grouped search (rag_dpo_amd/groups.py states the definition and the ladder) ---------------------------
+    def _groups_check(self, group_by, n_groups, group_size, where_document):
+        if not isinstance(group_by, str) or not group_by:
+            raise ValueError(f"Expected group_by to be a non-empty str, got {group_by!r}")
+        for name, v, hi in (("n_groups", n_groups, GR.MAX_GROUPS), ("group_size", group_size, GR.MAX_GROUP_SIZE)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 1 <= v <= hi:
+                raise ValueError(f"Expected {name} to be an int in [1, {hi}], got {v!r}")
+        if not WD.is_empty(where_document):
+            WD.validate(where_document)
+        space = self.metadata.get("hnsw:space", "cosine")
+        if space != "cosine":
+            raise NotImplementedError(f"query_groups ranks by the cosine score: not available in the {space!r} space")
+        if self._engine is not None and hasattr(self._engine, "devices"):
+            raise NotImplementedError("query_groups runs on one device in this version: not on a collection spread over several")
+
+    @property
+    def group_stats(self) -> Dict[str, int]:
+        """counters of the grouped search since the collection was created: `queries`; how many of them were `proven_first_fetch`
+        (the first list held the groups), took the `second_fetch`, went to `brute` force; and the `fill_jobs` given to the fill kernel"""
+        return dict(self._group_stats)
+
+    def group_values(self, group_by: str, codes) -> list:
+        """the value of key `group_by` behind the group codes query_groups_device returned (any nesting of lists / an array; a negative
+        code, padding, gives None). Codes belong to the state of the rows they were returned for: map them before the next write."""
+        with self._lock:
+            vals = GR.group_tables(self, group_by).values
+            cc = codes.tolist() if hasattr(codes, "tolist") else codes
+            walk = lambda x: [walk(y) for y in x] if isinstance(x, (list, tuple)) else (vals[x] if x >= 0 else None)
+            return walk(cc)
+
+    def _grouped(self, q, group_by, n_groups, group_size, where, where_document, device_out: bool):
+        """-> (scores, rows, counts, codes, n_found): torch tensors on the device (device_out) or numpy arrays; the lock is held"""
+        stats = self._group_stats
+        tables = GR.group_tables(self, group_by)
+        args = self._search_args(where, where_document)
+        G, m = int(n_groups), int(group_size)
+        if not hasattr(self._engine, "search_device"):
+            if device_out:
+                raise NotImplementedError("this collection's engine has no device-pointer search")
+            stats["queries"] += q.shape[0]
+            return GR.grouped_search_host(self._engine, q, tables, G, m, args)
+        if "allow_bits" in args:
+            raise NotImplementedError("query_groups needs an engine with resident masks")
+        import torch
+        if not _is_device_tensor(q):
+            q = torch.from_numpy(q).to(torch.device("cuda", self._engine.device))
+        with torch.cuda.device(q.device):
+            out = GR.grouped_search_device(self, q.contiguous(), tables, G, m, args.get("mask"), stats)
+        return out if device_out else tuple(t.cpu().numpy() for t in out)
+
+    def query_groups_device(self, query_embeddings, group_by: str, n_groups: int, group_size: int, where=None, where_document=None):
+        """query_groups for callers that hold their query embeddings on the GPU ([nq][dim] fp32 torch CUDA tensor) -> (distances f32
+        [nq, G, m], rows i64 [nq, G, m], counts i32 [nq, G], group_codes i32 [nq, G], n_found i32 [nq]) on the collection's device;
+        padding is distance +inf, row -1, code -1. `group_values(group_by, codes)` maps the codes to the key's values, `ids_of` /
+        `payload_of` the rows to ids and payloads. The same groups, rows and floats as query_groups."""
+        self._groups_check(group_by, n_groups, group_size, where_document)
+        with self._lock:
+            if self._engine is None or self._rows == 0:
+                raise ValueError("query_groups_device: the collection is empty")
+            s, r, c, codes, found = self._grouped(query_embeddings, group_by, n_groups, group_size, where, where_document, True)
+            return (1.0 - s), r, c, codes, found
+
+    def query_groups(self, query_embeddings, group_by: str, n_groups: int = 5, group_size: int = 3, where=None, where_document=None,
+                     include=None):
+        """Exact top-k grouped by metadata key `group_by`: per query the first n_groups distinct values of the key met while walking
+        the ranking of the allowed rows (cosine score descending, row ascending — query()'s order and floats), each with its first
+        group_size rows. It is what the reference approximates by fetching n_docs*10 chunks and deduplicating them by document
+        (src/rag/retriever.py:202, 539-578). Rows without the key are ignored; 1 and True are different groups; fewer groups or rows
+        come back only when the allowed rows hold no more. -> {"groups": [nq][<= G] the key's values, "ids": [nq][<= G][<= m], and per
+        `include` "distances", "documents", "metadatas" of the same shape, "included"}."""
+        include = DEFAULT_INCLUDE_QUERY if include is None else list(include)
+        self._check_include(include, {"documents", "metadatas", "distances"})
+        self._groups_check(group_by, n_groups, group_size, where_document)
+        if query_embeddings is None:
+            raise ValueError("this collection has no embedding function: pass query_embeddings=")
+        q = _as_matrix(query_embeddings, "query_embeddings")
+        nq = q.shape[0]
+        with self._lock:
+            out = {"groups": [[] for _ in range(nq)], "ids": [[] for _ in range(nq)], "included": include}
+            for inc in ("distances", "documents", "metadatas"):
+                out[inc] = [[] for _ in range(nq)] if inc in include else None
+            if self._engine is None or self._rows == 0:
+                return out
+            if q.shape[1] != self._dim:
+                raise ValueError(f"Embedding dimension {q.shape[1]} does not match collection dimensionality {self._dim}")
+            s, r, c, codes, found = self._grouped(q, group_by, n_groups, group_size, where, where_document, False)
+            dist = (np.float32(1.0) - s).astype(np.float32)
+            vals = GR.group_tables(self, group_by).values
+            for b in range(nq):
+                for g in range(int(found[b])):
+                    rr = r[b, g, : c[b, g]].tolist()
+                    out["groups"][b].append(vals[int(codes[b, g])])
+                    out["ids"][b].append([self._ids[x] for x in rr])
+                    if "distances" in include:
+                        out["distances"][b].append([float(x) for x in dist[b, g, : c[b, g]]])
+                    if "documents" in include:
+                        out["documents"][b].append([self._docs[x] for x in rr])
+                    if "metadatas" in include:
+                        out["metadatas"][b].append(self._metas_of(rr))
+            return out
 
     def ids_of(self, rows) -> List[List[str]]:
         """Chroma ids of row ids as returned by query_device (negative = padding, skipped)"""

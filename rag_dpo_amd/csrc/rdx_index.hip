@@ -127,6 +127,7 @@ struct rdx_index {
     I8Copy i8;
     // the int8 pass's per-search query copy, scales, bounds, thresholds (nothing of it outlives a search)
     DevBuf qshadow8, tq8, eq8, nq8, thr8, taus8, twoe8;
+    DevBuf gjobs;            // rdx_index_group_fill: the call's jobs (query | begin | end)
     DevBuf spill;            // k_refine<true>: [nq_pad][spill_cap] hit lists of the queries that outgrow the LDS list (first spilling plan)
     // end-of-search mailbox in pinned host memory (k_finish writes it over PCIe; the host spins on its sequence number)
     MappedPin<Mailbox> mbox;
@@ -1307,6 +1308,84 @@ extern "C" int rdx_search_masked(rdx_index* h, const float* queries, int64_t nq,
     std::lock_guard<std::mutex> lk(h->mu);
     RDX_TRY(check_mask(h, mask, "rdx_search_masked"));
     return search_impl(h, queries, nq, k, mask ? mask->words.as<uint32_t>() : nullptr, true, out_score, out_row, out_count, space, stream);
+}
+
+// ---- grouped search: the fill ---------------------------------------------------------------------------------
+static_assert(GROUP_FILL_SPAN == RDX_GROUP_FILL_SPAN && GROUP_FILL_MAX_M == RDX_GROUP_MAX_SIZE, "k_rows.hpp and include/rdx.h disagree");
+
+template <int U>
+static void launch_group_fill(const GroupFillParams& gp, hipStream_t st) {
+    hipLaunchKernelGGL(k_group_fill<U>, dim3((unsigned)gp.n_jobs), dim3(64 * GROUP_FILL_WAVES), 0, st, gp);   // one workgroup per job
+}
+
+extern "C" int rdx_index_group_fill(rdx_index* h, const float* queries, int64_t nq, const rdx_mask* mask, const int32_t* job_query,
+                                    const int64_t* job_begin, const int64_t* job_end, int64_t n_jobs, const int64_t* group_rows,
+                                    int64_t n_group_rows, int m, float* out_score, int64_t* out_row, int32_t* out_count, void* stream) {
+    if (!h) return fail(RDX_ERR_INVALID, "rdx_index_group_fill: null index");
+    if (nq < 1 || nq > 65535) return fail(RDX_ERR_INVALID, "rdx_index_group_fill: nq must be in [1, 65535]");
+    if (n_jobs < 0 || n_jobs > (int64_t)1 << 22) return fail(RDX_ERR_INVALID, "rdx_index_group_fill: n_jobs must be in [0, 2^22]");
+    if (m < 1 || m > GROUP_FILL_MAX_M) return fail(RDX_ERR_INVALID, "rdx_index_group_fill: m must be in [1, 16]");
+    if (n_group_rows < 0) return fail(RDX_ERR_INVALID, "rdx_index_group_fill: n_group_rows must be >= 0");
+    if (n_jobs == 0) return RDX_OK;
+    if (!queries || !job_query || !job_begin || !job_end || !out_score || !out_row || !out_count || (n_group_rows > 0 && !group_rows))
+        return fail(RDX_ERR_INVALID, "rdx_index_group_fill: null pointer");
+    if (((uintptr_t)queries & 15) || (((uintptr_t)group_rows | (uintptr_t)out_row) & 7) || (((uintptr_t)out_score | (uintptr_t)out_count) & 3))
+        return fail(RDX_ERR_INVALID, "rdx_index_group_fill: misaligned pointer");
+    for (int64_t j = 0; j < n_jobs; ++j) {   // the jobs are host memory: held to the header's words before anything is enqueued
+        if (job_query[j] < 0 || job_query[j] >= nq)
+            return fail(RDX_ERR_INVALID, "rdx_index_group_fill: job " + std::to_string(j) + " names query " + std::to_string(job_query[j]) +
+                                             " of " + std::to_string(nq));
+        if (job_begin[j] < 0 || job_end[j] < job_begin[j] || job_end[j] > n_group_rows || job_end[j] - job_begin[j] > GROUP_FILL_SPAN)
+            return fail(RDX_ERR_INVALID, "rdx_index_group_fill: job " + std::to_string(j) + " must span 0 <= begin <= end <= n_group_rows, at most " +
+                                             std::to_string(GROUP_FILL_SPAN) + " rows");
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    RDX_TRY(check_mask(h, mask, "rdx_index_group_fill"));
+    if (h->store.row_map.p || h->row_base != 0)
+        return fail(RDX_ERR_STATE, "rdx_index_group_fill: the index returns mapped row ids (a shard): group_rows must be the index's own rows");
+    RDX_TRY(finish_pending(h, nullptr));
+    RDX_TRY(set_device(h));
+    hipStream_t st = (hipStream_t)stream;
+    RDX_TRY(h->qhat.ensure((size_t)nq * h->dim * 4));
+    RDX_TRY(h->bad.ensure(sizeof(int)));
+    const size_t jq = ((size_t)n_jobs * 4 + 7) & ~(size_t)7, jb = (size_t)n_jobs * 8;
+    RDX_TRY(h->gjobs.ensure(jq + 2 * jb));
+    char* const dj = h->gjobs.as<char>();
+    HIP_TRY(hipMemcpyAsync(dj, job_query, (size_t)n_jobs * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dj + jq, job_begin, jb, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dj + jq + jb, job_end, jb, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(h->bad.p, 0, sizeof(int), st));
+    // K1 on the queries, the call rdx_search makes: the same qhat bits
+    hipLaunchKernelGGL(k_normalize<false>, dim3((int)((nq + 3) / 4)), dim3(256), 0, st, queries, (const uint16_t*)nullptr, nq, h->dim,
+                       (const int64_t*)nullptr, (int64_t)0, MasterView{h->qhat.as<float>(), nullptr, nullptr}, (_Float16*)nullptr, 0, 1.0f, h->bad.as<int>());
+    HIP_TRY(hipGetLastError());
+    GroupFillParams gp = {};
+    gp.master = h->mv();
+    gp.rows = h->rows;
+    gp.dim = h->dim;
+    gp.qhat = h->qhat.as<float>();
+    gp.allow = mask ? mask->words.as<uint32_t>() : nullptr;
+    gp.job_query = reinterpret_cast<const int32_t*>(dj);
+    gp.job_begin = reinterpret_cast<const int64_t*>(dj + jq);
+    gp.job_end = reinterpret_cast<const int64_t*>(dj + jq + jb);
+    gp.n_jobs = n_jobs;
+    gp.group_rows = group_rows;
+    gp.m = m;
+    gp.out_score = out_score;
+    gp.out_row = out_row;
+    gp.out_count = out_count;
+    const int u = h->dim <= 1024 ? (h->dim / 4 + 63) / 64 : 0;
+    if (u == 1) launch_group_fill<1>(gp, st);
+    else if (u == 2) launch_group_fill<2>(gp, st);
+    else if (u == 3) launch_group_fill<3>(gp, st);
+    else if (u == 4) launch_group_fill<4>(gp, st);
+    else launch_group_fill<0>(gp, st);
+    HIP_TRY(hipGetLastError());
+    int b = 0;
+    HIP_TRY(hipMemcpyAsync(&b, h->bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // the jobs' host arrays are the caller's again, and the NaN/Inf verdict is part of the return value
+    if (b) return fail(RDX_ERR_INVALID, "embeddings contain NaN or Inf");
+    return RDX_OK;
 }
 
 #ifdef RDX_REFINE_STAMPS

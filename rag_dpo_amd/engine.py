@@ -474,6 +474,63 @@ def space_distances(kind: int, queries, vecs, scale_exp: int, allow_bits, first_
                                     ctypes.c_void_p(out.data_ptr() + 4 * col0), out.shape[1], ctypes.c_void_p(HipIndex._raw_stream(dev))))
 
 
+# ---- grouped search (include/rdx.h rdx_group_select / rdx_index_group_fill; rag_dpo_amd/groups.py drives them) -----------------
+def group_select(scores, rows, counts, row_group, group_off, n_groups: int, group_size: int):
+    """ranked lists (scores f32 / rows i64 [nq][k], counts i32 [nq]) and the tables row_group i32 [n_rows], group_off i64 [groups + 1],
+    all on one device -> dict of tensors there: score f32 / row i64 [nq][G][m], count / code / complete i32 [nq][G], found / short
+    i32 [nq], bad i32 [1] (1 = a listed row or code lies outside the tables: the caller treats the call as failed). Enqueued on the
+    current torch stream."""
+    import torch
+    lib = L.load(require_gpu=True)
+    nq, k = rows.shape
+    G, m = int(n_groups), int(group_size)
+    dev = rows.device
+    out = {"score": torch.empty((nq, G, m), dtype=torch.float32, device=dev), "row": torch.empty((nq, G, m), dtype=torch.int64, device=dev),
+           "count": torch.empty((nq, G), dtype=torch.int32, device=dev), "code": torch.empty((nq, G), dtype=torch.int32, device=dev),
+           "complete": torch.empty((nq, G), dtype=torch.int32, device=dev), "found": torch.empty(nq, dtype=torch.int32, device=dev),
+           "short": torch.empty(nq, dtype=torch.int32, device=dev), "bad": torch.zeros(1, dtype=torch.int32, device=dev)}
+    ins = (scores, rows, counts, row_group, group_off)
+    want = (torch.float32, torch.int64, torch.int32, torch.int32, torch.int64)
+    for t, dt in zip(ins, want):
+        if not t.is_cuda or t.device != dev or t.dtype != dt or not t.is_contiguous():
+            raise ValueError("group_select takes contiguous torch tensors of the documented types on one CUDA device")
+    if scores.shape != rows.shape or counts.shape != (nq,) or group_off.numel() < 1:
+        raise ValueError("group_select: scores / rows must be [nq][k], counts [nq], group_off [groups + 1]")
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    L.check(lib.rdx_group_select(dev.index or 0, p(scores), p(rows), p(counts), nq, int(k), p(row_group), row_group.numel(), p(group_off),
+                                 group_off.numel() - 1, G, m, p(out["score"]), p(out["row"]), p(out["count"]), p(out["code"]),
+                                 p(out["complete"]), p(out["found"]), p(out["short"]), p(out["bad"]),
+                                 ctypes.c_void_p(HipIndex._raw_stream(dev))))
+    return out
+
+
+def group_fill(index: "HipIndex", queries, job_query, job_begin, job_end, group_rows, group_size: int, mask: Optional[ResidentMask] = None):
+    """jobs (numpy: job_query i32, job_begin / job_end i64 into group_rows, spans of at most L.GROUP_FILL_SPAN) -> (score f32 [jobs][m],
+    row i64 [jobs][m], count i32 [jobs]) on the device: each job's best m allowed rows by (exact score descending, row ascending).
+    queries fp32 [nq][dim] and group_rows i64 are torch tensors on the index's device; complete on return."""
+    import torch
+    jq = np.ascontiguousarray(job_query, dtype=np.int32)
+    jb = np.ascontiguousarray(job_begin, dtype=np.int64)
+    je = np.ascontiguousarray(job_end, dtype=np.int64)
+    n_jobs, m = jq.shape[0], int(group_size)
+    if jb.shape != (n_jobs,) or je.shape != (n_jobs,):
+        raise ValueError("group_fill: job_query, job_begin and job_end must have one entry per job")
+    if not (queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous() and queries.dim() == 2
+            and queries.shape[1] == index.dim and queries.device.index == index.device):
+        raise ValueError(f"group_fill: queries must be a contiguous fp32 [nq][{index.dim}] tensor on cuda:{index.device}")
+    if not (group_rows.is_cuda and group_rows.dtype == torch.int64 and group_rows.is_contiguous() and group_rows.device == queries.device):
+        raise ValueError("group_fill: group_rows must be a contiguous int64 tensor on the index's device")
+    dev = queries.device
+    sc = torch.empty((n_jobs, max(m, 1)), dtype=torch.float32, device=dev)
+    ro = torch.empty((n_jobs, max(m, 1)), dtype=torch.int64, device=dev)
+    cn = torch.empty(n_jobs, dtype=torch.int32, device=dev)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    L.check(index._lib.rdx_index_group_fill(index._h, p(queries), queries.shape[0], mask._h if mask is not None else None, _np_ptr(jq),
+                                            _np_ptr(jb), _np_ptr(je), n_jobs, p(group_rows), group_rows.numel(), m, p(sc), p(ro), p(cn),
+                                            ctypes.c_void_p(HipIndex._raw_stream(dev))))
+    return sc, ro, cn
+
+
 def l2_normalize(x: np.ndarray, device: int = 0) -> np.ndarray:
     lib = L.load(require_gpu=True)
     a = np.ascontiguousarray(x, dtype=np.float32)
