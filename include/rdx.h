@@ -752,6 +752,32 @@ int rdx_index_group_fill(rdx_index* h, const float* queries, int64_t nq, const r
                          const int64_t* job_begin, const int64_t* job_end, int64_t n_jobs, const int64_t* group_rows,
                          int64_t n_group_rows, int m, float* out_score, int64_t* out_row, int32_t* out_count, void* stream);
 
+/* Diversity-aware selection (MMR) --------------------------------------------------------------- */
+/* Maximal marginal relevance over candidate lists, as a search returned them: what a user of the reference's store gets today only by
+ * fetching more chunks than needed (src/rag/retriever.py:202) and deduplicating them on the host (:539-578), which cannot tell two
+ * near-identical chunks of different documents apart. rag_dpo_amd/mmr.py states the definition and drives the call; DESIGN.md §22.
+ *
+ * rdx_index_mmr. Per query: the live entries of its list are those at a position below cand_count whose row is in [0, rows of the index).
+ * Pick 0 is the first live position. Every later pick is the live unpicked position i with the largest
+ *     v_i = lambda * (double)s_i - (1.0 - lambda) * (double)m_i        (three fp64 operations, each rounded once, never fused)
+ * where s_i is the entry's score as given and m_i the largest fp32 pair score p(i, j) over the picked j; ties go to the smaller
+ * position. p(i, j) is the exact score of rdx_search with the stored (normalised) row of j as the query and the row of i as the corpus
+ * row: the same summation order, the same bits, and symmetric. min(k, live entries) picks are made.
+ *   cand_score fp32 / cand_row int64 [nq][fetch_k], cand_count int32 [nq]: the lists (a count outside [0, fetch_k] is clamped). The scores
+ *     of live entries must be finite. The lists need not be sorted; those of a search are, and then pick 0 is the best entry.
+ *   out_pos int32 / out_row int64 / out_score fp32 / out_value double [nq][k], in pick order: the pick's position in its list, its row, its
+ *     score as given and its v (pick 0: lambda * (double)s); padding -1 / -1 / -inf / -inf. out_count int32 [nq]: picks made.
+ *   out_bad int32 [1], zeroed by the caller: set to 1 when a listed row is >= the index's rows. Such an entry is treated as padding and
+ *     nothing is read through it; the caller treats the call as failed.
+ * Device pointers only; one launch enqueued on `stream`, nothing allocated or synchronised; the same list gives the same bits whatever nq.
+ * Limits (RDX_ERR_INVALID, before anything is enqueued): nq <= 65535, 1 <= k <= RDX_MMR_MAX_K, k <= fetch_k <= RDX_MMR_MAX_FETCH,
+ * 0 <= lambda <= 1 (a NaN is refused). RDX_ERR_STATE on an index with mapped row ids (a shard). */
+#define RDX_MMR_MAX_FETCH 1024
+#define RDX_MMR_MAX_K 64
+int rdx_index_mmr(rdx_index* h, const float* cand_score, const int64_t* cand_row, const int32_t* cand_count, int64_t nq, int fetch_k,
+                  int k, double lambda, int32_t* out_pos, int64_t* out_row, float* out_score, double* out_value, int32_t* out_count,
+                  int32_t* out_bad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,8 @@ other engines, of smaller collections and of trees over the device's limits; res
 `query_groups` / `query_groups_device` (not part of chromadb's API) return the exact top groups of a metadata key, each with its best
 rows, instead of rows: what the reference approximates by over-fetching chunks and deduplicating them by document
 (src/rag/retriever.py:202, 539-578); rag_dpo_amd/groups.py states the definition. Cosine collections on one device.
+`query_mmr` / `query_mmr_device` (not part of chromadb's API either) return a diverse top-k: maximal marginal relevance over the
+fetch_k best rows, for corpora whose near-duplicate chunks share no key; rag_dpo_amd/mmr.py states the definition. Same limits.
 ids/documents/metadata stay on the host; embeddings go to the device index (`engine`). The engine is
 always librdx (rag_dpo_amd.engine.HipIndex): there is no CPU search path in this package.
 
@@ -42,6 +44,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence
 import numpy as np
 
 from . import groups as GR
+from . import mmr as MM
 from . import where as W
 from . import where_document as WD
 
@@ -891,6 +894,97 @@ class Collection:
                         out["documents"][b].append([self._docs[x] for x in rr])
                     if "metadatas" in include:
                         out["metadatas"][b].append(self._metas_of(rr))
+            return out
+
+    # ---- diversity-aware search (rag_dpo_amd/mmr.py states the definition) ---------------------------------------
+    def _mmr_check(self, n_results, fetch_k, lambda_mult, where_document):
+        for name, v, lo, hi in (("n_results", n_results, 1, MM.MAX_K), ("fetch_k", fetch_k, 1, MM.MAX_FETCH)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not lo <= v <= hi:
+                raise ValueError(f"Expected {name} to be an int in [{lo}, {hi}], got {v!r}")
+        if fetch_k < n_results:
+            raise ValueError(f"Expected fetch_k >= n_results, got fetch_k={fetch_k!r}, n_results={n_results!r}")
+        if not isinstance(lambda_mult, (int, float, np.integer, np.floating)) or isinstance(lambda_mult, bool) \
+                or not 0.0 <= float(lambda_mult) <= 1.0:                      # (a NaN fails both comparisons)
+            raise ValueError(f"Expected lambda_mult to be a number in [0, 1], got {lambda_mult!r}")
+        if not WD.is_empty(where_document):
+            WD.validate(where_document)
+        space = self.metadata.get("hnsw:space", "cosine")
+        if space != "cosine":
+            raise NotImplementedError(f"query_mmr ranks and compares by the cosine score: not available in the {space!r} space")
+        if self._engine is not None and hasattr(self._engine, "devices"):
+            raise NotImplementedError("query_mmr runs on one device in this version: not on a collection spread over several")
+
+    def query_mmr_device(self, query_embeddings, n_results: int = 10, fetch_k: int = 50, lambda_mult: float = 0.5, where=None,
+                         where_document=None):
+        """query_mmr for callers that hold their query embeddings on the GPU ([nq][dim] fp32 torch CUDA tensor) -> (distances f32
+        [nq, n_results], rows i64 [nq, n_results], values f64 [nq, n_results], counts i32 [nq]) on the collection's device, in pick
+        order; padding is distance +inf, row -1, value -inf. One search and one launch, nothing crosses PCIe but the call itself;
+        `ids_of` / `payload_of` map the rows. The same picks and floats as query_mmr."""
+        self._mmr_check(n_results, fetch_k, lambda_mult, where_document)
+        with self._lock:
+            if self._engine is None or self._rows == 0:
+                raise ValueError("query_mmr_device: the collection is empty")
+            if not hasattr(self._engine, "search_device"):
+                raise NotImplementedError("this collection's engine has no device-pointer search")
+            args = self._search_args(where, where_document)
+            if "allow_bits" in args:
+                raise NotImplementedError("query_mmr_device needs an engine with resident masks")
+            import torch
+            q = query_embeddings.contiguous()
+            with torch.cuda.device(q.device):
+                s, r, v, c, _ = MM.mmr_search_device(self._engine, q, int(n_results), int(fetch_k), float(lambda_mult), args.get("mask"))
+            return (1.0 - s), r, v, c
+
+    def query_mmr(self, query_embeddings, n_results: int = 10, fetch_k: int = 50, lambda_mult: float = 0.5, where=None,
+                  where_document=None, include=None):
+        """Diversity-aware top-k (maximal marginal relevance): of the fetch_k best allowed rows (query()'s ranking and floats) pick
+        n_results one by one — first the best, then always the row with the largest lambda_mult * (its score) - (1 - lambda_mult) *
+        (its largest exact cosine score with a row picked before), ties to the better-ranked. lambda_mult = 1 is query(n_results);
+        smaller values trade relevance for diversity. -> query()'s dict in pick order, plus "mmr_scores": [nq][<= n_results], the value
+        each row was picked with. rag_dpo_amd/mmr.py states the arithmetic; results are the same on every path."""
+        include = DEFAULT_INCLUDE_QUERY if include is None else list(include)
+        self._check_include(include, {"documents", "metadatas", "distances", "embeddings"})
+        self._mmr_check(n_results, fetch_k, lambda_mult, where_document)
+        if query_embeddings is None:
+            raise ValueError("this collection has no embedding function: pass query_embeddings=")
+        q = _as_matrix(query_embeddings, "query_embeddings")
+        if _is_device_tensor(q):
+            q = q.cpu().numpy()
+        nq = q.shape[0]
+        k, F, lam = int(n_results), int(fetch_k), float(lambda_mult)
+        with self._lock:
+            out = {"ids": [[] for _ in range(nq)], "uris": None, "data": None, "included": include,
+                   "mmr_scores": [[] for _ in range(nq)]}
+            for inc in ("documents", "metadatas", "distances", "embeddings"):
+                out[inc] = [[] for _ in range(nq)] if inc in include else None
+            if self._engine is None or self._rows == 0:
+                return out
+            if q.shape[1] != self._dim:
+                raise ValueError(f"Embedding dimension {q.shape[1]} does not match collection dimensionality {self._dim}")
+            args = self._search_args(where, where_document)
+            if hasattr(self._engine, "search_device") and "allow_bits" not in args:
+                import torch
+                qd = torch.from_numpy(q).to(torch.device("cuda", self._engine.device))
+                with torch.cuda.device(qd.device):
+                    res = MM.mmr_search_device(self._engine, qd, k, F, lam, args.get("mask"))
+                s, r, v, c, bad = (t.cpu().numpy() for t in res)
+                if bad[0]:
+                    raise RuntimeError("query_mmr: the search returned a row the index does not hold")
+            else:
+                s, r, v, c = MM.mmr_search_host(self._engine, q, k, F, lam, args)
+            dist = (np.float32(1.0) - s).astype(np.float32)
+            for b in range(nq):
+                rr = r[b, : c[b]].tolist()
+                out["ids"][b] = [self._ids[x] for x in rr]
+                out["mmr_scores"][b] = [float(x) for x in v[b, : c[b]]]
+                if "documents" in include:
+                    out["documents"][b] = [self._docs[x] for x in rr]
+                if "metadatas" in include:
+                    out["metadatas"][b] = self._metas_of(rr)
+                if "distances" in include:
+                    out["distances"][b] = [float(x) for x in dist[b, : c[b]]]
+                if "embeddings" in include:
+                    out["embeddings"][b] = self._engine.get(np.array(rr, dtype=np.int64)) if rr else np.zeros((0, self._dim), dtype=np.float32)
             return out
 
     def ids_of(self, rows) -> List[List[str]]:

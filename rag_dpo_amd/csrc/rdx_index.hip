@@ -13,6 +13,7 @@
 
 #include "index_state.hpp"
 #include "k_rows.hpp"
+#include "mmr_kernel.hpp"
 #include "refine_kernel.hpp"
 #include "scan_kernel.hpp"
 #include "search_plan.hpp"
@@ -1385,6 +1386,59 @@ extern "C" int rdx_index_group_fill(rdx_index* h, const float* queries, int64_t 
     HIP_TRY(hipMemcpyAsync(&b, h->bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));   // the jobs' host arrays are the caller's again, and the NaN/Inf verdict is part of the return value
     if (b) return fail(RDX_ERR_INVALID, "embeddings contain NaN or Inf");
+    return RDX_OK;
+}
+
+// ---- diversity-aware selection ---------------------------------------------------------------------------------
+static_assert(MMR_MAX_FETCH == RDX_MMR_MAX_FETCH && MMR_MAX_K == RDX_MMR_MAX_K, "mmr_kernel.hpp and include/rdx.h disagree");
+
+template <int U>
+static void launch_mmr(const MmrParams& mp, int64_t nq, hipStream_t st) {
+    hipLaunchKernelGGL(k_mmr<U>, dim3((unsigned)nq), dim3(64 * MMR_WAVES), 0, st, mp);   // one workgroup per query
+}
+
+extern "C" int rdx_index_mmr(rdx_index* h, const float* cand_score, const int64_t* cand_row, const int32_t* cand_count, int64_t nq,
+                             int fetch_k, int k, double lambda, int32_t* out_pos, int64_t* out_row, float* out_score, double* out_value,
+                             int32_t* out_count, int32_t* out_bad, void* stream) {
+    if (!h) return fail(RDX_ERR_INVALID, "rdx_index_mmr: null index");
+    if (nq < 0 || nq > 65535) return fail(RDX_ERR_INVALID, "rdx_index_mmr: nq must be in [0, 65535]");
+    if (k < 1 || k > MMR_MAX_K) return fail(RDX_ERR_INVALID, "rdx_index_mmr: k (the picks per query) must be in [1, 64]");
+    if (fetch_k < k || fetch_k > MMR_MAX_FETCH) return fail(RDX_ERR_INVALID, "rdx_index_mmr: fetch_k (the entries per list) must be in [k, 1024]");
+    if (!(lambda >= 0.0 && lambda <= 1.0)) return fail(RDX_ERR_INVALID, "rdx_index_mmr: lambda must be in [0, 1]");
+    if (nq == 0) return RDX_OK;
+    if (!cand_score || !cand_row || !cand_count) return fail(RDX_ERR_INVALID, "rdx_index_mmr: null input pointer");
+    if (!out_pos || !out_row || !out_score || !out_value || !out_count || !out_bad) return fail(RDX_ERR_INVALID, "rdx_index_mmr: null output pointer");
+    if (((uintptr_t)cand_row | (uintptr_t)out_row | (uintptr_t)out_value) & 7) return fail(RDX_ERR_INVALID, "rdx_index_mmr: misaligned pointer");
+    if (((uintptr_t)cand_score | (uintptr_t)cand_count | (uintptr_t)out_pos | (uintptr_t)out_score | (uintptr_t)out_count | (uintptr_t)out_bad) & 3)
+        return fail(RDX_ERR_INVALID, "rdx_index_mmr: misaligned pointer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->store.row_map.p || h->row_base != 0)
+        return fail(RDX_ERR_STATE, "rdx_index_mmr: the index returns mapped row ids (a shard): cand_row must be the index's own rows");
+    RDX_TRY(set_device(h));
+    MmrParams mp = {};
+    mp.master = h->mv();
+    mp.rows = h->rows;
+    mp.dim = h->dim;
+    mp.cand_score = cand_score;
+    mp.cand_row = cand_row;
+    mp.cand_count = cand_count;
+    mp.fetch_k = fetch_k;
+    mp.k = k;
+    mp.lambda = lambda;
+    mp.out_pos = out_pos;
+    mp.out_row = out_row;
+    mp.out_score = out_score;
+    mp.out_value = out_value;
+    mp.out_count = out_count;
+    mp.out_bad = out_bad;
+    hipStream_t st = (hipStream_t)stream;
+    const int u = h->dim <= 1024 ? (h->dim / 4 + 63) / 64 : 0;
+    if (u == 1) launch_mmr<1>(mp, nq, st);
+    else if (u == 2) launch_mmr<2>(mp, nq, st);
+    else if (u == 3) launch_mmr<3>(mp, nq, st);
+    else if (u == 4) launch_mmr<4>(mp, nq, st);
+    else launch_mmr<0>(mp, nq, st);
+    HIP_TRY(hipGetLastError());
     return RDX_OK;
 }
 

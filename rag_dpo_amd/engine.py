@@ -531,6 +531,33 @@ def group_fill(index: "HipIndex", queries, job_query, job_begin, job_end, group_
     return sc, ro, cn
 
 
+# ---- diversity-aware selection (include/rdx.h rdx_index_mmr; rag_dpo_amd/mmr.py states the definition) --------------------------
+def mmr_select(index: "HipIndex", cand_score, cand_row, cand_count, n_results: int, lambda_mult: float):
+    """candidate lists (cand_score f32 / cand_row i64 [nq][fetch_k], cand_count i32 [nq], torch tensors on the index's device; rows are the
+    index's own) -> dict of tensors there, in pick order: pos i32 / row i64 / score f32 / value f64 [nq][k] (padding -1 / -1 / -inf / -inf),
+    count i32 [nq], bad i32 [1] (1 = a listed row lies outside the index: it was skipped, the caller treats the call as failed).
+    One launch enqueued on the current torch stream."""
+    import torch
+    nq, F = cand_row.shape
+    k = int(n_results)
+    dev = cand_row.device
+    want = (torch.float32, torch.int64, torch.int32)
+    for t, dt in zip((cand_score, cand_row, cand_count), want):
+        if not t.is_cuda or t.device != dev or t.dtype != dt or not t.is_contiguous() or t.device.index != index.device:
+            raise ValueError(f"mmr_select takes contiguous torch tensors of the documented types on cuda:{index.device}")
+    if cand_score.shape != cand_row.shape or cand_count.shape != (nq,):
+        raise ValueError("mmr_select: cand_score / cand_row must be [nq][fetch_k], cand_count [nq]")
+    kk = max(k, 1)
+    out = {"pos": torch.empty((nq, kk), dtype=torch.int32, device=dev), "row": torch.empty((nq, kk), dtype=torch.int64, device=dev),
+           "score": torch.empty((nq, kk), dtype=torch.float32, device=dev), "value": torch.empty((nq, kk), dtype=torch.float64, device=dev),
+           "count": torch.empty(nq, dtype=torch.int32, device=dev), "bad": torch.zeros(1, dtype=torch.int32, device=dev)}
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    L.check(index._lib.rdx_index_mmr(index._h, p(cand_score), p(cand_row), p(cand_count), nq, int(F), k, float(lambda_mult), p(out["pos"]),
+                                     p(out["row"]), p(out["score"]), p(out["value"]), p(out["count"]), p(out["bad"]),
+                                     ctypes.c_void_p(HipIndex._raw_stream(dev))))
+    return out
+
+
 def l2_normalize(x: np.ndarray, device: int = 0) -> np.ndarray:
     lib = L.load(require_gpu=True)
     a = np.ascontiguousarray(x, dtype=np.float32)
