@@ -85,10 +85,14 @@ int rdx_index_add_bf16(rdx_index* h, const uint16_t* rows, int64_t n, int space)
  * L2-normalised; they are stored VERBATIM (no second normalisation, which could move a component by an ulp), so scores
  * after a reload are bit-identical to those before it. NaN/Inf rows are rejected as in rdx_index_add. */
 int rdx_index_add_stored(rdx_index* h, const float* rows, int64_t n, int space);
-/* `collection.update(ids=, embeddings=)` / upsert: overwrite existing rows in place. */
+/* `collection.update(ids=, embeddings=)` / upsert: overwrite existing rows in place. All or nothing: a call with a row id outside
+ * [0, count()), a row id given more than once (two rows of one call have no order: RDX_ERR_INVALID, the message names the id) or a
+ * row containing NaN/Inf (RDX_ERR_INVALID) is refused before anything is written; every row of the index and every search result
+ * is then what it was before the call. */
 int rdx_index_update(rdx_index* h, const int64_t* row_ids, const float* rows, int64_t n, int space);
 /* rdx_index_update for rows that ARE stored values, as rdx_index_add_stored is to rdx_index_add: written verbatim (the lifted rows
- * of an "ip" / "l2" collection, below). Additive: rdx_index_update is unchanged. */
+ * of an "ip" / "l2" collection, below). Additive: rdx_index_update is unchanged. Refused under the same rules, as completely: an id
+ * out of range or given more than once, or a NaN/Inf row, and nothing is written. */
 int rdx_index_update_stored(rdx_index* h, const int64_t* row_ids, const float* rows, int64_t n, int space);
 /* `collection.get(include=["embeddings"])`: the stored (normalised) fp32 rows. */
 int rdx_index_get(rdx_index* h, const int64_t* row_ids, int64_t n, float* out, int space);

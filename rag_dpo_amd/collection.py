@@ -97,6 +97,15 @@ def _is_device_tensor(x) -> bool:
     return torch is not None and isinstance(x, torch.Tensor) and x.is_cuda
 
 
+def _check_unique(ids):
+    """add's and update's rule, chromadb's wording: an id appears once in a call"""
+    if len(set(ids)) != len(ids):
+        seen, dups = set(), set()
+        for s in ids:
+            (dups if s in seen else seen).add(s)
+        raise DuplicateIDError(f"Expected IDs to be unique, found duplicates of: {', '.join(sorted(dups))}")
+
+
 def _as_matrix(embeddings, what: str):
     """-> contiguous fp32 [n][dim]: a numpy array, or the caller's torch CUDA tensor passed through untouched
     (EmbeddingProvider.embed_device -> add: the batch never becomes Python floats)"""
@@ -530,11 +539,7 @@ class Collection:
         for name, lst in (("metadatas", metadatas), ("documents", documents)):
             if lst is not None and len(lst) != n:
                 raise ValueError(f"Unequal lengths for fields: ids: {n}, {name}: {len(lst)}")
-        if len(set(ids)) != n:
-            seen, dups = set(), set()
-            for s in ids:
-                (dups if s in seen else seen).add(s)
-            raise DuplicateIDError(f"Expected IDs to be unique, found duplicates of: {', '.join(sorted(dups))}")
+        _check_unique(ids)
         for s in ids:
             if not isinstance(s, str) or not s:
                 raise ValueError(f"Expected ID to be a non-empty str, got {s!r}")
@@ -570,11 +575,12 @@ class Collection:
 
     def update(self, ids, embeddings=None, metadatas=None, documents=None, **_ignored):
         """reference tag_all_chunks.py:215,224 (metadatas only). Metadata updates MERGE into the stored dict,
-        as chromadb does; ids that do not exist are ignored."""
+        as chromadb does; ids that do not exist are ignored; duplicate ids inside one call raise DuplicateIDError."""
         if isinstance(ids, str):
             ids = [ids]
         ids = list(ids)
         n = len(ids)
+        _check_unique(ids)           # as add does and as chromadb does: two rows for one id have no order, nothing is touched
         emb = _as_matrix(embeddings, "embeddings") if embeddings is not None else None
         if _is_device_tensor(emb):
             emb = emb.cpu().numpy()    # in-place row updates are rare and small: through the host path

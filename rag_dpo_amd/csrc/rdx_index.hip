@@ -907,15 +907,15 @@ extern "C" int rdx_index_xcd_shares(rdx_index* h, double* out8, const double* in
 // ------------------------------------------------------------------------------------------------
 static const int64_t STAGE_ROWS = 32768;
 
-// normalise n rows (host or device, fp32 or bf16) into master/shadow at dst rows (row0.. or dst_ids)
-static int ingest(rdx_index* h, const void* rows, bool is_bf16, int64_t n, int space, int64_t row0, const int64_t* d_dst_ids,
-                  bool verbatim = false) {
+// One pass of K1 over the call's n rows in chunks of STAGE_ROWS (host rows through the staging buffer). write: into master/shadow at
+// the dst rows; otherwise only the verdict — K1 with no master and no scan copy stores nothing but the `bad` flag.
+// *bad = a row of the call holds a NaN or an Inf.
+static int normalize_pass(rdx_index* h, const void* rows, bool is_bf16, int64_t n, int space, int64_t row0, const int64_t* d_dst_ids,
+                          bool verbatim, bool write, int* bad) {
     hipStream_t st = h->own_stream;
-    // the int8 copy: an update may touch any block, an append the last partial one and the new ones
-    if (d_dst_ids) h->i8.mark.rewritten();
-    else h->i8.mark.appended(row0);
-    if (space == RDX_DEVICE) HIP_TRY(hipDeviceSynchronize());   // the caller's producers of `rows` (any stream) are done
     const size_t esz = is_bf16 ? 2 : 4;
+    const MasterView mv = write ? h->mv() : MasterView{nullptr, nullptr, nullptr};
+    _Float16* const shadow = write ? h->store.shadow.as<_Float16>() : nullptr;
     RDX_TRY(h->bad.ensure(sizeof(int)));
     HIP_TRY(hipMemsetAsync(h->bad.p, 0, sizeof(int), st));
     for (int64_t off = 0; off < n; off += STAGE_ROWS) {
@@ -930,13 +930,27 @@ static int ingest(rdx_index* h, const void* rows, bool is_bf16, int64_t n, int s
         const int grid = (int)((m + 3) / 4);
         hipLaunchKernelGGL(k_normalize<false>, dim3(grid), dim3(256), 0, st, is_bf16 ? nullptr : (const float*)src,
                            is_bf16 ? (const uint16_t*)src : nullptr, m, h->dim, d_dst_ids ? d_dst_ids + off : nullptr,
-                           row0 + off, h->mv(), h->store.shadow.as<_Float16>(), h->ksteps, h->scale(), h->bad.as<int>(), (int64_t)0, verbatim ? 1 : 0);
+                           row0 + off, mv, shadow, h->ksteps, h->scale(), h->bad.as<int>(), (int64_t)0, verbatim ? 1 : 0);
         HIP_TRY(hipGetLastError());
         if (space == RDX_HOST) HIP_TRY(hipStreamSynchronize(st));   // staging is reused by the next chunk
     }
-    int bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, h->bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(bad, h->bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return RDX_OK;
+}
+
+// normalise n rows (host or device, fp32 or bf16) into master/shadow at dst rows (row0.. or dst_ids)
+static int ingest(rdx_index* h, const void* rows, bool is_bf16, int64_t n, int space, int64_t row0, const int64_t* d_dst_ids,
+                  bool verbatim = false) {
+    // the int8 copy: an update may touch any block, an append the last partial one and the new ones
+    if (d_dst_ids) h->i8.mark.rewritten();
+    else h->i8.mark.appended(row0);
+    if (space == RDX_DEVICE) HIP_TRY(hipDeviceSynchronize());   // the caller's producers of `rows` (any stream) are done
+    int bad = 0;
+    // An update writes over rows the index holds, and K1 stops only the wave of the bad row: the call's rows are judged first, so that
+    // a refused update has written nothing (include/rdx.h). A refused append leaves its rows beyond the count, where no call reads.
+    if (d_dst_ids) RDX_TRY(normalize_pass(h, rows, is_bf16, n, space, row0, d_dst_ids, verbatim, false, &bad));
+    if (!bad) RDX_TRY(normalize_pass(h, rows, is_bf16, n, space, row0, d_dst_ids, verbatim, true, &bad));
     if (bad) return fail(RDX_ERR_INVALID, "embeddings contain NaN or Inf");
     return RDX_OK;
 }
@@ -989,6 +1003,16 @@ static int check_row_ids(const rdx_index* h, const int64_t* ids, int64_t n) {
     return RDX_OK;
 }
 
+// the ids of rdx_index_update*: each row at most once — two rows of one call for the same destination would be written by two waves
+// at once, and the row could end up holding float4 groups of both
+static int check_distinct_ids(const int64_t* ids, int64_t n) {
+    std::vector<int64_t> s(ids, ids + n);
+    std::sort(s.begin(), s.end());
+    const auto dup = std::adjacent_find(s.begin(), s.end());
+    if (dup != s.end()) return fail(RDX_ERR_INVALID, "row id " + std::to_string(*dup) + " is given more than once");
+    return RDX_OK;
+}
+
 // A host or device int64 id list: checked on the host by check(host copy) — a device list is brought over for that — and made
 // available on the device: a device list as it is, a host list through the scratch `ids`.
 template <class Check>
@@ -1023,7 +1047,11 @@ static int update_impl(const char* fn, rdx_index* h, const int64_t* row_ids, con
     if (h->store.compact) return fail(RDX_ERR_STATE, std::string(fn) + " takes fp32 rows: not available on an index with a compact (bf16) master");
     RDX_TRY(set_device(h));
     const int64_t* d_ids = nullptr;
-    RDX_TRY(stage_ids(h, row_ids, n, space, [&](const int64_t* v) { return check_row_ids(h, v, n); }, &d_ids));
+    const auto held_once = [&](const int64_t* v) {
+        RDX_TRY(check_row_ids(h, v, n));
+        return check_distinct_ids(v, n);
+    };
+    RDX_TRY(stage_ids(h, row_ids, n, space, held_once, &d_ids));
     return ingest(h, rows, false, n, space, 0, d_ids, verbatim);
 }
 

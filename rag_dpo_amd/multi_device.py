@@ -221,6 +221,9 @@ class MultiDeviceIndex:
             raise ValueError("update: rows must be [len(row_ids)][dim]")
         if not np.isfinite(a).all():                      # checked up front: an update must not land on some shards only
             raise ValueError("embeddings contain NaN or Inf")
+        uniq, times = np.unique(ids, return_counts=True)  # ... nor a repeated id, which every shard refuses (include/rdx.h)
+        if (times > 1).any():
+            raise ValueError(f"row id {int(uniq[times > 1][0])} is given more than once")
         self._each(lambda d: self._shards[d].update(self._loc_of[ids[where[d]]], a[where[d]]) if where[d].size else None)
 
     def get(self, row_ids) -> np.ndarray:

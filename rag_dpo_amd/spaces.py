@@ -347,6 +347,9 @@ class SpaceEngine:
         ids = np.ascontiguousarray(row_ids, dtype=np.int64)
         if ids.size and (ids.min() < 0 or ids.max() >= len(self.inner)):
             raise ValueError(f"row id out of range [0, {len(self.inner)})")
+        uniq, times = np.unique(ids, return_counts=True)
+        if (times > 1).any():       # the engine's refusal (include/rdx.h), ahead of a lift that may rescale the stored rows
+            raise ValueError(f"row id {int(uniq[times > 1][0])} is given more than once")
         y = self._lift_batch(np.ascontiguousarray(rows, dtype=np.float32))
         if y.shape[0] != ids.shape[0]:
             raise ValueError("update: rows must be [len(row_ids)][dim]")

@@ -29,8 +29,19 @@ class OracleEngine:
     def add_stored(self, x):
         self.rows = np.concatenate([self.rows, self._check(x)])
 
+    def _check_ids(self, ids):
+        """the ids of an update: rows the engine holds, each at most once (include/rdx.h rdx_index_update)"""
+        ids = np.asarray(ids, dtype=np.int64)
+        if ids.size and (ids.min() < 0 or ids.max() >= len(self)):
+            raise ValueError(f"row id out of range [0, {len(self)})")
+        uniq, times = np.unique(ids, return_counts=True)
+        if (times > 1).any():
+            raise ValueError(f"row id {int(uniq[times > 1][0])} is given more than once")
+        return ids
+
     def update(self, ids, x):
-        self.rows[np.asarray(ids, dtype=np.int64)] = O.normalize_rows(self._check(x))
+        ids, y = self._check_ids(ids), O.normalize_rows(self._check(x))   # all or nothing: both judged before a row changes
+        self.rows[ids] = y
 
     def get(self, ids):
         return self.rows[np.asarray(ids, dtype=np.int64)].copy()

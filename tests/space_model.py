@@ -18,7 +18,8 @@ class StoredOracleEngine(OracleEngine):
     """OracleEngine plus the verbatim in-place update SpaceEngine needs (rdx_index_update_stored)"""
 
     def update_stored(self, ids, x):
-        self.rows[np.asarray(ids, dtype=np.int64)] = self._check(x)
+        ids, y = self._check_ids(ids), self._check(x)
+        self.rows[ids] = y
 
 
 def factory(dim, device=0):

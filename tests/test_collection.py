@@ -119,6 +119,55 @@ def test_collection_contract_cpu():
     run_collection_contract(oracle_factory)
 
 
+def _snapshot(col):
+    g = col.get(include=["embeddings", "metadatas", "documents"])
+    return g["ids"], np.asarray(g["embeddings"]).tobytes(), g["metadatas"], g["documents"]
+
+
+def refuse_update(col, how, dim=64):
+    """one refused update of three rows (how: "repeated" id, or a "nan" in the second embedding) with metadata and documents riding
+    along; the collection must be left as it was. The GPU twin (test_gpu_collection.py) makes the same call on the HIP engine."""
+    fresh = synth.make_queries(3, dim).astype(np.float32)
+    kw = dict(metadatas=[{"t": 1}, {"t": 2}, {"t": 3}], documents=["a", "b", "c"])
+    if how == "repeated":
+        with pytest.raises(DuplicateIDError, match="chunk_5"):
+            col.update(ids=["chunk_5", "chunk_9", "chunk_5"], embeddings=fresh.tolist(), **kw)
+    else:
+        fresh[1, dim // 2] = np.nan
+        with pytest.raises(ValueError, match="NaN"):
+            col.update(ids=["chunk_5", "chunk_9", "chunk_11"], embeddings=fresh.tolist(), **kw)
+
+
+def land_update(col, dim=64):
+    """... and the valid update that follows lands where it should"""
+    fresh = synth.make_queries(2, dim).astype(np.float32)
+    col.update(ids=["chunk_9", "chunk_5"], embeddings=fresh.tolist(), metadatas=[{"t": 2}, {"t": 1}])
+    g = col.get(ids=["chunk_5", "chunk_9"], include=["embeddings", "metadatas"])
+    want = fresh[[1, 0]] / np.linalg.norm(fresh[[1, 0]], axis=1, keepdims=True)
+    assert np.allclose(g["embeddings"], want, atol=1e-6) and [m["t"] for m in g["metadatas"]] == [1, 2]
+
+
+def test_update_with_repeated_ids_raises_and_changes_nothing():
+    col = Collection("rag_dpo_chunks", metadata={"hnsw:space": "cosine"}, engine_factory=oracle_factory)
+    fill(col, n=120)
+    before = _snapshot(col)
+    refuse_update(col, "repeated")
+    assert _snapshot(col) == before
+    with pytest.raises(DuplicateIDError):
+        col.update(ids=["chunk_5", "chunk_5"], metadatas=[{"t": 1}, {"t": 2}])   # without embeddings too
+    assert _snapshot(col) == before
+    land_update(col)
+
+
+def test_update_with_nan_embedding_changes_nothing():
+    col = Collection("rag_dpo_chunks", metadata={"hnsw:space": "cosine"}, engine_factory=oracle_factory)
+    fill(col, n=120)
+    before = _snapshot(col)
+    refuse_update(col, "nan")
+    assert _snapshot(col) == before      # embeddings, metadata and documents
+    land_update(col)
+
+
 def test_where_grammar():
     n = 8
     cols = {"s": Column(n), "i": Column(n), "f": Column(n), "b": Column(n)}

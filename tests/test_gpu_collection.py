@@ -39,6 +39,31 @@ def test_persistent_client_gpu(tmp_path):
         col3._engine.xcd_shares([1, 1, 1, 1, 1, 1, 1, float("nan")])
 
 
+@pytest.mark.parametrize("how", ["repeated", "nan"])
+def test_refused_update_changes_nothing_gpu(tmp_path, how):
+    """the twin of test_collection.py's two refused updates on the HIP engine: the refusal leaves the rows in HBM what the journal
+    holds, so persist + reload answers a query with the same distances as before the refused call"""
+    import numpy as np
+    from rag_dpo_amd import synth
+    from rag_dpo_amd.collection import PersistentClient
+    from test_collection import _snapshot, fill, land_update, refuse_update
+    cl = PersistentClient(path=str(tmp_path / "db"))
+    col = cl.create_collection(name="rag_dpo_chunks", metadata={"hnsw:space": "cosine"})
+    emb, ids, docs, metas = fill(col, n=120)
+    q = np.concatenate([synth.make_queries(2, 64, emb), emb[[5, 9, 11]]]).tolist()   # the rows of the refused call among the queries
+    before, rows = col.query(query_embeddings=q, n_results=20), _snapshot(col)
+    refuse_update(col, how)
+    assert _snapshot(col) == rows
+    now = col.query(query_embeddings=q, n_results=20)
+    assert now["ids"] == before["ids"] and now["distances"] == before["distances"]
+    cl.persist()
+    col2 = PersistentClient(path=str(tmp_path / "db")).get_collection("rag_dpo_chunks")
+    again = col2.query(query_embeddings=q, n_results=20)
+    assert again["ids"] == before["ids"] and again["distances"] == before["distances"]
+    assert _snapshot(col2) == rows
+    land_update(col2)
+
+
 def test_indexer_flow_gpu(tmp_path):
     """ingest -> verify -> reopen -> update on the HIP engine leaves the records (and the verify answers) the reference
     indexer left (tests/golden/indexer_golden.json)"""

@@ -110,6 +110,27 @@ def test_collection_over_several_devices_cpu():
     run_mask_cache(factory)
 
 
+def test_refused_updates_land_on_no_shard():
+    """a repeated id, like a NaN row, is refused before any shard is written (ids 0 and 1 live on different shards)"""
+    dim = 64
+    md, one = make(dim, 3), OracleEngine(dim)
+    corpus = synth.make_corpus(300, dim, duplicates=False)
+    md.add(corpus); one.add(corpus)
+    every = np.arange(300)
+    new = synth.make_queries(3, dim)
+    with pytest.raises(ValueError, match="row id 1 is given more than once"):
+        md.update(np.array([1, 0, 1]), new)
+    same([md.get(every)], [one.get(every)])
+    bad = new.copy()
+    bad[2, 5] = np.inf
+    with pytest.raises(ValueError, match="NaN or Inf"):
+        md.update(np.array([1, 0, 2]), bad)
+    same([md.get(every)], [one.get(every)])
+    md.update(np.array([1, 0, 2]), new); one.update(np.array([1, 0, 2]), new)
+    same([md.get(every)], [one.get(every)])
+    md.close()
+
+
 def test_empty_and_tiny():
     md = make(64, 4)
     q = np.ones((2, 64), np.float32)

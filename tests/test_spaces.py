@@ -195,6 +195,23 @@ def test_rows_that_cannot_be_lifted_are_refused_and_nothing_is_added(space):
     assert col.count() == 20 and len(col._engine) == 20
 
 
+@pytest.mark.parametrize("space", SPACES)
+def test_a_repeated_row_id_is_refused_before_the_lift_rescales(space):
+    """the engine's refusal (include/rdx.h rdx_index_update_stored) comes ahead of the lift: rows 100 times longer than the stored
+    ones would rescale every stored row first"""
+    x = np.random.default_rng(12).standard_normal((20, 8)).astype(np.float32)
+    col = _collection(space, x)
+    eng = col._engine
+    before = (eng.scale_exp, eng.rescales, eng.inner.get(np.arange(20)).tobytes())
+    with pytest.raises(ValueError, match="row id 3 is given more than once"):
+        eng.update(np.array([3, 5, 3]), 100 * x[:3])
+    assert (eng.scale_exp, eng.rescales, eng.inner.get(np.arange(20)).tobytes()) == before
+    from rag_dpo_amd.collection import DuplicateIDError
+    with pytest.raises(DuplicateIDError):
+        col.update(ids=["r3", "r5", "r3"], embeddings=100 * x[:3])
+    assert (eng.scale_exp, eng.rescales, eng.inner.get(np.arange(20)).tobytes()) == before
+
+
 # ---- persistence and import ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("space", SPACES)
 def test_reload_gives_the_same_bits_and_import_keeps_the_space(space, tmp_path):
