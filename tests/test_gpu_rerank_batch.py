@@ -77,6 +77,23 @@ def test_head_rows_equals_the_single_call_on_slices(H):
             assert (np.abs(got.double().cpu().numpy() - ref) <= 1.0001 * bound).all()
 
 
+def test_head_rows_one_row_past_the_single_call_at_hidden_2048():
+    """n = 1025 at H = 2048: 17 row blocks, the last holding one row, and two passes of the k0 loop in each"""
+    H, n = 2048, 1025
+    w = make_head(H, H)
+    cls = torch.randn(n, H, generator=torch.Generator().manual_seed(H + 3)).cuda()
+    cls[n - 1] = cls[0]
+    got, guard_s, guard_w = head_rows(cls, *w)
+    assert (guard_s == SENT_F).all() and (guard_w == SENT_F).all()
+    want = torch.cat([head(cls[a:a + 1024].contiguous(), *w) for a in range(0, n, 1024)])
+    assert torch.equal(got.view(torch.int32), want.view(torch.int32))
+    assert got[0].item() == got[n - 1].item()
+    ref, bound = head_reference(cls, *w)
+    err = np.abs(got.double().cpu().numpy() - ref)
+    assert (err <= 1.0001 * bound).all(), float((err / bound).max())
+    assert np.ptp(ref) > 0.3
+
+
 # ---- selection -----------------------------------------------------------------------------------------------------------------------
 
 def select_batch(scores, boosts, lengths, top_k, min_score, keep_min=3, want_boosted=True):
@@ -210,7 +227,7 @@ def topic_inputs(dim):
     return table, out
 
 
-@pytest.mark.parametrize("dim", [64, 100, 1024])
+@pytest.mark.parametrize("dim", [64, 100, 1024, 4096])
 def test_topic_boost_batch_equals_the_single_call_per_question(dim):
     L, lib_ = lib()
     table, questions = topic_inputs(dim)

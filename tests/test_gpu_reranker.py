@@ -15,11 +15,13 @@ from rag_dpo_amd import reranker as RR
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "golden"))
+import rerank_head_model as HM  # noqa: E402
 import reranker_world as W  # noqa: E402
 from test_reranker import GOLDEN, check_against_gold, run_case  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 U32 = 2.0 ** -24
+head_reference = HM.reference                                                # (score, derived bound): test_gpu_rerank_batch imports it from here
 
 
 def lib():
@@ -53,52 +55,156 @@ def select(scores, boosts, top_k, min_score, keep_min=3):
     return order.cpu().tolist(), final.cpu().tolist(), int(count.item())
 
 
-def head_reference(cls, wd, bd, wo, bo):
-    """fp64 of the fp16 weights: (score, the derived bound on |kernel score - score|)"""
-    h = cls.double().cpu().numpy()
-    W_, b_, w_, c_ = (t.double().cpu().numpy() for t in (wd, bd, wo, bo))
-    H = h.shape[1]
-    z = h @ W_.T + b_
-    logit = np.tanh(z) @ w_ + c_[0]
-    score = 1.0 / (1.0 + np.exp(-logit))
-    # z: per lane an fma chain of H / 64 terms, then a 6-level butterfly, then + b_d: m = H / 64 + 7 roundings of partial sums
-    m = H // 64 + 7
-    gamma = m * U32 / (1 - m * U32)
-    dz = gamma * (np.abs(h) @ np.abs(W_).T) + gamma * np.abs(b_)
-    # tanh is 1-Lipschitz; the rest is fp64 (tanh, the products and at most H / 8 + 7 sums): 1e-12 relative covers it
-    dlogit = dz @ np.abs(w_) + 1e-12 * (np.abs(np.tanh(z)) @ np.abs(w_) + abs(c_[0]))
-    bound = dlogit / 4 + U32 * score + 1e-15                                               # sigmoid is 1/4-Lipschitz; one fp32 rounding
-    return score, bound
-
-
 def make_head(H, seed, scale=3.0):
-    g = torch.Generator().manual_seed(seed)
-    wd = (torch.randn(H, H, generator=g) / H ** 0.5).half().cuda()
-    bd = (torch.randn(H, generator=g) * 0.1).half().cuda()
-    wo = (torch.randn(H, generator=g) * scale / H ** 0.5).half().cuda()
-    bo = (torch.randn(1, generator=g) * 0.5).half().cuda()
-    return wd, bd, wo, bo
+    return tuple(t.cuda() for t in HM.random_head(H, seed, scale))
 
 
-@pytest.mark.parametrize("H", [512, 768, 1024])
+def on_gpu(arrays):
+    return tuple(torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays)
+
+
+HIDDEN = [64, 512, 768, 1024, 1088, 2048, 4096]     # the ends of the admitted range, the tested models' sizes, one and more passes of the k0 loop
+RATIOS = {}                                          # (bound, H) -> max(err / bound) seen: printed by test_report_head_ratios
+
+
+@pytest.mark.parametrize("H", HIDDEN)
 def test_head_against_fp64_with_derived_bound(H):
+    """n = 65 and 129: a second / third row block of one row, whose wave has no second row (two == false). H > 1024: the k0 loop's second
+    and later passes; H = 4096 asks for 64 KiB of dynamic LDS beside the kernel's 2 KiB of static LDS"""
     w = make_head(H, H)
-    g = torch.Generator().manual_seed(H + 1)
-    for n in (1, 3, 40, 100, 1024):
-        cls = torch.randn(n, H, generator=g).cuda()                         # LayerNorm output scale
+    worst = 0.0
+    for n, rows in HM.random_rows(H, (1, 3, 40, 100, 1024, 65, 129) if H <= 1024 else (1, 65, 130)):
+        cls = rows.cuda()
         got = head(cls, *w).double().cpu().numpy()
         want, bound = head_reference(cls, *w)
         err = np.abs(got - want)
+        worst = max(worst, float((err / bound).max()))
         assert (err <= 1.0001 * bound).all(), (H, n, float((err / bound).max()))
         assert np.ptp(want) > 0.3 if n >= 40 else True
         again = head(cls, *w)                                               # no atomics: bit-identical on every call
         assert torch.equal(again, head(cls, *w)) and np.array_equal(again.double().cpu().numpy(), got)
+    RATIOS[("derived", H)] = worst
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
         other = head(cls, *w, stream=side)
     torch.cuda.current_stream().wait_stream(side)
     assert torch.equal(other, again)
+
+
+@pytest.mark.parametrize("H", HIDDEN)
+def test_head_exact_probes_every_hidden(H):
+    """inputs whose every partial sum is exact in fp32 (tests/rerank_head_model.py exact_probe): the whole error allowance is the score's one
+    rounding to fp32 and the fp64 tail. tests/test_rerank_head_model.py shows what that rejects: an fp16 accumulator, a dropped k-round,
+    exchanged w_o entries, a row pair reading one row twice and a missing b_d all miss it by factors of 1e5 and more"""
+    worst = 0.0
+    for n in (1, 2, 65):
+        p = HM.exact_probe(H, n, n)
+        got = head(*on_gpu(p)).double().cpu().numpy()
+        want, tight = HM.tight_reference(*p)
+        err = np.abs(got - want)
+        worst = max(worst, float((err / tight).max()))
+        assert (err <= tight).all(), (H, n, float((err / tight).max()))
+    RATIOS[("tight", H)] = worst
+
+
+def test_report_head_ratios():
+    """(prints what the two tests above measured in this run: max(err / bound) per hidden size)"""
+    for kind in ("derived", "tight"):
+        print(kind + ": " + ", ".join(f"H={H}: {RATIOS[(kind, H)]:.3g}" for H in HIDDEN if (kind, H) in RATIOS))
+
+
+def one_hot_weights(H):
+    """W_d[f][k] in multiples of 1/32 within +-1.5 such that moving f by 1 or k by 1, 64 or 1024 changes the entry"""
+    f = np.arange(H, dtype=np.int64)[:, None]
+    k = np.arange(H, dtype=np.int64)[None, :]
+    return (((7 * f + 13 * k + 5 * (k // 64) + 3 * (k // 1024)) % 97 - 48) / 32.0).astype(np.float16)
+
+
+@pytest.mark.parametrize("H", [1088, 4096])
+def test_head_one_hot_probes_reach_every_k_round_and_feature_block(H):
+    """cls row = e_k, w_o = c e_f: score = sigmoid(c tanh(W_d[f][k] + b_d[f]) + b_o), z exact up to the one fp32 add of b_d. k: the first and
+    last column of every 1024-wide pass of the k0 loop; f: first and last feature of the first and last block, and one mid-block"""
+    c, b_o = 2.0, 0.25
+    Wn = one_hot_weights(H)
+    W64 = Wn.astype(np.float64)
+    rng = np.random.default_rng(H)
+    bn = (rng.standard_normal(H) * 0.1).astype(np.float16)
+    ks = sorted({k for a in range(0, H, 1024) for k in (a, min(a + 1023, H - 1))})
+    fs = [0, 7, 8 * (H // 16) + 3, H - 8, H - 1]
+    assert H - 1 in ks and 1024 in ks and len(ks) == 2 * ((H + 1023) // 1024)
+    cls_n = np.zeros((len(ks), H), dtype=np.float32)
+    cls_n[np.arange(len(ks)), ks] = 1.0
+    wd, bd, cls, bo = on_gpu((Wn, bn, cls_n, np.asarray([b_o], dtype=np.float16)))
+    score_of = lambda z: 1.0 / (1.0 + np.exp(-(c * np.tanh(z) + b_o)))      # noqa: E731
+    for f in fs:
+        wo_n = np.zeros(H, dtype=np.float16)
+        wo_n[f] = c
+        got = head(cls, wd, bd, on_gpu((wo_n,))[0], bo).double().cpu().numpy()
+        z = W64[f, ks] + float(bn[f])
+        want = score_of(z)
+        bound = U32 * want + 1e-12 * (abs(c) + abs(b_o)) / 4 + 1e-15 + U32 * np.abs(z) * abs(c) / 4
+        assert (np.abs(got - want) <= bound).all(), (H, f, (np.abs(got - want) / bound).max())
+        for i, k in enumerate(ks):                                          # a wrong (f, k) would show: every neighbour scores differently
+            for f2, k2 in ((f - 1, k), (f + 1, k), (f, k - 1), (f, k + 1), (f, k - 64), (f, k + 64), (f, k - 1024), (f, k + 1024)):
+                if 0 <= f2 < H and 0 <= k2 < H:
+                    assert abs(score_of(W64[f2, k2] + float(bn[f2])) - want[i]) > 100 * bound[i], (H, f, k, f2, k2)
+
+
+def test_head_saturates_to_exact_zero_and_one_and_never_to_nan():
+    """|z| >= 40: tanh = +-1 exactly. logit >= 40: 1.0f. logit <= -800: exp overflows to inf and 1 / (1 + inf) = 0.0f. fp16 w_o reaches
+    65504, so a checkpoint can get there. Finite inputs whose dot products stay finite in fp32 never give NaN"""
+    H = 1088
+    rng = np.random.default_rng(7)
+    sign = rng.choice([-1.0, 1.0], H)
+    Wn = np.zeros((H, H), dtype=np.float16)
+    Wn[:, 1030] = sign                                                      # z_f = +-v + b_d[f], the column in the second pass of the k0 loop
+    bn = (rng.standard_normal(H) * 0.1).astype(np.float16)
+    v = np.asarray([40.5, -40.5, 1e3, -1e3, 1e30, -1e30, 3e38, -3e38], dtype=np.float32)
+    cls_n = np.zeros((len(v), H), dtype=np.float32)
+    cls_n[:, 1030] = v
+    wd, bd, cls = on_gpu((Wn, bn, cls_n))
+    t = np.sign(v)[:, None] * sign[None, :]                                 # tanh(z) exactly
+    for w0, b0 in ((40.0, 0.0), (-800.0, 0.0), (65504.0, 0.0), (-65504.0, 65504.0), (40.0, 0.5)):
+        wo_n = np.zeros(H, dtype=np.float16)
+        wo_n[H - 3] = w0                                                    # one feature: logit = +-w0 + b0, exact in any order
+        got = head(cls, wd, bd, *on_gpu((wo_n, np.asarray([b0], dtype=np.float16)))).cpu().numpy()
+        logit = t[:, H - 3] * w0 + b0
+        assert not np.isnan(got).any() and ((got == 0.0) | (got == 1.0))[np.abs(logit) >= 800].all()
+        assert (got[logit >= 40] == 1.0).all() and (got[logit <= -800] == 0.0).all() and (logit >= 40).any(), (w0, b0)
+        mid = (logit > -800) & (logit < 40)
+        want = 1.0 / (1.0 + np.exp(-logit[mid]))
+        assert (np.abs(got[mid].astype(np.float64) - want) <= U32 * want + 1e-45).all()   # (-40 and -65504 + 65504 = 0 land here)
+    wo_n = (rng.choice([-1.0, 1.0], H) * rng.choice([65504.0, 800.0, 40.0, 0.5], H)).astype(np.float16)   # every feature saturated, logits in the millions
+    got = head(cls, wd, bd, *on_gpu((wo_n, np.zeros(1, dtype=np.float16)))).cpu().numpy()
+    logit = t @ wo_n.astype(np.float64)                                     # exact: 1088 fp16 values in fp64
+    assert (np.abs(logit) >= 800).all() and not np.isnan(got).any()
+    assert np.array_equal(got, (logit > 0).astype(np.float32))
+
+
+def test_head_non_finite_rows_touch_no_other_row():
+    """NaN and +-Inf rows at the even and the odd place of a wave's row pair, and in the last row of a block with an odd row count: every
+    other row keeps its bits; the poisoned rows score NaN or something in [0, 1]"""
+    H, n = 1088, 64 + 3
+    w = make_head(H, 3)
+    g = torch.Generator().manual_seed(17)
+    clean = torch.randn(n, H, generator=g)
+    nan_row = clean[0].clone()
+    nan_row[[5, 1029]] = float("nan")
+    inf_row = clean[1].clone()
+    inf_row[[0, 63, 1087]] = torch.tensor([float("inf"), float("-inf"), float("inf")])
+    bad = clean.clone()
+    poisoned = {10: nan_row, 11: inf_row, 20: inf_row, 21: nan_row, 33: inf_row, 66: nan_row}   # (10, 11) and (20, 21) are pairs of one wave; 66: block 1's third row
+    for r, row in poisoned.items():
+        bad[r] = row
+    want = head(clean.cuda(), *w).cpu()
+    got = head(bad.cuda(), *w).cpu()
+    others = [r for r in range(n) if r not in poisoned]
+    assert torch.equal(got[others].view(torch.int32), want[others].view(torch.int32))
+    mine = got[sorted(poisoned)].numpy()
+    assert (np.isnan(mine) | ((mine >= 0) & (mine <= 1))).all()
+    assert np.isnan(got[[10, 21, 66]].numpy()).all()                        # a NaN in cls reaches every z of its row: its score is NaN
+    assert torch.equal(head(bad[66:67].contiguous().cuda(), *w).cpu().view(torch.int32), got[66:67].view(torch.int32))   # the same bits alone
 
 
 def test_head_exact_probes():
@@ -133,7 +239,7 @@ def test_select_reproduces_golden_fixture():
         assert sorted(order) == list(range(len(case["idx"])))
 
 
-def test_select_fuzz_against_python_restatement():
+def fuzz_select(keep_min_of):
     rng = np.random.default_rng(11)
     for it in range(60):
         n = int(rng.choice([1, 2, 3, 4, 17, 40, 100, 513, 1000, 1024]))
@@ -144,10 +250,57 @@ def test_select_fuzz_against_python_restatement():
             boosts = np.where(rng.uniform(size=n) < 0.4, rng.choice([0.15, 0.05, -0.1, 0.0, 0.15 * 0.5], n), 0.0)
         top_k = int(rng.choice([0, 1, 2, 3, 8, 10, n, n + 5]))
         min_score = float(rng.choice([0.08, 0.0, 0.5, float(levels[0]), 2.0]))
-        want = RR.select_host(scores, boosts, top_k, min_score)
-        got = select(scores, boosts, top_k, min_score)
-        assert got[0] == want[0] and got[2] == want[2], (it, n, top_k, min_score)
+        keep_min = keep_min_of(n)
+        want = RR.select_host(scores, boosts, top_k, min_score, keep_min)
+        got = select(scores, boosts, top_k, min_score, keep_min)
+        assert got[0] == want[0] and got[2] == want[2], (it, n, top_k, min_score, keep_min)
         assert np.array_equal(np.asarray(got[1]).view(np.int64), np.asarray(want[1]).view(np.int64)), it
+        assert HM.select_model(scores, boosts, top_k, min_score, keep_min)[::2] == want[::2]
+
+
+def test_select_fuzz_against_python_restatement():
+    fuzz_select(lambda n: 3)
+
+
+KEEP_MIN = {"0": lambda n: 0, "1": lambda n: 1, "n": lambda n: n, "n + 1": lambda n: n + 1}
+
+
+@pytest.mark.parametrize("keep_min", list(KEEP_MIN))
+def test_select_fuzz_over_keep_min(keep_min):
+    fuzz_select(KEEP_MIN[keep_min])
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 64, 65, 1024])
+def test_select_with_nan_equals_the_stated_order(n):
+    """numbers first and descending, NaN finals last, ties and NaN among themselves in input order (rerank_head_model.select_model);
+    `boost > 0.0` is false for a NaN boost: that final is the plain score. count = min(top_k, #{final >= min_score}) lifted to keep_min"""
+    rng = np.random.default_rng(n)
+    nan = np.float32("nan")
+    levels = np.asarray([0.0, -0.0, 0.1, 0.29999, 0.3, 0.30001, 0.7, 0.7, 0.95], dtype=np.float32)
+    cases = []
+    for variant in range(3):
+        s = levels[rng.integers(0, len(levels), n)] if variant else rng.uniform(0, 1, n).astype(np.float32)
+        b = rng.choice([0.15, 0.05, -0.1, 0.0, 0.6], n)
+        if variant == 0:
+            s[rng.integers(0, n, max(1, n // 7))] = nan                     # NaN scores (a positive boost on one stays NaN)
+        elif variant == 1:
+            b[rng.integers(0, n, max(1, n // 5))] = np.nan                  # NaN boosts
+        else:
+            s[::2] = nan                                                    # both, NaN first and on every other candidate
+            b[rng.integers(0, n, max(1, n // 5))] = np.nan
+        cases.append((s, b))
+    cases.append((np.full(n, nan, dtype=np.float32), None))                # nothing but NaN
+    seen_nan_kept = False
+    for s, b in cases:
+        for keep_min in (0, 1, 3, n, n + 1):
+            for top_k in (0, 1, n, n + 5):
+                want = HM.select_model(s, b, top_k, 0.3, keep_min)
+                got = select(s, b, top_k, 0.3, keep_min)
+                where = (n, keep_min, top_k)
+                assert got[0] == want[0] and got[2] == want[2], where
+                assert np.array_equal(np.asarray(got[1]).view(np.int64), np.asarray(want[1]).view(np.int64)), where   # (NaN bits too: the score's, widened)
+                seen_nan_kept |= any(np.isnan(got[1][i]) for i in got[0][:got[2]])
+    assert seen_nan_kept or n < 2                                           # keep_min reaches into the NaN tail somewhere
 
 
 def test_invalid_arguments_on_device():

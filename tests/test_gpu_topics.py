@@ -97,7 +97,7 @@ def run_kernel(table, topic_slots, tag_slots, offsets, pairs, threshold, stream=
     return boosts.cpu().numpy(), best.cpu().numpy(), sims.cpu().numpy()
 
 
-DIMS = (1, 63, 64, 65, 1024)
+DIMS = (1, 63, 64, 65, 512, 513, 1024, 4096)    # 512: one full round of TOPIC_KU loads a lane; 513: a second round of one element; 1024: two; 4096: eight
 # (n, topics, tags per candidate, variants): every n, topic count and tag count of the grid, the largest of each together once per
 # dim class; n = 1 runs four variants so that each crafted pair list lands on its only candidate
 SHAPES = [(1, 1, 0, 1), (1, 1, 1, 4), (1, 32, 3, 4), (1, 32, 64, 2), (40, 1, 1, 2), (40, 1, 3, 2), (40, 32, 3, 2), (40, 32, 64, 1), (40, 1, 64, 1),
