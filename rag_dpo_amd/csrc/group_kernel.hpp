@@ -82,6 +82,18 @@ __global__ __launch_bounds__(NT) void k_group_select(const GroupSelectArgs a) {
     __syncthreads();
     // 2. insert: the slot of a code holds the smallest position of that code (the key of a slot is code[tab[slot]], which an
     //    atomicMin among positions of one code never changes)
+    //    Termination: a slot is written once from GROUP_EMPTY (the CAS) and afterwards only by atomicMin among positions of its code,
+    //    so it never becomes empty again and its key never changes. A list holds at most GROUP_MAX_K distinct codes and one code
+    //    claims at most one slot (below), so at most GROUP_MAX_K = GROUP_TABLE / 2 slots are ever taken: a walk that steps
+    //    (s + 1) & (GROUP_TABLE - 1), through the wrap from the last slot to slot 0, meets its own code or an empty slot within
+    //    GROUP_TABLE steps.
+    //    The outputs do not depend on who wins a slot. A position of code c passes a slot only when another code holds it, and
+    //    that slot keeps that code for good; so every position of c passes the same slots and stops at the first slot after them
+    //    that is empty or holds c — all positions of c end in ONE slot, and no other code can end there. WHICH slot that is depends
+    //    on the order in which the codes of a chain arrive; what the later steps read does not: my_slot[] is used only to reach
+    //    tab[my_slot], and after the barrier that is the minimum over the positions of c, whatever the slot.
+    //    (Dense codes below 4182 never share a home slot — the multiplier is 2^32 / phi; tests/test_group_table_model.py states it
+    //    and tests/test_gpu_group_kernels.py::test_select_on_colliding_codes runs the codes that do.)
     int my_slot[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {

@@ -2,7 +2,8 @@
 definition as a literal loop (tests/groups_model.py) and the oracle's exact scores.
 
 k_group_select: list lengths around the wave (63, 64, 65), around the switch between its two workgroup widths (1024, 1025) and the
-largest (4096); each with the smallest, the default and the largest (groups, rows per group). k_group_fill: dims whose float4 groups
+largest (4096); each with the smallest, the default and the largest (groups, rows per group); and, since the dense codes of those
+lists never collide in its position table, codes chosen by home slot (test_select_on_colliding_codes). k_group_fill: dims whose float4 groups
 sit around one and four per lane and beyond the register path (1028), with the job spans (around a wave's 64 listed rows and the
 workgroup's 256), masks and ties the header names."""
 import numpy as np
@@ -15,7 +16,8 @@ pytestmark = pytest.mark.gpu
 
 # ---- k_group_select --------------------------------------------------------------------------------------------------------------
 class Lists:
-    """a batch of ranked lists over one row -> group table; every query owns a disjoint range of rows and of codes"""
+    """a batch of ranked lists over one row -> group table; every query owns a disjoint range of rows, and (add) a disjoint range of
+    codes or (add_global) whatever codes it names"""
 
     def __init__(self, k):
         self.k = k
@@ -37,6 +39,20 @@ class Lists:
             n_local = max(n_local, c + 1)
             self.row_code += [c + self.next_code] * more
         self.next_code += n_local
+        self._list(base, count, scores)
+
+    def add_global(self, codes, count=None, scores=None):
+        """codes: the GLOBAL code of each of the k listed rows (-1: no group). A code may recur in another query: a group's size is
+        its rows in the whole table."""
+        codes = np.asarray(codes, dtype=np.int64)
+        assert codes.shape == (self.k,) and codes.min() >= -1
+        base = len(self.row_code)
+        self.row_code += codes.tolist()
+        self.next_code = max(self.next_code, int(codes.max()) + 1)
+        self._list(base, count, scores)
+
+    def _list(self, base, count, scores):
+        k = self.k
         count = k if count is None else count
         rows = np.arange(base, base + k, dtype=np.int64)
         rows[count:] = -1
@@ -54,12 +70,15 @@ class Lists:
         return rg, off
 
 
-def run_select(L, G, m):
+def run_select(L, G, m, only=None):
+    """only: a slice of the batch's lists to run alone, over the same tables"""
     import torch
     from rag_dpo_amd import engine as E
     dev = torch.device("cuda", 0)
     rg, off = L.tables()
     s, r, c = np.stack(L.scores), np.stack(L.rows), np.asarray(L.counts, dtype=np.int32)
+    if only is not None:
+        s, r, c = (np.ascontiguousarray(a[only]) for a in (s, r, c))
     t = lambda a: torch.from_numpy(a).to(dev)
     out = {k: v.cpu().numpy() for k, v in E.group_select(t(s), t(r), t(c), t(rg), t(off), G, m).items()}
     return out, (s, r, c, rg, off)
@@ -95,9 +114,13 @@ def check_select(out, inputs, G, m):
             assert out["complete"][b, g] == int(not full or listed[code] >= min(m, size)), (b, g, listed[code], size)
 
 
-@pytest.mark.parametrize("G,m", [(1, 1), (5, 3), (64, 16)])
-@pytest.mark.parametrize("k", [1, 63, 64, 65, 1024, 1025, 4096])
-def test_select_matches_the_definition(k, G, m):
+DEFINITION_K = [1, 63, 64, 65, 1024, 1025, 4096]
+GROUPS_AND_SIZES = [(1, 1), (5, 3), (64, 16)]
+
+
+def definition_lists(k, G):
+    """the batch of test_select_matches_the_definition (tests/test_group_table_model.py walks it through the table's model: every
+    query's codes are a dense range, which never collides)"""
     rng = np.random.default_rng(k * 100 + G)
     L = Lists(k)
     L.add(rng.integers(-1, max(2, k // 3), size=k))                               # many groups, some rows without one
@@ -119,8 +142,43 @@ def test_select_matches_the_definition(k, G, m):
         L.add(np.arange(k) % G)
         L.add(np.minimum(np.arange(k), G - 1))                                     # the G-th group appears at the last possible moment
         L.add(np.maximum(np.arange(k) - (k - G), 0))                               # ... and G groups whose last G - 1 close the list
+    return L
+
+
+@pytest.mark.parametrize("G,m", GROUPS_AND_SIZES)
+@pytest.mark.parametrize("k", DEFINITION_K)
+def test_select_matches_the_definition(k, G, m):
+    L = definition_lists(k, G)
     out, inputs = run_select(L, G, m)
     check_select(out, inputs, G, m)
+
+
+@pytest.mark.parametrize("G,m", GROUPS_AND_SIZES)
+@pytest.mark.parametrize("k", [64, 65, 1024, 1025, 4096])
+def test_select_on_colliding_codes(k, G, m):
+    """The position table's probing path, which dense codes never enter (tests/test_group_table_model.py): codes below 2^20 chosen by
+    home slot (GM.collision_lists: one home slot, chains across the wrap from the last slot to slot 0, the first group at the end of
+    a chain, collisions inside one thread, sparse random codes, chains with keyless rows and a list that is not full). Which code
+    gets which slot depends on who wins a CAS; the outputs must not: every output equals the literal loop's, a second run and a
+    run of one list alone return the same bytes."""
+    specs = GM.collision_lists(k)
+    L = Lists(k)
+    seen = set()
+    for spec in specs:
+        displaced, longest, wraps = GM.check_claims(spec)                           # the branch the list is built for is really taken
+        seen |= {name for name, hit in (("displaced", displaced > 0), ("wraps", wraps > 0), ("long", longest >= 64)) if hit}
+        L.add_global(spec.codes, count=spec.count)
+    assert {"displaced", "wraps"} <= seen and (k < 100 or "long" in seen)
+    out, inputs = run_select(L, G, m)
+    check_select(out, inputs, G, m)
+    again, _ = run_select(L, G, m)
+    for name in out:
+        assert again[name].tobytes() == out[name].tobytes(), name
+    j = [spec.name for spec in specs].index("chain_shuffled")
+    alone, _ = run_select(L, G, m, only=slice(j, j + 1))
+    for name in ("row", "score", "count", "code", "complete", "found", "short"):
+        assert alone[name][0].tobytes() == out[name][j].tobytes(), name
+    assert alone["bad"].tolist() == [0]
 
 
 @pytest.mark.parametrize("k", [64, 4096])

@@ -1,5 +1,7 @@
 """GPU: Collection.query_groups / query_groups_device end to end against the definition evaluated from the ORACLE's ranking
-(tests/groups_model.py), bit for bit, on corpora planted so that every rung of the ladder runs — which `group_stats` then shows."""
+(tests/groups_model.py), bit for bit, on corpora planted so that every rung of the ladder runs — which `group_stats` then shows —
+and on one with enough groups (12 000) that their codes collide in k_group_select's position table, which the table's model shows
+from the oracle's ranking before the GPU is asked."""
 import numpy as np
 import pytest
 
@@ -184,6 +186,128 @@ def test_tombstones_and_key_updates(oracle):
     col.update(ids=keep[:1], metadatas=[{"doc": 7}])             # a value of another kind is a group of its own
     values[int(keep[0][2:])] = 7
     check(col, oracle, emb, q, values, allow=alive)
+
+
+# ---- many groups: k_group_select's table past the codes that never collide (tests/test_group_table_model.py) ----------------------
+def dense_codes(values, alive=None):
+    """GroupTables' numbering restated: codes by first appearance in row order among the live rows that carry the key"""
+    seen, out = {}, np.full(len(values), -1, dtype=np.int64)
+    for i, v in enumerate(values):
+        if v is not None and (alive is None or alive[i]):
+            out[i] = seen.setdefault(GM.group_key(v), len(seen))
+    return out
+
+
+def colliding_pairs(codes, n_pairs, taken, must=()):
+    """pairs of codes whose groups share a home slot in k_group_select's table, none of them in `taken`; `must` come first"""
+    n_groups = int(codes.max()) + 1
+    pairs = [p for p in must]
+    for slot in range(1, GM.GROUP_TABLE):
+        if len(pairs) == n_pairs:
+            break
+        free = [int(c) for c in GM.codes_with_home(slot, n_groups) if c not in taken]
+        if len(free) >= 2:
+            pairs.append((free[0], free[1]))
+    assert len(pairs) == n_pairs and all(GM.home_slot(a) == GM.home_slot(b) and a != b for a, b in pairs)
+    return pairs
+
+
+class ManyGroups:
+    """20 000 rows in about 12 000 groups of 1 - 3 rows scattered over the collection (every 50th row without the key), and three
+    queries: next to query 0 lie the rows of four pairs of groups whose codes collide (0 and 4181 among them); next to query 1 lie
+    300 rows of one group, so its first fetch is short and the second one lists thousands of codes; next to query 2 lie four pairs
+    that collide under the numbering AFTER `gone` (every other of the best 8 rows of queries 0 and 1) is deleted. `keep` is a
+    metadata flag three rows in four carry, the planted ones among them."""
+
+    def __init__(self, O):
+        n, rng = 20_000, np.random.default_rng(21)
+        self.emb = emb = unit(rng, n)
+        sizes = np.resize([1, 1, 2, 1, 2, 3], 12_000)
+        assert sizes.sum() == n
+        owner = rng.permutation(np.repeat(np.arange(len(sizes)), sizes))
+        self.values = values = [None if i % 50 == 49 else f"doc{owner[i]}" for i in range(n)]
+        self.q = q = unit(rng, 3)
+        big = rng.choice(n, 300, replace=False)
+        for i in big:
+            values[i] = "big"
+        emb[big] = q[1] + 0.2 * unit(rng, 300)
+        planted = np.zeros(n, dtype=bool)
+        planted[big] = True
+
+        def plant(codes, pairs, query):
+            rows = np.flatnonzero(np.isin(codes, [c for p in pairs for c in p]))
+            assert not planted[rows].any() and 2 * len(pairs) <= len(rows) <= 6 * len(pairs)
+            emb[rows] = query + 0.3 * unit(rng, len(rows))
+            planted[rows] = True
+
+        best8 = lambda: sorted({int(r) for rows in O.cosine_topk(O.normalize_rows(emb), q[:2], 8)[1] for r in rows[::2]})   # noqa: E731
+        self.codes0 = dense_codes(values)
+        big_code = int(self.codes0[big[0]])
+        self.pairs0 = colliding_pairs(self.codes0, 4, {big_code}, must=[(0, 4181)])
+        assert big_code not in (0, 4181)
+        plant(self.codes0, self.pairs0, q[0])
+        gone = best8()
+        self.alive = np.ones(n, dtype=bool)
+        self.alive[gone] = False
+        self.codes1 = dense_codes(values, self.alive)
+        assert (self.codes1 != self.codes0).any()                                     # the deletes renumber the groups
+        touched = set(self.codes1[planted & self.alive].tolist()) | set(self.codes1[np.isin(self.codes0, self.codes0[gone])].tolist())
+        self.pairs1 = colliding_pairs(self.codes1, 4, touched)
+        plant(self.codes1, self.pairs1, q[2])
+        assert best8() == gone                                                        # (query 2's rows did not change what is deleted)
+        self.gone = [f"id{r}" for r in gone]
+        self.keep = planted | (rng.random(n) < 0.75)
+        self.metas = [({"doc": v} if v is not None else {}) | {"keep": bool(self.keep[i])} for i, v in enumerate(values)]
+
+    def collection(self):
+        from rag_dpo_amd.groups import group_tables
+        col = build(self.emb, self.metas)
+        assert group_tables(col, "doc").row_group.tolist() == self.codes0.tolist()
+        return col
+
+    def displaced(self, O, codes, query, k, allow=None):
+        """codes of the table's model that leave their home slot when k_group_select cuts the oracle's best k rows of `query`"""
+        _, rows, counts = O.cosine_topk(O.normalize_rows(self.emb), self.q[query: query + 1], k, allow)
+        assert counts[0] == k
+        return GM.table_walk(codes[rows[0]])[0]
+
+
+@pytest.fixture(scope="module")
+def many(oracle):
+    return ManyGroups(oracle)
+
+
+def check_many(col, oracle, w, codes, pairs, query, allow=None, **filters):
+    """both fetches on colliding codes — shown from the oracle's ranking before the GPU is asked — then the two answers' bits"""
+    from rag_dpo_amd import groups as GR
+    G, m = 64, 4
+    assert GR.first_fetch_k(G, m) == 256 and GR.K_SECOND == GM.GROUP_MAX_K
+    assert w.displaced(oracle, codes, query, 256, allow) >= len(pairs) == 4          # a pair shares a home slot: one of the two leaves it
+    assert w.displaced(oracle, codes, 1, GR.K_SECOND, allow) > 0                     # the second fetch's list: thousands of codes
+    for G_, m_ in ((G, m), (5, 3)):
+        d = check(col, oracle, w.emb, w.q, w.values, G=G_, m=m_, allow=allow, **filters)
+        assert d["queries"] == 3 and d["proven_first_fetch"] == 2 and d["second_fetch"] == 1 and d["brute"] == 0, (G_, m_, d)
+
+
+def test_many_groups_collide_in_the_first_and_the_second_fetch(many, oracle):
+    check_many(many.collection(), oracle, many, many.codes0, many.pairs0, 0)
+
+
+def test_many_groups_after_deletes_and_under_a_device_filter(many, oracle):
+    from rag_dpo_amd.groups import group_tables
+    w = many
+    col = w.collection()
+    col.delete(ids=w.gone)                                                            # tombstones: the rows stay, the codes are renumbered
+    assert col._n_dead == len(w.gone) and col._rows == len(w.values)
+    assert group_tables(col, "doc").row_group.tolist() == w.codes1.tolist()
+    check_many(col, oracle, w, w.codes1, w.pairs1, 2, allow=w.alive)
+    col._WHERE_DEVICE_MIN_ROWS = 0                                                    # the predicate scan in HBM
+    try:
+        col._drop_masks()
+        check_many(col, oracle, w, w.codes1, w.pairs1, 2, allow=w.alive & w.keep, where={"keep": True})
+    finally:
+        del col._WHERE_DEVICE_MIN_ROWS
+        col._drop_masks()
 
 
 def test_nobody_s_key_and_refusals(spread):
