@@ -782,6 +782,28 @@ int rdx_index_mmr(rdx_index* h, const float* cand_score, const int64_t* cand_row
                   int k, double lambda, int32_t* out_pos, int64_t* out_row, float* out_score, double* out_value, int32_t* out_count,
                   int32_t* out_bad, void* stream);
 
+/* Threshold search ------------------------------------------------------------------------------ */
+/* Which allowed rows score at least t against a query, and how many: the question the reference asks on every request by fetching a
+ * fixed 50 chunks and dropping those with distance > 0.30 on the host (src/rag/validators.py:64-81). rag_dpo_amd/range_search.py states
+ * the definition and turns a distance into t; DESIGN.md §23.
+ *
+ * rdx_index_range. Per query q, with t = thresholds[q]: the ranking is rdx_search's (the same exact fp32 scores, score descending, row
+ * ascending); a row is in range iff it is allowed and its score >= t (float comparison; t = -inf: every allowed row, t = +inf: none).
+ *   out_total int64 [nq]: the rows in range, exact, whatever max_results.
+ *   out_score fp32 / out_row int64 [nq][max_results]: the first min(max_results, total) entries of the ranking; padding -inf / -1.
+ *   out_count int32 [nq]: min(max_results, total).
+ *   out_paths HOST int32[2] (may be NULL): queries answered by the MFMA path (threshold from t, main scan, exact re-score of the hits) /
+ *     by the exact full scan (small problems, option force_exact, and queries whose hits overflowed a segment or the hit list).
+ * Both paths return the same bits. All other pointers are device pointers; the work is enqueued on `stream` and the call returns when the
+ * results are complete. A pending asynchronous search is completed first. The search options force_exact, force_fast, force_bn,
+ * small_scan, fuse_epilogue, cand_cap and refine_list steer it; the statistics and the feedback state of rdx_search are not touched.
+ * RDX_ERR_INVALID before anything is enqueued: max_results outside [1, RDX_RANGE_MAX_RESULTS], nq outside [0, 65535], a mask made for
+ * another device or row count. A NaN threshold or a query holding NaN/Inf: RDX_ERR_INVALID after the run,
+ * the outputs undefined. RDX_ERR_STATE on an index with mapped row ids (a shard). */
+#define RDX_RANGE_MAX_RESULTS 1024
+int rdx_index_range(rdx_index* h, const float* queries, int64_t nq, const float* thresholds, int max_results, const rdx_mask* mask,
+                    float* out_score, int64_t* out_row, int32_t* out_count, int64_t* out_total, int32_t* out_paths, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 // rdx_index.hip — the dense index of librdx: the rdx_index lifecycle, options and ingest, rdx_l2_normalize, the search, masks,
-// merge and signal of include/rdx.h. The only unit that holds a k_scan kernel (rag_dpo_amd/build.py checks that).
+// merge and signal, the grouped fill, the MMR selection and the threshold search of include/rdx.h. The only unit that holds a k_scan kernel (rag_dpo_amd/build.py checks that).
 // The scans and the tail of a search are launched from parameter structs filled by name: enqueue_scan fills ScanParams and its split-K kin,
 // refine_params fills k_refine's RefineParams, run_exact fills the exact path's ExactParams and SelectParams.
 #include "rdx_host.hpp"
@@ -14,6 +14,7 @@
 #include "index_state.hpp"
 #include "k_rows.hpp"
 #include "mmr_kernel.hpp"
+#include "range_kernel.hpp"
 #include "refine_kernel.hpp"
 #include "scan_kernel.hpp"
 #include "search_plan.hpp"
@@ -129,6 +130,7 @@ struct rdx_index {
     // the int8 pass's per-search query copy, scales, bounds, thresholds (nothing of it outlives a search)
     DevBuf qshadow8, tq8, eq8, nq8, thr8, taus8, twoe8;
     DevBuf gjobs;            // rdx_index_group_fill: the call's jobs (query | begin | end)
+    DevBuf rng_ctr;          // rdx_index_range: its own counter block (range_kernel.hpp RangeCounters)
     DevBuf spill;            // k_refine<true>: [nq_pad][spill_cap] hit lists of the queries that outgrow the LDS list (first spilling plan)
     // end-of-search mailbox in pinned host memory (k_finish writes it over PCIe; the host spins on its sequence number)
     MappedPin<Mailbox> mbox;
@@ -254,6 +256,22 @@ static void launch_exact_reg(const rdx_index* h, const ExactParams& ep, hipStrea
     hipLaunchKernelGGL(k_exact_scores_reg<U>, g, dim3(256), 0, st, ep);
 }
 
+// K5a for one group of ep.nq <= QX queries: the register kernel up to dim 1024, the LDS kernel beyond
+static int launch_exact_scores(const rdx_index* h, const ExactParams& ep, int grid_rows, hipStream_t st) {
+    if (h->rows > 0 && h->dim <= 1024) {
+        const int u = (h->dim / 4 + 63) / 64;
+        if (u == 1) launch_exact_reg<1>(h, ep, st);
+        else if (u == 2) launch_exact_reg<2>(h, ep, st);
+        else if (u == 3) launch_exact_reg<3>(h, ep, st);
+        else launch_exact_reg<4>(h, ep, st);
+        HIP_TRY(hipGetLastError());
+    } else if (h->rows > 0) {
+        hipLaunchKernelGGL(k_exact_scores, dim3(std::max(grid_rows, 1)), dim3(256), (size_t)ep.nq * h->dim * 4, st, ep);
+        HIP_TRY(hipGetLastError());
+    }
+    return RDX_OK;
+}
+
 // exact full scan for the queries listed in d_list[0..n_list)
 static int run_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, const uint32_t* d_allow, float* d_score,
                      int64_t* d_row, int32_t* d_count, hipStream_t st, bool stamps = false, const FinishArgs* fin = nullptr) {
@@ -280,17 +298,7 @@ static int run_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, con
     for (int j0 = 0; j0 < n_list; j0 += QX) {
         ep.q_list = sel.q_list = d_list + j0;
         ep.nq = std::min(QX, n_list - j0);
-        if (h->rows > 0 && h->dim <= 1024) {
-            const int u = (h->dim / 4 + 63) / 64;
-            if (u == 1) launch_exact_reg<1>(h, ep, st);
-            else if (u == 2) launch_exact_reg<2>(h, ep, st);
-            else if (u == 3) launch_exact_reg<3>(h, ep, st);
-            else launch_exact_reg<4>(h, ep, st);
-            HIP_TRY(hipGetLastError());
-        } else if (h->rows > 0) {
-            hipLaunchKernelGGL(k_exact_scores, dim3(std::max(grid_rows, 1)), dim3(256), (size_t)ep.nq * h->dim * 4, st, ep);
-            HIP_TRY(hipGetLastError());
-        }
+        RDX_TRY(launch_exact_scores(h, ep, grid_rows, st));
         hipLaunchKernelGGL(k_select_dense, dim3(ep.nq), dim3(1024), 0, st, sel, (fin && j0 + QX >= n_list) ? *fin : no_fin);
         HIP_TRY(hipGetLastError());
     }
@@ -492,6 +500,18 @@ static int prepare_i8(rdx_index* h, const SearchPlan& p, hipStream_t st) {
     return RDX_OK;
 }
 
+// the identity query list of an exact-only search, uploaded once (grow-only), not per search
+static int ensure_iota(rdx_index* h, int nq_pad, hipStream_t st) {
+    if ((size_t)nq_pad * 4 <= h->iota.bytes) return RDX_OK;
+    RDX_TRY(h->iota.ensure((size_t)nq_pad * 4));
+    const size_t cnt = h->iota.bytes / 4;
+    std::vector<int32_t> io_list(cnt);
+    for (size_t i = 0; i < cnt; ++i) io_list[i] = (int32_t)i;
+    HIP_TRY(hipMemcpyAsync(h->iota.p, io_list.data(), cnt * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RDX_OK;
+}
+
 // Grow the scratch the plan needs and enqueue it, up to k_finish and the D2H copies of large host results; *seq: the search's number
 static int enqueue_search(rdx_index* h, const SearchPlan& p, const SearchIO& io, const HostOut* ho, hipStream_t st,
                           unsigned long long* seq) {
@@ -530,14 +550,7 @@ static int enqueue_search(rdx_index* h, const SearchPlan& p, const SearchIO& io,
     const FinishArgs fin = finish_args(h, p, io, *seq);
     if (p.exact_only) {
         for (int i = 2; i <= 3; ++i) mark(h, p, st, i);   // events 3..4 bracket the dominant kernels of this path too (K5a + K5b)
-        if ((size_t)p.nq_pad * 4 > h->iota.bytes) {   // identity query list, uploaded once (grow-only), not per search
-            RDX_TRY(h->iota.ensure((size_t)p.nq_pad * 4));
-            const size_t cnt = h->iota.bytes / 4;
-            std::vector<int32_t> io_list(cnt);
-            for (size_t i = 0; i < cnt; ++i) io_list[i] = (int32_t)i;
-            HIP_TRY(hipMemcpyAsync(h->iota.p, io_list.data(), cnt * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
+        RDX_TRY(ensure_iota(h, p.nq_pad, st));
         RDX_TRY(run_exact(h, h->iota.as<int32_t>(), (int)p.nq, p.k, io.allow, io.score, io.row, io.count, st, p.prof == 3,
                           p.fuse_finish ? &fin : nullptr));
         for (int i = 4; i <= 5; ++i) mark(h, p, st, i);
@@ -1467,6 +1480,179 @@ extern "C" int rdx_index_mmr(rdx_index* h, const float* cand_score, const int64_
     else if (u == 4) launch_mmr<4>(mp, nq, st);
     else launch_mmr<0>(mp, nq, st);
     HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+// ---- threshold search ------------------------------------------------------------------------------------------
+static_assert(RDX_RANGE_MAX_RESULTS <= REFINE_PMAX && RDX_RANGE_MAX_RESULTS <= SELECT_MAX_K, "range_kernel.hpp ranks max_results entries in k_refine's arrays");
+
+// the caller's buffers of one chunk of a range search (device addresses)
+struct RangeIO {
+    const float* queries;
+    const float* thr;
+    const uint32_t* allow;
+    float* score;
+    int64_t* row;
+    int32_t* count;
+    int64_t* total;
+};
+
+// the exact path of a range search for the queries listed in d_list[0..n_list): K5a per group of QX queries, then k_range_select_dense
+static int run_range_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, const RangeIO& io, hipStream_t st) {
+    RDX_TRY(h->dense.ensure((size_t)QX * std::max<int64_t>(h->rows, 1) * 4));
+    ExactParams ep = {};
+    ep.master = h->mv();
+    ep.rows = h->rows;
+    ep.dim = h->dim;
+    ep.qhat = h->qhat.as<float>();
+    ep.allow = io.allow;
+    ep.out = h->dense.as<float>();
+    SelectParams sel = {};
+    sel.scores = h->dense.as<float>();
+    sel.rows = h->rows;
+    sel.k = k;
+    sel.ids = RowIds{h->row_base, h->store.ids()};
+    sel.out = TopkOut{io.score, io.row, io.count};
+    const int grid_rows = (int)std::min<int64_t>((h->rows + 3) / 4, (int64_t)h->n_cu * 16);
+    for (int j0 = 0; j0 < n_list; j0 += QX) {
+        ep.q_list = sel.q_list = d_list + j0;
+        ep.nq = std::min(QX, n_list - j0);
+        RDX_TRY(launch_exact_scores(h, ep, grid_rows, st));
+        hipLaunchKernelGGL(k_range_select_dense, dim3(ep.nq), dim3(1024), 0, st, sel, io.thr, io.total);
+        HIP_TRY(hipGetLastError());
+    }
+    return RDX_OK;
+}
+
+// One chunk (nq <= 4096) of a range search: plan_range, K1, k_range_tau, then the exact path for everybody, or the main scan,
+// k_range_refine and the exact path for the queries it listed. Returns with the stream drained; paths[0] / [1] take the chunk's queries
+// by path.
+static int range_chunk(rdx_index* h, const RangeIO& io, int64_t nq, int k, hipStream_t st, int32_t* paths) {
+    SearchPlan p;
+    std::string err;
+    const int prc = plan_range(h->shape(), h->opt, nq, k, &p, &err);
+    if (prc != RDX_OK) return fail(prc, err);
+    RDX_TRY(h->qhat.ensure((size_t)p.nq_pad * h->dim * 4));
+    RDX_TRY(h->tau.ensure((size_t)p.nq_pad * 4));
+    RDX_TRY(h->exact_list.ensure((size_t)p.nq_pad * 4));
+    RDX_TRY(h->rng_ctr.ensure(sizeof(RangeCounters)));
+    if (!p.exact_only) {
+        RDX_TRY(h->qshadow.ensure((size_t)p.nq_pad * h->dim_pad * 2));
+        RDX_TRY(h->cntw.ensure((size_t)p.nq_pad * p.n_streams * 4));
+        RDX_TRY(h->cand.ensure((size_t)p.nq_pad * p.n_streams * p.capw * 8));
+    }
+    RangeCounters* const ctr = h->rng_ctr.as<RangeCounters>();
+    int* const d_bad = reinterpret_cast<int*>(h->rng_ctr.as<char>() + offsetof(RangeCounters, bad));
+    HIP_TRY(hipMemsetAsync(h->rng_ctr.p, 0, sizeof(RangeCounters), st));
+    // K1 on the queries, the call a search makes: the same qhat bits (and, for the scan, the same tiled fp16 copy)
+    hipLaunchKernelGGL(k_normalize<true>, dim3((int)((p.nq_pad + 3) / 4)), dim3(256), 0, st, io.queries, (const uint16_t*)nullptr, nq, h->dim,
+                       (const int64_t*)nullptr, (int64_t)0, MasterView{h->qhat.as<float>(), nullptr, nullptr},
+                       p.exact_only ? (_Float16*)nullptr : h->qshadow.as<_Float16>(), h->ksteps, h->scale(), d_bad, (int64_t)p.nq_pad, 0);
+    HIP_TRY(hipGetLastError());
+    // (on the exact path too: it is also what refuses a NaN threshold)
+    hipLaunchKernelGGL(k_range_tau, dim3((p.nq_pad + 255) / 256), dim3(256), 0, st, io.thr, (int)nq, p.nq_pad, 0.5f * h->two_e(),
+                       std::ldexp(1.0f, 2 * h->scale_log2), h->tau.as<float>(), d_bad);
+    HIP_TRY(hipGetLastError());
+    if (p.exact_only) {
+        RDX_TRY(ensure_iota(h, p.nq_pad, st));
+        RDX_TRY(run_range_exact(h, h->iota.as<int32_t>(), (int)nq, k, io, st));
+    } else {
+        ScanParams sp = {};
+        sp.shadow = h->store.shadow.as<_Float16>();
+        sp.qshadow = h->qshadow.as<_Float16>();
+        sp.ksteps = h->ksteps;
+        sp.rows = h->rows;
+        sp.n_tiles = p.n_tiles;
+        sp.tile_stride = 1;
+        sp.nqt = p.nqt;
+        sp.nq_pad = p.nq_pad;
+        sp.allow = io.allow;
+        sp.tau = h->tau.as<float>();
+        sp.cntw = h->cntw.as<uint32_t>();
+        sp.cand = h->cand.as<uint2>();
+        sp.capw = p.capw;
+        sp.inv_scale2 = std::ldexp(1.0f, -2 * h->scale_log2);
+        sp.shadow_bytes = (int64_t)h->store.shadow.bytes;
+        sp.oob = reinterpret_cast<int*>(h->rng_ctr.as<char>() + offsetof(RangeCounters, oob));
+        if (p.use_small) {
+            const SplitKParams sk = {sp.shadow, sp.qshadow, sp.ksteps, sp.rows, p.n_blocks32, sp.allow};
+            const SmallScanParams ss = {sk, sp.tau, sp.cntw, sp.cand, sp.capw, sp.inv_scale2, nullptr};
+            hipLaunchKernelGGL(k_scan_small, dim3((unsigned)p.grid), dim3(512), 0, st, ss);
+            HIP_TRY(hipGetLastError());
+        } else {
+            RDX_TRY(launch_scan_bn<EPI_EMIT>(h, p.bn, p.res, p.fused, sp, p.grid, st));
+        }
+        RangeParams rp = {};
+        rp.r.cand = sp.cand;
+        rp.r.cntw = sp.cntw;
+        rp.r.n_streams = p.n_streams;
+        rp.r.capw = p.capw;
+        rp.r.list_cap = p.list_cap;
+        rp.r.k = k;
+        rp.r.qhat = h->qhat.as<float>();
+        rp.r.master = h->mv();
+        rp.r.dim = h->dim;
+        rp.r.ids = RowIds{h->row_base, h->store.ids()};
+        rp.r.out = TopkOut{io.score, io.row, io.count};
+        rp.thr = io.thr;
+        rp.total = io.total;
+        rp.fallback_list = h->exact_list.as<int32_t>();
+        rp.ctr = ctr;
+        const size_t lds = (size_t)p.list_cap * 8;
+        RDX_TRY(dynamic_lds(h->device, (const void*)k_range_refine, lds));
+        hipLaunchKernelGGL(k_range_refine, dim3((unsigned)nq), dim3(1024), lds, st, rp);
+        HIP_TRY(hipGetLastError());
+    }
+    RangeCounters c = {};
+    HIP_TRY(hipMemcpyAsync(&c, h->rng_ctr.p, sizeof(c), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (c.oob) return fail(RDX_ERR_STATE, "internal: the scan computed a corpus address outside the scan copy (RDX_CHECK_BOUNDS build)");
+    if (c.bad) return fail(RDX_ERR_INVALID, "query embeddings contain NaN or Inf, or a threshold is NaN");
+    int n_fb = p.exact_only ? (int)nq : c.n_fallback;
+    if (!p.exact_only && n_fb > 0) {
+        if (n_fb > nq) return fail(RDX_ERR_STATE, "internal: more fallback queries than queries");
+        RDX_TRY(run_range_exact(h, h->exact_list.as<int32_t>(), n_fb, k, io, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    paths[0] += (int32_t)(nq - n_fb);
+    paths[1] += n_fb;
+    return RDX_OK;
+}
+
+extern "C" int rdx_index_range(rdx_index* h, const float* queries, int64_t nq, const float* thresholds, int max_results, const rdx_mask* mask,
+                               float* out_score, int64_t* out_row, int32_t* out_count, int64_t* out_total, int32_t* out_paths, void* stream) {
+    if (!h) return fail(RDX_ERR_INVALID, "rdx_index_range: null index");
+    if (max_results < 1 || max_results > RDX_RANGE_MAX_RESULTS)
+        return fail(RDX_ERR_INVALID, "rdx_index_range: max_results must be in [1, " + std::to_string(RDX_RANGE_MAX_RESULTS) + "]");
+    if (nq < 0 || nq > 65535) return fail(RDX_ERR_INVALID, "rdx_index_range: nq must be in [0, 65535]");
+    int32_t paths[2] = {0, 0};
+    if (out_paths) out_paths[0] = out_paths[1] = 0;
+    if (nq == 0) return RDX_OK;
+    if (!queries || !thresholds || !out_score || !out_row || !out_count || !out_total) return fail(RDX_ERR_INVALID, "rdx_index_range: null pointer");
+    if (((uintptr_t)queries & 15) || (((uintptr_t)out_row | (uintptr_t)out_total) & 7) ||
+        (((uintptr_t)thresholds | (uintptr_t)out_score | (uintptr_t)out_count) & 3))
+        return fail(RDX_ERR_INVALID, "rdx_index_range: misaligned pointer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (mask && (mask->device != h->device || mask->rows != h->rows))
+        return fail(RDX_ERR_INVALID, "rdx_index_range: the mask was made for " + std::to_string(mask->rows) + " rows on device " +
+                                         std::to_string(mask->device) + ", the index now holds " + std::to_string(h->rows) +
+                                         " (a mask does not outlive a write to the index)");
+    if (h->store.row_map.p || h->row_base != 0)
+        return fail(RDX_ERR_STATE, "rdx_index_range: the index returns mapped row ids (a shard): not available");
+    RDX_TRY(finish_pending(h, nullptr));
+    RDX_TRY(set_device(h));
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t CHUNK = 4096;   // queries per pipeline pass, as a search chunks them (search_impl)
+    for (int64_t q0 = 0; q0 < nq; q0 += CHUNK) {
+        const int64_t m = std::min(CHUNK, nq - q0);
+        const RangeIO io = {queries + (size_t)q0 * h->dim, thresholds + q0, mask ? mask->words.as<uint32_t>() : nullptr,
+                            out_score + (size_t)q0 * max_results, out_row + (size_t)q0 * max_results, out_count + q0, out_total + q0};
+        RDX_TRY(range_chunk(h, io, m, max_results, st, paths));
+    }
+    if (out_paths) {
+        out_paths[0] = paths[0];
+        out_paths[1] = paths[1];
+    }
     return RDX_OK;
 }
 

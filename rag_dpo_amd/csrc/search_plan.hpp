@@ -323,6 +323,49 @@ inline int plan_search(const PlanShape& h, const SearchOptions& o, const SearchA
     return RDX_OK;
 }
 
+// What a threshold search (rdx_index_range) of nq queries with lists of max_results launches: the MAIN-SCAN half of what
+// plan_search decides for (nq, k = max_results, depth 0), from the shape and the options alone — no feedback state is read, none is
+// written. The user supplies the threshold, so nothing of a bootstrap is planned; the scan is the fp16 one (never int8), hit lists
+// live in LDS (never spill), every tile is dealt with stride 1, no XCD split and no stamps. Filled: exact_only (the small /
+// force_exact / force_fast rule), bn, nqt, grid, G, n_streams, res, fused, use_small, n_tiles, n_blocks32, capw, list_cap; the options
+// force_exact, force_fast, force_bn, small_scan, fuse_epilogue, cand_cap and refine_list steer it as they steer a search.
+// max_results only SIZES the segments: above K_FAST_MAX (where plan_search leaves the MFMA path) they are those of K_FAST_MAX times
+// ceil(max_results / K_FAST_MAX), at most 4096 slots. The hit list is always the largest one, REFINE_LIST entries (option refine_list
+// lowers it): plan_search sizes its list by the hits a SAMPLED threshold is expected to leave, which says nothing about a threshold the
+// user chose, and a shorter list would only send queries to the exact scan that the kernel could have answered.
+inline int plan_range(const PlanShape& h, const SearchOptions& o, int64_t nq, int max_results, SearchPlan* out, std::string* err) {
+    SearchOptions oo = o;
+    oo.coarse_i8 = 0;
+    oo.refine_spill = 0;
+    oo.profile = 0;
+    oo.xcd_balance = 0;
+    const int k_plan = std::min(max_results, K_FAST_MAX);
+    SearchPlan s;
+    const int rc = plan_search(h, oo, SearchAdapt{}, nq, k_plan, 0, false, &s, err);
+    if (rc != RDX_OK) return rc;
+    SearchPlan& p = *out = SearchPlan{};
+    p.nq = nq;
+    p.k = max_results;
+    p.nq_pad = s.nq_pad;
+    p.exact_only = s.exact_only;
+    if (p.exact_only) return RDX_OK;
+    p.bn = s.bn;
+    p.nqt = s.nqt;
+    p.grid = s.grid;
+    p.G = s.G;
+    p.n_streams = s.n_streams;
+    p.res = s.res;
+    p.fused = s.fused;
+    p.use_small = s.use_small;
+    p.n_tiles = s.n_tiles;
+    p.n_blocks32 = s.n_blocks32;
+    p.capw = s.capw;
+    p.list_cap = o.refine_list ? std::min<uint32_t>(REFINE_LIST, (uint32_t)o.refine_list) : (uint32_t)REFINE_LIST;
+    const int mul = (max_results + K_FAST_MAX - 1) / K_FAST_MAX;
+    if (mul > 1 && !o.cand_cap) p.capw = (uint32_t)std::min<int64_t>((int64_t)s.capw * mul, 4096);
+    return RDX_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // the option table
 // ------------------------------------------------------------------------------------------------

@@ -558,6 +558,35 @@ def mmr_select(index: "HipIndex", cand_score, cand_row, cand_count, n_results: i
     return out
 
 
+# ---- threshold search (include/rdx.h rdx_index_range; rag_dpo_amd/range_search.py states the definition) ------------------------
+def range_search(index: "HipIndex", queries, thresholds, max_results: int, mask: Optional[ResidentMask] = None):
+    """queries fp32 [nq][dim] and thresholds fp32 [nq] (score thresholds t, range_search.score_threshold) as contiguous torch tensors on
+    the index's device -> (scores f32 [nq][m], rows i64 [nq][m], counts i32 [nq], totals i64 [nq]) there and paths = [queries answered
+    by the MFMA path, by the exact scan] (a host list): per query the allowed rows with score >= t, counted exactly, the best m =
+    max_results of them in a search's order, padding -inf / -1. Enqueued on the current torch stream, complete on return."""
+    import torch
+    m = int(max_results)
+    dev = queries.device
+    for t in (queries, thresholds):
+        if not t.is_cuda or t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.device.index != index.device:
+            raise ValueError(f"range_search takes contiguous fp32 torch tensors on cuda:{index.device}")
+    if queries.dim() != 2 or queries.shape[1] != index.dim:
+        raise ValueError(f"range_search: queries must be [nq][{index.dim}]")
+    nq = int(queries.shape[0])
+    if thresholds.shape != (nq,):
+        raise ValueError("range_search: thresholds must be [nq]")
+    mm = max(m, 1)
+    sc = torch.empty((nq, mm), dtype=torch.float32, device=dev)
+    ro = torch.empty((nq, mm), dtype=torch.int64, device=dev)
+    cn = torch.empty(nq, dtype=torch.int32, device=dev)
+    tt = torch.empty(nq, dtype=torch.int64, device=dev)
+    paths = (ctypes.c_int32 * 2)(0, 0)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    L.check(index._lib.rdx_index_range(index._h, p(queries), nq, p(thresholds), m, mask._h if mask is not None else None, p(sc), p(ro),
+                                       p(cn), p(tt), paths, ctypes.c_void_p(HipIndex._raw_stream(dev))))
+    return sc, ro, cn, tt, [int(paths[0]), int(paths[1])]
+
+
 def l2_normalize(x: np.ndarray, device: int = 0) -> np.ndarray:
     lib = L.load(require_gpu=True)
     a = np.ascontiguousarray(x, dtype=np.float32)
