@@ -155,7 +155,8 @@ int rdx_index_set_row_ids(rdx_index* h, int64_t first_row, const int64_t* ids, i
  * (edges at the 50 / 75 / 87.5 ... % quantiles of the blocks' errors, the top class the corpus' largest) instead of the corpus' largest
  * throughout: fewer hits to gather, the same answers; 0 = 8 where "coarse_i8" = 2 chose the int8 pass, 1 elsewhere (speed only);
  * developer options "refine_list" (0 = automatic, or 32..7168: upper bound on the LDS list's entries) and "spill_cap" (0 = automatic,
- * or 32..40960: upper bound on the HBM list's entries) drive the two lists' limits at small sizes (tests). */
+ * or 32..40960: upper bound on the HBM list's entries) drive the two lists' limits at small sizes (tests);
+ * developer option "dup_batch" (0 = automatic, or 1..4096): rows per batch of rdx_index_near_dup (tests: edges across batch borders). */
 int rdx_index_set_option(rdx_index* h, const char* name, int64_t value);
 
 /* The main scan's tile shares of the 8 XCDs (1.0 = an eighth; option "xcd_balance"): learned from the workgroups' own time stamps
@@ -803,6 +804,30 @@ int rdx_index_mmr(rdx_index* h, const float* cand_score, const int64_t* cand_row
 #define RDX_RANGE_MAX_RESULTS 1024
 int rdx_index_range(rdx_index* h, const float* queries, int64_t nq, const float* thresholds, int max_results, const rdx_mask* mask,
                     float* out_score, int64_t* out_row, int32_t* out_count, int64_t* out_total, int32_t* out_paths, void* stream);
+
+/* Near-duplicate clustering ---------------------------------------------------------------------- */
+/* Which stored rows are near-copies of which others: the threshold search asked of the corpus itself, and the answers joined into
+ * connected components on the device. rag_dpo_amd/dedup.py states the definition; DESIGN.md §24.
+ *
+ * rdx_index_near_dup. "Allowed" = every row, or the rows of `mask`. For an allowed row i, R(i) = the allowed rows whose exact fp32
+ * score against the stored row i (as a query: through the normalisation of every search) is >= threshold: what rdx_index_range
+ * counts for that query. The graph has an edge i - j for every j in R(i), j != i, in either direction.
+ *   out_label int64 [rows] (device): the smallest row of the row's connected component; -1 for a row that is not allowed.
+ *   out_total int64 [rows] (device): |R(i)| (the row itself counts when it is in range); 0 for a row that is not allowed.
+ *   out_stats HOST int64[4] (may be NULL): allowed rows examined / rows linked from their lists / rows linked by the dense pass /
+ *     batches.
+ * The allowed rows are taken as queries in batches (4 096; option "dup_batch"), gathered on the device: the rows never reach the
+ * host. A row with at most list_cap rows in range is linked from the threshold search's list. A row with more ("heavy") is linked
+ * from dense exact scores instead — none of a truncated list is used — at the cost of a quarter of an exact pass over the corpus;
+ * when more than max_dense rows are heavy the call stops with RDX_ERR_INVALID (the distance is too loose for duplicate detection;
+ * the message names the count and list_cap) and the outputs are undefined. Labels and totals do not depend on list_cap, the batch
+ * size, the path or the schedule. The work is enqueued on `stream`; the call returns when the results are complete. A pending
+ * asynchronous search is completed first; an empty index returns RDX_OK. The options that steer rdx_index_range steer it here; the
+ * statistics and the feedback state of rdx_search are not touched.
+ * RDX_ERR_INVALID before anything is enqueued: list_cap outside [1, RDX_RANGE_MAX_RESULTS], a NaN threshold, max_dense < 0, a mask
+ * made for another device or row count, 2^31 rows or more. RDX_ERR_STATE on an index with mapped row ids (a shard). */
+int rdx_index_near_dup(rdx_index* h, float threshold, const rdx_mask* mask, int list_cap, int64_t max_dense, int64_t* out_label,
+                       int64_t* out_total, int64_t* out_stats, void* stream);
 
 #ifdef __cplusplus
 }

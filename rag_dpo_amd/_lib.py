@@ -161,6 +161,7 @@ SYMBOLS = {
     "rdx_index_group_fill": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
     "rdx_index_mmr": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rdx_index_range": (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rdx_index_near_dup": (_i, [_vp, ctypes.c_float, _vp, _i, _i64, _vp, _vp, _vp, _vp]),
 }
 
 

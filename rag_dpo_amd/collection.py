@@ -27,6 +27,9 @@ fetch_k best rows, for corpora whose near-duplicate chunks share no key; rag_dpo
 `query_range` / `query_range_device` (not part of chromadb's API either) return every allowed row within a distance of the query, counted
 exactly, the best max_results of them listed: what the reference does by fetching a fixed 50 and cutting at distance 0.30 on the host
 (src/rag/validators.py:64-81); rag_dpo_amd/range_search.py states the definition. Same limits.
+`near_duplicates` / `near_duplicates_device` (not part of chromadb's API either) ask that question of the stored chunks themselves and
+join the answers into clusters of near-copies on the device: what the reference can only do by content hash before ingest
+(src/processing/deduplicate_corpus.py); rag_dpo_amd/dedup.py states the definition. Same limits.
 ids/documents/metadata stay on the host; embeddings go to the device index (`engine`). The engine is
 always librdx (rag_dpo_amd.engine.HipIndex): there is no CPU search path in this package.
 
@@ -46,6 +49,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
+from . import dedup as DD
 from . import groups as GR
 from . import mmr as MM
 from . import range_search as RS
@@ -177,6 +181,7 @@ class Collection:
         self._group_tables: Dict[str, Any] = {}    # groups.GroupTables per metadata key query_groups has grouped by (valid for one _writes)
         self._group_stats = {k: 0 for k in GR.STAT_KEYS}   # group_stats
         self._range_stats = {"queries": 0, "mfma": 0, "exact": 0, "host": 0}   # range_stats
+        self._dedup_stats = {k: 0 for k in DD.STAT_KEYS}   # dedup_stats
 
     # ---- small helpers ----------------------------------------------------------------------
     @property
@@ -1108,6 +1113,77 @@ class Collection:
                 if "embeddings" in include:
                     out["embeddings"][b] = self._engine.get(np.array(rr, dtype=np.int64)) if rr else np.zeros((0, self._dim), dtype=np.float32)
             return out
+
+    # ---- near-duplicate clustering (rag_dpo_amd/dedup.py states the definition) -----------------------------------
+    def _dedup_check(self, max_neighbors, max_dense_rows, where_document):
+        if not isinstance(max_neighbors, (int, np.integer)) or isinstance(max_neighbors, bool) or not 1 <= max_neighbors <= DD.MAX_NEIGHBORS:
+            raise ValueError(f"Expected max_neighbors to be an int in [1, {DD.MAX_NEIGHBORS}], got {max_neighbors!r}")
+        if not isinstance(max_dense_rows, (int, np.integer)) or isinstance(max_dense_rows, bool) or max_dense_rows < 0:
+            raise ValueError(f"Expected max_dense_rows to be an int >= 0, got {max_dense_rows!r}")
+        if not WD.is_empty(where_document):
+            WD.validate(where_document)
+        space = self.metadata.get("hnsw:space", "cosine")
+        if space != "cosine":
+            raise NotImplementedError(f"near_duplicates cuts at a cosine distance: not available in the {space!r} space")
+        if self._engine is not None and hasattr(self._engine, "devices"):
+            raise NotImplementedError("near_duplicates runs on one device in this version: not on a collection spread over several")
+
+    @property
+    def dedup_stats(self) -> Dict[str, int]:
+        """counters of near_duplicates since the collection was created: `calls`, the allowed `rows` they examined, how many of those
+        the engine linked from their neighbour lists (`listed`) and from dense exact scores (`dense`: rows with more than
+        max_neighbors rows in range), the engine's `batches`, and the rows answered on the `host` (engines without the clustering)"""
+        return dict(self._dedup_stats)
+
+    def _near_dup(self, max_distance, where, where_document, max_neighbors, max_dense_rows, device: bool):
+        """-> (labels, totals): torch tensors on the engine's device (device engines), numpy arrays otherwise; the lock is held"""
+        t = RS.score_threshold(max_distance)
+        args = self._search_args(where, where_document)
+        st = self._dedup_stats
+        st["calls"] += 1
+        if hasattr(self._engine, "search_device") and "allow_bits" not in args:
+            from . import engine as E
+            lab, tot, stats = E.near_dup(self._engine, t, args.get("mask"), int(max_neighbors), int(max_dense_rows))
+            for key, v in zip(("rows", "listed", "dense", "batches"), stats):
+                st[key] += v
+            return lab, tot
+        if device:
+            raise NotImplementedError("this collection's engine has no device-pointer search")
+        allowed = self._mask(where) if WD.is_empty(where_document) else self._wd_mask(where, where_document)
+        lab, tot = DD.near_dup_host(self._engine, t, args, allowed)
+        n = int(self._rows if allowed is None else np.count_nonzero(allowed))
+        st["rows"] += n
+        st["host"] += n
+        return lab, tot
+
+    def near_duplicates_device(self, max_distance, where=None, where_document=None, max_neighbors: int = 1024, max_dense_rows: int = 4096):
+        """near_duplicates for callers that stay on the GPU -> (labels i64 [rows], totals i64 [rows]) on the collection's device:
+        labels[r] = the smallest row of r's cluster (r itself for a row without near-copies), -1 for a row that is deleted or filtered
+        out; totals[r] = the rows within the distance of row r, itself included. `ids_of` / `payload_of` map the rows."""
+        self._dedup_check(max_neighbors, max_dense_rows, where_document)
+        with self._lock:
+            if self._engine is None or self._rows == 0:
+                raise ValueError("near_duplicates_device: the collection is empty")
+            return self._near_dup(max_distance, where, where_document, max_neighbors, max_dense_rows, True)
+
+    def near_duplicates(self, max_distance, where=None, where_document=None, max_neighbors: int = 1024, max_dense_rows: int = 4096):
+        """Near-duplicate clusters of the stored chunks themselves: two allowed rows belong together when one lies within the cosine
+        distance `max_distance` (query()'s floats) of the other, directly or through a chain of such rows.
+        -> {"clusters": [[id, ...], ...], "neighbors": [[total, ...], ...]}: the clusters of at least two rows, each in row order (its
+        first id is the earliest-added row, the natural one to keep), ordered by their first row; beside every id the number of rows
+        within the distance of it, itself included. `max_neighbors` (at most 1 024): rows with more rows than this in range are
+        linked by an exact pass over the corpus instead of from their list; more than `max_dense_rows` such rows raise ValueError
+        (the distance is too loose for duplicate detection). rag_dpo_amd/dedup.py states the definition."""
+        self._dedup_check(max_neighbors, max_dense_rows, where_document)
+        with self._lock:
+            if self._engine is None or self._rows == 0:
+                RS.score_threshold(max_distance)            # (a NaN distance is refused on an empty collection too)
+                return {"clusters": [], "neighbors": []}
+            lab, tot = self._near_dup(max_distance, where, where_document, max_neighbors, max_dense_rows, False)
+            if _is_device_tensor(lab):
+                lab, tot = lab.cpu().numpy(), tot.cpu().numpy()
+            groups = DD.clusters_of(lab)
+            return {"clusters": [[self._ids[r] for r in g] for g in groups], "neighbors": [[int(tot[r]) for r in g] for g in groups]}
 
     def ids_of(self, rows) -> List[List[str]]:
         """Chroma ids of row ids as returned by query_device (negative = padding, skipped)"""

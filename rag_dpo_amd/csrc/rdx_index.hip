@@ -1,5 +1,5 @@
 // rdx_index.hip — the dense index of librdx: the rdx_index lifecycle, options and ingest, rdx_l2_normalize, the search, masks,
-// merge and signal, the grouped fill, the MMR selection and the threshold search of include/rdx.h. The only unit that holds a k_scan kernel (rag_dpo_amd/build.py checks that).
+// merge and signal, the grouped fill, the MMR selection, the threshold search and the near-duplicate clustering of include/rdx.h. The only unit that holds a k_scan kernel (rag_dpo_amd/build.py checks that).
 // The scans and the tail of a search are launched from parameter structs filled by name: enqueue_scan fills ScanParams and its split-K kin,
 // refine_params fills k_refine's RefineParams, run_exact fills the exact path's ExactParams and SelectParams.
 #include "rdx_host.hpp"
@@ -18,6 +18,7 @@
 #include "refine_kernel.hpp"
 #include "scan_kernel.hpp"
 #include "search_plan.hpp"
+#include "dup_kernel.hpp"   // (after the search's kernels: the code object lists them in the order it always did, the new ones behind)
 
 using namespace rdx;
 
@@ -106,6 +107,8 @@ struct I8Copy {
     }
 };
 
+constexpr int64_t RANGE_CHUNK = 4096;   // queries per pipeline pass of rdx_index_range, as a search chunks them (search_impl)
+
 struct rdx_index {
     int device = 0;
     int dim = 0, dim_pad = 0, ksteps = 0, scale_log2 = 0;
@@ -131,6 +134,10 @@ struct rdx_index {
     DevBuf qshadow8, tq8, eq8, nq8, thr8, taus8, twoe8;
     DevBuf gjobs;            // rdx_index_group_fill: the call's jobs (query | begin | end)
     DevBuf rng_ctr;          // rdx_index_range: its own counter block (range_kernel.hpp RangeCounters)
+    // rdx_index_near_dup: the parent array, and per batch the query rows, the gathered queries, their thresholds, the threshold
+    // search's answers, the heavy list and the counter block (dup_kernel.hpp)
+    DevBuf dup_parent, dup_ids, dup_q, dup_thr, dup_score, dup_row, dup_count, dup_total, dup_heavy, dup_ctr;
+    int dup_batch = 0;       // option "dup_batch": rows per batch of rdx_index_near_dup, 0 = the range chunk (tests lower it)
     DevBuf spill;            // k_refine<true>: [nq_pad][spill_cap] hit lists of the queries that outgrow the LDS list (first spilling plan)
     // end-of-search mailbox in pinned host memory (k_finish writes it over PCIe; the host spins on its sequence number)
     MappedPin<Mailbox> mbox;
@@ -893,6 +900,11 @@ extern "C" int rdx_index_set_option(rdx_index* h, const char* name, int64_t valu
         h->row_base = value;
         return RDX_OK;
     }
+    if (n == "dup_batch") {
+        if (value < 0 || value > RANGE_CHUNK) return fail(RDX_ERR_INVALID, "dup_batch must be 0 (the range chunk) or 1.." + std::to_string(RANGE_CHUNK));
+        h->dup_batch = (int)value;
+        return RDX_OK;
+    }
     std::string err;   // every other option is a search's (search_plan.hpp)
     const int rc = set_search_option(h->opt, h->adapt, name, value, &err);
     return rc == RDX_OK ? rc : fail(rc, err);
@@ -1642,9 +1654,8 @@ extern "C" int rdx_index_range(rdx_index* h, const float* queries, int64_t nq, c
     RDX_TRY(finish_pending(h, nullptr));
     RDX_TRY(set_device(h));
     hipStream_t st = (hipStream_t)stream;
-    const int64_t CHUNK = 4096;   // queries per pipeline pass, as a search chunks them (search_impl)
-    for (int64_t q0 = 0; q0 < nq; q0 += CHUNK) {
-        const int64_t m = std::min(CHUNK, nq - q0);
+    for (int64_t q0 = 0; q0 < nq; q0 += RANGE_CHUNK) {
+        const int64_t m = std::min(RANGE_CHUNK, nq - q0);
         const RangeIO io = {queries + (size_t)q0 * h->dim, thresholds + q0, mask ? mask->words.as<uint32_t>() : nullptr,
                             out_score + (size_t)q0 * max_results, out_row + (size_t)q0 * max_results, out_count + q0, out_total + q0};
         RDX_TRY(range_chunk(h, io, m, max_results, st, paths));
@@ -1652,6 +1663,140 @@ extern "C" int rdx_index_range(rdx_index* h, const float* queries, int64_t nq, c
     if (out_paths) {
         out_paths[0] = paths[0];
         out_paths[1] = paths[1];
+    }
+    return RDX_OK;
+}
+
+// ---- near-duplicate clustering ------------------------------------------------------------------------------------
+// Batches of allowed rows, ascending: gather the stored rows as queries (they never leave the device), the threshold search of the
+// batch with lists of list_cap, k_dup_link_lists; then, while the chunk's qhat is still resident, the exact scores of the batch's heavy
+// rows per group of QX and k_dup_link_dense; k_dup_labels after the last batch.
+extern "C" int rdx_index_near_dup(rdx_index* h, float threshold, const rdx_mask* mask, int list_cap, int64_t max_dense, int64_t* out_label,
+                                  int64_t* out_total, int64_t* out_stats, void* stream) {
+    if (!h) return fail(RDX_ERR_INVALID, "rdx_index_near_dup: null index");
+    if (list_cap < 1 || list_cap > RDX_RANGE_MAX_RESULTS)
+        return fail(RDX_ERR_INVALID, "rdx_index_near_dup: list_cap must be in [1, " + std::to_string(RDX_RANGE_MAX_RESULTS) + "]");
+    if (threshold != threshold) return fail(RDX_ERR_INVALID, "rdx_index_near_dup: the threshold is NaN");
+    if (max_dense < 0) return fail(RDX_ERR_INVALID, "rdx_index_near_dup: max_dense must be >= 0");
+    if (out_stats) out_stats[0] = out_stats[1] = out_stats[2] = out_stats[3] = 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (mask && (mask->device != h->device || mask->rows != h->rows))
+        return fail(RDX_ERR_INVALID, "rdx_index_near_dup: the mask was made for " + std::to_string(mask->rows) + " rows on device " +
+                                         std::to_string(mask->device) + ", the index now holds " + std::to_string(h->rows) +
+                                         " (a mask does not outlive a write to the index)");
+    if (h->store.row_map.p || h->row_base != 0)
+        return fail(RDX_ERR_STATE, "rdx_index_near_dup: the index returns mapped row ids (a shard): not available");
+    if (h->rows >= ((int64_t)1 << 31)) return fail(RDX_ERR_INVALID, "rdx_index_near_dup: the parent array holds int32 rows: fewer than 2^31 rows");
+    RDX_TRY(finish_pending(h, nullptr));
+    const int64_t rows = h->rows;
+    if (rows == 0) return RDX_OK;
+    if (!out_label || !out_total) return fail(RDX_ERR_INVALID, "rdx_index_near_dup: null pointer");
+    if (((uintptr_t)out_label | (uintptr_t)out_total) & 7) return fail(RDX_ERR_INVALID, "rdx_index_near_dup: misaligned pointer");
+    RDX_TRY(set_device(h));
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t* const allow = mask ? mask->words.as<uint32_t>() : nullptr;
+    // the allowed rows, ascending: from the bitmap (the only thing of the call the host reads beside counters)
+    std::vector<int64_t> ids;
+    if (allow) {
+        std::vector<uint32_t> words((size_t)((rows + 31) / 32));
+        HIP_TRY(hipMemcpyAsync(words.data(), allow, words.size() * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (int64_t r = 0; r < rows; ++r)
+            if ((words[(size_t)(r >> 5)] >> (r & 31)) & 1u) ids.push_back(r);
+    } else {
+        ids.resize((size_t)rows);
+        for (int64_t r = 0; r < rows; ++r) ids[(size_t)r] = r;
+    }
+    const int64_t n = (int64_t)ids.size();
+    const int64_t B = std::min<int64_t>(h->dup_batch > 0 ? h->dup_batch : RANGE_CHUNK, std::max<int64_t>(n, 1));
+    RDX_TRY(h->dup_parent.ensure((size_t)rows * 4));
+    RDX_TRY(h->dup_ids.ensure((size_t)B * 8));
+    RDX_TRY(h->dup_q.ensure((size_t)B * h->dim * 4));
+    RDX_TRY(h->dup_thr.ensure((size_t)B * 4));
+    RDX_TRY(h->dup_score.ensure((size_t)B * list_cap * 4));
+    RDX_TRY(h->dup_row.ensure((size_t)B * list_cap * 8));
+    RDX_TRY(h->dup_count.ensure((size_t)B * 4));
+    RDX_TRY(h->dup_total.ensure((size_t)B * 8));
+    RDX_TRY(h->dup_heavy.ensure((size_t)B * 4));
+    RDX_TRY(h->dup_ctr.ensure(sizeof(DupCounters)));
+    int32_t* const parent = h->dup_parent.as<int32_t>();
+    const unsigned row_blocks = (unsigned)((rows + 255) / 256);
+    hipLaunchKernelGGL(k_dup_init, dim3(row_blocks), dim3(256), 0, st, parent, allow, rows, out_total);
+    HIP_TRY(hipGetLastError());
+    const std::vector<float> thr((size_t)B, threshold);
+    HIP_TRY(hipMemcpyAsync(h->dup_thr.p, thr.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int64_t n_light = 0, n_heavy = 0, n_batches = 0;
+    int32_t paths[2] = {0, 0};
+    for (int64_t b0 = 0; b0 < n; b0 += B) {
+        const int64_t m = std::min(B, n - b0);
+        HIP_TRY(hipMemcpyAsync(h->dup_ids.p, ids.data() + b0, (size_t)m * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, h->mv(), h->dup_ids.as<int64_t>(), m, h->dim,
+                           h->dup_q.as<float>());
+        HIP_TRY(hipGetLastError());
+        const RangeIO io = {h->dup_q.as<float>(), h->dup_thr.as<float>(), allow, h->dup_score.as<float>(), h->dup_row.as<int64_t>(),
+                            h->dup_count.as<int32_t>(), h->dup_total.as<int64_t>()};
+        RDX_TRY(range_chunk(h, io, m, list_cap, st, paths));
+        HIP_TRY(hipMemsetAsync(h->dup_ctr.p, 0, sizeof(DupCounters), st));
+        DupListParams lp = {};
+        lp.parent = parent;
+        lp.rows = rows;
+        lp.qrow = h->dup_ids.as<int64_t>();
+        lp.nq = (int)m;
+        lp.list_cap = list_cap;
+        lp.row = io.row;
+        lp.count = io.count;
+        lp.total = io.total;
+        lp.out_total = out_total;
+        lp.heavy = h->dup_heavy.as<int32_t>();
+        lp.ctr = h->dup_ctr.as<DupCounters>();
+        hipLaunchKernelGGL(k_dup_link_lists, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, lp);
+        HIP_TRY(hipGetLastError());
+        DupCounters c = {};
+        HIP_TRY(hipMemcpyAsync(&c, h->dup_ctr.p, sizeof(c), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (c.n_heavy < 0 || c.n_heavy > m) return fail(RDX_ERR_STATE, "internal: more heavy rows than rows in the batch");
+        n_heavy += c.n_heavy;
+        n_light += m - c.n_heavy;
+        ++n_batches;
+        if (n_heavy > max_dense)
+            return fail(RDX_ERR_INVALID, "rdx_index_near_dup: " + std::to_string(n_heavy) + " rows so far have more than list_cap = " +
+                                             std::to_string(list_cap) + " rows within the distance (max_dense = " + std::to_string(max_dense) +
+                                             "): the distance is too loose for duplicate detection");
+        if (c.n_heavy > 0) {   // the chunk's qhat (K1 of the gathered rows) is still what range_chunk left
+            RDX_TRY(h->dense.ensure((size_t)QX * rows * 4));
+            ExactParams ep = {};
+            ep.master = h->mv();
+            ep.rows = rows;
+            ep.dim = h->dim;
+            ep.qhat = h->qhat.as<float>();
+            ep.allow = allow;
+            ep.out = h->dense.as<float>();
+            DupDenseParams dp = {};
+            dp.parent = parent;
+            dp.rows = rows;
+            dp.scores = h->dense.as<float>();
+            dp.qrow = h->dup_ids.as<int64_t>();
+            dp.t = threshold;
+            const int grid_rows = (int)std::min<int64_t>((rows + 3) / 4, (int64_t)h->n_cu * 16);
+            const unsigned link_blocks = (unsigned)std::min<int64_t>(row_blocks, (int64_t)h->n_cu * 4);
+            for (int j0 = 0; j0 < c.n_heavy; j0 += QX) {
+                ep.q_list = dp.q_list = h->dup_heavy.as<int32_t>() + j0;
+                ep.nq = dp.nq = std::min(QX, c.n_heavy - j0);
+                RDX_TRY(launch_exact_scores(h, ep, grid_rows, st));
+                hipLaunchKernelGGL(k_dup_link_dense, dim3(link_blocks), dim3(256), 0, st, dp);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+    }
+    hipLaunchKernelGGL(k_dup_labels, dim3(row_blocks), dim3(256), 0, st, parent, rows, out_label);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    if (out_stats) {
+        out_stats[0] = n;
+        out_stats[1] = n_light;
+        out_stats[2] = n_heavy;
+        out_stats[3] = n_batches;
     }
     return RDX_OK;
 }

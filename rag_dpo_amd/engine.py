@@ -587,6 +587,26 @@ def range_search(index: "HipIndex", queries, thresholds, max_results: int, mask:
     return sc, ro, cn, tt, [int(paths[0]), int(paths[1])]
 
 
+# ---- near-duplicate clustering (include/rdx.h rdx_index_near_dup; rag_dpo_amd/dedup.py states the definition) ---------------------
+def near_dup(index: "HipIndex", t, mask: Optional[ResidentMask] = None, list_cap: int = 1024, max_dense: int = 4096):
+    """-> (labels i64 [rows], totals i64 [rows]) on the index's device and stats = [allowed rows examined, rows linked from their
+    lists, rows linked by the dense pass, batches] (a host list): the connected components of "allowed row j scores >= t against the
+    stored row i", labelled by their smallest row (-1: not allowed), and per row the number of rows in range (0: not allowed).
+    Enqueued on the current torch stream, complete on return. ValueError: a NaN t, list_cap outside [1, RANGE_MAX_RESULTS], more
+    than max_dense rows with more than list_cap rows in range (the distance is too loose for duplicate detection)."""
+    import torch
+    dev = torch.device("cuda", index.device)
+    n = len(index)
+    lab = torch.empty(n, dtype=torch.int64, device=dev)
+    tot = torch.empty(n, dtype=torch.int64, device=dev)
+    stats = (ctypes.c_int64 * 4)(0, 0, 0, 0)
+    p = lambda x: ctypes.c_void_p(x.data_ptr()) if n else None   # noqa: E731
+    with torch.cuda.device(dev):
+        L.check(index._lib.rdx_index_near_dup(index._h, ctypes.c_float(float(t)), mask._h if mask is not None else None, int(list_cap),
+                                              int(max_dense), p(lab), p(tot), stats, ctypes.c_void_p(HipIndex._raw_stream(dev))))
+    return lab, tot, [int(x) for x in stats]
+
+
 def l2_normalize(x: np.ndarray, device: int = 0) -> np.ndarray:
     lib = L.load(require_gpu=True)
     a = np.ascontiguousarray(x, dtype=np.float32)
