@@ -1,7 +1,7 @@
 // rdx_index.hip — the dense index of librdx: the rdx_index lifecycle, options and ingest, rdx_l2_normalize, the search, masks,
 // merge and signal, the grouped fill, the MMR selection, the threshold search and the near-duplicate clustering of include/rdx.h. The only unit that holds a k_scan kernel (rag_dpo_amd/build.py checks that).
-// The scans and the tail of a search are launched from parameter structs filled by name: enqueue_scan fills ScanParams and its split-K kin,
-// refine_params fills k_refine's RefineParams, run_exact fills the exact path's ExactParams and SelectParams.
+// The scans and the tail of a search are launched from parameter structs filled by name, each in one place whoever searches: main_scan_params fills
+// ScanParams, refine_lists / refine_params k_refine's RefineParams, exact_params / select_params the exact path's, which for_exact_groups drives.
 #include "rdx_host.hpp"
 
 #include <cmath>
@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "index_state.hpp"
@@ -109,6 +110,19 @@ struct I8Copy {
 
 constexpr int64_t RANGE_CHUNK = 4096;   // queries per pipeline pass of rdx_index_range, as a search chunks them (search_impl)
 
+// rdx_index_near_dup's scratch (grow-only): the parent array, and per batch the query rows, the gathered queries, their thresholds, the
+// threshold search's answers, the heavy list and the counter block (dup_kernel.hpp)
+struct DupScratch {
+    DevBuf parent, ids, q, thr, score, row, count, total, heavy, ctr;
+    int ensure(int64_t batch, int64_t rows, int list_cap, int dim) {
+        const size_t B = (size_t)batch;
+        DevBuf* const buf[10] = {&parent, &ids, &q, &thr, &score, &row, &count, &total, &heavy, &ctr};
+        const size_t need[10] = {(size_t)rows * 4, B * 8, B * dim * 4, B * 4, B * list_cap * 4, B * list_cap * 8, B * 4, B * 8, B * 4, sizeof(DupCounters)};
+        for (int i = 0; i < 10; ++i) RDX_TRY(buf[i]->ensure(need[i]));
+        return RDX_OK;
+    }
+};
+
 struct rdx_index {
     int device = 0;
     int dim = 0, dim_pad = 0, ksteps = 0, scale_log2 = 0;
@@ -134,9 +148,7 @@ struct rdx_index {
     DevBuf qshadow8, tq8, eq8, nq8, thr8, taus8, twoe8;
     DevBuf gjobs;            // rdx_index_group_fill: the call's jobs (query | begin | end)
     DevBuf rng_ctr;          // rdx_index_range: its own counter block (range_kernel.hpp RangeCounters)
-    // rdx_index_near_dup: the parent array, and per batch the query rows, the gathered queries, their thresholds, the threshold
-    // search's answers, the heavy list and the counter block (dup_kernel.hpp)
-    DevBuf dup_parent, dup_ids, dup_q, dup_thr, dup_score, dup_row, dup_count, dup_total, dup_heavy, dup_ctr;
+    DupScratch dup;          // rdx_index_near_dup
     int dup_batch = 0;       // option "dup_batch": rows per batch of rdx_index_near_dup, 0 = the range chunk (tests lower it)
     DevBuf spill;            // k_refine<true>: [nq_pad][spill_cap] hit lists of the queries that outgrow the LDS list (first spilling plan)
     // end-of-search mailbox in pinned host memory (k_finish writes it over PCIe; the host spins on its sequence number)
@@ -246,70 +258,85 @@ static int launch_scan_bn(rdx_index* h, int bn, bool res, bool fused, const Scan
     return launch_scan<256, EPI, false>(h, p, grid, st);
 }
 
-// the int8 main pass (plan_search p.i8: 256-query tiles, several of them, so never the one-tile nt variants). Its k-steps are 128
-// dimensions wide, half as many as the plan counted: the fused variant needs THEIR number even (dim_pad a multiple of 256).
-static int launch_scan_i8(rdx_index* h, bool fused, const ScanParams& p, int grid, hipStream_t st) {
-#ifndef RDX_CHECK_BOUNDS
-    if (fused && (p.ksteps & 1) == 0) return launch_scan<256, EPI_EMIT, false, false, true, true>(h, p, grid, st);
-#endif
-    return launch_scan<256, EPI_EMIT, false, false, false, true>(h, p, grid, st);
+// f(std::integral_constant<int, U>) for the kernels that hold a row's float4 groups in registers, U per lane: 1..4 up to dim 1024,
+// U = 0 (their form for any dim) beyond
+template <class F>
+static void dispatch_u(int dim, F f) {
+    const int u = dim <= 1024 ? (dim / 4 + 63) / 64 : 0;
+    if (u == 1) f(std::integral_constant<int, 1>{});
+    else if (u == 2) f(std::integral_constant<int, 2>{});
+    else if (u == 3) f(std::integral_constant<int, 3>{});
+    else if (u == 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 0>{});
 }
 
-// K5a for dim <= 1024 with U = float4 groups per lane: queries in registers, two rows in flight per wave, 2 blocks per CU (all
-// resident at once)
-template <int U>
-static void launch_exact_reg(const rdx_index* h, const ExactParams& ep, hipStream_t st) {
-    const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>((h->rows + 3) / 4, (int64_t)h->n_cu * 2)));
-    hipLaunchKernelGGL(k_exact_scores_reg<U>, g, dim3(256), 0, st, ep);
-}
-
-// K5a for one group of ep.nq <= QX queries: the register kernel up to dim 1024, the LDS kernel beyond
+// K5a for one group of ep.nq <= QX queries. Up to dim 1024 the register kernel with U = float4 groups per lane: queries in registers,
+// two rows in flight per wave, 2 blocks per CU (all resident at once); the LDS kernel beyond
 static int launch_exact_scores(const rdx_index* h, const ExactParams& ep, int grid_rows, hipStream_t st) {
-    if (h->rows > 0 && h->dim <= 1024) {
-        const int u = (h->dim / 4 + 63) / 64;
-        if (u == 1) launch_exact_reg<1>(h, ep, st);
-        else if (u == 2) launch_exact_reg<2>(h, ep, st);
-        else if (u == 3) launch_exact_reg<3>(h, ep, st);
-        else launch_exact_reg<4>(h, ep, st);
-        HIP_TRY(hipGetLastError());
-    } else if (h->rows > 0) {
-        hipLaunchKernelGGL(k_exact_scores, dim3(std::max(grid_rows, 1)), dim3(256), (size_t)ep.nq * h->dim * 4, st, ep);
+    if (h->rows <= 0) return RDX_OK;
+    const dim3 g_reg((unsigned)std::max<int64_t>(1, std::min<int64_t>((h->rows + 3) / 4, (int64_t)h->n_cu * 2)));
+    dispatch_u(h->dim, [&](auto u) {
+        if constexpr (decltype(u)::value > 0) hipLaunchKernelGGL(k_exact_scores_reg<decltype(u)::value>, g_reg, dim3(256), 0, st, ep);
+        else hipLaunchKernelGGL(k_exact_scores, dim3(std::max(grid_rows, 1)), dim3(256), (size_t)ep.nq * h->dim * 4, st, ep);
+    });
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+// K5a's parameters for this index and the queries in qhat (q_list and nq: per group of QX queries, for_exact_groups)
+static ExactParams exact_params(const rdx_index* h, const uint32_t* allow) {
+    ExactParams ep = {};
+    ep.master = h->mv();
+    ep.rows = h->rows;
+    ep.dim = h->dim;
+    ep.qhat = h->qhat.as<float>();
+    ep.allow = allow;
+    ep.out = h->dense.as<float>();
+    return ep;
+}
+
+// K5b's parameters: the best k of each dense score row into `out` (q_list: per group)
+static SelectParams select_params(const rdx_index* h, int k, const TopkOut& out) {
+    SelectParams sel = {};
+    sel.scores = h->dense.as<float>();
+    sel.rows = h->rows;
+    sel.k = k;
+    sel.ids = RowIds{h->row_base, h->store.ids()};
+    sel.out = out;
+    return sel;
+}
+
+// The exact full scan for the queries listed in d_list[0..n_list), QX at a time: K5a leaves a group's scores in `dense`, then
+// after(q_list, nq, last) launches what consumes them. t_first_inv: see run_exact.
+template <class After>
+static int for_exact_groups(rdx_index* h, const int32_t* d_list, int n_list, const uint32_t* allow, unsigned long long* t_first_inv, hipStream_t st, After after) {
+    RDX_TRY(h->dense.ensure((size_t)QX * std::max<int64_t>(h->rows, 1) * 4));
+    ExactParams ep = exact_params(h, allow);
+    ep.t_first_inv = t_first_inv;
+    const int grid_rows = (int)std::min<int64_t>((h->rows + 3) / 4, (int64_t)h->n_cu * 16);   // one row per wave up to 16 Ki rows
+    for (int j0 = 0; j0 < n_list; j0 += QX) {
+        ep.q_list = d_list + j0;
+        ep.nq = std::min(QX, n_list - j0);
+        RDX_TRY(launch_exact_scores(h, ep, grid_rows, st));
+        after(ep.q_list, ep.nq, j0 + QX >= n_list);
         HIP_TRY(hipGetLastError());
     }
     return RDX_OK;
 }
 
 // exact full scan for the queries listed in d_list[0..n_list)
-static int run_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, const uint32_t* d_allow, float* d_score,
-                     int64_t* d_row, int32_t* d_count, hipStream_t st, bool stamps = false, const FinishArgs* fin = nullptr) {
+static int run_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, const uint32_t* d_allow, const TopkOut& out, hipStream_t st,
+                     bool stamps = false, const FinishArgs* fin = nullptr) {
     const FinishArgs no_fin = {};   // (ctr == NULL: the launch does not end a search)
-    RDX_TRY(h->dense.ensure((size_t)QX * std::max<int64_t>(h->rows, 1) * 4));
     // profile = 3: the scoring kernel's first block and the select kernel's last block leave their times in the counter block
     char* const ctr = stamps ? h->ctr.as<char>() : nullptr;
-    ExactParams ep = {};   // (q_list and nq: per group of QX queries, below)
-    ep.master = h->mv();
-    ep.rows = h->rows;
-    ep.dim = h->dim;
-    ep.qhat = h->qhat.as<float>();
-    ep.allow = d_allow;
-    ep.out = h->dense.as<float>();
-    ep.t_first_inv = ctr ? reinterpret_cast<unsigned long long*>(ctr + offsetof(RefineCounters, t_first_inv)) : nullptr;
-    SelectParams sel = {};
-    sel.scores = h->dense.as<float>();
-    sel.rows = h->rows;
-    sel.k = k;
-    sel.ids = RowIds{h->row_base, h->store.ids()};
-    sel.out = TopkOut{d_score, d_row, d_count};
-    sel.t_last = ctr ? reinterpret_cast<unsigned long long*>(ctr + offsetof(RefineCounters, t_last)) : nullptr;
-    const int grid_rows = (int)std::min<int64_t>((h->rows + 3) / 4, (int64_t)h->n_cu * 16);   // one row per wave up to 16 Ki rows
-    for (int j0 = 0; j0 < n_list; j0 += QX) {
-        ep.q_list = sel.q_list = d_list + j0;
-        ep.nq = std::min(QX, n_list - j0);
-        RDX_TRY(launch_exact_scores(h, ep, grid_rows, st));
-        hipLaunchKernelGGL(k_select_dense, dim3(ep.nq), dim3(1024), 0, st, sel, (fin && j0 + QX >= n_list) ? *fin : no_fin);
-        HIP_TRY(hipGetLastError());
-    }
-    return RDX_OK;
+    const auto stamp = [&](size_t off) { return ctr ? reinterpret_cast<unsigned long long*>(ctr + off) : nullptr; };
+    return for_exact_groups(h, d_list, n_list, d_allow, stamp(offsetof(RefineCounters, t_first_inv)), st, [&](const int32_t* q_list, int nq, bool last) {
+        SelectParams sel = select_params(h, k, out);
+        sel.q_list = q_list;
+        sel.t_last = stamp(offsetof(RefineCounters, t_last));
+        hipLaunchKernelGGL(k_select_dense, dim3(nq), dim3(1024), 0, st, sel, (fin && last) ? *fin : no_fin);
+    });
 }
 
 // Host callers (HostOut): small results travel with the end-of-search kernel into pinned staging and are copied to the
@@ -362,26 +389,33 @@ static FinishArgs finish_args(const rdx_index* h, const SearchPlan& p, const Sea
     return f;
 }
 
-// what k_refine is told about a plan's search (refine_kernel.hpp RefineParams). An int8 search (p.i8) is refined against the
-// bounds and thresholds k_tau8 left: 2 E_q per query, and tau_s, which is in score units already.
-static RefineParams refine_params(const rdx_index* h, const SearchPlan& p, const SearchIO& io) {
+// What k_refine and k_range_refine (RangeParams::r) are told alike: the plan's hit segments and list, the k best into `out`, and what the
+// exact re-score reads. The fields of a top-k search's thresholds and bands stay zero: refine_params adds them.
+static RefineParams refine_lists(const rdx_index* h, const SearchPlan& p, int k, const TopkOut& out) {
     RefineParams r = {};
     r.cand = h->cand.as<uint2>();
     r.cntw = h->cntw.as<uint32_t>();
     r.n_streams = p.n_streams;
     r.capw = p.capw;
     r.list_cap = p.list_cap;
-    r.k = p.k;
+    r.k = k;
+    r.qhat = h->qhat.as<float>();
+    r.master = h->mv();
+    r.dim = h->dim;
+    r.ids = RowIds{h->row_base, h->store.ids()};
+    r.out = out;
+    return r;
+}
+
+// what k_refine is told about a plan's search (refine_kernel.hpp RefineParams). An int8 search (p.i8) is refined against the
+// bounds and thresholds k_tau8 left: 2 E_q per query, and tau_s, which is in score units already.
+static RefineParams refine_params(const rdx_index* h, const SearchPlan& p, const SearchIO& io) {
+    RefineParams r = refine_lists(h, p, p.k, TopkOut{io.score, io.row, io.count});
     r.two_e = h->two_e();
     r.pilot = p.pilot;
     r.two_e_q = p.i8 ? h->twoe8.as<float>() : nullptr;
     r.tau = p.i8 ? h->taus8.as<float>() : h->tau.as<float>();
     r.inv_scale2 = p.i8 ? 1.0f : std::ldexp(1.0f, -2 * h->scale_log2);
-    r.qhat = h->qhat.as<float>();
-    r.master = h->mv();
-    r.dim = h->dim;
-    r.ids = RowIds{h->row_base, h->store.ids()};
-    r.out = TopkOut{io.score, io.row, io.count};
     r.exact_list = h->exact_list.as<int32_t>();
     r.ctr = h->ctr.as<RefineCounters>();
     r.spill_cap = p.spill_cap;
@@ -389,41 +423,85 @@ static RefineParams refine_params(const rdx_index* h, const SearchPlan& p, const
     return r;
 }
 
-// the MFMA path of a plan: bootstrap (k_boot or k_scan<EPI_SETMAX>), k_tau, main scan (k_scan_small or k_scan<EPI_EMIT>), k_refine
-static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, hipStream_t st, const FinishArgs& fin) {
+// The ScanParams of a plan's main scan. What its callers set differently are inputs: the `oob` word of the caller's counter block
+// (RefineCounters, RangeCounters); the sets of a search's bootstrap and how many per query (a range search has none); xcd_ranges: the
+// plan's use_xlo, bulk_it and xlo (a search: without them every stream is interleaved to its end); the workgroups' time stamps or NULL
+static ScanParams main_scan_params(const rdx_index* h, const SearchPlan& p, const uint32_t* allow, int* oob, float* setmax, int n_sets,
+                                   bool xcd_ranges, unsigned long long* wgt) {
     ScanParams sp = {};
     sp.shadow = h->store.shadow.as<_Float16>();
     sp.qshadow = h->qshadow.as<_Float16>();
     sp.ksteps = h->ksteps;
     sp.rows = h->rows;
     sp.n_tiles = p.n_tiles;
+    sp.tile_stride = 1;
     sp.nqt = p.nqt;
     sp.nq_pad = p.nq_pad;
-    sp.allow = io.allow;
-    sp.setmax = h->setmax.as<float>();
-    sp.n_sets = p.n_sets;
+    sp.allow = allow;
+    sp.setmax = setmax;
+    sp.n_sets = n_sets;
     sp.tau = h->tau.as<float>();
     sp.cntw = h->cntw.as<uint32_t>();
     sp.cand = h->cand.as<uint2>();
     sp.capw = p.capw;
     sp.inv_scale2 = std::ldexp(1.0f, -2 * h->scale_log2);
+    if (xcd_ranges) {
+        sp.use_xlo = p.balance ? 1 : 0;
+        sp.bulk_it = p.bulk_it;
+        std::copy(p.xlo, p.xlo + 9, sp.xlo);
+    }
+    sp.wgt = wgt;
     sp.shadow_bytes = (int64_t)h->store.shadow.bytes;
-    sp.oob = reinterpret_cast<int*>(h->ctr.as<char>() + offsetof(RefineCounters, oob));
-    const SplitKParams sk = {sp.shadow, sp.qshadow, sp.ksteps, sp.rows, p.n_blocks32, sp.allow};   // k_boot's and k_scan_small's share
+    sp.oob = oob;
+    return sp;
+}
 
+// k_boot's and k_scan_small's share of a scan's parameters
+static SplitKParams split_k_params(const ScanParams& sp, const SearchPlan& p) { return {sp.shadow, sp.qshadow, sp.ksteps, sp.rows, p.n_blocks32, sp.allow}; }
+
+// The main scan of a plan: k_scan_small, or k_scan<EPI_EMIT> on the fp16 copies or (i8: a search whose plan chose them and prepare_i8 made
+// them) on the int8 ones: 256-query tiles, several of them, so never the one-tile nt variants. The int8 k-steps are 128 dimensions wide, half
+// as many as the plan counted: the fused variant needs THEIR number even (dim_pad a multiple of 256).
+static int launch_main_scan(rdx_index* h, const SearchPlan& p, const ScanParams& sp, bool i8, hipStream_t st) {
+    if (p.use_small) {
+        const SmallScanParams ss = {split_k_params(sp, p), sp.tau, sp.cntw, sp.cand, sp.capw, sp.inv_scale2, sp.wgt};
+        hipLaunchKernelGGL(k_scan_small, dim3((unsigned)p.grid), dim3(512), 0, st, ss);
+        HIP_TRY(hipGetLastError());
+        return RDX_OK;
+    }
+    if (!i8) return launch_scan_bn<EPI_EMIT>(h, p.bn, p.res, p.fused, sp, p.grid, st);
+    ScanParams s8 = sp;
+    s8.shadow = reinterpret_cast<const _Float16*>(h->i8.c8.p);
+    s8.qshadow = reinterpret_cast<const _Float16*>(h->qshadow8.p);
+    s8.ksteps = h->dim_pad / 128;
+    s8.tau = h->thr8.as<float>();
+    s8.sblk = h->i8.sblk.as<float>();
+    s8.qscale = h->tq8.as<float>();
+    s8.cls = h->i8.cls8.as<uint32_t>();
+    s8.ncls = p.eps_classes;
+    s8.shadow_bytes = (int64_t)h->store.cap * h->dim_pad;
+#ifndef RDX_CHECK_BOUNDS
+    if (p.fused && (s8.ksteps & 1) == 0) return launch_scan<256, EPI_EMIT, false, false, true, true>(h, s8, p.grid, st);
+#endif
+    return launch_scan<256, EPI_EMIT, false, false, false, true>(h, s8, p.grid, st);
+}
+
+// the MFMA path of a plan: bootstrap (k_boot or k_scan<EPI_SETMAX>), k_tau, main scan (k_scan_small or k_scan<EPI_EMIT>), k_refine
+static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, hipStream_t st, const FinishArgs& fin) {
+    int* const oob = reinterpret_cast<int*>(h->ctr.as<char>() + offsetof(RefineCounters, oob));
+    const ScanParams sp = main_scan_params(h, p, io.allow, oob, h->setmax.as<float>(), p.n_sets, true, p.stamps ? h->wgt.as<unsigned long long>() : nullptr);
     if (p.use_boot) {
-        const BootParams bp = {sk, (int)p.boot_units, sp.setmax, p.boot_sets};
+        const BootParams bp = {split_k_params(sp, p), (int)p.boot_units, sp.setmax, p.boot_sets};
         hipLaunchKernelGGL(k_boot, dim3((unsigned)p.boot_units), dim3(512), 0, st, bp);
         HIP_TRY(hipGetLastError());
-    } else {
-        ScanParams pb = sp;
+    } else {   // the sample: the scan's parameters without XCD ranges and stamps, over the sampled tiles
+        ScanParams pb = main_scan_params(h, p, io.allow, oob, sp.setmax, p.n_sets_b, false, nullptr);
         pb.tile_stride = p.div;
         pb.wave_off = p.boot_wave_off;
         pb.row_off = p.boot_row_off;
         pb.span = p.boot_span;
         pb.n_tiles = p.boot_tiles;
         pb.nqt = p.nqt_b;
-        pb.n_sets = p.n_sets_b;
         RDX_TRY(launch_scan_bn<EPI_SETMAX>(h, p.bn_b, p.bn_b == p.bn ? p.res : false, false, pb, p.grid, st));
     }
     mark(h, p, st, 2);
@@ -438,30 +516,7 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
         HIP_TRY(hipGetLastError());
     }
     mark(h, p, st, 3);
-    sp.tile_stride = 1;
-    sp.use_xlo = p.balance ? 1 : 0;
-    sp.bulk_it = p.bulk_it;
-    std::copy(p.xlo, p.xlo + 9, sp.xlo);
-    sp.wgt = p.stamps ? h->wgt.as<unsigned long long>() : nullptr;
-    if (p.use_small) {
-        const SmallScanParams ss = {sk, sp.tau, sp.cntw, sp.cand, sp.capw, sp.inv_scale2, sp.wgt};
-        hipLaunchKernelGGL(k_scan_small, dim3((unsigned)p.grid), dim3(512), 0, st, ss);
-        HIP_TRY(hipGetLastError());
-    } else if (p.i8) {
-        ScanParams s8 = sp;
-        s8.shadow = reinterpret_cast<const _Float16*>(h->i8.c8.p);
-        s8.qshadow = reinterpret_cast<const _Float16*>(h->qshadow8.p);
-        s8.ksteps = h->dim_pad / 128;
-        s8.tau = h->thr8.as<float>();
-        s8.sblk = h->i8.sblk.as<float>();
-        s8.qscale = h->tq8.as<float>();
-        s8.cls = h->i8.cls8.as<uint32_t>();
-        s8.ncls = p.eps_classes;
-        s8.shadow_bytes = (int64_t)h->store.cap * h->dim_pad;
-        RDX_TRY(launch_scan_i8(h, p.fused, s8, p.grid, st));
-    } else {
-        RDX_TRY(launch_scan_bn<EPI_EMIT>(h, p.bn, p.res, p.fused, sp, p.grid, st));
-    }
+    RDX_TRY(launch_main_scan(h, p, sp, p.i8, st));
     mark(h, p, st, 4);
     // ONE launch, the search's last kernel on this path: a query with more hits than the LDS list holds goes on in its own block,
     // on its row of the spill buffer (plans that spill run the instantiation that holds both routes)
@@ -507,6 +562,17 @@ static int prepare_i8(rdx_index* h, const SearchPlan& p, hipStream_t st) {
     return RDX_OK;
 }
 
+// K1 on nq caller queries: h->qhat (fp32, what every exact score is taken against) and, with qshadow, their tiled fp16 copy for the scan, padded to
+// nq_pad queries (0: none). QUERY: the call site's instantiation; the query form is told the scan copy's geometry whether or not it writes one.
+template <bool QUERY>
+static int normalize_queries(rdx_index* h, const float* queries, int64_t nq, int64_t nq_pad, _Float16* qshadow, int* d_bad, int verbatim, hipStream_t st) {
+    hipLaunchKernelGGL(k_normalize<QUERY>, dim3((int)((std::max(nq, nq_pad) + 3) / 4)), dim3(256), 0, st, queries, (const uint16_t*)nullptr, nq,
+                       h->dim, (const int64_t*)nullptr, (int64_t)0, MasterView{h->qhat.as<float>(), nullptr, nullptr}, qshadow,
+                       QUERY ? h->ksteps : 0, QUERY ? h->scale() : 1.0f, d_bad, nq_pad, verbatim);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
 // the identity query list of an exact-only search, uploaded once (grow-only), not per search
 static int ensure_iota(rdx_index* h, int nq_pad, hipStream_t st) {
     if ((size_t)nq_pad * 4 <= h->iota.bytes) return RDX_OK;
@@ -547,10 +613,8 @@ static int enqueue_search(rdx_index* h, const SearchPlan& p, const SearchIO& io,
     int* d_bad = reinterpret_cast<int*>(h->ctr.as<char>() + offsetof(RefineCounters, bad));
     *seq = ++h->seq;
     mark(h, p, st, 0);
-    hipLaunchKernelGGL(k_normalize<true>, dim3((int)((p.nq_pad + 3) / 4)), dim3(256), 0, st, io.queries, (const uint16_t*)nullptr, p.nq, h->dim,
-                       (const int64_t*)nullptr, (int64_t)0, MasterView{h->qhat.as<float>(), nullptr, nullptr}, h->qshadow.as<_Float16>(), h->ksteps, h->scale(),
-                       d_bad, (int64_t)p.nq_pad, p.depth > 0 ? 1 : 0);   // depth 1: the rows ARE normalised queries (gathered from qhat): kept bit for bit
-    HIP_TRY(hipGetLastError());
+    // depth 1: the rows ARE normalised queries (gathered from qhat): kept bit for bit
+    RDX_TRY(normalize_queries<true>(h, io.queries, p.nq, p.nq_pad, h->qshadow.as<_Float16>(), d_bad, p.depth > 0 ? 1 : 0, st));
     if (p.i8) RDX_TRY(prepare_i8(h, p, st));
     mark(h, p, st, 1);
 
@@ -558,7 +622,7 @@ static int enqueue_search(rdx_index* h, const SearchPlan& p, const SearchIO& io,
     if (p.exact_only) {
         for (int i = 2; i <= 3; ++i) mark(h, p, st, i);   // events 3..4 bracket the dominant kernels of this path too (K5a + K5b)
         RDX_TRY(ensure_iota(h, p.nq_pad, st));
-        RDX_TRY(run_exact(h, h->iota.as<int32_t>(), (int)p.nq, p.k, io.allow, io.score, io.row, io.count, st, p.prof == 3,
+        RDX_TRY(run_exact(h, h->iota.as<int32_t>(), (int)p.nq, p.k, io.allow, TopkOut{io.score, io.row, io.count}, st, p.prof == 3,
                           p.fuse_finish ? &fin : nullptr));
         for (int i = 4; i <= 5; ++i) mark(h, p, st, i);
     } else {
@@ -704,7 +768,7 @@ static int redo_overflowed(rdx_index* h, const PendingSearch& ps, int* n_exact, 
         acc->rescored += sub.rescored;
         *n_exact = (int)sub.exact_queries;
     } else {
-        RDX_TRY(run_exact(h, h->exact_list.as<int32_t>(), *n_exact, p.k, ps.io.allow, ps.io.score, ps.io.row, ps.io.count, st));
+        RDX_TRY(run_exact(h, h->exact_list.as<int32_t>(), *n_exact, p.k, ps.io.allow, TopkOut{ps.io.score, ps.io.row, ps.io.count}, st));
     }
     if (ps.io.flags) HIP_TRY(hipMemsetAsync(ps.io.flags, 0, 16, st));   // the partial is complete now
     HIP_TRY(hipStreamSynchronize(st));   // rdx_search returns with the stream drained
@@ -1237,11 +1301,19 @@ static int begin_search(rdx_index* h, int64_t nq, int k, rdx_search_stats* s) {
     return RDX_OK;
 }
 
-static int check_mask(const rdx_index* h, const rdx_mask* mask, const char* who) {
+// a resident mask is the index's, as it stands; code: RDX_ERR_STATE, or RDX_ERR_INVALID from the threshold search and the clustering (include/rdx.h)
+static int check_mask(const rdx_index* h, const rdx_mask* mask, const char* who, int code) {
     if (mask && (mask->device != h->device || mask->rows != h->rows))
-        return fail(RDX_ERR_STATE, std::string(who) + ": the mask was made for " + std::to_string(mask->rows) + " rows on device " +
-                                       std::to_string(mask->device) + ", the index now holds " + std::to_string(h->rows) +
-                                       " (a mask does not outlive a write to the index)");
+        return fail(code, std::string(who) + ": the mask was made for " + std::to_string(mask->rows) + " rows on device " +
+                              std::to_string(mask->device) + ", the index now holds " + std::to_string(h->rows) +
+                              " (a mask does not outlive a write to the index)");
+    return RDX_OK;
+}
+
+// calls that take or return the index's own rows are not a shard's; tail: what the caller is told instead
+static int check_own_rows(const rdx_index* h, const char* who, const char* tail) {
+    if (h->store.row_map.p || h->row_base != 0)
+        return fail(RDX_ERR_STATE, std::string(who) + ": the index returns mapped row ids (a shard): " + tail);
     return RDX_OK;
 }
 
@@ -1309,7 +1381,7 @@ extern "C" int rdx_search_async(rdx_index* h, const float* queries, int64_t nq, 
     if (nq < 1 || nq > 4096 || k < 0 || k > SELECT_MAX_K) return fail(RDX_ERR_INVALID, "rdx_search_async: 1 <= nq <= 4096, 0 <= k <= " + std::to_string(SELECT_MAX_K));
     if (!queries || !out_count || (k > 0 && (!out_score || !out_row))) return fail(RDX_ERR_INVALID, "rdx_search_async: null pointer");
     std::lock_guard<std::mutex> lk(h->mu);
-    RDX_TRY(check_mask(h, mask, "rdx_search_async"));
+    RDX_TRY(check_mask(h, mask, "rdx_search_async", RDX_ERR_STATE));
     rdx_search_stats s;
     RDX_TRY(begin_search(h, nq, k, &s));
     const SearchIO io = {queries, mask ? mask->words.as<uint32_t>() : nullptr, out_score, out_row, out_count, out_flags};
@@ -1360,17 +1432,12 @@ extern "C" int rdx_search_masked(rdx_index* h, const float* queries, int64_t nq,
                                  int64_t* out_row, int32_t* out_count, int space, void* stream) {
     if (!h) return fail(RDX_ERR_INVALID, "rdx_search_masked: null index");
     std::lock_guard<std::mutex> lk(h->mu);
-    RDX_TRY(check_mask(h, mask, "rdx_search_masked"));
+    RDX_TRY(check_mask(h, mask, "rdx_search_masked", RDX_ERR_STATE));
     return search_impl(h, queries, nq, k, mask ? mask->words.as<uint32_t>() : nullptr, true, out_score, out_row, out_count, space, stream);
 }
 
 // ---- grouped search: the fill ---------------------------------------------------------------------------------
 static_assert(GROUP_FILL_SPAN == RDX_GROUP_FILL_SPAN && GROUP_FILL_MAX_M == RDX_GROUP_MAX_SIZE, "k_rows.hpp and include/rdx.h disagree");
-
-template <int U>
-static void launch_group_fill(const GroupFillParams& gp, hipStream_t st) {
-    hipLaunchKernelGGL(k_group_fill<U>, dim3((unsigned)gp.n_jobs), dim3(64 * GROUP_FILL_WAVES), 0, st, gp);   // one workgroup per job
-}
 
 extern "C" int rdx_index_group_fill(rdx_index* h, const float* queries, int64_t nq, const rdx_mask* mask, const int32_t* job_query,
                                     const int64_t* job_begin, const int64_t* job_end, int64_t n_jobs, const int64_t* group_rows,
@@ -1394,9 +1461,8 @@ extern "C" int rdx_index_group_fill(rdx_index* h, const float* queries, int64_t 
                                              std::to_string(GROUP_FILL_SPAN) + " rows");
     }
     std::lock_guard<std::mutex> lk(h->mu);
-    RDX_TRY(check_mask(h, mask, "rdx_index_group_fill"));
-    if (h->store.row_map.p || h->row_base != 0)
-        return fail(RDX_ERR_STATE, "rdx_index_group_fill: the index returns mapped row ids (a shard): group_rows must be the index's own rows");
+    RDX_TRY(check_mask(h, mask, "rdx_index_group_fill", RDX_ERR_STATE));
+    RDX_TRY(check_own_rows(h, "rdx_index_group_fill", "group_rows must be the index's own rows"));
     RDX_TRY(finish_pending(h, nullptr));
     RDX_TRY(set_device(h));
     hipStream_t st = (hipStream_t)stream;
@@ -1410,9 +1476,7 @@ extern "C" int rdx_index_group_fill(rdx_index* h, const float* queries, int64_t 
     HIP_TRY(hipMemcpyAsync(dj + jq + jb, job_end, jb, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(h->bad.p, 0, sizeof(int), st));
     // K1 on the queries, the call rdx_search makes: the same qhat bits
-    hipLaunchKernelGGL(k_normalize<false>, dim3((int)((nq + 3) / 4)), dim3(256), 0, st, queries, (const uint16_t*)nullptr, nq, h->dim,
-                       (const int64_t*)nullptr, (int64_t)0, MasterView{h->qhat.as<float>(), nullptr, nullptr}, (_Float16*)nullptr, 0, 1.0f, h->bad.as<int>());
-    HIP_TRY(hipGetLastError());
+    RDX_TRY(normalize_queries<false>(h, queries, nq, 0, nullptr, h->bad.as<int>(), 0, st));
     GroupFillParams gp = {};
     gp.master = h->mv();
     gp.rows = h->rows;
@@ -1428,12 +1492,9 @@ extern "C" int rdx_index_group_fill(rdx_index* h, const float* queries, int64_t 
     gp.out_score = out_score;
     gp.out_row = out_row;
     gp.out_count = out_count;
-    const int u = h->dim <= 1024 ? (h->dim / 4 + 63) / 64 : 0;
-    if (u == 1) launch_group_fill<1>(gp, st);
-    else if (u == 2) launch_group_fill<2>(gp, st);
-    else if (u == 3) launch_group_fill<3>(gp, st);
-    else if (u == 4) launch_group_fill<4>(gp, st);
-    else launch_group_fill<0>(gp, st);
+    dispatch_u(h->dim, [&](auto u) {   // one workgroup per job
+        hipLaunchKernelGGL(k_group_fill<decltype(u)::value>, dim3((unsigned)gp.n_jobs), dim3(64 * GROUP_FILL_WAVES), 0, st, gp);
+    });
     HIP_TRY(hipGetLastError());
     int b = 0;
     HIP_TRY(hipMemcpyAsync(&b, h->bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1444,11 +1505,6 @@ extern "C" int rdx_index_group_fill(rdx_index* h, const float* queries, int64_t 
 
 // ---- diversity-aware selection ---------------------------------------------------------------------------------
 static_assert(MMR_MAX_FETCH == RDX_MMR_MAX_FETCH && MMR_MAX_K == RDX_MMR_MAX_K, "mmr_kernel.hpp and include/rdx.h disagree");
-
-template <int U>
-static void launch_mmr(const MmrParams& mp, int64_t nq, hipStream_t st) {
-    hipLaunchKernelGGL(k_mmr<U>, dim3((unsigned)nq), dim3(64 * MMR_WAVES), 0, st, mp);   // one workgroup per query
-}
 
 extern "C" int rdx_index_mmr(rdx_index* h, const float* cand_score, const int64_t* cand_row, const int32_t* cand_count, int64_t nq,
                              int fetch_k, int k, double lambda, int32_t* out_pos, int64_t* out_row, float* out_score, double* out_value,
@@ -1465,8 +1521,7 @@ extern "C" int rdx_index_mmr(rdx_index* h, const float* cand_score, const int64_
     if (((uintptr_t)cand_score | (uintptr_t)cand_count | (uintptr_t)out_pos | (uintptr_t)out_score | (uintptr_t)out_count | (uintptr_t)out_bad) & 3)
         return fail(RDX_ERR_INVALID, "rdx_index_mmr: misaligned pointer");
     std::lock_guard<std::mutex> lk(h->mu);
-    if (h->store.row_map.p || h->row_base != 0)
-        return fail(RDX_ERR_STATE, "rdx_index_mmr: the index returns mapped row ids (a shard): cand_row must be the index's own rows");
+    RDX_TRY(check_own_rows(h, "rdx_index_mmr", "cand_row must be the index's own rows"));
     RDX_TRY(set_device(h));
     MmrParams mp = {};
     mp.master = h->mv();
@@ -1485,12 +1540,9 @@ extern "C" int rdx_index_mmr(rdx_index* h, const float* cand_score, const int64_
     mp.out_count = out_count;
     mp.out_bad = out_bad;
     hipStream_t st = (hipStream_t)stream;
-    const int u = h->dim <= 1024 ? (h->dim / 4 + 63) / 64 : 0;
-    if (u == 1) launch_mmr<1>(mp, nq, st);
-    else if (u == 2) launch_mmr<2>(mp, nq, st);
-    else if (u == 3) launch_mmr<3>(mp, nq, st);
-    else if (u == 4) launch_mmr<4>(mp, nq, st);
-    else launch_mmr<0>(mp, nq, st);
+    dispatch_u(h->dim, [&](auto u) {   // one workgroup per query
+        hipLaunchKernelGGL(k_mmr<decltype(u)::value>, dim3((unsigned)nq), dim3(64 * MMR_WAVES), 0, st, mp);
+    });
     HIP_TRY(hipGetLastError());
     return RDX_OK;
 }
@@ -1511,29 +1563,11 @@ struct RangeIO {
 
 // the exact path of a range search for the queries listed in d_list[0..n_list): K5a per group of QX queries, then k_range_select_dense
 static int run_range_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, const RangeIO& io, hipStream_t st) {
-    RDX_TRY(h->dense.ensure((size_t)QX * std::max<int64_t>(h->rows, 1) * 4));
-    ExactParams ep = {};
-    ep.master = h->mv();
-    ep.rows = h->rows;
-    ep.dim = h->dim;
-    ep.qhat = h->qhat.as<float>();
-    ep.allow = io.allow;
-    ep.out = h->dense.as<float>();
-    SelectParams sel = {};
-    sel.scores = h->dense.as<float>();
-    sel.rows = h->rows;
-    sel.k = k;
-    sel.ids = RowIds{h->row_base, h->store.ids()};
-    sel.out = TopkOut{io.score, io.row, io.count};
-    const int grid_rows = (int)std::min<int64_t>((h->rows + 3) / 4, (int64_t)h->n_cu * 16);
-    for (int j0 = 0; j0 < n_list; j0 += QX) {
-        ep.q_list = sel.q_list = d_list + j0;
-        ep.nq = std::min(QX, n_list - j0);
-        RDX_TRY(launch_exact_scores(h, ep, grid_rows, st));
-        hipLaunchKernelGGL(k_range_select_dense, dim3(ep.nq), dim3(1024), 0, st, sel, io.thr, io.total);
-        HIP_TRY(hipGetLastError());
-    }
-    return RDX_OK;
+    return for_exact_groups(h, d_list, n_list, io.allow, nullptr, st, [&](const int32_t* q_list, int nq, bool) {
+        SelectParams sel = select_params(h, k, TopkOut{io.score, io.row, io.count});
+        sel.q_list = q_list;
+        hipLaunchKernelGGL(k_range_select_dense, dim3(nq), dim3(1024), 0, st, sel, io.thr, io.total);
+    });
 }
 
 // One chunk (nq <= 4096) of a range search: plan_range, K1, k_range_tau, then the exact path for everybody, or the main scan,
@@ -1557,10 +1591,7 @@ static int range_chunk(rdx_index* h, const RangeIO& io, int64_t nq, int k, hipSt
     int* const d_bad = reinterpret_cast<int*>(h->rng_ctr.as<char>() + offsetof(RangeCounters, bad));
     HIP_TRY(hipMemsetAsync(h->rng_ctr.p, 0, sizeof(RangeCounters), st));
     // K1 on the queries, the call a search makes: the same qhat bits (and, for the scan, the same tiled fp16 copy)
-    hipLaunchKernelGGL(k_normalize<true>, dim3((int)((p.nq_pad + 3) / 4)), dim3(256), 0, st, io.queries, (const uint16_t*)nullptr, nq, h->dim,
-                       (const int64_t*)nullptr, (int64_t)0, MasterView{h->qhat.as<float>(), nullptr, nullptr},
-                       p.exact_only ? (_Float16*)nullptr : h->qshadow.as<_Float16>(), h->ksteps, h->scale(), d_bad, (int64_t)p.nq_pad, 0);
-    HIP_TRY(hipGetLastError());
+    RDX_TRY(normalize_queries<true>(h, io.queries, nq, p.nq_pad, p.exact_only ? nullptr : h->qshadow.as<_Float16>(), d_bad, 0, st));
     // (on the exact path too: it is also what refuses a NaN threshold)
     hipLaunchKernelGGL(k_range_tau, dim3((p.nq_pad + 255) / 256), dim3(256), 0, st, io.thr, (int)nq, p.nq_pad, 0.5f * h->two_e(),
                        std::ldexp(1.0f, 2 * h->scale_log2), h->tau.as<float>(), d_bad);
@@ -1569,43 +1600,11 @@ static int range_chunk(rdx_index* h, const RangeIO& io, int64_t nq, int k, hipSt
         RDX_TRY(ensure_iota(h, p.nq_pad, st));
         RDX_TRY(run_range_exact(h, h->iota.as<int32_t>(), (int)nq, k, io, st));
     } else {
-        ScanParams sp = {};
-        sp.shadow = h->store.shadow.as<_Float16>();
-        sp.qshadow = h->qshadow.as<_Float16>();
-        sp.ksteps = h->ksteps;
-        sp.rows = h->rows;
-        sp.n_tiles = p.n_tiles;
-        sp.tile_stride = 1;
-        sp.nqt = p.nqt;
-        sp.nq_pad = p.nq_pad;
-        sp.allow = io.allow;
-        sp.tau = h->tau.as<float>();
-        sp.cntw = h->cntw.as<uint32_t>();
-        sp.cand = h->cand.as<uint2>();
-        sp.capw = p.capw;
-        sp.inv_scale2 = std::ldexp(1.0f, -2 * h->scale_log2);
-        sp.shadow_bytes = (int64_t)h->store.shadow.bytes;
-        sp.oob = reinterpret_cast<int*>(h->rng_ctr.as<char>() + offsetof(RangeCounters, oob));
-        if (p.use_small) {
-            const SplitKParams sk = {sp.shadow, sp.qshadow, sp.ksteps, sp.rows, p.n_blocks32, sp.allow};
-            const SmallScanParams ss = {sk, sp.tau, sp.cntw, sp.cand, sp.capw, sp.inv_scale2, nullptr};
-            hipLaunchKernelGGL(k_scan_small, dim3((unsigned)p.grid), dim3(512), 0, st, ss);
-            HIP_TRY(hipGetLastError());
-        } else {
-            RDX_TRY(launch_scan_bn<EPI_EMIT>(h, p.bn, p.res, p.fused, sp, p.grid, st));
-        }
+        // the fp16 scan always, with neither bootstrap sets, XCD ranges nor stamps, and its bounds flag in this call's own counter block
+        int* const oob = reinterpret_cast<int*>(h->rng_ctr.as<char>() + offsetof(RangeCounters, oob));
+        RDX_TRY(launch_main_scan(h, p, main_scan_params(h, p, io.allow, oob, nullptr, 0, false, nullptr), false, st));
         RangeParams rp = {};
-        rp.r.cand = sp.cand;
-        rp.r.cntw = sp.cntw;
-        rp.r.n_streams = p.n_streams;
-        rp.r.capw = p.capw;
-        rp.r.list_cap = p.list_cap;
-        rp.r.k = k;
-        rp.r.qhat = h->qhat.as<float>();
-        rp.r.master = h->mv();
-        rp.r.dim = h->dim;
-        rp.r.ids = RowIds{h->row_base, h->store.ids()};
-        rp.r.out = TopkOut{io.score, io.row, io.count};
+        rp.r = refine_lists(h, p, k, TopkOut{io.score, io.row, io.count});
         rp.thr = io.thr;
         rp.total = io.total;
         rp.fallback_list = h->exact_list.as<int32_t>();
@@ -1645,12 +1644,8 @@ extern "C" int rdx_index_range(rdx_index* h, const float* queries, int64_t nq, c
         (((uintptr_t)thresholds | (uintptr_t)out_score | (uintptr_t)out_count) & 3))
         return fail(RDX_ERR_INVALID, "rdx_index_range: misaligned pointer");
     std::lock_guard<std::mutex> lk(h->mu);
-    if (mask && (mask->device != h->device || mask->rows != h->rows))
-        return fail(RDX_ERR_INVALID, "rdx_index_range: the mask was made for " + std::to_string(mask->rows) + " rows on device " +
-                                         std::to_string(mask->device) + ", the index now holds " + std::to_string(h->rows) +
-                                         " (a mask does not outlive a write to the index)");
-    if (h->store.row_map.p || h->row_base != 0)
-        return fail(RDX_ERR_STATE, "rdx_index_range: the index returns mapped row ids (a shard): not available");
+    RDX_TRY(check_mask(h, mask, "rdx_index_range", RDX_ERR_INVALID));
+    RDX_TRY(check_own_rows(h, "rdx_index_range", "not available"));
     RDX_TRY(finish_pending(h, nullptr));
     RDX_TRY(set_device(h));
     hipStream_t st = (hipStream_t)stream;
@@ -1670,7 +1665,101 @@ extern "C" int rdx_index_range(rdx_index* h, const float* queries, int64_t nq, c
 // ---- near-duplicate clustering ------------------------------------------------------------------------------------
 // Batches of allowed rows, ascending: gather the stored rows as queries (they never leave the device), the threshold search of the
 // batch with lists of list_cap, k_dup_link_lists; then, while the chunk's qhat is still resident, the exact scores of the batch's heavy
-// rows per group of QX and k_dup_link_dense; k_dup_labels after the last batch.
+// rows per group of QX and k_dup_link_dense; k_dup_labels after the last batch. DupRun: one call's arguments, and what its batches add up to.
+struct DupRun {
+    float threshold;
+    const uint32_t* allow;
+    int list_cap;
+    int64_t max_dense;
+    int64_t* out_total;
+    hipStream_t st;
+    unsigned row_blocks;   // blocks of 256 threads, one thread per row
+    int64_t n_heavy = 0, n_batches = 0;
+};
+
+// the allowed rows, ascending: from the bitmap (the only thing of the call the host reads beside counters)
+static int dup_allowed_rows(int64_t rows, const DupRun& run, std::vector<int64_t>* ids) {
+    if (run.allow) {
+        std::vector<uint32_t> words((size_t)((rows + 31) / 32));
+        HIP_TRY(hipMemcpyAsync(words.data(), run.allow, words.size() * 4, hipMemcpyDeviceToHost, run.st));
+        HIP_TRY(hipStreamSynchronize(run.st));
+        for (int64_t r = 0; r < rows; ++r)
+            if ((words[(size_t)(r >> 5)] >> (r & 31)) & 1u) ids->push_back(r);
+    } else {
+        ids->resize((size_t)rows);
+        for (int64_t r = 0; r < rows; ++r) (*ids)[(size_t)r] = r;
+    }
+    return RDX_OK;
+}
+
+// before the first batch: the scratch for batches of B rows, every allowed row a cluster of its own, the batch's thresholds
+static int dup_begin(rdx_index* h, const DupRun& run, int64_t B) {
+    RDX_TRY(h->dup.ensure(B, h->rows, run.list_cap, h->dim));
+    hipLaunchKernelGGL(k_dup_init, dim3(run.row_blocks), dim3(256), 0, run.st, h->dup.parent.as<int32_t>(), run.allow, h->rows, run.out_total);
+    HIP_TRY(hipGetLastError());
+    const std::vector<float> thr((size_t)B, run.threshold);
+    HIP_TRY(hipMemcpyAsync(h->dup.thr.p, thr.data(), (size_t)B * 4, hipMemcpyHostToDevice, run.st));
+    HIP_TRY(hipStreamSynchronize(run.st));
+    return RDX_OK;
+}
+
+// one batch of m allowed rows: gathered as queries, searched, linked from their lists; *heavy = its rows left to the dense pass
+static int dup_batch_lists(rdx_index* h, DupRun& run, const int64_t* ids, int64_t m, int* heavy) {
+    DupScratch& d = h->dup;
+    const hipStream_t st = run.st;
+    HIP_TRY(hipMemcpyAsync(d.ids.p, ids, (size_t)m * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, h->mv(), d.ids.as<int64_t>(), m, h->dim, d.q.as<float>());
+    HIP_TRY(hipGetLastError());
+    const RangeIO io = {d.q.as<float>(), d.thr.as<float>(), run.allow, d.score.as<float>(), d.row.as<int64_t>(), d.count.as<int32_t>(),
+                        d.total.as<int64_t>()};
+    int32_t paths[2] = {0, 0};
+    RDX_TRY(range_chunk(h, io, m, run.list_cap, st, paths));
+    HIP_TRY(hipMemsetAsync(d.ctr.p, 0, sizeof(DupCounters), st));
+    DupListParams lp = {};
+    lp.parent = d.parent.as<int32_t>();
+    lp.rows = h->rows;
+    lp.qrow = d.ids.as<int64_t>();
+    lp.nq = (int)m;
+    lp.list_cap = run.list_cap;
+    lp.row = io.row;
+    lp.count = io.count;
+    lp.total = io.total;
+    lp.out_total = run.out_total;
+    lp.heavy = d.heavy.as<int32_t>();
+    lp.ctr = d.ctr.as<DupCounters>();
+    hipLaunchKernelGGL(k_dup_link_lists, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, lp);
+    HIP_TRY(hipGetLastError());
+    DupCounters c = {};
+    HIP_TRY(hipMemcpyAsync(&c, d.ctr.p, sizeof(c), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (c.n_heavy < 0 || c.n_heavy > m) return fail(RDX_ERR_STATE, "internal: more heavy rows than rows in the batch");
+    run.n_heavy += c.n_heavy;
+    ++run.n_batches;
+    if (run.n_heavy > run.max_dense)
+        return fail(RDX_ERR_INVALID, "rdx_index_near_dup: " + std::to_string(run.n_heavy) + " rows so far have more than list_cap = " +
+                                         std::to_string(run.list_cap) + " rows within the distance (max_dense = " +
+                                         std::to_string(run.max_dense) + "): the distance is too loose for duplicate detection");
+    *heavy = c.n_heavy;
+    return RDX_OK;
+}
+
+// the dense pass of a batch's `heavy` heavy rows (the chunk's qhat — K1 of the gathered rows — is still what range_chunk left)
+static int dup_dense_pass(rdx_index* h, const DupRun& run, int heavy) {
+    const unsigned link_blocks = (unsigned)std::min<int64_t>(run.row_blocks, (int64_t)h->n_cu * 4);
+    return for_exact_groups(h, h->dup.heavy.as<int32_t>(), heavy, run.allow, nullptr, run.st, [&](const int32_t* q_list, int nq, bool) {
+        const DupDenseParams dp = {h->dup.parent.as<int32_t>(), h->rows, h->dense.as<float>(), q_list, h->dup.ids.as<int64_t>(), nq, run.threshold};
+        hipLaunchKernelGGL(k_dup_link_dense, dim3(link_blocks), dim3(256), 0, run.st, dp);
+    });
+}
+
+// after the last batch: every row's label, the smallest row of its cluster
+static int dup_labels(rdx_index* h, const DupRun& run, int64_t* out_label) {
+    hipLaunchKernelGGL(k_dup_labels, dim3(run.row_blocks), dim3(256), 0, run.st, h->dup.parent.as<int32_t>(), h->rows, out_label);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(run.st));
+    return RDX_OK;
+}
+
 extern "C" int rdx_index_near_dup(rdx_index* h, float threshold, const rdx_mask* mask, int list_cap, int64_t max_dense, int64_t* out_label,
                                   int64_t* out_total, int64_t* out_stats, void* stream) {
     if (!h) return fail(RDX_ERR_INVALID, "rdx_index_near_dup: null index");
@@ -1680,123 +1769,31 @@ extern "C" int rdx_index_near_dup(rdx_index* h, float threshold, const rdx_mask*
     if (max_dense < 0) return fail(RDX_ERR_INVALID, "rdx_index_near_dup: max_dense must be >= 0");
     if (out_stats) out_stats[0] = out_stats[1] = out_stats[2] = out_stats[3] = 0;
     std::lock_guard<std::mutex> lk(h->mu);
-    if (mask && (mask->device != h->device || mask->rows != h->rows))
-        return fail(RDX_ERR_INVALID, "rdx_index_near_dup: the mask was made for " + std::to_string(mask->rows) + " rows on device " +
-                                         std::to_string(mask->device) + ", the index now holds " + std::to_string(h->rows) +
-                                         " (a mask does not outlive a write to the index)");
-    if (h->store.row_map.p || h->row_base != 0)
-        return fail(RDX_ERR_STATE, "rdx_index_near_dup: the index returns mapped row ids (a shard): not available");
+    RDX_TRY(check_mask(h, mask, "rdx_index_near_dup", RDX_ERR_INVALID));
+    RDX_TRY(check_own_rows(h, "rdx_index_near_dup", "not available"));
     if (h->rows >= ((int64_t)1 << 31)) return fail(RDX_ERR_INVALID, "rdx_index_near_dup: the parent array holds int32 rows: fewer than 2^31 rows");
     RDX_TRY(finish_pending(h, nullptr));
-    const int64_t rows = h->rows;
-    if (rows == 0) return RDX_OK;
+    if (h->rows == 0) return RDX_OK;
     if (!out_label || !out_total) return fail(RDX_ERR_INVALID, "rdx_index_near_dup: null pointer");
     if (((uintptr_t)out_label | (uintptr_t)out_total) & 7) return fail(RDX_ERR_INVALID, "rdx_index_near_dup: misaligned pointer");
     RDX_TRY(set_device(h));
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t* const allow = mask ? mask->words.as<uint32_t>() : nullptr;
-    // the allowed rows, ascending: from the bitmap (the only thing of the call the host reads beside counters)
+    DupRun run = {threshold, mask ? mask->words.as<uint32_t>() : nullptr, list_cap, max_dense, out_total, (hipStream_t)stream, (unsigned)((h->rows + 255) / 256)};
     std::vector<int64_t> ids;
-    if (allow) {
-        std::vector<uint32_t> words((size_t)((rows + 31) / 32));
-        HIP_TRY(hipMemcpyAsync(words.data(), allow, words.size() * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (int64_t r = 0; r < rows; ++r)
-            if ((words[(size_t)(r >> 5)] >> (r & 31)) & 1u) ids.push_back(r);
-    } else {
-        ids.resize((size_t)rows);
-        for (int64_t r = 0; r < rows; ++r) ids[(size_t)r] = r;
-    }
+    RDX_TRY(dup_allowed_rows(h->rows, run, &ids));
     const int64_t n = (int64_t)ids.size();
     const int64_t B = std::min<int64_t>(h->dup_batch > 0 ? h->dup_batch : RANGE_CHUNK, std::max<int64_t>(n, 1));
-    RDX_TRY(h->dup_parent.ensure((size_t)rows * 4));
-    RDX_TRY(h->dup_ids.ensure((size_t)B * 8));
-    RDX_TRY(h->dup_q.ensure((size_t)B * h->dim * 4));
-    RDX_TRY(h->dup_thr.ensure((size_t)B * 4));
-    RDX_TRY(h->dup_score.ensure((size_t)B * list_cap * 4));
-    RDX_TRY(h->dup_row.ensure((size_t)B * list_cap * 8));
-    RDX_TRY(h->dup_count.ensure((size_t)B * 4));
-    RDX_TRY(h->dup_total.ensure((size_t)B * 8));
-    RDX_TRY(h->dup_heavy.ensure((size_t)B * 4));
-    RDX_TRY(h->dup_ctr.ensure(sizeof(DupCounters)));
-    int32_t* const parent = h->dup_parent.as<int32_t>();
-    const unsigned row_blocks = (unsigned)((rows + 255) / 256);
-    hipLaunchKernelGGL(k_dup_init, dim3(row_blocks), dim3(256), 0, st, parent, allow, rows, out_total);
-    HIP_TRY(hipGetLastError());
-    const std::vector<float> thr((size_t)B, threshold);
-    HIP_TRY(hipMemcpyAsync(h->dup_thr.p, thr.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    int64_t n_light = 0, n_heavy = 0, n_batches = 0;
-    int32_t paths[2] = {0, 0};
+    RDX_TRY(dup_begin(h, run, B));
     for (int64_t b0 = 0; b0 < n; b0 += B) {
-        const int64_t m = std::min(B, n - b0);
-        HIP_TRY(hipMemcpyAsync(h->dup_ids.p, ids.data() + b0, (size_t)m * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, h->mv(), h->dup_ids.as<int64_t>(), m, h->dim,
-                           h->dup_q.as<float>());
-        HIP_TRY(hipGetLastError());
-        const RangeIO io = {h->dup_q.as<float>(), h->dup_thr.as<float>(), allow, h->dup_score.as<float>(), h->dup_row.as<int64_t>(),
-                            h->dup_count.as<int32_t>(), h->dup_total.as<int64_t>()};
-        RDX_TRY(range_chunk(h, io, m, list_cap, st, paths));
-        HIP_TRY(hipMemsetAsync(h->dup_ctr.p, 0, sizeof(DupCounters), st));
-        DupListParams lp = {};
-        lp.parent = parent;
-        lp.rows = rows;
-        lp.qrow = h->dup_ids.as<int64_t>();
-        lp.nq = (int)m;
-        lp.list_cap = list_cap;
-        lp.row = io.row;
-        lp.count = io.count;
-        lp.total = io.total;
-        lp.out_total = out_total;
-        lp.heavy = h->dup_heavy.as<int32_t>();
-        lp.ctr = h->dup_ctr.as<DupCounters>();
-        hipLaunchKernelGGL(k_dup_link_lists, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, lp);
-        HIP_TRY(hipGetLastError());
-        DupCounters c = {};
-        HIP_TRY(hipMemcpyAsync(&c, h->dup_ctr.p, sizeof(c), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (c.n_heavy < 0 || c.n_heavy > m) return fail(RDX_ERR_STATE, "internal: more heavy rows than rows in the batch");
-        n_heavy += c.n_heavy;
-        n_light += m - c.n_heavy;
-        ++n_batches;
-        if (n_heavy > max_dense)
-            return fail(RDX_ERR_INVALID, "rdx_index_near_dup: " + std::to_string(n_heavy) + " rows so far have more than list_cap = " +
-                                             std::to_string(list_cap) + " rows within the distance (max_dense = " + std::to_string(max_dense) +
-                                             "): the distance is too loose for duplicate detection");
-        if (c.n_heavy > 0) {   // the chunk's qhat (K1 of the gathered rows) is still what range_chunk left
-            RDX_TRY(h->dense.ensure((size_t)QX * rows * 4));
-            ExactParams ep = {};
-            ep.master = h->mv();
-            ep.rows = rows;
-            ep.dim = h->dim;
-            ep.qhat = h->qhat.as<float>();
-            ep.allow = allow;
-            ep.out = h->dense.as<float>();
-            DupDenseParams dp = {};
-            dp.parent = parent;
-            dp.rows = rows;
-            dp.scores = h->dense.as<float>();
-            dp.qrow = h->dup_ids.as<int64_t>();
-            dp.t = threshold;
-            const int grid_rows = (int)std::min<int64_t>((rows + 3) / 4, (int64_t)h->n_cu * 16);
-            const unsigned link_blocks = (unsigned)std::min<int64_t>(row_blocks, (int64_t)h->n_cu * 4);
-            for (int j0 = 0; j0 < c.n_heavy; j0 += QX) {
-                ep.q_list = dp.q_list = h->dup_heavy.as<int32_t>() + j0;
-                ep.nq = dp.nq = std::min(QX, c.n_heavy - j0);
-                RDX_TRY(launch_exact_scores(h, ep, grid_rows, st));
-                hipLaunchKernelGGL(k_dup_link_dense, dim3(link_blocks), dim3(256), 0, st, dp);
-                HIP_TRY(hipGetLastError());
-            }
-        }
+        int heavy = 0;
+        RDX_TRY(dup_batch_lists(h, run, ids.data() + b0, std::min(B, n - b0), &heavy));
+        if (heavy > 0) RDX_TRY(dup_dense_pass(h, run, heavy));
     }
-    hipLaunchKernelGGL(k_dup_labels, dim3(row_blocks), dim3(256), 0, st, parent, rows, out_label);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
+    RDX_TRY(dup_labels(h, run, out_label));
     if (out_stats) {
         out_stats[0] = n;
-        out_stats[1] = n_light;
-        out_stats[2] = n_heavy;
-        out_stats[3] = n_batches;
+        out_stats[1] = n - run.n_heavy;
+        out_stats[2] = run.n_heavy;
+        out_stats[3] = run.n_batches;
     }
     return RDX_OK;
 }
