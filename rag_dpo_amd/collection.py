@@ -59,6 +59,7 @@ from . import where_document as WD
 DEFAULT_INCLUDE_QUERY = ["metadatas", "documents", "distances"]
 DEFAULT_INCLUDE_GET = ["metadatas", "documents"]
 _VALID_INCLUDE = {"embeddings", "documents", "metadatas", "distances", "uris", "data"}
+_ROW_KEYS = ("embeddings", "documents", "metadatas", "distances")   # what query / query_mmr / query_range can put beside the ids
 
 
 class DuplicateIDError(ValueError):
@@ -129,6 +130,13 @@ def _as_matrix(embeddings, what: str):
     if a.ndim != 2 or a.shape[0] == 0 or a.shape[1] == 0:
         raise ValueError(f"Expected {what} to be a non-empty list of embeddings, got shape {a.shape}")
     return np.ascontiguousarray(a)
+
+
+def _check_int(name: str, v, lo: int, hi: Optional[int] = None, message: Optional[str] = None):
+    """a count argument: an int (not a bool, not a float) in [lo, hi], or >= lo where there is no hi; message: other words, around {}"""
+    if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < lo or (hi is not None and v > hi):
+        bounds = f">= {lo}" if hi is None else f"in [{lo}, {hi}]"
+        raise ValueError(message.format(v) if message else f"Expected {name} to be an int {bounds}, got {v!r}")
 
 
 class Collection:
@@ -306,11 +314,14 @@ class Collection:
 
     _MASK_CACHE_MAX = 32
 
+    def _evict_mask(self, key: str):
+        _, r0 = self._mask_cache.pop(key)
+        if r0 is not None and hasattr(r0, "close"):
+            r0.close()
+
     def _drop_masks(self):
-        for _, res in self._mask_cache.values():
-            if res is not None and hasattr(res, "close"):
-                res.close()
-        self._mask_cache.clear()
+        for key in list(self._mask_cache):
+            self._evict_mask(key)
 
     # ---- where on the device --------------------------------------------------------------------
     # Below this many rows the host evaluator (0.1 ms at the reference's 16 919 rows) beats a set_query + launch + make_mask:
@@ -449,56 +460,132 @@ class Collection:
     def _search_args(self, where: Optional[dict], where_document: Optional[dict] = None) -> dict:
         """-> keyword arguments for engine.search: nothing (no filter, no tombstones), mask= (resident bitmap of a filter
         seen before or just uploaded) or allow_bits= (engines without resident masks)"""
-        if not WD.is_empty(where_document):
-            return self._search_args_wd(where, where_document)
+        if not WD.is_empty(where_document):             # a key of its own: "wd:" + both filters (where-only keys are unchanged)
+            WD.validate(where_document)
+            return self._cached_args("wd:", [where, where_document], lambda: self._wd_resident(where, where_document))
         if where in (None, {}) and not self._n_dead:
             return {}
+        return self._cached_args("", where, lambda: self._where_entry(where))
+
+    def _where_entry(self, where: Optional[dict]):
+        """-> the cache entry (host words or None, resident mask or None) of `where` AND not deleted; None = everything passes"""
+        dev_bits = self._where_device(where)
+        if dev_bits is not None:                        # computed in HBM and handed to the resident mask there
+            return None, self._engine.make_mask(dev_bits)
+        m = self._mask(where)
+        if m is None:
+            return None
+        bits = W.pack_bits(m)
+        return bits, (self._engine.make_mask(bits) if hasattr(self._engine, "make_mask") else None)
+
+    def _cached_args(self, prefix: str, filters, compute) -> dict:
+        """_search_args' body: look the filters' canonical JSON up in the mask cache, else compute() the entry, bound the cache and
+        store it. Entries are dropped on every write."""
         try:
-            key = json.dumps(where, sort_keys=True, ensure_ascii=False, allow_nan=False)
+            key = prefix + json.dumps(filters, sort_keys=True, ensure_ascii=False, allow_nan=False)
         except (TypeError, ValueError):
-            key = None                                  # not canonicalisable: W.evaluate will say what is wrong with it
+            key = None                                  # not canonicalisable: the evaluation will say what is wrong with it
         ent = self._mask_cache.get(key) if key is not None else None
-        if ent is None:
-            dev_bits = self._where_device(where)
-            if dev_bits is not None:                    # computed in HBM and handed to the resident mask there
-                ent = (None, self._engine.make_mask(dev_bits))
-            else:
-                m = self._mask(where)
-                if m is None:
-                    return {}
-                bits = W.pack_bits(m)
-                ent = (bits, self._engine.make_mask(bits) if hasattr(self._engine, "make_mask") else None)
+        if ent is not None:
+            self.mask_cache_hits += 1
+        else:
+            ent = compute()
+            if ent is None:
+                return {}
             if key is not None:
                 if len(self._mask_cache) >= self._MASK_CACHE_MAX:
-                    old = next(iter(self._mask_cache))          # oldest entry (insertion order)
-                    _, r0 = self._mask_cache.pop(old)
-                    if r0 is not None and hasattr(r0, "close"):
-                        r0.close()
+                    self._evict_mask(next(iter(self._mask_cache)))      # the oldest entry (insertion order)
                 self._mask_cache[key] = ent
-        else:
-            self.mask_cache_hits += 1
         return {"mask": ent[1]} if ent[1] is not None else {"allow_bits": ent[0]}
 
-    def _search_args_wd(self, where: Optional[dict], where_document: dict) -> dict:
-        """_search_args with a where_document: cached under a key of its own ("wd:" + both filters; where-only keys are
-        unchanged), dropped on every write like the others"""
-        WD.validate(where_document)
-        try:
-            key = "wd:" + json.dumps([where, where_document], sort_keys=True, ensure_ascii=False, allow_nan=False)
-        except (TypeError, ValueError):
-            key = None
-        ent = self._mask_cache.get(key) if key is not None else None
-        if ent is None:
-            ent = self._wd_resident(where, where_document)
-            if key is not None:
-                if len(self._mask_cache) >= self._MASK_CACHE_MAX:
-                    _, r0 = self._mask_cache.pop(next(iter(self._mask_cache)))
-                    if r0 is not None and hasattr(r0, "close"):
-                        r0.close()
-                self._mask_cache[key] = ent
-        else:
-            self.mask_cache_hits += 1
-        return {"mask": ent[1]} if ent[1] is not None else {"allow_bits": ent[0]}
+    # ---- the stages every query shares (DESIGN.md §25) -------------------------------------------------------------------------------
+    def _derived_check(self, method: str, how: str, where_document):
+        """the end of the four derived families' argument checks: a cosine collection on one device"""
+        if not WD.is_empty(where_document):
+            WD.validate(where_document)
+        space = self.metadata.get("hnsw:space", "cosine")
+        if space != "cosine":
+            raise NotImplementedError(f"{method} {how}: not available in the {space!r} space")
+        if self._engine is not None and hasattr(self._engine, "devices"):
+            raise NotImplementedError(f"{method} runs on one device in this version: not on a collection spread over several")
+
+    @staticmethod
+    def _need_queries(query_embeddings, why: str = ""):
+        if query_embeddings is None:
+            raise ValueError("this collection has no embedding function: pass query_embeddings=" + why)
+
+    def _host_queries(self, query_embeddings, keep_device: bool = False):
+        """a host-list method's queries -> fp32 [nq][dim] on the host (keep_device: a device tensor stays where it is)"""
+        self._need_queries(query_embeddings)
+        q = _as_matrix(query_embeddings, "query_embeddings")
+        if _is_device_tensor(q) and not keep_device:
+            q = q.cpu().numpy()        # results are Python lists anyway; device callers use the *_device methods
+        return q
+
+    def _check_dim(self, dim: int, is_matrix: bool = True):
+        if not is_matrix or dim != self._dim:
+            raise ValueError(f"Embedding dimension {dim} does not match collection dimensionality {self._dim}")
+
+    # What a *_device method refuses, one rule each; _device_args is their usual order. query_range_device, _grouped and _near_dup
+    # call the rules one by one, because each of them reports two broken rules in an order of its own (kept as found).
+    def _refuse_empty(self, method: str):
+        if self._engine is None or self._rows == 0:
+            raise ValueError(f"{method}: the collection is empty")
+
+    def _refuse_host_engine(self, always: bool = False):
+        if always or not hasattr(self._engine, "search_device"):
+            raise NotImplementedError("this collection's engine has no device-pointer search")
+
+    @staticmethod
+    def _resident(method: str, args: dict):
+        """_search_args' answer -> the resident mask, or None, of a call that stays on the device"""
+        if "allow_bits" in args:
+            raise NotImplementedError(f"{method} needs an engine with resident masks")
+        return args.get("mask")
+
+    def _device_args(self, method: str, where, where_document):
+        """the lock is held -> the resident mask or None"""
+        self._refuse_empty(method)
+        self._refuse_host_engine()
+        return self._resident(method, self._search_args(where, where_document))
+
+    def _on_device(self, args: dict) -> bool:
+        """a host-list method's choice: the device path, or the host model over engine.search"""
+        return hasattr(self._engine, "search_device") and "allow_bits" not in args
+
+    def _distances(self, scores):
+        if getattr(self._engine, "returns_distances", False):
+            return scores                                               # "ip" / "l2": the wrapper's exact distances (spaces.py)
+        return (np.float32(1.0) - scores).astype(np.float32)            # Chroma cosine distance, fp32 like chromadb
+
+    @staticmethod
+    def _empty_result(nq: int, include, keys, **extra) -> dict:
+        """query()'s dict before any row is in it: per query an empty list under "ids" and under each of `keys` that is included"""
+        out = {"ids": [[] for _ in range(nq)]}
+        for key in keys:
+            out[key] = [[] for _ in range(nq)] if key in include else None
+        out["uris"] = out["data"] = None
+        out["included"] = include
+        out.update(extra)
+        return out
+
+    def _fill_rows(self, out: dict, rows, counts, dist):
+        """the result lists: for every b the ids of rows[b, :counts[b]] into out["ids"][b], and beside them what `out` has a list for
+        (None or no entry: not included). One call per search, not per query: at the reference's shape this loop is most of query()."""
+        ids, docs = self._ids, self._docs
+        o_ids, o_docs, o_meta, o_dist, o_emb = out["ids"], out.get("documents"), out.get("metadatas"), out.get("distances"), out.get("embeddings")
+        for b in range(len(counts)):
+            n = counts[b]
+            rr = rows[b, :n].tolist()
+            o_ids[b] = [ids[r] for r in rr]
+            if o_docs is not None:
+                o_docs[b] = [docs[r] for r in rr]
+            if o_meta is not None:
+                o_meta[b] = self._metas_of(rr)
+            if o_dist is not None:
+                o_dist[b] = [float(x) for x in dist[b, :n]]
+            if o_emb is not None:
+                o_emb[b] = self._engine.get(np.array(rr, dtype=np.int64)) if rr else np.zeros((0, self._dim), dtype=np.float32)
 
     @staticmethod
     def _check_include(include: Sequence[str], allowed: set):
@@ -615,9 +702,7 @@ class Collection:
                     self._docs[row] = documents[i]
             if documents is not None and hit:
                 for key in [k for k in self._mask_cache if k.startswith("wd:")]:   # where-only bitmaps do not read documents
-                    _, r0 = self._mask_cache.pop(key)
-                    if r0 is not None and hasattr(r0, "close"):
-                        r0.close()
+                    self._evict_mask(key)
                 self._docs_write(lambda st: st.replace([r for _, r in hit], [documents[i] for i, _ in hit]))
             if hit:
                 idx = [i for i, _ in hit]
@@ -733,55 +818,21 @@ class Collection:
         documents+metadatas+distances) and create_chromadb_index.py:405-408 (no include/where)."""
         include = DEFAULT_INCLUDE_QUERY if include is None else list(include)
         self._check_include(include, _VALID_INCLUDE)
-        if query_embeddings is None:
-            raise ValueError("this collection has no embedding function: pass query_embeddings= "
-                             "(the reference always does, retriever.py:215-220)")
+        self._need_queries(query_embeddings, " (the reference always does, retriever.py:215-220)")   # (before the two checks below, as found)
         if not WD.is_empty(where_document):
             WD.validate(where_document)
-        if not isinstance(n_results, (int, np.integer)) or isinstance(n_results, bool) or n_results <= 0:
-            raise ValueError(f"Number of requested results {n_results}, cannot be negative, or zero.")
-        q = _as_matrix(query_embeddings, "query_embeddings")
-        if _is_device_tensor(q):
-            q = q.cpu().numpy()        # results are Python lists anyway; device callers use HipIndex.search_device
+        _check_int("n_results", n_results, 1, None, "Number of requested results {}, cannot be negative, or zero.")
+        q = self._host_queries(query_embeddings)
         nq = q.shape[0]
         with self._lock:
-            if self._engine is None:   # nothing was ever added
-                empty = [[] for _ in range(nq)]
-                return {"ids": [[] for _ in range(nq)], "embeddings": None,
-                        "documents": [list(e) for e in empty] if "documents" in include else None,
-                        "metadatas": [list(e) for e in empty] if "metadatas" in include else None,
-                        "distances": [list(e) for e in empty] if "distances" in include else None,
-                        "uris": None, "data": None, "included": include}
-            if q.shape[1] != self._dim:
-                raise ValueError(f"Embedding dimension {q.shape[1]} does not match collection dimensionality {self._dim}")
+            out = self._empty_result(nq, include, _ROW_KEYS)
+            if self._engine is None:   # nothing was ever added. As found: rows that are all gone do not count as empty here, and
+                out["embeddings"] = None                                # "embeddings" is None whatever include says
+                return out
+            self._check_dim(q.shape[1])
             scores, rows, counts = self._engine.search(q, int(n_results), **self._search_args(where, where_document))
-            if getattr(self._engine, "returns_distances", False):
-                dist = scores                                       # "ip" / "l2": the wrapper's exact distances (spaces.py)
-            else:
-                dist = (np.float32(1.0) - scores).astype(np.float32)   # Chroma cosine distance, fp32 like chromadb
-            out_ids, out_docs, out_meta, out_dist, out_emb = [], [], [], [], []
-            for b in range(nq):
-                rr = rows[b, : counts[b]].tolist()
-                out_ids.append([self._ids[r] for r in rr])
-                if "documents" in include:
-                    out_docs.append([self._docs[r] for r in rr])
-                if "metadatas" in include:
-                    out_meta.append(self._metas_of(rr))
-                if "distances" in include:
-                    out_dist.append([float(x) for x in dist[b, : counts[b]]])
-                if "embeddings" in include:
-                    out_emb.append(self._engine.get(np.array(rr, dtype=np.int64)) if rr
-                                   else np.zeros((0, self._dim), dtype=np.float32))
-            return {
-                "ids": out_ids,
-                "embeddings": out_emb if "embeddings" in include else None,
-                "documents": out_docs if "documents" in include else None,
-                "metadatas": out_meta if "metadatas" in include else None,
-                "distances": out_dist if "distances" in include else None,
-                "uris": None,
-                "data": None,
-                "included": include,
-            }
+            self._fill_rows(out, rows, counts, self._distances(scores))
+            return out
 
     def query_device(self, query_embeddings, n_results: int = 10, where=None, where_document=None):
         """Batch callers that already hold their query embeddings on the GPU (the provider's `embed_device`, reference
@@ -793,20 +844,14 @@ class Collection:
         if not WD.is_empty(where_document):
             WD.validate(where_document)
         with self._lock:
-            if self._engine is None or self._rows == 0:
-                raise ValueError("query_device: the collection is empty")
-            if not hasattr(self._engine, "search_device"):
-                raise NotImplementedError("this collection's engine has no device-pointer search")
+            mask = self._device_args("query_device", where, where_document)
             q = query_embeddings.contiguous()
             nq, k = int(q.shape[0]), int(n_results)
-            args = self._search_args(where, where_document)
-            if "allow_bits" in args:
-                raise NotImplementedError("query_device needs an engine with resident masks")
             dev = q.device
             s = torch.empty((nq, k), dtype=torch.float32, device=dev)
             r = torch.empty((nq, k), dtype=torch.int64, device=dev)
             c = torch.empty((nq,), dtype=torch.int32, device=dev)
-            self._engine.search_device(q, k, s, r, c, mask=args.get("mask"))
+            self._engine.search_device(q, k, s, r, c, mask=mask)
             if getattr(self._engine, "returns_distances", False):
                 return s, r, c
             return (1.0 - s), r, c            # Chroma cosine distance, fp32 (padding entries: distance +inf, row -1)
@@ -815,16 +860,9 @@ class Collection:
     def _groups_check(self, group_by, n_groups, group_size, where_document):
         if not isinstance(group_by, str) or not group_by:
             raise ValueError(f"Expected group_by to be a non-empty str, got {group_by!r}")
-        for name, v, hi in (("n_groups", n_groups, GR.MAX_GROUPS), ("group_size", group_size, GR.MAX_GROUP_SIZE)):
-            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 1 <= v <= hi:
-                raise ValueError(f"Expected {name} to be an int in [1, {hi}], got {v!r}")
-        if not WD.is_empty(where_document):
-            WD.validate(where_document)
-        space = self.metadata.get("hnsw:space", "cosine")
-        if space != "cosine":
-            raise NotImplementedError(f"query_groups ranks by the cosine score: not available in the {space!r} space")
-        if self._engine is not None and hasattr(self._engine, "devices"):
-            raise NotImplementedError("query_groups runs on one device in this version: not on a collection spread over several")
+        _check_int("n_groups", n_groups, 1, GR.MAX_GROUPS)
+        _check_int("group_size", group_size, 1, GR.MAX_GROUP_SIZE)
+        self._derived_check("query_groups", "ranks by the cosine score", where_document)
 
     @property
     def group_stats(self) -> Dict[str, int]:
@@ -845,20 +883,19 @@ class Collection:
         """-> (scores, rows, counts, codes, n_found): torch tensors on the device (device_out) or numpy arrays; the lock is held"""
         stats = self._group_stats
         tables = GR.group_tables(self, group_by)
-        args = self._search_args(where, where_document)
+        args = self._search_args(where, where_document)     # as found: the filters are judged before the engine, unlike in _device_args
         G, m = int(n_groups), int(group_size)
         if not hasattr(self._engine, "search_device"):
             if device_out:
-                raise NotImplementedError("this collection's engine has no device-pointer search")
+                self._refuse_host_engine()
             stats["queries"] += q.shape[0]
             return GR.grouped_search_host(self._engine, q, tables, G, m, args)
-        if "allow_bits" in args:
-            raise NotImplementedError("query_groups needs an engine with resident masks")
+        mask = self._resident("query_groups", args)         # as found: the host form refuses this too, and both under this name
         import torch
         if not _is_device_tensor(q):
             q = torch.from_numpy(q).to(torch.device("cuda", self._engine.device))
         with torch.cuda.device(q.device):
-            out = GR.grouped_search_device(self, q.contiguous(), tables, G, m, args.get("mask"), stats)
+            out = GR.grouped_search_device(self, q.contiguous(), tables, G, m, mask, stats)
         return out if device_out else tuple(t.cpu().numpy() for t in out)
 
     def query_groups_device(self, query_embeddings, group_by: str, n_groups: int, group_size: int, where=None, where_document=None):
@@ -868,8 +905,7 @@ class Collection:
         `payload_of` the rows to ids and payloads. The same groups, rows and floats as query_groups."""
         self._groups_check(group_by, n_groups, group_size, where_document)
         with self._lock:
-            if self._engine is None or self._rows == 0:
-                raise ValueError("query_groups_device: the collection is empty")
+            self._refuse_empty("query_groups_device")
             s, r, c, codes, found = self._grouped(query_embeddings, group_by, n_groups, group_size, where, where_document, True)
             return (1.0 - s), r, c, codes, found
 
@@ -884,9 +920,7 @@ class Collection:
         include = DEFAULT_INCLUDE_QUERY if include is None else list(include)
         self._check_include(include, {"documents", "metadatas", "distances"})
         self._groups_check(group_by, n_groups, group_size, where_document)
-        if query_embeddings is None:
-            raise ValueError("this collection has no embedding function: pass query_embeddings=")
-        q = _as_matrix(query_embeddings, "query_embeddings")
+        q = self._host_queries(query_embeddings, keep_device=True)      # as found: _grouped takes a device tensor as it is
         nq = q.shape[0]
         with self._lock:
             out = {"groups": [[] for _ in range(nq)], "ids": [[] for _ in range(nq)], "included": include}
@@ -894,41 +928,29 @@ class Collection:
                 out[inc] = [[] for _ in range(nq)] if inc in include else None
             if self._engine is None or self._rows == 0:
                 return out
-            if q.shape[1] != self._dim:
-                raise ValueError(f"Embedding dimension {q.shape[1]} does not match collection dimensionality {self._dim}")
+            self._check_dim(q.shape[1])
             s, r, c, codes, found = self._grouped(q, group_by, n_groups, group_size, where, where_document, False)
-            dist = (np.float32(1.0) - s).astype(np.float32)
+            dist = self._distances(s)
             vals = GR.group_tables(self, group_by).values
             for b in range(nq):
-                for g in range(int(found[b])):
-                    rr = r[b, g, : c[b, g]].tolist()
-                    out["groups"][b].append(vals[int(codes[b, g])])
-                    out["ids"][b].append([self._ids[x] for x in rr])
-                    if "distances" in include:
-                        out["distances"][b].append([float(x) for x in dist[b, g, : c[b, g]]])
-                    if "documents" in include:
-                        out["documents"][b].append([self._docs[x] for x in rr])
-                    if "metadatas" in include:
-                        out["metadatas"][b].append(self._metas_of(rr))
+                n = int(found[b])
+                out["groups"][b] = [vals[int(x)] for x in codes[b, :n]]
+                one = {key: [None] * n for key in ("ids", *include)}    # query b's groups: one level deeper than a query's rows
+                self._fill_rows(one, r[b], c[b, :n], dist[b])
+                for key, lists in one.items():
+                    out[key][b] = lists
             return out
 
     # ---- diversity-aware search (rag_dpo_amd/mmr.py states the definition) ---------------------------------------
     def _mmr_check(self, n_results, fetch_k, lambda_mult, where_document):
-        for name, v, lo, hi in (("n_results", n_results, 1, MM.MAX_K), ("fetch_k", fetch_k, 1, MM.MAX_FETCH)):
-            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not lo <= v <= hi:
-                raise ValueError(f"Expected {name} to be an int in [{lo}, {hi}], got {v!r}")
+        _check_int("n_results", n_results, 1, MM.MAX_K)
+        _check_int("fetch_k", fetch_k, 1, MM.MAX_FETCH)
         if fetch_k < n_results:
             raise ValueError(f"Expected fetch_k >= n_results, got fetch_k={fetch_k!r}, n_results={n_results!r}")
         if not isinstance(lambda_mult, (int, float, np.integer, np.floating)) or isinstance(lambda_mult, bool) \
                 or not 0.0 <= float(lambda_mult) <= 1.0:                      # (a NaN fails both comparisons)
             raise ValueError(f"Expected lambda_mult to be a number in [0, 1], got {lambda_mult!r}")
-        if not WD.is_empty(where_document):
-            WD.validate(where_document)
-        space = self.metadata.get("hnsw:space", "cosine")
-        if space != "cosine":
-            raise NotImplementedError(f"query_mmr ranks and compares by the cosine score: not available in the {space!r} space")
-        if self._engine is not None and hasattr(self._engine, "devices"):
-            raise NotImplementedError("query_mmr runs on one device in this version: not on a collection spread over several")
+        self._derived_check("query_mmr", "ranks and compares by the cosine score", where_document)
 
     def query_mmr_device(self, query_embeddings, n_results: int = 10, fetch_k: int = 50, lambda_mult: float = 0.5, where=None,
                          where_document=None):
@@ -938,17 +960,11 @@ class Collection:
         `ids_of` / `payload_of` map the rows. The same picks and floats as query_mmr."""
         self._mmr_check(n_results, fetch_k, lambda_mult, where_document)
         with self._lock:
-            if self._engine is None or self._rows == 0:
-                raise ValueError("query_mmr_device: the collection is empty")
-            if not hasattr(self._engine, "search_device"):
-                raise NotImplementedError("this collection's engine has no device-pointer search")
-            args = self._search_args(where, where_document)
-            if "allow_bits" in args:
-                raise NotImplementedError("query_mmr_device needs an engine with resident masks")
+            mask = self._device_args("query_mmr_device", where, where_document)
             import torch
-            q = query_embeddings.contiguous()
+            q = query_embeddings.contiguous()                           # as found: its shape is not compared here (query_range_device does)
             with torch.cuda.device(q.device):
-                s, r, v, c, _ = MM.mmr_search_device(self._engine, q, int(n_results), int(fetch_k), float(lambda_mult), args.get("mask"))
+                s, r, v, c, _ = MM.mmr_search_device(self._engine, q, int(n_results), int(fetch_k), float(lambda_mult), mask)
             return (1.0 - s), r, v, c
 
     def query_mmr(self, query_embeddings, n_results: int = 10, fetch_k: int = 50, lambda_mult: float = 0.5, where=None,
@@ -959,61 +975,35 @@ class Collection:
         smaller values trade relevance for diversity. -> query()'s dict in pick order, plus "mmr_scores": [nq][<= n_results], the value
         each row was picked with. rag_dpo_amd/mmr.py states the arithmetic; results are the same on every path."""
         include = DEFAULT_INCLUDE_QUERY if include is None else list(include)
-        self._check_include(include, {"documents", "metadatas", "distances", "embeddings"})
+        self._check_include(include, set(_ROW_KEYS))
         self._mmr_check(n_results, fetch_k, lambda_mult, where_document)
-        if query_embeddings is None:
-            raise ValueError("this collection has no embedding function: pass query_embeddings=")
-        q = _as_matrix(query_embeddings, "query_embeddings")
-        if _is_device_tensor(q):
-            q = q.cpu().numpy()
+        q = self._host_queries(query_embeddings)
         nq = q.shape[0]
         k, F, lam = int(n_results), int(fetch_k), float(lambda_mult)
         with self._lock:
-            out = {"ids": [[] for _ in range(nq)], "uris": None, "data": None, "included": include,
-                   "mmr_scores": [[] for _ in range(nq)]}
-            for inc in ("documents", "metadatas", "distances", "embeddings"):
-                out[inc] = [[] for _ in range(nq)] if inc in include else None
+            out = self._empty_result(nq, include, _ROW_KEYS, mmr_scores=[[] for _ in range(nq)])
             if self._engine is None or self._rows == 0:
                 return out
-            if q.shape[1] != self._dim:
-                raise ValueError(f"Embedding dimension {q.shape[1]} does not match collection dimensionality {self._dim}")
+            self._check_dim(q.shape[1])
             args = self._search_args(where, where_document)
-            if hasattr(self._engine, "search_device") and "allow_bits" not in args:
+            if self._on_device(args):
                 import torch
                 qd = torch.from_numpy(q).to(torch.device("cuda", self._engine.device))
                 with torch.cuda.device(qd.device):
                     res = MM.mmr_search_device(self._engine, qd, k, F, lam, args.get("mask"))
                 s, r, v, c, bad = (t.cpu().numpy() for t in res)
-                if bad[0]:
+                if bad[0]:                                              # as found: only this host form reads the flag
                     raise RuntimeError("query_mmr: the search returned a row the index does not hold")
             else:
                 s, r, v, c = MM.mmr_search_host(self._engine, q, k, F, lam, args)
-            dist = (np.float32(1.0) - s).astype(np.float32)
-            for b in range(nq):
-                rr = r[b, : c[b]].tolist()
-                out["ids"][b] = [self._ids[x] for x in rr]
-                out["mmr_scores"][b] = [float(x) for x in v[b, : c[b]]]
-                if "documents" in include:
-                    out["documents"][b] = [self._docs[x] for x in rr]
-                if "metadatas" in include:
-                    out["metadatas"][b] = self._metas_of(rr)
-                if "distances" in include:
-                    out["distances"][b] = [float(x) for x in dist[b, : c[b]]]
-                if "embeddings" in include:
-                    out["embeddings"][b] = self._engine.get(np.array(rr, dtype=np.int64)) if rr else np.zeros((0, self._dim), dtype=np.float32)
+            self._fill_rows(out, r, c, self._distances(s))
+            out["mmr_scores"] = [[float(x) for x in v[b, : c[b]]] for b in range(nq)]
             return out
 
     # ---- threshold search (rag_dpo_amd/range_search.py states the definition; DESIGN.md §23) ------------------------------------
     def _range_check(self, max_results, where_document):
-        if not isinstance(max_results, (int, np.integer)) or isinstance(max_results, bool) or not 1 <= max_results <= RS.MAX_RESULTS:
-            raise ValueError(f"Expected max_results to be an int in [1, {RS.MAX_RESULTS}], got {max_results!r}")
-        if not WD.is_empty(where_document):
-            WD.validate(where_document)
-        space = self.metadata.get("hnsw:space", "cosine")
-        if space != "cosine":
-            raise NotImplementedError(f"query_range cuts at a cosine distance: not available in the {space!r} space")
-        if self._engine is not None and hasattr(self._engine, "devices"):
-            raise NotImplementedError("query_range runs on one device in this version: not on a collection spread over several")
+        _check_int("max_results", max_results, 1, RS.MAX_RESULTS)
+        self._derived_check("query_range", "cuts at a cosine distance", where_document)
 
     @property
     def range_stats(self) -> Dict[str, int]:
@@ -1038,27 +1028,22 @@ class Collection:
         The same rows and floats as query_range."""
         self._range_check(max_results, where_document)
         with self._lock:
-            if self._engine is None or self._rows == 0:
-                raise ValueError("query_range_device: the collection is empty")
-            if not hasattr(self._engine, "search_device"):
-                raise NotImplementedError("this collection's engine has no device-pointer search")
+            self._refuse_empty("query_range_device")
+            self._refuse_host_engine()
             import torch
             from . import engine as E
             q = query_embeddings.contiguous()
-            if q.dim() != 2 or q.shape[1] != self._dim:
-                raise ValueError(f"Embedding dimension {tuple(q.shape)[-1]} does not match collection dimensionality {self._dim}")
+            self._check_dim(tuple(q.shape)[-1], q.dim() == 2)           # as found: the shape and the distance are judged before the filters
             if _is_device_tensor(max_distance):
                 max_distance = max_distance.cpu().numpy()
             thr = RS.as_thresholds(max_distance, int(q.shape[0]))
-            args = self._search_args(where, where_document)
-            if "allow_bits" in args:
-                raise NotImplementedError("query_range_device needs an engine with resident masks")
+            mask = self._resident("query_range_device", self._search_args(where, where_document))
             with torch.cuda.device(q.device):
                 if (thr == thr[0]).all():           # one distance for the batch: a fill on the stream instead of a pageable upload
                     thr_d = torch.full((thr.shape[0],), float(thr[0]), dtype=torch.float32, device=q.device)
                 else:
                     thr_d = torch.from_numpy(thr).to(q.device)
-                s, r, c, t, paths = E.range_search(self._engine, q, thr_d, int(max_results), args.get("mask"))
+                s, r, c, t, paths = E.range_search(self._engine, q, thr_d, int(max_results), mask)
             self._range_count(int(q.shape[0]), paths)
             return (1.0 - s), r, c, t
 
@@ -1068,27 +1053,20 @@ class Collection:
         -> query()'s dict for the rows in range, plus "totals": [rows in range per query] (it may exceed max_results). The entries are
         those of query(n_results=max_results) with distance <= max_distance; rag_dpo_amd/range_search.py states the definition."""
         include = DEFAULT_INCLUDE_QUERY if include is None else list(include)
-        self._check_include(include, {"documents", "metadatas", "distances", "embeddings"})
+        self._check_include(include, set(_ROW_KEYS))
         self._range_check(max_results, where_document)
-        if query_embeddings is None:
-            raise ValueError("this collection has no embedding function: pass query_embeddings=")
-        q = _as_matrix(query_embeddings, "query_embeddings")
-        if _is_device_tensor(q):
-            q = q.cpu().numpy()
+        q = self._host_queries(query_embeddings)
         nq, m = q.shape[0], int(max_results)
         if _is_device_tensor(max_distance):
             max_distance = max_distance.cpu().numpy()
         thr = RS.as_thresholds(max_distance, nq)
         with self._lock:
-            out = {"ids": [[] for _ in range(nq)], "uris": None, "data": None, "included": include, "totals": [0] * nq}
-            for inc in ("documents", "metadatas", "distances", "embeddings"):
-                out[inc] = [[] for _ in range(nq)] if inc in include else None
+            out = self._empty_result(nq, include, _ROW_KEYS, totals=[0] * nq)
             if self._engine is None or self._rows == 0:
                 return out
-            if q.shape[1] != self._dim:
-                raise ValueError(f"Embedding dimension {q.shape[1]} does not match collection dimensionality {self._dim}")
+            self._check_dim(q.shape[1])
             args = self._search_args(where, where_document)
-            if hasattr(self._engine, "search_device") and "allow_bits" not in args:
+            if self._on_device(args):
                 import torch
                 from . import engine as E
                 dev = torch.device("cuda", self._engine.device)
@@ -1099,34 +1077,15 @@ class Collection:
             else:
                 s, r, c, t = RS.range_search_host(self._engine, q, thr, m, args)
                 self._range_count(nq, None)
-            dist = (np.float32(1.0) - s).astype(np.float32)
-            for b in range(nq):
-                rr = r[b, : c[b]].tolist()
-                out["ids"][b] = [self._ids[x] for x in rr]
-                out["totals"][b] = int(t[b])
-                if "documents" in include:
-                    out["documents"][b] = [self._docs[x] for x in rr]
-                if "metadatas" in include:
-                    out["metadatas"][b] = self._metas_of(rr)
-                if "distances" in include:
-                    out["distances"][b] = [float(x) for x in dist[b, : c[b]]]
-                if "embeddings" in include:
-                    out["embeddings"][b] = self._engine.get(np.array(rr, dtype=np.int64)) if rr else np.zeros((0, self._dim), dtype=np.float32)
+            self._fill_rows(out, r, c, self._distances(s))
+            out["totals"] = [int(x) for x in t]
             return out
 
     # ---- near-duplicate clustering (rag_dpo_amd/dedup.py states the definition) -----------------------------------
     def _dedup_check(self, max_neighbors, max_dense_rows, where_document):
-        if not isinstance(max_neighbors, (int, np.integer)) or isinstance(max_neighbors, bool) or not 1 <= max_neighbors <= DD.MAX_NEIGHBORS:
-            raise ValueError(f"Expected max_neighbors to be an int in [1, {DD.MAX_NEIGHBORS}], got {max_neighbors!r}")
-        if not isinstance(max_dense_rows, (int, np.integer)) or isinstance(max_dense_rows, bool) or max_dense_rows < 0:
-            raise ValueError(f"Expected max_dense_rows to be an int >= 0, got {max_dense_rows!r}")
-        if not WD.is_empty(where_document):
-            WD.validate(where_document)
-        space = self.metadata.get("hnsw:space", "cosine")
-        if space != "cosine":
-            raise NotImplementedError(f"near_duplicates cuts at a cosine distance: not available in the {space!r} space")
-        if self._engine is not None and hasattr(self._engine, "devices"):
-            raise NotImplementedError("near_duplicates runs on one device in this version: not on a collection spread over several")
+        _check_int("max_neighbors", max_neighbors, 1, DD.MAX_NEIGHBORS)
+        _check_int("max_dense_rows", max_dense_rows, 0)
+        self._derived_check("near_duplicates", "cuts at a cosine distance", where_document)
 
     @property
     def dedup_stats(self) -> Dict[str, int]:
@@ -1141,14 +1100,14 @@ class Collection:
         args = self._search_args(where, where_document)
         st = self._dedup_stats
         st["calls"] += 1
-        if hasattr(self._engine, "search_device") and "allow_bits" not in args:
+        if self._on_device(args):
             from . import engine as E
             lab, tot, stats = E.near_dup(self._engine, t, args.get("mask"), int(max_neighbors), int(max_dense_rows))
             for key, v in zip(("rows", "listed", "dense", "batches"), stats):
                 st[key] += v
             return lab, tot
-        if device:
-            raise NotImplementedError("this collection's engine has no device-pointer search")
+        if device:                                       # as found: after the distance and the filters, and in these words for an engine
+            self._refuse_host_engine(always=True)        # that has the search but no resident masks as well
         allowed = self._mask(where) if WD.is_empty(where_document) else self._wd_mask(where, where_document)
         lab, tot = DD.near_dup_host(self._engine, t, args, allowed)
         n = int(self._rows if allowed is None else np.count_nonzero(allowed))
@@ -1162,8 +1121,7 @@ class Collection:
         out; totals[r] = the rows within the distance of row r, itself included. `ids_of` / `payload_of` map the rows."""
         self._dedup_check(max_neighbors, max_dense_rows, where_document)
         with self._lock:
-            if self._engine is None or self._rows == 0:
-                raise ValueError("near_duplicates_device: the collection is empty")
+            self._refuse_empty("near_duplicates_device")
             return self._near_dup(max_distance, where, where_document, max_neighbors, max_dense_rows, True)
 
     def near_duplicates(self, max_distance, where=None, where_document=None, max_neighbors: int = 1024, max_dense_rows: int = 4096):
@@ -1177,7 +1135,7 @@ class Collection:
         self._dedup_check(max_neighbors, max_dense_rows, where_document)
         with self._lock:
             if self._engine is None or self._rows == 0:
-                RS.score_threshold(max_distance)            # (a NaN distance is refused on an empty collection too)
+                RS.score_threshold(max_distance)            # as found: a NaN distance is refused on an empty collection too
                 return {"clusters": [], "neighbors": []}
             lab, tot = self._near_dup(max_distance, where, where_document, max_neighbors, max_dense_rows, False)
             if _is_device_tensor(lab):

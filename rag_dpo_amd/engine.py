@@ -17,6 +17,21 @@ def _np_ptr(a: np.ndarray):
     return ctypes.c_void_p(a.ctypes.data)
 
 
+def _ptr(t):
+    """a torch tensor's data pointer as the C-ABI takes it; None stays None (an optional argument)"""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _want_tensors(what: str, device_index, *pairs):
+    """ValueError(what) unless every (tensor, dtype) is a contiguous CUDA tensor of that dtype on the first one's device — on
+    cuda:device_index where one is given"""
+    dev = pairs[0][0].device
+    for t, dt in pairs:
+        if not t.is_cuda or t.device != dev or t.dtype != dt or not t.is_contiguous() \
+                or (device_index is not None and t.device.index != device_index):
+            raise ValueError(what)
+
+
 class _Handle:
     """one opaque librdx handle and the rdx_*_destroy that frees it: close() may be called any number of times, and __del__
     swallows errors (at interpreter exit the library may be gone before the object)"""
@@ -70,8 +85,7 @@ def _filter_device(fn, lead, device: int, words: int, out_bits, base_bits):
                               or t.numel() != words or not t.is_contiguous()):
             raise ValueError(f"expected a contiguous int32 tensor of {words} words on cuda:{device}")
     stream = HipIndex._raw_stream(out_bits.device)
-    L.check(fn(*lead, ctypes.c_void_p(base_bits.data_ptr()) if base_bits is not None else None,
-               ctypes.c_void_p(out_bits.data_ptr()), L.RDX_DEVICE, ctypes.c_void_p(stream)))
+    L.check(fn(*lead, _ptr(base_bits), _ptr(out_bits), L.RDX_DEVICE, ctypes.c_void_p(stream)))
 
 
 class HipIndex(_Handle):
@@ -116,7 +130,7 @@ class HipIndex(_Handle):
                     raise ValueError("tensor lives on another device than the index")
                 x = x.contiguous()
                 torch.cuda.current_stream(x.device).synchronize()  # ingest runs on the index's own stream
-                return ctypes.c_void_p(x.data_ptr()), x.shape[0], L.RDX_DEVICE, x
+                return _ptr(x), x.shape[0], L.RDX_DEVICE, x
             x = x.numpy() if dtype == np.float32 else x.view(torch.uint16).numpy()
         a = np.ascontiguousarray(x, dtype=dtype if dtype == np.float32 else np.uint16)
         if a.ndim != 2 or a.shape[1] != self.dim:
@@ -161,7 +175,7 @@ class HipIndex(_Handle):
                 and row_ids.dtype == torch.int64 and out.dtype == torch.float32 and row_ids.is_contiguous() and out.is_contiguous()
                 and out.numel() == n * self.dim):
             raise ValueError(f"get_device: expected int64 [n] and fp32 [n][{self.dim}] contiguous tensors on cuda:{self.device}")
-        L.check(self._lib.rdx_index_get(self._h, ctypes.c_void_p(row_ids.data_ptr()), n, ctypes.c_void_p(out.data_ptr()), L.RDX_DEVICE))
+        L.check(self._lib.rdx_index_get(self._h, _ptr(row_ids), n, _ptr(out), L.RDX_DEVICE))
 
     def get(self, row_ids) -> np.ndarray:
         ids = np.ascontiguousarray(row_ids, dtype=np.int64)
@@ -191,7 +205,7 @@ class HipIndex(_Handle):
                 raise ValueError("allow_bits lives on another device than the index")
             if allow_bits.element_size() != 4 or allow_bits.numel() != words or not allow_bits.is_contiguous():
                 raise ValueError("allow_bits must hold ceil(count/32) contiguous 32-bit words")
-            L.check(self._lib.rdx_mask_create(self._h, ctypes.c_void_p(allow_bits.data_ptr()), L.RDX_DEVICE, ctypes.byref(h)))
+            L.check(self._lib.rdx_mask_create(self._h, _ptr(allow_bits), L.RDX_DEVICE, ctypes.byref(h)))
             return ResidentMask(self._lib, h)
         allow_bits = np.ascontiguousarray(allow_bits, dtype=np.uint32)
         if allow_bits.shape[0] != words:
@@ -210,21 +224,25 @@ class HipIndex(_Handle):
         sc = np.empty((nq, k), dtype=np.float32)
         ro = np.empty((nq, k), dtype=np.int64)
         cn = np.zeros((nq,), dtype=np.int32)
-        if mask is not None:
-            if allow_bits is not None:
-                raise ValueError("pass allow_bits or mask, not both")
-            L.check(self._lib.rdx_search_masked(self._h, _np_ptr(q), nq, int(k), mask._h, _np_ptr(sc), _np_ptr(ro), _np_ptr(cn),
-                                                L.RDX_HOST, None))
-            return sc, ro, cn
-        mp = None
-        if allow_bits is not None:
+        bits = allow_bits
+        if allow_bits is not None and mask is None:     # (beside a mask it is refused unread)
             allow_bits = np.ascontiguousarray(allow_bits, dtype=np.uint32)
             if allow_bits.shape[0] != (len(self) + 31) // 32:
                 raise ValueError("allow_bits must hold ceil(count/32) words")
-            mp = _np_ptr(allow_bits)
-        L.check(self._lib.rdx_search(self._h, _np_ptr(q), nq, int(k), mp, _np_ptr(sc), _np_ptr(ro), _np_ptr(cn),
-                                     L.RDX_HOST, None))
+            bits = _np_ptr(allow_bits)
+        self._search(_np_ptr(q), nq, k, bits, mask, (_np_ptr(sc), _np_ptr(ro), _np_ptr(cn)), L.RDX_HOST, None)
         return sc, ro, cn
+
+    def _search(self, q, nq: int, k: int, bits, mask: Optional[ResidentMask], outs, where: int, stream):
+        """search's and search_device's one call into the library: rdx_search_masked with a resident mask, else rdx_search with `bits`
+        (the call's own bitmap, or None). q, bits and outs = (score, row, count) are pointers on the side `where` names (RDX_HOST /
+        RDX_DEVICE)."""
+        if mask is not None:
+            if bits is not None:
+                raise ValueError("pass allow_bits or mask, not both")
+            L.check(self._lib.rdx_search_masked(self._h, q, nq, int(k), mask._h, *outs, where, stream))
+        else:
+            L.check(self._lib.rdx_search(self._h, q, nq, int(k), bits, *outs, where, stream))
 
     @staticmethod
     def _raw_stream(device) -> int:
@@ -238,42 +256,30 @@ class HipIndex(_Handle):
     def search_device(self, queries, k: int, out_score, out_row, out_count, allow_bits=None, mask: Optional[ResidentMask] = None):
         """torch CUDA tensors in/out, enqueued on the current torch stream (no host copies).
         allow_bits: a device bitmap for this call; mask: a resident one (make_mask) — not both."""
+        nq = self._device_call_shapes(queries, k, out_score, out_row, out_count)
+        self._search(_ptr(queries), nq, k, _ptr(allow_bits), mask, (_ptr(out_score), _ptr(out_row), _ptr(out_count)), L.RDX_DEVICE,
+                     ctypes.c_void_p(self._raw_stream(queries.device)))
+
+    @staticmethod
+    def _device_call_shapes(queries, k: int, out_score, out_row, out_count) -> int:
+        """search_device's and search_device_async's conditions on their tensors -> nq"""
         import torch
         nq = queries.shape[0]
         assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
         assert out_score.shape == (nq, k) and out_score.dtype == torch.float32 and out_score.is_contiguous()
         assert out_row.shape == (nq, k) and out_row.dtype == torch.int64 and out_row.is_contiguous()
         assert out_count.shape == (nq,) and out_count.dtype == torch.int32
-        stream = self._raw_stream(queries.device)
-        if mask is not None:
-            if allow_bits is not None:
-                raise ValueError("pass allow_bits or mask, not both")
-            L.check(self._lib.rdx_search_masked(self._h, ctypes.c_void_p(queries.data_ptr()), nq, int(k), mask._h,
-                                                ctypes.c_void_p(out_score.data_ptr()), ctypes.c_void_p(out_row.data_ptr()),
-                                                ctypes.c_void_p(out_count.data_ptr()), L.RDX_DEVICE, ctypes.c_void_p(stream)))
-            return
-        mp = ctypes.c_void_p(allow_bits.data_ptr()) if allow_bits is not None else None
-        L.check(self._lib.rdx_search(self._h, ctypes.c_void_p(queries.data_ptr()), nq, int(k), mp,
-                                     ctypes.c_void_p(out_score.data_ptr()), ctypes.c_void_p(out_row.data_ptr()),
-                                     ctypes.c_void_p(out_count.data_ptr()), L.RDX_DEVICE, ctypes.c_void_p(stream)))
+        return nq
 
     def search_device_async(self, queries, k: int, out_score, out_row, out_count, out_flags=None, mask: Optional[ResidentMask] = None):
         """enqueue the search on the current torch stream and return at once; search_wait() completes it (include/rdx.h).
         `queries` may be reused by stream-ordered work enqueued afterwards; the outputs (and out_flags: int32[4] on the device,
         [0] = 1 while the results are incomplete) must stay valid until search_wait() has returned."""
         import torch
-        nq = queries.shape[0]
-        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
-        assert out_score.shape == (nq, k) and out_score.dtype == torch.float32 and out_score.is_contiguous()
-        assert out_row.shape == (nq, k) and out_row.dtype == torch.int64 and out_row.is_contiguous()
-        assert out_count.shape == (nq,) and out_count.dtype == torch.int32
+        nq = self._device_call_shapes(queries, k, out_score, out_row, out_count)
         assert out_flags is None or (out_flags.numel() >= L.PACKED_FLAGS and out_flags.dtype == torch.int32)
-        stream = self._raw_stream(queries.device)
-        L.check(self._lib.rdx_search_async(self._h, ctypes.c_void_p(queries.data_ptr()), nq, int(k), mask._h if mask is not None else None,
-                                           ctypes.c_void_p(out_score.data_ptr()), ctypes.c_void_p(out_row.data_ptr()),
-                                           ctypes.c_void_p(out_count.data_ptr()),
-                                           ctypes.c_void_p(out_flags.data_ptr()) if out_flags is not None else None,
-                                           ctypes.c_void_p(stream)))
+        L.check(self._lib.rdx_search_async(self._h, _ptr(queries), nq, int(k), mask._h if mask is not None else None, _ptr(out_score),
+                                           _ptr(out_row), _ptr(out_count), _ptr(out_flags), ctypes.c_void_p(self._raw_stream(queries.device))))
 
     def search_wait(self) -> bool:
         """-> True when fallback passes rewrote results after the asynchronous search's kernels (consumers must be re-run)"""
@@ -288,9 +294,7 @@ class HipIndex(_Handle):
         return s
 
     def last_stats(self) -> dict:
-        s = L.SearchStats()
-        L.check(self._lib.rdx_search_last_stats(self._h, ctypes.byref(s)))
-        d = s.as_dict()
+        d = self.last_stats_struct().as_dict()
         bits = ctypes.c_int32(0)
         L.check(self._lib.rdx_search_last_coarse_bits(self._h, ctypes.byref(bits)))
         d["coarse_bits"] = int(bits.value)   # 16 / 8: which MFMA pass ran the main scan; 0: the exact scan alone
@@ -416,7 +420,7 @@ def _space_ptrs(*tensors):
     for t in tensors:
         if t is not None and (not t.is_cuda or t.device != dev or not t.is_contiguous()):
             raise ValueError("the rdx_space_* calls take contiguous torch tensors on one CUDA device")
-    return dev, [ctypes.c_void_p(t.data_ptr()) if t is not None else None for t in tensors]
+    return dev, [_ptr(t) for t in tensors]
 
 
 def space_measure(kind: int, rows):
@@ -489,14 +493,11 @@ def group_select(scores, rows, counts, row_group, group_off, n_groups: int, grou
            "count": torch.empty((nq, G), dtype=torch.int32, device=dev), "code": torch.empty((nq, G), dtype=torch.int32, device=dev),
            "complete": torch.empty((nq, G), dtype=torch.int32, device=dev), "found": torch.empty(nq, dtype=torch.int32, device=dev),
            "short": torch.empty(nq, dtype=torch.int32, device=dev), "bad": torch.zeros(1, dtype=torch.int32, device=dev)}
-    ins = (scores, rows, counts, row_group, group_off)
-    want = (torch.float32, torch.int64, torch.int32, torch.int32, torch.int64)
-    for t, dt in zip(ins, want):
-        if not t.is_cuda or t.device != dev or t.dtype != dt or not t.is_contiguous():
-            raise ValueError("group_select takes contiguous torch tensors of the documented types on one CUDA device")
+    _want_tensors("group_select takes contiguous torch tensors of the documented types on one CUDA device", None, (scores, torch.float32),
+                  (rows, torch.int64), (counts, torch.int32), (row_group, torch.int32), (group_off, torch.int64))
     if scores.shape != rows.shape or counts.shape != (nq,) or group_off.numel() < 1:
         raise ValueError("group_select: scores / rows must be [nq][k], counts [nq], group_off [groups + 1]")
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    p = _ptr
     L.check(lib.rdx_group_select(dev.index or 0, p(scores), p(rows), p(counts), nq, int(k), p(row_group), row_group.numel(), p(group_off),
                                  group_off.numel() - 1, G, m, p(out["score"]), p(out["row"]), p(out["count"]), p(out["code"]),
                                  p(out["complete"]), p(out["found"]), p(out["short"]), p(out["bad"]),
@@ -515,16 +516,16 @@ def group_fill(index: "HipIndex", queries, job_query, job_begin, job_end, group_
     n_jobs, m = jq.shape[0], int(group_size)
     if jb.shape != (n_jobs,) or je.shape != (n_jobs,):
         raise ValueError("group_fill: job_query, job_begin and job_end must have one entry per job")
-    if not (queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous() and queries.dim() == 2
-            and queries.shape[1] == index.dim and queries.device.index == index.device):
-        raise ValueError(f"group_fill: queries must be a contiguous fp32 [nq][{index.dim}] tensor on cuda:{index.device}")
-    if not (group_rows.is_cuda and group_rows.dtype == torch.int64 and group_rows.is_contiguous() and group_rows.device == queries.device):
-        raise ValueError("group_fill: group_rows must be a contiguous int64 tensor on the index's device")
+    what = f"group_fill: queries must be a contiguous fp32 [nq][{index.dim}] tensor on cuda:{index.device}"
+    _want_tensors(what, index.device, (queries, torch.float32))
+    if queries.dim() != 2 or queries.shape[1] != index.dim:
+        raise ValueError(what)
+    _want_tensors("group_fill: group_rows must be a contiguous int64 tensor on the index's device", index.device, (group_rows, torch.int64))
     dev = queries.device
     sc = torch.empty((n_jobs, max(m, 1)), dtype=torch.float32, device=dev)
     ro = torch.empty((n_jobs, max(m, 1)), dtype=torch.int64, device=dev)
     cn = torch.empty(n_jobs, dtype=torch.int32, device=dev)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    p = _ptr
     L.check(index._lib.rdx_index_group_fill(index._h, p(queries), queries.shape[0], mask._h if mask is not None else None, _np_ptr(jq),
                                             _np_ptr(jb), _np_ptr(je), n_jobs, p(group_rows), group_rows.numel(), m, p(sc), p(ro), p(cn),
                                             ctypes.c_void_p(HipIndex._raw_stream(dev))))
@@ -541,17 +542,15 @@ def mmr_select(index: "HipIndex", cand_score, cand_row, cand_count, n_results: i
     nq, F = cand_row.shape
     k = int(n_results)
     dev = cand_row.device
-    want = (torch.float32, torch.int64, torch.int32)
-    for t, dt in zip((cand_score, cand_row, cand_count), want):
-        if not t.is_cuda or t.device != dev or t.dtype != dt or not t.is_contiguous() or t.device.index != index.device:
-            raise ValueError(f"mmr_select takes contiguous torch tensors of the documented types on cuda:{index.device}")
+    _want_tensors(f"mmr_select takes contiguous torch tensors of the documented types on cuda:{index.device}", index.device,
+                  (cand_score, torch.float32), (cand_row, torch.int64), (cand_count, torch.int32))
     if cand_score.shape != cand_row.shape or cand_count.shape != (nq,):
         raise ValueError("mmr_select: cand_score / cand_row must be [nq][fetch_k], cand_count [nq]")
     kk = max(k, 1)
     out = {"pos": torch.empty((nq, kk), dtype=torch.int32, device=dev), "row": torch.empty((nq, kk), dtype=torch.int64, device=dev),
            "score": torch.empty((nq, kk), dtype=torch.float32, device=dev), "value": torch.empty((nq, kk), dtype=torch.float64, device=dev),
            "count": torch.empty(nq, dtype=torch.int32, device=dev), "bad": torch.zeros(1, dtype=torch.int32, device=dev)}
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    p = _ptr
     L.check(index._lib.rdx_index_mmr(index._h, p(cand_score), p(cand_row), p(cand_count), nq, int(F), k, float(lambda_mult), p(out["pos"]),
                                      p(out["row"]), p(out["score"]), p(out["value"]), p(out["count"]), p(out["bad"]),
                                      ctypes.c_void_p(HipIndex._raw_stream(dev))))
@@ -567,9 +566,8 @@ def range_search(index: "HipIndex", queries, thresholds, max_results: int, mask:
     import torch
     m = int(max_results)
     dev = queries.device
-    for t in (queries, thresholds):
-        if not t.is_cuda or t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.device.index != index.device:
-            raise ValueError(f"range_search takes contiguous fp32 torch tensors on cuda:{index.device}")
+    _want_tensors(f"range_search takes contiguous fp32 torch tensors on cuda:{index.device}", index.device, (queries, torch.float32),
+                  (thresholds, torch.float32))
     if queries.dim() != 2 or queries.shape[1] != index.dim:
         raise ValueError(f"range_search: queries must be [nq][{index.dim}]")
     nq = int(queries.shape[0])
@@ -581,7 +579,7 @@ def range_search(index: "HipIndex", queries, thresholds, max_results: int, mask:
     cn = torch.empty(nq, dtype=torch.int32, device=dev)
     tt = torch.empty(nq, dtype=torch.int64, device=dev)
     paths = (ctypes.c_int32 * 2)(0, 0)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    p = _ptr
     L.check(index._lib.rdx_index_range(index._h, p(queries), nq, p(thresholds), m, mask._h if mask is not None else None, p(sc), p(ro),
                                        p(cn), p(tt), paths, ctypes.c_void_p(HipIndex._raw_stream(dev))))
     return sc, ro, cn, tt, [int(paths[0]), int(paths[1])]
@@ -600,7 +598,7 @@ def near_dup(index: "HipIndex", t, mask: Optional[ResidentMask] = None, list_cap
     lab = torch.empty(n, dtype=torch.int64, device=dev)
     tot = torch.empty(n, dtype=torch.int64, device=dev)
     stats = (ctypes.c_int64 * 4)(0, 0, 0, 0)
-    p = lambda x: ctypes.c_void_p(x.data_ptr()) if n else None   # noqa: E731
+    p = lambda x: _ptr(x) if n else None   # noqa: E731  (no rows: null pointers)
     with torch.cuda.device(dev):
         L.check(index._lib.rdx_index_near_dup(index._h, ctypes.c_float(float(t)), mask._h if mask is not None else None, int(list_cap),
                                               int(max_dense), p(lab), p(tot), stats, ctypes.c_void_p(HipIndex._raw_stream(dev))))
@@ -625,7 +623,7 @@ def merge_topk_device(part_score, part_row, part_count, k: int, out_score, out_r
     dev = part_score.device
     assert part_score.is_contiguous() and part_row.is_contiguous() and part_count.is_contiguous()
     stream = HipIndex._raw_stream(dev)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    p = _ptr
     L.check(lib.rdx_merge_topk(dev.index or 0, p(part_score), p(part_row), p(part_count), int(P), int(nq), int(k),
                                p(out_score), p(out_row), p(out_count), L.RDX_DEVICE, ctypes.c_void_p(stream)))
 
