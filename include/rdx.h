@@ -367,6 +367,26 @@ int rdx_mask_destroy(rdx_mask* m);
 int rdx_search_masked(rdx_index* h, const float* queries, int64_t nq, int k, const rdx_mask* mask, float* out_score,
                       int64_t* out_row, int32_t* out_count, int space, void* stream);
 
+/* One search, a filter per query: a batch of questions from different users, each with the `where` the reference builds per user
+ * (src/rag/pipeline.py:35-71) and hands to collection.query (src/rag/retriever.py:380-385), scanned in ONE pass over the corpus
+ * instead of one rdx_search_masked per distinct filter.
+ *   filters       host array of n_filters resident masks of this index, 0 <= n_filters <= 65535
+ *   query_filter  host int32 [nq]: query q is held to filters[query_filter[q]], to no filter when query_filter[q] == -1. Equal entries
+ *                 share a mask; a mask of zeros is valid (count 0).
+ * Queries and outputs lie in `space`, as for rdx_search_masked; nq, k and the options follow rdx_search. Query q's scores, rows, count
+ * and (-inf, -1) padding are, bit for bit, what rdx_search_masked returns for that query alone with its mask (NULL for -1): no query's
+ * result depends on its neighbours, on nq, on the number of masks or on the path the search takes. The library uploads the masks'
+ * device pointers and the indices into scratch of the index; more than 4096 queries are searched in chunks of 4096, each with its
+ * slice of query_filter. When every query names the same mask, or none does, the call IS rdx_search_masked with that mask (NULL).
+ * Otherwise the scan runs on the fp16 MFMA kernels or the exact path with a filter per query; the int8 coarse pass knows one bitmap
+ * only and is not taken (planned with coarse_i8 = 0 whatever the option says: rdx_search_last_coarse_bits reports 16 or 0), and the
+ * 256-query main scan runs its stand-alone emit check (no fused variant) with plain loads.
+ * RDX_ERR_INVALID, before anything is enqueued and with the outputs untouched (the message names the query and the value): an entry
+ * of query_filter outside [-1, n_filters); filters NULL with n_filters > 0, or a NULL handle in it; query_filter NULL with nq > 0;
+ * n_filters outside [0, 65535]. A mask made for another row count or device: RDX_ERR_STATE, as for rdx_search_masked. */
+int rdx_search_filtered(rdx_index* h, const float* queries, int64_t nq, int k, const rdx_mask* const* filters, int32_t n_filters,
+                        const int32_t* query_filter, float* out_score, int64_t* out_row, int32_t* out_count, int space, void* stream);
+
 /* The search in two halves, for callers that enqueue consumers of the results on the same stream (the multi-GPU path: the
  * RCCL all-gather of the partial top-k and the merge, reference has no counterpart). rdx_search_async enqueues the whole
  * search (device pointers only, nq <= 4096; mask may be NULL) and returns without waiting; rdx_search_wait blocks until that

@@ -115,6 +115,7 @@ SYMBOLS = {
     "rdx_mask_create": (_i, [_vp, _vp, _i, ctypes.POINTER(_vp)]),
     "rdx_mask_destroy": (_i, [_vp]),
     "rdx_search_masked": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "rdx_search_filtered": (_i, [_vp, _vp, _i64, _i, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _i, _vp]),
     "rdx_search_async": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rdx_search_wait": (_i, [_vp, ctypes.POINTER(_i)]),
     "rdx_merge_topk": (_i, [_i, _vp, _vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _i, _vp]),

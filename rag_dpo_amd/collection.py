@@ -460,12 +460,26 @@ class Collection:
     def _search_args(self, where: Optional[dict], where_document: Optional[dict] = None) -> dict:
         """-> keyword arguments for engine.search: nothing (no filter, no tombstones), mask= (resident bitmap of a filter
         seen before or just uploaded) or allow_bits= (engines without resident masks)"""
+        plan = self._filter_plan(where, where_document)
+        return {} if plan is None else self._cached_args(*plan)
+
+    def _filter_plan(self, where: Optional[dict], where_document: Optional[dict]):
+        """-> _cached_args' arguments for the two filters (key prefix, what the key is made of, what computes the entry), or None:
+        nothing filters and no row is dead"""
         if not WD.is_empty(where_document):             # a key of its own: "wd:" + both filters (where-only keys are unchanged)
             WD.validate(where_document)
-            return self._cached_args("wd:", [where, where_document], lambda: self._wd_resident(where, where_document))
+            return "wd:", [where, where_document], lambda: self._wd_resident(where, where_document)
         if where in (None, {}) and not self._n_dead:
-            return {}
-        return self._cached_args("", where, lambda: self._where_entry(where))
+            return None
+        return "", where, lambda: self._where_entry(where)
+
+    @staticmethod
+    def _filter_key(prefix: str, filters) -> Optional[str]:
+        """the mask cache's key: the filters' canonical JSON; None = not canonicalisable (the evaluation will say what is wrong with it)"""
+        try:
+            return prefix + json.dumps(filters, sort_keys=True, ensure_ascii=False, allow_nan=False)
+        except (TypeError, ValueError):
+            return None
 
     def _where_entry(self, where: Optional[dict]):
         """-> the cache entry (host words or None, resident mask or None) of `where` AND not deleted; None = everything passes"""
@@ -478,13 +492,11 @@ class Collection:
         bits = W.pack_bits(m)
         return bits, (self._engine.make_mask(bits) if hasattr(self._engine, "make_mask") else None)
 
-    def _cached_args(self, prefix: str, filters, compute) -> dict:
+    def _cached_args(self, prefix: str, filters, compute, pin: Optional[dict] = None) -> dict:
         """_search_args' body: look the filters' canonical JSON up in the mask cache, else compute() the entry, bound the cache and
-        store it. Entries are dropped on every write."""
-        try:
-            key = prefix + json.dumps(filters, sort_keys=True, ensure_ascii=False, allow_nan=False)
-        except (TypeError, ValueError):
-            key = None                                  # not canonicalisable: the evaluation will say what is wrong with it
+        store it. Entries are dropped on every write. pin (query_filtered: one call that uses several entries at once) = {"keys": the
+        keys this call uses, never evicted while it runs; "own": the masks made beyond the cache's bound, which the call closes}."""
+        key = self._filter_key(prefix, filters)
         ent = self._mask_cache.get(key) if key is not None else None
         if ent is not None:
             self.mask_cache_hits += 1
@@ -492,10 +504,17 @@ class Collection:
             ent = compute()
             if ent is None:
                 return {}
-            if key is not None:
-                if len(self._mask_cache) >= self._MASK_CACHE_MAX:
-                    self._evict_mask(next(iter(self._mask_cache)))      # the oldest entry (insertion order)
+            if key is not None and len(self._mask_cache) >= self._MASK_CACHE_MAX:
+                # the oldest entry (insertion order) that the running call does not use
+                victim = next((k for k in self._mask_cache if pin is None or k not in pin["keys"]), None)
+                if victim is not None:
+                    self._evict_mask(victim)
+            if key is not None and len(self._mask_cache) < self._MASK_CACHE_MAX:
                 self._mask_cache[key] = ent
+            elif pin is not None:
+                pin["own"].append(ent[1])
+        if pin is not None and key is not None:
+            pin["keys"].add(key)
         return {"mask": ent[1]} if ent[1] is not None else {"allow_bits": ent[0]}
 
     # ---- the stages every query shares -------------------------------------------------------------------------------
@@ -854,6 +873,122 @@ class Collection:
             self._engine.search_device(q, k, s, r, c, mask=mask)
             if getattr(self._engine, "returns_distances", False):
                 return s, r, c
+            return (1.0 - s), r, c            # Chroma cosine distance, fp32 (padding entries: distance +inf, row -1)
+
+    # ---- one search, a filter per query --------------------------------------------------------------------------
+    def _filters_check(self, nq: int, wheres, where_documents):
+        """-> the two sequences as lists of nq entries; the refusals of the derived families"""
+        out = []
+        for name, seq in (("wheres", wheres), ("where_documents", where_documents)):
+            if seq is None and name == "where_documents":
+                seq = [None] * nq
+            if isinstance(seq, (dict, str, bytes)) or not isinstance(seq, Sequence) or len(seq) != nq:
+                raise ValueError(f"query_filtered: {name} must be a sequence with one entry per query ({nq}; None or {{}}: no filter), got "
+                                 f"{type(seq).__name__}" + (f" of length {len(seq)}" if isinstance(seq, Sequence) else ""))
+            out.append(list(seq))
+        for wd in out[1]:
+            self._derived_check("query_filtered", "searches the cosine engine with a filter per query", wd)
+        if not out[1]:
+            self._derived_check("query_filtered", "searches the cosine engine with a filter per query", None)
+        return out
+
+    def _resolve_filters(self, wheres, where_documents, pin: dict):
+        """the lock is held -> (the distinct filters' _search_args answers, per query the index of its own or -1: nothing filters).
+        Filters with the same cache key are one filter; each is resolved once, through the mask cache (pin: _cached_args)."""
+        args, index_of, qf = [], {}, np.empty(len(wheres), dtype=np.int32)
+        for i, (w, wd) in enumerate(zip(wheres, where_documents)):
+            plan = self._filter_plan(w, wd)
+            if plan is None:
+                qf[i] = -1
+                continue
+            key = self._filter_key(plan[0], plan[1])
+            f = index_of.get(key) if key is not None else None
+            if f is None:
+                a = self._cached_args(*plan, pin=pin)
+                if not a:                                # the filter passes every row
+                    f = -1
+                else:
+                    f = len(args)
+                    args.append(a)
+                if key is not None:
+                    index_of[key] = f
+            qf[i] = f
+        return args, qf
+
+    def _search_filtered(self, method: str, q, k: int, wheres, where_documents, device_out: bool):
+        """the lock is held; q: host fp32 [nq][dim], or a CUDA tensor (device_out) -> (scores, rows, counts) on q's side. ONE
+        engine.search_filtered where the engine has it and every filter is a resident mask; otherwise one search per distinct filter
+        (host engines, engines without resident masks) — the same results."""
+        import contextlib
+        eng, nq = self._engine, int(q.shape[0])
+        pin = {"keys": set(), "own": []}
+        try:
+            args, qf = self._resolve_filters(wheres, where_documents, pin)
+            resident = all("mask" in a for a in args)
+            if device_out:
+                import torch
+                if not resident:
+                    raise NotImplementedError(f"{method} needs an engine with resident masks")
+                s = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+                r = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+                c = torch.empty((nq,), dtype=torch.int32, device=q.device)
+                if hasattr(eng, "search_filtered_device"):
+                    eng.search_filtered_device(q, k, s, r, c, [a["mask"] for a in args], qf)
+                    return s, r, c
+                for f in np.unique(qf):                  # an engine with search_device alone: per distinct filter
+                    sel = torch.from_numpy(np.flatnonzero(qf == f)).to(q.device)
+                    n = int(sel.numel())
+                    sf, rf, cf = s.new_empty((n, k)), r.new_empty((n, k)), c.new_empty((n,))
+                    eng.search_device(q.index_select(0, sel).contiguous(), k, sf, rf, cf, mask=None if f < 0 else args[f]["mask"])
+                    s[sel], r[sel], c[sel] = sf, rf, cf
+                return s, r, c
+            if resident and hasattr(eng, "search_filtered"):
+                return eng.search_filtered(q, k, [a["mask"] for a in args], qf)
+            s = np.empty((nq, k), dtype=np.float32)
+            r = np.empty((nq, k), dtype=np.int64)
+            c = np.empty((nq,), dtype=np.int32)
+            for f in np.unique(qf):
+                sel = np.flatnonzero(qf == f)
+                s[sel], r[sel], c[sel] = eng.search(q[sel], k, **({} if f < 0 else args[f]))
+            return s, r, c
+        finally:
+            for m in pin["own"]:                         # made for this call beyond the cache's bound
+                if m is not None and hasattr(m, "close"):
+                    with contextlib.suppress(Exception):
+                        m.close()
+
+    def query_filtered(self, query_embeddings, wheres, n_results: int = 10, where_documents=None, include=None):
+        """query() for a batch of questions that each bring their own filters — the reference builds a `where` per user
+        (src/rag/pipeline.py:35-71) over one shared collection (app.py:42-67) — in ONE search of the engine instead of one per
+        distinct filter. wheres and where_documents: sequences with one entry per query (None or {}: no filter). Per query the
+        result is query(..., where=wheres[q], where_document=where_documents[q])'s: the same dict, floats and order."""
+        include = DEFAULT_INCLUDE_QUERY if include is None else list(include)
+        self._check_include(include, _VALID_INCLUDE)
+        self._need_queries(query_embeddings)
+        _check_int("n_results", n_results, 1, None, "Number of requested results {}, cannot be negative, or zero.")
+        q = self._host_queries(query_embeddings)
+        nq = q.shape[0]
+        wheres, where_documents = self._filters_check(nq, wheres, where_documents)
+        with self._lock:
+            out = self._empty_result(nq, include, _ROW_KEYS)
+            if self._engine is None:                     # nothing was ever added: query()'s answer
+                out["embeddings"] = None
+                return out
+            self._check_dim(q.shape[1])
+            scores, rows, counts = self._search_filtered("query_filtered", q, int(n_results), wheres, where_documents, False)
+            self._fill_rows(out, rows, counts, self._distances(scores))
+            return out
+
+    def query_filtered_device(self, query_embeddings, wheres, n_results: int = 10, where_documents=None):
+        """query_device() with a filter per query (see query_filtered): the same tuple, per query what
+        query_device(..., where=wheres[q], where_document=where_documents[q]) returns for it."""
+        nq = int(query_embeddings.shape[0])
+        wheres, where_documents = self._filters_check(nq, wheres, where_documents)
+        with self._lock:
+            self._refuse_empty("query_filtered_device")
+            self._refuse_host_engine()
+            s, r, c = self._search_filtered("query_filtered_device", query_embeddings.contiguous(), int(n_results), wheres,
+                                            where_documents, True)
             return (1.0 - s), r, c            # Chroma cosine distance, fp32 (padding entries: distance +inf, row -1)
 
     # ---- grouped search (rag_dpo_amd/groups.py states the definition and the ladder; DESIGN.md §21) ---------------------------

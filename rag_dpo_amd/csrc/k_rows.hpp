@@ -243,8 +243,29 @@ struct ExactParams {   // of k_exact_scores and k_exact_scores_reg<U>; run_exact
     const float* qhat; const int32_t* q_list; int nq;   // the normalised queries [..][dim], and which nq <= QX of them
     const uint32_t* allow; float* out;                  // the `where` bitmap or NULL; [nq][rows]
     unsigned long long* t_first_inv;                    // profile = 3: max(~clock) over the blocks' starts (RefineCounters), or NULL
+    // a filter per query (rdx_search_filtered; the PERQ instantiations, which do not read `allow`): query q is held to
+    // bitmap ftab[qf[q]], or to none when qf[q] < 0
+    const uint32_t* const* ftab; const int32_t* qf;
 };
 
+// PERQ: the bitmaps of the group's queries (NULL: no filter; j >= nq: the group's first query, never written) ...
+__device__ __forceinline__ void exact_group_masks(const ExactParams& p, const uint32_t* (&mk)[QX]) {
+#pragma unroll
+    for (int j = 0; j < QX; ++j) {
+        const int f = p.qf[p.q_list[j < p.nq ? j : 0]];
+        mk[j] = f < 0 ? nullptr : p.ftab[f];
+    }
+}
+// ... and which of them allow row r: bit j = query j of the group
+__device__ __forceinline__ uint32_t exact_group_ok(const uint32_t* const (&mk)[QX], int64_t r) {
+    uint32_t ok = 0;
+#pragma unroll
+    for (int j = 0; j < QX; ++j) ok |= (mk[j] ? ((mk[j][r >> 5] >> (r & 31)) & 1u) : 1u) << j;
+    return ok;
+}
+
+// (PERQ = false: the shared bitmap or none, the kernel as it always was)
+template <bool PERQ = false>
 __global__ __launch_bounds__(256) void k_exact_scores(const ExactParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (p.t_first_inv && threadIdx.x == 0) atomicMax(p.t_first_inv, ~wall_clock64());   // profile = 3: earliest block start
@@ -259,11 +280,19 @@ __global__ __launch_bounds__(256) void k_exact_scores(const ExactParams p) {
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    const uint32_t* mk[QX] = {};
+    if constexpr (PERQ) exact_group_masks(p, mk);
     // A wave owns rows wave0, wave0 + nwaves, ...; the loads of a row's next four float4 groups are all issued before the
     // first of them is used (four independent 1 KiB requests in flight per wave instead of one: the kernel is latency-bound
     // at the reference's 16,919 rows). Per lane the groups are still added in increasing g: the oracle's lane order (exact_dot4).
     for (int64_t r = wave0; r < rows; r += nwaves) {
-        const bool ok = !p.allow || ((p.allow[r >> 5] >> (r & 31)) & 1u);
+        // okq: bit j = query j of the group may have the row; the row is read and summed when any of them may
+        uint32_t okq = 0;
+        bool ok;
+        if constexpr (PERQ) {
+            okq = exact_group_ok(mk, r);
+            ok = okq != 0;
+        } else ok = !p.allow || ((p.allow[r >> 5] >> (r & 31)) & 1u);
         const MasterRow row4 = master_row(p.master, r, p.dim);
         double acc[QX];
 #pragma unroll
@@ -287,7 +316,7 @@ __global__ __launch_bounds__(256) void k_exact_scores(const ExactParams p) {
         for (int j = 0; j < QX; ++j) {
             if (j < nq) {
                 const float s = (float)wave_sum(acc[j]);
-                if (lane == 0) p.out[(int64_t)j * rows + r] = ok ? s : -INFINITY;
+                if (lane == 0) p.out[(int64_t)j * rows + r] = (PERQ ? ((okq >> j) & 1u) != 0 : ok) ? s : -INFINITY;
             }
         }
     }
@@ -301,7 +330,8 @@ __global__ __launch_bounds__(256) void k_exact_scores(const ExactParams p) {
 // stage a lane keeps two of the four partial sums, after m = 16 one, so 14 cross-lane dword moves and 7 additions replace 48
 // and 24 — every addition pairs the same two values as wave_sum's butterfly (the order stated at exact_dot4), so the bits
 // are the same. The sum of query j ends on lanes with (lane >> 4) == j.
-template <int U>
+// PERQ: a filter per query (ExactParams::qf); the row is loaded and summed either way, -inf is written per query.
+template <int U, bool PERQ = false>
 __global__ __launch_bounds__(256, 2) void k_exact_scores_reg(const ExactParams p) {
     if (p.t_first_inv && threadIdx.x == 0) atomicMax(p.t_first_inv, ~wall_clock64());   // profile = 3: earliest block start
     const int dim = p.dim, n4 = dim >> 2, nq = p.nq;
@@ -328,10 +358,14 @@ __global__ __launch_bounds__(256, 2) void k_exact_scores_reg(const ExactParams p
         }
     }
     const bool hi32 = (lane & 32) != 0, hi16 = (lane & 16) != 0;
+    const uint32_t* mk[QX] = {};
+    if constexpr (PERQ) exact_group_masks(p, mk);
     for (int64_t r = wave0; r < rows; r += nwaves) {
         const int64_t rn = r + nwaves < rows ? r + nwaves : r;   // (the last iteration re-reads its own row: no branch around loads)
         grp.load(master_row(p.master, rn, dim), nxt);
-        const bool ok = !p.allow || ((p.allow[r >> 5] >> (r & 31)) & 1u);
+        bool ok;   // of the query whose sum ends on this lane, j = lane >> 4
+        if constexpr (PERQ) ok = (exact_group_ok(mk, r) >> (lane >> 4)) & 1u;
+        else ok = !p.allow || ((p.allow[r >> 5] >> (r & 31)) & 1u);
         double acc[QX];
 #pragma unroll
         for (int j = 0; j < QX; ++j) acc[j] = 0.0;

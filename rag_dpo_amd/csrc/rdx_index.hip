@@ -31,10 +31,20 @@ struct HostOut {
     bool stale;
 };
 
+// Which rows a search's queries may return (device addresses): one bitmap for all of them or none — the shared form, what a plain
+// pointer converts to — or a bitmap per query (rdx_search_filtered): query q is held to ftab[qf[q]], to none when qf[q] < 0.
+struct RowFilter {
+    const uint32_t* allow = nullptr;
+    const uint32_t* const* ftab = nullptr;
+    const int32_t* qf = nullptr;   // NULL: the shared form
+    RowFilter(const uint32_t* a = nullptr) : allow(a) {}
+    RowFilter(const uint32_t* const* t, const int32_t* q) : ftab(t), qf(q) {}
+};
+
 // the caller's buffers of one search chunk (device addresses)
 struct SearchIO {
     const float* queries;
-    const uint32_t* allow;
+    RowFilter allow;
     float* score;
     int64_t* row;
     int32_t* count;
@@ -140,6 +150,9 @@ struct rdx_index {
 
     // scratch (grow-only; never allocated inside a warmed-up search)
     DevBuf r_list, r_q, r_s, r_r, r_c;   // second-chance batch of overflowed queries
+    DevBuf r_qf;                         //   ... and their filter indices (a filter per query)
+    DevBuf fq;                           // rdx_search_filtered: the masks' device pointers | the queries' filter indices
+    std::vector<char> fq_host;           //   ... and what they are uploaded from (kept until the next call)
     DevBuf wgt;                          // [grid][2] workgroup time stamps of the main scan
     DevBuf staging, qraw, qhat, qshadow, tau, cntw, cand, setmax, exact_list, iota, dense, ctr, bad, o_score, o_row,
         o_count, mask, ids;
@@ -232,8 +245,25 @@ static int launch_scan(rdx_index* h, const ScanParams& p, int grid, hipStream_t 
     return RDX_OK;
 }
 
+// ... with a filter per query (p.qf): BN bitmap pointers behind the thresholds. These kernels have no non-temporal and no fused variants
+// (both are speed only): whatever the plan chose there, a filtered search takes the plain unfused kernel of its tile width.
+template <int BN, int EPI, bool RES>
+static int launch_scan_q(rdx_index* h, const ScanParams& p, int grid, hipStream_t st) {
+    const size_t lds = (size_t)(RES ? p.ksteps : RING_SLOTS) * BN * BK * 2 + BN * 8 + BN * sizeof(const uint32_t*);
+    void (*kern)(const ScanParams) = k_scan<BN, EPI, false, RES, false, false, false, true>;
+    RDX_TRY(dynamic_lds(h->device, (const void*)kern, lds));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, p);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
 template <int EPI>
 static int launch_scan_bn(rdx_index* h, int bn, bool res, bool fused, const ScanParams& p, int grid, hipStream_t st) {
+    if (p.qf) {
+        if (bn == 64) return res ? launch_scan_q<64, EPI, true>(h, p, grid, st) : launch_scan_q<64, EPI, false>(h, p, grid, st);
+        if (bn == 128) return launch_scan_q<128, EPI, false>(h, p, grid, st);
+        return launch_scan_q<256, EPI, false>(h, p, grid, st);
+    }
     // NTT (4th template argument): one query tile -> every corpus byte is read by exactly one workgroup -> non-temporal loads
     if (bn == 64) {
         if (p.nqt == 1) return res ? launch_scan<64, EPI, true, true>(h, p, grid, st) : launch_scan<64, EPI, false, true>(h, p, grid, st);
@@ -276,21 +306,26 @@ static int launch_exact_scores(const rdx_index* h, const ExactParams& ep, int gr
     if (h->rows <= 0) return RDX_OK;
     const dim3 g_reg((unsigned)std::max<int64_t>(1, std::min<int64_t>((h->rows + 3) / 4, (int64_t)h->n_cu * 2)));
     dispatch_u(h->dim, [&](auto u) {
-        if constexpr (decltype(u)::value > 0) hipLaunchKernelGGL(k_exact_scores_reg<decltype(u)::value>, g_reg, dim3(256), 0, st, ep);
-        else hipLaunchKernelGGL(k_exact_scores, dim3(std::max(grid_rows, 1)), dim3(256), (size_t)ep.nq * h->dim * 4, st, ep);
+        constexpr int U = decltype(u)::value;
+        void (*kern)(const ExactParams) = ep.qf ? k_exact_scores<true> : k_exact_scores<false>;   // (qf: a filter per query)
+        if constexpr (U > 0) kern = ep.qf ? k_exact_scores_reg<U, true> : k_exact_scores_reg<U, false>;
+        if constexpr (U > 0) hipLaunchKernelGGL(kern, g_reg, dim3(256), 0, st, ep);
+        else hipLaunchKernelGGL(kern, dim3(std::max(grid_rows, 1)), dim3(256), (size_t)ep.nq * h->dim * 4, st, ep);
     });
     HIP_TRY(hipGetLastError());
     return RDX_OK;
 }
 
 // K5a's parameters for this index and the queries in qhat (q_list and nq: per group of QX queries, for_exact_groups)
-static ExactParams exact_params(const rdx_index* h, const uint32_t* allow) {
+static ExactParams exact_params(const rdx_index* h, const RowFilter& allow) {
     ExactParams ep = {};
     ep.master = h->mv();
     ep.rows = h->rows;
     ep.dim = h->dim;
     ep.qhat = h->qhat.as<float>();
-    ep.allow = allow;
+    ep.allow = allow.allow;
+    ep.ftab = allow.ftab;
+    ep.qf = allow.qf;
     ep.out = h->dense.as<float>();
     return ep;
 }
@@ -309,7 +344,7 @@ static SelectParams select_params(const rdx_index* h, int k, const TopkOut& out)
 // The exact full scan for the queries listed in d_list[0..n_list), QX at a time: K5a leaves a group's scores in `dense`, then
 // after(q_list, nq, last) launches what consumes them. t_first_inv: see run_exact.
 template <class After>
-static int for_exact_groups(rdx_index* h, const int32_t* d_list, int n_list, const uint32_t* allow, unsigned long long* t_first_inv, hipStream_t st, After after) {
+static int for_exact_groups(rdx_index* h, const int32_t* d_list, int n_list, const RowFilter& allow, unsigned long long* t_first_inv, hipStream_t st, After after) {
     RDX_TRY(h->dense.ensure((size_t)QX * std::max<int64_t>(h->rows, 1) * 4));
     ExactParams ep = exact_params(h, allow);
     ep.t_first_inv = t_first_inv;
@@ -325,7 +360,7 @@ static int for_exact_groups(rdx_index* h, const int32_t* d_list, int n_list, con
 }
 
 // exact full scan for the queries listed in d_list[0..n_list)
-static int run_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, const uint32_t* d_allow, const TopkOut& out, hipStream_t st,
+static int run_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, const RowFilter& d_allow, const TopkOut& out, hipStream_t st,
                      bool stamps = false, const FinishArgs* fin = nullptr) {
     const FinishArgs no_fin = {};   // (ctr == NULL: the launch does not end a search)
     // profile = 3: the scoring kernel's first block and the select kernel's last block leave their times in the counter block
@@ -426,7 +461,7 @@ static RefineParams refine_params(const rdx_index* h, const SearchPlan& p, const
 // The ScanParams of a plan's main scan. What its callers set differently are inputs: the `oob` word of the caller's counter block
 // (RefineCounters, RangeCounters); the sets of a search's bootstrap and how many per query (a range search has none); xcd_ranges: the
 // plan's use_xlo, bulk_it and xlo (a search: without them every stream is interleaved to its end); the workgroups' time stamps or NULL
-static ScanParams main_scan_params(const rdx_index* h, const SearchPlan& p, const uint32_t* allow, int* oob, float* setmax, int n_sets,
+static ScanParams main_scan_params(const rdx_index* h, const SearchPlan& p, const RowFilter& allow, int* oob, float* setmax, int n_sets,
                                    bool xcd_ranges, unsigned long long* wgt) {
     ScanParams sp = {};
     sp.shadow = h->store.shadow.as<_Float16>();
@@ -437,7 +472,9 @@ static ScanParams main_scan_params(const rdx_index* h, const SearchPlan& p, cons
     sp.tile_stride = 1;
     sp.nqt = p.nqt;
     sp.nq_pad = p.nq_pad;
-    sp.allow = allow;
+    sp.allow = allow.allow;
+    sp.ftab = allow.ftab;
+    sp.qf = allow.qf;
     sp.setmax = setmax;
     sp.n_sets = n_sets;
     sp.tau = h->tau.as<float>();
@@ -464,8 +501,8 @@ static SplitKParams split_k_params(const ScanParams& sp, const SearchPlan& p) { 
 // as many as the plan counted: the fused variant needs THEIR number even (dim_pad a multiple of 256).
 static int launch_main_scan(rdx_index* h, const SearchPlan& p, const ScanParams& sp, bool i8, hipStream_t st) {
     if (p.use_small) {
-        const SmallScanParams ss = {split_k_params(sp, p), sp.tau, sp.cntw, sp.cand, sp.capw, sp.inv_scale2, sp.wgt};
-        hipLaunchKernelGGL(k_scan_small, dim3((unsigned)p.grid), dim3(512), 0, st, ss);
+        const SmallScanParams ss = {split_k_params(sp, p), sp.tau, sp.cntw, sp.cand, sp.capw, sp.inv_scale2, sp.wgt, {sp.ftab, sp.qf}};
+        hipLaunchKernelGGL(sp.qf ? k_scan_small<true> : k_scan_small<false>, dim3((unsigned)p.grid), dim3(512), 0, st, ss);
         HIP_TRY(hipGetLastError());
         return RDX_OK;
     }
@@ -491,8 +528,8 @@ static int enqueue_scan(rdx_index* h, const SearchPlan& p, const SearchIO& io, h
     int* const oob = reinterpret_cast<int*>(h->ctr.as<char>() + offsetof(RefineCounters, oob));
     const ScanParams sp = main_scan_params(h, p, io.allow, oob, h->setmax.as<float>(), p.n_sets, true, p.stamps ? h->wgt.as<unsigned long long>() : nullptr);
     if (p.use_boot) {
-        const BootParams bp = {split_k_params(sp, p), (int)p.boot_units, sp.setmax, p.boot_sets};
-        hipLaunchKernelGGL(k_boot, dim3((unsigned)p.boot_units), dim3(512), 0, st, bp);
+        const BootParams bp = {split_k_params(sp, p), (int)p.boot_units, sp.setmax, p.boot_sets, {sp.ftab, sp.qf}};
+        hipLaunchKernelGGL(sp.qf ? k_boot<true> : k_boot<false>, dim3((unsigned)p.boot_units), dim3(512), 0, st, bp);
         HIP_TRY(hipGetLastError());
     } else {   // the sample: the scan's parameters without XCD ranges and stamps, over the sampled tiles
         ScanParams pb = main_scan_params(h, p, io.allow, oob, sp.setmax, p.n_sets_b, false, nullptr);
@@ -757,8 +794,16 @@ static int redo_overflowed(rdx_index* h, const PendingSearch& ps, int* n_exact, 
         hipLaunchKernelGGL(k_gather_queries, dim3((m + 3) / 4), dim3(256), 0, st, h->qhat.as<float>(), h->r_list.as<int32_t>(), m, h->dim,
                            h->r_q.as<float>());
         HIP_TRY(hipGetLastError());
+        RowFilter sub_allow = ps.io.allow;
+        if (ps.io.allow.qf) {   // a filter per query: the batch's queries bring theirs along (padded to the nested search's 256)
+            const int m_pad = (m + 255) / 256 * 256;
+            RDX_TRY(h->r_qf.ensure((size_t)m_pad * 4));
+            hipLaunchKernelGGL(k_gather_filters, dim3(m_pad / 256), dim3(256), 0, st, ps.io.allow.qf, h->r_list.as<int32_t>(), m, m_pad, h->r_qf.as<int32_t>());
+            HIP_TRY(hipGetLastError());
+            sub_allow = RowFilter(ps.io.allow.ftab, h->r_qf.as<int32_t>());
+        }
         rdx_search_stats sub = {};
-        const SearchIO sub_io = {h->r_q.as<float>(), ps.io.allow, h->r_s.as<float>(), h->r_r.as<int64_t>(), h->r_c.as<int32_t>(), nullptr};
+        const SearchIO sub_io = {h->r_q.as<float>(), sub_allow, h->r_s.as<float>(), h->r_r.as<int64_t>(), h->r_c.as<int32_t>(), nullptr};
         RDX_TRY(search_chunk(h, sub_io, m, p.k, st, &sub, 1, nullptr, false));
         hipLaunchKernelGGL(k_scatter_topk, dim3(m), dim3(64), 0, st, h->r_s.as<float>(), h->r_r.as<int64_t>(), h->r_c.as<int32_t>(),
                            h->r_list.as<int32_t>(), m, p.k, ps.io.score, ps.io.row, ps.io.count);
@@ -849,7 +894,9 @@ static int search_chunk(rdx_index* h, const SearchIO& io, int64_t nq, int k, hip
     SearchPlan plan;
     unsigned long long seq = 0;
     std::string err;
-    int rc = plan_search(h->shape(), h->opt, h->adapt, nq, k, depth, ho != nullptr, &plan, &err);
+    SearchOptions opt = h->opt;
+    if (io.allow.qf) opt.coarse_i8 = 0;   // a filter per query: the int8 coarse pass knows one bitmap only (include/rdx.h rdx_search_filtered)
+    int rc = plan_search(h->shape(), opt, h->adapt, nq, k, depth, ho != nullptr, &plan, &err);
     if (rc != RDX_OK) (void)fail(rc, err);
     if (rc == RDX_OK && depth == 0) h->coarse_bits = plan.exact_only ? 0 : (plan.i8 ? 8 : 16);
     if (rc == RDX_OK) rc = enqueue_search(h, plan, io, ho, st, &seq);
@@ -1317,9 +1364,32 @@ static int check_own_rows(const rdx_index* h, const char* who, const char* tail)
     return RDX_OK;
 }
 
-// allow_resident: allow_bits is already device memory whatever `space` says (a resident rdx_mask)
+// a checked rdx_search_filtered call that names more than one filter (host arrays)
+struct FilterCall {
+    const rdx_mask* const* filters;
+    int32_t n_filters;
+    const int32_t* query_filter;
+};
+
+// The call's filter table and indices into the index's scratch, on the search's stream: n_filters device pointers, then the nq indices
+// padded with -1 to whole 256-query tiles (every chunk of a search reads its slice up to its own nq_pad).
+static int upload_filters(rdx_index* h, const FilterCall& fc, int64_t nq, hipStream_t st, RowFilter* out) {
+    const size_t b_tab = ((size_t)fc.n_filters * sizeof(const uint32_t*) + 15) & ~(size_t)15;
+    const size_t n_qf = (size_t)((nq + 255) / 256 * 256);
+    h->fq_host.assign(b_tab + n_qf * 4, (char)0xff);   // (every index -1)
+    const uint32_t** tab = reinterpret_cast<const uint32_t**>(h->fq_host.data());
+    for (int32_t f = 0; f < fc.n_filters; ++f) tab[f] = fc.filters[f]->words.as<uint32_t>();
+    std::memcpy(h->fq_host.data() + b_tab, fc.query_filter, (size_t)nq * 4);
+    RDX_TRY(h->fq.ensure(h->fq_host.size()));
+    HIP_TRY(hipMemcpyAsync(h->fq.p, h->fq_host.data(), h->fq_host.size(), hipMemcpyHostToDevice, st));
+    *out = RowFilter(reinterpret_cast<const uint32_t* const*>(h->fq.p), reinterpret_cast<const int32_t*>(h->fq.as<char>() + b_tab));
+    return RDX_OK;
+}
+
+// allow_resident: allow_bits is already device memory whatever `space` says (a resident rdx_mask). fc: a filter per query instead
+// (allow_bits NULL).
 static int search_impl(rdx_index* h, const float* queries, int64_t nq, int k, const uint32_t* allow_bits, bool allow_resident,
-                       float* out_score, int64_t* out_row, int32_t* out_count, int space, void* stream) {
+                       float* out_score, int64_t* out_row, int32_t* out_count, int space, void* stream, const FilterCall* fc = nullptr) {
     if (nq < 0 || k < 0) return fail(RDX_ERR_INVALID, "rdx_search: nq and k must be >= 0");
     if (k > SELECT_MAX_K) return fail(RDX_ERR_INVALID, "rdx_search: k larger than " + std::to_string(SELECT_MAX_K) + " is not supported");
     RDX_TRY(check_space(space));
@@ -1340,11 +1410,13 @@ static int search_impl(rdx_index* h, const float* queries, int64_t nq, int k, co
         HIP_TRY(hipMemcpyAsync(h->mask.p, allow_bits, mask_words * 4, hipMemcpyHostToDevice, st));
         d_allow = h->mask.as<uint32_t>();
     }
+    RowFilter per_query;
+    if (fc) RDX_TRY(upload_filters(h, *fc, nq, st, &per_query));
     const int64_t CHUNK = 4096;   // queries per pipeline pass (<= 256 * WGs per XCD)
     const int kk = std::max(k, 1);
     for (int64_t q0 = 0; q0 < nq; q0 += CHUNK) {
         const int64_t m = std::min(CHUNK, nq - q0);
-        SearchIO io = {queries + (size_t)q0 * h->dim, d_allow, out_score ? out_score + (size_t)q0 * k : nullptr,
+        SearchIO io = {queries + (size_t)q0 * h->dim, fc ? RowFilter(per_query.ftab, per_query.qf + q0) : RowFilter(d_allow), out_score ? out_score + (size_t)q0 * k : nullptr,
                        out_row ? out_row + (size_t)q0 * k : nullptr, out_count + q0, nullptr};
         HostOut ho = {io.score, io.row, io.count, false};
         if (space == RDX_HOST) {
@@ -1434,6 +1506,34 @@ extern "C" int rdx_search_masked(rdx_index* h, const float* queries, int64_t nq,
     std::lock_guard<std::mutex> lk(h->mu);
     RDX_TRY(check_mask(h, mask, "rdx_search_masked", RDX_ERR_STATE));
     return search_impl(h, queries, nq, k, mask ? mask->words.as<uint32_t>() : nullptr, true, out_score, out_row, out_count, space, stream);
+}
+
+// A filter per query. Everything the header refuses is refused here, before anything is enqueued; a call whose queries
+// all name one filter (or none) is the existing search.
+extern "C" int rdx_search_filtered(rdx_index* h, const float* queries, int64_t nq, int k, const rdx_mask* const* filters, int32_t n_filters,
+                                   const int32_t* query_filter, float* out_score, int64_t* out_row, int32_t* out_count, int space, void* stream) {
+    if (!h) return fail(RDX_ERR_INVALID, "rdx_search_filtered: null index");
+    if (n_filters < 0 || n_filters > 65535)
+        return fail(RDX_ERR_INVALID, "rdx_search_filtered: n_filters must be in [0, 65535] (got " + std::to_string(n_filters) + ")");
+    if (n_filters > 0 && !filters) return fail(RDX_ERR_INVALID, "rdx_search_filtered: filters is NULL with n_filters = " + std::to_string(n_filters));
+    for (int32_t f = 0; f < n_filters; ++f)
+        if (!filters[f]) return fail(RDX_ERR_INVALID, "rdx_search_filtered: filters[" + std::to_string(f) + "] is a NULL handle");
+    if (nq > 0 && !query_filter) return fail(RDX_ERR_INVALID, "rdx_search_filtered: query_filter is NULL with nq = " + std::to_string(nq));
+    bool one = true;   // every query names query_filter[0]
+    for (int64_t q = 0; q < nq; ++q) {
+        if (query_filter[q] < -1 || query_filter[q] >= n_filters)
+            return fail(RDX_ERR_INVALID, "rdx_search_filtered: query " + std::to_string(q) + " names filter " + std::to_string(query_filter[q]) +
+                                             ", outside [-1, " + std::to_string(n_filters) + ")");
+        one = one && query_filter[q] == query_filter[0];
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    for (int32_t f = 0; f < n_filters; ++f) RDX_TRY(check_mask(h, filters[f], "rdx_search_filtered", RDX_ERR_STATE));
+    if (nq <= 0 || one) {
+        const rdx_mask* mask = (nq > 0 && query_filter[0] >= 0) ? filters[query_filter[0]] : nullptr;
+        return search_impl(h, queries, nq, k, mask ? mask->words.as<uint32_t>() : nullptr, true, out_score, out_row, out_count, space, stream);
+    }
+    const FilterCall fc = {filters, n_filters, query_filter};
+    return search_impl(h, queries, nq, k, nullptr, true, out_score, out_row, out_count, space, stream, &fc);
 }
 
 // ---- grouped search: the fill ---------------------------------------------------------------------------------

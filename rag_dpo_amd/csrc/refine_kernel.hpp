@@ -548,6 +548,12 @@ __global__ __launch_bounds__(256) void k_gather_queries(const float* __restrict_
     float4* dst = reinterpret_cast<float4*>(out + (int64_t)i * dim);
     for (int g = lane; g < (dim >> 2); g += 64) dst[g] = src[g];
 }
+// ... with their filter indices, when the search has a filter per query (padding entries: -1, no filter) ...
+__global__ __launch_bounds__(256) void k_gather_filters(const int32_t* __restrict__ qf, const int32_t* __restrict__ list, int m, int m_pad,
+                                                        int32_t* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < m_pad) out[i] = i < m ? qf[list[i]] : -1;
+}
 // ... and the batch's answers are put back where those queries belong
 __global__ __launch_bounds__(256) void k_scatter_topk(const float* __restrict__ s, const int64_t* __restrict__ r,
                                                       const int32_t* __restrict__ c, const int32_t* __restrict__ list, int m, int k,

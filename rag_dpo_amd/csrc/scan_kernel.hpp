@@ -87,6 +87,10 @@ struct ScanParams {
     int ncls;                  // 1 .. EPS_CLASSES
     int64_t shadow_bytes;      // RDX_CHECK_BOUNDS builds: size of the scan copy ...
     int* oob;                  // ... and the flag a corpus read outside it raises (tests/test_gpu_bounds.py)
+    // PERQ (a filter per query, rdx_search_filtered; allow is NULL): query q is held to bitmap ftab[qf[q]], to none when
+    // qf[q] < 0. qf has nq_pad entries (the padding queries: -1)
+    const uint32_t* const* ftab;
+    const int32_t* qf;
 };
 
 // 16 B per lane straight into VGPRs; completion is the CALLER's business (counted s_waitcnt vmcnt)
@@ -111,9 +115,13 @@ __device__ __forceinline__ void wait_vmcnt_keep(half8 (&a)[4]) {
 // I8: the int8 main pass (EMIT, BN = 256 only): the same bytes move the same way; v_mfma_i32_16x16x64_i8 takes the cycles of the
 // fp16 instruction for twice the k, so a k-step covers 128 dimensions; the accumulators are exact int32 dot products D of the
 // quantised rows, the check compares (float)max D * s_b (one s_b per wave and tile: the block's scale) with thr in t_q units.
-template <int BN, int EPI, bool HAS_MASK, bool RES, bool NTT = false, bool FUSEDT = false, bool I8 = false>
+// PERQ: every query has its own bitmap or none (ScanParams::qf). The tile's pointer per query sits in LDS behind the thresholds: the
+// bootstrap masks each lane's query columns with that column's word, the emit check's rare path tests the lane's own query against
+// its own word (one global load, no dependent pair). fp16, the stand-alone check, plain loads only.
+template <int BN, int EPI, bool HAS_MASK, bool RES, bool NTT = false, bool FUSEDT = false, bool I8 = false, bool PERQ = false>
 __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
     static_assert(!I8 || (EPI == EPI_EMIT && BN == 256 && !RES), "int8 pass: main scan of 256-query tiles only");
+    static_assert(!PERQ || (!HAS_MASK && !NTT && !FUSEDT && !I8), "a filter per query: the unfused fp16 kernels without a shared bitmap");
     using accv = std::conditional_t<I8, i32x4, f32x4>;
     constexpr bool FUSED = FUSEDT && EPI == EPI_EMIT;
     constexpr bool NT_A = NTT;            // host: NTT launches have ONE query tile (every corpus byte is read by one workgroup)
@@ -214,6 +222,14 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
     // thresholds, one per class of block error
     float* tau_s = reinterpret_cast<float*>(lcnt + BN);
     constexpr int TAU0 = I8 ? BN : 0;   // where the (first) threshold table starts
+    // PERQ: [BN] the queries' bitmaps (NULL: no filter), behind the BN thresholds
+    const uint32_t** qm_s = reinterpret_cast<const uint32_t**>(tau_s + BN);
+    if constexpr (PERQ) {
+        for (int i = threadIdx.x; i < BN; i += 512) {
+            const int f = p.qf[qt * BN + i];
+            qm_s[i] = f < 0 ? nullptr : p.ftab[f];
+        }
+    }
     if constexpr (EPI == EPI_SETMAX) {
 #pragma unroll
         for (int n = 0; n < (int)(sizeof(runmax) / sizeof(runmax[0])); ++n)
@@ -316,6 +332,11 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
         int lc = l15, lr = lq * 4;
         asm volatile("" : "+v"(lc), "+v"(lr));
         const int ql = n * 16 + lc;
+        if constexpr (PERQ) {   // this lane's query against its own word for the block
+            const uint32_t* qm = qm_s[ql];
+            if (qm && row_b < p.rows) okbits &= qm[row_b >> 5];
+            filt = true;
+        }
         // candidate slot index in 32 bits (the host keeps nq_pad * n_streams * capw below 2^29 for this kernel): the
         // store address is an SGPR base + a 32-bit lane offset, no 64-bit vector arithmetic
         const uint32_t seg0 = ((uint32_t)(qt * BN + ql) * (uint32_t)n_streams + (uint32_t)stream) * capw_s;
@@ -540,7 +561,20 @@ __global__ __launch_bounds__(512) void k_scan(const ScanParams p) {
             } else tile_rows(it_done, row_b, okbits, filt);
 #pragma unroll
             for (int n = 0; n < NB16; ++n) {
-                if constexpr (EPI == EPI_SETMAX) {
+                if constexpr (EPI == EPI_SETMAX && PERQ) {
+                    // the lane's query column of block n counts the rows its own bitmap allows
+                    uint32_t okq = okbits;
+                    const uint32_t* qm = qm_s[n * 16 + l15];
+                    if (qm && row_b < p.rows) okq &= qm[row_b >> 5];
+#pragma unroll
+                    for (int m = 0; m < 2; ++m)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            float v = (float)acc[m][n][r];
+                            if (!((okq >> (m * 16 + lq * 4 + r)) & 1u)) v = -INFINITY;
+                            runmax[n][0] = fmaxf(runmax[n][0], v);
+                        }
+                } else if constexpr (EPI == EPI_SETMAX) {
 #pragma unroll
                     for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -687,6 +721,12 @@ struct SplitKParams {
     int64_t n_blocks32;        // ceil(rows / 32)
     const uint32_t* allow;     // NULL or row bitmap
 };
+// a filter per query (k_boot<true>, k_scan_small<true>; SplitKParams::allow is NULL): query q is held to bitmap ftab[qf[q]], to none when
+// qf[q] < 0; qf holds at least BOOT_BN entries (ScanParams::qf)
+struct SplitKFilters {
+    const uint32_t* const* ftab;
+    const int32_t* qf;
+};
 constexpr int BOOT_NB = BOOT_BN / 16;   // 16-query blocks
 constexpr int BOOT_LD = 32 + 4;   // floats per query in a partial-sum slab [query][row]: a lane's 4 rows are one ds_write_b128, and the 16 lanes of
                                   // a pass land on 16 distinct bank quads (9 * query mod 16)
@@ -760,6 +800,11 @@ __device__ __forceinline__ uint32_t block_row_mask(int64_t rb, int64_t rows, con
     if (allow && left > 0) ok &= allow[rb];
     return ok;
 }
+// ... for the thread that owns query q: from that query's own bitmap
+__device__ __forceinline__ uint32_t block_row_mask_q(int64_t rb, int64_t rows, const SplitKFilters& pq, int q) {
+    const int f = pq.qf[q];
+    return block_row_mask(rb, rows, f < 0 ? nullptr : pq.ftab[f]);
+}
 
 // K2b. Threshold bootstrap for SMALL launches (<= 64 queries, at most a few 32-row blocks per CU): the K loop split over the waves.
 // The scan kernel above samples whole 256-row tiles: a launch that samples 33 tiles (100 k rows, the sample is 8 K rows) keeps
@@ -776,7 +821,9 @@ struct BootParams {
     int units;
     float* setmax;
     int n_sets;
+    SplitKFilters pq;   // k_boot<true>
 };
+template <bool PERQ = false>   // PERQ: a filter per query (BootParams::pq)
 __global__ __launch_bounds__(512) void k_boot(const BootParams p) {
     __shared__ __attribute__((aligned(16))) SplitKSlabs slab;
     const int u = blockIdx.x;
@@ -816,9 +863,10 @@ __global__ __launch_bounds__(512) void k_boot(const BootParams p) {
         }
     }
     splitk_reduce(slab, wave, l15, lq, acc);
-    const uint32_t ok = block_row_mask(rb, p.sk.rows, p.sk.allow);
+    uint32_t ok = PERQ ? 0u : block_row_mask(rb, p.sk.rows, p.sk.allow);
     if (threadIdx.x < 4 * BOOT_BN) {
         const int q = threadIdx.x & (BOOT_BN - 1), j = threadIdx.x / BOOT_BN;   // set j = rows 8j .. 8j+7 of the block
+        if constexpr (PERQ) ok = block_row_mask_q(rb, p.sk.rows, p.pq, q);
         f32x4 lo, hi;
         splitk_sum(slab, q, j, lo, hi);
         float mx = -INFINITY;
@@ -848,7 +896,9 @@ struct SmallScanParams {
     uint32_t capw;
     float inv_scale2;
     unsigned long long* wgt;   // [grid][2] start / end stamps (NULL: not wanted)
+    SplitKFilters pq;          // k_scan_small<true>
 };
+template <bool PERQ = false>   // PERQ: a filter per query (SmallScanParams::pq)
 __global__ __launch_bounds__(512) void k_scan_small(const SmallScanParams p) {
     __shared__ __attribute__((aligned(16))) SplitKSlabs slab;
     __shared__ uint32_t lcnt[BOOT_BN];
@@ -904,7 +954,7 @@ __global__ __launch_bounds__(512) void k_scan_small(const SmallScanParams p) {
         if (threadIdx.x < 4 * BOOT_BN) {
             const int q = threadIdx.x & (BOOT_BN - 1), j = threadIdx.x / BOOT_BN;   // rows 8j .. 8j+7 of the block, query q
             const int64_t row0 = rb * 32;
-            const uint32_t ok = block_row_mask(rb, p.sk.rows, p.sk.allow);
+            const uint32_t ok = PERQ ? block_row_mask_q(rb, p.sk.rows, p.pq, q) : block_row_mask(rb, p.sk.rows, p.sk.allow);
             f32x4 lo, hi;
             splitk_sum(slab, q, j, lo, hi);
             const float tq = tau_s[q];

@@ -6,7 +6,7 @@ pointers (RDX_DEVICE) on the current torch stream. No arithmetic happens in this
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -259,6 +259,37 @@ class HipIndex(_Handle):
         nq = self._device_call_shapes(queries, k, out_score, out_row, out_count)
         self._search(_ptr(queries), nq, k, _ptr(allow_bits), mask, (_ptr(out_score), _ptr(out_row), _ptr(out_count)), L.RDX_DEVICE,
                      ctypes.c_void_p(self._raw_stream(queries.device)))
+
+    def _search_filtered(self, q, nq: int, k: int, masks: Sequence[ResidentMask], query_filter, outs, where: int, stream):
+        """search_filtered's and search_filtered_device's one call into the library (rdx_search_filtered): the masks' handles and
+        the queries' indices are host arrays whichever side `where` names for q and outs"""
+        qf = np.ascontiguousarray(query_filter, dtype=np.int32)
+        if qf.shape != (nq,):
+            raise ValueError(f"query_filter must hold one int32 per query ({nq}), got shape {qf.shape}")
+        handles = (ctypes.c_void_p * max(len(masks), 1))(*[m._h for m in masks])
+        L.check(self._lib.rdx_search_filtered(self._h, q, nq, int(k), handles if len(masks) else None, len(masks), _np_ptr(qf), *outs,
+                                              where, stream))
+
+    def search_filtered(self, queries, k: int, masks: Sequence[ResidentMask], query_filter
+                        ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """search() with a filter per query: query q is held to masks[query_filter[q]] (make_mask), to none when query_filter[q] is -1.
+        Host in / host out; per query the results search(mask=...) gives for it alone (include/rdx.h rdx_search_filtered)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [nq][{self.dim}] query embeddings, got shape {q.shape}")
+        nq = q.shape[0]
+        sc = np.empty((nq, k), dtype=np.float32)
+        ro = np.empty((nq, k), dtype=np.int64)
+        cn = np.zeros((nq,), dtype=np.int32)
+        self._search_filtered(_np_ptr(q), nq, k, masks, query_filter, (_np_ptr(sc), _np_ptr(ro), _np_ptr(cn)), L.RDX_HOST, None)
+        return sc, ro, cn
+
+    def search_filtered_device(self, queries, k: int, out_score, out_row, out_count, masks: Sequence[ResidentMask], query_filter):
+        """search_device() with a filter per query (see search_filtered): torch CUDA tensors in/out, enqueued on the current torch
+        stream; masks and query_filter (int32 numpy) stay on the host"""
+        nq = self._device_call_shapes(queries, k, out_score, out_row, out_count)
+        self._search_filtered(_ptr(queries), nq, k, masks, query_filter, (_ptr(out_score), _ptr(out_row), _ptr(out_count)), L.RDX_DEVICE,
+                              ctypes.c_void_p(self._raw_stream(queries.device)))
 
     @staticmethod
     def _device_call_shapes(queries, k: int, out_score, out_row, out_count) -> int:

@@ -248,6 +248,32 @@ def _embed_device(provider, texts: List[str], device):
     return torch.tensor(np.asarray(provider.embed(texts), dtype=np.float32), device=device)
 
 
+def dense_lists(col, vectors, sub_wheres: List[Any], n_fetch: int):
+    """the dense lists of the batch's sub-queries (`vectors`, a tensor of one row each, sub-query t under sub_wheres[t]) -> (distances,
+    rows, counts) on the vectors' device. One search for the whole batch: query_device when the sub-queries share their `where`, else
+    query_filtered_device with every sub-query under its own; a collection without it is asked once per distinct `where`."""
+    import torch
+    by_where: Dict[str, List[int]] = {}
+    for t, w in enumerate(sub_wheres):
+        by_where.setdefault(_where_key(w), []).append(t)
+    if len(by_where) == 1:
+        return col.query_device(vectors, n_results=n_fetch, where=sub_wheres[0])
+    if hasattr(col, "query_filtered_device"):
+        try:
+            return col.query_filtered_device(vectors, sub_wheres, n_results=n_fetch)
+        except NotImplementedError:      # an "ip" / "l2" collection: refused before anything ran; the loop serves it as it always did
+            pass
+    device = vectors.device
+    d_dist = torch.empty((len(sub_wheres), n_fetch), dtype=torch.float32, device=device)
+    d_rows = torch.empty((len(sub_wheres), n_fetch), dtype=torch.int64, device=device)
+    d_cnt = torch.empty((len(sub_wheres),), dtype=torch.int32, device=device)
+    for ts in by_where.values():
+        idx = torch.as_tensor(ts, dtype=torch.int64, device=device)
+        dd, rr, cc = col.query_device(vectors.index_select(0, idx), n_results=n_fetch, where=sub_wheres[ts[0]])
+        d_dist[idx], d_rows[idx], d_cnt[idx] = dd, rr, cc
+    return d_dist, d_rows, d_cnt
+
+
 def retrieve_candidates_device(r, expanded: List[tuple], n_candidates: int, wheres: List[Any]) -> List[List[RetrievedChunk]]:
     """retrieve_candidates of every question, given as DenseRetriever._expand's (main query, sub-queries) and all inside the kernel's
     limits, fused by one launch. Raises whatever the batched device calls raise: the caller falls back to the per-question path."""
@@ -275,20 +301,7 @@ def retrieve_candidates_device(r, expanded: List[tuple], n_candidates: int, wher
 
     with torch.cuda.device(device):
         vectors = _embed_device(r.embedding_provider, texts, device)
-        # one search per distinct `where` (one for the whole batch when the questions share theirs)
-        by_where: Dict[str, List[int]] = {}
-        for t, q in enumerate(sub_q):
-            by_where.setdefault(_where_key(wheres[q]), []).append(t)
-        if len(by_where) == 1:
-            d_dist, d_rows, d_cnt = col.query_device(vectors, n_results=n_fetch, where=wheres[0])
-        else:
-            d_dist = torch.empty((len(texts), n_fetch), dtype=torch.float32, device=device)
-            d_rows = torch.empty((len(texts), n_fetch), dtype=torch.int64, device=device)
-            d_cnt = torch.empty((len(texts),), dtype=torch.int32, device=device)
-            for ts in by_where.values():
-                idx = torch.as_tensor(ts, dtype=torch.int64, device=device)
-                dd, rr, cc = col.query_device(vectors.index_select(0, idx), n_results=n_fetch, where=wheres[sub_q[ts[0]]])
-                d_dist[idx], d_rows[idx], d_cnt[idx] = dd, rr, cc
+        d_dist, d_rows, d_cnt = dense_lists(col, vectors, [wheres[q] for q in sub_q], n_fetch)
 
         # BM25 of every sub-query, each under its question's summary filter: one device call; the hits stay arrays
         bm_rows = None

@@ -9,7 +9,9 @@ Kernels are matched by symbol. A k_scan instantiation of the OLD listing that th
 arguments <BN, EPI, MASK, RES, SIBT, NTT, FUSED> of the scan before the sibling lock-step was removed, is matched through
 SIBT = false to the six-argument symbol; SIBT = true instantiations have no counterpart and are listed as removed. k_refine,
 k_select_dense, k_exact_scores and k_exact_scores_reg with their loose arguments are matched to the symbols that take
-RefineParams / SelectParams / ExactParams.
+RefineParams / SelectParams / ExactParams. A k_scan with seven template arguments and a k_exact_scores_reg<U> are matched to the
+symbols with the trailing argument PERQ = false (a filter per query), k_exact_scores, k_boot and k_scan_small to their
+<false> instantiations.
 
 For every matched pair it compares
   * the compiler's resource remarks (SGPRs, VGPRs, AGPRs, scratch, occupancy, LDS, spills) and the .amdhsa_* descriptor
@@ -22,6 +24,11 @@ import re
 import sys
 
 _SCAN7 = re.compile(r"^(_ZN3rdx6k_scanI(?:Li\d+E){2})((?:Lb[01]E){5})(EEvNS_10ScanParamsE)$")
+# the scan before it had a filter per query: seven template arguments; the eighth, PERQ, is false for every kernel that existed then
+_SCAN_NO_PERQ = re.compile(r"^(_ZN3rdx6k_scanI(?:Li\d+E){2}(?:Lb[01]E){5})(EEvNS_10ScanParamsE)$")
+_EXACT_REG_NO_PERQ = re.compile(r"^(_ZN3rdx18k_exact_scores_regILi\dE)(EEvNS_11ExactParamsE)$")
+# ... and k_exact_scores, k_boot and k_scan_small, plain kernels then, are the <false> instantiations of templates on PERQ
+_PLAIN_NO_PERQ = re.compile(r"^(_ZN3rdx(?:14k_exact_scores|6k_boot|12k_scan_small))E(NS_\d+\w+ParamsE)$")
 _REMARK_KEYS = ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill",
                 "VGPRs Spill", "LDS Size [bytes/block]")
 
@@ -40,6 +47,11 @@ def new_name(sym: str):
     for pat, repl in _STRUCT_ARGS:
         if pat.match(sym):
             return pat.sub(repl, sym)
+    if _PLAIN_NO_PERQ.match(sym):
+        return _PLAIN_NO_PERQ.sub(r"\1ILb0EEEv\2", sym)
+    for pat in (_SCAN_NO_PERQ, _EXACT_REG_NO_PERQ):
+        if pat.match(sym):
+            return pat.sub(r"\1Lb0E\2", sym)
     m = _SCAN7.match(sym)
     if not m:
         return sym
