@@ -156,7 +156,9 @@ int rdx_index_set_row_ids(rdx_index* h, int64_t first_row, const int64_t* ids, i
  * throughout: fewer hits to gather, the same answers; 0 = 8 where "coarse_i8" = 2 chose the int8 pass, 1 elsewhere (speed only);
  * developer options "refine_list" (0 = automatic, or 32..7168: upper bound on the LDS list's entries) and "spill_cap" (0 = automatic,
  * or 32..40960: upper bound on the HBM list's entries) drive the two lists' limits at small sizes (tests);
- * developer option "dup_batch" (0 = automatic, or 1..4096): rows per batch of rdx_index_near_dup (tests: edges across batch borders). */
+ * developer option "dup_batch" (0 = automatic, or 1..4096): rows per batch of rdx_index_near_dup (tests: edges across batch borders);
+ * developer option "km_tiles" (0 = automatic, or 1..4096): at least this many tiles of 256 rows per block of rdx_index_kmeans' ordering
+ * (tests: blocks of several tiles, which the automatic choice takes beyond 2^22 / n_clusters blocks). */
 int rdx_index_set_option(rdx_index* h, const char* name, int64_t value);
 
 /* The main scan's tile shares of the 8 XCDs (1.0 = an eighth; option "xcd_balance"): learned from the workgroups' own time stamps
@@ -848,6 +850,36 @@ int rdx_index_range(rdx_index* h, const float* queries, int64_t nq, const float*
  * made for another device or row count, 2^31 rows or more. RDX_ERR_STATE on an index with mapped row ids (a shard). */
 int rdx_index_near_dup(rdx_index* h, float threshold, const rdx_mask* mask, int list_cap, int64_t max_dense, int64_t* out_label,
                        int64_t* out_total, int64_t* out_stats, void* stream);
+
+/* k-means of the stored rows ---------------------------------------------------------------------- */
+/* Which themes the corpus holds and which rows belong to each: spherical k-means (Lloyd's iterations) over the stored rows, every
+ * step in a stated order so that the answer is a function of the rows, `init`, max_iter and the mask alone.
+ * rag_dpo_amd/kmeans.py states the definition; DESIGN.md §27.
+ *
+ * rdx_index_kmeans. "Allowed" = every row, or the rows of `mask`. score(c, r) = rdx_search's exact fp32 score of row r for the query c
+ * (through the normalisation of every search). assign(C): every allowed row goes to the centroid with the largest score (compared as
+ * fp32 values, ties to the smaller index). update: a cluster's members in ascending row order are cut into segments of 256; per
+ * element a segment's total is the sequential fp64 sum of its members' stored values from +0.0, the cluster's sum the sequential fp64
+ * sum of its segments' totals from +0.0; the new centroid is the normalisation (as of an added row) of the sums rounded to fp32; a
+ * cluster without members keeps its centroid. C = normalised init; assign; then at most max_iter times update + assign, stopping
+ * after the first assignment that changes no label (converged).
+ *   init         fp32 [n_clusters][dim] (device; must not overlap out_centroid)
+ *   out_label    int64 [rows] (device): the row's cluster under out_centroid; -1 for a row that is not allowed
+ *   out_score    fp32 [rows] (device): its score against that centroid; -inf for a row that is not allowed
+ *   out_centroid fp32 [n_clusters][dim] (device): the final centroids (max_iter = 0: the normalised init)
+ *   out_count    int64 [n_clusters] (device): members per cluster
+ *   out_info     HOST int32[2]: updates run, converged (0/1); written on success only
+ * The work is enqueued on `stream`; the host reads one pinned word per assignment (the number of changed labels) and the call returns
+ * when the results are complete. A pending asynchronous search is completed first; the statistics and the feedback state of
+ * rdx_search are not touched. Labels, scores, centroids and counts do not depend on block sizes, the path or the schedule.
+ * RDX_ERR_INVALID before anything is enqueued, the outputs untouched: n_clusters outside [1, RDX_KMEANS_MAX_CLUSTERS], max_iter outside
+ * [0, RDX_KMEANS_MAX_ITER], a mask made for another device or row count, 2^31 rows or more, an empty index, a null or misaligned
+ * pointer (init and out_centroid: 16 bytes). A NaN or Inf in init: RDX_ERR_INVALID after its normalisation ran, the outputs undefined.
+ * RDX_ERR_STATE on an index with mapped row ids (a shard). */
+#define RDX_KMEANS_MAX_CLUSTERS 4096
+#define RDX_KMEANS_MAX_ITER 1000
+int rdx_index_kmeans(rdx_index* h, const float* init, int n_clusters, int max_iter, const rdx_mask* mask, int64_t* out_label, float* out_score,
+                     float* out_centroid, int64_t* out_count, int32_t* out_info, void* stream);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,9 @@ exactly, the best max_results of them listed: what the reference does by fetchin
 `near_duplicates` / `near_duplicates_device` (not part of chromadb's API either) ask that question of the stored chunks themselves and
 join the answers into clusters of near-copies on the device: what the reference can only do by content hash before ingest
 (src/processing/deduplicate_corpus.py); rag_dpo_amd/dedup.py states the definition. Same limits.
+`kmeans` / `kmeans_device` / `assign_clusters` (not part of chromadb's API either) cluster the stored chunks by spherical k-means on the
+device, every step in a stated order, so that the clusters are a function of the rows and the arguments alone: which themes the corpus
+holds, where the reference has one LLM call per chunk (tag_all_chunks.py); rag_dpo_amd/kmeans.py states the definition. Same limits.
 ids/documents/metadata stay on the host; embeddings go to the device index (`engine`). The engine is
 always librdx (rag_dpo_amd.engine.HipIndex): there is no CPU search path in this package.
 
@@ -51,6 +54,7 @@ import numpy as np
 
 from . import dedup as DD
 from . import groups as GR
+from . import kmeans as KM
 from . import mmr as MM
 from . import range_search as RS
 from . import where as W
@@ -190,6 +194,7 @@ class Collection:
         self._group_stats = {k: 0 for k in GR.STAT_KEYS}   # group_stats
         self._range_stats = {"queries": 0, "mfma": 0, "exact": 0, "host": 0}   # range_stats
         self._dedup_stats = {k: 0 for k in DD.STAT_KEYS}   # dedup_stats
+        self._kmeans_stats = {k: 0 for k in KM.STAT_KEYS}  # kmeans_stats
 
     # ---- small helpers ----------------------------------------------------------------------
     @property
@@ -1277,6 +1282,92 @@ class Collection:
                 lab, tot = lab.cpu().numpy(), tot.cpu().numpy()
             groups = DD.clusters_of(lab)
             return {"clusters": [[self._ids[r] for r in g] for g in groups], "neighbors": [[int(tot[r]) for r in g] for g in groups]}
+
+    # ---- k-means of the stored rows (rag_dpo_amd/kmeans.py states the definition) ------------------------------------
+    def _kmeans_check(self, n_clusters, max_iter, seed, init, where_document):
+        """-> init as a matrix (or None: sampled)"""
+        _check_int("max_iter", max_iter, 0, KM.MAX_ITER)
+        if init is None:
+            _check_int("n_clusters", n_clusters, 1, KM.MAX_CLUSTERS)
+            _check_int("seed", seed, 0)
+        else:
+            init = _as_matrix(init, "init")
+            k = int(init.shape[0])
+            if k > KM.MAX_CLUSTERS:
+                raise ValueError(f"Expected init to hold at most {KM.MAX_CLUSTERS} centroids, got {k}")
+            if n_clusters is not None and (isinstance(n_clusters, bool) or n_clusters != k):
+                raise ValueError(f"n_clusters = {n_clusters!r} disagrees with the {k} centroids of init")
+        self._derived_check("kmeans", "clusters by the cosine score", where_document)
+        return init
+
+    @property
+    def kmeans_stats(self) -> Dict[str, int]:
+        """counters of kmeans / kmeans_device / assign_clusters since the collection was created: `calls`, the allowed `rows` they
+        clustered, the `iterations` (updates) they ran, and the calls answered on the `host` (engines without the clustering)"""
+        return dict(self._kmeans_stats)
+
+    def _kmeans(self, init, n_clusters, max_iter, seed, where, where_document, device: bool):
+        """-> kmeans_model's tuple: torch tensors on the engine's device (device engines), numpy arrays otherwise; the lock is held"""
+        self._refuse_empty("kmeans_device" if device else "kmeans")
+        if init is not None:
+            self._check_dim(int(init.shape[1]))
+            if not (bool(init.isfinite().all()) if _is_device_tensor(init) else bool(np.isfinite(init).all())):
+                raise ValueError("init contains NaN or Inf")
+        args = self._search_args(where, where_document)
+        on_device = self._on_device(args)
+        allowed = None
+        if init is None or not on_device:                # the host's bitmap: for the sample, and for the host path
+            allowed = self._mask(where) if WD.is_empty(where_document) else self._wd_mask(where, where_document)
+        if init is None:
+            rows = np.arange(self._rows, dtype=np.int64) if allowed is None else np.flatnonzero(allowed)
+            init = self._engine.get(KM.sample_rows(rows, n_clusters, seed))
+        if device and not on_device:                     # after the arguments and the filters, in near_duplicates_device's words
+            self._refuse_host_engine(always=True)
+        st = self._kmeans_stats
+        st["calls"] += 1
+        if on_device:
+            import torch
+            from . import engine as E
+            t = init if _is_device_tensor(init) else torch.from_numpy(init).to(f"cuda:{self._engine.device}")
+            out = E.kmeans(self._engine, t, int(max_iter), args.get("mask"))
+        else:
+            out = KM.kmeans_host(self._engine, init.cpu().numpy() if _is_device_tensor(init) else init, int(max_iter), args, allowed)
+            st["host"] += 1
+        st["rows"] += int(out[3].sum())
+        st["iterations"] += int(out[4])
+        return out
+
+    def kmeans_device(self, n_clusters: Optional[int] = None, max_iter: int = 20, seed: int = 0, init=None, where=None, where_document=None):
+        """kmeans for callers that stay on the GPU -> (labels i64 [rows], scores f32 [rows], centroids f32 [K][dim], counts i64 [K], n_iter,
+        converged), the tensors on the collection's device: labels[r] = the row's cluster, -1 for a row that is deleted or filtered out;
+        scores[r] = its cosine score against that centroid (-inf there). `ids_of` / `payload_of` map the rows."""
+        init = self._kmeans_check(n_clusters, max_iter, seed, init, where_document)
+        with self._lock:
+            return self._kmeans(init, n_clusters, max_iter, seed, where, where_document, True)
+
+    def kmeans(self, n_clusters: Optional[int] = None, max_iter: int = 20, seed: int = 0, init=None, where=None, where_document=None):
+        """Spherical k-means of the stored chunks: every allowed row goes to the centroid it is closest to by query()'s cosine distance,
+        a centroid becomes the normalised sum of its rows, until no row moves or `max_iter` updates have run. Every sum is taken in a
+        stated order: the same rows and arguments give the same answer, bit for bit, on every path.
+        -> {"centroids": fp32 [K][dim], "clusters": [[id, ...], ...] per cluster in row order, "distances": beside every id its distance
+        to its centroid, "counts": [members, ...], "n_iter": updates run, "converged": no row moved in the last assignment}.
+        `init`: K starting centroids [K][dim]; None: the stored rows of K allowed rows drawn with `seed` (kmeans.sample_rows). A cluster
+        that loses all its rows keeps its centroid. rag_dpo_amd/kmeans.py states the definition."""
+        init = self._kmeans_check(n_clusters, max_iter, seed, init, where_document)
+        with self._lock:
+            lab, sc, cen, cnt, n_iter, conv = self._kmeans(init, n_clusters, max_iter, seed, where, where_document, False)
+            if _is_device_tensor(lab):
+                lab, sc, cen, cnt = lab.cpu().numpy(), sc.cpu().numpy(), cen.cpu().numpy(), cnt.cpu().numpy()
+            dist = self._distances(sc)
+            groups = KM.clusters_of(lab, cen.shape[0])
+            return {"centroids": cen, "clusters": [[self._ids[r] for r in g.tolist()] for g in groups],
+                    "distances": [[float(d) for d in dist[g]] for g in groups], "counts": [int(c) for c in cnt],
+                    "n_iter": int(n_iter), "converged": bool(conv)}
+
+    def assign_clusters(self, centroids, where=None, where_document=None):
+        """kmeans' dict for given centroids, nothing moved (max_iter = 0): which allowed rows belong to which of them. The returned
+        centroids are the given ones normalised."""
+        return self.kmeans(init=centroids, max_iter=0, where=where, where_document=where_document)
 
     def ids_of(self, rows) -> List[List[str]]:
         """Chroma ids of row ids as returned by query_device (negative = padding, skipped)"""

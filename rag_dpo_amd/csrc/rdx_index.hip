@@ -1,5 +1,5 @@
 // rdx_index.hip — the dense index of librdx: the rdx_index lifecycle, options and ingest, rdx_l2_normalize, the search, masks,
-// merge and signal, the grouped fill, the MMR selection, the threshold search and the near-duplicate clustering of include/rdx.h. The only unit that holds a k_scan kernel (rag_dpo_amd/build.py checks that).
+// merge and signal, the grouped fill, the MMR selection, the threshold search, the near-duplicate clustering and the k-means of include/rdx.h. The only unit that holds a k_scan kernel (rag_dpo_amd/build.py checks that).
 // The scans and the tail of a search are launched from parameter structs filled by name, each in one place whoever searches: main_scan_params fills
 // ScanParams, refine_lists / refine_params k_refine's RefineParams, exact_params / select_params the exact path's, which for_exact_groups drives.
 #include "rdx_host.hpp"
@@ -20,6 +20,7 @@
 #include "scan_kernel.hpp"
 #include "search_plan.hpp"
 #include "dup_kernel.hpp"   // (after the search's kernels: the code object lists them in the order it always did, the new ones behind)
+#include "kmeans_kernel.hpp"
 
 using namespace rdx;
 
@@ -133,6 +134,22 @@ struct DupScratch {
     }
 };
 
+// rdx_index_kmeans' scratch (grow-only): the histograms / offsets, the order, the two tables, the segments' totals, the counters, and
+// the pinned word the host reads once per assignment
+struct KmScratch {
+    DevBuf hist, order, cluster_off, seg_off, segsum, ctr;
+    MappedPin<unsigned long long> mail;
+    unsigned long long seq = 0;   // number of the last word asked for
+    int ensure(int64_t rows, int n_clusters, int dim, int64_t n_blocks) {
+        DevBuf* const buf[6] = {&hist, &order, &cluster_off, &seg_off, &segsum, &ctr};
+        const size_t need[6] = {((size_t)n_clusters * n_blocks + 1) * 4, (size_t)rows * 4, ((size_t)n_clusters + 1) * 4, ((size_t)n_clusters + 1) * 4,
+                                (size_t)km_max_segments(rows, n_clusters) * dim * 8, sizeof(KmCounters)};
+        for (int i = 0; i < 6; ++i) RDX_TRY(buf[i]->ensure(need[i]));
+        if (!mail.host) RDX_TRY(mail.map(64));
+        return RDX_OK;
+    }
+};
+
 struct rdx_index {
     int device = 0;
     int dim = 0, dim_pad = 0, ksteps = 0, scale_log2 = 0;
@@ -163,6 +180,8 @@ struct rdx_index {
     DevBuf rng_ctr;          // rdx_index_range: its own counter block (range_kernel.hpp RangeCounters)
     DupScratch dup;          // rdx_index_near_dup
     int dup_batch = 0;       // option "dup_batch": rows per batch of rdx_index_near_dup, 0 = the range chunk (tests lower it)
+    KmScratch km;            // rdx_index_kmeans
+    int km_tiles = 0;        // option "km_tiles": tiles of 256 rows per block of rdx_index_kmeans' order, 0 = km_block_span (tests raise it)
     DevBuf spill;            // k_refine<true>: [nq_pad][spill_cap] hit lists of the queries that outgrow the LDS list (first spilling plan)
     // end-of-search mailbox in pinned host memory (k_finish writes it over PCIe; the host spins on its sequence number)
     MappedPin<Mailbox> mbox;
@@ -1014,6 +1033,11 @@ extern "C" int rdx_index_set_option(rdx_index* h, const char* name, int64_t valu
     if (n == "dup_batch") {
         if (value < 0 || value > RANGE_CHUNK) return fail(RDX_ERR_INVALID, "dup_batch must be 0 (the range chunk) or 1.." + std::to_string(RANGE_CHUNK));
         h->dup_batch = (int)value;
+        return RDX_OK;
+    }
+    if (n == "km_tiles") {
+        if (value < 0 || value > 4096) return fail(RDX_ERR_INVALID, "km_tiles must be 0 (automatic) or 1..4096");
+        h->km_tiles = (int)value;
         return RDX_OK;
     }
     std::string err;   // every other option is a search's (search_plan.hpp)
@@ -1895,6 +1919,147 @@ extern "C" int rdx_index_near_dup(rdx_index* h, float threshold, const rdx_mask*
         out_stats[2] = run.n_heavy;
         out_stats[3] = run.n_batches;
     }
+    return RDX_OK;
+}
+
+// ---- k-means of the stored rows -------------------------------------------------------------------------------------
+// C = K1(init) in out_centroid; an assignment = K1 of the centroids into qhat (the call a search makes on its queries), k_km_assign,
+// k_km_publish; an update = the order of rows by label (k_km_hist, k_km_scan, k_km_place), the tables (k_km_seg_table),
+// k_km_segment_sums, k_km_finish. The host reads one pinned word per assignment: the changed labels and K1's flag.
+static_assert(RDX_KMEANS_MAX_CLUSTERS <= KM_MAX_HIST && RDX_KMEANS_MAX_CLUSTERS <= 4096, "k_km_seg_table holds the clusters in one tile of 4 096");
+
+struct KmRun {
+    int n_clusters;
+    const uint32_t* allow;
+    int64_t* label; float* score; float* centroid; int64_t* count;
+    hipStream_t st;
+    KmOrderParams order;
+};
+
+// the word of the work enqueued so far: *changed = labels the last assignment changed, *bad = K1 met a NaN or Inf
+static int km_read_word(rdx_index* h, const KmRun& run, unsigned int* changed, bool* bad) {
+    KmScratch& km = h->km;
+    const unsigned long long seq = ++km.seq;
+    hipLaunchKernelGGL(k_km_publish, dim3(1), dim3(1), 0, run.st, km.ctr.as<KmCounters>(), km.mail.dev, seq);
+    HIP_TRY(hipGetLastError());
+    unsigned long long w = 0;
+    const int rc = wait_word([&] { return ((w = __atomic_load_n(km.mail.host, __ATOMIC_ACQUIRE)) >> 33) == seq; }, run.st);
+    if (rc == 1) return fail(RDX_ERR_HIP, "internal: rdx_index_kmeans' assignment completed without publishing its word");
+    if (rc != 0) return rc;
+    *changed = (unsigned int)(w & 0xffffffffull);
+    *bad = ((w >> 32) & 1ull) != 0;
+    return RDX_OK;
+}
+
+static int km_assign(rdx_index* h, const KmRun& run) {
+    int* const d_bad = reinterpret_cast<int*>(h->km.ctr.as<char>() + offsetof(KmCounters, bad));
+    RDX_TRY(normalize_queries<true>(h, run.centroid, run.n_clusters, 0, nullptr, d_bad, 0, run.st));
+    KmAssignParams ap = {};
+    ap.master = h->mv();
+    ap.rows = h->rows;
+    ap.dim = h->dim;
+    ap.qhat = h->qhat.as<float>();
+    ap.n_clusters = run.n_clusters;
+    ap.allow = run.allow;
+    ap.label = run.label;
+    ap.score = run.score;
+    ap.ctr = h->km.ctr.as<KmCounters>();
+    int rc = RDX_OK;
+    dispatch_u(h->dim, [&](auto u) {
+        constexpr int U = decltype(u)::value;
+        constexpr int R = U == 0 ? 1 : (U <= 2 ? 4 : 2);   // rows per wave: each LDS read of a centroid serves R rows
+        const size_t per_centroid = (size_t)(U > 0 ? 64 * U : h->dim / 4) * 32;
+        const int k4 = (run.n_clusters + 3) / 4 * 4;
+        ap.chunk = std::max(4, std::min(k4, (int)(KM_ASSIGN_LDS / per_centroid) / 4 * 4));
+        const size_t lds = (size_t)ap.chunk * per_centroid;
+        rc = dynamic_lds(h->device, (const void*)k_km_assign<U, R>, lds);
+        if (rc != RDX_OK) return;
+        const int64_t per_block = (int64_t)KM_ASSIGN_WAVES * R;
+        hipLaunchKernelGGL((k_km_assign<U, R>), dim3((unsigned)((h->rows + per_block - 1) / per_block)), dim3(64 * KM_ASSIGN_WAVES), lds, run.st, ap);
+    });
+    RDX_TRY(rc);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+// the order of rows by label and its tables; counts: the members per cluster into out_count as well
+static int km_order(rdx_index* h, const KmRun& run, bool place, int64_t* counts) {
+    KmScratch& km = h->km;
+    const KmOrderParams& op = run.order;
+    const size_t lds = (size_t)run.n_clusters * 4;
+    hipLaunchKernelGGL(k_km_hist, dim3((unsigned)op.n_blocks), dim3(KM_TILE), lds, run.st, op);
+    hipLaunchKernelGGL(k_km_scan, dim3(1), dim3(1024), 0, run.st, op.hist, (int64_t)run.n_clusters * op.n_blocks);
+    if (place) hipLaunchKernelGGL(k_km_place, dim3((unsigned)op.n_blocks), dim3(KM_TILE), lds, run.st, op);
+    hipLaunchKernelGGL(k_km_seg_table, dim3(1), dim3(1024), 0, run.st, op.hist, op.n_blocks, run.n_clusters, km.cluster_off.as<int32_t>(),
+                       km.seg_off.as<int32_t>(), counts);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+static int km_update(rdx_index* h, const KmRun& run) {
+    KmScratch& km = h->km;
+    RDX_TRY(km_order(h, run, true, nullptr));
+    const KmSumParams sp = {h->mv(), h->dim, run.n_clusters, km.seg_off.as<int32_t>(), km.cluster_off.as<int32_t>(), km.order.as<int32_t>(),
+                            km.segsum.as<double>(), run.centroid};
+    hipLaunchKernelGGL(k_km_segment_sums, dim3((unsigned)km_max_segments(h->rows, run.n_clusters)), dim3(h->dim / 4 <= 64 ? 64 : 256), 0, run.st, sp);
+    hipLaunchKernelGGL(k_km_finish, dim3(run.n_clusters), dim3(64), 0, run.st, sp);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+extern "C" int rdx_index_kmeans(rdx_index* h, const float* init, int n_clusters, int max_iter, const rdx_mask* mask, int64_t* out_label,
+                                float* out_score, float* out_centroid, int64_t* out_count, int32_t* out_info, void* stream) {
+    if (!h) return fail(RDX_ERR_INVALID, "rdx_index_kmeans: null index");
+    if (n_clusters < 1 || n_clusters > RDX_KMEANS_MAX_CLUSTERS)
+        return fail(RDX_ERR_INVALID, "rdx_index_kmeans: n_clusters must be in [1, " + std::to_string(RDX_KMEANS_MAX_CLUSTERS) + "]");
+    if (max_iter < 0 || max_iter > RDX_KMEANS_MAX_ITER)
+        return fail(RDX_ERR_INVALID, "rdx_index_kmeans: max_iter must be in [0, " + std::to_string(RDX_KMEANS_MAX_ITER) + "]");
+    std::lock_guard<std::mutex> lk(h->mu);
+    RDX_TRY(check_mask(h, mask, "rdx_index_kmeans", RDX_ERR_INVALID));
+    RDX_TRY(check_own_rows(h, "rdx_index_kmeans", "not available"));
+    if (h->rows >= ((int64_t)1 << 31)) return fail(RDX_ERR_INVALID, "rdx_index_kmeans: the order holds int32 rows: fewer than 2^31 rows");
+    if (h->rows == 0) return fail(RDX_ERR_INVALID, "rdx_index_kmeans: the index is empty");
+    if (!init || !out_label || !out_score || !out_centroid || !out_count || !out_info) return fail(RDX_ERR_INVALID, "rdx_index_kmeans: null pointer");
+    if ((((uintptr_t)init | (uintptr_t)out_centroid) & 15) || (((uintptr_t)out_label | (uintptr_t)out_count) & 7) || ((uintptr_t)out_score & 3))
+        return fail(RDX_ERR_INVALID, "rdx_index_kmeans: misaligned pointer");
+    RDX_TRY(finish_pending(h, nullptr));
+    RDX_TRY(set_device(h));
+    KmScratch& km = h->km;
+    KmRun run = {n_clusters, mask ? mask->words.as<uint32_t>() : nullptr, out_label, out_score, out_centroid, out_count, (hipStream_t)stream, {}};
+    const int64_t span = std::max<int64_t>(km_block_span(h->rows, n_clusters), (int64_t)h->km_tiles * KM_TILE), n_blocks = (h->rows + span - 1) / span;
+    RDX_TRY(km.ensure(h->rows, n_clusters, h->dim, n_blocks));
+    RDX_TRY(h->qhat.ensure((size_t)n_clusters * h->dim * 4));
+    run.order = KmOrderParams{out_label, h->rows, n_clusters, span, n_blocks, km.hist.as<int32_t>(), km.order.as<int32_t>()};
+    const hipStream_t st = run.st;
+    HIP_TRY(hipMemsetAsync(km.ctr.p, 0, sizeof(KmCounters), st));
+    // C = K1(init): the kernel and the instantiation a search's queries go through, written to the caller's centroids
+    int* const d_bad = reinterpret_cast<int*>(km.ctr.as<char>() + offsetof(KmCounters, bad));
+    hipLaunchKernelGGL(k_normalize<true>, dim3((unsigned)((n_clusters + 3) / 4)), dim3(256), 0, st, init, (const uint16_t*)nullptr, (int64_t)n_clusters,
+                       h->dim, (const int64_t*)nullptr, (int64_t)0, MasterView{out_centroid, nullptr, nullptr}, (_Float16*)nullptr, h->ksteps,
+                       h->scale(), d_bad, (int64_t)0, 0);
+    HIP_TRY(hipGetLastError());
+    unsigned int changed = 0;
+    bool bad = false;
+    RDX_TRY(km_read_word(h, run, &changed, &bad));
+    if (bad) return fail(RDX_ERR_INVALID, "rdx_index_kmeans: init contains NaN or Inf");
+    RDX_TRY(km_assign(h, run));
+    RDX_TRY(km_read_word(h, run, &changed, &bad));   // (the first assignment's count compares with what the caller's buffer held: not used)
+    int n_iter = 0, converged = 0;
+    while (n_iter < max_iter) {
+        RDX_TRY(km_update(h, run));
+        ++n_iter;
+        RDX_TRY(km_assign(h, run));
+        RDX_TRY(km_read_word(h, run, &changed, &bad));
+        if (bad) return fail(RDX_ERR_STATE, "internal: rdx_index_kmeans produced a centroid with NaN or Inf");
+        if (changed == 0) {
+            converged = 1;
+            break;
+        }
+    }
+    RDX_TRY(km_order(h, run, false, out_count));
+    HIP_TRY(hipStreamSynchronize(st));
+    out_info[0] = n_iter;
+    out_info[1] = converged;
     return RDX_OK;
 }
 

@@ -636,6 +636,30 @@ def near_dup(index: "HipIndex", t, mask: Optional[ResidentMask] = None, list_cap
     return lab, tot, [int(x) for x in stats]
 
 
+# ---- k-means of the stored rows (include/rdx.h rdx_index_kmeans; rag_dpo_amd/kmeans.py states the definition) -------------------
+def kmeans(index: "HipIndex", init, max_iter: int, mask: Optional[ResidentMask] = None):
+    """init fp32 [K][dim], a contiguous torch tensor on the index's device -> (labels i64 [rows], scores f32 [rows], centroids f32
+    [K][dim], counts i64 [K]) there and n_iter, converged on the host: spherical k-means of the allowed rows from the centroids
+    K1(init), at most max_iter updates. Enqueued on the current torch stream, complete on return. ValueError: K outside
+    [1, KMEANS_MAX_CLUSTERS], max_iter outside [0, KMEANS_MAX_ITER], an empty index, a NaN or Inf in init."""
+    import torch
+    _want_tensors(f"kmeans: init must be a contiguous fp32 [K][{index.dim}] tensor on cuda:{index.device}", index.device, (init, torch.float32))
+    if init.dim() != 2 or init.shape[1] != index.dim:
+        raise ValueError(f"kmeans: init must be [K][{index.dim}]")
+    dev = init.device
+    n, K = len(index), int(init.shape[0])
+    lab = torch.empty(n, dtype=torch.int64, device=dev)
+    sc = torch.empty(n, dtype=torch.float32, device=dev)
+    cen = torch.empty((max(K, 1), index.dim), dtype=torch.float32, device=dev)
+    cnt = torch.empty(max(K, 1), dtype=torch.int64, device=dev)
+    info = (ctypes.c_int32 * 2)(0, 0)
+    p = _ptr
+    with torch.cuda.device(dev):
+        L.check(index._lib.rdx_index_kmeans(index._h, p(init), K, int(max_iter), mask._h if mask is not None else None, p(lab), p(sc), p(cen),
+                                            p(cnt), info, ctypes.c_void_p(HipIndex._raw_stream(dev))))
+    return lab, sc, cen, cnt, int(info[0]), bool(info[1])
+
+
 def l2_normalize(x: np.ndarray, device: int = 0) -> np.ndarray:
     lib = L.load(require_gpu=True)
     a = np.ascontiguousarray(x, dtype=np.float32)
