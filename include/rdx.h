@@ -158,7 +158,9 @@ int rdx_index_set_row_ids(rdx_index* h, int64_t first_row, const int64_t* ids, i
  * or 32..40960: upper bound on the HBM list's entries) drive the two lists' limits at small sizes (tests);
  * developer option "dup_batch" (0 = automatic, or 1..4096): rows per batch of rdx_index_near_dup (tests: edges across batch borders);
  * developer option "km_tiles" (0 = automatic, or 1..4096): at least this many tiles of 256 rows per block of rdx_index_kmeans' ordering
- * (tests: blocks of several tiles, which the automatic choice takes beyond 2^22 / n_clusters blocks). */
+ * (tests: blocks of several tiles, which the automatic choice takes beyond 2^22 / n_clusters blocks);
+ * "facet_table_kb" (0 = the default, 262 144, or 1..4194304): the KiB that the per-query count tables of one pass of
+ * rdx_index_range_facets may take (speed and memory only: a pass holds budget / (4 B x n_groups) queries, one at the least). */
 int rdx_index_set_option(rdx_index* h, const char* name, int64_t value);
 
 /* The main scan's tile shares of the 8 XCDs (1.0 = an eighth; option "xcd_balance"): learned from the workgroups' own time stamps
@@ -880,6 +882,44 @@ int rdx_index_near_dup(rdx_index* h, float threshold, const rdx_mask* mask, int 
 #define RDX_KMEANS_MAX_ITER 1000
 int rdx_index_kmeans(rdx_index* h, const float* init, int n_clusters, int max_iter, const rdx_mask* mask, int64_t* out_label, float* out_score,
                      float* out_centroid, int64_t* out_count, int32_t* out_info, void* stream);
+
+/* Value counts (facets) -------------------------------------------------------------------------- */
+/* How many allowed rows carry each value of a metadata key: over the corpus, and over the rows within a distance of a query. The
+ * reference asks the first with one full id list per value (src/processing/create_chromadb_index.py:447-480) and by counting fetched
+ * metadata in a Python dict (pages/3_Documents.py:97-137). rag_dpo_amd/facets.py states the definitions; DESIGN.md §28.
+ *
+ * Both calls read a row -> code table: row_group int32 [rows of the index] (device), -1 = the row has no value, else a code in
+ * [0, n_groups). Any other code raises a flag on the device and fails the call with RDX_ERR_INVALID after the run, the outputs
+ * undefined; nothing is read or written through such a code. "Allowed" = every row, or the rows of `mask`.
+ *
+ * rdx_index_facet_count. out_counts int64 [n_groups] (device; may be NULL when n_groups == 0, and then row_group may be NULL too):
+ * allowed rows per code. out_missing / out_total HOST int64[1]: allowed rows with code -1 / allowed rows (= the sum of out_counts +
+ * missing). With n_groups == 0 the call counts the rows of a mask. The work is enqueued on `stream`; the call returns when the results
+ * are complete. A pending asynchronous search is completed first; an empty index gives zeros.
+ *
+ * rdx_index_range_facets. Per query q, with t = thresholds[q]: the rows in range are rdx_index_range's — allowed, exact fp32 score >= t —
+ * and they are counted by code instead of ranked.
+ *   out_total   int64 [nq]: the rows in range (rdx_index_range's out_total, the same number).
+ *   out_missing int64 [nq]: those of them with code -1.
+ *   out_found   int32 [nq]: codes with a non-zero count (it may exceed limit).
+ *   out_code int32 / out_n int64 [nq][limit]: the first min(limit, out_found) codes with a non-zero count by (count descending, code
+ *     ascending) and their counts; padding -1 / 0.
+ *   out_paths HOST int32[2] (may be NULL): as rdx_index_range's.
+ * All other pointers are device pointers. Integers throughout: the results do not depend on the path, the batch, the option
+ * "facet_table_kb" or the schedule. The queries are taken in passes whose uint32 tables [queries][n_groups] fit that option's budget
+ * (default 262 144 = 256 MiB; 1..4194304; at least one query per pass whatever n_groups), at most 4 096 queries per pass. The options
+ * that steer rdx_index_range steer it here; the statistics and the feedback state of rdx_search are not touched. The call returns when
+ * the results are complete.
+ * RDX_ERR_INVALID before anything is enqueued (both calls): n_groups outside [0, 2^31), limit outside [1, RDX_FACET_MAX_LIMIT], nq
+ * outside [0, 65535], a null or misaligned pointer (queries: 16 bytes), a mask made for another device or row count, 2^31 rows or
+ * more. A NaN threshold or a query holding NaN/Inf: RDX_ERR_INVALID after the run, the outputs undefined. RDX_ERR_STATE on an index
+ * with mapped row ids (a shard). */
+#define RDX_FACET_MAX_LIMIT 1024
+int rdx_index_facet_count(rdx_index* h, const rdx_mask* mask, const int32_t* row_group, int64_t n_groups, int64_t* out_counts,
+                          int64_t* out_missing, int64_t* out_total, void* stream);
+int rdx_index_range_facets(rdx_index* h, const float* queries, int64_t nq, const float* thresholds, const rdx_mask* mask,
+                           const int32_t* row_group, int64_t n_groups, int limit, int32_t* out_code, int64_t* out_n, int32_t* out_found,
+                           int64_t* out_missing, int64_t* out_total, int32_t* out_paths, void* stream);
 
 #ifdef __cplusplus
 }

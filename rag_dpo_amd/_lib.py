@@ -32,6 +32,7 @@ GROUP_MAX_K, GROUP_MAX_GROUPS, GROUP_MAX_SIZE, GROUP_FILL_SPAN = 4096, 64, 16, 4
 MMR_MAX_FETCH, MMR_MAX_K = 1024, 64   # include/rdx.h RDX_MMR_MAX_*: rdx_index_mmr's limits
 RANGE_MAX_RESULTS = 1024   # include/rdx.h RDX_RANGE_MAX_RESULTS: rdx_index_range's limit
 KMEANS_MAX_CLUSTERS, KMEANS_MAX_ITER = 4096, 1000   # include/rdx.h RDX_KMEANS_MAX_*: rdx_index_kmeans' limits
+FACET_MAX_LIMIT = 1024   # include/rdx.h RDX_FACET_MAX_LIMIT: rdx_index_range_facets' limit
 TOPIC_MAX_N, TOPIC_MAX_TOPICS, TOPIC_MAX_TAGS, TOPIC_MAX_DIM = 1024, 32, 64, 4096   # include/rdx.h rdx_topic_boost's limits
 # include/rdx.h RDX_RERANK_BATCH_MAX_ROWS / _MAX_QUESTIONS / RDX_RERANK_SELECT_WIDTHS: the batched reranker calls' limits, and the workgroup
 # widths rdx_rerank_select_batch chooses among (the smallest that holds the call's longest segment)
@@ -165,6 +166,8 @@ SYMBOLS = {
     "rdx_index_range": (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rdx_index_near_dup": (_i, [_vp, ctypes.c_float, _vp, _i, _i64, _vp, _vp, _vp, _vp]),
     "rdx_index_kmeans": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int32), _vp]),
+    "rdx_index_facet_count": (_i, [_vp, _vp, _vp, _i64, _vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _vp]),
+    "rdx_index_range_facets": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -53,6 +53,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence
 import numpy as np
 
 from . import dedup as DD
+from . import facets as FC
 from . import groups as GR
 from . import kmeans as KM
 from . import mmr as MM
@@ -195,6 +196,7 @@ class Collection:
         self._range_stats = {"queries": 0, "mfma": 0, "exact": 0, "host": 0}   # range_stats
         self._dedup_stats = {k: 0 for k in DD.STAT_KEYS}   # dedup_stats
         self._kmeans_stats = {k: 0 for k in KM.STAT_KEYS}  # kmeans_stats
+        self._facet_stats = {k: 0 for k in FC.STAT_KEYS}   # facet_stats
 
     # ---- small helpers ----------------------------------------------------------------------
     @property
@@ -638,9 +640,15 @@ class Collection:
         self._writes += 1
 
     # ---- chromadb.Collection API ---------------------------------------------------------------
-    def count(self) -> int:
+    def count(self, where=None, where_document=None) -> int:
+        """the live rows; with a filter, the live rows that pass it (the value counts' kernel with no table: no id list is built)"""
         with self._lock:
-            return self._rows - self._n_dead
+            if where in (None, {}) and WD.is_empty(where_document):
+                return self._rows - self._n_dead
+            if self._engine is None or self._rows == 0:
+                self._search_args(where, where_document)            # (the filters are judged all the same)
+                return 0
+            return self._facet_counts(None, where, where_document, False)[2]
 
     def add(self, ids, embeddings=None, metadatas=None, documents=None, _stored: bool = False, **_ignored):
         """reference create_chromadb_index.py:374-379, ingest_enterprise.py:241-246. Existing ids are skipped
@@ -1368,6 +1376,154 @@ class Collection:
         """kmeans' dict for given centroids, nothing moved (max_iter = 0): which allowed rows belong to which of them. The returned
         centroids are the given ones normalised."""
         return self.kmeans(init=centroids, max_iter=0, where=where, where_document=where_document)
+
+    # ---- value counts (rag_dpo_amd/facets.py states the definitions; DESIGN.md §28) --------------------------------------------------
+    @staticmethod
+    def _facet_check(key, limit, limit_may_be_none: bool):
+        if not isinstance(key, str) or not key:
+            raise ValueError(f"Expected key to be a non-empty str, got {key!r}")
+        if limit is not None or not limit_may_be_none:
+            _check_int("limit", limit, 1, FC.MAX_LIMIT)
+
+    @property
+    def facet_stats(self) -> Dict[str, int]:
+        """counters of the value counts since the collection was created: the corpus counts asked for (`calls`: facets, facets_device,
+        count with a filter) and how many of them were answered on the host (`calls_host`); the `queries` of query_facets /
+        query_facets_device and how many of them the engine answered on its `mfma` path, by its `exact` full scan, or were answered on
+        the `host` (engines without the counting search)"""
+        return dict(self._facet_stats)
+
+    def _facet_counts(self, key: Optional[str], where, where_document, device_out: bool):
+        """-> (counts int64 [G], missing, total) of the allowed rows by the code of `key` (None: no table, G = 0); counts is a torch tensor
+        on the engine's device where the engine counted, a numpy array otherwise. The lock is held and the collection is not empty."""
+        tables = GR.group_tables(self, key) if key is not None else None
+        G = tables.n_groups if tables is not None else 0
+        args = self._search_args(where, where_document)
+        eng = self._engine
+        st = self._facet_stats
+        if self.metadata.get("hnsw:space", "cosine") == "cosine" and not hasattr(eng, "devices") and self._on_device(args):
+            import torch
+            from . import engine as E
+            dev = torch.device("cuda", eng.device)
+            st["calls"] += 1
+            return E.facet_count(eng, tables.device(dev)[0] if G else None, G, args.get("mask"))
+        if device_out:
+            self._refuse_host_engine(always=True)
+        st["calls"] += 1
+        st["calls_host"] += 1
+        allowed = self._mask(where) if WD.is_empty(where_document) else self._wd_mask(where, where_document)
+        code = tables.row_group if tables is not None else np.full(self._rows, -1, dtype=np.int32)
+        return FC.facet_counts_model(code, G, allowed)
+
+    def facets_device(self, key: str, where=None, where_document=None):
+        """facets for callers that stay on the GPU -> (counts i64 [G] on the collection's device, missing, total): counts[c] = the
+        allowed rows that hold the value with code c (`group_values(key, codes)` maps codes to values: codes belong to the state of the
+        rows they were counted in), `missing` those without the key, `total` all of them."""
+        self._facet_check(key, None, True)
+        with self._lock:
+            self._refuse_empty("facets_device")
+            self._refuse_host_engine()
+            return self._facet_counts(key, where, where_document, True)
+
+    def facets(self, key: str, where=None, where_document=None, limit: Optional[int] = None):
+        """How many allowed rows carry each value of metadata key `key`, exactly: what the reference asks with one id list per value
+        (src/processing/create_chromadb_index.py:447-480). -> {"key", "values": the values with a non-zero count, count descending and
+        among equal counts the value that appears first in the rows first, "counts": beside them, "n_values": how many values have a
+        non-zero count (`limit` cuts the two lists, not this), "missing": allowed rows without the key, "total": allowed rows}.
+        1 and True are different values, as in query_groups. Works in every space and on every engine."""
+        self._facet_check(key, limit, True)
+        with self._lock:
+            if self._engine is None or self._rows == 0:
+                self._search_args(where, where_document)            # (the filters are judged all the same)
+                return {"key": key, "values": [], "counts": [], "n_values": 0, "missing": 0, "total": 0}
+            counts, missing, total = self._facet_counts(key, where, where_document, False)
+            if _is_device_tensor(counts):
+                counts = counts.cpu().numpy()
+            codes, cnt, n_values = FC.facet_order(counts, limit)
+            vals = GR.group_tables(self, key).values
+            return {"key": key, "values": [vals[c] for c in codes.tolist()], "counts": [int(x) for x in cnt], "n_values": n_values,
+                    "missing": int(missing), "total": int(total)}
+
+    def _query_facets_check(self, key, limit, where_document):
+        self._facet_check(key, limit, False)
+        self._derived_check("query_facets", "cuts at a cosine distance", where_document)
+
+    def _facet_queries_count(self, nq: int, paths):
+        st = self._facet_stats
+        st["queries"] += nq
+        if paths is None:
+            st["host"] += nq
+        else:
+            st["mfma"] += paths[0]
+            st["exact"] += paths[1]
+
+    def query_facets_device(self, query_embeddings, key: str, max_distance, limit: int = 10, where=None, where_document=None):
+        """query_facets for callers that hold their query embeddings on the GPU ([nq][dim] fp32 torch CUDA tensor) -> (codes i32
+        [nq, limit], counts i64 [nq, limit], n_values i32 [nq], missing i64 [nq], totals i64 [nq]) on the collection's device; padding is
+        code -1, count 0. `group_values(key, codes)` maps the codes. The same integers as query_facets."""
+        self._query_facets_check(key, limit, where_document)
+        with self._lock:
+            self._refuse_empty("query_facets_device")
+            self._refuse_host_engine()
+            import torch
+            from . import engine as E
+            q = query_embeddings.contiguous()
+            self._check_dim(tuple(q.shape)[-1], q.dim() == 2)
+            if _is_device_tensor(max_distance):
+                max_distance = max_distance.cpu().numpy()
+            thr = RS.as_thresholds(max_distance, int(q.shape[0]))
+            mask = self._resident("query_facets_device", self._search_args(where, where_document))
+            tables = GR.group_tables(self, key)
+            with torch.cuda.device(q.device):
+                if (thr == thr[0]).all():           # one distance for the batch: a fill on the stream instead of a pageable upload
+                    thr_d = torch.full((thr.shape[0],), float(thr[0]), dtype=torch.float32, device=q.device)
+                else:
+                    thr_d = torch.from_numpy(thr).to(q.device)
+                res = E.range_facets(self._engine, q, thr_d, tables.device(q.device)[0], tables.n_groups, int(limit), mask)
+            self._facet_queries_count(int(q.shape[0]), res[5])
+            return res[:5]
+
+    def query_facets(self, query_embeddings, key: str, max_distance, limit: int = 10, where=None, where_document=None):
+        """Of the allowed rows within cosine distance `max_distance` of each query (query_range's rows and floats: `totals` is its
+        `totals`), how many carry each value of metadata key `key`, exactly and however many rows are in range. `max_distance`: a
+        float, or one per query. -> {"key", "values": [nq][<= limit] the values with a non-zero count in facets' order, "counts": beside
+        them, "n_values": [values with a non-zero count per query], "missing": [rows in range without the key], "totals": [rows in
+        range]}. rag_dpo_amd/facets.py states the definition."""
+        self._query_facets_check(key, limit, where_document)
+        q = self._host_queries(query_embeddings)
+        nq, m = q.shape[0], int(limit)
+        if _is_device_tensor(max_distance):
+            max_distance = max_distance.cpu().numpy()
+        thr = RS.as_thresholds(max_distance, nq)
+        with self._lock:
+            out = {"key": key, "values": [[] for _ in range(nq)], "counts": [[] for _ in range(nq)], "n_values": [0] * nq,
+                   "missing": [0] * nq, "totals": [0] * nq}
+            if self._engine is None or self._rows == 0:
+                return out
+            self._check_dim(q.shape[1])
+            args = self._search_args(where, where_document)
+            tables = GR.group_tables(self, key)
+            if self._on_device(args):
+                import torch
+                from . import engine as E
+                dev = torch.device("cuda", self._engine.device)
+                with torch.cuda.device(dev):
+                    res = E.range_facets(self._engine, torch.from_numpy(q).to(dev), torch.from_numpy(thr).to(dev), tables.device(dev)[0],
+                                         tables.n_groups, m, args.get("mask"))
+                codes, cnt, nv, mis, tot = (x.cpu().numpy() for x in res[:5])
+                self._facet_queries_count(nq, res[5])
+            else:
+                codes, cnt, nv, mis, tot = FC.query_facets_host(self._engine, q, thr, tables.row_group, tables.n_groups, m, args)
+                self._facet_queries_count(nq, None)
+            vals = tables.values
+            for b in range(nq):
+                n = min(int(nv[b]), m)
+                out["values"][b] = [vals[c] for c in codes[b, :n].tolist()]
+                out["counts"][b] = [int(x) for x in cnt[b, :n]]
+            out["n_values"] = [int(x) for x in nv]
+            out["missing"] = [int(x) for x in mis]
+            out["totals"] = [int(x) for x in tot]
+            return out
 
     def ids_of(self, rows) -> List[List[str]]:
         """Chroma ids of row ids as returned by query_device (negative = padding, skipped)"""

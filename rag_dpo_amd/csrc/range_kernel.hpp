@@ -3,8 +3,11 @@
 //   k_range_tau          the main scan's threshold from the user's: no sample, no k_tau
 //   k_range_refine       re-scores the scan's hits exactly, counts those with exact >= t and orders the best of them (MFMA path)
 //   k_range_select_dense the same answer from the dense exact scores of k_exact_scores / k_exact_scores_reg (exact path, fallback)
+// Both are templates: <FACET = false> is the threshold search (rdx_index_range, rdx_index_near_dup); <FACET = true> counts the rows in
+// range by their code in a row -> code table instead of ranking them (rdx_index_range_facets, facet_count.hpp).
 // Included by rdx_index.hip only. The main scan between the first two is the search's own (scan_kernel.hpp), untouched.
 #pragma once
+#include "facet_count.hpp"
 #include "refine_kernel.hpp"
 
 namespace rdx {
@@ -53,7 +56,11 @@ struct RangeParams {
 //   > k puts the k-th key at or above t.
 //   A query with an overflowed segment or more hits than the list holds is appended to the fallback list (one atomic) and answered by
 //   the exact scan.
-__global__ __launch_bounds__(1024) void k_range_refine(const RangeParams args) {
+//   FACET: every hit with exact >= t adds one to its code's cell of the query's table row (fc.table) or to fc.missing[q], beside the
+//   total; nothing is ranked and no list is written. A query handed to the fallback list returns BEFORE it has counted anything: its
+//   table row is written by the dense stage alone, so it is counted exactly once.
+template <bool FACET>
+__global__ __launch_bounds__(1024) void k_range_refine(const RangeParams args, const FacetIO fc) {
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [list_cap] hits
     __shared__ RefineLds L;
     RefineParams p = args.r;
@@ -97,7 +104,11 @@ __global__ __launch_bounds__(1024) void k_range_refine(const RangeParams args) {
     int64_t* const o_r = p.out.row + (int64_t)q * k;
     if (m == 0) {
         if (threadIdx.x == 0) args.total[q] = 0;
-        rank_and_write(L.s_s, L.s_r, 0, k, o_s, o_r, p.out.count + q);
+        if constexpr (FACET) {
+            if (threadIdx.x == 0) fc.missing[q] = 0;
+        } else {
+            rank_and_write(L.s_s, L.s_r, 0, k, o_s, o_r, p.out.count + q);
+        }
         return;
     }
     uint2* const list = reinterpret_cast<uint2*>(smem);
@@ -107,6 +118,11 @@ __global__ __launch_bounds__(1024) void k_range_refine(const RangeParams args) {
     __syncthreads();
     // total = hits with exact >= t: per-lane counts, one shuffle reduction per wave, one LDS add per wave
     const float t = args.thr[q];
+    if constexpr (FACET) {
+        facet_count_block(fc, q, (int64_t)m, args.total, [&](int64_t i) { return __uint_as_float(list[i].x) >= t; },
+                          [&](int64_t i) { return (int64_t)list[i].y; });
+        return;
+    }
     reset_count(L);
     int loc = 0;
     for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) loc += __uint_as_float(list[i].x) >= t ? 1 : 0;
@@ -156,8 +172,17 @@ __global__ __launch_bounds__(1024) void k_range_refine(const RangeParams args) {
 // -inf = excluded by the `where` pre-filter, never counted and never returned): total = rows with score >= t; the best k rows by
 // select_dense_query, of which the first min(k, total) are in range (the list is sorted, and every row in range is an allowed row):
 // the rest becomes padding.
+// FACET: the rows with score >= t are counted by code into the query's table row (or fc.missing[q]) in the same walk; no list.
+template <bool FACET>
 __global__ __launch_bounds__(1024) void k_range_select_dense(const SelectParams p, const float* __restrict__ thr,
-                                                             int64_t* __restrict__ total) {
+                                                             int64_t* __restrict__ total, const FacetIO fc) {
+    if constexpr (FACET) {
+        const int q = p.q_list[blockIdx.x];
+        const float t = thr[q];
+        const float* __restrict__ sc = p.scores + (int64_t)blockIdx.x * p.rows;
+        facet_count_block(fc, q, p.rows, total, [&](int64_t i) { return sc[i] > -INFINITY && sc[i] >= t; }, [](int64_t i) { return i; });
+        return;
+    }
     __shared__ unsigned int s_total;
     const int j = blockIdx.x;
     const int q = p.q_list[j];

@@ -1,5 +1,5 @@
 // rdx_index.hip — the dense index of librdx: the rdx_index lifecycle, options and ingest, rdx_l2_normalize, the search, masks,
-// merge and signal, the grouped fill, the MMR selection, the threshold search, the near-duplicate clustering and the k-means of include/rdx.h. The only unit that holds a k_scan kernel (rag_dpo_amd/build.py checks that).
+// merge and signal, the grouped fill, the MMR selection, the threshold search, the near-duplicate clustering, the k-means and the value counts of include/rdx.h. The only unit that holds a k_scan kernel (rag_dpo_amd/build.py checks that).
 // The scans and the tail of a search are launched from parameter structs filled by name, each in one place whoever searches: main_scan_params fills
 // ScanParams, refine_lists / refine_params k_refine's RefineParams, exact_params / select_params the exact path's, which for_exact_groups drives.
 #include "rdx_host.hpp"
@@ -21,6 +21,7 @@
 #include "search_plan.hpp"
 #include "dup_kernel.hpp"   // (after the search's kernels: the code object lists them in the order it always did, the new ones behind)
 #include "kmeans_kernel.hpp"
+#include "facet_kernel.hpp"
 
 using namespace rdx;
 
@@ -182,6 +183,8 @@ struct rdx_index {
     int dup_batch = 0;       // option "dup_batch": rows per batch of rdx_index_near_dup, 0 = the range chunk (tests lower it)
     KmScratch km;            // rdx_index_kmeans
     int km_tiles = 0;        // option "km_tiles": tiles of 256 rows per block of rdx_index_kmeans' order, 0 = km_block_span (tests raise it)
+    DevBuf fct_ctr, fct_tab; // rdx_index_facet_count / rdx_index_range_facets: the counter block, a sub-chunk's tables (facet_kernel.hpp)
+    int64_t facet_table_kb = 0;   // option "facet_table_kb": the tables' budget, 0 = FACET_TABLE_KB
     DevBuf spill;            // k_refine<true>: [nq_pad][spill_cap] hit lists of the queries that outgrow the LDS list (first spilling plan)
     // end-of-search mailbox in pinned host memory (k_finish writes it over PCIe; the host spins on its sequence number)
     MappedPin<Mailbox> mbox;
@@ -1035,6 +1038,11 @@ extern "C" int rdx_index_set_option(rdx_index* h, const char* name, int64_t valu
         h->dup_batch = (int)value;
         return RDX_OK;
     }
+    if (n == "facet_table_kb") {
+        if (value < 0 || value > ((int64_t)1 << 22)) return fail(RDX_ERR_INVALID, "facet_table_kb must be 0 (automatic) or 1..4194304");
+        h->facet_table_kb = value;
+        return RDX_OK;
+    }
     if (n == "km_tiles") {
         if (value < 0 || value > 4096) return fail(RDX_ERR_INVALID, "km_tiles must be 0 (automatic) or 1..4096");
         h->km_tiles = (int)value;
@@ -1686,18 +1694,20 @@ struct RangeIO {
 };
 
 // the exact path of a range search for the queries listed in d_list[0..n_list): K5a per group of QX queries, then k_range_select_dense
-static int run_range_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, const RangeIO& io, hipStream_t st) {
+// (fc: the counting variant, for rdx_index_range_facets)
+static int run_range_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, const RangeIO& io, hipStream_t st, const FacetIO* fc) {
     return for_exact_groups(h, d_list, n_list, io.allow, nullptr, st, [&](const int32_t* q_list, int nq, bool) {
         SelectParams sel = select_params(h, k, TopkOut{io.score, io.row, io.count});
         sel.q_list = q_list;
-        hipLaunchKernelGGL(k_range_select_dense, dim3(nq), dim3(1024), 0, st, sel, io.thr, io.total);
+        if (fc) hipLaunchKernelGGL(k_range_select_dense<true>, dim3(nq), dim3(1024), 0, st, sel, io.thr, io.total, *fc);
+        else hipLaunchKernelGGL(k_range_select_dense<false>, dim3(nq), dim3(1024), 0, st, sel, io.thr, io.total, FacetIO{});
     });
 }
 
 // One chunk (nq <= 4096) of a range search: plan_range, K1, k_range_tau, then the exact path for everybody, or the main scan,
 // k_range_refine and the exact path for the queries it listed. Returns with the stream drained; paths[0] / [1] take the chunk's queries
-// by path.
-static int range_chunk(rdx_index* h, const RangeIO& io, int64_t nq, int k, hipStream_t st, int32_t* paths) {
+// by path. fc: the counting variants of the two last stages instead (rdx_index_range_facets): io's lists are not written, k is 1.
+static int range_chunk(rdx_index* h, const RangeIO& io, int64_t nq, int k, hipStream_t st, int32_t* paths, const FacetIO* fc = nullptr) {
     SearchPlan p;
     std::string err;
     const int prc = plan_range(h->shape(), h->opt, nq, k, &p, &err);
@@ -1722,7 +1732,7 @@ static int range_chunk(rdx_index* h, const RangeIO& io, int64_t nq, int k, hipSt
     HIP_TRY(hipGetLastError());
     if (p.exact_only) {
         RDX_TRY(ensure_iota(h, p.nq_pad, st));
-        RDX_TRY(run_range_exact(h, h->iota.as<int32_t>(), (int)nq, k, io, st));
+        RDX_TRY(run_range_exact(h, h->iota.as<int32_t>(), (int)nq, k, io, st, fc));
     } else {
         // the fp16 scan always, with neither bootstrap sets, XCD ranges nor stamps, and its bounds flag in this call's own counter block
         int* const oob = reinterpret_cast<int*>(h->rng_ctr.as<char>() + offsetof(RangeCounters, oob));
@@ -1734,8 +1744,13 @@ static int range_chunk(rdx_index* h, const RangeIO& io, int64_t nq, int k, hipSt
         rp.fallback_list = h->exact_list.as<int32_t>();
         rp.ctr = ctr;
         const size_t lds = (size_t)p.list_cap * 8;
-        RDX_TRY(dynamic_lds(h->device, (const void*)k_range_refine, lds));
-        hipLaunchKernelGGL(k_range_refine, dim3((unsigned)nq), dim3(1024), lds, st, rp);
+        if (fc) {
+            RDX_TRY(dynamic_lds(h->device, (const void*)k_range_refine<true>, lds));
+            hipLaunchKernelGGL(k_range_refine<true>, dim3((unsigned)nq), dim3(1024), lds, st, rp, *fc);
+        } else {
+            RDX_TRY(dynamic_lds(h->device, (const void*)k_range_refine<false>, lds));
+            hipLaunchKernelGGL(k_range_refine<false>, dim3((unsigned)nq), dim3(1024), lds, st, rp, FacetIO{});
+        }
         HIP_TRY(hipGetLastError());
     }
     RangeCounters c = {};
@@ -1746,7 +1761,7 @@ static int range_chunk(rdx_index* h, const RangeIO& io, int64_t nq, int k, hipSt
     int n_fb = p.exact_only ? (int)nq : c.n_fallback;
     if (!p.exact_only && n_fb > 0) {
         if (n_fb > nq) return fail(RDX_ERR_STATE, "internal: more fallback queries than queries");
-        RDX_TRY(run_range_exact(h, h->exact_list.as<int32_t>(), n_fb, k, io, st));
+        RDX_TRY(run_range_exact(h, h->exact_list.as<int32_t>(), n_fb, k, io, st, fc));
         HIP_TRY(hipStreamSynchronize(st));
     }
     paths[0] += (int32_t)(nq - n_fb);
@@ -2214,5 +2229,102 @@ extern "C" int rdx_merge_topk_packed(int device, const void* packed, int64_t par
                        part_stride / 8, part_stride / 4, n_parts, nq, k, out_score, out_row, out_count,
                        reinterpret_cast<const int32_t*>(b + flags_off), part_stride / 4, sig ? sig->word.dev : (unsigned long long*)nullptr, seq);
     HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
+// ---- value counts ---------------------------------------------------------------------------------------------------
+static_assert(FACET_MAX_LIMIT == RDX_FACET_MAX_LIMIT, "facet_kernel.hpp and include/rdx.h disagree");
+constexpr int64_t FACET_TABLE_KB = 262144;   // the default budget of a pass's tables: 256 MiB (DESIGN.md §28 says why)
+
+// what the two calls check alike before anything is enqueued (the caller holds the lock); on success the device is selected and the counters are zeroed
+static int facet_begin(rdx_index* h, const char* who, const rdx_mask* mask, hipStream_t st) {
+    RDX_TRY(check_mask(h, mask, who, RDX_ERR_INVALID));
+    RDX_TRY(check_own_rows(h, who, "not available"));
+    if (h->rows >= ((int64_t)1 << 31)) return fail(RDX_ERR_INVALID, std::string(who) + ": the table holds int32 codes per row: fewer than 2^31 rows");
+    RDX_TRY(finish_pending(h, nullptr));
+    RDX_TRY(set_device(h));
+    RDX_TRY(h->fct_ctr.ensure(sizeof(FacetCounters)));
+    HIP_TRY(hipMemsetAsync(h->fct_ctr.p, 0, sizeof(FacetCounters), st));
+    return RDX_OK;
+}
+
+// the counters back on the host, the stream drained; a code outside the table's range fails the call
+static int facet_end(rdx_index* h, const char* who, int64_t n_groups, hipStream_t st, FacetCounters* c) {
+    HIP_TRY(hipMemcpyAsync(c, h->fct_ctr.p, sizeof(*c), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (c->bad)
+        return fail(RDX_ERR_INVALID, std::string(who) + ": row_group holds a code outside -1 .. n_groups - 1 = " + std::to_string(n_groups - 1) +
+                                         " (nothing was counted through it; the outputs are undefined)");
+    return RDX_OK;
+}
+
+extern "C" int rdx_index_facet_count(rdx_index* h, const rdx_mask* mask, const int32_t* row_group, int64_t n_groups, int64_t* out_counts,
+                                     int64_t* out_missing, int64_t* out_total, void* stream) {
+    if (!h) return fail(RDX_ERR_INVALID, "rdx_index_facet_count: null index");
+    if (n_groups < 0 || n_groups >= ((int64_t)1 << 31)) return fail(RDX_ERR_INVALID, "rdx_index_facet_count: n_groups must be in [0, 2^31)");
+    if (!out_missing || !out_total || (n_groups > 0 && (!row_group || !out_counts))) return fail(RDX_ERR_INVALID, "rdx_index_facet_count: null pointer");
+    if (((uintptr_t)row_group & 3) || ((uintptr_t)out_counts & 7)) return fail(RDX_ERR_INVALID, "rdx_index_facet_count: misaligned pointer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    hipStream_t st = (hipStream_t)stream;
+    RDX_TRY(facet_begin(h, "rdx_index_facet_count", mask, st));
+    if (n_groups > 0) HIP_TRY(hipMemsetAsync(out_counts, 0, (size_t)n_groups * 8, st));
+    if (h->rows > 0) {
+        // a workgroup walks a span of rows, so that its table in LDS is zeroed and flushed once per span: eight workgroups per CU
+        const int64_t tiles = (h->rows + 255) / 256;
+        const int64_t span = (tiles + std::min<int64_t>(tiles, (int64_t)h->n_cu * 8) - 1) / std::min<int64_t>(tiles, (int64_t)h->n_cu * 8) * 256;
+        const FacetCountParams fp = {mask ? mask->words.as<uint32_t>() : nullptr, n_groups > 0 ? row_group : nullptr, h->rows, n_groups,
+                                     reinterpret_cast<unsigned long long*>(out_counts), h->fct_ctr.as<FacetCounters>(), span};
+        hipLaunchKernelGGL(k_facet_count, dim3((unsigned)((h->rows + span - 1) / span)), dim3(256), 0, st, fp);
+        HIP_TRY(hipGetLastError());
+    }
+    FacetCounters c = {};
+    RDX_TRY(facet_end(h, "rdx_index_facet_count", n_groups, st, &c));
+    *out_missing = (int64_t)c.missing;
+    *out_total = (int64_t)c.total;
+    return RDX_OK;
+}
+
+extern "C" int rdx_index_range_facets(rdx_index* h, const float* queries, int64_t nq, const float* thresholds, const rdx_mask* mask,
+                                      const int32_t* row_group, int64_t n_groups, int limit, int32_t* out_code, int64_t* out_n,
+                                      int32_t* out_found, int64_t* out_missing, int64_t* out_total, int32_t* out_paths, void* stream) {
+    if (!h) return fail(RDX_ERR_INVALID, "rdx_index_range_facets: null index");
+    if (limit < 1 || limit > RDX_FACET_MAX_LIMIT)
+        return fail(RDX_ERR_INVALID, "rdx_index_range_facets: limit must be in [1, " + std::to_string(RDX_FACET_MAX_LIMIT) + "]");
+    if (nq < 0 || nq > 65535) return fail(RDX_ERR_INVALID, "rdx_index_range_facets: nq must be in [0, 65535]");
+    if (n_groups < 0 || n_groups >= ((int64_t)1 << 31)) return fail(RDX_ERR_INVALID, "rdx_index_range_facets: n_groups must be in [0, 2^31)");
+    int32_t paths[2] = {0, 0};
+    if (out_paths) out_paths[0] = out_paths[1] = 0;
+    if (nq == 0) return RDX_OK;
+    if (!queries || !thresholds || !row_group || !out_code || !out_n || !out_found || !out_missing || !out_total)
+        return fail(RDX_ERR_INVALID, "rdx_index_range_facets: null pointer");
+    if (((uintptr_t)queries & 15) || (((uintptr_t)out_n | (uintptr_t)out_missing | (uintptr_t)out_total) & 7) ||
+        (((uintptr_t)thresholds | (uintptr_t)row_group | (uintptr_t)out_code | (uintptr_t)out_found) & 3))
+        return fail(RDX_ERR_INVALID, "rdx_index_range_facets: misaligned pointer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    hipStream_t st = (hipStream_t)stream;
+    RDX_TRY(facet_begin(h, "rdx_index_range_facets", mask, st));
+    // the queries of a pass share one table of n_groups cells each: as many queries as the budget holds, one at the least
+    const int64_t budget = (h->facet_table_kb > 0 ? h->facet_table_kb : FACET_TABLE_KB) * 1024;
+    const int64_t sub = std::max<int64_t>(1, std::min<int64_t>(RANGE_CHUNK, budget / std::max<int64_t>(n_groups * 4, 1)));
+    const size_t row_bytes = (size_t)n_groups * 4;
+    RDX_TRY(h->fct_tab.ensure(std::max<size_t>((size_t)std::min<int64_t>(sub, nq) * row_bytes, 16)));
+    int* const d_bad = reinterpret_cast<int*>(h->fct_ctr.as<char>() + offsetof(FacetCounters, bad));
+    for (int64_t q0 = 0; q0 < nq; q0 += sub) {
+        const int64_t m = std::min(sub, nq - q0);
+        if (row_bytes) HIP_TRY(hipMemsetAsync(h->fct_tab.p, 0, (size_t)m * row_bytes, st));
+        const RangeIO io = {queries + (size_t)q0 * h->dim, thresholds + q0, mask ? mask->words.as<uint32_t>() : nullptr, nullptr, nullptr, nullptr,
+                            out_total + q0};
+        const FacetIO fc = {row_group, n_groups, h->fct_tab.as<uint32_t>(), out_missing + q0, d_bad};
+        RDX_TRY(range_chunk(h, io, m, 1, st, paths, &fc));
+        const FacetTopParams tp = {h->fct_tab.as<uint32_t>(), n_groups, limit, out_code + (size_t)q0 * limit, out_n + (size_t)q0 * limit, out_found + q0};
+        hipLaunchKernelGGL(k_facet_top, dim3((unsigned)m), dim3(1024), 0, st, tp);
+        HIP_TRY(hipGetLastError());
+    }
+    FacetCounters c = {};
+    RDX_TRY(facet_end(h, "rdx_index_range_facets", n_groups, st, &c));
+    if (out_paths) {
+        out_paths[0] = paths[0];
+        out_paths[1] = paths[1];
+    }
     return RDX_OK;
 }

@@ -660,6 +660,61 @@ def kmeans(index: "HipIndex", init, max_iter: int, mask: Optional[ResidentMask] 
     return lab, sc, cen, cnt, int(info[0]), bool(info[1])
 
 
+# ---- value counts (include/rdx.h rdx_index_facet_count / rdx_index_range_facets; rag_dpo_amd/facets.py states the definitions) ----
+def facet_count(index: "HipIndex", row_group=None, n_groups: int = 0, mask: Optional[ResidentMask] = None):
+    """row_group i32 [rows] (a contiguous torch tensor on the index's device: -1 or a code < n_groups; None with n_groups = 0: no table)
+    -> (counts i64 [n_groups] on the device, missing, total): the allowed rows per code, those without a code, and their number.
+    Enqueued on the current torch stream, complete on return. ValueError: a code outside the table's range."""
+    import torch
+    dev = torch.device("cuda", index.device)
+    G = int(n_groups)
+    if row_group is not None:
+        _want_tensors(f"facet_count: row_group must be a contiguous int32 [rows] tensor on cuda:{index.device}", index.device, (row_group, torch.int32))
+        if row_group.shape != (len(index),):
+            raise ValueError("facet_count: row_group must hold one code per row of the index")
+    elif G:
+        raise ValueError("facet_count: n_groups > 0 needs row_group")
+    counts = torch.empty(G, dtype=torch.int64, device=dev)
+    missing, total = ctypes.c_int64(0), ctypes.c_int64(0)
+    with torch.cuda.device(dev):
+        L.check(index._lib.rdx_index_facet_count(index._h, mask._h if mask is not None else None, _ptr(row_group) if G else None, G,
+                                                 _ptr(counts) if G else None, ctypes.byref(missing), ctypes.byref(total),
+                                                 ctypes.c_void_p(HipIndex._raw_stream(dev))))
+    return counts, int(missing.value), int(total.value)
+
+
+def range_facets(index: "HipIndex", queries, thresholds, row_group, n_groups: int, limit: int, mask: Optional[ResidentMask] = None):
+    """queries fp32 [nq][dim], thresholds fp32 [nq] (score thresholds, as range_search takes them) and row_group i32 [rows] as contiguous
+    torch tensors on the index's device -> (codes i32 [nq][limit], counts i64 [nq][limit], n_values i32 [nq], missing i64 [nq], totals i64
+    [nq]) there and paths (a host list, range_search's): per query the rows in range counted by code, the best `limit` codes by (count
+    descending, code ascending), padding -1 / 0. Enqueued on the current torch stream, complete on return."""
+    import torch
+    dev = queries.device
+    _want_tensors(f"range_facets takes contiguous fp32 torch tensors on cuda:{index.device}", index.device, (queries, torch.float32),
+                  (thresholds, torch.float32))
+    _want_tensors(f"range_facets: row_group must be a contiguous int32 [rows] tensor on cuda:{index.device}", index.device, (row_group, torch.int32))
+    if queries.dim() != 2 or queries.shape[1] != index.dim:
+        raise ValueError(f"range_facets: queries must be [nq][{index.dim}]")
+    nq = int(queries.shape[0])
+    if thresholds.shape != (nq,):
+        raise ValueError("range_facets: thresholds must be [nq]")
+    if row_group.shape != (len(index),):
+        raise ValueError("range_facets: row_group must hold one code per row of the index")
+    m = int(limit)
+    mm = max(m, 1)
+    code = torch.empty((nq, mm), dtype=torch.int32, device=dev)
+    cnt = torch.empty((nq, mm), dtype=torch.int64, device=dev)
+    found = torch.empty(nq, dtype=torch.int32, device=dev)
+    mis = torch.empty(nq, dtype=torch.int64, device=dev)
+    tot = torch.empty(nq, dtype=torch.int64, device=dev)
+    paths = (ctypes.c_int32 * 2)(0, 0)
+    p = _ptr
+    L.check(index._lib.rdx_index_range_facets(index._h, p(queries), nq, p(thresholds), mask._h if mask is not None else None, p(row_group),
+                                              int(n_groups), m, p(code), p(cnt), p(found), p(mis), p(tot), paths,
+                                              ctypes.c_void_p(HipIndex._raw_stream(dev))))
+    return code, cnt, found, mis, tot, [int(paths[0]), int(paths[1])]
+
+
 def l2_normalize(x: np.ndarray, device: int = 0) -> np.ndarray:
     lib = L.load(require_gpu=True)
     a = np.ascontiguousarray(x, dtype=np.float32)
