@@ -554,8 +554,20 @@ class Collection:
 
     # What a *_device method refuses, one rule each; _device_args is their usual order. query_range_device, _grouped and _near_dup
     # call the rules one by one, because each of them reports two broken rules in an order of its own (kept as found).
+    def _no_rows(self) -> bool:
+        """nothing to answer from: nothing was ever added, or every row is deleted. Tombstones that no compaction has taken away yet
+        do not count: what a caller sees depends on the content, never on whether a compaction or a reload has happened"""
+        return self._engine is None or self._rows == self._n_dead
+
+    def _judge_filters(self, where, where_document=None):
+        """before an empty collection's answer: the filters a collection with rows refuses are refused all the same"""
+        if where not in (None, {}):
+            W.validate_where(where)
+        if not WD.is_empty(where_document):
+            WD.validate(where_document)
+
     def _refuse_empty(self, method: str):
-        if self._engine is None or self._rows == 0:
+        if self._no_rows():
             raise ValueError(f"{method}: the collection is empty")
 
     def _refuse_host_engine(self, always: bool = False):
@@ -645,8 +657,8 @@ class Collection:
         with self._lock:
             if where in (None, {}) and WD.is_empty(where_document):
                 return self._rows - self._n_dead
-            if self._engine is None or self._rows == 0:
-                self._search_args(where, where_document)            # (the filters are judged all the same)
+            if self._no_rows():
+                self._judge_filters(where, where_document)
                 return 0
             return self._facet_counts(None, where, where_document, False)[2]
 
@@ -837,8 +849,8 @@ class Collection:
                 "included": include,
             }
             if "embeddings" in include:
-                out["embeddings"] = (self._engine.get(np.array(rows, dtype=np.int64)) if rows and self._engine is not None
-                                     else np.zeros((0, self._dim or 0), dtype=np.float32))
+                dim = 0 if self._no_rows() else self._dim    # a collection without rows has no dimension, whatever it held before
+                out["embeddings"] = self._engine.get(np.array(rows, dtype=np.int64)) if rows else np.zeros((0, dim), dtype=np.float32)
             return out
 
     def peek(self, limit: int = 10):
@@ -858,8 +870,9 @@ class Collection:
         nq = q.shape[0]
         with self._lock:
             out = self._empty_result(nq, include, _ROW_KEYS)
-            if self._engine is None:   # nothing was ever added. As found: rows that are all gone do not count as empty here, and
-                out["embeddings"] = None                                # "embeddings" is None whatever include says
+            if self._no_rows():        # (as found: "embeddings" is None here whatever include says)
+                self._judge_filters(where, where_document)
+                out["embeddings"] = None
                 return out
             self._check_dim(q.shape[1])
             scores, rows, counts = self._engine.search(q, int(n_results), **self._search_args(where, where_document))
@@ -984,7 +997,9 @@ class Collection:
         wheres, where_documents = self._filters_check(nq, wheres, where_documents)
         with self._lock:
             out = self._empty_result(nq, include, _ROW_KEYS)
-            if self._engine is None:                     # nothing was ever added: query()'s answer
+            if self._no_rows():                          # query()'s answer
+                for w, wd in zip(wheres, where_documents):
+                    self._judge_filters(w, wd)
                 out["embeddings"] = None
                 return out
             self._check_dim(q.shape[1])
@@ -1074,7 +1089,8 @@ class Collection:
             out = {"groups": [[] for _ in range(nq)], "ids": [[] for _ in range(nq)], "included": include}
             for inc in ("distances", "documents", "metadatas"):
                 out[inc] = [[] for _ in range(nq)] if inc in include else None
-            if self._engine is None or self._rows == 0:
+            if self._no_rows():
+                self._judge_filters(where, where_document)
                 return out
             self._check_dim(q.shape[1])
             s, r, c, codes, found = self._grouped(q, group_by, n_groups, group_size, where, where_document, False)
@@ -1130,7 +1146,8 @@ class Collection:
         k, F, lam = int(n_results), int(fetch_k), float(lambda_mult)
         with self._lock:
             out = self._empty_result(nq, include, _ROW_KEYS, mmr_scores=[[] for _ in range(nq)])
-            if self._engine is None or self._rows == 0:
+            if self._no_rows():
+                self._judge_filters(where, where_document)
                 return out
             self._check_dim(q.shape[1])
             args = self._search_args(where, where_document)
@@ -1210,7 +1227,8 @@ class Collection:
         thr = RS.as_thresholds(max_distance, nq)
         with self._lock:
             out = self._empty_result(nq, include, _ROW_KEYS, totals=[0] * nq)
-            if self._engine is None or self._rows == 0:
+            if self._no_rows():
+                self._judge_filters(where, where_document)
                 return out
             self._check_dim(q.shape[1])
             args = self._search_args(where, where_document)
@@ -1282,8 +1300,9 @@ class Collection:
         (the distance is too loose for duplicate detection). rag_dpo_amd/dedup.py states the definition."""
         self._dedup_check(max_neighbors, max_dense_rows, where_document)
         with self._lock:
-            if self._engine is None or self._rows == 0:
+            if self._no_rows():
                 RS.score_threshold(max_distance)            # as found: a NaN distance is refused on an empty collection too
+                self._judge_filters(where, where_document)
                 return {"clusters": [], "neighbors": []}
             lab, tot = self._near_dup(max_distance, where, where_document, max_neighbors, max_dense_rows, False)
             if _is_device_tensor(lab):
@@ -1433,8 +1452,8 @@ class Collection:
         1 and True are different values, as in query_groups. Works in every space and on every engine."""
         self._facet_check(key, limit, True)
         with self._lock:
-            if self._engine is None or self._rows == 0:
-                self._search_args(where, where_document)            # (the filters are judged all the same)
+            if self._no_rows():
+                self._judge_filters(where, where_document)
                 return {"key": key, "values": [], "counts": [], "n_values": 0, "missing": 0, "total": 0}
             counts, missing, total = self._facet_counts(key, where, where_document, False)
             if _is_device_tensor(counts):
@@ -1498,7 +1517,8 @@ class Collection:
         with self._lock:
             out = {"key": key, "values": [[] for _ in range(nq)], "counts": [[] for _ in range(nq)], "n_values": [0] * nq,
                    "missing": [0] * nq, "totals": [0] * nq}
-            if self._engine is None or self._rows == 0:
+            if self._no_rows():
+                self._judge_filters(where, where_document)
                 return out
             self._check_dim(q.shape[1])
             args = self._search_args(where, where_document)

@@ -4,6 +4,8 @@ query / query_device and the four derived families (query_groups, query_mmr, que
 *_device form of each, crossed with every refusal the method can raise: REFUSALS pins the exception's type and its whole message, PAIRS
 which of two broken rules is reported. The literals are what the commit before the stages were given one helper each raised; the file
 passes on that commit and on every one after it. Then the empty-collection results key by key, and the mask cache's size, hits and keys.
+One rule has changed since: a collection whose rows are all deleted answers as one nothing was ever added to, compacted or not, and
+an empty collection refuses the `where` a populated one refuses (tests/history_model.py found both by replaying write histories).
 """
 import numpy as np
 import pytest
@@ -50,7 +52,8 @@ _made = {}
 
 def make(kind: str) -> Collection:
     """plain: OracleEngine (no search_device, no make_mask); device / bits / two: the engines above; ip / l2: that space, nothing added;
-    never: nothing was ever added (no engine); drained: every row added, deleted and compacted away (an engine of 0 rows)"""
+    never: nothing was ever added (no engine); drained: every row added, deleted and compacted away (an engine of 0 rows);
+    tombstoned: every row added and deleted, no compaction yet (an engine whose rows are all dead)"""
     if kind in _made:
         return _made[kind]
     eng = ENGINES.get(kind, OracleEngine)
@@ -62,6 +65,9 @@ def make(kind: str) -> Collection:
         col.delete(ids=IDS)
         col._compact()
         assert col._engine is not None and col._rows == 0
+    if kind == "tombstoned":
+        col.delete(ids=IDS)
+        assert col._rows == col._n_dead == ROWS
     _made[kind] = col
     return col
 
@@ -228,7 +234,7 @@ EMPTY = {
 }
 
 
-@pytest.mark.parametrize("kind", ["never", "drained"])
+@pytest.mark.parametrize("kind", ["never", "drained", "tombstoned"])
 @pytest.mark.parametrize("method", sorted(EMPTY))
 def test_empty_collection_results(method, kind):
     res = call(method, kind, {})
@@ -237,26 +243,53 @@ def test_empty_collection_results(method, kind):
         return
     lists = [v for v in res.values() if isinstance(v, list) and v and isinstance(v[0], list)]
     assert len({id(x) for v in lists for x in v}) == 2 * len(lists)                  # every per-query list is the caller's own
-    if (method, kind) != ("query", "drained"):                                       # (test_empty_collection_embeddings has that one)
-        assert call(method, kind, dict(query_embeddings=Q32)) == EMPTY[method]       # an empty collection has no dimension to miss ...
+    assert call(method, kind, dict(query_embeddings=Q32)) == EMPTY[method]           # an empty collection has no dimension to miss
     only = call(method, kind, dict(include=["distances"]))
     assert only["included"] == ["distances"] and only["distances"] == E2 and only["documents"] is None and only["metadatas"] is None
     assert only["ids"] == E2
 
 
 def test_empty_collection_embeddings():
-    """include=["embeddings"]: query_mmr / query_range give a list per query; query() gives None when nothing was ever added, and asks the
-    engine (per query an array of no rows) when the rows are gone but the engine is there: its own rule for "empty", kept as found"""
-    for method in ("query_mmr", "query_range"):
-        for kind in ("never", "drained"):
+    """include=["embeddings"]: query_mmr / query_range give a list per query; query() gives None. Rows that are all gone answer as a
+    collection nothing was ever added to: what a caller sees does not depend on whether a compaction or a reload has taken them away"""
+    for kind in ("never", "drained", "tombstoned"):
+        for method in ("query_mmr", "query_range"):
             res = call(method, kind, dict(include=["embeddings"]))
             assert res["embeddings"] == E2 and res["distances"] is None
-    assert call("query", "never", dict(include=["embeddings"]))["embeddings"] is None
-    got = call("query", "drained", dict(include=["embeddings"]))["embeddings"]
-    assert [(type(a), a.shape, a.dtype) for a in got] == [(np.ndarray, (0, DIM), np.float32)] * 2
-    with pytest.raises(ValueError) as e:                                             # ... and so query() still compares the dimension there
-        call("query", "drained", dict(query_embeddings=Q32))
-    assert str(e.value) == M_DIM
+        assert call("query", kind, dict(include=["embeddings"]))["embeddings"] is None
+        got = make(kind).get(include=["embeddings"])["embeddings"]
+        assert (type(got), got.shape, got.dtype) == (np.ndarray, (0, 0), np.float32)
+
+
+OTHERS = {
+    "query_filtered": lambda c, w: c.query_filtered(Q, [None, w]),
+    "query_facets": lambda c, w: c.query_facets(Q, "g", 0.3, where=w),
+    "facets": lambda c, w: c.facets("g", where=w),
+    "count": lambda c, w: c.count(where=w),
+    "get": lambda c, w: c.get(where=w),
+}
+
+
+@pytest.mark.parametrize("kind", ["never", "drained", "tombstoned", "plain"])
+@pytest.mark.parametrize("method", sorted(EMPTY) + sorted(OTHERS))
+def test_an_empty_collection_refuses_the_where_a_populated_one_refuses(method, kind):
+    with pytest.raises(ValueError) as e:
+        if method in OTHERS:
+            OTHERS[method](make(kind), NOT_A_WHERE)
+        else:
+            call(method, kind, dict(where=NOT_A_WHERE))
+    assert str(e.value) == M_WHERE
+
+
+@pytest.mark.parametrize("kind", ["never", "drained", "tombstoned"])
+def test_kmeans_and_the_device_forms_call_a_collection_without_live_rows_empty(kind):
+    col = make(kind)
+    for method, args in (("kmeans", dict(init=EMB[:2])), ("assign_clusters", dict(centroids=EMB[:2])), ("kmeans_device", dict(init=EMB[:2])),
+                         ("query_device", dict(query_embeddings=QT)), ("facets_device", dict(key="g"))):
+        with pytest.raises(ValueError) as e:
+            getattr(col, method)(**args)
+        assert str(e.value) == f"{'kmeans' if method == 'assign_clusters' else method}: the collection is empty"
+    assert col.count() == 0 and col.facets("g") == {"key": "g", "values": [], "counts": [], "n_values": 0, "missing": 0, "total": 0}
 
 
 # ---- the mask cache: size, hits and keys -----------------------------------------------------------------------------------------------
