@@ -349,6 +349,32 @@ int rdx_rerank_select_batch(int device, const float* scores, const double* boost
                             double min_score, int keep_min, int32_t* order, double* final_score, int32_t* count, int32_t* boosted,
                             void* stream);
 
+/* Late-interaction rerank (MaxSim) ---------------------------------------------------------------- */
+/* BGE-M3's third output, one vector per token, scored ColBERT-style (rag_dpo_amd/late_interaction.py):
+ *     score(q, d) = (1 / n_q) * sum_i max_j q_i . d_j
+ * over fp16 token vectors as stored. A dot product is accumulated in fp32 by v_mfma_f32_32x32x16_f16 in a fixed k order; the maximum
+ * over the slot's tokens is exact; the n_q maxima are added in fp64 in token order, divided by n_q and rounded once to fp32.
+ *   q_vecs fp16 [q_off[nq]][dim]: question q's token vectors are rows [q_off[q], q_off[q + 1]). q_off int32 [nq + 1] is a shape array
+ *     (the rule above: PINNED HOST memory, read by the library to check the call and by the kernel; device or pageable memory is
+ *     RDX_ERR_INVALID): q_off[0] >= 0, 1 to RDX_MAXSIM_MAX_Q_TOKENS rows per question, 1 <= nq <= RDX_RERANK_BATCH_MAX_QUESTIONS.
+ *   d_vecs fp16 [d_rows][dim]: the arena. Slot s is rows [slot_start[s], slot_start[s] + slot_len[s]), 1 to RDX_MAXSIM_MAX_SLOT_TOKENS
+ *     of them; slot_start int64 [n_slots], slot_len int32 [n_slots].
+ *   Pair p scores question pair_q[p] (int32) against slot pair_slot[p] (int64) into scores[p] (fp32), 1 <= n_pairs <=
+ *     RDX_MAXSIM_MAX_PAIRS; nothing behind scores[n_pairs - 1] is written. dim: a multiple of 32 in [32, RDX_MAXSIM_MAX_DIM].
+ *   q_vecs and d_vecs are 16-byte aligned. Everything but q_off is device memory.
+ * Invalid scalars or an invalid q_off return RDX_ERR_INVALID before anything is launched. A pair whose question or slot index is out
+ * of range, or whose slot does not lie inside [0, d_rows) with an admitted length, gets NaN and reads nothing outside the arrays; its
+ * neighbours are unaffected. No load leaves a pair's slot or its question's rows (a slot may end at the arena's last row). Enqueued on
+ * `stream`, nothing synchronised, nothing allocated, no float atomics; a pair's bits do not depend on its position, on n_pairs or on
+ * the other pairs of the call. One workgroup of four waves per pair (csrc/maxsim_kernel.hpp). */
+#define RDX_MAXSIM_MAX_Q_TOKENS 256
+#define RDX_MAXSIM_MAX_SLOT_TOKENS 8192
+#define RDX_MAXSIM_MAX_DIM 1024
+#define RDX_MAXSIM_MAX_PAIRS (1 << 20)
+int rdx_maxsim_f16(int device, const void* q_vecs, const int32_t* q_off, int nq, const void* d_vecs, int64_t d_rows,
+                   const int64_t* slot_start, const int32_t* slot_len, int64_t n_slots, const int32_t* pair_q,
+                   const int64_t* pair_slot, int64_t n_pairs, int dim, float* scores, void* stream);
+
 /* `collection.query(query_embeddings=, n_results=k, where=)` (reference
  * src/rag/retriever.py:215-220,380-385; create_chromadb_index.py:405-408,435-439).
  *   queries     [nq][dim] raw fp32 (normalised on the device like corpus rows)

@@ -37,6 +37,8 @@ TOPIC_MAX_N, TOPIC_MAX_TOPICS, TOPIC_MAX_TAGS, TOPIC_MAX_DIM = 1024, 32, 64, 409
 # include/rdx.h RDX_RERANK_BATCH_MAX_ROWS / _MAX_QUESTIONS / RDX_RERANK_SELECT_WIDTHS: the batched reranker calls' limits, and the workgroup
 # widths rdx_rerank_select_batch chooses among (the smallest that holds the call's longest segment)
 RERANK_BATCH_MAX_ROWS, RERANK_BATCH_MAX_QUESTIONS, RERANK_SELECT_WIDTHS = 1 << 20, 65535, (64, 256, 1024)
+# include/rdx.h RDX_MAXSIM_MAX_*: rdx_maxsim_f16's limits (token vectors per question and per slot, dim, pairs per call)
+MAXSIM_MAX_Q_TOKENS, MAXSIM_MAX_SLOT_TOKENS, MAXSIM_MAX_DIM, MAXSIM_MAX_PAIRS = 256, 8192, 1024, 1 << 20
 
 
 def topic_pair(topic: int, tag: int, exact: bool) -> int:
@@ -113,6 +115,7 @@ SYMBOLS = {
     "rdx_topic_boost_batch": (_i, [_i, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double,
                                    _vp, _vp, _vp, _vp]),
     "rdx_rerank_select_batch": (_i, [_i, _vp, _vp, _i, _vp, _i, ctypes.c_double, _i, _vp, _vp, _vp, _vp, _vp]),
+    "rdx_maxsim_f16": (_i, [_i, _vp, _vp, _i, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i, _vp, _vp]),
     "rdx_search": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "rdx_mask_create": (_i, [_vp, _vp, _i, ctypes.POINTER(_vp)]),
     "rdx_mask_destroy": (_i, [_vp]),

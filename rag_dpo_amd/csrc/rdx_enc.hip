@@ -445,29 +445,6 @@ extern "C" int rdx_rerank_head_rows_f16(int device, const float* cls, int64_t n,
                               b_out, workspace, scores, stream);
 }
 
-// A shape array of a batched call is read here, to check the call and size its grids, and by the kernels: it has to lie in pinned
-// host memory (hipHostMalloc / hipHostRegister), which both sides address. -> *dev = the address the kernels use. Anything
-// else (device memory, pageable host memory) is refused: nothing is copied and nothing waited for.
-static int shape_array(const char* fn, const char* name, const void* p, size_t align, const void** dev) {
-    if (!p) return fail(RDX_ERR_INVALID, std::string(fn) + ": null pointer (" + name + ")");
-    if ((uintptr_t)p & (align - 1)) return fail(RDX_ERR_INVALID, std::string(fn) + ": misaligned pointer (" + name + ")");
-    hipPointerAttribute_t attr;
-    hipError_t e = hipPointerGetAttributes(&attr, p);
-    if (e != hipSuccess || attr.type != hipMemoryTypeHost) {
-        (void)hipGetLastError();
-        return fail(RDX_ERR_INVALID, std::string(fn) + ": " + name + " must lie in pinned host memory (the library reads it to check the "
-                                     "call and size the launch, the kernels read the same words)");
-    }
-    void* d = nullptr;
-    e = hipHostGetDevicePointer(&d, const_cast<void*>(p), 0);
-    if (e != hipSuccess || !d) {
-        (void)hipGetLastError();
-        return fail(RDX_ERR_INVALID, std::string(fn) + ": " + name + " is pinned host memory that is not mapped to the device");
-    }
-    *dev = d;
-    return RDX_OK;
-}
-
 // cand_off [nq + 1]: starts at 0, never decreases, no segment above 1024, at most 2^20 candidates -> the longest segment
 static int check_segments(const char* fn, const int32_t* cand_off, int nq, int* longest) {
     if (cand_off[0] != 0) return fail(RDX_ERR_INVALID, std::string(fn) + ": cand_off must start at 0");

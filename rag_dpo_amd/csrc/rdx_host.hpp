@@ -1,6 +1,6 @@
-// rdx_host.hpp — what the host units of librdx (rdx_index.hip, rdx_enc.hip, rdx_bm25.hip, rdx_docs.hip, rdx_meta.hip) share: the error
-// string behind rdx_last_error(), the checks of `space` and `device`, the device / pinned buffers, the dynamic-LDS limit of a kernel,
-// and the wait on a word in pinned memory. What only the row-filter stores share (rdx_docs.hip, rdx_meta.hip) is in rdx_store.hpp.
+// rdx_host.hpp — what the host units of librdx (rdx_index.hip, rdx_enc.hip, rdx_bm25.hip, rdx_docs.hip, rdx_meta.hip, rdx_maxsim.hip)
+// share: the error string behind rdx_last_error(), the checks of `space`, `device` and a call's shape arrays, the device / pinned
+// buffers, the dynamic-LDS limit of a kernel, and the wait on a word in pinned memory. What only the row-filter stores share (rdx_docs.hip, rdx_meta.hip) is in rdx_store.hpp.
 #pragma once
 #include "../../include/rdx.h"
 #include "rdx_limits.hpp"
@@ -66,6 +66,30 @@ RDX_HOST_SHARED int check_device(const char* prefix, int device) {
 // the `device` argument of an entry point that keeps state per device (tables of rdx::MAX_DEVICES entries); who = the entry point
 RDX_HOST_SHARED int check_device_index(const char* who, int device) {
     if (device < 0 || device >= rdx::MAX_DEVICES) return fail(RDX_ERR_INVALID, std::string(who) + ": device out of range");
+    return RDX_OK;
+}
+
+// A shape array of a batched call (rdx_enc.hip's reranker batch, rdx_maxsim.hip) is read by the library, to check the call and size
+// its grids, and by the kernels: it has to lie in pinned host memory (hipHostMalloc / hipHostRegister), which both sides address.
+// -> *dev = the address the kernels use. Anything else (device memory, pageable host memory) is refused: nothing is copied and
+// nothing waited for.
+RDX_HOST_SHARED int shape_array(const char* fn, const char* name, const void* p, size_t align, const void** dev) {
+    if (!p) return fail(RDX_ERR_INVALID, std::string(fn) + ": null pointer (" + name + ")");
+    if ((uintptr_t)p & (align - 1)) return fail(RDX_ERR_INVALID, std::string(fn) + ": misaligned pointer (" + name + ")");
+    hipPointerAttribute_t attr;
+    hipError_t e = hipPointerGetAttributes(&attr, p);
+    if (e != hipSuccess || attr.type != hipMemoryTypeHost) {
+        (void)hipGetLastError();
+        return fail(RDX_ERR_INVALID, std::string(fn) + ": " + name + " must lie in pinned host memory (the library reads it to check the "
+                                     "call and size the launch, the kernels read the same words)");
+    }
+    void* d = nullptr;
+    e = hipHostGetDevicePointer(&d, const_cast<void*>(p), 0);
+    if (e != hipSuccess || !d) {
+        (void)hipGetLastError();
+        return fail(RDX_ERR_INVALID, std::string(fn) + ": " + name + " is pinned host memory that is not mapped to the device");
+    }
+    *dev = d;
     return RDX_OK;
 }
 

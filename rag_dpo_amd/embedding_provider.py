@@ -21,6 +21,7 @@ random weights and a hashing tokenizer — shape/perf faithful for benchmarks, N
 from __future__ import annotations
 
 import logging
+import os
 import time
 from typing import List, Optional
 
@@ -48,19 +49,25 @@ class _ProviderOptions(type):
         NOTE: "rdx" takes librdx's GEMM only for batches of at least `_PackedEncoder.GEMM_MIN_TOKENS` tokens, and that constant's
         measured default NEVER triggers (the kernel is slower than the BLAS library at every token count measured):
         with the default, gemm="rdx" still runs the BLAS path everywhere. Lower it (`provider._packed.GEMM_MIN_TOKENS = 33` after
-        load(), or RDX_ENC_GEMM_MIN=33 in the environment) to actually run the kernel."""
+        load(), or RDX_ENC_GEMM_MIN=33 in the environment) to actually run the kernel.
+      colbert_head = None | path | (weight [dim][hidden], bias [dim]): BGE-M3's per-token head, which `embed_tokens` /
+        `embed_tokens_device` need. None looks for `colbert_linear.pt` (a state dict with `weight` and `bias`) in the resolved local model
+        directory at load(); a path names such a file. Without a head those two methods raise; everything else works as before."""
 
-    def __call__(cls, *args, gemm: Optional[str] = None, **kwargs):
+    def __call__(cls, *args, gemm: Optional[str] = None, colbert_head=None, **kwargs):
         if gemm not in (None, "blas", "rdx"):
             raise ValueError(f"EmbeddingProvider: gemm must be 'blas' or 'rdx', not {gemm!r}")
         obj = super().__call__(*args, **kwargs)
         obj.gemm = gemm
+        obj.colbert_head = colbert_head
         return obj
 
 
 class EmbeddingProvider(metaclass=_ProviderOptions):
     """Dense BGE-M3 embeddings, L2-normalised (unit rows), d = 1024. Calls are synchronous and thread-safe."""
 
+    colbert_head = None                    # BGE-M3's per-token head: None (colbert_linear.pt of the local model directory), a path, or (weight, bias)
+    _colbert = None                        # the loaded head: (weight fp32 [dim][hidden], bias fp32 [dim]) on the model's device
     gemm: Optional[str] = None             # None: "blas", unless the developer knob RDX_ENC_GEMM says otherwise where the fused forward runs
 
     def __init__(self, model_name: str = DEFAULT_MODEL, device: str = DEFAULT_DEVICE, dtype: torch.dtype = DEFAULT_DTYPE,
@@ -119,6 +126,7 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
             self._tokenizer = lambda texts: tok(texts, padding=True, truncation=True, max_length=MAX_SEQ_LENGTH, return_tensors="pt")
         self._model = model.to(device=self.device, dtype=self.dtype).eval()
         self._dims = int(self._model.config.hidden_size)
+        self._colbert = self._load_colbert_head(None if self.model_name.startswith("random-init:") else local)
         self._packed = None
         if self.packed_forward:
             try:
@@ -145,6 +153,7 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
                 self._packed = None
                 self._pinned.clear()
                 self._model = None
+                self._colbert = None
                 self._tokenizer = None
                 if str(self.device).startswith("cuda"):
                     import gc
@@ -314,6 +323,76 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
             if self._model is None:
                 self.load()
             return self._encode_raw([t[:TRUNCATE_CHARS] if len(t) > TRUNCATE_CHARS else t for t in texts])
+
+    # ---- BGE-M3's per-token (ColBERT) output: rag_dpo_amd/late_interaction.py scores it, DESIGN.md §29 ---------------------------------
+    COLBERT_FILE = "colbert_linear.pt"
+
+    def _load_colbert_head(self, local_dir: Optional[str]):
+        """-> (weight fp32 [dim][hidden], bias fp32 [dim]) on the model's device, or None when there is no head"""
+        head = self.colbert_head
+        if head is None:
+            path = os.path.join(local_dir, self.COLBERT_FILE) if local_dir else None
+            if path is None or not os.path.exists(path):
+                return None
+            head = path
+        if isinstance(head, (str, os.PathLike)):
+            sd = torch.load(head, map_location="cpu", weights_only=True)
+            head = (sd["weight"], sd["bias"])
+        w, b = (torch.as_tensor(np.asarray(t) if not isinstance(t, torch.Tensor) else t).detach().to(device=self.device, dtype=torch.float32).contiguous()
+                for t in head)
+        if w.dim() != 2 or w.shape[1] != self._dims or b.shape != (w.shape[0],):
+            raise ValueError(f"EmbeddingProvider: colbert_head must be weight [dim][{self._dims}] and bias [dim], got {tuple(w.shape)} and {tuple(b.shape)}")
+        return w, b
+
+    @torch.no_grad()
+    def _token_states(self, texts: List[str]):
+        """-> (fp32 [sum(len_i - 1)][hidden] last hidden states of every token but <s>, </s> included, in input order; int64 [B + 1] offsets)"""
+        parts, counts = [], []
+        for a in range(0, len(texts), self.batch_size):
+            enc = self._tokenizer(list(texts[a: a + self.batch_size]))
+            ids, att = enc["input_ids"], enc["attention_mask"]
+            lens = att.numpy().sum(axis=1).astype(np.int64)
+            first = np.cumsum(lens) - lens
+            if self._packed is not None:
+                h = self._packed.tokens(ids, lens, self._h2d)                     # [T][hidden], text b at first[b]
+                keep = np.setdiff1d(np.arange(int(lens.sum()), dtype=np.int64), first)
+            else:
+                w = int(lens.max())
+                feed = {"input_ids": self._h2d("ids", ids[:, :w]), "attention_mask": self._h2d("att", att[:, :w])}
+                feed.update({k: self._h2d(k, v[:, :w]) for k, v in enc.items() if k not in ("input_ids", "attention_mask")})
+                h = self._model(**feed).last_hidden_state.to(torch.float32).reshape(-1, self._dims)
+                cols = np.arange(w, dtype=np.int64)[None, :]
+                keep = np.flatnonzero(((cols >= 1) & (cols < lens[:, None])).reshape(-1)).astype(np.int64)
+            parts.append(h.index_select(0, self._h2d("tok_keep", torch.from_numpy(keep))))
+            counts.append(lens - 1)
+        off = np.zeros(len(texts) + 1, dtype=np.int64)
+        np.cumsum(np.concatenate(counts), out=off[1:])
+        return (parts[0] if len(parts) == 1 else torch.cat(parts)), off
+
+    def embed_tokens_device(self, texts: List[str]):
+        """BGE-M3's per-token vectors of every text: the last hidden states of all tokens but <s> (</s> included) through
+        the ColBERT head, each row divided by max(|row|, 1e-12) in fp32 and rounded once to fp16. -> (vecs fp16 [sum(T_i - 1)][dim] on
+        the model's device, off int64 numpy [B + 1]): text i's vectors are rows [off[i], off[i + 1]), input order, never empty. Same
+        truncation as embed(). The head and the normalisation are torch operations."""
+        with self._lock:
+            if self._model is None:
+                self.load()
+            if self._colbert is None:
+                raise RuntimeError(f"EmbeddingProvider: no ColBERT head — pass colbert_head=, or put {self.COLBERT_FILE} (a state dict with "
+                                   "'weight' and 'bias') into the local model directory")
+            w, b = self._colbert
+            if not texts:
+                return torch.empty((0, w.shape[0]), dtype=torch.float16, device=self.device), np.zeros(1, dtype=np.int64)
+            h, off = self._token_states([t[:TRUNCATE_CHARS] if len(t) > TRUNCATE_CHARS else t for t in texts])
+            v = torch.nn.functional.linear(h, w, b)
+            v = v / v.norm(dim=1, keepdim=True).clamp_min(1e-12)
+            return v.to(torch.float16), off
+
+    def embed_tokens(self, texts: List[str]) -> List[np.ndarray]:
+        """embed_tokens_device() as a list of fp16 numpy matrices [T_i - 1][dim]"""
+        v, off = self.embed_tokens_device(texts)
+        v = v.cpu().numpy()
+        return [v[off[i]:off[i + 1]] for i in range(len(texts))]
 
     def _normalize(self, raw: torch.Tensor) -> np.ndarray:
         """K1 on the device (librdx); x / max(|x|, 1e-12), the arithmetic the index uses for corpus rows"""

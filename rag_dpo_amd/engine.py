@@ -509,6 +509,34 @@ def space_distances(kind: int, queries, vecs, scale_exp: int, allow_bits, first_
                                     ctypes.c_void_p(out.data_ptr() + 4 * col0), out.shape[1], ctypes.c_void_p(HipIndex._raw_stream(dev))))
 
 
+# ---- late-interaction scoring (include/rdx.h rdx_maxsim_f16; rag_dpo_amd/late_interaction.py drives it) ---------------------------
+def maxsim(q_vecs, q_off, d_vecs, slot_start, slot_len, pair_q, pair_slot, scores=None, n_pairs: Optional[int] = None):
+    """score(q, d) = (1 / n_q) sum_i max_j q_i . d_j for the listed pairs -> fp32 [n_pairs] on the device (written into `scores` when
+    given). q_vecs fp16 [sum n_q][dim], d_vecs fp16 [rows][dim], slot_start i64 / slot_len i32 [slots], pair_q i32 / pair_slot i64
+    [pairs]: contiguous torch tensors on one CUDA device; q_off int32 [nq + 1]: a PINNED host tensor, left unchanged until the stream
+    has passed the call. Enqueued on the current torch stream, nothing synchronised."""
+    import torch
+    lib = L.load(require_gpu=True)
+    _want_tensors("maxsim takes contiguous torch tensors of the documented types on one CUDA device", None, (q_vecs, torch.float16),
+                  (d_vecs, torch.float16), (slot_start, torch.int64), (slot_len, torch.int32), (pair_q, torch.int32), (pair_slot, torch.int64))
+    if q_vecs.dim() != 2 or d_vecs.dim() != 2 or q_vecs.shape[1] != d_vecs.shape[1] or slot_start.shape != slot_len.shape or pair_q.shape != pair_slot.shape:
+        raise ValueError("maxsim: q_vecs / d_vecs must be [rows][dim] of one dim, the slot tables and the pair lists of one length each")
+    if q_off.is_cuda or q_off.dtype != torch.int32 or not q_off.is_contiguous() or q_off.numel() < 2:
+        raise ValueError("maxsim: q_off must be a contiguous int32 host tensor [nq + 1]")
+    dev = q_vecs.device
+    n = int(pair_q.numel()) if n_pairs is None else int(n_pairs)
+    if scores is None:
+        scores = torch.empty((n,), dtype=torch.float32, device=dev)
+    _want_tensors("maxsim: scores must be a contiguous fp32 tensor on the vectors' device", dev.index, (scores, torch.float32))
+    if n > pair_q.numel() or n > scores.numel() or int(q_off[-1]) > q_vecs.shape[0]:
+        raise ValueError("maxsim: n_pairs exceeds the pair lists or the scores, or q_off reaches past q_vecs")
+    p = _ptr
+    L.check(lib.rdx_maxsim_f16(dev.index or 0, p(q_vecs), p(q_off), int(q_off.numel()) - 1, p(d_vecs), int(d_vecs.shape[0]), p(slot_start),
+                               p(slot_len), int(slot_start.numel()), p(pair_q), p(pair_slot), n, int(q_vecs.shape[1]), p(scores),
+                               ctypes.c_void_p(HipIndex._raw_stream(dev))))
+    return scores
+
+
 # ---- grouped search (include/rdx.h rdx_group_select / rdx_index_group_fill; rag_dpo_amd/groups.py drives them) -----------------
 def group_select(scores, rows, counts, row_group, group_off, n_groups: int, group_size: int):
     """ranked lists (scores f32 / rows i64 [nq][k], counts i32 [nq]) and the tables row_group i32 [n_rows], group_off i64 [groups + 1],

@@ -7,6 +7,7 @@ import logging
 import os
 import zlib
 from collections import namedtuple
+from types import SimpleNamespace
 from typing import List, NamedTuple, Optional
 
 import numpy as np
@@ -534,3 +535,31 @@ class _PackedEncoder:
             dev = {n: to_dev(n, t) for n, t in host.items()}
             out = self._fused_forward(plan, *(unpack(dev["pk_blob"]) if small else (dev[n] for n in self._ORDER)), dev.get("pk_qb"))
         return out[:B] if small else out
+
+    @torch.no_grad()
+    def tokens(self, ids: torch.Tensor, lens: np.ndarray, to_dev) -> torch.Tensor:
+        """cls()'s arguments -> fp32 [T][hidden] final hidden states of ALL packed tokens (text b's are rows first[b] .. first[b] +
+        lens[b], <s> first): what BGE-M3's per-token (ColBERT) head reads. The eager packed forward with every row selected behind the
+        last attention; no graph replay, no canonical shape, and not the one-question stage kernels (their last layer is written
+        for the <s> rows). cls() and the plans it takes are untouched."""
+        B, S = int(ids.shape[0]), int(ids.shape[1])
+        lens = np.asarray(lens, dtype=np.int64)
+        T = int(lens.sum())
+        first = np.cumsum(lens) - lens
+        row = np.repeat(np.arange(B, dtype=np.int64), lens)
+        col = np.arange(T, dtype=np.int64) - np.repeat(first, lens)
+        ids_packed = np.ascontiguousarray(ids.numpy()[row, col])
+        every = np.arange(T, dtype=np.int64)
+        caps = SimpleNamespace(fused=self.fused, small_linear=self.small_linear, small_stage=False, gemm_shapes=self.gemm_shapes)
+        knobs = SimpleNamespace(graphs=False, **{k: getattr(self, k) for k in (
+            "gemm", "GEMM_MIN_TOKENS", "SMALL_TOKENS", "FUSED_MAX_TOKENS", "long_attention", "MFMA_MIN_TOKENS", "SMALL_TEXTS", "STAGE_TOKENS",
+            "SMALL_TOKEN_GRANULE", "large_graphs", "LARGE_TOKEN_GRANULE")})
+        plan = plan_forward(caps, knobs, B, T, int(lens.max()), int(((lens + 63) // 64).sum()))
+        if plan.layout == "padded":
+            return self._padded_forward(plan, ids_packed, row, col, every, lens, B, S, to_dev)
+        tok, pos, _, tok_first, tok_len = canonical(ids_packed, col, first, lens, T, B, self.pad)
+        host = dict(zip(self._ORDER, map(torch.from_numpy, (tok, pos, every, tok_first, tok_len))))
+        if plan.work_units:
+            host["pk_qb"] = self._query_blocks(first, lens)
+        dev = {n: to_dev(n, t) for n, t in host.items()}
+        return self._fused_forward(plan, *(dev[n] for n in self._ORDER), dev.get("pk_qb"))
