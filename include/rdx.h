@@ -527,6 +527,52 @@ int rdx_bm25_search_filtered(rdx_bm25* h, const int64_t* term_offsets, const int
                              const uint32_t* filter_sets, int32_t n_filters, const int32_t* query_filter, double* out_score,
                              int64_t* out_row, int32_t* out_count, int space, void* stream);
 
+/* BGE-M3 lexical weights (learned-sparse retrieval) ---------------------------------------------- */
+/* BGE-M3's sparse output (rag_dpo_amd/lexical.py states the definition once, in numpy): a text is a set of terms
+ * (sub-word token id, fp16 weight), one per distinct id, and
+ *     score(question, chunk) = 0.0, then for each question term t in ascending id that the chunk has too:
+ *                              score = score + (double)wq[t] * (double)wd[t]
+ * in float64. The product of two fp16 values is exact in float64, so only the order of the additions rounds, and it is fixed.
+ *
+ * rdx_lex_reduce: the tokens of n_texts texts -> their terms. tok int32 [n_tok] and w fp32 [n_tok] are device memory: text i's tokens are
+ * [off[i], off[i + 1]); off int64 [n_texts + 1] is a shape array (the rule above: PINNED HOST memory, read by the library to check the
+ * call and by the kernel; device or pageable memory is RDX_ERR_INVALID), off[0] >= 0, non-decreasing, off[n_texts] <= n_tok, 0 to
+ * RDX_LEX_MAX_TOKENS tokens per text. The rule per token: the weight is rounded once to fp16, round to nearest even; the token is
+ * dropped when the fp16 value is not finite and above 0, or when its id is one of skip_ids[0 .. n_skip) (host pointer, 0 <= n_skip <=
+ * RDX_LEX_MAX_SKIP); of the tokens left, one entry per distinct id with the largest weight, ascending by id.
+ * Out (device memory): text i's terms are out_tok int32 / out_w uint16 (fp16 bits) [off[i] .. off[i] + out_n[i]); nothing else of
+ * [off[i], off[i + 1]) is written and nothing outside it; out_n int32 [n_texts]. A text with an id outside [0, vocab) gets out_n = -1
+ * and writes nothing; its neighbours are unaffected. Invalid scalars or an invalid off return RDX_ERR_INVALID before anything is
+ * launched. Enqueued on `stream`, nothing synchronised, nothing allocated, no float atomics; one workgroup per text
+ * (csrc/lex_kernel.hpp); a text's output does not depend on its position or on the other texts of the call. */
+#define RDX_LEX_MAX_TOKENS 8192
+#define RDX_LEX_MAX_SKIP 8
+int rdx_lex_reduce(int device, const int32_t* tok, const float* w, int64_t n_tok, const int64_t* off, int64_t n_texts, int vocab,
+                   const int32_t* skip_ids, int n_skip, int32_t* out_tok, uint16_t* out_w, int32_t* out_n, void* stream);
+typedef struct rdx_lex rdx_lex; /* opaque: one index of lexical weights resident in one GPU's HBM; immutable, rebuilt to refresh */
+/* All pointers are host pointers; they are copied. CSR by term over the tokenizer's vocabulary (n_terms = 250 002 for BGE-M3): term
+ * t's postings are [post_off[t], post_off[t+1]), post_off[0] = 0, rows strictly ascending and < n_rows (refused otherwise: a term
+ * occurs at most once per row, which is what fixes the order of a row's additions), post_w the fp16 bits of the weight, finite and
+ * above 0 (bits in [0x0001, 0x7BFF]; anything else is refused). row_group / n_groups as in rdx_bm25_create. 6 bytes per posting plus
+ * 8 (n_terms + 1) for the offsets, the per-term tile directory and 4 n_rows for the groups. */
+int rdx_lex_create(int device, int64_t n_rows, int64_t n_terms, const int64_t* post_off, const int32_t* post_row,
+                   const uint16_t* post_w, const int32_t* row_group, int32_t n_groups, rdx_lex** out);
+int rdx_lex_destroy(rdx_lex* h);
+/* nq questions: question q's terms are term_ids / term_w [term_offsets[q] .. term_offsets[q+1]) (term_offsets[0] = 0), term_w the fp16
+ * bits of the weights. The filters are rdx_bm25_search_filtered's: a table filter_sets [n_filters][(n_groups + 31) / 32] and
+ * query_filter[q] in [-1, n_filters), -1 = no filter (query_filter is required when nq > 0; n_filters = 0 with every entry -1 is an
+ * unfiltered search). Result per question: the rows with score > 0 whose group passes, score descending, ties by ascending row, the
+ * first k. Out as rdx_bm25_search: out_score f64 [nq][k], out_row int64 [nq][k], out_count [nq]; slots after the count hold 0 and -1.
+ * RDX_ERR_INVALID before anything is enqueued (the outputs are not written), the message naming the query and the value: term ids of
+ * a question not strictly ascending, or outside [0, n_terms); a weight that is not finite and above 0; more than 4096 terms in a
+ * question; k outside [1, 4096]; a query_filter entry outside [-1, n_filters); space other than RDX_HOST. A question without terms, or
+ * whose terms have no postings, returns count 0. Runs on `stream` (NULL = the index's own stream) and is complete on return.
+ * The scorer is rdx_bm25_search's with the question's weight in place of idf[t] and the posting's weight in place of the Okapi
+ * quotient (csrc/bm25_kernel.hpp k_lex_score); the merge is the same kernel. */
+int rdx_lex_search(rdx_lex* h, const int64_t* term_offsets, const int32_t* term_ids, const uint16_t* term_w, int64_t nq, int k,
+                   const uint32_t* filter_sets, int32_t n_filters, const int32_t* query_filter, double* out_score, int64_t* out_row,
+                   int32_t* out_count, int space, void* stream);
+
 /* Building a BM25 index from text ----------------------------------------------------------- */
 /* The tokenizer of the reference's indexes (tokenize_french, bm25_index.py:38-49) and the vocabulary and postings that
  * BM25Okapi(corpus_tokens) derives from its tokens (bm25_index.py:124, :234), on the GPU: rag_dpo_amd/bm25_build.py uploads the

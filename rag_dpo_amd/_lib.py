@@ -39,6 +39,7 @@ TOPIC_MAX_N, TOPIC_MAX_TOPICS, TOPIC_MAX_TAGS, TOPIC_MAX_DIM = 1024, 32, 64, 409
 RERANK_BATCH_MAX_ROWS, RERANK_BATCH_MAX_QUESTIONS, RERANK_SELECT_WIDTHS = 1 << 20, 65535, (64, 256, 1024)
 # include/rdx.h RDX_MAXSIM_MAX_*: rdx_maxsim_f16's limits (token vectors per question and per slot, dim, pairs per call)
 MAXSIM_MAX_Q_TOKENS, MAXSIM_MAX_SLOT_TOKENS, MAXSIM_MAX_DIM, MAXSIM_MAX_PAIRS = 256, 8192, 1024, 1 << 20
+LEX_MAX_TOKENS, LEX_MAX_SKIP = 8192, 8   # include/rdx.h RDX_LEX_MAX_*: rdx_lex_reduce's limits (tokens per text, skip ids)
 
 
 def topic_pair(topic: int, tag: int, exact: bool) -> int:
@@ -134,6 +135,10 @@ SYMBOLS = {
     "rdx_bm25_destroy": (_i, [_vp]),
     "rdx_bm25_search": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "rdx_bm25_search_filtered": (_i, [_vp, _vp, _vp, _i64, _i, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _i, _vp]),
+    "rdx_lex_reduce": (_i, [_i, _vp, _vp, _i64, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "rdx_lex_create": (_i, [_i, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.POINTER(_vp)]),
+    "rdx_lex_destroy": (_i, [_vp]),
+    "rdx_lex_search": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _i, _vp]),
     "rdx_bm25_build_create": (_i, [_i, _i64, ctypes.c_uint64, ctypes.POINTER(_vp)]),
     "rdx_bm25_build_destroy": (_i, [_vp]),
     "rdx_bm25_build_tokenize": (_i, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),

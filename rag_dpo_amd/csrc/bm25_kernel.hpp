@@ -24,6 +24,10 @@
 // (an FMA rounds once where numpy rounds twice), and f64 division is correctly rounded by default. Within one term no
 // two postings share a row, so the accumulation needs no atomics; terms are separated by a barrier, which keeps the
 // per-row order of additions = query order. The result is bit-identical to the numpy loop.
+//
+// The index of BGE-M3 lexical weights (rdx_lex, rdx_bm25.hip; rag_dpo_amd/lexical.py) has the same layout with
+//   post_w    uint16 [nnz]   the fp16 bits of the term's weight in that row (finite, > 0)
+// in place of post_tf, and neither idf nor denom: k_lex_score runs the same core with the LexWeights scorer, and k_bm25_merge serves both.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -97,21 +101,43 @@ __device__ __forceinline__ int bm25_pow2_at_least(int n) {
     return p;
 }
 
-// Grid (doc tile, query of this chunk). Writes the tile's top-min(k, passing) rows, UNORDERED, to
+// What a query term and a posting are worth: the two scorers that share bm25_score_core. `term(...)` is the factor of the query's term
+// at position pos (an index into q_terms) with id t; `posting(...)` is the value of posting p, which lies in row r. The core adds
+// term * posting to the row, one IEEE double product and one sum, in query order. The tables are the core's own (restrict) arguments,
+// handed to the scorer: post_val is post_tf or post_w; idf and denom are BM25's, q_w the lexical search's (the others are null).
+struct Bm25Okapi {   // rank_bm25: idf[t] * ((tf * 2.5) / (tf + denom[r]))
+    static __device__ __forceinline__ double term(const double* idf, const uint16_t*, int64_t, int t) { return idf[t]; }
+    static __device__ __forceinline__ double posting(const uint16_t* post_tf, const double* denom, int64_t p, int32_t r) {
+#pragma clang fp contract(off)
+        const double tf = (double)post_tf[p];
+        return (tf * 2.5) / (tf + denom[r]);
+    }
+};
+
+__device__ __forceinline__ double lex_half_bits(uint16_t bits) { return (double)__builtin_bit_cast(_Float16, bits); }
+
+struct LexWeights {   // BGE-M3 lexical weights (rag_dpo_amd/lexical.py): float64(wq) * float64(wd), both fp16 bits, the product exact
+    static __device__ __forceinline__ double term(const double*, const uint16_t* q_w, int64_t pos, int) { return lex_half_bits(q_w[pos]); }
+    static __device__ __forceinline__ double posting(const uint16_t* post_w, const double*, int64_t p, int32_t) { return lex_half_bits(post_w[p]); }
+};
+
+// The scorer of one (doc tile, query of this chunk) block. Writes the tile's top-min(k, passing) rows, UNORDERED, to
 // part_{score,row}[q][tile][0..count) and the count to part_count[q][tile]; rows are global. q_off and query_filter are the
 // chunk's own: entry 0 belongs to the chunk's first query.
-__global__ __launch_bounds__(BM25_THREADS) void k_bm25_score(
+template <class Policy>
+__device__ __forceinline__ void bm25_score_core(
     const int64_t* __restrict__ dir_off, const int32_t* __restrict__ dir_tile, const int64_t* __restrict__ dir_pos,
-    const int32_t* __restrict__ post_row, const uint16_t* __restrict__ post_tf, const double* __restrict__ idf,
+    const int32_t* __restrict__ post_row, const uint16_t* __restrict__ post_val, const double* __restrict__ idf,
     const double* __restrict__ denom, const int32_t* __restrict__ row_group, const uint32_t* __restrict__ filter_sets,
-    int allow_words, const int32_t* __restrict__ query_filter, const int64_t* __restrict__ q_off, const int32_t* __restrict__ q_terms, int64_t n_rows, int k, int n_tiles,
+    int allow_words, const int32_t* __restrict__ query_filter, const int64_t* __restrict__ q_off, const int32_t* __restrict__ q_terms,
+    const uint16_t* __restrict__ q_w, int64_t n_rows, int k, int n_tiles,
     double* __restrict__ part_score, int32_t* __restrict__ part_row, int32_t* __restrict__ part_count) {
 #pragma clang fp contract(off)
     __shared__ double acc[BM25_TILE];          // per-row scores; after phase C's compaction: the candidates' scores
     __shared__ int32_t crow[BM25_TILE];        // the candidates' rows (phase C, when the tile has more than k)
     __shared__ int64_t t_beg[BM25_TERM_CHUNK];
     __shared__ int32_t t_len[BM25_TERM_CHUNK];
-    __shared__ double t_idf[BM25_TERM_CHUNK];
+    __shared__ double t_idf[BM25_TERM_CHUNK];  // the terms' factors (Policy::term)
     __shared__ int s_wave[BM25_THREADS / 64];
     __shared__ int s_any;
 
@@ -147,7 +173,7 @@ __global__ __launch_bounds__(BM25_THREADS) void k_bm25_score(
             }
             t_beg[tid] = b;
             t_len[tid] = len;
-            t_idf[tid] = idf[t];
+            t_idf[tid] = Policy::term(idf, q_w, c0 + tid, t);
         }
         __syncthreads();
         // phase B: terms in query order; a barrier after each term that touched the tile
@@ -158,8 +184,7 @@ __global__ __launch_bounds__(BM25_THREADS) void k_bm25_score(
             const double w = t_idf[j];
             for (int p = tid; p < len; p += BM25_THREADS) {
                 const int32_t r = post_row[b + p];
-                const double tf = (double)post_tf[b + p];
-                const double x = (tf * 2.5) / (tf + denom[r]);
+                const double x = Policy::posting(post_val, denom, b + p, r);
                 const int l = r - (int)base;
                 acc[l] = acc[l] + w * x;
             }
@@ -224,6 +249,30 @@ __global__ __launch_bounds__(BM25_THREADS) void k_bm25_score(
         part_row[part * k + i] = crow[i];
     }
     if (tid == 0) part_count[part] = k;
+}
+
+// Grid (doc tile, query of this chunk): bm25_score_core with rank_bm25's scorer.
+__global__ __launch_bounds__(BM25_THREADS) void k_bm25_score(
+    const int64_t* __restrict__ dir_off, const int32_t* __restrict__ dir_tile, const int64_t* __restrict__ dir_pos,
+    const int32_t* __restrict__ post_row, const uint16_t* __restrict__ post_tf, const double* __restrict__ idf,
+    const double* __restrict__ denom, const int32_t* __restrict__ row_group, const uint32_t* __restrict__ filter_sets,
+    int allow_words, const int32_t* __restrict__ query_filter, const int64_t* __restrict__ q_off, const int32_t* __restrict__ q_terms, int64_t n_rows, int k, int n_tiles,
+    double* __restrict__ part_score, int32_t* __restrict__ part_row, int32_t* __restrict__ part_count) {
+    bm25_score_core<Bm25Okapi>(dir_off, dir_tile, dir_pos, post_row, post_tf, idf, denom, row_group, filter_sets, allow_words, query_filter,
+                               q_off, q_terms, nullptr, n_rows, k, n_tiles, part_score, part_row, part_count);
+}
+
+// The same grid and scheme for an index of lexical weights (rdx_lex_search): the term's factor is the question's weight q_w at that
+// position, a posting is worth its stored weight. A term occurs at most once per row (rdx_lex_create checks it), so the per-term
+// barrier keeps the additions of a row in the order of the question's terms, which rdx_lex_search requires to be ascending ids.
+__global__ __launch_bounds__(BM25_THREADS) void k_lex_score(
+    const int64_t* __restrict__ dir_off, const int32_t* __restrict__ dir_tile, const int64_t* __restrict__ dir_pos,
+    const int32_t* __restrict__ post_row, const uint16_t* __restrict__ post_w, const int32_t* __restrict__ row_group,
+    const uint32_t* __restrict__ filter_sets, int allow_words, const int32_t* __restrict__ query_filter, const int64_t* __restrict__ q_off,
+    const int32_t* __restrict__ q_terms, const uint16_t* __restrict__ q_w, int64_t n_rows, int k, int n_tiles,
+    double* __restrict__ part_score, int32_t* __restrict__ part_row, int32_t* __restrict__ part_count) {
+    bm25_score_core<LexWeights>(dir_off, dir_tile, dir_pos, post_row, post_w, nullptr, nullptr, row_group, filter_sets, allow_words,
+                                query_filter, q_off, q_terms, q_w, n_rows, k, n_tiles, part_score, part_row, part_count);
 }
 
 // One block per query: the global top-k of the tiles' partials in result order. Candidates stream through an LDS buffer;

@@ -1,4 +1,6 @@
-// rdx_bm25.hip — BM25 sparse retrieval (rdx_bm25_*) of include/rdx.h.
+// rdx_bm25.hip — sparse retrieval over a CSR-by-term index: BM25 (rdx_bm25_*) and BGE-M3 lexical weights (rdx_lex_create / _destroy /
+// _search) of include/rdx.h. Both indexes are one host core (SparseIndex: create, upload, search) and one merge; they differ in what a
+// posting holds and in the scoring kernel (bm25_kernel.hpp k_bm25_score / k_lex_score).
 #include "rdx_host.hpp"
 
 #include <cmath>
@@ -10,55 +12,61 @@
 using namespace rdx;
 
 // ------------------------------------------------------------------------------------------------
-// BM25 sparse retrieval (bm25_kernel.hpp): an immutable index, rebuilt to refresh, as in the reference
+// the immutable index both kinds share: rebuilt to refresh, as in the reference
 // ------------------------------------------------------------------------------------------------
-struct rdx_bm25 {
+struct SparseIndex {
     int device = 0;
     int64_t n_rows = 0, n_terms = 0, nnz = 0, n_dir = 0;
     int32_t n_groups = 0;
     int n_tiles = 0;
-    DevBuf post_off, post_row, post_tf, idf, denom, dir_off, dir_tile, dir_pos, group;
+    DevBuf post_off, post_row, post_val, dir_off, dir_tile, dir_pos, group;   // post_val: uint16 per posting (tf, or fp16 weight bits)
+    DevBuf idf, denom;             // BM25's own tables (empty in a lexical index): here, so that one destructor frees everything on `device`
     DevBuf in, part, out;          // per search: packed inputs, tile partials, packed outputs
     PinnedBuf h_in, h_out;
     hipStream_t own_stream = nullptr;
     std::mutex mu;                 // searches are synchronous: one at a time owns the buffers
+    ~SparseIndex() {
+        (void)hipSetDevice(device);
+        if (own_stream) {
+            (void)hipStreamSynchronize(own_stream);
+            (void)hipStreamDestroy(own_stream);
+        }
+    }
 };
+
+struct rdx_bm25 : SparseIndex {};
+
+struct rdx_lex : SparseIndex {};
 
 static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
-extern "C" int rdx_bm25_create(int device, int64_t n_rows, int64_t n_terms, const int64_t* post_off, const int32_t* post_row,
-                               const uint16_t* post_tf, const double* idf, const double* row_denom, const int32_t* row_group,
-                               int32_t n_groups, rdx_bm25** out) {
-    if (!out) return fail(RDX_ERR_INVALID, "rdx_bm25_create: null out pointer");
-    *out = nullptr;
-    if (n_rows < 1 || n_rows > INT32_MAX - BM25_TILE || n_terms < 0 || n_terms >= INT32_MAX)
-        return fail(RDX_ERR_INVALID, "rdx_bm25_create: n_rows must be in [1, 2^31 - 4097] and n_terms in [0, 2^31 - 1)");
-    if (!post_off || !row_denom || (n_terms > 0 && !idf)) return fail(RDX_ERR_INVALID, "rdx_bm25_create: null pointer");
-    if ((row_group == nullptr) != (n_groups == 0) || n_groups < 0)
-        return fail(RDX_ERR_INVALID, "rdx_bm25_create: row_group and n_groups > 0 go together");
+static int sparse_upload(DevBuf& d, const void* src, size_t bytes) {
+    RDX_TRY(d.ensure(std::max(bytes, (size_t)16)));
+    if (bytes) HIP_TRY(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+    return RDX_OK;
+}
+
+// The checks and the uploads of a create that both kinds share: the shape, the groups, the postings (term_ok(t) and value_ok(v) are the
+// kind's own checks of a term and of a posting's 16-bit value; bad_value names a refused one) and the per-term tile directory, built in
+// the same pass. `me` = "rdx_x_create".
+template <class TermOk, class ValueOk>
+static int sparse_create(const std::string& me, SparseIndex* h, int device, int64_t n_rows, int64_t n_terms, const int64_t* post_off,
+                         const int32_t* post_row, const uint16_t* post_val, const int32_t* row_group, int32_t n_groups, TermOk term_ok,
+                         ValueOk value_ok, const char* bad_value) {
     const int64_t nnz = post_off[n_terms];
-    if (post_off[0] != 0 || nnz < 0) return fail(RDX_ERR_INVALID, "rdx_bm25_create: post_off must start at 0");
-    if (nnz > 0 && (!post_row || !post_tf)) return fail(RDX_ERR_INVALID, "rdx_bm25_create: null postings");
-    for (int64_t r = 0; r < n_rows; ++r) {
-        if (!(row_denom[r] > 0.0) || !std::isfinite(row_denom[r]))
-            return fail(RDX_ERR_INVALID, "rdx_bm25_create: row_denom[" + std::to_string(r) + "] is not a positive finite number");
-        if (row_group && (row_group[r] < 0 || row_group[r] >= n_groups))
-            return fail(RDX_ERR_INVALID, "rdx_bm25_create: row_group[" + std::to_string(r) + "] out of [0, n_groups)");
-    }
-    // validate the postings and build the per-term tile directory (one pass)
     std::vector<int64_t> h_dir_off((size_t)n_terms + 1), h_dir_pos;
     std::vector<int32_t> h_dir_tile;
     for (int64_t t = 0; t < n_terms; ++t) {
-        if (!std::isfinite(idf[t])) return fail(RDX_ERR_INVALID, "rdx_bm25_create: idf[" + std::to_string(t) + "] is not finite");
+        RDX_TRY(term_ok(t));
         const int64_t b = post_off[t], e = post_off[t + 1];
-        if (e < b || e > nnz) return fail(RDX_ERR_INVALID, "rdx_bm25_create: post_off must be non-decreasing up to post_off[n_terms]");
+        if (e < b || e > nnz) return fail(RDX_ERR_INVALID, me + ": post_off must be non-decreasing up to post_off[n_terms]");
         h_dir_off[(size_t)t] = (int64_t)h_dir_tile.size();
         int32_t prev_row = -1, prev_tile = -1;
         for (int64_t p = b; p < e; ++p) {
             const int32_t r = post_row[p];
             if (r <= prev_row || r >= n_rows)
-                return fail(RDX_ERR_INVALID, "rdx_bm25_create: term " + std::to_string(t) + ": rows must be strictly ascending and < n_rows");
-            if (post_tf[p] == 0) return fail(RDX_ERR_INVALID, "rdx_bm25_create: term " + std::to_string(t) + ": tf 0 in a posting");
+                return fail(RDX_ERR_INVALID, me + ": term " + std::to_string(t) + ": rows must be strictly ascending and < n_rows");
+            if (!value_ok(post_val[p])) return fail(RDX_ERR_INVALID, me + ": term " + std::to_string(t) + ": " + bad_value);
             prev_row = r;
             const int32_t tile = r / BM25_TILE;
             if (tile != prev_tile) {
@@ -72,7 +80,6 @@ extern "C" int rdx_bm25_create(int device, int64_t n_rows, int64_t n_terms, cons
     h_dir_pos.push_back(nnz);
 
     HIP_TRY(hipSetDevice(device));
-    rdx_bm25* h = new rdx_bm25();
     h->device = device;
     h->n_rows = n_rows;
     h->n_terms = n_terms;
@@ -80,27 +87,55 @@ extern "C" int rdx_bm25_create(int device, int64_t n_rows, int64_t n_terms, cons
     h->n_dir = (int64_t)h_dir_tile.size();
     h->n_groups = n_groups;
     h->n_tiles = (int)((n_rows + BM25_TILE - 1) / BM25_TILE);
-    auto up = [&](DevBuf& d, const void* src, size_t bytes) -> int {
-        RDX_TRY(d.ensure(std::max(bytes, (size_t)16)));
-        if (bytes) HIP_TRY(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
-        return RDX_OK;
-    };
-    int rc = RDX_OK;
-    if (rc == RDX_OK) rc = up(h->post_off, post_off, (size_t)(n_terms + 1) * 8);
-    if (rc == RDX_OK) rc = up(h->post_row, post_row, (size_t)nnz * 4);
-    if (rc == RDX_OK) rc = up(h->post_tf, post_tf, (size_t)nnz * 2);
-    if (rc == RDX_OK) rc = up(h->idf, idf, (size_t)n_terms * 8);
-    if (rc == RDX_OK) rc = up(h->denom, row_denom, (size_t)n_rows * 8);
-    if (rc == RDX_OK) rc = up(h->dir_off, h_dir_off.data(), h_dir_off.size() * 8);
-    if (rc == RDX_OK) rc = up(h->dir_tile, h_dir_tile.data(), h_dir_tile.size() * 4);
-    if (rc == RDX_OK) rc = up(h->dir_pos, h_dir_pos.data(), h_dir_pos.size() * 8);
-    if (rc == RDX_OK && row_group) rc = up(h->group, row_group, (size_t)n_rows * 4);
-    if (rc == RDX_OK) {
-        hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-        if (e != hipSuccess) rc = fail(RDX_ERR_HIP, std::string("rdx_bm25_create: ") + hipGetErrorString(e));
-    }
+    RDX_TRY(sparse_upload(h->post_off, post_off, (size_t)(n_terms + 1) * 8));
+    RDX_TRY(sparse_upload(h->post_row, post_row, (size_t)nnz * 4));
+    RDX_TRY(sparse_upload(h->post_val, post_val, (size_t)nnz * 2));
+    RDX_TRY(sparse_upload(h->dir_off, h_dir_off.data(), h_dir_off.size() * 8));
+    RDX_TRY(sparse_upload(h->dir_tile, h_dir_tile.data(), h_dir_tile.size() * 4));
+    RDX_TRY(sparse_upload(h->dir_pos, h_dir_pos.data(), h_dir_pos.size() * 8));
+    if (row_group) RDX_TRY(sparse_upload(h->group, row_group, (size_t)n_rows * 4));
+    hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
+    if (e != hipSuccess) return fail(RDX_ERR_HIP, me + ": " + hipGetErrorString(e));
+    return RDX_OK;
+}
+
+// the argument checks every create starts with; tables_missing: a table of the kind's own is a null pointer
+static int sparse_create_args(const std::string& me, int64_t n_rows, int64_t n_terms, const int64_t* post_off, const int32_t* post_row,
+                              const uint16_t* post_val, const int32_t* row_group, int32_t n_groups, bool tables_missing) {
+    if (n_rows < 1 || n_rows > INT32_MAX - BM25_TILE || n_terms < 0 || n_terms >= INT32_MAX)
+        return fail(RDX_ERR_INVALID, me + ": n_rows must be in [1, 2^31 - 4097] and n_terms in [0, 2^31 - 1)");
+    if (!post_off || tables_missing) return fail(RDX_ERR_INVALID, me + ": null pointer");
+    if ((row_group == nullptr) != (n_groups == 0) || n_groups < 0)
+        return fail(RDX_ERR_INVALID, me + ": row_group and n_groups > 0 go together");
+    const int64_t nnz = post_off[n_terms];
+    if (post_off[0] != 0 || nnz < 0) return fail(RDX_ERR_INVALID, me + ": post_off must start at 0");
+    if (nnz > 0 && (!post_row || !post_val)) return fail(RDX_ERR_INVALID, me + ": null postings");
+    if (row_group)
+        for (int64_t r = 0; r < n_rows; ++r)
+            if (row_group[r] < 0 || row_group[r] >= n_groups)
+                return fail(RDX_ERR_INVALID, me + ": row_group[" + std::to_string(r) + "] out of [0, n_groups)");
+    return RDX_OK;
+}
+
+extern "C" int rdx_bm25_create(int device, int64_t n_rows, int64_t n_terms, const int64_t* post_off, const int32_t* post_row,
+                               const uint16_t* post_tf, const double* idf, const double* row_denom, const int32_t* row_group,
+                               int32_t n_groups, rdx_bm25** out) {
+    const std::string me = "rdx_bm25_create";
+    if (!out) return fail(RDX_ERR_INVALID, me + ": null out pointer");
+    *out = nullptr;
+    RDX_TRY(sparse_create_args(me, n_rows, n_terms, post_off, post_row, post_tf, row_group, n_groups, !row_denom || (n_terms > 0 && !idf)));
+    for (int64_t r = 0; r < n_rows; ++r)
+        if (!(row_denom[r] > 0.0) || !std::isfinite(row_denom[r]))
+            return fail(RDX_ERR_INVALID, me + ": row_denom[" + std::to_string(r) + "] is not a positive finite number");
+    rdx_bm25* h = new rdx_bm25();
+    int rc = sparse_create(
+        me, h, device, n_rows, n_terms, post_off, post_row, post_tf, row_group, n_groups,
+        [&](int64_t t) { return std::isfinite(idf[t]) ? RDX_OK : fail(RDX_ERR_INVALID, me + ": idf[" + std::to_string(t) + "] is not finite"); },
+        [](uint16_t tf) { return tf != 0; }, "tf 0 in a posting");
+    if (rc == RDX_OK) rc = sparse_upload(h->idf, idf, (size_t)n_terms * 8);
+    if (rc == RDX_OK) rc = sparse_upload(h->denom, row_denom, (size_t)n_rows * 8);
     if (rc != RDX_OK) {
-        rdx_bm25_destroy(h);
+        delete h;
         return rc;
     }
     *out = h;
@@ -108,21 +143,44 @@ extern "C" int rdx_bm25_create(int device, int64_t n_rows, int64_t n_terms, cons
 }
 
 extern "C" int rdx_bm25_destroy(rdx_bm25* h) {
-    if (!h) return RDX_OK;
-    (void)hipSetDevice(h->device);
-    if (h->own_stream) {
-        (void)hipStreamSynchronize(h->own_stream);
-        (void)hipStreamDestroy(h->own_stream);
-    }
     delete h;
     return RDX_OK;
 }
 
-// The one search behind rdx_bm25_search and rdx_bm25_search_filtered (`who` names the caller in messages). The filters are a table
-// of n_filters bitsets and, per query, its row of the table or -1; query_filter == nullptr gives every query `uniform_filter`.
-static int bm25_search(const char* who, rdx_bm25* h, const int64_t* term_offsets, const int32_t* term_ids, int64_t nq, int k,
-                       const uint32_t* filter_sets, int32_t n_filters, const int32_t* query_filter, int32_t uniform_filter,
-                       double* out_score, int64_t* out_row, int32_t* out_count, int space, void* stream) {
+// fp16 bits of a finite value > 0: sign clear, not zero, exponent below the infinities'
+static bool lex_weight_ok(uint16_t bits) { return bits >= 1 && bits <= 0x7BFF; }
+
+extern "C" int rdx_lex_create(int device, int64_t n_rows, int64_t n_terms, const int64_t* post_off, const int32_t* post_row,
+                              const uint16_t* post_w, const int32_t* row_group, int32_t n_groups, rdx_lex** out) {
+    const std::string me = "rdx_lex_create";
+    if (!out) return fail(RDX_ERR_INVALID, me + ": null out pointer");
+    *out = nullptr;
+    RDX_TRY(sparse_create_args(me, n_rows, n_terms, post_off, post_row, post_w, row_group, n_groups, false));
+    rdx_lex* h = new rdx_lex();
+    const int rc = sparse_create(me, h, device, n_rows, n_terms, post_off, post_row, post_w, row_group, n_groups,
+                                 [](int64_t) { return RDX_OK; }, lex_weight_ok, "a weight that is not a finite fp16 above 0");
+    if (rc != RDX_OK) {
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return RDX_OK;
+}
+
+extern "C" int rdx_lex_destroy(rdx_lex* h) {
+    delete h;
+    return RDX_OK;
+}
+
+// The one search behind rdx_bm25_search, rdx_bm25_search_filtered and rdx_lex_search (`who` names the caller in messages). The filters
+// are a table of n_filters bitsets and, per query, its row of the table or -1; query_filter == nullptr gives every query
+// `uniform_filter`. term_w != nullptr is the lexical search: a weight per term travels behind the ids, the ids of a query must be
+// strictly ascending and the weights finite and positive. `score(nqc, ...)` launches the kind's scoring kernel for one chunk of queries.
+template <class Score>
+static int sparse_search(const char* who, SparseIndex* h, const int64_t* term_offsets, const int32_t* term_ids, const uint16_t* term_w,
+                         bool weighted, int64_t nq, int k, const uint32_t* filter_sets, int32_t n_filters, const int32_t* query_filter,
+                         int32_t uniform_filter, double* out_score, int64_t* out_row, int32_t* out_count, int space, void* stream,
+                         Score score) {
     const std::string me = who;
     if (!h) return fail(RDX_ERR_INVALID, me + ": null index");
     if (nq < 0 || k < 1 || k > BM25_MAX_K)
@@ -154,31 +212,44 @@ static int bm25_search(const char* who, rdx_bm25* h, const int64_t* term_offsets
                                              std::to_string(BM25_MAX_TERMS) + ")");
     }
     const int64_t n_ids = off[nq];
-    if (n_ids > 0 && !term_ids) return fail(RDX_ERR_INVALID, me + ": null term_ids");
+    if (n_ids > 0 && (!term_ids || (weighted && !term_w))) return fail(RDX_ERR_INVALID, me + (term_ids ? ": null term_w" : ": null term_ids"));
     for (int64_t i = 0; i < n_ids; ++i)
         if (term_ids[i] < 0 || term_ids[i] >= h->n_terms)
             return fail(RDX_ERR_INVALID, me + ": term id " + std::to_string(term_ids[i]) + " out of [0, " +
                                              std::to_string(h->n_terms) + ")");
+    if (weighted)
+        for (int64_t q = 0; q < nq; ++q)
+            for (int64_t i = off[q]; i < off[q + 1]; ++i) {
+                if (i > off[q] && term_ids[i] <= term_ids[i - 1])
+                    return fail(RDX_ERR_INVALID, me + ": query " + std::to_string(q) + ": term id " + std::to_string(term_ids[i]) + " after " +
+                                                     std::to_string(term_ids[i - 1]) + " (the ids of a query must be strictly ascending)");
+                if (!lex_weight_ok(term_w[i]))
+                    return fail(RDX_ERR_INVALID, me + ": query " + std::to_string(q) + ": term id " + std::to_string(term_ids[i]) +
+                                                     " has weight bits " + std::to_string(term_w[i]) + " (not a finite fp16 above 0)");
+            }
 
-    // one upload through pinned staging: offsets | ids | query_filter | filter sets
+    // one upload through pinned staging: offsets | ids | weights (the lexical search's) | query_filter | filter sets
     const size_t allow_words = (size_t)(h->n_groups + 31) / 32;
     const size_t b_off = align16((size_t)(nq + 1) * 8), b_ids = align16((size_t)std::max<int64_t>(n_ids, 1) * 4);
+    const size_t b_w = weighted ? align16((size_t)std::max<int64_t>(n_ids, 1) * 2) : 0;
     const size_t b_qf = align16((size_t)nq * 4), n_set_bytes = (size_t)n_filters * allow_words * 4;
-    const size_t b_in = b_off + b_ids + b_qf + align16(n_set_bytes);
+    const size_t b_in = b_off + b_ids + b_w + b_qf + align16(n_set_bytes);
     RDX_TRY(h->h_in.ensure(b_in));
     RDX_TRY(h->in.ensure(b_in));
     char* hp = (char*)h->h_in.p;
     std::memcpy(hp, term_offsets, (size_t)(nq + 1) * 8);
     if (n_ids) std::memcpy(hp + b_off, term_ids, (size_t)n_ids * 4);
-    int32_t* h_qf = (int32_t*)(hp + b_off + b_ids);
+    if (weighted && n_ids) std::memcpy(hp + b_off + b_ids, term_w, (size_t)n_ids * 2);
+    int32_t* h_qf = (int32_t*)(hp + b_off + b_ids + b_w);
     if (query_filter) std::memcpy(h_qf, query_filter, (size_t)nq * 4);
     else std::fill(h_qf, h_qf + nq, uniform_filter);
-    if (n_set_bytes) std::memcpy(hp + b_off + b_ids + b_qf, filter_sets, n_set_bytes);
+    if (n_set_bytes) std::memcpy(hp + b_off + b_ids + b_w + b_qf, filter_sets, n_set_bytes);
     HIP_TRY(hipMemcpyAsync(h->in.p, hp, b_in, hipMemcpyHostToDevice, st));
     const int64_t* d_off = (const int64_t*)h->in.p;
     const int32_t* d_ids = (const int32_t*)((char*)h->in.p + b_off);
-    const int32_t* d_qf = (const int32_t*)((char*)h->in.p + b_off + b_ids);
-    const uint32_t* d_sets = (const uint32_t*)((char*)h->in.p + b_off + b_ids + b_qf);   // never read when n_filters = 0
+    const uint16_t* d_w = (const uint16_t*)((char*)h->in.p + b_off + b_ids);                 // never read when not weighted
+    const int32_t* d_qf = (const int32_t*)((char*)h->in.p + b_off + b_ids + b_w);
+    const uint32_t* d_sets = (const uint32_t*)((char*)h->in.p + b_off + b_ids + b_w + b_qf);   // never read when n_filters = 0
     const size_t b_score = align16((size_t)nq * k * 8), b_row = align16((size_t)nq * k * 8), b_cnt = align16((size_t)nq * 4);
     RDX_TRY(h->out.ensure(b_score + b_row + b_cnt));
     double* o_score = (double*)h->out.p;
@@ -194,10 +265,7 @@ static int bm25_search(const char* who, rdx_bm25* h, const int64_t* term_offsets
     int32_t* p_cnt = (int32_t*)((char*)h->part.p + c_score + c_row);
     for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
         const int nqc = (int)std::min<int64_t>(chunk, nq - q0);
-        hipLaunchKernelGGL(k_bm25_score, dim3(h->n_tiles, nqc), dim3(BM25_THREADS), 0, st, h->dir_off.as<int64_t>(),
-                           h->dir_tile.as<int32_t>(), h->dir_pos.as<int64_t>(), h->post_row.as<int32_t>(), h->post_tf.as<uint16_t>(),
-                           h->idf.as<double>(), h->denom.as<double>(), h->group.as<int32_t>(), d_sets, (int)allow_words,
-                           d_qf + q0, d_off + q0, d_ids, h->n_rows, k, h->n_tiles, p_score, p_row, p_cnt);
+        score(nqc, st, d_sets, (int)allow_words, d_qf + q0, d_off + q0, d_ids, d_w, k, p_score, p_row, p_cnt);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_bm25_merge, dim3(nqc), dim3(BM25_MERGE_THREADS), 0, st, p_score, p_row, p_cnt, h->n_tiles, k,
                            o_score + (size_t)q0 * k, o_row + (size_t)q0 * k, o_cnt + q0);
@@ -214,6 +282,21 @@ static int bm25_search(const char* who, rdx_bm25* h, const int64_t* term_offsets
     return RDX_OK;
 }
 
+static int bm25_search(const char* who, rdx_bm25* h, const int64_t* term_offsets, const int32_t* term_ids, int64_t nq, int k,
+                       const uint32_t* filter_sets, int32_t n_filters, const int32_t* query_filter, int32_t uniform_filter,
+                       double* out_score, int64_t* out_row, int32_t* out_count, int space, void* stream) {
+    return sparse_search(who, h, term_offsets, term_ids, nullptr, false, nq, k, filter_sets, n_filters, query_filter, uniform_filter,
+                         out_score, out_row, out_count, space, stream,
+                         [h](int nqc, hipStream_t st, const uint32_t* d_sets, int allow_words, const int32_t* d_qf, const int64_t* d_off,
+                             const int32_t* d_ids, const uint16_t*, int k, double* p_score, int32_t* p_row, int32_t* p_cnt) {
+                             hipLaunchKernelGGL(k_bm25_score, dim3(h->n_tiles, nqc), dim3(BM25_THREADS), 0, st, h->dir_off.as<int64_t>(),
+                                                h->dir_tile.as<int32_t>(), h->dir_pos.as<int64_t>(), h->post_row.as<int32_t>(),
+                                                h->post_val.as<uint16_t>(), h->idf.as<double>(), h->denom.as<double>(),
+                                                h->group.as<int32_t>(), d_sets, allow_words, d_qf, d_off, d_ids, h->n_rows, k, h->n_tiles,
+                                                p_score, p_row, p_cnt);
+                         });
+}
+
 extern "C" int rdx_bm25_search(rdx_bm25* h, const int64_t* term_offsets, const int32_t* term_ids, int64_t nq, int k,
                                const uint32_t* allow_groups, double* out_score, int64_t* out_row, int32_t* out_count, int space,
                                void* stream) {
@@ -228,4 +311,19 @@ extern "C" int rdx_bm25_search_filtered(rdx_bm25* h, const int64_t* term_offsets
     if (nq > 0 && !query_filter) return fail(RDX_ERR_INVALID, "rdx_bm25_search_filtered: null query_filter with nq = " + std::to_string(nq));
     return bm25_search("rdx_bm25_search_filtered", h, term_offsets, term_ids, nq, k, filter_sets, n_filters, query_filter, -1,
                        out_score, out_row, out_count, space, stream);
+}
+
+extern "C" int rdx_lex_search(rdx_lex* h, const int64_t* term_offsets, const int32_t* term_ids, const uint16_t* term_w, int64_t nq, int k,
+                              const uint32_t* filter_sets, int32_t n_filters, const int32_t* query_filter, double* out_score,
+                              int64_t* out_row, int32_t* out_count, int space, void* stream) {
+    if (nq > 0 && !query_filter) return fail(RDX_ERR_INVALID, "rdx_lex_search: null query_filter with nq = " + std::to_string(nq));
+    return sparse_search("rdx_lex_search", h, term_offsets, term_ids, term_w, true, nq, k, filter_sets, n_filters, query_filter, -1,
+                         out_score, out_row, out_count, space, stream,
+                         [h](int nqc, hipStream_t st, const uint32_t* d_sets, int allow_words, const int32_t* d_qf, const int64_t* d_off,
+                             const int32_t* d_ids, const uint16_t* d_w, int k, double* p_score, int32_t* p_row, int32_t* p_cnt) {
+                             hipLaunchKernelGGL(k_lex_score, dim3(h->n_tiles, nqc), dim3(BM25_THREADS), 0, st, h->dir_off.as<int64_t>(),
+                                                h->dir_tile.as<int32_t>(), h->dir_pos.as<int64_t>(), h->post_row.as<int32_t>(),
+                                                h->post_val.as<uint16_t>(), h->group.as<int32_t>(), d_sets, allow_words, d_qf, d_off, d_ids,
+                                                d_w, h->n_rows, k, h->n_tiles, p_score, p_row, p_cnt);
+                         });
 }

@@ -52,14 +52,18 @@ class _ProviderOptions(type):
         load(), or RDX_ENC_GEMM_MIN=33 in the environment) to actually run the kernel.
       colbert_head = None | path | (weight [dim][hidden], bias [dim]): BGE-M3's per-token head, which `embed_tokens` /
         `embed_tokens_device` need. None looks for `colbert_linear.pt` (a state dict with `weight` and `bias`) in the resolved local model
-        directory at load(); a path names such a file. Without a head those two methods raise; everything else works as before."""
+        directory at load(); a path names such a file. Without a head those two methods raise; everything else works as before.
+      sparse_head = None | path | (weight [1][hidden], bias [1]): BGE-M3's lexical-weight head, which `embed_lexical` /
+        `embed_lexical_device` need (rag_dpo_amd/lexical.py). None looks for `sparse_linear.pt` in the resolved local
+        model directory, loaded exactly as the ColBERT head's file is. Without a head those two methods raise; everything else is unchanged."""
 
-    def __call__(cls, *args, gemm: Optional[str] = None, colbert_head=None, **kwargs):
+    def __call__(cls, *args, gemm: Optional[str] = None, colbert_head=None, sparse_head=None, **kwargs):
         if gemm not in (None, "blas", "rdx"):
             raise ValueError(f"EmbeddingProvider: gemm must be 'blas' or 'rdx', not {gemm!r}")
         obj = super().__call__(*args, **kwargs)
         obj.gemm = gemm
         obj.colbert_head = colbert_head
+        obj.sparse_head = sparse_head
         return obj
 
 
@@ -68,6 +72,9 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
 
     colbert_head = None                    # BGE-M3's per-token head: None (colbert_linear.pt of the local model directory), a path, or (weight, bias)
     _colbert = None                        # the loaded head: (weight fp32 [dim][hidden], bias fp32 [dim]) on the model's device
+    sparse_head = None                     # BGE-M3's lexical-weight head: None (sparse_linear.pt of the local model directory), a path, or (weight, bias)
+    _sparse = None                         # the loaded head: (weight fp32 [1][hidden], bias fp32 [1]) on the model's device
+    _lexical_special = (0, 1, 2, 3)        # the ids that never become terms (lexical.special_ids of the tokenizer; XLM-R's by default)
     gemm: Optional[str] = None             # None: "blas", unless the developer knob RDX_ENC_GEMM says otherwise where the fused forward runs
 
     def __init__(self, model_name: str = DEFAULT_MODEL, device: str = DEFAULT_DEVICE, dtype: torch.dtype = DEFAULT_DTYPE,
@@ -124,9 +131,12 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
             model = XLMRobertaModel.from_pretrained(local, add_pooling_layer=False, local_files_only=True)
             tok = AutoTokenizer.from_pretrained(local, local_files_only=True)
             self._tokenizer = lambda texts: tok(texts, padding=True, truncation=True, max_length=MAX_SEQ_LENGTH, return_tensors="pt")
+            from .lexical import special_ids
+            self._lexical_special = special_ids(tok)
         self._model = model.to(device=self.device, dtype=self.dtype).eval()
         self._dims = int(self._model.config.hidden_size)
         self._colbert = self._load_colbert_head(None if self.model_name.startswith("random-init:") else local)
+        self._sparse = self._load_sparse_head(None if self.model_name.startswith("random-init:") else local)
         self._packed = None
         if self.packed_forward:
             try:
@@ -154,6 +164,7 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
                 self._pinned.clear()
                 self._model = None
                 self._colbert = None
+                self._sparse = None
                 self._tokenizer = None
                 if str(self.device).startswith("cuda"):
                     import gc
@@ -329,9 +340,18 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
 
     def _load_colbert_head(self, local_dir: Optional[str]):
         """-> (weight fp32 [dim][hidden], bias fp32 [dim]) on the model's device, or None when there is no head"""
-        head = self.colbert_head
+        head = self._load_head(self.colbert_head, local_dir, self.COLBERT_FILE)
         if head is None:
-            path = os.path.join(local_dir, self.COLBERT_FILE) if local_dir else None
+            return None
+        w, b = head
+        if w.dim() != 2 or w.shape[1] != self._dims or b.shape != (w.shape[0],):
+            raise ValueError(f"EmbeddingProvider: colbert_head must be weight [dim][{self._dims}] and bias [dim], got {tuple(w.shape)} and {tuple(b.shape)}")
+        return w, b
+
+    def _load_head(self, head, local_dir: Optional[str], file_name: str):
+        """a head given as None (file_name in local_dir, if there), a path or (weight, bias) -> (weight, bias) fp32 on the model's device, or None"""
+        if head is None:
+            path = os.path.join(local_dir, file_name) if local_dir else None
             if path is None or not os.path.exists(path):
                 return None
             head = path
@@ -340,14 +360,13 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
             head = (sd["weight"], sd["bias"])
         w, b = (torch.as_tensor(np.asarray(t) if not isinstance(t, torch.Tensor) else t).detach().to(device=self.device, dtype=torch.float32).contiguous()
                 for t in head)
-        if w.dim() != 2 or w.shape[1] != self._dims or b.shape != (w.shape[0],):
-            raise ValueError(f"EmbeddingProvider: colbert_head must be weight [dim][{self._dims}] and bias [dim], got {tuple(w.shape)} and {tuple(b.shape)}")
         return w, b
 
     @torch.no_grad()
-    def _token_states(self, texts: List[str]):
-        """-> (fp32 [sum(len_i - 1)][hidden] last hidden states of every token but <s>, </s> included, in input order; int64 [B + 1] offsets)"""
-        parts, counts = [], []
+    def _token_states(self, texts: List[str], with_ids: bool = False):
+        """-> (fp32 [sum(len_i - 1)][hidden] last hidden states of every token but <s>, </s> included, in input order; int64 [B + 1] offsets);
+        with_ids: and, third, the token ids of those rows (int32 numpy, on the host)"""
+        parts, counts, tok = [], [], []
         for a in range(0, len(texts), self.batch_size):
             enc = self._tokenizer(list(texts[a: a + self.batch_size]))
             ids, att = enc["input_ids"], enc["attention_mask"]
@@ -356,6 +375,7 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
             if self._packed is not None:
                 h = self._packed.tokens(ids, lens, self._h2d)                     # [T][hidden], text b at first[b]
                 keep = np.setdiff1d(np.arange(int(lens.sum()), dtype=np.int64), first)
+                flat_ids = ids.numpy()[np.arange(ids.shape[1])[None, :] < lens[:, None]] if with_ids else None   # the packed order: text by text
             else:
                 w = int(lens.max())
                 feed = {"input_ids": self._h2d("ids", ids[:, :w]), "attention_mask": self._h2d("att", att[:, :w])}
@@ -363,11 +383,15 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
                 h = self._model(**feed).last_hidden_state.to(torch.float32).reshape(-1, self._dims)
                 cols = np.arange(w, dtype=np.int64)[None, :]
                 keep = np.flatnonzero(((cols >= 1) & (cols < lens[:, None])).reshape(-1)).astype(np.int64)
+                flat_ids = ids.numpy()[:, :w].reshape(-1) if with_ids else None
             parts.append(h.index_select(0, self._h2d("tok_keep", torch.from_numpy(keep))))
             counts.append(lens - 1)
+            if with_ids:
+                tok.append(flat_ids[keep].astype(np.int32))
         off = np.zeros(len(texts) + 1, dtype=np.int64)
         np.cumsum(np.concatenate(counts), out=off[1:])
-        return (parts[0] if len(parts) == 1 else torch.cat(parts)), off
+        h = parts[0] if len(parts) == 1 else torch.cat(parts)
+        return (h, off, np.concatenate(tok)) if with_ids else (h, off)
 
     def embed_tokens_device(self, texts: List[str]):
         """BGE-M3's per-token vectors of every text: the last hidden states of all tokens but <s> (</s> included) through
@@ -393,6 +417,76 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
         v, off = self.embed_tokens_device(texts)
         v = v.cpu().numpy()
         return [v[off[i]:off[i + 1]] for i in range(len(texts))]
+
+    # ---- BGE-M3's lexical weights: rag_dpo_amd/lexical.py states the rule and searches them, DESIGN.md §30 ----------------------------------
+    SPARSE_FILE = "sparse_linear.pt"
+
+    def _load_sparse_head(self, local_dir: Optional[str]):
+        """-> (weight fp32 [1][hidden], bias fp32 [1]) on the model's device, or None when there is no head"""
+        head = self._load_head(self.sparse_head, local_dir, self.SPARSE_FILE)
+        if head is None:
+            return None
+        w, b = head
+        if tuple(w.shape) != (1, self._dims) or tuple(b.shape) != (1,):
+            raise ValueError(f"EmbeddingProvider: sparse_head must be weight [1][{self._dims}] and bias [1], got {tuple(w.shape)} and {tuple(b.shape)}")
+        return w, b
+
+    @property
+    def lexical_vocab(self) -> int:
+        """the size of the id space the lexical terms live in: the model's vocabulary"""
+        if self._model is None:
+            self.load()
+        return int(self._model.config.vocab_size)
+
+    @property
+    def lexical_special_ids(self) -> tuple:
+        if self._model is None:
+            self.load()
+        return tuple(self._lexical_special)
+
+    @torch.no_grad()
+    def embed_lexical_device(self, texts: List[str]):
+        """BGE-M3's lexical weights of every text: relu(h . W + b) in fp32 (torch operations) for every token but <s>,
+        reduced to the text's terms by the rule of rag_dpo_amd/lexical.py — on a GPU provider by librdx's k_lex_reduce (rdx_lex_reduce),
+        on a CPU provider by the numpy model. -> (term_ids int32 [nnz], term_w fp16 [nnz]) on the model's device and off int64 numpy
+        [B + 1]: text i's terms are [off[i], off[i + 1]), ascending ids, possibly none; input order; embed()'s truncation."""
+        from . import lexical
+        with self._lock:
+            if self._model is None:
+                self.load()
+            if self._sparse is None:
+                raise RuntimeError(f"EmbeddingProvider: no lexical-weight head — pass sparse_head=, or put {self.SPARSE_FILE} (a state dict with "
+                                   "'weight' [1][hidden] and 'bias' [1]) into the local model directory")
+            if not texts:
+                return (torch.empty((0,), dtype=torch.int32, device=self.device), torch.empty((0,), dtype=torch.float16, device=self.device),
+                        np.zeros(1, dtype=np.int64))
+            h, off, tok = self._token_states([t[:TRUNCATE_CHARS] if len(t) > TRUNCATE_CHARS else t for t in texts], with_ids=True)
+            w = torch.relu(torch.nn.functional.linear(h, *self._sparse)).reshape(-1).contiguous()
+            vocab, skip = int(self._model.config.vocab_size), tuple(self._lexical_special)
+            if not w.is_cuda:
+                ids, ws, out_off = lexical.terms_of_texts_model(tok, w.numpy(), off, vocab, skip)
+                return torch.from_numpy(ids).to(self.device), torch.from_numpy(ws).to(self.device), out_off
+            from . import engine
+            n, T = len(texts), int(off[-1])
+            tok_d = self._h2d("lex_tok", torch.from_numpy(tok))
+            off_p = torch.from_numpy(off).pin_memory()           # read by the library and by the kernel; alive until the copy of out_n below has drained the stream
+            out_tok, out_w, out_n = engine.lex_reduce(tok_d, w, off_p, vocab, skip)
+            counts = out_n.cpu().numpy().astype(np.int64)
+            if (counts < 0).any():
+                raise ValueError(f"text {int(np.flatnonzero(counts < 0)[0])}: a token id outside [0, {vocab})")
+            # the per-text runs packed into one CSR
+            text_of = torch.repeat_interleave(torch.arange(n, device=w.device), torch.from_numpy(np.diff(off)).to(w.device), output_size=T)
+            pos = torch.arange(T, device=w.device) - torch.from_numpy(off[:-1].copy()).to(w.device)[text_of]
+            keep = pos < out_n[text_of]
+            out_off = np.zeros(n + 1, dtype=np.int64)
+            np.cumsum(counts, out=out_off[1:])
+            return out_tok[keep], out_w[keep], out_off
+
+    def embed_lexical(self, texts: List[str]) -> List[dict]:
+        """embed_lexical_device() as a list of {token_id: weight} (the fp16 weights as Python floats)"""
+        ids, ws, off = self.embed_lexical_device(texts)
+        ids, ws = ids.cpu().numpy().tolist(), ws.cpu().numpy().astype(np.float64).tolist()
+        return [dict(zip(ids[off[i]:off[i + 1]], ws[off[i]:off[i + 1]])) for i in range(len(texts))]
 
     def _normalize(self, raw: torch.Tensor) -> np.ndarray:
         """K1 on the device (librdx); x / max(|x|, 1e-12), the arithmetic the index uses for corpus rows"""

@@ -537,6 +537,33 @@ def maxsim(q_vecs, q_off, d_vecs, slot_start, slot_len, pair_q, pair_slot, score
     return scores
 
 
+# ---- BGE-M3 lexical weights (include/rdx.h rdx_lex_reduce; rag_dpo_amd/lexical.py states the rule) ------------------------------
+def lex_reduce(tok, w, off, vocab: int, skip_ids, out_tok=None, out_w=None, out_n=None):
+    """the terms of every text: tok int32 [T], w fp32 [T] contiguous torch tensors on one CUDA device, off int64 [n + 1] a PINNED host
+    tensor (left unchanged until the stream has passed the call) -> (out_tok int32 [T], out_w fp16 [T], out_n int32 [n]) on the device:
+    text i's terms are out_*[off[i] : off[i] + out_n[i]], out_n[i] = -1 for a text with an id outside [0, vocab). Enqueued on the
+    current torch stream, nothing synchronised. Outputs that are given are written in place (nothing of them is touched elsewhere)."""
+    import torch
+    lib = L.load(require_gpu=True)
+    _want_tensors("lex_reduce takes contiguous torch tensors (tok int32, w fp32) on one CUDA device", None, (tok, torch.int32), (w, torch.float32))
+    if tok.dim() != 1 or tok.shape != w.shape:
+        raise ValueError("lex_reduce: tok and w must be [T] of one length")
+    if off.is_cuda or off.dtype != torch.int64 or not off.is_contiguous() or off.dim() != 1 or off.numel() < 1:
+        raise ValueError("lex_reduce: off must be a contiguous int64 host tensor [n + 1]")
+    dev, n, T = tok.device, int(off.numel()) - 1, int(tok.numel())
+    out_tok = torch.empty((T,), dtype=torch.int32, device=dev) if out_tok is None else out_tok
+    out_w = torch.empty((T,), dtype=torch.float16, device=dev) if out_w is None else out_w
+    out_n = torch.empty((n,), dtype=torch.int32, device=dev) if out_n is None else out_n
+    _want_tensors("lex_reduce: the outputs must be contiguous (int32, fp16, int32) tensors on the tokens' device", dev.index,
+                  (out_tok, torch.int32), (out_w, torch.float16), (out_n, torch.int32))
+    if out_tok.numel() < T or out_w.numel() < T or out_n.numel() < n:
+        raise ValueError("lex_reduce: an output is shorter than its input")
+    skip = np.ascontiguousarray(list(skip_ids), dtype=np.int32)
+    L.check(lib.rdx_lex_reduce(dev.index or 0, _ptr(tok), _ptr(w), T, _ptr(off), n, int(vocab), _np_ptr(skip), int(skip.shape[0]),
+                               _ptr(out_tok), _ptr(out_w), _ptr(out_n), ctypes.c_void_p(HipIndex._raw_stream(dev))))
+    return out_tok, out_w, out_n
+
+
 # ---- grouped search (include/rdx.h rdx_group_select / rdx_index_group_fill; rag_dpo_amd/groups.py drives them) -----------------
 def group_select(scores, rows, counts, row_group, group_off, n_groups: int, group_size: int):
     """ranked lists (scores f32 / rows i64 [nq][k], counts i32 [nq]) and the tables row_group i32 [n_rows], group_off i64 [groups + 1],
