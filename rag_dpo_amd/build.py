@@ -28,10 +28,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librdx.so")
 RESOURCES = os.path.join(HERE, "librdx.resources.json")
-# one translation unit per subsystem, each compiled as a job of its own; whatever lies in csrc/ is a source and is hashed
+# one translation unit per subsystem (the dense index: its core, what is derived from it, the merge), each compiled as a job of its own;
+# whatever lies in csrc/ is a source and is hashed. No kernel is defined in two units (csrc/rdx_index.hpp "ONE DEFINITION")
 SOURCES = sorted(os.path.basename(f) for f in glob.glob(os.path.join(CSRC, "*.hip")))
 HEADERS = sorted(os.path.basename(f) for f in glob.glob(os.path.join(CSRC, "*.hpp"))) + ["../../include/rdx.h"]
-CORE = "rdx_index.hip"        # the dense index and its search: the only unit that may hold a k_scan kernel
+CORE = "rdx_index.hip"        # the dense index's core (lifecycle, writes, the search pipeline, the threshold search, the grouped fill): the only
+                              # unit that may hold a k_scan kernel; rdx_derived.hip and rdx_merge.hip are built on it and beside it
 CHECKERS = ["isa_check.py"]   # part of the recorded hash: a library is only "fresh" if it passed THIS version of the ISA check
 
 
@@ -142,7 +144,7 @@ SPILL_CHECKS = (
                "the batched reranker kernels (rerank_batch_kernel.hpp) spill or were not found — refused:"),
     SpillCheck(("k_space",), 5, "required", True, True, "the ip / l2 space kernels (space_kernel.hpp) spill or were not found — refused:"),
     SpillCheck(("k_fuse",), 1, "required", True, True, "the rank fusion kernel (fuse_kernel.hpp) spills or was not found — refused:"),
-    SpillCheck(("k_group",), 0, "ignored", True, True, "the grouped search's kernels (group_kernel.hpp, k_rows.hpp k_group_fill) spill — refused:"),
+    SpillCheck(("k_group",), 0, "ignored", True, True, "the grouped search's kernels (group_kernel.hpp, group_fill_kernel.hpp) spill — refused:"),
     SpillCheck(("k_mmr",), 0, "ignored", True, True, "the diversity-aware selection kernel (mmr_kernel.hpp) spills — refused:"),
     SpillCheck(("k_range",), 0, "ignored", True, True, "the threshold search's kernels (range_kernel.hpp) spill — refused:"),
     SpillCheck(("k_dup",), 0, "ignored", True, True, "the near-duplicate clustering kernels (dup_kernel.hpp) spill — refused:"),

@@ -5,7 +5,7 @@
 //                     neighbourhood is listed (total <= list_cap) are united with their list; the others are "heavy" and are handed on
 //   k_dup_link_dense  heavy rows: united with every row whose dense exact score (k_exact_scores / k_exact_scores_reg) reaches t
 //   k_dup_labels      label[r] = root of r, in a launch of its own
-// Included by rdx_index.hip only. The union-find itself is dup_union.hpp (HIP-free, rehearsed on the host); its termination argument
+// Included by rdx_derived.hip only. The union-find itself is dup_union.hpp (HIP-free, rehearsed on the host); its termination argument
 // is written there. No kernel here waits for another thread, workgroup or launch.
 //
 // Visibility. Workgroups on different XCDs link the same components at the same time. The XCDs' L2s are not coherent with each other

@@ -3,8 +3,7 @@
 //   k_facet_count   the masked histogram of the row -> code table: counts per code, rows without a code, allowed rows
 //   k_facet_top     one query's table row -> its best `limit` cells by (count descending, code ascending)
 // The rows in range are counted by the counting variants of the threshold search's last stages (range_kernel.hpp, <FACET = true>);
-// what they and k_facet_count share is facet_count.hpp. Included by rdx_index.hip only, behind the search's kernels (the code object
-// lists those in the order it always did). Every result is an integer: sums of ones in any order, so nothing here depends on a
+// what they and k_facet_count share is facet_count.hpp. Included by rdx_derived.hip only. Every result is an integer: sums of ones in any order, so nothing here depends on a
 // schedule. No kernel waits for another thread, workgroup or launch.
 #pragma once
 #include "facet_count.hpp"

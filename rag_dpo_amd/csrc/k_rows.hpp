@@ -1,53 +1,12 @@
 // k_rows.hpp — row-wise kernels: K1 L2-normalise (+ tiled fp16 scan copy), gather, exact scoring, dense select.
 // One 64-lane wavefront owns one row: 16 B/lane coalesced loads, fp64 lane-order sums (oracle/rdx_oracle.c: see exact_dot4).
 // The exact path's kernels take ExactParams / SelectParams; RowIds and TopkOut are the value types they share with k_refine.
+// The device helpers without a kernel (MasterView, exact_score, rank_and_write, ...) are rows_core.hpp, which other units include too;
+// this header holds kernels, so rdx_index.hip alone includes it.
 #pragma once
-#include "rdx_common.hpp"
+#include "rows_core.hpp"
 
 namespace rdx {
-
-// The exact copy of the corpus rows ("master"): what the exact re-score K4, the exact scan K5 and get() read.
-//   default : fp32 [cap][dim], the L2-normalised rows (4 B/element)
-//   compact : the raw bf16 rows as delivered (2 B/element) + each row's divisor den = max(|x|_2, 1e-12) as a double. The
-//             normalised element y_i = (float)((double)x_i / den) is RECOMPUTED wherever it is needed — the same two
-//             operands and the same operation K1 uses, hence the same bits (oracle/rdx_oracle.c) — instead of being stored:
-//             a bf16 corpus (BASELINE config 5) then costs 2 (raw) + 2 (fp16 scan copy) B/element instead of 4 + 2.
-struct MasterView {
-    float* f32;
-    uint16_t* raw16;
-    double* den;
-};
-struct MasterRow {
-    const float4* p32;
-    const ushort4* p16;
-    double den;
-    __device__ __forceinline__ float4 operator[](int g) const {
-        if (p32) return p32[g];
-        const ushort4 u = p16[g];
-        float4 y;
-        y.x = (float)((double)__uint_as_float((uint32_t)u.x << 16) / den);
-        y.y = (float)((double)__uint_as_float((uint32_t)u.y << 16) / den);
-        y.z = (float)((double)__uint_as_float((uint32_t)u.z << 16) / den);
-        y.w = (float)((double)__uint_as_float((uint32_t)u.w << 16) / den);
-        return y;
-    }
-};
-__device__ __forceinline__ MasterRow master_row(const MasterView& mv, int64_t r, int dim) {
-    MasterRow m;
-    m.p32 = mv.f32 ? reinterpret_cast<const float4*>(mv.f32 + r * (int64_t)dim) : nullptr;
-    m.p16 = mv.f32 ? nullptr : reinterpret_cast<const ushort4*>(mv.raw16 + r * (int64_t)dim);
-    m.den = mv.f32 ? 1.0 : mv.den[r];
-    return m;
-}
-
-// The id a search returns for a local row: through the shard's (strictly increasing) row-id map, or local + base without one.
-// The one place that says so: k_refine's ranking and k_select_dense's three collections go through of().
-struct RowIds {
-    int64_t base;
-    const int64_t* map;
-    __device__ __forceinline__ int64_t of(int64_t local) const { return map ? map[local] : local + base; }
-};
-struct TopkOut { float* score; int64_t* row; int32_t* count; };   // a search's answers: [nq][k], [nq][k] returned ids, [nq]
 
 // write the 4 consecutive elements k..k+3 of a normalised row into a scan copy (corpus: fragment order, queries: LDS images)
 template <bool QUERY>
@@ -193,46 +152,6 @@ __global__ __launch_bounds__(256) void k_gather_raw(MasterView master, const int
     ushort4* dst = reinterpret_cast<ushort4*>(out.raw16 + i * (int64_t)dim);
     for (int g = lane; g < (dim >> 2); g += 64) dst[g] = src[g];
     if (lane == 0) out.den[i] = master.den[r];
-}
-
-// The exact score's arithmetic, stated once. oracle/rdx_oracle.c sums a row's products per LANE — lane l takes the float4 groups
-// l, l + 64, ... in increasing order, and within a group x, y, z, w — into one fp64 accumulator, then adds the 64 lanes by the
-// butterfly of wave_sum. A product of two floats is exact in fp64 (fused or not), so the score's bits depend only on the ORDER of
-// the additions. Every site that scores a row keeps that order and therefore those bits: exact_score, k_exact_scores and
-// k_refine's re-score through exact_dot4; k_exact_scores_reg with the query widened to doubles beforehand (the same operands).
-// A group past the row's end (lane_groups) multiplies by a zero query: it adds zeros, which leave a sum that started at +0.0 as it is.
-__device__ __forceinline__ void exact_dot4(double& acc, const float4& q, const float4& c) {
-    acc += (double)q.x * (double)c.x;
-    acc += (double)q.y * (double)c.y;
-    acc += (double)q.z * (double)c.z;
-    acc += (double)q.w * (double)c.w;
-}
-
-// A lane's U float4 groups of a row of n4 <= 64 U groups kept in registers: gi = lane + 64 u, clamped (a group past the row's end
-// re-reads the last one: no branch around loads), gv = whether the group exists (its query values are zeros where it does not).
-template <int U>
-struct lane_groups {
-    int gi[U];
-    bool gv[U];
-    __device__ __forceinline__ lane_groups(int lane, int n4) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            gv[u] = lane + 64 * u < n4;
-            gi[u] = gv[u] ? lane + 64 * u : n4 - 1;
-        }
-    }
-    __device__ __forceinline__ void load(const MasterRow& row4, float4 (&c)[U]) const {
-#pragma unroll
-        for (int u = 0; u < U; ++u) c[u] = row4[gi[u]];
-    }
-};
-
-// exact score of one normalised query (float4 view, global or LDS) against one master row, all 64 lanes get it
-template <class Q4>
-__device__ __forceinline__ float exact_score(const MasterRow& row4, Q4 q4, int n4, int lane) {
-    double acc = 0.0;
-    for (int g = lane; g < n4; g += 64) exact_dot4(acc, q4[g], row4[g]);
-    return (float)wave_sum(acc);
 }
 
 // K5a. Exact scores of up to QX queries against EVERY row (small problems, huge k, overflow fallback):
@@ -397,164 +316,10 @@ __global__ __launch_bounds__(256, 2) void k_exact_scores_reg(const ExactParams p
     }
 }
 
-// K5c. Grouped search's fill: job j = the best m <= 16 allowed rows of group_rows[begin[j], end[j]) for query
-// job_query[j], by (exact score descending, row ascending) — the order of every search. One workgroup of GROUP_FILL_WAVES waves per job, wave w taking
-// the listed rows [64 (w + 4 i), 64 (w + 4 i) + 64); a job spans at most GROUP_FILL_SPAN rows (the host splits longer groups and merges
-// the parts), so no wave walks an unbounded range. A wave takes 64 listed rows at a time (lane l tests row l against the bitmap), then
-// scores the allowed ones in list order; the waves' lists meet in LDS, where wave 0 ranks their 4 m <= 64 entries, one per lane. U = float4 groups per
-// lane kept in registers (dim <= 1024): the next allowed row's loads are issued before the current row is summed, and the sum adds a
-// lane's groups in increasing order through exact_dot4 — the order exact_score states. U = 0 (longer rows) calls exact_score itself.
-// The list lives in lanes 0..m-1, best first: a new entry's place is the number of entries before it (one ballot), the rest shift up.
-constexpr int GROUP_FILL_SPAN = 4096;
-constexpr int GROUP_FILL_MAX_M = 16;
-constexpr int GROUP_FILL_WAVES = 4;
-struct GroupFillParams {
-    MasterView master; int64_t rows; int dim;
-    const float* qhat;                                  // the normalised queries [nq][dim]
-    const uint32_t* allow;                              // the `where` bitmap or NULL
-    const int32_t* job_query; const int64_t* job_begin; const int64_t* job_end; int64_t n_jobs;
-    const int64_t* group_rows; int m;
-    float* out_score; int64_t* out_row; int32_t* out_count;   // [n_jobs][m] (padding -inf / -1), [n_jobs]
-};
-
-template <int U>
-__global__ __launch_bounds__(64 * GROUP_FILL_WAVES) void k_group_fill(const GroupFillParams p) {
-    __shared__ float part_s[GROUP_FILL_WAVES * GROUP_FILL_MAX_M];
-    __shared__ int64_t part_r[GROUP_FILL_WAVES * GROUP_FILL_MAX_M];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t j = blockIdx.x;   // (the grid is the jobs: every wave of the workgroup reaches the barrier below)
-    const int dim = p.dim, n4 = dim >> 2, m = p.m;
-    const float4* q4 = reinterpret_cast<const float4*>(p.qhat + (int64_t)p.job_query[j] * dim);
-    const int64_t begin = p.job_begin[j], end = p.job_end[j];
-    constexpr int UR = U > 0 ? U : 1;
-    const lane_groups<UR> grp(lane, n4);
-    float4 qr[UR], cur[UR], nxt[UR];
-    if constexpr (U > 0) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) qr[u] = q4[grp.gi[u]];
-    }
-    float best_s = -INFINITY;   // lane l < have: the list's entry l
-    int64_t best_r = -1;
-    int have = 0;
-    for (int64_t base = begin + 64 * wave; base < end; base += 64 * GROUP_FILL_WAVES) {
-        const int64_t at = base + lane;
-        int64_t my = at < end ? p.group_rows[at] : -1;
-        if (my < 0 || my >= p.rows) my = -1;   // (a row the index does not hold is never read)
-        if (my >= 0 && p.allow && !((p.allow[my >> 5] >> (my & 31)) & 1u)) my = -1;
-        unsigned long long live = __ballot(my >= 0);
-        if (!live) continue;
-        if constexpr (U > 0) grp.load(master_row(p.master, __shfl(my, __ffsll((long long)live) - 1, 64), dim), cur);
-        while (live) {
-            const int src = __ffsll((long long)live) - 1;
-            live &= live - 1;
-            const int64_t r = __shfl(my, src, 64);
-            float s;
-            if constexpr (U > 0) {
-                const int64_t rn = __shfl(my, live ? __ffsll((long long)live) - 1 : src, 64);   // (the last one re-reads its own row)
-                grp.load(master_row(p.master, rn, dim), nxt);
-                double acc = 0.0;
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    if (grp.gv[u]) exact_dot4(acc, qr[u], cur[u]);
-                s = (float)wave_sum(acc);
-#pragma unroll
-                for (int u = 0; u < U; ++u) cur[u] = nxt[u];
-            } else {
-                s = exact_score(master_row(p.master, r, dim), q4, n4, lane);
-            }
-            const bool before = lane < have && (best_s > s || (best_s == s && best_r < r));
-            const int pos = __popcll(__ballot(before));
-            if (pos < m) {
-                const float up_s = __shfl_up(best_s, 1, 64);
-                const int64_t up_r = __shfl_up(best_r, 1, 64);
-                if (lane > pos) {
-                    best_s = up_s;
-                    best_r = up_r;
-                } else if (lane == pos) {
-                    best_s = s;
-                    best_r = r;
-                }
-                if (have < m) ++have;
-            }
-        }
-    }
-    if (lane < m) {
-        part_s[wave * m + lane] = lane < have ? best_s : -INFINITY;
-        part_r[wave * m + lane] = lane < have ? best_r : -1;
-    }
-    __syncthreads();
-    if (wave != 0) return;
-    // the best m of the waves' lists: lane l ranks entry l among the n = 4 m entries (equal entries, which only a row listed twice
-    // can make, keep their list order)
-    const int n = GROUP_FILL_WAVES * m;
-    const float s = lane < n ? part_s[lane] : -INFINITY;
-    const int64_t r = lane < n ? part_r[lane] : -1;
-    int rank = 0;
-    for (int t = 0; t < n; ++t) {
-        const float st = part_s[t];
-        const int64_t rt = part_r[t];
-        rank += rt >= 0 && (st > s || (st == s && (rt < r || (rt == r && t < lane))));
-    }
-    const int found = __popcll(__ballot(r >= 0));
-    const int cnt = found < m ? found : m;
-    if (r >= 0 && rank < m) {
-        p.out_score[j * m + rank] = s;
-        p.out_row[j * m + rank] = r;
-    }
-    if (lane >= cnt && lane < m) {
-        p.out_score[j * m + lane] = -INFINITY;
-        p.out_row[j * m + lane] = -1;
-    }
-    if (lane == 0) p.out_count[j] = cnt;
-}
-
-// rank entries (score desc, row asc) held in LDS and write the best k; all threads of the block call it.
-// Wave-parallel: a wave takes entry i, its lanes take the entries j it is compared with (64 at a time), the rank is the
-// population count of the ballots — p/64 LDS reads per entry instead of p dependent ones per thread (p = 50: 5.2 -> ~1 us in
-// k_select_dense; the same routine ends k_refine and k_merge).
-__device__ __forceinline__ void rank_and_write(const float* __restrict__ s, const int64_t* __restrict__ r, int p, int k,
-                                               float* __restrict__ out_score, int64_t* __restrict__ out_row,
-                                               int32_t* __restrict__ out_count) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    for (int i = wave; i < p; i += nw) {
-        const float si = s[i];
-        const int64_t ri = r[i];
-        int rank = 0;
-        for (int j0 = 0; j0 < p; j0 += 64) {
-            const int j = j0 + lane;
-            bool before = false;
-            if (j < p) {
-                const float sj = s[j];
-                before = (sj > si) || (sj == si && r[j] < ri);
-            }
-            rank += __popcll(__ballot(before));
-        }
-        if (lane == 0 && rank < k) {
-            out_score[rank] = si;
-            out_row[rank] = ri;
-        }
-    }
-    const int c = p < k ? p : k;
-    for (int i = c + threadIdx.x; i < k; i += blockDim.x) {
-        out_score[i] = -INFINITY;
-        out_row[i] = -1;
-    }
-    if (threadIdx.x == 0) *out_count = c;
-}
-
-// Selection key of an EXACT score: f2key with -0.0 put onto +0.0. The documented order (include/rdx.h) compares scores as floats,
-// so the two zeros are one value and row ids decide among them; f2key alone keeps every -0.0 strictly below every +0.0. The
-// selects that choose a k-th exact score and its ties use this key; what they return is the row's own score, read back from where
-// it is stored (the key of a zero does not say which zero it was). The scan's thresholds keep f2key (rdx_common.hpp).
-constexpr uint32_t SEL_KEY_ZERO = 0x80000000u;   // f2key(+0.0f)
-__device__ __forceinline__ uint32_t f2key_sel(float f) {
-    return __float_as_uint(f) == 0x80000000u ? SEL_KEY_ZERO : f2key(f);
-}
 
 // K5b. top-k of a dense score row (one block per listed query): radix select of the k-th largest score, then
 // everything above it plus the LOWEST-row entries equal to it (ties -> ascending row id), then a rank sort.
-// -inf marks rows excluded by the `where` pre-filter; they are never returned.
-constexpr int SELECT_MAX_K = 4096;
+// -inf marks rows excluded by the `where` pre-filter; they are never returned. (SELECT_MAX_K: rows_core.hpp)
 #ifdef RDX_SELECT_STAMPS   // developer build (tools/select_stamps.py): where k_select_dense spends its time
 __device__ unsigned long long g_select_stamps[16];
 #define RDX_STAMP(i) do { __syncthreads(); if (blockIdx.x == 0 && threadIdx.x == 0) g_select_stamps[i] = wall_clock64(); } while (0)

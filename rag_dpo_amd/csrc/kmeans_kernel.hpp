@@ -1,9 +1,9 @@
 // kmeans_kernel.hpp — the kernels of rdx_index_kmeans (rag_dpo_amd/kmeans.py states the definition): the assignment
 // (an argmax per stored row over the centroids, in the exact score's arithmetic), the stable order of rows by label (histogram per
 // block of rows, one scan, placement by counted ranks: km_order.hpp), the ordered per-cluster sum in segments of KM_SEGMENT members
-// and the new centroids. Included by rdx_index.hip only. No kernel waits for another workgroup or launch.
+// and the new centroids. Included by rdx_derived.hip only. No kernel waits for another workgroup or launch.
 #pragma once
-#include "k_rows.hpp"
+#include "rows_core.hpp"
 #include "km_order.hpp"
 
 namespace rdx {

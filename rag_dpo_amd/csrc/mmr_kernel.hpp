@@ -1,5 +1,5 @@
 // mmr_kernel.hpp — K5d: diversity-aware selection (maximal marginal relevance) over a search's candidate lists.
-// Included by rdx_index.hip after k_rows.hpp, which owns MasterRow, lane_groups, exact_dot4 and exact_score.
+// Included by rdx_derived.hip only; MasterRow, lane_groups, exact_dot4 and exact_score are rows_core.hpp.
 //
 // One workgroup per query. Its list's live entries (position < count, 0 <= row < rows) sit in LDS as s (the query score), m (the
 // largest pair score with a picked entry so far), row and a picked flag. Pick 0 is the first live position; every later round
@@ -14,7 +14,7 @@
 // Nothing leaves the workgroup between rounds and no float is ever added atomically: the same list gives the same bits whatever the
 // batch around it.
 #pragma once
-#include "k_rows.hpp"
+#include "rows_core.hpp"
 
 namespace rdx {
 

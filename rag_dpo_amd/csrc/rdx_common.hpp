@@ -1,6 +1,6 @@
 // rdx_common.hpp — shared device helpers and the HBM layouts of librdx (gfx950 only).
 //
-// HBM layout of one corpus shard (all owned by rdx_index, see rdx_index.hip):
+// HBM layout of one corpus shard (all owned by rdx_index, see rdx_index.hpp):
 //   master  fp32 [cap_rows][dim]   row-major L2-normalised rows; the exact re-score and the exact scan read it
 //   shadow  fp16 "scan copy", value = master * 2^scale_log2, stored in MFMA FRAGMENT ORDER:
 //           [row block rb = row/32][k chunk c = k/32][row half m][lane 0..63][8 halfs]

@@ -1,6 +1,7 @@
-// rdx_host.hpp — what the host units of librdx (rdx_index.hip, rdx_enc.hip, rdx_bm25.hip, rdx_docs.hip, rdx_meta.hip, rdx_maxsim.hip)
-// share: the error string behind rdx_last_error(), the checks of `space`, `device` and a call's shape arrays, the device / pinned
-// buffers, the dynamic-LDS limit of a kernel, and the wait on a word in pinned memory. What only the row-filter stores share (rdx_docs.hip, rdx_meta.hip) is in rdx_store.hpp.
+// rdx_host.hpp — what the host units of librdx (rdx_index.hip, rdx_derived.hip, rdx_merge.hip, rdx_enc.hip, rdx_bm25.hip, rdx_docs.hip,
+// rdx_meta.hip, rdx_maxsim.hip) share: the error string behind rdx_last_error(), the checks of `space`, `device` and a call's shape arrays,
+// the device / pinned buffers, the copy of a host caller's results, the dynamic-LDS limit of a kernel, and the wait on a word in pinned
+// memory. It holds no kernel (the rule: rdx_index.hpp "ONE DEFINITION"). What only the row-filter stores share (rdx_docs.hip, rdx_meta.hip) is in rdx_store.hpp.
 #pragma once
 #include "../../include/rdx.h"
 #include "rdx_limits.hpp"
@@ -209,6 +210,27 @@ struct MappedPin {
         if (host) (void)hipHostFree(host);
     }
 };
+
+// Host callers: where the results go (rdx_index.hip search_chunk, rdx_merge.hip)
+struct HostOut {
+    float* score;
+    int64_t* row;
+    int32_t* count;
+    bool stale;
+};
+
+// Host callers (HostOut): small results travel with the end-of-search kernel into pinned staging and are copied to the
+// caller's buffers by the CPU once the mailbox says the search is complete; large ones use D2H copies. When a fallback pass
+// had to rewrite some results afterwards they are copied again (HostOut::stale). (PIN_MAX: search_plan.hpp)
+RDX_HOST_SHARED int copy_results_to_host(const HostOut& ho, const float* d_score, const int64_t* d_row, const int32_t* d_count, int64_t nq,
+                                         int k, hipStream_t st) {
+    if (k > 0) {
+        HIP_TRY(hipMemcpyAsync(ho.score, d_score, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(ho.row, d_row, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(ho.count, d_count, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    return RDX_OK;
+}
 
 // Kernels that use more than 64 KiB of dynamic LDS need the limit raised, once per kernel and device and again when the need
 // grows. The limits already raised on a device are a table that is replaced, never changed: a launch reads the current one

@@ -1,222 +1,25 @@
-// rdx_index.hip — the dense index of librdx: the rdx_index lifecycle, options and ingest, rdx_l2_normalize, the search, masks,
-// merge and signal, the grouped fill, the MMR selection, the threshold search, the near-duplicate clustering, the k-means and the value counts of include/rdx.h. The only unit that holds a k_scan kernel (rag_dpo_amd/build.py checks that).
+// rdx_index.hip — the core unit of the dense index (struct rdx_index: rdx_index.hpp): its lifecycle, options and write path, rdx_l2_normalize,
+// the search pipeline and its entry points, masks, the debug and statistics getters, and the threshold search, which is a variant of the
+// pipeline (the main scan, then the k_range_* kernels built on k_refine's device code), and the grouped fill, which shares exact_score's long-row
+// form with k_refine (rdx_index.hpp says why that keeps it here). The only unit that holds a k_scan kernel (rag_dpo_amd/build.py checks that).
+// What is built ON an index and a search — MMR, clustering, k-means, value counts — is rdx_derived.hip; it reaches this unit through the host
+// functions rdx_index.hpp declares: set_device, finish_pending, check_mask, check_own_rows, normalize_queries, gather_rows, exact_groups and
+// range_chunk. The merge and the signal are rdx_merge.hip.
 // The scans and the tail of a search are launched from parameter structs filled by name, each in one place whoever searches: main_scan_params fills
 // ScanParams, refine_lists / refine_params k_refine's RefineParams, exact_params / select_params the exact path's, which for_exact_groups drives.
-#include "rdx_host.hpp"
+#include "rdx_index.hpp"
 
-#include <cmath>
 #include <cstddef>
 #include <cstdio>
 #include <memory>
-#include <mutex>
-#include <type_traits>
-#include <vector>
 
-#include "index_state.hpp"
+#include "group_fill_kernel.hpp"
 #include "k_rows.hpp"
-#include "mmr_kernel.hpp"
 #include "range_kernel.hpp"
 #include "refine_kernel.hpp"
 #include "scan_kernel.hpp"
-#include "search_plan.hpp"
-#include "dup_kernel.hpp"   // (after the search's kernels: the code object lists them in the order it always did, the new ones behind)
-#include "kmeans_kernel.hpp"
-#include "facet_kernel.hpp"
 
-using namespace rdx;
-
-// Host callers: where the results go (see search_chunk)
-struct HostOut {
-    float* score;
-    int64_t* row;
-    int32_t* count;
-    bool stale;
-};
-
-// Which rows a search's queries may return (device addresses): one bitmap for all of them or none — the shared form, what a plain
-// pointer converts to — or a bitmap per query (rdx_search_filtered): query q is held to ftab[qf[q]], to none when qf[q] < 0.
-struct RowFilter {
-    const uint32_t* allow = nullptr;
-    const uint32_t* const* ftab = nullptr;
-    const int32_t* qf = nullptr;   // NULL: the shared form
-    RowFilter(const uint32_t* a = nullptr) : allow(a) {}
-    RowFilter(const uint32_t* const* t, const int32_t* q) : ftab(t), qf(q) {}
-};
-
-// the caller's buffers of one search chunk (device addresses)
-struct SearchIO {
-    const float* queries;
-    RowFilter allow;
-    float* score;
-    int64_t* row;
-    int32_t* count;
-    int32_t* flags;   // rdx_search_async(out_flags): the "incomplete" word of the packed partial, or NULL
-};
-
-// A search whose kernels (up to k_finish) are enqueued and whose host half — waiting for the mailbox, copying small
-// results out, re-weighting the XCD shares, the fallback passes for overflowed queries, the statistics — has not run yet.
-// rdx_search runs that half at once; rdx_search_async leaves it to rdx_search_wait, so that the caller can enqueue what
-// consumes the results (the RCCL all-gather and the merge) while the scan is still running.
-struct PendingSearch {
-    bool active = false;
-    SearchPlan plan;
-    SearchIO io = {};
-    hipStream_t st = nullptr;
-    unsigned long long seq = 0;
-    rdx_search_stats stats = {};   // rdx_search_async only: the statistics of the deferred search
-};
-
-// ------------------------------------------------------------------------------------------------
-// the index: one corpus shard resident in one GPU's HBM
-// ------------------------------------------------------------------------------------------------
-// The rows, allocated for `cap` of them (a multiple of 256; the policy: index_state.hpp). grow() and rdx_index_compact() fill a
-// fresh store and move it into place once everything enqueued on it has run: leaving early frees the fresh one, and the index
-// stands as it was.
-struct RowStore {
-    int compact = 0;   // option "compact_master" (settable while the index is empty): 4 instead of 6 B/element
-    int64_t cap = 0;
-    DevBuf master;     // [cap][dim] normalised fp32 rows (default), or none with compact_master:
-    DevBuf raw16;      //   [cap][dim] raw bf16 rows as delivered ...
-    DevBuf den;        //   [cap] ... and their divisors max(|x|, 1e-12); k_rows.hpp MasterView
-    DevBuf shadow;     // [cap][dim_pad] fp16 scan copy in MFMA fragment order (rdx_common.hpp corpus_off)
-    DevBuf row_map;    // [cap] local row -> returned row id (strictly increasing), or none = local + row_base
-
-    MasterView mv() const { return MasterView{master.as<float>(), raw16.as<uint16_t>(), den.as<double>()}; }
-    const int64_t* ids() const { return row_map.as<int64_t>(); }
-    // master (in this store's mode) and shadow for ncap rows; all or nothing
-    hipError_t alloc_rows(int64_t ncap, int dim, int dim_pad) {
-        hipError_t e = compact ? raw16.alloc((size_t)ncap * dim * 2) : master.alloc((size_t)ncap * dim * 4);
-        if (e == hipSuccess && compact) e = den.alloc((size_t)ncap * 8);
-        if (e == hipSuccess) e = shadow.alloc((size_t)ncap * dim_pad * 2);
-        if (e != hipSuccess)
-            for (DevBuf* b : {&master, &raw16, &den, &shadow}) b->release();
-        cap = e == hipSuccess ? ncap : 0;
-        return e;
-    }
-    hipError_t alloc_ids() { return row_map.alloc((size_t)std::max<int64_t>(cap, 256) * 8); }
-};
-
-// The int8 coarse pass's copy of the corpus, built by the first search that takes the path and brought up to date by every later
-// one (prepare_i8); not persisted. Which rows of it are current is the watermark's to say (index_state.hpp).
-struct I8Copy {
-    DevBuf c8;      // [cap][dim_pad] in corpus_off8 order
-    DevBuf sblk;    // s_b per 32-row block
-    DevBuf eps8;    // the largest eps_b
-    // the classes of block error: eps_b per block, the EPS_CLASSES - 1 stored edges (taken at a full quantisation), a class byte per block
-    DevBuf epsb, edge8, cls8;
-    I8Watermark mark;
-
-    // room for cap rows; a buffer that had to be allocated anew lost its contents, and the watermark is told
-    int ensure(int64_t cap, int dim_pad) {
-        const size_t need[6] = {(size_t)cap * dim_pad, (size_t)(cap / 32) * 4, 4, (size_t)(cap / 32) * 4, (size_t)EPS_CLASSES * 4,
-                                (size_t)(cap / 32 + 3) / 4 * 4};   // (cls8: k_scan<I8> reads whole dwords)
-        DevBuf* const buf[6] = {&c8, &sblk, &eps8, &epsb, &edge8, &cls8};
-        for (int i = 0; i < 6; ++i) {
-            const void* was = buf[i]->p;
-            RDX_TRY(buf[i]->ensure(need[i]));
-            if (buf[i]->p != was) mark.reallocated();
-        }
-        return RDX_OK;
-    }
-};
-
-constexpr int64_t RANGE_CHUNK = 4096;   // queries per pipeline pass of rdx_index_range, as a search chunks them (search_impl)
-
-// rdx_index_near_dup's scratch (grow-only): the parent array, and per batch the query rows, the gathered queries, their thresholds, the
-// threshold search's answers, the heavy list and the counter block (dup_kernel.hpp)
-struct DupScratch {
-    DevBuf parent, ids, q, thr, score, row, count, total, heavy, ctr;
-    int ensure(int64_t batch, int64_t rows, int list_cap, int dim) {
-        const size_t B = (size_t)batch;
-        DevBuf* const buf[10] = {&parent, &ids, &q, &thr, &score, &row, &count, &total, &heavy, &ctr};
-        const size_t need[10] = {(size_t)rows * 4, B * 8, B * dim * 4, B * 4, B * list_cap * 4, B * list_cap * 8, B * 4, B * 8, B * 4, sizeof(DupCounters)};
-        for (int i = 0; i < 10; ++i) RDX_TRY(buf[i]->ensure(need[i]));
-        return RDX_OK;
-    }
-};
-
-// rdx_index_kmeans' scratch (grow-only): the histograms / offsets, the order, the two tables, the segments' totals, the counters, and
-// the pinned word the host reads once per assignment
-struct KmScratch {
-    DevBuf hist, order, cluster_off, seg_off, segsum, ctr;
-    MappedPin<unsigned long long> mail;
-    unsigned long long seq = 0;   // number of the last word asked for
-    int ensure(int64_t rows, int n_clusters, int dim, int64_t n_blocks) {
-        DevBuf* const buf[6] = {&hist, &order, &cluster_off, &seg_off, &segsum, &ctr};
-        const size_t need[6] = {((size_t)n_clusters * n_blocks + 1) * 4, (size_t)rows * 4, ((size_t)n_clusters + 1) * 4, ((size_t)n_clusters + 1) * 4,
-                                (size_t)km_max_segments(rows, n_clusters) * dim * 8, sizeof(KmCounters)};
-        for (int i = 0; i < 6; ++i) RDX_TRY(buf[i]->ensure(need[i]));
-        if (!mail.host) RDX_TRY(mail.map(64));
-        return RDX_OK;
-    }
-};
-
-struct rdx_index {
-    int device = 0;
-    int dim = 0, dim_pad = 0, ksteps = 0, scale_log2 = 0;
-    int n_cu = 256;
-    int64_t rows = 0;
-    RowStore store;
-    hipStream_t own_stream = nullptr;
-    std::mutex mu;
-
-    // what a plan reads (search_plan.hpp), beside shape()
-    SearchOptions opt;      // the search options of rdx_index_set_option
-    SearchAdapt adapt;      // what finished searches feed back
-    int coarse_bits = 0;    // the last search's coarse pass: 16, 8, or 0 (exact path only); rdx_search_last_coarse_bits
-    int64_t row_base = 0;   // added to every returned row id (global ids of a shard)
-
-    // scratch (grow-only; never allocated inside a warmed-up search)
-    DevBuf r_list, r_q, r_s, r_r, r_c;   // second-chance batch of overflowed queries
-    DevBuf r_qf;                         //   ... and their filter indices (a filter per query)
-    DevBuf fq;                           // rdx_search_filtered: the masks' device pointers | the queries' filter indices
-    std::vector<char> fq_host;           //   ... and what they are uploaded from (kept until the next call)
-    DevBuf wgt;                          // [grid][2] workgroup time stamps of the main scan
-    DevBuf staging, qraw, qhat, qshadow, tau, cntw, cand, setmax, exact_list, iota, dense, ctr, bad, o_score, o_row,
-        o_count, mask, ids;
-    I8Copy i8;
-    // the int8 pass's per-search query copy, scales, bounds, thresholds (nothing of it outlives a search)
-    DevBuf qshadow8, tq8, eq8, nq8, thr8, taus8, twoe8;
-    DevBuf gjobs;            // rdx_index_group_fill: the call's jobs (query | begin | end)
-    DevBuf rng_ctr;          // rdx_index_range: its own counter block (range_kernel.hpp RangeCounters)
-    DupScratch dup;          // rdx_index_near_dup
-    int dup_batch = 0;       // option "dup_batch": rows per batch of rdx_index_near_dup, 0 = the range chunk (tests lower it)
-    KmScratch km;            // rdx_index_kmeans
-    int km_tiles = 0;        // option "km_tiles": tiles of 256 rows per block of rdx_index_kmeans' order, 0 = km_block_span (tests raise it)
-    DevBuf fct_ctr, fct_tab; // rdx_index_facet_count / rdx_index_range_facets: the counter block, a sub-chunk's tables (facet_kernel.hpp)
-    int64_t facet_table_kb = 0;   // option "facet_table_kb": the tables' budget, 0 = FACET_TABLE_KB
-    DevBuf spill;            // k_refine<true>: [nq_pad][spill_cap] hit lists of the queries that outgrow the LDS list (first spilling plan)
-    // end-of-search mailbox in pinned host memory (k_finish writes it over PCIe; the host spins on its sequence number)
-    MappedPin<Mailbox> mbox;
-    unsigned long long seq = 0;       // number of the last search enqueued on this index
-    MappedPin<char> pin_out;          // pinned staging for the small results of host callers (score | row | count)
-    bool ctr_ready = false;           // the counter block was zeroed once; afterwards every k_finish re-zeroes it
-    PendingSearch pending;            // rdx_search_async: the search whose host half is still to run
-    hipEvent_t ev[8] = {};
-    bool ev_ok = false;
-    rdx_search_stats stats = {};
-
-    MasterView mv() const { return store.mv(); }
-    float scale() const { return std::ldexp(1.0f, scale_log2); }
-    float two_e() const { return 2.0f * (1.0e-3f + 2.5e-7f * (float)dim_pad); }   // see DESIGN.md "error bound"
-    PlanShape shape() const { return PlanShape{rows, dim_pad, ksteps, n_cu, two_e()}; }
-};
-
-// a `where` bitmap kept resident in HBM between searches (the reference's filters are a handful of fixed shapes)
-struct rdx_mask {
-    int device = 0;
-    int64_t rows = 0;   // row count of the index when the mask was made: a mask never outlives a write to the index
-    DevBuf words;
-};
-
-// a pinned, device-visible word the merge kernel publishes ((sequence << 1) | value) and the host waits on
-struct rdx_signal {
-    int device = 0;
-    MappedPin<unsigned long long> word;
-    unsigned long long seq = 0;   // number of the last merge that was given this signal
-};
-
-static int set_device(const rdx_index* h) {
+int rdx::set_device(const rdx_index* h) {
     HIP_TRY(hipSetDevice(h->device));
     return RDX_OK;
 }
@@ -310,18 +113,6 @@ static int launch_scan_bn(rdx_index* h, int bn, bool res, bool fused, const Scan
     return launch_scan<256, EPI, false>(h, p, grid, st);
 }
 
-// f(std::integral_constant<int, U>) for the kernels that hold a row's float4 groups in registers, U per lane: 1..4 up to dim 1024,
-// U = 0 (their form for any dim) beyond
-template <class F>
-static void dispatch_u(int dim, F f) {
-    const int u = dim <= 1024 ? (dim / 4 + 63) / 64 : 0;
-    if (u == 1) f(std::integral_constant<int, 1>{});
-    else if (u == 2) f(std::integral_constant<int, 2>{});
-    else if (u == 3) f(std::integral_constant<int, 3>{});
-    else if (u == 4) f(std::integral_constant<int, 4>{});
-    else f(std::integral_constant<int, 0>{});
-}
-
 // K5a for one group of ep.nq <= QX queries. Up to dim 1024 the register kernel with U = float4 groups per lane: queries in registers,
 // two rows in flight per wave, 2 blocks per CU (all resident at once); the LDS kernel beyond
 static int launch_exact_scores(const rdx_index* h, const ExactParams& ep, int grid_rows, hipStream_t st) {
@@ -381,6 +172,11 @@ static int for_exact_groups(rdx_index* h, const int32_t* d_list, int n_list, con
     return RDX_OK;
 }
 
+int rdx::exact_groups(rdx_index* h, const int32_t* d_list, int n_list, const RowFilter& allow, hipStream_t st,
+                      const std::function<void(const int32_t*, int, bool)>& after) {
+    return for_exact_groups(h, d_list, n_list, allow, nullptr, st, after);
+}
+
 // exact full scan for the queries listed in d_list[0..n_list)
 static int run_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, const RowFilter& d_allow, const TopkOut& out, hipStream_t st,
                      bool stamps = false, const FinishArgs* fin = nullptr) {
@@ -394,19 +190,6 @@ static int run_exact(rdx_index* h, const int32_t* d_list, int n_list, int k, con
         sel.t_last = stamp(offsetof(RefineCounters, t_last));
         hipLaunchKernelGGL(k_select_dense, dim3(nq), dim3(1024), 0, st, sel, (fin && last) ? *fin : no_fin);
     });
-}
-
-// Host callers (HostOut): small results travel with the end-of-search kernel into pinned staging and are copied to the
-// caller's buffers by the CPU once the mailbox says the search is complete; large ones use D2H copies. When a fallback pass
-// had to rewrite some results afterwards they are copied again (HostOut::stale). (PIN_MAX: search_plan.hpp)
-static int copy_results_to_host(const HostOut& ho, const float* d_score, const int64_t* d_row, const int32_t* d_count, int64_t nq,
-                                int k, hipStream_t st) {
-    if (k > 0) {
-        HIP_TRY(hipMemcpyAsync(ho.score, d_score, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(ho.row, d_row, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipMemcpyAsync(ho.count, d_count, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-    return RDX_OK;
 }
 
 // the wait policy of wait_word (rdx_host.hpp)
@@ -621,16 +404,17 @@ static int prepare_i8(rdx_index* h, const SearchPlan& p, hipStream_t st) {
     return RDX_OK;
 }
 
-// K1 on nq caller queries: h->qhat (fp32, what every exact score is taken against) and, with qshadow, their tiled fp16 copy for the scan, padded to
-// nq_pad queries (0: none). QUERY: the call site's instantiation; the query form is told the scan copy's geometry whether or not it writes one.
+// K1 on nq caller queries (rdx_index.hpp); the query form is instantiated here for rdx_derived.hip as well
 template <bool QUERY>
-static int normalize_queries(rdx_index* h, const float* queries, int64_t nq, int64_t nq_pad, _Float16* qshadow, int* d_bad, int verbatim, hipStream_t st) {
+int rdx::normalize_queries(rdx_index* h, const float* queries, int64_t nq, int64_t nq_pad, _Float16* qshadow, int* d_bad, int verbatim, hipStream_t st,
+                           float* out) {
     hipLaunchKernelGGL(k_normalize<QUERY>, dim3((int)((std::max(nq, nq_pad) + 3) / 4)), dim3(256), 0, st, queries, (const uint16_t*)nullptr, nq,
-                       h->dim, (const int64_t*)nullptr, (int64_t)0, MasterView{h->qhat.as<float>(), nullptr, nullptr}, qshadow,
+                       h->dim, (const int64_t*)nullptr, (int64_t)0, MasterView{out ? out : h->qhat.as<float>(), nullptr, nullptr}, qshadow,
                        QUERY ? h->ksteps : 0, QUERY ? h->scale() : 1.0f, d_bad, nq_pad, verbatim);
     HIP_TRY(hipGetLastError());
     return RDX_OK;
 }
+template int rdx::normalize_queries<true>(rdx_index*, const float*, int64_t, int64_t, _Float16*, int*, int, hipStream_t, float*);
 
 // the identity query list of an exact-only search, uploaded once (grow-only), not per search
 static int ensure_iota(rdx_index* h, int nq_pad, hipStream_t st) {
@@ -933,7 +717,7 @@ static int search_chunk(rdx_index* h, const SearchIO& io, int64_t nq, int k, hip
 }
 
 // run the host half of a search left pending by rdx_search_async (call with h->mu held)
-static int finish_pending(rdx_index* h, bool* redone) {
+int rdx::finish_pending(rdx_index* h, bool* redone) {
     if (redone) *redone = false;
     if (!h->pending.active) return RDX_OK;
     PendingSearch ps = h->pending;
@@ -1230,6 +1014,12 @@ extern "C" int rdx_index_update_stored(rdx_index* h, const int64_t* row_ids, con
     return update_impl("rdx_index_update_stored", h, row_ids, rows, n, space, true);
 }
 
+int rdx::gather_rows(const rdx_index* h, const int64_t* d_ids, int64_t n, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(k_gather_rows, dim3((int)((n + 3) / 4)), dim3(256), 0, st, h->mv(), d_ids, n, h->dim, out);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
+}
+
 extern "C" int rdx_index_get(rdx_index* h, const int64_t* row_ids, int64_t n, float* out, int space) {
     if (!h || n < 0 || (n > 0 && (!row_ids || !out))) return fail(RDX_ERR_INVALID, "rdx_index_get: bad argument");
     RDX_TRY(check_space(space));
@@ -1247,8 +1037,7 @@ extern "C" int rdx_index_get(rdx_index* h, const int64_t* row_ids, int64_t n, fl
             RDX_TRY(h->staging.ensure((size_t)STAGE_ROWS * h->dim * 4));
             dst = h->staging.as<float>();
         }
-        hipLaunchKernelGGL(k_gather_rows, dim3((int)((m + 3) / 4)), dim3(256), 0, st, h->mv(), d_ids + off, m, h->dim, dst);
-        HIP_TRY(hipGetLastError());
+        RDX_TRY(gather_rows(h, d_ids + off, m, dst, st));
         if (space == RDX_HOST) {
             HIP_TRY(hipMemcpyAsync(out + (size_t)off * h->dim, dst, (size_t)m * h->dim * 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
@@ -1362,7 +1151,7 @@ extern "C" int rdx_l2_normalize(int device, const float* in, int64_t n, int dim,
 }
 
 // ------------------------------------------------------------------------------------------------
-// search: the entry points, masks, merge and signal
+// search: the entry points and masks
 // ------------------------------------------------------------------------------------------------
 // what rdx_search and rdx_search_async do first (h->mu held): the pending search completes (scratch buffers are shared), the
 // device is selected, the profiling events exist, and the statistics start from the call's shape
@@ -1381,7 +1170,7 @@ static int begin_search(rdx_index* h, int64_t nq, int k, rdx_search_stats* s) {
 }
 
 // a resident mask is the index's, as it stands; code: RDX_ERR_STATE, or RDX_ERR_INVALID from the threshold search and the clustering (include/rdx.h)
-static int check_mask(const rdx_index* h, const rdx_mask* mask, const char* who, int code) {
+int rdx::check_mask(const rdx_index* h, const rdx_mask* mask, const char* who, int code) {
     if (mask && (mask->device != h->device || mask->rows != h->rows))
         return fail(code, std::string(who) + ": the mask was made for " + std::to_string(mask->rows) + " rows on device " +
                               std::to_string(mask->device) + ", the index now holds " + std::to_string(h->rows) +
@@ -1390,7 +1179,7 @@ static int check_mask(const rdx_index* h, const rdx_mask* mask, const char* who,
 }
 
 // calls that take or return the index's own rows are not a shard's; tail: what the caller is told instead
-static int check_own_rows(const rdx_index* h, const char* who, const char* tail) {
+int rdx::check_own_rows(const rdx_index* h, const char* who, const char* tail) {
     if (h->store.row_map.p || h->row_base != 0)
         return fail(RDX_ERR_STATE, std::string(who) + ": the index returns mapped row ids (a shard): " + tail);
     return RDX_OK;
@@ -1569,7 +1358,7 @@ extern "C" int rdx_search_filtered(rdx_index* h, const float* queries, int64_t n
 }
 
 // ---- grouped search: the fill ---------------------------------------------------------------------------------
-static_assert(GROUP_FILL_SPAN == RDX_GROUP_FILL_SPAN && GROUP_FILL_MAX_M == RDX_GROUP_MAX_SIZE, "k_rows.hpp and include/rdx.h disagree");
+static_assert(GROUP_FILL_SPAN == RDX_GROUP_FILL_SPAN && GROUP_FILL_MAX_M == RDX_GROUP_MAX_SIZE, "group_fill_kernel.hpp and include/rdx.h disagree");
 
 extern "C" int rdx_index_group_fill(rdx_index* h, const float* queries, int64_t nq, const rdx_mask* mask, const int32_t* job_query,
                                     const int64_t* job_begin, const int64_t* job_end, int64_t n_jobs, const int64_t* group_rows,
@@ -1635,63 +1424,8 @@ extern "C" int rdx_index_group_fill(rdx_index* h, const float* queries, int64_t 
     return RDX_OK;
 }
 
-// ---- diversity-aware selection ---------------------------------------------------------------------------------
-static_assert(MMR_MAX_FETCH == RDX_MMR_MAX_FETCH && MMR_MAX_K == RDX_MMR_MAX_K, "mmr_kernel.hpp and include/rdx.h disagree");
-
-extern "C" int rdx_index_mmr(rdx_index* h, const float* cand_score, const int64_t* cand_row, const int32_t* cand_count, int64_t nq,
-                             int fetch_k, int k, double lambda, int32_t* out_pos, int64_t* out_row, float* out_score, double* out_value,
-                             int32_t* out_count, int32_t* out_bad, void* stream) {
-    if (!h) return fail(RDX_ERR_INVALID, "rdx_index_mmr: null index");
-    if (nq < 0 || nq > 65535) return fail(RDX_ERR_INVALID, "rdx_index_mmr: nq must be in [0, 65535]");
-    if (k < 1 || k > MMR_MAX_K) return fail(RDX_ERR_INVALID, "rdx_index_mmr: k (the picks per query) must be in [1, 64]");
-    if (fetch_k < k || fetch_k > MMR_MAX_FETCH) return fail(RDX_ERR_INVALID, "rdx_index_mmr: fetch_k (the entries per list) must be in [k, 1024]");
-    if (!(lambda >= 0.0 && lambda <= 1.0)) return fail(RDX_ERR_INVALID, "rdx_index_mmr: lambda must be in [0, 1]");
-    if (nq == 0) return RDX_OK;
-    if (!cand_score || !cand_row || !cand_count) return fail(RDX_ERR_INVALID, "rdx_index_mmr: null input pointer");
-    if (!out_pos || !out_row || !out_score || !out_value || !out_count || !out_bad) return fail(RDX_ERR_INVALID, "rdx_index_mmr: null output pointer");
-    if (((uintptr_t)cand_row | (uintptr_t)out_row | (uintptr_t)out_value) & 7) return fail(RDX_ERR_INVALID, "rdx_index_mmr: misaligned pointer");
-    if (((uintptr_t)cand_score | (uintptr_t)cand_count | (uintptr_t)out_pos | (uintptr_t)out_score | (uintptr_t)out_count | (uintptr_t)out_bad) & 3)
-        return fail(RDX_ERR_INVALID, "rdx_index_mmr: misaligned pointer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    RDX_TRY(check_own_rows(h, "rdx_index_mmr", "cand_row must be the index's own rows"));
-    RDX_TRY(set_device(h));
-    MmrParams mp = {};
-    mp.master = h->mv();
-    mp.rows = h->rows;
-    mp.dim = h->dim;
-    mp.cand_score = cand_score;
-    mp.cand_row = cand_row;
-    mp.cand_count = cand_count;
-    mp.fetch_k = fetch_k;
-    mp.k = k;
-    mp.lambda = lambda;
-    mp.out_pos = out_pos;
-    mp.out_row = out_row;
-    mp.out_score = out_score;
-    mp.out_value = out_value;
-    mp.out_count = out_count;
-    mp.out_bad = out_bad;
-    hipStream_t st = (hipStream_t)stream;
-    dispatch_u(h->dim, [&](auto u) {   // one workgroup per query
-        hipLaunchKernelGGL(k_mmr<decltype(u)::value>, dim3((unsigned)nq), dim3(64 * MMR_WAVES), 0, st, mp);
-    });
-    HIP_TRY(hipGetLastError());
-    return RDX_OK;
-}
-
 // ---- threshold search ------------------------------------------------------------------------------------------
 static_assert(RDX_RANGE_MAX_RESULTS <= REFINE_PMAX && RDX_RANGE_MAX_RESULTS <= SELECT_MAX_K, "range_kernel.hpp ranks max_results entries in k_refine's arrays");
-
-// the caller's buffers of one chunk of a range search (device addresses)
-struct RangeIO {
-    const float* queries;
-    const float* thr;
-    const uint32_t* allow;
-    float* score;
-    int64_t* row;
-    int32_t* count;
-    int64_t* total;
-};
 
 // the exact path of a range search for the queries listed in d_list[0..n_list): K5a per group of QX queries, then k_range_select_dense
 // (fc: the counting variant, for rdx_index_range_facets)
@@ -1707,7 +1441,7 @@ static int run_range_exact(rdx_index* h, const int32_t* d_list, int n_list, int 
 // One chunk (nq <= 4096) of a range search: plan_range, K1, k_range_tau, then the exact path for everybody, or the main scan,
 // k_range_refine and the exact path for the queries it listed. Returns with the stream drained; paths[0] / [1] take the chunk's queries
 // by path. fc: the counting variants of the two last stages instead (rdx_index_range_facets): io's lists are not written, k is 1.
-static int range_chunk(rdx_index* h, const RangeIO& io, int64_t nq, int k, hipStream_t st, int32_t* paths, const FacetIO* fc = nullptr) {
+int rdx::range_chunk(rdx_index* h, const RangeIO& io, int64_t nq, int k, hipStream_t st, int32_t* paths, const FacetIO* fc) {
     SearchPlan p;
     std::string err;
     const int prc = plan_range(h->shape(), h->opt, nq, k, &p, &err);
@@ -1801,283 +1535,6 @@ extern "C" int rdx_index_range(rdx_index* h, const float* queries, int64_t nq, c
     return RDX_OK;
 }
 
-// ---- near-duplicate clustering ------------------------------------------------------------------------------------
-// Batches of allowed rows, ascending: gather the stored rows as queries (they never leave the device), the threshold search of the
-// batch with lists of list_cap, k_dup_link_lists; then, while the chunk's qhat is still resident, the exact scores of the batch's heavy
-// rows per group of QX and k_dup_link_dense; k_dup_labels after the last batch. DupRun: one call's arguments, and what its batches add up to.
-struct DupRun {
-    float threshold;
-    const uint32_t* allow;
-    int list_cap;
-    int64_t max_dense;
-    int64_t* out_total;
-    hipStream_t st;
-    unsigned row_blocks;   // blocks of 256 threads, one thread per row
-    int64_t n_heavy = 0, n_batches = 0;
-};
-
-// the allowed rows, ascending: from the bitmap (the only thing of the call the host reads beside counters)
-static int dup_allowed_rows(int64_t rows, const DupRun& run, std::vector<int64_t>* ids) {
-    if (run.allow) {
-        std::vector<uint32_t> words((size_t)((rows + 31) / 32));
-        HIP_TRY(hipMemcpyAsync(words.data(), run.allow, words.size() * 4, hipMemcpyDeviceToHost, run.st));
-        HIP_TRY(hipStreamSynchronize(run.st));
-        for (int64_t r = 0; r < rows; ++r)
-            if ((words[(size_t)(r >> 5)] >> (r & 31)) & 1u) ids->push_back(r);
-    } else {
-        ids->resize((size_t)rows);
-        for (int64_t r = 0; r < rows; ++r) (*ids)[(size_t)r] = r;
-    }
-    return RDX_OK;
-}
-
-// before the first batch: the scratch for batches of B rows, every allowed row a cluster of its own, the batch's thresholds
-static int dup_begin(rdx_index* h, const DupRun& run, int64_t B) {
-    RDX_TRY(h->dup.ensure(B, h->rows, run.list_cap, h->dim));
-    hipLaunchKernelGGL(k_dup_init, dim3(run.row_blocks), dim3(256), 0, run.st, h->dup.parent.as<int32_t>(), run.allow, h->rows, run.out_total);
-    HIP_TRY(hipGetLastError());
-    const std::vector<float> thr((size_t)B, run.threshold);
-    HIP_TRY(hipMemcpyAsync(h->dup.thr.p, thr.data(), (size_t)B * 4, hipMemcpyHostToDevice, run.st));
-    HIP_TRY(hipStreamSynchronize(run.st));
-    return RDX_OK;
-}
-
-// one batch of m allowed rows: gathered as queries, searched, linked from their lists; *heavy = its rows left to the dense pass
-static int dup_batch_lists(rdx_index* h, DupRun& run, const int64_t* ids, int64_t m, int* heavy) {
-    DupScratch& d = h->dup;
-    const hipStream_t st = run.st;
-    HIP_TRY(hipMemcpyAsync(d.ids.p, ids, (size_t)m * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, h->mv(), d.ids.as<int64_t>(), m, h->dim, d.q.as<float>());
-    HIP_TRY(hipGetLastError());
-    const RangeIO io = {d.q.as<float>(), d.thr.as<float>(), run.allow, d.score.as<float>(), d.row.as<int64_t>(), d.count.as<int32_t>(),
-                        d.total.as<int64_t>()};
-    int32_t paths[2] = {0, 0};
-    RDX_TRY(range_chunk(h, io, m, run.list_cap, st, paths));
-    HIP_TRY(hipMemsetAsync(d.ctr.p, 0, sizeof(DupCounters), st));
-    DupListParams lp = {};
-    lp.parent = d.parent.as<int32_t>();
-    lp.rows = h->rows;
-    lp.qrow = d.ids.as<int64_t>();
-    lp.nq = (int)m;
-    lp.list_cap = run.list_cap;
-    lp.row = io.row;
-    lp.count = io.count;
-    lp.total = io.total;
-    lp.out_total = run.out_total;
-    lp.heavy = d.heavy.as<int32_t>();
-    lp.ctr = d.ctr.as<DupCounters>();
-    hipLaunchKernelGGL(k_dup_link_lists, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, lp);
-    HIP_TRY(hipGetLastError());
-    DupCounters c = {};
-    HIP_TRY(hipMemcpyAsync(&c, d.ctr.p, sizeof(c), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (c.n_heavy < 0 || c.n_heavy > m) return fail(RDX_ERR_STATE, "internal: more heavy rows than rows in the batch");
-    run.n_heavy += c.n_heavy;
-    ++run.n_batches;
-    if (run.n_heavy > run.max_dense)
-        return fail(RDX_ERR_INVALID, "rdx_index_near_dup: " + std::to_string(run.n_heavy) + " rows so far have more than list_cap = " +
-                                         std::to_string(run.list_cap) + " rows within the distance (max_dense = " +
-                                         std::to_string(run.max_dense) + "): the distance is too loose for duplicate detection");
-    *heavy = c.n_heavy;
-    return RDX_OK;
-}
-
-// the dense pass of a batch's `heavy` heavy rows (the chunk's qhat — K1 of the gathered rows — is still what range_chunk left)
-static int dup_dense_pass(rdx_index* h, const DupRun& run, int heavy) {
-    const unsigned link_blocks = (unsigned)std::min<int64_t>(run.row_blocks, (int64_t)h->n_cu * 4);
-    return for_exact_groups(h, h->dup.heavy.as<int32_t>(), heavy, run.allow, nullptr, run.st, [&](const int32_t* q_list, int nq, bool) {
-        const DupDenseParams dp = {h->dup.parent.as<int32_t>(), h->rows, h->dense.as<float>(), q_list, h->dup.ids.as<int64_t>(), nq, run.threshold};
-        hipLaunchKernelGGL(k_dup_link_dense, dim3(link_blocks), dim3(256), 0, run.st, dp);
-    });
-}
-
-// after the last batch: every row's label, the smallest row of its cluster
-static int dup_labels(rdx_index* h, const DupRun& run, int64_t* out_label) {
-    hipLaunchKernelGGL(k_dup_labels, dim3(run.row_blocks), dim3(256), 0, run.st, h->dup.parent.as<int32_t>(), h->rows, out_label);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(run.st));
-    return RDX_OK;
-}
-
-extern "C" int rdx_index_near_dup(rdx_index* h, float threshold, const rdx_mask* mask, int list_cap, int64_t max_dense, int64_t* out_label,
-                                  int64_t* out_total, int64_t* out_stats, void* stream) {
-    if (!h) return fail(RDX_ERR_INVALID, "rdx_index_near_dup: null index");
-    if (list_cap < 1 || list_cap > RDX_RANGE_MAX_RESULTS)
-        return fail(RDX_ERR_INVALID, "rdx_index_near_dup: list_cap must be in [1, " + std::to_string(RDX_RANGE_MAX_RESULTS) + "]");
-    if (threshold != threshold) return fail(RDX_ERR_INVALID, "rdx_index_near_dup: the threshold is NaN");
-    if (max_dense < 0) return fail(RDX_ERR_INVALID, "rdx_index_near_dup: max_dense must be >= 0");
-    if (out_stats) out_stats[0] = out_stats[1] = out_stats[2] = out_stats[3] = 0;
-    std::lock_guard<std::mutex> lk(h->mu);
-    RDX_TRY(check_mask(h, mask, "rdx_index_near_dup", RDX_ERR_INVALID));
-    RDX_TRY(check_own_rows(h, "rdx_index_near_dup", "not available"));
-    if (h->rows >= ((int64_t)1 << 31)) return fail(RDX_ERR_INVALID, "rdx_index_near_dup: the parent array holds int32 rows: fewer than 2^31 rows");
-    RDX_TRY(finish_pending(h, nullptr));
-    if (h->rows == 0) return RDX_OK;
-    if (!out_label || !out_total) return fail(RDX_ERR_INVALID, "rdx_index_near_dup: null pointer");
-    if (((uintptr_t)out_label | (uintptr_t)out_total) & 7) return fail(RDX_ERR_INVALID, "rdx_index_near_dup: misaligned pointer");
-    RDX_TRY(set_device(h));
-    DupRun run = {threshold, mask ? mask->words.as<uint32_t>() : nullptr, list_cap, max_dense, out_total, (hipStream_t)stream, (unsigned)((h->rows + 255) / 256)};
-    std::vector<int64_t> ids;
-    RDX_TRY(dup_allowed_rows(h->rows, run, &ids));
-    const int64_t n = (int64_t)ids.size();
-    const int64_t B = std::min<int64_t>(h->dup_batch > 0 ? h->dup_batch : RANGE_CHUNK, std::max<int64_t>(n, 1));
-    RDX_TRY(dup_begin(h, run, B));
-    for (int64_t b0 = 0; b0 < n; b0 += B) {
-        int heavy = 0;
-        RDX_TRY(dup_batch_lists(h, run, ids.data() + b0, std::min(B, n - b0), &heavy));
-        if (heavy > 0) RDX_TRY(dup_dense_pass(h, run, heavy));
-    }
-    RDX_TRY(dup_labels(h, run, out_label));
-    if (out_stats) {
-        out_stats[0] = n;
-        out_stats[1] = n - run.n_heavy;
-        out_stats[2] = run.n_heavy;
-        out_stats[3] = run.n_batches;
-    }
-    return RDX_OK;
-}
-
-// ---- k-means of the stored rows -------------------------------------------------------------------------------------
-// C = K1(init) in out_centroid; an assignment = K1 of the centroids into qhat (the call a search makes on its queries), k_km_assign,
-// k_km_publish; an update = the order of rows by label (k_km_hist, k_km_scan, k_km_place), the tables (k_km_seg_table),
-// k_km_segment_sums, k_km_finish. The host reads one pinned word per assignment: the changed labels and K1's flag.
-static_assert(RDX_KMEANS_MAX_CLUSTERS <= KM_MAX_HIST && RDX_KMEANS_MAX_CLUSTERS <= 4096, "k_km_seg_table holds the clusters in one tile of 4 096");
-
-struct KmRun {
-    int n_clusters;
-    const uint32_t* allow;
-    int64_t* label; float* score; float* centroid; int64_t* count;
-    hipStream_t st;
-    KmOrderParams order;
-};
-
-// the word of the work enqueued so far: *changed = labels the last assignment changed, *bad = K1 met a NaN or Inf
-static int km_read_word(rdx_index* h, const KmRun& run, unsigned int* changed, bool* bad) {
-    KmScratch& km = h->km;
-    const unsigned long long seq = ++km.seq;
-    hipLaunchKernelGGL(k_km_publish, dim3(1), dim3(1), 0, run.st, km.ctr.as<KmCounters>(), km.mail.dev, seq);
-    HIP_TRY(hipGetLastError());
-    unsigned long long w = 0;
-    const int rc = wait_word([&] { return ((w = __atomic_load_n(km.mail.host, __ATOMIC_ACQUIRE)) >> 33) == seq; }, run.st);
-    if (rc == 1) return fail(RDX_ERR_HIP, "internal: rdx_index_kmeans' assignment completed without publishing its word");
-    if (rc != 0) return rc;
-    *changed = (unsigned int)(w & 0xffffffffull);
-    *bad = ((w >> 32) & 1ull) != 0;
-    return RDX_OK;
-}
-
-static int km_assign(rdx_index* h, const KmRun& run) {
-    int* const d_bad = reinterpret_cast<int*>(h->km.ctr.as<char>() + offsetof(KmCounters, bad));
-    RDX_TRY(normalize_queries<true>(h, run.centroid, run.n_clusters, 0, nullptr, d_bad, 0, run.st));
-    KmAssignParams ap = {};
-    ap.master = h->mv();
-    ap.rows = h->rows;
-    ap.dim = h->dim;
-    ap.qhat = h->qhat.as<float>();
-    ap.n_clusters = run.n_clusters;
-    ap.allow = run.allow;
-    ap.label = run.label;
-    ap.score = run.score;
-    ap.ctr = h->km.ctr.as<KmCounters>();
-    int rc = RDX_OK;
-    dispatch_u(h->dim, [&](auto u) {
-        constexpr int U = decltype(u)::value;
-        constexpr int R = U == 0 ? 1 : (U <= 2 ? 4 : 2);   // rows per wave: each LDS read of a centroid serves R rows
-        const size_t per_centroid = (size_t)(U > 0 ? 64 * U : h->dim / 4) * 32;
-        const int k4 = (run.n_clusters + 3) / 4 * 4;
-        ap.chunk = std::max(4, std::min(k4, (int)(KM_ASSIGN_LDS / per_centroid) / 4 * 4));
-        const size_t lds = (size_t)ap.chunk * per_centroid;
-        rc = dynamic_lds(h->device, (const void*)k_km_assign<U, R>, lds);
-        if (rc != RDX_OK) return;
-        const int64_t per_block = (int64_t)KM_ASSIGN_WAVES * R;
-        hipLaunchKernelGGL((k_km_assign<U, R>), dim3((unsigned)((h->rows + per_block - 1) / per_block)), dim3(64 * KM_ASSIGN_WAVES), lds, run.st, ap);
-    });
-    RDX_TRY(rc);
-    HIP_TRY(hipGetLastError());
-    return RDX_OK;
-}
-
-// the order of rows by label and its tables; counts: the members per cluster into out_count as well
-static int km_order(rdx_index* h, const KmRun& run, bool place, int64_t* counts) {
-    KmScratch& km = h->km;
-    const KmOrderParams& op = run.order;
-    const size_t lds = (size_t)run.n_clusters * 4;
-    hipLaunchKernelGGL(k_km_hist, dim3((unsigned)op.n_blocks), dim3(KM_TILE), lds, run.st, op);
-    hipLaunchKernelGGL(k_km_scan, dim3(1), dim3(1024), 0, run.st, op.hist, (int64_t)run.n_clusters * op.n_blocks);
-    if (place) hipLaunchKernelGGL(k_km_place, dim3((unsigned)op.n_blocks), dim3(KM_TILE), lds, run.st, op);
-    hipLaunchKernelGGL(k_km_seg_table, dim3(1), dim3(1024), 0, run.st, op.hist, op.n_blocks, run.n_clusters, km.cluster_off.as<int32_t>(),
-                       km.seg_off.as<int32_t>(), counts);
-    HIP_TRY(hipGetLastError());
-    return RDX_OK;
-}
-
-static int km_update(rdx_index* h, const KmRun& run) {
-    KmScratch& km = h->km;
-    RDX_TRY(km_order(h, run, true, nullptr));
-    const KmSumParams sp = {h->mv(), h->dim, run.n_clusters, km.seg_off.as<int32_t>(), km.cluster_off.as<int32_t>(), km.order.as<int32_t>(),
-                            km.segsum.as<double>(), run.centroid};
-    hipLaunchKernelGGL(k_km_segment_sums, dim3((unsigned)km_max_segments(h->rows, run.n_clusters)), dim3(h->dim / 4 <= 64 ? 64 : 256), 0, run.st, sp);
-    hipLaunchKernelGGL(k_km_finish, dim3(run.n_clusters), dim3(64), 0, run.st, sp);
-    HIP_TRY(hipGetLastError());
-    return RDX_OK;
-}
-
-extern "C" int rdx_index_kmeans(rdx_index* h, const float* init, int n_clusters, int max_iter, const rdx_mask* mask, int64_t* out_label,
-                                float* out_score, float* out_centroid, int64_t* out_count, int32_t* out_info, void* stream) {
-    if (!h) return fail(RDX_ERR_INVALID, "rdx_index_kmeans: null index");
-    if (n_clusters < 1 || n_clusters > RDX_KMEANS_MAX_CLUSTERS)
-        return fail(RDX_ERR_INVALID, "rdx_index_kmeans: n_clusters must be in [1, " + std::to_string(RDX_KMEANS_MAX_CLUSTERS) + "]");
-    if (max_iter < 0 || max_iter > RDX_KMEANS_MAX_ITER)
-        return fail(RDX_ERR_INVALID, "rdx_index_kmeans: max_iter must be in [0, " + std::to_string(RDX_KMEANS_MAX_ITER) + "]");
-    std::lock_guard<std::mutex> lk(h->mu);
-    RDX_TRY(check_mask(h, mask, "rdx_index_kmeans", RDX_ERR_INVALID));
-    RDX_TRY(check_own_rows(h, "rdx_index_kmeans", "not available"));
-    if (h->rows >= ((int64_t)1 << 31)) return fail(RDX_ERR_INVALID, "rdx_index_kmeans: the order holds int32 rows: fewer than 2^31 rows");
-    if (h->rows == 0) return fail(RDX_ERR_INVALID, "rdx_index_kmeans: the index is empty");
-    if (!init || !out_label || !out_score || !out_centroid || !out_count || !out_info) return fail(RDX_ERR_INVALID, "rdx_index_kmeans: null pointer");
-    if ((((uintptr_t)init | (uintptr_t)out_centroid) & 15) || (((uintptr_t)out_label | (uintptr_t)out_count) & 7) || ((uintptr_t)out_score & 3))
-        return fail(RDX_ERR_INVALID, "rdx_index_kmeans: misaligned pointer");
-    RDX_TRY(finish_pending(h, nullptr));
-    RDX_TRY(set_device(h));
-    KmScratch& km = h->km;
-    KmRun run = {n_clusters, mask ? mask->words.as<uint32_t>() : nullptr, out_label, out_score, out_centroid, out_count, (hipStream_t)stream, {}};
-    const int64_t span = std::max<int64_t>(km_block_span(h->rows, n_clusters), (int64_t)h->km_tiles * KM_TILE), n_blocks = (h->rows + span - 1) / span;
-    RDX_TRY(km.ensure(h->rows, n_clusters, h->dim, n_blocks));
-    RDX_TRY(h->qhat.ensure((size_t)n_clusters * h->dim * 4));
-    run.order = KmOrderParams{out_label, h->rows, n_clusters, span, n_blocks, km.hist.as<int32_t>(), km.order.as<int32_t>()};
-    const hipStream_t st = run.st;
-    HIP_TRY(hipMemsetAsync(km.ctr.p, 0, sizeof(KmCounters), st));
-    // C = K1(init): the kernel and the instantiation a search's queries go through, written to the caller's centroids
-    int* const d_bad = reinterpret_cast<int*>(km.ctr.as<char>() + offsetof(KmCounters, bad));
-    hipLaunchKernelGGL(k_normalize<true>, dim3((unsigned)((n_clusters + 3) / 4)), dim3(256), 0, st, init, (const uint16_t*)nullptr, (int64_t)n_clusters,
-                       h->dim, (const int64_t*)nullptr, (int64_t)0, MasterView{out_centroid, nullptr, nullptr}, (_Float16*)nullptr, h->ksteps,
-                       h->scale(), d_bad, (int64_t)0, 0);
-    HIP_TRY(hipGetLastError());
-    unsigned int changed = 0;
-    bool bad = false;
-    RDX_TRY(km_read_word(h, run, &changed, &bad));
-    if (bad) return fail(RDX_ERR_INVALID, "rdx_index_kmeans: init contains NaN or Inf");
-    RDX_TRY(km_assign(h, run));
-    RDX_TRY(km_read_word(h, run, &changed, &bad));   // (the first assignment's count compares with what the caller's buffer held: not used)
-    int n_iter = 0, converged = 0;
-    while (n_iter < max_iter) {
-        RDX_TRY(km_update(h, run));
-        ++n_iter;
-        RDX_TRY(km_assign(h, run));
-        RDX_TRY(km_read_word(h, run, &changed, &bad));
-        if (bad) return fail(RDX_ERR_STATE, "internal: rdx_index_kmeans produced a centroid with NaN or Inf");
-        if (changed == 0) {
-            converged = 1;
-            break;
-        }
-    }
-    RDX_TRY(km_order(h, run, false, out_count));
-    HIP_TRY(hipStreamSynchronize(st));
-    out_info[0] = n_iter;
-    out_info[1] = converged;
-    return RDX_OK;
-}
-
 #ifdef RDX_REFINE_STAMPS
 extern "C" int rdx_debug_refine_stamps(unsigned long long* out16) {
     return hipMemcpyFromSymbol(out16, HIP_SYMBOL(rdx::g_refine_stamps), 16 * sizeof(unsigned long long)) == hipSuccess ? 0 : 2;
@@ -2100,231 +1557,5 @@ extern "C" int rdx_search_last_stats(rdx_index* h, rdx_search_stats* out) {
     if (!h || !out) return fail(RDX_ERR_INVALID, "rdx_search_last_stats: null pointer");
     std::lock_guard<std::mutex> lk(h->mu);
     *out = h->stats;
-    return RDX_OK;
-}
-
-extern "C" int rdx_merge_topk(int device, const float* part_score, const int64_t* part_row, const int32_t* part_count, int n_parts,
-                              int64_t nq, int k, float* out_score, int64_t* out_row, int32_t* out_count, int space, void* stream) {
-    if (n_parts < 1 || n_parts > 64 || nq < 0 || k < 0 || k > SELECT_MAX_K) return fail(RDX_ERR_INVALID, "rdx_merge_topk: bad shape");
-    RDX_TRY(check_space(space));
-    if (nq == 0) return RDX_OK;
-    if (!part_count || !out_count || (k > 0 && (!part_score || !part_row || !out_score || !out_row)))
-        return fail(RDX_ERR_INVALID, "rdx_merge_topk: null pointer");
-    HIP_TRY(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
-    const size_t np = (size_t)n_parts * nq;
-    const int kk = std::max(k, 1);
-    DevBuf ps, pr, pc, os, orow, oc;
-    const float* d_ps = part_score;
-    const int64_t* d_pr = part_row;
-    const int32_t* d_pc = part_count;
-    float* d_os = out_score;
-    int64_t* d_or = out_row;
-    int32_t* d_oc = out_count;
-    if (space == RDX_HOST) {
-        RDX_TRY(ps.ensure(np * kk * 4));
-        RDX_TRY(pr.ensure(np * kk * 8));
-        RDX_TRY(pc.ensure(np * 4));
-        RDX_TRY(os.ensure((size_t)nq * kk * 4));
-        RDX_TRY(orow.ensure((size_t)nq * kk * 8));
-        RDX_TRY(oc.ensure((size_t)nq * 4));
-        if (k > 0) {
-            HIP_TRY(hipMemcpyAsync(ps.p, part_score, np * k * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(pr.p, part_row, np * k * 8, hipMemcpyHostToDevice, st));
-        }
-        HIP_TRY(hipMemcpyAsync(pc.p, part_count, np * 4, hipMemcpyHostToDevice, st));
-        d_ps = ps.as<float>();
-        d_pr = pr.as<int64_t>();
-        d_pc = pc.as<int32_t>();
-        d_os = os.as<float>();
-        d_or = orow.as<int64_t>();
-        d_oc = oc.as<int32_t>();
-    }
-    DevBuf t_s[2], t_r[2], t_c[2];   // the fold's intermediate lists (large k only)
-    if ((int64_t)n_parts * k <= MERGE_MAX) {
-        hipLaunchKernelGGL(k_merge, dim3((int)nq), dim3(256), 0, st, d_ps, d_pr, d_pc, (int64_t)nq * k, (int64_t)nq * k, (int64_t)nq, n_parts, nq, k,
-                           d_os, d_or, d_oc);
-        HIP_TRY(hipGetLastError());
-    } else {
-        // more candidates per query than k_merge ranks in LDS (several shards at k > 2048 / n_parts): fold the parts pairwise
-        const size_t nk = (size_t)nq * k;
-        for (int j = 0; j < 2 && n_parts > 2; ++j) {
-            RDX_TRY(t_s[j].ensure(nk * 4));
-            RDX_TRY(t_r[j].ensure(nk * 8));
-            RDX_TRY(t_c[j].ensure((size_t)nq * 4));
-        }
-        const float* a_s = d_ps;
-        const int64_t* a_r = d_pr;
-        const int32_t* a_c = d_pc;
-        for (int p = 1; p < n_parts; ++p) {
-            const bool last = p == n_parts - 1;
-            float* o_s = last ? d_os : t_s[p & 1].as<float>();
-            int64_t* o_r = last ? d_or : t_r[p & 1].as<int64_t>();
-            int32_t* o_c = last ? d_oc : t_c[p & 1].as<int32_t>();
-            hipLaunchKernelGGL(k_merge_pair, dim3((int)nq), dim3(256), 0, st, a_s, a_r, a_c, d_ps + (size_t)p * nk, d_pr + (size_t)p * nk,
-                               d_pc + (size_t)p * nq, k, o_s, o_r, o_c);
-            HIP_TRY(hipGetLastError());
-            a_s = o_s;
-            a_r = o_r;
-            a_c = o_c;
-        }
-        if (space == RDX_DEVICE && n_parts > 2) HIP_TRY(hipStreamSynchronize(st));   // the intermediates are freed on return
-    }
-    if (space == RDX_HOST) {
-        RDX_TRY(copy_results_to_host(HostOut{out_score, out_row, out_count, false}, d_os, d_or, d_oc, nq, k, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (DevBuf* b : {&ps, &pr, &pc, &os, &orow, &oc}) b->release();
-    }
-    return RDX_OK;
-}
-
-extern "C" int rdx_signal_create(int device, rdx_signal** out) {
-    if (!out) return fail(RDX_ERR_INVALID, "rdx_signal_create: null out pointer");
-    HIP_TRY(hipSetDevice(device));
-    auto s = std::make_unique<rdx_signal>();
-    s->device = device;
-    RDX_TRY(s->word.map(64));
-    *out = s.release();
-    return RDX_OK;
-}
-
-extern "C" int rdx_signal_destroy(rdx_signal* s) {
-    if (!s) return RDX_OK;
-    (void)hipSetDevice(s->device);
-    const std::unique_ptr<rdx_signal> owner(s);
-    return RDX_OK;
-}
-
-extern "C" int rdx_signal_wait(rdx_signal* s, void* stream, int32_t* value) {
-    if (!s || !value) return fail(RDX_ERR_INVALID, "rdx_signal_wait: null pointer");
-    if (s->seq == 0) return fail(RDX_ERR_STATE, "rdx_signal_wait: no merge has been given this signal");
-    HIP_TRY(hipSetDevice(s->device));
-    unsigned long long w = 0;
-    const int rc = wait_word([&] { return ((w = __atomic_load_n(s->word.host, __ATOMIC_ACQUIRE)) >> 1) == s->seq; }, (hipStream_t)stream);
-    if (rc == 1) return fail(RDX_ERR_HIP, "internal: the merge completed without publishing its signal");
-    if (rc != 0) return rc;
-    *value = (int32_t)(w & 1ull);
-    return RDX_OK;
-}
-
-// the packed layout one rank contributes to the all-gather: rows i64[nq][k] | scores f32[nq][k] | counts i32[nq] | flags i32[4]
-extern "C" int rdx_merge_topk_packed(int device, const void* packed, int64_t part_stride, int n_parts, int64_t nq, int k,
-                                     float* out_score, int64_t* out_row, int32_t* out_count, rdx_signal* sig, void* stream) {
-    if (n_parts < 1 || n_parts > 64 || nq < 0 || k < 1) return fail(RDX_ERR_INVALID, "rdx_merge_topk_packed: bad shape");
-    if ((int64_t)n_parts * k > MERGE_MAX) return fail(RDX_ERR_INVALID, "rdx_merge_topk_packed: n_parts * k exceeds " + std::to_string(MERGE_MAX));
-    const int64_t flags_off = nq * k * 12 + nq * 4;
-    if (part_stride % 16 != 0 || part_stride < flags_off + 4 * RDX_PACKED_FLAGS)
-        return fail(RDX_ERR_INVALID, "rdx_merge_topk_packed: part_stride must be a multiple of 16 covering one packed partial (rows | scores | counts | flags)");
-    if (sig && sig->device != device) return fail(RDX_ERR_INVALID, "rdx_merge_topk_packed: the signal belongs to another device");
-    if (nq == 0) {
-        if (sig) return fail(RDX_ERR_INVALID, "rdx_merge_topk_packed: a signal needs nq >= 1");
-        return RDX_OK;
-    }
-    if (!packed || !out_score || !out_row || !out_count) return fail(RDX_ERR_INVALID, "rdx_merge_topk_packed: null pointer");
-    HIP_TRY(hipSetDevice(device));
-    const char* b = reinterpret_cast<const char*>(packed);
-    const unsigned long long seq = sig ? ++sig->seq : 0;
-    hipLaunchKernelGGL(k_merge, dim3((int)nq), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float*>(b + nq * k * 8),
-                       reinterpret_cast<const int64_t*>(b), reinterpret_cast<const int32_t*>(b + nq * k * 12), part_stride / 4,
-                       part_stride / 8, part_stride / 4, n_parts, nq, k, out_score, out_row, out_count,
-                       reinterpret_cast<const int32_t*>(b + flags_off), part_stride / 4, sig ? sig->word.dev : (unsigned long long*)nullptr, seq);
-    HIP_TRY(hipGetLastError());
-    return RDX_OK;
-}
-
-// ---- value counts ---------------------------------------------------------------------------------------------------
-static_assert(FACET_MAX_LIMIT == RDX_FACET_MAX_LIMIT, "facet_kernel.hpp and include/rdx.h disagree");
-constexpr int64_t FACET_TABLE_KB = 262144;   // the default budget of a pass's tables: 256 MiB (DESIGN.md §28 says why)
-
-// what the two calls check alike before anything is enqueued (the caller holds the lock); on success the device is selected and the counters are zeroed
-static int facet_begin(rdx_index* h, const char* who, const rdx_mask* mask, hipStream_t st) {
-    RDX_TRY(check_mask(h, mask, who, RDX_ERR_INVALID));
-    RDX_TRY(check_own_rows(h, who, "not available"));
-    if (h->rows >= ((int64_t)1 << 31)) return fail(RDX_ERR_INVALID, std::string(who) + ": the table holds int32 codes per row: fewer than 2^31 rows");
-    RDX_TRY(finish_pending(h, nullptr));
-    RDX_TRY(set_device(h));
-    RDX_TRY(h->fct_ctr.ensure(sizeof(FacetCounters)));
-    HIP_TRY(hipMemsetAsync(h->fct_ctr.p, 0, sizeof(FacetCounters), st));
-    return RDX_OK;
-}
-
-// the counters back on the host, the stream drained; a code outside the table's range fails the call
-static int facet_end(rdx_index* h, const char* who, int64_t n_groups, hipStream_t st, FacetCounters* c) {
-    HIP_TRY(hipMemcpyAsync(c, h->fct_ctr.p, sizeof(*c), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (c->bad)
-        return fail(RDX_ERR_INVALID, std::string(who) + ": row_group holds a code outside -1 .. n_groups - 1 = " + std::to_string(n_groups - 1) +
-                                         " (nothing was counted through it; the outputs are undefined)");
-    return RDX_OK;
-}
-
-extern "C" int rdx_index_facet_count(rdx_index* h, const rdx_mask* mask, const int32_t* row_group, int64_t n_groups, int64_t* out_counts,
-                                     int64_t* out_missing, int64_t* out_total, void* stream) {
-    if (!h) return fail(RDX_ERR_INVALID, "rdx_index_facet_count: null index");
-    if (n_groups < 0 || n_groups >= ((int64_t)1 << 31)) return fail(RDX_ERR_INVALID, "rdx_index_facet_count: n_groups must be in [0, 2^31)");
-    if (!out_missing || !out_total || (n_groups > 0 && (!row_group || !out_counts))) return fail(RDX_ERR_INVALID, "rdx_index_facet_count: null pointer");
-    if (((uintptr_t)row_group & 3) || ((uintptr_t)out_counts & 7)) return fail(RDX_ERR_INVALID, "rdx_index_facet_count: misaligned pointer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t st = (hipStream_t)stream;
-    RDX_TRY(facet_begin(h, "rdx_index_facet_count", mask, st));
-    if (n_groups > 0) HIP_TRY(hipMemsetAsync(out_counts, 0, (size_t)n_groups * 8, st));
-    if (h->rows > 0) {
-        // a workgroup walks a span of rows, so that its table in LDS is zeroed and flushed once per span: eight workgroups per CU
-        const int64_t tiles = (h->rows + 255) / 256;
-        const int64_t span = (tiles + std::min<int64_t>(tiles, (int64_t)h->n_cu * 8) - 1) / std::min<int64_t>(tiles, (int64_t)h->n_cu * 8) * 256;
-        const FacetCountParams fp = {mask ? mask->words.as<uint32_t>() : nullptr, n_groups > 0 ? row_group : nullptr, h->rows, n_groups,
-                                     reinterpret_cast<unsigned long long*>(out_counts), h->fct_ctr.as<FacetCounters>(), span};
-        hipLaunchKernelGGL(k_facet_count, dim3((unsigned)((h->rows + span - 1) / span)), dim3(256), 0, st, fp);
-        HIP_TRY(hipGetLastError());
-    }
-    FacetCounters c = {};
-    RDX_TRY(facet_end(h, "rdx_index_facet_count", n_groups, st, &c));
-    *out_missing = (int64_t)c.missing;
-    *out_total = (int64_t)c.total;
-    return RDX_OK;
-}
-
-extern "C" int rdx_index_range_facets(rdx_index* h, const float* queries, int64_t nq, const float* thresholds, const rdx_mask* mask,
-                                      const int32_t* row_group, int64_t n_groups, int limit, int32_t* out_code, int64_t* out_n,
-                                      int32_t* out_found, int64_t* out_missing, int64_t* out_total, int32_t* out_paths, void* stream) {
-    if (!h) return fail(RDX_ERR_INVALID, "rdx_index_range_facets: null index");
-    if (limit < 1 || limit > RDX_FACET_MAX_LIMIT)
-        return fail(RDX_ERR_INVALID, "rdx_index_range_facets: limit must be in [1, " + std::to_string(RDX_FACET_MAX_LIMIT) + "]");
-    if (nq < 0 || nq > 65535) return fail(RDX_ERR_INVALID, "rdx_index_range_facets: nq must be in [0, 65535]");
-    if (n_groups < 0 || n_groups >= ((int64_t)1 << 31)) return fail(RDX_ERR_INVALID, "rdx_index_range_facets: n_groups must be in [0, 2^31)");
-    int32_t paths[2] = {0, 0};
-    if (out_paths) out_paths[0] = out_paths[1] = 0;
-    if (nq == 0) return RDX_OK;
-    if (!queries || !thresholds || !row_group || !out_code || !out_n || !out_found || !out_missing || !out_total)
-        return fail(RDX_ERR_INVALID, "rdx_index_range_facets: null pointer");
-    if (((uintptr_t)queries & 15) || (((uintptr_t)out_n | (uintptr_t)out_missing | (uintptr_t)out_total) & 7) ||
-        (((uintptr_t)thresholds | (uintptr_t)row_group | (uintptr_t)out_code | (uintptr_t)out_found) & 3))
-        return fail(RDX_ERR_INVALID, "rdx_index_range_facets: misaligned pointer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t st = (hipStream_t)stream;
-    RDX_TRY(facet_begin(h, "rdx_index_range_facets", mask, st));
-    // the queries of a pass share one table of n_groups cells each: as many queries as the budget holds, one at the least
-    const int64_t budget = (h->facet_table_kb > 0 ? h->facet_table_kb : FACET_TABLE_KB) * 1024;
-    const int64_t sub = std::max<int64_t>(1, std::min<int64_t>(RANGE_CHUNK, budget / std::max<int64_t>(n_groups * 4, 1)));
-    const size_t row_bytes = (size_t)n_groups * 4;
-    RDX_TRY(h->fct_tab.ensure(std::max<size_t>((size_t)std::min<int64_t>(sub, nq) * row_bytes, 16)));
-    int* const d_bad = reinterpret_cast<int*>(h->fct_ctr.as<char>() + offsetof(FacetCounters, bad));
-    for (int64_t q0 = 0; q0 < nq; q0 += sub) {
-        const int64_t m = std::min(sub, nq - q0);
-        if (row_bytes) HIP_TRY(hipMemsetAsync(h->fct_tab.p, 0, (size_t)m * row_bytes, st));
-        const RangeIO io = {queries + (size_t)q0 * h->dim, thresholds + q0, mask ? mask->words.as<uint32_t>() : nullptr, nullptr, nullptr, nullptr,
-                            out_total + q0};
-        const FacetIO fc = {row_group, n_groups, h->fct_tab.as<uint32_t>(), out_missing + q0, d_bad};
-        RDX_TRY(range_chunk(h, io, m, 1, st, paths, &fc));
-        const FacetTopParams tp = {h->fct_tab.as<uint32_t>(), n_groups, limit, out_code + (size_t)q0 * limit, out_n + (size_t)q0 * limit, out_found + q0};
-        hipLaunchKernelGGL(k_facet_top, dim3((unsigned)m), dim3(1024), 0, st, tp);
-        HIP_TRY(hipGetLastError());
-    }
-    FacetCounters c = {};
-    RDX_TRY(facet_end(h, "rdx_index_range_facets", n_groups, st, &c));
-    if (out_paths) {
-        out_paths[0] = paths[0];
-        out_paths[1] = paths[1];
-    }
     return RDX_OK;
 }

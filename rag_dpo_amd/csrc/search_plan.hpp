@@ -94,7 +94,7 @@ struct SearchPlan {
 
 constexpr int K_FAST_MAX = 256;   // larger k goes through the exact full scan
 
-// Host callers (rdx_index.hip HostOut): small results travel with the end-of-search kernel into pinned staging and are copied to the
+// Host callers (rdx_host.hpp HostOut): small results travel with the end-of-search kernel into pinned staging and are copied to the
 // caller's buffers by the CPU once the mailbox says the search is complete; large ones use D2H copies.
 constexpr size_t PIN_MAX = 256 * 1024;   // results up to this size ride with k_finish (one block writing over PCIe)
 

@@ -31,7 +31,7 @@ from . import where as W
 MAX_GROUPS, MAX_GROUP_SIZE = 64, 16       # include/rdx.h RDX_GROUP_MAX_GROUPS / RDX_GROUP_MAX_SIZE
 FILL_SPAN = 4096                          # include/rdx.h RDX_GROUP_FILL_SPAN: rows one fill job walks
 K_FAST_MAX = 256                          # csrc/search_plan.hpp: the largest k of the scan path
-K_SECOND = 4096                           # csrc/k_rows.hpp SELECT_MAX_K: the second fetch (the exact scan path)
+K_SECOND = 4096                           # csrc/rows_core.hpp SELECT_MAX_K: the second fetch (the exact scan path)
 STAT_KEYS = ("queries", "proven_first_fetch", "second_fetch", "brute", "fill_jobs")
 
 

@@ -22,9 +22,9 @@ import numpy as np
 
 EQ_CAP = 1024           # k_rows.hpp: ties at the k-th ranked from a side list up to here, by an in-order walk beyond
 RN = 32                 # k_rows.hpp: K5b keeps score rows of up to RN * 1024 in registers
-SELECT_MAX_K = 4096     # k_rows.hpp: largest k of a search
+SELECT_MAX_K = 4096     # rows_core.hpp: largest k of a search
 REFINE_PMAX = 1024      # refine_kernel.hpp: the ranking arrays of k_refine
-MERGE_MAX = 4096        # refine_kernel.hpp: most candidates per query one k_merge launch ranks
+MERGE_MAX = 4096        # merge_kernel.hpp: most candidates per query one k_merge launch ranks
 REG_ROWS = RN * 1024    # 32 768: the register form of K5b up to here, the global form beyond
 
 TINY = 1e-25

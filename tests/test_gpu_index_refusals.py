@@ -1,4 +1,4 @@
-"""GPU: the refusals that the index's derived searches share (rdx_index.hip check_mask / check_own_rows), word for word and code for
+"""GPU: the refusals that the index's derived searches share (rdx_index.hip check_mask / check_own_rows, called from rdx_derived.hip too), word for word and code for
 code, and that a refused call leaves the index usable.
 
 An index of dim 64 with 256 rows, a resident mask made for it, then one more row: the mask is stale. rdx_search_masked and

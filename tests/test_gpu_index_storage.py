@@ -1,4 +1,4 @@
-"""The index's row storage through a reallocation and a compaction (rdx_index.hip RowStore): both master forms and the row-id map
+"""The index's row storage through a reallocation and a compaction (rdx_index.hpp RowStore): both master forms and the row-id map
 are carried from the old arrays to the new ones. After every step the count, the returned ids and the score bits are the CPU
 oracle's, on the path the library picks, on the exact full scan and on the MFMA path.
 

@@ -66,9 +66,9 @@ def test_landscapes_hold_what_they_are_built_for(oracle):
 
 
 @pytest.mark.parametrize("name,file,value", [("EQ_CAP", "k_rows.hpp", SL.EQ_CAP), ("RN", "k_rows.hpp", SL.RN),
-                                             ("SELECT_MAX_K", "k_rows.hpp", SL.SELECT_MAX_K),
+                                             ("SELECT_MAX_K", "rows_core.hpp", SL.SELECT_MAX_K),
                                              ("REFINE_PMAX", "rdx_limits.hpp", SL.REFINE_PMAX),
-                                             ("MERGE_MAX", "refine_kernel.hpp", SL.MERGE_MAX)])
+                                             ("MERGE_MAX", "merge_kernel.hpp", SL.MERGE_MAX)])
 def test_selector_constants_are_where_the_landscapes_aim(name, file, value):
     src = open(os.path.join(CSRC, file)).read()
     found = re.findall(r"constexpr\s+int\s+" + name + r"\s*=\s*(\d+)\s*;", src)
