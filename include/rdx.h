@@ -572,6 +572,21 @@ int rdx_lex_destroy(rdx_lex* h);
 int rdx_lex_search(rdx_lex* h, const int64_t* term_offsets, const int32_t* term_ids, const uint16_t* term_w, int64_t nq, int k,
                    const uint32_t* filter_sets, int32_t n_filters, const int32_t* query_filter, double* out_score, int64_t* out_row,
                    int32_t* out_count, int space, void* stream);
+/* rdx_lex_score_pairs: the score above of NAMED (question, row) pairs. Questions as in rdx_lex_search, but term_ids int32
+ * and term_w uint16 are DEVICE memory (what EmbeddingProvider.embed_lexical_device returns, without a trip to the host) and
+ * term_offsets int64 [nq + 1] is a shape array (the rule above: PINNED HOST memory, read by the library to check the call and by the
+ * kernel): term_offsets[0] >= 0, non-decreasing, at most 4096 terms per question. Pair p scores question pair_q[p] (int32) against row
+ * pair_row[p] (int64) into out_score[p] (f64), all device memory. Per pair the row is looked up in every question term's postings (a
+ * binary search, behind the term's tile directory when its postings span more than one tile of 4 096 rows) and the exact products are
+ * added in ascending term id from +0.0: bit for bit the score rdx_lex_search returns for that (question, row), and +0.0 for a row it
+ * would not list. NaN, the neighbours unaffected and nothing read through it: a pair whose question is outside [0, nq) or whose row is
+ * outside [0, n_rows); every pair of a question whose ids are not strictly ascending or outside [0, n_terms), or which holds a weight
+ * whose bits are outside [0x0001, 0x7BFF]. RDX_ERR_INVALID before anything is launched: nq outside [1, 65535], n_pairs outside
+ * [1, 2^20], an invalid term_offsets, a null or misaligned pointer. Enqueued on `stream`, nothing synchronised, nothing allocated, no
+ * float atomics; a pair's bits do not depend on its position, on n_pairs or on its neighbours. One wave per pair
+ * (csrc/lex_pairs_kernel.hpp; the lookup: csrc/lex_find.hpp). */
+int rdx_lex_score_pairs(rdx_lex* h, const int64_t* term_offsets, const int32_t* term_ids, const uint16_t* term_w, int64_t nq,
+                        const int32_t* pair_q, const int64_t* pair_row, int64_t n_pairs, double* out_score, void* stream);
 
 /* Building a BM25 index from text ----------------------------------------------------------- */
 /* The tokenizer of the reference's indexes (tokenize_french, bm25_index.py:38-49) and the vocabulary and postings that
@@ -992,6 +1007,29 @@ int rdx_index_facet_count(rdx_index* h, const rdx_mask* mask, const int32_t* row
 int rdx_index_range_facets(rdx_index* h, const float* queries, int64_t nq, const float* thresholds, const rdx_mask* mask,
                            const int32_t* row_group, int64_t n_groups, int limit, int32_t* out_code, int64_t* out_n, int32_t* out_found,
                            int64_t* out_missing, int64_t* out_total, int32_t* out_paths, void* stream);
+
+/* The combined BGE-M3 score ------------------------------------------------------------------------ */
+/* score(question, chunk) = (w_dense dense + w_sparse sparse + w_colbert colbert) / (w_dense + w_sparse + w_colbert) over BGE-M3's three
+ * outputs: rag_dpo_amd/m3.py states the definition once, in numpy, and drives the calls; DESIGN.md §31. The colbert component is
+ * rdx_maxsim_f16's, the sparse one rdx_lex_score_pairs' (above), the dense one and the sum are the two calls here. Both take device
+ * pointers only, are enqueued on `stream`, allocate and synchronise nothing, use no float atomics, and give an element the same bits
+ * whatever its position, the call's length or its neighbours. Invalid scalars return RDX_ERR_INVALID before anything is launched.
+ *
+ * rdx_index_score_pairs. queries fp32 [nq][dim] are raw (16-byte aligned); each pair's query is normalised on the device exactly as
+ * rdx_search normalises it. out_score[p] (fp32) is the exact score of rdx_search for query pair_q[p] (int32) and row pair_row[p]
+ * (int64): the same summation order, the same bits, on the fp32 master and on a compact_master index alike. NaN, and nothing read
+ * through the pair: a query outside [0, nq), a row outside [0, rows of the index), a query holding NaN or Inf. Limits: 1 <= nq <=
+ * 65535, 1 <= n_pairs <= 2^20. RDX_ERR_STATE on an index with mapped row ids (a shard). One wave per pair (csrc/m3_kernel.hpp).
+ *
+ * rdx_m3_combine. value = ((w_dense * (double)dense + w_sparse * sparse) + w_colbert * (double)colbert) / W, W = (w_dense + w_sparse) +
+ * w_colbert: three products, two sums and one division in fp64, each rounded once, never fused. A component whose weight is 0 is
+ * skipped: it is not read and no 0 * x is added; its pointer must be NULL, and a component with a non-zero weight must not be
+ * (RDX_ERR_INVALID otherwise). out_final fp32 [n] = (float)value; out_value f64 [n] (may be NULL) = value. A NaN component gives NaN.
+ * Weights: finite, >= 0, W > 0 (a NaN is refused). 1 <= n <= 2^20. dense and colbert fp32 [n], sparse f64 [n]. */
+int rdx_index_score_pairs(rdx_index* h, const float* queries, int64_t nq, const int32_t* pair_q, const int64_t* pair_row, int64_t n_pairs,
+                          float* out_score, void* stream);
+int rdx_m3_combine(int device, const float* dense, const double* sparse, const float* colbert, int64_t n, double w_dense, double w_sparse,
+                   double w_colbert, float* out_final, double* out_value, void* stream);
 
 #ifdef __cplusplus
 }

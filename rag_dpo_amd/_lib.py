@@ -139,6 +139,7 @@ SYMBOLS = {
     "rdx_lex_create": (_i, [_i, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.POINTER(_vp)]),
     "rdx_lex_destroy": (_i, [_vp]),
     "rdx_lex_search": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _i, _vp]),
+    "rdx_lex_score_pairs": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
     "rdx_bm25_build_create": (_i, [_i, _i64, ctypes.c_uint64, ctypes.POINTER(_vp)]),
     "rdx_bm25_build_destroy": (_i, [_vp]),
     "rdx_bm25_build_tokenize": (_i, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
@@ -176,6 +177,8 @@ SYMBOLS = {
     "rdx_index_kmeans": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int32), _vp]),
     "rdx_index_facet_count": (_i, [_vp, _vp, _vp, _i64, _vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _vp]),
     "rdx_index_range_facets": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rdx_index_score_pairs": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "rdx_m3_combine": (_i, [_i, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp]),
 }
 
 

@@ -151,7 +151,8 @@ SPILL_CHECKS = (
     SpillCheck(("k_km_",), 0, "ignored", True, True, "the k-means kernels (kmeans_kernel.hpp) spill — refused:"),
     SpillCheck(("k_facet",), 0, "ignored", True, True, "the value counts' kernels (facet_kernel.hpp) spill — refused:"),
     SpillCheck(("k_maxsim",), 0, "ignored", True, True, "the late-interaction scoring kernel (maxsim_kernel.hpp) spills — refused:"),
-    SpillCheck(("k_lex",), 0, "ignored", True, True, "the lexical-weight kernels (lex_kernel.hpp k_lex_reduce, bm25_kernel.hpp k_lex_score) spill — refused:"),
+    SpillCheck(("k_lex",), 0, "ignored", True, True, "the lexical-weight kernels (lex_kernel.hpp k_lex_reduce, bm25_kernel.hpp k_lex_score, lex_pairs_kernel.hpp k_lex_score_pairs) spill — refused:"),
+    SpillCheck(("k_score_pairs", "k_m3_combine"), 0, "ignored", True, True, "the combined score's kernels (m3_kernel.hpp) spill — refused:"),
     # k_refine<false> / k_refine<true> (the plans that spill to the HBM list) run 1024 threads at the 128-register limit (refine_kernel.hpp): a spill would be paid on every search
     SpillCheck(("k_refine",), 2, "required", True, False, "the refine kernels (refine_kernel.hpp) spill or were not found — refused:"),
     # kernels that are given an occupancy target (amdgpu_waves_per_eu: the latency-bound attention kernel E12) pay for a miss

@@ -1165,6 +1165,60 @@ class Collection:
             out["mmr_scores"] = [[float(x) for x in v[b, : c[b]]] for b in range(nq)]
             return out
 
+    # ---- the score of named pairs (rag_dpo_amd/m3.py states the definition) -----------------------------------------
+    def _pairs_check(self, method: str, pair_query, ids):
+        self._derived_check(method, "returns the cosine score", None)
+        ids = list(ids)
+        pq = np.ascontiguousarray(pair_query, dtype=np.int32).reshape(-1)
+        if pq.shape[0] != len(ids):
+            raise ValueError(f"{method}: {pq.shape[0]} pair_query entries for {len(ids)} ids")
+        return pq, ids
+
+    def score_pairs_device(self, query_embeddings, pair_query, ids):
+        """score_pairs for callers that hold their query embeddings on the GPU ([nq][dim] fp32 torch CUDA tensor) -> fp32 [n] on the
+        collection's device: one launch (rdx_index_score_pairs), nothing synchronised; NaN for an id the collection does not hold
+        and for a pair_query entry outside [0, nq). The same floats as score_pairs."""
+        pq, ids = self._pairs_check("score_pairs_device", pair_query, ids)
+        with self._lock:
+            self._refuse_empty("score_pairs_device")
+            self._refuse_host_engine()
+            import torch
+            from . import engine as E
+            q = query_embeddings.contiguous()
+            if q.dim() != 2:
+                raise ValueError("score_pairs_device: query_embeddings must be [nq][dim]")
+            self._check_dim(int(q.shape[1]))
+            get = self._row_of.get
+            rows = np.fromiter((get(s, -1) for s in ids), dtype=np.int64, count=len(ids))
+            if not len(ids):
+                return torch.empty((0,), dtype=torch.float32, device=q.device)
+            with torch.cuda.device(q.device):
+                return E.score_pairs(self._engine, q, torch.from_numpy(pq).to(q.device), torch.from_numpy(rows).to(q.device))
+
+    def score_pairs(self, query_embeddings, pair_query, ids) -> np.ndarray:
+        """The cosine score (1 - query()'s distance, the same bits) of each named pair: pair p is query pair_query[p] against the row
+        of Chroma id ids[p] -> fp32 numpy [n]. NaN for an id the collection does not hold (never added, or deleted) and for a
+        pair_query entry outside [0, nq). Cosine collections on one device; engines without the device call go through the numpy
+        model over engine.get (rag_dpo_amd/m3.py dense_pairs_model)."""
+        pq, ids = self._pairs_check("score_pairs", pair_query, ids)
+        q = self._host_queries(query_embeddings)
+        with self._lock:
+            out = np.full((len(ids),), np.nan, dtype=np.float32)
+            if self._no_rows() or not len(ids):
+                return out
+            self._check_dim(q.shape[1])
+            get = self._row_of.get
+            rows = np.fromiter((get(s, -1) for s in ids), dtype=np.int64, count=len(ids))
+            if hasattr(self._engine, "search_device"):
+                import torch
+                from . import engine as E
+                dev = torch.device("cuda", self._engine.device)
+                with torch.cuda.device(dev):
+                    return E.score_pairs(self._engine, torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)).to(dev),
+                                         torch.from_numpy(pq).to(dev), torch.from_numpy(rows).to(dev)).cpu().numpy()
+            from . import m3 as M3
+            return M3.dense_pairs_model(self._engine.get, len(self._engine), q, pq, rows)
+
     # ---- threshold search (rag_dpo_amd/range_search.py states the definition; DESIGN.md §23) ------------------------------------
     def _range_check(self, max_results, where_document):
         _check_int("max_results", max_results, 1, RS.MAX_RESULTS)

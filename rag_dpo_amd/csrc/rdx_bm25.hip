@@ -1,6 +1,7 @@
 // rdx_bm25.hip — sparse retrieval over a CSR-by-term index: BM25 (rdx_bm25_*) and BGE-M3 lexical weights (rdx_lex_create / _destroy /
-// _search) of include/rdx.h. Both indexes are one host core (SparseIndex: create, upload, search) and one merge; they differ in what a
-// posting holds and in the scoring kernel (bm25_kernel.hpp k_bm25_score / k_lex_score).
+// _search / _score_pairs) of include/rdx.h. Both indexes are one host core (SparseIndex: create, upload, search) and one merge; they differ in what a
+// posting holds and in the scoring kernel (bm25_kernel.hpp k_bm25_score / k_lex_score). The score of named (question, row) pairs of a
+// lexical index (lex_pairs_kernel.hpp k_lex_score_pairs) is here because the handle is.
 #include "rdx_host.hpp"
 
 #include <cmath>
@@ -8,6 +9,7 @@
 #include <vector>
 
 #include "bm25_kernel.hpp"
+#include "lex_pairs_kernel.hpp"
 
 using namespace rdx;
 
@@ -326,4 +328,50 @@ extern "C" int rdx_lex_search(rdx_lex* h, const int64_t* term_offsets, const int
                                                 h->post_val.as<uint16_t>(), h->group.as<int32_t>(), d_sets, allow_words, d_qf, d_off, d_ids,
                                                 d_w, h->n_rows, k, h->n_tiles, p_score, p_row, p_cnt);
                          });
+}
+
+// ---- the lexical score of named pairs --------------------------------------------------------------------------------
+static_assert(LEX_PAIRS_MAX_TERMS == BM25_MAX_TERMS, "a question the pair call admits is one the search admits");
+
+extern "C" int rdx_lex_score_pairs(rdx_lex* h, const int64_t* term_offsets, const int32_t* term_ids, const uint16_t* term_w, int64_t nq,
+                                   const int32_t* pair_q, const int64_t* pair_row, int64_t n_pairs, double* out_score, void* stream) {
+    static const char* fn = "rdx_lex_score_pairs";
+    if (!h) return fail(RDX_ERR_INVALID, "rdx_lex_score_pairs: null index");
+    if (nq < 1 || nq > LEX_PAIRS_MAX_QUESTIONS) return fail(RDX_ERR_INVALID, "rdx_lex_score_pairs: nq must be in [1, 65535]");
+    if (n_pairs < 1 || n_pairs > LEX_PAIRS_MAX_PAIRS) return fail(RDX_ERR_INVALID, "rdx_lex_score_pairs: n_pairs must be in [1, 2^20]");
+    if (!pair_q || !pair_row || !out_score) return fail(RDX_ERR_INVALID, "rdx_lex_score_pairs: null pointer");
+    if ((((uintptr_t)pair_row | (uintptr_t)out_score) & 7) || (((uintptr_t)pair_q | (uintptr_t)term_ids) & 3) || ((uintptr_t)term_w & 1))
+        return fail(RDX_ERR_INVALID, "rdx_lex_score_pairs: misaligned pointer");
+    HIP_TRY(hipSetDevice(h->device));
+    const void* d_off;
+    RDX_TRY(shape_array(fn, "term_offsets", term_offsets, 8, &d_off));
+    if (term_offsets[0] < 0) return fail(RDX_ERR_INVALID, "rdx_lex_score_pairs: term_offsets must start at 0 or above");
+    for (int64_t q = 0; q < nq; ++q) {
+        const int64_t T = term_offsets[q + 1] - term_offsets[q];
+        if (T < 0 || T > LEX_PAIRS_MAX_TERMS)
+            return fail(RDX_ERR_INVALID, "rdx_lex_score_pairs: question " + std::to_string(q) + " has " + std::to_string(T) + " terms (0.." +
+                                             std::to_string(LEX_PAIRS_MAX_TERMS) + "; term_offsets must not decrease)");
+    }
+    if (term_offsets[nq] > 0 && (!term_ids || !term_w)) return fail(RDX_ERR_INVALID, "rdx_lex_score_pairs: null term_ids or term_w");
+    LexPairsParams lp = {};
+    lp.post_off = h->post_off.as<int64_t>();
+    lp.post_row = h->post_row.as<int32_t>();
+    lp.post_w = h->post_val.as<uint16_t>();
+    lp.dir_off = h->dir_off.as<int64_t>();
+    lp.dir_tile = h->dir_tile.as<int32_t>();
+    lp.dir_pos = h->dir_pos.as<int64_t>();
+    lp.n_rows = h->n_rows;
+    lp.n_terms = h->n_terms;
+    lp.q_off = (const int64_t*)d_off;
+    lp.q_terms = term_ids;
+    lp.q_w = term_w;
+    lp.nq = nq;
+    lp.pair_q = pair_q;
+    lp.pair_row = pair_row;
+    lp.n_pairs = n_pairs;
+    lp.out = out_score;
+    hipLaunchKernelGGL(k_lex_score_pairs, dim3((unsigned)((n_pairs + LEX_PAIRS_WAVES - 1) / LEX_PAIRS_WAVES)), dim3(64 * LEX_PAIRS_WAVES), 0,
+                       (hipStream_t)stream, lp);
+    HIP_TRY(hipGetLastError());
+    return RDX_OK;
 }

@@ -363,10 +363,11 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
         return w, b
 
     @torch.no_grad()
-    def _token_states(self, texts: List[str], with_ids: bool = False):
+    def _token_states(self, texts: List[str], with_ids: bool = False, with_cls: bool = False):
         """-> (fp32 [sum(len_i - 1)][hidden] last hidden states of every token but <s>, </s> included, in input order; int64 [B + 1] offsets);
-        with_ids: and, third, the token ids of those rows (int32 numpy, on the host)"""
-        parts, counts, tok = [], [], []
+        with_ids: and, third, the token ids of those rows (int32 numpy, on the host; None without); with_cls: and, fourth, the <s> rows
+        of the same forward, fp32 [B][hidden]"""
+        parts, counts, tok, cls = [], [], [], []
         for a in range(0, len(texts), self.batch_size):
             enc = self._tokenizer(list(texts[a: a + self.batch_size]))
             ids, att = enc["input_ids"], enc["attention_mask"]
@@ -376,6 +377,7 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
                 h = self._packed.tokens(ids, lens, self._h2d)                     # [T][hidden], text b at first[b]
                 keep = np.setdiff1d(np.arange(int(lens.sum()), dtype=np.int64), first)
                 flat_ids = ids.numpy()[np.arange(ids.shape[1])[None, :] < lens[:, None]] if with_ids else None   # the packed order: text by text
+                first_rows = first
             else:
                 w = int(lens.max())
                 feed = {"input_ids": self._h2d("ids", ids[:, :w]), "attention_mask": self._h2d("att", att[:, :w])}
@@ -384,13 +386,18 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
                 cols = np.arange(w, dtype=np.int64)[None, :]
                 keep = np.flatnonzero(((cols >= 1) & (cols < lens[:, None])).reshape(-1)).astype(np.int64)
                 flat_ids = ids.numpy()[:, :w].reshape(-1) if with_ids else None
+                first_rows = np.arange(len(lens), dtype=np.int64) * w
             parts.append(h.index_select(0, self._h2d("tok_keep", torch.from_numpy(keep))))
             counts.append(lens - 1)
             if with_ids:
                 tok.append(flat_ids[keep].astype(np.int32))
+            if with_cls:
+                cls.append(h.index_select(0, self._h2d("tok_first", torch.from_numpy(np.ascontiguousarray(first_rows)))))
         off = np.zeros(len(texts) + 1, dtype=np.int64)
         np.cumsum(np.concatenate(counts), out=off[1:])
         h = parts[0] if len(parts) == 1 else torch.cat(parts)
+        if with_cls:
+            return h, off, (np.concatenate(tok) if with_ids else None), (cls[0] if len(cls) == 1 else torch.cat(cls))
         return (h, off, np.concatenate(tok)) if with_ids else (h, off)
 
     def embed_tokens_device(self, texts: List[str]):
@@ -408,9 +415,14 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
             if not texts:
                 return torch.empty((0, w.shape[0]), dtype=torch.float16, device=self.device), np.zeros(1, dtype=np.int64)
             h, off = self._token_states([t[:TRUNCATE_CHARS] if len(t) > TRUNCATE_CHARS else t for t in texts])
-            v = torch.nn.functional.linear(h, w, b)
-            v = v / v.norm(dim=1, keepdim=True).clamp_min(1e-12)
-            return v.to(torch.float16), off
+            return self._colbert_rows(h), off
+
+    def _colbert_rows(self, h: torch.Tensor) -> torch.Tensor:
+        """the ColBERT head over token states [T][hidden] -> fp16 [T][dim]: embed_tokens_device's and embed_m3_device's"""
+        w, b = self._colbert
+        v = torch.nn.functional.linear(h, w, b)
+        v = v / v.norm(dim=1, keepdim=True).clamp_min(1e-12)
+        return v.to(torch.float16)
 
     def embed_tokens(self, texts: List[str]) -> List[np.ndarray]:
         """embed_tokens_device() as a list of fp16 numpy matrices [T_i - 1][dim]"""
@@ -450,7 +462,6 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
         reduced to the text's terms by the rule of rag_dpo_amd/lexical.py — on a GPU provider by librdx's k_lex_reduce (rdx_lex_reduce),
         on a CPU provider by the numpy model. -> (term_ids int32 [nnz], term_w fp16 [nnz]) on the model's device and off int64 numpy
         [B + 1]: text i's terms are [off[i], off[i + 1]), ascending ids, possibly none; input order; embed()'s truncation."""
-        from . import lexical
         with self._lock:
             if self._model is None:
                 self.load()
@@ -461,26 +472,70 @@ class EmbeddingProvider(metaclass=_ProviderOptions):
                 return (torch.empty((0,), dtype=torch.int32, device=self.device), torch.empty((0,), dtype=torch.float16, device=self.device),
                         np.zeros(1, dtype=np.int64))
             h, off, tok = self._token_states([t[:TRUNCATE_CHARS] if len(t) > TRUNCATE_CHARS else t for t in texts], with_ids=True)
-            w = torch.relu(torch.nn.functional.linear(h, *self._sparse)).reshape(-1).contiguous()
-            vocab, skip = int(self._model.config.vocab_size), tuple(self._lexical_special)
-            if not w.is_cuda:
-                ids, ws, out_off = lexical.terms_of_texts_model(tok, w.numpy(), off, vocab, skip)
-                return torch.from_numpy(ids).to(self.device), torch.from_numpy(ws).to(self.device), out_off
-            from . import engine
-            n, T = len(texts), int(off[-1])
-            tok_d = self._h2d("lex_tok", torch.from_numpy(tok))
-            off_p = torch.from_numpy(off).pin_memory()           # read by the library and by the kernel; alive until the copy of out_n below has drained the stream
-            out_tok, out_w, out_n = engine.lex_reduce(tok_d, w, off_p, vocab, skip)
-            counts = out_n.cpu().numpy().astype(np.int64)
-            if (counts < 0).any():
-                raise ValueError(f"text {int(np.flatnonzero(counts < 0)[0])}: a token id outside [0, {vocab})")
-            # the per-text runs packed into one CSR
-            text_of = torch.repeat_interleave(torch.arange(n, device=w.device), torch.from_numpy(np.diff(off)).to(w.device), output_size=T)
-            pos = torch.arange(T, device=w.device) - torch.from_numpy(off[:-1].copy()).to(w.device)[text_of]
-            keep = pos < out_n[text_of]
-            out_off = np.zeros(n + 1, dtype=np.int64)
-            np.cumsum(counts, out=out_off[1:])
-            return out_tok[keep], out_w[keep], out_off
+            return self._lexical_terms(h, off, tok)
+
+    @torch.no_grad()
+    def _lexical_terms(self, h: torch.Tensor, off: np.ndarray, tok: np.ndarray):
+        """the sparse head over token states [T][hidden] with their offsets and ids, and the reduction to terms -> embed_lexical_device's
+        triple: that method's and embed_m3_device's"""
+        from . import lexical
+        w = torch.relu(torch.nn.functional.linear(h, *self._sparse)).reshape(-1).contiguous()
+        vocab, skip = int(self._model.config.vocab_size), tuple(self._lexical_special)
+        if not w.is_cuda:
+            ids, ws, out_off = lexical.terms_of_texts_model(tok, w.numpy(), off, vocab, skip)
+            return torch.from_numpy(ids).to(self.device), torch.from_numpy(ws).to(self.device), out_off
+        from . import engine
+        n, T = len(off) - 1, int(off[-1])
+        tok_d = self._h2d("lex_tok", torch.from_numpy(tok))
+        off_p = torch.from_numpy(off).pin_memory()           # read by the library and by the kernel; alive until the copy of out_n below has drained the stream
+        out_tok, out_w, out_n = engine.lex_reduce(tok_d, w, off_p, vocab, skip)
+        counts = out_n.cpu().numpy().astype(np.int64)
+        if (counts < 0).any():
+            raise ValueError(f"text {int(np.flatnonzero(counts < 0)[0])}: a token id outside [0, {vocab})")
+        # the per-text runs packed into one CSR
+        text_of = torch.repeat_interleave(torch.arange(n, device=w.device), torch.from_numpy(np.diff(off)).to(w.device), output_size=T)
+        pos = torch.arange(T, device=w.device) - torch.from_numpy(off[:-1].copy()).to(w.device)[text_of]
+        keep = pos < out_n[text_of]
+        out_off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(counts, out=out_off[1:])
+        return out_tok[keep], out_w[keep], out_off
+
+    @torch.no_grad()
+    def embed_m3_device(self, texts: List[str], dense: bool = True, sparse: bool = True, colbert: bool = True) -> dict:
+        """BGE-M3's three outputs from ONE forward per batch of texts -> a dict with, for the outputs asked for,
+        "dense": fp32 [B][hidden] on the model's device, the <s> rows of that forward as embed_device returns them (not normalised:
+        the index normalises what it is given); "lex": embed_lexical_device's triple; "tokens": embed_tokens_device's pair. "lex" and
+        "tokens" are those methods' bits (the same token forward, the same heads); "dense" agrees with embed_device up to the
+        difference between the token forward and the <s>-only one. A head that is missing and asked for raises RuntimeError.
+        embed()'s truncation."""
+        with self._lock:
+            if self._model is None:
+                self.load()
+            if colbert and self._colbert is None:
+                raise RuntimeError(f"EmbeddingProvider: no ColBERT head — pass colbert_head=, or put {self.COLBERT_FILE} (a state dict with "
+                                   "'weight' and 'bias') into the local model directory")
+            if sparse and self._sparse is None:
+                raise RuntimeError(f"EmbeddingProvider: no lexical-weight head — pass sparse_head=, or put {self.SPARSE_FILE} (a state dict with "
+                                   "'weight' [1][hidden] and 'bias' [1]) into the local model directory")
+            out = {}
+            if not texts:
+                if dense:
+                    out["dense"] = torch.empty((0, self._dims), dtype=torch.float32, device=self.device)
+                if sparse:
+                    out["lex"] = (torch.empty((0,), dtype=torch.int32, device=self.device), torch.empty((0,), dtype=torch.float16, device=self.device),
+                                  np.zeros(1, dtype=np.int64))
+                if colbert:
+                    out["tokens"] = (torch.empty((0, self._colbert[0].shape[0]), dtype=torch.float16, device=self.device), np.zeros(1, dtype=np.int64))
+                return out
+            h, off, tok, cls = self._token_states([t[:TRUNCATE_CHARS] if len(t) > TRUNCATE_CHARS else t for t in texts], with_ids=sparse,
+                                                  with_cls=True)
+            if dense:
+                out["dense"] = cls.contiguous()
+            if sparse:
+                out["lex"] = self._lexical_terms(h, off, tok)
+            if colbert:
+                out["tokens"] = (self._colbert_rows(h), off)
+            return out
 
     def embed_lexical(self, texts: List[str]) -> List[dict]:
         """embed_lexical_device() as a list of {token_id: weight} (the fp16 weights as Python floats)"""

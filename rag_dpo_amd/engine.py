@@ -643,6 +643,82 @@ def mmr_select(index: "HipIndex", cand_score, cand_row, cand_count, n_results: i
     return out
 
 
+# ---- the combined BGE-M3 score (include/rdx.h rdx_index_score_pairs / rdx_lex_score_pairs / rdx_m3_combine; rag_dpo_amd/m3.py) -------
+def score_pairs(index: "HipIndex", queries, pair_q, pair_row, out=None):
+    """the exact search score of each named pair: queries fp32 [nq][dim] (raw), pair_q int32 [n], pair_row int64 [n] (the index's own
+    rows) as contiguous torch tensors on the index's device -> fp32 [n] there; NaN for a pair out of range. One launch enqueued on the
+    current torch stream, nothing synchronised."""
+    import torch
+    what = f"score_pairs: queries must be a contiguous fp32 [nq][{index.dim}] tensor on cuda:{index.device}"
+    _want_tensors(what, index.device, (queries, torch.float32))
+    if queries.dim() != 2 or queries.shape[1] != index.dim:
+        raise ValueError(what)
+    _want_tensors("score_pairs: pair_q int32 and pair_row int64 must be contiguous tensors on the index's device", index.device,
+                  (pair_q, torch.int32), (pair_row, torch.int64))
+    if pair_q.dim() != 1 or pair_q.shape != pair_row.shape:
+        raise ValueError("score_pairs: pair_q and pair_row must be [n] of one length")
+    n = int(pair_q.numel())
+    out = torch.empty((n,), dtype=torch.float32, device=queries.device) if out is None else out
+    _want_tensors("score_pairs: out must be a contiguous fp32 tensor on the index's device", index.device, (out, torch.float32))
+    if out.numel() < n:
+        raise ValueError("score_pairs: out is shorter than the pair lists")
+    p = _ptr
+    L.check(index._lib.rdx_index_score_pairs(index._h, p(queries), int(queries.shape[0]), p(pair_q), p(pair_row), n, p(out),
+                                             ctypes.c_void_p(HipIndex._raw_stream(queries.device))))
+    return out
+
+
+def lex_score_pairs(lex, term_off, term_ids, term_w, pair_q, pair_row, out=None):
+    """the lexical score of each named pair over a HipLexical: term_ids int32 / term_w fp16 (or its uint16 bits' int16 view) and pair_q
+    int32 / pair_row int64 [n] as contiguous torch tensors on the index's device, term_off int64 [nq + 1] a PINNED host tensor (left
+    unchanged until the stream has passed the call) -> f64 [n] on the device; NaN for a pair out of range or of a bad question. One
+    launch enqueued on the current torch stream, nothing synchronised."""
+    import torch
+    if term_off.is_cuda or term_off.dtype != torch.int64 or not term_off.is_contiguous() or term_off.dim() != 1 or term_off.numel() < 2:
+        raise ValueError("lex_score_pairs: term_off must be a contiguous int64 host tensor [nq + 1]")
+    _want_tensors("lex_score_pairs: pair_q int32 and pair_row int64 must be contiguous tensors on the index's device", lex.device,
+                  (pair_q, torch.int32), (pair_row, torch.int64))
+    if term_w.dtype not in (torch.float16, torch.int16, torch.uint16):
+        raise ValueError("lex_score_pairs: term_w must hold fp16 values or their 16-bit patterns")
+    _want_tensors("lex_score_pairs: term_ids int32 and term_w must be contiguous tensors on the index's device", lex.device,
+                  (term_ids, torch.int32), (term_w, term_w.dtype))
+    if pair_q.dim() != 1 or pair_q.shape != pair_row.shape or term_ids.dim() != 1 or term_ids.shape != term_w.shape:
+        raise ValueError("lex_score_pairs: pair_q / pair_row and term_ids / term_w must be lists of one length each")
+    if int(term_off[-1]) > term_ids.numel():
+        raise ValueError("lex_score_pairs: term_off reaches past term_ids")
+    n, dev = int(pair_q.numel()), pair_q.device
+    out = torch.empty((n,), dtype=torch.float64, device=dev) if out is None else out
+    _want_tensors("lex_score_pairs: out must be a contiguous f64 tensor on the index's device", lex.device, (out, torch.float64))
+    if out.numel() < n:
+        raise ValueError("lex_score_pairs: out is shorter than the pair lists")
+    p = _ptr
+    L.check(lex._lib.rdx_lex_score_pairs(lex._h, p(term_off), p(term_ids), p(term_w), int(term_off.numel()) - 1, p(pair_q), p(pair_row), n,
+                                         p(out), ctypes.c_void_p(HipIndex._raw_stream(dev))))
+    return out
+
+
+def m3_combine(dense, sparse, colbert, weights, want_value: bool = False):
+    """value = ((w_d dense + w_s sparse) + w_c colbert) / W per element (rag_dpo_amd/m3.py combine_model): dense fp32 / sparse f64 /
+    colbert fp32 [n] contiguous torch tensors on one CUDA device, each None exactly when its weight is 0 -> final fp32 [n] there, or
+    (final, value f64 [n]) with want_value. One launch enqueued on the current torch stream, nothing synchronised."""
+    import torch
+    lib = L.load(require_gpu=True)
+    given = [(t, dt) for t, dt in ((dense, torch.float32), (sparse, torch.float64), (colbert, torch.float32)) if t is not None]
+    if not given:
+        raise ValueError("m3_combine: no component given")
+    _want_tensors("m3_combine takes contiguous torch tensors (dense fp32, sparse f64, colbert fp32) on one CUDA device", None, *given)
+    n, dev = int(given[0][0].numel()), given[0][0].device
+    if any(t.dim() != 1 or t.numel() != n for t, _ in given):
+        raise ValueError("m3_combine: the components must be [n] of one length")
+    final = torch.empty((n,), dtype=torch.float32, device=dev)
+    value = torch.empty((n,), dtype=torch.float64, device=dev) if want_value else None
+    w = [float(x) for x in weights]
+    p = _ptr
+    L.check(lib.rdx_m3_combine(dev.index or 0, p(dense), p(sparse), p(colbert), n, w[0], w[1], w[2], p(final), p(value),
+                               ctypes.c_void_p(HipIndex._raw_stream(dev))))
+    return (final, value) if want_value else final
+
+
 # ---- threshold search (include/rdx.h rdx_index_range; rag_dpo_amd/range_search.py states the definition) ------------------------
 def range_search(index: "HipIndex", queries, thresholds, max_results: int, mask: Optional[ResidentMask] = None):
     """queries fp32 [nq][dim] and thresholds fp32 [nq] (score thresholds t, range_search.score_threshold) as contiguous torch tensors on

@@ -288,7 +288,10 @@ class _MaxSimModel:
 
     def _vectors(self, texts, cap: int):
         """one embed_tokens_device call -> (vecs in the store's arena type, off int64 numpy), every text cut to its first `cap` vectors"""
-        v, off = self.provider.embed_tokens_device(list(texts))
+        return self._cut(*self.provider.embed_tokens_device(list(texts)), cap)
+
+    def _cut(self, v, off, cap: int):
+        """embed_tokens_device's pair -> (vecs in the store's arena type, off int64 numpy), every text cut to its first `cap` vectors"""
         v, off = (torch.from_numpy(v) if isinstance(v, np.ndarray) else v), np.asarray(off, dtype=np.int64)
         if v.shape[1] != self.store.dim:
             raise ValueError(f"the provider's token vectors are {v.shape[1]} wide, the store's {self.store.dim}")
@@ -301,12 +304,14 @@ class _MaxSimModel:
             v, off = v.index_select(0, torch.from_numpy(src).to(v.device)), new_off
         return self.store._to_arena_type(v), off
 
-    def _score(self, pairs) -> "torch.Tensor | np.ndarray":
+    def _score(self, pairs, q_tokens=None) -> "torch.Tensor | np.ndarray":
+        """q_tokens: embed_tokens_device's pair for the distinct questions in order of first appearance, for a caller that has
+        encoded them already (rag_dpo_amd/m3.py); None: encoded here"""
         st, n = self.store, len(pairs)
         self.calls = 0
         questions: dict = {}
         pair_q = np.fromiter((questions.setdefault(q, len(questions)) for q, _ in pairs), dtype=np.int32, count=n)
-        q_vecs, q_off = self._vectors(list(questions), MAX_Q_TOKENS)
+        q_vecs, q_off = self._vectors(list(questions), MAX_Q_TOKENS) if q_tokens is None else self._cut(*q_tokens, MAX_Q_TOKENS)
         slots = st.slots_of([c.chunk_id for _, c in pairs])
         held, missing = np.flatnonzero(slots >= 0), np.flatnonzero(slots < 0)
         if st.on_gpu:
@@ -365,6 +370,7 @@ class LateInteractionReranker(CrossEncoderReranker):
                          min_score=float("-inf") if min_score is None else float(min_score))
         self.provider, self.store = provider, store
         self._model = _MaxSimModel(provider, store)
+        self._on_gpu = store.on_gpu                      # which of rerank's two paths runs (M3Reranker may have no store)
         self._is_loaded = True
         self._nested = False
 
@@ -396,7 +402,7 @@ class LateInteractionReranker(CrossEncoderReranker):
             return []
         if not self._nested:
             self._model.encoded = 0
-        if not self.store.on_gpu:
+        if not self._on_gpu:
             out = super().rerank(query, chunks, top_k=top_k, topic_matcher=topic_matcher, question_topics=question_topics)
             self._finish(self.last_rerank_stats)
             return out

@@ -312,7 +312,16 @@ class LexicalChunkIndex(ChunkBM25Index):
         self.arrays = LexArrays(len(self.chunk_ids), len(post_off) - 1, np.ascontiguousarray(post_off, np.int64),
                                 np.ascontiguousarray(post_row, np.int32), _as_bits(post_w), groups, len(self._group_of))
         self.engine = self._factory(self.arrays, self.device) if self.arrays.n_rows else None
+        self._row_of_id = {c: r for r, c in enumerate(self.chunk_ids)}
         self._is_built = True
+
+    def rows_of(self, ids: Sequence[str]) -> np.ndarray:
+        """int64 [len(ids)]: each chunk id's row in this index, -1 for an id it does not hold (a chunk without terms, or one added
+        since the build)"""
+        if not self._is_built:
+            raise RuntimeError("the lexical index is not built")
+        get = self._row_of_id.get
+        return np.fromiter((get(c, -1) for c in ids), dtype=np.int64, count=len(ids))
 
     # -- files --------------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:
