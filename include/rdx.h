@@ -375,6 +375,30 @@ int rdx_maxsim_f16(int device, const void* q_vecs, const int32_t* q_off, int nq,
                    const int64_t* slot_start, const int32_t* slot_len, int64_t n_slots, const int32_t* pair_q,
                    const int64_t* pair_slot, int64_t n_pairs, int dim, float* scores, void* stream);
 
+/* The same score over per-token symmetric int8 token vectors (rag_dpo_amd/late_interaction.py quantize_model / maxsim_i8_model,
+ * DESIGN.md §32): half the bytes of a stored token, and a score that is the numpy model's bit for bit.
+ *
+ * rdx_maxsim_quantize_i8. vecs_f16 fp16 [rows][dim] -> codes int8 [rows][dim], scales fp32 [rows], per row:
+ *     a = max_k |x_k|, scale = (float)((double)a / 127.0), c_k = clamp(rint((double)x_k / (double)scale), -127, 127)
+ *   (fp64 divisions, ties to even). A row of zeros, or one holding NaN or Inf, gets codes 0 and scale +0.0. rows >= 1; dim: a multiple
+ *   of 32 in [32, RDX_MAXSIM_MAX_DIM]. vecs_f16 and codes are 16-byte aligned device memory; nothing behind codes[rows * dim - 1] or
+ *   scales[rows - 1] is written. One wave per row (csrc/maxsim_i8_kernel.hpp k_maxsim_quant).
+ *
+ * rdx_maxsim_i8. rdx_maxsim_f16's arguments with (q_codes, q_scales) and (d_codes, d_scales) in place of q_vecs and d_vecs: codes int8
+ *   [rows][dim] (16-byte aligned), scales fp32 [rows], as rdx_maxsim_quantize_i8 writes them (scales finite and >= 0, +0.0 only for a row
+ *   of zero codes, codes in [-127, 127]).
+ *     acc_ij = sum_k cq_ik cd_jk  (int32, exact: v_mfma_i32_32x32x32_i8),  v_ij = (float)acc_ij * sd_j  (one fp32 multiply),
+ *     m_i = max_j v_ij,  score = (float)((sum_i (double)sq_i * (double)m_i) / n_q)  (fp64, token order from +0.0).
+ *   The limits, the q_off shape-array rule (PINNED HOST memory), the refusals, the NaN of an out-of-range pair, and what is read and
+ *   written are rdx_maxsim_f16's. One workgroup of four waves per pair (csrc/maxsim_i8_kernel.hpp k_maxsim_i8).
+ * Both are enqueued on `stream`, allocate nothing, synchronise nothing and use no atomics; an element's bits do not depend on its
+ * position, on the call's length or on its neighbours. */
+int rdx_maxsim_quantize_i8(int device, const void* vecs_f16, int64_t rows, int dim, int8_t* codes, float* scales, void* stream);
+int rdx_maxsim_i8(int device, const int8_t* q_codes, const float* q_scales, const int32_t* q_off, int nq,
+                  const int8_t* d_codes, const float* d_scales, int64_t d_rows,
+                  const int64_t* slot_start, const int32_t* slot_len, int64_t n_slots,
+                  const int32_t* pair_q, const int64_t* pair_slot, int64_t n_pairs, int dim, float* scores, void* stream);
+
 /* `collection.query(query_embeddings=, n_results=k, where=)` (reference
  * src/rag/retriever.py:215-220,380-385; create_chromadb_index.py:405-408,435-439).
  *   queries     [nq][dim] raw fp32 (normalised on the device like corpus rows)

@@ -117,6 +117,8 @@ SYMBOLS = {
                                    _vp, _vp, _vp, _vp]),
     "rdx_rerank_select_batch": (_i, [_i, _vp, _vp, _i, _vp, _i, ctypes.c_double, _i, _vp, _vp, _vp, _vp, _vp]),
     "rdx_maxsim_f16": (_i, [_i, _vp, _vp, _i, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i, _vp, _vp]),
+    "rdx_maxsim_quantize_i8": (_i, [_i, _vp, _i64, _i, _vp, _vp, _vp]),
+    "rdx_maxsim_i8": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i, _vp, _vp]),
     "rdx_search": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "rdx_mask_create": (_i, [_vp, _vp, _i, ctypes.POINTER(_vp)]),
     "rdx_mask_destroy": (_i, [_vp]),

@@ -509,7 +509,7 @@ def space_distances(kind: int, queries, vecs, scale_exp: int, allow_bits, first_
                                     ctypes.c_void_p(out.data_ptr() + 4 * col0), out.shape[1], ctypes.c_void_p(HipIndex._raw_stream(dev))))
 
 
-# ---- late-interaction scoring (include/rdx.h rdx_maxsim_f16; rag_dpo_amd/late_interaction.py drives it) ---------------------------
+# ---- late-interaction scoring (include/rdx.h rdx_maxsim_f16, rdx_maxsim_quantize_i8, rdx_maxsim_i8; rag_dpo_amd/late_interaction.py drives it)
 def maxsim(q_vecs, q_off, d_vecs, slot_start, slot_len, pair_q, pair_slot, scores=None, n_pairs: Optional[int] = None):
     """score(q, d) = (1 / n_q) sum_i max_j q_i . d_j for the listed pairs -> fp32 [n_pairs] on the device (written into `scores` when
     given). q_vecs fp16 [sum n_q][dim], d_vecs fp16 [rows][dim], slot_start i64 / slot_len i32 [slots], pair_q i32 / pair_slot i64
@@ -534,6 +534,55 @@ def maxsim(q_vecs, q_off, d_vecs, slot_start, slot_len, pair_q, pair_slot, score
     L.check(lib.rdx_maxsim_f16(dev.index or 0, p(q_vecs), p(q_off), int(q_off.numel()) - 1, p(d_vecs), int(d_vecs.shape[0]), p(slot_start),
                                p(slot_len), int(slot_start.numel()), p(pair_q), p(pair_slot), n, int(q_vecs.shape[1]), p(scores),
                                ctypes.c_void_p(HipIndex._raw_stream(dev))))
+    return scores
+
+
+def maxsim_quantize(vecs, codes=None, scales=None):
+    """per-token symmetric int8 (late_interaction.quantize_model): vecs fp16 [rows][dim], rows >= 1, a contiguous torch tensor on a
+    CUDA device -> (codes int8 [rows][dim], scales fp32 [rows]) there (written into `codes` / `scales` when given). Enqueued on the
+    current torch stream, nothing synchronised."""
+    import torch
+    lib = L.load(require_gpu=True)
+    _want_tensors("maxsim_quantize takes a contiguous fp16 torch tensor [rows][dim] on a CUDA device", None, (vecs, torch.float16))
+    if vecs.dim() != 2 or vecs.shape[0] < 1:
+        raise ValueError("maxsim_quantize: vecs must be [rows][dim] with at least one row")
+    dev, rows, dim = vecs.device, int(vecs.shape[0]), int(vecs.shape[1])
+    codes = torch.empty((rows, dim), dtype=torch.int8, device=dev) if codes is None else codes
+    scales = torch.empty((rows,), dtype=torch.float32, device=dev) if scales is None else scales
+    _want_tensors("maxsim_quantize: codes / scales must be contiguous int8 / fp32 tensors on the vectors' device", dev.index,
+                  (codes, torch.int8), (scales, torch.float32))
+    if codes.numel() < rows * dim or scales.numel() < rows:
+        raise ValueError("maxsim_quantize: codes or scales are too small for the rows")
+    p = _ptr
+    L.check(lib.rdx_maxsim_quantize_i8(dev.index or 0, p(vecs), rows, dim, p(codes), p(scales), ctypes.c_void_p(HipIndex._raw_stream(dev))))
+    return codes, scales
+
+
+def maxsim_i8(q_codes, q_scales, q_off, d_codes, d_scales, slot_start, slot_len, pair_q, pair_slot, scores=None, n_pairs: Optional[int] = None):
+    """maxsim over quantised token vectors (late_interaction.maxsim_i8_model): q_codes int8 [sum n_q][dim] / q_scales fp32 [sum n_q],
+    d_codes int8 [rows][dim] / d_scales fp32 [rows], the rest as maxsim takes it -> fp32 [n_pairs] on the device. Enqueued on the
+    current torch stream, nothing synchronised."""
+    import torch
+    lib = L.load(require_gpu=True)
+    _want_tensors("maxsim_i8 takes contiguous torch tensors of the documented types on one CUDA device", None, (q_codes, torch.int8),
+                  (q_scales, torch.float32), (d_codes, torch.int8), (d_scales, torch.float32), (slot_start, torch.int64), (slot_len, torch.int32),
+                  (pair_q, torch.int32), (pair_slot, torch.int64))
+    if q_codes.dim() != 2 or d_codes.dim() != 2 or q_codes.shape[1] != d_codes.shape[1] or q_scales.shape != q_codes.shape[:1] or \
+            d_scales.shape != d_codes.shape[:1] or slot_start.shape != slot_len.shape or pair_q.shape != pair_slot.shape:
+        raise ValueError("maxsim_i8: codes must be [rows][dim] of one dim with one scale per row, the slot tables and the pair lists of one length each")
+    if q_off.is_cuda or q_off.dtype != torch.int32 or not q_off.is_contiguous() or q_off.numel() < 2:
+        raise ValueError("maxsim_i8: q_off must be a contiguous int32 host tensor [nq + 1]")
+    dev = q_codes.device
+    n = int(pair_q.numel()) if n_pairs is None else int(n_pairs)
+    if scores is None:
+        scores = torch.empty((n,), dtype=torch.float32, device=dev)
+    _want_tensors("maxsim_i8: scores must be a contiguous fp32 tensor on the vectors' device", dev.index, (scores, torch.float32))
+    if n > pair_q.numel() or n > scores.numel() or int(q_off[-1]) > q_codes.shape[0]:
+        raise ValueError("maxsim_i8: n_pairs exceeds the pair lists or the scores, or q_off reaches past q_codes")
+    p = _ptr
+    L.check(lib.rdx_maxsim_i8(dev.index or 0, p(q_codes), p(q_scales), p(q_off), int(q_off.numel()) - 1, p(d_codes), p(d_scales),
+                              int(d_codes.shape[0]), p(slot_start), p(slot_len), int(slot_start.numel()), p(pair_q), p(pair_slot), n,
+                              int(q_codes.shape[1]), p(scores), ctypes.c_void_p(HipIndex._raw_stream(dev))))
     return scores
 
 

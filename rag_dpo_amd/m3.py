@@ -8,7 +8,8 @@ pair (question q, chunk c) and weights (w_d, w_s, w_c), each finite and >= 0 wit
   dense    the search's exact fp32 score of q's dense vector against c's stored row: the bits query() returns for that row
            (`mmr.pair_scores` over engine.get's row and the query normalised as the search normalises it, `kmeans.k1`).
   sparse   `lexical.score_model`: float64, the products added in ascending term id from +0.0.
-  colbert  `late_interaction.maxsim_model`: fp32.
+  colbert  `late_interaction.maxsim_model`: fp32. With an int8 `MultiVectorStore` the component's source is
+           `late_interaction.maxsim_i8_model` over the quantised vectors instead; nothing else of the definition changes.
   value    ((w_d * float64(dense) + w_s * sparse) + w_c * float64(colbert)) / W: three products, two sums and one division in float64,
            each rounded once and never fused. A component whose weight is 0 is skipped: it is not read, and no 0 * x is added.
   final    float32(value). A NaN component gives a NaN value.
